@@ -5,8 +5,11 @@ Workload (`--config`, default 720p4 = BASELINE.json configs[1]): 4-camera rig, 1
 extract + all-pairs intra-rig match; 1080p8 = configs[2]: 8 cameras, 1920x1080 (one camera per GPU at --gpus 8).
 One *step* = one batch of F synthetic rig frames per rank through the whole hot path (pyramid -> FAST -> selection ->
 blur -> BRIEF -> k-NN(k=2) + ratio filter -> track merge), inputs resident in HBM before the timed region.
-`value` = rig frames / second over all ranks: the median of `--repeats` timed regions of exactly `--steps` steps each
-(`value_min` / `value_max` give the spread).
+`value` = rig frames / second over all ranks: the median of `--repeats` timed regions of `--steps` steps each
+(`value_min` / `value_max` give the spread); `ms_per_step` = milliseconds of one timed step.  A plain run sets up, warms
+up, times exactly `--steps` steps once and prints the JSON line; `--dump-outputs DIR` also writes what the last step
+computed (dump_outputs).  `--full` adds everything else: the roofline and per-kernel figures, the legs below, and
+regions of at least `--min-region-s` seconds, repeated 3 times.
 
 N = 1: cameras and pairs all on one GPU, S slots in flight (the host selection stage of one sub-batch overlaps the GPU
 phases of the others).
@@ -14,7 +17,7 @@ N > 1 (weak scaling, F frames per rank per step, F*N frames per step in total): 
 rank (c + f) mod N; every descriptor set travels to the rank that matches its frame (f mod N) with ONE RCCL all-to-all
 per step (uneven splits, mc-slam_amd/sharding.py) -- stream-ordered: export -> collective -> match without a host sync.
 
-Extra legs on rank 0 at N = 1 (none of them part of `value`):
+Extra legs on rank 0 at N = 1 with --full (none of them part of `value`):
   value_with_staging / value_with_upload_u8 / pcie_gbs   the same steps with the PCIe hand-off in front of every batch
   cpu_baseline                                           the CPU oracle on a bounded sample, every frame checked bit-exact
   single_frame_latency_ms                                one rig frame at a time, nothing in flight
@@ -48,6 +51,8 @@ HBM_PEAK_GBS = 8000.0       # MI355X HBM3E spec peak (MI355X_MICROARCH.md); ~6.3
 GPU_KERNELS = ("k_resize", "k_fast_cells", "k_compact", "k_describe_fused", "k_knn2")   # k_blur: only with MCORB_BLUR_PLANES / orientation
 TIMING_FIELD = {"k_resize": "pyramid_us", "k_fast_cells": "fast_us", "k_compact": "compact_us",
                 "k_describe_fused": "describe_us", "k_knn2": "knn2_us", "select_host": "select_us"}
+DUMP_FRAMES, DUMP_SEED = 16, 20261016    # --dump-outputs: rig frames sampled from the last step (fixed for fixed arguments)
+DUMP_BYTES_MAX = 64 << 20
 
 
 def algorithmic_bytes(kernel, S, S0, s_last, K, Kc, buckets):
@@ -97,6 +102,33 @@ def cpu_baseline(cfg, frames, threads):
         t_extract.append(t1 - t0)
         results.append((res, tracks))
     return np.array(times), np.array(t_extract), results
+
+
+def dump_outputs(dirname, ncams, kcap, frames, tracks_of, features_of=None, suffix=""):
+    """--dump-outputs: what a caller of the timed path receives for a seeded sample of the rig frames of the last step --
+    per camera image the keypoints (x, y, size, angle, response, octave, class_id) and descriptors (32 bytes), per rig
+    frame the intra-rig tracks (keypoint index per camera, -1 = none) -- as float32 / float64 .npy files, ragged lists
+    concatenated in (frame, camera) order with their counts beside them.  tracks_of(f) -> (tracks, merged);
+    features_of(f, c) -> (mono_index, keypoints, descriptors), None where the path hands back tracks only."""
+    per_frame = ncams * kcap * ((7 + 32) * 4 + ncams * 8) + 64
+    n = max(1, min(DUMP_FRAMES, len(frames), DUMP_BYTES_MAX // per_frame))
+    pick = sorted(int(frames[i]) for i in np.random.default_rng(DUMP_SEED).choice(len(frames), n, replace=False))
+    arrs = {"frames": np.array(pick, np.float64)}
+    tr = [tracks_of(f) for f in pick]
+    arrs["tracks"] = np.concatenate([t.reshape(-1, ncams) for t, _ in tr]).astype(np.float64)
+    arrs["track_counts"] = np.array([len(t) for t, _ in tr], np.float64)
+    arrs["tracks_merged"] = np.array([m for _, m in tr], np.float64)
+    if features_of is not None:
+        ft = [features_of(f, c) for f in pick for c in range(ncams)]
+        arrs["mono_index"] = np.array([m for m, _, _ in ft], np.float64).reshape(n, ncams)
+        arrs["keypoint_counts"] = np.array([len(k) for _, k, _ in ft], np.float64).reshape(n, ncams)
+        arrs["keypoints"] = np.concatenate([np.stack([k[name].astype(np.float32) for name in k.dtype.names], axis=1).reshape(-1, len(k.dtype.names))
+                                            for _, k, _ in ft])
+        arrs["descriptors"] = np.concatenate([d.reshape(-1, 32) for _, _, d in ft]).astype(np.float32)
+    assert sum(a.nbytes for a in arrs.values()) <= DUMP_BYTES_MAX
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrs.items():
+        np.save(os.path.join(dirname, name + suffix + ".npy"), a)
 
 
 def free_port():
@@ -149,7 +181,7 @@ def spawn_ranks(n):
 def child_value(extra, timeout=600):
     """one more bench line from a fresh child process (own HIP / RCCL state); returns its parsed JSON or {"error": ...}"""
     import subprocess
-    cmd = [sys.executable, os.path.abspath(__file__), "--no-cpu", "--no-latency", "--no-staging", "--host-cores", "0", "--no-extra-legs"] + extra
+    cmd = [sys.executable, os.path.abspath(__file__), "--full", "--no-cpu", "--no-latency", "--no-staging", "--host-cores", "0", "--no-extra-legs"] + extra
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "LOCAL_WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     try:
         pr = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=timeout)
@@ -171,14 +203,22 @@ def main():
     ap.add_argument("--steps", type=int, default=40)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--config", choices=sorted(CONFIGS), default="720p4")
-    ap.add_argument("--repeats", type=int, default=3, help="timed regions; value = their median")
-    ap.add_argument("--min-region-s", type=float, default=1.0,
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: roofline and per-kernel figures (isolated jobs), the PCIe, "
+                         "host-cores, CPU-oracle, single-frame-latency and child-process legs, and the --repeats / "
+                         "--min-region-s defaults of 3 regions of >= 1 s.  Without it a run times exactly --steps steps once")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the timed path computed in its last step (keypoints, descriptors, "
+                         "tracks of a fixed sample of rig frames) as DIR/<name>.npy, float32 / float64")
+    ap.add_argument("--repeats", type=int, default=None, help="timed regions; value = their median (default 1, 3 with --full)")
+    ap.add_argument("--min-region-s", type=float, default=None,
                     help="a timed region runs at least this long: the steps per region are raised above --steps when needed "
                          "(20 steps last 0.11 s -- a 3 %% kernel change is invisible through that); `steps` in the output is the "
-                         "number actually timed per region, `steps_requested` what was asked for.  0 = exactly --steps")
+                         "number actually timed per region, `steps_requested` what was asked for.  0 = exactly --steps "
+                         "(default 0, 1.0 with --full)")
     ap.add_argument("--host-cores", type=int, default=4,
-                    help="extra leg `value_host_cores`: the same steps with the process (engine workers, slot drivers, caller) "
-                         "confined to this many cores; 0 = skip")
+                    help="extra leg `value_host_cores` (--full): the same steps with the process (engine workers, slot drivers, "
+                         "caller) confined to this many cores; 0 = skip")
     ap.add_argument("--frames", type=int, default=None, help="rig frames per rank per step (default: slots x 128 images / cameras)")
     ap.add_argument("--slots", type=int, default=None, help="buffer sets in flight per rank (default 6; 12 = 6 groups x 2 on the N>1 path)")
     ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
@@ -208,6 +248,10 @@ def main():
                     help="(tests, no GPU) the ranks only rendezvous over gloo, all-reduce their rank numbers and rank 0 prints "
                          "what it saw; rank FAIL_RANK (>= 0) exits with status 3 instead")
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 3 if args.full else 1
+    if args.min_region_s is None:
+        args.min_region_s = 1.0 if args.full else 0.0
     if args.spawn_selftest is not None and "RANK" in os.environ:
         rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
         if rank == args.spawn_selftest:
@@ -588,63 +632,27 @@ def main():
         np.savez(args.dump_tracks, frames=np.array(my_frames[:fps] if DIST else list(range(fps))),
                  **{"t%d" % i: rig.tracks(i, slot=0)[0] for i in range(fps)})
 
+    if args.dump_outputs:
+        # every job of a slot sees the same uploaded images, so the slot's results are those of its job in the last step
+        sfx = "_r%d" % rank if world > 1 else ""
+        if PAIRS:
+            if rank == 0:
+                dump_outputs(args.dump_outputs, NCAMS, kcap, list(range(total_frames)), lambda f: pairs_result[f])
+        elif DIST:
+            g_last = (args.steps * IT - 1) % G          # the group of the last exchange round; its slot i matched my_frames[i*fps ..]
+            pos = {int(f): i for i, f in enumerate(my_frames)}
+            dump_outputs(args.dump_outputs, NCAMS, kcap, list(my_frames),
+                         lambda f: rig.tracks(pos[f] % fps, slot=g_last * SG + pos[f] // fps), suffix=sfx)
+        else:                                           # slot s holds rig frames s*fps .. (s+1)*fps-1
+            dump_outputs(args.dump_outputs, NCAMS, kcap, list(range(F)), lambda f: rig.tracks(f % fps, slot=f // fps),
+                         lambda f, c: rig.features((f % fps) * NCAMS + c, slot=f // fps))
+
     if rank != 0:
         if dist is not None:
             dist.destroy_process_group()
         return
 
     value = total_frames * IT * args.steps / dt
-    launches = args.steps * IT * SG * len(dts)
-    # workload constants for the algorithmic-byte formulas
-    lv = [rig.level_size(l) for l in range(rig.nlevels)]
-    Spx = sum(w * h for w, h in lv)
-    S0, s_last = lv[0][0] * lv[0][1], lv[-1][0] * lv[-1][1]
-    info = rig.info()
-    nimg_launch = per_slot
-    pairs_launch = fps * NCAMS * (NCAMS - 1) // 2
-    Kc = np.mean([sum(len(rig.candidates(m, l, slot=0)[0]) for l in range(rig.nlevels)) for m in range(min(4, per_slot))])
-    K = np.mean([rig.features(m, slot=0)[1].shape[0] for m in range(min(4, per_slot))])
-    # Which kernel dominates is decided on ISOLATED durations (one job at a time, nothing else on the GPU): with several
-    # jobs in flight every kernel's wall duration is stretched by whatever shares the GPU with it, and the ranking of
-    # two close kernels flips from run to run.  The roofline figures themselves use the timed region, as specified.
-    iso = None
-    if not DIST:
-        acc = {k: [] for k in TIMING_FIELD}
-        rig.set_graph(0)           # launch by launch: every kernel between its own HIP events
-        for _ in range(args.iso_jobs):
-            rig.process_submit(fps, slot=0)
-            rig.process_wait(slot=0)
-            t = rig.timing(slot=0)
-            for k, f in TIMING_FIELD.items():
-                acc[k].append(t[f])
-        iso = {k: float(np.median(v)) for k, v in acc.items()}
-    rank_by = {k: (iso or ksum)[k] for k in GPU_KERNELS}
-    dominant = max(rank_by, key=rank_by.get)
-    sampled = max(1, ksamples[0])            # jobs of the timed regions that ran launch by launch (all of them unless graphs are on)
-    avg_us = ksum[dominant] / sampled if ksamples[0] else (iso[dominant] if iso else 0.0)
-    units = pairs_launch if dominant == "k_knn2" else nimg_launch
-    unit_bytes = algorithmic_bytes(dominant, Spx, S0, s_last, K, Kc, info["bucket_total"])
-    achieved = unit_bytes * units / (avg_us * 1e-6) / 1e9 if avg_us > 0 else 0.0
-    # PMC-derived HBM bytes per launch: only if profiles/traffic.json was measured on exactly these kernels
-    traffic, traffic_note, valu_insts = None, "profiles/traffic.json absent", None
-    tpath = os.path.join(ROOT, "profiles", "traffic.json")
-    if os.path.exists(tpath):
-        try:
-            tj = json.load(open(tpath))
-            if tj.get("kernels_sha256_16") != kernels_sha():
-                traffic_note = "profiles/traffic.json was measured on other kernel sources (sha %s, now %s): not reported" % (
-                    tj.get("kernels_sha256_16"), kernels_sha())
-            elif tj.get("config") != args.config:
-                traffic_note = "profiles/traffic.json is for config %s" % tj.get("config")
-            else:
-                traffic = int(tj[dominant]["bytes_per_image"] * nimg_launch)
-                traffic_note = tj.get("_correction", "")
-                # (the counters were read on launches of tj[...]["images_per_launch"] images: scaled to this run's launch size)
-                lscale = nimg_launch / float(tj[dominant].get("images_per_launch", nimg_launch))
-                valu_insts = tj[dominant].get("valu_insts_per_launch")
-                valu_insts = valu_insts * lscale if valu_insts else valu_insts
-        except Exception as e:      # noqa: BLE001
-            traffic_note = "profiles/traffic.json unreadable: %s" % e
     out = {
         "metric": "multi-cam frames/sec (%d-cam %dx%d @%d kpts/cam, extract + intra-rig match)" % (NCAMS, W, H, NFEAT),
         "value": round(value, 2), "unit": "frames/s", "n_gpus": N, "steps": args.steps, "steps_requested": steps_requested,
@@ -660,60 +668,114 @@ def main():
                     "matched on rank (i+j+f) mod N, accepted lists gathered on rank 0 for the serial track merge (SURVEY 8e as written; not pipelined)"
                     if PAIRS else
                     "camera (c+f) mod N for extraction, one RCCL all-to-all of descriptor sets per step (each set goes to rank f mod N only), frame f mod N for matching")},
-        "roofline": {"bound": "hbm", "kernel": dominant, "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS,
-                     "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic, "traffic_note": traffic_note,
-                     "avg_launch_us": round(avg_us, 2), "algorithmic_bytes_per_launch": int(unit_bytes * units),
-                     "images_per_launch": nimg_launch, "fast_candidates_per_image": int(Kc),
-                     "note": "avg_launch_us is the HIP-event average over the timed regions, where %d jobs share the GPU; "
-                             "isolated_* is the same kernel with one job in flight (median of %d)" % (S, args.iso_jobs)},
-        "kernel_us_per_step": {k: round(v / sampled * launches / args.steps / len(dts), 2) for k, v in ksum.items()},
-        "kernel_timing_samples": {"jobs_sampled": ksamples[0], "jobs_timed": launches,
-                                  "note": "jobs that ran launch by launch with per-kernel HIP events inside the timed regions; the others were replayed "
-                                          "from their captured HIP graph (mcorb_rig_set_graph)"},
     }
-    # the whole path against the HBM roof: SURVEY 8(d)'s bytes per rig frame (every plane once per logical pass, the blur's
-    # 2 S included although this build no longer moves them) and the bytes this build's kernels really have to move
-    pairs_frame = NCAMS * (NCAMS - 1) // 2
-    b_extract = (Spx - s_last) + (Spx - S0) + Spx + 2 * Spx + K * (512 + 32) + Kc * 12 + K * 28
-    b_match = 2 * K * 32 + K * 16
-    b_frame = NCAMS * b_extract + pairs_frame * b_match
-    b_frame_build = NCAMS * sum(algorithmic_bytes(k, Spx, S0, s_last, K, Kc, info["bucket_total"]) for k in GPU_KERNELS if k != "k_knn2") \
-        + pairs_frame * algorithmic_bytes("k_knn2", Spx, S0, s_last, K, Kc, info["bucket_total"])
-    out["roofline"]["whole_path"] = {
-        "bytes_per_frame_survey_8d": int(b_frame), "achieved": round(b_frame * value / 1e9, 1), "frac": round(b_frame * value / 1e9 / HBM_PEAK_GBS, 4),
-        "bytes_per_frame_this_build": int(b_frame_build), "frac_this_build": round(b_frame_build * value / 1e9 / HBM_PEAK_GBS, 4),
-        "unit": "GB/s", "note": "frames/s x bytes per rig frame / 8 TB/s; 8(d) counts a full-plane blur (2 S per image) that is fused "
-                                "into the descriptor kernel here and never travels"}
-    # per-kernel instruction-issue floors (SQ_INSTS_VALU / SQ_INSTS_MFMA per launch from profiles/traffic.json, same sha check):
-    # a wave64 vector instruction occupies its SIMD's issue port for 4 cycles in these kernels whatever its class
-    # (profiles/r03_valu_rates.txt: 2.2 for v_add / v_and / v_xor when two waves issue them back to back, 4.1 for everything
-    # else; SQ_ACTIVE_INST_VALU / SQ_INSTS_VALU = 1.008 quad-cycles in k_fast_cells), a 32x32x32 i8 multiply its matrix pipe for 32
-    SIMDS, CLK_HZ = 1024, 2.4e9
-    floors = {}
-    if traffic is not None:
-        for k in GPU_KERNELS:
-            e = tj.get(k, {})
-            if e.get("valu_insts_per_launch"):
-                sc = nimg_launch / float(e.get("images_per_launch", nimg_launch))   # counters of a 128-image launch -> this launch size
-                f = {"valu_insts": int(e["valu_insts_per_launch"] * sc), "valu_floor_us": round(e["valu_insts_per_launch"] * sc * 4 / SIMDS / CLK_HZ * 1e6, 1)}
-                if e.get("mfma_insts_per_launch"):
-                    f["mfma_insts"] = int(e["mfma_insts_per_launch"] * sc)
-                    f["mfma_floor_us"] = round(e["mfma_insts_per_launch"] * sc * 32.6 / SIMDS / CLK_HZ * 1e6, 1)   # 32.6 cycles per scaled FP4 step (r04_fp4_probe.txt)
-                floors[k] = f
-    if valu_insts:
-        # k_fast_cells' issue floor by phase: staging, pass 1 and the work-list expansion are made of the
-        # 4.1-cycle class (packed 16-bit, v_perm, mbcnt: profiles/r03_valu_rates.txt), the arc score + NMS mix sustains 3.0 cycles
-        # per instruction at the kernel's occupancy (the same file's mix_score row); 47 % of a cell-wave's 794 instructions are
-        # score + NMS (245 + 130 of 794)
-        share_score, cyc_a, cyc_b = 0.47, 4.1, 3.0
-        cyc = (1.0 - share_score) * cyc_a + share_score * cyc_b
-        floor_us = valu_insts * cyc / SIMDS / CLK_HZ * 1e6
-        out["roofline"]["valu"] = {"insts_per_launch": int(valu_insts), "cycles_per_inst": round(cyc, 2),
-                                   "cycles_by_phase": {"staging_pass1_expansion": cyc_a, "arc_score_nms": cyc_b, "share_arc_score_nms": share_score},
-                                   "simds": SIMDS, "clock_ghz": 2.4,
-                                   "floor_us": round(floor_us, 1), "floor_us_flat_4_cycles": round(valu_insts * 4 / SIMDS / CLK_HZ * 1e6, 1),
-                                   "frac_in_flight": round(floor_us / avg_us, 3),
-                                   "evidence": "profiles/r03_valu_rates.txt (tools/valu_rates.hip, 1/2/4/8 waves per SIMD)"}
+    iso = None
+    if args.full:
+        launches = args.steps * IT * SG * len(dts)
+        # workload constants for the algorithmic-byte formulas
+        lv = [rig.level_size(l) for l in range(rig.nlevels)]
+        Spx = sum(w * h for w, h in lv)
+        S0, s_last = lv[0][0] * lv[0][1], lv[-1][0] * lv[-1][1]
+        info = rig.info()
+        nimg_launch = per_slot
+        pairs_launch = fps * NCAMS * (NCAMS - 1) // 2
+        Kc = np.mean([sum(len(rig.candidates(m, l, slot=0)[0]) for l in range(rig.nlevels)) for m in range(min(4, per_slot))])
+        K = np.mean([rig.features(m, slot=0)[1].shape[0] for m in range(min(4, per_slot))])
+        # Which kernel dominates is decided on ISOLATED durations (one job at a time, nothing else on the GPU): with several
+        # jobs in flight every kernel's wall duration is stretched by whatever shares the GPU with it, and the ranking of
+        # two close kernels flips from run to run.  The roofline figures themselves use the timed region, as specified.
+        if not DIST:
+            acc = {k: [] for k in TIMING_FIELD}
+            rig.set_graph(0)           # launch by launch: every kernel between its own HIP events
+            for _ in range(args.iso_jobs):
+                rig.process_submit(fps, slot=0)
+                rig.process_wait(slot=0)
+                t = rig.timing(slot=0)
+                for k, f in TIMING_FIELD.items():
+                    acc[k].append(t[f])
+            iso = {k: float(np.median(v)) for k, v in acc.items()}
+        rank_by = {k: (iso or ksum)[k] for k in GPU_KERNELS}
+        dominant = max(rank_by, key=rank_by.get)
+        sampled = max(1, ksamples[0])            # jobs of the timed regions that ran launch by launch (all of them unless graphs are on)
+        avg_us = ksum[dominant] / sampled if ksamples[0] else (iso[dominant] if iso else 0.0)
+        units = pairs_launch if dominant == "k_knn2" else nimg_launch
+        unit_bytes = algorithmic_bytes(dominant, Spx, S0, s_last, K, Kc, info["bucket_total"])
+        achieved = unit_bytes * units / (avg_us * 1e-6) / 1e9 if avg_us > 0 else 0.0
+        # PMC-derived HBM bytes per launch: only if profiles/traffic.json was measured on exactly these kernels
+        traffic, traffic_note, valu_insts = None, "profiles/traffic.json absent", None
+        tpath = os.path.join(ROOT, "profiles", "traffic.json")
+        if os.path.exists(tpath):
+            try:
+                tj = json.load(open(tpath))
+                if tj.get("kernels_sha256_16") != kernels_sha():
+                    traffic_note = "profiles/traffic.json was measured on other kernel sources (sha %s, now %s): not reported" % (
+                        tj.get("kernels_sha256_16"), kernels_sha())
+                elif tj.get("config") != args.config:
+                    traffic_note = "profiles/traffic.json is for config %s" % tj.get("config")
+                else:
+                    traffic = int(tj[dominant]["bytes_per_image"] * nimg_launch)
+                    traffic_note = tj.get("_correction", "")
+                    # (the counters were read on launches of tj[...]["images_per_launch"] images: scaled to this run's launch size)
+                    lscale = nimg_launch / float(tj[dominant].get("images_per_launch", nimg_launch))
+                    valu_insts = tj[dominant].get("valu_insts_per_launch")
+                    valu_insts = valu_insts * lscale if valu_insts else valu_insts
+            except Exception as e:      # noqa: BLE001
+                traffic_note = "profiles/traffic.json unreadable: %s" % e
+        out.update({
+            "roofline": {"bound": "hbm", "kernel": dominant, "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS,
+                         "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic, "traffic_note": traffic_note,
+                         "avg_launch_us": round(avg_us, 2), "algorithmic_bytes_per_launch": int(unit_bytes * units),
+                         "images_per_launch": nimg_launch, "fast_candidates_per_image": int(Kc),
+                         "note": "avg_launch_us is the HIP-event average over the timed regions, where %d jobs share the GPU; "
+                                 "isolated_* is the same kernel with one job in flight (median of %d)" % (S, args.iso_jobs)},
+            "kernel_us_per_step": {k: round(v / sampled * launches / args.steps / len(dts), 2) for k, v in ksum.items()},
+            "kernel_timing_samples": {"jobs_sampled": ksamples[0], "jobs_timed": launches,
+                                      "note": "jobs that ran launch by launch with per-kernel HIP events inside the timed regions; the others were replayed "
+                                              "from their captured HIP graph (mcorb_rig_set_graph)"},
+        })
+        # the whole path against the HBM roof: SURVEY 8(d)'s bytes per rig frame (every plane once per logical pass, the blur's
+        # 2 S included although this build no longer moves them) and the bytes this build's kernels really have to move
+        pairs_frame = NCAMS * (NCAMS - 1) // 2
+        b_extract = (Spx - s_last) + (Spx - S0) + Spx + 2 * Spx + K * (512 + 32) + Kc * 12 + K * 28
+        b_match = 2 * K * 32 + K * 16
+        b_frame = NCAMS * b_extract + pairs_frame * b_match
+        b_frame_build = NCAMS * sum(algorithmic_bytes(k, Spx, S0, s_last, K, Kc, info["bucket_total"]) for k in GPU_KERNELS if k != "k_knn2") \
+            + pairs_frame * algorithmic_bytes("k_knn2", Spx, S0, s_last, K, Kc, info["bucket_total"])
+        out["roofline"]["whole_path"] = {
+            "bytes_per_frame_survey_8d": int(b_frame), "achieved": round(b_frame * value / 1e9, 1), "frac": round(b_frame * value / 1e9 / HBM_PEAK_GBS, 4),
+            "bytes_per_frame_this_build": int(b_frame_build), "frac_this_build": round(b_frame_build * value / 1e9 / HBM_PEAK_GBS, 4),
+            "unit": "GB/s", "note": "frames/s x bytes per rig frame / 8 TB/s; 8(d) counts a full-plane blur (2 S per image) that is fused "
+                                    "into the descriptor kernel here and never travels"}
+        # per-kernel instruction-issue floors (SQ_INSTS_VALU / SQ_INSTS_MFMA per launch from profiles/traffic.json, same sha check):
+        # a wave64 vector instruction occupies its SIMD's issue port for 4 cycles in these kernels whatever its class
+        # (profiles/r03_valu_rates.txt: 2.2 for v_add / v_and / v_xor when two waves issue them back to back, 4.1 for everything
+        # else; SQ_ACTIVE_INST_VALU / SQ_INSTS_VALU = 1.008 quad-cycles in k_fast_cells), a 32x32x32 i8 multiply its matrix pipe for 32
+        SIMDS, CLK_HZ = 1024, 2.4e9
+        floors = {}
+        if traffic is not None:
+            for k in GPU_KERNELS:
+                e = tj.get(k, {})
+                if e.get("valu_insts_per_launch"):
+                    sc = nimg_launch / float(e.get("images_per_launch", nimg_launch))   # counters of a 128-image launch -> this launch size
+                    f = {"valu_insts": int(e["valu_insts_per_launch"] * sc), "valu_floor_us": round(e["valu_insts_per_launch"] * sc * 4 / SIMDS / CLK_HZ * 1e6, 1)}
+                    if e.get("mfma_insts_per_launch"):
+                        f["mfma_insts"] = int(e["mfma_insts_per_launch"] * sc)
+                        f["mfma_floor_us"] = round(e["mfma_insts_per_launch"] * sc * 32.6 / SIMDS / CLK_HZ * 1e6, 1)   # 32.6 cycles per scaled FP4 step (r04_fp4_probe.txt)
+                    floors[k] = f
+        if valu_insts:
+            # k_fast_cells' issue floor by phase: staging, pass 1 and the work-list expansion are made of the
+            # 4.1-cycle class (packed 16-bit, v_perm, mbcnt: profiles/r03_valu_rates.txt), the arc score + NMS mix sustains 3.0 cycles
+            # per instruction at the kernel's occupancy (the same file's mix_score row); 47 % of a cell-wave's 794 instructions are
+            # score + NMS (245 + 130 of 794)
+            share_score, cyc_a, cyc_b = 0.47, 4.1, 3.0
+            cyc = (1.0 - share_score) * cyc_a + share_score * cyc_b
+            floor_us = valu_insts * cyc / SIMDS / CLK_HZ * 1e6
+            out["roofline"]["valu"] = {"insts_per_launch": int(valu_insts), "cycles_per_inst": round(cyc, 2),
+                                       "cycles_by_phase": {"staging_pass1_expansion": cyc_a, "arc_score_nms": cyc_b, "share_arc_score_nms": share_score},
+                                       "simds": SIMDS, "clock_ghz": 2.4,
+                                       "floor_us": round(floor_us, 1), "floor_us_flat_4_cycles": round(valu_insts * 4 / SIMDS / CLK_HZ * 1e6, 1),
+                                       "frac_in_flight": round(floor_us / avg_us, 3),
+                                       "evidence": "profiles/r03_valu_rates.txt (tools/valu_rates.hip, 1/2/4/8 waves per SIMD)"}
     if DIST:
         out["exchange"] = {"collective": "all_gather_into_tensor + gather of the pair tables to rank 0" if PAIRS else "all_to_all_single (uneven splits)", "bytes_sent_per_rank_per_step": int(exchange_bytes * IT), "rounds_per_step": IT,
                            "send_splits_rank0": None if PAIRS else send_splits,
@@ -732,7 +794,7 @@ def main():
                                    (pairs_launch if k == "k_knn2" else nimg_launch) / (iso[k] * 1e-6) / 1e9, 1)}, **floors.get(k, {}))
             for k in GPU_KERNELS if iso[k] > 0}
 
-    if N == 1 and not DIST and not args.no_staging:
+    if args.full and N == 1 and not DIST and not args.no_staging:
         # the same steps with the frame hand-off in front of every batch: the reader's side of the boundary
         plane = W * H
         dt_st = timed_region(args.steps, False, stage=lambda s: rig.upload_staged(per_slot, slot=s))
@@ -745,7 +807,7 @@ def main():
                                "bytes/s in the staged region.  `value` itself keeps its inputs resident in HBM; fed from a host it is "
                                "bounded by these.")
 
-    if N == 1 and not DIST and args.host_cores > 0 and hasattr(os, "sched_setaffinity"):
+    if args.full and N == 1 and not DIST and args.host_cores > 0 and hasattr(os, "sched_setaffinity"):
         # how much of `value` hangs on host cores (selection workers, slot drivers, track merges): the same steps from a
         # second rig whose threads -- created under the narrowed affinity mask -- and the caller share args.host_cores cores
         allowed = sorted(os.sched_getaffinity(0))
@@ -775,7 +837,7 @@ def main():
                 S = S_main
                 os.sched_setaffinity(0, set(allowed))
 
-    if N == 1 and not DIST and not args.no_cpu:
+    if args.full and N == 1 and not DIST and not args.no_cpu:
         ncpu = os.cpu_count()
         times, t_ext, results = cpu_baseline(cfg, list(range(4 + args.cpu_frames)), NCAMS)
         times, t_ext = times[4:], t_ext[4:]
@@ -808,7 +870,7 @@ def main():
             checked += 1
         out["gpu_equals_oracle_frames_checked"] = checked
         out["gpu_equals_oracle_frame0"] = bool(ok)   # (kept under its round-1 name) true only if ALL checked frames are bit-identical
-    if N == 1 and not DIST and not args.no_latency:
+    if args.full and N == 1 and not DIST and not args.no_latency:
         # one rig frame at a time, nothing in flight (how MC-SLAM's tracking loop calls the front-end): host u8 images in,
         # keypoints / descriptors / tracks back on the host.  Not part of `value`.
         rig.close()
@@ -818,7 +880,7 @@ def main():
         out["single_frame_latency_ms"] = {k: lat[k] for k in ("upload_ms", "extract_match_ms", "readback_ms", "total_ms", "total_p95_ms", "separated")}
         out["single_frame_latency_ms"]["note"] = ("upload_ms = staging copy + DMA enqueue; the PCIe transfer itself runs at the head of "
                                                   "extract_match_ms (`separated` drains the stream between the two)")
-    if N == 1 and not DIST and not args.no_extra_legs and args.config == "720p4":
+    if args.full and N == 1 and not DIST and not args.no_extra_legs and args.config == "720p4":
         # two more driver-visible numbers, each from a fresh child process after this one's legs are done (its rig is closed):
         rig.close()
         fd = child_value(["--force-dist", "--repeats", "1"])

@@ -4,7 +4,7 @@
 O=gpurun_out/${1:-ab}; mkdir -p $O; shift
 one() {
   local tag=$1; shift
-  env "$@" python bench.py --no-cpu --no-latency --no-staging --repeats 3 > $O/$tag.json 2>$O/$tag.err
+  env "$@" python bench.py --full --no-cpu --no-latency --no-staging --repeats 3 > $O/$tag.json 2>$O/$tag.err
   python3 -c "
 import json
 d=json.loads(open('$O/$tag.json').read().strip().splitlines()[-1])

@@ -5,7 +5,7 @@ O=gpurun_out/${1:-ab2}; mkdir -p $O
 one() {
   local tag=$1 cfg=$2
   local envs=${cfg%%--*} args=${cfg#*--}
-  env $envs python bench.py --no-cpu --no-latency --no-staging --host-cores 0 --no-extra-legs --repeats 3 $args > $O/$tag.json 2>$O/$tag.err
+  env $envs python bench.py --full --no-cpu --no-latency --no-staging --host-cores 0 --no-extra-legs --repeats 3 $args > $O/$tag.json 2>$O/$tag.err
   python3 -c "
 import json
 d=json.loads(open('$O/$tag.json').read().strip().splitlines()[-1])

@@ -4,7 +4,7 @@
 O=gpurun_out/${1:-abba}; mkdir -p $O; KV=$2
 one() {
   local tag=$1; shift
-  env "$@" python bench.py --no-cpu --no-latency --no-staging --host-cores 0 --repeats 3 > $O/$tag.json 2>$O/$tag.err
+  env "$@" python bench.py --full --no-cpu --no-latency --no-staging --host-cores 0 --repeats 3 > $O/$tag.json 2>$O/$tag.err
   python3 -c "
 import json
 d=json.loads(open('$O/$tag.json').read().strip().splitlines()[-1])

@@ -9,13 +9,13 @@ ROOT=$(pwd)
 cd /tmp && export TMPDIR=/tmp && cd $ROOT
 export MCORB_GRAPH=0   # per-kernel events and one launch per kernel everywhere in this collection (single-slot rigs would replay a graph)
 ONE="--steps 3 --warmup 1 --repeats 1 --min-region-s 0 --host-cores 0 --no-cpu --no-latency --no-staging --slots 1 --frames 32 --iso-jobs 1"
-timeout -k 10 400 python3 bench.py --no-extra-legs 2>$O/bench.err | tail -1 > $O/bench_default.json   # provisional (install_profiles.py reads the launch size from it)
+timeout -k 10 400 python3 bench.py --full --no-extra-legs 2>$O/bench.err | tail -1 > $O/bench_default.json   # provisional (install_profiles.py reads the launch size from it)
 echo "bench done"
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/p_def -o d -- python3 bench.py --no-cpu --no-latency --no-staging --repeats 1 > $O/p_def.log 2>&1
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/p_1s -o s -- python3 bench.py $ONE > $O/p_1s.log 2>&1
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/p_def -o d -- python3 bench.py --full --no-cpu --no-latency --no-staging --repeats 1 > $O/p_def.log 2>&1
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/p_1s -o s -- python3 bench.py --full $ONE > $O/p_1s.log 2>&1
 echo "stats done"
-timeout -k 10 300 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $O/p_f -o f -- python3 bench.py $ONE > $O/p_f.log 2>&1
-timeout -k 10 300 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $O/p_w -o w -- python3 bench.py $ONE > $O/p_w.log 2>&1
+timeout -k 10 300 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $O/p_f -o f -- python3 bench.py --full $ONE > $O/p_f.log 2>&1
+timeout -k 10 300 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $O/p_w -o w -- python3 bench.py --full $ONE > $O/p_w.log 2>&1
 python3 scripts/pmc_summary.py $(find $O/p_f -name '*counter_collection.csv' | head -1) > $O/fetch.txt
 python3 scripts/pmc_summary.py $(find $O/p_w -name '*counter_collection.csv' | head -1) > $O/write.txt
 echo "traffic done"
@@ -37,7 +37,7 @@ cp $(find $O/p_1s -name '*kernel_stats.csv' | head -1) $O/stats_1slot.csv
 # roofline.valu are filled in (bench.py drops them when the kernel sources' sha does not match)
 python3 scripts/install_profiles.py $O ${2:-r04} > /dev/null
 unset MCORB_GRAPH
-timeout -k 10 400 python3 bench.py 2>$O/bench.err | tail -1 > $O/bench_default.json
+timeout -k 10 400 python3 bench.py --full 2>$O/bench.err | tail -1 > $O/bench_default.json
 # the raw traces stay on the box (gpurun copies back at most 64 MiB): summaries only
 rm -rf $O/p_def $O/p_1s $O/p_f $O/p_w $O/calib $O/sq/p[0-9] $O/sq/p[0-9]/ 2>/dev/null
 find $O -name '*.csv' -size +2M -delete

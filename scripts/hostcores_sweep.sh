@@ -3,7 +3,7 @@
 O=gpurun_out/${1:-hc}; mkdir -p $O
 for t in default 1 3 4 6; do
   if [ $t = default ]; then unset MCORB_HOST_THREADS; else export MCORB_HOST_THREADS=$t; fi
-  timeout -k 10 300 python3 bench.py --no-cpu --no-latency --no-staging --no-extra-legs --repeats 1 --iso-jobs 0 > $O/t$t.json 2> $O/t$t.err || { echo "threads $t failed"; tail -3 $O/t$t.err; exit 1; }
+  timeout -k 10 300 python3 bench.py --full --no-cpu --no-latency --no-staging --no-extra-legs --repeats 1 --iso-jobs 0 > $O/t$t.json 2> $O/t$t.err || { echo "threads $t failed"; tail -3 $O/t$t.err; exit 1; }
   python3 -c "
 import json
 d=json.loads([l for l in open('$O/t$t.json') if l.startswith('{')][-1])

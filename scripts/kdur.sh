@@ -4,7 +4,7 @@
 O=gpurun_out/${1:-kdur}; mkdir -p $O; shift
 ROOT=$(pwd); cd /tmp && export TMPDIR=/tmp && cd $ROOT
 for kv in "$@"; do export "$kv"; done
-timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $O/p -o t -- python3 bench.py --no-cpu --no-latency --no-staging --repeats 1 --iso-jobs 0 ${BARGS} > $O/log 2>&1
+timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $O/p -o t -- python3 bench.py --full --no-cpu --no-latency --no-staging --repeats 1 --iso-jobs 0 ${BARGS} > $O/log 2>&1
 python3 - <<PY
 import csv,statistics,glob
 f=glob.glob('$O/p/**/*kernel_trace.csv',recursive=True)[0]

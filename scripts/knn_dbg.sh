@@ -3,7 +3,7 @@
 # results are wrong, only the durations mean something): isolated kernel time per variant from the bench's HIP events
 O=gpurun_out/${1:-knndbg}; mkdir -p $O
 for d in ${KNN_DBG_LIST:-0 16 1 4 5 0}; do
-  MCORB_KNN_DBG=$d python bench.py --no-cpu --no-latency --no-staging --host-cores 0 --repeats 1 --min-region-s 0.2 > $O/d$d.json 2>$O/d$d.err
+  MCORB_KNN_DBG=$d python bench.py --full --no-cpu --no-latency --no-staging --host-cores 0 --repeats 1 --min-region-s 0.2 > $O/d$d.json 2>$O/d$d.err
   python3 -c "
 import json
 d=json.loads(open('$O/d$d.json').read().strip().splitlines()[-1])

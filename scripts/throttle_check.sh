@@ -6,7 +6,7 @@ cat $CG/cpu.max 2>/dev/null || cat $CG/cpu/cpu.cfs_quota_us $CG/cpu/cpu.cfs_peri
 nproc
 cat $CG/cpu.stat 2>/dev/null > $O/stat0 || cat $CG/cpu/cpu.stat > $O/stat0
 shift
-python bench.py --no-cpu --no-latency --no-staging --repeats 3 --iso-jobs 0 "$@" > $O/b.json 2>$O/b.err
+python bench.py --full --no-cpu --no-latency --no-staging --repeats 3 --iso-jobs 0 "$@" > $O/b.json 2>$O/b.err
 cat $CG/cpu.stat 2>/dev/null > $O/stat1 || cat $CG/cpu/cpu.stat > $O/stat1
 paste $O/stat0 $O/stat1
 python3 -c "

@@ -5,7 +5,7 @@ CG=/sys/fs/cgroup
 run() {
   local tag=$1; shift
   local a=$(grep -E "^(nr_throttled|throttled_usec|usage_usec)" $CG/cpu.stat | awk '{print $2}' | tr '\n' ' ')
-  env "$@" python bench.py --no-cpu --no-latency --no-staging --repeats 3 --iso-jobs 0 $BARGS > $O/$tag.json 2>$O/$tag.err
+  env "$@" python bench.py --full --no-cpu --no-latency --no-staging --repeats 3 --iso-jobs 0 $BARGS > $O/$tag.json 2>$O/$tag.err
   local b=$(grep -E "^(nr_throttled|throttled_usec|usage_usec)" $CG/cpu.stat | awk '{print $2}' | tr '\n' ' ')
   python3 -c "
 import json,sys

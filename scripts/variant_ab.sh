@@ -6,7 +6,7 @@ cp mc-slam_amd/libmcorb.so $O/orig.so
 for rep in 1 2; do
 for v in "$@"; do
   cp mc-slam_amd/_variants/libmcorb_$v.so mc-slam_amd/libmcorb.so
-  timeout -k 10 300 python3 bench.py --no-cpu --no-latency --no-staging --no-extra-legs --host-cores 0 --repeats 1 > $O/$v$rep.json 2> $O/$v$rep.err || { echo "$v failed"; tail -3 $O/$v$rep.err; cp $O/orig.so mc-slam_amd/libmcorb.so; exit 1; }
+  timeout -k 10 300 python3 bench.py --full --no-cpu --no-latency --no-staging --no-extra-legs --host-cores 0 --repeats 1 > $O/$v$rep.json 2> $O/$v$rep.err || { echo "$v failed"; tail -3 $O/$v$rep.err; cp $O/orig.so mc-slam_amd/libmcorb.so; exit 1; }
   python3 -c "
 import json
 d=json.loads([l for l in open('$O/$v$rep.json') if l.startswith('{')][-1])

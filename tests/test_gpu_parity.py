@@ -478,7 +478,10 @@ def test_sharded_path_export_gather_match_external(mc):
     import ctypes
     from importlib import import_module
     shard = import_module("mc-slam_amd.sharding")
-    hip = ctypes.CDLL("libamdhip64.so")          # the runtime libmcorb already loaded (torch would bring its own copy)
+    # the HIP runtime libmcorb is bound to: symbols looked up through libmcorb's handle resolve in its own dependencies.  (By
+    # bare name, "libamdhip64.so" finds torch's private copy once torch has been imported after libmcorb -- as the CPU tests
+    # of a whole-suite run do -- and that second runtime sees no device.)
+    hip = ctypes.CDLL(mc._lib.LIB_PATH)
     world, C, W, H, N, FPR = 2, 4, 640, 480, 800, 2          # 2 frames per rank per step
     total = FPR * world
     per = shard.sets_per_rank(world, C, total)
