@@ -134,6 +134,27 @@ int mcorb_rig_num_keypoints(mcorb_rig *r, int slot, int m);
 int mcorb_rig_get_features(mcorb_rig *r, int slot, int m, mcorb_keypoint *kps, uint8_t *desc, int cap,
                            int *n_out, int *mono_index_out);
 
+/* MultiCameraFrame::UndistortKeyPoints (MultiCameraFrame.cpp:300-347) on the device, inside every extraction job: for a camera
+ * with undistortion set, k_undistort runs cv::undistortPoints(pts, pts, K, dist, noArray(), K) (OpenCV 4.x, 5 fixed iterations,
+ * fp64, no contraction) on every keypoint the job selects, and the result comes back with the job.  K (3x3 row-major) and dist are
+ * camconfig's CV_64F values; both go through float as in the reference (:324-325).  ncoeffs: 4, 5, 8 or 12; dist == NULL or
+ * ncoeffs == 0 clears the camera.  MCORB_E_ARG: bad camera, count (14, the tilt model, included) or a non-finite / zero fx, fy;
+ * MCORB_E_STATE while any slot has a job submitted and not yet waited for.  With no camera set a job is exactly what it is
+ * without this call.
+ * The reference's zero test, quirk included: it passes a camera through unchanged when dist_coeffs_[cam].at<float>(0) == 0.0 on
+ * the CV_64F Mat (:302), i.e. when the LOW 32 BITS of the double k1 are a float zero -- true for k1 == 0, and also for short binary
+ * values such as k1 = -0.25 whatever the other coefficients say.  mcorb_rig_undistortion_active reports that decision: 1 if the
+ * reference would call undistortPoints for the camera, 0 if it copies (camera not set, or passed through). */
+int mcorb_rig_set_undistortion(mcorb_rig *r, int cam, const double *K, const double *dist, int ncoeffs);
+int mcorb_rig_undistortion_active(mcorb_rig *r, int cam);
+/* image_kps_undist of image m (m = frame*ncams + cam): the records of mcorb_rig_get_features with x, y replaced (:336-344); for a
+ * camera that is not set or passed through, the raw records.  MCORB_E_STATE for an image not extracted since the last
+ * mcorb_rig_set_undistortion.  With undistortion set for any camera, the consumers below that take an undistorted set
+ * (mcorb_rig_get_tracks_epipolar's kps_undist, mcorb_rig_match_bow_frames' y_undist, mcorb_rig_obtain_lf_features(_frames)'
+ * kps_undist) read this set where the caller passes NULL (as a whole or per entry), and so does mcorb_rig_match_bow; an explicit
+ * pointer still wins.  With nothing set they read the raw keypoints, as without this feature. */
+int mcorb_rig_get_features_undist(mcorb_rig *r, int slot, int m, mcorb_keypoint *kps, int cap, int *n_out);
+
 /* computeIntraMatches(matches, false) (MultiCameraFrame.cpp:1100-1288) for the
  * first `nframes` rig frames of a slot: BruteForceMatch(i, j, dist_thresh,
  * ratio) for all i<j on the GPU (all-pairs Hamming k-NN, k = 2), then the

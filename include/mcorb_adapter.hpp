@@ -15,6 +15,7 @@
 #include <stdint.h>
 #include <string.h>
 
+#include <algorithm>
 #include <array>
 #include <map>
 #include <stdexcept>
@@ -266,8 +267,45 @@ public:
             image_descriptors[c].resize((size_t)n * 32);
         }
         image_kps_undist.clear();   // belongs to the previous frame
+        if (std::find(distorted_.begin(), distorted_.end(), 1) != distorted_.end()) {
+            // UndistortKeyPoints (:236-245, :300-347) ran on the device inside the extraction job
+            image_kps_undist.resize(num_cams_);
+            for (int c = 0; c < num_cams_; c++) {
+                image_kps_undist[c].resize(cap);
+                int n = 0;
+                check(mcorb_rig_get_features_undist(rig_, 0, c, image_kps_undist[c].data(), cap, &n), "mcorb_rig_get_features_undist");
+                image_kps_undist[c].resize(n);
+            }
+        }
         matched_ = false;
     }
+    // camconfig_.K_mats_[cam] (row-major 3x3) and dist_coeffs_[cam] (n = 4, 5, 8 or 12 values; NULL or 0 clears), CV_64F.  Call
+    // once at init, in place of the host's cv::undistortPoints: from then on extractFeaturesParallel() fills image_kps_undist as
+    // UndistortKeyPoints (MultiCameraFrame.cpp:300-347) does, on the device, the reference's zero test on k1 (:302) included.
+    void setDistortion(int cam, const double *K, const double *dist, int n)
+    {
+        check(mcorb_rig_set_undistortion(rig_, cam, K, dist, n), "mcorb_rig_set_undistortion");
+        if ((int)distorted_.size() != num_cams_) distorted_.assign(num_cams_, 0);
+        distorted_[cam] = dist && n ? 1 : 0;
+    }
+#ifdef MCORB_WITH_OPENCV
+    // the same from camconfig_.K_mats_ / dist_coeffs_ as the reader fills them (CV_64F; 1 x n or n x 1; an empty Mat = none)
+    void setDistortion(const std::vector<cv::Mat> &K_mats, const std::vector<cv::Mat> &dist_coeffs)
+    {
+        if ((int)K_mats.size() != num_cams_ || (int)dist_coeffs.size() != num_cams_) throw std::runtime_error("ERROR:: one K and one dist per camera");
+        for (int c = 0; c < num_cams_; c++) {
+            const cv::Mat &K = K_mats[c], &D = dist_coeffs[c];
+            if (K.type() != CV_64F || K.rows != 3 || K.cols != 3) throw std::runtime_error("ERROR:: K_mats_ must be 3x3 CV_64F");
+            const int n = D.rows * D.cols;
+            if (n && (D.type() != CV_64F || (D.rows != 1 && D.cols != 1))) throw std::runtime_error("ERROR:: dist_coeffs_ must be a CV_64F vector");
+            double k[9], d[12] = {0};
+            for (int r = 0; r < 3; r++)
+                for (int j = 0; j < 3; j++) k[r * 3 + j] = K.at<double>(r, j);
+            for (int i = 0; i < n && i < 12; i++) d[i] = D.rows == 1 ? D.at<double>(0, i) : D.at<double>(i, 0);
+            setDistortion(c, k, n ? d : nullptr, n);
+        }
+    }
+#endif
     // BruteForceMatch (MultiCameraFrame.cpp:1024-1086), cam1 < cam2 as at every reference call site
     void BruteForceMatch(int img1_ind, int img2_ind, float dist_thresh, float neigh_ratio,
                          std::vector<unsigned int> &indices_1, std::vector<unsigned int> &indices_2,
@@ -415,6 +453,7 @@ private:
     bool matched_ = false;
     float thr_ = 0, ratio_ = 0;
     std::vector<double> F_pairs_;
+    std::vector<int> distorted_;   // per camera: setDistortion gave it coefficients
 };
 
 }  // namespace mcorb

@@ -141,6 +141,33 @@ class Rig:
                                                  C.byref(nn), C.byref(mono)))
         return mono.value, kps, desc
 
+    # -- UndistortKeyPoints (MultiCameraFrame.cpp:300-347), on the device inside every job -------------------------------
+    def set_undistortion(self, cam, K=None, dist=None):
+        """camconfig_.K_mats_[cam] (3x3) and dist_coeffs_[cam] (4, 5, 8 or 12 values) as CV_64F; dist None or empty clears"""
+        if dist is None or len(np.ravel(dist)) == 0:
+            _lib.check(self.L.mcorb_rig_set_undistortion(self.h_rig, cam, None, None, 0))
+            return
+        K = np.ascontiguousarray(K, np.float64).reshape(9)
+        d = np.ascontiguousarray(dist, np.float64).ravel()
+        _lib.check(self.L.mcorb_rig_set_undistortion(self.h_rig, cam, K.ctypes.data, d.ctypes.data, d.size))
+
+    def undistortion_active(self, cam):
+        """True if the reference would call cv::undistortPoints for this camera (set, and not passed by its zero test)"""
+        v = self.L.mcorb_rig_undistortion_active(self.h_rig, cam)
+        if v < 0:
+            _lib.check(v)
+        return bool(v)
+
+    def features_undist(self, m, slot=0):
+        """image_kps_undist of image m: the keypoint records with pt undistorted (raw for cameras that are not)"""
+        n = self.L.mcorb_rig_num_keypoints(self.h_rig, slot, m)
+        if n < 0:
+            _lib.check(n)
+        kps = np.zeros(n, KP_DTYPE)
+        nn = C.c_int()
+        _lib.check(self.L.mcorb_rig_get_features_undist(self.h_rig, slot, m, kps.ctypes.data, n, C.byref(nn)))
+        return kps
+
     # -- matching -----------------------------------------------------------
     def match(self, nframes, slot=0, dist_thresh=75.0, ratio=0.85):
         _lib.check(self.L.mcorb_rig_match(self.h_rig, slot, nframes, dist_thresh, ratio))
@@ -722,6 +749,7 @@ class MultiCameraFrame:
         self.imgs = []
         self.image_kps, self.image_kps_undist, self.image_descriptors = [], [], []
         self._matched = False
+        self._distorted = False   # setDistortion gave some camera coefficients: extraction fills image_kps_undist from the rig
 
     def setData(self, img_set, segmap_set=None):
         """setData (MultiCameraFrame.cpp:95-152): accepts the reference's CV_32F [0,1] frames or u8."""
@@ -741,10 +769,23 @@ class MultiCameraFrame:
             _, k, d = self.rig.features(c)
             self.image_kps.append(k)
             self.image_descriptors.append(d)
-        self.image_kps_undist = self.image_kps   # RECTIFY, or zero distortion: UndistortKeyPoints copies (:241-242, :302-305)
+        if self._distorted:   # UndistortKeyPoints (:236-245, :300-347), run on the device inside the extraction job
+            self.image_kps_undist = [self.rig.features_undist(c) for c in range(self.num_cams_)]
+        else:
+            self.image_kps_undist = self.image_kps   # RECTIFY, or zero distortion: UndistortKeyPoints copies (:241-242, :302-305)
         self._matched = False
 
     extractFeatures = extractFeaturesParallel
+
+    def setDistortion(self, K_mats, dist_coeffs):
+        """camconfig_.K_mats_ / dist_coeffs_ (CV_64F, 4, 5, 8 or 12 coefficients per camera; None or empty = no distortion):
+        call once at init.  From then on extractFeaturesParallel() fills image_kps_undist as UndistortKeyPoints does, zero test
+        included (a camera whose k1 passes it is copied)."""
+        if len(K_mats) != self.num_cams_ or len(dist_coeffs) != self.num_cams_:
+            raise ValueError("one K and one coefficient set per camera")
+        for c in range(self.num_cams_):
+            self.rig.set_undistortion(c, K_mats[c], dist_coeffs[c])
+        self._distorted = any(d is not None and len(np.ravel(d)) > 0 for d in dist_coeffs)
 
     def setUndistorted(self, image_kps_undist):
         """image_kps_undist as UndistortKeyPoints (MultiCameraFrame.cpp:300-347) fills it for a distorted, unrectified rig

@@ -65,6 +65,9 @@ SIGNATURES = {
     "mcorb_rig_process_wait": (_i, [_vp, _i]),
     "mcorb_rig_num_keypoints": (_i, [_vp, _i, _i]),
     "mcorb_rig_get_features": (_i, [_vp, _i, _i, _vp, _vp, _i, _ip, _ip]),
+    "mcorb_rig_set_undistortion": (_i, [_vp, _i, _vp, _vp, _i]),
+    "mcorb_rig_undistortion_active": (_i, [_vp, _i]),
+    "mcorb_rig_get_features_undist": (_i, [_vp, _i, _i, _vp, _i, _ip]),
     "mcorb_rig_match": (_i, [_vp, _i, _i, _f, _f]),
     "mcorb_rig_match_submit": (_i, [_vp, _i, _i, _f, _f]),
     "mcorb_rig_match_wait": (_i, [_vp, _i]),

@@ -268,6 +268,33 @@ int mcorb_rig_get_tracks(mcorb_rig *r, int slot, int frame, int32_t *tracks, int
     return MCORB_OK;
 }
 
+int mcorb_rig_set_undistortion(mcorb_rig *r, int cam, const double *K, const double *dist, int ncoeffs)
+{
+    if (!r) { set_error("bad rig"); return MCORB_E_ARG; }
+    return r->rig.set_undistortion(cam, K, dist, ncoeffs);
+}
+
+int mcorb_rig_undistortion_active(mcorb_rig *r, int cam)
+{
+    if (!r || cam < 0 || cam >= r->rig.ncams) { set_error("bad rig/camera"); return MCORB_E_ARG; }
+    return r->rig.undist_set[cam] && r->rig.undist_cams[cam].mode == 1 ? 1 : 0;
+}
+
+int mcorb_rig_get_features_undist(mcorb_rig *r, int slot, int m, mcorb_keypoint *kps, int cap, int *n_out)
+{
+    Slot *s = get_slot(r, slot);
+    if (!s) return MCORB_E_STATE;
+    if (m < 0 || m >= s->nimg_done) { set_error("image index out of range"); return MCORB_E_ARG; }
+    std::vector<const mcorb_keypoint *> p;
+    const int st = r->rig.undist_records(*s, m, 1, p);
+    if (st != MCORB_OK) return st;
+    const int n = (int)s->kps[m].size();
+    if (n_out) *n_out = n;
+    if (n > cap) { set_error("keypoint buffer too small"); return MCORB_E_CAP; }
+    if (kps && n) memcpy(kps, p[0], (size_t)n * sizeof(mcorb_keypoint));
+    return MCORB_OK;
+}
+
 int mcorb_rig_get_tracks_epipolar(mcorb_rig *r, int slot, int frame, const double *F, const mcorb_keypoint *const *kps_undist,
                                   int32_t *tracks, int cap_tracks, int *ntracks_out, int *mergeable_out)
 {
@@ -276,7 +303,12 @@ int mcorb_rig_get_tracks_epipolar(mcorb_rig *r, int slot, int frame, const doubl
     if (frame < 0 || frame >= s->nframes_done || !F) { set_error("bad frame / no fundamental matrices"); return MCORB_E_ARG; }
     const int C = r->rig.ncams;
     std::vector<const mcorb_keypoint *> kp(C);
-    for (int c = 0; c < C; c++) kp[c] = kps_undist && kps_undist[c] ? kps_undist[c] : s->kps[frame * C + c].data();
+    std::vector<const mcorb_keypoint *> def;   // the rig's own set for entries the caller leaves NULL (undistortion set)
+    bool need_def = false;
+    for (int c = 0; c < C; c++) need_def |= !(kps_undist && kps_undist[c]);
+    const int dst = need_def ? r->rig.undist_default(*s, frame * C, C, def) : 0;
+    if (dst < 0) return dst;
+    for (int c = 0; c < C; c++) kp[c] = kps_undist && kps_undist[c] ? kps_undist[c] : dst ? def[c] : s->kps[frame * C + c].data();
     mcorb::EpipolarGate gate{F, kp.data(), r->rig.tab.sigma2};
     std::vector<int32_t> tr;
     int mergeable = 0;

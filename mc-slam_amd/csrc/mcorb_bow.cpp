@@ -443,6 +443,11 @@ extern "C" int mcorb_rig_match_bow_frames(mcorb_rig *r, int slot, int frame0, in
     HIPCHK(hipSetDevice(R.device));
     const int TH_LOW = 75;   // ORBextractor.h:27
     const int img0 = frame0 * C, nimg = nframes * C;
+    std::vector<const mcorb_keypoint *> kdef;   // the rig's own undistorted set for rows the caller leaves NULL (undistortion set)
+    bool kneed = !y_undist;
+    for (int m = 0; m < nimg && !kneed; m++) kneed = !y_undist[img0 + m];
+    const int kdst = kneed ? R.undist_default(*s, img0, nimg, kdef) : 0;
+    if (kdst < 0) return kdst;
     if ((int)s->bow.size() < R.max_frames) { s->bow.resize(R.max_frames); s->bow_ok.assign(R.max_frames, 0); }
 
     static const bool prof = getenv("MCORB_HOST_PROF") != nullptr;
@@ -489,7 +494,8 @@ extern "C" int mcorb_rig_match_bow_frames(mcorb_rig *r, int slot, int frame0, in
             // image_kps_undist[c][k].pt.y (:708-716): the caller's undistorted rows, or the raw ones (RECTIFY / zero distortion)
             const std::vector<mcorb_keypoint> &K = s->kps[img0 + m];
             const float *yu = y_undist ? y_undist[img0 + m] : nullptr;
-            for (int k = 0; k < n; k++) h_yv[(size_t)m * kcap + k] = yu ? yu[k] : K[k].y;
+            const mcorb_keypoint *ku = kdst ? kdef[m] : K.data();
+            for (int k = 0; k < n; k++) h_yv[(size_t)m * kcap + k] = yu ? yu[k] : ku[k].y;
         }
         for (int c = 0; c < C; c++)
             for (const FvRun &e : F.fv[c]) F.slots.push_back(e.node);

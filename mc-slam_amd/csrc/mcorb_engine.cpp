@@ -412,6 +412,8 @@ int Rig::init(const mcorb_params &p, int ncams_, int W_, int H_, int max_frames_
     params = p;
     ncams = ncams_; W = W_; H = H_; max_frames = max_frames_;
     max_images = ncams * max_frames;
+    undist_cams.assign(ncams, UndistCam{});
+    undist_set.assign(ncams, 0);
     npp = ncams * (ncams - 1) / 2;
     device = p.device_id;
     HIPCHK(hipSetDevice(device));
@@ -628,6 +630,9 @@ Rig::~Rig()
         (void)hipHostFree(s->h_stage);
         (void)hipHostFree(s->h_desc); (void)hipHostFree(s->h_angles);
         (void)hipFree(s->d_selval); (void)hipFree(s->d_selcnt); (void)hipFree(s->d_res); (void)hipHostFree(s->h_res); (void)hipHostFree(s->h_sig);
+        (void)hipFree(s->d_undist); (void)hipHostFree(s->h_undist);
+        if (s->ev_u0) (void)hipEventDestroy(s->ev_u0);
+        if (s->ev_u1) (void)hipEventDestroy(s->ev_u1);
         if (s->ev_s) (void)hipEventDestroy(s->ev_s);
         if (s->ev_g) (void)hipEventDestroy(s->ev_g);
         if (s->graph_exec) (void)hipGraphExecDestroy(s->graph_exec);
@@ -646,6 +651,7 @@ Rig::~Rig()
     if (d_taps) (void)hipFree(d_taps);
     if (d_lut) (void)hipFree(d_lut);
     if (d_fasttab) (void)hipFree(d_fasttab);
+    if (d_undist_cams) (void)hipFree(d_undist_cams);
 }
 
 // An upload into a slot whose job is still running would overwrite the staging buffer and level 0 between the job's
@@ -763,6 +769,7 @@ int Rig::submit(int slot, const Job &job)
     if (s.busy) { set_error("slot busy"); return MCORB_E_STATE; }
     s.job = job;
     s.busy = true;
+    s.submitted = true;
     s.status = MCORB_OK;
     lk.unlock();
     s.cv.notify_all();
@@ -775,6 +782,7 @@ int Rig::wait(int slot)
     Slot &s = *slots[slot];
     std::unique_lock<std::mutex> lk(s.m);
     s.cv.wait(lk, [&s] { return !s.busy; });
+    s.submitted = false;
     if (s.status != MCORB_OK) set_error(s.err);
     return s.status;
 }
@@ -895,6 +903,7 @@ int Rig::run_extract_phaseA(Slot &s, const Job &j)
 {
     if (j.nimg < 1 || j.nimg > max_images) { set_error("extract: bad image count"); return MCORB_E_ARG; }
     s.invalidate_bow();   // tracks / BoW vectors of the previous batch index keypoints that are about to disappear
+    undist_job_start(s);
     // A single rig frame (how MC-SLAM calls, mc_slam_app.cpp:564-572) is launch- and hand-off-bound: ~25 runtime calls and three
     // small copies around 250 us of kernels.  For small batches the three copies go: k_compact writes its tables straight into the
     // host-mapped h_tbl, the describe / k-NN kernels read the control block from host-mapped h_ctrl, k_describe_fused writes the
@@ -1044,8 +1053,13 @@ int Rig::run_select_and_describe(Slot &s, const Job &j, bool then_match)
         HIPCHK(hipEventRecord(s.ev[5], s.st));
         launch_describe(s.st, s.d_pyr, nullptr, geom, s.h_sel, s.h_nsel, 0, s.d_desc, s.d_angles, nimg, s.h_desc);
         HIPCHK(hipEventRecord(s.ev[6], s.st));
+        if (undist_on) {   // beside the descriptors and the matcher, from the host-mapped list, into host-mapped memory
+            HIPCHK(hipStreamWaitEvent(s.st_dma, s.ev[5], 0));
+            TRY(enqueue_undistort(s, s.h_sel, s.h_nsel, nimg, true));
+        }
         if (then_match) TRY(enqueue_match(s, j, true));
         HIPCHK(hipGetLastError());
+        if (undist_on) HIPCHK(hipStreamWaitEvent(s.st, s.ev_u1, 0));
         HIPCHK(hipEventRecord(s.ev[10], s.st));
         LatProf::mark(4);
         HIPCHK(wait_event(s.ev[10]));
@@ -1085,6 +1099,7 @@ int Rig::run_select_and_describe(Slot &s, const Job &j, bool then_match)
     else launch_copy_to_host(s.st_dma, s.d_desc, s.h_desc, (size_t)nimg * geom.kcap * 32);
     if (params.orientation)
         HIPCHK(hipMemcpyAsync(s.h_angles, s.d_angles, (size_t)nimg * geom.kcap * sizeof(float), hipMemcpyDeviceToHost, s.st_dma));
+    if (undist_on) TRY(enqueue_undistort(s, s.d_sel, s.d_nsel, nimg, false));   // behind the result copies: the side stream's last work
     if (then_match && !d2h_late && !d2h_mid) TRY(enqueue_match(s, j, true));
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(s.ev[10], s.st));
@@ -1145,6 +1160,11 @@ int Rig::enqueue_gpu_job(Slot &s, const Job &j, bool then_match)
                         reinterpret_cast<int *>(s.d_res + s.res_mono_off), d_flags, nimg);
     if (ev_on) HIPCHK(hipEventRecord(s.ev_s, s.st));
     if (ev_on) HIPCHK(hipEventRecord(s.ev[3], s.st));
+    if (small && undist_on) {   // fork: k_undistort runs on the side stream beside the descriptors and the matcher (joined below)
+        HIPCHK(hipEventRecord(s.ev_u0, s.st));
+        HIPCHK(hipStreamWaitEvent(s.st_dma, s.ev_u0, 0));
+        TRY(enqueue_undistort(s, s.d_sel, s.d_nsel, nimg, true));
+    }
     if (blur_planes) launch_blur(s.st, s.d_pyr, s.d_blur, geom, nimg);
     if (ev_on) HIPCHK(hipEventRecord(s.ev[4], s.st));
     if (ev_on) HIPCHK(hipEventRecord(s.ev[5], s.st));
@@ -1154,6 +1174,7 @@ int Rig::enqueue_gpu_job(Slot &s, const Job &j, bool then_match)
     if (small) {
         if (then_match) TRY(enqueue_match(s, j, true));
         HIPCHK(hipGetLastError());
+        if (undist_on) HIPCHK(hipStreamWaitEvent(s.st, s.ev_u1, 0));   // join
         if (ev_on) HIPCHK(hipEventRecord(s.ev[11], s.st));
         return MCORB_OK;
     }
@@ -1167,10 +1188,97 @@ int Rig::enqueue_gpu_job(Slot &s, const Job &j, bool then_match)
     HIPCHK(hipMemcpyAsync(s.h_res, s.d_res, s.res_resp_off + (size_t)nimg * geom.kcap, hipMemcpyDeviceToHost, s.st_dma));
     if (params.orientation)
         HIPCHK(hipMemcpyAsync(s.h_angles, s.d_angles, (size_t)nimg * geom.kcap * sizeof(float), hipMemcpyDeviceToHost, s.st_dma));
+    if (undist_on) TRY(enqueue_undistort(s, s.d_sel, s.d_nsel, nimg, false));   // behind the result copies: the side stream's last work
     if (then_match) TRY(enqueue_match(s, j, true));
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(s.ev[11], s.st_dma));
     return MCORB_OK;
+}
+
+// ---------------------------------------------------------------------------
+// UndistortKeyPoints (MultiCameraFrame.cpp:300-347) inside the job.  Nothing of this runs, is allocated or is captured while no
+// camera has undistortion set (undist_on): such a job is exactly the job without the feature.
+// ---------------------------------------------------------------------------
+void Rig::undist_job_start(Slot &s)
+{
+    s.undist_job = undist_on;
+    s.undist_gen = undist_gen;
+    std::fill(s.kps_undist_ok.begin(), s.kps_undist_ok.end(), (uint8_t)0);
+}
+
+// on the side stream, behind whatever the caller ordered it after; small batches (host_out) write the host-mapped points
+// directly and record ev_u1 for the caller's join, the others copy them back behind the kernel
+int Rig::enqueue_undistort(Slot &s, const uint32_t *sel, const int *nsel, int nimg, bool host_out)
+{
+    launch_undistort(s.st_dma, sel, nsel, geom.kcap, nimg, ncams, d_undist_cams, tab.scale, tab.nlevels, host_out ? s.h_undist : s.d_undist);
+    if (host_out) HIPCHK(hipEventRecord(s.ev_u1, s.st_dma));
+    else HIPCHK(hipMemcpyAsync(s.h_undist, s.d_undist, (size_t)nimg * geom.kcap * sizeof(float2), hipMemcpyDeviceToHost, s.st_dma));
+    return MCORB_OK;
+}
+
+int Rig::set_undistortion(int cam, const double *K, const double *dist, int ncoeffs)
+{
+    if (cam < 0 || cam >= ncams) { set_error("set_undistortion: camera out of range"); return MCORB_E_ARG; }
+    const bool clear = !dist || ncoeffs == 0;
+    UndistCam c = {};
+    if (!clear) {
+        if (!K) { set_error("set_undistortion: no camera matrix"); return MCORB_E_ARG; }
+        if (undist_prepare(K, dist, ncoeffs, c) != 0) { set_error("set_undistortion: 4, 5, 8 or 12 coefficients (the tilt model is not supported)"); return MCORB_E_ARG; }
+        for (double f : {K[0], K[4], c.K[0], c.K[4]})
+            if (!std::isfinite(f) || f == 0.) { set_error("set_undistortion: fx / fy must be finite and non-zero"); return MCORB_E_ARG; }
+    }
+    // no job of any slot may be in flight, or be waiting to be waited for: every slot stays locked until the tables are in place
+    std::vector<std::unique_lock<std::mutex>> locks;
+    for (Slot *sp : slots) {
+        locks.emplace_back(sp->m);
+        if (sp->busy || sp->submitted) { set_error("set_undistortion: a submitted job has not been waited for"); return MCORB_E_STATE; }
+    }
+    HIPCHK(hipSetDevice(device));
+    if (!clear && !d_undist_cams) {   // first set call: the device table and every slot's buffers and events
+        HIPCHK(hipMalloc((void **)&d_undist_cams, (size_t)ncams * sizeof(UndistCam)));
+        for (Slot *sp : slots) {
+            HIPCHK(hipMalloc((void **)&sp->d_undist, (size_t)max_images * geom.kcap * sizeof(float2)));
+            HIPCHK(hipHostMalloc((void **)&sp->h_undist, (size_t)max_images * geom.kcap * sizeof(float2), hipHostMallocMapped | hipHostMallocPortable));
+            HIPCHK(hipEventCreateWithFlags(&sp->ev_u0, hipEventDisableTiming));
+            HIPCHK(hipEventCreateWithFlags(&sp->ev_u1, hipEventDisableTiming));
+            sp->kps_undist.assign(max_images, {});
+            sp->kps_undist_ok.assign(max_images, 0);
+        }
+    }
+    undist_cams[cam] = c;
+    undist_set[cam] = clear ? 0 : 1;
+    undist_on = std::any_of(undist_set.begin(), undist_set.end(), [](uint8_t v) { return v != 0; });
+    if (d_undist_cams) HIPCHK(hipMemcpy(d_undist_cams, undist_cams.data(), (size_t)ncams * sizeof(UndistCam), hipMemcpyHostToDevice));
+    undist_gen++;
+    return MCORB_OK;
+}
+
+int Rig::undist_records(Slot &s, int m0, int n, std::vector<const mcorb_keypoint *> &out)
+{
+    if (m0 < 0 || n < 0 || m0 + n > s.nimg_done) { set_error("undistorted keypoints: image index out of range"); return MCORB_E_ARG; }
+    if (s.undist_gen != undist_gen) { set_error("undistorted keypoints: image not extracted since the last mcorb_rig_set_undistortion"); return MCORB_E_STATE; }
+    std::lock_guard<std::mutex> lk(s.undist_m);
+    out.resize((size_t)n);
+    for (int i = 0; i < n; i++) {
+        const int m = m0 + i;
+        if (!s.undist_job) { out[i] = s.kps[m].data(); continue; }
+        if (!s.kps_undist_ok[m]) {   // the keypoint records with pt replaced (:336-344)
+            std::vector<mcorb_keypoint> &U = s.kps_undist[m];
+            U = s.kps[m];
+            const float2 *p = s.h_undist + (size_t)m * geom.kcap;
+            for (size_t k = 0; k < U.size(); k++) { U[k].x = p[k].x; U[k].y = p[k].y; }
+            s.kps_undist_ok[m] = 1;
+        }
+        out[i] = s.kps_undist[m].data();
+    }
+    return MCORB_OK;
+}
+
+int Rig::undist_default(Slot &s, int m0, int n, std::vector<const mcorb_keypoint *> &out)
+{
+    if (!undist_on) return 0;
+    const int st = undist_records(s, m0, n, out);
+    return st == MCORB_OK ? 1 : st;
 }
 
 // MCORB_SELECT_GPU: the whole job -- pyramid, FAST, compaction, selection, assembly, descriptors, matching -- is enqueued in one go;
@@ -1199,6 +1307,7 @@ int Rig::run_gpu_selected(Slot &s, const Job &j, bool then_match)
     if (j.nimg < 1 || j.nimg > max_images) { set_error("extract: bad image count"); return MCORB_E_ARG; }
     const int nimg = j.nimg;
     s.invalidate_bow();
+    undist_job_start(s);
     s.small_job = false;
     s.h_overflow[0] = 0;
     s.nimg_done = nimg;
@@ -1279,7 +1388,7 @@ int Rig::run_gpu_selected(Slot &s, const Job &j, bool then_match)
         ~GpuTurn() { done(); }
     } turn(*this);
     if (graphed) {
-        const Slot::GraphKey key{nimg, then_match ? 1 : 0, j.nframes, j.lap0, j.lap1, j.dist_thresh, j.ratio};
+        const Slot::GraphKey key{nimg, then_match ? 1 : 0, j.nframes, j.lap0, j.lap1, j.dist_thresh, j.ratio, undist_on ? 1 : 0};
         if (!s.graph_exec || memcmp(&key, &s.graph_key, sizeof(key)) != 0) {
             if (s.graph_exec) { (void)hipGraphExecDestroy(s.graph_exec); s.graph_exec = nullptr; }
             hipGraph_t graph = nullptr;

@@ -167,7 +167,7 @@ struct Slot {
     int fallbacks = 0;         // jobs of this slot the host stage had to redo (a tree below the bucketing depth)
     hipEvent_t ev_s = nullptr; // k_select + k_assemble finished
     hipEvent_t ev_g = nullptr; // in front of a replayed job graph
-    struct GraphKey { int nimg, match, nframes, lap0, lap1; float dist_thresh, ratio; };
+    struct GraphKey { int nimg, match, nframes, lap0, lap1; float dist_thresh, ratio; int undist; };
     hipGraphExec_t graph_exec = nullptr;   // the captured job (run_gpu_selected), valid for graph_key
     GraphKey graph_key = {};
     unsigned job_counter = 0;
@@ -196,6 +196,18 @@ struct Slot {
         std::fill(bowvec_ok.begin(), bowvec_ok.end(), (uint8_t)0);
     }
     float timing[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    // UndistortKeyPoints (mcorb_rig_set_undistortion): k_undistort's points of the images in the slot, [image][kcap] (d_ device,
+    // h_ host-mapped pinned; both allocated at the rig's first set call, never while no camera has undistortion set); a fork / join
+    // pair of events for small batches, whose kernel runs beside the descriptors and the matcher on the side stream
+    float2 *d_undist = nullptr, *h_undist = nullptr;
+    hipEvent_t ev_u0 = nullptr, ev_u1 = nullptr;
+    bool undist_job = false;      // the images in the slot were extracted with k_undistort (some camera had undistortion set)
+    unsigned undist_gen = 0;      // Rig::undist_gen when they were extracted
+    bool submitted = false;       // a job was submitted and not yet waited for (mcorb_rig_set_undistortion refuses then)
+    // image_kps_undist of the images, built on first read from kps and h_undist (Rig::undist_records)
+    std::vector<std::vector<mcorb_keypoint>> kps_undist;
+    std::vector<uint8_t> kps_undist_ok;
+    std::mutex undist_m;
     std::vector<int> match_sets, match_counts;   // per (frame, cam) of the last match: set index, descriptor count
     bool match_external = false;
     bool small_job = false;   // the running job is a small batch: tables, control block and descriptors go through host-mapped memory, no copies
@@ -262,6 +274,21 @@ public:
     std::vector<SelectScratch *> scratch;   // one per worker
 
     void merge_tracks(Slot &s, int f, const EpipolarGate *gate, std::vector<int32_t> &tr, int &mergeable_out) const;
+
+    // UndistortKeyPoints (MultiCameraFrame.cpp:300-347) on the device, inside the job: per camera the host's table (mode 0 for
+    // cameras not set), its device copy k_undistort reads (graph replays included), and which cameras are set at all
+    std::vector<UndistCam> undist_cams;
+    std::vector<uint8_t> undist_set;
+    UndistCam *d_undist_cams = nullptr;
+    bool undist_on = false;     // some camera is set: jobs run k_undistort; otherwise a job is exactly what it is without the feature
+    unsigned undist_gen = 0;    // set calls so far (images extracted before the last one have no undistorted set)
+    int set_undistortion(int cam, const double *K, const double *dist, int ncoeffs);
+    // the slot's image_kps_undist of images [m0, m0 + n): MCORB_E_STATE for images not extracted since the last set call; the
+    // records are the raw ones when the job ran with nothing set
+    int undist_records(Slot &s, int m0, int n, std::vector<const mcorb_keypoint *> &out);
+    // the set a consumer reads when the caller passes none: 0 = nothing set (the raw keypoints, as before), 1 = `out` holds the
+    // rig's own set, < 0 = error (images extracted before the last set call)
+    int undist_default(Slot &s, int m0, int n, std::vector<const mcorb_keypoint *> &out);
     int max_pairs() const { return std::max(1, npp * max_frames); }
 
 private:
@@ -273,6 +300,10 @@ private:
     int run_select_and_describe(Slot &s, const Job &j, bool then_match);
     int run_gpu_selected(Slot &s, const Job &j, bool then_match);   // the whole job as one submission (gpu_select)
     int enqueue_gpu_job(Slot &s, const Job &j, bool then_match);
+    // k_undistort of the job's images on the side stream st_dma: sel / nsel in device or host-mapped memory, out in device or
+    // host-mapped memory; copy_back: the D2H copy of the points follows on the same stream
+    int enqueue_undistort(Slot &s, const uint32_t *sel, const int *nsel, int nimg, bool host_out);
+    void undist_job_start(Slot &s);
     int prepare_match(Slot &s, const Job &j);
     int enqueue_match(Slot &s, const Job &j, bool ctrl_on_device);
     int finish_match(Slot &s, const Job &j);

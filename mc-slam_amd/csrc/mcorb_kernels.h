@@ -4,6 +4,7 @@
 #include <vector>
 #include "mcorb_common.h"
 #include "mcorb_signal.h"
+#include "mcorb_undistort.h"
 
 namespace mcorb {
 
@@ -81,6 +82,12 @@ void launch_assemble(hipStream_t st, const uint32_t *sel_val, const int *sel_cnt
 // (the signal word of an image, k_assemble -> host: mcorb_signal.h)
 // test hook: std::sort's permutation of n 64-bit entries (upper halves compared) by one wave (wave_std_sort)
 hipError_t sort_selftest(const uint64_t *in_dev, int n, uint64_t *out_dev);
+
+// UndistortKeyPoints of the selected keypoints of nimg images (k_undistort, mcorb_undistort.h): sel / nsel as the descriptor
+// kernel reads them, cams: ncams per-camera tables in device memory (image m is camera m % ncams), scale: the level scale factors;
+// out[m * kcap + k] = the undistorted pt of keypoint k of image m (device or host-mapped memory)
+void launch_undistort(hipStream_t st, const uint32_t *sel, const int *nsel, int kcap, int nimg, int ncams, const UndistCam *cams,
+                      const float *scale, int nlevels, float2 *out);
 
 // device -> host-mapped pinned memory with a small grid (instead of the runtime's blit kernel); sizes rounded up to 16 bytes
 void launch_copy_to_host(hipStream_t st, const void *src_dev, void *dst_host_mapped, size_t bytes);

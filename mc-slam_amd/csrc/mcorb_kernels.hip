@@ -12,6 +12,7 @@
 
 #include "mcorb_common.h"
 #include "mcorb_kernels.h"
+#include "mcorb_undistort.h"
 #include <stdlib.h>
 #include <string.h>
 #include <vector>
@@ -1949,6 +1950,37 @@ void launch_copy_to_host(hipStream_t st, const void *src_dev, void *dst_host_map
     const int wgs = (int)((n16 + 255) / 256 < cap ? (n16 + 255) / 256 : cap);
     hipLaunchKernelGGL(k_copy_to_host, dim3(wgs), dim3(256), 0, st, reinterpret_cast<const uint4 *>(src_dev),
                        reinterpret_cast<uint4 *>(dst_host_mapped), n16);
+}
+
+// ---------------------------------------------------------------------------
+// MultiCameraFrame::UndistortKeyPoints (MultiCameraFrame.cpp:300-347): cv::undistortPoints of every selected keypoint, one lane
+// per keypoint (mcorb_undistort.h).  pt is rebuilt from the packed selection exactly as the host's keypoint records are
+// ((float)x, times the float scale factor above level 0); image m belongs to camera m % ncams.  fp64 throughout, no contraction
+// (-ffp-contract=off): bit-equal to the host restatement.
+// ---------------------------------------------------------------------------
+struct UndistScales { float s[kMaxLevels]; };
+
+__global__ __launch_bounds__(256) void k_undistort(const uint32_t *__restrict__ sel, const int *__restrict__ nsel, int kcap, int ncams,
+                                                   const UndistCam *__restrict__ cams, UndistScales sc, float2 *__restrict__ out)
+{
+    const int m = blockIdx.y, k = blockIdx.x * 256 + threadIdx.x;
+    const int n = min(nsel[m], kcap);
+    if (k >= n) return;
+    const uint32_t v = sel[(size_t)m * kcap + k];
+    const int l = (int)(v >> 28), yl = (int)((v >> 14) & 0x3fffu), xl = (int)(v & 0x3fffu);
+    float x = (float)xl, y = (float)yl;
+    if (l != 0) { x *= sc.s[l]; y *= sc.s[l]; }
+    float ox, oy;
+    undistort_point(cams[m % ncams], x, y, ox, oy);
+    out[(size_t)m * kcap + k] = make_float2(ox, oy);
+}
+
+void launch_undistort(hipStream_t st, const uint32_t *sel, const int *nsel, int kcap, int nimg, int ncams, const UndistCam *cams,
+                      const float *scale, int nlevels, float2 *out)
+{
+    UndistScales sc = {};
+    for (int l = 0; l < nlevels && l < kMaxLevels; l++) sc.s[l] = scale[l];
+    hipLaunchKernelGGL(k_undistort, dim3((kcap + 255) / 256, nimg), dim3(256), 0, st, sel, nsel, kcap, ncams, cams, sc, out);
 }
 
 // ---------------------------------------------------------------------------

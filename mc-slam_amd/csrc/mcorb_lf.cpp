@@ -385,6 +385,24 @@ static int lf_one_frame(Rig &R, Slot *s, int slot, int frame, const int32_t *tra
     return MCORB_OK;
 }
 
+// kps_undist of frames [frame0, frame0 + nframes) with the rig's own undistorted set filled in where the caller passes NULL (as a
+// whole or per entry) and some camera has undistortion set: 1 = `out` holds the merged pointers, 0 = use the caller's (nothing
+// set, or every entry explicit), < 0 = error.  The frame range itself is checked by the caller's per-frame code.
+static int undist_inputs(Rig &R, Slot *s, int frame0, int nframes, const mcorb_keypoint *const *kps_undist,
+                         std::vector<const mcorb_keypoint *> &out)
+{
+    const int C = R.ncams, n = nframes * C;
+    bool need = !kps_undist;
+    for (int i = 0; i < n && !need; i++) need = !kps_undist[i];
+    if (!need || !R.undist_on || frame0 < 0 || (frame0 + nframes) * C > s->nimg_done) return 0;
+    std::vector<const mcorb_keypoint *> def;
+    const int st = R.undist_default(*s, frame0 * C, n, def);
+    if (st <= 0) return st;
+    out.resize((size_t)n);
+    for (int i = 0; i < n; i++) out[i] = kps_undist && kps_undist[i] ? kps_undist[i] : def[i];
+    return 1;
+}
+
 extern "C" int mcorb_rig_obtain_lf_features(mcorb_rig *r, int slot, int frame, const int32_t *tracks, int ntracks,
                                             const uint32_t *words, const mcorb_camera *cams, const float *const *seg_masks,
                                             int seg_stride, const mcorb_keypoint *const *kps_undist, int total_feats,
@@ -399,8 +417,11 @@ extern "C" int mcorb_rig_obtain_lf_features(mcorb_rig *r, int slot, int frame, c
         std::lock_guard<std::mutex> lk(s->m);
         if (s->busy) { set_error("slot busy"); return MCORB_E_STATE; }
     }
-    return lf_one_frame(R, s, slot, frame, tracks, ntracks, words, cams, seg_masks, seg_stride, kps_undist, total_feats, out, cap, n_out,
-                        intramatch_size_out, mono_size_out, words_fil, cap_words, nwords_fil_out, true);
+    std::vector<const mcorb_keypoint *> ku;
+    const int kst = undist_inputs(R, s, frame, 1, kps_undist, ku);
+    if (kst < 0) return kst;
+    return lf_one_frame(R, s, slot, frame, tracks, ntracks, words, cams, seg_masks, seg_stride, kst ? ku.data() : kps_undist, total_feats, out,
+                        cap, n_out, intramatch_size_out, mono_size_out, words_fil, cap_words, nwords_fil_out, true);
 }
 
 // All frames [frame0, frame0 + nframes) of a slot in one call, one worker-pool task per frame (the per-frame call is 70 x the
@@ -427,6 +448,10 @@ extern "C" int mcorb_rig_obtain_lf_features_frames(mcorb_rig *r, int slot, int f
         if (s->busy) { set_error("slot busy"); return MCORB_E_STATE; }
     }
     const int C = R.ncams;
+    std::vector<const mcorb_keypoint *> ku;
+    const int kst = undist_inputs(R, s, frame0, nframes, kps_undist, ku);
+    if (kst < 0) return kst;
+    if (kst) kps_undist = ku.data();
     std::vector<size_t> off((size_t)nframes + 1, 0);
     for (int f = 0; f < nframes; f++) {
         if (ntracks[f] < 0) { set_error("obtain_lf_features_frames: negative track count"); return MCORB_E_ARG; }
