@@ -379,6 +379,25 @@ int mcorb_rig_match_bow_frames(mcorb_rig *r, int slot, int frame0, int nframes, 
 int mcorb_rig_get_bow_tracks(mcorb_rig *r, int slot, int frame, int32_t *tracks, int32_t *n_rays, int cap_tracks,
                              int *ntracks_out, uint32_t *words, int cap_words, int *nwords_out);
 
+/* Bind a vocabulary to the rig: every later extraction job (extract, extract_submit, process, process_submit; all slots) also runs
+ * the requested BoW stages on the GPU inside the same submission, with no host round trip between the descent and the match table:
+ *   MCORB_BOW_TRANSFORM  transform(desc, BowVector, FeatureVector, levelsup) of every image (MultiCameraFrame.cpp:257); read with
+ *                        mcorb_rig_get_transform for every image of the job.
+ *   MCORB_BOW_MATCH      also computeIntraMatches(matches, words_) of every frame (:586-943; implies the transform); read with
+ *                        mcorb_rig_get_bow_tracks for every frame of the job.  The |dy| < 50 gate reads the rig's own undistorted
+ *                        rows when undistortion is set (mcorb_rig_set_undistortion), else the raw keypoint rows; a job whose image
+ *                        count is not a whole number of frames is refused (MCORB_E_ARG) at submit.
+ * The results equal the explicit calls' (mcorb_rig_transform_images, mcorb_rig_match_bow_frames with y_undist = NULL) bit for bit;
+ * a later explicit call still overwrites them.  v = NULL or flags = 0 unbinds: a job is then exactly what it is without this call.
+ * The vocabulary must live on the rig's device and outlive the binding.  MCORB_E_ARG: another device, levelsup < 0, unknown flags,
+ * or a rig whose kcap (mcorb_rig_kcap) exceeds MCORB_BOW_MAX_KCAP -- the per-image fold sorts an image's keys in LDS; kcap is
+ * nfeatures + 4 x nlevels + 48 rounded up to 64, so nfeatures = 4000 at 8 levels fits.  MCORB_E_STATE while a submitted job has
+ * not been waited for. */
+#define MCORB_BOW_TRANSFORM 1
+#define MCORB_BOW_MATCH 2
+#define MCORB_BOW_MAX_KCAP 4096
+int mcorb_rig_set_vocabulary(mcorb_rig *r, mcorb_vocab *v, int levelsup, double max_neighbor_ratio, int flags);
+
 /* ------------------------------------------------------------------------- */
 /* FrontEnd::obtainLfFeatures (MCSlam/src/FrontEnd.cpp:213-593): the consumer  */
 /* of the IntraMatch tracks.  Host code.                     */

@@ -277,7 +277,36 @@ public:
                 image_kps_undist[c].resize(n);
             }
         }
+        rows_replaced_ = false;
+        if (bound_voc_) {
+            // orb_vocabulary->transform(vec_desc, bowVec, featVec, 4) per camera (:252-261): made by the extraction job
+            BoW_vecs.assign(num_cams_, {});
+            BoW_feats.assign(num_cams_, {});
+            for (int c = 0; c < num_cams_; c++) {
+                const int n = (int)image_kps[c].size();
+                std::vector<uint32_t> ids(n + 1), nodes(n + 1);
+                std::vector<double> vals(n + 1);
+                std::vector<int32_t> offs(n + 2), feats(n + 1);
+                int nb = 0, nf = 0;
+                check(mcorb_rig_get_transform(rig_, 0, c, ids.data(), vals.data(), n + 1, &nb, nodes.data(), offs.data(), n + 1, &nf,
+                                              feats.data(), n + 1), "mcorb_rig_get_transform");
+                ORBVocabulary::fill(ids, vals, nb, nodes, offs, feats, nf, BoW_vecs[c], BoW_feats[c]);
+            }
+        }
         matched_ = false;
+    }
+    // orb_vocabulary (MultiCameraFrame.cpp:252-261), once at init: from then on extractFeaturesParallel() fills BoW_vecs / BoW_feats
+    // and the extraction job also makes computeIntraMatches(matches, words_), which the BoW-guided computeIntraMatches below reads
+    // when it is called with this vocabulary, levelsup and ratio and setUndistorted() has not replaced the rows.  nullptr unbinds;
+    // the vocabulary must outlive the binding.
+    void setVocabulary(const ORBVocabulary *voc, int levelsup = 4, double max_neighbor_ratio = 0.85)
+    {
+        check(mcorb_rig_set_vocabulary(rig_, voc ? voc->handle() : nullptr, levelsup, max_neighbor_ratio, voc ? MCORB_BOW_MATCH : 0),
+              "mcorb_rig_set_vocabulary");
+        bound_voc_ = voc;
+        bound_levelsup_ = levelsup;
+        bound_ratio_ = max_neighbor_ratio;
+        if (!voc) { BoW_vecs.clear(); BoW_feats.clear(); }
     }
     // camconfig_.K_mats_[cam] (row-major 3x3) and dist_coeffs_[cam] (n = 4, 5, 8 or 12 values; NULL or 0 clears), CV_64F.  Call
     // once at init, in place of the host's cv::undistortPoints: from then on extractFeaturesParallel() fills image_kps_undist as
@@ -366,6 +395,12 @@ public:
         std::vector<int32_t> tr((size_t)cap * num_cams_), rays(cap);
         std::vector<uint32_t> w(cap);
         int n = 0, nw = 0;
+        if (&voc == bound_voc_ && levelsup == bound_levelsup_ && max_neighbor_ratio == bound_ratio_ && !rows_replaced_) {
+            // made by the extraction job (setVocabulary)
+            check(mcorb_rig_get_bow_tracks(rig_, 0, 0, tr.data(), rays.data(), cap, &n, w.data(), cap, &nw), "mcorb_rig_get_bow_tracks");
+            fill_matches(tr, rays, n, w, nw, matches, words_);
+            return;
+        }
         // the |dy| < 50 gate reads image_kps_undist[cam][k].pt.y (:708-716)
         std::vector<std::vector<float>> yu(num_cams_);
         std::vector<const float *> yp(num_cams_, nullptr);
@@ -381,13 +416,7 @@ public:
                 if (!yp[c]) { for (const mcorb_keypoint &k : image_kps[c]) yu[c].push_back(k.y); yp[c] = yu[c].data(); }
         check(mcorb_rig_match_bow_frames(rig_, 0, 0, 1, voc.handle(), levelsup, max_neighbor_ratio, any ? yp.data() : nullptr), "mcorb_rig_match_bow_frames");
         check(mcorb_rig_get_bow_tracks(rig_, 0, 0, tr.data(), rays.data(), cap, &n, w.data(), cap, &nw), "mcorb_rig_get_bow_tracks");
-        matches.clear();
-        matches.resize(n);
-        for (int m = 0; m < n; m++) {
-            for (int c = 0; c < num_cams_; c++) matches[m].matchIndex[c] = tr[(size_t)m * num_cams_ + c];
-            matches[m].n_rays = rays[m];
-        }
-        words_.insert(words_.end(), w.begin(), w.begin() + nw);
+        fill_matches(tr, rays, n, w, nw, matches, words_);
     }
     // orb_vocabulary->transform(image_descriptors[cam], BoW_vecs[cam], BoW_feats[cam], levelsup) (MultiCameraFrame.cpp:257),
     // reading the descriptors where extraction left them on the device
@@ -407,7 +436,7 @@ public:
     // BruteForceMatch's returned keypoints, the epipolar check and the BoW-guided matcher's row gate.  Not needed when RECTIFY is
     // on or the distortion is zero: the reference then copies image_kps, which is the default here.  Call after
     // extractFeaturesParallel(); it is dropped by the next extraction.
-    void setUndistorted(const std::vector<std::vector<mcorb_keypoint>> &kps_undist) { image_kps_undist = kps_undist; }
+    void setUndistorted(const std::vector<std::vector<mcorb_keypoint>> &kps_undist) { image_kps_undist = kps_undist; rows_replaced_ = true; }
     bool undist_ok(int c) const { return (int)image_kps_undist.size() == num_cams_ && image_kps_undist[c].size() == image_kps[c].size() && !image_kps[c].empty(); }
 
     // computeIntraMatches(matches, old) (MultiCameraFrame.cpp:1100-1288)
@@ -439,9 +468,22 @@ public:
     std::vector<std::vector<mcorb_keypoint>> image_kps;
     std::vector<std::vector<uint8_t>> image_descriptors;   // per camera, n x 32
     std::vector<std::vector<mcorb_keypoint>> image_kps_undist;
+    std::vector<ORBVocabulary::BowVector> BoW_vecs;       // per camera, filled by extractFeaturesParallel after setVocabulary
+    std::vector<ORBVocabulary::FeatureVector> BoW_feats;
     int cnt_mergable_matches = 0;
 
 private:
+    void fill_matches(const std::vector<int32_t> &tr, const std::vector<int32_t> &rays, int n, const std::vector<uint32_t> &w, int nw,
+                      std::vector<IntraMatch> &matches, std::vector<unsigned int> &words_) const
+    {
+        matches.clear();
+        matches.resize(n);
+        for (int m = 0; m < n; m++) {
+            for (int c = 0; c < num_cams_; c++) matches[m].matchIndex[c] = tr[(size_t)m * num_cams_ + c];
+            matches[m].n_rays = rays[m];
+        }
+        words_.insert(words_.end(), w.begin(), w.begin() + nw);
+    }
     void ensure_match(float thr, float ratio)
     {
         if (matched_ && thr == thr_ && ratio == ratio_) return;
@@ -454,6 +496,10 @@ private:
     float thr_ = 0, ratio_ = 0;
     std::vector<double> F_pairs_;
     std::vector<int> distorted_;   // per camera: setDistortion gave it coefficients
+    const ORBVocabulary *bound_voc_ = nullptr;   // setVocabulary
+    int bound_levelsup_ = 4;
+    double bound_ratio_ = 0.85;
+    bool rows_replaced_ = false;   // setUndistorted gave the row gate other rows than the job's
 };
 
 }  // namespace mcorb

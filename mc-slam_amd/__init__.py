@@ -151,6 +151,29 @@ class Rig:
         d = np.ascontiguousarray(dist, np.float64).ravel()
         _lib.check(self.L.mcorb_rig_set_undistortion(self.h_rig, cam, K.ctypes.data, d.ctypes.data, d.size))
 
+    # -- transform() and computeIntraMatches(matches, words_) inside every extraction job -------------------------------------
+    def set_vocabulary(self, voc, levelsup=4, match=True, max_neighbor_ratio=0.85):
+        """Bind an ORBVocabulary (None unbinds): every later extraction job also runs transform(desc, BowVector, FeatureVector,
+        levelsup) of every image and, with match, computeIntraMatches(matches, words_) of every frame, on the device in the same
+        submission.  Read them with bow_transforms / bow_tracks.  The vocabulary is kept alive while it is bound."""
+        if voc is None or voc.h is None:
+            _lib.check(self.L.mcorb_rig_set_vocabulary(self.h_rig, None, 0, 0.0, 0))
+            self._bow_voc = None
+            return
+        flags = _lib.BOW_TRANSFORM | (_lib.BOW_MATCH if match else 0)
+        _lib.check(self.L.mcorb_rig_set_vocabulary(self.h_rig, voc.h, levelsup, max_neighbor_ratio, flags))
+        self._bow_voc = voc
+
+    def bow_transforms(self, img0, nimg, slot=0):
+        """the last job's transform() of images [img0, img0 + nimg) -> list of (BowVector, FeatureVector), as
+        ORBVocabulary.transform_rig_images returns them"""
+        return _read_transforms(self, img0, nimg, slot)
+
+    def bow_tracks(self, frame0, nframes, slot=0):
+        """the last job's computeIntraMatches(matches, words_) of frames [frame0, frame0 + nframes) -> list of
+        (tracks, n_rays, words), as ORBVocabulary.match_rig_frames returns them"""
+        return _read_tracks(self, frame0, nframes, slot)
+
     def undistortion_active(self, cam):
         """True if the reference would call cv::undistortPoints for this camera (set, and not passed by its zero test)"""
         v = self.L.mcorb_rig_undistortion_active(self.h_rig, cam)
@@ -558,6 +581,40 @@ class ORBextractor:
         return np.array(mA, np.uint32), np.array(mB, np.uint32), book
 
 
+def _read_transform_lists(fn, n):
+    """one image's BowVector / FeatureVector through a getter of the mcorb_vocab_transform output layout"""
+    cap = max(n, 1)
+    ids, vals = np.zeros(cap, np.uint32), np.zeros(cap, np.float64)
+    nodes, offs, feats = np.zeros(cap, np.uint32), np.zeros(cap + 1, np.int32), np.zeros(cap, np.int32)
+    nb, nf = C.c_int(), C.c_int()
+    _lib.check(fn(ids.ctypes.data, vals.ctypes.data, cap, C.byref(nb), nodes.ctypes.data, offs.ctypes.data, cap, C.byref(nf),
+                  feats.ctypes.data, cap))
+    bow = (ids[:nb.value].copy(), vals[:nb.value].copy())
+    fv = {int(nodes[i]): feats[offs[i]:offs[i + 1]].copy() for i in range(nf.value)}
+    return bow, fv
+
+
+def _read_transforms(rig, img0, nimg, slot):
+    out = []
+    for m in range(img0, img0 + nimg):
+        n = max(rig.L.mcorb_rig_num_keypoints(rig.h_rig, slot, m), 0)
+        out.append(_read_transform_lists(lambda *a, m=m: rig.L.mcorb_rig_get_transform(rig.h_rig, slot, m, *a), n))
+    return out
+
+
+def _read_tracks(rig, frame0, nframes, slot):
+    out, cap = [], rig.kcap * rig.ncams
+    for f in range(frame0, frame0 + nframes):
+        tr = np.full((cap, rig.ncams), -1, np.int32)
+        nr = np.zeros(cap, np.int32)
+        words = np.zeros(cap, np.uint32)
+        nt, nw = C.c_int(), C.c_int()
+        _lib.check(rig.L.mcorb_rig_get_bow_tracks(rig.h_rig, slot, f, tr.ctypes.data, nr.ctypes.data, cap, C.byref(nt),
+                                                  words.ctypes.data, cap, C.byref(nw)))
+        out.append((tr[:nt.value].copy(), nr[:nt.value].copy(), words[:nw.value].copy()))
+    return out
+
+
 class ORBVocabulary:
     """DBoW2::ORBVocabulary (MCSlam/include/MCSlam/ORBVocabulary.h:21-30) as far as this path uses it:
     loadFromTextFile + transform(features, BowVector, FeatureVector, levelsup)."""
@@ -605,15 +662,7 @@ class ORBVocabulary:
         return dict(k=k.value, L=L.value, nodes=nn.value, words=nw.value)
 
     def _call(self, fn, head, n, levelsup):
-        cap = max(n, 1)
-        ids, vals = np.zeros(cap, np.uint32), np.zeros(cap, np.float64)
-        nodes, offs, feats = np.zeros(cap, np.uint32), np.zeros(cap + 1, np.int32), np.zeros(cap, np.int32)
-        nb, nf = C.c_int(), C.c_int()
-        _lib.check(fn(*head, levelsup, ids.ctypes.data, vals.ctypes.data, cap, C.byref(nb), nodes.ctypes.data,
-                      offs.ctypes.data, cap, C.byref(nf), feats.ctypes.data, cap))
-        bow = (ids[:nb.value].copy(), vals[:nb.value].copy())
-        fv = {int(nodes[i]): feats[offs[i]:offs[i + 1]].copy() for i in range(nf.value)}
-        return bow, fv
+        return _read_transform_lists(lambda *a: fn(*head, levelsup, *a), n)
 
     def transform(self, features, levelsup=4):
         """-> BowVector as (word ids ascending, values), FeatureVector as {node id: feature indices}."""
@@ -645,25 +694,12 @@ class ORBVocabulary:
                     arr[i] = a.ctypes.data
             ptrs = arr
         _lib.check(self.L_.mcorb_rig_match_bow_frames(rig.h_rig, slot, frame0, nframes, self.h, levelsup, max_neighbor_ratio, ptrs))
-        out, cap = [], rig.kcap * rig.ncams
-        for f in range(frame0, frame0 + nframes):
-            tr = np.full((cap, rig.ncams), -1, np.int32)
-            nr = np.zeros(cap, np.int32)
-            words = np.zeros(cap, np.uint32)
-            nt, nw = C.c_int(), C.c_int()
-            _lib.check(self.L_.mcorb_rig_get_bow_tracks(rig.h_rig, slot, f, tr.ctypes.data, nr.ctypes.data, cap, C.byref(nt),
-                                                        words.ctypes.data, cap, C.byref(nw)))
-            out.append((tr[:nt.value].copy(), nr[:nt.value].copy(), words[:nw.value].copy()))
-        return out
+        return _read_tracks(rig, frame0, nframes, slot)
 
     def transform_rig_images(self, rig, img0, nimg, slot=0, levelsup=4):
         """transform() of images [img0, img0 + nimg) of a slot in one call -> list of (BowVector, FeatureVector)."""
         _lib.check(self.L_.mcorb_rig_transform_images(rig.h_rig, slot, img0, nimg, self.h, levelsup))
-        out = []
-        for m in range(img0, img0 + nimg):
-            n = max(rig.L.mcorb_rig_num_keypoints(rig.h_rig, slot, m), 0)
-            out.append(self._call(lambda *a, m=m: self.L_.mcorb_rig_get_transform(rig.h_rig, slot, m, *a[1:]), (), n, levelsup))   # (a[0] = levelsup)
-        return out
+        return _read_transforms(rig, img0, nimg, slot)
 
     def transform_rig_image(self, rig, m, slot=0, levelsup=4):
         """transform() of image m's descriptors straight from the rig's HBM buffers (MultiCameraFrame.cpp:257)."""
@@ -750,6 +786,9 @@ class MultiCameraFrame:
         self.image_kps, self.image_kps_undist, self.image_descriptors = [], [], []
         self._matched = False
         self._distorted = False   # setDistortion gave some camera coefficients: extraction fills image_kps_undist from the rig
+        self.BoW_vecs, self.BoW_feats = [], []   # per camera, filled by extractFeaturesParallel once setVocabulary was called
+        self._voc, self._voc_levelsup = None, 4
+        self._rows_replaced = False   # setUndistorted() gave rows other than the rig's: the job's tracks do not apply
 
     def setData(self, img_set, segmap_set=None):
         """setData (MultiCameraFrame.cpp:95-152): accepts the reference's CV_32F [0,1] frames or u8."""
@@ -773,6 +812,11 @@ class MultiCameraFrame:
             self.image_kps_undist = [self.rig.features_undist(c) for c in range(self.num_cams_)]
         else:
             self.image_kps_undist = self.image_kps   # RECTIFY, or zero distortion: UndistortKeyPoints copies (:241-242, :302-305)
+        self._rows_replaced = False
+        if self._voc is not None:   # orb_vocabulary->transform(vec_desc, bowVec, featVec, 4) per camera (:252-261), made by the job
+            tf = self.rig.bow_transforms(0, self.num_cams_)
+            self.BoW_vecs = [bow for bow, _ in tf]
+            self.BoW_feats = [fv for _, fv in tf]
         self._matched = False
 
     extractFeatures = extractFeaturesParallel
@@ -787,6 +831,15 @@ class MultiCameraFrame:
             self.rig.set_undistortion(c, K_mats[c], dist_coeffs[c])
         self._distorted = any(d is not None and len(np.ravel(d)) > 0 for d in dist_coeffs)
 
+    def setVocabulary(self, voc, levelsup=4):
+        """orb_vocabulary (MultiCameraFrame.cpp:252-261): from now on extractFeaturesParallel() fills BoW_vecs[cam] as
+        (word ids, values) and BoW_feats[cam] as {node: feature indices}, and computeIntraMatchesBoW(voc, levelsup=levelsup)
+        reads the tracks the extraction job already made.  None unbinds."""
+        self.rig.set_vocabulary(voc, levelsup=levelsup, match=True)
+        self._voc, self._voc_levelsup = voc, levelsup
+        if voc is None:
+            self.BoW_vecs, self.BoW_feats = [], []
+
     def setUndistorted(self, image_kps_undist):
         """image_kps_undist as UndistortKeyPoints (MultiCameraFrame.cpp:300-347) fills it for a distorted, unrectified rig
         (cv::undistortPoints is the caller's).  Read by BruteForceMatch's returned keypoints, the epipolar check of
@@ -794,6 +847,7 @@ class MultiCameraFrame:
         if len(image_kps_undist) != self.num_cams_ or any(len(u) != len(k) for u, k in zip(image_kps_undist, self.image_kps)):
             raise ValueError("image_kps_undist must hold one entry per extracted keypoint")
         self.image_kps_undist = list(image_kps_undist)
+        self._rows_replaced = True
 
     def _ensure_match(self, dist_thresh, ratio):
         key = (float(dist_thresh), float(ratio))
@@ -812,8 +866,11 @@ class MultiCameraFrame:
     def computeIntraMatchesBoW(self, vocabulary, words_=None, levelsup=4):
         """computeIntraMatches(matches, words_) (MultiCameraFrame.cpp:586-943), the call FrontEnd.cpp:1009 makes.  The
         |dy| < 50 gate reads image_kps_undist (:708-716): set it with setUndistorted() when the rig is not rectified."""
-        yu = [np.ascontiguousarray(k["y"], np.float32) for k in self.image_kps_undist]
-        tr, nr, words = vocabulary.match_rig_frames(self.rig, 0, 1, levelsup=levelsup, y_undist=yu)[0]
+        if vocabulary is self._voc and levelsup == self._voc_levelsup and not self._rows_replaced:
+            tr, nr, words = self.rig.bow_tracks(0, 1)[0]   # made by the extraction job (setVocabulary)
+        else:
+            yu = [np.ascontiguousarray(k["y"], np.float32) for k in self.image_kps_undist]
+            tr, nr, words = vocabulary.match_rig_frames(self.rig, 0, 1, levelsup=levelsup, y_undist=yu)[0]
         if words_ is not None:
             words_.extend(int(w) for w in words)
         out = [IntraMatch(row) for row in tr]

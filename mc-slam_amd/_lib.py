@@ -15,6 +15,7 @@ LIB_PATH = os.path.join(PKG_DIR, "libmcorb.so")
 
 OK, E_EMPTY, E_SIZE, E_CAP, E_ARG, E_HIP, E_NODEVICE, E_STATE, E_OVERFLOW = 0, -1, -2, -3, -4, -5, -6, -7, -8
 ORIENT_NONE, ORIENT_IC_ANGLE = 0, 1
+BOW_TRANSFORM, BOW_MATCH = 1, 2
 MAX_LEVELS, MAX_CAMS = 16, 16
 
 KP_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"),
@@ -126,6 +127,7 @@ SIGNATURES = {
     "mcorb_rig_transform_images": (_i, [_vp, _i, _i, _i, _vp, _i]),
     "mcorb_rig_get_transform": (_i, [_vp, _i, _i, _vp, _vp, _i, _ip, _vp, _vp, _i, _ip, _vp, _i]),
     "mcorb_rig_match_bow_frames": (_i, [_vp, _i, _i, _i, _vp, _i, C.c_double, _vp]),
+    "mcorb_rig_set_vocabulary": (_i, [_vp, _vp, _i, C.c_double, _i]),
     "mcorb_rig_get_bow_tracks": (_i, [_vp, _i, _i, _vp, _vp, _i, _ip, _vp, _i, _ip]),
     "mcorb_rig_obtain_lf_features": (_i, [_vp, _i, _i, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, _i, _ip, _ip, _ip, _vp, _i, _ip]),
     "mcorb_rig_obtain_lf_features_frames": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp]),

@@ -427,6 +427,125 @@ struct FrameTables {                                    // per frame, built on t
 
 static int pair_of(int C, int c1, int c2) { return c1 * C - c1 * (c1 + 1) / 2 + (c2 - c1 - 1); }
 
+// the reference's serial walk over the common nodes of one frame (:647-929) and its track bookkeeping, reading best / second-best from
+// k_bow_best2's table of the frame (tab: npairs x kcap entries); hd: the host's descriptors, image img_base + c of camera c
+static void bow_replay(const FrameTables &F, int C, int kcap, const int4 *tab, const uint8_t *hd, int img_base, double max_neighbor_ratio,
+                       BowFrameOut &out)
+{
+    const int TH_LOW = 75;   // ORBextractor.h:27
+    out.tracks.clear(); out.n_rays.clear(); out.words.clear();
+    if (F.empty) return;
+    std::vector<int> it(C, 0), last(C);
+    for (int c = 0; c < C; c++) last[c] = (int)F.fv[c].size() - 1;   // std::prev(end()): the last node is never visited (reference quirk)
+    std::vector<BowTrack> matches;
+    matches.reserve(10000);   // (:587)
+    int intraMatchInd = 0;
+    auto dist = [&](int ca, int fa, int cb, int fb) {
+        return mcorb_hamming256(hd + ((size_t)(img_base + ca) * kcap + fa) * 32, hd + ((size_t)(img_base + cb) * kcap + fb) * 32);
+    };
+    std::vector<int> selected;
+    std::vector<std::vector<int>> matchedFlags;
+    for (;;) {
+        bool end = true;   // checkItersEnd (:569-575)
+        for (int c = 0; c < C; c++) end = end && F.fv[c][it[c]].node >= F.fv[c][last[c]].node;
+        if (end) break;
+        uint32_t min_val = 0x7ffffffeu;
+        selected.clear();
+        for (int c = 0; c < C; c++) {
+            const uint32_t w = it[c] == last[c] ? 0x7fffffffu : F.fv[c][it[c]].node;
+            if (w < min_val) { min_val = w; selected.clear(); selected.push_back(c); }
+            else if (w == min_val) selected.push_back(c);
+        }
+        matchedFlags.assign(selected.size(), std::vector<int>());
+        for (size_t i = 0; i < selected.size(); i++) matchedFlags[i].assign(F.fv[selected[i]][it[selected[i]]].cnt, -1);
+        if (selected.size() >= 2) {
+            for (int i = 0; i < (int)selected.size() - 1; i++) {
+                const int cam1 = selected[i];
+                const FvRun &run1 = F.fv[cam1][it[cam1]];
+                const int32_t *feat_cam1 = F.feats[cam1].data() + run1.beg;
+                for (int a = 0; a < run1.cnt; a++) {
+                    bool foundMatch = false;
+                    if (matchedFlags[i][a] != -1) continue;
+                    BowTrack temp;
+                    for (int tt = 0; tt < C; tt++) temp.matchIndex[tt] = -1;
+                    temp.matchIndex[cam1] = feat_cam1[a];
+                    temp.n_rays = 1;
+                    matches.push_back(temp);
+                    matchedFlags[i][a] = intraMatchInd;
+                    bool updateOnce = true;
+                    for (int j = i + 1; j < (int)selected.size(); j++) {
+                        const int cam2 = selected[j];
+                        const int32_t *feat_cam2 = F.feats[cam2].data() + F.fv[cam2][it[cam2]].beg;
+                        const int4 t = tab[(size_t)pair_of(C, cam1, cam2) * kcap + feat_cam1[a]];
+                        const int best_j_now = t.x;
+                        const double best_dist_1 = t.x < 0 ? 1e9 : (double)t.y;
+                        const double best_dist_2 = t.z == 0x7fffffff ? 1e9 : (double)t.z;
+                        if (best_dist_1 <= TH_LOW && best_dist_1 / best_dist_2 <= max_neighbor_ratio) {
+                            const int existing = matchedFlags[j][best_j_now];
+                            if (existing == intraMatchInd) continue;
+                            if (existing == -1) {
+                                matches[intraMatchInd].matchIndex[cam2] = feat_cam2[best_j_now];
+                                matches[intraMatchInd].n_rays++;
+                                matchedFlags[j][best_j_now] = intraMatchInd;
+                                foundMatch = true;
+                            } else {
+                                const int old_cam1 = matches[existing].matchIndex[cam1];
+                                if (old_cam1 == -1) {
+                                    if (updateOnce) updateOnce = false;
+                                    else continue;
+                                    bool update_match = true;
+                                    int tmp[MCORB_MAX_CAMS];
+                                    for (int tt = 0; tt < C; tt++) tmp[tt] = matches[existing].matchIndex[tt];
+                                    int inc = 0;
+                                    for (int tt = 0; tt < C; tt++) {
+                                        if (matches[intraMatchInd].matchIndex[tt] != -1) {
+                                            if (matches[existing].matchIndex[tt] != -1) { update_match = false; break; }
+                                            tmp[tt] = matches[intraMatchInd].matchIndex[tt];
+                                            inc++;
+                                        }
+                                    }
+                                    if (update_match) {
+                                        for (int tt = 0; tt < C; tt++) matches[existing].matchIndex[tt] = tmp[tt];
+                                        matches[existing].n_rays += inc;
+                                        matchedFlags[i][a] = existing;
+                                        intraMatchInd = existing;
+                                        foundMatch = true;
+                                        matches.pop_back();
+                                    }
+                                    continue;
+                                }
+                                const double d = dist(cam1, old_cam1, cam2, feat_cam2[best_j_now]);
+                                if (best_dist_1 < d) {
+                                    matches[existing].matchIndex[cam2] = -1;
+                                    matches[existing].n_rays--;
+                                    matches[intraMatchInd].matchIndex[cam2] = feat_cam2[best_j_now];
+                                    matches[intraMatchInd].n_rays++;
+                                    matchedFlags[j][best_j_now] = intraMatchInd;
+                                    foundMatch = true;
+                                }
+                            }
+                        }
+                    }
+                    if (foundMatch) {
+                        out.words.push_back(F.fv[selected[0]][it[selected[0]]].node);
+                        intraMatchInd = (int)matches.size();
+                    } else {
+                        matches.pop_back();
+                        matchedFlags[i][a] = -1;
+                    }
+                }
+            }
+        }
+        for (int c : selected) ++it[c];
+    }
+    out.tracks.resize(matches.size() * C);
+    out.n_rays.resize(matches.size());
+    for (size_t m = 0; m < matches.size(); m++) {
+        for (int c = 0; c < C; c++) out.tracks[m * C + c] = matches[m].matchIndex[c];
+        out.n_rays[m] = matches[m].n_rays;
+    }
+}
+
 extern "C" int mcorb_rig_match_bow_frames(mcorb_rig *r, int slot, int frame0, int nframes, mcorb_vocab *v, int levelsup,
                                           double max_neighbor_ratio, const float *const *y_undist)
 {
@@ -441,7 +560,6 @@ extern "C" int mcorb_rig_match_bow_frames(mcorb_rig *r, int slot, int frame0, in
     if (frame0 < 0 || (frame0 + nframes) * C > s->nimg_done) { set_error("match_bow: frames not extracted"); return MCORB_E_STATE; }
     if (v->device != R.device) { set_error("vocabulary lives on another device"); return MCORB_E_ARG; }
     HIPCHK(hipSetDevice(R.device));
-    const int TH_LOW = 75;   // ORBextractor.h:27
     const int img0 = frame0 * C, nimg = nframes * C;
     std::vector<const mcorb_keypoint *> kdef;   // the rig's own undistorted set for rows the caller leaves NULL (undistortion set)
     bool kneed = !y_undist;
@@ -560,128 +678,67 @@ extern "C" int mcorb_rig_match_bow_frames(mcorb_rig *r, int slot, int frame0, in
     const auto T3 = now();
 
     // 4. per frame: the reference's serial walk over common nodes (:647-929), reading best/second-best from the table
-    const uint8_t *hd = s->h_desc;
     R.pool->parallel_for(nframes, [&](int f, int) {
-        BowFrameOut &out = s->bow[frame0 + f];
-        out.tracks.clear(); out.n_rays.clear(); out.words.clear();
-        const FrameTables &F = ft[f];
-        if (F.empty) return;
-        const int4 *tab = v->h_mtab + (size_t)f * npairs * kcap;
-        std::vector<int> it(C, 0), last(C);
-        for (int c = 0; c < C; c++) last[c] = (int)F.fv[c].size() - 1;   // std::prev(end()): the last node is never visited (reference quirk)
-        std::vector<BowTrack> matches;
-        matches.reserve(10000);   // (:587)
-        int intraMatchInd = 0;
-        auto dist = [&](int ca, int fa, int cb, int fb) {
-            return mcorb_hamming256(hd + ((size_t)(img0 + f * C + ca) * kcap + fa) * 32, hd + ((size_t)(img0 + f * C + cb) * kcap + fb) * 32);
-        };
-        std::vector<int> selected;
-        std::vector<std::vector<int>> matchedFlags;
-        for (;;) {
-            bool end = true;   // checkItersEnd (:569-575)
-            for (int c = 0; c < C; c++) end = end && F.fv[c][it[c]].node >= F.fv[c][last[c]].node;
-            if (end) break;
-            uint32_t min_val = 0x7ffffffeu;
-            selected.clear();
-            for (int c = 0; c < C; c++) {
-                const uint32_t w = it[c] == last[c] ? 0x7fffffffu : F.fv[c][it[c]].node;
-                if (w < min_val) { min_val = w; selected.clear(); selected.push_back(c); }
-                else if (w == min_val) selected.push_back(c);
-            }
-            matchedFlags.assign(selected.size(), std::vector<int>());
-            for (size_t i = 0; i < selected.size(); i++) matchedFlags[i].assign(F.fv[selected[i]][it[selected[i]]].cnt, -1);
-            if (selected.size() >= 2) {
-                for (int i = 0; i < (int)selected.size() - 1; i++) {
-                    const int cam1 = selected[i];
-                    const FvRun &run1 = F.fv[cam1][it[cam1]];
-                    const int32_t *feat_cam1 = F.feats[cam1].data() + run1.beg;
-                    for (int a = 0; a < run1.cnt; a++) {
-                        bool foundMatch = false;
-                        if (matchedFlags[i][a] != -1) continue;
-                        BowTrack temp;
-                        for (int tt = 0; tt < C; tt++) temp.matchIndex[tt] = -1;
-                        temp.matchIndex[cam1] = feat_cam1[a];
-                        temp.n_rays = 1;
-                        matches.push_back(temp);
-                        matchedFlags[i][a] = intraMatchInd;
-                        bool updateOnce = true;
-                        for (int j = i + 1; j < (int)selected.size(); j++) {
-                            const int cam2 = selected[j];
-                            const int32_t *feat_cam2 = F.feats[cam2].data() + F.fv[cam2][it[cam2]].beg;
-                            const int4 t = tab[(size_t)pair_of(C, cam1, cam2) * kcap + feat_cam1[a]];
-                            const int best_j_now = t.x;
-                            const double best_dist_1 = t.x < 0 ? 1e9 : (double)t.y;
-                            const double best_dist_2 = t.z == 0x7fffffff ? 1e9 : (double)t.z;
-                            if (best_dist_1 <= TH_LOW && best_dist_1 / best_dist_2 <= max_neighbor_ratio) {
-                                const int existing = matchedFlags[j][best_j_now];
-                                if (existing == intraMatchInd) continue;
-                                if (existing == -1) {
-                                    matches[intraMatchInd].matchIndex[cam2] = feat_cam2[best_j_now];
-                                    matches[intraMatchInd].n_rays++;
-                                    matchedFlags[j][best_j_now] = intraMatchInd;
-                                    foundMatch = true;
-                                } else {
-                                    const int old_cam1 = matches[existing].matchIndex[cam1];
-                                    if (old_cam1 == -1) {
-                                        if (updateOnce) updateOnce = false;
-                                        else continue;
-                                        bool update_match = true;
-                                        int tmp[MCORB_MAX_CAMS];
-                                        for (int tt = 0; tt < C; tt++) tmp[tt] = matches[existing].matchIndex[tt];
-                                        int inc = 0;
-                                        for (int tt = 0; tt < C; tt++) {
-                                            if (matches[intraMatchInd].matchIndex[tt] != -1) {
-                                                if (matches[existing].matchIndex[tt] != -1) { update_match = false; break; }
-                                                tmp[tt] = matches[intraMatchInd].matchIndex[tt];
-                                                inc++;
-                                            }
-                                        }
-                                        if (update_match) {
-                                            for (int tt = 0; tt < C; tt++) matches[existing].matchIndex[tt] = tmp[tt];
-                                            matches[existing].n_rays += inc;
-                                            matchedFlags[i][a] = existing;
-                                            intraMatchInd = existing;
-                                            foundMatch = true;
-                                            matches.pop_back();
-                                        }
-                                        continue;
-                                    }
-                                    const double d = dist(cam1, old_cam1, cam2, feat_cam2[best_j_now]);
-                                    if (best_dist_1 < d) {
-                                        matches[existing].matchIndex[cam2] = -1;
-                                        matches[existing].n_rays--;
-                                        matches[intraMatchInd].matchIndex[cam2] = feat_cam2[best_j_now];
-                                        matches[intraMatchInd].n_rays++;
-                                        matchedFlags[j][best_j_now] = intraMatchInd;
-                                        foundMatch = true;
-                                    }
-                                }
-                            }
-                        }
-                        if (foundMatch) {
-                            out.words.push_back(F.fv[selected[0]][it[selected[0]]].node);
-                            intraMatchInd = (int)matches.size();
-                        } else {
-                            matches.pop_back();
-                            matchedFlags[i][a] = -1;
-                        }
-                    }
-                }
-            }
-            for (int c : selected) ++it[c];
-        }
-        out.tracks.resize(matches.size() * C);
-        out.n_rays.resize(matches.size());
-        for (size_t m = 0; m < matches.size(); m++) {
-            for (int c = 0; c < C; c++) out.tracks[m * C + c] = matches[m].matchIndex[c];
-            out.n_rays[m] = matches[m].n_rays;
-        }
+        bow_replay(ft[f], C, kcap, v->h_mtab + (size_t)f * npairs * kcap, s->h_desc, img0 + f * C, max_neighbor_ratio, s->bow[frame0 + f]);
     }, R.pool_threads + s->index);
     for (int f = 0; f < nframes; f++) s->bow_ok[frame0 + f] = 1;   // exactly the frames matched by this call
     if (prof)
         fprintf(stderr, "[mcorb host prof] match_bow x%d frames: descend+sync %.0f us, feature vectors + tables %.0f, best2+copy %.0f, replay %.0f\n",
                 nframes, us(T0, T1), us(T1, T2), us(T2, T3), us(T3, now()));
     return MCORB_OK;
+}
+
+// the host half of a bound job (Rig::enqueue_bow): BowImageOut of every image straight from k_bow_fold's records, then with
+// MCORB_BOW_MATCH every frame's replay on k_bow_best2's table -- the FeatureVectors are the records' own lists
+int mcorb::bow_job_finish(Rig &R, Slot &s, int nimg)
+{
+    const int C = R.ncams, kcap = R.geom.kcap, npairs = C * (C - 1) / 2;
+    if ((int)s.bowvec.size() < R.max_images) { s.bowvec.resize(R.max_images); s.bowvec_ok.assign(R.max_images, 0); }
+    R.pool->parallel_for(nimg, [&](int m, int) {
+        const BowRecView r = bow_rec(s.h_bowrec, kcap, m);
+        const int nbow = r.cnt[0], nfv = r.cnt[1], nf = r.cnt[2];
+        BowImageOut &o = s.bowvec[m];
+        o.bow_ids.assign(r.ids, r.ids + nbow);
+        o.bow_vals.assign(r.vals, r.vals + nbow);
+        o.fv_nodes.assign(r.nodes, r.nodes + nfv);
+        o.fv_offsets.assign(r.offs, r.offs + nfv + 1);
+        o.fv_feats.assign(r.feats, r.feats + nf);
+        s.bowvec_ok[m] = 1;
+    }, R.pool_threads + s.index);
+    if (!(s.bow_job & MCORB_BOW_MATCH)) return MCORB_OK;
+    const int nframes = nimg / C;
+    if ((int)s.bow.size() < R.max_frames) { s.bow.resize(R.max_frames); s.bow_ok.assign(R.max_frames, 0); }
+    const double ratio = R.bow_bind.ratio;
+    R.pool->parallel_for(nframes, [&](int f, int) {
+        FrameTables F;
+        F.fv.resize(C); F.feats.resize(C);
+        for (int c = 0; c < C; c++) {
+            const BowImageOut &o = s.bowvec[f * C + c];
+            for (size_t e = 0; e < o.fv_nodes.size(); e++) F.fv[c].push_back(FvRun{o.fv_nodes[e], o.fv_offsets[e], o.fv_offsets[e + 1] - o.fv_offsets[e]});
+            F.feats[c] = o.fv_feats;
+            if (F.fv[c].empty()) F.empty = true;   // the reference returns with no matches (:602-603)
+        }
+        bow_replay(F, C, kcap, s.h_btab + (size_t)f * npairs * kcap, s.h_desc, f * C, ratio, s.bow[f]);
+        s.bow_ok[f] = 1;
+    }, R.pool_threads + s.index);
+    return MCORB_OK;
+}
+
+extern "C" int mcorb_rig_set_vocabulary(mcorb_rig *r, mcorb_vocab *v, int levelsup, double max_neighbor_ratio, int flags)
+{
+    if (!r) { set_error("set_vocabulary: bad argument"); return MCORB_E_ARG; }
+    Rig &R = r->rig;
+    Rig::BowBinding b;
+    if (v && flags) {
+        if (flags & ~(MCORB_BOW_TRANSFORM | MCORB_BOW_MATCH)) { set_error("set_vocabulary: unknown flags"); return MCORB_E_ARG; }
+        if (v->device != R.device) { set_error("set_vocabulary: the vocabulary lives on another device"); return MCORB_E_ARG; }
+        if (levelsup < 0) { set_error("set_vocabulary: levelsup must be >= 0"); return MCORB_E_ARG; }
+        b.flags = flags | MCORB_BOW_TRANSFORM;   // (the match needs the transform's descent and FeatureVectors)
+        b.levelsup = levelsup; b.L = v->L; b.weighting = v->weighting; b.scoring = v->scoring; b.ratio = max_neighbor_ratio;
+        b.child_start = v->d_child_start; b.child_count = v->d_child_count; b.child_id = v->d_child_id; b.word_id = v->d_word_id;
+        b.child_desc = v->d_child_desc; b.weight = v->d_weight;
+    }
+    return R.set_vocabulary(b);
 }
 
 extern "C" int mcorb_rig_get_bow_tracks(mcorb_rig *r, int slot, int frame, int32_t *tracks, int32_t *n_rays, int cap_tracks,

@@ -40,6 +40,27 @@ __host__ __device__ inline int tbl_ints(int bucketTotal) { return (tbl_win_off(b
 // happens for a well-formed tree), and the node id `levelsup` levels above the leaves (FeatureVector key)
 struct BowRes { int32_t word, nodeup; double weight; };
 
+// transform() of one image as k_bow_fold writes it (mcorb_rig_set_vocabulary): one record of bow_rec_ints(kcap) ints per image,
+// [nbow, nfv, nfeats, 0] | BowVector word ids [kcap] | FeatureVector node ids [kcap] | offsets [kcap + 4] (nfv + 1 used) |
+// feature indices [kcap] | BowVector values [kcap] doubles (8-byte aligned: kcap is a multiple of 64)
+constexpr int kBowFoldMaxKcap = 4096;   // MCORB_BOW_MAX_KCAP: k_bow_fold sorts an image's keys in LDS (32 KB of 64-bit keys)
+struct BowRecView {
+    int *cnt; uint32_t *ids, *nodes; int *offs, *feats; double *vals;
+};
+__host__ __device__ inline size_t bow_rec_ints(int kcap) { return 6 * (size_t)kcap + 8; }
+__host__ __device__ inline BowRecView bow_rec(int *base, int kcap, int m)
+{
+    int *r = base + (size_t)m * bow_rec_ints(kcap);
+    BowRecView v;
+    v.cnt = r;
+    v.ids = reinterpret_cast<uint32_t *>(r + 4);
+    v.nodes = reinterpret_cast<uint32_t *>(r + 4 + kcap);
+    v.offs = r + 4 + 2 * kcap;
+    v.feats = r + 8 + 3 * kcap;
+    v.vals = reinterpret_cast<double *>(r + 8 + 4 * kcap);
+    return v;
+}
+
 // Packed selected keypoint handed back to the device: level (4) | y (14) | x (14), level coordinates.
 __host__ __device__ inline uint32_t pack_sel(int level, int x, int y) { return ((uint32_t)level << 28) | ((uint32_t)y << 14) | (uint32_t)x; }
 

@@ -633,6 +633,10 @@ Rig::~Rig()
         (void)hipFree(s->d_undist); (void)hipHostFree(s->h_undist);
         if (s->ev_u0) (void)hipEventDestroy(s->ev_u0);
         if (s->ev_u1) (void)hipEventDestroy(s->ev_u1);
+        (void)hipFree(s->d_bowres); (void)hipFree(s->d_bowrec); (void)hipHostFree(s->h_bowrec); (void)hipFree(s->d_bslot);
+        (void)hipFree(s->d_bnfeats); (void)hipFree(s->d_bnfeat); (void)hipFree(s->d_brgbase); (void)hipFree(s->d_byv); (void)hipFree(s->d_brange);
+        (void)hipFree(s->d_btab); (void)hipHostFree(s->h_btab);
+        if (s->ev_b) (void)hipEventDestroy(s->ev_b);
         if (s->ev_s) (void)hipEventDestroy(s->ev_s);
         if (s->ev_g) (void)hipEventDestroy(s->ev_g);
         if (s->graph_exec) (void)hipGraphExecDestroy(s->graph_exec);
@@ -765,6 +769,7 @@ int Rig::submit(int slot, const Job &job)
 {
     if (slot < 0 || slot >= (int)slots.size()) { set_error("bad slot"); return MCORB_E_ARG; }
     Slot &s = *slots[slot];
+    TRY(check_job_shape(job));
     std::unique_lock<std::mutex> lk(s.m);
     if (s.busy) { set_error("slot busy"); return MCORB_E_STATE; }
     s.job = job;
@@ -816,9 +821,12 @@ int Rig::execute(Slot &s, const Job &j)
     int st = MCORB_OK;
     switch (j.kind) {
     case Job::EXTRACT:
-        if (gpu_select) { st = run_gpu_selected(s, j, false); break; }
-        st = run_extract_phaseA(s, j);
-        if (st == MCORB_OK) st = run_select_and_describe(s, j, false);
+        if (gpu_select) st = run_gpu_selected(s, j, false);
+        else {
+            st = run_extract_phaseA(s, j);
+            if (st == MCORB_OK) st = run_select_and_describe(s, j, false);
+        }
+        if (st == MCORB_OK && s.bow_job) st = bow_job_finish(*this, s, j.nimg);
         break;
     case Job::PROCESS:
         LatProf::mark(0);
@@ -830,6 +838,7 @@ int Rig::execute(Slot &s, const Job &j)
             if (st == MCORB_OK) st = run_select_and_describe(s, j, true);
         }
         LatProf::mark(6);
+        if (st == MCORB_OK && s.bow_job) st = bow_job_finish(*this, s, j.nimg);
         if (st == MCORB_OK) st = finish_match(s, j);
         LatProf::mark(7);
         LatProf::flush();
@@ -854,6 +863,7 @@ int Rig::run_sync(int slot, const Job &job)
 {
     if (slot < 0 || slot >= (int)slots.size()) { set_error("bad slot"); return MCORB_E_ARG; }
     Slot &s = *slots[slot];
+    TRY(check_job_shape(job));
     {
         std::lock_guard<std::mutex> lk(s.m);
         if (s.busy) { set_error("slot busy"); return MCORB_E_STATE; }
@@ -1060,6 +1070,7 @@ int Rig::run_select_and_describe(Slot &s, const Job &j, bool then_match)
         if (then_match) TRY(enqueue_match(s, j, true));
         HIPCHK(hipGetLastError());
         if (undist_on) HIPCHK(hipStreamWaitEvent(s.st, s.ev_u1, 0));
+        if (s.bow_job) TRY(enqueue_bow(s, nimg, s.h_sel, s.h_nsel, true));
         HIPCHK(hipEventRecord(s.ev[10], s.st));
         LatProf::mark(4);
         HIPCHK(wait_event(s.ev[10]));
@@ -1100,6 +1111,7 @@ int Rig::run_select_and_describe(Slot &s, const Job &j, bool then_match)
     if (params.orientation)
         HIPCHK(hipMemcpyAsync(s.h_angles, s.d_angles, (size_t)nimg * geom.kcap * sizeof(float), hipMemcpyDeviceToHost, s.st_dma));
     if (undist_on) TRY(enqueue_undistort(s, s.d_sel, s.d_nsel, nimg, false));   // behind the result copies: the side stream's last work
+    if (s.bow_job) TRY(enqueue_bow(s, nimg, s.d_sel, s.d_nsel, false));
     if (then_match && !d2h_late && !d2h_mid) TRY(enqueue_match(s, j, true));
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(s.ev[10], s.st));
@@ -1175,6 +1187,7 @@ int Rig::enqueue_gpu_job(Slot &s, const Job &j, bool then_match)
         if (then_match) TRY(enqueue_match(s, j, true));
         HIPCHK(hipGetLastError());
         if (undist_on) HIPCHK(hipStreamWaitEvent(s.st, s.ev_u1, 0));   // join
+        if (s.bow_job) TRY(enqueue_bow(s, nimg, s.d_sel, s.d_nsel, true));
         if (ev_on) HIPCHK(hipEventRecord(s.ev[11], s.st));
         return MCORB_OK;
     }
@@ -1189,6 +1202,7 @@ int Rig::enqueue_gpu_job(Slot &s, const Job &j, bool then_match)
     if (params.orientation)
         HIPCHK(hipMemcpyAsync(s.h_angles, s.d_angles, (size_t)nimg * geom.kcap * sizeof(float), hipMemcpyDeviceToHost, s.st_dma));
     if (undist_on) TRY(enqueue_undistort(s, s.d_sel, s.d_nsel, nimg, false));   // behind the result copies: the side stream's last work
+    if (s.bow_job) TRY(enqueue_bow(s, nimg, s.d_sel, s.d_nsel, false));
     if (then_match) TRY(enqueue_match(s, j, true));
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(s.ev[11], s.st_dma));
@@ -1201,6 +1215,7 @@ int Rig::enqueue_gpu_job(Slot &s, const Job &j, bool then_match)
 // ---------------------------------------------------------------------------
 void Rig::undist_job_start(Slot &s)
 {
+    s.bow_job = bow_bind.flags;   // (the BoW stages' snapshot too: both are fixed while a job is in flight)
     s.undist_job = undist_on;
     s.undist_gen = undist_gen;
     std::fill(s.kps_undist_ok.begin(), s.kps_undist_ok.end(), (uint8_t)0);
@@ -1211,8 +1226,8 @@ void Rig::undist_job_start(Slot &s)
 int Rig::enqueue_undistort(Slot &s, const uint32_t *sel, const int *nsel, int nimg, bool host_out)
 {
     launch_undistort(s.st_dma, sel, nsel, geom.kcap, nimg, ncams, d_undist_cams, tab.scale, tab.nlevels, host_out ? s.h_undist : s.d_undist);
-    if (host_out) HIPCHK(hipEventRecord(s.ev_u1, s.st_dma));
-    else HIPCHK(hipMemcpyAsync(s.h_undist, s.d_undist, (size_t)nimg * geom.kcap * sizeof(float2), hipMemcpyDeviceToHost, s.st_dma));
+    if (host_out || s.bow_job) HIPCHK(hipEventRecord(s.ev_u1, s.st_dma));   // (a bound job's BoW tables read the points: enqueue_bow)
+    if (!host_out) HIPCHK(hipMemcpyAsync(s.h_undist, s.d_undist, (size_t)nimg * geom.kcap * sizeof(float2), hipMemcpyDeviceToHost, s.st_dma));
     return MCORB_OK;
 }
 
@@ -1250,6 +1265,82 @@ int Rig::set_undistortion(int cam, const double *K, const double *dist, int ncoe
     undist_on = std::any_of(undist_set.begin(), undist_set.end(), [](uint8_t v) { return v != 0; });
     if (d_undist_cams) HIPCHK(hipMemcpy(d_undist_cams, undist_cams.data(), (size_t)ncams * sizeof(UndistCam), hipMemcpyHostToDevice));
     undist_gen++;
+    return MCORB_OK;
+}
+
+// ---------------------------------------------------------------------------
+// transform() (MultiCameraFrame.cpp:257) and computeIntraMatches(matches, words_) (:586-943) inside the job.  Nothing of this runs,
+// is allocated or is captured while no vocabulary is bound (bow_bind.flags == 0): such a job is exactly the job without the feature.
+// ---------------------------------------------------------------------------
+int Rig::check_job_shape(const Job &j) const
+{
+    if ((j.kind == Job::EXTRACT || j.kind == Job::PROCESS) && (bow_bind.flags & MCORB_BOW_MATCH) && j.nimg % ncams != 0) {
+        set_error("extract: a vocabulary bound with MCORB_BOW_MATCH needs whole rig frames (nimg a multiple of the camera count)");
+        return MCORB_E_ARG;
+    }
+    return MCORB_OK;
+}
+
+int Rig::enqueue_bow(Slot &s, int nimg, const uint32_t *sel, const int *nsel, bool host_out)
+{
+    const BowBinding &b = bow_bind;
+    const int kcap = geom.kcap, nframes = nimg / ncams;
+    const bool match = (s.bow_job & MCORB_BOW_MATCH) && npp > 0 && nframes > 0;
+    launch_bow_descend(s.st, s.d_desc, nimg * kcap, b.child_start, b.child_count, b.child_desc, b.child_id, b.word_id, b.weight,
+                       b.L - b.levelsup, s.d_bowres);
+    launch_bow_fold(s.st, s.d_bowres, nsel, kcap, nimg, b.weighting, b.scoring, s.d_bowrec, host_out ? s.h_bowrec : nullptr);
+    if (match) {
+        // the rows of the |dy| < 50 gate: the job's own undistorted points when undistortion is set (k_undistort on the side stream)
+        if (undist_on && !host_out) HIPCHK(hipStreamWaitEvent(s.st, s.ev_u1, 0));   // (small batches joined it already)
+        launch_bow_tables(s.st, s.d_bowrec, kcap, ncams, nframes, nsel, sel, tab.scale, tab.nlevels,
+                          undist_on ? (host_out ? s.h_undist : s.d_undist) : nullptr, s.d_bslot, s.d_bnfeats, s.d_bnfeat, s.d_brgbase,
+                          s.d_byv, s.d_brange);
+        launch_bow_best2(s.st, s.d_desc, 0, kcap, ncams, nframes, s.d_byv, s.d_bslot, s.d_brange, s.d_brgbase, s.d_bnfeats, s.d_bnfeat,
+                         host_out ? s.h_btab : s.d_btab);
+    }
+    HIPCHK(hipGetLastError());
+    if (host_out) return MCORB_OK;
+    HIPCHK(hipEventRecord(s.ev_b, s.st));
+    HIPCHK(hipStreamWaitEvent(s.st_dma, s.ev_b, 0));
+    HIPCHK(hipMemcpyAsync(s.h_bowrec, s.d_bowrec, (size_t)nimg * bow_rec_ints(kcap) * sizeof(int), hipMemcpyDeviceToHost, s.st_dma));
+    if (match)
+        HIPCHK(hipMemcpyAsync(s.h_btab, s.d_btab, (size_t)nframes * npp * kcap * sizeof(int4), hipMemcpyDeviceToHost, s.st_dma));
+    return MCORB_OK;
+}
+
+int Rig::set_vocabulary(const BowBinding &b)
+{
+    if (b.flags && geom.kcap > kBowFoldMaxKcap) {
+        set_error("set_vocabulary: the rig's keypoint capacity (kcap " + std::to_string(geom.kcap) + ") exceeds MCORB_BOW_MAX_KCAP (" +
+                  std::to_string(kBowFoldMaxKcap) + ")");
+        return MCORB_E_ARG;
+    }
+    std::vector<std::unique_lock<std::mutex>> locks;
+    for (Slot *sp : slots) {
+        locks.emplace_back(sp->m);
+        if (sp->busy || sp->submitted) { set_error("set_vocabulary: a submitted job has not been waited for"); return MCORB_E_STATE; }
+    }
+    HIPCHK(hipSetDevice(device));
+    if (b.flags && !slots.empty() && !slots[0]->d_bowres) {   // first bind: every slot's buffers
+        const size_t M = (size_t)max_images, kc = (size_t)geom.kcap, F = (size_t)max_frames;
+        const size_t tab_n = std::max<size_t>((size_t)std::max(npp, 1) * F * kc, 1);
+        for (Slot *sp : slots) {
+            HIPCHK(hipMalloc((void **)&sp->d_bowres, M * kc * sizeof(BowRes)));
+            HIPCHK(hipMalloc((void **)&sp->d_bowrec, M * bow_rec_ints(geom.kcap) * sizeof(int)));
+            HIPCHK(hipHostMalloc((void **)&sp->h_bowrec, M * bow_rec_ints(geom.kcap) * sizeof(int), hipHostMallocMapped | hipHostMallocPortable));
+            HIPCHK(hipMalloc((void **)&sp->d_bslot, M * kc * sizeof(int)));
+            HIPCHK(hipMalloc((void **)&sp->d_bnfeats, M * kc * sizeof(int)));
+            HIPCHK(hipMalloc((void **)&sp->d_bnfeat, M * sizeof(int)));
+            HIPCHK(hipMalloc((void **)&sp->d_brgbase, (F + 1) * sizeof(int)));
+            HIPCHK(hipMalloc((void **)&sp->d_byv, M * kc * sizeof(float)));
+            HIPCHK(hipMalloc((void **)&sp->d_brange, M * kc * (size_t)ncams * sizeof(int2)));
+            HIPCHK(hipMalloc((void **)&sp->d_btab, tab_n * sizeof(int4)));
+            HIPCHK(hipHostMalloc((void **)&sp->h_btab, tab_n * sizeof(int4), hipHostMallocMapped | hipHostMallocPortable));
+            HIPCHK(hipEventCreateWithFlags(&sp->ev_b, hipEventDisableTiming));
+        }
+    }
+    bow_bind = b.flags ? b : BowBinding{};
+    bow_gen++;
     return MCORB_OK;
 }
 
@@ -1388,7 +1479,8 @@ int Rig::run_gpu_selected(Slot &s, const Job &j, bool then_match)
         ~GpuTurn() { done(); }
     } turn(*this);
     if (graphed) {
-        const Slot::GraphKey key{nimg, then_match ? 1 : 0, j.nframes, j.lap0, j.lap1, j.dist_thresh, j.ratio, undist_on ? 1 : 0};
+        const Slot::GraphKey key{nimg, then_match ? 1 : 0, j.nframes, j.lap0, j.lap1, j.dist_thresh, j.ratio, undist_on ? 1 : 0,
+                                 bow_bind.flags, bow_bind.flags ? bow_bind.levelsup : 0, bow_gen};
         if (!s.graph_exec || memcmp(&key, &s.graph_key, sizeof(key)) != 0) {
             if (s.graph_exec) { (void)hipGraphExecDestroy(s.graph_exec); s.graph_exec = nullptr; }
             hipGraph_t graph = nullptr;

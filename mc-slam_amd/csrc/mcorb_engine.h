@@ -167,7 +167,10 @@ struct Slot {
     int fallbacks = 0;         // jobs of this slot the host stage had to redo (a tree below the bucketing depth)
     hipEvent_t ev_s = nullptr; // k_select + k_assemble finished
     hipEvent_t ev_g = nullptr; // in front of a replayed job graph
-    struct GraphKey { int nimg, match, nframes, lap0, lap1; float dist_thresh, ratio; int undist; };
+    // (bow_*: the vocabulary binding the job was captured with -- its tables and levelsup are kernel arguments; bow_gen counts
+    // mcorb_rig_set_vocabulary calls, so a freed vocabulary whose address comes back never replays a stale graph.  4-byte fields
+    // only: the key is compared with memcmp)
+    struct GraphKey { int nimg, match, nframes, lap0, lap1; float dist_thresh, ratio; int undist, bow_flags, bow_levelsup; unsigned bow_gen; };
     hipGraphExec_t graph_exec = nullptr;   // the captured job (run_gpu_selected), valid for graph_key
     GraphKey graph_key = {};
     unsigned job_counter = 0;
@@ -204,6 +207,18 @@ struct Slot {
     bool undist_job = false;      // the images in the slot were extracted with k_undistort (some camera had undistortion set)
     unsigned undist_gen = 0;      // Rig::undist_gen when they were extracted
     bool submitted = false;       // a job was submitted and not yet waited for (mcorb_rig_set_undistortion refuses then)
+    // transform() / computeIntraMatches(matches, words_) inside the job (mcorb_rig_set_vocabulary), all allocated at the rig's first
+    // bind, never while no vocabulary was bound: descent results, k_bow_fold's per-image records (d_ device, h_ host-mapped pinned),
+    // k_bow_best2's index tables and its best / second-best table (d_ device, h_ host-mapped pinned); ev_b: the BoW kernels are done
+    // (the copies of a large batch follow it on st_dma)
+    BowRes *d_bowres = nullptr;
+    int *d_bowrec = nullptr, *h_bowrec = nullptr;
+    int *d_bslot = nullptr, *d_bnfeats = nullptr, *d_bnfeat = nullptr, *d_brgbase = nullptr;
+    float *d_byv = nullptr;
+    int2 *d_brange = nullptr;
+    int4 *d_btab = nullptr, *h_btab = nullptr;
+    hipEvent_t ev_b = nullptr;
+    int bow_job = 0;              // MCORB_BOW_* flags the images in the slot were extracted with (0: no BoW stage ran)
     // image_kps_undist of the images, built on first read from kps and h_undist (Rig::undist_records)
     std::vector<std::vector<mcorb_keypoint>> kps_undist;
     std::vector<uint8_t> kps_undist_ok;
@@ -291,6 +306,20 @@ public:
     int undist_default(Slot &s, int m0, int n, std::vector<const mcorb_keypoint *> &out);
     int max_pairs() const { return std::max(1, npp * max_frames); }
 
+    // the vocabulary bound to the rig (mcorb_rig_set_vocabulary): flags = 0 unbound; otherwise the vocabulary's device tables,
+    // levelsup and weighting / scoring, which every extraction job's BoW stages read; bow_gen counts the set calls
+    struct BowBinding {
+        int flags = 0, levelsup = 0, L = 0, weighting = 0, scoring = 0;
+        double ratio = 0.85;
+        const int *child_start = nullptr, *child_count = nullptr, *child_id = nullptr, *word_id = nullptr;
+        const void *child_desc = nullptr;
+        const double *weight = nullptr;
+    };
+    BowBinding bow_bind;
+    unsigned bow_gen = 0;
+    int set_vocabulary(const BowBinding &b);
+    int check_job_shape(const Job &j) const;   // a bound MCORB_BOW_MATCH needs whole frames
+
 private:
     bool copy_kernel = false;  // D2H of tables / descriptors by k_copy_to_host instead of hipMemcpyAsync (see Rig::init)
     bool blur_planes = false;  // k_blur runs with every job (orientation mode / MCORB_BLUR_PLANES); otherwise blur is fused into k_describe_fused
@@ -304,10 +333,17 @@ private:
     // host-mapped memory; copy_back: the D2H copy of the points follows on the same stream
     int enqueue_undistort(Slot &s, const uint32_t *sel, const int *nsel, int nimg, bool host_out);
     void undist_job_start(Slot &s);
+    // the BoW stages of the job's nimg images on the compute stream, behind the descriptors (and k_undistort when it gives the rows):
+    // host_out = a small batch, results in host-mapped memory; otherwise copied on st_dma behind the job's other result copies
+    int enqueue_bow(Slot &s, int nimg, const uint32_t *sel, const int *nsel, bool host_out);
     int prepare_match(Slot &s, const Job &j);
     int enqueue_match(Slot &s, const Job &j, bool ctrl_on_device);
     int finish_match(Slot &s, const Job &j);
 };
+
+// the host half of a job's BoW stages (mcorb_bow.cpp): the BowImageOut of every image from k_bow_fold's records and, with
+// MCORB_BOW_MATCH, the reference's serial track bookkeeping of every frame on the worker pool
+int bow_job_finish(Rig &R, Slot &s, int nimg);
 
 }  // namespace mcorb
 

@@ -96,6 +96,15 @@ void launch_copy_to_host(hipStream_t st, const void *src_dev, void *dst_host_map
 // batch-local image index f * ncams + c (see k_bow_best2)
 void launch_bow_best2(hipStream_t st, const uint8_t *desc, int img0, int kcap, int ncams, int nframes, const float *yv,
                       const int *slot_of, const int2 *node_range, const int *rg_base, const int *node_feats, const int *nfeat, int4 *out);
+// k_bow_fold: transform()'s FeatureVector + BowVector of nimg images from their descent results (res, kcap-strided), into
+// bow_rec records (mcorb_common.h) in device memory, and also in host-mapped memory when out_host is given (kcap <= kBowFoldMaxKcap)
+void launch_bow_fold(hipStream_t st, const BowRes *res, const int *nsel, int kcap, int nimg, int weighting, int scoring, int *out_dev,
+                     int *out_host);
+// k_bow_tables: k_bow_best2's slot_of / nfeat / rg_base / yv / node_range of nframes frames from k_bow_fold's device records
+// (node_feats: the records' feature lists, kcap-strided); undist = NULL: the rows are the keypoint records' y, rebuilt from sel
+void launch_bow_tables(hipStream_t st, const int *fold, int kcap, int ncams, int nframes, const int *nsel, const uint32_t *sel,
+                       const float *scale, int nlevels, const float2 *undist, int *slot_of, int *node_feats, int *nfeat, int *rg_base,
+                       float *yv, int2 *node_range);
 void launch_bow_descend(hipStream_t st, const uint8_t *desc, int n, const int *child_start, const int *child_count,
                         const void *child_desc, const int *child_id, const int *word_id, const double *weight, int nid_level,
                         BowRes *out);
