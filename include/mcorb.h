@@ -442,6 +442,28 @@ int mcorb_rig_obtain_lf_features_frames(mcorb_rig *r, int slot, int frame0, int 
                                         int *n_out, int *intramatch_size_out, int *mono_size_out, uint32_t *words_fil, int cap_words,
                                         int *nwords_fil_out);
 
+/* Bind obtainLfFeatures to the rig's jobs (FrontEnd.cpp:1009-1024): every later extraction job whose vocabulary is bound with
+ * MCORB_BOW_MATCH (mcorb_rig_set_vocabulary) also runs, for every frame, obtainLfFeatures on the job's own BoW-guided tracks
+ * (mcorb_rig_get_bow_tracks) with words_ all 1 (:1010), all-zero segmentation masks (mc_slam_app.cpp:224) and the rig's
+ * image_kps_undist (its own undistorted set when mcorb_rig_set_undistortion is active, else the raw keypoints), and the LF
+ * set's transform() with the bound levelsup (:525).  The triangulations run on the GPU (k_lf_tracks), the order-dependent
+ * bookkeeping on the host.  Results equal mcorb_rig_obtain_lf_features(those tracks, ones, NULL, 0, NULL, total_feats) and
+ * mcorb_vocab_transform(its descriptors, levelsup) bit for bit; extract / process and their waits return once they are ready.
+ * cams: ncams entries (K, build_Rt); total_feats: 3000 in the reference (FrontEnd.cpp:515), >= 0; cams = NULL unbinds (a job is
+ * then exactly what it is without this call).  MCORB_E_STATE while a submitted job has not been waited for. */
+int mcorb_rig_set_lf(mcorb_rig *r, const mcorb_camera *cams, int total_feats);
+/* the job's obtainLfFeatures output of one frame, laid out as mcorb_rig_obtain_lf_features'.  MCORB_E_STATE for a frame the
+ * slot's last extraction did not run the stage on; MCORB_E_CAP (with the needed counts set) when out / words_fil are short */
+int mcorb_rig_get_lf_features(mcorb_rig *r, int slot, int frame, mcorb_lf_feature *out, int cap, int *n_out,
+                              int *intramatch_size_out, int *mono_size_out, uint32_t *words_fil, int cap_words, int *nwords_fil_out);
+/* the job's lfBoW / lfFeatVec of one frame, laid out as mcorb_rig_get_transform's; same states */
+int mcorb_rig_get_lf_bow(mcorb_rig *r, int slot, int frame, uint32_t *bow_ids, double *bow_vals, int bow_cap, int *nbow,
+                         uint32_t *fv_nodes, int32_t *fv_offsets, int fv_cap, int *nfv, int32_t *fv_feats, int feat_cap);
+/* test hook: k_lf_tracks' triangulation of n arbitrary problems on the device (x: 2 * nv[i] normalised coordinates, P: nv[i]
+ * row-major 3x4 matrices, problems back to back; 2 <= nv[i] <= MCORB_MAX_CAMS); branch[i] = the exit of the null-vector solver
+ * taken: 0 zero trace, 1 unshifted steps only, 2 Rayleigh-quotient steps, 3 Sylvester check failed and re-run */
+int mcorb_dev_triangulate_selftest(int device, const double *x, const double *P, const int32_t *nv, int n, double *X, int32_t *branch);
+
 /* ------------------------------------------------------------------------- */
 /* Host stages exposed for the CPU test-suite (no device needed)              */
 /* ------------------------------------------------------------------------- */
@@ -465,6 +487,8 @@ int mcorb_host_geometry(const mcorb_params *p, int w, int h, int32_t *six_per_le
 /* the N-view DLT triangulation of mcorb_rig_obtain_lf_features alone (cv::sfm::triangulatePoints for one point):
  * x = nv normalised image points (x0, y0, x1, y1, ..), P = nv row-major 3x4 [R|t], 2 <= nv <= MCORB_MAX_CAMS */
 int mcorb_host_triangulate(const double *x, const double *P, int nv, double X[3]);
+/* the same, also giving the null-vector solver's exit (the codes of mcorb_dev_triangulate_selftest) */
+int mcorb_host_triangulate_branch(const double *x, const double *P, int nv, double X[3], int32_t *branch);
 
 /* ------------------------------------------------------------------------- */
 /* Synthetic input; host utility, see csrc/mcorb_synth.c       */

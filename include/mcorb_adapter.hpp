@@ -175,6 +175,11 @@ public:
     std::array<int, MCORB_MAX_CAMS> matchIndex;
     bool mono;
     int n_rays;
+    // set by obtainLfFeatures (FrontEnd.cpp:213-593, MultiCameraFrontEnd::setLfConfig): the representative descriptor, the
+    // triangulated point (multi-view entries) and the point in the reference camera
+    std::array<uint8_t, 32> matchDesc{};
+    std::array<double, 3> point3D{};
+    std::array<float, 2> uv_ref{};
     IntraMatch() : mono(true), n_rays(0) { matchIndex.fill(-1); }
 };
 
@@ -239,6 +244,7 @@ public:
         image_descriptors.resize(num_cams);
     }
     ~MultiCameraFrontEnd() { mcorb_rig_destroy(rig_); }
+    mcorb_rig *rig() const { return rig_; }   // the rig underneath (explicit C-ABI calls on the same frame)
 
     // setData (MultiCameraFrame.cpp:95-152): 8-bit gray frames ...
     void setData(const std::vector<const uint8_t *> &imgs, int stride)
@@ -292,9 +298,52 @@ public:
                                               feats.data(), n + 1), "mcorb_rig_get_transform");
                 ORBVocabulary::fill(ids, vals, nb, nodes, offs, feats, nf, BoW_vecs[c], BoW_feats[c]);
             }
+            if (lf_bound_) read_lf();
         }
         matched_ = false;
     }
+    // camconfig_.K_mats_ / R_mats_ / t_mats_ (row-major 3x3, 3x3, 3 doubles per camera), once at init, after setVocabulary: from
+    // then on extractFeaturesParallel() also fills intraMatches, intramatch_size, mono_size, lfBoW and lfFeatVec as
+    // FrontEnd::processFrame's obtainLfFeatures (:1009-1024, words_ all 1, no segmentation masks) and its transform of the LF
+    // set (:525) leave them, made by the extraction job.  Empty K_mats unbinds.
+    void setLfConfig(const std::vector<std::array<double, 9>> &K_mats, const std::vector<std::array<double, 9>> &R_mats,
+                     const std::vector<std::array<double, 3>> &t_mats, int total_feats = 3000)
+    {
+        if (K_mats.empty()) {
+            check(mcorb_rig_set_lf(rig_, nullptr, 0), "mcorb_rig_set_lf");
+            lf_bound_ = false;
+            intraMatches.clear(); intramatch_size = mono_size = 0; lfBoW.clear(); lfFeatVec.clear();
+            return;
+        }
+        if ((int)K_mats.size() != num_cams_ || (int)R_mats.size() != num_cams_ || (int)t_mats.size() != num_cams_)
+            throw std::runtime_error("ERROR:: setLfConfig needs one K, R and t per camera");
+        std::vector<mcorb_camera> cams((size_t)num_cams_);
+        for (int c = 0; c < num_cams_; c++) {
+            for (int i = 0; i < 9; i++) cams[c].K[i] = K_mats[c][i];
+            for (int r = 0; r < 3; r++) {   // build_Rt(R, t) (FrontEnd.cpp:224)
+                for (int k = 0; k < 3; k++) cams[c].Rt[4 * r + k] = R_mats[c][3 * r + k];
+                cams[c].Rt[4 * r + 3] = t_mats[c][r];
+            }
+        }
+        check(mcorb_rig_set_lf(rig_, cams.data(), total_feats), "mcorb_rig_set_lf");
+        lf_bound_ = true;
+    }
+#ifdef MCORB_WITH_OPENCV
+    // the same from the reference's CV_64F camconfig_ Mats
+    void setLfConfig(const std::vector<cv::Mat> &K_mats, const std::vector<cv::Mat> &R_mats, const std::vector<cv::Mat> &t_mats,
+                     int total_feats = 3000)
+    {
+        std::vector<std::array<double, 9>> K(K_mats.size()), R(R_mats.size());
+        std::vector<std::array<double, 3>> t(t_mats.size());
+        for (size_t c = 0; c < K_mats.size(); c++)
+            for (int i = 0; i < 9; i++) K[c][i] = K_mats[c].at<double>(i / 3, i % 3);
+        for (size_t c = 0; c < R_mats.size(); c++)
+            for (int i = 0; i < 9; i++) R[c][i] = R_mats[c].at<double>(i / 3, i % 3);
+        for (size_t c = 0; c < t_mats.size(); c++)
+            for (int i = 0; i < 3; i++) t[c][i] = t_mats[c].at<double>(i, 0);   // (3x1)
+        setLfConfig(K, R, t, total_feats);
+    }
+#endif
     // orb_vocabulary (MultiCameraFrame.cpp:252-261), once at init: from then on extractFeaturesParallel() fills BoW_vecs / BoW_feats
     // and the extraction job also makes computeIntraMatches(matches, words_), which the BoW-guided computeIntraMatches below reads
     // when it is called with this vocabulary, levelsup and ratio and setUndistorted() has not replaced the rows.  nullptr unbinds;
@@ -471,8 +520,41 @@ public:
     std::vector<ORBVocabulary::BowVector> BoW_vecs;       // per camera, filled by extractFeaturesParallel after setVocabulary
     std::vector<ORBVocabulary::FeatureVector> BoW_feats;
     int cnt_mergable_matches = 0;
+    // currentFrame->intraMatches / intramatch_size / mono_size / lfBoW / lfFeatVec after obtainLfFeatures (setLfConfig)
+    std::vector<IntraMatch> intraMatches;
+    int intramatch_size = 0, mono_size = 0;
+    ORBVocabulary::BowVector lfBoW;
+    ORBVocabulary::FeatureVector lfFeatVec;
 
 private:
+    bool lf_bound_ = false;
+    void read_lf()
+    {
+        int n = 0, ni = 0, nm = 0, nw = 0;
+        int st = mcorb_rig_get_lf_features(rig_, 0, 0, nullptr, 0, &n, &ni, &nm, nullptr, 0, &nw);
+        if (st != MCORB_E_CAP) check(st, "mcorb_rig_get_lf_features");
+        std::vector<mcorb_lf_feature> f((size_t)n + 1);
+        check(mcorb_rig_get_lf_features(rig_, 0, 0, f.data(), n + 1, &n, &ni, &nm, nullptr, 0, &nw), "mcorb_rig_get_lf_features");
+        intramatch_size = ni;
+        mono_size = nm;
+        intraMatches.assign((size_t)n, IntraMatch());
+        for (int i = 0; i < n; i++) {
+            IntraMatch &m = intraMatches[i];
+            for (int c = 0; c < MCORB_MAX_CAMS; c++) m.matchIndex[c] = f[i].match_index[c];
+            m.mono = f[i].mono != 0;
+            m.n_rays = f[i].n_rays;
+            for (int k = 0; k < 32; k++) m.matchDesc[k] = f[i].desc[k];
+            for (int k = 0; k < 3; k++) m.point3D[k] = f[i].point3d[k];
+            m.uv_ref[0] = f[i].uv_ref[0]; m.uv_ref[1] = f[i].uv_ref[1];
+        }
+        std::vector<uint32_t> ids(n + 1), nodes(n + 1);
+        std::vector<double> vals(n + 1);
+        std::vector<int32_t> offs(n + 2), feats(n + 1);
+        int nb = 0, nf = 0;
+        check(mcorb_rig_get_lf_bow(rig_, 0, 0, ids.data(), vals.data(), n + 1, &nb, nodes.data(), offs.data(), n + 1, &nf, feats.data(), n + 1),
+              "mcorb_rig_get_lf_bow");
+        ORBVocabulary::fill(ids, vals, nb, nodes, offs, feats, nf, lfBoW, lfFeatVec);
+    }
     void fill_matches(const std::vector<int32_t> &tr, const std::vector<int32_t> &rays, int n, const std::vector<uint32_t> &w, int nw,
                       std::vector<IntraMatch> &matches, std::vector<unsigned int> &words_) const
     {

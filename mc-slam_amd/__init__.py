@@ -174,6 +174,37 @@ class Rig:
         (tracks, n_rays, words), as ORBVocabulary.match_rig_frames returns them"""
         return _read_tracks(self, frame0, nframes, slot)
 
+    # -- obtainLfFeatures + the LF set's transform inside every extraction job -------------------------------------------------
+    def set_lf(self, K_mats, R_mats, t_mats, total_feats=3000):
+        """camconfig_ K / R / t per camera: from now on every job of a vocabulary bound with match=True also runs obtainLfFeatures
+        on its BoW-guided tracks (words_ all 1, no segmentation masks) and the LF set's transform (FrontEnd.cpp:1009-1024).  Read
+        them with lf_features / lf_bow.  K_mats = None unbinds."""
+        if K_mats is None:
+            _lib.check(self.L.mcorb_rig_set_lf(self.h_rig, None, 0))
+            return
+        _lib.check(self.L.mcorb_rig_set_lf(self.h_rig, _cameras(self.ncams, K_mats, R_mats, t_mats), total_feats))
+
+    def lf_features(self, frame, slot=0):
+        """the last job's obtainLfFeatures of one frame -> (features as obtain_lf_features returns them, intramatch_size,
+        mono_size, words_fil)"""
+        n, ni, nm, nw = (C.c_int() for _ in range(4))
+        st = self.L.mcorb_rig_get_lf_features(self.h_rig, slot, frame, None, 0, C.byref(n), C.byref(ni), C.byref(nm), None, 0, C.byref(nw))
+        if st != E_CAP:
+            _lib.check(st)
+        out = np.empty(max(n.value, 1), _lib.LF_DTYPE)
+        wf = np.zeros(max(nw.value, 1), np.uint32)
+        _lib.check(self.L.mcorb_rig_get_lf_features(self.h_rig, slot, frame, out.ctypes.data, len(out), C.byref(n), C.byref(ni), C.byref(nm),
+                                                    wf.ctypes.data, len(wf), C.byref(nw)))
+        return out[:n.value].copy(), ni.value, nm.value, wf[:nw.value].copy()
+
+    def lf_bow(self, frame, slot=0):
+        """the last job's lfBoW / lfFeatVec of one frame -> (BowVector as (ids, values), FeatureVector as {node: features})"""
+        n = C.c_int()
+        st = self.L.mcorb_rig_get_lf_features(self.h_rig, slot, frame, None, 0, C.byref(n), None, None, None, 0, None)
+        if st != E_CAP:
+            _lib.check(st)
+        return _read_transform_lists(lambda *a: self.L.mcorb_rig_get_lf_bow(self.h_rig, slot, frame, *a), n.value)
+
     def undistortion_active(self, cam):
         """True if the reference would call cv::undistortPoints for this camera (set, and not passed by its zero test)"""
         v = self.L.mcorb_rig_undistortion_active(self.h_rig, cam)
@@ -594,6 +625,17 @@ def _read_transform_lists(fn, n):
     return bow, fv
 
 
+def _cameras(ncams, K_mats, R_mats, t_mats):
+    """mcorb_camera per camera: K and build_Rt(R, t) (FrontEnd.cpp:224)"""
+    cams = (_lib.Camera * ncams)()
+    for c in range(ncams):
+        K = np.asarray(K_mats[c], np.float64).reshape(3, 3)
+        Rt = np.hstack([np.asarray(R_mats[c], np.float64).reshape(3, 3), np.asarray(t_mats[c], np.float64).reshape(3, 1)])
+        cams[c].K[:] = K.ravel().tolist()
+        cams[c].Rt[:] = Rt.ravel().tolist()
+    return cams
+
+
 def _read_transforms(rig, img0, nimg, slot):
     out = []
     for m in range(img0, img0 + nimg):
@@ -774,6 +816,17 @@ class IntraMatch:
         self.mono = True
         self.n_rays = 0
 
+    @classmethod
+    def from_lf(cls, row):
+        """one entry of currentFrame->intraMatches after obtainLfFeatures (a row of Rig.lf_features' array)"""
+        m = cls(row["match_index"])
+        m.mono = bool(row["mono"])
+        m.n_rays = int(row["n_rays"])
+        m.uv_ref = (float(row["uv_ref"][0]), float(row["uv_ref"][1]))
+        m.point3D = np.array(row["point3d"], np.float64)
+        m.matchDesc = np.array(row["desc"], np.uint8)
+        return m
+
 
 class MultiCameraFrame:
     """Mirror of the extract + intra-rig-match members of MultiCameraFrame
@@ -789,6 +842,8 @@ class MultiCameraFrame:
         self.BoW_vecs, self.BoW_feats = [], []   # per camera, filled by extractFeaturesParallel once setVocabulary was called
         self._voc, self._voc_levelsup = None, 4
         self._rows_replaced = False   # setUndistorted() gave rows other than the rig's: the job's tracks do not apply
+        self._lf = False   # setLfConfig: extractFeaturesParallel() also fills intraMatches / lfBoW / lfFeatVec from the job
+        self.intraMatches, self.intramatch_size, self.mono_size, self.lfBoW, self.lfFeatVec = [], 0, 0, None, None
 
     def setData(self, img_set, segmap_set=None):
         """setData (MultiCameraFrame.cpp:95-152): accepts the reference's CV_32F [0,1] frames or u8."""
@@ -817,6 +872,10 @@ class MultiCameraFrame:
             tf = self.rig.bow_transforms(0, self.num_cams_)
             self.BoW_vecs = [bow for bow, _ in tf]
             self.BoW_feats = [fv for _, fv in tf]
+            if self._lf:   # obtainLfFeatures + orb_vocabulary->transform of the LF set (FrontEnd.cpp:1009-1024, :525)
+                feats, self.intramatch_size, self.mono_size, _ = self.rig.lf_features(0)
+                self.intraMatches = [IntraMatch.from_lf(row) for row in feats]
+                self.lfBoW, self.lfFeatVec = self.rig.lf_bow(0)
         self._matched = False
 
     extractFeatures = extractFeaturesParallel
@@ -839,6 +898,15 @@ class MultiCameraFrame:
         self._voc, self._voc_levelsup = voc, levelsup
         if voc is None:
             self.BoW_vecs, self.BoW_feats = [], []
+
+    def setLfConfig(self, K_mats, R_mats, t_mats, total_feats=3000):
+        """camconfig_ K / R / t for obtainLfFeatures (FrontEnd.cpp:213-593): after setVocabulary, extractFeaturesParallel() also
+        fills intraMatches (IntraMatch with matchDesc, point3D, uv_ref, mono, n_rays), intramatch_size, mono_size, lfBoW and
+        lfFeatVec as FrontEnd::processFrame leaves them (:1009-1024), made by the extraction job.  K_mats = None unbinds."""
+        self.rig.set_lf(K_mats, R_mats, t_mats, total_feats)
+        self._lf = K_mats is not None
+        if not self._lf:
+            self.intraMatches, self.intramatch_size, self.mono_size, self.lfBoW, self.lfFeatVec = [], 0, 0, None, None
 
     def setUndistorted(self, image_kps_undist):
         """image_kps_undist as UndistortKeyPoints (MultiCameraFrame.cpp:300-347) fills it for a distorted, unrectified rig

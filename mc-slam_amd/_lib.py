@@ -134,6 +134,11 @@ SIGNATURES = {
     "mcorb_host_select": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i]),
     "mcorb_host_resize_axis": (_i, [_i, _i, _i, _vp]),
     "mcorb_host_triangulate": (_i, [_vp, _vp, _i, _vp]),
+    "mcorb_host_triangulate_branch": (_i, [_vp, _vp, _i, _vp, _vp]),
+    "mcorb_rig_set_lf": (_i, [_vp, _vp, _i]),
+    "mcorb_rig_get_lf_features": (_i, [_vp, _i, _i, _vp, _i, _ip, _ip, _ip, _vp, _i, _ip]),
+    "mcorb_rig_get_lf_bow": (_i, [_vp, _i, _i, _vp, _vp, _i, _ip, _vp, _vp, _i, _ip, _vp, _i]),
+    "mcorb_dev_triangulate_selftest": (_i, [_i, _vp, _vp, _vp, _i, _vp, _vp]),
     "mcorb_host_geometry": (_i, [C.POINTER(Params), _i, _i, _vp]),
     "mcorb_synth_rig_frame": (_i, [C.c_uint32, _i, _i, _i, _i, _vp, _i]),
 }

@@ -146,10 +146,10 @@ static int build_vocab(int k, int L, int scoring, int weighting, const int32_t *
 // sorted by id and folded left to right, so every sum adds its terms in the order addWeight would have (bit-identical
 // doubles) and addIfNotExist keeps the first.
 typedef std::vector<std::pair<uint32_t, double>> BowList;
-static void assemble(const mcorb_vocab *v, const mcorb::BowRes *res, int n, BowList &bow,
+static void assemble(int weighting, int scoring, const mcorb::BowRes *res, int n, BowList &bow,
                      std::map<uint32_t, std::vector<int32_t>> &fv)
 {
-    const bool tf_like = v->weighting == 0 || v->weighting == 1;   // TF_IDF, TF
+    const bool tf_like = weighting == 0 || weighting == 1;   // TF_IDF, TF
     BowList raw;
     raw.reserve(n);
     for (int i = 0; i < n; i++) {
@@ -170,14 +170,14 @@ static void assemble(const mcorb_vocab *v, const mcorb::BowRes *res, int n, BowL
         }
     }
     // mustNormalize: L1_NORM, CHI_SQUARE, KL, BHATTACHARYYA -> L1; L2_NORM -> L2; DOT_PRODUCT -> none
-    const bool must = v->scoring != 5;
+    const bool must = scoring != 5;
     if (tf_like && !bow.empty() && !must) {
         const double nd = (double)bow.size();
         for (auto &e : bow) e.second /= nd;
     }
     if (must) {
         double norm = 0.0;
-        if (v->scoring == 1) {
+        if (scoring == 1) {
             for (auto &e : bow) norm += e.second * e.second;
             norm = sqrt(norm);
         } else {
@@ -186,6 +186,31 @@ static void assemble(const mcorb_vocab *v, const mcorb::BowRes *res, int n, BowL
         if (norm > 0.0)
             for (auto &e : bow) e.second /= norm;
     }
+}
+
+static void assemble(const mcorb_vocab *v, const mcorb::BowRes *res, int n, BowList &bow, std::map<uint32_t, std::vector<int32_t>> &fv)
+{
+    assemble(v->weighting, v->scoring, res, n, bow, fv);
+}
+
+static void to_image_out(const BowList &bow, const std::map<uint32_t, std::vector<int32_t>> &fv, BowImageOut &o)
+{
+    o.bow_ids.clear(); o.bow_vals.clear(); o.fv_nodes.clear(); o.fv_offsets.clear(); o.fv_feats.clear();
+    for (auto &e : bow) { o.bow_ids.push_back(e.first); o.bow_vals.push_back(e.second); }
+    for (auto &e : fv) {
+        o.fv_nodes.push_back(e.first);
+        o.fv_offsets.push_back((int32_t)o.fv_feats.size());
+        o.fv_feats.insert(o.fv_feats.end(), e.second.begin(), e.second.end());
+    }
+    o.fv_offsets.push_back((int32_t)o.fv_feats.size());
+}
+
+void mcorb::bow_assemble(int weighting, int scoring, const BowRes *res, int n, BowImageOut &o)
+{
+    BowList bow;
+    std::map<uint32_t, std::vector<int32_t>> fv;
+    assemble(weighting, scoring, res, n, bow, fv);
+    to_image_out(bow, fv, o);
 }
 
 static int emit(const BowList &bow, const std::map<uint32_t, std::vector<int32_t>> &fv, uint32_t *bow_ids,
@@ -370,15 +395,7 @@ extern "C" int mcorb_rig_transform_images(mcorb_rig *r, int slot, int img0, int 
         BowList bow;
         std::map<uint32_t, std::vector<int32_t>> fv;
         assemble(v, v->h_out + (size_t)i * kcap, s->h_nsel[img0 + i], bow, fv);
-        BowImageOut &o = s->bowvec[img0 + i];
-        o.bow_ids.clear(); o.bow_vals.clear(); o.fv_nodes.clear(); o.fv_offsets.clear(); o.fv_feats.clear();
-        for (auto &e : bow) { o.bow_ids.push_back(e.first); o.bow_vals.push_back(e.second); }
-        for (auto &e : fv) {
-            o.fv_nodes.push_back(e.first);
-            o.fv_offsets.push_back((int32_t)o.fv_feats.size());
-            o.fv_feats.insert(o.fv_feats.end(), e.second.begin(), e.second.end());
-        }
-        o.fv_offsets.push_back((int32_t)o.fv_feats.size());
+        to_image_out(bow, fv, s->bowvec[img0 + i]);
         s->bowvec_ok[img0 + i] = 1;
     }, R.pool_threads + s->index);
     return MCORB_OK;
@@ -693,6 +710,8 @@ extern "C" int mcorb_rig_match_bow_frames(mcorb_rig *r, int slot, int frame0, in
 int mcorb::bow_job_finish(Rig &R, Slot &s, int nimg)
 {
     const int C = R.ncams, kcap = R.geom.kcap, npairs = C * (C - 1) / 2;
+    // the LF stage's transform reads the descent results of the LF descriptors: brought back while the host replays the tracks
+    if (s.lf_job) HIPCHK(hipMemcpyAsync(s.h_lfres, s.d_bowres, (size_t)nimg * kcap * sizeof(BowRes), hipMemcpyDeviceToHost, s.st_dma));
     if ((int)s.bowvec.size() < R.max_images) { s.bowvec.resize(R.max_images); s.bowvec_ok.assign(R.max_images, 0); }
     R.pool->parallel_for(nimg, [&](int m, int) {
         const BowRecView r = bow_rec(s.h_bowrec, kcap, m);
@@ -721,6 +740,7 @@ int mcorb::bow_job_finish(Rig &R, Slot &s, int nimg)
         bow_replay(F, C, kcap, s.h_btab + (size_t)f * npairs * kcap, s.h_desc, f * C, ratio, s.bow[f]);
         s.bow_ok[f] = 1;
     }, R.pool_threads + s.index);
+    if (s.lf_job) return lf_job_finish(R, s, nframes);
     return MCORB_OK;
 }
 

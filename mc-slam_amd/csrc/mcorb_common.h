@@ -61,6 +61,14 @@ __host__ __device__ inline BowRecView bow_rec(int *base, int kcap, int m)
     return v;
 }
 
+// obtainLfFeatures inside the job (mcorb_rig_set_lf): k_lf_tracks' input per track with two views or more -- {first view in the
+// view list, view count, rig frame in the slot, output record} -- its views {camera, keypoint, raw point}, and its result per
+// track: the triangulated point, K_0 X projected to the reference camera (uv_ref), the 0.5 < z < 40 gate and the view whose
+// descriptor computeRepresentativeDesc picks (an index into the track's views)
+struct LfView { int32_t cam, kp; float x, y; };
+struct LfCam { double K[9], Rt[12]; };
+struct LfTrackOut { double X[3]; float uv[2]; int32_t accept, rep; };
+
 // Packed selected keypoint handed back to the device: level (4) | y (14) | x (14), level coordinates.
 __host__ __device__ inline uint32_t pack_sel(int level, int x, int y) { return ((uint32_t)level << 28) | ((uint32_t)y << 14) | (uint32_t)x; }
 

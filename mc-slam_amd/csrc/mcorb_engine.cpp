@@ -637,6 +637,9 @@ Rig::~Rig()
         (void)hipFree(s->d_bnfeats); (void)hipFree(s->d_bnfeat); (void)hipFree(s->d_brgbase); (void)hipFree(s->d_byv); (void)hipFree(s->d_brange);
         (void)hipFree(s->d_btab); (void)hipHostFree(s->h_btab);
         if (s->ev_b) (void)hipEventDestroy(s->ev_b);
+        (void)hipHostFree(s->h_lftrk); (void)hipFree(s->d_lftrk); (void)hipHostFree(s->h_lfview); (void)hipFree(s->d_lfview);
+        (void)hipHostFree(s->h_lfout); (void)hipHostFree(s->h_lfres);
+        if (s->ev_lf) (void)hipEventDestroy(s->ev_lf);
         if (s->ev_s) (void)hipEventDestroy(s->ev_s);
         if (s->ev_g) (void)hipEventDestroy(s->ev_g);
         if (s->graph_exec) (void)hipGraphExecDestroy(s->graph_exec);
@@ -656,6 +659,7 @@ Rig::~Rig()
     if (d_lut) (void)hipFree(d_lut);
     if (d_fasttab) (void)hipFree(d_fasttab);
     if (d_undist_cams) (void)hipFree(d_undist_cams);
+    if (d_lfcams) (void)hipFree(d_lfcams);
 }
 
 // An upload into a slot whose job is still running would overwrite the staging buffer and level 0 between the job's
@@ -1216,6 +1220,7 @@ int Rig::enqueue_gpu_job(Slot &s, const Job &j, bool then_match)
 void Rig::undist_job_start(Slot &s)
 {
     s.bow_job = bow_bind.flags;   // (the BoW stages' snapshot too: both are fixed while a job is in flight)
+    s.lf_job = lf_on && (bow_bind.flags & MCORB_BOW_MATCH);   // (and the LF stage's: it reads the job's BoW-guided tracks)
     s.undist_job = undist_on;
     s.undist_gen = undist_gen;
     std::fill(s.kps_undist_ok.begin(), s.kps_undist_ok.end(), (uint8_t)0);
@@ -1341,6 +1346,47 @@ int Rig::set_vocabulary(const BowBinding &b)
     }
     bow_bind = b.flags ? b : BowBinding{};
     bow_gen++;
+    return MCORB_OK;
+}
+
+// obtainLfFeatures inside the job (lf_job_finish).  Nothing of it runs, is allocated or is captured while no cameras are bound.
+int Rig::set_lf(const mcorb_camera *cams, int total_feats)
+{
+    if (cams && total_feats < 0) { set_error("set_lf: total_feats must be >= 0"); return MCORB_E_ARG; }
+    std::vector<std::unique_lock<std::mutex>> locks;
+    for (Slot *sp : slots) {
+        locks.emplace_back(sp->m);
+        if (sp->busy || sp->submitted) { set_error("set_lf: a submitted job has not been waited for"); return MCORB_E_STATE; }
+    }
+    HIPCHK(hipSetDevice(device));
+    if (cams && !d_lfcams) {   // first bind: the camera table and every slot's buffers, sized for one track per keypoint
+        HIPCHK(hipMalloc((void **)&d_lfcams, MCORB_MAX_CAMS * sizeof(LfCam)));
+        const size_t n = (size_t)max_images * geom.kcap;
+        for (Slot *sp : slots) {
+            HIPCHK(hipHostMalloc((void **)&sp->h_lftrk, n * sizeof(int4), hipHostMallocDefault));
+            HIPCHK(hipMalloc((void **)&sp->d_lftrk, n * sizeof(int4)));
+            HIPCHK(hipHostMalloc((void **)&sp->h_lfview, n * sizeof(LfView), hipHostMallocDefault));
+            HIPCHK(hipMalloc((void **)&sp->d_lfview, n * sizeof(LfView)));
+            HIPCHK(hipHostMalloc((void **)&sp->h_lfout, n * sizeof(LfTrackOut), hipHostMallocMapped | hipHostMallocPortable));
+            HIPCHK(hipHostMalloc((void **)&sp->h_lfres, n * sizeof(BowRes), hipHostMallocDefault));
+            sp->lf_trk_cap = sp->lf_view_cap = n;
+            HIPCHK(hipEventCreateWithFlags(&sp->ev_lf, hipEventDisableTiming));
+        }
+    }
+    if (cams) {
+        std::vector<LfCam> dc((size_t)ncams);
+        for (int c = 0; c < ncams; c++) {
+            memcpy(dc[c].K, cams[c].K, sizeof(dc[c].K));
+            memcpy(dc[c].Rt, cams[c].Rt, sizeof(dc[c].Rt));
+        }
+        HIPCHK(hipMemcpy(d_lfcams, dc.data(), dc.size() * sizeof(LfCam), hipMemcpyHostToDevice));
+        lf_cams.assign(cams, cams + ncams);
+        lf_total_feats = total_feats;
+    } else {
+        lf_cams.clear();
+    }
+    lf_on = cams != nullptr;
+    lf_gen++;
     return MCORB_OK;
 }
 
@@ -1480,7 +1526,7 @@ int Rig::run_gpu_selected(Slot &s, const Job &j, bool then_match)
     } turn(*this);
     if (graphed) {
         const Slot::GraphKey key{nimg, then_match ? 1 : 0, j.nframes, j.lap0, j.lap1, j.dist_thresh, j.ratio, undist_on ? 1 : 0,
-                                 bow_bind.flags, bow_bind.flags ? bow_bind.levelsup : 0, bow_gen};
+                                 bow_bind.flags, bow_bind.flags ? bow_bind.levelsup : 0, bow_gen, lf_on ? 1 : 0, lf_gen};
         if (!s.graph_exec || memcmp(&key, &s.graph_key, sizeof(key)) != 0) {
             if (s.graph_exec) { (void)hipGraphExecDestroy(s.graph_exec); s.graph_exec = nullptr; }
             hipGraph_t graph = nullptr;

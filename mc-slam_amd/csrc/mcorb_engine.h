@@ -113,6 +113,17 @@ struct BowImageOut {
     std::vector<int32_t> fv_offsets, fv_feats;
 };
 
+// obtainLfFeatures of one frame (mcorb_rig_obtain_lf_features, and the job's stage of mcorb_rig_set_lf): the features in output
+// order, words_fil, intramatch_size / mono_size; src: per feature, the slot-local keypoint its descriptor is (image * kcap + k);
+// bow: the LF set's transform() (FrontEnd.cpp:525), filled by the job's stage only
+struct LfFrameOut {
+    std::vector<mcorb_lf_feature> feats;
+    std::vector<uint32_t> words_fil;
+    std::vector<int32_t> src;
+    int intramatch_size = 0, mono_size = 0;
+    BowImageOut bow;
+};
+
 struct Slot {
     Rig *rig = nullptr;
     int index = 0;
@@ -167,10 +178,11 @@ struct Slot {
     int fallbacks = 0;         // jobs of this slot the host stage had to redo (a tree below the bucketing depth)
     hipEvent_t ev_s = nullptr; // k_select + k_assemble finished
     hipEvent_t ev_g = nullptr; // in front of a replayed job graph
-    // (bow_*: the vocabulary binding the job was captured with -- its tables and levelsup are kernel arguments; bow_gen counts
+    // (lf / lf_gen: mcorb_rig_set_lf's binding and set calls -- the LF stage runs after the graph, the key keeps it in view;
+    // bow_*: the vocabulary binding the job was captured with -- its tables and levelsup are kernel arguments; bow_gen counts
     // mcorb_rig_set_vocabulary calls, so a freed vocabulary whose address comes back never replays a stale graph.  4-byte fields
     // only: the key is compared with memcmp)
-    struct GraphKey { int nimg, match, nframes, lap0, lap1; float dist_thresh, ratio; int undist, bow_flags, bow_levelsup; unsigned bow_gen; };
+    struct GraphKey { int nimg, match, nframes, lap0, lap1; float dist_thresh, ratio; int undist, bow_flags, bow_levelsup; unsigned bow_gen; int lf; unsigned lf_gen; };
     hipGraphExec_t graph_exec = nullptr;   // the captured job (run_gpu_selected), valid for graph_key
     GraphKey graph_key = {};
     unsigned job_counter = 0;
@@ -197,7 +209,10 @@ struct Slot {
     {
         std::fill(bow_ok.begin(), bow_ok.end(), (uint8_t)0);
         std::fill(bowvec_ok.begin(), bowvec_ok.end(), (uint8_t)0);
+        std::fill(lf_ok.begin(), lf_ok.end(), (uint8_t)0);
     }
+    std::vector<LfFrameOut> lf;     // per frame: the job's obtainLfFeatures + LF transform (mcorb_rig_set_lf)
+    std::vector<uint8_t> lf_ok;
     float timing[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     // UndistortKeyPoints (mcorb_rig_set_undistortion): k_undistort's points of the images in the slot, [image][kcap] (d_ device,
     // h_ host-mapped pinned; both allocated at the rig's first set call, never while no camera has undistortion set); a fork / join
@@ -219,6 +234,17 @@ struct Slot {
     int4 *d_btab = nullptr, *h_btab = nullptr;
     hipEvent_t ev_b = nullptr;
     int bow_job = 0;              // MCORB_BOW_* flags the images in the slot were extracted with (0: no BoW stage ran)
+    // obtainLfFeatures inside the job (mcorb_rig_set_lf), allocated at the rig's first LF bind, never while nothing was bound:
+    // k_lf_tracks' tracks and views (h_ pinned, staged for one H2D copy; d_ device), its per-track records (host-mapped pinned,
+    // written by the kernel), the job's descent results (pinned copy of d_bowres: the LF set's transform reads them); capacities
+    // in tracks / views (grown on a job that needs more); ev_lf: the stage's kernel and copies are done
+    int4 *h_lftrk = nullptr, *d_lftrk = nullptr;
+    LfView *h_lfview = nullptr, *d_lfview = nullptr;
+    LfTrackOut *h_lfout = nullptr;
+    BowRes *h_lfres = nullptr;
+    size_t lf_trk_cap = 0, lf_view_cap = 0;
+    hipEvent_t ev_lf = nullptr;
+    bool lf_job = false;          // the job ran the LF stage (LF bound and the vocabulary bound with MCORB_BOW_MATCH)
     // image_kps_undist of the images, built on first read from kps and h_undist (Rig::undist_records)
     std::vector<std::vector<mcorb_keypoint>> kps_undist;
     std::vector<uint8_t> kps_undist_ok;
@@ -317,6 +343,14 @@ public:
     };
     BowBinding bow_bind;
     unsigned bow_gen = 0;
+    // obtainLfFeatures inside the job (mcorb_rig_set_lf): the cameras (host copy and the device copy k_lf_tracks reads) and
+    // total_feats; lf_gen counts the set calls
+    bool lf_on = false;
+    int lf_total_feats = 3000;
+    std::vector<mcorb_camera> lf_cams;
+    LfCam *d_lfcams = nullptr;
+    unsigned lf_gen = 0;
+    int set_lf(const mcorb_camera *cams, int total_feats);
     int set_vocabulary(const BowBinding &b);
     int check_job_shape(const Job &j) const;   // a bound MCORB_BOW_MATCH needs whole frames
 
@@ -344,6 +378,11 @@ private:
 // the host half of a job's BoW stages (mcorb_bow.cpp): the BowImageOut of every image from k_bow_fold's records and, with
 // MCORB_BOW_MATCH, the reference's serial track bookkeeping of every frame on the worker pool
 int bow_job_finish(Rig &R, Slot &s, int nimg);
+// the job's obtainLfFeatures stage (mcorb_lf.cpp), called by bow_job_finish once the frames' tracks are replayed: k_lf_tracks on
+// every track of every frame in one launch, then the order-dependent bookkeeping and the LF transform per frame on the worker pool
+int lf_job_finish(Rig &R, Slot &s, int nframes);
+// transform()'s BowVector / FeatureVector (mcorb_bow.cpp's assemble) of n descent results, for the given weighting / scoring
+void bow_assemble(int weighting, int scoring, const BowRes *res, int n, BowImageOut &o);
 
 }  // namespace mcorb
 

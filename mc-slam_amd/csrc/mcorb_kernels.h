@@ -109,4 +109,11 @@ void launch_bow_descend(hipStream_t st, const uint8_t *desc, int n, const int *c
                         const void *child_desc, const int *child_id, const int *word_id, const double *weight, int nid_level,
                         BowRes *out);
 
+// k_lf_tracks (mcorb_lf_gpu.hip): the per-track half of obtainLfFeatures for ntr tracks (trk: {first view, view count, frame,
+// output record}, views: LfView) of the slot's descriptors (kcap-strided, image = frame * ncams + cam), records to out[record]
+void launch_lf_tracks(hipStream_t st, const int4 *trk, const LfView *views, int ntr, const LfCam *cams, const uint8_t *desc, int kcap,
+                      int ncams, LfTrackOut *out);
+// the same triangulation on n arbitrary problems (mcorb_dev_triangulate_selftest)
+void launch_tri_selftest(hipStream_t st, const double *x, const double *P, const int *nv, const int *voff, int n, double *X, int *branch);
+
 }  // namespace mcorb

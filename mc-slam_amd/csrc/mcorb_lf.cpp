@@ -11,7 +11,9 @@
 // design matrix, more views -> the 3n x (4+n) "x = alpha P X" design, null vector by SVD (cv::SVD::solveZ).  Restated here with
 // the smallest eigenvector of the design's Gram matrix in FP64 (inverse iteration): the null vector of a
 // full-column-rank-minus-one matrix is unique up to scale, so any stable method returns the same point to ~1e-11 relative;
-// parity for this step is tolerance-based (1e-9) and UNPINNED.
+// parity for this step is tolerance-based (1e-9) and UNPINNED.  The per-track arithmetic (triangulation, representative
+// descriptor) is in mcorb_triangulate.h, shared with k_lf_tracks (mcorb_lf_gpu.hip): the extraction job's stage (lf_job_finish,
+// mcorb_rig_set_lf) gives the same bits as this host path.
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -25,174 +27,9 @@
 #include <vector>
 
 #include "mcorb_engine.h"
+#include "mcorb_triangulate.h"
 
 using namespace mcorb;
-
-namespace {
-
-// right singular vector of the smallest singular value of the m x n matrix A (row-major, m >= n, n <= 20)
-// = eigenvector of the smallest eigenvalue of G = A^T A, found by inverse iteration: G + delta I is factored ONCE (LU with
-// partial pivoting, n^3 / 3 multiplications), every further step is two triangular solves.  The design matrices of the
-// triangulation have one singular value far below the rest (zero for exact correspondences): unshifted steps until the
-// iterate has settled, then Rayleigh-quotient shifts (a fresh n^3 / 3 factorisation per step, nothing at n = 4 .. 8) until
-// two successive iterates agree to 1e-15.  Accuracy: eps |G| / (lambda_2 - lambda_1) on the unit vector, 1e-12 .. 1e-11
-// for this geometry (the one-sided Jacobi SVD it replaces worked on A itself, eps / sigma_2, at 50 x the cost: 60 sweeps
-// of 6 .. 28 column pairs per track were 10 of the 13 ms a 4-camera frame took in round 2).  The test against LAPACK's SVD
-// (600 cases of 2 .. 6 views, small and gross noise) holds its 1e-9.
-constexpr int kLfMaxN = 4 + MCORB_MAX_CAMS, kLfMaxM = 3 * MCORB_MAX_CAMS;
-// M, N > 0: compile-time shape (the 2-, 3- and 4-view designs are almost all the tracks of a 4-camera rig: with the loop
-// bounds known the compiler unrolls and keeps G / LU in registers); M = N = 0: run-time shape
-template <int M, int N>
-inline void null_vector_t(const double *A, int m_rt, int n_rt, double *x)
-{
-    const int m = M > 0 ? M : m_rt, n = N > 0 ? N : n_rt;
-    double G[kLfMaxN * kLfMaxN], LU[kLfMaxN * kLfMaxN];
-    int piv[kLfMaxN];
-    double tr = 0.0;
-    for (int p = 0; p < n; p++)
-        for (int q = p; q < n; q++) {
-            double sacc = 0.0;
-            for (int i = 0; i < m; i++) sacc += A[i * n + p] * A[i * n + q];
-            G[p * n + q] = G[q * n + p] = sacc;
-            if (p == q) tr += sacc;
-        }
-    if (!(tr > 0.0)) { for (int i = 0; i < n; i++) x[i] = i == n - 1 ? 1.0 : 0.0; return; }
-    const double pivmin = 1e-30 * tr;
-    // factor G - shift I (LU, partial pivoting); a vanishing pivot is nudged: the solve then blows up along the null vector,
-    // which is the point of inverse iteration
-    auto factor = [&](double shift) {
-        for (int i = 0; i < n * n; i++) LU[i] = G[i];
-        for (int i = 0; i < n; i++) LU[i * n + i] -= shift;
-        for (int k = 0; k < n; k++) {
-            int pk = k;
-            for (int i = k + 1; i < n; i++) if (fabs(LU[i * n + k]) > fabs(LU[pk * n + k])) pk = i;
-            piv[k] = pk;
-            if (pk != k) for (int j = 0; j < n; j++) std::swap(LU[k * n + j], LU[pk * n + j]);
-            double d = LU[k * n + k];
-            // (a shift that IS an eigenvalue to the last bit can leave an exactly zero pivot; the nudge must keep the solve
-            // finite -- 1 / 1e-300 squared overflows, and the normalisation then turns the iterate into NaNs)
-            if (fabs(d) < pivmin) { d = d < 0 ? -pivmin : pivmin; LU[k * n + k] = d; }
-            const double inv = 1.0 / d;
-            for (int i = k + 1; i < n; i++) {
-                const double f = LU[i * n + k] * inv;
-                LU[i * n + k] = f;
-                if (f != 0.0) for (int j = k + 1; j < n; j++) LU[i * n + j] -= f * LU[k * n + j];
-            }
-        }
-    };
-    double v[N > 0 ? N : kLfMaxN], y[N > 0 ? N : kLfMaxN];
-    auto solve_step = [&]() -> double {   // v <- normalised (G - shift I)^-1 v, sign kept; returns the largest change of a component
-        for (int i = 0; i < n; i++) y[i] = v[i];
-        for (int k = 0; k < n; k++)            // P (all row exchanges first: the multipliers sit in their final rows)
-            if (piv[k] != k) std::swap(y[k], y[piv[k]]);
-        for (int k = 0; k < n; k++)            // L
-            for (int i = k + 1; i < n; i++) y[i] -= LU[i * n + k] * y[k];
-        for (int k = n - 1; k >= 0; k--) {     // U
-            double t = y[k];
-            for (int j = k + 1; j < n; j++) t -= LU[k * n + j] * y[j];
-            y[k] = t / LU[k * n + k];
-        }
-        double nn = 0.0, dotp = 0.0;
-        for (int i = 0; i < n; i++) nn += y[i] * y[i];
-        nn = 1.0 / sqrt(nn);
-        for (int i = 0; i < n; i++) { y[i] *= nn; dotp += y[i] * v[i]; }
-        const double sgn = dotp < 0 ? -1.0 : 1.0;
-        double diff = 0.0;
-        for (int i = 0; i < n; i++) { y[i] *= sgn; diff = std::max(diff, fabs(y[i] - v[i])); v[i] = y[i]; }
-        return diff;
-    };
-    auto rayleigh = [&]() {
-        double r = 0.0;
-        for (int p = 0; p < n; p++) {
-            double gp = 0.0;
-            for (int q = 0; q < n; q++) gp += G[p * n + q] * v[q];
-            r += v[p] * gp;
-        }
-        return r;
-    };
-    for (int i = 0; i < n; i++) v[i] = 1.0 / sqrt((double)n) * (1.0 + 0.01 * i);   // any start with a component along the answer
-    // Unshifted steps -- which can only converge to the eigenvector of the eigenvalue nearest zero, the smallest (G is positive
-    // semi-definite) -- until the iterate has settled to 1e-3; only then Rayleigh-quotient shifts (cubic from there: two or
-    // three steps where the unshifted iteration, contracting by lambda_1 / lambda_2 = 0.1 .. 0.5 on tracks with a wrong
-    // correspondence, needs dozens).  Shifting earlier is not safe: a start vector that happens to be nearly orthogonal to the
-    // answer still has its quotient near lambda_2 after a few steps, and the shifted iteration then converges THERE (seen on 2 %
-    // of real tracks).  Should a shifted step move the iterate by more than 1e-2 it has left the basin: back to unshifted steps.
-    factor(-1e-14 * tr);   // (keeps the factorisation away from an exactly singular matrix)
-    double diff = 1.0;
-    for (int it = 0; it < 400 && diff >= 1e-3; it++) diff = solve_step();
-    bool shifted = false;
-    for (int it = 0; it < 8 && diff >= 1e-15; it++) {
-        factor(rayleigh());
-        diff = solve_step();
-        shifted = true;
-        if (diff > 1e-2) break;
-    }
-    if (shifted) {
-        // "settled" can also mean: sitting next to ANOTHER eigenvector with a tiny component along the wanted one (an unlucky
-        // start); the shifted steps then polish that one.  Sylvester: G - (rho - tol) I has as many negative pivots in its LDL^T
-        // as G has eigenvalues below rho - tol -- none when rho is the smallest.  Otherwise: unshifted iteration to the end.
-        const double rho = rayleigh(), tol = 1e-10 * tr + 1e-3 * fabs(rho);
-        bool smallest = diff <= 1e-2;   // (false for a NaN too)
-        if (smallest) {
-            for (int i = 0; i < n * n; i++) LU[i] = G[i];
-            for (int i = 0; i < n; i++) LU[i * n + i] -= rho - tol;
-            for (int k = 0; k < n && smallest; k++) {
-                const double d = LU[k * n + k];
-                if (!(d > 0.0)) { smallest = false; break; }
-                for (int i = k + 1; i < n; i++) {
-                    const double f = LU[i * n + k] / d;
-                    for (int j = k + 1; j < n; j++) LU[i * n + j] -= f * LU[k * n + j];
-                }
-            }
-        }
-        if (!smallest) {
-            for (int i = 0; i < n; i++) v[i] = 1.0 / sqrt((double)n) * (1.0 + 0.01 * i);
-            factor(-1e-14 * tr);
-            diff = 1.0;
-            for (int k = 0; k < 2000 && diff >= 1e-15; k++) diff = solve_step();
-        }
-    }
-    for (int i = 0; i < n; i++) x[i] = v[i];
-}
-void null_vector(const double *A, int m, int n, double *x)
-{
-    if (m == 4 && n == 4) null_vector_t<4, 4>(A, m, n, x);
-    else if (m == 9 && n == 7) null_vector_t<9, 7>(A, m, n, x);
-    else if (m == 12 && n == 8) null_vector_t<12, 8>(A, m, n, x);
-    else null_vector_t<0, 0>(A, m, n, x);
-}
-
-// cv::sfm::triangulatePoints for one point seen in nv views: x = normalised image coordinates, P = 3x4 [R|t] (row-major)
-void triangulate(const double *x, const double *const *P, int nv, double X[3])
-{
-    double h[4];
-    if (nv == 2) {   // triangulateDLT
-        double D[16];
-        for (int i = 0; i < 4; i++) {
-            D[0 * 4 + i] = x[0] * P[0][8 + i] - P[0][0 + i];
-            D[1 * 4 + i] = x[1] * P[0][8 + i] - P[0][4 + i];
-            D[2 * 4 + i] = x[2] * P[1][8 + i] - P[1][0 + i];
-            D[3 * 4 + i] = x[3] * P[1][8 + i] - P[1][4 + i];
-        }
-        null_vector(D, 4, 4, h);
-    } else {         // triangulateNViews: [-P_i | x_i in column 4+i] (X, alpha_1..alpha_n)^T = 0
-        const int m = 3 * nv, n = 4 + nv;
-        double D[kLfMaxM * kLfMaxN], sol[kLfMaxN];
-        for (int i = 0; i < m * n; i++) D[i] = 0.0;
-        for (int i = 0; i < nv; i++) {
-            for (int jj = 0; jj < 3; jj++)
-                for (int ii = 0; ii < 4; ii++) D[(size_t)(3 * i + jj) * n + ii] = -P[i][4 * jj + ii];
-            D[(size_t)(3 * i + 0) * n + 4 + i] = x[2 * i];
-            D[(size_t)(3 * i + 1) * n + 4 + i] = x[2 * i + 1];
-            D[(size_t)(3 * i + 2) * n + 4 + i] = 1.0;
-        }
-        null_vector(D, m, n, sol);
-        for (int i = 0; i < 4; i++) h[i] = sol[i];
-    }
-    for (int i = 0; i < 3; i++) X[i] = h[i] / h[3];   // homogeneousToEuclidean
-}
-
-}  // namespace
 
 // host-stage hook for the CPU test-suite: the triangulation alone (x: nv normalised points, P: nv row-major 3x4 matrices)
 extern "C" int mcorb_host_triangulate(const double *x, const double *P, int nv, double X[3])
@@ -204,18 +41,18 @@ extern "C" int mcorb_host_triangulate(const double *x, const double *P, int nv, 
     return MCORB_OK;
 }
 
-// obtainLfFeatures of one frame of a slot.  parallel_tri: spread the triangulations over the worker pool (a single frame per
-// call); the batched entry point runs whole frames as pool tasks instead and passes false.
-static int lf_one_frame(Rig &R, Slot *s, int slot, int frame, const int32_t *tracks, int ntracks, const uint32_t *words,
-                        const mcorb_camera *cams, const float *const *seg_masks, int seg_stride, const mcorb_keypoint *const *kps_undist,
-                        int total_feats, mcorb_lf_feature *out, int cap, int *n_out, int *intramatch_size_out, int *mono_size_out,
-                        uint32_t *words_fil, int cap_words, int *nwords_fil_out, bool parallel_tri)
+// obtainLfFeatures of one frame of a slot into o (feats, words_fil, the two sizes, and in o.src the image-local keypoint of every
+// feature's descriptor: m * kcap + k, m the slot's image).  parallel_tri: spread the triangulations over the worker pool (a single
+// frame per call); the batched entry point runs whole frames as pool tasks instead and passes false.  pre (the extraction job's
+// stage, lf_job_finish): k_lf_tracks' record of every track with two views or more, indexed like the tracks; the host then
+// triangulates nothing and takes the point, uv_ref and representative view from the records (same arithmetic, same bits).
+static int lf_frame_core(Rig &R, Slot *s, int slot, int frame, const int32_t *tracks, int ntracks, const uint32_t *words,
+                         const mcorb_camera *cams, const float *const *seg_masks, int seg_stride, const mcorb_keypoint *const *kps_undist,
+                         int total_feats, const LfTrackOut *pre, LfFrameOut &o, bool parallel_tri)
 {
-    if (n_out) *n_out = 0;
-    if (intramatch_size_out) *intramatch_size_out = 0;
-    if (mono_size_out) *mono_size_out = 0;
-    if (nwords_fil_out) *nwords_fil_out = 0;
-    if (ntracks < 0 || (ntracks && !tracks) || !cams || !out || cap < 0) {
+    o.feats.clear(); o.words_fil.clear(); o.src.clear();
+    o.intramatch_size = o.mono_size = 0;
+    if (ntracks < 0 || (ntracks && !tracks) || !cams) {
         set_error("obtain_lf_features: bad argument");
         return MCORB_E_ARG;
     }
@@ -246,13 +83,14 @@ static int lf_one_frame(Rig &R, Slot *s, int slot, int frame, const int32_t *tra
     // mono candidates are kept as (camera, keypoint) only: every one of them becomes the same kind of feature (:396-412 and
     // :489-512 fill the same fields), and only the best total_feats - intramatch_size are materialised after the sort
     struct MonoRef { int cam, kp; };
-    std::vector<mcorb_lf_feature> intra;
+    std::vector<mcorb_lf_feature> &intra = o.feats;
     std::vector<MonoRef> mono_keypoints;
     std::vector<float> responses;
-    std::vector<uint32_t> wfil;
+    std::vector<uint32_t> &wfil = o.words_fil;
+    std::vector<int32_t> &src = o.src;
     size_t nkp_total = 0;
     for (int c = 0; c < C; c++) nkp_total += KP(c).size();
-    intra.reserve((size_t)std::max(total_feats, ntracks) + 8); mono_keypoints.reserve(nkp_total + 8); responses.reserve(nkp_total + 8);
+    intra.reserve((size_t)std::max(total_feats, ntracks) + 8); src.reserve(intra.capacity()); mono_keypoints.reserve(nkp_total + 8); responses.reserve(nkp_total + 8);
     int intramatch_size = 0, mono_size = 0;
     auto blank = [&]() {
         mcorb_lf_feature f;
@@ -265,8 +103,8 @@ static int lf_one_frame(Rig &R, Slot *s, int slot, int frame, const int32_t *tra
     // (a null vector by Jacobi sweeps per track was 10 of the 13 ms this call took for 2 100 tracks); the bookkeeping below
     // then walks the tracks in order, as the reference does.
     struct Tri { double X[3]; };
-    std::vector<Tri> tri((size_t)ntracks);
-    {
+    std::vector<Tri> tri(pre ? 0 : (size_t)ntracks);
+    if (!pre) {
         constexpr int kChunk = 64;
         const std::function<void(int, int)> tri_task = [&](int chunk, int) {
             for (int ind = chunk * kChunk; ind < std::min(ntracks, (chunk + 1) * kChunk); ind++) {
@@ -314,20 +152,19 @@ static int lf_one_frame(Rig &R, Slot *s, int slot, int frame, const int32_t *tra
             }
         }
         if (num_views > 1) {
-            const double *X = tri[ind].X;                        // cv::sfm::triangulatePoints of the views kept above (:291-306)
-            if (X[2] < 40 && X[2] > 0.5) {                       // (:309)
+            const double *X = pre ? pre[ind].X : tri[ind].X;     // cv::sfm::triangulatePoints of the views kept above (:291-306)
+            if (pre ? pre[ind].accept != 0 : (X[2] < 40 && X[2] > 0.5)) {   // (:309)
                 // K_mats_[0] * pt3d (:339-341): the point is taken in the reference camera's frame
                 const double *K0 = cams[0].K;
                 const double px = K0[0] * X[0] + K0[1] * X[1] + K0[2] * X[2], py = K0[3] * X[0] + K0[4] * X[1] + K0[5] * X[2],
                              pz = K0[6] * X[0] + K0[7] * X[1] + K0[8] * X[2];
                 if (words) wfil.push_back(words[ind]);
-                uint8_t packed[MCORB_MAX_CAMS * 32];
-                for (int ii = 0; ii < num_views; ii++) memcpy(packed + 32 * ii, descs[ii], 32);
-                const int rep = mcorb_representative_desc(packed, num_views);   // computeRepresentativeDesc (:349)
+                const int rep = pre ? pre[ind].rep : representative_desc(descs, num_views);   // computeRepresentativeDesc (:349)
                 memcpy(temp.desc, descs[rep], 32);
+                src.push_back((m0 + view_inds[rep]) * kcap + temp.match_index[view_inds[rep]]);
                 temp.point3d[0] = X[0]; temp.point3d[1] = X[1]; temp.point3d[2] = X[2];
-                temp.uv_ref[0] = (float)(px / pz);               // cv::Point2f(expected_x, expected_y)
-                temp.uv_ref[1] = (float)(py / pz);
+                temp.uv_ref[0] = pre ? pre[ind].uv[0] : (float)(px / pz);   // cv::Point2f(expected_x, expected_y)
+                temp.uv_ref[1] = pre ? pre[ind].uv[1] : (float)(py / pz);
                 temp.mono = 0;
                 temp.n_rays = num_views;
                 intra.push_back(temp);
@@ -361,6 +198,7 @@ static int lf_one_frame(Rig &R, Slot *s, int slot, int frame, const int32_t *tra
         mcorb_lf_feature f = blank();
         f.match_index[mr.cam] = mr.kp;
         memcpy(f.desc, DESC(mr.cam, mr.kp), 32);
+        src.push_back((m0 + mr.cam) * kcap + mr.kp);
         f.uv_ref[0] = KPU(mr.cam, mr.kp).x; f.uv_ref[1] = KPU(mr.cam, mr.kp).y;
         f.n_rays = 1;
         f.mono = 1;
@@ -372,17 +210,43 @@ static int lf_one_frame(Rig &R, Slot *s, int slot, int frame, const int32_t *tra
     std::sort(wfil.begin(), wfil.end());
     wfil.erase(std::unique(wfil.begin(), wfil.end()), wfil.end());
 
-    if (n_out) *n_out = (int)intra.size();
-    if (intramatch_size_out) *intramatch_size_out = intramatch_size;
-    if (mono_size_out) *mono_size_out = mono_size;
-    if (nwords_fil_out) *nwords_fil_out = (int)wfil.size();
-    if ((int)intra.size() > cap || (words_fil && (int)wfil.size() > cap_words)) { set_error("obtain_lf_features: output too small"); return MCORB_E_CAP; }
-    if (!intra.empty()) memcpy(out, intra.data(), intra.size() * sizeof(mcorb_lf_feature));
-    if (words_fil && !wfil.empty()) memcpy(words_fil, wfil.data(), wfil.size() * sizeof(uint32_t));
+    o.intramatch_size = intramatch_size;
+    o.mono_size = mono_size;
     if (prof && frame == 0)
-        fprintf(stderr, "[mcorb host prof] obtain_lf_features frame 0: setup + triangulation %.0f us, track bookkeeping %.0f, mono pool %.0f, sort + fill %.0f, copy out %.0f\n",
-                us(T0, T1), us(T1, T2), us(T2, T3), us(T3, T4), us(T4, now()));
+        fprintf(stderr, "[mcorb host prof] obtain_lf_features frame 0%s: setup + triangulation %.0f us, track bookkeeping %.0f, mono pool %.0f, sort + fill %.0f, words %.0f\n",
+                pre ? " (job)" : "", us(T0, T1), us(T1, T2), us(T2, T3), us(T3, T4), us(T4, now()));
     return MCORB_OK;
+}
+
+// o into the caller's arrays, with the getters' capacity convention (the counts are set either way)
+static int lf_copy_out(const LfFrameOut &o, mcorb_lf_feature *out, int cap, int *n_out, int *intramatch_size_out, int *mono_size_out,
+                       uint32_t *words_fil, int cap_words, int *nwords_fil_out)
+{
+    if (n_out) *n_out = (int)o.feats.size();
+    if (intramatch_size_out) *intramatch_size_out = o.intramatch_size;
+    if (mono_size_out) *mono_size_out = o.mono_size;
+    if (nwords_fil_out) *nwords_fil_out = (int)o.words_fil.size();
+    if ((int)o.feats.size() > cap || (words_fil && (int)o.words_fil.size() > cap_words)) { set_error("obtain_lf_features: output too small"); return MCORB_E_CAP; }
+    if (!o.feats.empty()) memcpy(out, o.feats.data(), o.feats.size() * sizeof(mcorb_lf_feature));
+    if (words_fil && !o.words_fil.empty()) memcpy(words_fil, o.words_fil.data(), o.words_fil.size() * sizeof(uint32_t));
+    return MCORB_OK;
+}
+
+static int lf_one_frame(Rig &R, Slot *s, int slot, int frame, const int32_t *tracks, int ntracks, const uint32_t *words,
+                        const mcorb_camera *cams, const float *const *seg_masks, int seg_stride, const mcorb_keypoint *const *kps_undist,
+                        int total_feats, mcorb_lf_feature *out, int cap, int *n_out, int *intramatch_size_out, int *mono_size_out,
+                        uint32_t *words_fil, int cap_words, int *nwords_fil_out, bool parallel_tri)
+{
+    if (n_out) *n_out = 0;
+    if (intramatch_size_out) *intramatch_size_out = 0;
+    if (mono_size_out) *mono_size_out = 0;
+    if (nwords_fil_out) *nwords_fil_out = 0;
+    if (!out || cap < 0) { set_error("obtain_lf_features: bad argument"); return MCORB_E_ARG; }
+    LfFrameOut o;
+    const int st = lf_frame_core(R, s, slot, frame, tracks, ntracks, words, cams, seg_masks, seg_stride, kps_undist, total_feats, nullptr, o,
+                                 parallel_tri);
+    if (st != MCORB_OK) return st;
+    return lf_copy_out(o, out, cap, n_out, intramatch_size_out, mono_size_out, words_fil, cap_words, nwords_fil_out);
 }
 
 // kps_undist of frames [frame0, frame0 + nframes) with the rig's own undistorted set filled in where the caller passes NULL (as a
@@ -470,5 +334,232 @@ extern "C" int mcorb_rig_obtain_lf_features_frames(mcorb_rig *r, int slot, int f
     }, R.pool_threads + slot);
     for (int f = 0; f < nframes; f++)
         if (status[f] != MCORB_OK) { set_error("frame " + std::to_string(frame0 + f) + ": " + errs[f]); return status[f]; }
+    return MCORB_OK;
+}
+
+// ---------------------------------------------------------------------------
+// obtainLfFeatures + the LF set's transform inside the extraction job (mcorb_rig_set_lf).  FrontEnd::processFrame calls
+// obtainLfFeatures right after computeIntraMatches(matches_map, words_) with words_ overwritten by ones (FrontEnd.cpp:1010) and
+// all-zero segmentation masks (mc_slam_app.cpp:224): every view of a track is kept, words_fil is {1} or empty.
+// ---------------------------------------------------------------------------
+#define HIPCHK(x)                                                                      \
+    do {                                                                               \
+        hipError_t e_ = (x);                                                           \
+        if (e_ != hipSuccess) {                                                        \
+            set_error(std::string(#x) + ": " + hipGetErrorString(e_));                 \
+            return MCORB_E_HIP;                                                        \
+        }                                                                              \
+    } while (0)
+
+int mcorb::lf_job_finish(Rig &R, Slot &s, int nframes)
+{
+    const int C = R.ncams, kcap = R.geom.kcap;
+    static const bool prof = getenv("MCORB_HOST_PROF") != nullptr;
+    auto now = [] { return std::chrono::steady_clock::now(); };
+    auto us = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::micro>(b - a).count(); };
+    const auto T0 = now();
+    if ((int)s.lf.size() < R.max_frames) { s.lf.resize(R.max_frames); s.lf_ok.assign(R.max_frames, 0); }
+    // 1. k_lf_tracks' input: the tracks with two views or more, binned by view count (2, 3, 4, more) so that a wave runs one
+    //    shape; record = the track's index among all tracks of the job (tbase[f] + t), the views in camera order
+    constexpr int kBins = 4;
+    auto bin_of = [](int nv) { return nv <= 4 ? nv - 2 : 3; };
+    std::vector<int> tbase((size_t)nframes + 1, 0), vbase((size_t)nframes + 1, 0), cnt((size_t)kBins * nframes, 0);
+    for (int f = 0; f < nframes; f++) {
+        const BowFrameOut &b = s.bow[f];
+        const int nt = (int)b.n_rays.size();
+        int nvs = 0;
+        for (int t = 0; t < nt; t++) {
+            int nv = 0;
+            for (int c = 0; c < C; c++) nv += b.tracks[(size_t)t * C + c] != -1;
+            if (nv >= 2) { cnt[(size_t)bin_of(nv) * nframes + f]++; nvs += nv; }
+        }
+        tbase[f + 1] = tbase[f] + nt;
+        vbase[f + 1] = vbase[f] + nvs;
+    }
+    std::vector<int> boff((size_t)kBins * nframes + 1, 0);   // bin-major, frame-minor
+    for (size_t i = 0; i < cnt.size(); i++) boff[i + 1] = boff[i] + cnt[i];
+    const int nsend = boff.back();
+    // (the first bind sized the buffers for one track and one view per keypoint, which the BoW-guided tracks never exceed; grown
+    // here all the same should a job need more)
+    if ((size_t)tbase[nframes] > s.lf_trk_cap) {
+        (void)hipHostFree(s.h_lftrk); (void)hipFree(s.d_lftrk); (void)hipHostFree(s.h_lfout);
+        s.h_lftrk = s.d_lftrk = nullptr; s.h_lfout = nullptr; s.lf_trk_cap = 0;
+        const size_t n = (size_t)tbase[nframes];
+        HIPCHK(hipHostMalloc((void **)&s.h_lftrk, n * sizeof(int4), hipHostMallocDefault));
+        HIPCHK(hipMalloc((void **)&s.d_lftrk, n * sizeof(int4)));
+        HIPCHK(hipHostMalloc((void **)&s.h_lfout, n * sizeof(LfTrackOut), hipHostMallocMapped | hipHostMallocPortable));
+        s.lf_trk_cap = n;
+    }
+    if ((size_t)vbase[nframes] > s.lf_view_cap) {
+        (void)hipHostFree(s.h_lfview); (void)hipFree(s.d_lfview);
+        s.h_lfview = s.d_lfview = nullptr; s.lf_view_cap = 0;
+        const size_t n = (size_t)vbase[nframes];
+        HIPCHK(hipHostMalloc((void **)&s.h_lfview, n * sizeof(LfView), hipHostMallocDefault));
+        HIPCHK(hipMalloc((void **)&s.d_lfview, n * sizeof(LfView)));
+        s.lf_view_cap = n;
+    }
+    R.pool->parallel_for(nframes, [&](int f, int) {
+        const BowFrameOut &b = s.bow[f];
+        const int nt = (int)b.n_rays.size();
+        int next[kBins], vo = vbase[f];
+        for (int k = 0; k < kBins; k++) next[k] = boff[(size_t)k * nframes + f];
+        for (int t = 0; t < nt; t++) {
+            const int32_t *tr = b.tracks.data() + (size_t)t * C;
+            int nv = 0;
+            for (int c = 0; c < C; c++) nv += tr[c] != -1;
+            if (nv < 2) continue;
+            s.h_lftrk[next[bin_of(nv)]++] = make_int4(vo, nv, f, tbase[f] + t);
+            for (int c = 0; c < C; c++)
+                if (tr[c] != -1) {
+                    const mcorb_keypoint &kp = s.kps[f * C + c][tr[c]];
+                    s.h_lfview[vo++] = LfView{c, tr[c], kp.x, kp.y};
+                }
+        }
+    }, R.pool_threads + s.index);
+    const auto T1 = now();
+    // 2. one launch behind the descent results' copy (bow_job_finish), records straight to host-mapped memory
+    if (nsend) {
+        HIPCHK(hipMemcpyAsync(s.d_lftrk, s.h_lftrk, (size_t)nsend * sizeof(int4), hipMemcpyHostToDevice, s.st_dma));
+        HIPCHK(hipMemcpyAsync(s.d_lfview, s.h_lfview, (size_t)vbase[nframes] * sizeof(LfView), hipMemcpyHostToDevice, s.st_dma));
+        launch_lf_tracks(s.st_dma, s.d_lftrk, s.d_lfview, nsend, R.d_lfcams, s.d_desc, kcap, C, s.h_lfout);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipEventRecord(s.ev_lf, s.st_dma));
+    HIPCHK(R.wait_event(s.ev_lf));
+    const auto T2 = now();
+    // 3. per frame: the order-dependent bookkeeping on the records, then the LF set's transform from the job's descent results
+    std::vector<const mcorb_keypoint *> ku;
+    const int kst = undist_inputs(R, &s, 0, nframes, nullptr, ku);
+    if (kst < 0) return kst;
+    std::vector<int> status((size_t)nframes, MCORB_OK);
+    std::vector<std::string> errs((size_t)nframes);
+    const int weighting = R.bow_bind.weighting, scoring = R.bow_bind.scoring;
+    R.pool->parallel_for(nframes, [&](int f, int) {
+        const BowFrameOut &b = s.bow[f];
+        const int nt = (int)b.n_rays.size();
+        const std::vector<uint32_t> ones((size_t)nt, 1u);   // words_ (FrontEnd.cpp:1010)
+        LfFrameOut &o = s.lf[f];
+        status[f] = lf_frame_core(R, &s, s.index, f, b.tracks.data(), nt, ones.data(), R.lf_cams.data(), nullptr, 0,
+                                  kst ? ku.data() + (size_t)f * C : nullptr, R.lf_total_feats, s.h_lfout + tbase[f], o, false);
+        if (status[f] != MCORB_OK) { errs[f] = get_error(); return; }
+        std::vector<BowRes> res(o.src.size());
+        for (size_t i = 0; i < o.src.size(); i++) res[i] = s.h_lfres[o.src[i]];
+        bow_assemble(weighting, scoring, res.data(), (int)res.size(), o.bow);
+        s.lf_ok[f] = 1;
+    }, R.pool_threads + s.index);
+    if (prof)
+        fprintf(stderr, "[mcorb host prof] lf stage x%d frames (%d tracks to the GPU): pack %.0f us, k_lf_tracks + wait %.0f, bookkeeping + transform %.0f\n",
+                nframes, nsend, us(T0, T1), us(T1, T2), us(T2, now()));
+    for (int f = 0; f < nframes; f++)
+        if (status[f] != MCORB_OK) { set_error("lf stage, frame " + std::to_string(f) + ": " + errs[f]); return status[f]; }
+    return MCORB_OK;
+}
+
+extern "C" int mcorb_rig_set_lf(mcorb_rig *r, const mcorb_camera *cams, int total_feats)
+{
+    if (!r) { set_error("set_lf: bad argument"); return MCORB_E_ARG; }
+    return r->rig.set_lf(cams, total_feats);
+}
+
+// the job's LF results of one frame: MCORB_E_STATE unless the slot's last extraction ran the stage for it
+static int lf_frame_of(mcorb_rig *r, int slot, int frame, const LfFrameOut **o)
+{
+    if (!r || slot < 0 || slot >= (int)r->rig.slots.size()) { set_error("lf getter: bad argument"); return MCORB_E_ARG; }
+    Slot *s = r->rig.slots[slot];
+    {
+        std::lock_guard<std::mutex> lk(s->m);
+        if (s->busy) { set_error("slot busy"); return MCORB_E_STATE; }
+    }
+    if (frame < 0 || frame >= (int)s->lf_ok.size() || !s->lf_ok[frame]) {
+        set_error("lf getter: frame not processed by the LF stage since the slot's last extraction");
+        return MCORB_E_STATE;
+    }
+    *o = &s->lf[frame];
+    return MCORB_OK;
+}
+
+extern "C" int mcorb_rig_get_lf_features(mcorb_rig *r, int slot, int frame, mcorb_lf_feature *out, int cap, int *n_out,
+                                         int *intramatch_size_out, int *mono_size_out, uint32_t *words_fil, int cap_words,
+                                         int *nwords_fil_out)
+{
+    if (n_out) *n_out = 0;
+    if (intramatch_size_out) *intramatch_size_out = 0;
+    if (mono_size_out) *mono_size_out = 0;
+    if (nwords_fil_out) *nwords_fil_out = 0;
+    const LfFrameOut *o = nullptr;
+    const int st = lf_frame_of(r, slot, frame, &o);
+    if (st != MCORB_OK) return st;
+    if (cap < 0 || (cap > 0 && !out)) { set_error("lf getter: bad argument"); return MCORB_E_ARG; }
+    return lf_copy_out(*o, out, cap, n_out, intramatch_size_out, mono_size_out, words_fil, cap_words, nwords_fil_out);
+}
+
+extern "C" int mcorb_rig_get_lf_bow(mcorb_rig *r, int slot, int frame, uint32_t *bow_ids, double *bow_vals, int bow_cap, int *nbow,
+                                    uint32_t *fv_nodes, int32_t *fv_offsets, int fv_cap, int *nfv, int32_t *fv_feats, int feat_cap)
+{
+    if (nbow) *nbow = 0;
+    if (nfv) *nfv = 0;
+    const LfFrameOut *o = nullptr;
+    const int st = lf_frame_of(r, slot, frame, &o);
+    if (st != MCORB_OK) return st;
+    const BowImageOut &b = o->bow;
+    if (nbow) *nbow = (int)b.bow_ids.size();
+    if (nfv) *nfv = (int)b.fv_nodes.size();
+    if ((int)b.bow_ids.size() > bow_cap || (int)b.fv_nodes.size() > fv_cap || (int)b.fv_feats.size() > feat_cap) { set_error("lf bow: output too small"); return MCORB_E_CAP; }
+    if (!fv_offsets || (!b.bow_ids.empty() && (!bow_ids || !bow_vals)) || (!b.fv_nodes.empty() && !fv_nodes) || (!b.fv_feats.empty() && !fv_feats)) {
+        set_error("lf bow: bad argument");
+        return MCORB_E_ARG;
+    }
+    if (!b.bow_ids.empty()) { memcpy(bow_ids, b.bow_ids.data(), b.bow_ids.size() * 4); memcpy(bow_vals, b.bow_vals.data(), b.bow_vals.size() * 8); }
+    if (!b.fv_nodes.empty()) memcpy(fv_nodes, b.fv_nodes.data(), b.fv_nodes.size() * 4);
+    memcpy(fv_offsets, b.fv_offsets.data(), b.fv_offsets.size() * 4);
+    if (!b.fv_feats.empty()) memcpy(fv_feats, b.fv_feats.data(), b.fv_feats.size() * 4);
+    return MCORB_OK;
+}
+
+// test hook: k_lf_tracks' triangulation (mcorb_triangulate.h) of n arbitrary problems on the device
+extern "C" int mcorb_dev_triangulate_selftest(int device, const double *x, const double *P, const int32_t *nv, int n, double *X,
+                                              int32_t *branch)
+{
+    if (!x || !P || !nv || !X || !branch || n < 1) { set_error("triangulate selftest: bad argument"); return MCORB_E_ARG; }
+    std::vector<int> voff((size_t)n);
+    size_t nviews = 0;
+    for (int i = 0; i < n; i++) {
+        if (nv[i] < 2 || nv[i] > MCORB_MAX_CAMS) { set_error("triangulate selftest: view count out of range"); return MCORB_E_ARG; }
+        voff[i] = (int)nviews;
+        nviews += (size_t)nv[i];
+    }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) { set_error("no usable HIP device"); return MCORB_E_NODEVICE; }
+    HIPCHK(hipSetDevice(device));
+    double *d_x = nullptr, *d_P = nullptr, *d_X = nullptr;
+    int *d_nv = nullptr, *d_voff = nullptr, *d_br = nullptr;
+    hipError_t e = hipMalloc((void **)&d_x, nviews * 2 * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc((void **)&d_P, nviews * 12 * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc((void **)&d_X, (size_t)n * 3 * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc((void **)&d_nv, (size_t)n * sizeof(int));
+    if (e == hipSuccess) e = hipMalloc((void **)&d_voff, (size_t)n * sizeof(int));
+    if (e == hipSuccess) e = hipMalloc((void **)&d_br, (size_t)n * sizeof(int));
+    if (e == hipSuccess) e = hipMemcpy(d_x, x, nviews * 2 * sizeof(double), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_P, P, nviews * 12 * sizeof(double), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_nv, nv, (size_t)n * sizeof(int), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_voff, voff.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        launch_tri_selftest(nullptr, d_x, d_P, d_nv, d_voff, n, d_X, d_br);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpy(X, d_X, (size_t)n * 3 * sizeof(double), hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(branch, d_br, (size_t)n * sizeof(int), hipMemcpyDeviceToHost);
+    (void)hipFree(d_x); (void)hipFree(d_P); (void)hipFree(d_X); (void)hipFree(d_nv); (void)hipFree(d_voff); (void)hipFree(d_br);
+    if (e != hipSuccess) { set_error(std::string("triangulate selftest: ") + hipGetErrorString(e)); return MCORB_E_HIP; }
+    return MCORB_OK;
+}
+
+// host twin of the self-test's branch output (the CPU suite checks the shared header against it)
+extern "C" int mcorb_host_triangulate_branch(const double *x, const double *P, int nv, double X[3], int32_t *branch)
+{
+    if (!x || !P || !X || !branch || nv < 2 || nv > MCORB_MAX_CAMS) return MCORB_E_ARG;
+    const double *Pp[MCORB_MAX_CAMS];
+    for (int i = 0; i < nv; i++) Pp[i] = P + 12 * i;
+    *branch = triangulate(x, Pp, nv, X);
     return MCORB_OK;
 }
