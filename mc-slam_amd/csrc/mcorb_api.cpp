@@ -384,7 +384,7 @@ int mcorb_rig_get_candidates(mcorb_rig *r, int slot, int m, int level, uint32_t 
     // selection path) or brought them over; the device copy is what every other job leaves
     int lo_dev[kMaxLevels + 1];
     const int *lo = s->tbl(m) + kTblLvlOff;
-    if (!s->small_job) {
+    if (!(s->host_results && !r->rig.gpu_select)) {
         HIPCHK(hipSetDevice(r->rig.device));
         HIPCHK(hipMemcpy(lo_dev, s->d_tbl + (size_t)m * s->tbl_ints_per_image + kTblLvlOff, sizeof(lo_dev), hipMemcpyDeviceToHost));
         lo = lo_dev;

@@ -665,6 +665,7 @@ Rig::~Rig()
 // An upload into a slot whose job is still running would overwrite the staging buffer and level 0 between the job's
 // GPU phases (the slot's stream is idle while the host selects): refuse it like every other call on a busy slot.
 constexpr int kSmallBatch = 8;   // images: at most two 4-camera rig frames
+static const char *const kCandOverflowMsg = "candidate list of a sparse level does not fit the host buffer (raise mcorb_params.cand_cap)";
 
 static bool slot_busy(Slot &s)
 {
@@ -913,47 +914,93 @@ void Rig::driver(Slot *sp)
     }
 }
 
-int Rig::run_extract_phaseA(Slot &s, const Job &j)
+// What every extraction job does before its first launch.  A single rig frame (how MC-SLAM calls, mc_slam_app.cpp:564-572) is launch-
+// and hand-off-bound: ~25 runtime calls and three small copies around 250 us of kernels.  For such small batches the copies go:
+// the results travel through host-mapped memory.  Selected on the host, k_compact writes its tables straight into h_tbl and the
+// describe / k-NN kernels read the control block from h_ctrl; selected on the GPU, k_assemble writes the host's sel / responses /
+// counts itself and signals them per image, and the matcher reads its pair list from h_ctrl; either way k_describe_fused writes
+// the host's descriptor copy itself (a few hundred KB over PCIe in all).
+int Rig::begin_extract(Slot &s, const Job &j)
 {
     if (j.nimg < 1 || j.nimg > max_images) { set_error("extract: bad image count"); return MCORB_E_ARG; }
     s.invalidate_bow();   // tracks / BoW vectors of the previous batch index keypoints that are about to disappear
-    undist_job_start(s);
-    // A single rig frame (how MC-SLAM calls, mc_slam_app.cpp:564-572) is launch- and hand-off-bound: ~25 runtime calls and three
-    // small copies around 250 us of kernels.  For small batches the three copies go: k_compact writes its tables straight into the
-    // host-mapped h_tbl, the describe / k-NN kernels read the control block from host-mapped h_ctrl, k_describe_fused writes the
-    // host's descriptor copy itself (a few hundred KB over PCIe in all).
-    static const bool side = getenv("MCORB_COMPACT_SIDE") != nullptr;   // round-1 placement of k_compact, for comparison
-    s.small_job = j.nimg <= kSmallBatch && params.orientation == 0 && !blur_planes && !side;   // (the knob keeps the copy path: it must not select half of each)
+    // the bindings the job runs with: all fixed while a job is in flight
+    s.bow_job = bow_bind.flags;
+    s.lf_job = lf_on && (bow_bind.flags & MCORB_BOW_MATCH);   // (the LF stage reads the job's BoW-guided tracks)
+    s.undist_job = undist_on;
+    s.undist_gen = undist_gen;
+    std::fill(s.kps_undist_ok.begin(), s.kps_undist_ok.end(), (uint8_t)0);
     s.h_overflow[0] = 0;
-    HIPCHK(hipEventRecord(s.ev[0], s.st));
-    launch_pyramid(s.st, s.d_pyr, geom, d_taps, resize_win, j.nimg);
-    HIPCHK(hipEventRecord(s.ev[1], s.st));
-    launch_fast(s.st, s.d_pyr, geom, params.ini_th_fast, params.min_th_fast, d_fasttab + fast_cell_off, s.d_cellkp, s.d_cellcnt, j.nimg);
-    HIPCHK(hipEventRecord(s.ev[2], s.st));
-    // compaction fills the per-image table blocks in device memory (a short kernel: it runs on the compute stream, ahead
-    // of whatever comes next); the DMA that takes the blocks to the host runs on the side stream.
-    if (side) HIPCHK(hipStreamWaitEvent(s.st_copy, s.ev[2], 0));
-    launch_compact(side ? s.st_copy : s.st, s.d_cellkp, s.d_cellcnt, geom, d_lut, s.d_sorted, s.h_cand, s.small_job ? s.h_tbl : s.d_tbl, s.h_overflow, j.nimg);
-    HIPCHK(hipEventRecord(s.ev_c, side ? s.st_copy : s.st));
-    if (s.small_job) {
-        HIPCHK(hipEventRecord(s.ev[3], s.st));   // the tables are in host memory when k_compact is done
-        s.blur_valid = false;
-        HIPCHK(hipEventRecord(s.ev[4], s.st));
-        HIPCHK(hipGetLastError());
-        return MCORB_OK;
-    }
-    if (!side) HIPCHK(hipStreamWaitEvent(s.st_copy, s.ev_c, 0));
-    if (!copy_kernel) HIPCHK(hipMemcpyAsync(s.h_tbl, s.d_tbl, (size_t)j.nimg * s.tbl_ints_per_image * sizeof(int), hipMemcpyDeviceToHost, s.st_copy));
-    else launch_copy_to_host(s.st_copy, s.d_tbl, s.h_tbl, (size_t)j.nimg * s.tbl_ints_per_image * sizeof(int));
-    HIPCHK(hipEventRecord(s.ev[3], s.st_copy));
+    s.host_results = j.nimg <= kSmallBatch && params.orientation == 0 && !blur_planes &&
+                     (!gpu_select || (!j.ext_desc && geom.kcap <= kSelSignalMaxCount));   // (the signal word carries the count)
+    s.set_ctl(s.host_results, s.host_results && !gpu_select);   // (k_assemble's sel / nsel are the device's in a small batch too)
     // Reference mode blurs inside the descriptor kernel, only around the kept keypoints (k_describe_fused).  Whole
     // blurred planes are made when the rotated taps of the orientation mode need them, when MCORB_BLUR_PLANES asks for
     // the plane-based path (A/B comparison), or later, on demand, for mcorb_rig_get_blurred.
     s.blur_valid = blur_planes;
-    if (blur_planes) launch_blur(s.st, s.d_pyr, s.d_blur, geom, j.nimg);
+    return MCORB_OK;
+}
+
+int Rig::enqueue_front(Slot &s, int nimg, int *tbl)
+{
+    const bool ev_on = s.ev_on();
+    if (ev_on) HIPCHK(hipEventRecord(s.ev[0], s.st));
+    launch_pyramid(s.st, s.d_pyr, geom, d_taps, resize_win, nimg);
+    if (ev_on) HIPCHK(hipEventRecord(s.ev[1], s.st));
+    launch_fast(s.st, s.d_pyr, geom, params.ini_th_fast, params.min_th_fast, d_fasttab + fast_cell_off, s.d_cellkp, s.d_cellcnt, nimg);
+    if (ev_on) HIPCHK(hipEventRecord(s.ev[2], s.st));
+    // compaction fills the per-image table blocks (a short kernel: it runs on the compute stream, ahead of whatever comes next)
+    launch_compact(s.st, s.d_cellkp, s.d_cellcnt, geom, d_lut, s.d_sorted, s.h_cand, tbl, s.h_overflow, nimg);
+    if (ev_on) HIPCHK(hipEventRecord(s.ev_c, s.st));
+    return MCORB_OK;
+}
+
+int Rig::run_extract_phaseA(Slot &s, const Job &j)
+{
+    TRY(begin_extract(s, j));
+    TRY(enqueue_front(s, j.nimg, s.host_results ? s.h_tbl : s.d_tbl));
+    if (s.host_results) {
+        HIPCHK(hipEventRecord(s.ev[3], s.st));   // the tables are in host memory when k_compact is done
+    } else {   // the DMA that takes the blocks to the host runs on the side stream
+        HIPCHK(hipStreamWaitEvent(s.st_copy, s.ev_c, 0));
+        if (!copy_kernel) HIPCHK(hipMemcpyAsync(s.h_tbl, s.d_tbl, (size_t)j.nimg * s.tbl_ints_per_image * sizeof(int), hipMemcpyDeviceToHost, s.st_copy));
+        else launch_copy_to_host(s.st_copy, s.d_tbl, s.h_tbl, (size_t)j.nimg * s.tbl_ints_per_image * sizeof(int));
+        HIPCHK(hipEventRecord(s.ev[3], s.st_copy));
+        if (blur_planes) launch_blur(s.st, s.d_pyr, s.d_blur, geom, j.nimg);
+    }
     HIPCHK(hipEventRecord(s.ev[4], s.st));
     HIPCHK(hipGetLastError());
     return MCORB_OK;
+}
+
+// the keypoint record (ORBextractor.cpp:1103-1170's fields) of a retained candidate at (xl, yl) of its level's plane
+mcorb_keypoint Rig::make_keypoint(int level, int xl, int yl, float response, float angle) const
+{
+    mcorb_keypoint kp;
+    kp.x = (float)xl; kp.y = (float)yl;
+    kp.size = (float)tab.scaled_patch[level];
+    kp.angle = angle;
+    kp.response = response;
+    kp.octave = level;
+    kp.class_id = -1;
+    if (level != 0) { kp.x *= tab.scale[level]; kp.y *= tab.scale[level]; }
+    return kp;
+}
+
+// per-kernel times (us) of a job that ran launch by launch, from its events
+void Rig::read_timing(Slot &s, hipEvent_t blur0)
+{
+    float a = 0, b = 0, c = 0, t = 0;
+    ev_elapsed(&a, s.ev[0], s.ev[2]);
+    if (blur0) ev_elapsed(&b, blur0, s.ev[4]);
+    ev_elapsed(&c, s.ev[5], s.ev[6]);
+    s.timing[0] = a * 1000.f;
+    s.timing[2] = (b + c) * 1000.f;
+    s.timing[8] = b * 1000.f;   // k_blur
+    s.timing[9] = c * 1000.f;   // k_describe
+    ev_elapsed(&t, s.ev[0], s.ev[1]); s.timing[4] = t * 1000.f;   // pyramid launches
+    ev_elapsed(&t, s.ev[1], s.ev[2]); s.timing[5] = t * 1000.f;   // k_fast_cells
+    ev_elapsed(&t, s.ev[2], s.ev_c); s.timing[6] = t * 1000.f;   // k_compact (the table DMA behind it is not included)
 }
 
 int Rig::run_select_and_describe(Slot &s, const Job &j, bool then_match)
@@ -961,7 +1008,7 @@ int Rig::run_select_and_describe(Slot &s, const Job &j, bool then_match)
     HIPCHK(wait_event(s.ev[3]));
     LatProf::mark(2);
     if (s.h_overflow[0]) {
-        set_error("candidate list of a sparse level does not fit the host buffer (raise mcorb_params.cand_cap)");
+        set_error(kCandOverflowMsg);
         (void)hipStreamSynchronize(s.st);
         return MCORB_E_OVERFLOW;
     }
@@ -1031,17 +1078,9 @@ int Rig::run_select_and_describe(Slot &s, const Job &j, bool then_match)
         int monoIndex = 0, stereoIndex = total - 1;
         if (total) {
             for (int l = 0; l < L; l++) {
-                const float scale = tab.scale[l];
                 for (const uint32_t c : s.sel_val[(size_t)m * L + l]) {
                     const int xl = cand_x(c) + kMinBorder, yl = cand_y(c) + kMinBorder;
-                    mcorb_keypoint kp;
-                    kp.x = (float)xl; kp.y = (float)yl;
-                    kp.size = (float)tab.scaled_patch[l];
-                    kp.angle = 0.f;
-                    kp.response = (float)cand_resp(c);
-                    kp.octave = l;
-                    kp.class_id = -1;
-                    if (l != 0) { kp.x *= scale; kp.y *= scale; }
+                    const mcorb_keypoint kp = make_keypoint(l, xl, yl, (float)cand_resp(c), 0.f);
                     int pos;
                     if (kp.x >= (float)j.lap0 && kp.x <= (float)j.lap1) pos = stereoIndex--;
                     else pos = monoIndex++;
@@ -1062,175 +1101,103 @@ int Rig::run_select_and_describe(Slot &s, const Job &j, bool then_match)
 
     s.nimg_done = nimg;
     if (then_match) TRY(prepare_match(s, j));
-    if (s.small_job) {
-        // no copies: the kernels read the control block from the host-mapped h_ctrl and k_describe_fused writes h_desc itself
-        HIPCHK(hipEventRecord(s.ev[5], s.st));
-        launch_describe(s.st, s.d_pyr, nullptr, geom, s.h_sel, s.h_nsel, 0, s.d_desc, s.d_angles, nimg, s.h_desc);
-        HIPCHK(hipEventRecord(s.ev[6], s.st));
-        if (undist_on) {   // beside the descriptors and the matcher, from the host-mapped list, into host-mapped memory
-            HIPCHK(hipStreamWaitEvent(s.st_dma, s.ev[5], 0));
-            TRY(enqueue_undistort(s, s.h_sel, s.h_nsel, nimg, true));
-        }
-        if (then_match) TRY(enqueue_match(s, j, true));
-        HIPCHK(hipGetLastError());
-        if (undist_on) HIPCHK(hipStreamWaitEvent(s.st, s.ev_u1, 0));
-        if (s.bow_job) TRY(enqueue_bow(s, nimg, s.h_sel, s.h_nsel, true));
-        HIPCHK(hipEventRecord(s.ev[10], s.st));
-        LatProf::mark(4);
-        HIPCHK(wait_event(s.ev[10]));
-        LatProf::mark(5);
-        s.nimg_done = nimg;
-        float a = 0, c = 0, t = 0;
-        ev_elapsed(&a, s.ev[0], s.ev[2]);
-        ev_elapsed(&c, s.ev[5], s.ev[6]);
-        s.timing[0] = a * 1000.f;
-        s.timing[2] = c * 1000.f;
-        s.timing[8] = 0.f;
-        s.timing[9] = c * 1000.f;
-        ev_elapsed(&t, s.ev[0], s.ev[1]); s.timing[4] = t * 1000.f;
-        ev_elapsed(&t, s.ev[1], s.ev[2]); s.timing[5] = t * 1000.f;
-        ev_elapsed(&t, s.ev[2], s.ev_c); s.timing[6] = t * 1000.f;
-        return MCORB_OK;
-    }
-    // one H2D copy of the control block: counts, pair list, packed selected keypoints
-    HIPCHK(hipMemcpyAsync(s.d_ctrl, s.h_ctrl, s.ctrl_bytes, hipMemcpyHostToDevice, s.st));
-    HIPCHK(hipEventRecord(s.ev[5], s.st));
-    launch_describe(s.st, s.d_pyr, blur_planes ? s.d_blur : nullptr, geom, s.d_sel, s.d_nsel, params.orientation, s.d_desc, s.d_angles, nimg);
-    HIPCHK(hipEventRecord(s.ev[6], s.st));
-    // descriptors go back to the host on the side stream (DMA) while the matcher already runs
-    static const bool d2h_late = getenv("MCORB_D2H_LATE") != nullptr;   // experiment: copy after the k-NN instead of beside it
-    static const int d2h_mid_env = getenv("MCORB_D2H_AFTER_EXPAND") ? atoi(getenv("MCORB_D2H_AFTER_EXPAND")) : -1;
-    // (experiment, MCORB_D2H_AFTER_EXPAND=1: start the copy behind k_expand.  Whatever kernel of the job ENDS while the copy's
-    // host writes are in flight is held until they have drained -- k_expand 12 -> 148 us beside the copy, k_knn2 154 -> 276 us when
-    // the copy starts behind k_expand, with the runtime's blit and with k_copy_to_host alike (profiles/r03_copy_kernel_ab.txt) --
-    // so the copy stays beside k_expand, whose result nobody needs before k_knn2 anyway: 13.3 k vs 13.0 k frames/s at one slot.)
-    const bool d2h_mid = then_match && !d2h_late && d2h_mid_env > 0;
-    if ((!d2h_late && !d2h_mid) || !then_match) HIPCHK(hipStreamWaitEvent(s.st_dma, s.ev[6], 0));
-    if (then_match && (d2h_late || d2h_mid)) {
-        TRY(enqueue_match(s, j, true));
-        HIPCHK(hipStreamWaitEvent(s.st_dma, d2h_mid && s.npairs_done > 0 ? s.ev_e : s.ev[9], 0));
-    }
-    if (!copy_kernel) HIPCHK(hipMemcpyAsync(s.h_desc, s.d_desc, (size_t)nimg * geom.kcap * 32, hipMemcpyDeviceToHost, s.st_dma));
-    else launch_copy_to_host(s.st_dma, s.d_desc, s.h_desc, (size_t)nimg * geom.kcap * 32);
-    if (params.orientation)
-        HIPCHK(hipMemcpyAsync(s.h_angles, s.d_angles, (size_t)nimg * geom.kcap * sizeof(float), hipMemcpyDeviceToHost, s.st_dma));
-    if (undist_on) TRY(enqueue_undistort(s, s.d_sel, s.d_nsel, nimg, false));   // behind the result copies: the side stream's last work
-    if (s.bow_job) TRY(enqueue_bow(s, nimg, s.d_sel, s.d_nsel, false));
-    if (then_match && !d2h_late && !d2h_mid) TRY(enqueue_match(s, j, true));
-    HIPCHK(hipGetLastError());
+    TRY(enqueue_back(s, j, then_match, false));
     HIPCHK(hipEventRecord(s.ev[10], s.st));
-    HIPCHK(hipEventRecord(s.ev[11], s.st_dma));
+    LatProf::mark(4);
     HIPCHK(wait_event(s.ev[10]));   // events, not streams: the compute stream may be shared between slots
-    HIPCHK(wait_event(s.ev[11]));
+    if (!s.host_results) HIPCHK(wait_event(s.ev[11]));
+    LatProf::mark(5);
     if (params.orientation)
         for (int m = 0; m < nimg; m++)
             for (size_t k = 0; k < s.kps[m].size(); k++) s.kps[m][k].angle = s.h_angles[(size_t)m * geom.kcap + k];
-    s.nimg_done = nimg;
-    float a = 0, b = 0, c = 0, t = 0;
-    ev_elapsed(&a, s.ev[0], s.ev[2]);
-    ev_elapsed(&b, s.ev_c, s.ev[4]);
-    ev_elapsed(&c, s.ev[5], s.ev[6]);
-    s.timing[0] = a * 1000.f;
-    s.timing[2] = (b + c) * 1000.f;
-    s.timing[8] = b * 1000.f;   // k_blur
-    s.timing[9] = c * 1000.f;   // k_describe
-    ev_elapsed(&t, s.ev[0], s.ev[1]); s.timing[4] = t * 1000.f;   // pyramid launches
-    ev_elapsed(&t, s.ev[1], s.ev[2]); s.timing[5] = t * 1000.f;   // k_fast_cells
-    ev_elapsed(&t, s.ev[2], s.ev_c); s.timing[6] = t * 1000.f;   // k_compact (the table DMA behind it is not included)
+    read_timing(s, s.host_results ? nullptr : s.ev_c);
     return MCORB_OK;
 }
 
-// MCORB_SELECT_GPU: the whole job -- pyramid, FAST, compaction, selection, assembly, descriptors, matching -- is enqueued in one go;
-// the host comes back when the results have landed (descriptors, the control block's sel / nsel, responses, monoIndex, flags) and
-// only builds its keypoint records from them.  A batch with a level whose tree goes below the bucketing depth (flag) is redone
-// through the host stage: run_select_and_describe on the tables, exactly the MCORB_SELECT_HOST path.
-// everything a GPU-selected job puts on the slot's streams, from the control block's head to the result copies
-int Rig::enqueue_gpu_job(Slot &s, const Job &j, bool then_match)
+// From ev[5] to the last operation the job enqueues: descriptors, then -- a small batch -- k_undistort forked onto the side stream
+// beside them and the matcher, joined in front of the BoW stages, no copies; or -- a large batch -- the result copies on the side
+// stream while the BoW stages and the matcher run.  ev[11] closes the side stream's work (a GPU-selected small batch's: the compute
+// stream's; the host-selected small batch has none and records nothing).
+int Rig::enqueue_back(Slot &s, const Job &j, bool then_match, bool gpu_sel)
 {
     const int nimg = j.nimg;
-    (void)hipGetLastError();   // (a stale error of this thread -- e.g. an elapsed-time query on an event a replayed graph never recorded -- is not this job's)
-    // A small batch (one rig frame at a time) is launch- and copy-bound: its results travel through host-mapped memory -- k_assemble
-    // writes the host's sel / responses / counts itself and signals them per image, k_describe_fused writes the host's descriptors, the
-    // matcher reads its pair list from the host's control block: no copy is left in the job.
-    const bool small = s.gpu_small;
-    if (then_match && !small)   // pair list / set map first: k_assemble overwrites the control block's nsel and sel afterwards, in stream order
-        HIPCHK(hipMemcpyAsync(s.d_ctrl, s.h_ctrl, s.ctrl_pairs_end, hipMemcpyHostToDevice, s.st));
-    int *d_flags = reinterpret_cast<int *>(s.d_res);
-    if (!small) HIPCHK(hipMemsetAsync(d_flags, 0, 16 * sizeof(int), s.st));   // (a small batch's flags travel with its per-image signals)
-    // (a small batch replayed from its graph: kernels only -- event-record nodes between them split the graph into separately
-    // submitted pieces, and nothing reads these events after a replay)
-    const bool ev_on = !(small && s.capturing);
-    if (ev_on) HIPCHK(hipEventRecord(s.ev[0], s.st));
-    launch_pyramid(s.st, s.d_pyr, geom, d_taps, resize_win, nimg);
-    if (ev_on) HIPCHK(hipEventRecord(s.ev[1], s.st));
-    launch_fast(s.st, s.d_pyr, geom, params.ini_th_fast, params.min_th_fast, d_fasttab + fast_cell_off, s.d_cellkp, s.d_cellcnt, nimg);
-    if (ev_on) HIPCHK(hipEventRecord(s.ev[2], s.st));
-    launch_compact(s.st, s.d_cellkp, s.d_cellcnt, geom, d_lut, s.d_sorted, s.h_cand, s.d_tbl, s.h_overflow, nimg);
-    if (ev_on) HIPCHK(hipEventRecord(s.ev_c, s.st));
-    HIPCHK(launch_select(s.st, s.d_tbl, s.d_sorted, geom, s.d_selval, s.d_selcnt, d_flags, nimg, select_deep_cap));
-    if (small)
-        launch_assemble(s.st, s.d_selval, s.d_selcnt, geom, tab.scale, j.lap0, j.lap1, s.d_sel, s.d_res + s.res_resp_off, s.d_nsel,
-                        reinterpret_cast<int *>(s.d_res + s.res_mono_off), d_flags, nimg, s.h_sel, s.h_res + s.res_resp_off, s.h_sig);
-    else
-        launch_assemble(s.st, s.d_selval, s.d_selcnt, geom, tab.scale, j.lap0, j.lap1, s.d_sel, s.d_res + s.res_resp_off, s.d_nsel,
-                        reinterpret_cast<int *>(s.d_res + s.res_mono_off), d_flags, nimg);
-    if (ev_on) HIPCHK(hipEventRecord(s.ev_s, s.st));
-    if (ev_on) HIPCHK(hipEventRecord(s.ev[3], s.st));
-    if (small && undist_on) {   // fork: k_undistort runs on the side stream beside the descriptors and the matcher (joined below)
+    const bool small = s.host_results, ev_on = s.ev_on();
+    // selected on the host: one H2D copy of the control block -- counts, pair list, packed selected keypoints
+    if (!gpu_sel && !small) HIPCHK(hipMemcpyAsync(s.d_ctrl, s.h_ctrl, s.ctrl_bytes, hipMemcpyHostToDevice, s.st));
+    if (ev_on) HIPCHK(hipEventRecord(s.ev[5], s.st));
+    if (small && undist_on) {   // fork: into host-mapped memory (ev_u0, not ev[5]: a captured job records no ev[5])
         HIPCHK(hipEventRecord(s.ev_u0, s.st));
         HIPCHK(hipStreamWaitEvent(s.st_dma, s.ev_u0, 0));
-        TRY(enqueue_undistort(s, s.d_sel, s.d_nsel, nimg, true));
+        TRY(enqueue_undistort(s, nimg));
     }
-    if (blur_planes) launch_blur(s.st, s.d_pyr, s.d_blur, geom, nimg);
-    if (ev_on) HIPCHK(hipEventRecord(s.ev[4], s.st));
-    if (ev_on) HIPCHK(hipEventRecord(s.ev[5], s.st));
-    launch_describe(s.st, s.d_pyr, blur_planes ? s.d_blur : nullptr, geom, s.d_sel, s.d_nsel, params.orientation, s.d_desc, s.d_angles, nimg,
+    launch_describe(s.st, s.d_pyr, blur_planes ? s.d_blur : nullptr, geom, s.ctl.sel, s.ctl.nsel, params.orientation, s.d_desc, s.d_angles, nimg,
                     small ? s.h_desc : nullptr);
     if (ev_on) HIPCHK(hipEventRecord(s.ev[6], s.st));
     if (small) {
         if (then_match) TRY(enqueue_match(s, j, true));
         HIPCHK(hipGetLastError());
         if (undist_on) HIPCHK(hipStreamWaitEvent(s.st, s.ev_u1, 0));   // join
-        if (s.bow_job) TRY(enqueue_bow(s, nimg, s.d_sel, s.d_nsel, true));
-        if (ev_on) HIPCHK(hipEventRecord(s.ev[11], s.st));
+        if (s.bow_job) TRY(enqueue_bow(s, nimg));
+        if (gpu_sel && ev_on) HIPCHK(hipEventRecord(s.ev[11], s.st));
         return MCORB_OK;
     }
-    // results to the host on the side stream while the matcher runs: descriptors, the control block from nsel on (nsel, the set
-    // map and pair list as uploaded, sel), responses + monoIndex + flags
+    // results to the host on the side stream (DMA) while the matcher already runs: descriptors; of a GPU-selected job also the
+    // control block from nsel on (nsel, the set map and pair list as uploaded, sel) and responses + monoIndex + flags.
+    // (The descriptor copy starts beside k_expand.  Whatever kernel of the job ENDS while the copy's host writes are in flight is
+    // held until they have drained -- k_expand 12 -> 148 us beside the copy, k_knn2 154 -> 276 us when the copy starts behind
+    // k_expand, with the runtime's blit and with k_copy_to_host alike (profiles/r03_copy_kernel_ab.txt) -- so the copy stays beside
+    // k_expand, whose result nobody needs before k_knn2 anyway: 13.3 k vs 13.0 k frames/s at one slot.)
+    const size_t nk = (size_t)nimg * geom.kcap;
     HIPCHK(hipStreamWaitEvent(s.st_dma, s.ev[6], 0));
-    if (!copy_kernel) HIPCHK(hipMemcpyAsync(s.h_desc, s.d_desc, (size_t)nimg * geom.kcap * 32, hipMemcpyDeviceToHost, s.st_dma));
-    else launch_copy_to_host(s.st_dma, s.d_desc, s.h_desc, (size_t)nimg * geom.kcap * 32);
-    HIPCHK(hipMemcpyAsync(s.h_ctrl + s.ctrl_nsel_off, s.d_ctrl + s.ctrl_nsel_off, s.ctrl_pairs_end - s.ctrl_nsel_off + (size_t)nimg * geom.kcap * sizeof(uint32_t),
-                          hipMemcpyDeviceToHost, s.st_dma));
-    HIPCHK(hipMemcpyAsync(s.h_res, s.d_res, s.res_resp_off + (size_t)nimg * geom.kcap, hipMemcpyDeviceToHost, s.st_dma));
-    if (params.orientation)
-        HIPCHK(hipMemcpyAsync(s.h_angles, s.d_angles, (size_t)nimg * geom.kcap * sizeof(float), hipMemcpyDeviceToHost, s.st_dma));
-    if (undist_on) TRY(enqueue_undistort(s, s.d_sel, s.d_nsel, nimg, false));   // behind the result copies: the side stream's last work
-    if (s.bow_job) TRY(enqueue_bow(s, nimg, s.d_sel, s.d_nsel, false));
+    if (!copy_kernel) HIPCHK(hipMemcpyAsync(s.h_desc, s.d_desc, nk * 32, hipMemcpyDeviceToHost, s.st_dma));
+    else launch_copy_to_host(s.st_dma, s.d_desc, s.h_desc, nk * 32);
+    if (gpu_sel) {
+        HIPCHK(hipMemcpyAsync(s.h_ctrl + s.ctrl_nsel_off, s.d_ctrl + s.ctrl_nsel_off, s.ctrl_pairs_end - s.ctrl_nsel_off + nk * sizeof(uint32_t),
+                              hipMemcpyDeviceToHost, s.st_dma));
+        HIPCHK(hipMemcpyAsync(s.h_res, s.d_res, s.res_resp_off + nk, hipMemcpyDeviceToHost, s.st_dma));
+    }
+    if (params.orientation) HIPCHK(hipMemcpyAsync(s.h_angles, s.d_angles, nk * sizeof(float), hipMemcpyDeviceToHost, s.st_dma));
+    if (undist_on) TRY(enqueue_undistort(s, nimg));   // behind the result copies: the side stream's last work
+    if (s.bow_job) TRY(enqueue_bow(s, nimg));
     if (then_match) TRY(enqueue_match(s, j, true));
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(s.ev[11], s.st_dma));
     return MCORB_OK;
 }
 
+// everything a GPU-selected job puts on the slot's streams, from the control block's head to the result copies
+int Rig::enqueue_gpu_job(Slot &s, const Job &j, bool then_match)
+{
+    const int nimg = j.nimg;
+    (void)hipGetLastError();   // (a stale error of this thread -- e.g. an elapsed-time query on an event a replayed graph never recorded -- is not this job's)
+    const bool small = s.host_results, ev_on = s.ev_on();
+    if (then_match && !small)   // pair list / set map first: k_assemble overwrites the control block's nsel and sel afterwards, in stream order
+        HIPCHK(hipMemcpyAsync(s.d_ctrl, s.h_ctrl, s.ctrl_pairs_end, hipMemcpyHostToDevice, s.st));
+    int *d_flags = reinterpret_cast<int *>(s.d_res);
+    if (!small) HIPCHK(hipMemsetAsync(d_flags, 0, 16 * sizeof(int), s.st));   // (a small batch's flags travel with its per-image signals)
+    TRY(enqueue_front(s, nimg, s.d_tbl));
+    HIPCHK(launch_select(s.st, s.d_tbl, s.d_sorted, geom, s.d_selval, s.d_selcnt, d_flags, nimg, select_deep_cap));
+    launch_assemble(s.st, s.d_selval, s.d_selcnt, geom, tab.scale, j.lap0, j.lap1, s.d_sel, s.d_res + s.res_resp_off, s.d_nsel,
+                    reinterpret_cast<int *>(s.d_res + s.res_mono_off), d_flags, nimg, small ? s.h_sel : nullptr,
+                    small ? s.h_res + s.res_resp_off : nullptr, small ? s.h_sig : nullptr);
+    if (ev_on) HIPCHK(hipEventRecord(s.ev_s, s.st));
+    if (ev_on) HIPCHK(hipEventRecord(s.ev[3], s.st));
+    if (blur_planes) launch_blur(s.st, s.d_pyr, s.d_blur, geom, nimg);
+    if (ev_on) HIPCHK(hipEventRecord(s.ev[4], s.st));
+    return enqueue_back(s, j, then_match, true);
+}
+
+
 // ---------------------------------------------------------------------------
 // UndistortKeyPoints (MultiCameraFrame.cpp:300-347) inside the job.  Nothing of this runs, is allocated or is captured while no
 // camera has undistortion set (undist_on): such a job is exactly the job without the feature.
 // ---------------------------------------------------------------------------
-void Rig::undist_job_start(Slot &s)
+// on the side stream, behind whatever the caller ordered it after; small batches write the host-mapped points directly and record
+// ev_u1 for the caller's join, the others copy them back behind the kernel
+int Rig::enqueue_undistort(Slot &s, int nimg)
 {
-    s.bow_job = bow_bind.flags;   // (the BoW stages' snapshot too: both are fixed while a job is in flight)
-    s.lf_job = lf_on && (bow_bind.flags & MCORB_BOW_MATCH);   // (and the LF stage's: it reads the job's BoW-guided tracks)
-    s.undist_job = undist_on;
-    s.undist_gen = undist_gen;
-    std::fill(s.kps_undist_ok.begin(), s.kps_undist_ok.end(), (uint8_t)0);
-}
-
-// on the side stream, behind whatever the caller ordered it after; small batches (host_out) write the host-mapped points
-// directly and record ev_u1 for the caller's join, the others copy them back behind the kernel
-int Rig::enqueue_undistort(Slot &s, const uint32_t *sel, const int *nsel, int nimg, bool host_out)
-{
-    launch_undistort(s.st_dma, sel, nsel, geom.kcap, nimg, ncams, d_undist_cams, tab.scale, tab.nlevels, host_out ? s.h_undist : s.d_undist);
+    const bool host_out = s.host_results;
+    launch_undistort(s.st_dma, s.ctl.sel, s.ctl.nsel, geom.kcap, nimg, ncams, d_undist_cams, tab.scale, tab.nlevels, host_out ? s.h_undist : s.d_undist);
     if (host_out || s.bow_job) HIPCHK(hipEventRecord(s.ev_u1, s.st_dma));   // (a bound job's BoW tables read the points: enqueue_bow)
     if (!host_out) HIPCHK(hipMemcpyAsync(s.h_undist, s.d_undist, (size_t)nimg * geom.kcap * sizeof(float2), hipMemcpyDeviceToHost, s.st_dma));
     return MCORB_OK;
@@ -1286,9 +1253,12 @@ int Rig::check_job_shape(const Job &j) const
     return MCORB_OK;
 }
 
-int Rig::enqueue_bow(Slot &s, int nimg, const uint32_t *sel, const int *nsel, bool host_out)
+int Rig::enqueue_bow(Slot &s, int nimg)
 {
     const BowBinding &b = bow_bind;
+    const uint32_t *sel = s.ctl.sel;
+    const int *nsel = s.ctl.nsel;
+    const bool host_out = s.host_results;
     const int kcap = geom.kcap, nframes = nimg / ncams;
     const bool match = (s.bow_job & MCORB_BOW_MATCH) && npp > 0 && nframes > 0;
     launch_bow_descend(s.st, s.d_desc, nimg * kcap, b.child_start, b.child_count, b.child_desc, b.child_id, b.word_id, b.weight,
@@ -1418,10 +1388,6 @@ int Rig::undist_default(Slot &s, int m0, int n, std::vector<const mcorb_keypoint
     return st == MCORB_OK ? 1 : st;
 }
 
-// MCORB_SELECT_GPU: the whole job -- pyramid, FAST, compaction, selection, assembly, descriptors, matching -- is enqueued in one go;
-// the host comes back when the results have landed (descriptors, the control block's sel / nsel, responses, monoIndex, flags) and
-// only builds its keypoint records from them.  A batch with a level whose tree goes below the bucketing depth (flag) is redone
-// through the host stage: run_select_and_describe on the tables, exactly the MCORB_SELECT_HOST path.
 void Rig::gpu_job_begin()
 {
     if (!gpu_job_limit) return;
@@ -1439,26 +1405,24 @@ void Rig::gpu_job_end()
     gpu_jobs_cv.notify_one();
 }
 
+// MCORB_SELECT_GPU: the whole job -- pyramid, FAST, compaction, selection, assembly, descriptors, matching -- is enqueued in one go;
+// the host comes back when the results have landed (descriptors, the control block's sel / nsel, responses, monoIndex, flags) and
+// only builds its keypoint records from them.  A batch with a level whose tree goes below the bucketing depth (flag) is redone
+// through the host stage: run_select_and_describe on the tables, exactly the MCORB_SELECT_HOST path.
 int Rig::run_gpu_selected(Slot &s, const Job &j, bool then_match)
 {
-    if (j.nimg < 1 || j.nimg > max_images) { set_error("extract: bad image count"); return MCORB_E_ARG; }
+    TRY(begin_extract(s, j));
     const int nimg = j.nimg;
-    s.invalidate_bow();
-    undist_job_start(s);
-    s.small_job = false;
-    s.h_overflow[0] = 0;
     s.nimg_done = nimg;
-    s.gpu_small = nimg <= kSmallBatch && params.orientation == 0 && !blur_planes && !j.ext_desc && geom.kcap <= kSelSignalMaxCount;
     if (then_match) TRY(prepare_match(s, j));
-    if (s.gpu_small)
+    if (s.host_results)
         for (int m = 0; m < nimg; m++) reinterpret_cast<volatile unsigned long long *>(s.h_sig)[m] = 0;
-    s.blur_valid = blur_planes;
     // The job is the same ~20 launches and copies every time: captured once per (slot, shape of the job) into a HIP graph and
     // replayed with one call -- the CPU side of a job drops from ~20 runtime calls to one, the gaps between its kernels shrink.
     // (Per-kernel HIP events do not exist inside a replayed graph: mcorb_rig_last_timing reports the job as a whole then.)
     // graph_every: 0 = never, 1 = every job, K > 1 = all but every K-th job of a slot, which runs launch by launch with its
     // per-kernel events (a sample of the same pipeline for mcorb_rig_last_timing)
-    // keypoint records (ORBextractor.cpp:1103-1170's fields) of one image from what k_assemble left
+    // keypoint records of one image from what k_assemble left
     auto records = [&](int m) {
         const int n = s.h_nsel[m];
         std::vector<mcorb_keypoint> &K = s.kps[m];
@@ -1468,23 +1432,23 @@ int Rig::run_gpu_selected(Slot &s, const Job &j, bool then_match)
         const float *ang = params.orientation ? s.h_angles + (size_t)m * geom.kcap : nullptr;
         for (int k = 0; k < n; k++) {
             const uint32_t v = sel[k];
-            const int l = (int)(v >> 28), yl = (int)((v >> 14) & 0x3fffu), xl = (int)(v & 0x3fffu);
-            mcorb_keypoint kp;
-            kp.x = (float)xl; kp.y = (float)yl;
-            kp.size = (float)tab.scaled_patch[l];
-            kp.angle = ang ? ang[k] : 0.f;
-            kp.response = (float)rs[k];
-            kp.octave = l;
-            kp.class_id = -1;
-            if (l != 0) { kp.x *= tab.scale[l]; kp.y *= tab.scale[l]; }
-            K[k] = kp;
+            K[k] = make_keypoint((int)(v >> 28), (int)(v & 0x3fffu), (int)((v >> 14) & 0x3fffu), (float)rs[k], ang ? ang[k] : 0.f);
         }
         s.mono[m] = reinterpret_cast<const int *>(s.h_res + s.res_mono_off)[m];
+    };
+    // a small batch: count, monoIndex and flags of an image travel in its signal word (sel_signal()); returns the count
+    int small_flags = 0;
+    auto decode_signal = [&](int m, unsigned long long w) {
+        small_flags |= sel_signal_bad(w);
+        const int n = std::min(sel_signal_count(w), geom.kcap);   // (k_assemble never signals more than kcap; the clamp is for the reads that follow)
+        s.h_nsel[m] = n;
+        reinterpret_cast<int *>(s.h_res + s.res_mono_off)[m] = sel_signal_mono(w);
+        return n;
     };
     // a small batch: the records are built here, image by image as k_assemble signals them, while the descriptor and matching
     // kernels still run; returns the number of images done (all of them unless the job ended without signalling: an error), -1 on
     // a HIP error
-    int records_done = 0, small_flags = 0, early_stale = 0;
+    int records_done = 0, early_stale = 0;
     auto records_early = [&](hipEvent_t end) {
         const volatile unsigned long long *sig = s.h_sig;
         for (int m = 0; m < nimg; m++) {
@@ -1499,13 +1463,10 @@ int Rig::run_gpu_selected(Slot &s, const Job &j, bool then_match)
                 else __builtin_ia32_pause();
             }
             std::atomic_thread_fence(std::memory_order_acquire);
-            const unsigned long long w = sig[m];   // count and monoIndex travel in the signal word itself (sel_signal())
-            small_flags |= sel_signal_bad(w);
-            const int n = std::min(sel_signal_count(w), geom.kcap);   // (k_assemble never signals more than kcap; the clamp is for the reads below)
-            s.h_nsel[m] = n;
-            reinterpret_cast<int *>(s.h_res + s.res_mono_off)[m] = sel_signal_mono(w);
-            // ... and so does a checksum of the sel / response values k_assemble sent: values the word does not vouch for have not
-            // all landed yet (never seen with the atomic signal; cheap to be sure) -- this image and the ones behind it are expanded
+            const unsigned long long w = sig[m];
+            const int n = decode_signal(m, w);
+            // the word also carries a checksum of the sel / response values k_assemble sent: values the word does not vouch for have
+            // not all landed yet (never seen with the atomic signal; cheap to be sure) -- this image and the ones behind it are expanded
             // after the job's end event instead
             uint32_t x = 0;
             const uint32_t *sel = s.h_sel + (size_t)m * geom.kcap;
@@ -1534,7 +1495,7 @@ int Rig::run_gpu_selected(Slot &s, const Job &j, bool then_match)
             s.capturing = true;
             int st = enqueue_gpu_job(s, j, then_match);
             s.capturing = false;
-            hipError_t e = s.gpu_small ? hipSuccess : hipStreamWaitEvent(s.st, s.ev[11], 0);   // the side stream joins again
+            hipError_t e = s.host_results ? hipSuccess : hipStreamWaitEvent(s.st, s.ev[11], 0);   // the side stream joins again
             const hipError_t e2 = hipStreamEndCapture(s.st, &graph);
             if (st != MCORB_OK) { if (graph) (void)hipGraphDestroy(graph); return st; }
             if (e == hipSuccess) e = e2;
@@ -1545,101 +1506,53 @@ int Rig::run_gpu_selected(Slot &s, const Job &j, bool then_match)
         }
         HIPCHK(hipEventRecord(s.ev_g, s.st));
         HIPCHK(hipGraphLaunch(s.graph_exec, s.st));
-        HIPCHK(hipEventRecord(s.ev[10], s.st));
-        LatProf::mark(1); LatProf::mark(2); LatProf::mark(3);
-        if (s.gpu_small) records_early(s.ev[10]);
-        LatProf::mark(4);
-        HIPCHK(wait_event(s.ev[10]));
     } else {
         TRY(enqueue_gpu_job(s, j, then_match));
-        HIPCHK(hipEventRecord(s.ev[10], s.st));
-        LatProf::mark(1); LatProf::mark(2); LatProf::mark(3);
-        if (s.gpu_small) records_early(s.ev[10]);
-        LatProf::mark(4);
-        HIPCHK(wait_event(s.ev[10]));
-        HIPCHK(wait_event(s.ev[11]));
     }
+    HIPCHK(hipEventRecord(s.ev[10], s.st));
+    LatProf::mark(1); LatProf::mark(2); LatProf::mark(3);
+    if (s.host_results) records_early(s.ev[10]);
+    LatProf::mark(4);
+    HIPCHK(wait_event(s.ev[10]));
+    if (!graphed) HIPCHK(wait_event(s.ev[11]));   // (the replayed graph joins the side stream itself)
     LatProf::mark(5);
     turn.done();
-    if (s.h_overflow[0]) { set_error("candidate list of a sparse level does not fit the host buffer (raise mcorb_params.cand_cap)"); return MCORB_E_OVERFLOW; }
+    if (s.h_overflow[0]) { set_error(kCandOverflowMsg); return MCORB_E_OVERFLOW; }
     if (records_done < 0) return MCORB_E_HIP;
-    if (s.gpu_small && records_done < nimg) {
+    if (s.host_results && records_done < nimg) {
         // the job is over: every signal word and everything behind it has landed
         for (int m = records_done; m < nimg; m++) {
             const unsigned long long w = reinterpret_cast<const volatile unsigned long long *>(s.h_sig)[m];
             if (!sel_signal_done(w)) { set_error("extract: the job ended without its results"); return MCORB_E_HIP; }
-            small_flags |= sel_signal_bad(w);
-            s.h_nsel[m] = std::min(sel_signal_count(w), geom.kcap);
-            reinterpret_cast<int *>(s.h_res + s.res_mono_off)[m] = sel_signal_mono(w);
+            decode_signal(m, w);
         }
-        if (early_stale) {
-            s.stale_reads += early_stale;
-            static const bool dbg = getenv("MCORB_DEBUG_EMPTY") != nullptr;
-            if (dbg) fprintf(stderr, "[mcorb debug] image %d: values read ahead of the signal word's checksum; records redone after the end event\n", records_done);
-        }
+        s.stale_reads += early_stale;
     }
-    const int flags = s.gpu_small ? small_flags : reinterpret_cast<const int *>(s.h_res)[0];
+    const int flags = s.host_results ? small_flags : reinterpret_cast<const int *>(s.h_res)[0];
     if (flags) {
         // the host stage on the same tables (bit 0: a tree below the bucketing depth; bit 1: more than kcap keypoints -- the host
         // stage reports that error itself)
         s.fallbacks++;
         s.graph_timing = false;
-        s.gpu_small = false;   // (the host stage uploads the whole control block and copies its results back)
+        s.host_results = false;   // (the host stage uploads the whole control block and copies its results back)
+        s.set_ctl(false, false);
         HIPCHK(hipMemcpyAsync(s.h_tbl, s.d_tbl, (size_t)nimg * s.tbl_ints_per_image * sizeof(int), hipMemcpyDeviceToHost, s.st_copy));
         HIPCHK(hipEventRecord(s.ev[3], s.st_copy));
         return run_select_and_describe(s, j, then_match);
     }
     if (records_done < nimg) pool->parallel_for(nimg, [&](int m, int) { records(m); }, pool_threads + s.index);
-    {
-        // MCORB_DEBUG_EMPTY=1: an image that came back without keypoints is looked at again, after the job: what the device holds
-        // (counts of FAST candidates, per-level selections, nsel) against what the host read -- to tell "nothing to find" from a
-        // result that was read before it had landed
-        static const bool dbg_empty = getenv("MCORB_DEBUG_EMPTY") != nullptr;
-        if (dbg_empty)
-            for (int m = 0; m < nimg; m++) {
-                if (!s.kps[m].empty()) continue;
-                (void)hipStreamSynchronize(s.st);
-                std::vector<int> cc(geom.cells), sc(geom.nlevels);
-                int dn = -1;
-                (void)hipMemcpy(cc.data(), s.d_cellcnt + (size_t)m * geom.cells, cc.size() * sizeof(int), hipMemcpyDeviceToHost);
-                (void)hipMemcpy(sc.data(), s.d_selcnt + (size_t)m * geom.nlevels, sc.size() * sizeof(int), hipMemcpyDeviceToHost);
-                (void)hipMemcpy(&dn, s.d_nsel + m, sizeof(int), hipMemcpyDeviceToHost);
-                long long cand = 0;
-                for (int v : cc) cand += v;
-                long long px = 0;
-                std::vector<uint8_t> row(W);
-                (void)hipMemcpy(row.data(), s.d_pyr + (size_t)m * geom.imgBytes + geom.lv[0].off + (size_t)(H / 2) * geom.lv[0].pitch, W, hipMemcpyDeviceToHost);
-                for (uint8_t v : row) px += v;
-                fprintf(stderr, "[mcorb debug empty] image %d of %d: small %d graphed %d | host: sig %d nsel %d | device now: nsel %d, FAST candidates %lld, "
-                                "selected per level", m, nimg, (int)s.gpu_small, (int)graphed, s.gpu_small ? (int)(s.h_sig[m] & 0xff) : -1, s.h_nsel[m], dn, cand);
-                for (int v : sc) fprintf(stderr, " %d", v);
-                fprintf(stderr, " | middle row of level 0 sums to %lld (staging row: ", px);
-                long long hx = 0;
-                for (int x = 0; x < W; x++) hx += s.h_stage[(size_t)m * W * H + (size_t)(H / 2) * W + x];
-                fprintf(stderr, "%lld)\n", hx);
-            }
-    }
     if (then_match && !j.ext_desc)
         for (size_t i = 0; i < s.match_counts.size(); i++) s.match_counts[i] = s.h_nsel[s.match_sets[i]];
-    float a = 0, b = 0, c = 0, t = 0;
+    s.graph_timing = graphed;
     if (graphed) {   // one interval: the whole job
+        float a = 0;
         for (float &v : s.timing) v = 0.f;
         ev_elapsed(&a, s.ev_g, s.ev[10]);
         s.timing[0] = a * 1000.f;
-        s.graph_timing = true;
         return MCORB_OK;
     }
-    s.graph_timing = false;
-    ev_elapsed(&a, s.ev[0], s.ev[2]);
-    ev_elapsed(&b, s.ev[3], s.ev[4]);
-    ev_elapsed(&c, s.ev[5], s.ev[6]);
-    s.timing[0] = a * 1000.f;
-    s.timing[2] = (b + c) * 1000.f;
-    s.timing[8] = b * 1000.f;
-    s.timing[9] = c * 1000.f;
-    ev_elapsed(&t, s.ev[0], s.ev[1]); s.timing[4] = t * 1000.f;
-    ev_elapsed(&t, s.ev[1], s.ev[2]); s.timing[5] = t * 1000.f;
-    ev_elapsed(&t, s.ev[2], s.ev_c); s.timing[6] = t * 1000.f;
+    read_timing(s, s.ev[3]);
+    float t = 0;
     ev_elapsed(&t, s.ev_c, s.ev_s); s.timing[1] = t * 1000.f;   // k_select + k_assemble
     return MCORB_OK;
 }
@@ -1722,6 +1635,7 @@ int Rig::enqueue_match(Slot &s, const Job &j, bool ctrl_on_device)
     if (!ctrl_on_device) {
         TRY(prepare_match(s, j));
         HIPCHK(hipMemcpyAsync(s.d_ctrl, s.h_ctrl, s.ctrl_pairs_end, hipMemcpyHostToDevice, s.st));
+        s.set_ctl(false, false);
     }
     if (j.after_stream)   // the block is being produced on another stream (a collective): order this stream behind what the
         HIPCHK(hipStreamWaitEvent(s.st, s.ev_x, 0));   // caller had enqueued there at submit time (ev_x, recorded by the submit call)
@@ -1731,11 +1645,10 @@ int Rig::enqueue_match(Slot &s, const Job &j, bool ctrl_on_device)
     }
     if (s.npairs_done == 0) return MCORB_OK;
     const bool ext = j.ext_desc != nullptr;
-    const bool ev_on = !(s.gpu_small && s.capturing);   // (see enqueue_gpu_job)
+    const bool ev_on = s.ev_on();
     if (ev_on) HIPCHK(hipEventRecord(s.ev[7], s.st));
-    const bool hostctrl = ctrl_on_device && (s.small_job || s.gpu_small) && !ext;   // (the fused path of a small batch: no H2D copy was made)
-    launch_knn2(s.st, ext ? (const uint8_t *)j.ext_desc : s.d_desc, ext ? s.d_extcounts : (hostctrl && !s.gpu_small ? s.h_nsel : s.d_nsel),
-                hostctrl ? s.h_setmap : s.d_setmap, s.nsets_local, hostctrl ? s.h_pairs : s.d_pairs, s.npairs_done, geom.kcap, s.d_exp, s.d_lcounts, s.d_part, j.dist_thresh, j.ratio, s.d_knn, s.h_mlist,
+    launch_knn2(s.st, ext ? (const uint8_t *)j.ext_desc : s.d_desc, ext ? s.d_extcounts : s.ctl.nsel, s.ctl.setmap, s.nsets_local, s.ctl.pairs,
+                s.npairs_done, geom.kcap, s.d_exp, s.d_lcounts, s.d_part, j.dist_thresh, j.ratio, s.d_knn, s.h_mlist,
                 s.h_mcount, ev_on ? s.ev_e : nullptr, ev_on ? s.ev[8] : nullptr);
     if (ev_on) HIPCHK(hipEventRecord(s.ev[9], s.st));
     HIPCHK(hipGetLastError());

@@ -173,7 +173,6 @@ struct Slot {
     size_t res_bytes = 0, res_mono_off = 0, res_resp_off = 0, ctrl_nsel_off = 0;
     unsigned long long *h_sig = nullptr;      // small GPU-selected jobs: per image, set by k_assemble behind its host-mapped results
     bool capturing = false;    // enqueue_gpu_job is being captured into the slot's graph
-    bool gpu_small = false;    // the running GPU-selected job is a small batch: results through host-mapped memory, no copies but the flags
     int stale_reads = 0;       // small batches: images whose early read did not match the signal word's checksum (redone after the end event)
     int fallbacks = 0;         // jobs of this slot the host stage had to redo (a tree below the bucketing depth)
     hipEvent_t ev_s = nullptr; // k_select + k_assemble finished
@@ -199,7 +198,7 @@ struct Slot {
     std::vector<std::vector<uint32_t>> m_idx1, m_idx2;   // per pair
     std::vector<std::vector<int32_t>> tracks;            // per frame, ncams ints per track
     std::vector<int> mergeable;
-    // cached BoW results of the images the slot holds NOW: a new extraction clears the flags (run_extract_phaseA), the
+    // cached BoW results of the images the slot holds NOW: a new extraction clears the flags (begin_extract), the
     // getters refuse frames / images that were not matched / transformed since
     std::vector<BowFrameOut> bow;   // per frame
     std::vector<uint8_t> bow_ok;    // per frame: bow[f] belongs to the current extraction
@@ -251,7 +250,23 @@ struct Slot {
     std::mutex undist_m;
     std::vector<int> match_sets, match_counts;   // per (frame, cam) of the last match: set index, descriptor count
     bool match_external = false;
-    bool small_job = false;   // the running job is a small batch: tables, control block and descriptors go through host-mapped memory, no copies
+    // the running job is a small batch: its results (and, selected on the host, its tables and control block) go through host-mapped
+    // memory, no copies; cleared when the host stage redoes a GPU-selected job.  Implies orientation == 0 and no blurred planes.
+    bool host_results = false;
+    // (a small batch replayed from its graph: kernels only -- event-record nodes between them split the graph into separately
+    // submitted pieces, and nothing reads these events after a replay)
+    bool ev_on() const { return !(host_results && capturing); }
+    // the control block as the job's kernels read it, chosen once per job (begin_extract; the fallback redo and a MATCH job read
+    // the device mirror): the host-mapped side where no upload is made -- set map and pair list / the host's sel and nsel
+    struct Ctrl {
+        const int *nsel, *setmap;
+        const int2 *pairs;
+        const uint32_t *sel;
+    } ctl = {};
+    void set_ctl(bool host_lists, bool host_sel)
+    {
+        ctl = {host_sel ? h_nsel : d_nsel, host_lists ? h_setmap : d_setmap, host_lists ? h_pairs : d_pairs, host_sel ? h_sel : d_sel};
+    }
     // driver thread
     std::thread th;
     std::mutex m;
@@ -359,17 +374,25 @@ private:
     bool blur_planes = false;  // k_blur runs with every job (orientation mode / MCORB_BLUR_PLANES); otherwise blur is fused into k_describe_fused
     void driver(Slot *s);
     int execute(Slot &s, const Job &j);
+    // The stages every extraction job is assembled from.  begin_extract: what a job does before its first launch (argument check,
+    // the bindings' snapshot, small batch or not, the control block view).  enqueue_front: ev0 . pyramid . ev1 . FAST . ev2 .
+    // k_compact . ev_c on the compute stream, the tables into tbl.  enqueue_back: from ev[5] to the job's last enqueued operation;
+    // gpu_sel: k_assemble left sel / nsel on the device (else the host filled the control block).
+    int begin_extract(Slot &s, const Job &j);
+    int enqueue_front(Slot &s, int nimg, int *tbl);
+    int enqueue_back(Slot &s, const Job &j, bool then_match, bool gpu_sel);
+    void read_timing(Slot &s, hipEvent_t blur0);   // per-kernel times of an ungraphed job; blur0: k_blur's start event (null: none ran)
+    mcorb_keypoint make_keypoint(int level, int xl, int yl, float response, float angle) const;
     int run_extract_phaseA(Slot &s, const Job &j);
     int run_select_and_describe(Slot &s, const Job &j, bool then_match);
     int run_gpu_selected(Slot &s, const Job &j, bool then_match);   // the whole job as one submission (gpu_select)
     int enqueue_gpu_job(Slot &s, const Job &j, bool then_match);
-    // k_undistort of the job's images on the side stream st_dma: sel / nsel in device or host-mapped memory, out in device or
-    // host-mapped memory; copy_back: the D2H copy of the points follows on the same stream
-    int enqueue_undistort(Slot &s, const uint32_t *sel, const int *nsel, int nimg, bool host_out);
-    void undist_job_start(Slot &s);
+    // k_undistort of the job's images on the side stream st_dma; a small batch writes the host-mapped points, the others copy them
+    // back behind the kernel
+    int enqueue_undistort(Slot &s, int nimg);
     // the BoW stages of the job's nimg images on the compute stream, behind the descriptors (and k_undistort when it gives the rows):
-    // host_out = a small batch, results in host-mapped memory; otherwise copied on st_dma behind the job's other result copies
-    int enqueue_bow(Slot &s, int nimg, const uint32_t *sel, const int *nsel, bool host_out);
+    // a small batch's results go to host-mapped memory; otherwise they are copied on st_dma behind the job's other result copies
+    int enqueue_bow(Slot &s, int nimg);
     int prepare_match(Slot &s, const Job &j);
     int enqueue_match(Slot &s, const Job &j, bool ctrl_on_device);
     int finish_match(Slot &s, const Job &j);

@@ -1529,7 +1529,7 @@ __global__ __launch_bounds__(256) void k_expand(const uint8_t *__restrict__ desc
 // BruteForceMatch accept test and the accepted pairs compacted per 256-query block (mlist[pair][block * 256 + k], count in
 // mcount[pair * qblocks + block]; blocks are in query order, so the host concatenates them) -- instead of writing partials
 // for k_knn2_finalize: one launch, a 23-us kernel and a partial-table round trip less per batch.
-template <int kKnnStageTiles, int kWavesPerSimd, bool FOLD, int DBG = 0>
+template <int kKnnStageTiles, int kWavesPerSimd, bool FOLD>
 __global__ __launch_bounds__(64 * kKnnWaves, kWavesPerSimd) void k_knn2(const uint4 *__restrict__ E, const int *__restrict__ lcounts,
                                                            const int2 *__restrict__ pairs, int kcap, int nchunks, int npairs,
                                                            int qblocks, uint2 *__restrict__ part, int chunkLen,
@@ -1632,7 +1632,6 @@ __global__ __launch_bounds__(64 * kKnnWaves, kWavesPerSimd) void k_knn2(const ui
                 }
 #pragma unroll
                 for (int u = 0; u < kKnnQT; u++) {
-                    if (DBG & 4) { if (s == 0) fold2(u, old[u][0], old[u][15]); continue; }
                     fold2(u, old[u][4 * s], old[u][4 * s + 1]);
                     fold2(u, old[u][4 * s + 2], old[u][4 * s + 3]);
                 }
@@ -1663,7 +1662,7 @@ __global__ __launch_bounds__(64 * kKnnWaves, kWavesPerSimd) void k_knn2(const ui
 #pragma unroll
             for (int e = 0; e < 16; e++) accA[u][e] = kNone;   // "nothing pending": folding it changes nothing
         for (int st = 0; st < nstage; st++) {
-            if (!(DBG & 1) && st + 1 < nstage) fill(st + 1, (st + 1) & 1);   // travels while this stage is multiplied (that buffer was last read a barrier ago)
+            if (st + 1 < nstage) fill(st + 1, (st + 1) & 1);   // travels while this stage is multiplied (that buffer was last read a barrier ago)
             const uint4 *Sst = stage + (st & 1) * kKnnStageTiles * kTileU4;
             Af[0] = __builtin_bit_cast(v4i, Sst[lane]);
             Af[1] = __builtin_bit_cast(v4i, Sst[64 + lane]);
@@ -1675,10 +1674,8 @@ __global__ __launch_bounds__(64 * kKnnWaves, kWavesPerSimd) void k_knn2(const ui
                 tile(0, S, tb0, accB, accA);
                 if (2 * pr + 1 < tcount) tile(4, S, tb0 + 32, accA, accB);
             }
-            if (!(DBG & 1)) {
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's share of the next stage has landed
-                if (!(DBG & 16)) __syncthreads();
-            }
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's share of the next stage has landed
+            __syncthreads();
         }
         if (ntiles & 1) top2(accB); else top2(accA);           // the last tile's keys are still pending
     }
@@ -1718,7 +1715,6 @@ __global__ __launch_bounds__(64 * kKnnWaves, kWavesPerSimd) void k_knn2(const ui
             const float f0 = (float)d0, f1 = (float)d1;   // DMatch::distance is float
             acc = (f0 < __fmul_rn(ratio, f1)) && !(f0 > dist_thresh);
         }
-        if (DBG) acc = 0;   // (timing variants compute garbage: nothing is accepted, the host sees empty lists)
         const bool mine = half == 0 && q < nq;
         if (mine) {
             KnnRow r;
@@ -2113,10 +2109,6 @@ void launch_knn2(hipStream_t st, const uint8_t *desc, const int *counts, const i
     const int qblocks = knn_qblocks(kcap), units = npairs * nchunks;
     dim3 grid(8 * qblocks * ((units + 7) / 8));
     // 130 VGPRs: 3 waves per SIMD.  (Capping at 128 for 4 waves spills one query fragment into scratch: 177 vs 162 us.)
-    static const int dbg = getenv("MCORB_KNN_DBG") ? atoi(getenv("MCORB_KNN_DBG")) : 0;   // timing experiments only (scripts/knn_dbg.sh): results are wrong
-    // bit 0: no LDS fill, no barrier; bit 2: no top-2 folds; bit 4: fill, but no barrier
-#define MCORB_KNN_DBG_LAUNCH(D_) if (dbg == D_) { hipLaunchKernelGGL((k_knn2<4, 3, true, D_>), grid, dim3(64 * kKnnWaves), 0, st, E, lcounts, pairs, kcap, nchunks, npairs, qblocks, part, chunkLen, dist_thresh, ratio, out, mlist, mcount); if (ev_mid) (void)hipEventRecord(ev_mid, st); return; }
-    if (nchunks == 1 && dbg) { MCORB_KNN_DBG_LAUNCH(1) MCORB_KNN_DBG_LAUNCH(4) MCORB_KNN_DBG_LAUNCH(5) MCORB_KNN_DBG_LAUNCH(16) }
     if (nchunks == 1) {
         hipLaunchKernelGGL((k_knn2<4, 3, true>), grid, dim3(64 * kKnnWaves), 0, st, E, lcounts, pairs, kcap, nchunks, npairs, qblocks, part, chunkLen,
                            dist_thresh, ratio, out, mlist, mcount);
