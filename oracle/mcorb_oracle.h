@@ -6,12 +6,15 @@
  * as the checker / timed CPU baseline.  libmcorb (the HIP product) never links
  * or calls anything in this directory.
  *
- * PARITY UNPINNED: the reference ships no golden vectors, known-answer tests
- * or fixtures for this path, and its arithmetic lives in
- * un-vendored OpenCV (4.x generic C++ paths are what is restated here), which
- * is not installed in this container.  The restatement is pinned only by
- * hand-derivable known-answer tests of each primitive (tests/test_oracle_*.py)
- * and by structural invariants taken from the reference source.
+ * PARITY: THE REFERENCE'S OWN LOGIC IS PINNED, OPENCV'S PRIMITIVES ARE NOT.  The reference's MCSlam/src/ORBextractor.cpp
+ * is compiled unchanged against the stand-in cv:: types of oracle/refcv (oracle/Makefile, target `ref`) and everything
+ * this file restates from it -- tables, pyramid assembly, cell loop, DistributeOctTree, operator(), IC_Angle,
+ * computeOrbDescriptor, DescriptorDistance, getMatches_distRatio -- is compared with it bit for bit
+ * (tests/test_reference_cpu.py live, tests/test_reference_golden_cpu.py from recorded results).  The reference ships no
+ * golden vectors of its own.  Still unpinned: the third-party primitives below (OpenCV 4.x generic C++
+ * paths are what is restated; OpenCV is not installed here, and the reference build takes exactly these functions from
+ * this file), held only by hand-derivable known-answer tests (tests/test_oracle_*.py); and everything restated from
+ * MultiCameraFrame.cpp / FrontEnd.cpp / DBoW2, which needs libraries that are absent.
  *
  * Every function cites the reference file:line (relative to the MC-SLAM
  * checkout) or the OpenCV routine whose published algorithm it follows.

@@ -28,19 +28,42 @@ def content(rng, W, H):
     return np.clip(base, 0, 255).astype(np.uint8), int(kind)
 
 
+def draw_rig_case(rng):
+    """The next random rig of the stream: camera count, size, feature budget, match threshold / ratio, one image per camera."""
+    C = int(rng.integers(2, 7))
+    W, H = int(rng.integers(320, 900)), int(rng.integers(240, 640))
+    nf = int(rng.integers(200, 1500))
+    thr, ratio = float(rng.integers(30, 110)), float(rng.choice([0.6, 0.7, 0.85, 0.95, 1.0]))
+    frame = int(rng.integers(0, 500))
+    imgs = [mcorb.synth_rig_frame(frame, C, c, W, H) for c in range(C)]
+    if rng.random() < 0.3:   # one camera sees noise: few matches, different counts per camera
+        imgs[int(rng.integers(0, C))] = rng.integers(0, 256, (H, W)).astype(np.uint8)
+    return C, W, H, nf, thr, ratio, imgs
+
+
+def draw_case(rng, orient_mix=False):
+    """The next random single-image case of the stream: size, extractor parameters, orientation mode (drawn only when
+    orient_mix), content.  main() and the CPU test against the reference binary (tests/test_reference_cpu.py) both draw here."""
+    W, H = int(rng.integers(160, 1700)), int(rng.integers(120, 1200))
+    if W > 2.4 * H:
+        W = int(2.4 * H)
+    if H > 1.4 * W:
+        H = int(1.4 * W)
+    nf = int(rng.integers(50, 3500))
+    sf = float(rng.choice([1.1, 1.2, 1.2, 1.2, 1.3, 1.5, 2.0]))
+    nl = int(rng.integers(1, 10))
+    ini, mn = int(rng.integers(5, 40)), int(rng.integers(3, 25))
+    orient = int(orient_mix) and int(rng.integers(0, 2))   # IC-angle mode (not the reference's default)
+    img, kind = content(rng, W, H)
+    return W, H, nf, sf, nl, ini, mn, orient, img, kind
+
+
 def rig_cases(ncases, rng):
     """Random rigs: camera count, size, feature budget, match threshold / ratio; pair lists and tracks against the oracle."""
     bad = 0
     for case in range(ncases):
-        C = int(rng.integers(2, 7))
-        W, H = int(rng.integers(320, 900)), int(rng.integers(240, 640))
-        nf = int(rng.integers(200, 1500))
-        thr, ratio = float(rng.integers(30, 110)), float(rng.choice([0.6, 0.7, 0.85, 0.95, 1.0]))
-        frame = int(rng.integers(0, 500))
+        C, W, H, nf, thr, ratio, imgs = draw_rig_case(rng)
         tag = "rig case %d: %d cams %dx%d nf %d thr %.0f ratio %.2f" % (case, C, W, H, nf, thr, ratio)
-        imgs = [mcorb.synth_rig_frame(frame, C, c, W, H) for c in range(C)]
-        if rng.random() < 0.3:   # one camera sees noise: few matches, different counts per camera
-            imgs[int(rng.integers(0, C))] = rng.integers(0, 256, (H, W)).astype(np.uint8)
         try:
             rig = mcorb.Rig(C, W, H, 1, 1, nfeatures=nf)
         except Exception as e:   # sizes the reference's cell / root-node arithmetic cannot handle (MCORB_E_SIZE); the oracle says -2
@@ -80,17 +103,7 @@ def main():
         return 1 if bad else 0
     bad = 0
     for case in range(ncases):
-        W, H = int(rng.integers(160, 1700)), int(rng.integers(120, 1200))
-        if W > 2.4 * H:
-            W = int(2.4 * H)
-        if H > 1.4 * W:
-            H = int(1.4 * W)
-        nf = int(rng.integers(50, 3500))
-        sf = float(rng.choice([1.1, 1.2, 1.2, 1.2, 1.3, 1.5, 2.0]))
-        nl = int(rng.integers(1, 10))
-        ini, mn = int(rng.integers(5, 40)), int(rng.integers(3, 25))
-        orient = int(os.environ.get("FUZZ_ORIENT", "0")) and int(rng.integers(0, 2))   # IC-angle mode (not the reference's default)
-        img, kind = content(rng, W, H)
+        W, H, nf, sf, nl, ini, mn, orient, img, kind = draw_case(rng, int(os.environ.get("FUZZ_ORIENT", "0")))
         tag = "case %d: %dx%d kind %d nf %d sf %.1f nl %d th %d/%d orient %d" % (case, W, H, kind, nf, sf, nl, ini, mn, orient)
         if os.environ.get("FUZZ_ONLY") and case != int(os.environ["FUZZ_ONLY"]):   # same random stream, one case
             continue

@@ -1,10 +1,11 @@
 #!/usr/bin/env python3
 """Generates tests/golden/*.npz with the CPU oracle (oracle/mcorb_oracle.cpp).
 
-The reference has no fixtures for this path and cannot be built or imported here
-(C++ on OpenCV/DBoW2/glog, none installed), so these vectors are produced by the
-restatement, not by the reference: they pin the oracle against regressions and give
-the GPU tests a second, committed target.  Inputs are the deterministic synthetic
+These vectors are produced by the restatement, not by the reference: they pin the
+oracle against regressions and give the GPU tests a second, committed target
+(matching included, which needs MultiCameraFrame.cpp: not buildable without
+OpenCV/DBoW2/glog).  What the reference's own ORBextractor.cpp returns is recorded
+by make_ref_golden.py in ref_*.npz.  Inputs are the deterministic synthetic
 rig frames (mc-slam_amd/synth.py); only a checksum of each input is stored.
 Run from the repository root:  python tests/golden/make_golden.py
 """

@@ -297,14 +297,14 @@ def intra_matches(descs, dist_thresh=75.0, ratio=0.85, F=None, kps=None, sigma2=
     return tracks[:n].copy(), merg.value
 
 
-def get_matches_dist_ratio(A, iA, B, iB, ratio=0.85):
+def get_matches_dist_ratio(A, iA, B, iB, ratio=0.85, book=0):
     A = np.ascontiguousarray(A, np.uint8).reshape(-1, 32)
     B = np.ascontiguousarray(B, np.uint8).reshape(-1, 32)
     iA = np.ascontiguousarray(iA, np.uint32)
     iB = np.ascontiguousarray(iB, np.uint32)
     mA = np.zeros(len(iA) + 1, np.uint32)
     mB = np.zeros(len(iA) + 1, np.uint32)
-    bk = C.c_int(0)
+    bk = C.c_int(book)   # BookK accumulates across calls in the reference
     n = lib().orc_get_matches_dist_ratio(_ptr(A), _ptr(iA, _u32p), len(iA), _ptr(B), _ptr(iB, _u32p), len(iB),
                                          ratio, _ptr(mA, _u32p), _ptr(mB, _u32p), C.byref(bk))
     return mA[:n].copy(), mB[:n].copy(), bk.value
