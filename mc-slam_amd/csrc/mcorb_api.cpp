@@ -11,28 +11,18 @@ using namespace mcorb;
 
 struct mcorb_extractor {
     mcorb_params params;
-    Rig *rig = nullptr;   // rebuilt when the image size changes
+    std::unique_ptr<Rig> rig;   // rebuilt when the image size changes
     int w = 0, h = 0;
-    // scratch for mcorb_knn2 on host arrays
-    uint8_t *d_desc = nullptr, *d_exp = nullptr;
-    int *d_lcounts = nullptr;
-    uint2 *d_part = nullptr;
-    KnnRow *h_rows = nullptr;
-    uint32_t *h_mlist = nullptr;
-    int *h_mcount = nullptr;
-    int *h_counts = nullptr;
-    int2 *h_pair = nullptr;
+    // scratch for mcorb_knn2 on host arrays, sized for kc descriptors a side (0: to be allocated)
+    DevBuf<uint8_t> d_desc, d_exp;
+    DevBuf<int> d_lcounts;
+    DevBuf<uint2> d_part;
+    HostBuf<KnnRow> h_rows;
+    HostBuf<uint32_t> h_mlist;
+    HostBuf<int> h_mcount, h_counts;
+    HostBuf<int2> h_pair;
     int kc = 0;
 };
-
-#define HIPCHK(x)                                                                      \
-    do {                                                                               \
-        hipError_t e_ = (x);                                                           \
-        if (e_ != hipSuccess) {                                                        \
-            set_error(std::string(#x) + ": " + hipGetErrorString(e_));                 \
-            return MCORB_E_HIP;                                                        \
-        }                                                                              \
-    } while (0)
 
 extern "C" {
 
@@ -94,7 +84,7 @@ int mcorb_rig_upload_u8(mcorb_rig *r, int slot, const uint8_t *const *images, in
 int mcorb_rig_staging(mcorb_rig *r, int slot, int m, uint8_t **ptr, int *stride)
 {
     if (!r || slot < 0 || slot >= (int)r->rig.slots.size() || m < 0 || m >= r->rig.max_images || !ptr) { set_error("staging: bad argument"); return MCORB_E_ARG; }
-    Slot *s = r->rig.slots[slot];
+    Slot *s = r->rig.slots[slot].get();
     {
         std::lock_guard<std::mutex> lk(s->m);
         if (s->busy) { set_error("slot busy"); return MCORB_E_STATE; }
@@ -169,7 +159,7 @@ int mcorb_rig_process(mcorb_rig *r, int slot, int nframes, int lap_x0, int lap_x
 static Slot *get_slot(mcorb_rig *r, int slot)
 {
     if (!r || slot < 0 || slot >= (int)r->rig.slots.size()) { set_error("bad rig/slot"); return nullptr; }
-    Slot *s = r->rig.slots[slot];
+    Slot *s = r->rig.slots[slot].get();
     std::lock_guard<std::mutex> lk(s->m);
     if (s->busy) { set_error("slot busy"); return nullptr; }
     return s;
@@ -346,7 +336,7 @@ static int copy_plane(mcorb_rig *r, int slot, int m, int level, bool blurred, ui
         return MCORB_OK;
     }
     if (!s->d_blur) {       // reference mode does not even allocate them (k_describe_fused blurs around the keypoints only)
-        HIPCHK(hipMalloc((void **)&s->d_blur, (size_t)r->rig.max_images * g.imgBytes));
+        TRY(s->d_blur.alloc((size_t)r->rig.max_images * g.imgBytes));
         HIPCHK(hipMemset(s->d_blur, 0, (size_t)r->rig.max_images * g.imgBytes));
     }
     if (!s->blur_valid) {   // ... nor writes them: make them now from the slot's pyramid
@@ -448,14 +438,12 @@ int mcorb_dev_sort_selftest(int device, const uint32_t *keys, int n, uint32_t *p
     std::sort(b.begin(), b.end(), [](uint64_t x, uint64_t y) { return (x >> 32) < (y >> 32); });
     for (int i = 0; i < n; i++) perm_std[i] = (uint32_t)b[i];
     HIPCHK(hipSetDevice(device));
-    uint64_t *d_in = nullptr, *d_out = nullptr;
-    HIPCHK(hipMalloc((void **)&d_in, (size_t)n * 8));
-    if (hipMalloc((void **)&d_out, (size_t)n * 8) != hipSuccess) { (void)hipFree(d_in); set_error("sort_selftest: out of device memory"); return MCORB_E_HIP; }
-    hipError_t e = hipMemcpy(d_in, a.data(), (size_t)n * 8, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = sort_selftest(d_in, n, d_out);
-    if (e == hipSuccess) e = hipMemcpy(b.data(), d_out, (size_t)n * 8, hipMemcpyDeviceToHost);
-    (void)hipFree(d_in); (void)hipFree(d_out);
-    if (e != hipSuccess) { set_error(hipGetErrorString(e)); return MCORB_E_HIP; }
+    DevBuf<uint64_t> d_in, d_out;
+    TRY(d_in.alloc((size_t)n));
+    TRY(d_out.alloc((size_t)n));
+    HIPCHK(hipMemcpy(d_in, a.data(), (size_t)n * 8, hipMemcpyHostToDevice));
+    HIPCHK(sort_selftest(d_in, n, d_out));
+    HIPCHK(hipMemcpy(b.data(), d_out, (size_t)n * 8, hipMemcpyDeviceToHost));
     for (int i = 0; i < n; i++) perm_dev[i] = (uint32_t)b[i];
     return MCORB_OK;
 }
@@ -565,8 +553,8 @@ int mcorb_rig_get_pairlist(mcorb_rig *r, int slot, int pair, uint32_t *idx1, uin
 //      FrontEnd.cpp:3344-3500: the previous keyframe's set stays in HBM, only the new one is uploaded) ----
 struct mcorb_descblock {
     int device = 0, nsets = 0, kcap = 0;
-    uint8_t *d_desc = nullptr;
-    int32_t *d_counts = nullptr;
+    DevBuf<uint8_t> d_desc;
+    DevBuf<int32_t> d_counts;
     std::vector<int32_t> h_counts;
 };
 
@@ -577,25 +565,19 @@ int mcorb_descblock_create(int device, int nsets, int kcap, mcorb_descblock **ou
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) { set_error("no such device"); return MCORB_E_NODEVICE; }
     HIPCHK(hipSetDevice(device));
-    mcorb_descblock *b = new mcorb_descblock;
+    std::unique_ptr<mcorb_descblock> b(new mcorb_descblock);
     b->device = device; b->nsets = nsets; b->kcap = kcap;
     b->h_counts.assign(nsets, 0);
-    if (hipMalloc((void **)&b->d_desc, (size_t)nsets * kcap * 32) != hipSuccess || hipMalloc((void **)&b->d_counts, (size_t)nsets * sizeof(int32_t)) != hipSuccess ||
-        hipMemset(b->d_counts, 0, (size_t)nsets * sizeof(int32_t)) != hipSuccess) {
-        (void)hipFree(b->d_desc); (void)hipFree(b->d_counts);
-        delete b;
-        set_error("descblock: out of device memory");
-        return MCORB_E_HIP;
-    }
-    *out = b;
+    TRY(b->d_desc.alloc((size_t)nsets * kcap * 32));
+    TRY(b->d_counts.alloc((size_t)nsets));
+    HIPCHK(hipMemset(b->d_counts, 0, (size_t)nsets * sizeof(int32_t)));
+    *out = b.release();
     return MCORB_OK;
 }
 
 void mcorb_descblock_destroy(mcorb_descblock *b)
 {
-    if (!b) return;
-    (void)hipSetDevice(b->device);
-    (void)hipFree(b->d_desc); (void)hipFree(b->d_counts);
+    if (b) (void)hipSetDevice(b->device);
     delete b;
 }
 
@@ -710,11 +692,10 @@ int mcorb_create(const mcorb_params *p, int max_width, int max_height, mcorb_t *
     if (!e) return MCORB_E_ARG;
     e->params = *p;
     if (max_width > 0 && max_height > 0) {
-        e->rig = new Rig;
+        e->rig.reset(new Rig);
         st = e->rig->init(*p, 1, max_width, max_height, 1, 1);
         if (st != MCORB_OK) {
             const std::string keep = get_error();
-            delete e->rig;
             delete e;
             set_error(keep);
             return st;
@@ -729,41 +710,17 @@ int mcorb_create(const mcorb_params *p, int max_width, int max_height, mcorb_t *
     return MCORB_OK;
 }
 
-static void free_knn_scratch(mcorb_t *e)
-{
-    if (e->d_desc) (void)hipFree(e->d_desc);
-    if (e->d_part) (void)hipFree(e->d_part);
-    if (e->d_exp) (void)hipFree(e->d_exp);
-    if (e->d_lcounts) (void)hipFree(e->d_lcounts);
-    e->d_exp = nullptr; e->d_lcounts = nullptr;
-    if (e->h_rows) (void)hipHostFree(e->h_rows);
-    if (e->h_mlist) (void)hipHostFree(e->h_mlist);
-    if (e->h_mcount) (void)hipHostFree(e->h_mcount);
-    e->h_mlist = nullptr; e->h_mcount = nullptr;
-    if (e->h_counts) (void)hipHostFree(e->h_counts);
-    if (e->h_pair) (void)hipHostFree(e->h_pair);
-    e->d_desc = nullptr; e->d_part = nullptr; e->h_rows = nullptr; e->h_counts = nullptr; e->h_pair = nullptr;
-    e->kc = 0;
-}
-
-void mcorb_destroy(mcorb_t *e)
-{
-    if (!e) return;
-    free_knn_scratch(e);
-    delete e->rig;
-    delete e;
-}
+void mcorb_destroy(mcorb_t *e) { delete e; }
 
 static int ensure_rig(mcorb_t *e, int w, int h)
 {
     if (e->rig && e->w == w && e->h == h) return MCORB_OK;
-    delete e->rig;
-    e->rig = new Rig;
+    e->rig.reset();
+    e->rig.reset(new Rig);
     const int st = e->rig->init(e->params, 1, w, h, 1, 1);
     if (st != MCORB_OK) {
         const std::string keep = get_error();
-        delete e->rig;
-        e->rig = nullptr;
+        e->rig.reset();
         set_error(keep);
         return st;
     }
@@ -779,7 +736,7 @@ static int finish_extract(mcorb_t *e, int lap_x0, int lap_x1, mcorb_keypoint *kp
     int st = e->rig->submit(0, j);
     if (st == MCORB_OK) st = e->rig->wait(0);
     if (st != MCORB_OK) return st;
-    Slot *s = e->rig->slots[0];
+    Slot *s = e->rig->slots[0].get();
     const int n = (int)s->kps[0].size();
     if (n_out) *n_out = n;
     if (mono_index_out) *mono_index_out = s->mono[0];
@@ -843,7 +800,7 @@ int mcorb_get_pyramid_level(mcorb_t *e, int level, uint8_t *dst, int dst_stride,
     if (h) *h = g.lv[level].h;
     if (!dst) return MCORB_OK;
     if (dst_stride < g.lv[level].w) return MCORB_E_ARG;
-    Slot *s = e->rig->slots[0];
+    Slot *s = e->rig->slots[0].get();
     HIPCHK(hipSetDevice(e->rig->device));
     HIPCHK(hipStreamSynchronize(s->st));
     HIPCHK(hipMemcpy2D(dst, dst_stride, s->d_pyr + g.lv[level].off, g.lv[level].pitch, g.lv[level].w, g.lv[level].h,
@@ -889,16 +846,16 @@ static int knn2_host_arrays(mcorb_t *e, const uint8_t *q, int nq, const uint8_t 
     HIPCHK(hipSetDevice(e->params.device_id));
     const int need = (std::max(std::max(nq, nt), 1) + 63) / 64 * 64;
     if (need > e->kc) {
-        free_knn_scratch(e);
-        HIPCHK(hipMalloc((void **)&e->d_desc, (size_t)2 * need * 32));
-        HIPCHK(hipMalloc((void **)&e->d_part, knn_part_entries(1, need) * sizeof(uint2)));
-        HIPCHK(hipMalloc((void **)&e->d_exp, (size_t)2 * need * kKnnExpandBytes));
-        HIPCHK(hipMalloc((void **)&e->d_lcounts, 2 * sizeof(int)));
-        HIPCHK(hipHostMalloc((void **)&e->h_rows, (size_t)need * sizeof(KnnRow), hipHostMallocMapped));
-        HIPCHK(hipHostMalloc((void **)&e->h_mlist, knn_mlist_stride(need) * sizeof(uint32_t), hipHostMallocMapped));
-        HIPCHK(hipHostMalloc((void **)&e->h_mcount, (size_t)knn_qblocks(need) * sizeof(int), hipHostMallocMapped));
-        HIPCHK(hipHostMalloc((void **)&e->h_counts, 2 * sizeof(int), hipHostMallocMapped));
-        HIPCHK(hipHostMalloc((void **)&e->h_pair, sizeof(int2), hipHostMallocMapped));
+        e->kc = 0;   // (each alloc releases what it held; a failure on the way leaves kc 0, and the next call allocates all again)
+        TRY(e->d_desc.alloc((size_t)2 * need * 32));
+        TRY(e->d_part.alloc(knn_part_entries(1, need)));
+        TRY(e->d_exp.alloc((size_t)2 * need * kKnnExpandBytes));
+        TRY(e->d_lcounts.alloc(2));
+        TRY(e->h_rows.alloc((size_t)need, hipHostMallocMapped));
+        TRY(e->h_mlist.alloc(knn_mlist_stride(need), hipHostMallocMapped));
+        TRY(e->h_mcount.alloc((size_t)knn_qblocks(need), hipHostMallocMapped));
+        TRY(e->h_counts.alloc(2, hipHostMallocMapped));
+        TRY(e->h_pair.alloc(1, hipHostMallocMapped));
         e->kc = need;
     }
     if (nq) HIPCHK(hipMemcpy(e->d_desc, q, (size_t)nq * 32, hipMemcpyHostToDevice));

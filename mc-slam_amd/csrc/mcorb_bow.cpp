@@ -24,15 +24,6 @@
 
 using namespace mcorb;
 
-#define HIPCHK(x)                                                                      \
-    do {                                                                               \
-        hipError_t e_ = (x);                                                           \
-        if (e_ != hipSuccess) {                                                        \
-            set_error(std::string(#x) + ": " + hipGetErrorString(e_));                 \
-            return MCORB_E_HIP;                                                        \
-        }                                                                              \
-    } while (0)
-
 struct mcorb_vocab {
     int k = 0, L = 0, scoring = 0, weighting = 0, device = 0;
     int nnodes = 0;                              // including the root (node 0)
@@ -41,33 +32,25 @@ struct mcorb_vocab {
     std::vector<int> child_start, child_count;   // into the flattened children arrays
     int nwords = 0;
     // device copies
-    int *d_child_start = nullptr, *d_child_count = nullptr, *d_child_id = nullptr;
-    uint8_t *d_child_desc = nullptr;
-    // scratch for host-array transforms
-    uint8_t *d_desc = nullptr;
-    int *d_word_id = nullptr; double *d_weight = nullptr;
-    mcorb::BowRes *d_out = nullptr, *h_out = nullptr;
-    int cap = 0;
+    DevBuf<int> d_child_start, d_child_count, d_child_id, d_word_id;
+    DevBuf<uint8_t> d_child_desc;
+    DevBuf<double> d_weight;
+    // scratch for host-array transforms (grow-only, ensure_scratch): descriptors, descent results + pinned host mirror
+    DevBuf<uint8_t> d_desc;
+    DevBuf<mcorb::BowRes> d_out;
+    HostBuf<mcorb::BowRes> h_out;
     // scratch of mcorb_rig_match_bow (grow-only): device index tables + result table, pinned host mirror
-    int *d_mi = nullptr; float *d_my = nullptr; int2 *d_mrg = nullptr; int4 *d_mtab = nullptr, *h_mtab = nullptr;
-    size_t mi_cap = 0, my_cap = 0, mrg_cap = 0, mtab_cap = 0;
+    DevBuf<int> d_mi;
+    DevBuf<float> d_my;
+    DevBuf<int2> d_mrg;
+    DevBuf<int4> d_mtab;
+    HostBuf<int4> h_mtab;
     // The scratch above belongs to the vocabulary, the launches that use it go to the calling slot's stream: two threads
     // driving two slots with one vocabulary (the reference transforms from per-camera threads) would race on it, and a
     // grow on one would free what the other's kernel still reads.  Every entry point that touches the scratch holds this
     // from ensure_scratch to its final stream synchronisation.
     std::mutex scratch_mu;
 };
-
-static void free_vocab(mcorb_vocab *v)
-{
-    if (!v) return;
-    (void)hipFree(v->d_child_start); (void)hipFree(v->d_child_count); (void)hipFree(v->d_child_id);
-    (void)hipFree(v->d_child_desc); (void)hipFree(v->d_desc); (void)hipFree(v->d_out); (void)hipFree(v->d_word_id); (void)hipFree(v->d_weight);
-    (void)hipFree(v->d_mi); (void)hipFree(v->d_my); (void)hipFree(v->d_mrg); (void)hipFree(v->d_mtab);
-    if (v->h_mtab) (void)hipHostFree(v->h_mtab);
-    if (v->h_out) (void)hipHostFree(v->h_out);
-    delete v;
-}
 
 static int build_vocab(int k, int L, int scoring, int weighting, const int32_t *parent, const uint8_t *is_leaf,
                        const uint8_t *desc, const double *weight, int n, int device, mcorb_vocab **out)
@@ -82,7 +65,7 @@ static int build_vocab(int k, int L, int scoring, int weighting, const int32_t *
         set_error("no usable HIP device (libmcorb has no CPU path)");
         return MCORB_E_NODEVICE;
     }
-    mcorb_vocab *v = new mcorb_vocab;
+    std::unique_ptr<mcorb_vocab> v(new mcorb_vocab);
     v->k = k; v->L = L; v->scoring = scoring; v->weighting = weighting; v->device = device;
     v->nnodes = n + 1;
     v->parent.assign(n + 1, -1);
@@ -91,7 +74,7 @@ static int build_vocab(int k, int L, int scoring, int weighting, const int32_t *
     std::vector<std::vector<int>> children(n + 1);
     for (int i = 0; i < n; i++) {
         const int nid = i + 1, pid = parent[i];
-        if (pid < 0 || pid >= nid) { delete v; set_error("vocabulary: parent id must precede the node"); return MCORB_E_ARG; }
+        if (pid < 0 || pid >= nid) { set_error("vocabulary: parent id must precede the node"); return MCORB_E_ARG; }
         v->parent[nid] = pid;
         children[pid].push_back(nid);                 // m_nodes[pid].children.push_back(nid): file order
         v->weight[nid] = weight[i];
@@ -99,11 +82,10 @@ static int build_vocab(int k, int L, int scoring, int weighting, const int32_t *
     }
     for (int nid = 1; nid <= n; nid++)
         if ((v->word_id[nid] >= 0) != children[nid].empty()) {
-            delete v;
             set_error("vocabulary: leaf flag disagrees with the tree (a leaf with children or an inner node without)");
             return MCORB_E_ARG;
         }
-    if (children[0].empty()) { delete v; set_error("vocabulary: root has no children"); return MCORB_E_ARG; }
+    if (children[0].empty()) { set_error("vocabulary: root has no children"); return MCORB_E_ARG; }
     v->child_start.assign(n + 1, 0);
     v->child_count.assign(n + 1, 0);
     std::vector<int> child_id;
@@ -118,26 +100,21 @@ static int build_vocab(int k, int L, int scoring, int weighting, const int32_t *
             child_desc.insert(child_desc.end(), desc + (size_t)(c - 1) * 32, desc + (size_t)c * 32);
         }
     }
-    // device copies; a failure on the way frees the half-built object (free_vocab tolerates null members)
-    auto upload = [&]() -> int {
-        HIPCHK(hipSetDevice(device));
-        HIPCHK(hipMalloc((void **)&v->d_child_start, (n + 1) * sizeof(int)));
-        HIPCHK(hipMalloc((void **)&v->d_child_count, (n + 1) * sizeof(int)));
-        HIPCHK(hipMalloc((void **)&v->d_child_id, child_id.size() * sizeof(int)));
-        HIPCHK(hipMalloc((void **)&v->d_child_desc, child_desc.size()));
-        HIPCHK(hipMemcpy(v->d_child_start, v->child_start.data(), (n + 1) * sizeof(int), hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(v->d_child_count, v->child_count.data(), (n + 1) * sizeof(int), hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(v->d_child_id, child_id.data(), child_id.size() * sizeof(int), hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(v->d_child_desc, child_desc.data(), child_desc.size(), hipMemcpyHostToDevice));
-        HIPCHK(hipMalloc((void **)&v->d_word_id, (size_t)(n + 1) * sizeof(int)));
-        HIPCHK(hipMalloc((void **)&v->d_weight, (size_t)(n + 1) * sizeof(double)));
-        HIPCHK(hipMemcpy(v->d_word_id, v->word_id.data(), (size_t)(n + 1) * sizeof(int), hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(v->d_weight, v->weight.data(), (size_t)(n + 1) * sizeof(double), hipMemcpyHostToDevice));
-        return MCORB_OK;
-    };
-    const int st = upload();
-    if (st != MCORB_OK) { free_vocab(v); return st; }
-    *out = v;
+    // device copies; a failure on the way releases the half-built object
+    HIPCHK(hipSetDevice(device));
+    TRY(v->d_child_start.alloc((size_t)n + 1));
+    TRY(v->d_child_count.alloc((size_t)n + 1));
+    TRY(v->d_child_id.alloc(child_id.size()));
+    TRY(v->d_child_desc.alloc(child_desc.size()));
+    HIPCHK(hipMemcpy(v->d_child_start, v->child_start.data(), (n + 1) * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(v->d_child_count, v->child_count.data(), (n + 1) * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(v->d_child_id, child_id.data(), child_id.size() * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(v->d_child_desc, child_desc.data(), child_desc.size(), hipMemcpyHostToDevice));
+    TRY(v->d_word_id.alloc((size_t)n + 1));
+    TRY(v->d_weight.alloc((size_t)n + 1));
+    HIPCHK(hipMemcpy(v->d_word_id, v->word_id.data(), (size_t)(n + 1) * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(v->d_weight, v->weight.data(), (size_t)(n + 1) * sizeof(double), hipMemcpyHostToDevice));
+    *out = v.release();
     return MCORB_OK;
 }
 
@@ -238,15 +215,10 @@ static int emit(const BowList &bow, const std::map<uint32_t, std::vector<int32_t
 
 static int ensure_scratch(mcorb_vocab *v, int n)
 {
-    if (n <= v->cap) return MCORB_OK;
-    (void)hipFree(v->d_desc); (void)hipFree(v->d_out);
-    if (v->h_out) (void)hipHostFree(v->h_out);
-    v->d_desc = nullptr; v->d_out = nullptr; v->h_out = nullptr; v->cap = 0;
-    const int cap = (n + 1023) / 1024 * 1024;
-    HIPCHK(hipMalloc((void **)&v->d_desc, (size_t)cap * 32));
-    HIPCHK(hipMalloc((void **)&v->d_out, (size_t)cap * sizeof(mcorb::BowRes)));
-    HIPCHK(hipHostMalloc((void **)&v->h_out, (size_t)cap * sizeof(mcorb::BowRes), hipHostMallocDefault));
-    v->cap = cap;
+    const size_t cap = ((size_t)n + 1023) / 1024 * 1024;   // (a multiple of 1024 that holds n: what is there already, if that holds n)
+    TRY(v->d_desc.grow(cap * 32));
+    TRY(v->d_out.grow(cap));
+    TRY(v->h_out.grow(cap, hipHostMallocDefault));
     return MCORB_OK;
 }
 
@@ -295,7 +267,7 @@ int mcorb_vocab_load_text(const char *path, int device, mcorb_vocab **out)
     return build_vocab(k, L, n1, n2, parent.data(), leaf.data(), desc.data(), weight.data(), (int)parent.size(), device, out);
 }
 
-void mcorb_vocab_destroy(mcorb_vocab *v) { free_vocab(v); }
+void mcorb_vocab_destroy(mcorb_vocab *v) { delete v; }
 
 int mcorb_vocab_info(const mcorb_vocab *v, int *k, int *L, int *nnodes, int *nwords)
 {
@@ -350,7 +322,7 @@ extern "C" int mcorb_rig_transform_image(mcorb_rig *r, int slot, int m, mcorb_vo
                                          int fv_cap, int *nfv, int32_t *fv_feats, int feat_cap)
 {
     if (!r || !v || slot < 0 || slot >= (int)r->rig.slots.size()) { set_error("rig transform: bad argument"); return MCORB_E_ARG; }
-    Slot *s = r->rig.slots[slot];
+    Slot *s = r->rig.slots[slot].get();
     {
         std::lock_guard<std::mutex> lk(s->m);
         if (s->busy) { set_error("slot busy"); return MCORB_E_STATE; }
@@ -373,7 +345,7 @@ extern "C" int mcorb_rig_transform_images(mcorb_rig *r, int slot, int img0, int 
 {
     if (!r || !v || slot < 0 || slot >= (int)r->rig.slots.size() || nimg < 1) { set_error("rig transform: bad argument"); return MCORB_E_ARG; }
     Rig &R = r->rig;
-    Slot *s = R.slots[slot];
+    Slot *s = R.slots[slot].get();
     {
         std::lock_guard<std::mutex> lk(s->m);
         if (s->busy) { set_error("slot busy"); return MCORB_E_STATE; }
@@ -405,7 +377,7 @@ extern "C" int mcorb_rig_get_transform(mcorb_rig *r, int slot, int m, uint32_t *
                                        uint32_t *fv_nodes, int32_t *fv_offsets, int fv_cap, int *nfv, int32_t *fv_feats, int feat_cap)
 {
     if (!r || slot < 0 || slot >= (int)r->rig.slots.size()) { set_error("get transform: bad argument"); return MCORB_E_ARG; }
-    Slot *s = r->rig.slots[slot];
+    Slot *s = r->rig.slots[slot].get();
     {
         std::lock_guard<std::mutex> lk(s->m);
         if (s->busy) { set_error("slot busy"); return MCORB_E_STATE; }
@@ -568,7 +540,7 @@ extern "C" int mcorb_rig_match_bow_frames(mcorb_rig *r, int slot, int frame0, in
 {
     if (!r || !v || slot < 0 || slot >= (int)r->rig.slots.size() || nframes < 1) { set_error("match_bow: bad argument"); return MCORB_E_ARG; }
     Rig &R = r->rig;
-    Slot *s = R.slots[slot];
+    Slot *s = R.slots[slot].get();
     {
         std::lock_guard<std::mutex> lk(s->m);
         if (s->busy) { set_error("slot busy"); return MCORB_E_STATE; }
@@ -660,27 +632,11 @@ extern "C" int mcorb_rig_match_bow_frames(mcorb_rig *r, int slot, int frame0, in
 
     // 3. best / second-best tables on the GPU (scratch lives in the vocabulary object, grow-only)
     const size_t n_i = (size_t)nimg * kcap * 2 + nimg + nframes + 1, tab_n = (size_t)nframes * npairs * kcap;
-    auto grow = [](void **p, size_t &cap, size_t need, size_t elem) -> bool {
-        if (need <= cap) return true;
-        (void)hipFree(*p);
-        *p = nullptr; cap = 0;
-        if (hipMalloc(p, need * elem) != hipSuccess) return false;
-        cap = need;
-        return true;
-    };
-    if (!grow((void **)&v->d_mi, v->mi_cap, n_i, sizeof(int)) || !grow((void **)&v->d_my, v->my_cap, h_yv.size(), sizeof(float)) ||
-        !grow((void **)&v->d_mrg, v->mrg_cap, h_rg.size(), sizeof(int2))) {
-        set_error("match_bow: device allocation failed");
-        return MCORB_E_HIP;
-    }
-    if (std::max<size_t>(tab_n, 1) > v->mtab_cap) {
-        (void)hipFree(v->d_mtab);
-        if (v->h_mtab) (void)hipHostFree(v->h_mtab);
-        v->d_mtab = nullptr; v->h_mtab = nullptr; v->mtab_cap = 0;
-        HIPCHK(hipMalloc((void **)&v->d_mtab, std::max<size_t>(tab_n, 1) * sizeof(int4)));
-        HIPCHK(hipHostMalloc((void **)&v->h_mtab, std::max<size_t>(tab_n, 1) * sizeof(int4), hipHostMallocDefault));
-        v->mtab_cap = std::max<size_t>(tab_n, 1);
-    }
+    TRY(v->d_mi.grow(n_i));
+    TRY(v->d_my.grow(h_yv.size()));
+    TRY(v->d_mrg.grow(h_rg.size()));
+    TRY(v->d_mtab.grow(std::max<size_t>(tab_n, 1)));
+    TRY(v->h_mtab.grow(std::max<size_t>(tab_n, 1), hipHostMallocDefault));
     int *d_slot_of = v->d_mi, *d_node_feats = d_slot_of + (size_t)nimg * kcap, *d_nfeat = d_node_feats + (size_t)nimg * kcap, *d_rgbase = d_nfeat + nimg;
     HIPCHK(hipMemcpyAsync(d_slot_of, h_slot_of.data(), h_slot_of.size() * sizeof(int), hipMemcpyHostToDevice, s->st));
     HIPCHK(hipMemcpyAsync(d_node_feats, h_node_feats.data(), h_node_feats.size() * sizeof(int), hipMemcpyHostToDevice, s->st));
@@ -711,10 +667,10 @@ int mcorb::bow_job_finish(Rig &R, Slot &s, int nimg)
 {
     const int C = R.ncams, kcap = R.geom.kcap, npairs = C * (C - 1) / 2;
     // the LF stage's transform reads the descent results of the LF descriptors: brought back while the host replays the tracks
-    if (s.lf_job) HIPCHK(hipMemcpyAsync(s.h_lfres, s.d_bowres, (size_t)nimg * kcap * sizeof(BowRes), hipMemcpyDeviceToHost, s.st_dma));
+    if (s.lf_job) HIPCHK(hipMemcpyAsync(s.lbuf.h_lfres, s.bbuf.d_bowres, (size_t)nimg * kcap * sizeof(BowRes), hipMemcpyDeviceToHost, s.st_dma));
     if ((int)s.bowvec.size() < R.max_images) { s.bowvec.resize(R.max_images); s.bowvec_ok.assign(R.max_images, 0); }
     R.pool->parallel_for(nimg, [&](int m, int) {
-        const BowRecView r = bow_rec(s.h_bowrec, kcap, m);
+        const BowRecView r = bow_rec(s.bbuf.h_bowrec, kcap, m);
         const int nbow = r.cnt[0], nfv = r.cnt[1], nf = r.cnt[2];
         BowImageOut &o = s.bowvec[m];
         o.bow_ids.assign(r.ids, r.ids + nbow);
@@ -737,7 +693,7 @@ int mcorb::bow_job_finish(Rig &R, Slot &s, int nimg)
             F.feats[c] = o.fv_feats;
             if (F.fv[c].empty()) F.empty = true;   // the reference returns with no matches (:602-603)
         }
-        bow_replay(F, C, kcap, s.h_btab + (size_t)f * npairs * kcap, s.h_desc, f * C, ratio, s.bow[f]);
+        bow_replay(F, C, kcap, s.bbuf.h_btab + (size_t)f * npairs * kcap, s.h_desc, f * C, ratio, s.bow[f]);
         s.bow_ok[f] = 1;
     }, R.pool_threads + s.index);
     if (s.lf_job) return lf_job_finish(R, s, nframes);
@@ -767,7 +723,7 @@ extern "C" int mcorb_rig_get_bow_tracks(mcorb_rig *r, int slot, int frame, int32
     if (ntracks_out) *ntracks_out = 0;
     if (nwords_out) *nwords_out = 0;
     if (!r || slot < 0 || slot >= (int)r->rig.slots.size()) { set_error("bow tracks: bad argument"); return MCORB_E_ARG; }
-    Slot *s = r->rig.slots[slot];
+    Slot *s = r->rig.slots[slot].get();
     {
         std::lock_guard<std::mutex> lk(s->m);
         if (s->busy) { set_error("slot busy"); return MCORB_E_STATE; }

@@ -31,15 +31,6 @@ static thread_local std::string g_err;
 void set_error(const std::string &msg) { g_err = msg; }
 const char *get_error() { return g_err.c_str(); }
 
-#define HIPCHK(x)                                                                      \
-    do {                                                                               \
-        hipError_t e_ = (x);                                                           \
-        if (e_ != hipSuccess) {                                                        \
-            set_error(std::string(#x) + ": " + hipGetErrorString(e_));                 \
-            return MCORB_E_HIP;                                                        \
-        }                                                                              \
-    } while (0)
-
 static inline int cv_round_f(float v) { return (int)lrintf(v); }
 static inline int cv_round_d(double v) { return (int)lrint(v); }
 static inline int cv_floor_f(float v) { int i = (int)v; return i - (i > v); }
@@ -373,24 +364,15 @@ static int usable_cores()
     return n;
 }
 
+constexpr unsigned kHostMapped = hipHostMallocMapped | hipHostMallocPortable;
+// the buffers Rig::init allocates on the host: device-mapped, zero-filled
 template <typename T>
-static int dev_alloc(T **p, size_t n)
+static int host_alloc(HostBuf<T> &b, size_t n)
 {
-    HIPCHK(hipMalloc((void **)p, n * sizeof(T)));
+    TRY(b.alloc(n, kHostMapped));
+    memset(b, 0, n * sizeof(T));
     return MCORB_OK;
 }
-template <typename T>
-static int host_alloc(T **p, size_t n)
-{
-    HIPCHK(hipHostMalloc((void **)p, n * sizeof(T), hipHostMallocMapped | hipHostMallocPortable));
-    memset(*p, 0, n * sizeof(T));
-    return MCORB_OK;
-}
-#define TRY(x)                       \
-    do {                             \
-        int r_ = (x);                \
-        if (r_ != MCORB_OK) return r_; \
-    } while (0)
 
 int Rig::init(const mcorb_params &p, int ncams_, int W_, int H_, int max_frames_, int nslots)
 {
@@ -442,14 +424,14 @@ int Rig::init(const mcorb_params &p, int ncams_, int W_, int H_, int max_frames_
         resize_win[2 * l + 1] = maxr;
         if ((size_t)maxc * maxr > 60000) { set_error("scale factor too large for the resize window"); return MCORB_E_ARG; }
     }
-    TRY(dev_alloc(&d_taps, taps.size()));
+    TRY(d_taps.alloc(taps.size()));
     HIPCHK(hipMemcpy(d_taps, taps.data(), taps.size() * sizeof(ResizeTap), hipMemcpyHostToDevice));
-    TRY(dev_alloc(&d_lut, lut.size() + 8));
+    TRY(d_lut.alloc(lut.size() + 8));
     HIPCHK(hipMemcpy(d_lut, lut.data(), lut.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
     {
         std::vector<uint32_t> ft;
         fast_cell_off = fast_cell_table(geom, ft);   // (16-byte aligned: the records are read 16 bytes at a time)
-        TRY(dev_alloc(&d_fasttab, ft.size()));
+        TRY(d_fasttab.alloc(ft.size()));
         HIPCHK(hipMemcpy(d_fasttab, ft.data(), ft.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     }
     HIPCHK(upload_umax(tab.umax));
@@ -494,70 +476,55 @@ int Rig::init(const mcorb_params &p, int ncams_, int W_, int H_, int max_frames_
         upload_pipelined = !(getenv("MCORB_UPLOAD_PIPE") && atoi(getenv("MCORB_UPLOAD_PIPE")) == 0);   // (A/B knob)
         graph_every = !gpu_select ? 0 : getenv("MCORB_GRAPH") ? std::max(0, atoi(getenv("MCORB_GRAPH"))) : (nslots == 1 ? 1 : 0);   // (mcorb_rig_select_mode reports what the rig really runs)
     }
-    pool = new WorkerPool(nthreads);
+    pool.reset(new WorkerPool(nthreads));
     pool_threads = nthreads;
-    for (int i = 0; i < nthreads + nslots; i++) scratch.push_back(new SelectScratch);   // workers, then one per slot's submitting thread
+    for (int i = 0; i < nthreads + nslots; i++) scratch.emplace_back(new SelectScratch);   // workers, then one per slot's submitting thread
 
     const int npairs_max = std::max(1, npp * max_frames);
     // an external block usually holds the sets of all slots of a rank (all-to-all) or of all ranks (all-gather)
     ext_cap = (int)align_up(std::max((size_t)4096, (size_t)64 * max_images), 64);
     for (int si = 0; si < nslots; si++) {
-        Slot *s = new Slot;
-        slots.push_back(s);
+        slots.emplace_back(new Slot);
+        Slot *s = slots.back().get();
         s->rig = this;
         s->index = si;
-        if (si > 0 && getenv("MCORB_SHARED_STREAM")) { s->st = slots[0]->st; s->shared_st = true; }
-        else if (getenv("MCORB_CU_SPLIT") && atoi(getenv("MCORB_CU_SPLIT")) >= 2) {
-            // experiment: the slots' compute streams are confined to disjoint groups of XCDs (CU-masked
-            // streams), so that jobs of different groups run side by side instead of taking turns on the whole chip
-            const int parts = std::min(8, atoi(getenv("MCORB_CU_SPLIT")));
-            const int ncu = prop.multiProcessorCount, words = (ncu + 31) / 32;
-            std::vector<uint32_t> mask(words, 0u);
-            const int part = si % parts;
-            // CU index c belongs to XCD c % 8 in the mask's numbering on this part (round-robin): give a group whole XCDs
-            for (int c = 0; c < ncu; c++)
-                if ((c % 8) * parts / 8 == part) mask[c / 32] |= 1u << (c % 32);
-            HIPCHK(hipExtStreamCreateWithCUMask(&s->st, (uint32_t)words, mask.data()));
-        }
-        else HIPCHK(hipStreamCreateWithFlags(&s->st, hipStreamNonBlocking));
-        HIPCHK(hipStreamCreateWithFlags(&s->st_copy, hipStreamNonBlocking));
-        HIPCHK(hipStreamCreateWithFlags(&s->st_dma, hipStreamNonBlocking));
+        for (Stream *st : {&s->st, &s->st_copy, &s->st_dma}) TRY(st->create(hipStreamNonBlocking));
         // events a driver thread waits on (3 compaction, 10 compute stream, 11 DMA stream).  HIP spins by default, which
         // measured 2-4 % faster than interrupt-driven waits at 6 slots; with many slots the spinning drivers would take
         // the cores the selection workers need, so those rigs sleep instead.  MCORB_SYNC=block|spin overrides.
         const char *sync_env = getenv("MCORB_SYNC");
         const bool blocking = sync_env ? !strcmp(sync_env, "block") : crowded;
-        HIPCHK(hipEventCreateWithFlags(&s->ev_x, hipEventDisableTiming));
-        HIPCHK(hipEventCreateWithFlags(&s->ev_c, hipEventDefault));
-        HIPCHK(hipEventCreateWithFlags(&s->ev_e, hipEventDefault));
+        TRY(s->ev_x.create(hipEventDisableTiming));
+        TRY(s->ev_c.create(hipEventDefault));
+        TRY(s->ev_e.create(hipEventDefault));
         for (int e = 0; e < 12; e++) {
             const bool waited = e == 3 || e == 10 || e == 11;
-            HIPCHK(hipEventCreateWithFlags(&s->ev[e], waited && blocking ? hipEventBlockingSync : hipEventDefault));
+            TRY(s->ev[e].create(waited && blocking ? hipEventBlockingSync : hipEventDefault));
         }
         const size_t M = (size_t)max_images;
-        TRY(dev_alloc(&s->d_pyr, M * geom.imgBytes));
+        TRY(s->d_pyr.alloc(M * geom.imgBytes));
         HIPCHK(hipMemset(s->d_pyr, 0, M * geom.imgBytes));
         if (blur_planes) {   // whole blurred planes: only the plane-based descriptor paths write them with every job;
-            TRY(dev_alloc(&s->d_blur, M * geom.imgBytes));   // mcorb_rig_get_blurred allocates on first use otherwise
+            TRY(s->d_blur.alloc(M * geom.imgBytes));   // mcorb_rig_get_blurred allocates on first use otherwise
             HIPCHK(hipMemset(s->d_blur, 0, M * geom.imgBytes));
         }
-        TRY(dev_alloc(&s->d_cellkp, M * geom.cells * geom.cellCap));
-        TRY(dev_alloc(&s->d_cellcnt, M * geom.cells));
-        TRY(dev_alloc(&s->d_sorted, M * geom.candCap));
+        TRY(s->d_cellkp.alloc(M * geom.cells * geom.cellCap));
+        TRY(s->d_cellcnt.alloc(M * geom.cells));
+        TRY(s->d_sorted.alloc(M * geom.candCap));
         s->tbl_ints_per_image = tbl_ints(geom.bucketTotal);
-        TRY(dev_alloc(&s->d_tbl, M * s->tbl_ints_per_image));
-        TRY(host_alloc(&s->h_tbl, M * s->tbl_ints_per_image));
-        TRY(dev_alloc(&s->d_desc, M * geom.kcap * 32));
+        TRY(s->d_tbl.alloc(M * s->tbl_ints_per_image));
+        TRY(host_alloc(s->h_tbl, M * s->tbl_ints_per_image));
+        TRY(s->d_desc.alloc(M * geom.kcap * 32));
         HIPCHK(hipMemset(s->d_desc, 0, M * geom.kcap * 32));
-        TRY(dev_alloc(&s->d_angles, M * geom.kcap));
-        TRY(dev_alloc(&s->d_part, knn_part_entries(npairs_max, geom.kcap)));
-        TRY(dev_alloc(&s->d_exp, M * geom.kcap * (size_t)kKnnExpandBytes));
-        TRY(dev_alloc(&s->d_lcounts, M));
-        TRY(host_alloc(&s->h_cand, M * geom.hostCandCap));
-        TRY(host_alloc(&s->h_overflow, 16));
-        TRY(dev_alloc(&s->d_knn, (size_t)npairs_max * geom.kcap));
-        TRY(host_alloc(&s->h_mlist, (size_t)npairs_max * knn_mlist_stride(geom.kcap)));
-        TRY(host_alloc(&s->h_mcount, (size_t)npairs_max * knn_qblocks(geom.kcap)));
+        TRY(s->d_angles.alloc(M * geom.kcap));
+        TRY(s->d_part.alloc(knn_part_entries(npairs_max, geom.kcap)));
+        TRY(s->d_exp.alloc(M * geom.kcap * (size_t)kKnnExpandBytes));
+        TRY(s->d_lcounts.alloc(M));
+        TRY(host_alloc(s->h_cand, M * geom.hostCandCap));
+        TRY(host_alloc(s->h_overflow, 16));
+        TRY(s->d_knn.alloc((size_t)npairs_max * geom.kcap));
+        TRY(host_alloc(s->h_mlist, (size_t)npairs_max * knn_mlist_stride(geom.kcap)));
+        TRY(host_alloc(s->h_mcount, (size_t)npairs_max * knn_qblocks(geom.kcap)));
         {
             const size_t o_nsel = (size_t)ext_cap * sizeof(int);
             const size_t o_setmap = align_up(o_nsel + M * sizeof(int), 64);
@@ -566,31 +533,31 @@ int Rig::init(const mcorb_params &p, int ncams_, int W_, int H_, int max_frames_
             s->ctrl_pairs_end = o_sel;
             s->ctrl_nsel_off = o_nsel;
             s->ctrl_bytes = o_sel + M * geom.kcap * sizeof(uint32_t);
-            TRY(host_alloc(&s->h_ctrl, s->ctrl_bytes));
-            TRY(dev_alloc(&s->d_ctrl, s->ctrl_bytes));
+            TRY(host_alloc(s->h_ctrl, s->ctrl_bytes));
+            TRY(s->d_ctrl.alloc(s->ctrl_bytes));
             HIPCHK(hipMemset(s->d_ctrl, 0, s->ctrl_bytes));
-            s->h_extcounts = (int *)s->h_ctrl;            s->d_extcounts = (int *)s->d_ctrl;
+            s->h_extcounts = (int *)s->h_ctrl.get();        s->d_extcounts = (int *)s->d_ctrl.get();
             s->h_nsel = (int *)(s->h_ctrl + o_nsel);      s->d_nsel = (int *)(s->d_ctrl + o_nsel);
             s->h_setmap = (int *)(s->h_ctrl + o_setmap);  s->d_setmap = (int *)(s->d_ctrl + o_setmap);
             s->h_pairs = (int2 *)(s->h_ctrl + o_pairs);   s->d_pairs = (int2 *)(s->d_ctrl + o_pairs);
             s->h_sel = (uint32_t *)(s->h_ctrl + o_sel);   s->d_sel = (uint32_t *)(s->d_ctrl + o_sel);
         }
         if (gpu_select) {
-            TRY(dev_alloc(&s->d_selval, M * geom.nlevels * (size_t)select_cap(geom)));
-            TRY(dev_alloc(&s->d_selcnt, M * geom.nlevels));
+            TRY(s->d_selval.alloc(M * geom.nlevels * (size_t)select_cap(geom)));
+            TRY(s->d_selcnt.alloc(M * geom.nlevels));
             s->res_mono_off = 16 * sizeof(int);
             s->res_resp_off = align_up(s->res_mono_off + M * sizeof(int), 64);
             s->res_bytes = align_up(s->res_resp_off + M * geom.kcap, 64);
-            TRY(dev_alloc(&s->d_res, s->res_bytes));
-            TRY(host_alloc(&s->h_res, s->res_bytes));
+            TRY(s->d_res.alloc(s->res_bytes));
+            TRY(host_alloc(s->h_res, s->res_bytes));
             HIPCHK(hipMemset(s->d_res, 0, s->res_bytes));
-            TRY(host_alloc(&s->h_sig, M));
-            HIPCHK(hipEventCreateWithFlags(&s->ev_s, hipEventDefault));
-            HIPCHK(hipEventCreateWithFlags(&s->ev_g, hipEventDefault));
+            TRY(host_alloc(s->h_sig, M));
+            TRY(s->ev_s.create(hipEventDefault));
+            TRY(s->ev_g.create(hipEventDefault));
         }
-        TRY(host_alloc(&s->h_stage, M * (size_t)W * H));
-        TRY(host_alloc(&s->h_desc, M * geom.kcap * 32));
-        TRY(host_alloc(&s->h_angles, M * geom.kcap));
+        TRY(host_alloc(s->h_stage, M * (size_t)W * H));
+        TRY(host_alloc(s->h_desc, M * geom.kcap * 32));
+        TRY(host_alloc(s->h_angles, M * geom.kcap));
         s->kps.resize(M);
         s->mono.assign(M, 0);
         s->sel_val.resize(M * geom.nlevels);
@@ -607,10 +574,13 @@ int Rig::init(const mcorb_params &p, int ncams_, int W_, int H_, int max_frames_
     return MCORB_OK;
 }
 
+// What is order-dependent: a slot's driver thread stops before its streams drain, and the graph exec goes before the buffers
+// and events it names.  Everything else is released by the members' destructors (order: the comment at the top of Slot).
 Rig::~Rig()
 {
     HostProf::report();
-    for (Slot *s : slots) {
+    (void)hipSetDevice(device);
+    for (auto &s : slots) {
         if (s->th.joinable()) {
             {
                 std::lock_guard<std::mutex> lk(s->m);
@@ -619,47 +589,10 @@ Rig::~Rig()
             s->cv.notify_all();
             s->th.join();
         }
-        (void)hipSetDevice(device);
-        if (s->st) (void)hipStreamSynchronize(s->st);
-        if (s->st_copy) (void)hipStreamSynchronize(s->st_copy);
-        if (s->st_dma) (void)hipStreamSynchronize(s->st_dma);
-        (void)hipFree(s->d_pyr); (void)hipFree(s->d_blur); (void)hipFree(s->d_desc); (void)hipFree(s->d_cellkp);
-        (void)hipFree(s->d_cellcnt); (void)hipFree(s->d_sorted); (void)hipFree(s->d_tbl); (void)hipHostFree(s->h_tbl); (void)hipFree(s->d_angles); (void)hipFree(s->d_part); (void)hipFree(s->d_exp); (void)hipFree(s->d_lcounts); (void)hipFree(s->d_f32);
-        (void)hipHostFree(s->h_cand); (void)hipHostFree(s->h_overflow);
-        (void)hipFree(s->d_knn); (void)hipHostFree(s->h_mlist); (void)hipHostFree(s->h_mcount); (void)hipHostFree(s->h_ctrl); (void)hipFree(s->d_ctrl);
-        (void)hipHostFree(s->h_stage);
-        (void)hipHostFree(s->h_desc); (void)hipHostFree(s->h_angles);
-        (void)hipFree(s->d_selval); (void)hipFree(s->d_selcnt); (void)hipFree(s->d_res); (void)hipHostFree(s->h_res); (void)hipHostFree(s->h_sig);
-        (void)hipFree(s->d_undist); (void)hipHostFree(s->h_undist);
-        if (s->ev_u0) (void)hipEventDestroy(s->ev_u0);
-        if (s->ev_u1) (void)hipEventDestroy(s->ev_u1);
-        (void)hipFree(s->d_bowres); (void)hipFree(s->d_bowrec); (void)hipHostFree(s->h_bowrec); (void)hipFree(s->d_bslot);
-        (void)hipFree(s->d_bnfeats); (void)hipFree(s->d_bnfeat); (void)hipFree(s->d_brgbase); (void)hipFree(s->d_byv); (void)hipFree(s->d_brange);
-        (void)hipFree(s->d_btab); (void)hipHostFree(s->h_btab);
-        if (s->ev_b) (void)hipEventDestroy(s->ev_b);
-        (void)hipHostFree(s->h_lftrk); (void)hipFree(s->d_lftrk); (void)hipHostFree(s->h_lfview); (void)hipFree(s->d_lfview);
-        (void)hipHostFree(s->h_lfout); (void)hipHostFree(s->h_lfres);
-        if (s->ev_lf) (void)hipEventDestroy(s->ev_lf);
-        if (s->ev_s) (void)hipEventDestroy(s->ev_s);
-        if (s->ev_g) (void)hipEventDestroy(s->ev_g);
+        for (hipStream_t st : {(hipStream_t)s->st, (hipStream_t)s->st_copy, (hipStream_t)s->st_dma})
+            if (st) (void)hipStreamSynchronize(st);
         if (s->graph_exec) (void)hipGraphExecDestroy(s->graph_exec);
-        for (auto &e : s->ev) if (e) (void)hipEventDestroy(e);
-        if (s->ev_x) (void)hipEventDestroy(s->ev_x);
-        if (s->ev_c) (void)hipEventDestroy(s->ev_c);
-        if (s->ev_e) (void)hipEventDestroy(s->ev_e);
-        if (s->st && !s->shared_st) (void)hipStreamDestroy(s->st);
-        if (s->st_copy) (void)hipStreamDestroy(s->st_copy);
-        if (s->st_dma) (void)hipStreamDestroy(s->st_dma);
-        delete s;
     }
-    slots.clear();
-    delete pool;
-    for (auto *sc : scratch) delete sc;
-    if (d_taps) (void)hipFree(d_taps);
-    if (d_lut) (void)hipFree(d_lut);
-    if (d_fasttab) (void)hipFree(d_fasttab);
-    if (d_undist_cams) (void)hipFree(d_undist_cams);
-    if (d_lfcams) (void)hipFree(d_lfcams);
 }
 
 // An upload into a slot whose job is still running would overwrite the staging buffer and level 0 between the job's
@@ -753,12 +686,7 @@ int Rig::upload_f32(int slot, const float *const *images, int nimg, int stride_b
     HIPCHK(hipSetDevice(device));
     HIPCHK(hipStreamSynchronize(s.st));
     const size_t row_f = (size_t)W * channels, img_f = row_f * H;
-    const size_t need = img_f * 4 * (size_t)max_images;
-    if (s.f32_bytes < need) {
-        if (s.d_f32) HIPCHK(hipFree(s.d_f32));
-        HIPCHK(hipMalloc((void **)&s.d_f32, need));
-        s.f32_bytes = need;
-    }
+    TRY(s.d_f32.grow(img_f * (size_t)max_images));
     for (int m = 0; m < nimg; m++) {
         if (!images[m]) { set_error("upload_f32: empty image"); return MCORB_E_EMPTY; }
         HIPCHK(hipMemcpy2DAsync(s.d_f32 + (size_t)m * img_f, row_f * 4, images[m], stride_bytes, row_f * 4, H,
@@ -1104,7 +1032,7 @@ int Rig::run_select_and_describe(Slot &s, const Job &j, bool then_match)
     TRY(enqueue_back(s, j, then_match, false));
     HIPCHK(hipEventRecord(s.ev[10], s.st));
     LatProf::mark(4);
-    HIPCHK(wait_event(s.ev[10]));   // events, not streams: the compute stream may be shared between slots
+    HIPCHK(wait_event(s.ev[10]));   // (events, not stream synchronisation: wait_event waits the way the rig's wait_mode says)
     if (!s.host_results) HIPCHK(wait_event(s.ev[11]));
     LatProf::mark(5);
     if (params.orientation)
@@ -1126,8 +1054,8 @@ int Rig::enqueue_back(Slot &s, const Job &j, bool then_match, bool gpu_sel)
     if (!gpu_sel && !small) HIPCHK(hipMemcpyAsync(s.d_ctrl, s.h_ctrl, s.ctrl_bytes, hipMemcpyHostToDevice, s.st));
     if (ev_on) HIPCHK(hipEventRecord(s.ev[5], s.st));
     if (small && undist_on) {   // fork: into host-mapped memory (ev_u0, not ev[5]: a captured job records no ev[5])
-        HIPCHK(hipEventRecord(s.ev_u0, s.st));
-        HIPCHK(hipStreamWaitEvent(s.st_dma, s.ev_u0, 0));
+        HIPCHK(hipEventRecord(s.ubuf.ev_u0, s.st));
+        HIPCHK(hipStreamWaitEvent(s.st_dma, s.ubuf.ev_u0, 0));
         TRY(enqueue_undistort(s, nimg));
     }
     launch_describe(s.st, s.d_pyr, blur_planes ? s.d_blur : nullptr, geom, s.ctl.sel, s.ctl.nsel, params.orientation, s.d_desc, s.d_angles, nimg,
@@ -1136,7 +1064,7 @@ int Rig::enqueue_back(Slot &s, const Job &j, bool then_match, bool gpu_sel)
     if (small) {
         if (then_match) TRY(enqueue_match(s, j, true));
         HIPCHK(hipGetLastError());
-        if (undist_on) HIPCHK(hipStreamWaitEvent(s.st, s.ev_u1, 0));   // join
+        if (undist_on) HIPCHK(hipStreamWaitEvent(s.st, s.ubuf.ev_u1, 0));   // join
         if (s.bow_job) TRY(enqueue_bow(s, nimg));
         if (gpu_sel && ev_on) HIPCHK(hipEventRecord(s.ev[11], s.st));
         return MCORB_OK;
@@ -1173,7 +1101,7 @@ int Rig::enqueue_gpu_job(Slot &s, const Job &j, bool then_match)
     const bool small = s.host_results, ev_on = s.ev_on();
     if (then_match && !small)   // pair list / set map first: k_assemble overwrites the control block's nsel and sel afterwards, in stream order
         HIPCHK(hipMemcpyAsync(s.d_ctrl, s.h_ctrl, s.ctrl_pairs_end, hipMemcpyHostToDevice, s.st));
-    int *d_flags = reinterpret_cast<int *>(s.d_res);
+    int *d_flags = reinterpret_cast<int *>(s.d_res.get());
     if (!small) HIPCHK(hipMemsetAsync(d_flags, 0, 16 * sizeof(int), s.st));   // (a small batch's flags travel with its per-image signals)
     TRY(enqueue_front(s, nimg, s.d_tbl));
     HIPCHK(launch_select(s.st, s.d_tbl, s.d_sorted, geom, s.d_selval, s.d_selcnt, d_flags, nimg, select_deep_cap));
@@ -1197,9 +1125,28 @@ int Rig::enqueue_gpu_job(Slot &s, const Job &j, bool then_match)
 int Rig::enqueue_undistort(Slot &s, int nimg)
 {
     const bool host_out = s.host_results;
-    launch_undistort(s.st_dma, s.ctl.sel, s.ctl.nsel, geom.kcap, nimg, ncams, d_undist_cams, tab.scale, tab.nlevels, host_out ? s.h_undist : s.d_undist);
-    if (host_out || s.bow_job) HIPCHK(hipEventRecord(s.ev_u1, s.st_dma));   // (a bound job's BoW tables read the points: enqueue_bow)
-    if (!host_out) HIPCHK(hipMemcpyAsync(s.h_undist, s.d_undist, (size_t)nimg * geom.kcap * sizeof(float2), hipMemcpyDeviceToHost, s.st_dma));
+    launch_undistort(s.st_dma, s.ctl.sel, s.ctl.nsel, geom.kcap, nimg, ncams, d_undist_cams, tab.scale, tab.nlevels, host_out ? s.ubuf.h_undist : s.ubuf.d_undist);
+    if (host_out || s.bow_job) HIPCHK(hipEventRecord(s.ubuf.ev_u1, s.st_dma));   // (a bound job's BoW tables read the points: enqueue_bow)
+    if (!host_out) HIPCHK(hipMemcpyAsync(s.ubuf.h_undist, s.ubuf.d_undist, (size_t)nimg * geom.kcap * sizeof(float2), hipMemcpyDeviceToHost, s.st_dma));
+    return MCORB_OK;
+}
+
+int Rig::lock_idle_slots(const char *who, std::vector<std::unique_lock<std::mutex>> &locks)
+{
+    for (auto &sp : slots) {
+        locks.emplace_back(sp->m);
+        if (sp->busy || sp->submitted) { set_error(std::string(who) + ": a submitted job has not been waited for"); return MCORB_E_STATE; }
+    }
+    return MCORB_OK;
+}
+
+int UndistBufs::alloc(size_t npoints)
+{
+    TRY(d_undist.alloc(npoints));
+    TRY(h_undist.alloc(npoints, kHostMapped));
+    TRY(ev_u0.create(hipEventDisableTiming));
+    TRY(ev_u1.create(hipEventDisableTiming));
+    bound = true;
     return MCORB_OK;
 }
 
@@ -1214,22 +1161,19 @@ int Rig::set_undistortion(int cam, const double *K, const double *dist, int ncoe
         for (double f : {K[0], K[4], c.K[0], c.K[4]})
             if (!std::isfinite(f) || f == 0.) { set_error("set_undistortion: fx / fy must be finite and non-zero"); return MCORB_E_ARG; }
     }
-    // no job of any slot may be in flight, or be waiting to be waited for: every slot stays locked until the tables are in place
     std::vector<std::unique_lock<std::mutex>> locks;
-    for (Slot *sp : slots) {
-        locks.emplace_back(sp->m);
-        if (sp->busy || sp->submitted) { set_error("set_undistortion: a submitted job has not been waited for"); return MCORB_E_STATE; }
-    }
+    TRY(lock_idle_slots("set_undistortion", locks));
     HIPCHK(hipSetDevice(device));
-    if (!clear && !d_undist_cams) {   // first set call: the device table and every slot's buffers and events
-        HIPCHK(hipMalloc((void **)&d_undist_cams, (size_t)ncams * sizeof(UndistCam)));
-        for (Slot *sp : slots) {
-            HIPCHK(hipMalloc((void **)&sp->d_undist, (size_t)max_images * geom.kcap * sizeof(float2)));
-            HIPCHK(hipHostMalloc((void **)&sp->h_undist, (size_t)max_images * geom.kcap * sizeof(float2), hipHostMallocMapped | hipHostMallocPortable));
-            HIPCHK(hipEventCreateWithFlags(&sp->ev_u0, hipEventDisableTiming));
-            HIPCHK(hipEventCreateWithFlags(&sp->ev_u1, hipEventDisableTiming));
-            sp->kps_undist.assign(max_images, {});
-            sp->kps_undist_ok.assign(max_images, 0);
+    if (!clear && !slots[0]->ubuf.bound) {   // first set call: the device table and every slot's buffers and events
+        DevBuf<UndistCam> cams;
+        std::vector<UndistBufs> fresh(slots.size());
+        TRY(cams.alloc((size_t)ncams));
+        for (UndistBufs &b : fresh) TRY(b.alloc((size_t)max_images * geom.kcap));
+        d_undist_cams = std::move(cams);   // all there: commit (nothing below fails before every slot has its bundle)
+        for (size_t i = 0; i < slots.size(); i++) {
+            slots[i]->ubuf = std::move(fresh[i]);
+            slots[i]->kps_undist.assign(max_images, {});
+            slots[i]->kps_undist_ok.assign(max_images, 0);
         }
     }
     undist_cams[cam] = c;
@@ -1262,24 +1206,44 @@ int Rig::enqueue_bow(Slot &s, int nimg)
     const int kcap = geom.kcap, nframes = nimg / ncams;
     const bool match = (s.bow_job & MCORB_BOW_MATCH) && npp > 0 && nframes > 0;
     launch_bow_descend(s.st, s.d_desc, nimg * kcap, b.child_start, b.child_count, b.child_desc, b.child_id, b.word_id, b.weight,
-                       b.L - b.levelsup, s.d_bowres);
-    launch_bow_fold(s.st, s.d_bowres, nsel, kcap, nimg, b.weighting, b.scoring, s.d_bowrec, host_out ? s.h_bowrec : nullptr);
+                       b.L - b.levelsup, s.bbuf.d_bowres);
+    launch_bow_fold(s.st, s.bbuf.d_bowres, nsel, kcap, nimg, b.weighting, b.scoring, s.bbuf.d_bowrec, host_out ? s.bbuf.h_bowrec : nullptr);
     if (match) {
         // the rows of the |dy| < 50 gate: the job's own undistorted points when undistortion is set (k_undistort on the side stream)
-        if (undist_on && !host_out) HIPCHK(hipStreamWaitEvent(s.st, s.ev_u1, 0));   // (small batches joined it already)
-        launch_bow_tables(s.st, s.d_bowrec, kcap, ncams, nframes, nsel, sel, tab.scale, tab.nlevels,
-                          undist_on ? (host_out ? s.h_undist : s.d_undist) : nullptr, s.d_bslot, s.d_bnfeats, s.d_bnfeat, s.d_brgbase,
-                          s.d_byv, s.d_brange);
-        launch_bow_best2(s.st, s.d_desc, 0, kcap, ncams, nframes, s.d_byv, s.d_bslot, s.d_brange, s.d_brgbase, s.d_bnfeats, s.d_bnfeat,
-                         host_out ? s.h_btab : s.d_btab);
+        if (undist_on && !host_out) HIPCHK(hipStreamWaitEvent(s.st, s.ubuf.ev_u1, 0));   // (small batches joined it already)
+        launch_bow_tables(s.st, s.bbuf.d_bowrec, kcap, ncams, nframes, nsel, sel, tab.scale, tab.nlevels,
+                          undist_on ? (host_out ? s.ubuf.h_undist : s.ubuf.d_undist) : nullptr, s.bbuf.d_bslot, s.bbuf.d_bnfeats, s.bbuf.d_bnfeat, s.bbuf.d_brgbase,
+                          s.bbuf.d_byv, s.bbuf.d_brange);
+        launch_bow_best2(s.st, s.d_desc, 0, kcap, ncams, nframes, s.bbuf.d_byv, s.bbuf.d_bslot, s.bbuf.d_brange, s.bbuf.d_brgbase, s.bbuf.d_bnfeats, s.bbuf.d_bnfeat,
+                         host_out ? s.bbuf.h_btab : s.bbuf.d_btab);
     }
     HIPCHK(hipGetLastError());
     if (host_out) return MCORB_OK;
-    HIPCHK(hipEventRecord(s.ev_b, s.st));
-    HIPCHK(hipStreamWaitEvent(s.st_dma, s.ev_b, 0));
-    HIPCHK(hipMemcpyAsync(s.h_bowrec, s.d_bowrec, (size_t)nimg * bow_rec_ints(kcap) * sizeof(int), hipMemcpyDeviceToHost, s.st_dma));
+    HIPCHK(hipEventRecord(s.bbuf.ev_b, s.st));
+    HIPCHK(hipStreamWaitEvent(s.st_dma, s.bbuf.ev_b, 0));
+    HIPCHK(hipMemcpyAsync(s.bbuf.h_bowrec, s.bbuf.d_bowrec, (size_t)nimg * bow_rec_ints(kcap) * sizeof(int), hipMemcpyDeviceToHost, s.st_dma));
     if (match)
-        HIPCHK(hipMemcpyAsync(s.h_btab, s.d_btab, (size_t)nframes * npp * kcap * sizeof(int4), hipMemcpyDeviceToHost, s.st_dma));
+        HIPCHK(hipMemcpyAsync(s.bbuf.h_btab, s.bbuf.d_btab, (size_t)nframes * npp * kcap * sizeof(int4), hipMemcpyDeviceToHost, s.st_dma));
+    return MCORB_OK;
+}
+
+int BowBufs::alloc(const Rig &R)
+{
+    const size_t M = (size_t)R.max_images, kc = (size_t)R.geom.kcap, F = (size_t)R.max_frames;
+    const size_t tab_n = std::max<size_t>((size_t)std::max(R.npp, 1) * F * kc, 1);
+    TRY(d_bowres.alloc(M * kc));
+    TRY(d_bowrec.alloc(M * bow_rec_ints(R.geom.kcap)));
+    TRY(h_bowrec.alloc(M * bow_rec_ints(R.geom.kcap), kHostMapped));
+    TRY(d_bslot.alloc(M * kc));
+    TRY(d_bnfeats.alloc(M * kc));
+    TRY(d_bnfeat.alloc(M));
+    TRY(d_brgbase.alloc(F + 1));
+    TRY(d_byv.alloc(M * kc));
+    TRY(d_brange.alloc(M * kc * (size_t)R.ncams));
+    TRY(d_btab.alloc(tab_n));
+    TRY(h_btab.alloc(tab_n, kHostMapped));
+    TRY(ev_b.create(hipEventDisableTiming));
+    bound = true;
     return MCORB_OK;
 }
 
@@ -1291,31 +1255,28 @@ int Rig::set_vocabulary(const BowBinding &b)
         return MCORB_E_ARG;
     }
     std::vector<std::unique_lock<std::mutex>> locks;
-    for (Slot *sp : slots) {
-        locks.emplace_back(sp->m);
-        if (sp->busy || sp->submitted) { set_error("set_vocabulary: a submitted job has not been waited for"); return MCORB_E_STATE; }
-    }
+    TRY(lock_idle_slots("set_vocabulary", locks));
     HIPCHK(hipSetDevice(device));
-    if (b.flags && !slots.empty() && !slots[0]->d_bowres) {   // first bind: every slot's buffers
-        const size_t M = (size_t)max_images, kc = (size_t)geom.kcap, F = (size_t)max_frames;
-        const size_t tab_n = std::max<size_t>((size_t)std::max(npp, 1) * F * kc, 1);
-        for (Slot *sp : slots) {
-            HIPCHK(hipMalloc((void **)&sp->d_bowres, M * kc * sizeof(BowRes)));
-            HIPCHK(hipMalloc((void **)&sp->d_bowrec, M * bow_rec_ints(geom.kcap) * sizeof(int)));
-            HIPCHK(hipHostMalloc((void **)&sp->h_bowrec, M * bow_rec_ints(geom.kcap) * sizeof(int), hipHostMallocMapped | hipHostMallocPortable));
-            HIPCHK(hipMalloc((void **)&sp->d_bslot, M * kc * sizeof(int)));
-            HIPCHK(hipMalloc((void **)&sp->d_bnfeats, M * kc * sizeof(int)));
-            HIPCHK(hipMalloc((void **)&sp->d_bnfeat, M * sizeof(int)));
-            HIPCHK(hipMalloc((void **)&sp->d_brgbase, (F + 1) * sizeof(int)));
-            HIPCHK(hipMalloc((void **)&sp->d_byv, M * kc * sizeof(float)));
-            HIPCHK(hipMalloc((void **)&sp->d_brange, M * kc * (size_t)ncams * sizeof(int2)));
-            HIPCHK(hipMalloc((void **)&sp->d_btab, tab_n * sizeof(int4)));
-            HIPCHK(hipHostMalloc((void **)&sp->h_btab, tab_n * sizeof(int4), hipHostMallocMapped | hipHostMallocPortable));
-            HIPCHK(hipEventCreateWithFlags(&sp->ev_b, hipEventDisableTiming));
-        }
+    if (b.flags && !slots.empty() && !slots[0]->bbuf.bound) {   // first bind: every slot's buffers
+        std::vector<BowBufs> fresh(slots.size());
+        for (BowBufs &f : fresh) TRY(f.alloc(*this));
+        for (size_t i = 0; i < slots.size(); i++) slots[i]->bbuf = std::move(fresh[i]);   // all there: commit
     }
     bow_bind = b.flags ? b : BowBinding{};
     bow_gen++;
+    return MCORB_OK;
+}
+
+int LfBufs::alloc(size_t n)
+{
+    TRY(h_lftrk.alloc(n, hipHostMallocDefault));
+    TRY(d_lftrk.alloc(n));
+    TRY(h_lfview.alloc(n, hipHostMallocDefault));
+    TRY(d_lfview.alloc(n));
+    TRY(h_lfout.alloc(n, kHostMapped));
+    TRY(h_lfres.alloc(n, hipHostMallocDefault));
+    TRY(ev_lf.create(hipEventDisableTiming));
+    bound = true;
     return MCORB_OK;
 }
 
@@ -1324,24 +1285,15 @@ int Rig::set_lf(const mcorb_camera *cams, int total_feats)
 {
     if (cams && total_feats < 0) { set_error("set_lf: total_feats must be >= 0"); return MCORB_E_ARG; }
     std::vector<std::unique_lock<std::mutex>> locks;
-    for (Slot *sp : slots) {
-        locks.emplace_back(sp->m);
-        if (sp->busy || sp->submitted) { set_error("set_lf: a submitted job has not been waited for"); return MCORB_E_STATE; }
-    }
+    TRY(lock_idle_slots("set_lf", locks));
     HIPCHK(hipSetDevice(device));
-    if (cams && !d_lfcams) {   // first bind: the camera table and every slot's buffers, sized for one track per keypoint
-        HIPCHK(hipMalloc((void **)&d_lfcams, MCORB_MAX_CAMS * sizeof(LfCam)));
-        const size_t n = (size_t)max_images * geom.kcap;
-        for (Slot *sp : slots) {
-            HIPCHK(hipHostMalloc((void **)&sp->h_lftrk, n * sizeof(int4), hipHostMallocDefault));
-            HIPCHK(hipMalloc((void **)&sp->d_lftrk, n * sizeof(int4)));
-            HIPCHK(hipHostMalloc((void **)&sp->h_lfview, n * sizeof(LfView), hipHostMallocDefault));
-            HIPCHK(hipMalloc((void **)&sp->d_lfview, n * sizeof(LfView)));
-            HIPCHK(hipHostMalloc((void **)&sp->h_lfout, n * sizeof(LfTrackOut), hipHostMallocMapped | hipHostMallocPortable));
-            HIPCHK(hipHostMalloc((void **)&sp->h_lfres, n * sizeof(BowRes), hipHostMallocDefault));
-            sp->lf_trk_cap = sp->lf_view_cap = n;
-            HIPCHK(hipEventCreateWithFlags(&sp->ev_lf, hipEventDisableTiming));
-        }
+    if (cams && !slots[0]->lbuf.bound) {   // first bind: the camera table and every slot's buffers, sized for one track per keypoint
+        DevBuf<LfCam> table;
+        std::vector<LfBufs> fresh(slots.size());
+        TRY(table.alloc(MCORB_MAX_CAMS));
+        for (LfBufs &f : fresh) TRY(f.alloc((size_t)max_images * geom.kcap));
+        d_lfcams = std::move(table);   // all there: commit
+        for (size_t i = 0; i < slots.size(); i++) slots[i]->lbuf = std::move(fresh[i]);
     }
     if (cams) {
         std::vector<LfCam> dc((size_t)ncams);
@@ -1372,7 +1324,7 @@ int Rig::undist_records(Slot &s, int m0, int n, std::vector<const mcorb_keypoint
         if (!s.kps_undist_ok[m]) {   // the keypoint records with pt replaced (:336-344)
             std::vector<mcorb_keypoint> &U = s.kps_undist[m];
             U = s.kps[m];
-            const float2 *p = s.h_undist + (size_t)m * geom.kcap;
+            const float2 *p = s.ubuf.h_undist + (size_t)m * geom.kcap;
             for (size_t k = 0; k < U.size(); k++) { U[k].x = p[k].x; U[k].y = p[k].y; }
             s.kps_undist_ok[m] = 1;
         }
@@ -1416,7 +1368,7 @@ int Rig::run_gpu_selected(Slot &s, const Job &j, bool then_match)
     s.nimg_done = nimg;
     if (then_match) TRY(prepare_match(s, j));
     if (s.host_results)
-        for (int m = 0; m < nimg; m++) reinterpret_cast<volatile unsigned long long *>(s.h_sig)[m] = 0;
+        for (int m = 0; m < nimg; m++) static_cast<volatile unsigned long long *>(s.h_sig)[m] = 0;
     // The job is the same ~20 launches and copies every time: captured once per (slot, shape of the job) into a HIP graph and
     // replayed with one call -- the CPU side of a job drops from ~20 runtime calls to one, the gaps between its kernels shrink.
     // (Per-kernel HIP events do not exist inside a replayed graph: mcorb_rig_last_timing reports the job as a whole then.)
@@ -1522,13 +1474,13 @@ int Rig::run_gpu_selected(Slot &s, const Job &j, bool then_match)
     if (s.host_results && records_done < nimg) {
         // the job is over: every signal word and everything behind it has landed
         for (int m = records_done; m < nimg; m++) {
-            const unsigned long long w = reinterpret_cast<const volatile unsigned long long *>(s.h_sig)[m];
+            const unsigned long long w = static_cast<const volatile unsigned long long *>(s.h_sig)[m];
             if (!sel_signal_done(w)) { set_error("extract: the job ended without its results"); return MCORB_E_HIP; }
             decode_signal(m, w);
         }
         s.stale_reads += early_stale;
     }
-    const int flags = s.host_results ? small_flags : reinterpret_cast<const int *>(s.h_res)[0];
+    const int flags = s.host_results ? small_flags : reinterpret_cast<const int *>(s.h_res.get())[0];
     if (flags) {
         // the host stage on the same tables (bit 0: a tree below the bucketing depth; bit 1: more than kcap keypoints -- the host
         // stage reports that error itself)

@@ -15,12 +15,12 @@
 
 #include "../../include/mcorb.h"
 #include "mcorb_common.h"
+#include "mcorb_hip.h"
 #include "mcorb_kernels.h"
 #include "mcorb_select.h"
 
 namespace mcorb {
 
-void set_error(const std::string &msg);
 const char *get_error();
 
 // ORBextractor constructor tables (ORBextractor.cpp:408-468)
@@ -124,40 +124,88 @@ struct LfFrameOut {
     BowImageOut bow;
 };
 
+// UndistortKeyPoints (mcorb_rig_set_undistortion): k_undistort's points of the images in the slot, [image][kcap] (d_ device, h_
+// host-mapped pinned); a fork / join pair of events for small batches, whose kernel runs beside the descriptors and the matcher on
+// the side stream.  Like the two bundles below: allocated whole for every slot at the rig's first set call and only then moved
+// into the slots (`bound`), never while the feature is unused.
+struct UndistBufs {
+    Event ev_u0, ev_u1;
+    DevBuf<float2> d_undist;
+    HostBuf<float2> h_undist;
+    bool bound = false;
+    int alloc(size_t npoints);
+};
+
+// transform() / computeIntraMatches(matches, words_) inside the job (mcorb_rig_set_vocabulary): descent results, k_bow_fold's
+// per-image records (d_ device, h_ host-mapped pinned), k_bow_best2's index tables and its best / second-best table (d_ device, h_
+// host-mapped pinned); ev_b: the BoW kernels are done (the copies of a large batch follow it on st_dma)
+struct BowBufs {
+    Event ev_b;
+    DevBuf<BowRes> d_bowres;
+    DevBuf<int> d_bowrec, d_bslot, d_bnfeats, d_bnfeat, d_brgbase;
+    HostBuf<int> h_bowrec;
+    DevBuf<float> d_byv;
+    DevBuf<int2> d_brange;
+    DevBuf<int4> d_btab;
+    HostBuf<int4> h_btab;
+    bool bound = false;
+    int alloc(const Rig &R);
+};
+
+// obtainLfFeatures inside the job (mcorb_rig_set_lf): k_lf_tracks' tracks and views (h_ pinned, staged for one H2D copy; d_
+// device), its per-track records (host-mapped pinned, written by the kernel), the job's descent results (pinned copy of d_bowres:
+// the LF set's transform reads them); tracks and views are grown by a job that needs more (lf_job_finish); ev_lf: the stage's
+// kernel and copies are done
+struct LfBufs {
+    Event ev_lf;
+    HostBuf<int4> h_lftrk;
+    DevBuf<int4> d_lftrk;
+    HostBuf<LfView> h_lfview;
+    DevBuf<LfView> d_lfview;
+    HostBuf<LfTrackOut> h_lfout;
+    HostBuf<BowRes> h_lfres;
+    bool bound = false;
+    int alloc(size_t n);
+};
+
+// Members are destroyed in reverse order of declaration: the three bundles and the buffers go first, then the events, the streams
+// last.  Rig::~Rig has joined the driver thread, synchronised the streams and destroyed the graph exec before that.
 struct Slot {
     Rig *rig = nullptr;
     int index = 0;
-    bool shared_st = false;
     bool blur_valid = false;   // d_blur holds the blurred planes of the images in d_pyr
-    hipStream_t st = nullptr, st_copy = nullptr, st_dma = nullptr;   // compute; PCIe-bound compaction kernel; D2H copies only
-    hipEvent_t ev_x = nullptr;   // cross-stream hand-offs with the caller's streams (export / external match)
-    hipEvent_t ev_c = nullptr;   // k_compact finished (the table DMA follows it on the side stream)
-    hipEvent_t ev_e = nullptr;   // k_expand finished (k_knn2 follows)
-    hipEvent_t ev[12] = {};  // 0 start, 1 pyramid done, 2 FAST done, 3 compact done, 4 blur done, 5/6 describe(+D2H), 7 knn2 start, 8 knn2 done, 9 finalize done
+    Stream st, st_copy, st_dma;   // compute; PCIe-bound compaction kernel; D2H copies only
+    Event ev_x;   // cross-stream hand-offs with the caller's streams (export / external match)
+    Event ev_c;   // k_compact finished (the table DMA follows it on the side stream)
+    Event ev_e;   // k_expand finished (k_knn2 follows)
+    Event ev[12];  // 0 start, 1 pyramid done, 2 FAST done, 3 compact done, 4 blur done, 5/6 describe(+D2H), 7 knn2 start, 8 knn2 done, 9 finalize done
+    Event ev_s;   // k_select + k_assemble finished
+    Event ev_g;   // in front of a replayed job graph
     // device
-    uint8_t *d_pyr = nullptr, *d_blur = nullptr, *d_desc = nullptr;
-    uint32_t *d_cellkp = nullptr, *d_sorted = nullptr;
-    int *d_cellcnt = nullptr;
-    float *d_angles = nullptr, *d_f32 = nullptr;
-    uint2 *d_part = nullptr;
-    uint8_t *d_exp = nullptr;        // descriptors of the sets being matched, expanded to +-64 int8 in MFMA fragment order (k_expand)
-    int *d_lcounts = nullptr;        // their clamped counts, local set order
-    size_t f32_bytes = 0;
+    DevBuf<uint8_t> d_pyr, d_blur, d_desc;
+    DevBuf<uint32_t> d_cellkp, d_sorted;
+    DevBuf<int> d_cellcnt;
+    DevBuf<float> d_angles, d_f32;   // (d_f32: upload_f32's staging, grown on first use)
+    DevBuf<uint2> d_part;
+    DevBuf<uint8_t> d_exp;           // descriptors of the sets being matched, expanded to +-64 int8 in MFMA fragment order (k_expand)
+    DevBuf<int> d_lcounts;           // their clamped counts, local set order
     // host, device-mapped (kernels write/read these directly over PCIe)
-    uint32_t *h_cand = nullptr;
-    int *h_overflow = nullptr;
+    HostBuf<uint32_t> h_cand;
+    HostBuf<int> h_overflow;
     // k_compact's per-image table blocks (level offsets, shipped flags, bucket starts, bucket winners; layout in
     // mcorb_common.h): written to d_tbl by the kernel, brought to the pinned h_tbl by one DMA per batch
-    int *d_tbl = nullptr, *h_tbl = nullptr;
+    DevBuf<int> d_tbl;
+    HostBuf<int> h_tbl;
     int tbl_ints_per_image = 0;
     const int *tbl(int img) const { return h_tbl + (size_t)img * tbl_ints_per_image; }
     volatile uint32_t touch_sink[16] = {};
-    KnnRow *d_knn = nullptr;         // k-NN rows per pair (device; read back only by mcorb_rig_get_pair_knn2)
-    uint32_t *h_mlist = nullptr;     // per pair: accepted (query << 16 | train), query order (k_knn2_finalize)
-    int *h_mcount = nullptr;
+    DevBuf<KnnRow> d_knn;            // k-NN rows per pair (device; read back only by mcorb_rig_get_pair_knn2)
+    HostBuf<uint32_t> h_mlist;       // per pair: accepted (query << 16 | train), query order (k_knn2_finalize)
+    HostBuf<int> h_mcount;
     // control block: one pinned host buffer + one device mirror, copied with a single
-    // hipMemcpyAsync: [extcounts ext_cap ints][nsel][setmap][pairs][sel]
-    uint8_t *h_ctrl = nullptr, *d_ctrl = nullptr;
+    // hipMemcpyAsync: [extcounts ext_cap ints][nsel][setmap][pairs][sel]; the h_ / d_ pointers below are views into the pair
+    HostBuf<uint8_t> h_ctrl;
+    DevBuf<uint8_t> d_ctrl;
     size_t ctrl_pairs_end = 0, ctrl_bytes = 0;
     int *h_extcounts = nullptr, *h_nsel = nullptr, *h_setmap = nullptr;
     int2 *h_pairs = nullptr;
@@ -167,16 +215,15 @@ struct Slot {
     uint32_t *d_sel = nullptr;
     // GPU selection (MCORB_SELECT_GPU): k_select's per-(image, level) lists, and the result block k_assemble fills for the host
     // ([16 ints of flags][mono M ints][responses M x kcap bytes]; sel / nsel are written into the control block)
-    uint32_t *d_selval = nullptr;
-    int *d_selcnt = nullptr;
-    uint8_t *d_res = nullptr, *h_res = nullptr;
+    DevBuf<uint32_t> d_selval;
+    DevBuf<int> d_selcnt;
+    DevBuf<uint8_t> d_res;
+    HostBuf<uint8_t> h_res;
     size_t res_bytes = 0, res_mono_off = 0, res_resp_off = 0, ctrl_nsel_off = 0;
-    unsigned long long *h_sig = nullptr;      // small GPU-selected jobs: per image, set by k_assemble behind its host-mapped results
+    HostBuf<unsigned long long> h_sig;        // small GPU-selected jobs: per image, set by k_assemble behind its host-mapped results
     bool capturing = false;    // enqueue_gpu_job is being captured into the slot's graph
     int stale_reads = 0;       // small batches: images whose early read did not match the signal word's checksum (redone after the end event)
     int fallbacks = 0;         // jobs of this slot the host stage had to redo (a tree below the bucketing depth)
-    hipEvent_t ev_s = nullptr; // k_select + k_assemble finished
-    hipEvent_t ev_g = nullptr; // in front of a replayed job graph
     // (lf / lf_gen: mcorb_rig_set_lf's binding and set calls -- the LF stage runs after the graph, the key keeps it in view;
     // bow_*: the vocabulary binding the job was captured with -- its tables and levelsup are kernel arguments; bow_gen counts
     // mcorb_rig_set_vocabulary calls, so a freed vocabulary whose address comes back never replays a stale graph.  4-byte fields
@@ -187,8 +234,8 @@ struct Slot {
     unsigned job_counter = 0;
     bool graph_timing = false;             // the last job ran as a graph: timing[] holds the whole job only
     // host, pinned
-    uint8_t *h_stage = nullptr, *h_desc = nullptr;
-    float *h_angles = nullptr;
+    HostBuf<uint8_t> h_stage, h_desc;
+    HostBuf<float> h_angles;
     // results
     std::vector<std::vector<mcorb_keypoint>> kps;   // per image
     std::vector<int> mono;
@@ -213,36 +260,10 @@ struct Slot {
     std::vector<LfFrameOut> lf;     // per frame: the job's obtainLfFeatures + LF transform (mcorb_rig_set_lf)
     std::vector<uint8_t> lf_ok;
     float timing[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    // UndistortKeyPoints (mcorb_rig_set_undistortion): k_undistort's points of the images in the slot, [image][kcap] (d_ device,
-    // h_ host-mapped pinned; both allocated at the rig's first set call, never while no camera has undistortion set); a fork / join
-    // pair of events for small batches, whose kernel runs beside the descriptors and the matcher on the side stream
-    float2 *d_undist = nullptr, *h_undist = nullptr;
-    hipEvent_t ev_u0 = nullptr, ev_u1 = nullptr;
     bool undist_job = false;      // the images in the slot were extracted with k_undistort (some camera had undistortion set)
     unsigned undist_gen = 0;      // Rig::undist_gen when they were extracted
     bool submitted = false;       // a job was submitted and not yet waited for (mcorb_rig_set_undistortion refuses then)
-    // transform() / computeIntraMatches(matches, words_) inside the job (mcorb_rig_set_vocabulary), all allocated at the rig's first
-    // bind, never while no vocabulary was bound: descent results, k_bow_fold's per-image records (d_ device, h_ host-mapped pinned),
-    // k_bow_best2's index tables and its best / second-best table (d_ device, h_ host-mapped pinned); ev_b: the BoW kernels are done
-    // (the copies of a large batch follow it on st_dma)
-    BowRes *d_bowres = nullptr;
-    int *d_bowrec = nullptr, *h_bowrec = nullptr;
-    int *d_bslot = nullptr, *d_bnfeats = nullptr, *d_bnfeat = nullptr, *d_brgbase = nullptr;
-    float *d_byv = nullptr;
-    int2 *d_brange = nullptr;
-    int4 *d_btab = nullptr, *h_btab = nullptr;
-    hipEvent_t ev_b = nullptr;
     int bow_job = 0;              // MCORB_BOW_* flags the images in the slot were extracted with (0: no BoW stage ran)
-    // obtainLfFeatures inside the job (mcorb_rig_set_lf), allocated at the rig's first LF bind, never while nothing was bound:
-    // k_lf_tracks' tracks and views (h_ pinned, staged for one H2D copy; d_ device), its per-track records (host-mapped pinned,
-    // written by the kernel), the job's descent results (pinned copy of d_bowres: the LF set's transform reads them); capacities
-    // in tracks / views (grown on a job that needs more); ev_lf: the stage's kernel and copies are done
-    int4 *h_lftrk = nullptr, *d_lftrk = nullptr;
-    LfView *h_lfview = nullptr, *d_lfview = nullptr;
-    LfTrackOut *h_lfout = nullptr;
-    BowRes *h_lfres = nullptr;
-    size_t lf_trk_cap = 0, lf_view_cap = 0;
-    hipEvent_t ev_lf = nullptr;
     bool lf_job = false;          // the job ran the LF stage (LF bound and the vocabulary bound with MCORB_BOW_MATCH)
     // image_kps_undist of the images, built on first read from kps and h_undist (Rig::undist_records)
     std::vector<std::vector<mcorb_keypoint>> kps_undist;
@@ -275,6 +296,10 @@ struct Slot {
     bool busy = false, quit = false, inline_job = false;
     int status = MCORB_OK;
     std::string err;
+    // the lazily bound bundles (last: released first)
+    UndistBufs ubuf;
+    BowBufs bbuf;
+    LfBufs lbuf;
 };
 
 // inputs of the old=true epipolar check: F per camera pair (i<j, row-major 3x3, x_j^T F x_i = 0), the
@@ -304,14 +329,14 @@ public:
     int ncams = 0, W = 0, H = 0, max_frames = 0, max_images = 0, npp = 0 /* pairs per frame */;
     int ext_cap = 0;   // descriptor sets an external block may hold (mcorb_rig_match_external*)
     int device = 0;
-    ResizeTap *d_taps = nullptr;
-    uint16_t *d_lut = nullptr;             // path-code tables of all levels (k_compact)
-    uint32_t *d_fasttab = nullptr;         // k_fast_cells' per-cell records (fast_cell_table)
+    DevBuf<ResizeTap> d_taps;
+    DevBuf<uint16_t> d_lut;                // path-code tables of all levels (k_compact)
+    DevBuf<uint32_t> d_fasttab;            // k_fast_cells' per-cell records (fast_cell_table)
     int fast_cell_off = 0;                  // dword offset of the records inside d_fasttab
     SelectParams selp[kMaxLevels];         // per-level DistributeOctTree constants + bucketing depth
     int resize_win[2 * kMaxLevels] = {};   // per level: LDS window pitch, rows (see launch_pyramid)
-    std::vector<Slot *> slots;
-    WorkerPool *pool = nullptr;
+    std::vector<std::unique_ptr<Slot>> slots;
+    std::unique_ptr<WorkerPool> pool;
     int pool_threads = 0;
     // admission to the GPU (mcorb_params.gpu_jobs): with more slots than jobs the GPU runs well side by side, the extra slots are
     // the ones whose results the host is post-processing -- the GPU does not wait for the host, and is not oversubscribed either
@@ -327,7 +352,7 @@ public:
     bool gpu_select = false;   // DistributeOctTree's list discipline runs in k_select (MCORB_SELECT_GPU); else on the worker pool
     int wait_mode = 0;         // how a thread waits for a HIP event: 0 spin (hipEventSynchronize), 1 interrupt-driven, 2 poll + short sleeps
     hipError_t wait_event(hipEvent_t ev) const;
-    std::vector<SelectScratch *> scratch;   // one per worker
+    std::vector<std::unique_ptr<SelectScratch>> scratch;   // one per worker
 
     void merge_tracks(Slot &s, int f, const EpipolarGate *gate, std::vector<int32_t> &tr, int &mergeable_out) const;
 
@@ -335,7 +360,7 @@ public:
     // cameras not set), its device copy k_undistort reads (graph replays included), and which cameras are set at all
     std::vector<UndistCam> undist_cams;
     std::vector<uint8_t> undist_set;
-    UndistCam *d_undist_cams = nullptr;
+    DevBuf<UndistCam> d_undist_cams;   // (allocated with the slots' UndistBufs)
     bool undist_on = false;     // some camera is set: jobs run k_undistort; otherwise a job is exactly what it is without the feature
     unsigned undist_gen = 0;    // set calls so far (images extracted before the last one have no undistorted set)
     int set_undistortion(int cam, const double *K, const double *dist, int ncoeffs);
@@ -363,11 +388,14 @@ public:
     bool lf_on = false;
     int lf_total_feats = 3000;
     std::vector<mcorb_camera> lf_cams;
-    LfCam *d_lfcams = nullptr;
+    DevBuf<LfCam> d_lfcams;            // (allocated with the slots' LfBufs)
     unsigned lf_gen = 0;
     int set_lf(const mcorb_camera *cams, int total_feats);
     int set_vocabulary(const BowBinding &b);
     int check_job_shape(const Job &j) const;   // a bound MCORB_BOW_MATCH needs whole frames
+    // what the three set_* calls start with: no job of any slot may be in flight, or be waiting to be waited for -- every slot is
+    // locked (the caller keeps `locks` until its tables are in place), MCORB_E_STATE with `who` in the message otherwise
+    int lock_idle_slots(const char *who, std::vector<std::unique_lock<std::mutex>> &locks);
 
 private:
     bool copy_kernel = false;  // D2H of tables / descriptors by k_copy_to_host instead of hipMemcpyAsync (see Rig::init)

@@ -1,0 +1,113 @@
+// mcorb_hip.h -- the one place where HIP buffers, events and streams are acquired and released: the error macros and four
+// move-only owners.  No shared ownership, no allocator policy: an owner holds one handle and its destructor releases it.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+
+#include <string>
+#include <utility>
+
+#include "../../include/mcorb.h"
+
+namespace mcorb {
+void set_error(const std::string &msg);
+}
+
+#define HIPCHK(x)                                                                      \
+    do {                                                                               \
+        hipError_t e_ = (x);                                                           \
+        if (e_ != hipSuccess) {                                                        \
+            mcorb::set_error(std::string(#x) + ": " + hipGetErrorString(e_));          \
+            return MCORB_E_HIP;                                                        \
+        }                                                                              \
+    } while (0)
+#define TRY(x)                         \
+    do {                               \
+        int r_ = (x);                  \
+        if (r_ != MCORB_OK) return r_; \
+    } while (0)
+
+namespace mcorb {
+
+// what the four owners share: handle H (null = empty), released with Release(H); n_ is the element count of a buffer
+template <typename H, auto Release>
+class Owner {
+public:
+    Owner() = default;
+    Owner(Owner &&o) noexcept { swap(o); }
+    Owner &operator=(Owner &&o) noexcept { swap(o); return *this; }   // (o's destructor releases what this held)
+    Owner(const Owner &) = delete;
+    Owner &operator=(const Owner &) = delete;
+    ~Owner() { reset(); }
+    void reset()
+    {
+        if (h_) (void)Release(h_);
+        h_ = nullptr;
+        n_ = 0;
+    }
+    operator H() const { return h_; }   // call sites pass the owner where they passed the raw handle
+    H get() const { return h_; }        // (where a cast to another pointer type follows)
+
+protected:
+    void swap(Owner &o) { std::swap(h_, o.h_); std::swap(n_, o.n_); }
+    H h_ = nullptr;
+    size_t n_ = 0;
+};
+
+// alloc / create: release what is held, then acquire; MCORB_E_HIP through set_error (and an empty owner) on failure.
+// grow, for grow-only scratch: nothing when n elements fit already, otherwise alloc -- size() is 0 after a failed one, so the next
+// call allocates again.
+template <typename T>
+class DevBuf : public Owner<T *, hipFree> {
+public:
+    size_t size() const { return this->n_; }   // elements allocated
+    int alloc(size_t n)
+    {
+        this->reset();
+        void *p = nullptr;
+        HIPCHK(hipMalloc(&p, n * sizeof(T)));
+        this->h_ = (T *)p;
+        this->n_ = n;
+        return MCORB_OK;
+    }
+    int grow(size_t n) { return n <= size() ? MCORB_OK : alloc(n); }
+};
+
+// pinned host memory; flags: hipHostMallocDefault, or hipHostMallocMapped [| hipHostMallocPortable] where kernels access it
+template <typename T>
+class HostBuf : public Owner<T *, hipHostFree> {
+public:
+    size_t size() const { return this->n_; }
+    int alloc(size_t n, unsigned flags)
+    {
+        this->reset();
+        void *p = nullptr;
+        HIPCHK(hipHostMalloc(&p, n * sizeof(T), flags));
+        this->h_ = (T *)p;
+        this->n_ = n;
+        return MCORB_OK;
+    }
+    int grow(size_t n, unsigned flags) { return n <= size() ? MCORB_OK : alloc(n, flags); }
+};
+
+class Event : public Owner<hipEvent_t, hipEventDestroy> {
+public:
+    int create(unsigned flags)
+    {
+        reset();
+        HIPCHK(hipEventCreateWithFlags(&h_, flags));
+        return MCORB_OK;
+    }
+};
+
+class Stream : public Owner<hipStream_t, hipStreamDestroy> {
+public:
+    int create(unsigned flags)
+    {
+        reset();
+        HIPCHK(hipStreamCreateWithFlags(&h_, flags));
+        return MCORB_OK;
+    }
+};
+
+}  // namespace mcorb

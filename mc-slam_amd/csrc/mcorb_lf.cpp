@@ -276,7 +276,7 @@ extern "C" int mcorb_rig_obtain_lf_features(mcorb_rig *r, int slot, int frame, c
     if (n_out) *n_out = 0;
     if (!r || slot < 0 || slot >= (int)r->rig.slots.size()) { set_error("obtain_lf_features: bad argument"); return MCORB_E_ARG; }
     Rig &R = r->rig;
-    Slot *s = R.slots[slot];
+    Slot *s = R.slots[slot].get();
     {
         std::lock_guard<std::mutex> lk(s->m);
         if (s->busy) { set_error("slot busy"); return MCORB_E_STATE; }
@@ -306,7 +306,7 @@ extern "C" int mcorb_rig_obtain_lf_features_frames(mcorb_rig *r, int slot, int f
         return MCORB_E_ARG;
     }
     Rig &R = r->rig;
-    Slot *s = R.slots[slot];
+    Slot *s = R.slots[slot].get();
     {
         std::lock_guard<std::mutex> lk(s->m);
         if (s->busy) { set_error("slot busy"); return MCORB_E_STATE; }
@@ -342,14 +342,6 @@ extern "C" int mcorb_rig_obtain_lf_features_frames(mcorb_rig *r, int slot, int f
 // obtainLfFeatures right after computeIntraMatches(matches_map, words_) with words_ overwritten by ones (FrontEnd.cpp:1010) and
 // all-zero segmentation masks (mc_slam_app.cpp:224): every view of a track is kept, words_fil is {1} or empty.
 // ---------------------------------------------------------------------------
-#define HIPCHK(x)                                                                      \
-    do {                                                                               \
-        hipError_t e_ = (x);                                                           \
-        if (e_ != hipSuccess) {                                                        \
-            set_error(std::string(#x) + ": " + hipGetErrorString(e_));                 \
-            return MCORB_E_HIP;                                                        \
-        }                                                                              \
-    } while (0)
 
 int mcorb::lf_job_finish(Rig &R, Slot &s, int nframes)
 {
@@ -381,23 +373,12 @@ int mcorb::lf_job_finish(Rig &R, Slot &s, int nframes)
     const int nsend = boff.back();
     // (the first bind sized the buffers for one track and one view per keypoint, which the BoW-guided tracks never exceed; grown
     // here all the same should a job need more)
-    if ((size_t)tbase[nframes] > s.lf_trk_cap) {
-        (void)hipHostFree(s.h_lftrk); (void)hipFree(s.d_lftrk); (void)hipHostFree(s.h_lfout);
-        s.h_lftrk = s.d_lftrk = nullptr; s.h_lfout = nullptr; s.lf_trk_cap = 0;
-        const size_t n = (size_t)tbase[nframes];
-        HIPCHK(hipHostMalloc((void **)&s.h_lftrk, n * sizeof(int4), hipHostMallocDefault));
-        HIPCHK(hipMalloc((void **)&s.d_lftrk, n * sizeof(int4)));
-        HIPCHK(hipHostMalloc((void **)&s.h_lfout, n * sizeof(LfTrackOut), hipHostMallocMapped | hipHostMallocPortable));
-        s.lf_trk_cap = n;
-    }
-    if ((size_t)vbase[nframes] > s.lf_view_cap) {
-        (void)hipHostFree(s.h_lfview); (void)hipFree(s.d_lfview);
-        s.h_lfview = s.d_lfview = nullptr; s.lf_view_cap = 0;
-        const size_t n = (size_t)vbase[nframes];
-        HIPCHK(hipHostMalloc((void **)&s.h_lfview, n * sizeof(LfView), hipHostMallocDefault));
-        HIPCHK(hipMalloc((void **)&s.d_lfview, n * sizeof(LfView)));
-        s.lf_view_cap = n;
-    }
+    const size_t ntrk = (size_t)tbase[nframes], nview = (size_t)vbase[nframes];
+    TRY(s.lbuf.h_lftrk.grow(ntrk, hipHostMallocDefault));
+    TRY(s.lbuf.d_lftrk.grow(ntrk));
+    TRY(s.lbuf.h_lfout.grow(ntrk, hipHostMallocMapped | hipHostMallocPortable));
+    TRY(s.lbuf.h_lfview.grow(nview, hipHostMallocDefault));
+    TRY(s.lbuf.d_lfview.grow(nview));
     R.pool->parallel_for(nframes, [&](int f, int) {
         const BowFrameOut &b = s.bow[f];
         const int nt = (int)b.n_rays.size();
@@ -408,24 +389,24 @@ int mcorb::lf_job_finish(Rig &R, Slot &s, int nframes)
             int nv = 0;
             for (int c = 0; c < C; c++) nv += tr[c] != -1;
             if (nv < 2) continue;
-            s.h_lftrk[next[bin_of(nv)]++] = make_int4(vo, nv, f, tbase[f] + t);
+            s.lbuf.h_lftrk[next[bin_of(nv)]++] = make_int4(vo, nv, f, tbase[f] + t);
             for (int c = 0; c < C; c++)
                 if (tr[c] != -1) {
                     const mcorb_keypoint &kp = s.kps[f * C + c][tr[c]];
-                    s.h_lfview[vo++] = LfView{c, tr[c], kp.x, kp.y};
+                    s.lbuf.h_lfview[vo++] = LfView{c, tr[c], kp.x, kp.y};
                 }
         }
     }, R.pool_threads + s.index);
     const auto T1 = now();
     // 2. one launch behind the descent results' copy (bow_job_finish), records straight to host-mapped memory
     if (nsend) {
-        HIPCHK(hipMemcpyAsync(s.d_lftrk, s.h_lftrk, (size_t)nsend * sizeof(int4), hipMemcpyHostToDevice, s.st_dma));
-        HIPCHK(hipMemcpyAsync(s.d_lfview, s.h_lfview, (size_t)vbase[nframes] * sizeof(LfView), hipMemcpyHostToDevice, s.st_dma));
-        launch_lf_tracks(s.st_dma, s.d_lftrk, s.d_lfview, nsend, R.d_lfcams, s.d_desc, kcap, C, s.h_lfout);
+        HIPCHK(hipMemcpyAsync(s.lbuf.d_lftrk, s.lbuf.h_lftrk, (size_t)nsend * sizeof(int4), hipMemcpyHostToDevice, s.st_dma));
+        HIPCHK(hipMemcpyAsync(s.lbuf.d_lfview, s.lbuf.h_lfview, (size_t)vbase[nframes] * sizeof(LfView), hipMemcpyHostToDevice, s.st_dma));
+        launch_lf_tracks(s.st_dma, s.lbuf.d_lftrk, s.lbuf.d_lfview, nsend, R.d_lfcams, s.d_desc, kcap, C, s.lbuf.h_lfout);
         HIPCHK(hipGetLastError());
     }
-    HIPCHK(hipEventRecord(s.ev_lf, s.st_dma));
-    HIPCHK(R.wait_event(s.ev_lf));
+    HIPCHK(hipEventRecord(s.lbuf.ev_lf, s.st_dma));
+    HIPCHK(R.wait_event(s.lbuf.ev_lf));
     const auto T2 = now();
     // 3. per frame: the order-dependent bookkeeping on the records, then the LF set's transform from the job's descent results
     std::vector<const mcorb_keypoint *> ku;
@@ -440,10 +421,10 @@ int mcorb::lf_job_finish(Rig &R, Slot &s, int nframes)
         const std::vector<uint32_t> ones((size_t)nt, 1u);   // words_ (FrontEnd.cpp:1010)
         LfFrameOut &o = s.lf[f];
         status[f] = lf_frame_core(R, &s, s.index, f, b.tracks.data(), nt, ones.data(), R.lf_cams.data(), nullptr, 0,
-                                  kst ? ku.data() + (size_t)f * C : nullptr, R.lf_total_feats, s.h_lfout + tbase[f], o, false);
+                                  kst ? ku.data() + (size_t)f * C : nullptr, R.lf_total_feats, s.lbuf.h_lfout + tbase[f], o, false);
         if (status[f] != MCORB_OK) { errs[f] = get_error(); return; }
         std::vector<BowRes> res(o.src.size());
-        for (size_t i = 0; i < o.src.size(); i++) res[i] = s.h_lfres[o.src[i]];
+        for (size_t i = 0; i < o.src.size(); i++) res[i] = s.lbuf.h_lfres[o.src[i]];
         bow_assemble(weighting, scoring, res.data(), (int)res.size(), o.bow);
         s.lf_ok[f] = 1;
     }, R.pool_threads + s.index);
@@ -465,7 +446,7 @@ extern "C" int mcorb_rig_set_lf(mcorb_rig *r, const mcorb_camera *cams, int tota
 static int lf_frame_of(mcorb_rig *r, int slot, int frame, const LfFrameOut **o)
 {
     if (!r || slot < 0 || slot >= (int)r->rig.slots.size()) { set_error("lf getter: bad argument"); return MCORB_E_ARG; }
-    Slot *s = r->rig.slots[slot];
+    Slot *s = r->rig.slots[slot].get();
     {
         std::lock_guard<std::mutex> lk(s->m);
         if (s->busy) { set_error("slot busy"); return MCORB_E_STATE; }
@@ -531,26 +512,22 @@ extern "C" int mcorb_dev_triangulate_selftest(int device, const double *x, const
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) { set_error("no usable HIP device"); return MCORB_E_NODEVICE; }
     HIPCHK(hipSetDevice(device));
-    double *d_x = nullptr, *d_P = nullptr, *d_X = nullptr;
-    int *d_nv = nullptr, *d_voff = nullptr, *d_br = nullptr;
-    hipError_t e = hipMalloc((void **)&d_x, nviews * 2 * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void **)&d_P, nviews * 12 * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void **)&d_X, (size_t)n * 3 * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void **)&d_nv, (size_t)n * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc((void **)&d_voff, (size_t)n * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc((void **)&d_br, (size_t)n * sizeof(int));
-    if (e == hipSuccess) e = hipMemcpy(d_x, x, nviews * 2 * sizeof(double), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_P, P, nviews * 12 * sizeof(double), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_nv, nv, (size_t)n * sizeof(int), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_voff, voff.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        launch_tri_selftest(nullptr, d_x, d_P, d_nv, d_voff, n, d_X, d_br);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpy(X, d_X, (size_t)n * 3 * sizeof(double), hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(branch, d_br, (size_t)n * sizeof(int), hipMemcpyDeviceToHost);
-    (void)hipFree(d_x); (void)hipFree(d_P); (void)hipFree(d_X); (void)hipFree(d_nv); (void)hipFree(d_voff); (void)hipFree(d_br);
-    if (e != hipSuccess) { set_error(std::string("triangulate selftest: ") + hipGetErrorString(e)); return MCORB_E_HIP; }
+    DevBuf<double> d_x, d_P, d_X;
+    DevBuf<int> d_nv, d_voff, d_br;
+    TRY(d_x.alloc(nviews * 2));
+    TRY(d_P.alloc(nviews * 12));
+    TRY(d_X.alloc((size_t)n * 3));
+    TRY(d_nv.alloc((size_t)n));
+    TRY(d_voff.alloc((size_t)n));
+    TRY(d_br.alloc((size_t)n));
+    HIPCHK(hipMemcpy(d_x, x, nviews * 2 * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_P, P, nviews * 12 * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_nv, nv, (size_t)n * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_voff, voff.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice));
+    launch_tri_selftest(nullptr, d_x, d_P, d_nv, d_voff, n, d_X, d_br);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpy(X, d_X, (size_t)n * 3 * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(branch, d_br, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
     return MCORB_OK;
 }
 

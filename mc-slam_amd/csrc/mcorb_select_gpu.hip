@@ -24,6 +24,7 @@
 #include <stdlib.h>
 
 #include "mcorb_common.h"
+#include "mcorb_hip.h"
 #include "mcorb_kernels.h"
 #include "mcorb_sortmodel.h"
 
@@ -697,9 +698,9 @@ hipError_t launch_select(hipStream_t st, const int *tbl, const uint32_t *sorted,
         if (e != hipSuccess) return e;
         configured = lds;
     }
-    static unsigned long long *prof = nullptr;
+    static HostBuf<unsigned long long> prof;
     static const bool prof_on = getenv("MCORB_SELECT_PROF") != nullptr;
-    if (prof_on && !prof) (void)hipHostMalloc((void **)&prof, kMaxLevels * 32 * 8, hipHostMallocMapped);
+    if (prof_on && !prof) (void)prof.alloc(kMaxLevels * 32, hipHostMallocMapped);
     if (prof_on && prof) {
         static int calls = 0;
         if (++calls == 40) {   // a steady-state job: print the previous launch's stamps (cycles between phase boundaries)
