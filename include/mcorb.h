@@ -155,6 +155,32 @@ int mcorb_rig_undistortion_active(mcorb_rig *r, int cam);
  * pointer still wins.  With nothing set they read the raw keypoints, as without this feature. */
 int mcorb_rig_get_features_undist(mcorb_rig *r, int slot, int m, mcorb_keypoint *kps, int cap, int *n_out);
 
+/* The RECTIFY branch of MultiCameraFrame::setData (MultiCameraFrame.cpp:123-136) on the device, at the hand-off: for a camera with
+ * image undistortion set, every upload form (u8, staged, f32) lands the plane in a raw buffer and k_remap_u8 writes
+ * cv::undistort(img, undistImg, K, dist) into level 0 of the pyramid behind the copies, so a job -- and a job re-run on the
+ * resident images -- reads the undistorted image and mcorb_rig_get_level(.., 0, ..) returns it.  The fixed-point map of
+ * cv::undistort (OpenCV 4.x: stripes of min(max(1, 4096 / w), h) rows, initUndistortRectifyMap to CV_16SC2 per stripe, all in
+ * fp64 without contraction) is built once per camera on the host by this call; the per-frame work is the resampling,
+ * remap(INTER_LINEAR, BORDER_CONSTANT 0).  K (3x3 row-major) and dist are camconfig's CV_64F values, used as they are.
+ * ncoeffs: 4, 5, 8 or 12; dist == NULL or ncoeffs == 0 clears the camera (cameras not set are copied through).  There is no zero
+ * test: the reference calls cv::undistort for all-zero coefficients too.  MCORB_E_ARG: bad camera, count (14, the tilt model,
+ * included), non-finite values or a zero fx, fy.  MCORB_E_STATE while any slot has a job submitted and not yet waited for.
+ * RECTIFY is rig-wide in the reference and excludes UndistortKeyPoints (image_kps_undist is then the raw keypoint set, :241-242):
+ * this call returns MCORB_E_STATE while any camera has keypoint undistortion set, and mcorb_rig_set_undistortion returns it while
+ * any camera has image undistortion set.  A rig that never sets it allocates nothing and uploads exactly as before.
+ * mcorb_rig_image_undistortion_active: 1 if the camera is set, else 0. */
+int mcorb_rig_set_image_undistortion(mcorb_rig *r, int cam, const double *K, const double *dist, int ncoeffs);
+int mcorb_rig_image_undistortion_active(mcorb_rig *r, int cam);
+/* test hooks: the camera's maps as built on the host (map1_xy: width * height (x, y) pairs, map2: width * height; cap_pixels >=
+ * width * height; MCORB_E_STATE for a camera not set), and the raw plane of image m as uploaded (MCORB_E_STATE on a rig that never
+ * set image undistortion; meaningful for images uploaded while it was set) */
+int mcorb_rig_get_undistort_map(mcorb_rig *r, int cam, int16_t *map1_xy, uint16_t *map2, int cap_pixels);
+int mcorb_rig_get_raw_image(mcorb_rig *r, int slot, int m, uint8_t *dst, int dst_stride);
+/* the two halves alone, on the host, no device: the map of a w x h image, and remap(INTER_LINEAR, BORDER_CONSTANT 0) under a map */
+int mcorb_host_undistort_map(const double *K, const double *dist, int ncoeffs, int w, int h, int16_t *map1_xy, uint16_t *map2);
+int mcorb_host_remap_u8(const uint8_t *src, int src_stride, int w, int h, const int16_t *map1_xy, const uint16_t *map2,
+                        uint8_t *dst, int dst_stride);
+
 /* computeIntraMatches(matches, false) (MultiCameraFrame.cpp:1100-1288) for the
  * first `nframes` rig frames of a slot: BruteForceMatch(i, j, dist_thresh,
  * ratio) for all i<j on the GPU (all-pairs Hamming k-NN, k = 2), then the

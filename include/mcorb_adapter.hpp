@@ -384,6 +384,32 @@ public:
         }
     }
 #endif
+    // camconfig_.RECTIFY (MultiCameraFrame.cpp:123-136): K_mats_[cam] / dist_coeffs_[cam] as setDistortion takes them (NULL or 0
+    // clears).  Call once at init, in place of the host's cv::undistort: from then on setData / setDataF32 leave
+    // cv::undistort(img, K, dist) of the camera's image in the rig (k_remap_u8, at the hand-off), and extractFeaturesParallel()
+    // leaves image_kps_undist empty -- the consumers then read image_kps, the copy the reference makes (:241-242).  Excludes
+    // setDistortion, as RECTIFY excludes UndistortKeyPoints.
+    void setRectify(int cam, const double *K, const double *dist, int n)
+    {
+        check(mcorb_rig_set_image_undistortion(rig_, cam, K, dist, n), "mcorb_rig_set_image_undistortion");
+    }
+#ifdef MCORB_WITH_OPENCV
+    void setRectify(const std::vector<cv::Mat> &K_mats, const std::vector<cv::Mat> &dist_coeffs)
+    {
+        if ((int)K_mats.size() != num_cams_ || (int)dist_coeffs.size() != num_cams_) throw std::runtime_error("ERROR:: one K and one dist per camera");
+        for (int c = 0; c < num_cams_; c++) {
+            const cv::Mat &K = K_mats[c], &D = dist_coeffs[c];
+            if (K.type() != CV_64F || K.rows != 3 || K.cols != 3) throw std::runtime_error("ERROR:: K_mats_ must be 3x3 CV_64F");
+            const int n = D.rows * D.cols;
+            if (n && (D.type() != CV_64F || (D.rows != 1 && D.cols != 1))) throw std::runtime_error("ERROR:: dist_coeffs_ must be a CV_64F vector");
+            double k[9], d[12] = {0};
+            for (int r = 0; r < 3; r++)
+                for (int j = 0; j < 3; j++) k[r * 3 + j] = K.at<double>(r, j);
+            for (int i = 0; i < n && i < 12; i++) d[i] = D.rows == 1 ? D.at<double>(0, i) : D.at<double>(i, 0);
+            setRectify(c, k, n ? d : nullptr, n);
+        }
+    }
+#endif
     // BruteForceMatch (MultiCameraFrame.cpp:1024-1086), cam1 < cam2 as at every reference call site
     void BruteForceMatch(int img1_ind, int img2_ind, float dist_thresh, float neigh_ratio,
                          std::vector<unsigned int> &indices_1, std::vector<unsigned int> &indices_2,

@@ -151,6 +151,37 @@ class Rig:
         d = np.ascontiguousarray(dist, np.float64).ravel()
         _lib.check(self.L.mcorb_rig_set_undistortion(self.h_rig, cam, K.ctypes.data, d.ctypes.data, d.size))
 
+    # -- the RECTIFY branch of setData (MultiCameraFrame.cpp:123-136): cv::undistort of every image, on the device at the hand-off --
+    def set_image_undistortion(self, cam, K=None, dist=None):
+        """camconfig_.K_mats_[cam] (3x3) and dist_coeffs_[cam] (4, 5, 8 or 12 values) as CV_64F; dist None or empty clears.  From
+        then on every upload() / upload_staged() leaves cv::undistort(img, K, dist) of this camera's images in level 0.  Excludes
+        set_undistortion (a rectified rig copies its keypoints)."""
+        if dist is None or len(np.ravel(dist)) == 0:
+            _lib.check(self.L.mcorb_rig_set_image_undistortion(self.h_rig, cam, None, None, 0))
+            return
+        K = np.ascontiguousarray(K, np.float64).reshape(9)
+        d = np.ascontiguousarray(dist, np.float64).ravel()
+        _lib.check(self.L.mcorb_rig_set_image_undistortion(self.h_rig, cam, K.ctypes.data, d.ctypes.data, d.size))
+
+    def image_undistortion_active(self, cam):
+        v = self.L.mcorb_rig_image_undistortion_active(self.h_rig, cam)
+        if v < 0:
+            _lib.check(v)
+        return bool(v)
+
+    def undistort_map(self, cam):
+        """(map1 (H, W, 2) int16, map2 (H, W) uint16) of a camera with image undistortion set, as built on the host (test hook)"""
+        m1 = np.zeros((self.h, self.w, 2), np.int16)
+        m2 = np.zeros((self.h, self.w), np.uint16)
+        _lib.check(self.L.mcorb_rig_get_undistort_map(self.h_rig, cam, m1.ctypes.data, m2.ctypes.data, self.w * self.h))
+        return m1, m2
+
+    def raw_image(self, m, slot=0):
+        """the plane of image m as uploaded, before cv::undistort (test hook)"""
+        out = np.zeros((self.h, self.w), np.uint8)
+        _lib.check(self.L.mcorb_rig_get_raw_image(self.h_rig, slot, m, out.ctypes.data, self.w))
+        return out
+
     # -- transform() and computeIntraMatches(matches, words_) inside every extraction job -------------------------------------
     def set_vocabulary(self, voc, levelsup=4, match=True, max_neighbor_ratio=0.85):
         """Bind an ORBVocabulary (None unbinds): every later extraction job also runs transform(desc, BowVector, FeatureVector,
@@ -889,6 +920,15 @@ class MultiCameraFrame:
         for c in range(self.num_cams_):
             self.rig.set_undistortion(c, K_mats[c], dist_coeffs[c])
         self._distorted = any(d is not None and len(np.ravel(d)) > 0 for d in dist_coeffs)
+
+    def setRectify(self, K_mats, dist_coeffs):
+        """camconfig_.RECTIFY (MultiCameraFrame.cpp:123-136): K_mats_ / dist_coeffs_ as setDistortion takes them.  From then on
+        setData() leaves cv::undistort(img, K, dist) of every camera image in the rig, and extractFeaturesParallel() copies the
+        keypoints into image_kps_undist (:241-242).  A camera given None or no coefficients is cleared.  Excludes setDistortion."""
+        if len(K_mats) != self.num_cams_ or len(dist_coeffs) != self.num_cams_:
+            raise ValueError("one K and one coefficient set per camera")
+        for c in range(self.num_cams_):
+            self.rig.set_image_undistortion(c, K_mats[c], dist_coeffs[c])
 
     def setVocabulary(self, voc, levelsup=4):
         """orb_vocabulary (MultiCameraFrame.cpp:252-261): from now on extractFeaturesParallel() fills BoW_vecs[cam] as

@@ -69,6 +69,12 @@ SIGNATURES = {
     "mcorb_rig_set_undistortion": (_i, [_vp, _i, _vp, _vp, _i]),
     "mcorb_rig_undistortion_active": (_i, [_vp, _i]),
     "mcorb_rig_get_features_undist": (_i, [_vp, _i, _i, _vp, _i, _ip]),
+    "mcorb_rig_set_image_undistortion": (_i, [_vp, _i, _vp, _vp, _i]),
+    "mcorb_rig_image_undistortion_active": (_i, [_vp, _i]),
+    "mcorb_rig_get_undistort_map": (_i, [_vp, _i, _vp, _vp, _i]),
+    "mcorb_rig_get_raw_image": (_i, [_vp, _i, _i, _vp, _i]),
+    "mcorb_host_undistort_map": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
+    "mcorb_host_remap_u8": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _i]),
     "mcorb_rig_match": (_i, [_vp, _i, _i, _f, _f]),
     "mcorb_rig_match_submit": (_i, [_vp, _i, _i, _f, _f]),
     "mcorb_rig_match_wait": (_i, [_vp, _i]),

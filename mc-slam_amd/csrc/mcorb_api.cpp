@@ -2,6 +2,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <cmath>
 #include <chrono>
 #include <new>
 
@@ -282,6 +283,64 @@ int mcorb_rig_get_features_undist(mcorb_rig *r, int slot, int m, mcorb_keypoint 
     if (n_out) *n_out = n;
     if (n > cap) { set_error("keypoint buffer too small"); return MCORB_E_CAP; }
     if (kps && n) memcpy(kps, p[0], (size_t)n * sizeof(mcorb_keypoint));
+    return MCORB_OK;
+}
+
+int mcorb_rig_set_image_undistortion(mcorb_rig *r, int cam, const double *K, const double *dist, int ncoeffs)
+{
+    if (!r) { set_error("bad rig"); return MCORB_E_ARG; }
+    return r->rig.set_image_undistortion(cam, K, dist, ncoeffs);
+}
+
+int mcorb_rig_image_undistortion_active(mcorb_rig *r, int cam)
+{
+    if (!r || cam < 0 || cam >= r->rig.ncams) { set_error("bad rig/camera"); return MCORB_E_ARG; }
+    return r->rig.imgud_set[cam] ? 1 : 0;
+}
+
+int mcorb_rig_get_undistort_map(mcorb_rig *r, int cam, int16_t *map1_xy, uint16_t *map2, int cap_pixels)
+{
+    if (!r || cam < 0 || cam >= r->rig.ncams || !map1_xy || !map2) { set_error("get_undistort_map: bad argument"); return MCORB_E_ARG; }
+    if (!r->rig.imgud_set[cam]) { set_error("get_undistort_map: camera has no image undistortion set"); return MCORB_E_STATE; }
+    const size_t n = (size_t)r->rig.W * r->rig.H;
+    if (cap_pixels < 0 || (size_t)cap_pixels < n) { set_error("get_undistort_map: buffer too small"); return MCORB_E_CAP; }
+    memcpy(map1_xy, r->rig.imgud_map1[cam].data(), n * 4);
+    memcpy(map2, r->rig.imgud_map2[cam].data(), n * 2);
+    return MCORB_OK;
+}
+
+int mcorb_rig_get_raw_image(mcorb_rig *r, int slot, int m, uint8_t *dst, int dst_stride)
+{
+    if (!r || slot < 0 || slot >= (int)r->rig.slots.size() || m < 0 || m >= r->rig.max_images || !dst || dst_stride < r->rig.W) {
+        set_error("get_raw_image: bad argument");
+        return MCORB_E_ARG;
+    }
+    Slot *s = r->rig.slots[slot].get();
+    if (!s->d_raw) { set_error("get_raw_image: the rig never set image undistortion"); return MCORB_E_STATE; }
+    const int W = r->rig.W, H = r->rig.H;
+    HIPCHK(hipSetDevice(r->rig.device));
+    HIPCHK(hipStreamSynchronize(s->st));
+    HIPCHK(hipMemcpy2D(dst, dst_stride, s->d_raw + (size_t)m * W * H, W, W, H, hipMemcpyDeviceToHost));
+    return MCORB_OK;
+}
+
+int mcorb_host_undistort_map(const double *K, const double *dist, int ncoeffs, int w, int h, int16_t *map1_xy, uint16_t *map2)
+{
+    if (!K || !dist || !map1_xy || !map2 || w < 1 || h < 1 || w > 4096 || h > 4096) { set_error("host_undistort_map: bad argument"); return MCORB_E_ARG; }
+    UndistImageCam c;
+    if (undist_image_prepare(K, dist, ncoeffs, c) != 0) { set_error("host_undistort_map: 4, 5, 8 or 12 coefficients (the tilt model is not supported)"); return MCORB_E_ARG; }
+    for (double v : c.K) if (!std::isfinite(v)) { set_error("host_undistort_map: non-finite camera matrix"); return MCORB_E_ARG; }
+    for (double v : c.k) if (!std::isfinite(v)) { set_error("host_undistort_map: non-finite coefficient"); return MCORB_E_ARG; }
+    if (c.K[0] == 0. || c.K[4] == 0.) { set_error("host_undistort_map: fx / fy must be non-zero"); return MCORB_E_ARG; }
+    undist_image_map(c, w, h, map1_xy, map2);
+    return MCORB_OK;
+}
+
+int mcorb_host_remap_u8(const uint8_t *src, int src_stride, int w, int h, const int16_t *map1_xy, const uint16_t *map2,
+                        uint8_t *dst, int dst_stride)
+{
+    if (!src || !map1_xy || !map2 || !dst || w < 1 || h < 1 || src_stride < w || dst_stride < w) { set_error("host_remap_u8: bad argument"); return MCORB_E_ARG; }
+    remap_u8(src, src_stride, w, h, map1_xy, map2, dst, dst_stride);
     return MCORB_OK;
 }
 

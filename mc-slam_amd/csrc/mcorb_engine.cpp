@@ -396,6 +396,12 @@ int Rig::init(const mcorb_params &p, int ncams_, int W_, int H_, int max_frames_
     max_images = ncams * max_frames;
     undist_cams.assign(ncams, UndistCam{});
     undist_set.assign(ncams, 0);
+    imgud_cams.assign(ncams, UndistImageCam{});
+    imgud_set.assign(ncams, 0);
+    imgud_map1.assign(ncams, {});
+    imgud_map2.assign(ncams, {});
+    d_imgud_map1.resize(ncams);
+    d_imgud_map2.resize(ncams);
     npp = ncams * (ncams - 1) / 2;
     device = p.device_id;
     HIPCHK(hipSetDevice(device));
@@ -631,6 +637,7 @@ int Rig::upload_u8(int slot, const uint8_t *const *images, int nimg, int stride)
         // one rig frame at a time: the staging copy and the DMA overlap -- the planes are copied a quarter at a time, image by image,
         // and whoever finishes an image's last quarter puts its DMA on the stream while the others go on with the next image
         constexpr int Q = 4;
+        const bool raw = imgud_on;   // image undistortion set: into the raw planes, k_remap_u8 behind the last copy
         std::atomic<int> left[kSmallBatch];
         for (int m = 0; m < nimg; m++) left[m].store(Q);
         std::atomic<int> err{(int)hipSuccess};
@@ -643,12 +650,13 @@ int Rig::upload_u8(int slot, const uint8_t *const *images, int nimg, int stride)
             if (left[m].fetch_sub(1, std::memory_order_acq_rel) != 1) return;
             hipError_t e = hipSetDevice(device);   // (pool threads make no other HIP call)
             if (e == hipSuccess)
-                e = hipMemcpy2DAsync(s.d_pyr + (size_t)m * geom.imgBytes + geom.lv[0].off, geom.lv[0].pitch, dst, W, W, H, hipMemcpyHostToDevice, s.st);
+                e = raw ? hipMemcpyAsync(s.d_raw + (size_t)m * plane, dst, plane, hipMemcpyHostToDevice, s.st)
+                        : hipMemcpy2DAsync(s.d_pyr + (size_t)m * geom.imgBytes + geom.lv[0].off, geom.lv[0].pitch, dst, W, W, H, hipMemcpyHostToDevice, s.st);
             if (e != hipSuccess) err.store((int)e);
         };
         pool->parallel_for(nimg * Q, quarter, pool_threads + s.index);
         HIPCHK((hipError_t)err.load());
-        return MCORB_OK;
+        return raw ? enqueue_remap(s, nimg) : MCORB_OK;
     }
     if (nimg > 1) pool->parallel_for(nimg, copy_one, pool_threads + s.index);
     else copy_one(0, 0);
@@ -663,6 +671,10 @@ int Rig::upload_staged(int slot, int nimg)
     if (slot_busy(s)) return MCORB_E_STATE;
     HIPCHK(hipSetDevice(device));
     const size_t plane = (size_t)W * H;
+    if (imgud_on) {   // the raw planes are the staging buffer's layout: one copy, then cv::undistort into level 0
+        HIPCHK(hipMemcpyAsync(s.d_raw, s.h_stage, plane * nimg, hipMemcpyHostToDevice, s.st));
+        return enqueue_remap(s, nimg);
+    }
     if (geom.lv[0].pitch == W) {
         // level-0 rows are contiguous: the whole batch is one strided copy (one row = one image)
         HIPCHK(hipMemcpy2DAsync(s.d_pyr + geom.lv[0].off, geom.imgBytes, s.h_stage, plane, plane, nimg, hipMemcpyHostToDevice, s.st));
@@ -692,7 +704,13 @@ int Rig::upload_f32(int slot, const float *const *images, int nimg, int stride_b
         HIPCHK(hipMemcpy2DAsync(s.d_f32 + (size_t)m * img_f, row_f * 4, images[m], stride_bytes, row_f * 4, H,
                                 hipMemcpyHostToDevice, s.st));
     }
-    launch_stage_f32(s.st, s.d_f32, W, H, (int)row_f, channels, img_f, s.d_pyr, geom, nimg);
+    if (imgud_on) {
+        launch_stage_f32_raw(s.st, s.d_f32, W, H, (int)row_f, channels, img_f, s.d_raw, nimg);
+        HIPCHK(hipGetLastError());
+        TRY(enqueue_remap(s, nimg));
+    } else {
+        launch_stage_f32(s.st, s.d_f32, W, H, (int)row_f, channels, img_f, s.d_pyr, geom, nimg);
+    }
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(s.st));   // caller memory may be pageable: copies above were staged by the runtime
     return MCORB_OK;
@@ -1163,6 +1181,10 @@ int Rig::set_undistortion(int cam, const double *K, const double *dist, int ncoe
     }
     std::vector<std::unique_lock<std::mutex>> locks;
     TRY(lock_idle_slots("set_undistortion", locks));
+    if (imgud_on) {   // RECTIFY: image_kps_undist is the raw keypoint set (MultiCameraFrame.cpp:241-242)
+        set_error("set_undistortion: image undistortion is set (mcorb_rig_set_image_undistortion); a rig is rectified or it is not");
+        return MCORB_E_STATE;
+    }
     HIPCHK(hipSetDevice(device));
     if (!clear && !slots[0]->ubuf.bound) {   // first set call: the device table and every slot's buffers and events
         DevBuf<UndistCam> cams;
@@ -1181,6 +1203,88 @@ int Rig::set_undistortion(int cam, const double *K, const double *dist, int ncoe
     undist_on = std::any_of(undist_set.begin(), undist_set.end(), [](uint8_t v) { return v != 0; });
     if (d_undist_cams) HIPCHK(hipMemcpy(d_undist_cams, undist_cams.data(), (size_t)ncams * sizeof(UndistCam), hipMemcpyHostToDevice));
     undist_gen++;
+    return MCORB_OK;
+}
+
+// ---------------------------------------------------------------------------
+// cv::undistort at the hand-off (the RECTIFY branch of setData, MultiCameraFrame.cpp:123-136).  It belongs to the upload, as it
+// belongs to setData: a job, its captured graph and a re-run on resident inputs read level 0 and never know.  Nothing of this
+// runs or is allocated while no camera has it set (imgud_on): an upload is then exactly the upload without the feature.
+// ---------------------------------------------------------------------------
+int Rig::enqueue_remap(Slot &s, int nimg)
+{
+    launch_remap_u8(s.st, s.d_raw, s.d_pyr, geom, d_remap_cams, ncams, nimg);
+    HIPCHK(hipGetLastError());
+    return MCORB_OK;
+}
+
+int Rig::set_image_undistortion(int cam, const double *K, const double *dist, int ncoeffs)
+{
+    if (cam < 0 || cam >= ncams) { set_error("set_image_undistortion: camera out of range"); return MCORB_E_ARG; }
+    const bool clear = !dist || ncoeffs == 0;
+    UndistImageCam c = {};
+    if (!clear) {
+        if (!K) { set_error("set_image_undistortion: no camera matrix"); return MCORB_E_ARG; }
+        if (undist_image_prepare(K, dist, ncoeffs, c) != 0) { set_error("set_image_undistortion: 4, 5, 8 or 12 coefficients (the tilt model is not supported)"); return MCORB_E_ARG; }
+        for (double v : c.K) if (!std::isfinite(v)) { set_error("set_image_undistortion: non-finite camera matrix"); return MCORB_E_ARG; }
+        for (double v : c.k) if (!std::isfinite(v)) { set_error("set_image_undistortion: non-finite coefficient"); return MCORB_E_ARG; }
+        if (c.K[0] == 0. || c.K[4] == 0.) { set_error("set_image_undistortion: fx / fy must be non-zero"); return MCORB_E_ARG; }
+    }
+    std::vector<std::unique_lock<std::mutex>> locks;
+    TRY(lock_idle_slots("set_image_undistortion", locks));
+    if (undist_on) {   // the reference's RECTIFY is rig-wide and excludes UndistortKeyPoints (MultiCameraFrame.cpp:241-242)
+        set_error("set_image_undistortion: keypoint undistortion is set (mcorb_rig_set_undistortion); a rig is rectified or it is not");
+        return MCORB_E_STATE;
+    }
+    HIPCHK(hipSetDevice(device));
+    for (auto &sp : slots) HIPCHK(hipStreamSynchronize(sp->st));   // an earlier upload's k_remap_u8 reads the tables changed below
+    const size_t plane = (size_t)W * H, mp = remap_map_pitch(W);
+    if (!clear) {
+        if (!d_remap_cams) {   // first set call: the camera table and every slot's raw planes
+            DevBuf<RemapCam> cams;
+            std::vector<DevBuf<uint8_t>> fresh(slots.size());
+            TRY(cams.alloc((size_t)ncams));
+            for (auto &b : fresh) {
+                TRY(b.alloc((size_t)max_images * plane));
+                HIPCHK(hipMemset(b, 0, (size_t)max_images * plane));
+            }
+            d_remap_cams = std::move(cams);
+            for (size_t i = 0; i < slots.size(); i++) slots[i]->d_raw = std::move(fresh[i]);
+        }
+        // the camera's maps: built here, once (the row loop is a serial sum), padded for the device
+        std::vector<int16_t> m1(plane * 2);
+        std::vector<uint16_t> m2(plane);
+        undist_image_map(c, W, H, m1.data(), m2.data());
+        std::vector<int16_t> p1((size_t)H * mp * 2, 0);
+        std::vector<uint16_t> p2((size_t)H * mp, 0);
+        for (int y = 0; y < H; y++) {
+            memcpy(p1.data() + (size_t)y * mp * 2, m1.data() + (size_t)y * W * 2, (size_t)W * 4);
+            memcpy(p2.data() + (size_t)y * mp, m2.data() + (size_t)y * W, (size_t)W * 2);
+        }
+        DevBuf<int16_t> d1;
+        DevBuf<uint16_t> d2;
+        TRY(d1.alloc(p1.size()));
+        TRY(d2.alloc(p2.size()));
+        HIPCHK(hipMemcpy(d1, p1.data(), p1.size() * 2, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(d2, p2.data(), p2.size() * 2, hipMemcpyHostToDevice));
+        d_imgud_map1[cam] = std::move(d1);   // all there: commit
+        d_imgud_map2[cam] = std::move(d2);
+        imgud_map1[cam] = std::move(m1);
+        imgud_map2[cam] = std::move(m2);
+    } else {
+        d_imgud_map1[cam].reset();
+        d_imgud_map2[cam].reset();
+        imgud_map1[cam] = {};
+        imgud_map2[cam] = {};
+    }
+    imgud_cams[cam] = c;
+    imgud_set[cam] = clear ? 0 : 1;
+    imgud_on = std::any_of(imgud_set.begin(), imgud_set.end(), [](uint8_t v) { return v != 0; });
+    if (d_remap_cams) {
+        std::vector<RemapCam> t((size_t)ncams);
+        for (int i = 0; i < ncams; i++) t[i] = RemapCam{d_imgud_map1[i].get(), d_imgud_map2[i].get(), imgud_set[i] ? 1 : 0, 0};
+        HIPCHK(hipMemcpy(d_remap_cams, t.data(), t.size() * sizeof(RemapCam), hipMemcpyHostToDevice));
+    }
     return MCORB_OK;
 }
 

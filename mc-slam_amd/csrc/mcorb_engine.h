@@ -189,6 +189,7 @@ struct Slot {
     DevBuf<uint2> d_part;
     DevBuf<uint8_t> d_exp;           // descriptors of the sets being matched, expanded to +-64 int8 in MFMA fragment order (k_expand)
     DevBuf<int> d_lcounts;           // their clamped counts, local set order
+    DevBuf<uint8_t> d_raw;           // raw planes of a rig with image undistortion set (image m at m * W * H); empty otherwise
     // host, device-mapped (kernels write/read these directly over PCIe)
     HostBuf<uint32_t> h_cand;
     HostBuf<int> h_overflow;
@@ -371,6 +372,22 @@ public:
     // rig's own set, < 0 = error (images extracted before the last set call)
     int undist_default(Slot &s, int m0, int n, std::vector<const mcorb_keypoint *> &out);
     int max_pairs() const { return std::max(1, npp * max_frames); }
+
+    // The RECTIFY branch of setData (MultiCameraFrame.cpp:123-136): cv::undistort of every camera image at the hand-off.  Per
+    // camera the calibration and the maps built from it on the host (mcorb_undistort_image.h) with their device copies, allocated
+    // when the camera is set; d_remap_cams: what k_remap_u8 reads (mode 0 for cameras not set).  While imgud_on, every upload
+    // form lands its planes in the slot's d_raw and enqueues k_remap_u8 behind the copies; a job never sees the difference.
+    // Nothing of this is allocated or runs on a rig that never sets it.
+    std::vector<UndistImageCam> imgud_cams;
+    std::vector<uint8_t> imgud_set;
+    std::vector<std::vector<int16_t>> imgud_map1;    // [cam][H * W * 2], unpadded rows (mcorb_rig_get_undistort_map)
+    std::vector<std::vector<uint16_t>> imgud_map2;   // [cam][H * W]
+    std::vector<DevBuf<int16_t>> d_imgud_map1;       // [cam][H * remap_map_pitch(W) * 2]
+    std::vector<DevBuf<uint16_t>> d_imgud_map2;
+    DevBuf<RemapCam> d_remap_cams;
+    bool imgud_on = false;
+    int set_image_undistortion(int cam, const double *K, const double *dist, int ncoeffs);
+    int enqueue_remap(Slot &s, int nimg);   // k_remap_u8 on the slot's stream, behind the upload's copies
 
     // the vocabulary bound to the rig (mcorb_rig_set_vocabulary): flags = 0 unbound; otherwise the vocabulary's device tables,
     // levelsup and weighting / scoring, which every extraction job's BoW stages read; bow_gen counts the set calls

@@ -5,6 +5,7 @@
 #include "mcorb_common.h"
 #include "mcorb_signal.h"
 #include "mcorb_undistort.h"
+#include "mcorb_undistort_image.h"
 
 namespace mcorb {
 
@@ -45,6 +46,15 @@ __host__ __device__ inline bool knn_accept(const KnnRow &r) { return (r.d >> 18)
 hipError_t upload_umax(const int umax[16]);
 void launch_stage_f32(hipStream_t st, const float *src, int w, int h, int pitch_f, int channels, size_t img_stride_f,
                       uint8_t *pyr, const Geom &g, int nimg);
+// cv::undistort at the hand-off (mcorb_rig_set_image_undistortion).  A camera's maps on the device: rows padded with zero entries
+// to remap_map_pitch(w) (k_remap_u8 loads four entries at a time), map1 as (x, y) pairs of shorts; mode 0: not set, copied through
+struct RemapCam { const int16_t *map1; const uint16_t *map2; int32_t mode, pad; };
+__host__ __device__ inline int remap_map_pitch(int w) { return (w + 3) & ~3; }
+// upload_f32's conversion into the raw planes (image m at m * w * h, row stride w) instead of level 0
+void launch_stage_f32_raw(hipStream_t st, const float *src, int w, int h, int pitch_f, int channels, size_t img_stride_f,
+                          uint8_t *raw, int nimg);
+// level 0 of images [0, nimg) from their raw planes: image m is camera m % ncams
+void launch_remap_u8(hipStream_t st, const uint8_t *raw, uint8_t *pyr, const Geom &g, const RemapCam *cams, int ncams, int nimg);
 // win[2*l], win[2*l+1]: LDS source-window pitch (bytes, multiple of 4) and rows of level l's resize workgroups
 void launch_pyramid(hipStream_t st, uint8_t *pyr, const Geom &g, const ResizeTap *tabs, const int *win, int nimg);
 // k_fast_cells' per-cell records for this geometry (built once per rig, uploaded by the caller): ROI origin, size,

@@ -13,6 +13,7 @@
 #include "mcorb_common.h"
 #include "mcorb_kernels.h"
 #include "mcorb_undistort.h"
+#include "mcorb_undistort_image.h"
 #include <stdlib.h>
 #include <string.h>
 #include <vector>
@@ -56,6 +57,16 @@ __device__ __forceinline__ int sat_u8_rne(float v)
     return r < 0 ? 0 : (r > 255 ? 255 : r);
 }
 
+// one output pixel of row S (x < w)
+__device__ __forceinline__ int stage_f32_px(const float *__restrict__ S, int x, int channels)
+{
+    if (channels == 1) return sat_u8_rne(__fmul_rn(S[x], 255.f));
+    int b = sat_u8_rne(__fmul_rn(S[3 * x + 0], 255.f));
+    int gg = sat_u8_rne(__fmul_rn(S[3 * x + 1], 255.f));
+    int r = sat_u8_rne(__fmul_rn(S[3 * x + 2], 255.f));
+    return (b * 1868 + gg * 9617 + r * 4899 + 8192) >> 14;
+}
+
 __global__ __launch_bounds__(256) void k_stage_f32(const float *__restrict__ src, int w, int h, int src_pitch_f,
                                                    int channels, size_t src_img_stride_f, uint8_t *__restrict__ pyr,
                                                    Geom g)
@@ -65,16 +76,71 @@ __global__ __launch_bounds__(256) void k_stage_f32(const float *__restrict__ src
     const int y = blockIdx.y;
     if (x >= w) return;
     const float *S = src + (size_t)img * src_img_stride_f + (size_t)y * src_pitch_f;
-    int v;
-    if (channels == 1) {
-        v = sat_u8_rne(__fmul_rn(S[x], 255.f));
-    } else {
-        int b = sat_u8_rne(__fmul_rn(S[3 * x + 0], 255.f));
-        int gg = sat_u8_rne(__fmul_rn(S[3 * x + 1], 255.f));
-        int r = sat_u8_rne(__fmul_rn(S[3 * x + 2], 255.f));
-        v = (b * 1868 + gg * 9617 + r * 4899 + 8192) >> 14;
+    pyr[(size_t)img * g.imgBytes + g.lv[0].off + (size_t)y * g.lv[0].pitch + x] = (uint8_t)stage_f32_px(S, x, channels);
+}
+
+// the same into the raw planes of a rig with image undistortion set (image m at m * w * h, row stride w): k_remap_u8 follows
+__global__ __launch_bounds__(256) void k_stage_f32_raw(const float *__restrict__ src, int w, int h, int src_pitch_f,
+                                                       int channels, size_t src_img_stride_f, uint8_t *__restrict__ raw)
+{
+    const int img = blockIdx.z;
+    const int x = blockIdx.x * 256 + threadIdx.x;
+    const int y = blockIdx.y;
+    if (x >= w) return;
+    const float *S = src + (size_t)img * src_img_stride_f + (size_t)y * src_pitch_f;
+    raw[((size_t)img * h + y) * w + x] = (uint8_t)stage_f32_px(S, x, channels);
+}
+
+// ---------------------------------------------------------------------------
+// Frame hand-off of a rectified rig (RECTIFY, MultiCameraFrame.cpp:123-136): cv::undistort of every raw plane into level 0.
+// The map of a camera (mcorb_undistort_image.h, built on the host when the calibration is set) is the same for every frame, and
+// it is 6 of the 8 bytes an output pixel moves.  So a workgroup owns 1024 consecutive output pixels of ONE camera: each lane
+// loads the map entries of its 4 pixels once (16 + 8 bytes), turns them into tap offsets and weights in registers, and then
+// walks the batch's frames of that camera -- per frame 16 byte gathers (two short row segments per pixel, shared with the
+// neighbouring lanes: they hit in TCP / L2) and one dword store.  Cameras that are not set (mode 0) are copied through.
+// Every tap offset lies inside the plane by construction (remap_taps: a tap outside gets offset 0, weight 0).
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_remap_u8(const uint8_t *__restrict__ raw, uint8_t *__restrict__ pyr,
+                                                  const RemapCam *__restrict__ cams, int ncams, int nimg, int w, int h, int wq,
+                                                  uint32_t imgBytes, uint32_t off0, int pitch0)
+{
+    const int cam = blockIdx.y;
+    const int q = blockIdx.x * 256 + threadIdx.x;   // quad of 4 output pixels; wq quads per row
+    if (q >= wq * h) return;
+    const int y = q / wq, x = (q - y * wq) * 4;
+    const int nv = min(4, w - x);
+    const size_t plane = (size_t)w * h;
+    const RemapCam C = cams[cam];
+    uint8_t *dst = pyr + off0 + (size_t)y * pitch0 + x;
+    if (C.mode == 0) {
+        const size_t so = (size_t)y * w + x;
+        for (int m = cam; m < nimg; m += ncams) {
+            const uint8_t *s = raw + (size_t)m * plane + so;
+            uint8_t *d = dst + (size_t)m * imgBytes;
+            if (nv == 4 && (w & 3) == 0) *reinterpret_cast<uint32_t *>(d) = *reinterpret_cast<const uint32_t *>(s);
+            else for (int i = 0; i < nv; i++) d[i] = s[i];
+        }
+        return;
     }
-    pyr[(size_t)img * g.imgBytes + g.lv[0].off + (size_t)y * g.lv[0].pitch + x] = (uint8_t)v;
+    // the device maps are padded to wq * 4 entries per row (zeros): both loads are aligned whatever w is
+    const size_t mo = ((size_t)y * wq) * 4 + x;
+    const uint4 a = *reinterpret_cast<const uint4 *>(C.map1 + mo * 2);
+    const uint2 b = *reinterpret_cast<const uint2 *>(C.map2 + mo);
+    const uint32_t a4[4] = {a.x, a.y, a.z, a.w};
+    const uint32_t b4[4] = {b.x & 0xffffu, b.x >> 16, b.y & 0xffffu, b.y >> 16};
+    RemapTaps t[4];
+#pragma unroll
+    for (int i = 0; i < 4; i++) remap_taps((int)(int16_t)(a4[i] & 0xffffu), (int)(int16_t)(a4[i] >> 16), b4[i], w, h, w, t[i]);
+#pragma unroll 2
+    for (int m = cam; m < nimg; m += ncams) {
+        const uint8_t *s = raw + (size_t)m * plane;
+        uint32_t v = 0;
+#pragma unroll
+        for (int i = 0; i < 4; i++) v |= (uint32_t)remap_pixel(s, t[i]) << (8 * i);
+        uint8_t *d = dst + (size_t)m * imgBytes;
+        if (nv == 4) *reinterpret_cast<uint32_t *>(d) = v;
+        else for (int i = 0; i < nv; i++) d[i] = (uint8_t)(v >> (8 * i));
+    }
 }
 
 // ---------------------------------------------------------------------------
@@ -1996,6 +2062,20 @@ void launch_stage_f32(hipStream_t st, const float *src, int w, int h, int pitch_
 {
     dim3 grid((w + 255) / 256, h, nimg);
     hipLaunchKernelGGL(k_stage_f32, grid, dim3(256), 0, st, src, w, h, pitch_f, channels, img_stride_f, pyr, g);
+}
+
+void launch_stage_f32_raw(hipStream_t st, const float *src, int w, int h, int pitch_f, int channels, size_t img_stride_f,
+                          uint8_t *raw, int nimg)
+{
+    dim3 grid((w + 255) / 256, h, nimg);
+    hipLaunchKernelGGL(k_stage_f32_raw, grid, dim3(256), 0, st, src, w, h, pitch_f, channels, img_stride_f, raw);
+}
+
+void launch_remap_u8(hipStream_t st, const uint8_t *raw, uint8_t *pyr, const Geom &g, const RemapCam *cams, int ncams, int nimg)
+{
+    const int w = g.lv[0].w, h = g.lv[0].h, wq = remap_map_pitch(w) / 4;
+    dim3 grid((wq * h + 255) / 256, ncams < nimg ? ncams : nimg);
+    hipLaunchKernelGGL(k_remap_u8, grid, dim3(256), 0, st, raw, pyr, cams, ncams, nimg, w, h, wq, g.imgBytes, g.lv[0].off, g.lv[0].pitch);
 }
 
 void launch_pyramid(hipStream_t st, uint8_t *pyr, const Geom &g, const ResizeTap *tabs, const int *win, int nimg)
