@@ -71,6 +71,12 @@ struct LfTrackOut { double X[3]; float uv[2]; int32_t accept, rep; };
 
 // Packed selected keypoint handed back to the device: level (4) | y (14) | x (14), level coordinates.
 __host__ __device__ inline uint32_t pack_sel(int level, int x, int y) { return ((uint32_t)level << 28) | ((uint32_t)y << 14) | (uint32_t)x; }
+__host__ __device__ inline void unpack_sel(uint32_t v, int &level, int &x, int &y)
+{
+    level = (int)(v >> 28);
+    y = (int)((v >> 14) & 0x3fffu);
+    x = (int)(v & 0x3fffu);
+}
 
 // The BLURRED planes are stored in tiles of 16 px x 8 rows = 128 bytes (one fabric line): k_describe stages a
 // 27 x 27 neighbourhood per keypoint, which is 27 lines of a row-major plane but 12-15 tiles.  Tile (tr, tc) of a

@@ -473,8 +473,10 @@ int Rig::init(const mcorb_params &p, int ncams_, int W_, int H_, int max_frames_
         if (mode == MCORB_SELECT_AUTO && e) mode = !strcmp(e, "host") ? MCORB_SELECT_HOST : (!strcmp(e, "gpu") ? MCORB_SELECT_GPU : MCORB_SELECT_AUTO);
         if (mode != MCORB_SELECT_AUTO && mode != MCORB_SELECT_HOST && mode != MCORB_SELECT_GPU) { set_error("mcorb_params.selection: unknown mode"); return MCORB_E_ARG; }
         gpu_select = mode != MCORB_SELECT_HOST && select_fits(geom);
-        // (test knob, read once here -- never from the slot drivers' threads: a getenv per launch raced with a profiler's setenv)
+        // (test knobs, read once here -- never from the slot drivers' threads: a getenv per launch raced with a profiler's setenv)
         if (getenv("MCORB_SELECT_DEEP_CAP")) select_deep_cap = std::max(1, atoi(getenv("MCORB_SELECT_DEEP_CAP")));
+        compact_one_copy = getenv("MCORB_COMPACT_ONE_COPY") != nullptr;
+        select_prof = getenv("MCORB_SELECT_PROF") != nullptr;
         // HIP graphs: a single-slot rig (one job at a time, how MC-SLAM calls) replays its job from a captured graph -- 0.35 -> 0.29 ms
         // per rig frame; with several jobs in flight the replay measured 3 - 5 % SLOWER than launch by launch (profiles/r04_overlap.txt)
         gpu_job_limit = getenv("MCORB_GPU_JOBS") ? atoi(getenv("MCORB_GPU_JOBS")) : p.gpu_jobs;
@@ -896,7 +898,7 @@ int Rig::enqueue_front(Slot &s, int nimg, int *tbl)
     launch_fast(s.st, s.d_pyr, geom, params.ini_th_fast, params.min_th_fast, d_fasttab + fast_cell_off, s.d_cellkp, s.d_cellcnt, nimg);
     if (ev_on) HIPCHK(hipEventRecord(s.ev[2], s.st));
     // compaction fills the per-image table blocks (a short kernel: it runs on the compute stream, ahead of whatever comes next)
-    launch_compact(s.st, s.d_cellkp, s.d_cellcnt, geom, d_lut, s.d_sorted, s.h_cand, tbl, s.h_overflow, nimg);
+    launch_compact(s.st, s.d_cellkp, s.d_cellcnt, geom, d_lut, s.d_sorted, s.h_cand, tbl, s.h_overflow, nimg, compact_one_copy);
     if (ev_on) HIPCHK(hipEventRecord(s.ev_c, s.st));
     return MCORB_OK;
 }
@@ -1122,7 +1124,7 @@ int Rig::enqueue_gpu_job(Slot &s, const Job &j, bool then_match)
     int *d_flags = reinterpret_cast<int *>(s.d_res.get());
     if (!small) HIPCHK(hipMemsetAsync(d_flags, 0, 16 * sizeof(int), s.st));   // (a small batch's flags travel with its per-image signals)
     TRY(enqueue_front(s, nimg, s.d_tbl));
-    HIPCHK(launch_select(s.st, s.d_tbl, s.d_sorted, geom, s.d_selval, s.d_selcnt, d_flags, nimg, select_deep_cap));
+    HIPCHK(launch_select(s.st, s.d_tbl, s.d_sorted, geom, s.d_selval, s.d_selcnt, d_flags, nimg, select_deep_cap, select_prof));
     launch_assemble(s.st, s.d_selval, s.d_selcnt, geom, tab.scale, j.lap0, j.lap1, s.d_sel, s.d_res + s.res_resp_off, s.d_nsel,
                     reinterpret_cast<int *>(s.d_res + s.res_mono_off), d_flags, nimg, small ? s.h_sel : nullptr,
                     small ? s.h_res + s.res_resp_off : nullptr, small ? s.h_sig : nullptr);
@@ -1487,8 +1489,9 @@ int Rig::run_gpu_selected(Slot &s, const Job &j, bool then_match)
         const uint8_t *rs = s.h_res + s.res_resp_off + (size_t)m * geom.kcap;
         const float *ang = params.orientation ? s.h_angles + (size_t)m * geom.kcap : nullptr;
         for (int k = 0; k < n; k++) {
-            const uint32_t v = sel[k];
-            K[k] = make_keypoint((int)(v >> 28), (int)(v & 0x3fffu), (int)((v >> 14) & 0x3fffu), (float)rs[k], ang ? ang[k] : 0.f);
+            int level, x, y;
+            unpack_sel(sel[k], level, x, y);
+            K[k] = make_keypoint(level, x, y, (float)rs[k], ang ? ang[k] : 0.f);
         }
         s.mono[m] = reinterpret_cast<const int *>(s.h_res + s.res_mono_off)[m];
     };

@@ -350,6 +350,8 @@ public:
     bool upload_pipelined = true;   // upload_u8 of a small batch: staging copy and DMA overlapped image by image
     std::atomic<int> graph_every{0};   // GPU-selected jobs replayed from a captured HIP graph: 0 never, 1 always, K all but every K-th (mcorb_rig_set_graph)
     int select_deep_cap = 4096; // k_select: largest bucket it scans node by node below the bucketing depth (MCORB_SELECT_DEEP_CAP at rig creation)
+    bool compact_one_copy = false;   // k_compact with one table copy in LDS even where four fit (MCORB_COMPACT_ONE_COPY at rig creation: test knob)
+    bool select_prof = false;        // k_select's phase stamps on stderr (MCORB_SELECT_PROF at rig creation)
     bool gpu_select = false;   // DistributeOctTree's list discipline runs in k_select (MCORB_SELECT_GPU); else on the worker pool
     int wait_mode = 0;         // how a thread waits for a HIP event: 0 spin (hipEventSynchronize), 1 interrupt-driven, 2 poll + short sleeps
     hipError_t wait_event(hipEvent_t ev) const;

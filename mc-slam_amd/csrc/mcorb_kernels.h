@@ -1,4 +1,5 @@
-// mcorb_kernels.h -- launch wrappers of the gfx950 kernels (mcorb_kernels.hip).
+// mcorb_kernels.h -- launch wrappers of the gfx950 kernels (mcorb_kernels.hip, mcorb_select_gpu.hip, mcorb_handoff_gpu.hip,
+// mcorb_bow_gpu.hip, mcorb_lf_gpu.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <vector>
@@ -63,9 +64,9 @@ int fast_cell_table(const Geom &g, std::vector<uint32_t> &tab);
 void launch_fast(hipStream_t st, const uint8_t *pyr, const Geom &g, int iniTh, int minTh, const uint32_t *cellRec,
                  uint32_t *cell_kp, int *cell_cnt, int nimg);
 // tbl: device table blocks (tbl_ints(g.bucketTotal) ints per image, layout in mcorb_common.h); cand / overflow: host-mapped
-// lut: path-code tables (LevelGeom::lutx / luty)
+// lut: path-code tables (LevelGeom::lutx / luty); one_copy: one table copy in LDS even where four fit (a rig's MCORB_COMPACT_ONE_COPY)
 void launch_compact(hipStream_t st, const uint32_t *cell_kp, const int *cell_cnt, const Geom &g, const uint16_t *lut,
-                    uint32_t *sorted_dev, uint32_t *cand, int *tbl, int *overflow, int nimg);
+                    uint32_t *sorted_dev, uint32_t *cand, int *tbl, int *overflow, int nimg, bool one_copy = false);
 void launch_blur(hipStream_t st, const uint8_t *pyr, uint8_t *blur, const Geom &g, int nimg);
 void launch_describe(hipStream_t st, const uint8_t *pyr, const uint8_t *blur, const Geom &g, const uint32_t *sel,
                      const int *nsel, int orientation, uint8_t *desc, float *angles, int nimg,
@@ -84,7 +85,9 @@ void launch_knn2(hipStream_t st, const uint8_t *desc, const int *counts, const i
 int select_cap(const Geom &g);
 bool select_fits(const Geom &g);   // false: the level trees of this geometry do not fit a wave's LDS (very large feature budgets)
 // deep_cap: a bucket with more candidates than this is not scanned node by node when a tree goes below the bucketing depth
-hipError_t launch_select(hipStream_t st, const int *tbl, const uint32_t *sorted, const Geom &g, uint32_t *sel_val, int *sel_cnt, int *fallback, int nimg, int deep_cap = 4096);
+// prof: shader-clock stamps of k_select's phases on stderr (a rig's MCORB_SELECT_PROF)
+hipError_t launch_select(hipStream_t st, const int *tbl, const uint32_t *sorted, const Geom &g, uint32_t *sel_val, int *sel_cnt, int *fallback, int nimg,
+                         int deep_cap = 4096, bool prof = false);
 void launch_assemble(hipStream_t st, const uint32_t *sel_val, const int *sel_cnt, const Geom &g, const float *scale, int lap0, int lap1,
                      uint32_t *sel, uint8_t *resp, int *nsel, int *mono, int *fallback, int nimg,
                      // optional (all or none): host-mapped copies of sel / resp and a per-image signal word set behind them

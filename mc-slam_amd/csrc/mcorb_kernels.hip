@@ -1,4 +1,9 @@
-// mcorb_kernels.hip -- hand-written gfx950 (CDNA4, wave64) kernels of the ORB front-end.
+// mcorb_kernels.hip -- the hand-written gfx950 (CDNA4, wave64) kernels of the extraction and matching job, and nothing else:
+// pyramid (k_resize), FAST (k_fast_cells), compaction (k_compact), blur and BRIEF (k_blur, k_describe, k_describe_fused,
+// k_describe_oriented), matching (k_expand, k_knn2, k_knn2_finalize), and their launch wrappers.  This is the job the benchmark
+// times and profiles/traffic.json describes, which is why the profile is guarded by the hash of this one file; the selection
+// (mcorb_select_gpu.hip), the hand-off (mcorb_handoff_gpu.hip), the BoW rows (mcorb_bow_gpu.hip) and the light-field rows
+// (mcorb_lf_gpu.hip) have files of their own.
 //
 // One image = one camera frame; every kernel is launched over a whole batch of
 // images (grid.y or grid.z = image index) so that launch cost is shared by all
@@ -6,142 +11,17 @@
 // the reference's OpenCV CPU path as restated in oracle/ (see DESIGN.md).
 // The levers are LDS tiles, packed 16-bit min/max, wave64 ballots and popcounts; one kernel is
 // GEMM-shaped: the all-pairs Hamming k-NN has an exact dense formulation and runs on the matrix
-// cores (k_knn2: v_mfma_i32_32x32x32_i8 on +-64 expanded descriptors).
+// cores (k_knn2: the block-scaled FP4 form, v_mfma_scale_f32_32x32x64_f8f6f4 on descriptors expanded to e2m1 +-1 nibbles).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-
-#include "mcorb_common.h"
-#include "mcorb_kernels.h"
-#include "mcorb_undistort.h"
-#include "mcorb_undistort_image.h"
-#include <stdlib.h>
 #include <string.h>
 #include <vector>
 
+#include "mcorb_common.h"
+#include "mcorb_device.h"
+#include "mcorb_kernels.h"
+
 namespace mcorb {
-
-typedef short s16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
-// number of set bits of a wave mask below this lane, plus acc (v_mbcnt_lo/hi: two instructions)
-__device__ __forceinline__ int lane_rank(unsigned long long mask, int acc = 0)
-{
-    return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, (uint32_t)acc));
-}
-// XCD-aware work index: workgroups b and b+8 share an XCD (and its L2) under the observed round-robin
-// placement, so give each XCD one contiguous eighth of the work items -- spatial neighbours (cells or
-// tiles that re-read the same 64-B lines for their halos) then hit in the same L2.  Bijective for any n;
-// placement only changes speed, never results.
-__device__ __forceinline__ int xcd_remap(int b, int n)
-{
-    const int q = n >> 3, r = n & 7, x = b & 7;
-    return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (b >> 3);
-}
-__device__ __forceinline__ int reflect101(int p, int len)
-{
-    // cv::borderInterpolate(BORDER_REFLECT_101); |overshoot| < len here
-    if (p < 0) p = -p;
-    if (p >= len) p = 2 * len - 2 - p;
-    return p;
-}
-
-// ---------------------------------------------------------------------------
-// Frame hand-off: CV_32F [0,1] (1 or 3 channels, BGR) -> u8 gray level-0 plane.
-// multiply(img,255) -> convertTo(CV_8U) -> cvtColor(BGR2GRAY)
-// (MCSlam/src/MultiCameraFrame.cpp:108-116).
-// ---------------------------------------------------------------------------
-__device__ __forceinline__ int sat_u8_rne(float v)
-{
-    int r = __float2int_rn(v);   // cvRound: round-half-even
-    return r < 0 ? 0 : (r > 255 ? 255 : r);
-}
-
-// one output pixel of row S (x < w)
-__device__ __forceinline__ int stage_f32_px(const float *__restrict__ S, int x, int channels)
-{
-    if (channels == 1) return sat_u8_rne(__fmul_rn(S[x], 255.f));
-    int b = sat_u8_rne(__fmul_rn(S[3 * x + 0], 255.f));
-    int gg = sat_u8_rne(__fmul_rn(S[3 * x + 1], 255.f));
-    int r = sat_u8_rne(__fmul_rn(S[3 * x + 2], 255.f));
-    return (b * 1868 + gg * 9617 + r * 4899 + 8192) >> 14;
-}
-
-__global__ __launch_bounds__(256) void k_stage_f32(const float *__restrict__ src, int w, int h, int src_pitch_f,
-                                                   int channels, size_t src_img_stride_f, uint8_t *__restrict__ pyr,
-                                                   Geom g)
-{
-    const int img = blockIdx.z;
-    const int x = blockIdx.x * 256 + threadIdx.x;
-    const int y = blockIdx.y;
-    if (x >= w) return;
-    const float *S = src + (size_t)img * src_img_stride_f + (size_t)y * src_pitch_f;
-    pyr[(size_t)img * g.imgBytes + g.lv[0].off + (size_t)y * g.lv[0].pitch + x] = (uint8_t)stage_f32_px(S, x, channels);
-}
-
-// the same into the raw planes of a rig with image undistortion set (image m at m * w * h, row stride w): k_remap_u8 follows
-__global__ __launch_bounds__(256) void k_stage_f32_raw(const float *__restrict__ src, int w, int h, int src_pitch_f,
-                                                       int channels, size_t src_img_stride_f, uint8_t *__restrict__ raw)
-{
-    const int img = blockIdx.z;
-    const int x = blockIdx.x * 256 + threadIdx.x;
-    const int y = blockIdx.y;
-    if (x >= w) return;
-    const float *S = src + (size_t)img * src_img_stride_f + (size_t)y * src_pitch_f;
-    raw[((size_t)img * h + y) * w + x] = (uint8_t)stage_f32_px(S, x, channels);
-}
-
-// ---------------------------------------------------------------------------
-// Frame hand-off of a rectified rig (RECTIFY, MultiCameraFrame.cpp:123-136): cv::undistort of every raw plane into level 0.
-// The map of a camera (mcorb_undistort_image.h, built on the host when the calibration is set) is the same for every frame, and
-// it is 6 of the 8 bytes an output pixel moves.  So a workgroup owns 1024 consecutive output pixels of ONE camera: each lane
-// loads the map entries of its 4 pixels once (16 + 8 bytes), turns them into tap offsets and weights in registers, and then
-// walks the batch's frames of that camera -- per frame 16 byte gathers (two short row segments per pixel, shared with the
-// neighbouring lanes: they hit in TCP / L2) and one dword store.  Cameras that are not set (mode 0) are copied through.
-// Every tap offset lies inside the plane by construction (remap_taps: a tap outside gets offset 0, weight 0).
-// ---------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_remap_u8(const uint8_t *__restrict__ raw, uint8_t *__restrict__ pyr,
-                                                  const RemapCam *__restrict__ cams, int ncams, int nimg, int w, int h, int wq,
-                                                  uint32_t imgBytes, uint32_t off0, int pitch0)
-{
-    const int cam = blockIdx.y;
-    const int q = blockIdx.x * 256 + threadIdx.x;   // quad of 4 output pixels; wq quads per row
-    if (q >= wq * h) return;
-    const int y = q / wq, x = (q - y * wq) * 4;
-    const int nv = min(4, w - x);
-    const size_t plane = (size_t)w * h;
-    const RemapCam C = cams[cam];
-    uint8_t *dst = pyr + off0 + (size_t)y * pitch0 + x;
-    if (C.mode == 0) {
-        const size_t so = (size_t)y * w + x;
-        for (int m = cam; m < nimg; m += ncams) {
-            const uint8_t *s = raw + (size_t)m * plane + so;
-            uint8_t *d = dst + (size_t)m * imgBytes;
-            if (nv == 4 && (w & 3) == 0) *reinterpret_cast<uint32_t *>(d) = *reinterpret_cast<const uint32_t *>(s);
-            else for (int i = 0; i < nv; i++) d[i] = s[i];
-        }
-        return;
-    }
-    // the device maps are padded to wq * 4 entries per row (zeros): both loads are aligned whatever w is
-    const size_t mo = ((size_t)y * wq) * 4 + x;
-    const uint4 a = *reinterpret_cast<const uint4 *>(C.map1 + mo * 2);
-    const uint2 b = *reinterpret_cast<const uint2 *>(C.map2 + mo);
-    const uint32_t a4[4] = {a.x, a.y, a.z, a.w};
-    const uint32_t b4[4] = {b.x & 0xffffu, b.x >> 16, b.y & 0xffffu, b.y >> 16};
-    RemapTaps t[4];
-#pragma unroll
-    for (int i = 0; i < 4; i++) remap_taps((int)(int16_t)(a4[i] & 0xffffu), (int)(int16_t)(a4[i] >> 16), b4[i], w, h, w, t[i]);
-#pragma unroll 2
-    for (int m = cam; m < nimg; m += ncams) {
-        const uint8_t *s = raw + (size_t)m * plane;
-        uint32_t v = 0;
-#pragma unroll
-        for (int i = 0; i < 4; i++) v |= (uint32_t)remap_pixel(s, t[i]) << (8 * i);
-        uint8_t *d = dst + (size_t)m * imgBytes;
-        if (nv == 4) *reinterpret_cast<uint32_t *>(d) = v;
-        else for (int i = 0; i < nv; i++) d[i] = (uint8_t)(v >> (8 * i));
-    }
-}
 
 // ---------------------------------------------------------------------------
 // Pyramid: level L from level L-1, cv::resize INTER_LINEAR 8UC1 fixed point
@@ -170,7 +50,7 @@ __global__ __launch_bounds__(256) void k_resize(uint8_t *__restrict__ pyr, Geom 
     const int nq = ((sx1 - sx0) >> 4) + 1, nr = sy1 - sy0 + 1;   // nq*16 <= srcPitch, nr <= srcRows by construction
     // this wave's row taps, one per lane, fetched now so that the latency hides behind the window fill (read back with
     // v_readlane below: a load inside the row loop is a vector load the whole wave waits for, eight times in a row)
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wave = wave_uniform(tid >> 6);
     const int wy0 = by0 + wave * (kResizeRows / 4);
     uint2 ytap;
     {
@@ -631,7 +511,7 @@ __global__ __launch_bounds__(64) void k_fast_cells(const uint8_t *__restrict__ p
     const int lane = threadIdx.x;
     const int img = blockIdx.y;
     FastCell C;
-    fast_cell_setup(pyr, g, img, __builtin_amdgcn_readfirstlane(xcd_remap(blockIdx.x, gridDim.x)), cellRec, C);
+    fast_cell_setup(pyr, g, img, wave_uniform(xcd_remap(blockIdx.x, gridDim.x)), cellRec, C);
     int *out_cnt = cell_cnt + (size_t)img * g.cells + C.cell;
     if (!C.on) {
         if (lane == 0) *out_cnt = 0;
@@ -753,7 +633,8 @@ __global__ __launch_bounds__(64) void k_fast_cells(const uint8_t *__restrict__ p
 // Private copies of every bucket's counter and winner key in LDS; lane & (copies - 1) picks one.  A cell's candidates fall into
 // one to four buckets, so most lanes of an LDS atomic hit the same address and are served one after the other: with four
 // copies a quarter as many (46 -> 39.6 us per 128 images; two: 40.3, eight: 39.3).  One copy when four would not fit 64 KiB
-// of LDS (levels with thousands of buckets: very large feature budgets on wide images).
+// of LDS (levels with thousands of buckets: very large feature budgets on wide images), or when the rig asks for it (launch_compact's
+// one_copy: MCORB_COMPACT_ONE_COPY at rig creation, which is how a test reaches that form).
 constexpr int kCompactCopies = 4;
 template <int kCompactWaves>
 __device__ __forceinline__ int block_exclusive_scan(int v, int *wsum, int *total)   // 64 * kCompactWaves threads
@@ -838,7 +719,7 @@ __global__ __launch_bounds__(kCompactWG, 8) void k_compact(const uint32_t *__res
     // every load sat under its own branch behind its own LDS read of the count, and a wait that follows loads under branches
     // is a wait for all of them; with eight cells per group the kernel also needed 83 registers, which halved the resident
     // workgroups: levels 4 - 7 started when levels 0 - 3 were done.  67 -> 50 us per 128 images.)
-    const int wave_u = __builtin_amdgcn_readfirstlane(wave);
+    const int wave_u = wave_uniform(wave);
     auto walk = [&](auto &&fn) {
         static_assert(kCompactCells == 8 || kCompactCells == 4 || kCompactCells == 2, "the counts are read as one 4-, 8- or 16-byte word");
         constexpr int step = kCompactWaves * kCompactCells;
@@ -966,6 +847,52 @@ __global__ __launch_bounds__(kCompactWG, 8) void k_compact(const uint32_t *__res
 // packed u16 (every partial sum <= 65280, so v_pk_* arithmetic is exact), vertical
 // pass in 32 bits, dword stores.
 // ---------------------------------------------------------------------------
+// The arithmetic, shared with k_describe_fused (which blurs only the windows around the kept keypoints):
+// byte window of four starting at byte B of the dwords D (B a compile-time constant)
+template <int B>
+__device__ __forceinline__ uint32_t gauss_window(const uint32_t (&D)[4])
+{
+    constexpr int q = B >> 2, sh = B & 3;
+    if constexpr (sh == 0) return D[q];
+    else return __builtin_amdgcn_alignbyte(D[q + 1], D[q], sh);
+}
+// horizontal: the 8.8 sums of four consecutive output pixels of one row; pixel j needs bytes SH + j .. SH + j + 6 of D: two
+// v_dot4_u32_u8 on the byte windows [j, j + 4) (taps 18,34,48,56) and [j + 4, j + 8) (taps 48,34,18,0), the second accumulating
+// into the first; the sum is <= 65280, so it is exactly the 8.8 fixed-point value OpenCV's horizontal pass produces
+template <int SH>
+__device__ __forceinline__ void gauss_hsum4(const uint32_t (&D)[4], uint32_t (&h)[4])
+{
+    constexpr uint32_t T1 = 0x38302212u, T2 = 0x00122230u;
+    h[0] = __builtin_amdgcn_udot4(gauss_window<SH + 4>(D), T2, __builtin_amdgcn_udot4(gauss_window<SH>(D), T1, 0u, false), false);
+    h[1] = __builtin_amdgcn_udot4(gauss_window<SH + 5>(D), T2, __builtin_amdgcn_udot4(gauss_window<SH + 1>(D), T1, 0u, false), false);
+    h[2] = __builtin_amdgcn_udot4(gauss_window<SH + 6>(D), T2, __builtin_amdgcn_udot4(gauss_window<SH + 2>(D), T1, 0u, false), false);
+    h[3] = __builtin_amdgcn_udot4(gauss_window<SH + 7>(D), T2, __builtin_amdgcn_udot4(gauss_window<SH + 3>(D), T1, 0u, false), false);
+}
+// the sums of two vertically adjacent rows as row-pair dwords, h0[x] | h1[x] << 16: the vertical pass's v_dot2_u32_u16 operands
+__device__ __forceinline__ uint4 gauss_pair4(const uint32_t (&h0)[4], const uint32_t (&h1)[4])
+{
+    return uint4{__builtin_amdgcn_perm(h1[0], h0[0], 0x05040100u), __builtin_amdgcn_perm(h1[1], h0[1], 0x05040100u),
+                 __builtin_amdgcn_perm(h1[2], h0[2], 0x05040100u), __builtin_amdgcn_perm(h1[3], h0[3], 0x05040100u)};
+}
+// vertical: four columns of output row k (0 .. 3, a constant once unrolled) of the rows P's five row pairs start at, as four
+// bytes.  Row k covers rows k .. k + 6: taps {18,34,48,56,48,34,18} paired with the rows, 0 for the eighth row of the four pairs
+__device__ __forceinline__ uint32_t gauss_vrow4(const uint32_t (&P)[5][4], int k)
+{
+    const int tap[9] = {0, 18, 34, 48, 56, 48, 34, 18, 0};   // tap[1 + n] = tap of the window's row n
+    const int q = k >> 1, o = 1 - (k & 1);
+    uint32_t acc[4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        uint32_t a = 32768u;
+#pragma unroll
+        for (int i = 0; i < 4; i++)
+            a = __builtin_amdgcn_udot2(__builtin_bit_cast(u16x2, P[q + i][j]), u16x2{(unsigned short)tap[2 * i + o], (unsigned short)tap[2 * i + o + 1]}, a, false);
+        acc[j] = a;
+    }
+    // (acc + 32768) >> 16 fits a byte: pick byte 2 of each accumulator
+    return __builtin_amdgcn_perm(acc[1], acc[0], 0x0c0c0602u) | __builtin_amdgcn_perm(acc[3], acc[2], 0x06020c0cu);
+}
+
 __global__ __launch_bounds__(256) void k_blur(const uint8_t *__restrict__ pyr, uint8_t *__restrict__ blur, Geom g)
 {
     constexpr int TW = kBlurTW, TH = kBlurTH;
@@ -1058,29 +985,16 @@ __global__ __launch_bounds__(256) void k_blur(const uint8_t *__restrict__ pyr, u
     }
     __syncthreads();
     // horizontal: work item = (row pair, group of 4 output pixels); bytes b0..b11 = tile columns 4g .. 4g+11,
-    // output pixel j sits at tile column 4g+4+j and needs b[j+1 .. j+7]: two v_dot4_u32_u8 on the byte windows
-    // b[j+1..j+4] (taps 18,34,48,56) and b[j+5..j+8] (taps 48,34,18,0), the second accumulating into the first;
-    // the sum is <= 65280, so it is exactly the 8.8 fixed-point value OpenCV's horizontal pass produces
+    // output pixel j sits at tile column 4g+4+j and needs b[j+1 .. j+7]
     for (int i = tid; i < NP * (TW / 4); i += 256) {
         const int p = i / (TW / 4), gx = i - p * (TW / 4);
         uint32_t h[2][4];
 #pragma unroll
         for (int rr = 0; rr < 2; rr++) {
             const uint32_t *row = in32 + (2 * p + rr) * ID + A0 + gx;
-            const uint32_t d0 = row[0], d1 = row[1], d2 = row[2];
-            constexpr uint32_t T1 = 0x38302212u, T2 = 0x00122230u;
-#define WIN(hi, lo, sh) ((sh) == 4 ? (hi) : __builtin_amdgcn_alignbyte(hi, lo, sh))
-#define HTAP(j) __builtin_amdgcn_udot4(WIN(d2, d1, (j) + 1), T2, __builtin_amdgcn_udot4(WIN(d1, d0, (j) + 1), T1, 0u, false), false)
-            h[rr][0] = HTAP(0); h[rr][1] = HTAP(1); h[rr][2] = HTAP(2); h[rr][3] = HTAP(3);
-#undef HTAP
-#undef WIN
+            gauss_hsum4<1>({row[0], row[1], row[2], 0u}, h[rr]);   // (byte 12 is not reached at shift 1)
         }
-        uint4 v;   // (h[r][x], h[r+1][x]) per dword
-        v.x = __builtin_amdgcn_perm(h[1][0], h[0][0], 0x05040100u);
-        v.y = __builtin_amdgcn_perm(h[1][1], h[0][1], 0x05040100u);
-        v.z = __builtin_amdgcn_perm(h[1][2], h[0][2], 0x05040100u);
-        v.w = __builtin_amdgcn_perm(h[1][3], h[0][3], 0x05040100u);
-        *reinterpret_cast<uint4 *>(hp + p * TW + 4 * gx) = v;
+        *reinterpret_cast<uint4 *>(hp + p * TW + 4 * gx) = gauss_pair4(h[0], h[1]);
     }
     __syncthreads();
     // vertical: thread = 4 columns x 4 rows from five row pairs; taps {18,34,48,56,48,34,18} paired with the rows
@@ -1091,34 +1005,11 @@ __global__ __launch_bounds__(256) void k_blur(const uint8_t *__restrict__ pyr, u
         const uint4 v = *reinterpret_cast<const uint4 *>(hp + (2 * rg + q) * TW + 4 * gx);
         P[q][0] = v.x; P[q][1] = v.y; P[q][2] = v.z; P[q][3] = v.w;
     }
-#define KK(lo, hi) (u16x2{(unsigned short)(lo), (unsigned short)(hi)})
-#define DOT(a, k, c) __builtin_amdgcn_udot2(__builtin_bit_cast(u16x2, a), k, c, false)
     // The output goes through LDS (in32 is dead since the horizontal pass) so that it reaches HBM as whole tiles of the
     // 16 x 8 blurred-plane layout (mcorb_common.h): eight lanes write one 128-byte line.
     static_assert(ID >= TW / 4 && (TH + 6) * ID >= TH * ID, "output staging reuses the input rows");
 #pragma unroll
-    for (int k = 0; k < 4; k++) {
-        uint32_t acc[4];
-        const int q = k >> 1;   // first row pair of this output row
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            uint32_t a = 32768u;
-            if ((k & 1) == 0) {   // rows 2q .. 2q+6
-                a = DOT(P[q][j], KK(18, 34), a);
-                a = DOT(P[q + 1][j], KK(48, 56), a);
-                a = DOT(P[q + 2][j], KK(48, 34), a);
-                a = DOT(P[q + 3][j], KK(18, 0), a);
-            } else {              // rows 2q+1 .. 2q+7
-                a = DOT(P[q][j], KK(0, 18), a);
-                a = DOT(P[q + 1][j], KK(34, 48), a);
-                a = DOT(P[q + 2][j], KK(56, 48), a);
-                a = DOT(P[q + 3][j], KK(34, 18), a);
-            }
-            acc[j] = a;
-        }
-        // (acc + 32768) >> 16 fits a byte: pick byte 2 of each accumulator
-        in32[(rg * 4 + k) * ID + gx] = __builtin_amdgcn_perm(acc[1], acc[0], 0x0c0c0602u) | __builtin_amdgcn_perm(acc[3], acc[2], 0x06020c0cu);
-    }
+    for (int k = 0; k < 4; k++) in32[(rg * 4 + k) * ID + gx] = gauss_vrow4(P, k);
     __syncthreads();
     {
         static_assert(TW == 128 && TH == 32, "one 16-byte tile row per thread: 4 x 8 tiles of 16 x 8");
@@ -1127,8 +1018,6 @@ __global__ __launch_bounds__(256) void k_blur(const uint8_t *__restrict__ pyr, u
         const uint4 o = *reinterpret_cast<const uint4 *>(in32 + (8 * tr + sr) * ID + 4 * tc);
         if (x < L.w && y < L.h) *reinterpret_cast<uint4 *>(blur + (size_t)img * g.imgBytes + L.off + blur_tiled_offset(L.pitch, x, y)) = o;
     }
-#undef KK
-#undef DOT
 }
 
 // ---------------------------------------------------------------------------
@@ -1167,6 +1056,12 @@ __device__ __forceinline__ float fast_atan2_deg(float y, float x)
     return a;
 }
 
+// the four ballots ARE the descriptor: lanes 0 .. 3 store eight bytes each
+__device__ __forceinline__ void store_ballots(const unsigned long long (&bits)[4], int lane, void *dst)
+{
+    if (lane < 4) reinterpret_cast<unsigned long long *>(dst)[lane] = lane == 0 ? bits[0] : lane == 1 ? bits[1] : lane == 2 ? bits[2] : bits[3];
+}
+
 constexpr int kDescPerWave = 4;   // keypoints per wave
 constexpr int kPatchRows = 27, kPatchDw = 12;  // unrotated taps lie within +-13 px: 27 rows x 3 tile columns of 16 bytes
 
@@ -1200,8 +1095,8 @@ __global__ __launch_bounds__(256) void k_describe(const uint8_t *__restrict__ bl
 #pragma unroll
     for (int u = 0; u < kDescPerWave; u++) {
         const int k = k0 + u < n ? k0 + u : n - 1;   // tail keypoints are recomputed, never stored
-        const uint32_t s = sel[(size_t)img * g.kcap + k];
-        const int level = (int)(s >> 28), ky = (int)((s >> 14) & 0x3fffu), kx = (int)(s & 0x3fffu);
+        int level, kx, ky;
+        unpack_sel(sel[(size_t)img * g.kcap + k], level, kx, ky);
         const LevelGeom &L = g.lv[level];
         const int tc0 = (kx - 13) >> 4;              // keypoints sit >= 19 px from every edge: tile columns tc0 .. tc0+2 exist
         shift[u] = kx - 16 * tc0;                     // 13..28
@@ -1220,9 +1115,7 @@ __global__ __launch_bounds__(256) void k_describe(const uint8_t *__restrict__ bl
         *reinterpret_cast<uint4 *>(&patch[wave][u][lane * 4]) = v[u][0];
         if (lane < kPatchRows * 3 - 64) *reinterpret_cast<uint4 *>(&patch[wave][u][(64 + lane) * 4]) = v[u][1];
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");   // each wave only reads the patches it wrote itself
+    wave_lds_sync();   // each wave only reads the patches it wrote itself
 
     // this lane's four test pairs (pairs lane, 64+lane, 128+lane, 192+lane) as LDS byte offsets
     int o0[4], o1[4];
@@ -1238,10 +1131,7 @@ __global__ __launch_bounds__(256) void k_describe(const uint8_t *__restrict__ bl
         unsigned long long bits[4];
 #pragma unroll
         for (int j = 0; j < 4; j++) bits[j] = __ballot(c[o0[j]] < c[o1[j]]);
-        if (lane < 4 && k0 + u < n) {
-            const unsigned long long b = lane == 0 ? bits[0] : lane == 1 ? bits[1] : lane == 2 ? bits[2] : bits[3];
-            reinterpret_cast<unsigned long long *>(desc + ((size_t)img * g.kcap + k0 + u) * 32)[lane] = b;
-        }
+        if (k0 + u < n) store_ballots(bits, lane, desc + ((size_t)img * g.kcap + k0 + u) * 32);
     }
 }
 
@@ -1270,14 +1160,6 @@ __constant__ uint8_t c_brief_groups[64] = {   // [0, 32): slot -> byte; [32, 64)
 };
 constexpr int kFdWaveDw = kFdSrcDw + kFdHpDw + kFdOutDw;
 
-template <int B>
-__device__ __forceinline__ uint32_t fd_window(const uint32_t (&D)[4])
-{
-    constexpr int q = B >> 2, sh = B & 3;
-    if constexpr (sh == 0) return D[q];
-    else return __builtin_amdgcn_alignbyte(D[q + 1], D[q], sh);
-}
-
 // horizontal pass for a window whose first source byte sits SH bytes into dword `a` of every row
 template <int SH>
 __device__ __forceinline__ void fd_hpass(const uint32_t *__restrict__ src, uint32_t *__restrict__ hp, int a, int lane)
@@ -1291,31 +1173,14 @@ __device__ __forceinline__ void fd_hpass(const uint32_t *__restrict__ src, uint3
 #pragma unroll
             for (int rr = 0; rr < 2; rr++) {
                 const uint32_t *row = src + (2 * p + rr) * 12 + a + j;
-                uint32_t D[4] = {row[0], row[1], row[2], 0u};
-                D[3] = SH == 3 ? row[3] : D[2];   // byte 12 is only ever needed at SH = 3
-                constexpr uint32_t T1 = 0x38302212u, T2 = 0x00122230u;   // taps 18,34,48,56 | 48,34,18,0
-#define FD_HTAP(o) __builtin_amdgcn_udot4(fd_window<SH + (o) + 4>(D), T2, __builtin_amdgcn_udot4(fd_window<SH + (o)>(D), T1, 0u, false), false)
-                h[rr][0] = FD_HTAP(0); h[rr][1] = FD_HTAP(1); h[rr][2] = FD_HTAP(2); h[rr][3] = FD_HTAP(3);
-#undef FD_HTAP
+                gauss_hsum4<SH>({row[0], row[1], row[2], SH == 3 ? row[3] : 0u}, h[rr]);   // byte 12 is only ever needed at SH = 3
             }
-            uint4 v;
-            v.x = __builtin_amdgcn_perm(h[1][0], h[0][0], 0x05040100u);
-            v.y = __builtin_amdgcn_perm(h[1][1], h[0][1], 0x05040100u);
-            v.z = __builtin_amdgcn_perm(h[1][2], h[0][2], 0x05040100u);
-            v.w = __builtin_amdgcn_perm(h[1][3], h[0][3], 0x05040100u);
-            *reinterpret_cast<uint4 *>(hp + p * kFdHpPitch + 4 * j) = v;
+            *reinterpret_cast<uint4 *>(hp + p * kFdHpPitch + 4 * j) = gauss_pair4(h[0], h[1]);
         }
     }
 }
 
-__device__ __forceinline__ void fd_wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");   // a wave only ever reads what it wrote itself
-}
-
-// (65 registers: seven waves per SIMD where the LDS would allow eight; capped at 64 the compiler spills three and the kernel
+// (67 registers: seven waves per SIMD where the LDS would allow eight; capped at 64 the compiler spills three and the kernel
 // takes 131 instead of 110 us; with the tap offsets packed two to a register it needs 61 and runs eight waves: 109 us, no
 // gain -- the kernel is held by vector issue and the LDS pipe together, not by waves to switch to)
 __global__ __launch_bounds__(256) void k_describe_fused(const uint8_t *__restrict__ pyr, Geom g,
@@ -1328,7 +1193,7 @@ __global__ __launch_bounds__(256) void k_describe_fused(const uint8_t *__restric
     // 1-D grid, remapped so that each XCD works through whole images one after the other: the windows of neighbouring
     // keypoints overlap, and with an image's workgroups dealt round-robin over the eight L2s none of that overlap hit
     // (0.92 GB fetched per 128 images, 7 KB per keypoint).
-    const int b = __builtin_amdgcn_readfirstlane(xcd_remap(blockIdx.x, gridDim.x));
+    const int b = wave_uniform(xcd_remap(blockIdx.x, gridDim.x));
     const int img = b / groups;
     const int k0 = ((b - img * groups) * 4 + wave) * kDescPerWave;
     const int n = nsel[img];
@@ -1366,8 +1231,8 @@ __global__ __launch_bounds__(256) void k_describe_fused(const uint8_t *__restric
     int kxn;
 #define FD_FETCH(u)                                                                                                         \
     {                                                                                                                       \
-        const uint32_t s_ = (uint32_t)__builtin_amdgcn_readlane((int)selv, (u));                                            \
-        const int level_ = (int)(s_ >> 28), ky_ = (int)((s_ >> 14) & 0x3fffu), kx_ = (int)(s_ & 0x3fffu);                   \
+        int level_, kx_, ky_;                                                                                               \
+        unpack_sel((uint32_t)__builtin_amdgcn_readlane((int)selv, (u)), level_, kx_, ky_);                                  \
         const LevelGeom &L_ = g.lv[level_];                                                                                 \
         const uint8_t *p0_ = pyr + (size_t)img * g.imgBytes + L_.off + (size_t)(ky_ - 16) * L_.pitch + ((kx_ - 16) & ~15);  \
         va = *reinterpret_cast<const uint4 *>(p0_ + (size_t)__mul24(toff0 & 0xff, L_.pitch) + 16 * (toff0 >> 8));           \
@@ -1385,14 +1250,14 @@ __global__ __launch_bounds__(256) void k_describe_fused(const uint8_t *__restric
         *reinterpret_cast<uint4 *>(src + tlds0) = va;
         if (tact1) *reinterpret_cast<uint4 *>(src + tlds1) = vb;
         if (u + 1 < kDescPerWave) FD_FETCH(u + 1)
-        fd_wave_sync();
+        wave_lds_sync();
         switch (A & 3) {   // wave-uniform: four copies of the pass with compile-time byte shifts
         case 0: fd_hpass<0>(src, hp, A >> 2, lane); break;
         case 1: fd_hpass<1>(src, hp, A >> 2, lane); break;
         case 2: fd_hpass<2>(src, hp, A >> 2, lane); break;
         default: fd_hpass<3>(src, hp, A >> 2, lane); break;
         }
-        fd_wave_sync();
+        wave_lds_sync();
         if (lane < 49) {   // vertical: lane = 4 rows x 4 columns from five row pairs
             const int rg = (int)(__umul24((uint32_t)lane, 147u) >> 10), j = lane - 7 * rg;
             uint32_t P[5][4];
@@ -1401,46 +1266,18 @@ __global__ __launch_bounds__(256) void k_describe_fused(const uint8_t *__restric
                 const uint4 w = *reinterpret_cast<const uint4 *>(hp + (2 * rg + q) * kFdHpPitch + 4 * j);
                 P[q][0] = w.x; P[q][1] = w.y; P[q][2] = w.z; P[q][3] = w.w;
             }
-#define KK(lo, hi) (u16x2{(unsigned short)(lo), (unsigned short)(hi)})
-#define DOT(a, k, c) __builtin_amdgcn_udot2(__builtin_bit_cast(u16x2, a), k, c, false)
 #pragma unroll
-            for (int k = 0; k < 4; k++) {
-                uint32_t acc[4];
-                const int q = k >> 1;
-#pragma unroll
-                for (int c = 0; c < 4; c++) {
-                    uint32_t a = 32768u;
-                    if ((k & 1) == 0) {
-                        a = DOT(P[q][c], KK(18, 34), a);
-                        a = DOT(P[q + 1][c], KK(48, 56), a);
-                        a = DOT(P[q + 2][c], KK(48, 34), a);
-                        a = DOT(P[q + 3][c], KK(18, 0), a);
-                    } else {
-                        a = DOT(P[q][c], KK(0, 18), a);
-                        a = DOT(P[q + 1][c], KK(34, 48), a);
-                        a = DOT(P[q + 2][c], KK(56, 48), a);
-                        a = DOT(P[q + 3][c], KK(34, 18), a);
-                    }
-                    acc[c] = a;
-                }
-                out[(4 * rg + k) * kFdOutPitchDw + j] =
-                    __builtin_amdgcn_perm(acc[1], acc[0], 0x0c0c0602u) | __builtin_amdgcn_perm(acc[3], acc[2], 0x06020c0cu);
-            }
-#undef KK
-#undef DOT
+            for (int k = 0; k < 4; k++) out[(4 * rg + k) * kFdOutPitchDw + j] = gauss_vrow4(P, k);
         }
-        fd_wave_sync();
+        wave_lds_sync();
         const uint8_t *c = reinterpret_cast<const uint8_t *>(out);
         unsigned long long bits[4];
 #pragma unroll
         for (int j = 0; j < 4; j++) bits[j] = __ballot(c[o0[j]] < c[o1[j]]);
         // the four ballot words hold the 32 descriptor bytes in slot order: through 32 bytes of LDS (the row-pair region is idle
         // by now), lane b picks up descriptor byte b from its slot
-        if (lane < 4) {
-            const unsigned long long b = lane == 0 ? bits[0] : lane == 1 ? bits[1] : lane == 2 ? bits[2] : bits[3];
-            reinterpret_cast<unsigned long long *>(hp)[lane] = b;
-        }
-        fd_wave_sync();
+        store_ballots(bits, lane, hp);
+        wave_lds_sync();
         if (lane < 32 && k0 + u < n) {   // lane b stores descriptor byte b
             const uint8_t byte = reinterpret_cast<const uint8_t *>(hp)[bslot];
             desc[((size_t)img * g.kcap + k0 + u) * 32 + lane] = byte;
@@ -1462,8 +1299,8 @@ __global__ __launch_bounds__(256) void k_describe_oriented(const uint8_t *__rest
     const int img = blockIdx.y;
     const int k = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (k >= nsel[img]) return;
-    const uint32_t s = sel[(size_t)img * g.kcap + k];
-    const int level = (int)(s >> 28), ky = (int)((s >> 14) & 0x3fffu), kx = (int)(s & 0x3fffu);
+    int level, kx, ky;
+    unpack_sel(sel[(size_t)img * g.kcap + k], level, kx, ky);
     const LevelGeom &L = g.lv[level];
     const int pitch = L.pitch;
     const size_t coff = (size_t)img * g.imgBytes + L.off + (size_t)ky * pitch + kx;
@@ -1510,10 +1347,7 @@ __global__ __launch_bounds__(256) void k_describe_oriented(const uint8_t *__rest
         const int t0 = cb[blur_tiled_offset(pitch, kx + ox0, ky + oy0)], t1 = cb[blur_tiled_offset(pitch, kx + ox1, ky + oy1)];
         bits[j] = __ballot(t0 < t1);
     }
-    if (lane < 4) {
-        const unsigned long long b = lane == 0 ? bits[0] : lane == 1 ? bits[1] : lane == 2 ? bits[2] : bits[3];
-        reinterpret_cast<unsigned long long *>(desc + ((size_t)img * g.kcap + k) * 32)[lane] = b;
-    }
+    store_ballots(bits, lane, desc + ((size_t)img * g.kcap + k) * 32);
 }
 
 // ---------------------------------------------------------------------------
@@ -1878,205 +1712,10 @@ __global__ __launch_bounds__(1024) void k_knn2_finalize(const uint2 *__restrict_
     if (tid < qblocks) mcount[pair * qblocks + tid] = tid == 0 ? s_run : 0;
 }
 
-// popcount(x) + acc in one instruction; chaining the eight words of a 256-bit XOR through the
-// accumulator operand saves the separate adds the compiler otherwise emits
-__device__ __forceinline__ uint32_t bcnt_acc(uint32_t x, uint32_t acc)
-{
-    uint32_t r;
-    asm("v_bcnt_u32_b32 %0, %1, %2" : "=v"(r) : "v"(x), "v"(acc));
-    return r;
-}
-__device__ __forceinline__ uint32_t hamming256(const ulonglong4 &a, const ulonglong4 &b)
-{
-    const unsigned long long x0 = a.x ^ b.x, x1 = a.y ^ b.y, x2 = a.z ^ b.z, x3 = a.w ^ b.w;
-    uint32_t d = __builtin_popcount((uint32_t)x0);
-    d = bcnt_acc((uint32_t)(x0 >> 32), d);
-    d = bcnt_acc((uint32_t)x1, d);
-    d = bcnt_acc((uint32_t)(x1 >> 32), d);
-    d = bcnt_acc((uint32_t)x2, d);
-    d = bcnt_acc((uint32_t)(x2 >> 32), d);
-    d = bcnt_acc((uint32_t)x3, d);
-    d = bcnt_acc((uint32_t)(x3 >> 32), d);
-    return d;
-}
-
-// ---------------------------------------------------------------------------
-// DBoW2 vocabulary-tree descent (TemplatedVocabulary::transform's per-feature part, used by
-// MultiCameraFrame::extractFeatureSingle, MultiCameraFrame.cpp:257): from the root, move to the child
-// with the smallest Hamming distance (strict '<': the first child wins ties) until a leaf; remember the
-// node reached at depth `nid_level`.  One descriptor per lane; the children of a node are stored
-// contiguously (descriptor + node id), k*32 bytes per step.
-// ---------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_bow_descend(const uint8_t *__restrict__ desc, int n, const int *__restrict__ child_start,
-                                                     const int *__restrict__ child_count, const ulonglong4 *__restrict__ child_desc,
-                                                     const int *__restrict__ child_id, const int *__restrict__ word_id,
-                                                     const double *__restrict__ weight, int nid_level, BowRes *__restrict__ out)
-{
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const ulonglong4 q = *reinterpret_cast<const ulonglong4 *>(desc + (size_t)i * 32);
-    int node = 0, nid = 0, level = 0;
-    int cc = child_count[0];
-    while (cc > 0) {
-        ++level;
-        const int cs = child_start[node];
-        uint32_t best = 0xffffffffu;
-        int bj = 0;
-        for (int j = 0; j < cc; j++) {
-            const uint32_t d = hamming256(q, child_desc[cs + j]);
-            if (d < best) { best = d; bj = j; }
-        }
-        node = child_id[cs + bj];
-        if (level == nid_level) nid = node;
-        cc = child_count[node];
-    }
-    out[i] = BowRes{word_id[node], nid, weight[node]};
-}
-
-// ---------------------------------------------------------------------------
-// BoW-guided intra-rig matching, the data-parallel half (MultiCameraFrame::computeIntraMatches(matches,
-// words_), MultiCameraFrame.cpp:708-745): for feature a of camera c1 and every camera c2 > c1, the best
-// and second-best Hamming distance among c2's features that fell into the same vocabulary node, skipping
-// candidates whose row differs by 50 px or more; strict '<' so the first minimum wins.  The serial
-// track bookkeeping that consumes this table stays on the host.
-// All frames of a batch in one launch: blockIdx.z = frame, blockIdx.y = camera pair (c1 < c2).  Per frame f the
-// index tables are laid out for image index m = f * ncams + c: slot_of / node_feats / yv at m * kcap,
-// node_range at (rg_base[f] + slot) * ncams + c; out at ((f * npairs + pair) * kcap + a).
-// ---------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_bow_best2(const uint8_t *__restrict__ desc, int img0, int kcap, int ncams,
-                                                   const float *__restrict__ yv, const int *__restrict__ slot_of,
-                                                   const int2 *__restrict__ node_range, const int *__restrict__ rg_base,
-                                                   const int *__restrict__ node_feats, const int *__restrict__ nfeat,
-                                                   int4 *__restrict__ out)
-{
-    const int a = blockIdx.x * 256 + threadIdx.x;
-    const int f = blockIdx.z, npairs = ncams * (ncams - 1) / 2;
-    int c1 = 0, rem = blockIdx.y;   // pair index -> (c1, c2), pairs in (0,1), (0,2), .., (1,2), .. order
-    while (rem >= ncams - 1 - c1) { rem -= ncams - 1 - c1; c1++; }
-    const int c2 = c1 + 1 + rem;
-    const int m1 = f * ncams + c1, m2 = f * ncams + c2;
-    if (a >= nfeat[m1]) return;
-    int4 r = int4{-1, 0x7fffffff, 0x7fffffff, 0};
-    const int slot = slot_of[(size_t)m1 * kcap + a];
-    if (slot >= 0) {
-        const int2 rg = node_range[(size_t)(rg_base[f] + slot) * ncams + c2];
-        const ulonglong4 q = *reinterpret_cast<const ulonglong4 *>(desc + ((size_t)(img0 + m1) * kcap + a) * 32);
-        const float y1 = yv[(size_t)m1 * kcap + a];
-        for (int j = 0; j < rg.y; j++) {
-            const int b = node_feats[(size_t)m2 * kcap + rg.x + j];
-            if (fabsf(__fsub_rn(y1, yv[(size_t)m2 * kcap + b])) >= 50.f) continue;
-            const int d = (int)hamming256(q, *reinterpret_cast<const ulonglong4 *>(desc + ((size_t)(img0 + m2) * kcap + b) * 32));
-            if (d < r.y) { r.x = j; r.z = r.y; r.y = d; }
-            else if (d < r.z) r.z = d;
-        }
-    }
-    out[((size_t)f * npairs + blockIdx.y) * kcap + a] = r;
-}
-
-// ---------------------------------------------------------------------------
-// Device -> pinned host copy as a SMALL kernel.  hipMemcpyAsync to pinned memory runs as a blit kernel on this stack
-// (__amd_rocclr_copyBuffer; HSA_ENABLE_SDMA changes nothing), and the kernel of the job that runs beside it is stretched
-// to the copy's length (k_expand: 12 us alone, 150 us beside the descriptor read-back).  The link moves ~50 GB/s whatever
-// feeds it; kCopyWG workgroups looping over the buffer with 16-byte accesses, four loads in flight per lane, feed it as
-// well and leave the neighbour alone (k_expand 23 us).  Used for single-slot rigs only: with six slots in flight the
-// runtime's copy still gives 4-6 % more frames/s (profiles/r03_copy_kernel_ab.txt; the smaller the grid the closer: 1024
-// workgroups 30.7 k, 128: 30.9 k, 24: 32.3 k, 4: 33.5 k, runtime 34.0 k frames/s).
-// ---------------------------------------------------------------------------
-constexpr int kCopyWG = 24;
-__global__ __launch_bounds__(256) void k_copy_to_host(const uint4 *__restrict__ src, uint4 *__restrict__ dst, size_t n16)
-{
-    const v4i *s = reinterpret_cast<const v4i *>(src);
-    v4i *d = reinterpret_cast<v4i *>(dst);
-    const size_t stride = (size_t)gridDim.x * 256;
-    size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    for (; i + 3 * stride < n16; i += 4 * stride) {   // four 16-byte loads in flight per lane
-        const v4i a = __builtin_nontemporal_load(s + i), b = __builtin_nontemporal_load(s + i + stride);
-        const v4i c = __builtin_nontemporal_load(s + i + 2 * stride), e = __builtin_nontemporal_load(s + i + 3 * stride);
-        __builtin_nontemporal_store(a, d + i);
-        __builtin_nontemporal_store(b, d + i + stride);
-        __builtin_nontemporal_store(c, d + i + 2 * stride);
-        __builtin_nontemporal_store(e, d + i + 3 * stride);
-    }
-    for (; i < n16; i += stride) {
-        const v4i v = __builtin_nontemporal_load(s + i);
-        __builtin_nontemporal_store(v, d + i);
-    }
-}
-
-void launch_copy_to_host(hipStream_t st, const void *src_dev, void *dst_host_mapped, size_t bytes)
-{
-    const size_t n16 = (bytes + 15) / 16;   // both buffers are allocated in multiples of 16 bytes
-    if (!n16) return;
-    static const int wg_env = getenv("MCORB_COPY_WG") ? atoi(getenv("MCORB_COPY_WG")) : 0;
-    const size_t cap = wg_env > 0 ? (size_t)wg_env : (size_t)kCopyWG;
-    const int wgs = (int)((n16 + 255) / 256 < cap ? (n16 + 255) / 256 : cap);
-    hipLaunchKernelGGL(k_copy_to_host, dim3(wgs), dim3(256), 0, st, reinterpret_cast<const uint4 *>(src_dev),
-                       reinterpret_cast<uint4 *>(dst_host_mapped), n16);
-}
-
-// ---------------------------------------------------------------------------
-// MultiCameraFrame::UndistortKeyPoints (MultiCameraFrame.cpp:300-347): cv::undistortPoints of every selected keypoint, one lane
-// per keypoint (mcorb_undistort.h).  pt is rebuilt from the packed selection exactly as the host's keypoint records are
-// ((float)x, times the float scale factor above level 0); image m belongs to camera m % ncams.  fp64 throughout, no contraction
-// (-ffp-contract=off): bit-equal to the host restatement.
-// ---------------------------------------------------------------------------
-struct UndistScales { float s[kMaxLevels]; };
-
-// pt of a selected keypoint from its packed selection word (level, x, y of the level), as the host's keypoint records build it:
-// (float)x, (float)y, times the float scale factor above level 0
-__device__ __forceinline__ float2 sel_point(uint32_t v, const UndistScales &sc)
-{
-    const int l = (int)(v >> 28), yl = (int)((v >> 14) & 0x3fffu), xl = (int)(v & 0x3fffu);
-    float x = (float)xl, y = (float)yl;
-    if (l != 0) { x *= sc.s[l]; y *= sc.s[l]; }
-    return make_float2(x, y);
-}
-
-__global__ __launch_bounds__(256) void k_undistort(const uint32_t *__restrict__ sel, const int *__restrict__ nsel, int kcap, int ncams,
-                                                   const UndistCam *__restrict__ cams, UndistScales sc, float2 *__restrict__ out)
-{
-    const int m = blockIdx.y, k = blockIdx.x * 256 + threadIdx.x;
-    const int n = min(nsel[m], kcap);
-    if (k >= n) return;
-    const float2 p = sel_point(sel[(size_t)m * kcap + k], sc);
-    float ox, oy;
-    undistort_point(cams[m % ncams], p.x, p.y, ox, oy);
-    out[(size_t)m * kcap + k] = make_float2(ox, oy);
-}
-
-void launch_undistort(hipStream_t st, const uint32_t *sel, const int *nsel, int kcap, int nimg, int ncams, const UndistCam *cams,
-                      const float *scale, int nlevels, float2 *out)
-{
-    UndistScales sc = {};
-    for (int l = 0; l < nlevels && l < kMaxLevels; l++) sc.s[l] = scale[l];
-    hipLaunchKernelGGL(k_undistort, dim3((kcap + 255) / 256, nimg), dim3(256), 0, st, sel, nsel, kcap, ncams, cams, sc, out);
-}
-
 // ---------------------------------------------------------------------------
 // launch wrappers
 // ---------------------------------------------------------------------------
 hipError_t upload_umax(const int umax[16]) { return hipMemcpyToSymbol(HIP_SYMBOL(c_umax), umax, 16 * sizeof(int)); }
-
-void launch_stage_f32(hipStream_t st, const float *src, int w, int h, int pitch_f, int channels, size_t img_stride_f,
-                      uint8_t *pyr, const Geom &g, int nimg)
-{
-    dim3 grid((w + 255) / 256, h, nimg);
-    hipLaunchKernelGGL(k_stage_f32, grid, dim3(256), 0, st, src, w, h, pitch_f, channels, img_stride_f, pyr, g);
-}
-
-void launch_stage_f32_raw(hipStream_t st, const float *src, int w, int h, int pitch_f, int channels, size_t img_stride_f,
-                          uint8_t *raw, int nimg)
-{
-    dim3 grid((w + 255) / 256, h, nimg);
-    hipLaunchKernelGGL(k_stage_f32_raw, grid, dim3(256), 0, st, src, w, h, pitch_f, channels, img_stride_f, raw);
-}
-
-void launch_remap_u8(hipStream_t st, const uint8_t *raw, uint8_t *pyr, const Geom &g, const RemapCam *cams, int ncams, int nimg)
-{
-    const int w = g.lv[0].w, h = g.lv[0].h, wq = remap_map_pitch(w) / 4;
-    dim3 grid((wq * h + 255) / 256, ncams < nimg ? ncams : nimg);
-    hipLaunchKernelGGL(k_remap_u8, grid, dim3(256), 0, st, raw, pyr, cams, ncams, nimg, w, h, wq, g.imgBytes, g.lv[0].off, g.lv[0].pitch);
-}
 
 void launch_pyramid(hipStream_t st, uint8_t *pyr, const Geom &g, const ResizeTap *tabs, const int *win, int nimg)
 {
@@ -2085,9 +1724,8 @@ void launch_pyramid(hipStream_t st, uint8_t *pyr, const Geom &g, const ResizeTap
         const int srcPitch = win[2 * l], srcRows = win[2 * l + 1];   // LDS window, sized on the host from the tables
         const int chunks = (srcPitch >> 4) * srcRows, nf = (chunks + 255) / 256;   // 16-byte loads per thread to fill the window
         const size_t lds = (size_t)srcPitch * srcRows + 16;   // + the spare chunk idle fill lanes write
-        if (nf <= 4) hipLaunchKernelGGL(k_resize<4>, grid, dim3(256), lds, st, pyr, g, l, tabs, srcPitch, srcRows);
-        else if (nf <= 8) hipLaunchKernelGGL(k_resize<8>, grid, dim3(256), lds, st, pyr, g, l, tabs, srcPitch, srcRows);
-        else hipLaunchKernelGGL(k_resize<0>, grid, dim3(256), lds, st, pyr, g, l, tabs, srcPitch, srcRows);
+        const auto kern = nf <= 4 ? k_resize<4> : nf <= 8 ? k_resize<8> : k_resize<0>;
+        hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, pyr, g, l, tabs, srcPitch, srcRows);
     }
 }
 
@@ -2110,25 +1748,20 @@ void launch_fast(hipStream_t st, const uint8_t *pyr, const Geom &g, int iniTh, i
     // LDS per wave: the tile, the score map (four rows fewer), the bounded survivor list
     int tp, rows;
     fast_layout(g, tp, rows);
-    static const int cap_env = getenv("MCORB_FAST_LISTCAP") ? atoi(getenv("MCORB_FAST_LISTCAP")) : 0;   // tuning knob; any multiple of 8 >= 512 is safe
-    const int cap = cap_env >= 512 ? (cap_env & ~7) : kFastListCap;
+    const int cap = kFastListCap;
     const int tileB = (rows * tp + 15) & ~15, scB = ((rows - 4) * tp + 15) & ~15;
-    // MCORB_FAST_LDS_PAD (experiment): extra bytes per one-wave workgroup -- 29 waves of 5.4 KiB fill a CU's
-    // 160 KiB, so no other kernel's workgroup fits beside them; padded to 6.6 KiB there are 24 and 32 KiB stay free
-    static const int pad_env = getenv("MCORB_FAST_LDS_PAD") ? atoi(getenv("MCORB_FAST_LDS_PAD")) : 0;
-    const size_t lds = 16 + (size_t)tileB + 16 + (size_t)scB + 16 + (size_t)cap * 2 + (size_t)(pad_env > 0 ? (pad_env & ~15) : 0);
+    const size_t lds = 16 + (size_t)tileB + 16 + (size_t)scB + 16 + (size_t)cap * 2;
     dim3 grid(g.cells, nimg);
     if (iniTh < 0) iniTh = 0;   // (pass 1's sign tests rely on thresholds in 0 .. 255; FAST thresholds are)
     if (minTh < 0) minTh = 0;
     if (iniTh > 255) iniTh = 255;   // no pixel passes at 255 or above either way
     if (minTh > 255) minTh = 255;
-    if (tp == 48) hipLaunchKernelGGL(k_fast_cells<48>, grid, dim3(64), lds, st, pyr, g, iniTh, minTh, tileB, scB, cap, cellRec, cell_kp, cell_cnt);
-    else if (tp == 64) hipLaunchKernelGGL(k_fast_cells<64>, grid, dim3(64), lds, st, pyr, g, iniTh, minTh, tileB, scB, cap, cellRec, cell_kp, cell_cnt);
-    else hipLaunchKernelGGL(k_fast_cells<80>, grid, dim3(64), lds, st, pyr, g, iniTh, minTh, tileB, scB, cap, cellRec, cell_kp, cell_cnt);
+    const auto kern = tp == 48 ? k_fast_cells<48> : tp == 64 ? k_fast_cells<64> : k_fast_cells<80>;
+    hipLaunchKernelGGL(kern, grid, dim3(64), lds, st, pyr, g, iniTh, minTh, tileB, scB, cap, cellRec, cell_kp, cell_cnt);
 }
 
 void launch_compact(hipStream_t st, const uint32_t *cell_kp, const int *cell_cnt, const Geom &g, const uint16_t *lut,
-                    uint32_t *sorted_dev, uint32_t *cand, int *tbl, int *overflow, int nimg)
+                    uint32_t *sorted_dev, uint32_t *cand, int *tbl, int *overflow, int nimg, bool one_copy)
 {
     int maxb = 1, maxc = 1, maxwh = 2;
     for (int l = 0; l < g.nlevels; l++) {
@@ -2138,25 +1771,19 @@ void launch_compact(hipStream_t st, const uint32_t *cell_kp, const int *cell_cnt
         maxwh = maxwh > wh ? maxwh : wh;
     }
     const int bktCap = (maxb + 1 + 3) & ~3;
-    static const int wg_env = getenv("MCORB_COMPACT_WG") ? atoi(getenv("MCORB_COMPACT_WG")) : 0;
-    static const int cells_env = getenv("MCORB_COMPACT_CELLS") ? atoi(getenv("MCORB_COMPACT_CELLS")) : 0;
     // 512 threads per (level, image) workgroup and four cells per group for a full batch (1024 threads: 42 against 39.5 us per
     // 128 images; two cells: 45.6; eight cells need more than 64 registers, which halves the resident workgroups); a small
     // batch is the latency of its level-0 workgroup, shorter with 1024 threads
-    const int wg = wg_env == 1024 || wg_env == 512 ? wg_env : (nimg <= 8 ? 1024 : 512), cellsInFlight = cells_env == 2 ? 2 : 4;
+    const int wg = nimg <= 8 ? 1024 : 512;
     const int cellsCap = (maxc + 8 + 7) & ~7;   // u16 entries, a multiple of 8
     const size_t ldsTail = (size_t)(cellsCap + maxwh + 8) * sizeof(uint16_t);
     const bool fits = (size_t)(2 * kCompactCopies * bktCap) * sizeof(int) + ldsTail <= 64 * 1024;
-    static const bool one_env = getenv("MCORB_COMPACT_ONE_COPY") != nullptr;   // (test / comparison knob)
-    const int copies = fits && !one_env ? kCompactCopies : 1;
+    const int copies = fits && !one_copy ? kCompactCopies : 1;
     const size_t lds = (size_t)(2 * copies * bktCap) * sizeof(int) + ldsTail;
     const dim3 grid(nimg, g.nlevels);
-#define MCORB_COMPACT_LAUNCH(WG_, C_) \
-    do { if (copies == 1) hipLaunchKernelGGL((k_compact<WG_, C_, 1>), grid, dim3(WG_), lds, st, cell_kp, cell_cnt, g, lut, sorted_dev, cand, tbl, overflow, bktCap, cellsCap); \
-         else hipLaunchKernelGGL((k_compact<WG_, C_, kCompactCopies>), grid, dim3(WG_), lds, st, cell_kp, cell_cnt, g, lut, sorted_dev, cand, tbl, overflow, bktCap, cellsCap); } while (0)
-    if (wg == 1024) { if (cellsInFlight == 2) MCORB_COMPACT_LAUNCH(1024, 2); else MCORB_COMPACT_LAUNCH(1024, 4); }
-    else { if (cellsInFlight == 2) MCORB_COMPACT_LAUNCH(512, 2); else MCORB_COMPACT_LAUNCH(512, 4); }
-#undef MCORB_COMPACT_LAUNCH
+    const auto kern = wg == 1024 ? (copies == 1 ? k_compact<1024, 4, 1> : k_compact<1024, 4, kCompactCopies>)
+                                 : (copies == 1 ? k_compact<512, 4, 1> : k_compact<512, 4, kCompactCopies>);
+    hipLaunchKernelGGL(kern, grid, dim3(wg), lds, st, cell_kp, cell_cnt, g, lut, sorted_dev, cand, tbl, overflow, bktCap, cellsCap);
 }
 
 void launch_blur(hipStream_t st, const uint8_t *pyr, uint8_t *blur, const Geom &g, int nimg)
@@ -2188,7 +1815,7 @@ void launch_knn2(hipStream_t st, const uint8_t *desc, const int *counts, const i
     const int chunkLen = knn_chunk_len(npairs), nchunks = (kcap + chunkLen - 1) / chunkLen;
     const int qblocks = knn_qblocks(kcap), units = npairs * nchunks;
     dim3 grid(8 * qblocks * ((units + 7) / 8));
-    // 130 VGPRs: 3 waves per SIMD.  (Capping at 128 for 4 waves spills one query fragment into scratch: 177 vs 162 us.)
+    // 151 / 149 VGPRs (folded / partials): 3 waves per SIMD.  (Capping at 128 for 4 waves spills one query fragment into scratch: 177 vs 162 us.)
     if (nchunks == 1) {
         hipLaunchKernelGGL((k_knn2<4, 3, true>), grid, dim3(64 * kKnnWaves), 0, st, E, lcounts, pairs, kcap, nchunks, npairs, qblocks, part, chunkLen,
                            dist_thresh, ratio, out, mlist, mcount);
@@ -2200,266 +1827,5 @@ void launch_knn2(hipStream_t st, const uint8_t *desc, const int *counts, const i
     if (ev_mid) (void)hipEventRecord(ev_mid, st);
     hipLaunchKernelGGL(k_knn2_finalize, dim3(npairs), dim3(1024), 0, st, part, lcounts, pairs, kcap, nchunks, chunkLen, dist_thresh, ratio, out, mlist,
                        mcount, qblocks);
-}
-
-void launch_bow_best2(hipStream_t st, const uint8_t *desc, int img0, int kcap, int ncams, int nframes, const float *yv,
-                      const int *slot_of, const int2 *node_range, const int *rg_base, const int *node_feats, const int *nfeat, int4 *out)
-{
-    if (ncams < 2 || nframes < 1) return;
-    dim3 grid((kcap + 255) / 256, ncams * (ncams - 1) / 2, nframes);
-    hipLaunchKernelGGL(k_bow_best2, grid, dim3(256), 0, st, desc, img0, kcap, ncams, yv, slot_of, node_range, rg_base, node_feats, nfeat, out);
-}
-
-void launch_bow_descend(hipStream_t st, const uint8_t *desc, int n, const int *child_start, const int *child_count,
-                        const void *child_desc, const int *child_id, const int *word_id, const double *weight, int nid_level,
-                        BowRes *out)
-{
-    if (n <= 0) return;
-    hipLaunchKernelGGL(k_bow_descend, dim3((n + 255) / 256), dim3(256), 0, st, desc, n, child_start, child_count,
-                       reinterpret_cast<const ulonglong4 *>(child_desc), child_id, word_id, weight, nid_level, out);
-}
-
-
-// ---------------------------------------------------------------------------
-// transform()'s order-defined half inside the extraction job (mcorb_rig_set_vocabulary): k_bow_fold turns one image's descent
-// results into its FeatureVector and BowVector exactly as the host's assemble() does (mcorb_bow.cpp), k_bow_tables turns one
-// frame's FeatureVectors into the index tables k_bow_best2 reads (node_feats: the feature lists, kcap-strided).  Nothing crosses to the host in between.
-// ---------------------------------------------------------------------------
-constexpr int kFoldT = 512;
-static_assert(kBowFoldMaxKcap % kFoldT == 0, "k_bow_fold: whole keys per lane");
-
-// ascending bitonic sort of K[0, N), N a power of two, by the whole workgroup
-__device__ void fold_sort(uint64_t *K, int N)
-{
-    for (int k = 2; k <= N; k <<= 1)
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int i = threadIdx.x; i < N; i += kFoldT) {
-                const int ixj = i ^ j;
-                if (ixj > i) {
-                    const uint64_t a = K[i], b = K[ixj];
-                    if ((a > b) == ((i & k) == 0)) { K[i] = b; K[ixj] = a; }
-                }
-            }
-            __syncthreads();
-        }
-}
-
-// exclusive prefix sum of one value per lane over the workgroup; *total = the sum
-__device__ int fold_scan(int v, int *sh, int *total)
-{
-    const int t = threadIdx.x;
-    sh[t] = v;
-    __syncthreads();
-    for (int o = 1; o < kFoldT; o <<= 1) {
-        const int x = t >= o ? sh[t - o] : 0;
-        __syncthreads();
-        sh[t] += x;
-        __syncthreads();
-    }
-    const int incl = sh[t];
-    *total = sh[kFoldT - 1];
-    __syncthreads();
-    return incl - v;
-}
-
-// runs of equal high words in the sorted keys K[0, m): heads[0, nruns) = their first positions, ascending; heads[nruns] = m
-__device__ int fold_runs(const uint64_t *K, int m, int *heads, int *sh)
-{
-    const int t = threadIdx.x, chunk = (m + kFoldT - 1) / kFoldT;
-    const int p0 = min(m, t * chunk), p1 = min(m, p0 + chunk);
-    int c = 0;
-    for (int p = p0; p < p1; p++) c += p == 0 || (K[p] >> 32) != (K[p - 1] >> 32);
-    int total = 0;
-    int j = fold_scan(c, sh, &total);
-    for (int p = p0; p < p1; p++)
-        if (p == 0 || (K[p] >> 32) != (K[p - 1] >> 32)) heads[j++] = p;
-    if (t == 0) heads[total] = m;
-    __syncthreads();
-    return total;
-}
-
-// One workgroup per image.  Stable sorts are sorts of (key << 32 | feature index): unique keys, so any sort is stable.  Each word's
-// run is folded left to right by one lane and the norm is one lane's sum over the words in ascending order: the host's additions in
-// the host's order (no contraction, correctly rounded '/' and sqrt), so the doubles are bit-equal.
-__global__ __launch_bounds__(kFoldT) void k_bow_fold(const BowRes *__restrict__ res, const int *__restrict__ nsel, int kcap, int weighting,
-                                                     int scoring, int *__restrict__ out_dev, int *__restrict__ out_host)
-{
-    __shared__ uint64_t K[kBowFoldMaxKcap];
-    __shared__ int heads[kBowFoldMaxKcap + 1];
-    __shared__ int sh[kFoldT];
-    __shared__ int nvalid;
-    __shared__ double norm_sh;
-    const int m = blockIdx.x, t = threadIdx.x;
-    const int n = min(nsel[m], kcap);
-    const BowRes *r = res + (size_t)m * kcap;
-    int N = 1;
-    while (N < n) N <<= 1;
-    const BowRecView od = bow_rec(out_dev, kcap, m);
-    const BowRecView oh = bow_rec(out_host ? out_host : out_dev, kcap, m);
-    const bool both = out_host != nullptr;
-    // FeatureVector: the non-stopped features by node id, feature order within a node
-    if (t == 0) nvalid = 0;
-    __syncthreads();
-    for (int i = t; i < N; i += kFoldT) {
-        uint64_t k = ~0ull;
-        if (i < n && r[i].weight > 0) { k = ((uint64_t)(uint32_t)r[i].nodeup << 32) | (uint32_t)i; atomicAdd(&nvalid, 1); }
-        K[i] = k;
-    }
-    __syncthreads();
-    const int nv = nvalid;
-    fold_sort(K, N);
-    const int nfv = fold_runs(K, nv, heads, sh);
-    for (int j = t; j <= nfv; j += kFoldT) {
-        const int h = heads[j];
-        od.offs[j] = h;
-        if (both) oh.offs[j] = h;
-        if (j < nfv) {
-            const uint32_t node = (uint32_t)(K[h] >> 32);
-            od.nodes[j] = node;
-            if (both) oh.nodes[j] = node;
-        }
-    }
-    for (int p = t; p < nv; p += kFoldT) {
-        const int fi = (int)(uint32_t)K[p];
-        od.feats[p] = fi;
-        if (both) oh.feats[p] = fi;
-    }
-    __syncthreads();
-    // BowVector: the same features by word id, each word's weights folded in feature order
-    for (int i = t; i < N; i += kFoldT)
-        K[i] = i < n && r[i].weight > 0 ? ((uint64_t)(uint32_t)r[i].word << 32) | (uint32_t)i : ~0ull;
-    __syncthreads();
-    fold_sort(K, N);
-    const int nbow = fold_runs(K, nv, heads, sh);
-    const bool tf_like = weighting == 0 || weighting == 1;   // TF_IDF, TF accumulate; IDF, BINARY keep the first
-    constexpr int kPer = kBowFoldMaxKcap / kFoldT;
-    double v[kPer];
-#pragma unroll
-    for (int q = 0; q < kPer; q++) {
-        const int j = t + q * kFoldT;
-        v[q] = 0.0;
-        if (j < nbow) {
-            const int p = heads[j], e = heads[j + 1];
-            const uint32_t word = (uint32_t)(K[p] >> 32);
-            od.ids[j] = word;
-            if (both) oh.ids[j] = word;
-            double s = r[(uint32_t)K[p]].weight;
-            if (tf_like)
-                for (int x = p + 1; x < e; x++) s += r[(uint32_t)K[x]].weight;
-            v[q] = s;
-        }
-    }
-    __syncthreads();   // K is free: the values take its place
-    double *V = reinterpret_cast<double *>(K);
-#pragma unroll
-    for (int q = 0; q < kPer; q++)
-        if (t + q * kFoldT < nbow) V[t + q * kFoldT] = v[q];
-    __syncthreads();
-    const bool must = scoring != 5;   // L1_NORM, CHI_SQUARE, KL, BHATTACHARYYA -> L1; L2_NORM -> L2; DOT_PRODUCT -> none
-    if (must) {
-        if (t == 0) {
-            double s = 0.0;
-            if (scoring == 1) {
-                for (int j = 0; j < nbow; j++) s += V[j] * V[j];
-                s = sqrt(s);
-            } else {
-                for (int j = 0; j < nbow; j++) s += fabs(V[j]);
-            }
-            norm_sh = s;
-        }
-        __syncthreads();
-    }
-    const double norm = must ? norm_sh : 0.0, nd = (double)nbow;
-    for (int j = t; j < nbow; j += kFoldT) {
-        double x = V[j];
-        if (tf_like && !must) x /= nd;
-        if (must && norm > 0.0) x /= norm;
-        od.vals[j] = x;
-        if (both) oh.vals[j] = x;
-    }
-    if (t == 0) {
-        od.cnt[0] = nbow; od.cnt[1] = nfv; od.cnt[2] = nv; od.cnt[3] = 0;
-        if (both) { oh.cnt[0] = nbow; oh.cnt[1] = nfv; oh.cnt[2] = nv; oh.cnt[3] = 0; }
-    }
-}
-
-// binary search of `node` in the ascending list a[0, n): its index, or -1
-__device__ __forceinline__ int fv_find(const uint32_t *a, int n, uint32_t node)
-{
-    int lo = 0, hi = n;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (a[mid] < node) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo < n && a[lo] == node ? lo : -1;
-}
-
-// One workgroup per frame: the tables of k_bow_best2 from the frame's FeatureVectors (k_bow_fold's device records).  A node's slot
-// is (first camera holding it) * kcap + its index there: unique per node, the same for every camera, fewer than ncams * kcap per
-// frame (rg_base[f] = f * ncams * kcap).  Only the slots that exist are written; k_bow_best2 reads no other.  yv: the rows of the
-// |dy| < 50 gate, the undistorted points' y when undist is given, else the keypoint records' y rebuilt from sel.
-__global__ __launch_bounds__(256) void k_bow_tables(const int *__restrict__ fold, int kcap, int ncams, const int *__restrict__ nsel,
-                                                    const uint32_t *__restrict__ sel, UndistScales sc, const float2 *__restrict__ undist,
-                                                    int *__restrict__ slot_of, int *__restrict__ node_feats, int *__restrict__ nfeat,
-                                                    int *__restrict__ rg_base, float *__restrict__ yv, int2 *__restrict__ node_range)
-{
-    const int f = blockIdx.x, t = threadIdx.x, C = ncams;
-    const size_t base = (size_t)f * C * kcap;
-    for (int c = 0; c < C; c++) {
-        const int m = f * C + c, n = min(nsel[m], kcap);
-        for (int k = t; k < n; k += 256) {
-            const size_t i = (size_t)m * kcap + k;
-            slot_of[i] = -1;
-            yv[i] = undist ? undist[i].y : sel_point(sel[i], sc).y;
-        }
-        if (t == 0) nfeat[m] = n;
-    }
-    if (t == 0) rg_base[f] = (int)base;
-    __syncthreads();
-    for (int c = 0; c < C; c++) {
-        const int m = f * C + c;
-        const BowRecView a = bow_rec(const_cast<int *>(fold), kcap, m);
-        const int nfv = a.cnt[1];
-        for (int e = t; e < nfv; e += 256) {
-            const uint32_t node = a.nodes[e];
-            int oc = c, oe = e;
-            for (int c2 = 0; c2 < c; c2++) {
-                const BowRecView b = bow_rec(const_cast<int *>(fold), kcap, f * C + c2);
-                const int i = fv_find(b.nodes, b.cnt[1], node);
-                if (i >= 0) { oc = c2; oe = i; break; }
-            }
-            const int slot = oc * kcap + oe;
-            const int beg = a.offs[e], end = a.offs[e + 1];
-            for (int p = beg; p < end; p++) {
-                node_feats[(size_t)m * kcap + p] = a.feats[p];
-                slot_of[(size_t)m * kcap + a.feats[p]] = slot;
-            }
-            if (oc != c) continue;   // the slot's ranges are written by its first camera
-            int2 *rg = node_range + (base + slot) * C;
-            for (int c2 = 0; c2 < C; c2++) {
-                if (c2 == c) { rg[c2] = make_int2(beg, end - beg); continue; }
-                const BowRecView b = bow_rec(const_cast<int *>(fold), kcap, f * C + c2);
-                const int i = c2 < c ? -1 : fv_find(b.nodes, b.cnt[1], node);
-                rg[c2] = i < 0 ? make_int2(0, 0) : make_int2(b.offs[i], b.offs[i + 1] - b.offs[i]);
-            }
-        }
-    }
-}
-
-void launch_bow_fold(hipStream_t st, const BowRes *res, const int *nsel, int kcap, int nimg, int weighting, int scoring, int *out_dev,
-                     int *out_host)
-{
-    hipLaunchKernelGGL(k_bow_fold, dim3(nimg), dim3(kFoldT), 0, st, res, nsel, kcap, weighting, scoring, out_dev, out_host);
-}
-
-void launch_bow_tables(hipStream_t st, const int *fold, int kcap, int ncams, int nframes, const int *nsel, const uint32_t *sel,
-                       const float *scale, int nlevels, const float2 *undist, int *slot_of, int *node_feats, int *nfeat, int *rg_base,
-                       float *yv, int2 *node_range)
-{
-    UndistScales sc = {};
-    for (int l = 0; l < nlevels && l < kMaxLevels; l++) sc.s[l] = scale[l];
-    hipLaunchKernelGGL(k_bow_tables, dim3(nframes), dim3(256), 0, st, fold, kcap, ncams, nsel, sel, sc, undist, slot_of, node_feats, nfeat,
-                       rg_base, yv, node_range);
 }
 }  // namespace mcorb

@@ -21,9 +21,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
-#include <stdlib.h>
 
 #include "mcorb_common.h"
+#include "mcorb_device.h"
 #include "mcorb_hip.h"
 #include "mcorb_kernels.h"
 #include "mcorb_sortmodel.h"
@@ -32,24 +32,12 @@ namespace mcorb {
 
 namespace {
 
-__device__ __forceinline__ int sel_lane() { return threadIdx.x & 63; }
-__device__ __forceinline__ int sel_rank(unsigned long long mask, int acc = 0)
-{
-    return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, (uint32_t)acc));
-}
-__device__ __forceinline__ void sel_sync()   // LDS written by some lanes of this wave, read by others
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
-__device__ __forceinline__ int sel_uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
 // inclusive prefix sum over the wave for values 0 .. 7 (children per node): three ballots, no cross-lane traffic; tot = the wave's sum
 __device__ __forceinline__ int sel_scan3(int v, int &tot)
 {
     const unsigned long long b0 = __ballot(v & 1), b1 = __ballot(v & 2), b2 = __ballot(v & 4);
     tot = __popcll(b0) + 2 * __popcll(b1) + 4 * __popcll(b2);
-    return sel_rank(b0) + 2 * sel_rank(b1) + 4 * sel_rank(b2) + v;
+    return lane_rank(b0) + 2 * lane_rank(b1) + 4 * lane_rank(b2) + v;
 }
 
 // a tree node: x = path code (root index, then 2 bits per split) | depth << 28, y = UL.x | UR.x << 16 (level coordinates relative
@@ -177,20 +165,20 @@ __host__ __device__ inline size_t sel_lds_bytes(int B, int cap) { return (size_t
 // std::sort(a, a + n) on the upper halves, libstdc++'s permutation (mcorb_sortmodel.h); the result is in `out`
 __device__ void wave_std_sort(uint64_t *a, int n, uint64_t *out, SelLds &S)
 {
-    const int lane = sel_lane();
+    const int lane = lane_id();
     uint16_t *lp = S.ta, *rp = S.tb;
     if (n <= 0) return;
     int sp = 0;
     if (lane == 0) { S.stk[0] = 0; S.stk[1] = n; S.stk[2] = 2 * sm_lg(n); }
     sp = 1;
-    sel_sync();
+    wave_lds_sync();
     while (sp > 0) {
         sp--;
-        int f = sel_uni(S.stk[3 * sp]), l = sel_uni(S.stk[3 * sp + 1]), dl = sel_uni(S.stk[3 * sp + 2]);
+        int f = wave_uniform(S.stk[3 * sp]), l = wave_uniform(S.stk[3 * sp + 1]), dl = wave_uniform(S.stk[3 * sp + 2]);
         while (l - f > 16) {
             if (dl == 0) {   // depth budget used up: heap sort, one lane (rare: median-of-three killers)
                 if (lane == 0) sm_heap_sort(a, f, l);
-                sel_sync();
+                wave_lds_sync();
                 break;
             }
             dl--;
@@ -198,7 +186,7 @@ __device__ void wave_std_sort(uint64_t *a, int n, uint64_t *out, SelLds &S)
             const uint32_t ka = sm_key(a[f + 1]), kb = sm_key(a[mid]), kc = sm_key(a[l - 1]);
             const int mi = sm_median3(ka, kb, kc, f + 1, mid, l - 1);
             if (lane == 0) { const uint64_t t = a[f]; a[f] = a[mi]; a[mi] = t; }
-            sel_sync();
+            wave_lds_sync();
             const uint32_t p = mi == f + 1 ? ka : (mi == mid ? kb : kc);   // = key(a[f]) after the swap
             if (l - f - 1 <= 64) {
                 // the range fits the wave: one position per lane, one read; lane j learns L_j (ascending) and R_j (descending)
@@ -210,7 +198,7 @@ __device__ void wave_std_sort(uint64_t *a, int n, uint64_t *out, SelLds &S)
                 const bool isL = in && !(k < p), isR = in && !(p < k);
                 const unsigned long long bl = __ballot(isL), br = __ballot(isR);
                 const int nL = __popcll(bl), nR = __popcll(br);
-                const int below = sel_rank(bl);                                            // L lanes below this one
+                const int below = lane_rank(bl);                                            // L lanes below this one
                 const int above = __popcll(lane == 63 ? 0ull : br >> (lane + 1));          // R lanes above this one
                 const int Lj = __builtin_amdgcn_ds_permute((isL ? below : nL + (lane - below)) << 2, i);
                 const int Rj = __builtin_amdgcn_ds_permute((isR ? above : nR + (63 - lane - above)) << 2, i);
@@ -225,7 +213,7 @@ __device__ void wave_std_sort(uint64_t *a, int n, uint64_t *out, SelLds &S)
                 if (lane == 0) { S.stk[3 * sp] = cut; S.stk[3 * sp + 1] = l; S.stk[3 * sp + 2] = dl; }
                 sp++;
                 l = cut;
-                sel_sync();
+                wave_lds_sync();
                 continue;
             }
             // L: positions of (f, l) with key >= p, ascending; R: positions with key <= p, descending
@@ -234,17 +222,17 @@ __device__ void wave_std_sort(uint64_t *a, int n, uint64_t *out, SelLds &S)
                 const int i = c0 + lane;
                 const bool isL = i < l && !(sm_key(a[min(i, l - 1)]) < p);
                 const unsigned long long b = __ballot(isL);
-                if (isL) lp[sel_rank(b, nL)] = (uint16_t)i;
+                if (isL) lp[lane_rank(b, nL)] = (uint16_t)i;
                 nL += __popcll(b);
             }
             for (int c0 = 0; c0 < l - f - 1; c0 += 64) {
                 const int i = l - 1 - (c0 + lane);
                 const bool isR = i > f && !(p < sm_key(a[max(i, f + 1)]));
                 const unsigned long long b = __ballot(isR);
-                if (isR) rp[sel_rank(b, nR)] = (uint16_t)i;
+                if (isR) rp[lane_rank(b, nR)] = (uint16_t)i;
                 nR += __popcll(b);
             }
-            sel_sync();
+            wave_lds_sync();
             const int m = min(nL, nR);
             int s = 0;
             for (int c0 = 0; c0 < m; c0 += 64) {   // the swapped pairs are a prefix: L ascends, R descends
@@ -267,11 +255,11 @@ __device__ void wave_std_sort(uint64_t *a, int n, uint64_t *out, SelLds &S)
             if (lane == 0) { S.stk[3 * sp] = cut; S.stk[3 * sp + 1] = l; S.stk[3 * sp + 2] = dl; }
             sp++;
             l = cut;
-            sel_sync();
+            wave_lds_sync();
         }
         for (int t = lane; t < l - f; t += 64) S.blk[f + t] = (uint32_t)f | ((uint32_t)l << 16);
     }
-    sel_sync();
+    wave_lds_sync();
     // __final_insertion_sort = stable rank inside each block
     for (int i = lane; i < n; i += 64) {
         const uint32_t b = S.blk[i];
@@ -285,13 +273,13 @@ __device__ void wave_std_sort(uint64_t *a, int n, uint64_t *out, SelLds &S)
         }
         out[bf + r] = e;
     }
-    sel_sync();
+    wave_lds_sync();
 }
 
 // one full pass over the list (:615-678); returns the new length, m = nodes that can be divided again (nToExpand)
 __device__ int full_pass(const SelLds &S, const SelCtx &C, const SelNode *in, int n, SelNode *out, uint64_t *exp, int cap, int &m, int &fb)
 {
-    const int lane = sel_lane();
+    const int lane = lane_id();
     uint16_t *info = S.ta;
     int H = 0, bad = 0, singles = 0;
     for (int c0 = 0; c0 < n; c0 += 64) {
@@ -315,7 +303,7 @@ __device__ int full_pass(const SelLds &S, const SelCtx &C, const SelNode *in, in
         singles += __popcll(__ballot(!(inf & 0x100u)));
     }
     if (__ballot(bad != 0) != 0ull || H + singles > cap) { fb = 1; m = 0; return n; }
-    sel_sync();
+    wave_lds_sync();
     int crun = 0, erun = 0, trun = 0;
     for (int c0 = 0; c0 < n; c0 += 64) {
         const int i = c0 + lane;
@@ -341,13 +329,13 @@ __device__ int full_pass(const SelLds &S, const SelCtx &C, const SelNode *in, in
                     exp[eexcl + __popc(emask & ((1u << q) - 1u))] = ((uint64_t)(((uint32_t)cnt[q] << 12) | (ch.y & 0xffffu)) << 32) | (uint32_t)pos;
             }
         } else if (single) {
-            out[H + sel_rank(bs, trun)] = in[i];
+            out[H + lane_rank(bs, trun)] = in[i];
         }
         crun += ctot;
         erun += etot;
         trun += __popcll(bs);
     }
-    sel_sync();
+    wave_lds_sync();
     m = erun;
     return H + trun;
 }
@@ -356,7 +344,7 @@ __device__ int full_pass(const SelLds &S, const SelCtx &C, const SelNode *in, in
 __device__ int careful_round(const SelLds &S, const SelCtx &C, const SelNode *in, int n, SelNode *out, const uint64_t *srt, int m, uint64_t *exp, int N, int cap,
                              int &mOut, int &fb)
 {
-    const int lane = sel_lane();
+    const int lane = lane_id();
     uint16_t *divided = S.ta, *einfo = S.tb;   // per old list position: divided in this round; per entry (division order): summary
     for (int i = lane; i < n; i += 64) divided[i] = 0;
     // division order t = 0 .. m-1 is the sorted order from the back; k = how many divisions until the list holds N nodes
@@ -380,7 +368,7 @@ __device__ int careful_round(const SelLds &S, const SelCtx &C, const SelNode *in
         srun += itot - min(64, m - t0);
     }
     if (k < 0) k = m;
-    sel_sync();
+    wave_lds_sync();
     int Hc = 0, badk = 0;
     for (int t0 = 0; t0 < k; t0 += 64) {
         const int t = t0 + lane;
@@ -419,16 +407,16 @@ __device__ int careful_round(const SelLds &S, const SelCtx &C, const SelNode *in
         crun += ctot;
         erun += etot;
     }
-    sel_sync();
+    wave_lds_sync();
     int trun = 0;
     for (int c0 = 0; c0 < n; c0 += 64) {   // the nodes that were not divided keep their order behind the new children
         const int i = c0 + lane;
         const bool keep = i < n && divided[i] == 0;
         const unsigned long long b = __ballot(keep);
-        if (keep) out[Hc + sel_rank(b, trun)] = in[i];
+        if (keep) out[Hc + lane_rank(b, trun)] = in[i];
         trun += __popcll(b);
     }
-    sel_sync();
+    wave_lds_sync();
     mOut = erun;
     return Hc + trun;
 }
@@ -441,7 +429,7 @@ __global__ __launch_bounds__(64) void k_select(const int *__restrict__ tbl, cons
                                                int selcap, int ldsB, int ldsCap, int deepCap, int *__restrict__ fallback, unsigned long long *__restrict__ prof)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t sel_sh[];
-    const int lane = sel_lane();
+    const int lane = lane_id();
     const int img = blockIdx.x, level = blockIdx.y;
     int prof_i = 0;
     auto stamp = [&]() {   // (MCORB_SELECT_PROF: shader-clock stamps of image 0's waves at the phase boundaries)
@@ -495,7 +483,7 @@ __global__ __launch_bounds__(64) void k_select(const int *__restrict__ tbl, cons
         for (int b = lane; b <= B; b += 64) S.bst[b] = bsrc[b];
         for (int b = lane; b < B; b += 64) wdst[b] = wsrc[b];
     }
-    sel_sync();
+    wave_lds_sync();
     stamp();
     // root nodes (:567-600): empty ones are erased
     int n, m = 0, fb = 0, cur = 0;
@@ -510,10 +498,10 @@ __global__ __launch_bounds__(64) void k_select(const int *__restrict__ tbl, cons
             keep = nd.z > 0;
         }
         const unsigned long long b = __ballot(keep);
-        if (keep) S.list[0][sel_rank(b)] = nd;
+        if (keep) S.list[0][lane_rank(b)] = nd;
         n = __popcll(b);
     }
-    sel_sync();
+    wave_lds_sync();
     if (L.nIni > 64 || L.nIni < 1 || N + 8 > cap || C.maxDepth < D) fb = 1;
     bool finish = fb != 0;
     while (!finish) {
@@ -574,7 +562,7 @@ __global__ __launch_bounds__(64 * kMaxLevels) void k_assemble(const uint32_t *__
     // it give its first mono / stereo position
     __shared__ int s_cnt[kMaxLevels], s_st[kMaxLevels];
     __shared__ uint32_t s_chk[kMaxLevels];   // (its own array: a slow wave may still be reading s_st when a fast one gets here)
-    const int lane = sel_lane(), level = threadIdx.x >> 6, img = blockIdx.x;
+    const int lane = lane_id(), level = threadIdx.x >> 6, img = blockIdx.x;
     const int c = sel_cnt[(size_t)img * g.nlevels + level];
     const uint32_t *v = sel_val + ((size_t)img * g.nlevels + level) * selcap;
     const float sc = P.scale[level], lo = (float)P.lap0, hi = (float)P.lap1;
@@ -628,7 +616,7 @@ __global__ __launch_bounds__(64 * kMaxLevels) void k_assemble(const uint32_t *__
         const bool stereo = valid && is_stereo(cd);
         const unsigned long long bs = __ballot(stereo), bm = __ballot(valid && !stereo);
         if (valid) {
-            const int pos = stereo ? stereoIndex - sel_rank(bs) : monoIndex + sel_rank(bm);
+            const int pos = stereo ? stereoIndex - lane_rank(bs) : monoIndex + lane_rank(bm);
             const uint32_t ps = pack_sel(level, cand_x(cd) + kMinBorder, cand_y(cd) + kMinBorder);
             so[pos] = ps;
             ro[pos] = (uint8_t)cand_resp(cd);
@@ -686,7 +674,7 @@ bool select_fits(const Geom &g)
     return select_cap(g) <= 65535 && select_lds(g, B) <= 160 * 1024;
 }
 
-hipError_t launch_select(hipStream_t st, const int *tbl, const uint32_t *sorted, const Geom &g, uint32_t *sel_val, int *sel_cnt, int *fallback, int nimg, int deep_cap)
+hipError_t launch_select(hipStream_t st, const int *tbl, const uint32_t *sorted, const Geom &g, uint32_t *sel_val, int *sel_cnt, int *fallback, int nimg, int deep_cap, bool prof_on)
 {
     int B;
     const int cap = select_cap(g);
@@ -699,7 +687,6 @@ hipError_t launch_select(hipStream_t st, const int *tbl, const uint32_t *sorted,
         configured = lds;
     }
     static HostBuf<unsigned long long> prof;
-    static const bool prof_on = getenv("MCORB_SELECT_PROF") != nullptr;
     if (prof_on && !prof) (void)prof.alloc(kMaxLevels * 32, hipHostMallocMapped);
     if (prof_on && prof) {
         static int calls = 0;
@@ -741,10 +728,10 @@ __global__ __launch_bounds__(64) void k_sort_selftest(const uint64_t *__restrict
     S.ta = reinterpret_cast<uint16_t *>(p); p += (size_t)cap * 2;
     S.tb = reinterpret_cast<uint16_t *>(p); p += (size_t)cap * 2;
     S.stk = reinterpret_cast<int *>(p);
-    for (int i = sel_lane(); i < n; i += 64) S.exp[0][i] = in[i];
-    sel_sync();
+    for (int i = lane_id(); i < n; i += 64) S.exp[0][i] = in[i];
+    wave_lds_sync();
     wave_std_sort(S.exp[0], n, S.exp[1], S);
-    for (int i = sel_lane(); i < n; i += 64) out[i] = S.exp[1][i];
+    for (int i = lane_id(); i < n; i += 64) out[i] = S.exp[1][i];
 }
 
 hipError_t sort_selftest(const uint64_t *in_dev, int n, uint64_t *out_dev)

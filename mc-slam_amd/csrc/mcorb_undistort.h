@@ -1,5 +1,5 @@
 // mcorb_undistort.h -- MultiCameraFrame::UndistortKeyPoints (MCSlam/src/MultiCameraFrame.cpp:300-347) for one keypoint: the
-// arithmetic of cv::undistortPoints as the reference calls it.  No HIP dependency: k_undistort (mcorb_kernels.hip) and a plain
+// arithmetic of cv::undistortPoints as the reference calls it.  No HIP dependency: k_undistort (mcorb_handoff_gpu.hip) and a plain
 // g++ test (tests/cpp/test_undistort.cpp) include the same code.  Compile with -ffp-contract=off (the library's flag): every
 // product and sum below is one IEEE double operation in the order written, so device, host and a numpy restatement agree bit
 // for bit.

@@ -1,7 +1,7 @@
 // mcorb_undistort_image.h -- the RECTIFY branch of MultiCameraFrame::setData (MCSlam/src/MultiCameraFrame.cpp:123-136):
 // cv::undistort(img, undistImg, K, dist) on an 8-bit one-channel image, in its two halves.  (a) The fixed-point map, which depends
 // on the calibration alone: built once per camera on the host (its row loop is a serial sum).  (b) The resampling of one pixel,
-// remap(.., INTER_LINEAR, BORDER_CONSTANT): the hot path, shared by k_remap_u8 (mcorb_kernels.hip), the host form and a plain g++
+// remap(.., INTER_LINEAR, BORDER_CONSTANT): the hot path, shared by k_remap_u8 (mcorb_handoff_gpu.hip), the host form and a plain g++
 // test (tests/cpp/test_undistort_image.cpp).  No HIP dependency.  Compile with -ffp-contract=off (the library's flag): every
 // product and sum of the map is one IEEE double operation in the order written.
 // Restated from OpenCV 4.x (modules/calib3d/src/undistort.dispatch.cpp, undistort.simd.hpp, core/src/lapack.cpp) as recalled:

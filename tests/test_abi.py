@@ -61,6 +61,8 @@ def test_product_does_not_link_or_import_the_oracle():
         if fn.endswith((".cpp", ".hip", ".h", ".c")):
             txt = open(os.path.join(ROOT, "mc-slam_amd", "csrc", fn)).read()
             assert "mcorb_oracle" not in txt and "orc_" not in txt, fn
+            # a launch wrapper reads no environment: a knob is read once where the rig is created and handed down as an argument
+            assert not fn.endswith(".hip") or "getenv" not in txt, fn
 
 
 def test_param_struct_layout_and_defaults():

@@ -130,6 +130,33 @@ def test_plane_based_descriptor_path_equals_fused(mc, monkeypatch):
         assert np.array_equal(a, b)
 
 
+@pytest.mark.parametrize("C,F", [(2, 1), (3, 3)], ids=["2img_wg1024", "9img_wg512"])
+def test_compact_one_table_copy_equals_four(mc, monkeypatch, C, F):
+    """MCORB_COMPACT_ONE_COPY=1 at rig creation makes k_compact keep ONE copy of its bucket tables in LDS (the form that
+    geometries whose four copies do not fit 64 KiB take) where this geometry's default is four.  The knob belongs to the rig, so
+    the two rigs of one process differ in nothing else.  Every level's candidates and every image's features must be the
+    same bit for bit, at both workgroup sizes: up to 8 images per job run 1024 threads, more run 512."""
+    W, H, N = 640, 480, 1000
+    imgs = [mc.synth_rig_frame(f, C, c, W, H) for f in range(F) for c in range(C)]
+    got = []
+    for one_copy in (True, False):
+        if one_copy:
+            monkeypatch.setenv("MCORB_COMPACT_ONE_COPY", "1")
+        else:
+            monkeypatch.delenv("MCORB_COMPACT_ONE_COPY")
+        rig = mc.Rig(C, W, H, F, 1, nfeatures=N)
+        rig.upload(imgs)
+        rig.extract(C * F)
+        got.append([([rig.candidates(m, l) for l in range(8)], rig.features(m)) for m in range(C * F)])
+        rig.close()
+    for m, ((cand1, feat1), (cand4, feat4)) in enumerate(zip(*got)):
+        assert len(feat4[1]) > 100, "image %d: too few keypoints for the comparison to mean anything" % m
+        for l in range(8):
+            for a, b in zip(cand1[l], cand4[l]):
+                assert np.array_equal(a, b), "candidates of image %d level %d" % (m, l)
+        assert_same_features(feat4, feat1, "image %d" % m)
+
+
 @pytest.mark.parametrize("mode", ["spin", "block", "poll"])
 def test_driver_wait_modes_give_the_same_frames(mc, monkeypatch, mode):
     """MCORB_SYNC only changes how the slot drivers wait for the GPU (hipEventSynchronize, interrupt-driven, hipEventQuery

@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
-"""Compile mcorb_kernels.hip for gfx950 with --save-temps and print, for one kernel, the instruction mix per
-basic block (VALU / LDS / SALU / VMEM counts) -- the static counterpart of the SQ_INSTS_VALU counter.
+"""Compile one kernel source of mc-slam_amd/csrc (default: mcorb_kernels.hip) for gfx950 with --save-temps and print, for one
+kernel, the instruction mix per basic block (VALU / LDS / SALU / VMEM counts) -- the static counterpart of the SQ_INSTS_VALU counter.
 
-    python3 tools/isa_stats.py k_fast_cellsILi48ELi2 [--dump]      # substring of the mangled name
+    python3 tools/isa_stats.py k_fast_cellsILi48E [--dump]                 # substring of the mangled name
+    python3 tools/isa_stats.py k_bow_fold mcorb_bow_gpu.hip [--dump]       # a kernel of another file
 """
 import os
 import re
@@ -14,14 +15,17 @@ OUT = "/tmp/mcorb_isa"
 
 
 def main():
-    pat = sys.argv[1]
+    args = [a for a in sys.argv[1:] if a != "--dump"]
+    pat, name = args[0], args[1] if len(args) > 1 else "mcorb_kernels.hip"
     dump = "--dump" in sys.argv
     os.makedirs(OUT, exist_ok=True)
-    src = os.path.join(ROOT, "mc-slam_amd", "csrc", "mcorb_kernels.hip")
-    subprocess.check_call(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "--offload-arch=gfx950", "-mllvm", "-amdgpu-mfma-vgpr-form",
-                           "-I" + os.path.join(ROOT, "mc-slam_amd", "csrc"), "-I" + os.path.join(ROOT, "include"),
+    src = os.path.join(ROOT, "mc-slam_amd", "csrc", os.path.basename(name))
+    stem = os.path.splitext(os.path.basename(name))[0]
+    flags = ["-mllvm", "-amdgpu-mfma-vgpr-form"] if stem == "mcorb_kernels" else []   # as csrc/Makefile builds each file
+    subprocess.check_call(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "--offload-arch=gfx950"] + flags +
+                          ["-I" + os.path.join(ROOT, "mc-slam_amd", "csrc"), "-I" + os.path.join(ROOT, "include"),
                            "--save-temps", "-c", src, "-o", os.path.join(OUT, "k.o")], cwd=OUT)
-    asm = open(os.path.join(OUT, "mcorb_kernels-hip-amdgcn-amd-amdhsa-gfx950.s")).read().split("\n")
+    asm = open(os.path.join(OUT, stem + "-hip-amdgcn-amd-amdhsa-gfx950.s")).read().split("\n")
     start = next(i for i, l in enumerate(asm) if re.match(r"^_Z\w*" + re.escape(pat) + r"\w*:", l))
     end = next(i for i in range(start, len(asm)) if "s_endpgm" in asm[i] and not any("s_endpgm" in x for x in asm[i + 1:i + 3]))
     end = max(i for i in range(start, len(asm)) if "s_endpgm" in asm[i] and i < start + 20000 and
