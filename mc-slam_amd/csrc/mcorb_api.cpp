@@ -10,21 +10,6 @@
 
 using namespace mcorb;
 
-struct mcorb_extractor {
-    mcorb_params params;
-    std::unique_ptr<Rig> rig;   // rebuilt when the image size changes
-    int w = 0, h = 0;
-    // scratch for mcorb_knn2 on host arrays, sized for kc descriptors a side (0: to be allocated)
-    DevBuf<uint8_t> d_desc, d_exp;
-    DevBuf<int> d_lcounts;
-    DevBuf<uint2> d_part;
-    HostBuf<KnnRow> h_rows;
-    HostBuf<uint32_t> h_mlist;
-    HostBuf<int> h_mcount, h_counts;
-    HostBuf<int2> h_pair;
-    int kc = 0;
-};
-
 extern "C" {
 
 void mcorb_default_params(mcorb_params *p)
@@ -106,55 +91,55 @@ int mcorb_rig_upload_f32(mcorb_rig *r, int slot, const float *const *images, int
     return r->rig.upload_f32(slot, images, nimg, stride_bytes, channels);
 }
 
-int mcorb_rig_extract_submit(mcorb_rig *r, int slot, int nimg, int lap_x0, int lap_x1)
+// the job of each kind, built once for its submit and its synchronous entry (the external matches add their block to match_job's)
+static Job extract_job(int nimg, int lap_x0, int lap_x1)
 {
-    if (!r) return MCORB_E_ARG;
     Job j;
     j.kind = Job::EXTRACT; j.nimg = nimg; j.lap0 = lap_x0; j.lap1 = lap_x1;
-    return r->rig.submit(slot, j);
+    return j;
+}
+static Job match_job(int nframes, float dist_thresh, float ratio)
+{
+    Job j;
+    j.kind = Job::MATCH; j.nframes = nframes; j.dist_thresh = dist_thresh; j.ratio = ratio;
+    return j;
+}
+static Job process_job(const Rig &R, int nframes, int lap_x0, int lap_x1, float dist_thresh, float ratio)
+{
+    Job j = match_job(nframes, dist_thresh, ratio);
+    j.kind = Job::PROCESS; j.nimg = nframes * R.ncams; j.lap0 = lap_x0; j.lap1 = lap_x1;
+    return j;
+}
+
+int mcorb_rig_extract_submit(mcorb_rig *r, int slot, int nimg, int lap_x0, int lap_x1)
+{
+    return r ? r->rig.submit(slot, extract_job(nimg, lap_x0, lap_x1)) : MCORB_E_ARG;
 }
 int mcorb_rig_extract_wait(mcorb_rig *r, int slot) { return r ? r->rig.wait(slot) : MCORB_E_ARG; }
 int mcorb_rig_extract(mcorb_rig *r, int slot, int nimg, int lap_x0, int lap_x1)
 {
-    if (!r) return MCORB_E_ARG;
-    Job j;
-    j.kind = Job::EXTRACT; j.nimg = nimg; j.lap0 = lap_x0; j.lap1 = lap_x1;
-    return r->rig.run_sync(slot, j);
+    return r ? r->rig.run_sync(slot, extract_job(nimg, lap_x0, lap_x1)) : MCORB_E_ARG;
 }
 
 int mcorb_rig_process_submit(mcorb_rig *r, int slot, int nframes, int lap_x0, int lap_x1, float dist_thresh, float ratio)
 {
-    if (!r) return MCORB_E_ARG;
-    Job j;
-    j.kind = Job::PROCESS; j.nframes = nframes; j.nimg = nframes * r->rig.ncams; j.lap0 = lap_x0; j.lap1 = lap_x1;
-    j.dist_thresh = dist_thresh; j.ratio = ratio;
-    return r->rig.submit(slot, j);
+    return r ? r->rig.submit(slot, process_job(r->rig, nframes, lap_x0, lap_x1, dist_thresh, ratio)) : MCORB_E_ARG;
 }
 int mcorb_rig_process_wait(mcorb_rig *r, int slot) { return r ? r->rig.wait(slot) : MCORB_E_ARG; }
 
 int mcorb_rig_match_submit(mcorb_rig *r, int slot, int nframes, float dist_thresh, float ratio)
 {
-    if (!r) return MCORB_E_ARG;
-    Job j;
-    j.kind = Job::MATCH; j.nframes = nframes; j.dist_thresh = dist_thresh; j.ratio = ratio;
-    return r->rig.submit(slot, j);
+    return r ? r->rig.submit(slot, match_job(nframes, dist_thresh, ratio)) : MCORB_E_ARG;
 }
 int mcorb_rig_match_wait(mcorb_rig *r, int slot) { return r ? r->rig.wait(slot) : MCORB_E_ARG; }
 int mcorb_rig_match(mcorb_rig *r, int slot, int nframes, float dist_thresh, float ratio)
 {
-    if (!r) return MCORB_E_ARG;
-    Job j;
-    j.kind = Job::MATCH; j.nframes = nframes; j.dist_thresh = dist_thresh; j.ratio = ratio;
-    return r->rig.run_sync(slot, j);
+    return r ? r->rig.run_sync(slot, match_job(nframes, dist_thresh, ratio)) : MCORB_E_ARG;
 }
 /* extract + match of nframes rig frames in one synchronous call (process_submit + process_wait on the caller's thread) */
 int mcorb_rig_process(mcorb_rig *r, int slot, int nframes, int lap_x0, int lap_x1, float dist_thresh, float ratio)
 {
-    if (!r) return MCORB_E_ARG;
-    Job j;
-    j.kind = Job::PROCESS; j.nframes = nframes; j.nimg = nframes * r->rig.ncams; j.lap0 = lap_x0; j.lap1 = lap_x1;
-    j.dist_thresh = dist_thresh; j.ratio = ratio;
-    return r->rig.run_sync(slot, j);
+    return r ? r->rig.run_sync(slot, process_job(r->rig, nframes, lap_x0, lap_x1, dist_thresh, ratio)) : MCORB_E_ARG;
 }
 
 static Slot *get_slot(mcorb_rig *r, int slot)
@@ -213,17 +198,6 @@ int mcorb_rig_get_pair_matches(mcorb_rig *r, int slot, int frame, int cam_i, int
         memcpy(idx2, s->m_idx2[pi].data(), (size_t)n * 4);
     }
     return MCORB_OK;
-}
-
-static void decode_rows(const KnnRow *rows, int nq, int32_t *idx, int32_t *dist)
-{
-    for (int q = 0; q < nq; q++) {
-        const KnnRow &k = rows[q];
-        idx[2 * q] = knn_idx0(k);
-        dist[2 * q] = knn_d0(k);
-        idx[2 * q + 1] = knn_idx1(k);
-        dist[2 * q + 1] = knn_d1(k);
-    }
 }
 
 int mcorb_rig_get_pair_knn2(mcorb_rig *r, int slot, int frame, int cam_i, int cam_j, int32_t *idx, int32_t *dist,
@@ -431,12 +405,12 @@ int mcorb_rig_get_candidates(mcorb_rig *r, int slot, int m, int level, uint32_t 
     if (m < 0 || m >= s->nimg_done || level < 0 || level >= g.nlevels) { set_error("bad candidate request"); return MCORB_E_ARG; }
     // level offsets of the image's table block: in host memory only when the job wrote them there (a small batch of the host
     // selection path) or brought them over; the device copy is what every other job leaves
-    int lo_dev[kMaxLevels + 1];
+    int dev_lo[kMaxLevels + 1];
     const int *lo = s->tbl(m) + kTblLvlOff;
     if (!(s->host_results && !r->rig.gpu_select)) {
         HIPCHK(hipSetDevice(r->rig.device));
-        HIPCHK(hipMemcpy(lo_dev, s->d_tbl + (size_t)m * s->tbl_ints_per_image + kTblLvlOff, sizeof(lo_dev), hipMemcpyDeviceToHost));
-        lo = lo_dev;
+        HIPCHK(hipMemcpy(dev_lo, s->d_tbl + (size_t)m * s->tbl_ints_per_image + kTblLvlOff, sizeof(dev_lo), hipMemcpyDeviceToHost));
+        lo = dev_lo;
     }
     const int n = lo[level + 1] - lo[level];
     if (n_out) *n_out = n;
@@ -465,7 +439,7 @@ int mcorb_rig_last_timing(mcorb_rig *r, int slot, float us[10])
 {
     Slot *s = get_slot(r, slot);
     if (!s) return MCORB_E_STATE;
-    for (int i = 0; i < 10; i++) us[i] = s->timing[i];
+    for (int i = 0; i < T_COUNT; i++) us[i] = s->timing[i];
     return MCORB_OK;
 }
 
@@ -480,22 +454,22 @@ int mcorb_rig_set_graph(mcorb_rig *r, int every)
 int mcorb_rig_select_fallbacks(mcorb_rig *r, int slot)
 {
     if (!r || slot < 0 || slot >= (int)r->rig.slots.size()) return MCORB_E_ARG;
-    return r->rig.slots[slot]->fallbacks;
+    return r->rig.slots[slot]->fallbacks.load(std::memory_order_relaxed);
 }
 int mcorb_rig_early_reads_rejected(mcorb_rig *r, int slot)
 {
     if (!r || slot < 0 || slot >= (int)r->rig.slots.size()) return MCORB_E_ARG;
-    return r->rig.slots[slot]->stale_reads;
+    return r->rig.slots[slot]->stale_reads.load(std::memory_order_relaxed);
 }
-int mcorb_dev_sort_selftest(int device, const uint32_t *keys, int n, uint32_t *perm_dev, uint32_t *perm_std)
+int mcorb_dev_sort_selftest(int device, const uint32_t *keys, int n, uint32_t *dev_perm, uint32_t *std_perm)
 {
-    if (n < 0 || n > 6000 || (n && (!keys || !perm_dev || !perm_std))) { set_error("sort_selftest: bad argument"); return MCORB_E_ARG; }
+    if (n < 0 || n > 6000 || (n && (!keys || !dev_perm || !std_perm))) { set_error("sort_selftest: bad argument"); return MCORB_E_ARG; }
     if (n == 0) return MCORB_OK;
     std::vector<uint64_t> a((size_t)n), b((size_t)n);
     for (int i = 0; i < n; i++) a[i] = ((uint64_t)keys[i] << 32) | (uint32_t)i;
     b = a;
     std::sort(b.begin(), b.end(), [](uint64_t x, uint64_t y) { return (x >> 32) < (y >> 32); });
-    for (int i = 0; i < n; i++) perm_std[i] = (uint32_t)b[i];
+    for (int i = 0; i < n; i++) std_perm[i] = (uint32_t)b[i];
     HIPCHK(hipSetDevice(device));
     DevBuf<uint64_t> d_in, d_out;
     TRY(d_in.alloc((size_t)n));
@@ -503,7 +477,7 @@ int mcorb_dev_sort_selftest(int device, const uint32_t *keys, int n, uint32_t *p
     HIPCHK(hipMemcpy(d_in, a.data(), (size_t)n * 8, hipMemcpyHostToDevice));
     HIPCHK(sort_selftest(d_in, n, d_out));
     HIPCHK(hipMemcpy(b.data(), d_out, (size_t)n * 8, hipMemcpyDeviceToHost));
-    for (int i = 0; i < n; i++) perm_dev[i] = (uint32_t)b[i];
+    for (int i = 0; i < n; i++) dev_perm[i] = (uint32_t)b[i];
     return MCORB_OK;
 }
 int mcorb_rig_host_threads(mcorb_rig *r) { return r ? r->rig.pool_threads : MCORB_E_ARG; }
@@ -530,8 +504,7 @@ int mcorb_rig_match_external_submit(mcorb_rig *r, int slot, const void *desc_dev
                                     const int32_t *sets, int nframes, float dist_thresh, float ratio)
 {
     if (!r || !desc_dev || !counts || !sets) { set_error("null argument"); return MCORB_E_ARG; }
-    Job j;
-    j.kind = Job::MATCH; j.nframes = nframes; j.dist_thresh = dist_thresh; j.ratio = ratio;
+    Job j = match_job(nframes, dist_thresh, ratio);
     j.ext_desc = desc_dev; j.ext_counts = counts; j.ext_total = ntotal; j.ext_sets = sets;
     return r->rig.submit(slot, j);
 }
@@ -547,8 +520,7 @@ int mcorb_rig_match_external_dev_submit(mcorb_rig *r, int slot, const void *desc
                                         const int32_t *sets, int nframes, float dist_thresh, float ratio, void *after_stream)
 {
     if (!r || !desc_dev || !counts_dev || !sets) { set_error("null argument"); return MCORB_E_ARG; }
-    Job j;
-    j.kind = Job::MATCH; j.nframes = nframes; j.dist_thresh = dist_thresh; j.ratio = ratio;
+    Job j = match_job(nframes, dist_thresh, ratio);
     j.ext_desc = desc_dev; j.ext_counts_dev = counts_dev; j.ext_total = ntotal; j.ext_sets = sets;
     j.after_stream = (hipStream_t)after_stream;
     if (after_stream) {
@@ -569,8 +541,7 @@ int mcorb_rig_match_pairs_external_dev_submit(mcorb_rig *r, int slot, const void
                                               const int32_t *pair_sets, int npairs, float dist_thresh, float ratio, void *after_stream)
 {
     if (!r || !desc_dev || !counts_dev || !pair_sets) { set_error("null argument"); return MCORB_E_ARG; }
-    Job j;
-    j.kind = Job::MATCH; j.nframes = 0; j.dist_thresh = dist_thresh; j.ratio = ratio;
+    Job j = match_job(0, dist_thresh, ratio);
     j.ext_desc = desc_dev; j.ext_counts_dev = counts_dev; j.ext_total = ntotal; j.ext_pairs = pair_sets; j.ext_npairs = npairs;
     j.after_stream = (hipStream_t)after_stream;
     if (after_stream) {
@@ -586,8 +557,7 @@ int mcorb_rig_match_pairs_external(mcorb_rig *r, int slot, const void *desc_dev,
                                    const int32_t *pair_sets, int npairs, float dist_thresh, float ratio)
 {
     if (!r || !desc_dev || !counts || !pair_sets) { set_error("null argument"); return MCORB_E_ARG; }
-    Job j;
-    j.kind = Job::MATCH; j.nframes = 0; j.dist_thresh = dist_thresh; j.ratio = ratio;
+    Job j = match_job(0, dist_thresh, ratio);
     j.ext_desc = desc_dev; j.ext_counts = counts; j.ext_total = ntotal; j.ext_pairs = pair_sets; j.ext_npairs = npairs;
     return r->rig.run_sync(slot, j);   // on the calling thread: no hand-off to the slot's driver and back
 }
@@ -668,7 +638,7 @@ int mcorb_rig_get_pairknn2(mcorb_rig *r, int slot, int pair, int32_t *idx, int32
     Slot *s = get_slot(r, slot);
     if (!s) return MCORB_E_STATE;
     if (pair < 0 || pair >= s->npairs_done || s->nframes_done != 0) { set_error("bad pair index (explicit-pair matches only)"); return MCORB_E_ARG; }
-    const int nq = s->match_counts[s->h_pairs[pair].x];
+    const int nq = s->match_counts[s->hc.pairs[pair].x];
     if (nq_out) *nq_out = nq;
     if (nq > cap_rows || (nq && (!idx || !dist))) { set_error("knn buffer too small"); return MCORB_E_CAP; }
     std::vector<KnnRow> rows((size_t)std::max(nq, 1));
@@ -715,7 +685,7 @@ int mcorb_rig_export_descriptors_dev(mcorb_rig *r, int slot, void *dst_dev, int3
     if (!dst_dev || !counts_dev || nimg < 1 || nimg > s->nimg_done) { set_error("export: bad argument"); return MCORB_E_ARG; }
     HIPCHK(hipSetDevice(r->rig.device));
     HIPCHK(hipMemcpyAsync(dst_dev, s->d_desc, (size_t)nimg * r->rig.geom.kcap * 32, hipMemcpyDeviceToDevice, s->st));
-    HIPCHK(hipMemcpyAsync(counts_dev, s->h_nsel, (size_t)nimg * sizeof(int), hipMemcpyHostToDevice, s->st));   // (pinned; the device mirror is not filled for small batches)
+    HIPCHK(hipMemcpyAsync(counts_dev, s->hc.nsel, (size_t)nimg * sizeof(int), hipMemcpyHostToDevice, s->st));   // (pinned; the device mirror is not filled for small batches)
     if (then_stream) {   // whatever the caller enqueues on then_stream next (the collective) runs after the two copies
         HIPCHK(hipEventRecord(s->ev_x, s->st));
         HIPCHK(hipStreamWaitEvent((hipStream_t)then_stream, s->ev_x, 0));
@@ -733,280 +703,7 @@ int mcorb_rig_export_descriptors(mcorb_rig *r, int slot, void *dst_dev, int32_t 
     HIPCHK(hipSetDevice(r->rig.device));
     HIPCHK(hipMemcpyAsync(dst_dev, s->d_desc, (size_t)nimg * r->rig.geom.kcap * 32, hipMemcpyDeviceToDevice, s->st));
     HIPCHK(hipStreamSynchronize(s->st));
-    if (counts_host) for (int m = 0; m < nimg; m++) counts_host[m] = s->h_nsel[m];
-    return MCORB_OK;
-}
-
-// ---------------------------------------------------------------------------
-// single-camera extractor
-// ---------------------------------------------------------------------------
-int mcorb_create(const mcorb_params *p, int max_width, int max_height, mcorb_t **out)
-{
-    if (!p || !out) { set_error("null argument"); return MCORB_E_ARG; }
-    *out = nullptr;
-    Tables t;
-    int st = compute_tables(*p, t);
-    if (st != MCORB_OK) return st;
-    mcorb_t *e = new (std::nothrow) mcorb_extractor;
-    if (!e) return MCORB_E_ARG;
-    e->params = *p;
-    if (max_width > 0 && max_height > 0) {
-        e->rig.reset(new Rig);
-        st = e->rig->init(*p, 1, max_width, max_height, 1, 1);
-        if (st != MCORB_OK) {
-            const std::string keep = get_error();
-            delete e;
-            set_error(keep);
-            return st;
-        }
-        e->w = max_width; e->h = max_height;
-    } else if (mcorb_device_count() < 1) {
-        delete e;
-        set_error("no usable gfx950 device (libmcorb has no CPU path)");
-        return MCORB_E_NODEVICE;
-    }
-    *out = e;
-    return MCORB_OK;
-}
-
-void mcorb_destroy(mcorb_t *e) { delete e; }
-
-static int ensure_rig(mcorb_t *e, int w, int h)
-{
-    if (e->rig && e->w == w && e->h == h) return MCORB_OK;
-    e->rig.reset();
-    e->rig.reset(new Rig);
-    const int st = e->rig->init(e->params, 1, w, h, 1, 1);
-    if (st != MCORB_OK) {
-        const std::string keep = get_error();
-        e->rig.reset();
-        set_error(keep);
-        return st;
-    }
-    e->w = w; e->h = h;
-    return MCORB_OK;
-}
-
-static int finish_extract(mcorb_t *e, int lap_x0, int lap_x1, mcorb_keypoint *kps, uint8_t *desc, int cap, int *n_out,
-                          int *mono_index_out)
-{
-    Job j;
-    j.kind = Job::EXTRACT; j.nimg = 1; j.lap0 = lap_x0; j.lap1 = lap_x1;
-    int st = e->rig->submit(0, j);
-    if (st == MCORB_OK) st = e->rig->wait(0);
-    if (st != MCORB_OK) return st;
-    Slot *s = e->rig->slots[0].get();
-    const int n = (int)s->kps[0].size();
-    if (n_out) *n_out = n;
-    if (mono_index_out) *mono_index_out = s->mono[0];
-    if (n > cap) { set_error("keypoint buffer too small"); return MCORB_E_CAP; }
-    if (kps && n) memcpy(kps, s->kps[0].data(), (size_t)n * sizeof(mcorb_keypoint));
-    if (desc && n) memcpy(desc, s->h_desc, (size_t)n * 32);
-    return MCORB_OK;
-}
-
-int mcorb_extract(mcorb_t *e, const uint8_t *gray, int w, int h, int stride_bytes, int lap_x0, int lap_x1,
-                  mcorb_keypoint *kps, uint8_t *desc, int cap, int *n_out, int *mono_index_out)
-{
-    if (!e) { set_error("null extractor"); return MCORB_E_ARG; }
-    if (n_out) *n_out = 0;
-    if (!gray || w <= 0 || h <= 0) { set_error("empty image"); return MCORB_E_EMPTY; }
-    int st = ensure_rig(e, w, h);
-    if (st != MCORB_OK) return st;
-    const uint8_t *imgs[1] = {gray};
-    st = e->rig->upload_u8(0, imgs, 1, stride_bytes);
-    if (st != MCORB_OK) return st;
-    return finish_extract(e, lap_x0, lap_x1, kps, desc, cap, n_out, mono_index_out);
-}
-
-int mcorb_extract_f32(mcorb_t *e, const float *img01, int w, int h, int stride_bytes, int channels, int lap_x0,
-                      int lap_x1, mcorb_keypoint *kps, uint8_t *desc, int cap, int *n_out, int *mono_index_out)
-{
-    if (!e) { set_error("null extractor"); return MCORB_E_ARG; }
-    if (n_out) *n_out = 0;
-    if (!img01 || w <= 0 || h <= 0) { set_error("empty image"); return MCORB_E_EMPTY; }
-    int st = ensure_rig(e, w, h);
-    if (st != MCORB_OK) return st;
-    const float *imgs[1] = {img01};
-    st = e->rig->upload_f32(0, imgs, 1, stride_bytes, channels);
-    if (st != MCORB_OK) return st;
-    return finish_extract(e, lap_x0, lap_x1, kps, desc, cap, n_out, mono_index_out);
-}
-
-int mcorb_get_tables(const mcorb_params *p, float *scale, float *inv_scale, float *sigma2, float *inv_sigma2,
-                     int *features_per_level)
-{
-    if (!p) return MCORB_E_ARG;
-    Tables t;
-    const int st = compute_tables(*p, t);
-    if (st != MCORB_OK) return st;
-    for (int i = 0; i < t.nlevels; i++) {
-        if (scale) scale[i] = t.scale[i];
-        if (inv_scale) inv_scale[i] = t.inv_scale[i];
-        if (sigma2) sigma2[i] = t.sigma2[i];
-        if (inv_sigma2) inv_sigma2[i] = t.inv_sigma2[i];
-        if (features_per_level) features_per_level[i] = t.quota[i];
-    }
-    return MCORB_OK;
-}
-
-int mcorb_get_pyramid_level(mcorb_t *e, int level, uint8_t *dst, int dst_stride, int *w, int *h)
-{
-    if (!e || !e->rig) { set_error("no image processed yet"); return MCORB_E_STATE; }
-    const Geom &g = e->rig->geom;
-    if (level < 0 || level >= g.nlevels) return MCORB_E_ARG;
-    if (w) *w = g.lv[level].w;
-    if (h) *h = g.lv[level].h;
-    if (!dst) return MCORB_OK;
-    if (dst_stride < g.lv[level].w) return MCORB_E_ARG;
-    Slot *s = e->rig->slots[0].get();
-    HIPCHK(hipSetDevice(e->rig->device));
-    HIPCHK(hipStreamSynchronize(s->st));
-    HIPCHK(hipMemcpy2D(dst, dst_stride, s->d_pyr + g.lv[level].off, g.lv[level].pitch, g.lv[level].w, g.lv[level].h,
-                       hipMemcpyDeviceToHost));
-    return MCORB_OK;
-}
-
-// ORBextractor::DescriptorDistance (ORBextractor.cpp:1202-1218)
-int mcorb_hamming256(const uint8_t a[32], const uint8_t b[32])
-{
-    uint64_t x[4], y[4];
-    memcpy(x, a, 32);
-    memcpy(y, b, 32);
-    return __builtin_popcountll(x[0] ^ y[0]) + __builtin_popcountll(x[1] ^ y[1]) + __builtin_popcountll(x[2] ^ y[2]) +
-           __builtin_popcountll(x[3] ^ y[3]);
-}
-
-// MultiCameraFrame::computeRepresentativeDesc (MultiCameraFrame.cpp:530-567): among n (<= 16) descriptors
-// of one track, the one with the least median Hamming distance to the others; first minimum wins.
-int mcorb_representative_desc(const uint8_t *descs, int n)
-{
-    if (!descs || n < 1 || n > 64) { set_error("representative_desc: bad argument"); return MCORB_E_ARG; }
-    int best_median = 0x7fffffff, best_idx = 0;
-    std::vector<int> row(n);
-    for (int i = 0; i < n; i++) {
-        for (int j = 0; j < n; j++) row[j] = i == j ? 0 : mcorb_hamming256(descs + (size_t)i * 32, descs + (size_t)j * 32);
-        std::sort(row.begin(), row.end());
-        const int median = row[(size_t)(0.5 * (n - 1))];
-        if (median < best_median) { best_median = median; best_idx = i; }
-    }
-    return best_idx;
-}
-
-static int knn2_host_arrays(mcorb_t *e, const uint8_t *q, int nq, const uint8_t *t, int nt, float thr, float ratio)
-{
-    if (!e || nq < 0 || nt < 0 || (nq && !q) || (nt && !t)) { set_error("knn2: bad argument"); return MCORB_E_ARG; }
-    if (nq > 65535 || nt > 65535) { set_error("knn2: more than 65535 descriptors"); return MCORB_E_ARG; }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || e->params.device_id >= ndev) {
-        set_error("no usable HIP device (libmcorb has no CPU path)");
-        return MCORB_E_NODEVICE;
-    }
-    HIPCHK(hipSetDevice(e->params.device_id));
-    const int need = (std::max(std::max(nq, nt), 1) + 63) / 64 * 64;
-    if (need > e->kc) {
-        e->kc = 0;   // (each alloc releases what it held; a failure on the way leaves kc 0, and the next call allocates all again)
-        TRY(e->d_desc.alloc((size_t)2 * need * 32));
-        TRY(e->d_part.alloc(knn_part_entries(1, need)));
-        TRY(e->d_exp.alloc((size_t)2 * need * kKnnExpandBytes));
-        TRY(e->d_lcounts.alloc(2));
-        TRY(e->h_rows.alloc((size_t)need, hipHostMallocMapped));
-        TRY(e->h_mlist.alloc(knn_mlist_stride(need), hipHostMallocMapped));
-        TRY(e->h_mcount.alloc((size_t)knn_qblocks(need), hipHostMallocMapped));
-        TRY(e->h_counts.alloc(2, hipHostMallocMapped));
-        TRY(e->h_pair.alloc(1, hipHostMallocMapped));
-        e->kc = need;
-    }
-    if (nq) HIPCHK(hipMemcpy(e->d_desc, q, (size_t)nq * 32, hipMemcpyHostToDevice));
-    if (nt) HIPCHK(hipMemcpy(e->d_desc + (size_t)e->kc * 32, t, (size_t)nt * 32, hipMemcpyHostToDevice));
-    e->h_counts[0] = nq;
-    e->h_counts[1] = nt;
-    e->h_pair[0] = int2{0, 1};
-    launch_knn2(nullptr, e->d_desc, e->h_counts, nullptr, 2, e->h_pair, 1, e->kc, e->d_exp, e->d_lcounts, e->d_part, thr, ratio, e->h_rows,
-                e->h_mlist, e->h_mcount, nullptr, nullptr);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(nullptr));
-    return MCORB_OK;
-}
-
-int mcorb_knn2(mcorb_t *e, const uint8_t *q, int nq, const uint8_t *t, int nt, int32_t *idx, int32_t *dist)
-{
-    if (!idx || !dist) { set_error("null output"); return MCORB_E_ARG; }
-    const int st = knn2_host_arrays(e, q, nq, t, nt, 75.f, 0.85f);
-    if (st != MCORB_OK) return st;
-    decode_rows(e->h_rows, nq, idx, dist);
-    return MCORB_OK;
-}
-
-int mcorb_match_ratio(mcorb_t *e, const uint8_t *q, int nq, const uint8_t *t, int nt, float dist_thresh, float ratio,
-                      uint32_t *idx1, uint32_t *idx2, int cap, int *n_out)
-{
-    const int st = knn2_host_arrays(e, q, nq, t, nt, dist_thresh, ratio);
-    if (st != MCORB_OK) return st;
-    int n = 0;
-    for (int i = 0; i < nq; i++) {
-        const KnnRow &r = e->h_rows[i];
-        if (knn_accept(r)) {
-            if (n < cap) { idx1[n] = (uint32_t)i; idx2[n] = (uint32_t)knn_idx0(r); }
-            n++;
-        }
-    }
-    if (n_out) *n_out = n;
-    if (n > cap) { set_error("match buffer too small"); return MCORB_E_CAP; }
-    return MCORB_OK;
-}
-
-int mcorb_host_select(const uint32_t *packed, int n, int minX, int maxX, int minY, int maxY, int nfeatures_level,
-                      int wCell, int hCell, int32_t *out_idx, int cap)
-{
-    if (n < 0 || (n && !packed) || !out_idx) { set_error("host_select: bad argument"); return MCORB_E_ARG; }
-    if (n == 0) return 0;
-    const SelectParams P = make_select_params(minX, maxX, minY, maxY, nfeatures_level, wCell, hCell);
-    if (P.nIni < 1) { set_error("host_select: level too tall"); return MCORB_E_SIZE; }
-    static thread_local SelectScratch sc;
-    std::vector<uint32_t> sorted;
-    std::vector<int> perm, bstart;
-    std::vector<mcorb::BucketBest> bbest;
-    host_bucket_sort(packed, n, P, sorted, perm, bstart, bbest);   // what k_compact does on the device
-    std::vector<int> out((size_t)std::max(nfeatures_level, 0) + 64 + 8);
-    std::vector<uint32_t> outv(out.size());
-    const int r = select_octree(sorted.data(), bstart.data(), bbest.data(), n, P, out.data(), outv.data(), sc);
-    if (r == -4) { set_error("host_select: 2^20 candidates or a level 4096 px wide: beyond the packed (count, UL.x) sort key"); return MCORB_E_SIZE; }
-    if (r < 0) { set_error("host_select: level too tall"); return MCORB_E_SIZE; }
-    if (r > cap) { set_error("host_select: output too small"); return MCORB_E_CAP; }
-    for (int i = 0; i < r; i++) {
-        out_idx[i] = perm[out[i]];
-        if (outv[i] != packed[out_idx[i]]) { set_error("host_select: value/index mismatch"); return MCORB_E_STATE; }
-    }
-    return r;
-}
-
-int mcorb_host_resize_axis(int ssize, int dsize, int is_x, int32_t *quads)
-{
-    if (ssize < 1 || dsize < 1 || !quads) return MCORB_E_ARG;
-    std::vector<ResizeTap> t;
-    build_resize_axis(ssize, dsize, is_x != 0, t, 1);
-    for (int d = 0; d < dsize; d++) {
-        quads[4 * d] = t[d].s0; quads[4 * d + 1] = t[d].s1; quads[4 * d + 2] = t[d].c0; quads[4 * d + 3] = t[d].c1;
-    }
-    return MCORB_OK;
-}
-
-int mcorb_host_geometry(const mcorb_params *p, int w, int h, int32_t *six)
-{
-    if (!p || !six) return MCORB_E_ARG;
-    Tables t;
-    int st = compute_tables(*p, t);
-    if (st != MCORB_OK) return st;
-    Geom g;
-    std::vector<ResizeTap> taps;
-    st = build_geometry(*p, t, w, h, g, taps);
-    if (st != MCORB_OK) return st;
-    for (int l = 0; l < g.nlevels; l++) {
-        const LevelGeom &L = g.lv[l];
-        int32_t *o = six + 6 * l;
-        o[0] = L.w; o[1] = L.h; o[2] = L.nCols; o[3] = L.nRows; o[4] = L.wCell; o[5] = L.hCell;
-    }
+    if (counts_host) for (int m = 0; m < nimg; m++) counts_host[m] = s->hc.nsel[m];
     return MCORB_OK;
 }
 

@@ -330,7 +330,7 @@ extern "C" int mcorb_rig_transform_image(mcorb_rig *r, int slot, int m, mcorb_vo
     if (m < 0 || m >= s->nimg_done) { set_error("image index out of range"); return MCORB_E_ARG; }
     if (v->device != r->rig.device) { set_error("vocabulary lives on another device"); return MCORB_E_ARG; }
     HIPCHK(hipSetDevice(v->device));
-    const int n = s->h_nsel[m];
+    const int n = s->hc.nsel[m];
     std::lock_guard<std::mutex> scratch_lock(v->scratch_mu);
     int st = ensure_scratch(v, std::max(n, 1));
     if (st != MCORB_OK) return st;
@@ -366,7 +366,7 @@ extern "C" int mcorb_rig_transform_images(mcorb_rig *r, int slot, int img0, int 
     R.pool->parallel_for(nimg, [&](int i, int) {
         BowList bow;
         std::map<uint32_t, std::vector<int32_t>> fv;
-        assemble(v, v->h_out + (size_t)i * kcap, s->h_nsel[img0 + i], bow, fv);
+        assemble(v, v->h_out + (size_t)i * kcap, s->hc.nsel[img0 + i], bow, fv);
         to_image_out(bow, fv, s->bowvec[img0 + i]);
         s->bowvec_ok[img0 + i] = 1;
     }, R.pool_threads + s->index);
@@ -584,7 +584,7 @@ extern "C" int mcorb_rig_match_bow_frames(mcorb_rig *r, int slot, int frame0, in
         F.fv.resize(C); F.feats.resize(C);
         std::vector<std::pair<uint32_t, int32_t>> tmp;
         for (int c = 0; c < C; c++) {
-            const int m = f * C + c, n = s->h_nsel[img0 + m];
+            const int m = f * C + c, n = s->hc.nsel[img0 + m];
             h_nfeat[m] = n;
             const mcorb::BowRes *res = v->h_out + (size_t)m * kcap;
             tmp.clear();

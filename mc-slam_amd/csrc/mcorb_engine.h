@@ -40,6 +40,14 @@ void build_resize_axis(int ssize, int dsize, bool is_x, std::vector<ResizeTap> &
 // lut (optional): receives the path-code tables of all levels (LevelGeom::lutx / luty index into it)
 int build_geometry(const mcorb_params &p, const Tables &t, int W, int H, Geom &g, std::vector<ResizeTap> &taps,
                    std::vector<uint16_t> *lut = nullptr);
+// LDS source window of one resize workgroup (256 x kResizeTileH outputs): per level, win[2 * l] = the widest column span (pitch) and
+// win[2 * l + 1] = the tallest row span of its taps; MCORB_E_ARG where a window does not fit the LDS
+int resize_windows(const Geom &g, const std::vector<ResizeTap> &taps, int win[2 * kMaxLevels]);
+
+static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+constexpr unsigned kHostMapped = hipHostMallocMapped | hipHostMallocPortable;   // pinned memory that kernels access
+constexpr int kSmallBatch = 8;   // images: at most two 4-camera rig frames
+int usable_cores();   // cores this process can use: affinity mask, cgroup quota, ranks per node (mcorb_pool.cpp)
 
 class WorkerPool {
 public:
@@ -91,6 +99,10 @@ struct Job {
 };
 
 class Rig;
+
+// mcorb_rig_last_timing's ten floats (us), in the public order of include/mcorb.h: pyramid + FAST + compaction (a graphed job: the
+// whole job) | selection | blur + describe | k-NN + finalize | pyramid | k_fast_cells | k_compact | k_knn2 | k_blur | k_describe
+enum Timing { T_FRONT, T_SELECT, T_DESC, T_MATCH, T_PYR, T_FAST, T_COMPACT, T_KNN2, T_BLUR, T_DESCRIBE, T_COUNT };
 
 // computeIntraMatches' track merge (MultiCameraFrame.cpp:1167-1268) over the BruteForceMatch lists of one frame's camera pairs
 // in (0,1), (0,2), .., (1,2), .. order: counts[c] keypoints per camera, idx1[p] / idx2[p] the accepted (query, train) indices of
@@ -178,7 +190,10 @@ struct Slot {
     Event ev_x;   // cross-stream hand-offs with the caller's streams (export / external match)
     Event ev_c;   // k_compact finished (the table DMA follows it on the side stream)
     Event ev_e;   // k_expand finished (k_knn2 follows)
-    Event ev[12];  // 0 start, 1 pyramid done, 2 FAST done, 3 compact done, 4 blur done, 5/6 describe(+D2H), 7 knn2 start, 8 knn2 done, 9 finalize done
+    // what has finished when each is reached, in job order: nothing yet | pyramid | FAST | the tables are with whoever selects (and
+    // the selection itself, on the GPU) | blur | control block in place, describe starts | describe | k-NN starts | k_knn2 | finalize |
+    // the compute stream's last operation | the side stream's.  A thread waits on ev_tables, ev_done and ev_side only.
+    Event ev_start, ev_pyr, ev_fast, ev_tables, ev_blur, ev_desc0, ev_desc1, ev_knn0, ev_knn1, ev_fin, ev_done, ev_side;
     Event ev_s;   // k_select + k_assemble finished
     Event ev_g;   // in front of a replayed job graph
     // device
@@ -204,16 +219,15 @@ struct Slot {
     HostBuf<uint32_t> h_mlist;       // per pair: accepted (query << 16 | train), query order (k_knn2_finalize)
     HostBuf<int> h_mcount;
     // control block: one pinned host buffer + one device mirror, copied with a single
-    // hipMemcpyAsync: [extcounts ext_cap ints][nsel][setmap][pairs][sel]; the h_ / d_ pointers below are views into the pair
+    // hipMemcpyAsync: [extcounts ext_cap ints][nsel][setmap][pairs][sel]; hc / dc: the host and the device side of that layout
     HostBuf<uint8_t> h_ctrl;
     DevBuf<uint8_t> d_ctrl;
     size_t ctrl_pairs_end = 0, ctrl_bytes = 0;
-    int *h_extcounts = nullptr, *h_nsel = nullptr, *h_setmap = nullptr;
-    int2 *h_pairs = nullptr;
-    uint32_t *h_sel = nullptr;
-    int *d_extcounts = nullptr, *d_nsel = nullptr, *d_setmap = nullptr;
-    int2 *d_pairs = nullptr;
-    uint32_t *d_sel = nullptr;
+    struct CtrlView {
+        int *extcounts, *nsel, *setmap;
+        int2 *pairs;
+        uint32_t *sel;
+    } hc = {}, dc = {};
     // GPU selection (MCORB_SELECT_GPU): k_select's per-(image, level) lists, and the result block k_assemble fills for the host
     // ([16 ints of flags][mono M ints][responses M x kcap bytes]; sel / nsel are written into the control block)
     DevBuf<uint32_t> d_selval;
@@ -223,8 +237,8 @@ struct Slot {
     size_t res_bytes = 0, res_mono_off = 0, res_resp_off = 0, ctrl_nsel_off = 0;
     HostBuf<unsigned long long> h_sig;        // small GPU-selected jobs: per image, set by k_assemble behind its host-mapped results
     bool capturing = false;    // enqueue_gpu_job is being captured into the slot's graph
-    int stale_reads = 0;       // small batches: images whose early read did not match the signal word's checksum (redone after the end event)
-    int fallbacks = 0;         // jobs of this slot the host stage had to redo (a tree below the bucketing depth)
+    std::atomic<int> stale_reads{0};   // small batches: images whose early read did not match the signal word's checksum (redone after the end event)
+    std::atomic<int> fallbacks{0};     // jobs of this slot the host stage had to redo (a tree below the bucketing depth)
     // (lf / lf_gen: mcorb_rig_set_lf's binding and set calls -- the LF stage runs after the graph, the key keeps it in view;
     // bow_*: the vocabulary binding the job was captured with -- its tables and levelsup are kernel arguments; bow_gen counts
     // mcorb_rig_set_vocabulary calls, so a freed vocabulary whose address comes back never replays a stale graph.  4-byte fields
@@ -260,7 +274,7 @@ struct Slot {
     }
     std::vector<LfFrameOut> lf;     // per frame: the job's obtainLfFeatures + LF transform (mcorb_rig_set_lf)
     std::vector<uint8_t> lf_ok;
-    float timing[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    float timing[T_COUNT] = {};
     bool undist_job = false;      // the images in the slot were extracted with k_undistort (some camera had undistortion set)
     unsigned undist_gen = 0;      // Rig::undist_gen when they were extracted
     bool submitted = false;       // a job was submitted and not yet waited for (mcorb_rig_set_undistortion refuses then)
@@ -287,7 +301,8 @@ struct Slot {
     } ctl = {};
     void set_ctl(bool host_lists, bool host_sel)
     {
-        ctl = {host_sel ? h_nsel : d_nsel, host_lists ? h_setmap : d_setmap, host_lists ? h_pairs : d_pairs, host_sel ? h_sel : d_sel};
+        const CtrlView &sel = host_sel ? hc : dc, &lists = host_lists ? hc : dc;
+        ctl = {sel.nsel, lists.setmap, lists.pairs, sel.sel};
     }
     // driver thread
     std::thread th;
@@ -422,11 +437,13 @@ private:
     void driver(Slot *s);
     int execute(Slot &s, const Job &j);
     // The stages every extraction job is assembled from.  begin_extract: what a job does before its first launch (argument check,
-    // the bindings' snapshot, small batch or not, the control block view).  enqueue_front: ev0 . pyramid . ev1 . FAST . ev2 .
-    // k_compact . ev_c on the compute stream, the tables into tbl.  enqueue_back: from ev[5] to the job's last enqueued operation;
+    // the bindings' snapshot, small batch or not, the control block view).  enqueue_front: ev_start . pyramid . ev_pyr . FAST . ev_fast .
+    // k_compact . ev_c on the compute stream, the tables into tbl.  enqueue_back: from ev_desc0 to the job's last enqueued operation;
     // gpu_sel: k_assemble left sel / nsel on the device (else the host filled the control block).
     int begin_extract(Slot &s, const Job &j);
     int enqueue_front(Slot &s, int nimg, int *tbl);
+    // the slot's table blocks to the pinned h_tbl on st_copy and ev_tables behind them; by_kernel: k_copy_to_host, not the runtime's copy
+    int enqueue_tables_to_host(Slot &s, int nimg, bool by_kernel);
     int enqueue_back(Slot &s, const Job &j, bool then_match, bool gpu_sel);
     void read_timing(Slot &s, hipEvent_t blur0);   // per-kernel times of an ungraphed job; blur0: k_blur's start event (null: none ran)
     mcorb_keypoint make_keypoint(int level, int xl, int yl, float response, float angle) const;
@@ -445,6 +462,24 @@ private:
     int finish_match(Slot &s, const Job &j);
 };
 
+// Elapsed milliseconds between two events of a finished job; 0 when either was not recorded on a stream (a job that ran from its
+// captured graph holds them as graph nodes).  A failed query must not stay behind as the thread's "last error".
+static inline void ev_elapsed(float *ms, hipEvent_t a, hipEvent_t b)
+{
+    if (hipEventElapsedTime(ms, a, b) != hipSuccess) { *ms = 0.f; (void)hipGetLastError(); }
+}
+
+// k-NN rows as the API hands them out: (idx0, idx1) and (d0, d1) per query
+inline void decode_rows(const KnnRow *rows, int nq, int32_t *idx, int32_t *dist)
+{
+    for (int q = 0; q < nq; q++) {
+        const KnnRow &k = rows[q];
+        idx[2 * q] = knn_idx0(k);
+        dist[2 * q] = knn_d0(k);
+        idx[2 * q + 1] = knn_idx1(k);
+        dist[2 * q + 1] = knn_d1(k);
+    }
+}
 // the host half of a job's BoW stages (mcorb_bow.cpp): the BowImageOut of every image from k_bow_fold's records and, with
 // MCORB_BOW_MATCH, the reference's serial track bookkeeping of every frame on the worker pool
 int bow_job_finish(Rig &R, Slot &s, int nimg);

@@ -84,6 +84,7 @@ void launch_knn2(hipStream_t st, const uint8_t *desc, const int *counts, const i
 // for the host's keypoint records; fallback bit 1 = more than kcap keypoints.
 int select_cap(const Geom &g);
 bool select_fits(const Geom &g);   // false: the level trees of this geometry do not fit a wave's LDS (very large feature budgets)
+hipError_t configure_select(const Geom &g);   // a rig that selects on the GPU calls this once, with its device current, before its first job
 // deep_cap: a bucket with more candidates than this is not scanned node by node when a tree goes below the bucketing depth
 // prof: shader-clock stamps of k_select's phases on stderr (a rig's MCORB_SELECT_PROF)
 hipError_t launch_select(hipStream_t st, const int *tbl, const uint32_t *sorted, const Geom &g, uint32_t *sel_val, int *sel_cnt, int *fallback, int nimg,

@@ -657,6 +657,7 @@ int select_cap(const Geom &g)   // retained candidates per (image, level): Distr
     return (q + 64 + 63) & ~63;
 }
 
+constexpr size_t kSelLdsMax = 160 * 1024;   // one workgroup's LDS on gfx950
 static size_t select_lds(const Geom &g, int &B)
 {
     B = 1;
@@ -671,7 +672,17 @@ bool select_fits(const Geom &g)
     int B;
     for (int l = 0; l < g.nlevels; l++)
         if (g.lv[l].nIni > 64) return false;
-    return select_cap(g) <= 65535 && select_lds(g, B) <= 160 * 1024;
+    return select_cap(g) <= 65535 && select_lds(g, B) <= kSelLdsMax;
+}
+
+// Once per rig, under its hipSetDevice (Rig::init), never on the launch path: a geometry whose k_select needs more than the 64 KiB a
+// kernel gets by default has the device's limit raised.  The limit belongs to (device, kernel), not to a rig, so it is raised to
+// what select_fits admits at all: no later rig with a smaller tree lowers it under an earlier one, and no state is kept here.
+hipError_t configure_select(const Geom &g)
+{
+    int B;
+    if (select_lds(g, B) <= 64 * 1024) return hipSuccess;
+    return hipFuncSetAttribute((const void *)k_select, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kSelLdsMax);
 }
 
 hipError_t launch_select(hipStream_t st, const int *tbl, const uint32_t *sorted, const Geom &g, uint32_t *sel_val, int *sel_cnt, int *fallback, int nimg, int deep_cap, bool prof_on)
@@ -680,12 +691,6 @@ hipError_t launch_select(hipStream_t st, const int *tbl, const uint32_t *sorted,
     const int cap = select_cap(g);
     const size_t lds = select_lds(g, B);
     if (!select_fits(g)) return hipErrorInvalidValue;
-    static size_t configured = 0;
-    if (lds > 64 * 1024 && lds > configured) {
-        const hipError_t e = hipFuncSetAttribute((const void *)k_select, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        configured = lds;
-    }
     static HostBuf<unsigned long long> prof;
     if (prof_on && !prof) (void)prof.alloc(kMaxLevels * 32, hipHostMallocMapped);
     if (prof_on && prof) {

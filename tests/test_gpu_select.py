@@ -201,3 +201,30 @@ def test_job_redone_by_the_host_stage_still_matches(mc, monkeypatch, frames):
         oi, od = O.knn2(descs[0], descs[1])
         assert np.array_equal(gi, oi) and np.array_equal(gd, od)
     rig.close()
+
+
+def test_second_rig_needing_more_than_64k_of_lds_after_a_small_one(mc):
+    """k_select's dynamic-LDS limit is raised when a rig is created (configure_select in Rig::init), not at the first launch that
+    needs it: a rig whose k_select fits the default 64 KiB runs a job first, then a second rig in the same process needs more.
+    160x120, 2 levels, one camera: nfeatures 300 gives sel_lds_bytes(B 256, cap 256) = 18 000 bytes; nfeatures 1527 is the smallest
+    budget beyond 64 KiB -- level 0's quota 833, select_cap 960, sel_lds_bytes(B 1024, cap 960) = 66 640 bytes (1526: 63 056) -- and
+    select_fits still holds.  Both jobs must be the oracle's bit for bit, selected on the GPU, without a host redo."""
+    W, H, L = 160, 120, 2
+    img = mc.synth_rig_frame(0, 1, 0, W, H)
+    rigs = []
+    for nf in (300, 1527):
+        mono, k, d = O.OracleExtractor(nf, nlevels=L)(img)
+        assert all(np.any(k["octave"] == lvl) for lvl in range(L)), "the frame must give every level a keypoint"
+        rig = mc.Rig(1, W, H, 1, 1, nfeatures=nf, nlevels=L, selection=2)
+        assert rig.select_mode() == "gpu"
+        rig.upload([img])
+        rig.extract(1)
+        m2, k2, d2 = rig.features(0)
+        assert mono == m2 and len(k) == len(k2), nf
+        for fld in k.dtype.names:
+            assert np.array_equal(k[fld], k2[fld]), "nfeatures %d field %s" % (nf, fld)
+        assert np.array_equal(d, d2), nf
+        assert rig.select_fallbacks() == 0, nf
+        rigs.append(rig)   # (the first stays alive beside the second)
+    for rig in rigs:
+        rig.close()
