@@ -17,8 +17,11 @@ namespace mcorb {
 // multiply(img,255) -> convertTo(CV_8U) -> cvtColor(BGR2GRAY)
 // (MCSlam/src/MultiCameraFrame.cpp:108-116).
 // ---------------------------------------------------------------------------
+// What an int cannot hold (NaN, +-Inf, a product outside [-2^31, 2^31)) is 0: x86's cvtss2si / cvtps2dq answer 0x80000000, which
+// the saturating packs clamp to 0 (docs/design/02_oracle.md).  The conversion alone would saturate +Inf to INT_MAX, i.e. 255.
 __device__ __forceinline__ int sat_u8_rne(float v)
 {
+    if (!(v >= -2147483648.f && v < 2147483648.f)) return 0;
     int r = __float2int_rn(v);   // cvRound: round-half-even
     return r < 0 ? 0 : (r > 255 ? 255 : r);
 }

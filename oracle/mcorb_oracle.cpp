@@ -369,7 +369,14 @@ extern "C" float orc_fast_atan2(float y, float x)
     return a;
 }
 
-/* MultiCameraFrame::setData hand-off, MultiCameraFrame.cpp:108-116 (A.6) */
+/* MultiCameraFrame::setData hand-off, MultiCameraFrame.cpp:108-116 (A.6).  A product an int cannot hold (NaN, +-Inf, outside
+   [-2^31, 2^31)) gives 0: cvtss2si / cvtps2dq answer 0x80000000 and the saturating packs clamp that to 0.  lrintf with a 64-bit
+   long would keep the low 32 bits of a large finite value instead, so the range is tested first. */
+static inline int stage_round(float v)
+{
+    if (!(v >= -2147483648.f && v < 2147483648.f)) return INT32_MIN;
+    return (int)lrintf(v);
+}
 extern "C" void orc_stage_f32(const float *img, int w, int h, int stride_bytes, int channels,
                               uint8_t *gray, int gstride)
 {
@@ -379,11 +386,11 @@ extern "C" void orc_stage_f32(const float *img, int w, int h, int stride_bytes, 
         for (int x = 0; x < w; x++) {
             if (channels == 1) {
                 float m = S[x] * 255.f;                       /* multiply(img,255,img) */
-                D[x] = sat_u8(orc_cv_round_f(m));             /* convertTo(CV_8U) */
+                D[x] = sat_u8(stage_round(m));             /* convertTo(CV_8U) */
             } else {
-                int b = sat_u8(orc_cv_round_f(S[3 * x + 0] * 255.f));
-                int g = sat_u8(orc_cv_round_f(S[3 * x + 1] * 255.f));
-                int r = sat_u8(orc_cv_round_f(S[3 * x + 2] * 255.f));
+                int b = sat_u8(stage_round(S[3 * x + 0] * 255.f));
+                int g = sat_u8(stage_round(S[3 * x + 1] * 255.f));
+                int r = sat_u8(stage_round(S[3 * x + 2] * 255.f));
                 /* cvtColor BGR2GRAY, 8U: (B*1868 + G*9617 + R*4899 + (1<<13)) >> 14 */
                 D[x] = (uint8_t)((b * 1868 + g * 9617 + r * 4899 + 8192) >> 14);
             }

@@ -20,8 +20,11 @@ L = _lib.load()
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "mc-slam_amd", "csrc")
 
-SIZES = [(160, 120), (640, 480), (752, 480), (1280, 720), (1920, 1080)]
-STRIPES = {160: 25, 640: 6, 752: 5, 1280: 3, 1920: 2}
+# the last four: widths with w % 4 in {1, 2, 3}, where the row of quads k_remap_u8 and a vectorised host loop walk ends in a
+# scalar tail (323: wider than one 256-lane block, w % 64 != 0)
+SIZES = [(160, 120), (640, 480), (752, 480), (1280, 720), (1920, 1080), (161, 120), (162, 121), (163, 123), (323, 243)]
+# cv::undistort's min(max(1, 4096 / cols), rows), worked out by hand: 4096 = 25 * 163 + 21 = 12 * 323 + 220
+STRIPES = {160: 25, 640: 6, 752: 5, 1280: 3, 1920: 2, 161: 25, 162: 25, 163: 25, 323: 12}
 
 # (name, coefficients): 4 / 5 / 8 / 12 coefficients; the strong ones push corners out of the source (pincushion) or fold the
 # far field back over the centre (barrel)
@@ -235,13 +238,18 @@ def test_argument_checks():
     assert L.mcorb_host_remap_u8(src.ctypes.data, w, w, h, m1.ctypes.data, m2.ctypes.data, dst.ctypes.data, w) == 0
 
 
-def test_strided_remap():
-    w, h = 160, 120
+def test_strided_remap(w=160, h=120, src_pad=24, dst_pad=8):
     st, m1, m2 = host_map(camera(w, h), MODELS[0][1], w, h)
-    src = image(3, w + 24, h)
-    dst = np.full((h, w + 8), 0xCD, np.uint8)
-    assert L.mcorb_host_remap_u8(src.ctypes.data, w + 24, w, h, m1.ctypes.data, m2.ctypes.data, dst.ctypes.data, w + 8) == 0
+    src = image(3, w + src_pad, h)
+    dst = np.full((h, w + dst_pad), 0xCD, np.uint8)
+    assert L.mcorb_host_remap_u8(src.ctypes.data, w + src_pad, w, h, m1.ctypes.data, m2.ctypes.data, dst.ctypes.data, w + dst_pad) == 0
     assert np.array_equal(dst[:, :w], R.remap(np.ascontiguousarray(src[:, :w]), m1, m2)[0]) and np.all(dst[:, w:] == 0xCD)
+
+
+@pytest.mark.parametrize("w,h", [(161, 120), (162, 121), (163, 123)])
+def test_strided_remap_at_unaligned_widths(w, h):
+    """odd paddings too: no row of either plane starts on a multiple of 4"""
+    test_strided_remap(w, h, 13, 5)
 
 
 # -- the header alone, plain g++ ------------------------------------------------------------------------------------------------
@@ -288,6 +296,21 @@ def test_header_under_plain_gxx_equals_restatement_and_library(exe, tmp_path, na
     with np.errstate(all="ignore"):
         r1, r2 = R.undistort_map(K, dist, w, h)
     assert np.array_equal(m1, r1) and np.array_equal(m2, r2) and np.array_equal(dst, R.remap(src, r1, r2)[0])
+    st, l1, l2 = host_map(K, dist, w, h)
+    assert st == 0 and np.array_equal(m1, l1) and np.array_equal(m2, l2)
+
+
+@pytest.mark.parametrize("w,h", [(161, 120), (163, 123)])
+def test_header_under_plain_gxx_at_widths_with_a_scalar_tail(exe, tmp_path, w, h):
+    name, dist = MODELS[1]   # the strong pincushion: taps outside the plane
+    K = camera(w, h)
+    src = image(23, w, h)
+    st, m1, m2, dst = run_exe(exe, str(tmp_path), K, dist, src)
+    assert st == 0
+    with np.errstate(all="ignore"):
+        r1, r2 = R.undistort_map(K, dist, w, h)
+    ref, outside = R.remap(src, r1, r2)
+    assert outside > 0 and np.array_equal(m1, r1) and np.array_equal(m2, r2) and np.array_equal(dst, ref)
     st, l1, l2 = host_map(K, dist, w, h)
     assert st == 0 and np.array_equal(m1, l1) and np.array_equal(m2, l2)
 
