@@ -364,7 +364,9 @@ int mcorb_match_ratio(mcorb_t *e, const uint8_t *q, int nq, const uint8_t *t, in
 typedef struct mcorb_vocab mcorb_vocab;
 /* nodes 1..nnodes in file order (node 0 is the root): parent id, leaf flag, 32-byte descriptor, weight.
  * scoring: 0 L1_NORM, 1 L2_NORM, 2 CHI_SQUARE, 3 KL, 4 BHATTACHARYYA, 5 DOT_PRODUCT;
- * weighting: 0 TF_IDF, 1 TF, 2 IDF, 3 BINARY (DBoW2's enums; ORBvoc.txt is "10 6 0 0"). */
+ * weighting: 0 TF_IDF, 1 TF, 2 IDF, 3 BINARY (DBoW2's enums; ORBvoc.txt is "10 6 0 0").
+ * device == -1: a host-only vocabulary (no device tables; the transforms return MCORB_E_NODEVICE), enough for a host-only
+ * keyframe database (mcorb_kfdb_create). */
 int mcorb_vocab_create(int k, int L, int scoring, int weighting, const int32_t *parent, const uint8_t *is_leaf,
                        const uint8_t *desc, const double *weight, int nnodes, int device, mcorb_vocab **out);
 /* TemplatedVocabulary::loadFromTextFile (FrontEnd.h:137-138) */
@@ -489,6 +491,64 @@ int mcorb_rig_get_lf_bow(mcorb_rig *r, int slot, int frame, uint32_t *bow_ids, d
  * row-major 3x4 matrices, problems back to back; 2 <= nv[i] <= MCORB_MAX_CAMS); branch[i] = the exit of the null-vector solver
  * taken: 0 zero trace, 1 unshifted steps only, 2 Rayleigh-quotient steps, 3 Sylvester check failed and re-run */
 int mcorb_dev_triangulate_selftest(int device, const double *x, const double *P, const int32_t *nv, int n, double *X, int32_t *branch);
+
+/* ------------------------------------------------------------------------- */
+/* Keyframe database: place recognition's consumer of lfBoW, lfFeatVec and    */
+/* the LF descriptors -- LoopCloser::callerDetectLoop (MCSlam/src/            */
+/* LoopCloser.cpp:59-193: orb_database->add :78, ->query :112, vocabulary     */
+/* score :119) and LoopCloser::featureMatchesBow (:195-241); Relocalization   */
+/* runs the same sequence (relocalization.cpp:64-99,205-237,327-360).         */
+/* DBoW2's TemplatedDatabase is un-vendored: its published semantics are      */
+/* restated (use_di = true, L1_NORM only).                                    */
+/* ------------------------------------------------------------------------- */
+typedef struct mcorb_kfdb mcorb_kfdb;
+#define MCORB_KFDB_MAX_WORDS 4096   /* a device database stages a query's BowVector in LDS: max_words <= this */
+/* A database of up to max_entries keyframes, each with a BowVector of up to max_words words and up to max_feats LF features
+ * (descriptors, FeatureVector nodes and feature indices): fixed strides per entry.  device >= 0: the store lives in HBM on that
+ * device, which must be the vocabulary's; queries, scores and featureMatchesBow's search run in HIP kernels.  device == -1: a
+ * host-only database that needs no GPU (DBoW2's own structure: a word-major inverted file); every call below works on it, and a
+ * host-only vocabulary (mcorb_vocab_create with device -1) is enough to create it.  Only L1_NORM vocabularies (scoring 0, what
+ * ORBvoc.txt is) are accepted: anything else is MCORB_E_ARG. */
+int mcorb_kfdb_create(const mcorb_vocab *v, int device, int max_entries, int max_words, int max_feats, mcorb_kfdb **out);
+void mcorb_kfdb_destroy(mcorb_kfdb *db);
+/* TemplatedDatabase::add(BowVector, FeatureVector) plus the keyframe's LF descriptors (ndesc x 32; m_image_intraMatches'
+ * matchDesc, LoopCloser.cpp:209-215), host vectors in the layout mcorb_vocab_transform writes; every (word, value) is stored as
+ * given.  *entry_out = the new entry id, counted from 0 (EntryId entryId = orb_database->size()).  MCORB_E_CAP, with nothing
+ * added, for a full database or vectors longer than the caps; MCORB_E_ARG for ids that do not ascend or feature indices outside
+ * the descriptor set. */
+int mcorb_kfdb_add(mcorb_kfdb *db, const uint32_t *bow_ids, const double *bow_vals, int nbow, const uint32_t *fv_nodes,
+                   const int32_t *fv_offsets, int nfv, const int32_t *fv_feats, const uint8_t *desc, int ndesc, int *entry_out);
+/* The same for lfBoW, lfFeatVec and the LF descriptors of a frame the slot's last job ran the LF stage on (mcorb_rig_set_lf;
+ * MCORB_E_STATE otherwise, like mcorb_rig_get_lf_bow).  The descriptors are gathered from the slot's descriptor block device to
+ * device on the slot's stream; the two vectors, which the job assembles on the host, are uploaded. */
+int mcorb_kfdb_add_rig_frame(mcorb_kfdb *db, mcorb_rig *r, int slot, int frame, int *entry_out);
+int mcorb_kfdb_size(const mcorb_kfdb *db);
+/* an entry as it is stored (a device database reads it back from HBM); MCORB_E_CAP with the counts set when an output is short */
+int mcorb_kfdb_get_entry(mcorb_kfdb *db, int entry, uint32_t *bow_ids, double *bow_vals, int bow_cap, int *nbow, uint32_t *fv_nodes,
+                         int32_t *fv_offsets, int fv_cap, int *nfv, int32_t *fv_feats, int feat_cap, uint8_t *desc, int desc_cap,
+                         int *ndesc);
+/* TemplatedDatabase::query(vec, ret, max_results, max_id), queryL1: every entry e with max_id == -1 || (int)e < max_id that
+ * shares a word with the query, scored with the sum over the shared words in ascending word id of (|q - d| - |q|) - |d| (fp64,
+ * one accumulator); the list in ascending entry id is sorted with std::sort by that raw value, cut to max_results when
+ * max_results > 0, and each score becomes -s / 2.0.  ids / scores: cap entries; *n_out = the count (MCORB_E_CAP when cap is short). */
+int mcorb_kfdb_query(mcorb_kfdb *db, const uint32_t *bow_ids, const double *bow_vals, int nbow, int max_results, int max_id,
+                     uint32_t *ids, double *scores, int cap, int *n_out);
+/* The same for nq queries that are entries of the database, in one launch (callerDetectLoop: add, then query yourself with
+ * maxId = entryId - dislocal).  Only entries below a query's max_id count, so a batch of keyframes can all be added first and
+ * then queried together, each with its own max_id: the results equal interleaved add / query (for max_id != -1, which is "no
+ * limit"; callerDetectLoop queries only when entryId > dislocal, :102-109, so its maxId is >= 1).  ids / scores: nq blocks of
+ * cap entries; n_out: nq counts. */
+int mcorb_kfdb_query_entries(mcorb_kfdb *db, const int32_t *entries, const int32_t *max_ids, int nq, int max_results, uint32_t *ids,
+                             double *scores, int cap, int *n_out);
+/* TemplatedVocabulary::score of two stored BowVectors (LoopCloser.cpp:119): 0 when they share no word */
+int mcorb_kfdb_score(mcorb_kfdb *db, int entry_a, int entry_b, double *score);
+/* LoopCloser::featureMatchesBow (:195-241): for every FeatureVector node the two entries share, in ascending node id,
+ * getMatches_distRatio (ORBextractor.cpp:1228-1290) of best_entry's descriptors (A) against curr_entry's (B), outputs appended in
+ * node order.  indices_1 index best_entry's LF set, indices_2 curr_entry's.  max_neighbor_ratio: 0.85 in the reference. */
+int mcorb_kfdb_feature_matches(mcorb_kfdb *db, int best_entry, int curr_entry, double max_neighbor_ratio, uint32_t *indices_1,
+                               uint32_t *indices_2, int cap, int *n_out);
+/* a device database's last k_kfdb_score (us[0]) and k_kfdb_best2 (us[1]) launch, microseconds between HIP events */
+int mcorb_kfdb_last_timing(mcorb_kfdb *db, float us[2]);
 
 /* ------------------------------------------------------------------------- */
 /* Host stages exposed for the CPU test-suite (no device needed)              */

@@ -780,6 +780,110 @@ class ORBVocabulary:
         return self._call(self.L_.mcorb_rig_transform_image, (rig.h_rig, slot, m, self.h), max(n, 0), levelsup)
 
 
+class ORBDatabase:
+    """DBoW2's ORBDatabase as place recognition uses it (LoopCloser::callerDetectLoop, MCSlam/src/LoopCloser.cpp:59-241): add,
+    query, the vocabulary's score of two stored vectors, and featureMatchesBow between two stored keyframes (mcorb_kfdb).
+    device >= 0: the store lives in HBM on the vocabulary's device; device = -1: a host-only database that needs no GPU."""
+
+    def __init__(self, voc, device=0, max_entries=1024, max_words=4096, max_feats=4096):
+        self.L = _lib.load()
+        self.h = C.c_void_p()
+        self.voc = voc   # (kept alive with the database)
+        self.max_entries, self.max_words, self.max_feats = max_entries, max_words, max_feats
+        _lib.check(self.L.mcorb_kfdb_create(voc.h, device, max_entries, max_words, max_feats, C.byref(self.h)))
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.mcorb_kfdb_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def add(self, bow, fv, desc):
+        """bow: (word ids ascending, values); fv: {node id: feature indices}; desc: the keyframe's LF descriptors -> entry id"""
+        ids = np.ascontiguousarray(bow[0], np.uint32)
+        vals = np.ascontiguousarray(bow[1], np.float64)
+        keys = sorted(fv)
+        nodes = np.array(keys, np.uint32)
+        offs = np.zeros(len(keys) + 1, np.int32)
+        offs[1:] = np.cumsum([len(fv[k]) for k in keys])
+        feats = np.concatenate([np.asarray(fv[k], np.int32).reshape(-1) for k in keys]).astype(np.int32) if keys else np.zeros(0, np.int32)
+        d = _u8(desc).reshape(-1, 32)
+        e = C.c_int()
+        _lib.check(self.L.mcorb_kfdb_add(self.h, ids.ctypes.data, vals.ctypes.data, len(ids), nodes.ctypes.data, offs.ctypes.data,
+                                         len(keys), feats.ctypes.data, d.ctypes.data, len(d), C.byref(e)))
+        return e.value
+
+    def add_rig_frame(self, rig, frame, slot=0):
+        """lfBoW, lfFeatVec and the LF descriptors of a frame of the slot's last job (Rig.set_lf) -> entry id"""
+        e = C.c_int()
+        _lib.check(self.L.mcorb_kfdb_add_rig_frame(self.h, rig.h_rig, slot, frame, C.byref(e)))
+        return e.value
+
+    def size(self):
+        return self.L.mcorb_kfdb_size(self.h)
+
+    def entry(self, i):
+        """-> (BowVector as (ids, values), FeatureVector as {node: feature indices}, descriptors) of entry i as stored"""
+        W, F = max(self.max_words, 1), max(self.max_feats, 1)
+        ids, vals = np.zeros(W, np.uint32), np.zeros(W, np.float64)
+        nodes, offs, feats = np.zeros(F, np.uint32), np.zeros(F + 1, np.int32), np.zeros(F, np.int32)
+        desc = np.zeros((F, 32), np.uint8)
+        nb, nf, nd = C.c_int(), C.c_int(), C.c_int()
+        _lib.check(self.L.mcorb_kfdb_get_entry(self.h, i, ids.ctypes.data, vals.ctypes.data, W, C.byref(nb), nodes.ctypes.data,
+                                               offs.ctypes.data, F, C.byref(nf), feats.ctypes.data, F, desc.ctypes.data, F, C.byref(nd)))
+        fv = {int(nodes[k]): feats[offs[k]:offs[k + 1]].copy() for k in range(nf.value)}
+        return (ids[:nb.value].copy(), vals[:nb.value].copy()), fv, desc[:nd.value].copy()
+
+    def query(self, bow, max_results, max_id=-1):
+        """TemplatedDatabase::query -> (entry ids, scores), best first"""
+        ids = np.ascontiguousarray(bow[0], np.uint32)
+        vals = np.ascontiguousarray(bow[1], np.float64)
+        cap = max(self.size(), 1)
+        out_ids, out_sc = np.zeros(cap, np.uint32), np.zeros(cap, np.float64)
+        n = C.c_int()
+        _lib.check(self.L.mcorb_kfdb_query(self.h, ids.ctypes.data, vals.ctypes.data, len(ids), max_results, max_id,
+                                           out_ids.ctypes.data, out_sc.ctypes.data, cap, C.byref(n)))
+        return out_ids[:n.value].copy(), out_sc[:n.value].copy()
+
+    def query_entries(self, entries, max_ids, max_results):
+        """the queries are entries of the database, all in one launch, each with its own max_id -> list of (entry ids, scores)"""
+        ent = np.ascontiguousarray(entries, np.int32)
+        mx = np.ascontiguousarray(max_ids, np.int32)
+        assert len(ent) == len(mx)
+        nq, cap = len(ent), max(self.size(), 1)
+        out_ids, out_sc = np.zeros((max(nq, 1), cap), np.uint32), np.zeros((max(nq, 1), cap), np.float64)
+        n = np.zeros(max(nq, 1), np.int32)
+        _lib.check(self.L.mcorb_kfdb_query_entries(self.h, ent.ctypes.data, mx.ctypes.data, nq, max_results, out_ids.ctypes.data,
+                                                   out_sc.ctypes.data, cap, n.ctypes.data))
+        return [(out_ids[q, :n[q]].copy(), out_sc[q, :n[q]].copy()) for q in range(nq)]
+
+    def score(self, a, b):
+        """TemplatedVocabulary::score of the BowVectors of entries a and b"""
+        s = C.c_double()
+        _lib.check(self.L.mcorb_kfdb_score(self.h, a, b, C.byref(s)))
+        return s.value
+
+    def featureMatchesBow(self, best_entry, curr_entry, max_neighbor_ratio=0.85):
+        """LoopCloser::featureMatchesBow -> (indices_1 into best_entry's LF set, indices_2 into curr_entry's)"""
+        cap = max(self.max_feats, 1)
+        i1, i2 = np.zeros(cap, np.uint32), np.zeros(cap, np.uint32)
+        n = C.c_int()
+        _lib.check(self.L.mcorb_kfdb_feature_matches(self.h, best_entry, curr_entry, max_neighbor_ratio, i1.ctypes.data, i2.ctypes.data,
+                                                     cap, C.byref(n)))
+        return i1[:n.value].copy(), i2[:n.value].copy()
+
+    def timing(self):
+        """microseconds of the last k_kfdb_score and k_kfdb_best2 launch (a device database)"""
+        us = (C.c_float * 2)()
+        _lib.check(self.L.mcorb_kfdb_last_timing(self.h, us))
+        return us[0], us[1]
+
+
 class DescriptorBlock:
     """nsets descriptor sets resident in HBM (mcorb_descblock): upload a keyframe's LF descriptors once, match any two sets with
     Rig.match_sets (findInterMatches' knnMatch, FrontEnd.cpp:3344-3500)."""

@@ -145,6 +145,17 @@ SIGNATURES = {
     "mcorb_rig_get_lf_features": (_i, [_vp, _i, _i, _vp, _i, _ip, _ip, _ip, _vp, _i, _ip]),
     "mcorb_rig_get_lf_bow": (_i, [_vp, _i, _i, _vp, _vp, _i, _ip, _vp, _vp, _i, _ip, _vp, _i]),
     "mcorb_dev_triangulate_selftest": (_i, [_i, _vp, _vp, _vp, _i, _vp, _vp]),
+    "mcorb_kfdb_create": (_i, [_vp, _i, _i, _i, _i, C.POINTER(_vp)]),
+    "mcorb_kfdb_destroy": (None, [_vp]),
+    "mcorb_kfdb_add": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _ip]),
+    "mcorb_kfdb_add_rig_frame": (_i, [_vp, _vp, _i, _i, _ip]),
+    "mcorb_kfdb_size": (_i, [_vp]),
+    "mcorb_kfdb_get_entry": (_i, [_vp, _i, _vp, _vp, _i, _ip, _vp, _vp, _i, _ip, _vp, _i, _vp, _i, _ip]),
+    "mcorb_kfdb_query": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _i, _ip]),
+    "mcorb_kfdb_query_entries": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _i, _vp]),
+    "mcorb_kfdb_score": (_i, [_vp, _i, _i, C.POINTER(C.c_double)]),
+    "mcorb_kfdb_feature_matches": (_i, [_vp, _i, _i, C.c_double, _vp, _vp, _i, _ip]),
+    "mcorb_kfdb_last_timing": (_i, [_vp, C.POINTER(_f)]),
     "mcorb_host_geometry": (_i, [C.POINTER(Params), _i, _i, _vp]),
     "mcorb_synth_rig_frame": (_i, [C.c_uint32, _i, _i, _i, _i, _vp, _i]),
 }

@@ -60,8 +60,10 @@ static int build_vocab(int k, int L, int scoring, int weighting, const int32_t *
         set_error("vocabulary: bad header or null argument");   // loadFromTextFile's own range check
         return MCORB_E_ARG;
     }
+    // device == -1: a host-only vocabulary (the tree and its header, no device tables): what a host-only keyframe database
+    // (mcorb_kfdb_create) is created on; transform() needs a device
     int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
+    if (device != -1 && (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)) {
         set_error("no usable HIP device (libmcorb has no CPU path)");
         return MCORB_E_NODEVICE;
     }
@@ -100,6 +102,7 @@ static int build_vocab(int k, int L, int scoring, int weighting, const int32_t *
             child_desc.insert(child_desc.end(), desc + (size_t)(c - 1) * 32, desc + (size_t)c * 32);
         }
     }
+    if (device == -1) { *out = v.release(); return MCORB_OK; }
     // device copies; a failure on the way releases the half-built object
     HIPCHK(hipSetDevice(device));
     TRY(v->d_child_start.alloc((size_t)n + 1));
@@ -213,6 +216,12 @@ static int emit(const BowList &bow, const std::map<uint32_t, std::vector<int32_t
     return MCORB_OK;
 }
 
+void mcorb::vocab_props(const mcorb_vocab *v, int &scoring, int &device)
+{
+    scoring = v->scoring;
+    device = v->device;
+}
+
 static int ensure_scratch(mcorb_vocab *v, int n)
 {
     const size_t cap = ((size_t)n + 1023) / 1024 * 1024;   // (a multiple of 1024 that holds n: what is there already, if that holds n)
@@ -301,6 +310,7 @@ int mcorb_vocab_transform(mcorb_vocab *v, const uint8_t *desc, int n, int levels
                           int32_t *fv_feats, int feat_cap)
 {
     if (!v || n < 0 || (n && !desc)) { set_error("transform: bad argument"); return MCORB_E_ARG; }
+    if (v->device < 0) { set_error("transform: a host-only vocabulary (device -1) has no device tables"); return MCORB_E_NODEVICE; }
     HIPCHK(hipSetDevice(v->device));
     std::lock_guard<std::mutex> scratch_lock(v->scratch_mu);
     int st = ensure_scratch(v, std::max(n, 1));

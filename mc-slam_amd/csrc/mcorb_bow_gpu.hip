@@ -10,28 +10,6 @@
 
 namespace mcorb {
 
-// popcount(x) + acc in one instruction; chaining the eight words of a 256-bit XOR through the
-// accumulator operand saves the separate adds the compiler otherwise emits
-__device__ __forceinline__ uint32_t bcnt_acc(uint32_t x, uint32_t acc)
-{
-    uint32_t r;
-    asm("v_bcnt_u32_b32 %0, %1, %2" : "=v"(r) : "v"(x), "v"(acc));
-    return r;
-}
-__device__ __forceinline__ uint32_t hamming256(const ulonglong4 &a, const ulonglong4 &b)
-{
-    const unsigned long long x0 = a.x ^ b.x, x1 = a.y ^ b.y, x2 = a.z ^ b.z, x3 = a.w ^ b.w;
-    uint32_t d = __builtin_popcount((uint32_t)x0);
-    d = bcnt_acc((uint32_t)(x0 >> 32), d);
-    d = bcnt_acc((uint32_t)x1, d);
-    d = bcnt_acc((uint32_t)(x1 >> 32), d);
-    d = bcnt_acc((uint32_t)x2, d);
-    d = bcnt_acc((uint32_t)(x2 >> 32), d);
-    d = bcnt_acc((uint32_t)x3, d);
-    d = bcnt_acc((uint32_t)(x3 >> 32), d);
-    return d;
-}
-
 // ---------------------------------------------------------------------------
 // DBoW2 vocabulary-tree descent (TemplatedVocabulary::transform's per-feature part, used by
 // MultiCameraFrame::extractFeatureSingle, MultiCameraFrame.cpp:257): from the root, move to the child

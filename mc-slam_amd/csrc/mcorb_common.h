@@ -61,6 +61,11 @@ __host__ __device__ inline BowRecView bow_rec(int *base, int kcap, int m)
     return v;
 }
 
+// the keyframe database (mcorb_kfdb): k_kfdb_score stages a query's (word id, value) list in LDS, 12 bytes a word, and a workgroup
+// scores a run of entries against it
+constexpr int kKfdbMaxWords = 4096;          // MCORB_KFDB_MAX_WORDS: 48 KB of LDS
+constexpr int kKfdbEntriesPerBlock = 32;
+
 // obtainLfFeatures inside the job (mcorb_rig_set_lf): k_lf_tracks' input per track with two views or more -- {first view in the
 // view list, view count, rig frame in the slot, output record} -- its views {camera, keypoint, raw point}, and its result per
 // track: the triangulated point, K_0 X projected to the reference camera (uv_ref), the 0.5 < z < 40 gate and the view whose

@@ -488,6 +488,8 @@ int bow_job_finish(Rig &R, Slot &s, int nimg);
 int lf_job_finish(Rig &R, Slot &s, int nframes);
 // transform()'s BowVector / FeatureVector (mcorb_bow.cpp's assemble) of n descent results, for the given weighting / scoring
 void bow_assemble(int weighting, int scoring, const BowRes *res, int n, BowImageOut &o);
+// scoring type (DBoW2's enum) and device (-1: a host-only vocabulary) of a vocabulary (mcorb_bow.cpp), for the keyframe database
+void vocab_props(const ::mcorb_vocab *v, int &scoring, int &device);
 
 }  // namespace mcorb
 

@@ -130,4 +130,16 @@ void launch_lf_tracks(hipStream_t st, const int4 *trk, const LfView *views, int 
 // the same triangulation on n arbitrary problems (mcorb_dev_triangulate_selftest)
 void launch_tri_selftest(hipStream_t st, const double *x, const double *P, const int *nv, const int *voff, int n, double *X, int *branch);
 
+// the keyframe database's kernels (mcorb_kfdb_gpu.hip).  k_kfdb_score: nq queries (q_sel[q] indexes q_ids / q_vals / q_n, strided
+// like the store) against entries [0, q_limit[q]) -- or, with e_list, against entry e_list[q * out_stride + x] for x below the
+// limit -- raw sum and shared-word count to raw / shared[q * out_stride + x]; max_limit = the largest q_limit
+void launch_kfdb_score(hipStream_t st, const uint32_t *ids, const double *vals, const int *nbow, int stride, const uint32_t *q_ids,
+                       const double *q_vals, const int *q_n, const int *q_sel, const int *q_limit, const int *e_list, int nq,
+                       int max_limit, int out_stride, double *raw, int *shared);
+// k_kfdb_best2: items {position in feats_a, shared node}, nodes {first position, count} in feats_b -> {best B feature or -1, best, second, A feature}
+void launch_kfdb_best2(hipStream_t st, const uint8_t *desc_a, const int *feats_a, const uint8_t *desc_b, const int *feats_b,
+                       const int2 *items, int nitems, const int2 *nodes, int4 *out);
+// k_kfdb_gather: dst[i] = descriptor src[i] of desc, 32 bytes each
+void launch_kfdb_gather(hipStream_t st, const uint8_t *desc, const int *src, int n, uint8_t *dst);
+
 }  // namespace mcorb
