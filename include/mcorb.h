@@ -550,6 +550,51 @@ int mcorb_kfdb_feature_matches(mcorb_kfdb *db, int best_entry, int curr_entry, d
 /* a device database's last k_kfdb_score (us[0]) and k_kfdb_best2 (us[1]) launch, microseconds between HIP events */
 int mcorb_kfdb_last_timing(mcorb_kfdb *db, float us[2]);
 
+/* Probe slots: a frame's lfBoW, lfFeatVec and LF descriptors held in the database's layout (the strides and caps of an entry)
+ * WITHOUT being an entry -- the current frame of FrontEnd::trackFrame (FrontEnd.cpp:6015-6023), which is matched against the last
+ * keyframe and deleted when it is not one, and of Relocalization (relocalization.cpp:327-371), which queries the database with
+ * a frame that is never added.  No probe call changes the size, an entry, or the result of any call above.
+ * reserve_probes allocates nprobes slots (1 .. 128), once per database (MCORB_E_STATE the second time).  set_probe takes
+ * mcorb_kfdb_add's arguments and validates them the same way (MCORB_E_CAP / MCORB_E_ARG leave the slot as it was); setting a slot
+ * again overwrites it.  set_probe_rig_frame is mcorb_kfdb_add_rig_frame's path into a slot (same MCORB_E_STATE conditions).
+ * get_probe reads a slot back as mcorb_kfdb_get_entry reads an entry.  Every call that names a slot that was never set is
+ * MCORB_E_STATE; a slot index outside [0, nprobes) is MCORB_E_ARG. */
+int mcorb_kfdb_reserve_probes(mcorb_kfdb *db, int nprobes);
+int mcorb_kfdb_set_probe(mcorb_kfdb *db, int probe, const uint32_t *bow_ids, const double *bow_vals, int nbow, const uint32_t *fv_nodes,
+                         const int32_t *fv_offsets, int nfv, const int32_t *fv_feats, const uint8_t *desc, int ndesc);
+int mcorb_kfdb_set_probe_rig_frame(mcorb_kfdb *db, int probe, mcorb_rig *r, int slot, int frame);
+int mcorb_kfdb_get_probe(mcorb_kfdb *db, int probe, uint32_t *bow_ids, double *bow_vals, int bow_cap, int *nbow, uint32_t *fv_nodes,
+                         int32_t *fv_offsets, int fv_cap, int *nfv, int32_t *fv_feats, int feat_cap, uint8_t *desc, int desc_cap,
+                         int *ndesc);
+/* mcorb_kfdb_query_entries / mcorb_kfdb_score with probes as the queries: one launch for all nq probes; a probe's result equals
+ * mcorb_kfdb_query of the same vectors.  score_probe: TemplatedVocabulary::score(entry's BowVector, probe's). */
+int mcorb_kfdb_query_probes(mcorb_kfdb *db, const int32_t *probes, const int32_t *max_ids, int nq, int max_results, uint32_t *ids,
+                            double *scores, int cap, int *n_out);
+int mcorb_kfdb_score_probe(mcorb_kfdb *db, int entry, int probe, double *score);
+/* FrontEnd::InterMatchingBow (FrontEnd.cpp:3676-3788, as findInterMatchesBow calls it, :3905-3971) / Relocalization::
+ * featureMatchesBow (relocalization.cpp:327-371) of one entry (A: the last keyframe, the best candidate) against np probes: per
+ * probe, mcorb_kfdb_feature_matches' walk -- getMatches_distRatio(A, B) for every FeatureVector node entry and probe share, in
+ * ascending node id, outputs appended (itr_cng_match is unused in the reference).  A device database searches all probes in one
+ * launch of k_kfdb_best2_probes and one copy back.  indices_1 (into the entry's LF set) and indices_2 (into the probe's): np
+ * blocks of cap; n_out: np counts (MCORB_E_CAP when a block is short, with the counts set).  The reference's `words` are the
+ * entry's FeatureVector nodes of indices_1. */
+int mcorb_kfdb_probe_feature_matches(mcorb_kfdb *db, int entry, const int32_t *probes, int np, double max_neighbor_ratio,
+                                     uint32_t *indices_1, uint32_t *indices_2, int cap, int *n_out);
+/* FrontEnd::findInterMatches (FrontEnd.cpp:3344-3499) of an entry (lf_prev) and a probe (lf_cur): knnMatch(descs_prev, descs_cur,
+ * 2) -- BFMatcher's order, the lowest train index first among equal distances; a device database runs it through the k-NN kernel
+ * of mcorb_knn2 -- and then, in query order: a row whose lids_prev is -1 is dropped when (double)d0 > 0.7 * (double)d1 (rows of
+ * landmarks skip that); when neither feature is mono, the row is dropped unless (float)sqrt(dx*dx + dy*dy + dz*dz) <= 2.0 (fp64,
+ * summed in that order: cv::norm of the 3x1 CV_64F difference); the first row to claim a train index holds its output position
+ * and a later one replaces it only when strictly closer.  lids_prev / mono_prev / p3d_prev (n x 3): per LF feature of the entry;
+ * mono_cur / p3d_cur: of the probe.  query_idx / train_idx / dist: matches_z_filtered, cap rows.  The one divergence: with a
+ * probe of fewer than two features the reference reads m[1] out of bounds; here a row without a second neighbour is dropped
+ * unless it is a landmark's.  An empty set on either side gives no match.  (Device: max_feats <= 65535, MCORB_E_SIZE otherwise.) */
+int mcorb_kfdb_probe_inter_matches_bf(mcorb_kfdb *db, int entry, int probe, const int32_t *lids_prev, const uint8_t *mono_prev,
+                                      const double *p3d_prev, const uint8_t *mono_cur, const double *p3d_cur, int32_t *query_idx,
+                                      int32_t *train_idx, int32_t *dist, int cap, int *n_out);
+/* a device database's last k_kfdb_best2_probes launch, microseconds between HIP events */
+int mcorb_kfdb_last_probe_timing(mcorb_kfdb *db, float *us);
+
 /* ------------------------------------------------------------------------- */
 /* Host stages exposed for the CPU test-suite (no device needed)              */
 /* ------------------------------------------------------------------------- */

@@ -782,7 +782,8 @@ class ORBVocabulary:
 
 class ORBDatabase:
     """DBoW2's ORBDatabase as place recognition uses it (LoopCloser::callerDetectLoop, MCSlam/src/LoopCloser.cpp:59-241): add,
-    query, the vocabulary's score of two stored vectors, and featureMatchesBow between two stored keyframes (mcorb_kfdb).
+    query, the vocabulary's score of two stored vectors, and featureMatchesBow between two stored keyframes (mcorb_kfdb); probe
+    slots hold the frames that are matched against keyframes without becoming one (tracking, relocalization).
     device >= 0: the store lives in HBM on the vocabulary's device; device = -1: a host-only database that needs no GPU."""
 
     def __init__(self, voc, device=0, max_entries=1024, max_words=4096, max_feats=4096):
@@ -803,8 +804,9 @@ class ORBDatabase:
         except Exception:
             pass
 
-    def add(self, bow, fv, desc):
-        """bow: (word ids ascending, values); fv: {node id: feature indices}; desc: the keyframe's LF descriptors -> entry id"""
+    @staticmethod
+    def _vectors(bow, fv, desc):
+        """a frame's vectors as the C ABI takes them: the arrays (kept alive by the caller) and mcorb_kfdb_add's argument list"""
         ids = np.ascontiguousarray(bow[0], np.uint32)
         vals = np.ascontiguousarray(bow[1], np.float64)
         keys = sorted(fv)
@@ -813,9 +815,15 @@ class ORBDatabase:
         offs[1:] = np.cumsum([len(fv[k]) for k in keys])
         feats = np.concatenate([np.asarray(fv[k], np.int32).reshape(-1) for k in keys]).astype(np.int32) if keys else np.zeros(0, np.int32)
         d = _u8(desc).reshape(-1, 32)
+        keep = (ids, vals, nodes, offs, feats, d)
+        return keep, (ids.ctypes.data, vals.ctypes.data, len(ids), nodes.ctypes.data, offs.ctypes.data, len(keys), feats.ctypes.data,
+                      d.ctypes.data, len(d))
+
+    def add(self, bow, fv, desc):
+        """bow: (word ids ascending, values); fv: {node id: feature indices}; desc: the keyframe's LF descriptors -> entry id"""
+        keep, args = self._vectors(bow, fv, desc)
         e = C.c_int()
-        _lib.check(self.L.mcorb_kfdb_add(self.h, ids.ctypes.data, vals.ctypes.data, len(ids), nodes.ctypes.data, offs.ctypes.data,
-                                         len(keys), feats.ctypes.data, d.ctypes.data, len(d), C.byref(e)))
+        _lib.check(self.L.mcorb_kfdb_add(self.h, *args, C.byref(e)))
         return e.value
 
     def add_rig_frame(self, rig, frame, slot=0):
@@ -827,17 +835,20 @@ class ORBDatabase:
     def size(self):
         return self.L.mcorb_kfdb_size(self.h)
 
-    def entry(self, i):
-        """-> (BowVector as (ids, values), FeatureVector as {node: feature indices}, descriptors) of entry i as stored"""
+    def _stored(self, get, i):
         W, F = max(self.max_words, 1), max(self.max_feats, 1)
         ids, vals = np.zeros(W, np.uint32), np.zeros(W, np.float64)
         nodes, offs, feats = np.zeros(F, np.uint32), np.zeros(F + 1, np.int32), np.zeros(F, np.int32)
         desc = np.zeros((F, 32), np.uint8)
         nb, nf, nd = C.c_int(), C.c_int(), C.c_int()
-        _lib.check(self.L.mcorb_kfdb_get_entry(self.h, i, ids.ctypes.data, vals.ctypes.data, W, C.byref(nb), nodes.ctypes.data,
-                                               offs.ctypes.data, F, C.byref(nf), feats.ctypes.data, F, desc.ctypes.data, F, C.byref(nd)))
+        _lib.check(get(self.h, i, ids.ctypes.data, vals.ctypes.data, W, C.byref(nb), nodes.ctypes.data, offs.ctypes.data, F, C.byref(nf),
+                       feats.ctypes.data, F, desc.ctypes.data, F, C.byref(nd)))
         fv = {int(nodes[k]): feats[offs[k]:offs[k + 1]].copy() for k in range(nf.value)}
         return (ids[:nb.value].copy(), vals[:nb.value].copy()), fv, desc[:nd.value].copy()
+
+    def entry(self, i):
+        """-> (BowVector as (ids, values), FeatureVector as {node: feature indices}, descriptors) of entry i as stored"""
+        return self._stored(self.L.mcorb_kfdb_get_entry, i)
 
     def query(self, bow, max_results, max_id=-1):
         """TemplatedDatabase::query -> (entry ids, scores), best first"""
@@ -882,6 +893,77 @@ class ORBDatabase:
         us = (C.c_float * 2)()
         _lib.check(self.L.mcorb_kfdb_last_timing(self.h, us))
         return us[0], us[1]
+
+    # probe slots: frames held in the database's layout without being entries (the current frame of FrontEnd::trackFrame and of
+    # Relocalization); no call below changes size(), an entry or a query's result
+    def reserve_probes(self, nprobes):
+        """allocates nprobes (1 .. 128) probe slots; once per database"""
+        _lib.check(self.L.mcorb_kfdb_reserve_probes(self.h, nprobes))
+
+    def set_probe(self, probe, bow, fv, desc):
+        """add()'s arguments into probe slot `probe` (overwrites it)"""
+        keep, args = self._vectors(bow, fv, desc)
+        _lib.check(self.L.mcorb_kfdb_set_probe(self.h, probe, *args))
+
+    def set_probe_rig_frame(self, probe, rig, frame, slot=0):
+        """add_rig_frame()'s frame into probe slot `probe`"""
+        _lib.check(self.L.mcorb_kfdb_set_probe_rig_frame(self.h, probe, rig.h_rig, slot, frame))
+
+    def get_probe(self, probe):
+        """-> (BowVector, FeatureVector, descriptors) of a probe slot as stored, like entry()"""
+        return self._stored(self.L.mcorb_kfdb_get_probe, probe)
+
+    def query_probes(self, probes, max_ids, max_results):
+        """query_entries() with probe slots as the queries, all in one launch -> list of (entry ids, scores)"""
+        pr = np.ascontiguousarray(probes, np.int32)
+        mx = np.ascontiguousarray(max_ids, np.int32)
+        assert len(pr) == len(mx)
+        nq, cap = len(pr), max(self.size(), 1)
+        out_ids, out_sc = np.zeros((max(nq, 1), cap), np.uint32), np.zeros((max(nq, 1), cap), np.float64)
+        n = np.zeros(max(nq, 1), np.int32)
+        _lib.check(self.L.mcorb_kfdb_query_probes(self.h, pr.ctypes.data, mx.ctypes.data, nq, max_results, out_ids.ctypes.data,
+                                                  out_sc.ctypes.data, cap, n.ctypes.data))
+        return [(out_ids[q, :n[q]].copy(), out_sc[q, :n[q]].copy()) for q in range(nq)]
+
+    def score_probe(self, entry, probe):
+        """TemplatedVocabulary::score of an entry's BowVector and a probe's"""
+        s = C.c_double()
+        _lib.check(self.L.mcorb_kfdb_score_probe(self.h, entry, probe, C.byref(s)))
+        return s.value
+
+    def probe_feature_matches(self, entry, probes, max_neighbor_ratio=0.85):
+        """FrontEnd::InterMatchingBow / Relocalization::featureMatchesBow of one entry against several probes in one launch ->
+        list of (indices_1 into the entry's LF set, indices_2 into the probe's)"""
+        pr = np.ascontiguousarray(probes, np.int32)
+        np_, cap = len(pr), max(self.max_feats, 1)
+        i1, i2 = np.zeros((max(np_, 1), cap), np.uint32), np.zeros((max(np_, 1), cap), np.uint32)
+        n = np.zeros(max(np_, 1), np.int32)
+        _lib.check(self.L.mcorb_kfdb_probe_feature_matches(self.h, entry, pr.ctypes.data, np_, max_neighbor_ratio, i1.ctypes.data,
+                                                           i2.ctypes.data, cap, n.ctypes.data))
+        return [(i1[p, :n[p]].copy(), i2[p, :n[p]].copy()) for p in range(np_)]
+
+    def probe_inter_matches_bf(self, entry, probe, lids_prev, mono_prev, p3d_prev, mono_cur, p3d_cur):
+        """FrontEnd::findInterMatches of an entry (lf_prev) and a probe (lf_cur): lids_prev / mono_prev / p3d_prev (n x 3) per LF
+        feature of the entry, mono_cur / p3d_cur of the probe -> (queryIdx, trainIdx, distance) of matches_z_filtered"""
+        lids = np.ascontiguousarray(lids_prev, np.int32).reshape(-1)
+        m1 = np.ascontiguousarray(np.asarray(mono_prev) != 0, np.uint8).reshape(-1)
+        m2 = np.ascontiguousarray(np.asarray(mono_cur) != 0, np.uint8).reshape(-1)
+        p1 = np.ascontiguousarray(p3d_prev, np.float64).reshape(-1, 3)
+        p2 = np.ascontiguousarray(p3d_cur, np.float64).reshape(-1, 3)
+        assert len(lids) == len(m1) == len(p1) and len(m2) == len(p2)
+        cap = max(self.max_feats, 1)
+        q, t, d = np.zeros(cap, np.int32), np.zeros(cap, np.int32), np.zeros(cap, np.int32)
+        n = C.c_int()
+        _lib.check(self.L.mcorb_kfdb_probe_inter_matches_bf(self.h, entry, probe, lids.ctypes.data, m1.ctypes.data, p1.ctypes.data,
+                                                            m2.ctypes.data, p2.ctypes.data, q.ctypes.data, t.ctypes.data, d.ctypes.data,
+                                                            cap, C.byref(n)))
+        return q[:n.value].copy(), t[:n.value].copy(), d[:n.value].copy()
+
+    def probe_timing(self):
+        """microseconds of the last k_kfdb_best2_probes launch (a device database)"""
+        us = C.c_float()
+        _lib.check(self.L.mcorb_kfdb_last_probe_timing(self.h, C.byref(us)))
+        return us.value
 
 
 class DescriptorBlock:

@@ -156,6 +156,15 @@ SIGNATURES = {
     "mcorb_kfdb_score": (_i, [_vp, _i, _i, C.POINTER(C.c_double)]),
     "mcorb_kfdb_feature_matches": (_i, [_vp, _i, _i, C.c_double, _vp, _vp, _i, _ip]),
     "mcorb_kfdb_last_timing": (_i, [_vp, C.POINTER(_f)]),
+    "mcorb_kfdb_reserve_probes": (_i, [_vp, _i]),
+    "mcorb_kfdb_set_probe": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i]),
+    "mcorb_kfdb_set_probe_rig_frame": (_i, [_vp, _i, _vp, _i, _i]),
+    "mcorb_kfdb_get_probe": (_i, [_vp, _i, _vp, _vp, _i, _ip, _vp, _vp, _i, _ip, _vp, _i, _vp, _i, _ip]),
+    "mcorb_kfdb_query_probes": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _i, _vp]),
+    "mcorb_kfdb_score_probe": (_i, [_vp, _i, _i, C.POINTER(C.c_double)]),
+    "mcorb_kfdb_probe_feature_matches": (_i, [_vp, _i, _vp, _i, C.c_double, _vp, _vp, _i, _vp]),
+    "mcorb_kfdb_probe_inter_matches_bf": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _ip]),
+    "mcorb_kfdb_last_probe_timing": (_i, [_vp, C.POINTER(_f)]),
     "mcorb_host_geometry": (_i, [C.POINTER(Params), _i, _i, _vp]),
     "mcorb_synth_rig_frame": (_i, [C.c_uint32, _i, _i, _i, _i, _vp, _i]),
 }

@@ -17,6 +17,12 @@
 //                 with `+=` in query-word order, and the literal getMatches_distRatio loop over the descriptors.
 // The final std::sort and the cut run on the host in both, on the same ascending-id input, so the order among equal scores is
 // libstdc++'s in both (the dependence mcorb_sortmodel.h documents for selection).
+//
+// Probe slots hold a frame in the same layout without making it an entry: the current frame of FrontEnd::trackFrame
+// (findInterMatchesBow -> InterMatchingBow, FrontEnd.cpp:3676-3788; findInterMatches, :3344-3499) and of Relocalization
+// (relocalization.cpp:327-371).  They are queried, scored and matched against entries; nothing they do touches n, the inverted
+// file or an entry.  In the descriptor allocation the probe slots lie behind the entries, all sets `fstride` rows apart, so
+// that findInterMatches' knnMatch of an entry and a probe is one launch_knn2 on two sets of one base.
 #include <math.h>
 #include <string.h>
 
@@ -33,6 +39,7 @@ using namespace mcorb;
 namespace {
 
 constexpr int TH_LOW = 75;   // ORBextractor.h:27
+constexpr int kMaxProbes = 128;
 
 struct Result {   // DBoW2::Result: ordered by score alone
     uint32_t id;
@@ -68,10 +75,14 @@ struct Vectors {   // a keyframe's vectors in mcorb_vocab_transform's layout
 struct mcorb_kfdb {
     int device = -1, max_entries = 0, max_words = 0, max_feats = 0;
     int n = 0;
+    int nprobes = 0;   // 0: mcorb_kfdb_reserve_probes has not run
+    int fstride = 0;   // descriptor rows per set in d_desc: max_feats rounded up to launch_knn2's multiple of 64
+    std::vector<char> probe_set;
     std::mutex mu;   // one call at a time: the scratch below is the database's
     // host-only database
     std::vector<HostEntry> entries;
     std::map<uint32_t, std::vector<std::pair<uint32_t, double>>> ifile;   // word -> (entry, value), entries ascending
+    std::vector<HostEntry> probes;
     // device database: the store, strided per entry
     Stream st;
     Event ev0, ev1;
@@ -79,8 +90,14 @@ struct mcorb_kfdb {
     DevBuf<double> d_vals;               // [max_words]
     DevBuf<int> d_nbow;                  // one per entry
     DevBuf<int> d_offs, d_feats;         // [max_feats + 1], [max_feats]
-    DevBuf<uint8_t> d_desc;              // [max_feats][32]
+    DevBuf<uint8_t> d_desc;              // [fstride][32]: the entries, then the probe slots
+    DevBuf<int> d_ndesc;                 // descriptors of each set of d_desc (launch_knn2's counts)
     std::vector<Mirror> mirror;
+    // the probe store: the entries' strides
+    DevBuf<uint32_t> p_ids, p_nodes;
+    DevBuf<double> p_vals;
+    DevBuf<int> p_nbow, p_offs, p_feats;
+    std::vector<Mirror> pmirror;
     // a host query vector's place on the device (one entry's stride), the control arrays and results of a launch (grow-only)
     DevBuf<uint32_t> d_qids;
     DevBuf<double> d_qvals;
@@ -89,18 +106,26 @@ struct mcorb_kfdb {
     HostBuf<double> h_raw;
     HostBuf<int> h_shared;
     DevBuf<int2> d_items, d_mnodes;
-    DevBuf<int4> d_mtab;
+    DevBuf<int4> d_mtab, d_pnodes;
     HostBuf<int4> h_mtab;
-    float us_score = 0.f, us_best2 = 0.f;   // the last launch of each kernel, between HIP events
+    // launch_knn2's scratch for one (entry, probe) pair at capacity fstride; the control words and results are host-mapped
+    DevBuf<uint8_t> d_exp;
+    DevBuf<int> d_lcounts;
+    DevBuf<uint2> d_part;
+    HostBuf<int> h_knnctl, h_mcount;     // {setmap[2], pair}
+    HostBuf<KnnRow> h_rows;
+    HostBuf<uint32_t> h_mlist;
+    float us_score = 0.f, us_best2 = 0.f, us_best2p = 0.f;   // the last launch of each kernel, between HIP events
 };
 
-static int check_vectors(const mcorb_kfdb *db, const Vectors &v, int ndesc)
+// (entry: the vectors become a new entry, which needs room; a probe slot is overwritten)
+static int check_vectors(const mcorb_kfdb *db, const Vectors &v, int ndesc, bool entry)
 {
     if (v.nbow < 0 || v.nfv < 0 || ndesc < 0 || (v.nbow && (!v.bow_ids || !v.bow_vals)) || (v.nfv && (!v.fv_nodes || !v.fv_offsets))) {
         set_error("kfdb add: bad argument");
         return MCORB_E_ARG;
     }
-    if (db->n >= db->max_entries) { set_error("kfdb add: the database is full (max_entries)"); return MCORB_E_CAP; }
+    if (entry && db->n >= db->max_entries) { set_error("kfdb add: the database is full (max_entries)"); return MCORB_E_CAP; }
     if (v.nbow > db->max_words || v.nfv > db->max_feats || ndesc > db->max_feats) {
         set_error("kfdb add: a vector is longer than the database's caps (max_words / max_feats)");
         return MCORB_E_CAP;
@@ -119,35 +144,52 @@ static int check_vectors(const mcorb_kfdb *db, const Vectors &v, int ndesc)
     return MCORB_OK;
 }
 
-// the entry's BowVector and FeatureVector to its place in the store, on `st` (the descriptors are the caller's)
-static int store_vectors(mcorb_kfdb *db, int e, const Vectors &v, hipStream_t st)
+// a frame's rows in the device store: entry e, or probe slot e (whose descriptors lie behind the entries')
+struct Place {
+    uint32_t *ids; double *vals; int *nbow;
+    uint32_t *nodes; int *offs, *feats;
+    uint8_t *desc; int *ndesc;
+};
+
+static Place place_of(const mcorb_kfdb *db, int e, bool probe)
 {
-    const size_t W = (size_t)db->max_words, F = (size_t)db->max_feats;
+    const size_t i = (size_t)e, W = (size_t)db->max_words, F = (size_t)db->max_feats;
+    const size_t set = probe ? (size_t)db->max_entries + i : i;
+    if (probe)
+        return Place{db->p_ids + i * W, db->p_vals + i * W, db->p_nbow + i, db->p_nodes + i * F, db->p_offs + i * (F + 1), db->p_feats + i * F,
+                     db->d_desc + set * db->fstride * 32, db->d_ndesc + set};
+    return Place{db->d_ids + i * W, db->d_vals + i * W, db->d_nbow + i, db->d_nodes + i * F, db->d_offs + i * (F + 1), db->d_feats + i * F,
+                 db->d_desc + set * db->fstride * 32, db->d_ndesc + set};
+}
+
+// a frame's BowVector, FeatureVector and descriptor count to its place in the store, on `st` (the descriptors are the caller's)
+static int store_vectors(const Place &p, const Vectors &v, const int &ndesc, hipStream_t st)
+{
     if (v.nbow) {
-        HIPCHK(hipMemcpyAsync(db->d_ids + e * W, v.bow_ids, (size_t)v.nbow * 4, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(db->d_vals + e * W, v.bow_vals, (size_t)v.nbow * 8, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(p.ids, v.bow_ids, (size_t)v.nbow * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(p.vals, v.bow_vals, (size_t)v.nbow * 8, hipMemcpyHostToDevice, st));
     }
-    HIPCHK(hipMemcpyAsync(db->d_nbow + e, &v.nbow, sizeof(int), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(p.nbow, &v.nbow, sizeof(int), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(p.ndesc, &ndesc, sizeof(int), hipMemcpyHostToDevice, st));
     if (v.nfv) {
-        HIPCHK(hipMemcpyAsync(db->d_nodes + e * F, v.fv_nodes, (size_t)v.nfv * 4, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(db->d_offs + e * (F + 1), v.fv_offsets, (size_t)(v.nfv + 1) * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(p.nodes, v.fv_nodes, (size_t)v.nfv * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(p.offs, v.fv_offsets, (size_t)(v.nfv + 1) * 4, hipMemcpyHostToDevice, st));
     }
-    if (v.nff) HIPCHK(hipMemcpyAsync(db->d_feats + e * F, v.fv_feats, (size_t)v.nff * 4, hipMemcpyHostToDevice, st));
+    if (v.nff) HIPCHK(hipMemcpyAsync(p.feats, v.fv_feats, (size_t)v.nff * 4, hipMemcpyHostToDevice, st));
     return MCORB_OK;
 }
 
-static void commit_mirror(mcorb_kfdb *db, const Vectors &v, int ndesc)
+static Mirror mirror_of(const Vectors &v, int ndesc)
 {
     Mirror m;
     m.nbow = v.nbow; m.nfv = v.nfv; m.nff = v.nff; m.ndesc = ndesc;
     m.nodes.assign(v.fv_nodes, v.fv_nodes + v.nfv);
     if (v.nfv) m.offs.assign(v.fv_offsets, v.fv_offsets + v.nfv + 1);
     else m.offs.assign(1, 0);
-    db->mirror.push_back(std::move(m));
-    db->n++;
+    return m;
 }
 
-static void add_host(mcorb_kfdb *db, const Vectors &v, const uint8_t *desc, int ndesc)
+static HostEntry host_entry_of(const Vectors &v, const uint8_t *desc, int ndesc)
 {
     HostEntry h;
     h.ids.assign(v.bow_ids, v.bow_ids + v.nbow);
@@ -157,10 +199,81 @@ static void add_host(mcorb_kfdb *db, const Vectors &v, const uint8_t *desc, int 
     else h.offs.assign(1, 0);
     h.feats.assign(v.fv_feats, v.fv_feats + v.nff);
     h.desc.assign(desc, desc + (size_t)ndesc * 32);
-    const uint32_t e = (uint32_t)db->n;   // EntryId entry_id = m_nentries++
-    for (int i = 0; i < v.nbow; i++) db->ifile[v.bow_ids[i]].emplace_back(e, v.bow_vals[i]);   // m_ifile[word_id].push_back(IFPair(entry_id, word_weight))
-    db->entries.push_back(std::move(h));
-    db->n++;
+    return h;
+}
+
+// What add, add_rig_frame, set_probe and set_probe_rig_frame share: a frame's vectors and descriptors become entry db->n
+// (probe < 0) or overwrite probe slot `probe`.  The descriptors are host rows (desc), or, for a rig frame (s, o), rows of the
+// slot's descriptor block in HBM (LfFrameOut::src) gathered device to device on the slot's stream; lfBoW and lfFeatVec are
+// assembled on the host (lf_job_finish) and uploaded.  Nothing is stored when the vectors fail check_vectors.
+static int put_frame(mcorb_kfdb *db, int probe, const Vectors &v, const uint8_t *desc, int ndesc, Slot *s, const LfFrameOut *o)
+{
+    TRY(check_vectors(db, v, ndesc, probe < 0));
+    if (db->device < 0) {
+        std::vector<uint8_t> rows;
+        if (o) {
+            rows.resize((size_t)ndesc * 32);
+            for (int i = 0; i < ndesc; i++) memcpy(rows.data() + (size_t)i * 32, o->feats[i].desc, 32);
+            desc = rows.data();
+        }
+        HostEntry h = host_entry_of(v, desc, ndesc);
+        if (probe >= 0) {
+            db->probes[probe] = std::move(h);
+            db->probe_set[probe] = 1;
+            return MCORB_OK;
+        }
+        const uint32_t e = (uint32_t)db->n;   // EntryId entry_id = m_nentries++
+        for (int i = 0; i < v.nbow; i++) db->ifile[v.bow_ids[i]].emplace_back(e, v.bow_vals[i]);   // m_ifile[word_id].push_back(IFPair(entry_id, word_weight))
+        db->entries.push_back(std::move(h));
+        db->n++;
+        return MCORB_OK;
+    }
+    HIPCHK(hipSetDevice(db->device));
+    hipStream_t st = s ? (hipStream_t)s->st : (hipStream_t)db->st;
+    const Place p = place_of(db, probe < 0 ? db->n : probe, probe >= 0);
+    TRY(store_vectors(p, v, ndesc, st));
+    if (ndesc && o) {
+        TRY(db->d_src.grow((size_t)db->max_feats));
+        HIPCHK(hipMemcpyAsync(db->d_src, o->src.data(), (size_t)ndesc * sizeof(int), hipMemcpyHostToDevice, st));
+        launch_kfdb_gather(st, s->d_desc, db->d_src, ndesc, p.desc);
+        HIPCHK(hipGetLastError());
+    } else if (ndesc) {
+        HIPCHK(hipMemcpyAsync(p.desc, desc, (size_t)ndesc * 32, hipMemcpyHostToDevice, st));
+    }
+    HIPCHK(hipStreamSynchronize(st));
+    if (probe >= 0) {
+        db->pmirror[probe] = mirror_of(v, ndesc);
+        db->probe_set[probe] = 1;
+    } else {
+        db->mirror.push_back(mirror_of(v, ndesc));
+        db->n++;
+    }
+    return MCORB_OK;
+}
+
+// the frame of a rig slot that add_rig_frame / set_probe_rig_frame name: MCORB_E_STATE unless the slot's last job ran the LF stage on it
+static int rig_frame_of(const mcorb_kfdb *db, mcorb_rig *r, int slot, int frame, const char *who, Slot **s_out)
+{
+    if (!r || slot < 0 || slot >= (int)r->rig.slots.size()) { set_error(std::string(who) + ": bad argument"); return MCORB_E_ARG; }
+    Slot *s = r->rig.slots[slot].get();
+    {
+        std::lock_guard<std::mutex> lk(s->m);
+        if (s->busy) { set_error("slot busy"); return MCORB_E_STATE; }
+    }
+    if (frame < 0 || frame >= (int)s->lf_ok.size() || !s->lf_ok[frame]) {
+        set_error(std::string(who) + ": frame not processed by the LF stage since the slot's last extraction");
+        return MCORB_E_STATE;
+    }
+    if (db->device >= 0 && db->device != r->rig.device) { set_error(std::string(who) + ": the rig lives on another device"); return MCORB_E_ARG; }
+    *s_out = s;
+    return MCORB_OK;
+}
+
+static Vectors vectors_of(const LfFrameOut &o)
+{
+    const BowImageOut &b = o.bow;
+    return Vectors{b.bow_ids.data(), b.bow_vals.data(), (int)b.bow_ids.size(), b.fv_nodes.data(), b.fv_offsets.data(), (int)b.fv_nodes.size(),
+                   b.fv_feats.data(), (int)b.fv_feats.size()};
 }
 
 // TemplatedDatabase::queryL1 from the accumulation on: sort, cut, -s / 2
@@ -203,20 +316,26 @@ static void query_host(const mcorb_kfdb *db, const uint32_t *qids, const double 
 // entries [0, limit) of a query with this max_id
 static int limit_of(int max_id, int n) { return max_id == -1 ? n : std::min(std::max(max_id, 0), n); }
 
-// k_kfdb_score for nq queries; sel[q]: the entry that is the query, or -1 for the vector uploaded to the scratch place.  With
-// against != nullptr query q is held against the single entry against[q] instead of the entries below its limit.  raw / shared of
-// (q, x) land at h_raw / h_shared[q * stride_out + x].
-static int run_score(mcorb_kfdb *db, const int *sel, const int *limit, const int *against, int nq, int *stride_out)
+// BowVectors as k_kfdb_score reads them (max_words apart): the entries, the probe slots, or the one-vector scratch of a host query
+struct BowArrays { const uint32_t *ids; const double *vals; const int *n; };
+static BowArrays entry_bows(const mcorb_kfdb *db) { return BowArrays{db->d_ids, db->d_vals, db->d_nbow}; }
+static BowArrays probe_bows(const mcorb_kfdb *db) { return BowArrays{db->p_ids, db->p_vals, db->p_nbow}; }
+static BowArrays scratch_bow(const mcorb_kfdb *db) { return BowArrays{db->d_qids, db->d_qvals, db->d_qn}; }
+
+// k_kfdb_score for nq queries; sel[q]: the vector of `query` that is query q.  With against != nullptr query q is held against
+// the single vector against[q] of `store` instead of the entries below its limit.  raw / shared of (q, x) land at h_raw /
+// h_shared[q * stride_out + x].
+static int run_score(mcorb_kfdb *db, const BowArrays &store, const BowArrays &query, const int *sel, const int *limit, const int *against,
+                     int nq, int *stride_out)
 {
     const int os = std::max(against ? 1 : db->n, 1);
     *stride_out = os;
     int max_limit = 0;
     for (int q = 0; q < nq; q++) max_limit = std::max(max_limit, limit[q]);
     if (max_limit < 1) return MCORB_OK;
-    const bool scratch = sel[0] < 0;   // (a host query is one query per call)
     std::vector<int> ctl((size_t)nq * 2 + (against ? nq : 0));
     for (int q = 0; q < nq; q++) {
-        ctl[q] = scratch ? 0 : sel[q];
+        ctl[q] = sel[q];
         ctl[nq + q] = limit[q];
         if (against) ctl[2 * (size_t)nq + q] = against[q];
     }
@@ -229,9 +348,8 @@ static int run_score(mcorb_kfdb *db, const int *sel, const int *limit, const int
     hipStream_t st = db->st;
     HIPCHK(hipMemcpyAsync(db->d_ctl, ctl.data(), ctl.size() * sizeof(int), hipMemcpyHostToDevice, st));
     HIPCHK(hipEventRecord(db->ev0, st));
-    launch_kfdb_score(st, db->d_ids, db->d_vals, db->d_nbow, db->max_words, scratch ? db->d_qids.get() : db->d_ids.get(),
-                      scratch ? db->d_qvals.get() : db->d_vals.get(), scratch ? db->d_qn.get() : db->d_nbow.get(), db->d_ctl,
-                      db->d_ctl + nq, against ? db->d_ctl + 2 * (size_t)nq : nullptr, nq, max_limit, os, db->d_raw, db->d_shared);
+    launch_kfdb_score(st, store.ids, store.vals, store.n, db->max_words, query.ids, query.vals, query.n, db->d_ctl, db->d_ctl + nq,
+                      against ? db->d_ctl + 2 * (size_t)nq : nullptr, nq, max_limit, os, db->d_raw, db->d_shared);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(db->ev1, st));
     HIPCHK(hipMemcpyAsync(db->h_raw, db->d_raw, nout * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -263,6 +381,13 @@ static int check_entry(const mcorb_kfdb *db, int e, const char *who)
     return MCORB_OK;
 }
 
+static int check_probe(const mcorb_kfdb *db, int p, const char *who)
+{
+    if (p < 0 || p >= db->nprobes) { set_error(std::string(who) + ": no such probe slot"); return MCORB_E_ARG; }
+    if (!db->probe_set[p]) { set_error(std::string(who) + ": the probe slot was never set"); return MCORB_E_STATE; }
+    return MCORB_OK;
+}
+
 // getMatches_distRatio's acceptance and one-to-one bookkeeping (ORBextractor.cpp:1264-1287) for one A feature of a call whose
 // lists so far are mA / mB; mD: the best distance each holder was accepted with = DescriptorDistance(A[holder], B[idx_B])
 static void accept(double best_dist_1, double best_dist_2, uint32_t idx_A, uint32_t idx_B, double max_neighbor_ratio,
@@ -283,6 +408,66 @@ static void accept(double best_dist_1, double best_dist_2, uint32_t idx_A, uint3
     }
 }
 
+// L1Scoring::score: a merge walk over the two sorted vectors
+static double score_host(const HostEntry &a, const HostEntry &b)
+{
+    double s = 0;
+    size_t i = 0, j = 0;
+    while (i < a.ids.size() && j < b.ids.size()) {
+        if (a.ids[i] == b.ids[j]) {
+            const double vi = a.vals[i], wi = b.vals[j];
+            s += fabs(vi - wi) - fabs(vi) - fabs(wi);
+            ++i; ++j;
+        } else if (a.ids[i] < b.ids[j]) {
+            i = std::lower_bound(a.ids.begin() + i, a.ids.end(), b.ids[j]) - a.ids.begin();
+        } else {
+            j = std::lower_bound(b.ids.begin() + j, b.ids.end(), a.ids[i]) - b.ids.begin();
+        }
+    }
+    return -s / 2.0;
+}
+
+// LoopCloser::featureMatchesBow (:217-240) -- FrontEnd::InterMatchingBow and Relocalization::featureMatchesBow walk the same way --
+// calling the literal getMatches_distRatio (ORBextractor.cpp:1228-1290); the matches are appended to i1 / i2
+static void matches_host(const HostEntry &A, const HostEntry &B, double max_neighbor_ratio, std::vector<uint32_t> &i1, std::vector<uint32_t> &i2)
+{
+    std::vector<uint32_t> mA, mB;
+    size_t ia = 0, ib = 0;
+    while (ia < A.nodes.size() && ib < B.nodes.size()) {
+        if (A.nodes[ia] == B.nodes[ib]) {
+            mA.clear(); mB.clear();
+            for (int a = A.offs[ia]; a < A.offs[ia + 1]; a++) {
+                int best_j_now = -1;
+                double best_dist_1 = 1e9, best_dist_2 = 1e9;
+                for (int j = B.offs[ib]; j < B.offs[ib + 1]; j++) {
+                    const double d = mcorb_hamming256(A.desc.data() + (size_t)A.feats[a] * 32, B.desc.data() + (size_t)B.feats[j] * 32);
+                    if (d < best_dist_1) { best_j_now = j; best_dist_2 = best_dist_1; best_dist_1 = d; }
+                    else if (d < best_dist_2) best_dist_2 = d;
+                }
+                if (best_dist_1 <= TH_LOW && best_dist_1 / best_dist_2 <= max_neighbor_ratio) {
+                    const uint32_t idx_B = (uint32_t)B.feats[best_j_now];
+                    const auto bit = std::find(mB.begin(), mB.end(), idx_B);
+                    if (bit == mB.end()) {
+                        mB.push_back(idx_B);
+                        mA.push_back((uint32_t)A.feats[a]);
+                    } else {
+                        const uint32_t idx_A = mA[bit - mB.begin()];
+                        const double d = mcorb_hamming256(A.desc.data() + (size_t)idx_A * 32, B.desc.data() + (size_t)idx_B * 32);
+                        if (best_dist_1 < d) mA[bit - mB.begin()] = (uint32_t)A.feats[a];
+                    }
+                }
+            }
+            i1.insert(i1.end(), mA.begin(), mA.end());
+            i2.insert(i2.end(), mB.begin(), mB.end());
+            ++ia; ++ib;
+        } else if (A.nodes[ia] < B.nodes[ib]) {
+            ia = std::lower_bound(A.nodes.begin() + ia, A.nodes.end(), B.nodes[ib]) - A.nodes.begin();
+        } else {
+            ib = std::lower_bound(B.nodes.begin() + ib, B.nodes.end(), A.nodes[ia]) - B.nodes.begin();
+        }
+    }
+}
+
 extern "C" {
 
 int mcorb_kfdb_create(const mcorb_vocab *v, int device, int max_entries, int max_words, int max_feats, mcorb_kfdb **out)
@@ -297,6 +482,7 @@ int mcorb_kfdb_create(const mcorb_vocab *v, int device, int max_entries, int max
     static_assert(MCORB_KFDB_MAX_WORDS == kKfdbMaxWords, "the header's limit is the kernel's");
     std::unique_ptr<mcorb_kfdb> db(new mcorb_kfdb);
     db->device = device; db->max_entries = max_entries; db->max_words = max_words; db->max_feats = max_feats;
+    db->fstride = (max_feats + 63) / 64 * 64;   // (launch_knn2 walks whole 64-row tiles of a set)
     if (device >= 0) {
         int ndev = 0;
         if (hipGetDeviceCount(&ndev) != hipSuccess || device >= ndev) { set_error("kfdb create: no such HIP device"); return MCORB_E_NODEVICE; }
@@ -311,7 +497,8 @@ int mcorb_kfdb_create(const mcorb_vocab *v, int device, int max_entries, int max
         TRY(db->d_nodes.alloc(E * F));
         TRY(db->d_offs.alloc(E * (F + 1)));
         TRY(db->d_feats.alloc(E * F));
-        TRY(db->d_desc.alloc(E * F * 32));
+        TRY(db->d_desc.alloc(E * db->fstride * 32));
+        TRY(db->d_ndesc.alloc(E + kMaxProbes));
         TRY(db->d_qids.alloc(W));
         TRY(db->d_qvals.alloc(W));
         TRY(db->d_qn.alloc(1));
@@ -336,17 +523,8 @@ int mcorb_kfdb_add(mcorb_kfdb *db, const uint32_t *bow_ids, const double *bow_va
     std::lock_guard<std::mutex> lk(db->mu);
     if (nfv < 0 || (nfv && !fv_offsets) || (ndesc > 0 && !desc)) { set_error("kfdb add: bad argument"); return MCORB_E_ARG; }
     const Vectors v{bow_ids, bow_vals, nbow, fv_nodes, fv_offsets, nfv, fv_feats, nfv ? fv_offsets[nfv] : 0};
-    TRY(check_vectors(db, v, ndesc));
     const int e = db->n;
-    if (db->device < 0) {
-        add_host(db, v, desc, ndesc);
-    } else {
-        HIPCHK(hipSetDevice(db->device));
-        TRY(store_vectors(db, e, v, db->st));
-        if (ndesc) HIPCHK(hipMemcpyAsync(db->d_desc + (size_t)e * db->max_feats * 32, desc, (size_t)ndesc * 32, hipMemcpyHostToDevice, db->st));
-        HIPCHK(hipStreamSynchronize(db->st));
-        commit_mirror(db, v, ndesc);
-    }
+    TRY(put_frame(db, -1, v, desc, ndesc, nullptr, nullptr));
     if (entry_out) *entry_out = e;
     return MCORB_OK;
 }
@@ -354,45 +532,59 @@ int mcorb_kfdb_add(mcorb_kfdb *db, const uint32_t *bow_ids, const double *bow_va
 int mcorb_kfdb_add_rig_frame(mcorb_kfdb *db, mcorb_rig *r, int slot, int frame, int *entry_out)
 {
     TRY(check_db(db, "kfdb add_rig_frame"));
-    if (!r || slot < 0 || slot >= (int)r->rig.slots.size()) { set_error("kfdb add_rig_frame: bad argument"); return MCORB_E_ARG; }
-    Rig &R = r->rig;
-    Slot *s = R.slots[slot].get();
-    {
-        std::lock_guard<std::mutex> lk(s->m);
-        if (s->busy) { set_error("slot busy"); return MCORB_E_STATE; }
-    }
-    if (frame < 0 || frame >= (int)s->lf_ok.size() || !s->lf_ok[frame]) {
-        set_error("kfdb add_rig_frame: frame not processed by the LF stage since the slot's last extraction");
-        return MCORB_E_STATE;
-    }
-    if (db->device >= 0 && db->device != R.device) { set_error("kfdb add_rig_frame: the rig lives on another device"); return MCORB_E_ARG; }
+    Slot *s = nullptr;
+    TRY(rig_frame_of(db, r, slot, frame, "kfdb add_rig_frame", &s));
     std::lock_guard<std::mutex> lk(db->mu);
     const LfFrameOut &o = s->lf[frame];
-    const BowImageOut &b = o.bow;
-    const int ndesc = (int)o.feats.size(), nfv = (int)b.fv_nodes.size();
-    const Vectors v{b.bow_ids.data(), b.bow_vals.data(), (int)b.bow_ids.size(), b.fv_nodes.data(), b.fv_offsets.data(), nfv,
-                    b.fv_feats.data(), (int)b.fv_feats.size()};
-    TRY(check_vectors(db, v, ndesc));
     const int e = db->n;
-    if (db->device < 0) {
-        std::vector<uint8_t> desc((size_t)ndesc * 32);
-        for (int i = 0; i < ndesc; i++) memcpy(desc.data() + (size_t)i * 32, o.feats[i].desc, 32);
-        add_host(db, v, desc.data(), ndesc);
-    } else {
-        // lfBoW and lfFeatVec are assembled on the host (lf_job_finish): they are uploaded.  The LF descriptors are rows of the
-        // slot's descriptor block in HBM (LfFrameOut::src): gathered device to device, on the slot's stream.
-        HIPCHK(hipSetDevice(db->device));
-        TRY(store_vectors(db, e, v, s->st));
-        if (ndesc) {
-            TRY(db->d_src.grow((size_t)db->max_feats));
-            HIPCHK(hipMemcpyAsync(db->d_src, o.src.data(), (size_t)ndesc * sizeof(int), hipMemcpyHostToDevice, s->st));
-            launch_kfdb_gather(s->st, s->d_desc, db->d_src, ndesc, db->d_desc + (size_t)e * db->max_feats * 32);
-            HIPCHK(hipGetLastError());
-        }
-        HIPCHK(hipStreamSynchronize(s->st));
-        commit_mirror(db, v, ndesc);
-    }
+    TRY(put_frame(db, -1, vectors_of(o), nullptr, (int)o.feats.size(), s, &o));
     if (entry_out) *entry_out = e;
+    return MCORB_OK;
+}
+
+// get_entry / get_probe: a stored frame as it is stored
+static int get_frame(mcorb_kfdb *db, int idx, bool probe, const char *who, uint32_t *bow_ids, double *bow_vals, int bow_cap, int *nbow,
+                     uint32_t *fv_nodes, int32_t *fv_offsets, int fv_cap, int *nfv, int32_t *fv_feats, int feat_cap, uint8_t *desc,
+                     int desc_cap, int *ndesc)
+{
+    int c_bow, c_fv, c_ff, c_desc;
+    if (db->device < 0) {
+        const HostEntry &h = probe ? db->probes[idx] : db->entries[idx];
+        c_bow = (int)h.ids.size(); c_fv = (int)h.nodes.size(); c_ff = (int)h.feats.size(); c_desc = (int)(h.desc.size() / 32);
+    } else {
+        const Mirror &m = probe ? db->pmirror[idx] : db->mirror[idx];
+        c_bow = m.nbow; c_fv = m.nfv; c_ff = m.nff; c_desc = m.ndesc;
+    }
+    if (nbow) *nbow = c_bow;
+    if (nfv) *nfv = c_fv;
+    if (ndesc) *ndesc = c_desc;
+    if (c_bow > bow_cap || c_fv > fv_cap || c_ff > feat_cap || c_desc > desc_cap) { set_error(std::string(who) + ": output too small"); return MCORB_E_CAP; }
+    if (!fv_offsets || (c_bow && (!bow_ids || !bow_vals)) || (c_fv && !fv_nodes) || (c_ff && !fv_feats) || (c_desc && !desc)) {
+        set_error(std::string(who) + ": bad argument");
+        return MCORB_E_ARG;
+    }
+    if (db->device < 0) {
+        const HostEntry &h = probe ? db->probes[idx] : db->entries[idx];
+        if (c_bow) { memcpy(bow_ids, h.ids.data(), (size_t)c_bow * 4); memcpy(bow_vals, h.vals.data(), (size_t)c_bow * 8); }
+        if (c_fv) memcpy(fv_nodes, h.nodes.data(), (size_t)c_fv * 4);
+        memcpy(fv_offsets, h.offs.data(), h.offs.size() * 4);
+        if (c_ff) memcpy(fv_feats, h.feats.data(), (size_t)c_ff * 4);
+        if (c_desc) memcpy(desc, h.desc.data(), (size_t)c_desc * 32);
+        return MCORB_OK;
+    }
+    HIPCHK(hipSetDevice(db->device));
+    const Place p = place_of(db, idx, probe);
+    fv_offsets[0] = 0;
+    if (c_bow) {
+        HIPCHK(hipMemcpy(bow_ids, p.ids, (size_t)c_bow * 4, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(bow_vals, p.vals, (size_t)c_bow * 8, hipMemcpyDeviceToHost));
+    }
+    if (c_fv) {
+        HIPCHK(hipMemcpy(fv_nodes, p.nodes, (size_t)c_fv * 4, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(fv_offsets, p.offs, (size_t)(c_fv + 1) * 4, hipMemcpyDeviceToHost));
+    }
+    if (c_ff) HIPCHK(hipMemcpy(fv_feats, p.feats, (size_t)c_ff * 4, hipMemcpyDeviceToHost));
+    if (c_desc) HIPCHK(hipMemcpy(desc, p.desc, (size_t)c_desc * 32, hipMemcpyDeviceToHost));
     return MCORB_OK;
 }
 
@@ -403,45 +595,8 @@ int mcorb_kfdb_get_entry(mcorb_kfdb *db, int entry, uint32_t *bow_ids, double *b
     TRY(check_db(db, "kfdb get_entry"));
     std::lock_guard<std::mutex> lk(db->mu);
     TRY(check_entry(db, entry, "kfdb get_entry"));
-    int c_bow, c_fv, c_ff, c_desc;
-    if (db->device < 0) {
-        const HostEntry &h = db->entries[entry];
-        c_bow = (int)h.ids.size(); c_fv = (int)h.nodes.size(); c_ff = (int)h.feats.size(); c_desc = (int)(h.desc.size() / 32);
-    } else {
-        const Mirror &m = db->mirror[entry];
-        c_bow = m.nbow; c_fv = m.nfv; c_ff = m.nff; c_desc = m.ndesc;
-    }
-    if (nbow) *nbow = c_bow;
-    if (nfv) *nfv = c_fv;
-    if (ndesc) *ndesc = c_desc;
-    if (c_bow > bow_cap || c_fv > fv_cap || c_ff > feat_cap || c_desc > desc_cap) { set_error("kfdb get_entry: output too small"); return MCORB_E_CAP; }
-    if (!fv_offsets || (c_bow && (!bow_ids || !bow_vals)) || (c_fv && !fv_nodes) || (c_ff && !fv_feats) || (c_desc && !desc)) {
-        set_error("kfdb get_entry: bad argument");
-        return MCORB_E_ARG;
-    }
-    if (db->device < 0) {
-        const HostEntry &h = db->entries[entry];
-        if (c_bow) { memcpy(bow_ids, h.ids.data(), (size_t)c_bow * 4); memcpy(bow_vals, h.vals.data(), (size_t)c_bow * 8); }
-        if (c_fv) memcpy(fv_nodes, h.nodes.data(), (size_t)c_fv * 4);
-        memcpy(fv_offsets, h.offs.data(), h.offs.size() * 4);
-        if (c_ff) memcpy(fv_feats, h.feats.data(), (size_t)c_ff * 4);
-        if (c_desc) memcpy(desc, h.desc.data(), (size_t)c_desc * 32);
-        return MCORB_OK;
-    }
-    HIPCHK(hipSetDevice(db->device));
-    const size_t e = (size_t)entry, W = (size_t)db->max_words, F = (size_t)db->max_feats;
-    fv_offsets[0] = 0;
-    if (c_bow) {
-        HIPCHK(hipMemcpy(bow_ids, db->d_ids + e * W, (size_t)c_bow * 4, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(bow_vals, db->d_vals + e * W, (size_t)c_bow * 8, hipMemcpyDeviceToHost));
-    }
-    if (c_fv) {
-        HIPCHK(hipMemcpy(fv_nodes, db->d_nodes + e * F, (size_t)c_fv * 4, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(fv_offsets, db->d_offs + e * (F + 1), (size_t)(c_fv + 1) * 4, hipMemcpyDeviceToHost));
-    }
-    if (c_ff) HIPCHK(hipMemcpy(fv_feats, db->d_feats + e * F, (size_t)c_ff * 4, hipMemcpyDeviceToHost));
-    if (c_desc) HIPCHK(hipMemcpy(desc, db->d_desc + e * F * 32, (size_t)c_desc * 32, hipMemcpyDeviceToHost));
-    return MCORB_OK;
+    return get_frame(db, entry, false, "kfdb get_entry", bow_ids, bow_vals, bow_cap, nbow, fv_nodes, fv_offsets, fv_cap, nfv, fv_feats,
+                     feat_cap, desc, desc_cap, ndesc);
 }
 
 int mcorb_kfdb_query(mcorb_kfdb *db, const uint32_t *bow_ids, const double *bow_vals, int nbow, int max_results, int max_id,
@@ -465,9 +620,9 @@ int mcorb_kfdb_query(mcorb_kfdb *db, const uint32_t *bow_ids, const double *bow_
         HIPCHK(hipMemcpyAsync(db->d_qids, bow_ids, (size_t)nbow * 4, hipMemcpyHostToDevice, db->st));
         HIPCHK(hipMemcpyAsync(db->d_qvals, bow_vals, (size_t)nbow * 8, hipMemcpyHostToDevice, db->st));
         HIPCHK(hipMemcpyAsync(db->d_qn, &nbow, sizeof(int), hipMemcpyHostToDevice, db->st));
-        const int sel = -1;
+        const int sel = 0;
         int stride = 1;
-        TRY(run_score(db, &sel, &limit, nullptr, 1, &stride));
+        TRY(run_score(db, entry_bows(db), scratch_bow(db), &sel, &limit, nullptr, 1, &stride));
         list_of(db, 0, stride, limit, ret);
     }
     return finish_query(ret, max_results, ids, scores, cap, n_out);
@@ -499,7 +654,7 @@ int mcorb_kfdb_query_entries(mcorb_kfdb *db, const int32_t *entries, const int32
     std::vector<int> limit(nq);
     for (int q = 0; q < nq; q++) limit[q] = limit_of(max_ids[q], db->n);
     int stride = 1;
-    TRY(run_score(db, entries, limit.data(), nullptr, nq, &stride));
+    TRY(run_score(db, entry_bows(db), entry_bows(db), entries, limit.data(), nullptr, nq, &stride));
     for (int q = 0; q < nq; q++) {
         list_of(db, q, stride, limit[q], ret);
         const int st = finish_query(ret, max_results, ids + (size_t)q * cap, scores + (size_t)q * cap, cap, n_out + q);
@@ -516,28 +671,13 @@ int mcorb_kfdb_score(mcorb_kfdb *db, int entry_a, int entry_b, double *score)
     TRY(check_entry(db, entry_a, "kfdb score"));
     TRY(check_entry(db, entry_b, "kfdb score"));
     if (db->device < 0) {
-        // L1Scoring::score: a merge walk over the two sorted vectors
-        const HostEntry &a = db->entries[entry_a], &b = db->entries[entry_b];
-        double s = 0;
-        size_t i = 0, j = 0;
-        while (i < a.ids.size() && j < b.ids.size()) {
-            if (a.ids[i] == b.ids[j]) {
-                const double vi = a.vals[i], wi = b.vals[j];
-                s += fabs(vi - wi) - fabs(vi) - fabs(wi);
-                ++i; ++j;
-            } else if (a.ids[i] < b.ids[j]) {
-                i = std::lower_bound(a.ids.begin() + i, a.ids.end(), b.ids[j]) - a.ids.begin();
-            } else {
-                j = std::lower_bound(b.ids.begin() + j, b.ids.end(), a.ids[i]) - b.ids.begin();
-            }
-        }
-        *score = -s / 2.0;
+        *score = score_host(db->entries[entry_a], db->entries[entry_b]);
         return MCORB_OK;
     }
     HIPCHK(hipSetDevice(db->device));
     const int one = 1;
     int stride = 1;
-    TRY(run_score(db, &entry_a, &one, &entry_b, 1, &stride));
+    TRY(run_score(db, entry_bows(db), entry_bows(db), &entry_a, &one, &entry_b, 1, &stride));
     *score = db->h_shared[0] > 0 ? -db->h_raw[0] / 2.0 : 0.0;
     return MCORB_OK;
 }
@@ -554,42 +694,7 @@ int mcorb_kfdb_feature_matches(mcorb_kfdb *db, int best_entry, int curr_entry, d
     std::vector<uint32_t> i1, i2, mA, mB;
     std::vector<double> mD;
     if (db->device < 0) {
-        // LoopCloser::featureMatchesBow (:217-240) calling the literal getMatches_distRatio (ORBextractor.cpp:1228-1290)
-        const HostEntry &A = db->entries[best_entry], &B = db->entries[curr_entry];
-        size_t ia = 0, ib = 0;
-        while (ia < A.nodes.size() && ib < B.nodes.size()) {
-            if (A.nodes[ia] == B.nodes[ib]) {
-                mA.clear(); mB.clear(); mD.clear();
-                for (int a = A.offs[ia]; a < A.offs[ia + 1]; a++) {
-                    int best_j_now = -1;
-                    double best_dist_1 = 1e9, best_dist_2 = 1e9;
-                    for (int j = B.offs[ib]; j < B.offs[ib + 1]; j++) {
-                        const double d = mcorb_hamming256(A.desc.data() + (size_t)A.feats[a] * 32, B.desc.data() + (size_t)B.feats[j] * 32);
-                        if (d < best_dist_1) { best_j_now = j; best_dist_2 = best_dist_1; best_dist_1 = d; }
-                        else if (d < best_dist_2) best_dist_2 = d;
-                    }
-                    if (best_dist_1 <= TH_LOW && best_dist_1 / best_dist_2 <= max_neighbor_ratio) {
-                        const uint32_t idx_B = (uint32_t)B.feats[best_j_now];
-                        const auto bit = std::find(mB.begin(), mB.end(), idx_B);
-                        if (bit == mB.end()) {
-                            mB.push_back(idx_B);
-                            mA.push_back((uint32_t)A.feats[a]);
-                        } else {
-                            const uint32_t idx_A = mA[bit - mB.begin()];
-                            const double d = mcorb_hamming256(A.desc.data() + (size_t)idx_A * 32, B.desc.data() + (size_t)idx_B * 32);
-                            if (best_dist_1 < d) mA[bit - mB.begin()] = (uint32_t)A.feats[a];
-                        }
-                    }
-                }
-                i1.insert(i1.end(), mA.begin(), mA.end());
-                i2.insert(i2.end(), mB.begin(), mB.end());
-                ++ia; ++ib;
-            } else if (A.nodes[ia] < B.nodes[ib]) {
-                ia = std::lower_bound(A.nodes.begin() + ia, A.nodes.end(), B.nodes[ib]) - A.nodes.begin();
-            } else {
-                ib = std::lower_bound(B.nodes.begin() + ib, B.nodes.end(), A.nodes[ia]) - B.nodes.begin();
-            }
-        }
+        matches_host(db->entries[best_entry], db->entries[curr_entry], max_neighbor_ratio, i1, i2);
     } else {
         // the shared nodes in ascending id from the host's copy of the two node lists; one item per A feature of a shared node
         const Mirror &A = db->mirror[best_entry], &B = db->mirror[curr_entry];
@@ -614,12 +719,11 @@ int mcorb_kfdb_feature_matches(mcorb_kfdb *db, int best_entry, int curr_entry, d
             TRY(db->d_mtab.grow(items.size()));
             TRY(db->h_mtab.grow(items.size(), hipHostMallocDefault));
             hipStream_t st = db->st;
-            const size_t F = (size_t)db->max_feats;
+            const Place pa = place_of(db, best_entry, false), pb = place_of(db, curr_entry, false);
             HIPCHK(hipMemcpyAsync(db->d_items, items.data(), items.size() * sizeof(int2), hipMemcpyHostToDevice, st));
             HIPCHK(hipMemcpyAsync(db->d_mnodes, nodes.data(), nodes.size() * sizeof(int2), hipMemcpyHostToDevice, st));
             HIPCHK(hipEventRecord(db->ev0, st));
-            launch_kfdb_best2(st, db->d_desc + best_entry * F * 32, db->d_feats + best_entry * F, db->d_desc + curr_entry * F * 32,
-                              db->d_feats + curr_entry * F, db->d_items, nitems, db->d_mnodes, db->d_mtab);
+            launch_kfdb_best2(st, pa.desc, pa.feats, pb.desc, pb.feats, db->d_items, nitems, db->d_mnodes, db->d_mtab);
             HIPCHK(hipGetLastError());
             HIPCHK(hipEventRecord(db->ev1, st));
             HIPCHK(hipMemcpyAsync(db->h_mtab, db->d_mtab, items.size() * sizeof(int4), hipMemcpyDeviceToHost, st));
@@ -652,6 +756,326 @@ int mcorb_kfdb_last_timing(mcorb_kfdb *db, float us[2])
     std::lock_guard<std::mutex> lk(db->mu);
     us[0] = db->us_score;
     us[1] = db->us_best2;
+    return MCORB_OK;
+}
+
+// ---------------------------------------------------------------------------
+// probe slots
+// ---------------------------------------------------------------------------
+int mcorb_kfdb_reserve_probes(mcorb_kfdb *db, int nprobes)
+{
+    TRY(check_db(db, "kfdb reserve_probes"));
+    if (nprobes < 1 || nprobes > kMaxProbes) { set_error("kfdb reserve_probes: 1 .. 128 probe slots"); return MCORB_E_ARG; }
+    std::lock_guard<std::mutex> lk(db->mu);
+    if (db->nprobes) { set_error("kfdb reserve_probes: the probe slots are reserved already"); return MCORB_E_STATE; }
+    if (db->device < 0) {
+        db->probes.resize(nprobes);
+    } else {
+        HIPCHK(hipSetDevice(db->device));
+        const size_t P = (size_t)nprobes, E = (size_t)db->max_entries, W = (size_t)db->max_words, F = (size_t)db->max_feats;
+        const size_t set = (size_t)db->fstride * 32;
+        TRY(db->p_ids.alloc(P * W));
+        TRY(db->p_vals.alloc(P * W));
+        TRY(db->p_nbow.alloc(P));
+        TRY(db->p_nodes.alloc(P * F));
+        TRY(db->p_offs.alloc(P * (F + 1)));
+        TRY(db->p_feats.alloc(P * F));
+        // the probe slots go behind the entries in the descriptor allocation: a larger one, the entries copied over
+        DevBuf<uint8_t> desc;
+        TRY(desc.alloc((E + P) * set));
+        HIPCHK(hipStreamSynchronize(db->st));
+        if (db->n) HIPCHK(hipMemcpy(desc, db->d_desc, (size_t)db->n * set, hipMemcpyDeviceToDevice));
+        HIPCHK(hipStreamSynchronize(nullptr));
+        db->d_desc = std::move(desc);
+        db->pmirror.resize(nprobes);
+    }
+    db->probe_set.assign(nprobes, 0);
+    db->nprobes = nprobes;
+    return MCORB_OK;
+}
+
+static int check_slot(const mcorb_kfdb *db, int p, const char *who)
+{
+    if (p < 0 || p >= db->nprobes) { set_error(std::string(who) + ": no such probe slot"); return MCORB_E_ARG; }
+    return MCORB_OK;
+}
+
+int mcorb_kfdb_set_probe(mcorb_kfdb *db, int probe, const uint32_t *bow_ids, const double *bow_vals, int nbow, const uint32_t *fv_nodes,
+                         const int32_t *fv_offsets, int nfv, const int32_t *fv_feats, const uint8_t *desc, int ndesc)
+{
+    TRY(check_db(db, "kfdb set_probe"));
+    std::lock_guard<std::mutex> lk(db->mu);
+    TRY(check_slot(db, probe, "kfdb set_probe"));
+    if (nfv < 0 || (nfv && !fv_offsets) || (ndesc > 0 && !desc)) { set_error("kfdb set_probe: bad argument"); return MCORB_E_ARG; }
+    const Vectors v{bow_ids, bow_vals, nbow, fv_nodes, fv_offsets, nfv, fv_feats, nfv ? fv_offsets[nfv] : 0};
+    return put_frame(db, probe, v, desc, ndesc, nullptr, nullptr);
+}
+
+int mcorb_kfdb_set_probe_rig_frame(mcorb_kfdb *db, int probe, mcorb_rig *r, int slot, int frame)
+{
+    TRY(check_db(db, "kfdb set_probe_rig_frame"));
+    Slot *s = nullptr;
+    TRY(rig_frame_of(db, r, slot, frame, "kfdb set_probe_rig_frame", &s));
+    std::lock_guard<std::mutex> lk(db->mu);
+    TRY(check_slot(db, probe, "kfdb set_probe_rig_frame"));
+    const LfFrameOut &o = s->lf[frame];
+    return put_frame(db, probe, vectors_of(o), nullptr, (int)o.feats.size(), s, &o);
+}
+
+int mcorb_kfdb_get_probe(mcorb_kfdb *db, int probe, uint32_t *bow_ids, double *bow_vals, int bow_cap, int *nbow, uint32_t *fv_nodes,
+                         int32_t *fv_offsets, int fv_cap, int *nfv, int32_t *fv_feats, int feat_cap, uint8_t *desc, int desc_cap,
+                         int *ndesc)
+{
+    TRY(check_db(db, "kfdb get_probe"));
+    std::lock_guard<std::mutex> lk(db->mu);
+    TRY(check_probe(db, probe, "kfdb get_probe"));
+    return get_frame(db, probe, true, "kfdb get_probe", bow_ids, bow_vals, bow_cap, nbow, fv_nodes, fv_offsets, fv_cap, nfv, fv_feats, feat_cap,
+                     desc, desc_cap, ndesc);
+}
+
+int mcorb_kfdb_query_probes(mcorb_kfdb *db, const int32_t *probes, const int32_t *max_ids, int nq, int max_results, uint32_t *ids,
+                            double *scores, int cap, int *n_out)
+{
+    TRY(check_db(db, "kfdb query_probes"));
+    if (nq < 0 || (nq && (!probes || !max_ids || !n_out)) || cap < 0 || (cap && (!ids || !scores))) { set_error("kfdb query_probes: bad argument"); return MCORB_E_ARG; }
+    std::lock_guard<std::mutex> lk(db->mu);
+    for (int q = 0; q < nq; q++) {
+        n_out[q] = 0;
+        TRY(check_probe(db, probes[q], "kfdb query_probes"));
+    }
+    if (nq == 0) return MCORB_OK;
+    std::vector<Result> ret;
+    std::vector<int> limit(nq);
+    int status = MCORB_OK, stride = 1;
+    if (db->device >= 0) {
+        HIPCHK(hipSetDevice(db->device));
+        for (int q = 0; q < nq; q++) limit[q] = limit_of(max_ids[q], db->n);
+        TRY(run_score(db, entry_bows(db), probe_bows(db), probes, limit.data(), nullptr, nq, &stride));
+    }
+    for (int q = 0; q < nq; q++) {
+        if (db->device < 0) {
+            const HostEntry &h = db->probes[probes[q]];
+            query_host(db, h.ids.data(), h.vals.data(), (int)h.ids.size(), max_ids[q], ret);
+        } else {
+            list_of(db, q, stride, limit[q], ret);
+        }
+        const int st = finish_query(ret, max_results, ids + (size_t)q * cap, scores + (size_t)q * cap, cap, n_out + q);
+        if (st != MCORB_OK && status == MCORB_OK) status = st;
+    }
+    return status;
+}
+
+int mcorb_kfdb_score_probe(mcorb_kfdb *db, int entry, int probe, double *score)
+{
+    TRY(check_db(db, "kfdb score_probe"));
+    if (!score) { set_error("kfdb score_probe: bad argument"); return MCORB_E_ARG; }
+    std::lock_guard<std::mutex> lk(db->mu);
+    TRY(check_entry(db, entry, "kfdb score_probe"));
+    TRY(check_probe(db, probe, "kfdb score_probe"));
+    if (db->device < 0) {
+        *score = score_host(db->entries[entry], db->probes[probe]);
+        return MCORB_OK;
+    }
+    // score(entry's vector, probe's): the entry is the query, the probe store the one it is held against
+    HIPCHK(hipSetDevice(db->device));
+    const int one = 1;
+    int stride = 1;
+    TRY(run_score(db, probe_bows(db), entry_bows(db), &entry, &one, &probe, 1, &stride));
+    *score = db->h_shared[0] > 0 ? -db->h_raw[0] / 2.0 : 0.0;
+    return MCORB_OK;
+}
+
+int mcorb_kfdb_probe_feature_matches(mcorb_kfdb *db, int entry, const int32_t *probes, int np, double max_neighbor_ratio,
+                                     uint32_t *indices_1, uint32_t *indices_2, int cap, int *n_out)
+{
+    TRY(check_db(db, "kfdb probe_feature_matches"));
+    if (np < 0 || (np && (!probes || !n_out)) || cap < 0 || (cap && (!indices_1 || !indices_2))) {
+        set_error("kfdb probe_feature_matches: bad argument");
+        return MCORB_E_ARG;
+    }
+    std::lock_guard<std::mutex> lk(db->mu);
+    TRY(check_entry(db, entry, "kfdb probe_feature_matches"));
+    for (int p = 0; p < np; p++) {
+        n_out[p] = 0;
+        TRY(check_probe(db, probes[p], "kfdb probe_feature_matches"));
+    }
+    if (np == 0) return MCORB_OK;
+    std::vector<std::vector<uint32_t>> i1(np), i2(np);
+    if (db->device < 0) {
+        for (int p = 0; p < np; p++) matches_host(db->entries[entry], db->probes[probes[p]], max_neighbor_ratio, i1[p], i2[p]);
+    } else {
+        // every probe's shared nodes in ascending id, from the host's copies of the node lists; one item per A feature of a shared
+        // node, probe by probe and node by node: the order the kernel's lanes share B rows in and the host folds the results in
+        const Mirror &A = db->mirror[entry];
+        std::vector<int2> items;
+        std::vector<int4> nodes;
+        std::vector<int> first, first_node(1, 0);   // per shared-node record: its first item; per probe: its first record
+        for (int p = 0; p < np; p++) {
+            const Mirror &B = db->pmirror[probes[p]];
+            size_t ia = 0, ib = 0;
+            while (ia < A.nodes.size() && ib < B.nodes.size()) {
+                if (A.nodes[ia] == B.nodes[ib]) {
+                    first.push_back((int)items.size());
+                    for (int a = A.offs[ia]; a < A.offs[ia + 1]; a++) items.push_back(int2{a, (int)nodes.size()});
+                    nodes.push_back(int4{probes[p], B.offs[ib], B.offs[ib + 1] - B.offs[ib], 0});
+                    ++ia; ++ib;
+                } else if (A.nodes[ia] < B.nodes[ib]) ++ia;
+                else ++ib;
+            }
+            first_node.push_back((int)nodes.size());
+        }
+        first.push_back((int)items.size());
+        const int nitems = (int)items.size();
+        if (nitems) {
+            HIPCHK(hipSetDevice(db->device));
+            TRY(db->d_items.grow(items.size()));
+            TRY(db->d_pnodes.grow(nodes.size()));
+            TRY(db->d_mtab.grow(items.size()));
+            TRY(db->h_mtab.grow(items.size(), hipHostMallocDefault));
+            hipStream_t st = db->st;
+            const Place pa = place_of(db, entry, false), p0 = place_of(db, 0, true);
+            HIPCHK(hipMemcpyAsync(db->d_items, items.data(), items.size() * sizeof(int2), hipMemcpyHostToDevice, st));
+            HIPCHK(hipMemcpyAsync(db->d_pnodes, nodes.data(), nodes.size() * sizeof(int4), hipMemcpyHostToDevice, st));
+            HIPCHK(hipEventRecord(db->ev0, st));
+            launch_kfdb_best2_probes(st, pa.desc, pa.feats, p0.desc, (size_t)db->fstride * 32, p0.feats, (size_t)db->max_feats, db->d_items,
+                                     nitems, db->d_pnodes, db->d_mtab);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipEventRecord(db->ev1, st));
+            HIPCHK(hipMemcpyAsync(db->h_mtab, db->d_mtab, items.size() * sizeof(int4), hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));
+            float ms = 0.f;
+            ev_elapsed(&ms, db->ev0, db->ev1);
+            db->us_best2p = ms * 1000.f;
+            std::vector<uint32_t> mA, mB;
+            std::vector<double> mD;
+            for (int p = 0; p < np; p++)
+                for (int k = first_node[p]; k < first_node[p + 1]; k++) {
+                    mA.clear(); mB.clear(); mD.clear();
+                    for (int i = first[k]; i < first[k + 1]; i++) {
+                        const int4 t = db->h_mtab[i];   // {B feature of the best or -1, best, second, A feature}
+                        if (t.x < 0) continue;          // an empty B list: best_dist_1 stays 1e9
+                        accept((double)t.y, t.z == 0x7fffffff ? 1e9 : (double)t.z, (uint32_t)t.w, (uint32_t)t.x, max_neighbor_ratio, mA, mB, mD);
+                    }
+                    i1[p].insert(i1[p].end(), mA.begin(), mA.end());
+                    i2[p].insert(i2[p].end(), mB.begin(), mB.end());
+                }
+        }
+    }
+    int status = MCORB_OK;
+    for (int p = 0; p < np; p++) {
+        n_out[p] = (int)i1[p].size();
+        if ((int)i1[p].size() > cap) { set_error("kfdb probe_feature_matches: output too small"); status = MCORB_E_CAP; continue; }
+        if (!i1[p].empty()) {
+            memcpy(indices_1 + (size_t)p * cap, i1[p].data(), i1[p].size() * 4);
+            memcpy(indices_2 + (size_t)p * cap, i2[p].data(), i2[p].size() * 4);
+        }
+    }
+    return status;
+}
+
+// knnMatch(descs_prev, descs_cur, 2) of an entry's and a probe's descriptors: per query {trainIdx0, dist0, trainIdx1, dist1}, -1
+// for an absent neighbour; BFMatcher's order, the lowest train index first among equal distances
+static int knn2_frames(mcorb_kfdb *db, int entry, int probe, int na, int nb, std::vector<int4> &rows)
+{
+    rows.assign((size_t)na, int4{-1, -1, -1, -1});
+    if (na == 0 || nb == 0) return MCORB_OK;
+    if (db->device < 0) {
+        const uint8_t *A = db->entries[entry].desc.data(), *B = db->probes[probe].desc.data();
+        for (int q = 0; q < na; q++) {
+            int4 r = int4{-1, 0x7fffffff, -1, 0x7fffffff};
+            for (int t = 0; t < nb; t++) {
+                const int d = mcorb_hamming256(A + (size_t)q * 32, B + (size_t)t * 32);
+                if (d < r.y) { r.z = r.x; r.w = r.y; r.x = t; r.y = d; }
+                else if (d < r.w) { r.z = t; r.w = d; }
+            }
+            if (r.z < 0) r.w = -1;
+            rows[q] = r;
+        }
+        return MCORB_OK;
+    }
+    const int kc = db->fstride;
+    if (kc > 65535) { set_error("kfdb probe_inter_matches_bf: max_feats above 65535 (the k-NN table's 16-bit train index)"); return MCORB_E_SIZE; }
+    HIPCHK(hipSetDevice(db->device));
+    if (!db->h_rows.size()) {
+        TRY(db->d_exp.alloc((size_t)2 * kc * kKnnExpandBytes));
+        TRY(db->d_lcounts.alloc(2));
+        TRY(db->d_part.alloc(knn_part_entries(1, kc)));
+        TRY(db->h_knnctl.alloc(4, hipHostMallocMapped));
+        TRY(db->h_mlist.alloc(knn_mlist_stride(kc), hipHostMallocMapped));
+        TRY(db->h_mcount.alloc((size_t)knn_qblocks(kc), hipHostMallocMapped));
+        TRY(db->h_rows.alloc((size_t)kc, hipHostMallocMapped));
+    }
+    db->h_knnctl[0] = entry;                        // setmap: the two sets of d_desc that become local sets 0 and 1
+    db->h_knnctl[1] = db->max_entries + probe;
+    db->h_knnctl[2] = 0;                            // the pair (query, train)
+    db->h_knnctl[3] = 1;
+    launch_knn2(db->st, db->d_desc, db->d_ndesc, db->h_knnctl, 2, reinterpret_cast<const int2 *>(db->h_knnctl + 2), 1, kc, db->d_exp, db->d_lcounts,
+                db->d_part, 75.f, 0.85f, db->h_rows, db->h_mlist, db->h_mcount, nullptr, nullptr);   // (the accept flag is not read)
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(db->st));
+    for (int q = 0; q < na; q++) {
+        const KnnRow &k = db->h_rows[q];
+        rows[q] = int4{knn_idx0(k), knn_d0(k), knn_idx1(k), knn_d1(k)};
+    }
+    return MCORB_OK;
+}
+
+int mcorb_kfdb_probe_inter_matches_bf(mcorb_kfdb *db, int entry, int probe, const int32_t *lids_prev, const uint8_t *mono_prev,
+                                      const double *p3d_prev, const uint8_t *mono_cur, const double *p3d_cur, int32_t *query_idx,
+                                      int32_t *train_idx, int32_t *dist, int cap, int *n_out)
+{
+    if (n_out) *n_out = 0;
+    TRY(check_db(db, "kfdb probe_inter_matches_bf"));
+    if (cap < 0 || (cap && (!query_idx || !train_idx || !dist))) { set_error("kfdb probe_inter_matches_bf: bad argument"); return MCORB_E_ARG; }
+    std::lock_guard<std::mutex> lk(db->mu);
+    TRY(check_entry(db, entry, "kfdb probe_inter_matches_bf"));
+    TRY(check_probe(db, probe, "kfdb probe_inter_matches_bf"));
+    const int na = db->device < 0 ? (int)(db->entries[entry].desc.size() / 32) : db->mirror[entry].ndesc;
+    const int nb = db->device < 0 ? (int)(db->probes[probe].desc.size() / 32) : db->pmirror[probe].ndesc;
+    if ((na && (!lids_prev || !mono_prev || !p3d_prev)) || (nb && (!mono_cur || !p3d_cur))) {
+        set_error("kfdb probe_inter_matches_bf: bad argument");
+        return MCORB_E_ARG;
+    }
+    std::vector<int4> rows;
+    TRY(knn2_frames(db, entry, probe, na, nb, rows));
+    // `for (auto &m : matches)` of findInterMatches (FrontEnd.cpp:3392-3465)
+    std::vector<int> inds1, inds2, dists;
+    for (int q = 0; q < na; q++) {
+        const int4 m = rows[q];   // {m[0].trainIdx, m[0].distance, m[1].trainIdx, m[1].distance}
+        if (m.x < 0) continue;
+        if (lids_prev[q] == -1) {
+            if (m.z < 0) continue;   // (no second neighbour: the reference reads past m's end)
+            if ((double)(float)m.y > 0.7 * (double)(float)m.w) continue;
+        }
+        const int t = m.x;
+        if (!mono_prev[q] && !mono_cur[t]) {
+            const double dx = p3d_prev[3 * (size_t)q] - p3d_cur[3 * (size_t)t], dy = p3d_prev[3 * (size_t)q + 1] - p3d_cur[3 * (size_t)t + 1],
+                         dz = p3d_prev[3 * (size_t)q + 2] - p3d_cur[3 * (size_t)t + 2];
+            const float distance = (float)sqrt(dx * dx + dy * dy + dz * dz);   // cv::norm of the 3x1 CV_64F difference
+            if (!(distance <= 2.0)) continue;
+        }
+        const auto it = std::find(inds2.begin(), inds2.end(), t);
+        if (it == inds2.end()) {
+            inds2.push_back(t);
+            inds1.push_back(q);
+            dists.push_back(m.y);
+        } else {
+            const size_t k = it - inds2.begin();
+            if (m.y < dists[k]) { inds1[k] = q; dists[k] = m.y; }
+        }
+    }
+    if (n_out) *n_out = (int)inds1.size();
+    if ((int)inds1.size() > cap) { set_error("kfdb probe_inter_matches_bf: output too small"); return MCORB_E_CAP; }
+    for (size_t k = 0; k < inds1.size(); k++) { query_idx[k] = inds1[k]; train_idx[k] = inds2[k]; dist[k] = dists[k]; }
+    return MCORB_OK;
+}
+
+int mcorb_kfdb_last_probe_timing(mcorb_kfdb *db, float *us)
+{
+    TRY(check_db(db, "kfdb last_probe_timing"));
+    if (!us) { set_error("kfdb last_probe_timing: bad argument"); return MCORB_E_ARG; }
+    std::lock_guard<std::mutex> lk(db->mu);
+    *us = db->us_best2p;
     return MCORB_OK;
 }
 
