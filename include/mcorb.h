@@ -596,6 +596,80 @@ int mcorb_kfdb_probe_inter_matches_bf(mcorb_kfdb *db, int entry, int probe, cons
 int mcorb_kfdb_last_probe_timing(mcorb_kfdb *db, float *us);
 
 /* ------------------------------------------------------------------------- */
+/* Local map: FrontEnd::searchLocalMap2 (MCSlam/src/FrontEnd.cpp:4901-5223)   */
+/* from the landmarks of the neighbouring keyframes to the camera-filtered    */
+/* matches (:4953-5171, without the fbow block :5062-5095): the frustum test  */
+/* per landmark and camera, transform() of the accepted descriptors,          */
+/* InterMatchingBow against the current frame, the filter by viewing camera.  */
+/* OptimizePose and the 4x4 inverses stay with the caller.                    */
+/* ------------------------------------------------------------------------- */
+typedef struct mcorb_lmap mcorb_lmap;
+/* one camera of the current frame: camconfig_.R_mats_ / t_mats_ / K_mats_ (row-major) and the translation column of
+ * W_T_cur_vec[cam] = pose * cur_T_ref.inv() (:4964-4970), which the caller computes */
+typedef struct mcorb_lmap_cam {
+    double R[9], t[3], K[9], centre_w[3];
+} mcorb_lmap_cam;
+/* Rcw / tcw: the rotation rows and the translation column of currentFrame->pose.inv() (:4953-4955); width / height: im_size_ */
+typedef struct mcorb_lmap_view {
+    double Rcw[9], tcw[3];
+    int32_t ncams, width, height, reserved;
+    mcorb_lmap_cam cams[MCORB_MAX_CAMS];
+} mcorb_lmap_view;
+/* A store of up to max_landmarks landmarks, slot = lId: pt3D, normal, the descriptor of the landmark's latest observation
+ * (KFs.back()->intraMatches[featInds.back()].matchDesc, :5031-5033) and that observation's mono flag; a search takes up to
+ * max_candidates candidates.  device >= 0: points, normals and descriptors live in HBM on that device, which must be the
+ * vocabulary's, and the frustum test, the descent and the best / second-best search run in HIP kernels (k_lmap_cull,
+ * k_bow_descend, k_kfdb_best2).  device == -1: a host-only store on a host-only vocabulary (mcorb_vocab_create with device -1)
+ * that needs no GPU, written as the reference's loops are; it searches host-only databases.  MCORB_E_ARG for a vocabulary on
+ * another device. */
+int mcorb_lmap_create(mcorb_vocab *v, int device, int max_landmarks, int max_candidates, mcorb_lmap **out);
+void mcorb_lmap_destroy(mcorb_lmap *m);
+/* Sets n landmarks: slot lids[i] takes pt3d[3 * i ..], normal[3 * i ..], desc[32 * i ..] and mono[i] (0 / 1).  Any of the four
+ * arrays may be NULL, which keeps what the slots hold; a slot counts as set once it has a point and a normal, so pt3d or normal
+ * may be NULL only for slots that are set (MCORB_E_STATE otherwise).  Of an id that occurs twice the last occurrence holds.
+ * MCORB_E_ARG for an id outside [0, max_landmarks); nothing is stored on an error. */
+int mcorb_lmap_set(mcorb_lmap *m, const int32_t *lids, int n, const double *pt3d, const double *normal, const uint8_t *desc,
+                   const uint8_t *mono);
+/* The descriptors of LF features feats[i] of a database entry into slots lids[i], and mono[i] with them (mono may be NULL: kept).
+ * A device store copies the rows device to device in one launch: a keyframe's descriptors are in HBM since it was added.
+ * MCORB_E_ARG for an id outside the store, a feature index outside the entry, a missing entry or a database on another device;
+ * the slots need not be set yet. */
+int mcorb_lmap_set_desc_from_entry(mcorb_lmap *m, mcorb_kfdb *db, int entry, const int32_t *lids, const int32_t *feats, int n,
+                                   const uint8_t *mono);
+/* a slot as stored (a device store reads it back from HBM); outputs may be NULL.  *has_desc = 0: no descriptor yet (desc is
+ * then left alone).  MCORB_E_STATE for a slot that was never set. */
+int mcorb_lmap_get(mcorb_lmap *m, int lid, double pt3d[3], double normal[3], uint8_t desc[32], int *mono, int *has_desc);
+/* searchLocalMap2, :4953-5171.
+ * neighbour_lids: the lIds arrays of the keyframes of kfMap back to back in kfMap's order (ascending kfID); matched_lids: the
+ * members of matchedlmset.  db / probe: the current frame in a probe slot of a keyframe database on the store's device -- its
+ * FeatureVector and descriptors are currentFrame->lfFeatVec and img_desc2.  matched_cur / mono_cur / cam_cur: one entry per LF
+ * feature of the probe -- matchedFeatsCurFrame, im2.mono, and the first camera whose matchIndex is not -1 (ii2).
+ * 1. candidates (:4990-4998): neighbour_lids in order, skipping -1, ids seen before in this call and members of matched_lids.
+ * 2. the frustum test (:5000-5027), all in fp64 with separate multiplies and adds, a matrix product as cv::Mat evaluates it
+ *    (per element the sum over k ascending from 0.0, then the addend): pt_body = Rcw * pt + tcw; per camera pt_c = R * pt_body
+ *    + t, dropped if z < 0; curDir = pt - centre_w, dropped if normal . curDir < 0.5 * sqrt(curDir . curDir); tmp = K * pt_c
+ *    and then tmp * (1.0 / tmp_z) (cv::MatExpr's division by a scalar), dropped if x < 30 || x > width - 30 || y < 30 ||
+ *    y > height - 30.  A NaN fails none of these.  A landmark is accepted when at least one camera keeps it.
+ *    new_lids / cam_masks (bit c: camera c, lm_projected_cam_ids): the accepted landmarks in candidate order.
+ * 3. transform(newlm_vecDescs, levelsup)'s FeatureVector of the accepted descriptors (:5106).
+ * 4. InterMatchingBow (:5111, :3791-3845) of that FeatureVector (A) against the probe's (B): ind1 (into new_lids) / ind2 (into
+ *    the probe's LF set) as mcorb_kfdb_probe_feature_matches walks.
+ * 5. the filter (:5122-5171), in ind order: a pair is a match when !matched_cur[ind2], the landmark's mono flag and
+ *    mono_cur[ind2] are both set and cam_cur[ind2] is one of the landmark's cameras; match_query = ind1, match_train = ind2.
+ * Each *n_ receives its count; MCORB_E_CAP (with the counts set) when an output is short.  MCORB_E_ARG for an id other than -1
+ * outside the store, ncams outside 1 .. MCORB_MAX_CAMS or a database on another device; MCORB_E_STATE for a candidate that was
+ * never set, an accepted landmark without a descriptor or a probe slot that was never set; MCORB_E_CAP, before anything runs,
+ * for more candidates than max_candidates. */
+int mcorb_lmap_search(mcorb_lmap *m, const mcorb_lmap_view *view, const int32_t *neighbour_lids, int n_lids,
+                      const int32_t *matched_lids, int n_matched, mcorb_kfdb *db, int probe, const uint8_t *matched_cur,
+                      const uint8_t *mono_cur, const int32_t *cam_cur, int levelsup, double max_neighbor_ratio, int32_t *new_lids,
+                      uint32_t *cam_masks, int cap_new, int *n_new, uint32_t *ind1, uint32_t *ind2, int cap_ind, int *n_ind,
+                      int32_t *match_query, int32_t *match_train, int cap_matches, int *n_matches);
+/* a device store's last k_lmap_cull (us[0]) and k_kfdb_best2 (us[1]) launch, microseconds between HIP events, and the number of
+ * candidates of the last search (may be NULL) */
+int mcorb_lmap_last_timing(mcorb_lmap *m, float us[2], int *n_candidates);
+
+/* ------------------------------------------------------------------------- */
 /* Host stages exposed for the CPU test-suite (no device needed)              */
 /* ------------------------------------------------------------------------- */
 /* The engine's quad-tree selection, DistributeOctTree's equivalent (ORBextractor.cpp:554-778), run

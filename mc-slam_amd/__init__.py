@@ -966,6 +966,133 @@ class ORBDatabase:
         return us.value
 
 
+class LocalMapResult:
+    """what LocalMap.search returns: new_lids / cam_masks (lm_projected_cam_ids as bit masks) of the accepted landmarks in order,
+    ind1 / ind2 as InterMatchingBow returns them (ind1 indexes new_lids), and matches (queryIdx, trainIdx) after the camera filter"""
+
+    def __init__(self, new_lids, cam_masks, ind1, ind2, matches):
+        self.new_lids, self.cam_masks, self.ind1, self.ind2, self.matches = new_lids, cam_masks, ind1, ind2, matches
+
+    def cam_ids(self, i):
+        """lm_projected_cam_ids[i] as the reference's list"""
+        return [c for c in range(_lib.MAX_CAMS) if (int(self.cam_masks[i]) >> c) & 1]
+
+
+def lmap_view(Rcw, tcw, R_mats, t_mats, K_mats, centres_w, width, height):
+    """the view of LocalMap.search: rows and column of currentFrame->pose.inv(), camconfig_'s R / t / K per camera and the
+    translation column of W_T_cur_vec[cam] (FrontEnd.cpp:4953-4970), im_size_"""
+    v = _lib.LmapView()
+    v.Rcw[:] = np.asarray(Rcw, np.float64).reshape(9).tolist()
+    v.tcw[:] = np.asarray(tcw, np.float64).reshape(3).tolist()
+    v.ncams, v.width, v.height = len(R_mats), int(width), int(height)
+    if not 1 <= v.ncams <= _lib.MAX_CAMS or not len(t_mats) == len(K_mats) == len(centres_w) == v.ncams:
+        raise ValueError("lmap_view: 1 .. %d cameras, one R, t, K and centre each" % _lib.MAX_CAMS)
+    for c in range(v.ncams):
+        v.cams[c].R[:] = np.asarray(R_mats[c], np.float64).reshape(9).tolist()
+        v.cams[c].t[:] = np.asarray(t_mats[c], np.float64).reshape(3).tolist()
+        v.cams[c].K[:] = np.asarray(K_mats[c], np.float64).reshape(9).tolist()
+        v.cams[c].centre_w[:] = np.asarray(centres_w[c], np.float64).reshape(3).tolist()
+    return v
+
+
+def lf_mono_cam(lf):
+    """mono_cur / cam_cur of LocalMap.search from mcorb_lf_feature records (Rig.lf_features): im2.mono, and the first camera whose
+    matchIndex is not -1 (ii2, FrontEnd.cpp:5147-5153; -1 for a record without a view)"""
+    lf = np.asarray(lf)
+    seen = lf["match_index"] != -1
+    cam = np.where(seen.any(axis=1), seen.argmax(axis=1), -1).astype(np.int32)
+    return (lf["mono"] != 0).astype(np.uint8), cam
+
+
+class LocalMap:
+    """FrontEnd::searchLocalMap2 (MCSlam/src/FrontEnd.cpp:4901-5223) up to the camera-filtered matches (mcorb_lmap): a store of
+    landmarks (slot = lId: pt3D, normal, the latest observation's descriptor and mono flag) and the search of a frame held in a
+    probe slot of an ORBDatabase against the landmarks of its neighbouring keyframes.
+    device >= 0: the store lives in HBM on the vocabulary's device; device = -1: a host-only store that needs no GPU (on a host-only
+    vocabulary, searching host-only databases)."""
+
+    def __init__(self, voc, device=0, max_landmarks=1 << 16, max_candidates=1 << 16):
+        self.L = _lib.load()
+        self.h = C.c_void_p()
+        self.voc = voc   # (kept alive with the store)
+        self.max_landmarks, self.max_candidates = max_landmarks, max_candidates
+        _lib.check(self.L.mcorb_lmap_create(voc.h, device, max_landmarks, max_candidates, C.byref(self.h)))
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.mcorb_lmap_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @staticmethod
+    def _opt(a, dtype, shape):
+        if a is None:
+            return None, None
+        a = np.ascontiguousarray(a, dtype).reshape(shape)
+        return a, a.ctypes.data
+
+    def set(self, lids, pt3d=None, normal=None, desc=None, mono=None):
+        """slots lids take pt3d / normal (n x 3), desc (n x 32) and mono (n); None keeps what the slots hold"""
+        lids = np.ascontiguousarray(lids, np.int32).reshape(-1)
+        n = len(lids)
+        p, pp = self._opt(pt3d, np.float64, (n, 3))
+        q, qp = self._opt(normal, np.float64, (n, 3))
+        d, dp = self._opt(desc, np.uint8, (n, 32))
+        m, mp = self._opt(None if mono is None else np.asarray(mono) != 0, np.uint8, (n,))
+        _lib.check(self.L.mcorb_lmap_set(self.h, lids.ctypes.data, n, pp, qp, dp, mp))
+
+    def set_desc_from_entry(self, db, entry, lids, feats, mono=None):
+        """the descriptors of LF features `feats` of a database entry into slots lids (device to device on a device store)"""
+        lids = np.ascontiguousarray(lids, np.int32).reshape(-1)
+        feats = np.ascontiguousarray(feats, np.int32).reshape(-1)
+        assert len(lids) == len(feats)
+        m, mp = self._opt(None if mono is None else np.asarray(mono) != 0, np.uint8, (len(lids),))
+        _lib.check(self.L.mcorb_lmap_set_desc_from_entry(self.h, db.h, entry, lids.ctypes.data, feats.ctypes.data, len(lids), mp))
+
+    def get(self, lid):
+        """-> (pt3D, normal, descriptor or None, mono) of a slot as stored"""
+        p, q, d = np.zeros(3), np.zeros(3), np.zeros(32, np.uint8)
+        mono, has = C.c_int(), C.c_int()
+        _lib.check(self.L.mcorb_lmap_get(self.h, lid, p.ctypes.data, q.ctypes.data, d.ctypes.data, C.byref(mono), C.byref(has)))
+        return p, q, (d if has.value else None), bool(mono.value)
+
+    def search(self, view, neighbour_lids, matched_lids, db, probe, matched_cur, mono_cur, cam_cur, levelsup=4, max_neighbor_ratio=0.85,
+               caps=None):
+        """searchLocalMap2's candidates, frustum test, transform, InterMatchingBow and camera filter -> LocalMapResult.
+        view: lmap_view(...); neighbour_lids: the neighbouring keyframes' lIds back to back in kfMap's order; matched_lids:
+        matchedlmset; db / probe: the current frame's probe slot; matched_cur / mono_cur / cam_cur: per LF feature of the probe
+        (lf_mono_cam); caps: (accepted, ind, matches) output sizes, by default what cannot be exceeded"""
+        nl = np.ascontiguousarray(neighbour_lids, np.int32).reshape(-1)
+        ml = np.ascontiguousarray(matched_lids, np.int32).reshape(-1)
+        mc_ = np.ascontiguousarray(np.asarray(matched_cur) != 0, np.uint8).reshape(-1)
+        mo = np.ascontiguousarray(np.asarray(mono_cur) != 0, np.uint8).reshape(-1)
+        cc = np.ascontiguousarray(cam_cur, np.int32).reshape(-1)
+        assert len(mc_) == len(mo) == len(cc)
+        cap_new, cap_ind, cap_m = caps if caps is not None else (max(len(nl), 1), max(db.max_feats, 1), max(db.max_feats, 1))
+        new_lids, masks = np.zeros(max(cap_new, 1), np.int32), np.zeros(max(cap_new, 1), np.uint32)
+        i1, i2 = np.zeros(max(cap_ind, 1), np.uint32), np.zeros(max(cap_ind, 1), np.uint32)
+        mq, mt = np.zeros(max(cap_m, 1), np.int32), np.zeros(max(cap_m, 1), np.int32)
+        self.counts = nn, ni, nm = C.c_int(), C.c_int(), C.c_int()
+        _lib.check(self.L.mcorb_lmap_search(self.h, C.byref(view), nl.ctypes.data, len(nl), ml.ctypes.data, len(ml), db.h, probe,
+                                            mc_.ctypes.data, mo.ctypes.data, cc.ctypes.data, levelsup, max_neighbor_ratio,
+                                            new_lids.ctypes.data, masks.ctypes.data, cap_new, C.byref(nn), i1.ctypes.data, i2.ctypes.data,
+                                            cap_ind, C.byref(ni), mq.ctypes.data, mt.ctypes.data, cap_m, C.byref(nm)))
+        return LocalMapResult(new_lids[:nn.value].copy(), masks[:nn.value].copy(), i1[:ni.value].copy(), i2[:ni.value].copy(),
+                              np.stack([mq[:nm.value], mt[:nm.value]], axis=1).copy())
+
+    def last_timing(self):
+        """(microseconds of the last k_lmap_cull launch, of the last k_kfdb_best2 launch, candidates of the last search); a device store"""
+        us = (C.c_float * 2)()
+        n = C.c_int()
+        _lib.check(self.L.mcorb_lmap_last_timing(self.h, us, C.byref(n)))
+        return us[0], us[1], n.value
+
+
 class DescriptorBlock:
     """nsets descriptor sets resident in HBM (mcorb_descblock): upload a keyframe's LF descriptors once, match any two sets with
     Rig.match_sets (findInterMatches' knnMatch, FrontEnd.cpp:3344-3500)."""

@@ -37,6 +37,15 @@ LF_DTYPE = np.dtype([("match_index", "<i4", (MAX_CAMS,)), ("uv_ref", "<f4", (2,)
                      ("point3d", "<f8", (3,)), ("desc", "u1", (32,))])
 
 
+class LmapCam(C.Structure):
+    _fields_ = [("R", C.c_double * 9), ("t", C.c_double * 3), ("K", C.c_double * 9), ("centre_w", C.c_double * 3)]
+
+
+class LmapView(C.Structure):
+    _fields_ = [("Rcw", C.c_double * 9), ("tcw", C.c_double * 3), ("ncams", C.c_int32), ("width", C.c_int32), ("height", C.c_int32),
+                ("reserved", C.c_int32), ("cams", LmapCam * MAX_CAMS)]
+
+
 class McorbError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("mcorb error %d: %s" % (code, msg))
@@ -165,6 +174,14 @@ SIGNATURES = {
     "mcorb_kfdb_probe_feature_matches": (_i, [_vp, _i, _vp, _i, C.c_double, _vp, _vp, _i, _vp]),
     "mcorb_kfdb_probe_inter_matches_bf": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _ip]),
     "mcorb_kfdb_last_probe_timing": (_i, [_vp, C.POINTER(_f)]),
+    "mcorb_lmap_create": (_i, [_vp, _i, _i, _i, C.POINTER(_vp)]),
+    "mcorb_lmap_destroy": (None, [_vp]),
+    "mcorb_lmap_set": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    "mcorb_lmap_set_desc_from_entry": (_i, [_vp, _vp, _i, _vp, _vp, _i, _vp]),
+    "mcorb_lmap_get": (_i, [_vp, _i, _vp, _vp, _vp, _ip, _ip]),
+    "mcorb_lmap_search": (_i, [_vp, C.POINTER(LmapView), _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, C.c_double, _vp, _vp, _i, _ip,
+                               _vp, _vp, _i, _ip, _vp, _vp, _i, _ip]),
+    "mcorb_lmap_last_timing": (_i, [_vp, C.POINTER(_f), _ip]),
     "mcorb_host_geometry": (_i, [C.POINTER(Params), _i, _i, _vp]),
     "mcorb_synth_rig_frame": (_i, [C.c_uint32, _i, _i, _i, _i, _vp, _i]),
 }

@@ -31,6 +31,9 @@ struct mcorb_vocab {
     std::vector<double> weight;
     std::vector<int> child_start, child_count;   // into the flattened children arrays
     int nwords = 0;
+    // a host-only vocabulary (device -1) keeps the children's ids and descriptors for the host descent (vocab_feature_vector)
+    std::vector<int> child_id;
+    std::vector<uint8_t> child_desc;
     // device copies
     DevBuf<int> d_child_start, d_child_count, d_child_id, d_word_id;
     DevBuf<uint8_t> d_child_desc;
@@ -102,7 +105,12 @@ static int build_vocab(int k, int L, int scoring, int weighting, const int32_t *
             child_desc.insert(child_desc.end(), desc + (size_t)(c - 1) * 32, desc + (size_t)c * 32);
         }
     }
-    if (device == -1) { *out = v.release(); return MCORB_OK; }
+    if (device == -1) {
+        v->child_id = std::move(child_id);
+        v->child_desc = std::move(child_desc);
+        *out = v.release();
+        return MCORB_OK;
+    }
     // device copies; a failure on the way releases the half-built object
     HIPCHK(hipSetDevice(device));
     TRY(v->d_child_start.alloc((size_t)n + 1));
@@ -228,6 +236,48 @@ static int ensure_scratch(mcorb_vocab *v, int n)
     TRY(v->d_desc.grow(cap * 32));
     TRY(v->d_out.grow(cap));
     TRY(v->h_out.grow(cap, hipHostMallocDefault));
+    return MCORB_OK;
+}
+
+// k_bow_descend's walk on the host, for a host-only vocabulary: from the root to the child with the smallest Hamming distance
+// (strict '<': the first child wins) until a leaf, remembering the node at depth nid_level
+static void descend_host(const mcorb_vocab *v, const uint8_t *desc, int n, int nid_level, mcorb::BowRes *out)
+{
+    for (int i = 0; i < n; i++) {
+        int node = 0, nid = 0, level = 0;
+        while (v->child_count[node] > 0) {
+            ++level;
+            const int cs = v->child_start[node], cc = v->child_count[node];
+            int best = 0x7fffffff, bj = 0;
+            for (int j = 0; j < cc; j++) {
+                const int d = mcorb_hamming256(desc + (size_t)i * 32, v->child_desc.data() + (size_t)(cs + j) * 32);
+                if (d < best) { best = d; bj = j; }
+            }
+            node = v->child_id[cs + bj];
+            if (level == nid_level) nid = node;
+        }
+        out[i] = mcorb::BowRes{v->word_id[node], nid, v->weight[node]};
+    }
+}
+
+int mcorb::vocab_feature_vector(mcorb_vocab *v, const uint8_t *desc, int n, int levelsup, hipStream_t st, BowImageOut &o)
+{
+    BowList bow;
+    std::map<uint32_t, std::vector<int32_t>> fv;
+    if (n > 0 && v->device < 0) {
+        std::vector<mcorb::BowRes> res((size_t)n);
+        descend_host(v, desc, n, v->L - levelsup, res.data());
+        assemble(v, res.data(), n, bow, fv);
+    } else if (n > 0) {
+        std::lock_guard<std::mutex> scratch_lock(v->scratch_mu);
+        TRY(ensure_scratch(v, n));
+        launch_bow_descend(st, desc, n, v->d_child_start, v->d_child_count, v->d_child_desc, v->d_child_id, v->d_word_id, v->d_weight, v->L - levelsup, v->d_out);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(v->h_out, v->d_out, (size_t)n * sizeof(mcorb::BowRes), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        assemble(v, v->h_out, n, bow, fv);
+    }
+    to_image_out(bow, fv, o);
     return MCORB_OK;
 }
 

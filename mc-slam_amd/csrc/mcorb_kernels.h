@@ -1,8 +1,9 @@
 // mcorb_kernels.h -- launch wrappers of the gfx950 kernels (mcorb_kernels.hip, mcorb_select_gpu.hip, mcorb_handoff_gpu.hip,
-// mcorb_bow_gpu.hip, mcorb_lf_gpu.hip).
+// mcorb_bow_gpu.hip, mcorb_lf_gpu.hip, mcorb_kfdb_gpu.hip, mcorb_lmap_gpu.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <vector>
+#include "../../include/mcorb.h"
 #include "mcorb_common.h"
 #include "mcorb_signal.h"
 #include "mcorb_undistort.h"
@@ -145,5 +146,14 @@ void launch_kfdb_best2_probes(hipStream_t st, const uint8_t *desc_a, const int *
                               const int *feats_p, size_t feats_stride, const int2 *items, int nitems, const int4 *nodes, int4 *out);
 // k_kfdb_gather: dst[i] = descriptor src[i] of desc, 32 bytes each
 void launch_kfdb_gather(hipStream_t st, const uint8_t *desc, const int *src, int n, uint8_t *dst);
+
+// the local map's kernels (mcorb_lmap_gpu.hip).  k_lmap_cull: searchLocalMap2's frustum test of candidates cand[0 .. n) (slots of
+// geom: 6 doubles per landmark, pt3D then normal) against the cameras of *view (device memory) -> one camera bit mask each
+constexpr int kLmapCullT = 256;   // k_lmap_cull's workgroup: one lane per candidate
+void launch_lmap_cull(hipStream_t st, const mcorb_lmap_view *view, const double *geom, const int *cand, int n, uint32_t *masks);
+// k_lmap_put: entry i of a batch into slot lids[i] (-1: skipped) -- pt[3 * i ..] and normal[3 * i ..] into geom, row rows[i] (rows
+// == NULL: row i) of src_desc into desc; a NULL source leaves that part of the slots alone
+void launch_lmap_put(hipStream_t st, const int *lids, int n, const double *pt, const double *normal, const uint8_t *src_desc,
+                     const int *rows, double *geom, uint8_t *desc);
 
 }  // namespace mcorb

@@ -32,35 +32,18 @@
 #include <mutex>
 #include <vector>
 
-#include "mcorb_engine.h"
+#include "mcorb_kfdb_store.h"
 
 using namespace mcorb;
 
 namespace {
 
-constexpr int TH_LOW = 75;   // ORBextractor.h:27
 constexpr int kMaxProbes = 128;
 
 struct Result {   // DBoW2::Result: ordered by score alone
     uint32_t id;
     double score;
     bool operator<(const Result &r) const { return score < r.score; }
-};
-
-// one stored keyframe of the host-only database
-struct HostEntry {
-    std::vector<uint32_t> ids, nodes;
-    std::vector<double> vals;
-    std::vector<int32_t> offs, feats;
-    std::vector<uint8_t> desc;
-};
-
-// what the host keeps of an entry of the device database: the counts, and the FeatureVector's node ids and offsets (short: the
-// shared-node list of featureMatchesBow is built from them)
-struct Mirror {
-    int nbow = 0, nfv = 0, nff = 0, ndesc = 0;
-    std::vector<uint32_t> nodes;
-    std::vector<int32_t> offs;
 };
 
 struct Vectors {   // a keyframe's vectors in mcorb_vocab_transform's layout
@@ -71,52 +54,6 @@ struct Vectors {   // a keyframe's vectors in mcorb_vocab_transform's layout
 };
 
 }  // namespace
-
-struct mcorb_kfdb {
-    int device = -1, max_entries = 0, max_words = 0, max_feats = 0;
-    int n = 0;
-    int nprobes = 0;   // 0: mcorb_kfdb_reserve_probes has not run
-    int fstride = 0;   // descriptor rows per set in d_desc: max_feats rounded up to launch_knn2's multiple of 64
-    std::vector<char> probe_set;
-    std::mutex mu;   // one call at a time: the scratch below is the database's
-    // host-only database
-    std::vector<HostEntry> entries;
-    std::map<uint32_t, std::vector<std::pair<uint32_t, double>>> ifile;   // word -> (entry, value), entries ascending
-    std::vector<HostEntry> probes;
-    // device database: the store, strided per entry
-    Stream st;
-    Event ev0, ev1;
-    DevBuf<uint32_t> d_ids, d_nodes;     // [max_words], [max_feats]
-    DevBuf<double> d_vals;               // [max_words]
-    DevBuf<int> d_nbow;                  // one per entry
-    DevBuf<int> d_offs, d_feats;         // [max_feats + 1], [max_feats]
-    DevBuf<uint8_t> d_desc;              // [fstride][32]: the entries, then the probe slots
-    DevBuf<int> d_ndesc;                 // descriptors of each set of d_desc (launch_knn2's counts)
-    std::vector<Mirror> mirror;
-    // the probe store: the entries' strides
-    DevBuf<uint32_t> p_ids, p_nodes;
-    DevBuf<double> p_vals;
-    DevBuf<int> p_nbow, p_offs, p_feats;
-    std::vector<Mirror> pmirror;
-    // a host query vector's place on the device (one entry's stride), the control arrays and results of a launch (grow-only)
-    DevBuf<uint32_t> d_qids;
-    DevBuf<double> d_qvals;
-    DevBuf<int> d_qn, d_ctl, d_shared, d_src;
-    DevBuf<double> d_raw;
-    HostBuf<double> h_raw;
-    HostBuf<int> h_shared;
-    DevBuf<int2> d_items, d_mnodes;
-    DevBuf<int4> d_mtab, d_pnodes;
-    HostBuf<int4> h_mtab;
-    // launch_knn2's scratch for one (entry, probe) pair at capacity fstride; the control words and results are host-mapped
-    DevBuf<uint8_t> d_exp;
-    DevBuf<int> d_lcounts;
-    DevBuf<uint2> d_part;
-    HostBuf<int> h_knnctl, h_mcount;     // {setmap[2], pair}
-    HostBuf<KnnRow> h_rows;
-    HostBuf<uint32_t> h_mlist;
-    float us_score = 0.f, us_best2 = 0.f, us_best2p = 0.f;   // the last launch of each kernel, between HIP events
-};
 
 // (entry: the vectors become a new entry, which needs room; a probe slot is overwritten)
 static int check_vectors(const mcorb_kfdb *db, const Vectors &v, int ndesc, bool entry)
@@ -142,24 +79,6 @@ static int check_vectors(const mcorb_kfdb *db, const Vectors &v, int ndesc, bool
     for (int i = 0; i < v.nff; i++)
         if (v.fv_feats[i] < 0 || v.fv_feats[i] >= ndesc) { set_error("kfdb add: FeatureVector names a feature outside the descriptor set"); return MCORB_E_ARG; }
     return MCORB_OK;
-}
-
-// a frame's rows in the device store: entry e, or probe slot e (whose descriptors lie behind the entries')
-struct Place {
-    uint32_t *ids; double *vals; int *nbow;
-    uint32_t *nodes; int *offs, *feats;
-    uint8_t *desc; int *ndesc;
-};
-
-static Place place_of(const mcorb_kfdb *db, int e, bool probe)
-{
-    const size_t i = (size_t)e, W = (size_t)db->max_words, F = (size_t)db->max_feats;
-    const size_t set = probe ? (size_t)db->max_entries + i : i;
-    if (probe)
-        return Place{db->p_ids + i * W, db->p_vals + i * W, db->p_nbow + i, db->p_nodes + i * F, db->p_offs + i * (F + 1), db->p_feats + i * F,
-                     db->d_desc + set * db->fstride * 32, db->d_ndesc + set};
-    return Place{db->d_ids + i * W, db->d_vals + i * W, db->d_nbow + i, db->d_nodes + i * F, db->d_offs + i * (F + 1), db->d_feats + i * F,
-                 db->d_desc + set * db->fstride * 32, db->d_ndesc + set};
 }
 
 // a frame's BowVector, FeatureVector and descriptor count to its place in the store, on `st` (the descriptors are the caller's)
@@ -381,33 +300,6 @@ static int check_entry(const mcorb_kfdb *db, int e, const char *who)
     return MCORB_OK;
 }
 
-static int check_probe(const mcorb_kfdb *db, int p, const char *who)
-{
-    if (p < 0 || p >= db->nprobes) { set_error(std::string(who) + ": no such probe slot"); return MCORB_E_ARG; }
-    if (!db->probe_set[p]) { set_error(std::string(who) + ": the probe slot was never set"); return MCORB_E_STATE; }
-    return MCORB_OK;
-}
-
-// getMatches_distRatio's acceptance and one-to-one bookkeeping (ORBextractor.cpp:1264-1287) for one A feature of a call whose
-// lists so far are mA / mB; mD: the best distance each holder was accepted with = DescriptorDistance(A[holder], B[idx_B])
-static void accept(double best_dist_1, double best_dist_2, uint32_t idx_A, uint32_t idx_B, double max_neighbor_ratio,
-                   std::vector<uint32_t> &mA, std::vector<uint32_t> &mB, std::vector<double> &mD)
-{
-    if (best_dist_1 <= TH_LOW) {
-        if (best_dist_1 / best_dist_2 <= max_neighbor_ratio) {
-            const auto bit = std::find(mB.begin(), mB.end(), idx_B);
-            if (bit == mB.end()) {
-                mB.push_back(idx_B);
-                mA.push_back(idx_A);
-                mD.push_back(best_dist_1);
-            } else {
-                const size_t k = bit - mB.begin();
-                if (best_dist_1 < mD[k]) { mA[k] = idx_A; mD[k] = best_dist_1; }
-            }
-        }
-    }
-}
-
 // L1Scoring::score: a merge walk over the two sorted vectors
 static double score_host(const HostEntry &a, const HostEntry &b)
 {
@@ -425,47 +317,6 @@ static double score_host(const HostEntry &a, const HostEntry &b)
         }
     }
     return -s / 2.0;
-}
-
-// LoopCloser::featureMatchesBow (:217-240) -- FrontEnd::InterMatchingBow and Relocalization::featureMatchesBow walk the same way --
-// calling the literal getMatches_distRatio (ORBextractor.cpp:1228-1290); the matches are appended to i1 / i2
-static void matches_host(const HostEntry &A, const HostEntry &B, double max_neighbor_ratio, std::vector<uint32_t> &i1, std::vector<uint32_t> &i2)
-{
-    std::vector<uint32_t> mA, mB;
-    size_t ia = 0, ib = 0;
-    while (ia < A.nodes.size() && ib < B.nodes.size()) {
-        if (A.nodes[ia] == B.nodes[ib]) {
-            mA.clear(); mB.clear();
-            for (int a = A.offs[ia]; a < A.offs[ia + 1]; a++) {
-                int best_j_now = -1;
-                double best_dist_1 = 1e9, best_dist_2 = 1e9;
-                for (int j = B.offs[ib]; j < B.offs[ib + 1]; j++) {
-                    const double d = mcorb_hamming256(A.desc.data() + (size_t)A.feats[a] * 32, B.desc.data() + (size_t)B.feats[j] * 32);
-                    if (d < best_dist_1) { best_j_now = j; best_dist_2 = best_dist_1; best_dist_1 = d; }
-                    else if (d < best_dist_2) best_dist_2 = d;
-                }
-                if (best_dist_1 <= TH_LOW && best_dist_1 / best_dist_2 <= max_neighbor_ratio) {
-                    const uint32_t idx_B = (uint32_t)B.feats[best_j_now];
-                    const auto bit = std::find(mB.begin(), mB.end(), idx_B);
-                    if (bit == mB.end()) {
-                        mB.push_back(idx_B);
-                        mA.push_back((uint32_t)A.feats[a]);
-                    } else {
-                        const uint32_t idx_A = mA[bit - mB.begin()];
-                        const double d = mcorb_hamming256(A.desc.data() + (size_t)idx_A * 32, B.desc.data() + (size_t)idx_B * 32);
-                        if (best_dist_1 < d) mA[bit - mB.begin()] = (uint32_t)A.feats[a];
-                    }
-                }
-            }
-            i1.insert(i1.end(), mA.begin(), mA.end());
-            i2.insert(i2.end(), mB.begin(), mB.end());
-            ++ia; ++ib;
-        } else if (A.nodes[ia] < B.nodes[ib]) {
-            ia = std::lower_bound(A.nodes.begin() + ia, A.nodes.end(), B.nodes[ib]) - A.nodes.begin();
-        } else {
-            ib = std::lower_bound(B.nodes.begin() + ib, B.nodes.end(), A.nodes[ia]) - B.nodes.begin();
-        }
-    }
 }
 
 extern "C" {

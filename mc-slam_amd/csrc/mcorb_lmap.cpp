@@ -1,0 +1,468 @@
+// mcorb_lmap.cpp -- the local map: FrontEnd::searchLocalMap2 (MCSlam/src/FrontEnd.cpp:4901-5223) from the landmarks of the
+// neighbouring keyframes to the camera-filtered matches (:4953-5171), the consumer of the probe slot that holds the current frame
+// (mcorb_kfdb.cpp).  Not restated: the fbow block (:5062-5095), OptimizePose (:5198) and the 4x4 inverses, which are the caller's.
+//
+// A landmark's slot is its lId.  Two stores, as the keyframe database has two:
+//   device >= 0   points and normals (6 doubles per slot) and descriptors in HBM; the frustum test is k_lmap_cull, the accepted
+//                 rows are gathered (k_kfdb_gather) and descended (k_bow_descend), the best / second-best search is k_kfdb_best2
+//                 with the gathered rows as A and the probe's rows in the database's descriptor store as B, followed by the
+//                 database's accept() per shared node;
+//   device == -1  host only, written the way the reference is: a small cv::Mat-like product per landmark and camera, the host
+//                 descent of a host-only vocabulary, and the literal getMatches_distRatio loop (matches_host).
+// The candidate walk, the compaction of the accepted landmarks (in candidate order), the FeatureVector's assembly, the shared-node
+// walk and the camera filter run on the host in both.  The flags of a slot (has a point, a normal, a descriptor; mono) are
+// host state in both: the filter and the state checks read them, no kernel does.
+//
+// cv::Mat's arithmetic is un-vendored (the eighth unpinned third-party piece): the restated order is that of its small
+// matrix product -- per output element the sum over k ascending, from 0.0, of separately rounded products, then the addend --
+// of Mat::dot and cv::norm over three elements in order, and of MatExpr's `/ scalar`, a multiplication by the reciprocal.
+#include <math.h>
+#include <string.h>
+
+#include <algorithm>
+#include <memory>
+#include <mutex>
+#include <vector>
+
+#include "mcorb_kfdb_store.h"
+
+using namespace mcorb;
+
+namespace {
+constexpr uint8_t kHasPt = 1, kHasNormal = 2, kHasDesc = 4, kMono = 8, kSet = kHasPt | kHasNormal;
+}
+
+struct mcorb_lmap {
+    int device = -1, max_landmarks = 0, max_candidates = 0;
+    mcorb_vocab *voc = nullptr;
+    std::mutex mu;   // one call at a time: the scratch below is the store's
+    std::vector<uint8_t> flags;      // per slot
+    std::vector<int> stamp;          // per slot: the last search (or batch) that saw it
+    int tick = 0;
+    // host-only store
+    std::vector<double> geom;        // [max_landmarks][6]: pt3D, normal
+    std::vector<uint8_t> desc;       // [max_landmarks][32]
+    // device store
+    Stream st;
+    Event ev0, ev1, ev2, ev3;
+    DevBuf<double> d_geom;
+    DevBuf<uint8_t> d_desc;
+    DevBuf<mcorb_lmap_view> d_view;
+    // scratch of a batch (grow-only) and of a search (max_candidates)
+    DevBuf<int> d_blids, d_brows;
+    DevBuf<double> d_bpt, d_bnormal;
+    DevBuf<uint8_t> d_bdesc;
+    DevBuf<int> d_cand, d_afeats;
+    DevBuf<uint32_t> d_masks;
+    HostBuf<uint32_t> h_masks;
+    DevBuf<uint8_t> d_adesc;         // the accepted rows, gathered
+    DevBuf<int2> d_items, d_nodes;
+    DevBuf<int4> d_mtab;
+    HostBuf<int4> h_mtab;
+    float us_cull = 0.f, us_best2 = 0.f;
+    int last_candidates = 0;
+};
+
+static int check_lmap(const mcorb_lmap *m, const char *who)
+{
+    if (!m) { set_error(std::string(who) + ": bad argument"); return MCORB_E_ARG; }
+    return MCORB_OK;
+}
+
+// a new stamp value; the stamps start over before the counter wraps
+static int next_tick(mcorb_lmap *m)
+{
+    if (m->tick == 0x7fffffff) { std::fill(m->stamp.begin(), m->stamp.end(), 0); m->tick = 0; }
+    return ++m->tick;
+}
+
+// what set and set_desc_from_entry share: ids inside the store, and of an id that occurs twice only the last entry kept (keep[i])
+static int check_batch(mcorb_lmap *m, const int32_t *lids, int n, const char *who, std::vector<int> &keep)
+{
+    for (int i = 0; i < n; i++)
+        if (lids[i] < 0 || lids[i] >= m->max_landmarks) { set_error(std::string(who) + ": landmark id outside the store"); return MCORB_E_ARG; }
+    keep.assign(lids, lids + n);
+    const int t = next_tick(m);
+    for (int i = n - 1; i >= 0; i--) {
+        if (m->stamp[lids[i]] == t) keep[i] = -1;
+        m->stamp[lids[i]] = t;
+    }
+    return MCORB_OK;
+}
+
+// a batch into the device store: keep (the slots), the host arrays that are given, or rows `rows` of src_desc (device memory)
+static int put_device(mcorb_lmap *m, const std::vector<int> &keep, const double *pt3d, const double *normal, const uint8_t *desc,
+                      const uint8_t *src_desc, const int32_t *rows)
+{
+    const size_t n = keep.size();
+    HIPCHK(hipSetDevice(m->device));
+    hipStream_t st = m->st;
+    TRY(m->d_blids.grow(n));
+    HIPCHK(hipMemcpyAsync(m->d_blids, keep.data(), n * sizeof(int), hipMemcpyHostToDevice, st));
+    if (pt3d) {
+        TRY(m->d_bpt.grow(n * 3));
+        HIPCHK(hipMemcpyAsync(m->d_bpt, pt3d, n * 3 * sizeof(double), hipMemcpyHostToDevice, st));
+    }
+    if (normal) {
+        TRY(m->d_bnormal.grow(n * 3));
+        HIPCHK(hipMemcpyAsync(m->d_bnormal, normal, n * 3 * sizeof(double), hipMemcpyHostToDevice, st));
+    }
+    if (desc) {
+        TRY(m->d_bdesc.grow(n * 32));
+        HIPCHK(hipMemcpyAsync(m->d_bdesc, desc, n * 32, hipMemcpyHostToDevice, st));
+        src_desc = m->d_bdesc;
+    }
+    if (rows) {
+        TRY(m->d_brows.grow(n));
+        HIPCHK(hipMemcpyAsync(m->d_brows, rows, n * sizeof(int), hipMemcpyHostToDevice, st));
+    }
+    launch_lmap_put(st, m->d_blids, (int)n, pt3d ? m->d_bpt.get() : nullptr, normal ? m->d_bnormal.get() : nullptr, src_desc,
+                    rows ? m->d_brows.get() : nullptr, m->d_geom, m->d_desc);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st));   // (also covers the pageable host arrays)
+    return MCORB_OK;
+}
+
+// the frustum test of one landmark on the host (:5000-5027), with 3x3 * 3x1 products as cv::Mat's gemm evaluates them
+static void mat_mul_add(const double A[9], const double b[3], const double *c, double out[3])
+{
+    for (int r = 0; r < 3; r++) {
+        double s = 0.0;
+        for (int k = 0; k < 3; k++) s += A[3 * r + k] * b[k];
+        out[r] = c ? s + c[r] : s;
+    }
+}
+
+static uint32_t cull_host(const mcorb_lmap_view &v, const double *pt3D, const double *normal)
+{
+    double pt3d_body[3];
+    mat_mul_add(v.Rcw, pt3D, v.tcw, pt3d_body);
+    uint32_t cmids = 0;
+    for (int camID = 0; camID < v.ncams; camID++) {
+        const mcorb_lmap_cam &cam = v.cams[camID];
+        double pt3d_c[3];
+        mat_mul_add(cam.R, pt3d_body, cam.t, pt3d_c);
+        const double z = pt3d_c[2];
+        if (z < 0) continue;
+        double curDir[3];
+        for (int k = 0; k < 3; k++) curDir[k] = pt3D[k] - cam.centre_w[k];
+        double dot = 0.0, norm2 = 0.0;
+        for (int k = 0; k < 3; k++) dot += normal[k] * curDir[k];
+        for (int k = 0; k < 3; k++) norm2 += curDir[k] * curDir[k];
+        if (dot < 0.5 * sqrt(norm2)) continue;
+        double tmp[3];
+        mat_mul_add(cam.K, pt3d_c, nullptr, tmp);
+        const double scale = 1.0 / tmp[2];   // tmp / tmp.at<double>(2, 0): MatExpr multiplies by the reciprocal
+        for (int k = 0; k < 3; k++) tmp[k] = tmp[k] * scale;
+        if (tmp[0] < 30 || tmp[0] > (v.width - 30)) continue;
+        if (tmp[1] < 30 || tmp[1] > (v.height - 30)) continue;
+        cmids |= 1u << camID;
+    }
+    return cmids;
+}
+
+extern "C" {
+
+int mcorb_lmap_create(mcorb_vocab *v, int device, int max_landmarks, int max_candidates, mcorb_lmap **out)
+{
+    if (out) *out = nullptr;
+    if (!v || !out || device < -1 || max_landmarks < 1 || max_candidates < 1) { set_error("lmap create: bad argument"); return MCORB_E_ARG; }
+    int scoring = 0, vdev = 0;
+    vocab_props(v, scoring, vdev);
+    if (vdev != device) { set_error("lmap create: the vocabulary lives on another device (a host-only store needs a host-only vocabulary)"); return MCORB_E_ARG; }
+    std::unique_ptr<mcorb_lmap> m(new mcorb_lmap);
+    m->device = device; m->max_landmarks = max_landmarks; m->max_candidates = max_candidates; m->voc = v;
+    m->flags.assign((size_t)max_landmarks, 0);
+    m->stamp.assign((size_t)max_landmarks, 0);
+    if (device < 0) {
+        m->geom.assign((size_t)max_landmarks * 6, 0.0);
+        m->desc.assign((size_t)max_landmarks * 32, 0);
+    } else {
+        int ndev = 0;
+        if (hipGetDeviceCount(&ndev) != hipSuccess || device >= ndev) { set_error("lmap create: no such HIP device"); return MCORB_E_NODEVICE; }
+        HIPCHK(hipSetDevice(device));
+        const size_t N = (size_t)max_landmarks, C = (size_t)max_candidates;
+        TRY(m->st.create(hipStreamNonBlocking));
+        TRY(m->ev0.create(hipEventDefault));
+        TRY(m->ev1.create(hipEventDefault));
+        TRY(m->ev2.create(hipEventDefault));
+        TRY(m->ev3.create(hipEventDefault));
+        TRY(m->d_geom.alloc(N * 6));
+        TRY(m->d_desc.alloc(N * 32));
+        HIPCHK(hipMemset(m->d_geom, 0, N * 6 * sizeof(double)));
+        HIPCHK(hipMemset(m->d_desc, 0, N * 32));
+        TRY(m->d_view.alloc(1));
+        TRY(m->d_cand.alloc(C));
+        TRY(m->d_afeats.alloc(C));
+        TRY(m->d_masks.alloc(C));
+        TRY(m->h_masks.alloc(C, hipHostMallocDefault));
+        TRY(m->d_adesc.alloc(C * 32));
+    }
+    *out = m.release();
+    return MCORB_OK;
+}
+
+void mcorb_lmap_destroy(mcorb_lmap *m)
+{
+    if (!m) return;
+    if (m->device >= 0 && hipSetDevice(m->device) == hipSuccess && m->st.get()) (void)hipStreamSynchronize(m->st);
+    delete m;
+}
+
+int mcorb_lmap_set(mcorb_lmap *m, const int32_t *lids, int n, const double *pt3d, const double *normal, const uint8_t *desc,
+                   const uint8_t *mono)
+{
+    TRY(check_lmap(m, "lmap set"));
+    if (n < 0 || (n && !lids)) { set_error("lmap set: bad argument"); return MCORB_E_ARG; }
+    std::lock_guard<std::mutex> lk(m->mu);
+    std::vector<int> keep;
+    TRY(check_batch(m, lids, n, "lmap set", keep));
+    const uint8_t given = (pt3d ? kHasPt : 0) | (normal ? kHasNormal : 0);
+    for (int i = 0; i < n; i++)
+        if (((m->flags[lids[i]] | given) & kSet) != kSet) {
+            set_error("lmap set: a slot that was never set needs a point and a normal");
+            return MCORB_E_STATE;
+        }
+    if (n == 0) return MCORB_OK;
+    if (m->device < 0) {
+        for (int i = 0; i < n; i++) {
+            const size_t s = (size_t)lids[i];
+            if (pt3d) memcpy(&m->geom[s * 6], pt3d + 3 * (size_t)i, 3 * sizeof(double));
+            if (normal) memcpy(&m->geom[s * 6 + 3], normal + 3 * (size_t)i, 3 * sizeof(double));
+            if (desc) memcpy(&m->desc[s * 32], desc + 32 * (size_t)i, 32);
+        }
+    } else if (pt3d || normal || desc) {
+        TRY(put_device(m, keep, pt3d, normal, desc, nullptr, nullptr));
+    }
+    for (int i = 0; i < n; i++) {
+        uint8_t &f = m->flags[lids[i]];
+        f |= given | (desc ? kHasDesc : 0);
+        if (mono) f = (uint8_t)((f & ~kMono) | (mono[i] ? kMono : 0));
+    }
+    return MCORB_OK;
+}
+
+int mcorb_lmap_set_desc_from_entry(mcorb_lmap *m, mcorb_kfdb *db, int entry, const int32_t *lids, const int32_t *feats, int n,
+                                   const uint8_t *mono)
+{
+    TRY(check_lmap(m, "lmap set_desc_from_entry"));
+    if (!db || n < 0 || (n && (!lids || !feats))) { set_error("lmap set_desc_from_entry: bad argument"); return MCORB_E_ARG; }
+    std::lock_guard<std::mutex> lk(m->mu);
+    std::lock_guard<std::mutex> lkdb(db->mu);
+    if (db->device != m->device) { set_error("lmap set_desc_from_entry: the database lives on another device"); return MCORB_E_ARG; }
+    if (entry < 0 || entry >= db->n) { set_error("lmap set_desc_from_entry: no such entry"); return MCORB_E_ARG; }
+    const int ndesc = m->device < 0 ? (int)(db->entries[entry].desc.size() / 32) : db->mirror[entry].ndesc;
+    for (int i = 0; i < n; i++)
+        if (feats[i] < 0 || feats[i] >= ndesc) { set_error("lmap set_desc_from_entry: feature index outside the entry"); return MCORB_E_ARG; }
+    std::vector<int> keep;
+    TRY(check_batch(m, lids, n, "lmap set_desc_from_entry", keep));
+    if (n == 0) return MCORB_OK;
+    if (m->device < 0) {
+        const uint8_t *src = db->entries[entry].desc.data();
+        for (int i = 0; i < n; i++) memcpy(&m->desc[(size_t)lids[i] * 32], src + (size_t)feats[i] * 32, 32);
+    } else {
+        TRY(put_device(m, keep, nullptr, nullptr, nullptr, place_of(db, entry, false).desc, feats));
+    }
+    for (int i = 0; i < n; i++) {
+        uint8_t &f = m->flags[lids[i]];
+        f |= kHasDesc;
+        if (mono) f = (uint8_t)((f & ~kMono) | (mono[i] ? kMono : 0));
+    }
+    return MCORB_OK;
+}
+
+int mcorb_lmap_get(mcorb_lmap *m, int lid, double pt3d[3], double normal[3], uint8_t desc[32], int *mono, int *has_desc)
+{
+    TRY(check_lmap(m, "lmap get"));
+    std::lock_guard<std::mutex> lk(m->mu);
+    if (lid < 0 || lid >= m->max_landmarks) { set_error("lmap get: landmark id outside the store"); return MCORB_E_ARG; }
+    const uint8_t f = m->flags[lid];
+    if ((f & kSet) != kSet) { set_error("lmap get: the slot was never set"); return MCORB_E_STATE; }
+    if (mono) *mono = (f & kMono) ? 1 : 0;
+    if (has_desc) *has_desc = (f & kHasDesc) ? 1 : 0;
+    const bool want_desc = desc && (f & kHasDesc);
+    if (m->device < 0) {
+        if (pt3d) memcpy(pt3d, &m->geom[(size_t)lid * 6], 3 * sizeof(double));
+        if (normal) memcpy(normal, &m->geom[(size_t)lid * 6 + 3], 3 * sizeof(double));
+        if (want_desc) memcpy(desc, &m->desc[(size_t)lid * 32], 32);
+        return MCORB_OK;
+    }
+    HIPCHK(hipSetDevice(m->device));
+    if (pt3d) HIPCHK(hipMemcpy(pt3d, m->d_geom + (size_t)lid * 6, 3 * sizeof(double), hipMemcpyDeviceToHost));
+    if (normal) HIPCHK(hipMemcpy(normal, m->d_geom + (size_t)lid * 6 + 3, 3 * sizeof(double), hipMemcpyDeviceToHost));
+    if (want_desc) HIPCHK(hipMemcpy(desc, m->d_desc + (size_t)lid * 32, 32, hipMemcpyDeviceToHost));
+    return MCORB_OK;
+}
+
+int mcorb_lmap_search(mcorb_lmap *m, const mcorb_lmap_view *view, const int32_t *neighbour_lids, int n_lids,
+                      const int32_t *matched_lids, int n_matched, mcorb_kfdb *db, int probe, const uint8_t *matched_cur,
+                      const uint8_t *mono_cur, const int32_t *cam_cur, int levelsup, double max_neighbor_ratio, int32_t *new_lids,
+                      uint32_t *cam_masks, int cap_new, int *n_new, uint32_t *ind1, uint32_t *ind2, int cap_ind, int *n_ind,
+                      int32_t *match_query, int32_t *match_train, int cap_matches, int *n_matches)
+{
+    if (n_new) *n_new = 0;
+    if (n_ind) *n_ind = 0;
+    if (n_matches) *n_matches = 0;
+    TRY(check_lmap(m, "lmap search"));
+    if (!view || !db || n_lids < 0 || n_matched < 0 || (n_lids && !neighbour_lids) || (n_matched && !matched_lids) || cap_new < 0 ||
+        cap_ind < 0 || cap_matches < 0 || (cap_new && (!new_lids || !cam_masks)) || (cap_ind && (!ind1 || !ind2)) ||
+        (cap_matches && (!match_query || !match_train))) {
+        set_error("lmap search: bad argument");
+        return MCORB_E_ARG;
+    }
+    if (view->ncams < 1 || view->ncams > MCORB_MAX_CAMS) { set_error("lmap search: 1 .. MCORB_MAX_CAMS cameras"); return MCORB_E_ARG; }
+    std::lock_guard<std::mutex> lk(m->mu);
+    std::lock_guard<std::mutex> lkdb(db->mu);
+    if (db->device != m->device) { set_error("lmap search: the database lives on another device"); return MCORB_E_ARG; }
+    TRY(check_probe(db, probe, "lmap search"));
+    const int nb = m->device < 0 ? (int)(db->probes[probe].desc.size() / 32) : db->pmirror[probe].ndesc;
+    if (nb && (!matched_cur || !mono_cur || !cam_cur)) { set_error("lmap search: bad argument"); return MCORB_E_ARG; }
+    for (int i = 0; i < n_lids; i++)
+        if (neighbour_lids[i] < -1 || neighbour_lids[i] >= m->max_landmarks) { set_error("lmap search: landmark id outside the store"); return MCORB_E_ARG; }
+    for (int i = 0; i < n_matched; i++)
+        if (matched_lids[i] < 0 || matched_lids[i] >= m->max_landmarks) { set_error("lmap search: landmark id outside the store"); return MCORB_E_ARG; }
+
+    // 1. the candidates (:4990-4998): lmSet and matchedlmset are one stamp per slot
+    const int t = next_tick(m);
+    for (int i = 0; i < n_matched; i++) m->stamp[matched_lids[i]] = t;
+    std::vector<int> cand;
+    for (int i = 0; i < n_lids; i++) {
+        const int l = neighbour_lids[i];
+        if (l == -1 || m->stamp[l] == t) continue;
+        m->stamp[l] = t;
+        cand.push_back(l);
+    }
+    const int nc = (int)cand.size();
+    if (nc > m->max_candidates) { set_error("lmap search: more candidates than max_candidates"); return MCORB_E_CAP; }
+    for (int l : cand)
+        if ((m->flags[l] & kSet) != kSet) { set_error("lmap search: a candidate landmark was never set"); return MCORB_E_STATE; }
+    m->last_candidates = nc;
+
+    // 2. the frustum test (:5000-5027) and the accepted landmarks in candidate order
+    std::vector<int> acc;          // slots
+    std::vector<uint32_t> masks;   // lm_projected_cam_ids
+    hipStream_t st = m->st;
+    if (m->device < 0) {
+        for (int l : cand) {
+            const uint32_t cmids = cull_host(*view, &m->geom[(size_t)l * 6], &m->geom[(size_t)l * 6 + 3]);
+            if (cmids) { acc.push_back(l); masks.push_back(cmids); }
+        }
+    } else if (nc) {
+        HIPCHK(hipSetDevice(m->device));
+        HIPCHK(hipMemcpyAsync(m->d_view, view, sizeof(mcorb_lmap_view), hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(m->d_cand, cand.data(), (size_t)nc * sizeof(int), hipMemcpyHostToDevice, st));
+        HIPCHK(hipEventRecord(m->ev0, st));
+        launch_lmap_cull(st, m->d_view, m->d_geom, m->d_cand, nc, m->d_masks);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(m->ev1, st));
+        HIPCHK(hipMemcpyAsync(m->h_masks, m->d_masks, (size_t)nc * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));   // (also covers the pageable view and candidate list)
+        float ms = 0.f;
+        ev_elapsed(&ms, m->ev0, m->ev1);
+        m->us_cull = ms * 1000.f;
+        for (int i = 0; i < nc; i++)
+            if (m->h_masks[i]) { acc.push_back(cand[i]); masks.push_back(m->h_masks[i]); }
+    }
+    const int na = (int)acc.size();
+    for (int l : acc)
+        if (!(m->flags[l] & kHasDesc)) { set_error("lmap search: an accepted landmark has no descriptor yet"); return MCORB_E_STATE; }
+
+    // 3. transform(newlm_vecDescs, levelsup) (:5106) and 4. InterMatchingBow (:5111)
+    std::vector<uint32_t> i1, i2;
+    BowImageOut fv;
+    if (m->device < 0) {
+        HostEntry A;
+        A.desc.resize((size_t)na * 32);
+        for (int i = 0; i < na; i++) memcpy(&A.desc[(size_t)i * 32], &m->desc[(size_t)acc[i] * 32], 32);
+        TRY(vocab_feature_vector(m->voc, A.desc.data(), na, levelsup, nullptr, fv));
+        A.nodes = fv.fv_nodes; A.offs = fv.fv_offsets; A.feats = fv.fv_feats;
+        matches_host(A, db->probes[probe], max_neighbor_ratio, i1, i2);
+    } else if (na) {
+        HIPCHK(hipMemcpyAsync(m->d_cand, acc.data(), (size_t)na * sizeof(int), hipMemcpyHostToDevice, st));
+        launch_kfdb_gather(st, m->d_desc, m->d_cand, na, m->d_adesc);
+        HIPCHK(hipGetLastError());
+        TRY(vocab_feature_vector(m->voc, m->d_adesc, na, levelsup, st, fv));
+        // the shared nodes in ascending id; one item per A feature of a shared node (mcorb_kfdb_feature_matches' lists)
+        const Mirror &B = db->pmirror[probe];
+        std::vector<int2> items, nodes;
+        std::vector<int> first;
+        size_t ia = 0, ib = 0;
+        while (ia < fv.fv_nodes.size() && ib < B.nodes.size()) {
+            if (fv.fv_nodes[ia] == B.nodes[ib]) {
+                first.push_back((int)items.size());
+                for (int a = fv.fv_offsets[ia]; a < fv.fv_offsets[ia + 1]; a++) items.push_back(int2{a, (int)nodes.size()});
+                nodes.push_back(int2{B.offs[ib], B.offs[ib + 1] - B.offs[ib]});
+                ++ia; ++ib;
+            } else if (fv.fv_nodes[ia] < B.nodes[ib]) ++ia;
+            else ++ib;
+        }
+        first.push_back((int)items.size());
+        const int nitems = (int)items.size();
+        if (nitems) {
+            TRY(m->d_items.grow(items.size()));
+            TRY(m->d_nodes.grow(nodes.size()));
+            TRY(m->d_mtab.grow(items.size()));
+            TRY(m->h_mtab.grow(items.size(), hipHostMallocDefault));
+            const Place pb = place_of(db, probe, true);
+            HIPCHK(hipMemcpyAsync(m->d_afeats, fv.fv_feats.data(), fv.fv_feats.size() * sizeof(int), hipMemcpyHostToDevice, st));
+            HIPCHK(hipMemcpyAsync(m->d_items, items.data(), items.size() * sizeof(int2), hipMemcpyHostToDevice, st));
+            HIPCHK(hipMemcpyAsync(m->d_nodes, nodes.data(), nodes.size() * sizeof(int2), hipMemcpyHostToDevice, st));
+            HIPCHK(hipEventRecord(m->ev2, st));
+            launch_kfdb_best2(st, m->d_adesc, m->d_afeats, pb.desc, pb.feats, m->d_items, nitems, m->d_nodes, m->d_mtab);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipEventRecord(m->ev3, st));
+            HIPCHK(hipMemcpyAsync(m->h_mtab, m->d_mtab, items.size() * sizeof(int4), hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));
+            float ms = 0.f;
+            ev_elapsed(&ms, m->ev2, m->ev3);
+            m->us_best2 = ms * 1000.f;
+            std::vector<uint32_t> mA, mB;
+            std::vector<double> mD;
+            for (size_t k = 0; k + 1 < first.size(); k++) {
+                mA.clear(); mB.clear(); mD.clear();
+                for (int i = first[k]; i < first[k + 1]; i++) {
+                    const int4 r = m->h_mtab[i];   // {B feature of the best or -1, best, second, A feature}
+                    if (r.x < 0) continue;         // an empty B list: best_dist_1 stays 1e9
+                    accept((double)r.y, r.z == 0x7fffffff ? 1e9 : (double)r.z, (uint32_t)r.w, (uint32_t)r.x, max_neighbor_ratio, mA, mB, mD);
+                }
+                i1.insert(i1.end(), mA.begin(), mA.end());
+                i2.insert(i2.end(), mB.begin(), mB.end());
+            }
+        }
+    }
+
+    // 5. the filter by viewing camera (:5122-5171)
+    std::vector<int32_t> mq, mt;
+    for (size_t i = 0; i < i1.size(); i++) {
+        const uint32_t a = i1[i], b = i2[i];
+        if (matched_cur[b]) continue;
+        const bool im1_mono = (m->flags[acc[a]] & kMono) != 0, im2_mono = mono_cur[b] != 0;
+        if (!(im1_mono && im2_mono)) continue;
+        const int ii2 = cam_cur[b];
+        if (ii2 < 0 || ii2 >= MCORB_MAX_CAMS || !((masks[a] >> ii2) & 1u)) continue;
+        mq.push_back((int32_t)a);
+        mt.push_back((int32_t)b);
+    }
+
+    if (n_new) *n_new = na;
+    if (n_ind) *n_ind = (int)i1.size();
+    if (n_matches) *n_matches = (int)mq.size();
+    if (na > cap_new || (int)i1.size() > cap_ind || (int)mq.size() > cap_matches) { set_error("lmap search: output too small"); return MCORB_E_CAP; }
+    for (int i = 0; i < na; i++) { new_lids[i] = acc[i]; cam_masks[i] = masks[i]; }
+    if (!i1.empty()) { memcpy(ind1, i1.data(), i1.size() * 4); memcpy(ind2, i2.data(), i2.size() * 4); }
+    if (!mq.empty()) { memcpy(match_query, mq.data(), mq.size() * 4); memcpy(match_train, mt.data(), mt.size() * 4); }
+    return MCORB_OK;
+}
+
+int mcorb_lmap_last_timing(mcorb_lmap *m, float us[2], int *n_candidates)
+{
+    TRY(check_lmap(m, "lmap last_timing"));
+    if (!us) { set_error("lmap last_timing: bad argument"); return MCORB_E_ARG; }
+    std::lock_guard<std::mutex> lk(m->mu);
+    us[0] = m->us_cull;
+    us[1] = m->us_best2;
+    if (n_candidates) *n_candidates = m->last_candidates;
+    return MCORB_OK;
+}
+
+}  // extern "C"
