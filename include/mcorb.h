@@ -575,9 +575,9 @@ int mcorb_kfdb_score_probe(mcorb_kfdb *db, int entry, int probe, double *score);
  * featureMatchesBow (relocalization.cpp:327-371) of one entry (A: the last keyframe, the best candidate) against np probes: per
  * probe, mcorb_kfdb_feature_matches' walk -- getMatches_distRatio(A, B) for every FeatureVector node entry and probe share, in
  * ascending node id, outputs appended (itr_cng_match is unused in the reference).  A device database searches all probes in one
- * launch of k_kfdb_best2_probes and one copy back.  indices_1 (into the entry's LF set) and indices_2 (into the probe's): np
- * blocks of cap; n_out: np counts (MCORB_E_CAP when a block is short, with the counts set).  The reference's `words` are the
- * entry's FeatureVector nodes of indices_1. */
+ * launch of k_kfdb_best2 (the many-probe launch) and one copy back.  indices_1 (into the entry's LF set) and indices_2 (into the
+ * probe's): np blocks of cap; n_out: np counts (MCORB_E_CAP when a block is short, with the counts set).  The reference's
+ * `words` are the entry's FeatureVector nodes of indices_1. */
 int mcorb_kfdb_probe_feature_matches(mcorb_kfdb *db, int entry, const int32_t *probes, int np, double max_neighbor_ratio,
                                      uint32_t *indices_1, uint32_t *indices_2, int cap, int *n_out);
 /* FrontEnd::findInterMatches (FrontEnd.cpp:3344-3499) of an entry (lf_prev) and a probe (lf_cur): knnMatch(descs_prev, descs_cur,
@@ -592,7 +592,7 @@ int mcorb_kfdb_probe_feature_matches(mcorb_kfdb *db, int entry, const int32_t *p
 int mcorb_kfdb_probe_inter_matches_bf(mcorb_kfdb *db, int entry, int probe, const int32_t *lids_prev, const uint8_t *mono_prev,
                                       const double *p3d_prev, const uint8_t *mono_cur, const double *p3d_cur, int32_t *query_idx,
                                       int32_t *train_idx, int32_t *dist, int cap, int *n_out);
-/* a device database's last k_kfdb_best2_probes launch, microseconds between HIP events */
+/* a device database's last k_kfdb_best2, many-probe launch, microseconds between HIP events */
 int mcorb_kfdb_last_probe_timing(mcorb_kfdb *db, float *us);
 
 /* ------------------------------------------------------------------------- */

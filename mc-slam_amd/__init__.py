@@ -861,17 +861,19 @@ class ORBDatabase:
                                            out_ids.ctypes.data, out_sc.ctypes.data, cap, C.byref(n)))
         return out_ids[:n.value].copy(), out_sc[:n.value].copy()
 
-    def query_entries(self, entries, max_ids, max_results):
-        """the queries are entries of the database, all in one launch, each with its own max_id -> list of (entry ids, scores)"""
-        ent = np.ascontiguousarray(entries, np.int32)
+    def _query_stored(self, call, sel, max_ids, max_results):
+        sel = np.ascontiguousarray(sel, np.int32)
         mx = np.ascontiguousarray(max_ids, np.int32)
-        assert len(ent) == len(mx)
-        nq, cap = len(ent), max(self.size(), 1)
+        assert len(sel) == len(mx)
+        nq, cap = len(sel), max(self.size(), 1)
         out_ids, out_sc = np.zeros((max(nq, 1), cap), np.uint32), np.zeros((max(nq, 1), cap), np.float64)
         n = np.zeros(max(nq, 1), np.int32)
-        _lib.check(self.L.mcorb_kfdb_query_entries(self.h, ent.ctypes.data, mx.ctypes.data, nq, max_results, out_ids.ctypes.data,
-                                                   out_sc.ctypes.data, cap, n.ctypes.data))
+        _lib.check(call(self.h, sel.ctypes.data, mx.ctypes.data, nq, max_results, out_ids.ctypes.data, out_sc.ctypes.data, cap, n.ctypes.data))
         return [(out_ids[q, :n[q]].copy(), out_sc[q, :n[q]].copy()) for q in range(nq)]
+
+    def query_entries(self, entries, max_ids, max_results):
+        """the queries are entries of the database, all in one launch, each with its own max_id -> list of (entry ids, scores)"""
+        return self._query_stored(self.L.mcorb_kfdb_query_entries, entries, max_ids, max_results)
 
     def score(self, a, b):
         """TemplatedVocabulary::score of the BowVectors of entries a and b"""
@@ -915,15 +917,7 @@ class ORBDatabase:
 
     def query_probes(self, probes, max_ids, max_results):
         """query_entries() with probe slots as the queries, all in one launch -> list of (entry ids, scores)"""
-        pr = np.ascontiguousarray(probes, np.int32)
-        mx = np.ascontiguousarray(max_ids, np.int32)
-        assert len(pr) == len(mx)
-        nq, cap = len(pr), max(self.size(), 1)
-        out_ids, out_sc = np.zeros((max(nq, 1), cap), np.uint32), np.zeros((max(nq, 1), cap), np.float64)
-        n = np.zeros(max(nq, 1), np.int32)
-        _lib.check(self.L.mcorb_kfdb_query_probes(self.h, pr.ctypes.data, mx.ctypes.data, nq, max_results, out_ids.ctypes.data,
-                                                  out_sc.ctypes.data, cap, n.ctypes.data))
-        return [(out_ids[q, :n[q]].copy(), out_sc[q, :n[q]].copy()) for q in range(nq)]
+        return self._query_stored(self.L.mcorb_kfdb_query_probes, probes, max_ids, max_results)
 
     def score_probe(self, entry, probe):
         """TemplatedVocabulary::score of an entry's BowVector and a probe's"""
@@ -960,7 +954,7 @@ class ORBDatabase:
         return q[:n.value].copy(), t[:n.value].copy(), d[:n.value].copy()
 
     def probe_timing(self):
-        """microseconds of the last k_kfdb_best2_probes launch (a device database)"""
+        """microseconds of the last k_kfdb_best2, many-probe launch (a device database)"""
         us = C.c_float()
         _lib.check(self.L.mcorb_kfdb_last_probe_timing(self.h, C.byref(us)))
         return us.value

@@ -137,13 +137,11 @@ void launch_tri_selftest(hipStream_t st, const double *x, const double *P, const
 void launch_kfdb_score(hipStream_t st, const uint32_t *ids, const double *vals, const int *nbow, int stride, const uint32_t *q_ids,
                        const double *q_vals, const int *q_n, const int *q_sel, const int *q_limit, const int *e_list, int nq,
                        int max_limit, int out_stride, double *raw, int *shared);
-// k_kfdb_best2: items {position in feats_a, shared node}, nodes {first position, count} in feats_b -> {best B feature or -1, best, second, A feature}
-void launch_kfdb_best2(hipStream_t st, const uint8_t *desc_a, const int *feats_a, const uint8_t *desc_b, const int *feats_b,
-                       const int2 *items, int nitems, const int2 *nodes, int4 *out);
-// k_kfdb_best2_probes: the same for one entry against many probes: items {position in feats_a, shared-node record}, nodes {probe,
-// first position, count} in that probe's feature list (feats_p + probe * feats_stride; its descriptors at desc_p + probe * desc_stride bytes)
-void launch_kfdb_best2_probes(hipStream_t st, const uint8_t *desc_a, const int *feats_a, const uint8_t *desc_p, size_t desc_stride,
-                              const int *feats_p, size_t feats_stride, const int2 *items, int nitems, const int4 *nodes, int4 *out);
+// k_kfdb_best2: one frame A against one or many frames B (the many-probe launch): items {position in feats_a, shared-node record},
+// recs {B's set, first position, count, -} in that B's feature list (feats_b + set * feats_stride; its descriptors at desc_b + set *
+// desc_stride bytes; a single pair: B's own base, set 0) -> {best B feature or -1, best, second, A feature}
+void launch_kfdb_best2(hipStream_t st, const uint8_t *desc_a, const int *feats_a, const uint8_t *desc_b, size_t desc_stride,
+                       const int *feats_b, size_t feats_stride, const int2 *items, int nitems, const int4 *recs, int4 *out);
 // k_kfdb_gather: dst[i] = descriptor src[i] of desc, 32 bytes each
 void launch_kfdb_gather(hipStream_t st, const uint8_t *desc, const int *src, int n, uint8_t *dst);
 

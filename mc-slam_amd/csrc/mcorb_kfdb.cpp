@@ -319,6 +319,72 @@ static double score_host(const HostEntry &a, const HostEntry &b)
     return -s / 2.0;
 }
 
+int Best2Search::create()
+{
+    TRY(ev0.create(hipEventDefault));
+    return ev1.create(hipEventDefault);
+}
+
+void Best2Search::reset()
+{
+    items.clear(); recs.clear(); first_item.clear();
+    first_rec.assign(1, 0);
+}
+
+void Best2Search::add_b(const std::vector<uint32_t> &a_nodes, const std::vector<int32_t> &a_offs, const Mirror &B, int set)
+{
+    size_t ia = 0, ib = 0;
+    while (ia < a_nodes.size() && ib < B.nodes.size()) {
+        if (a_nodes[ia] == B.nodes[ib]) {
+            first_item.push_back((int)items.size());
+            for (int a = a_offs[ia]; a < a_offs[ia + 1]; a++) items.push_back(int2{a, (int)recs.size()});
+            recs.push_back(int4{set, B.offs[ib], B.offs[ib + 1] - B.offs[ib], 0});
+            ++ia; ++ib;
+        } else if (a_nodes[ia] < B.nodes[ib]) ++ia;
+        else ++ib;
+    }
+    first_rec.push_back((int)recs.size());
+}
+
+int Best2Search::run(hipStream_t st, const uint8_t *desc_a, const int *feats_a, const uint8_t *desc_b, size_t desc_stride,
+                     const int *feats_b, size_t feats_stride, double max_neighbor_ratio, std::vector<std::vector<uint32_t>> &i1,
+                     std::vector<std::vector<uint32_t>> &i2, float *us)
+{
+    const size_t nb = first_rec.size() - 1;
+    i1.assign(nb, {}); i2.assign(nb, {});
+    if (items.empty()) return MCORB_OK;
+    first_item.push_back((int)items.size());
+    TRY(d_items.grow(items.size()));
+    TRY(d_recs.grow(recs.size()));
+    TRY(d_mtab.grow(items.size()));
+    TRY(h_mtab.grow(items.size(), hipHostMallocDefault));
+    HIPCHK(hipMemcpyAsync(d_items, items.data(), items.size() * sizeof(int2), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_recs, recs.data(), recs.size() * sizeof(int4), hipMemcpyHostToDevice, st));
+    HIPCHK(hipEventRecord(ev0, st));
+    launch_kfdb_best2(st, desc_a, feats_a, desc_b, desc_stride, feats_b, feats_stride, d_items, (int)items.size(), d_recs, d_mtab);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(ev1, st));
+    HIPCHK(hipMemcpyAsync(h_mtab, d_mtab, items.size() * sizeof(int4), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));   // (also covers the pageable item and record lists)
+    float ms = 0.f;
+    ev_elapsed(&ms, ev0, ev1);
+    *us = ms * 1000.f;
+    std::vector<uint32_t> mA, mB;
+    std::vector<double> mD;
+    for (size_t b = 0; b < nb; b++)
+        for (int k = first_rec[b]; k < first_rec[b + 1]; k++) {
+            mA.clear(); mB.clear(); mD.clear();
+            for (int i = first_item[k]; i < first_item[k + 1]; i++) {
+                const int4 t = h_mtab[i];   // {B feature of the best or -1, best, second, A feature}
+                if (t.x < 0) continue;      // an empty B list: best_dist_1 stays 1e9
+                accept((double)t.y, t.z == 0x7fffffff ? 1e9 : (double)t.z, (uint32_t)t.w, (uint32_t)t.x, max_neighbor_ratio, mA, mB, mD);
+            }
+            i1[b].insert(i1[b].end(), mA.begin(), mA.end());
+            i2[b].insert(i2[b].end(), mB.begin(), mB.end());
+        }
+    return MCORB_OK;
+}
+
 extern "C" {
 
 int mcorb_kfdb_create(const mcorb_vocab *v, int device, int max_entries, int max_words, int max_feats, mcorb_kfdb **out)
@@ -342,6 +408,7 @@ int mcorb_kfdb_create(const mcorb_vocab *v, int device, int max_entries, int max
         TRY(db->st.create(hipStreamNonBlocking));
         TRY(db->ev0.create(hipEventDefault));
         TRY(db->ev1.create(hipEventDefault));
+        TRY(db->best2.create());
         TRY(db->d_ids.alloc(E * W));
         TRY(db->d_vals.alloc(E * W));
         TRY(db->d_nbow.alloc(E));
@@ -479,58 +546,69 @@ int mcorb_kfdb_query(mcorb_kfdb *db, const uint32_t *bow_ids, const double *bow_
     return finish_query(ret, max_results, ids, scores, cap, n_out);
 }
 
-int mcorb_kfdb_query_entries(mcorb_kfdb *db, const int32_t *entries, const int32_t *max_ids, int nq, int max_results, uint32_t *ids,
-                             double *scores, int cap, int *n_out)
+// query_entries / query_probes: nq stored vectors -- entries, or probe slots -- as the queries of one launch
+static int query_stored(mcorb_kfdb *db, bool probe, const char *who, const int32_t *sel, const int32_t *max_ids, int nq, int max_results,
+                        uint32_t *ids, double *scores, int cap, int *n_out)
 {
-    TRY(check_db(db, "kfdb query_entries"));
-    if (nq < 0 || (nq && (!entries || !max_ids || !n_out)) || cap < 0 || (cap && (!ids || !scores))) { set_error("kfdb query_entries: bad argument"); return MCORB_E_ARG; }
+    TRY(check_db(db, who));
+    if (nq < 0 || (nq && (!sel || !max_ids || !n_out)) || cap < 0 || (cap && (!ids || !scores))) { set_error(std::string(who) + ": bad argument"); return MCORB_E_ARG; }
     std::lock_guard<std::mutex> lk(db->mu);
     for (int q = 0; q < nq; q++) {
         n_out[q] = 0;
-        TRY(check_entry(db, entries[q], "kfdb query_entries"));
+        TRY(probe ? check_probe(db, sel[q], who) : check_entry(db, sel[q], who));
     }
     if (nq == 0) return MCORB_OK;
     std::vector<Result> ret;
-    int status = MCORB_OK;
-    if (db->device < 0) {
-        for (int q = 0; q < nq; q++) {
-            const HostEntry &h = db->entries[entries[q]];
-            query_host(db, h.ids.data(), h.vals.data(), (int)h.ids.size(), max_ids[q], ret);
-            const int st = finish_query(ret, max_results, ids + (size_t)q * cap, scores + (size_t)q * cap, cap, n_out + q);
-            if (st != MCORB_OK && status == MCORB_OK) status = st;
-        }
-        return status;
-    }
-    HIPCHK(hipSetDevice(db->device));
     std::vector<int> limit(nq);
-    for (int q = 0; q < nq; q++) limit[q] = limit_of(max_ids[q], db->n);
-    int stride = 1;
-    TRY(run_score(db, entry_bows(db), entry_bows(db), entries, limit.data(), nullptr, nq, &stride));
+    int status = MCORB_OK, stride = 1;
+    if (db->device >= 0) {
+        HIPCHK(hipSetDevice(db->device));
+        for (int q = 0; q < nq; q++) limit[q] = limit_of(max_ids[q], db->n);
+        TRY(run_score(db, entry_bows(db), probe ? probe_bows(db) : entry_bows(db), sel, limit.data(), nullptr, nq, &stride));
+    }
     for (int q = 0; q < nq; q++) {
-        list_of(db, q, stride, limit[q], ret);
+        if (db->device < 0) {
+            const HostEntry &h = probe ? db->probes[sel[q]] : db->entries[sel[q]];
+            query_host(db, h.ids.data(), h.vals.data(), (int)h.ids.size(), max_ids[q], ret);
+        } else {
+            list_of(db, q, stride, limit[q], ret);
+        }
         const int st = finish_query(ret, max_results, ids + (size_t)q * cap, scores + (size_t)q * cap, cap, n_out + q);
         if (st != MCORB_OK && status == MCORB_OK) status = st;
     }
     return status;
 }
 
-int mcorb_kfdb_score(mcorb_kfdb *db, int entry_a, int entry_b, double *score)
+int mcorb_kfdb_query_entries(mcorb_kfdb *db, const int32_t *entries, const int32_t *max_ids, int nq, int max_results, uint32_t *ids,
+                             double *scores, int cap, int *n_out)
 {
-    TRY(check_db(db, "kfdb score"));
-    if (!score) { set_error("kfdb score: bad argument"); return MCORB_E_ARG; }
+    return query_stored(db, false, "kfdb query_entries", entries, max_ids, nq, max_results, ids, scores, cap, n_out);
+}
+
+// score / score_probe: TemplatedVocabulary::score of an entry's vector and another entry's, or a probe's
+static int score_stored(mcorb_kfdb *db, int entry, int b, bool probe, const char *who, double *score)
+{
+    TRY(check_db(db, who));
+    if (!score) { set_error(std::string(who) + ": bad argument"); return MCORB_E_ARG; }
     std::lock_guard<std::mutex> lk(db->mu);
-    TRY(check_entry(db, entry_a, "kfdb score"));
-    TRY(check_entry(db, entry_b, "kfdb score"));
+    TRY(check_entry(db, entry, who));
+    TRY(probe ? check_probe(db, b, who) : check_entry(db, b, who));
     if (db->device < 0) {
-        *score = score_host(db->entries[entry_a], db->entries[entry_b]);
+        *score = score_host(db->entries[entry], probe ? db->probes[b] : db->entries[b]);
         return MCORB_OK;
     }
+    // the entry is the query, b's store the one it is held against
     HIPCHK(hipSetDevice(db->device));
     const int one = 1;
     int stride = 1;
-    TRY(run_score(db, entry_bows(db), entry_bows(db), &entry_a, &one, &entry_b, 1, &stride));
+    TRY(run_score(db, probe ? probe_bows(db) : entry_bows(db), entry_bows(db), &entry, &one, &b, 1, &stride));
     *score = db->h_shared[0] > 0 ? -db->h_raw[0] / 2.0 : 0.0;
     return MCORB_OK;
+}
+
+int mcorb_kfdb_score(mcorb_kfdb *db, int entry_a, int entry_b, double *score)
+{
+    return score_stored(db, entry_a, entry_b, false, "kfdb score", score);
 }
 
 int mcorb_kfdb_feature_matches(mcorb_kfdb *db, int best_entry, int curr_entry, double max_neighbor_ratio, uint32_t *indices_1,
@@ -542,61 +620,20 @@ int mcorb_kfdb_feature_matches(mcorb_kfdb *db, int best_entry, int curr_entry, d
     std::lock_guard<std::mutex> lk(db->mu);
     TRY(check_entry(db, best_entry, "kfdb feature_matches"));
     TRY(check_entry(db, curr_entry, "kfdb feature_matches"));
-    std::vector<uint32_t> i1, i2, mA, mB;
-    std::vector<double> mD;
+    std::vector<std::vector<uint32_t>> i1(1), i2(1);
     if (db->device < 0) {
-        matches_host(db->entries[best_entry], db->entries[curr_entry], max_neighbor_ratio, i1, i2);
+        matches_host(db->entries[best_entry], db->entries[curr_entry], max_neighbor_ratio, i1[0], i2[0]);
     } else {
-        // the shared nodes in ascending id from the host's copy of the two node lists; one item per A feature of a shared node
-        const Mirror &A = db->mirror[best_entry], &B = db->mirror[curr_entry];
-        std::vector<int2> items, nodes;
-        std::vector<int> first;   // per shared node: its first item
-        size_t ia = 0, ib = 0;
-        while (ia < A.nodes.size() && ib < B.nodes.size()) {
-            if (A.nodes[ia] == B.nodes[ib]) {
-                first.push_back((int)items.size());
-                for (int a = A.offs[ia]; a < A.offs[ia + 1]; a++) items.push_back(int2{a, (int)nodes.size()});
-                nodes.push_back(int2{B.offs[ib], B.offs[ib + 1] - B.offs[ib]});
-                ++ia; ++ib;
-            } else if (A.nodes[ia] < B.nodes[ib]) ++ia;
-            else ++ib;
-        }
-        first.push_back((int)items.size());
-        const int nitems = (int)items.size();
-        if (nitems) {
-            HIPCHK(hipSetDevice(db->device));
-            TRY(db->d_items.grow(items.size()));
-            TRY(db->d_mnodes.grow(nodes.size()));
-            TRY(db->d_mtab.grow(items.size()));
-            TRY(db->h_mtab.grow(items.size(), hipHostMallocDefault));
-            hipStream_t st = db->st;
-            const Place pa = place_of(db, best_entry, false), pb = place_of(db, curr_entry, false);
-            HIPCHK(hipMemcpyAsync(db->d_items, items.data(), items.size() * sizeof(int2), hipMemcpyHostToDevice, st));
-            HIPCHK(hipMemcpyAsync(db->d_mnodes, nodes.data(), nodes.size() * sizeof(int2), hipMemcpyHostToDevice, st));
-            HIPCHK(hipEventRecord(db->ev0, st));
-            launch_kfdb_best2(st, pa.desc, pa.feats, pb.desc, pb.feats, db->d_items, nitems, db->d_mnodes, db->d_mtab);
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipEventRecord(db->ev1, st));
-            HIPCHK(hipMemcpyAsync(db->h_mtab, db->d_mtab, items.size() * sizeof(int4), hipMemcpyDeviceToHost, st));
-            HIPCHK(hipStreamSynchronize(st));
-            float ms = 0.f;
-            ev_elapsed(&ms, db->ev0, db->ev1);
-            db->us_best2 = ms * 1000.f;
-            for (size_t k = 0; k + 1 < first.size(); k++) {
-                mA.clear(); mB.clear(); mD.clear();
-                for (int i = first[k]; i < first[k + 1]; i++) {
-                    const int4 t = db->h_mtab[i];   // {B feature of the best or -1, best, second, A feature}
-                    if (t.x < 0) continue;          // an empty B list: best_dist_1 stays 1e9
-                    accept((double)t.y, t.z == 0x7fffffff ? 1e9 : (double)t.z, (uint32_t)t.w, (uint32_t)t.x, max_neighbor_ratio, mA, mB, mD);
-                }
-                i1.insert(i1.end(), mA.begin(), mA.end());
-                i2.insert(i2.end(), mB.begin(), mB.end());
-            }
-        }
+        HIPCHK(hipSetDevice(db->device));
+        const Mirror &A = db->mirror[best_entry];
+        const Place pa = place_of(db, best_entry, false), pb = place_of(db, curr_entry, false);
+        db->best2.reset();
+        db->best2.add_b(A.nodes, A.offs, db->mirror[curr_entry], 0);
+        TRY(db->best2.run(db->st, pa.desc, pa.feats, pb.desc, 0, pb.feats, 0, max_neighbor_ratio, i1, i2, &db->us_best2));
     }
-    if (n_out) *n_out = (int)i1.size();
-    if ((int)i1.size() > cap) { set_error("kfdb feature_matches: output too small"); return MCORB_E_CAP; }
-    if (!i1.empty()) { memcpy(indices_1, i1.data(), i1.size() * 4); memcpy(indices_2, i2.data(), i2.size() * 4); }
+    if (n_out) *n_out = (int)i1[0].size();
+    if ((int)i1[0].size() > cap) { set_error("kfdb feature_matches: output too small"); return MCORB_E_CAP; }
+    if (!i1[0].empty()) { memcpy(indices_1, i1[0].data(), i1[0].size() * 4); memcpy(indices_2, i2[0].data(), i2[0].size() * 4); }
     return MCORB_OK;
 }
 
@@ -645,18 +682,12 @@ int mcorb_kfdb_reserve_probes(mcorb_kfdb *db, int nprobes)
     return MCORB_OK;
 }
 
-static int check_slot(const mcorb_kfdb *db, int p, const char *who)
-{
-    if (p < 0 || p >= db->nprobes) { set_error(std::string(who) + ": no such probe slot"); return MCORB_E_ARG; }
-    return MCORB_OK;
-}
-
 int mcorb_kfdb_set_probe(mcorb_kfdb *db, int probe, const uint32_t *bow_ids, const double *bow_vals, int nbow, const uint32_t *fv_nodes,
                          const int32_t *fv_offsets, int nfv, const int32_t *fv_feats, const uint8_t *desc, int ndesc)
 {
     TRY(check_db(db, "kfdb set_probe"));
     std::lock_guard<std::mutex> lk(db->mu);
-    TRY(check_slot(db, probe, "kfdb set_probe"));
+    TRY(check_probe(db, probe, "kfdb set_probe", false));
     if (nfv < 0 || (nfv && !fv_offsets) || (ndesc > 0 && !desc)) { set_error("kfdb set_probe: bad argument"); return MCORB_E_ARG; }
     const Vectors v{bow_ids, bow_vals, nbow, fv_nodes, fv_offsets, nfv, fv_feats, nfv ? fv_offsets[nfv] : 0};
     return put_frame(db, probe, v, desc, ndesc, nullptr, nullptr);
@@ -668,7 +699,7 @@ int mcorb_kfdb_set_probe_rig_frame(mcorb_kfdb *db, int probe, mcorb_rig *r, int 
     Slot *s = nullptr;
     TRY(rig_frame_of(db, r, slot, frame, "kfdb set_probe_rig_frame", &s));
     std::lock_guard<std::mutex> lk(db->mu);
-    TRY(check_slot(db, probe, "kfdb set_probe_rig_frame"));
+    TRY(check_probe(db, probe, "kfdb set_probe_rig_frame", false));
     const LfFrameOut &o = s->lf[frame];
     return put_frame(db, probe, vectors_of(o), nullptr, (int)o.feats.size(), s, &o);
 }
@@ -687,53 +718,12 @@ int mcorb_kfdb_get_probe(mcorb_kfdb *db, int probe, uint32_t *bow_ids, double *b
 int mcorb_kfdb_query_probes(mcorb_kfdb *db, const int32_t *probes, const int32_t *max_ids, int nq, int max_results, uint32_t *ids,
                             double *scores, int cap, int *n_out)
 {
-    TRY(check_db(db, "kfdb query_probes"));
-    if (nq < 0 || (nq && (!probes || !max_ids || !n_out)) || cap < 0 || (cap && (!ids || !scores))) { set_error("kfdb query_probes: bad argument"); return MCORB_E_ARG; }
-    std::lock_guard<std::mutex> lk(db->mu);
-    for (int q = 0; q < nq; q++) {
-        n_out[q] = 0;
-        TRY(check_probe(db, probes[q], "kfdb query_probes"));
-    }
-    if (nq == 0) return MCORB_OK;
-    std::vector<Result> ret;
-    std::vector<int> limit(nq);
-    int status = MCORB_OK, stride = 1;
-    if (db->device >= 0) {
-        HIPCHK(hipSetDevice(db->device));
-        for (int q = 0; q < nq; q++) limit[q] = limit_of(max_ids[q], db->n);
-        TRY(run_score(db, entry_bows(db), probe_bows(db), probes, limit.data(), nullptr, nq, &stride));
-    }
-    for (int q = 0; q < nq; q++) {
-        if (db->device < 0) {
-            const HostEntry &h = db->probes[probes[q]];
-            query_host(db, h.ids.data(), h.vals.data(), (int)h.ids.size(), max_ids[q], ret);
-        } else {
-            list_of(db, q, stride, limit[q], ret);
-        }
-        const int st = finish_query(ret, max_results, ids + (size_t)q * cap, scores + (size_t)q * cap, cap, n_out + q);
-        if (st != MCORB_OK && status == MCORB_OK) status = st;
-    }
-    return status;
+    return query_stored(db, true, "kfdb query_probes", probes, max_ids, nq, max_results, ids, scores, cap, n_out);
 }
 
 int mcorb_kfdb_score_probe(mcorb_kfdb *db, int entry, int probe, double *score)
 {
-    TRY(check_db(db, "kfdb score_probe"));
-    if (!score) { set_error("kfdb score_probe: bad argument"); return MCORB_E_ARG; }
-    std::lock_guard<std::mutex> lk(db->mu);
-    TRY(check_entry(db, entry, "kfdb score_probe"));
-    TRY(check_probe(db, probe, "kfdb score_probe"));
-    if (db->device < 0) {
-        *score = score_host(db->entries[entry], db->probes[probe]);
-        return MCORB_OK;
-    }
-    // score(entry's vector, probe's): the entry is the query, the probe store the one it is held against
-    HIPCHK(hipSetDevice(db->device));
-    const int one = 1;
-    int stride = 1;
-    TRY(run_score(db, probe_bows(db), entry_bows(db), &entry, &one, &probe, 1, &stride));
-    *score = db->h_shared[0] > 0 ? -db->h_raw[0] / 2.0 : 0.0;
-    return MCORB_OK;
+    return score_stored(db, entry, probe, true, "kfdb score_probe", score);
 }
 
 int mcorb_kfdb_probe_feature_matches(mcorb_kfdb *db, int entry, const int32_t *probes, int np, double max_neighbor_ratio,
@@ -755,62 +745,14 @@ int mcorb_kfdb_probe_feature_matches(mcorb_kfdb *db, int entry, const int32_t *p
     if (db->device < 0) {
         for (int p = 0; p < np; p++) matches_host(db->entries[entry], db->probes[probes[p]], max_neighbor_ratio, i1[p], i2[p]);
     } else {
-        // every probe's shared nodes in ascending id, from the host's copies of the node lists; one item per A feature of a shared
-        // node, probe by probe and node by node: the order the kernel's lanes share B rows in and the host folds the results in
+        // the probe store as the B sets, probe by probe: the order the kernel's lanes share B rows in
+        HIPCHK(hipSetDevice(db->device));
         const Mirror &A = db->mirror[entry];
-        std::vector<int2> items;
-        std::vector<int4> nodes;
-        std::vector<int> first, first_node(1, 0);   // per shared-node record: its first item; per probe: its first record
-        for (int p = 0; p < np; p++) {
-            const Mirror &B = db->pmirror[probes[p]];
-            size_t ia = 0, ib = 0;
-            while (ia < A.nodes.size() && ib < B.nodes.size()) {
-                if (A.nodes[ia] == B.nodes[ib]) {
-                    first.push_back((int)items.size());
-                    for (int a = A.offs[ia]; a < A.offs[ia + 1]; a++) items.push_back(int2{a, (int)nodes.size()});
-                    nodes.push_back(int4{probes[p], B.offs[ib], B.offs[ib + 1] - B.offs[ib], 0});
-                    ++ia; ++ib;
-                } else if (A.nodes[ia] < B.nodes[ib]) ++ia;
-                else ++ib;
-            }
-            first_node.push_back((int)nodes.size());
-        }
-        first.push_back((int)items.size());
-        const int nitems = (int)items.size();
-        if (nitems) {
-            HIPCHK(hipSetDevice(db->device));
-            TRY(db->d_items.grow(items.size()));
-            TRY(db->d_pnodes.grow(nodes.size()));
-            TRY(db->d_mtab.grow(items.size()));
-            TRY(db->h_mtab.grow(items.size(), hipHostMallocDefault));
-            hipStream_t st = db->st;
-            const Place pa = place_of(db, entry, false), p0 = place_of(db, 0, true);
-            HIPCHK(hipMemcpyAsync(db->d_items, items.data(), items.size() * sizeof(int2), hipMemcpyHostToDevice, st));
-            HIPCHK(hipMemcpyAsync(db->d_pnodes, nodes.data(), nodes.size() * sizeof(int4), hipMemcpyHostToDevice, st));
-            HIPCHK(hipEventRecord(db->ev0, st));
-            launch_kfdb_best2_probes(st, pa.desc, pa.feats, p0.desc, (size_t)db->fstride * 32, p0.feats, (size_t)db->max_feats, db->d_items,
-                                     nitems, db->d_pnodes, db->d_mtab);
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipEventRecord(db->ev1, st));
-            HIPCHK(hipMemcpyAsync(db->h_mtab, db->d_mtab, items.size() * sizeof(int4), hipMemcpyDeviceToHost, st));
-            HIPCHK(hipStreamSynchronize(st));
-            float ms = 0.f;
-            ev_elapsed(&ms, db->ev0, db->ev1);
-            db->us_best2p = ms * 1000.f;
-            std::vector<uint32_t> mA, mB;
-            std::vector<double> mD;
-            for (int p = 0; p < np; p++)
-                for (int k = first_node[p]; k < first_node[p + 1]; k++) {
-                    mA.clear(); mB.clear(); mD.clear();
-                    for (int i = first[k]; i < first[k + 1]; i++) {
-                        const int4 t = db->h_mtab[i];   // {B feature of the best or -1, best, second, A feature}
-                        if (t.x < 0) continue;          // an empty B list: best_dist_1 stays 1e9
-                        accept((double)t.y, t.z == 0x7fffffff ? 1e9 : (double)t.z, (uint32_t)t.w, (uint32_t)t.x, max_neighbor_ratio, mA, mB, mD);
-                    }
-                    i1[p].insert(i1[p].end(), mA.begin(), mA.end());
-                    i2[p].insert(i2[p].end(), mB.begin(), mB.end());
-                }
-        }
+        const Place pa = place_of(db, entry, false), p0 = place_of(db, 0, true);
+        db->best2.reset();
+        for (int p = 0; p < np; p++) db->best2.add_b(A.nodes, A.offs, db->pmirror[probes[p]], probes[p]);
+        TRY(db->best2.run(db->st, pa.desc, pa.feats, p0.desc, (size_t)db->fstride * 32, p0.feats, (size_t)db->max_feats, max_neighbor_ratio,
+                          i1, i2, &db->us_best2p));
     }
     int status = MCORB_OK;
     for (int p = 0; p < np; p++) {

@@ -1,8 +1,8 @@
 // mcorb_kfdb_gpu.hip -- the keyframe database's kernels (mcorb_kfdb.cpp): k_kfdb_score (DBoW2 TemplatedDatabase::queryL1 and
 // TemplatedVocabulary::score over the stored BowVectors), k_kfdb_best2 (the best / second-best search of getMatches_distRatio as
-// LoopCloser::featureMatchesBow calls it), k_kfdb_best2_probes (the same search for one entry against many probe frames in one
-// launch: FrontEnd::InterMatchingBow, Relocalization::featureMatchesBow) and k_kfdb_gather (a rig frame's LF descriptors into an
-// entry or a probe slot).  No extraction job runs them and no benchmark leg times them.
+// LoopCloser::featureMatchesBow calls it, and for one entry against many probe frames in one launch: FrontEnd::InterMatchingBow,
+// Relocalization::featureMatchesBow) and k_kfdb_gather (a rig frame's LF descriptors into an entry or a probe slot).  No
+// extraction job runs them and no benchmark leg times them.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -98,60 +98,29 @@ void launch_kfdb_score(hipStream_t st, const uint32_t *ids, const double *vals, 
 }
 
 // ---------------------------------------------------------------------------
-// getMatches_distRatio's search (ORBextractor.cpp:1240-1263) for every A feature of every node two entries share: item i =
-// {position of the A feature in entry A's feature list, shared node}; node k = {first position, count} of the node's B list in
-// entry B's feature list.  One lane per item loops over the B list in list order with strict '<' (the first minimum wins) and
+// getMatches_distRatio's search (ORBextractor.cpp:1240-1263) for every A feature of every node that frame A shares with one or
+// more frames B, in one launch: LoopCloser::featureMatchesBow (one B), FrontEnd::InterMatchingBow / Relocalization::
+// featureMatchesBow of a slot's worth of probe frames (many B's), the local map's search (one B).  item i = {position of the A
+// feature in A's feature list, shared-node record}; record k = {B's set, first position, count, -} of the node's B list in that
+// B's feature list (feats_b + set * feats_stride ints; its descriptors at desc_b + set * desc_stride bytes -- a single pair passes
+// B's own base and set 0).  One lane per item loops over the B list in list order with strict '<' (the first minimum wins) and
 // emits {the best B feature or -1, best, second best (0x7fffffff: none), the A feature}.  The acceptance and the one-to-one
-// bookkeeping stay on the host, in node order.
+// bookkeeping stay on the host, in record order (Best2Search, mcorb_kfdb_store.h).
+// The host lists the items B by B (probe by probe) and, within a B, node by node: the lanes of a wave mostly share a record, so a
+// step of the B loop is one 32-byte row for the whole wave (the same address in every lane), and the rows of a node, which every
+// item of it walks, stay in L2.  The A descriptor is loaded once and stays in registers.  No LDS, no atomics: the work is tens of
+// candidates per item; what a many-probe launch saves is np - 1 submissions and synchronisations.
 // ---------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_kfdb_best2(const uint8_t *__restrict__ desc_a, const int *__restrict__ feats_a,
-                                                    const uint8_t *__restrict__ desc_b, const int *__restrict__ feats_b,
-                                                    const int2 *__restrict__ items, int nitems, const int2 *__restrict__ nodes,
+                                                    const uint8_t *__restrict__ desc_p, size_t desc_stride,
+                                                    const int *__restrict__ feats_p, size_t feats_stride,
+                                                    const int2 *__restrict__ items, int nitems, const int4 *__restrict__ nodes,
                                                     int4 *__restrict__ out)
 {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= nitems) return;
     const int2 it = items[i];
-    const int2 rg = nodes[it.y];
-    const int a = feats_a[it.x];
-    const ulonglong4 q = *reinterpret_cast<const ulonglong4 *>(desc_a + (size_t)a * 32);
-    int4 r = int4{-1, 0x7fffffff, 0x7fffffff, a};
-    for (int j = 0; j < rg.y; j++) {
-        const int b = feats_b[rg.x + j];
-        const int d = (int)hamming256(q, *reinterpret_cast<const ulonglong4 *>(desc_b + (size_t)b * 32));
-        if (d < r.y) { r.x = b; r.z = r.y; r.y = d; }
-        else if (d < r.z) r.z = d;
-    }
-    out[i] = r;
-}
-
-void launch_kfdb_best2(hipStream_t st, const uint8_t *desc_a, const int *feats_a, const uint8_t *desc_b, const int *feats_b,
-                       const int2 *items, int nitems, const int2 *nodes, int4 *out)
-{
-    if (nitems < 1) return;
-    hipLaunchKernelGGL(k_kfdb_best2, dim3((nitems + 255) / 256), dim3(256), 0, st, desc_a, feats_a, desc_b, feats_b, items, nitems, nodes, out);
-}
-
-// ---------------------------------------------------------------------------
-// The same search for one entry (A) against many probes (B) in one launch: FrontEnd::InterMatchingBow / Relocalization::
-// featureMatchesBow of a slot's worth of frames.  item i = {position of the A feature in the entry's feature list, shared-node
-// record}; record k = {probe, first position, count} of the node's B list in that probe's feature list (feats_p / desc_p: the
-// probe store, feats_stride ints and desc_stride bytes per probe).  The host lists the items probe by probe and, within a probe,
-// node by node: the lanes of a wave mostly share a record, so a step of the B loop is one 32-byte row for the whole wave (the
-// same address in every lane), and the rows of a node, which every item of it walks, stay in L2.  The A descriptor is loaded once
-// and stays in registers.  No LDS, no atomics: the work is tens of candidates per item; what the launch saves is np - 1
-// submissions and synchronisations.  Output as k_kfdb_best2's.
-// ---------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_kfdb_best2_probes(const uint8_t *__restrict__ desc_a, const int *__restrict__ feats_a,
-                                                           const uint8_t *__restrict__ desc_p, size_t desc_stride,
-                                                           const int *__restrict__ feats_p, size_t feats_stride,
-                                                           const int2 *__restrict__ items, int nitems, const int4 *__restrict__ nodes,
-                                                           int4 *__restrict__ out)
-{
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= nitems) return;
-    const int2 it = items[i];
-    const int4 rg = nodes[it.y];   // {probe, first, count, -}
+    const int4 rg = nodes[it.y];   // {B's set, first, count, -}
     const int a = feats_a[it.x];
     const ulonglong4 q = *reinterpret_cast<const ulonglong4 *>(desc_a + (size_t)a * 32);
     const uint8_t *desc_b = desc_p + (size_t)rg.x * desc_stride;
@@ -166,12 +135,12 @@ __global__ __launch_bounds__(256) void k_kfdb_best2_probes(const uint8_t *__rest
     out[i] = r;
 }
 
-void launch_kfdb_best2_probes(hipStream_t st, const uint8_t *desc_a, const int *feats_a, const uint8_t *desc_p, size_t desc_stride,
-                              const int *feats_p, size_t feats_stride, const int2 *items, int nitems, const int4 *nodes, int4 *out)
+void launch_kfdb_best2(hipStream_t st, const uint8_t *desc_a, const int *feats_a, const uint8_t *desc_b, size_t desc_stride,
+                       const int *feats_b, size_t feats_stride, const int2 *items, int nitems, const int4 *recs, int4 *out)
 {
     if (nitems < 1) return;
-    hipLaunchKernelGGL(k_kfdb_best2_probes, dim3((nitems + 255) / 256), dim3(256), 0, st, desc_a, feats_a, desc_p, desc_stride, feats_p,
-                       feats_stride, items, nitems, nodes, out);
+    hipLaunchKernelGGL(k_kfdb_best2, dim3((nitems + 255) / 256), dim3(256), 0, st, desc_a, feats_a, desc_b, desc_stride, feats_b,
+                       feats_stride, items, nitems, recs, out);
 }
 
 // dst[i] = the slot's descriptor src[i] (image * kcap + keypoint), 32 bytes each: the LF set of a rig frame, device to device

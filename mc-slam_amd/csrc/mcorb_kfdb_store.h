@@ -1,6 +1,7 @@
 // mcorb_kfdb_store.h -- the keyframe database object and the pieces of mcorb_kfdb.cpp that the local map (mcorb_lmap.cpp) also
 // uses: a stored frame on the host (HostEntry) and on the device (Mirror, Place), the probe-slot check, and getMatches_distRatio --
-// the literal loop of the host-only database (matches_host) and the acceptance that follows k_kfdb_best2 (accept).
+// the literal loop of the host-only database (matches_host), and the device's: k_kfdb_best2 over the shared nodes and the
+// acceptance that follows it (Best2Search, accept).
 #pragma once
 #include <string.h>
 
@@ -30,6 +31,30 @@ struct Mirror {
     int nbow = 0, nfv = 0, nff = 0, ndesc = 0;
     std::vector<uint32_t> nodes;
     std::vector<int32_t> offs;
+};
+
+// getMatches_distRatio of frame A against one or more frames B over the nodes their FeatureVectors share, on the device: what
+// mcorb_kfdb_feature_matches, mcorb_kfdb_probe_feature_matches and mcorb_lmap_search run.  reset(), add_b() per B, run().  The
+// scratch is the owner's: one search at a time.
+struct Best2Search {
+    DevBuf<int2> d_items;
+    DevBuf<int4> d_recs, d_mtab;   // (grow-only, like h_mtab)
+    HostBuf<int4> h_mtab;
+    Event ev0, ev1;
+    std::vector<int2> items;                   // {position in A's feature list, record}, B by B and node by node
+    std::vector<int4> recs;                    // a node A shares with a B: {B's set, first position, count, -} in B's feature list
+    std::vector<int> first_item, first_rec;    // per record: its first item; per B: its first record
+
+    int create();   // (the events; the device is current)
+    void reset();
+    // the nodes that A (ascending node ids, offsets into its feature list) shares with B, whose rows are set `set` of the B store
+    void add_b(const std::vector<uint32_t> &a_nodes, const std::vector<int32_t> &a_offs, const Mirror &B, int set);
+    // One upload, one k_kfdb_best2 launch on st (none without items), one copy back, one synchronisation; then the acceptance
+    // record by record.  desc_a / feats_a: A's rows and feature list; desc_b / feats_b: set 0 of the B store, its sets desc_stride
+    // bytes and feats_stride ints apart.  i1[b] / i2[b]: the matches of the b-th B; *us: the launch between the events, if any.
+    int run(hipStream_t st, const uint8_t *desc_a, const int *feats_a, const uint8_t *desc_b, size_t desc_stride, const int *feats_b,
+            size_t feats_stride, double max_neighbor_ratio, std::vector<std::vector<uint32_t>> &i1,
+            std::vector<std::vector<uint32_t>> &i2, float *us);
 };
 
 }  // namespace mcorb
@@ -67,9 +92,7 @@ struct mcorb_kfdb {
     mcorb::DevBuf<double> d_raw;
     mcorb::HostBuf<double> h_raw;
     mcorb::HostBuf<int> h_shared;
-    mcorb::DevBuf<int2> d_items, d_mnodes;
-    mcorb::DevBuf<int4> d_mtab, d_pnodes;
-    mcorb::HostBuf<int4> h_mtab;
+    mcorb::Best2Search best2;
     // launch_knn2's scratch for one (entry, probe) pair at capacity fstride; the control words and results are host-mapped
     mcorb::DevBuf<uint8_t> d_exp;
     mcorb::DevBuf<int> d_lcounts;
@@ -100,10 +123,11 @@ inline Place place_of(const mcorb_kfdb *db, int e, bool probe)
                  db->d_desc + set * db->fstride * 32, db->d_ndesc + set};
 }
 
-inline int check_probe(const mcorb_kfdb *db, int p, const char *who)
+// (must_be_set = false: a slot about to be written)
+inline int check_probe(const mcorb_kfdb *db, int p, const char *who, bool must_be_set = true)
 {
     if (p < 0 || p >= db->nprobes) { set_error(std::string(who) + ": no such probe slot"); return MCORB_E_ARG; }
-    if (!db->probe_set[p]) { set_error(std::string(who) + ": the probe slot was never set"); return MCORB_E_STATE; }
+    if (must_be_set && !db->probe_set[p]) { set_error(std::string(who) + ": the probe slot was never set"); return MCORB_E_STATE; }
     return MCORB_OK;
 }
 

@@ -6,7 +6,7 @@
 //   device >= 0   points and normals (6 doubles per slot) and descriptors in HBM; the frustum test is k_lmap_cull, the accepted
 //                 rows are gathered (k_kfdb_gather) and descended (k_bow_descend), the best / second-best search is k_kfdb_best2
 //                 with the gathered rows as A and the probe's rows in the database's descriptor store as B, followed by the
-//                 database's accept() per shared node;
+//                 database's accept() per shared node (Best2Search, the database's own path);
 //   device == -1  host only, written the way the reference is: a small cv::Mat-like product per landmark and camera, the host
 //                 descent of a host-only vocabulary, and the literal getMatches_distRatio loop (matches_host).
 // The candidate walk, the compaction of the accepted landmarks (in candidate order), the FeatureVector's assembly, the shared-node
@@ -44,7 +44,7 @@ struct mcorb_lmap {
     std::vector<uint8_t> desc;       // [max_landmarks][32]
     // device store
     Stream st;
-    Event ev0, ev1, ev2, ev3;
+    Event ev0, ev1;
     DevBuf<double> d_geom;
     DevBuf<uint8_t> d_desc;
     DevBuf<mcorb_lmap_view> d_view;
@@ -56,9 +56,7 @@ struct mcorb_lmap {
     DevBuf<uint32_t> d_masks;
     HostBuf<uint32_t> h_masks;
     DevBuf<uint8_t> d_adesc;         // the accepted rows, gathered
-    DevBuf<int2> d_items, d_nodes;
-    DevBuf<int4> d_mtab;
-    HostBuf<int4> h_mtab;
+    Best2Search best2;
     float us_cull = 0.f, us_best2 = 0.f;
     int last_candidates = 0;
 };
@@ -185,8 +183,7 @@ int mcorb_lmap_create(mcorb_vocab *v, int device, int max_landmarks, int max_can
         TRY(m->st.create(hipStreamNonBlocking));
         TRY(m->ev0.create(hipEventDefault));
         TRY(m->ev1.create(hipEventDefault));
-        TRY(m->ev2.create(hipEventDefault));
-        TRY(m->ev3.create(hipEventDefault));
+        TRY(m->best2.create());
         TRY(m->d_geom.alloc(N * 6));
         TRY(m->d_desc.alloc(N * 32));
         HIPCHK(hipMemset(m->d_geom, 0, N * 6 * sizeof(double)));
@@ -382,53 +379,15 @@ int mcorb_lmap_search(mcorb_lmap *m, const mcorb_lmap_view *view, const int32_t 
         launch_kfdb_gather(st, m->d_desc, m->d_cand, na, m->d_adesc);
         HIPCHK(hipGetLastError());
         TRY(vocab_feature_vector(m->voc, m->d_adesc, na, levelsup, st, fv));
-        // the shared nodes in ascending id; one item per A feature of a shared node (mcorb_kfdb_feature_matches' lists)
-        const Mirror &B = db->pmirror[probe];
-        std::vector<int2> items, nodes;
-        std::vector<int> first;
-        size_t ia = 0, ib = 0;
-        while (ia < fv.fv_nodes.size() && ib < B.nodes.size()) {
-            if (fv.fv_nodes[ia] == B.nodes[ib]) {
-                first.push_back((int)items.size());
-                for (int a = fv.fv_offsets[ia]; a < fv.fv_offsets[ia + 1]; a++) items.push_back(int2{a, (int)nodes.size()});
-                nodes.push_back(int2{B.offs[ib], B.offs[ib + 1] - B.offs[ib]});
-                ++ia; ++ib;
-            } else if (fv.fv_nodes[ia] < B.nodes[ib]) ++ia;
-            else ++ib;
-        }
-        first.push_back((int)items.size());
-        const int nitems = (int)items.size();
-        if (nitems) {
-            TRY(m->d_items.grow(items.size()));
-            TRY(m->d_nodes.grow(nodes.size()));
-            TRY(m->d_mtab.grow(items.size()));
-            TRY(m->h_mtab.grow(items.size(), hipHostMallocDefault));
-            const Place pb = place_of(db, probe, true);
+        // A: the gathered rows and their FeatureVector; B: the probe, with its own base as set 0
+        const Place pb = place_of(db, probe, true);
+        std::vector<std::vector<uint32_t>> r1, r2;
+        m->best2.reset();
+        m->best2.add_b(fv.fv_nodes, fv.fv_offsets, db->pmirror[probe], 0);
+        if (!m->best2.items.empty())   // (the run's synchronisation covers the pageable list)
             HIPCHK(hipMemcpyAsync(m->d_afeats, fv.fv_feats.data(), fv.fv_feats.size() * sizeof(int), hipMemcpyHostToDevice, st));
-            HIPCHK(hipMemcpyAsync(m->d_items, items.data(), items.size() * sizeof(int2), hipMemcpyHostToDevice, st));
-            HIPCHK(hipMemcpyAsync(m->d_nodes, nodes.data(), nodes.size() * sizeof(int2), hipMemcpyHostToDevice, st));
-            HIPCHK(hipEventRecord(m->ev2, st));
-            launch_kfdb_best2(st, m->d_adesc, m->d_afeats, pb.desc, pb.feats, m->d_items, nitems, m->d_nodes, m->d_mtab);
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipEventRecord(m->ev3, st));
-            HIPCHK(hipMemcpyAsync(m->h_mtab, m->d_mtab, items.size() * sizeof(int4), hipMemcpyDeviceToHost, st));
-            HIPCHK(hipStreamSynchronize(st));
-            float ms = 0.f;
-            ev_elapsed(&ms, m->ev2, m->ev3);
-            m->us_best2 = ms * 1000.f;
-            std::vector<uint32_t> mA, mB;
-            std::vector<double> mD;
-            for (size_t k = 0; k + 1 < first.size(); k++) {
-                mA.clear(); mB.clear(); mD.clear();
-                for (int i = first[k]; i < first[k + 1]; i++) {
-                    const int4 r = m->h_mtab[i];   // {B feature of the best or -1, best, second, A feature}
-                    if (r.x < 0) continue;         // an empty B list: best_dist_1 stays 1e9
-                    accept((double)r.y, r.z == 0x7fffffff ? 1e9 : (double)r.z, (uint32_t)r.w, (uint32_t)r.x, max_neighbor_ratio, mA, mB, mD);
-                }
-                i1.insert(i1.end(), mA.begin(), mA.end());
-                i2.insert(i2.end(), mB.begin(), mB.end());
-            }
-        }
+        TRY(m->best2.run(st, m->d_adesc, m->d_afeats, pb.desc, 0, pb.feats, 0, max_neighbor_ratio, r1, r2, &m->us_best2));
+        i1.swap(r1[0]); i2.swap(r2[0]);
     }
 
     // 5. the filter by viewing camera (:5122-5171)

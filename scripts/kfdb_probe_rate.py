@@ -1,6 +1,6 @@
 """What matching a slot's worth of frames against one keyframe costs (mcorb_kfdb_probe_feature_matches), on the same machine and inputs:
 one entry and 1, 8, 32 and 128 probes of ~3000 LF features (near copies of the entry's; ~100 FeatureVector nodes):
-  device   k_kfdb_best2_probes between HIP events against its algorithmic bytes (32 B per A descriptor of a shared node once,
+  device   k_kfdb_best2, many-probe launch, between HIP events against its algorithmic bytes (32 B per A descriptor of a shared node once,
            + 32 B per candidate B descriptor), and the whole probe_feature_matches call;
   (a)      the same call on the host-only database;
   (b)      the same pairs as np calls of mcorb_kfdb_feature_matches on a scratch device database where the frames were added.

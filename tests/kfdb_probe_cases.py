@@ -40,6 +40,77 @@ def size_pair():
     return frame(A, fa, perm_a), frame(B, fb, perm_b)
 
 
+BEST2_ITEMS = (1, 255, 256, 257, 0)      # A's features over the nodes it shares with B0 .. B4: a lane, the 256-lane workgroup's edge, none
+BEST2_ORDERS = ([0, 1, 2, 3], [3, 4, 1, 1, 0, 2])
+
+
+@functools.lru_cache(maxsize=None)
+def best2_frames():
+    """frame A and frames B0 .. B4 from explicit FeatureVectors (exact node sizes), for the one best / second-best search behind
+    featureMatchesBow, probe_feature_matches and the local map.  A's nodes (id: features) and who shares them:
+      110: 1  B0, B2, B3   one B candidate: no second neighbour
+      120: 1  B3           two B candidates
+      130: 2  B1 .. B3     both A features are closest to the same B feature, the later one strictly closer
+      140: 2  B1 .. B3     the same at equal distances
+      150: 1  B1 .. B3     two equal minima in B: 4 / 4 passes at ratio 1.0 only, the first wins
+      160: 3  B1 .. B3     an empty B list
+      170: 100, 180: 64, 190: 81   B1 .. B3   near copies of distinct B rows (each B its own flips and order), 15 far A rows among them
+      200: 1, 210: 1  B1 .. B3     near copies, three B candidates
+      220: 5  nobody
+    Nodes 105, 155 and 500 are in B frames only; B4 has only those.  -> (A, [B0 .. B4], near, marks): near[p] = A's near-copy
+    features with a candidate in Bp; marks: node -> (A feature ids, Bp feature ids of B1 .. B3) of the hand-built nodes"""
+    rng = np.random.default_rng(31)
+
+    def rand(n):
+        return rng.integers(0, 256, (n, 32), dtype=np.uint8)
+
+    bulk = {170: 100, 180: 64, 190: 81}
+    base = {n: rand(k) for n, k in bulk.items()}
+    y, z, x, s1, s2, t1, t2 = rand(7)
+    far = rand(40)
+    a_rows = {110: [s1 ^ _bits(5)], 120: [s2 ^ _bits(9)], 130: [y ^ _bits(20), y ^ _bits(10, 100)], 140: [z ^ _bits(20), z ^ _bits(20, 100)],
+              150: [x], 160: [far[0], far[1], far[2]], 200: [t1 ^ _bits(3)], 210: [t2 ^ _bits(6, 50)], 220: list(rand(5))}
+    a_near = {n: [True] * len(r) for n, r in a_rows.items()}
+    for n, k in bulk.items():
+        a_near[n] = [bool(i % 17 != 5) for i in range(k)]                     # 6 + 4 + 5 = 15 far rows
+        a_rows[n] = [_flip(rng, base[n][i], 10) if a_near[n][i] else rand(1)[0] for i in range(k)]
+    assert sum(not v for n in bulk for v in a_near[n]) == 15
+
+    def b_rows(p):
+        r = np.random.default_rng(40 + p)
+        rows = {105: [far[3]], 155: [far[4], far[5]], 500: [far[6]]}
+        if p in (0, 2, 3):
+            rows[110] = [s1]
+        if p == 3:
+            rows[120] = [far[7], s2]
+        if p in (1, 2, 3):
+            rows.update({130: [y, far[8]], 140: [far[9], z], 150: [far[10], x ^ _bits(4), x ^ _bits(4, 100), far[11]], 160: [],
+                         200: [far[12], t1, far[13]], 210: [t2, far[14], far[15]]})
+            for n, k in bulk.items():
+                rows[n] = [_flip(r, base[n][i], 4) for i in r.permutation(k)] + list(far[16 + p:19 + p])
+        return rows
+
+    def frame(rows, seed):
+        nodes = sorted(rows)
+        flat = [d for n in nodes for d in rows[n]]
+        perm = np.random.default_rng(seed).permutation(len(flat))              # feature ids are not in node order
+        inv, fv, at = np.argsort(perm), {}, 0
+        for n in nodes:
+            fv[n] = [int(inv[at + i]) for i in range(len(rows[n]))]
+            at += len(rows[n])
+        return (ONE_WORD, fv, np.array(flat, np.uint8).reshape(-1, 32)[perm])
+
+    A = frame(a_rows, 50)
+    Bs = [frame(b_rows(p), 60 + p) for p in range(5)]
+    near = []
+    for p, B in enumerate(Bs):
+        shared = [n for n in sorted(a_rows) if n in B[1]]
+        assert sum(len(a_rows[n]) for n in shared) == BEST2_ITEMS[p]
+        near.append(sum(sum(a_near[n]) for n in shared if len(B[1][n])))
+    marks = {n: (A[1][n], [Bs[p][1].get(n) for p in (1, 2, 3)]) for n in (110, 120, 130, 140, 150, 160)}
+    return A, Bs, tuple(near), marks
+
+
 @functools.lru_cache(maxsize=None)
 def _lf_pool():
     return np.random.default_rng(7).integers(0, 256, (257, 32), dtype=np.uint8)

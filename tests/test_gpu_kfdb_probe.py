@@ -1,6 +1,6 @@
 """The keyframe database's probe slots on the device (device >= 0: the probe store in HBM, k_kfdb_score with probes as queries,
-k_kfdb_best2_probes, findInterMatches' knnMatch through the k-NN kernel) against the host-only database (device -1), bit for bit,
-on the inputs of test_kfdb_probe_cpu.py."""
+k_kfdb_best2's many-probe launch, findInterMatches' knnMatch through the k-NN kernel) against the host-only database (device -1),
+bit for bit, on the inputs of test_kfdb_probe_cpu.py."""
 import numpy as np
 import pytest
 
@@ -8,7 +8,7 @@ import kfdb_cases as K
 import kfdb_probe_cases as P
 import oracle_lib as O
 from test_gpu_live_lf import calib, frames
-from test_kfdb_probe_cpu import same_frame, same_matches, same_bf, snapshot, same_snapshot
+from test_kfdb_probe_cpu import best2_paths, same_frame, same_matches, same_bf, snapshot, same_snapshot
 
 pytestmark = pytest.mark.gpu
 
@@ -118,6 +118,23 @@ def test_probes_per_launch(lfdbs, nprobes):
                     same_matches(g, dev.probe_feature_matches(e, [p])[0], (e, p))
             if e == 0:
                 assert all(len(g[0]) > 0.5 * len(probes[p][2]) for p, g in zip(sel, got))       # near copies: most features match
+
+
+@pytest.fixture(scope="module")
+def b2dbs(mc, voc):
+    """P.best2_frames(): A as entry 0, B0 .. B4 as entries 1 .. 5 and as probes 0 .. 4, in a device and a host-only database"""
+    A, Bs, _, _ = P.best2_frames()
+    return pair(mc, voc, [A] + Bs, Bs, nprobes=len(Bs))
+
+
+@pytest.mark.parametrize("ratio", [0.85, 1.0])
+def test_best2_search_paths_agree(b2dbs, ratio):
+    """the one k_kfdb_best2 search through its call paths -- a single pair of entries, one probe, many probes in any order -- on
+    1, 255, 256, 257 and 0 items gives the lists of the host-only database (test_kfdb_probe_cpu.py holds those against the
+    restatement and counts the edge cases of the frames)"""
+    dev, host = b2dbs
+    for p, (g, w) in enumerate(zip(best2_paths(dev, ratio), best2_paths(host, ratio))):
+        same_matches(g, w, (p, ratio))
 
 
 def bf_args(rng, nq, nt):

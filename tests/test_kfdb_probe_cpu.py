@@ -160,6 +160,73 @@ def test_probe_equals_entry_of_the_same_frame(mdb):
             assert db.score_probe(e, p) == scratch.score(e, 3 + p)
 
 
+def best2_paths(db, ratio):
+    """the one shared-node best / second-best search through featureMatchesBow and probe_feature_matches on P.best2_frames(),
+    stored in db as entries 0 (A) and 1 .. 5 (B0 .. B4) and probes 0 .. 4 (B0 .. B4) -> the matches of A and each B"""
+    _, Bs, near, _ = P.best2_frames()
+    single = [db.probe_feature_matches(0, [p], ratio)[0] for p in range(len(Bs))]
+    for p in range(len(Bs)):
+        same_matches(db.featureMatchesBow(0, 1 + p, ratio), single[p], (p, ratio))
+    for order in P.BEST2_ORDERS:
+        got = db.probe_feature_matches(0, order, ratio)
+        assert len(got) == len(order)
+        for p, g in zip(order, got):
+            same_matches(g, single[p], (order, p, ratio))
+    assert len(single[4][0]) == 0                                   # no shared node: no item, no launch
+    for p in range(4):
+        assert 2 * len(single[p][0]) >= near[p] > 0, (p, len(single[p][0]), near[p])
+    return single
+
+
+def best2_edge_counts(A, B):
+    """getMatches_distRatio's search over the shared nodes of two frames in plain numpy -> how many A features meet an empty B
+    list, a single candidate or two equal minima, and how many B features are the best of two A features of a node at equal and
+    at unequal distances"""
+    bits_a, bits_b = np.unpackbits(A[2], axis=1).astype(np.int32), np.unpackbits(B[2], axis=1).astype(np.int32)
+    c = dict(empty=0, single=0, tie=0, contested_equal=0, contested_unequal=0)
+    for node in sorted(set(A[1]) & set(B[1])):
+        best = {}
+        for a in A[1][node]:
+            d = [int(np.abs(bits_a[a] - bits_b[b]).sum()) for b in B[1][node]]
+            c["empty"] += len(d) == 0
+            c["single"] += len(d) == 1
+            c["tie"] += len(d) > 1 and sorted(d)[0] == sorted(d)[1]
+            if d and min(d) <= 75:
+                best.setdefault(d.index(min(d)), []).append(min(d))
+        for ds in best.values():
+            c["contested_equal"] += len(ds) > 1 and len(set(ds)) == 1
+            c["contested_unequal"] += len(set(ds)) > 1
+    return c
+
+
+@pytest.mark.parametrize("ratio", [0.85, 1.0])
+def test_best2_search_paths_agree(ratio):
+    """featureMatchesBow(A, B as an entry), probe_feature_matches(A, [B as a probe]) and a many-probe call give the same lists on
+    frames whose shared nodes hold 1, 255, 256, 257 and 0 items, and the lists are the restatement's.  The constructed cases occur
+    (counted over B0 .. B3 by best2_edge_counts): an empty B list, a single candidate, two equal minima, a contested B feature."""
+    A, Bs, _, marks = P.best2_frames()
+    db, rp = fill([A] + Bs, Bs)
+    single = best2_paths(db, ratio)
+    want = [rp.feature_matches(0, p, ratio) for p in range(len(Bs))]
+    for p in range(len(Bs)):
+        same_matches(single[p], want[p], (p, ratio))
+    counts = [best2_edge_counts(A, B) for B in Bs[:4]]
+    total = {k: sum(c[k] for c in counts) for k in counts[0]}
+    assert all(v >= 1 for v in total.values()), total
+    assert counts[0]["single"] == 1 and all(c["empty"] == 3 and c["tie"] >= 1 and c["contested_equal"] >= 1 and c["contested_unequal"] >= 1
+                                            for c in counts[1:]), counts
+    # ... and the restatement alone decides them as constructed
+    for i, p in enumerate((1, 2, 3)):
+        m = dict(zip(want[p][0].tolist(), want[p][1].tolist()))                 # A feature -> B feature
+        (a130, b130), (a140, b140), (a150, b150), (a160, _) = ((marks[n][0], marks[n][1][i]) for n in (130, 140, 150, 160))
+        assert a130[0] not in m and m[a130[1]] == b130[0]                       # the later, strictly closer A takes the B feature
+        assert m[a140[0]] == b140[1] and a140[1] not in m                       # at equal distances the holder stays
+        assert (m.get(a150[0]) == b150[1]) if ratio == 1.0 else (a150[0] not in m)     # the first of two equal minima
+        assert not any(a in m for a in a160)
+    m0, m3 = (dict(zip(want[p][0].tolist(), want[p][1].tolist())) for p in (0, 3))
+    assert m0 == {marks[110][0][0]: Bs[0][1][110][0]} and m3[marks[120][0][0]] == marks[120][1][2][1]
+
+
 def bf_db(prev, cur):
     db, _ = fill([(P.ONE_WORD, {}, prev)], [(P.ONE_WORD, {}, cur)], max_feats=64)
     return db
