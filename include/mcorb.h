@@ -670,6 +670,91 @@ int mcorb_lmap_search(mcorb_lmap *m, const mcorb_lmap_view *view, const int32_t 
 int mcorb_lmap_last_timing(mcorb_lmap *m, float us[2], int *n_candidates);
 
 /* ------------------------------------------------------------------------- */
+/* Mapping: FrontEnd::triangulateNeighbors (MCSlam/src/FrontEnd.cpp:4856-4899) */
+/* with triangulateMatches (:5758-5953) and getSceneDepthStats (:4838-4853):  */
+/* the still-unassigned inter-frame matches of the current frame against its  */
+/* neighbouring keyframes become new landmarks of the local map.              */
+/* TriangulateNewLandmarks (:6465-6700), insertKeyFrame and the cv::Mat        */
+/* inverses stay with the caller.                                             */
+/* ------------------------------------------------------------------------- */
+/* one keyframe's observations */
+typedef struct mcorb_map_frame {
+    int32_t nfeat, ncams;
+    const int32_t *match_index;              /* nfeat x ncams: intraMatches[i].matchIndex, -1 = no view */
+    const mcorb_keypoint *const *kps_undist; /* per camera: image_kps_undist (pt and octave are read) */
+    const int32_t *nkps;                     /* per camera */
+    double centre_w[MCORB_MAX_CAMS][3];      /* per camera: the translation column of W_T_cur = pose * cur_T_ref.inv()
+                                              * (Landmark::updateNormal, GlobalMap.cpp:45-49) */
+    double proj[MCORB_MAX_CAMS][12];         /* per camera: rows 0..2 of cur_T_ref * pose.inv() (:5761-5776), row-major 3x4 */
+    double twc[3];                           /* the pose's translation column (:4860, :4869) */
+} mcorb_map_frame;
+/* the outputs of mcorb_lmap_triangulate_neighbours.  The per-match arrays hold the neighbours' matches back to back, cap_matches
+ * entries each (3 x cap_matches for pt3d and normal); neigh_skipped has one entry per neighbour; depth_vec has cap_depth. */
+typedef struct mcorb_map_out {
+    int32_t cap_matches, cap_depth;  /* in */
+    uint8_t *inliers;                /* triangulateMatches' inliers[i] */
+    uint8_t *verdict;                /* how the match ended: 0 a new landmark, 1 epipolar line with den == 0, 2 epipolar distance,
+                                      * 3 behind a camera, 4 reprojection error (chi-square), 5 outside the parallax window,
+                                      * 6 one of the two features had a landmark already, 7 the neighbour was skipped */
+    int32_t *new_lid;                /* the new landmark's id, or -1 */
+    double *pt3d, *normal;           /* of the new landmark (zero where new_lid is -1) */
+    double *dist2, *cos_parallax;    /* for verdicts 0 and 5, else zero */
+    uint8_t *neigh_skipped;          /* 0 used, 1 baseline / medianDepth < 0.01, 2 no landmark in its lIds */
+    double *depth_vec;               /* dist2 of the new landmarks in the order they were made (what :5933 appends) */
+    int32_t n_matches, n_depth, n_triangulated, next_lid;   /* out; next_lid: the first id not given out */
+} mcorb_map_out;
+/* triangulateNeighbors.  cur / lids_cur: the current frame and its lIds (nfeat entries; the reference reads currentFrame->lIds at
+ * :5819 although the parameter is curFrame -- in the live call they are one object); neigh / lids_neigh: n_neigh keyframes in
+ * kfMap.rbegin() order (descending id) and their lIds; every frame has cur->ncams cameras.  F21[s]: ncams x ncams row-major 3x3
+ * matrices for neighbour s, index [c_cur][c_neigh] = the cameras of the first current view and of the first neighbour view
+ * (:5841-5845; the inverses in it are the caller's).  match_query / match_train / n_matches: interMatches per neighbour (queryIdx
+ * into the neighbour's features, trainIdx into the current frame's).  K: ncams row-major 3x3 K_mats_; inv_sigma2: nlevels values of
+ * GetInverseScaleSigmaSquares(); Rcw / tcw: rows and column of currentFrame->pose.inv() (:4857-4859); next_lid: the id the first new
+ * landmark takes (GlobalMap::insertLandmark counts up).
+ * Per neighbour in order: medianDepth = element (n - 1) / 2 of the sorted z of Rcw * pt3D + tcw over its landmarks (read from the
+ * store), baseline = norm(cur->twc - neigh->twc); the neighbour is skipped when baseline / medianDepth < 0.01 (:4868-4873).  A
+ * neighbour with no landmark in its lIds is undefined behaviour in the reference (it indexes an empty vector); here it is skipped
+ * and flagged 2.  Then its matches in order: skipped (verdict 6, inliers false) when lids_neigh[q] != -1 || lids_cur[t] != -1;
+ * otherwise the views of both features (cameras ascending, the neighbour's first), the epipolar gate in the reference's mixed
+ * float / double arithmetic, cv::sfm::triangulatePoints (the DLT of mcorb_rig_obtain_lf_features: 1e-9 relative against an SVD,
+ * unpinned), per view p.z < 0 and the chi-square gate err * invSigma2[octave] > 5.991, and the parallax window cos < 0.99998 &&
+ * cos > 0.5; a match that passes every reject gate but fails the window keeps inliers true and makes no landmark, as in the
+ * reference.  A new landmark takes the next id, which is written to both lIds arrays (and so skips every later match of either
+ * feature, across neighbours for the current frame's), its dist2 is appended to depth_vec, and its point and its normal --
+ * Landmark::updateNormal for the neighbour (KFs.size() == 1) and then for the current frame, every division by a scalar a
+ * multiplication by the reciprocal as cv::MatExpr does it -- are stored in slot id of the map (flags: point and normal set, no
+ * descriptor yet).  All arithmetic is fp64 (float where the reference has float) with separate multiplies and adds in cv::Mat's
+ * order.  A device store computes the per-match part in k_map_triangulate and the depths in k_map_depth, one submission for all
+ * neighbours, and moves the accepted points and normals into their slots device to device; a host-only store runs the same
+ * code serially; the results are equal bit for bit.
+ * MCORB_E_ARG, before anything runs: a frame with another camera count, an index outside a frame or its keypoints, an octave
+ * outside [0, nlevels), a matched feature without a view, a match of more than MCORB_MAX_CAMS views in total (the solver's design
+ * limit), an id outside [-1, max_landmarks).  MCORB_E_STATE: a neighbour's landmark that was never set.  MCORB_E_CAP, with
+ * n_matches / n_depth / n_triangulated set and nothing stored or written: cap_matches or cap_depth short, or new ids at or beyond
+ * max_landmarks. */
+int mcorb_lmap_triangulate_neighbours(mcorb_lmap *m, const mcorb_map_frame *cur, int32_t *lids_cur, const mcorb_map_frame *neigh,
+                                      int32_t *const *lids_neigh, int n_neigh, const double *const *F21,
+                                      const int32_t *const *match_query, const int32_t *const *match_train, const int32_t *n_matches,
+                                      const double *K, const float *inv_sigma2, int nlevels, const double Rcw[9], const double tcw[3],
+                                      int32_t next_lid, mcorb_map_out *out);
+/* getSceneDepthStats' depthVec (:4843-4848) before its sort: z[i] = row 2 of Rcw * pt3D(lids[i]) + tcw, k_map_depth on a device store.
+ * MCORB_E_ARG for an id outside the store, MCORB_E_STATE for a slot that was never set. */
+int mcorb_lmap_depths(mcorb_lmap *m, const double Rcw[9], const double tcw[3], const int32_t *lids, int n, double *z);
+/* a device store's last k_map_triangulate launches (us[0], both instances) and k_map_depth launch (us[1]), microseconds between HIP
+ * events, the matches that were launched and the landmarks whose depth was taken (both may be NULL) */
+int mcorb_lmap_last_triangulate_timing(mcorb_lmap *m, float us[2], int *n_launched, int *n_depth);
+/* test hooks: everything of a match but the triangulation -- the epipolar gate, then for the caller's X the per-view gates, the
+ * parallax window and the normal -- for n cases on the host and in one launch on the device.  Case i has nv[i] views, the first
+ * nv1[i] the neighbour's (1 <= nv1 < nv <= MCORB_MAX_CAMS), views back to back: P 12, K 9, centre 3 doubles, kps 2 floats and one
+ * octave per view; X 3 and F 9 doubles per case.  verdict / n_rays: n entries; vals: 5 per case (dist2, cos, normal). */
+int mcorb_host_map_gates(int n, const double *X, const int32_t *nv1, const int32_t *nv, const double *P, const double *K,
+                         const double *centre, const float *kps, const int32_t *octave, const double *F, const float *inv_sigma2,
+                         int nlevels, int32_t *verdict, int32_t *n_rays, double *vals);
+int mcorb_dev_map_gates_selftest(int device, int n, const double *X, const int32_t *nv1, const int32_t *nv, const double *P,
+                                 const double *K, const double *centre, const float *kps, const int32_t *octave, const double *F,
+                                 const float *inv_sigma2, int nlevels, int32_t *verdict, int32_t *n_rays, double *vals);
+
+/* ------------------------------------------------------------------------- */
 /* Host stages exposed for the CPU test-suite (no device needed)              */
 /* ------------------------------------------------------------------------- */
 /* The engine's quad-tree selection, DistributeOctTree's equivalent (ORBextractor.cpp:554-778), run

@@ -998,6 +998,48 @@ def lf_mono_cam(lf):
     return (lf["mono"] != 0).astype(np.uint8), cam
 
 
+class MapFrameArrays:
+    """one keyframe's observations for LocalMap.triangulate_neighbours (mcorb_map_frame); keeps the arrays the struct points to"""
+
+    def __init__(self, match_index, kps_undist, centres_w, proj, twc):
+        self.match_index = np.ascontiguousarray(match_index, np.int32)
+        if self.match_index.ndim != 2:
+            raise ValueError("map_frame: match_index is nfeat x ncams")
+        nfeat, ncams = self.match_index.shape
+        if not 1 <= ncams <= _lib.MAX_CAMS or not len(kps_undist) == len(centres_w) == len(proj) == ncams:
+            raise ValueError("map_frame: 1 .. %d cameras, one keypoint array, centre and projection matrix each" % _lib.MAX_CAMS)
+        self.kps = [np.ascontiguousarray(k, KP_DTYPE).reshape(-1) for k in kps_undist]
+        self.nkps = np.array([len(k) for k in self.kps], np.int32)
+        self.ptrs = (C.c_void_p * ncams)(*[k.ctypes.data for k in self.kps])
+        f = self.struct = _lib.MapFrame()
+        f.nfeat, f.ncams = nfeat, ncams
+        f.match_index, f.kps_undist, f.nkps = self.match_index.ctypes.data, self.ptrs, self.nkps.ctypes.data
+        for c in range(ncams):
+            f.centre_w[c][:] = np.asarray(centres_w[c], np.float64).reshape(3).tolist()
+            f.proj[c][:] = np.asarray(proj[c], np.float64).reshape(-1)[:12].tolist()
+        f.twc[:] = np.asarray(twc, np.float64).reshape(3).tolist()
+
+
+def map_frame(lf, kps_undist, centres_w, proj, twc):
+    """the frame of LocalMap.triangulate_neighbours from mcorb_lf_feature records (Rig.lf_features; or an nfeat x ncams matchIndex
+    array) and image_kps_undist per camera; centres_w: W_T_cur's translation per camera; proj: cur_T_ref * pose.inv() per camera
+    (3x4 or 4x4, rows 0..2 are read); twc: the pose's translation column"""
+    lf = np.asarray(lf)
+    mi = lf["match_index"][:, :len(kps_undist)] if lf.dtype.names else lf
+    return MapFrameArrays(mi, kps_undist, centres_w, proj, twc)
+
+
+class TriangulationResult:
+    """what LocalMap.triangulate_neighbours returns.  Per match, the neighbours' matches back to back (offsets[s] is neighbour s's
+    first): inliers, verdict (0 landmark, 1 epipolar den == 0, 2 epipolar distance, 3 behind a camera, 4 chi-square, 5 parallax
+    window, 6 a feature had a landmark already, 7 neighbour skipped), new_lid (-1: none), pt3d, normal, dist2, cos_parallax; per
+    neighbour: neigh_skipped (0 used, 1 baseline gate, 2 no landmarks); depth_vec in the order the landmarks were made;
+    n_triangulated; next_lid; lids_cur and lids_neigh as the call leaves them"""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
 class LocalMap:
     """FrontEnd::searchLocalMap2 (MCSlam/src/FrontEnd.cpp:4901-5223) up to the camera-filtered matches (mcorb_lmap): a store of
     landmarks (slot = lId: pt3D, normal, the latest observation's descriptor and mono flag) and the search of a frame held in a
@@ -1085,6 +1127,88 @@ class LocalMap:
         n = C.c_int()
         _lib.check(self.L.mcorb_lmap_last_timing(self.h, us, C.byref(n)))
         return us[0], us[1], n.value
+
+
+    def triangulate_neighbours(self, cur, lids_cur, neigh, lids_neigh, F21, matches, K_mats, inv_sigma2, Rcw, tcw, next_lid, caps=None):
+        """FrontEnd::triangulateNeighbors (FrontEnd.cpp:4856-4899) -> TriangulationResult; the new landmarks' points and normals are
+        stored in their slots.  cur / neigh: map_frame(...) of the current frame and of the neighbouring keyframes in
+        kfMap.rbegin() order; lids_cur / lids_neigh: their lIds (copied: the result holds the updated arrays); F21: per neighbour
+        ncams x ncams x 3 x 3, index [c_cur][c_neigh]; matches: per neighbour an n x 2 array (queryIdx, trainIdx); K_mats: per
+        camera; inv_sigma2: GetInverseScaleSigmaSquares(); Rcw / tcw: currentFrame->pose.inv(); caps: (matches, depth_vec) output
+        sizes, by default what cannot be exceeded"""
+        S, nc = len(neigh), cur.struct.ncams
+        assert len(lids_neigh) == len(F21) == len(matches) == S
+        lc = np.array(lids_cur, np.int32).reshape(-1)
+        ln = [np.array(l, np.int32).reshape(-1) for l in lids_neigh]
+        assert len(lc) == cur.struct.nfeat and all(len(l) == f.struct.nfeat for l, f in zip(ln, neigh))
+        Fs = [np.ascontiguousarray(f, np.float64).reshape(nc, nc, 9) for f in F21]
+        ms = [np.asarray(m_, np.int32).reshape(-1, 2) for m_ in matches]
+        mq = [np.ascontiguousarray(m_[:, 0]) for m_ in ms]
+        mt = [np.ascontiguousarray(m_[:, 1]) for m_ in ms]
+        nm = np.array([len(m_) for m_ in ms], np.int32)
+        offsets = np.concatenate([[0], np.cumsum(nm)]).astype(np.int64)
+        total = int(offsets[-1])
+        cap_m, cap_d = caps if caps is not None else (total, total)
+        Kc = np.ascontiguousarray(K_mats, np.float64).reshape(nc, 9)
+        sig = np.ascontiguousarray(inv_sigma2, np.float32).reshape(-1)
+        Rc, tc = np.ascontiguousarray(Rcw, np.float64).reshape(9), np.ascontiguousarray(tcw, np.float64).reshape(3)
+        frames = (_lib.MapFrame * max(S, 1))(*[f.struct for f in neigh])
+        vpp = lambda arrs: (C.c_void_p * max(S, 1))(*[a.ctypes.data for a in arrs])
+        n1, n3 = max(cap_m, 1), 3 * max(cap_m, 1)
+        r = dict(inliers=np.zeros(n1, np.uint8), verdict=np.zeros(n1, np.uint8), new_lid=np.zeros(n1, np.int32), pt3d=np.zeros(n3),
+                 normal=np.zeros(n3), dist2=np.zeros(n1), cos_parallax=np.zeros(n1), neigh_skipped=np.zeros(max(S, 1), np.uint8),
+                 depth_vec=np.zeros(max(cap_d, 1)))
+        o = self.map_out = _lib.MapOut()
+        o.cap_matches, o.cap_depth = cap_m, cap_d
+        for k, a in r.items():
+            setattr(o, k, a.ctypes.data)
+        _lib.check(self.L.mcorb_lmap_triangulate_neighbours(self.h, C.byref(cur.struct), lc.ctypes.data, frames, vpp(ln), S, vpp(Fs),
+                                                            vpp(mq), vpp(mt), nm.ctypes.data, Kc.ctypes.data, sig.ctypes.data, len(sig),
+                                                            Rc.ctypes.data, tc.ctypes.data, int(next_lid), C.byref(o)))
+        nd = o.n_depth
+        return TriangulationResult(inliers=r["inliers"][:total].astype(bool), verdict=r["verdict"][:total].copy(),
+                                   new_lid=r["new_lid"][:total].copy(), pt3d=r["pt3d"][:3 * total].reshape(-1, 3).copy(),
+                                   normal=r["normal"][:3 * total].reshape(-1, 3).copy(), dist2=r["dist2"][:total].copy(),
+                                   cos_parallax=r["cos_parallax"][:total].copy(), neigh_skipped=r["neigh_skipped"][:S].copy(),
+                                   depth_vec=r["depth_vec"][:nd].copy(), n_triangulated=o.n_triangulated, next_lid=o.next_lid,
+                                   lids_cur=lc, lids_neigh=ln, offsets=offsets)
+
+    def depths(self, Rcw, tcw, lids):
+        """getSceneDepthStats' depthVec before its sort: z of Rcw * pt3D + tcw for the landmarks `lids`"""
+        Rc, tc = np.ascontiguousarray(Rcw, np.float64).reshape(9), np.ascontiguousarray(tcw, np.float64).reshape(3)
+        lids = np.ascontiguousarray(lids, np.int32).reshape(-1)
+        z = np.zeros(max(len(lids), 1))
+        _lib.check(self.L.mcorb_lmap_depths(self.h, Rc.ctypes.data, tc.ctypes.data, lids.ctypes.data, len(lids), z.ctypes.data))
+        return z[:len(lids)]
+
+    def last_triangulate_timing(self):
+        """(microseconds of the last k_map_triangulate launches, of the last k_map_depth launch, matches launched, depths taken)"""
+        us = (C.c_float * 2)()
+        n, nd = C.c_int(), C.c_int()
+        _lib.check(self.L.mcorb_lmap_last_triangulate_timing(self.h, us, C.byref(n), C.byref(nd)))
+        return us[0], us[1], n.value, nd.value
+
+
+def map_gates(X, nv1, nv, P, K, centre, kps, octave, F, inv_sigma2, device=None):
+    """the test hooks mcorb_host_map_gates (device None) / mcorb_dev_map_gates_selftest: everything of a match but the
+    triangulation for n cases with caller-given X -> (verdict, n_rays, dist2, cos, normal).  Views back to back: P (V x 12),
+    K (V x 9), centre (V x 3), kps (V x 2 float32), octave (V); per case X (3), nv1, nv, F (9)"""
+    X = np.ascontiguousarray(X, np.float64).reshape(-1, 3)
+    n = len(X)
+    nv1, nv = np.ascontiguousarray(nv1, np.int32).reshape(-1), np.ascontiguousarray(nv, np.int32).reshape(-1)
+    P, K = np.ascontiguousarray(P, np.float64).reshape(-1, 12), np.ascontiguousarray(K, np.float64).reshape(-1, 9)
+    centre, kps = np.ascontiguousarray(centre, np.float64).reshape(-1, 3), np.ascontiguousarray(kps, np.float32).reshape(-1, 2)
+    octave, F = np.ascontiguousarray(octave, np.int32).reshape(-1), np.ascontiguousarray(F, np.float64).reshape(-1, 9)
+    sig = np.ascontiguousarray(inv_sigma2, np.float32).reshape(-1)
+    V = int(nv.sum()) if len(nv) == n else -1
+    if not (len(nv1) == len(F) == n and len(P) == len(K) == len(centre) == len(kps) == len(octave) == V):
+        raise ValueError("map_gates: array lengths do not fit the view counts")
+    verdict, rays, vals = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32), np.zeros((max(n, 1), 5))
+    args = (n, X.ctypes.data, nv1.ctypes.data, nv.ctypes.data, P.ctypes.data, K.ctypes.data, centre.ctypes.data, kps.ctypes.data,
+            octave.ctypes.data, F.ctypes.data, sig.ctypes.data, len(sig), verdict.ctypes.data, rays.ctypes.data, vals.ctypes.data)
+    L = _lib.load()
+    _lib.check(L.mcorb_host_map_gates(*args) if device is None else L.mcorb_dev_map_gates_selftest(device, *args))
+    return verdict[:n], rays[:n], vals[:n, 0].copy(), vals[:n, 1].copy(), vals[:n, 2:].copy()
 
 
 class DescriptorBlock:

@@ -46,6 +46,19 @@ class LmapView(C.Structure):
                 ("reserved", C.c_int32), ("cams", LmapCam * MAX_CAMS)]
 
 
+class MapFrame(C.Structure):
+    _fields_ = [("nfeat", C.c_int32), ("ncams", C.c_int32), ("match_index", C.c_void_p), ("kps_undist", C.POINTER(C.c_void_p)),
+                ("nkps", C.c_void_p), ("centre_w", C.c_double * 3 * MAX_CAMS), ("proj", C.c_double * 12 * MAX_CAMS),
+                ("twc", C.c_double * 3)]
+
+
+class MapOut(C.Structure):
+    _fields_ = [("cap_matches", C.c_int32), ("cap_depth", C.c_int32), ("inliers", C.c_void_p), ("verdict", C.c_void_p),
+                ("new_lid", C.c_void_p), ("pt3d", C.c_void_p), ("normal", C.c_void_p), ("dist2", C.c_void_p),
+                ("cos_parallax", C.c_void_p), ("neigh_skipped", C.c_void_p), ("depth_vec", C.c_void_p), ("n_matches", C.c_int32),
+                ("n_depth", C.c_int32), ("n_triangulated", C.c_int32), ("next_lid", C.c_int32)]
+
+
 class McorbError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("mcorb error %d: %s" % (code, msg))
@@ -182,6 +195,13 @@ SIGNATURES = {
     "mcorb_lmap_search": (_i, [_vp, C.POINTER(LmapView), _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, C.c_double, _vp, _vp, _i, _ip,
                                _vp, _vp, _i, _ip, _vp, _vp, _i, _ip]),
     "mcorb_lmap_last_timing": (_i, [_vp, C.POINTER(_f), _ip]),
+    "mcorb_lmap_triangulate_neighbours": (_i, [_vp, C.POINTER(MapFrame), _vp, C.POINTER(MapFrame), C.POINTER(_vp), _i, C.POINTER(_vp),
+                                               C.POINTER(_vp), C.POINTER(_vp), _vp, _vp, _vp, _i, _vp, _vp, C.c_int32,
+                                               C.POINTER(MapOut)]),
+    "mcorb_lmap_depths": (_i, [_vp, _vp, _vp, _vp, _i, _vp]),
+    "mcorb_lmap_last_triangulate_timing": (_i, [_vp, C.POINTER(_f), _ip, _ip]),
+    "mcorb_host_map_gates": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
+    "mcorb_dev_map_gates_selftest": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
     "mcorb_host_geometry": (_i, [C.POINTER(Params), _i, _i, _vp]),
     "mcorb_synth_rig_frame": (_i, [C.c_uint32, _i, _i, _i, _i, _vp, _i]),
 }

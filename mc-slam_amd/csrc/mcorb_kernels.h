@@ -1,10 +1,11 @@
 // mcorb_kernels.h -- launch wrappers of the gfx950 kernels (mcorb_kernels.hip, mcorb_select_gpu.hip, mcorb_handoff_gpu.hip,
-// mcorb_bow_gpu.hip, mcorb_lf_gpu.hip, mcorb_kfdb_gpu.hip, mcorb_lmap_gpu.hip).
+// mcorb_bow_gpu.hip, mcorb_lf_gpu.hip, mcorb_kfdb_gpu.hip, mcorb_lmap_gpu.hip, mcorb_mapping_gpu.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <vector>
 #include "../../include/mcorb.h"
 #include "mcorb_common.h"
+#include "mcorb_mapping.h"
 #include "mcorb_signal.h"
 #include "mcorb_undistort.h"
 #include "mcorb_undistort_image.h"
@@ -153,5 +154,17 @@ void launch_lmap_cull(hipStream_t st, const mcorb_lmap_view *view, const double 
 // == NULL: row i) of src_desc into desc; a NULL source leaves that part of the slots alone
 void launch_lmap_put(hipStream_t st, const int *lids, int n, const double *pt, const double *normal, const uint8_t *src_desc,
                      const int *rows, double *geom, uint8_t *desc);
+
+// the mapping step's kernels (mcorb_mapping_gpu.hip).  k_map_triangulate: one lane per inter-frame match, one wave per block
+// record of a.blocks -- first nblocks_small records of matches with at most 4 views (the instance without the run-time-shaped
+// solver), then nblocks_any of the rest -- one MapOut to a.out[item.rec]
+constexpr int kMapBlock = 64;
+void launch_map_triangulate(hipStream_t st, const MapArgs &a, int nblocks_small, int nblocks_any);
+// k_map_depth: z[i] = row 2 of Rcw * pt3D(lids[i]) + tcw (getSceneDepthStats)
+void launch_map_depth(hipStream_t st, const double Rcw[9], const double tcw[3], const double *geom, const int *lids, int n, double *z);
+// k_map_put: point and normal of record put[i].x into slot put[i].y of geom
+void launch_map_put(hipStream_t st, const MapOut *rec, const int2 *put, int n, double *geom);
+// the gates of n caller-given cases (mcorb_dev_map_gates_selftest); every pointer of c is device memory
+void launch_map_gates(hipStream_t st, const MapGateCases &c, int n, MapOut *out);
 
 }  // namespace mcorb

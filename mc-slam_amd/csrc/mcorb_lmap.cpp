@@ -24,48 +24,9 @@
 #include <mutex>
 #include <vector>
 
-#include "mcorb_kfdb_store.h"
+#include "mcorb_lmap_store.h"
 
 using namespace mcorb;
-
-namespace {
-constexpr uint8_t kHasPt = 1, kHasNormal = 2, kHasDesc = 4, kMono = 8, kSet = kHasPt | kHasNormal;
-}
-
-struct mcorb_lmap {
-    int device = -1, max_landmarks = 0, max_candidates = 0;
-    mcorb_vocab *voc = nullptr;
-    std::mutex mu;   // one call at a time: the scratch below is the store's
-    std::vector<uint8_t> flags;      // per slot
-    std::vector<int> stamp;          // per slot: the last search (or batch) that saw it
-    int tick = 0;
-    // host-only store
-    std::vector<double> geom;        // [max_landmarks][6]: pt3D, normal
-    std::vector<uint8_t> desc;       // [max_landmarks][32]
-    // device store
-    Stream st;
-    Event ev0, ev1;
-    DevBuf<double> d_geom;
-    DevBuf<uint8_t> d_desc;
-    DevBuf<mcorb_lmap_view> d_view;
-    // scratch of a batch (grow-only) and of a search (max_candidates)
-    DevBuf<int> d_blids, d_brows;
-    DevBuf<double> d_bpt, d_bnormal;
-    DevBuf<uint8_t> d_bdesc;
-    DevBuf<int> d_cand, d_afeats;
-    DevBuf<uint32_t> d_masks;
-    HostBuf<uint32_t> h_masks;
-    DevBuf<uint8_t> d_adesc;         // the accepted rows, gathered
-    Best2Search best2;
-    float us_cull = 0.f, us_best2 = 0.f;
-    int last_candidates = 0;
-};
-
-static int check_lmap(const mcorb_lmap *m, const char *who)
-{
-    if (!m) { set_error(std::string(who) + ": bad argument"); return MCORB_E_ARG; }
-    return MCORB_OK;
-}
 
 // a new stamp value; the stamps start over before the counter wraps
 static int next_tick(mcorb_lmap *m)
@@ -183,6 +144,8 @@ int mcorb_lmap_create(mcorb_vocab *v, int device, int max_landmarks, int max_can
         TRY(m->st.create(hipStreamNonBlocking));
         TRY(m->ev0.create(hipEventDefault));
         TRY(m->ev1.create(hipEventDefault));
+        TRY(m->ev2.create(hipEventDefault));
+        TRY(m->ev3.create(hipEventDefault));
         TRY(m->best2.create());
         TRY(m->d_geom.alloc(N * 6));
         TRY(m->d_desc.alloc(N * 32));

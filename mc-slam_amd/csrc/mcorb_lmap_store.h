@@ -1,0 +1,62 @@
+// mcorb_lmap_store.h -- the local map object, shared by its search (mcorb_lmap.cpp) and by the mapping step that fills it
+// (mcorb_mapping.cpp).
+#pragma once
+#include <mutex>
+#include <string>
+#include <vector>
+
+#include "mcorb_kfdb_store.h"
+#include "mcorb_mapping.h"
+
+namespace mcorb {
+constexpr uint8_t kHasPt = 1, kHasNormal = 2, kHasDesc = 4, kMono = 8, kSet = kHasPt | kHasNormal;
+}  // namespace mcorb
+
+struct mcorb_lmap {
+    int device = -1, max_landmarks = 0, max_candidates = 0;
+    mcorb_vocab *voc = nullptr;
+    std::mutex mu;   // one call at a time: the scratch below is the store's
+    std::vector<uint8_t> flags;      // per slot
+    std::vector<int> stamp;          // per slot: the last search (or batch) that saw it
+    int tick = 0;
+    // host-only store
+    std::vector<double> geom;        // [max_landmarks][6]: pt3D, normal
+    std::vector<uint8_t> desc;       // [max_landmarks][32]
+    // device store
+    mcorb::Stream st;
+    mcorb::Event ev0, ev1;
+    mcorb::DevBuf<double> d_geom;
+    mcorb::DevBuf<uint8_t> d_desc;
+    mcorb::DevBuf<mcorb_lmap_view> d_view;
+    // scratch of a batch (grow-only) and of a search (max_candidates)
+    mcorb::DevBuf<int> d_blids, d_brows;
+    mcorb::DevBuf<double> d_bpt, d_bnormal;
+    mcorb::DevBuf<uint8_t> d_bdesc;
+    mcorb::DevBuf<int> d_cand, d_afeats;
+    mcorb::DevBuf<uint32_t> d_masks;
+    mcorb::HostBuf<uint32_t> h_masks;
+    mcorb::DevBuf<uint8_t> d_adesc;         // the accepted rows, gathered
+    mcorb::Best2Search best2;
+    float us_cull = 0.f, us_best2 = 0.f;
+    int last_candidates = 0;
+    // scratch of mcorb_lmap_triangulate_neighbours (mcorb_mapping.cpp), grow-only: the packed input (one block, one copy), the
+    // result records, the depth list and the write-back list
+    mcorb::HostBuf<uint8_t> h_mapin;
+    mcorb::DevBuf<uint8_t> d_mapin;
+    mcorb::HostBuf<mcorb::MapOut> h_mapout;
+    mcorb::DevBuf<mcorb::MapOut> d_mapout;
+    mcorb::HostBuf<double> h_mapz;
+    mcorb::DevBuf<double> d_mapz;
+    mcorb::HostBuf<int2> h_mapput;
+    mcorb::DevBuf<int2> d_mapput;
+    mcorb::Event ev2, ev3;
+    float us_map_depth = 0.f, us_map_tri = 0.f;
+    int last_map_launched = 0, last_map_depth = 0;
+};
+
+inline int check_lmap(const mcorb_lmap *m, const char *who)
+{
+    if (!m) { mcorb::set_error(std::string(who) + ": bad argument"); return MCORB_E_ARG; }
+    return MCORB_OK;
+}
+
