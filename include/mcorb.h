@@ -722,8 +722,8 @@ typedef struct mcorb_map_out {
  * reference.  A new landmark takes the next id, which is written to both lIds arrays (and so skips every later match of either
  * feature, across neighbours for the current frame's), its dist2 is appended to depth_vec, and its point and its normal --
  * Landmark::updateNormal for the neighbour (KFs.size() == 1) and then for the current frame, every division by a scalar a
- * multiplication by the reciprocal as cv::MatExpr does it -- are stored in slot id of the map (flags: point and normal set, no
- * descriptor yet).  All arithmetic is fp64 (float where the reference has float) with separate multiplies and adds in cv::Mat's
+ * multiplication by the reciprocal as cv::MatExpr does it -- and its n_rays are stored in slot id of the map (flags: point and
+ * normal set, no descriptor yet).  All arithmetic is fp64 (float where the reference has float) with separate multiplies and adds in cv::Mat's
  * order.  A device store computes the per-match part in k_map_triangulate and the depths in k_map_depth, one submission for all
  * neighbours, and moves the accepted points and normals into their slots device to device; a host-only store runs the same
  * code serially; the results are equal bit for bit.
@@ -753,6 +753,78 @@ int mcorb_host_map_gates(int n, const double *X, const int32_t *nv1, const int32
 int mcorb_dev_map_gates_selftest(int device, int n, const double *X, const int32_t *nv1, const int32_t *nv, const double *P,
                                  const double *K, const double *centre, const float *kps, const int32_t *octave, const double *F,
                                  const float *inv_sigma2, int nlevels, int32_t *verdict, int32_t *n_rays, double *vals);
+
+/* ------------------------------------------------------------------------- */
+/* Landmarks: the local map kept up to date as keyframes are inserted --      */
+/* Landmark::addLfFrame with updateNormal(frame, featInd)                     */
+/* (MCSlam/src/GlobalMap.cpp:24-74, constructor :6-14; FrontEnd.cpp:6326-6335, */
+/* :6680-6682, :2819-2821), GlobalMap::updateLandmark (GlobalMap.cpp:162-185;  */
+/* Backend.cpp:3835-3864, :3594-3663), GlobalMap::deleteLandmark               */
+/* (GlobalMap.cpp:151-160; Backend.cpp:3442-3449) and kfMap's keys             */
+/* (FrontEnd.cpp:4925-4933).  insertKeyFrame, the pose estimation, the         */
+/* optimisations and the 4x4 inverses stay with the caller.                    */
+/* ------------------------------------------------------------------------- */
+/* Beside its point, normal, descriptor and mono flag a slot holds n_rays (Landmark::n_rays; in HBM on a device store) and, as host
+ * state, its observations (kf_id, feat) in the order they were added: the reference's KFs / featInds.  mcorb_lmap_set leaves both
+ * alone; mcorb_lmap_triangulate_neighbours stores a new landmark's n_rays but, as its frames carry no keyframe id, records no
+ * observation: the caller registers the two with MCORB_OBS_RECORD. */
+/* the observing keyframe of mcorb_lmap_observe */
+typedef struct mcorb_obs_frame {
+    int32_t kf_id, nfeat, ncams, reserved;   /* kf_id >= 0 */
+    const int32_t *match_index;              /* nfeat x ncams: intraMatches[i].matchIndex, -1 = no view */
+    double centre_w[MCORB_MAX_CAMS][3];      /* per camera: the translation column of W_T_cur = pose * cur_T_ref.inv()
+                                              * (GlobalMap.cpp:45-49), which the caller computes */
+} mcorb_obs_frame;
+#define MCORB_OBS_UPDATE 0   /* addLfFrame (the constructor for a slot without an observation): the normal and n_rays change */
+#define MCORB_OBS_RECORD 1   /* the observation is appended, normal and n_rays stay: for a landmark fresh from
+                              * mcorb_lmap_triangulate_neighbours, whose normal already holds both frames */
+/* n_rays of slots that are set, for a caller that loads an existing map.  Of an id that occurs twice the last occurrence holds.
+ * MCORB_E_ARG for an id outside the store or a negative count, MCORB_E_STATE for a slot that was never set. */
+int mcorb_lmap_set_rays(mcorb_lmap *m, const int32_t *lids, int n, const int32_t *n_rays);
+/* a slot's n_rays and its observations in the order they were added (outputs may be NULL with cap 0); *n = their count,
+ * MCORB_E_CAP when cap is short, MCORB_E_STATE for a slot that was never set */
+int mcorb_lmap_get_observations(mcorb_lmap *m, int lid, int32_t *n_rays, int32_t *kfs, int32_t *feats, int cap, int *n);
+/* A batch of addLfFrame for one keyframe: item i is landmark lids[i] seen as LF feature feats[i] of `frame`.  Per item, in batch
+ * order, with the reference's serial meaning (a landmark may occur more than once: two features of one frame may match it):
+ *   acc = the sum over the cameras ascending with matchIndex != -1, from 0.0, of normal_cur * (1.0 / cv::norm(normal_cur)) with
+ *   normal_cur = pt3D - centre_w[cam] (the norm adds three squares in order, then sqrt; cv::MatExpr's division by a scalar is a
+ *   multiplication by the reciprocal), n the number of those cameras;
+ *   MCORB_OBS_UPDATE, a slot without an observation (GlobalMap.cpp:58-61): normal = acc * (1.0 / n), n_rays = n;
+ *   MCORB_OBS_UPDATE otherwise (:62-67): normal = normal * (double)n_rays + acc, n_rays += n, normal = normal * (1.0 / n_rays);
+ *   MCORB_OBS_RECORD: normal and n_rays untouched;
+ *   in both modes (kf_id, feats[i]) is appended to the slot's observations, with entry >= 0 row feats[i] of that entry of db
+ *   becomes the slot's descriptor (KFs.back()'s, FrontEnd.cpp:5031-5033; device to device on a device store) and mono[i] (mono may
+ *   be NULL: kept) its mono flag.  db may be NULL with entry = -1, which keeps the descriptors.
+ * All arithmetic is fp64 with separate multiplies and adds.  A device store runs it in k_lmap_observe, one lane per item, a batch
+ * that names a landmark more than once in rounds (round r: every landmark's r-th occurrence); a host-only store runs the same
+ * code serially; the results are equal bit for bit.  n_rays_out (may be NULL): n entries, the slot's n_rays after item i.
+ * MCORB_E_ARG, before anything runs: an id outside the store, kf_id < 0, feats[i] outside the frame, a feature without a view,
+ * ncams outside 1 .. MCORB_MAX_CAMS, an unknown mode, a database on another device, a missing entry or a row outside it;
+ * MCORB_E_STATE: a slot without a point. */
+int mcorb_lmap_observe(mcorb_lmap *m, const mcorb_obs_frame *frame, const int32_t *lids, const int32_t *feats, int n, int mode,
+                       mcorb_kfdb *db, int entry, const uint8_t *mono, int32_t *n_rays_out);
+/* A batch of GlobalMap::updateLandmark, in batch order: d = pt3D - pt_new[3 * i ..] per element, diff_norm[i] = sqrt(d0 * d0 +
+ * d1 * d1 + d2 * d2) added in order; the point is replaced and updated[i] = 1 iff diff_norm < max_diff (the reference's 5.0), in
+ * that form: a NaN stores nothing (and is returned as the default quiet NaN, 0x7ff8000000000000: IEEE 754 leaves a NaN's sign and
+ * payload to the implementation, and host and device differ in it).  Normal, n_rays and observations are untouched (Landmark::updateNormal() without arguments
+ * assigns nothing, GlobalMap.cpp:76-104).  A later item of the same landmark compares against the point the earlier one left.
+ * k_lmap_update on a device store, with mcorb_lmap_observe's rounds.  updated / diff_norm may be NULL.  The call sums nothing:
+ * updateVariables' mean_correction is the caller's serial sum over diff_norm.  MCORB_E_ARG for an id outside the store,
+ * MCORB_E_STATE for a slot without a point; nothing is stored on an error. */
+int mcorb_lmap_update_points(mcorb_lmap *m, const int32_t *lids, int n, const double *pt_new, double max_diff, uint8_t *updated,
+                             double *diff_norm);
+/* A batch of GlobalMap::deleteLandmark: the slots' flags, n_rays and observations are cleared, and the dropped (kf_id, feat)
+ * pairs come back in lids order, then observation order -- the lIds entries the caller sets to -1 (GlobalMap.cpp:154-157).
+ * *n_out = their count; MCORB_E_CAP when cap is short, MCORB_E_STATE for a slot that was never set, MCORB_E_ARG for an id outside
+ * the store or twice in the batch; nothing is deleted on an error.  A deleted slot may be set again; a search that names it as a
+ * candidate gets MCORB_E_STATE. */
+int mcorb_lmap_delete(mcorb_lmap *m, const int32_t *lids, int n, int32_t *kfs, int32_t *feats, int cap, int *n_out);
+/* kfMap's keys (FrontEnd.cpp:4925-4933): the ascending, duplicate-free kf_ids of the observations of lids[0 .. n).  Host only.
+ * *n_out = their count; MCORB_E_CAP when cap is short, MCORB_E_STATE for a slot that was never set. */
+int mcorb_lmap_observers(mcorb_lmap *m, const int32_t *lids, int n, int32_t *kf_ids, int cap, int *n_out);
+/* a device store's last k_lmap_observe rounds (us[0]) and last k_lmap_update rounds (us[1]), microseconds between HIP events; a
+ * call without items leaves them */
+int mcorb_lmap_last_landmark_timing(mcorb_lmap *m, float us[2]);
 
 /* ------------------------------------------------------------------------- */
 /* Host stages exposed for the CPU test-suite (no device needed)              */

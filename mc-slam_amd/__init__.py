@@ -16,7 +16,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import (E_ARG, E_CAP, E_EMPTY, E_HIP, E_NODEVICE, E_OVERFLOW, E_SIZE, E_STATE, KP_DTYPE, OK,
+from ._lib import (E_ARG, E_CAP, E_EMPTY, E_HIP, E_NODEVICE, E_OVERFLOW, E_SIZE, E_STATE, KP_DTYPE, OBS_RECORD, OBS_UPDATE, OK,
                    ORIENT_IC_ANGLE, ORIENT_NONE, McorbError, Params, default_params)
 from .synth import synth_rig_frame, synth_rig_frame_numpy
 
@@ -1187,6 +1187,107 @@ class LocalMap:
         n, nd = C.c_int(), C.c_int()
         _lib.check(self.L.mcorb_lmap_last_triangulate_timing(self.h, us, C.byref(n), C.byref(nd)))
         return us[0], us[1], n.value, nd.value
+
+    def set_rays(self, lids, n_rays):
+        """n_rays of slots that are set (a caller that loads an existing map)"""
+        lids = np.ascontiguousarray(lids, np.int32).reshape(-1)
+        r = np.ascontiguousarray(n_rays, np.int32).reshape(-1)
+        assert len(lids) == len(r)
+        _lib.check(self.L.mcorb_lmap_set_rays(self.h, lids.ctypes.data, len(lids), r.ctypes.data))
+
+    def observations(self, lid):
+        """-> (n_rays, [(kf_id, feat), ..]) of a slot: the reference's KFs / featInds in the order they were added"""
+        nr, n = C.c_int32(), C.c_int()
+        code = self.L.mcorb_lmap_get_observations(self.h, lid, C.byref(nr), None, None, 0, C.byref(n))
+        if code not in (_lib.OK, _lib.E_CAP):
+            _lib.check(code)
+        kfs, feats = np.zeros(max(n.value, 1), np.int32), np.zeros(max(n.value, 1), np.int32)
+        _lib.check(self.L.mcorb_lmap_get_observations(self.h, lid, C.byref(nr), kfs.ctypes.data, feats.ctypes.data, n.value, C.byref(n)))
+        return nr.value, list(zip(kfs[:n.value].tolist(), feats[:n.value].tolist()))
+
+    def observe(self, frame, lids, feats, mode=_lib.OBS_UPDATE, db=None, entry=-1, mono=None):
+        """a batch of Landmark::addLfFrame for one keyframe (GlobalMap.cpp:24-74) -> n_rays of every item's slot after it.
+        frame: obs_frame(...); landmark lids[i] is seen as LF feature feats[i]; mode OBS_UPDATE (normal and n_rays change) or
+        OBS_RECORD (the observation alone, for landmarks fresh from triangulate_neighbours); db / entry: the keyframe's database
+        entry, whose rows become the slots' descriptors; mono: the slots' new mono flags"""
+        lids = np.ascontiguousarray(lids, np.int32).reshape(-1)
+        feats = np.ascontiguousarray(feats, np.int32).reshape(-1)
+        assert len(lids) == len(feats)
+        m, mp = self._opt(None if mono is None else np.asarray(mono) != 0, np.uint8, (len(lids),))
+        out = np.zeros(max(len(lids), 1), np.int32)
+        _lib.check(self.L.mcorb_lmap_observe(self.h, C.byref(frame.struct), lids.ctypes.data, feats.ctypes.data, len(lids), mode,
+                                             db.h if db is not None else None, entry, mp, out.ctypes.data))
+        return out[:len(lids)]
+
+    def update_points(self, lids, pt_new, max_diff=5.0):
+        """a batch of GlobalMap::updateLandmark (GlobalMap.cpp:162-185) -> (updated, diff_norm): a point is replaced iff
+        norm(pt3D - pt_new) < max_diff"""
+        lids = np.ascontiguousarray(lids, np.int32).reshape(-1)
+        n = len(lids)
+        p = np.ascontiguousarray(pt_new, np.float64).reshape(n, 3)
+        upd, diff = np.zeros(max(n, 1), np.uint8), np.zeros(max(n, 1))
+        _lib.check(self.L.mcorb_lmap_update_points(self.h, lids.ctypes.data, n, p.ctypes.data, float(max_diff), upd.ctypes.data,
+                                                   diff.ctypes.data))
+        return upd[:n].astype(bool), diff[:n]
+
+    def delete(self, lids, cap=None):
+        """a batch of GlobalMap::deleteLandmark (GlobalMap.cpp:151-160) -> the dropped (kf_id, feat) pairs, in lids order and then
+        observation order: the lIds entries to set to -1"""
+        lids = np.ascontiguousarray(lids, np.int32).reshape(-1)
+        n = self.delete_count = C.c_int()
+        if cap is None:     # a first call without room returns the count and deletes nothing (or finds nothing to return)
+            code = self.L.mcorb_lmap_delete(self.h, lids.ctypes.data, len(lids), None, None, 0, C.byref(n))
+            if code == _lib.OK:
+                return []
+            if code != _lib.E_CAP:
+                _lib.check(code)
+            cap = n.value
+        kfs, feats = np.zeros(max(cap, 1), np.int32), np.zeros(max(cap, 1), np.int32)
+        _lib.check(self.L.mcorb_lmap_delete(self.h, lids.ctypes.data, len(lids), kfs.ctypes.data, feats.ctypes.data, cap, C.byref(n)))
+        return list(zip(kfs[:n.value].tolist(), feats[:n.value].tolist()))
+
+    def observers(self, lids, cap=None):
+        """kfMap's keys (FrontEnd.cpp:4925-4933): the ascending, duplicate-free kf_ids that observe the landmarks `lids`"""
+        lids = np.ascontiguousarray(lids, np.int32).reshape(-1)
+        n = self.observers_count = C.c_int()
+        if cap is None:
+            code = self.L.mcorb_lmap_observers(self.h, lids.ctypes.data, len(lids), None, 0, C.byref(n))
+            if code not in (_lib.OK, _lib.E_CAP):
+                _lib.check(code)
+            cap = n.value
+        out = np.zeros(max(cap, 1), np.int32)
+        _lib.check(self.L.mcorb_lmap_observers(self.h, lids.ctypes.data, len(lids), out.ctypes.data, cap, C.byref(n)))
+        return out[:n.value].copy()
+
+    def last_landmark_timing(self):
+        """(microseconds of the last k_lmap_observe rounds, of the last k_lmap_update rounds); a device store"""
+        us = (C.c_float * 2)()
+        _lib.check(self.L.mcorb_lmap_last_landmark_timing(self.h, us))
+        return us[0], us[1]
+
+
+class ObsFrameArrays:
+    """the observing keyframe of LocalMap.observe (mcorb_obs_frame); keeps the array the struct points to"""
+
+    def __init__(self, kf_id, match_index, centres_w):
+        self.match_index = np.ascontiguousarray(match_index, np.int32)
+        if self.match_index.ndim != 2:
+            raise ValueError("obs_frame: match_index is nfeat x ncams")
+        nfeat, ncams = self.match_index.shape
+        if not 1 <= ncams <= _lib.MAX_CAMS or len(centres_w) != ncams:
+            raise ValueError("obs_frame: 1 .. %d cameras, one centre each" % _lib.MAX_CAMS)
+        f = self.struct = _lib.ObsFrame()
+        f.kf_id, f.nfeat, f.ncams, f.match_index = int(kf_id), nfeat, ncams, self.match_index.ctypes.data
+        for c in range(ncams):
+            f.centre_w[c][:] = np.asarray(centres_w[c], np.float64).reshape(3).tolist()
+
+
+def obs_frame(kf_id, lf, centres_w):
+    """the keyframe of LocalMap.observe from its id, mcorb_lf_feature records (Rig.lf_features; or an nfeat x ncams matchIndex array)
+    and W_T_cur's translation per camera (the translation column of pose * cur_T_ref.inv(), GlobalMap.cpp:45-49)"""
+    lf = np.asarray(lf)
+    mi = lf["match_index"][:, :len(centres_w)] if lf.dtype.names else lf
+    return ObsFrameArrays(kf_id, mi, centres_w)
 
 
 def map_gates(X, nv1, nv, P, K, centre, kps, octave, F, inv_sigma2, device=None):

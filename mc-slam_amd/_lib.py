@@ -16,6 +16,7 @@ LIB_PATH = os.path.join(PKG_DIR, "libmcorb.so")
 OK, E_EMPTY, E_SIZE, E_CAP, E_ARG, E_HIP, E_NODEVICE, E_STATE, E_OVERFLOW = 0, -1, -2, -3, -4, -5, -6, -7, -8
 ORIENT_NONE, ORIENT_IC_ANGLE = 0, 1
 BOW_TRANSFORM, BOW_MATCH = 1, 2
+OBS_UPDATE, OBS_RECORD = 0, 1
 MAX_LEVELS, MAX_CAMS = 16, 16
 
 KP_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"),
@@ -57,6 +58,11 @@ class MapOut(C.Structure):
                 ("new_lid", C.c_void_p), ("pt3d", C.c_void_p), ("normal", C.c_void_p), ("dist2", C.c_void_p),
                 ("cos_parallax", C.c_void_p), ("neigh_skipped", C.c_void_p), ("depth_vec", C.c_void_p), ("n_matches", C.c_int32),
                 ("n_depth", C.c_int32), ("n_triangulated", C.c_int32), ("next_lid", C.c_int32)]
+
+
+class ObsFrame(C.Structure):
+    _fields_ = [("kf_id", C.c_int32), ("nfeat", C.c_int32), ("ncams", C.c_int32), ("reserved", C.c_int32), ("match_index", C.c_void_p),
+                ("centre_w", C.c_double * 3 * MAX_CAMS)]
 
 
 class McorbError(RuntimeError):
@@ -202,6 +208,13 @@ SIGNATURES = {
     "mcorb_lmap_last_triangulate_timing": (_i, [_vp, C.POINTER(_f), _ip, _ip]),
     "mcorb_host_map_gates": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
     "mcorb_dev_map_gates_selftest": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
+    "mcorb_lmap_set_rays": (_i, [_vp, _vp, _i, _vp]),
+    "mcorb_lmap_get_observations": (_i, [_vp, _i, C.POINTER(C.c_int32), _vp, _vp, _i, _ip]),
+    "mcorb_lmap_observe": (_i, [_vp, C.POINTER(ObsFrame), _vp, _vp, _i, _i, _vp, _i, _vp, _vp]),
+    "mcorb_lmap_update_points": (_i, [_vp, _vp, _i, _vp, C.c_double, _vp, _vp]),
+    "mcorb_lmap_delete": (_i, [_vp, _vp, _i, _vp, _vp, _i, _ip]),
+    "mcorb_lmap_observers": (_i, [_vp, _vp, _i, _vp, _i, _ip]),
+    "mcorb_lmap_last_landmark_timing": (_i, [_vp, C.POINTER(_f)]),
     "mcorb_host_geometry": (_i, [C.POINTER(Params), _i, _i, _vp]),
     "mcorb_synth_rig_frame": (_i, [C.c_uint32, _i, _i, _i, _i, _vp, _i]),
 }

@@ -162,9 +162,18 @@ constexpr int kMapBlock = 64;
 void launch_map_triangulate(hipStream_t st, const MapArgs &a, int nblocks_small, int nblocks_any);
 // k_map_depth: z[i] = row 2 of Rcw * pt3D(lids[i]) + tcw (getSceneDepthStats)
 void launch_map_depth(hipStream_t st, const double Rcw[9], const double tcw[3], const double *geom, const int *lids, int n, double *z);
-// k_map_put: point and normal of record put[i].x into slot put[i].y of geom
-void launch_map_put(hipStream_t st, const MapOut *rec, const int2 *put, int n, double *geom);
+// k_map_put: point, normal and n_rays of record put[i].x into slot put[i].y of geom / nrays
+void launch_map_put(hipStream_t st, const MapOut *rec, const int2 *put, int n, double *geom, int32_t *nrays);
 // the gates of n caller-given cases (mcorb_dev_map_gates_selftest); every pointer of c is device memory
 void launch_map_gates(hipStream_t st, const MapGateCases &c, int n, MapOut *out);
+
+
+// the landmarks' life (mcorb_landmark_gpu.hip).  k_lmap_observe: one lane per item of one round of mcorb_lmap_observe -- no two
+// items of a launch name one slot -- Landmark::updateNormal(frame, featInd) on the slot's point, normal and ray count
+void launch_lmap_observe(hipStream_t st, const LmCentres &cen, int ncams, const LmObsItem *items, int n, double *geom, int32_t *nrays);
+// k_lmap_update: one lane per item of one round of mcorb_lmap_update_points: GlobalMap::updateLandmark, result to out[item.idx]
+void launch_lmap_update(hipStream_t st, const LmUpdItem *items, int n, double max_diff, double *geom, LmUpdOut *out);
+// k_lmap_put_rays: nrays[lids[i]] = vals[i], or 0 with vals == NULL; every slot at most once
+void launch_lmap_put_rays(hipStream_t st, const int32_t *lids, const int32_t *vals, int n, int32_t *nrays);
 
 }  // namespace mcorb

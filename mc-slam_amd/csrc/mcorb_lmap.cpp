@@ -133,6 +133,9 @@ int mcorb_lmap_create(mcorb_vocab *v, int device, int max_landmarks, int max_can
     m->device = device; m->max_landmarks = max_landmarks; m->max_candidates = max_candidates; m->voc = v;
     m->flags.assign((size_t)max_landmarks, 0);
     m->stamp.assign((size_t)max_landmarks, 0);
+    m->n_rays.assign((size_t)max_landmarks, 0);
+    m->obs.resize((size_t)max_landmarks);
+    m->occ.assign((size_t)max_landmarks, 0);
     if (device < 0) {
         m->geom.assign((size_t)max_landmarks * 6, 0.0);
         m->desc.assign((size_t)max_landmarks * 32, 0);
@@ -146,11 +149,17 @@ int mcorb_lmap_create(mcorb_vocab *v, int device, int max_landmarks, int max_can
         TRY(m->ev1.create(hipEventDefault));
         TRY(m->ev2.create(hipEventDefault));
         TRY(m->ev3.create(hipEventDefault));
+        TRY(m->ev4.create(hipEventDefault));
+        TRY(m->ev5.create(hipEventDefault));
+        TRY(m->ev6.create(hipEventDefault));
+        TRY(m->ev7.create(hipEventDefault));
         TRY(m->best2.create());
         TRY(m->d_geom.alloc(N * 6));
         TRY(m->d_desc.alloc(N * 32));
         HIPCHK(hipMemset(m->d_geom, 0, N * 6 * sizeof(double)));
         HIPCHK(hipMemset(m->d_desc, 0, N * 32));
+        TRY(m->d_nrays.alloc(N));
+        HIPCHK(hipMemset(m->d_nrays, 0, N * sizeof(int32_t)));
         TRY(m->d_view.alloc(1));
         TRY(m->d_cand.alloc(C));
         TRY(m->d_afeats.alloc(C));

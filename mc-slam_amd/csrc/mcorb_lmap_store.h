@@ -1,5 +1,5 @@
-// mcorb_lmap_store.h -- the local map object, shared by its search (mcorb_lmap.cpp) and by the mapping step that fills it
-// (mcorb_mapping.cpp).
+// mcorb_lmap_store.h -- the local map object, shared by its search (mcorb_lmap.cpp), by the mapping step that fills it
+// (mcorb_mapping.cpp) and by the calls that keep its landmarks up to date (mcorb_landmark.cpp).
 #pragma once
 #include <mutex>
 #include <string>
@@ -10,6 +10,7 @@
 
 namespace mcorb {
 constexpr uint8_t kHasPt = 1, kHasNormal = 2, kHasDesc = 4, kMono = 8, kSet = kHasPt | kHasNormal;
+struct LmObs { int32_t kf_id, feat; };   // one observation of a landmark: KFs[i]'s id, featInds[i]
 }  // namespace mcorb
 
 struct mcorb_lmap {
@@ -52,6 +53,23 @@ struct mcorb_lmap {
     mcorb::Event ev2, ev3;
     float us_map_depth = 0.f, us_map_tri = 0.f;
     int last_map_launched = 0, last_map_depth = 0;
+    // the landmarks' life (mcorb_landmark.cpp).  n_rays: the host's copy of every slot's ray count (a device store's kernels read
+    // and write d_nrays); obs: per slot the observations (kf_id, feat) in the order they were added (KFs / featInds); occ: per
+    // slot how often a batch has named it so far, zero between calls
+    std::vector<int32_t> n_rays;
+    std::vector<std::vector<mcorb::LmObs>> obs;
+    std::vector<int32_t> occ;
+    mcorb::DevBuf<int32_t> d_nrays;
+    mcorb::HostBuf<mcorb::LmObsItem> h_obsitems;
+    mcorb::DevBuf<mcorb::LmObsItem> d_obsitems;
+    mcorb::HostBuf<mcorb::LmUpdItem> h_upditems;
+    mcorb::DevBuf<mcorb::LmUpdItem> d_upditems;
+    mcorb::HostBuf<mcorb::LmUpdOut> h_updout;
+    mcorb::DevBuf<mcorb::LmUpdOut> d_updout;
+    mcorb::HostBuf<int32_t> h_rays;        // a batch of (slot, n_rays) pairs for k_lmap_put_rays: slots, then values
+    mcorb::DevBuf<int32_t> d_rays;
+    mcorb::Event ev4, ev5, ev6, ev7;
+    float us_observe = 0.f, us_update = 0.f;
 };
 
 inline int check_lmap(const mcorb_lmap *m, const char *who)

@@ -8,8 +8,8 @@
 // the host-only store runs the same header serially.  What depends on order runs on the host in both: the baseline gate per
 // neighbour, and the walk over neighbours and matches in which an accepted match gives both features its new id and thereby skips
 // every later match of either feature.  An id is only ever set, never cleared, so a match that is assigned on entry is skipped in
-// the walk too and needs no record.  The accepted points and normals go from the records into their slots device to device
-// (k_map_put).
+// the walk too and needs no record.  The accepted points, normals and ray counts go from the records into their slots device to
+// device (k_map_put); the frames carry no keyframe id, so the caller registers the two observations (mcorb_lmap_observe).
 #include <math.h>
 #include <string.h>
 
@@ -373,7 +373,7 @@ int mcorb_lmap_triangulate_neighbours(mcorb_lmap *m, const mcorb_map_frame *cur,
         TRY(m->d_mapput.grow((size_t)ntri));
         for (int k = 0; k < ntri; k++) m->h_mapput[k] = make_int2(acc_rec[k], next_lid + k);
         HIPCHK(hipMemcpyAsync(m->d_mapput, m->h_mapput, (size_t)ntri * sizeof(int2), hipMemcpyHostToDevice, st));
-        launch_map_put(st, m->d_mapout, m->d_mapput, ntri, m->d_geom);
+        launch_map_put(st, m->d_mapout, m->d_mapput, ntri, m->d_geom, m->d_nrays);
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(st));
     } else {
@@ -383,7 +383,10 @@ int mcorb_lmap_triangulate_neighbours(mcorb_lmap *m, const mcorb_map_frame *cur,
             memcpy(g + 3, recs[acc_rec[k]].normal, 3 * sizeof(double));
         }
     }
-    for (int k = 0; k < ntri; k++) m->flags[next_lid + k] |= kSet;
+    for (int k = 0; k < ntri; k++) {
+        m->flags[next_lid + k] |= kSet;
+        m->n_rays[next_lid + k] = recs[acc_rec[k]].n_rays;
+    }
     for (size_t i = 0; i < total; i++) {
         out->verdict[i] = verdict[i];
         out->inliers[i] = verdict[i] == kMapLandmark || verdict[i] == kMapParallax;

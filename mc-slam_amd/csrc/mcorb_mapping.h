@@ -28,6 +28,7 @@
 // a NaN cos makes no landmark.  A match that passes every reject gate but fails the parallax window (a NaN cos included) keeps
 // inliers[i] == true in the reference although no landmark is made: verdict kMapParallax is an inlier.
 #pragma once
+#include "mcorb_landmark.h"
 #include "mcorb_triangulate.h"
 
 namespace mcorb {
@@ -92,17 +93,11 @@ MCORB_TRI_HD inline void map_centre(const double *P, double o[3])
     }
 }
 
-// the sum of normal_cur / cv::norm(normal_cur) over views [i0, i1)
+// the sum of normal_cur / cv::norm(normal_cur) over views [i0, i1) (mcorb_landmark.h has the ray)
 MCORB_TRI_HD inline void map_rays(const MapViews &v, int i0, int i1, const double X[3], double acc[3])
 {
     acc[0] = acc[1] = acc[2] = 0.0;
-    for (int i = i0; i < i1; i++) {
-        double d[3], sq = 0.0;
-        for (int k = 0; k < 3; k++) d[k] = X[k] - v.centre[i][k];
-        for (int k = 0; k < 3; k++) sq += d[k] * d[k];
-        const double inv = 1.0 / sqrt(sq);
-        for (int k = 0; k < 3; k++) acc[k] = acc[k] + d[k] * inv;
-    }
+    for (int i = i0; i < i1; i++) lm_ray_add(X, v.centre[i], acc);
 }
 
 // everything after the triangulation: the per-view gates, the parallax window, the normal of the new landmark
@@ -146,15 +141,9 @@ MCORB_TRI_HD inline void map_after(const MapViews &v, const double X[3], const f
     // normal = (normal * n_rays + rays) / (n_rays + rays')
     double acc[3];
     map_rays(v, 0, v.nv1, X, acc);
-    int n_rays = v.nv1;
-    const double inv1 = 1.0 / (double)n_rays;
-    for (int k = 0; k < 3; k++) o.normal[k] = acc[k] * inv1;
+    lm_normal_first(acc, v.nv1, o.normal, o.n_rays);
     map_rays(v, v.nv1, v.nv, X, acc);
-    for (int k = 0; k < 3; k++) o.normal[k] = o.normal[k] * (double)n_rays + acc[k];
-    n_rays += v.nv - v.nv1;
-    const double inv2 = 1.0 / (double)n_rays;
-    for (int k = 0; k < 3; k++) o.normal[k] = o.normal[k] * inv2;
-    o.n_rays = n_rays;
+    lm_normal_add(acc, v.nv - v.nv1, o.normal, o.n_rays);
     o.verdict = kMapLandmark;
 }
 

@@ -1,7 +1,7 @@
 // mcorb_mapping_gpu.hip -- the kernels of mcorb_lmap_triangulate_neighbours (mcorb_mapping.cpp): k_map_triangulate (one inter-frame
 // match of FrontEnd::triangulateMatches, FrontEnd.cpp:5826-5933, per lane: the views, the epipolar gate, the N-view DLT, the
 // reprojection and parallax gates and the new landmark's normal, mcorb_mapping.h), k_map_depth (getSceneDepthStats' z, :4846-4847),
-// k_map_put (accepted points and normals from the result records into the local map's slots) and the gates' self-test.  No
+// k_map_put (accepted points, normals and ray counts from the result records into the local map's slots) and the gates' self-test.  No
 // extraction job runs them and no benchmark leg times them.
 //
 // k_map_triangulate: one wave per workgroup, and a wave's matches belong to ONE neighbour (the host cuts every neighbour's matches
@@ -59,7 +59,7 @@ void launch_map_depth(hipStream_t st, const double Rcw[9], const double tcw[3], 
 // k_lmap_put's sibling: the source is the result records, put[i] = {record, slot}; the walk gives every new landmark an id of its
 // own, so no two lanes write one slot
 __global__ __launch_bounds__(256) void k_map_put(const MapOut *__restrict__ rec, const int2 *__restrict__ put, int n,
-                                                 double *__restrict__ geom)
+                                                 double *__restrict__ geom, int32_t *__restrict__ nrays)
 {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
@@ -67,12 +67,13 @@ __global__ __launch_bounds__(256) void k_map_put(const MapOut *__restrict__ rec,
     const MapOut &o = rec[p.x];
     double *g = geom + (size_t)p.y * 6;
     for (int k = 0; k < 3; k++) { g[k] = o.X[k]; g[3 + k] = o.normal[k]; }
+    nrays[p.y] = o.n_rays;
 }
 
-void launch_map_put(hipStream_t st, const MapOut *rec, const int2 *put, int n, double *geom)
+void launch_map_put(hipStream_t st, const MapOut *rec, const int2 *put, int n, double *geom, int32_t *nrays)
 {
     if (n < 1) return;
-    hipLaunchKernelGGL(k_map_put, dim3((n + 255) / 256), dim3(256), 0, st, rec, put, n, geom);
+    hipLaunchKernelGGL(k_map_put, dim3((n + 255) / 256), dim3(256), 0, st, rec, put, n, geom, nrays);
 }
 
 // mcorb_dev_map_gates_selftest: case i has nv[i] views (the first nv1[i] the neighbour's) starting at view voff[i]
