@@ -827,6 +827,85 @@ int mcorb_lmap_observers(mcorb_lmap *m, const int32_t *lids, int n, int32_t *kf_
 int mcorb_lmap_last_landmark_timing(mcorb_lmap *m, float us[2]);
 
 /* ------------------------------------------------------------------------- */
+/* Fast tracking: FrontEnd::startTrackingModule (MCSlam/src/FrontEnd.cpp:1570- */
+/* 1689) between the map-entry query and refinePose -- Tracking::project_      */
+/* (MCSlam/src/Tracking.cpp:208-260) of the gathered landmarks into every      */
+/* camera from the predicted pose, and Tracking::queryCurrentFrame /           */
+/* querryEachFrame (:319-449): the 10 nearest keypoints by image position, the */
+/* 100 px gate, the best Hamming distance below 20 and the serial              */
+/* de-duplication per keypoint.  Tracking::queryPoints, the JSON map and       */
+/* refinePose (OpenGV) stay with the caller.                                   */
+/* ------------------------------------------------------------------------- */
+#define MCORB_TRACK_KNN 10      /* the neighbours a projection is compared with (Tracking.cpp:335-345) */
+#define MCORB_TRACK_TILE 1024   /* keypoints per LDS tile of k_track_match; a camera may have any number */
+/* one camera of the rig: the pose (R, t) of its gtsam::PinholePose -- R_T_mats[i].inverse(), which the caller computes; R is
+ * row-major -- and the Cal3_S2 calibration */
+typedef struct mcorb_track_cam {
+    double R[9], t[3], fx, fy, s, u0, v0;
+} mcorb_track_cam;
+/* (R0, t0): cameraRig.c0_T_w, the predicted pose; cols / rows: imgCols / imgRows */
+typedef struct mcorb_track_view {
+    double R0[9], t0[3];
+    int32_t ncams, cols, rows, reserved;
+    mcorb_track_cam cams[MCORB_MAX_CAMS];
+} mcorb_track_view;
+/* the current frame, host arrays: per camera n_kp keypoints, kp_xy = image_kps[c][k].pt as 2 floats each (not the undistorted
+ * set) and desc = image_descriptors[c][k], 32 bytes each */
+typedef struct mcorb_track_frame {
+    int32_t ncams, reserved;
+    int32_t n_kp[MCORB_MAX_CAMS];
+    const float *kp_xy[MCORB_MAX_CAMS];
+    const uint8_t *desc[MCORB_MAX_CAMS];
+} mcorb_track_frame;
+/* the outputs of mcorb_lmap_track.  Every array is camera-major: camera c's entries start at c * cap_proj (c * cap_match).  An
+ * array may be NULL with its capacity 0; match_pt may be NULL at any capacity. */
+typedef struct mcorb_track_out {
+    int32_t cap_proj, cap_match;
+    int32_t *proj_lid;     /* [ncams][cap_proj]     projectedLandmarkIds[c], in candidate order */
+    float *proj_xy;        /* [ncams][cap_proj][2]  the projected keypoint's pt */
+    int32_t *best_kp;      /* [ncams][cap_proj]     bestMatchIndex of that query before the serial part, -1: none */
+    int32_t *best_dist;    /* [ncams][cap_proj]     its Hamming distance, 10000 with best_kp -1 */
+    int32_t *match_kp;     /* [ncams][cap_match]    bestMatches[c] as keypoint indices, in the reference's order */
+    int32_t *match_lid;    /* [ncams][cap_match]    bestMatchLandmarkIds[c] */
+    int32_t *match_dist;   /* [ncams][cap_match]    the distance recorded with the entry */
+    double *match_pt;      /* [ncams][cap_match][3] bestMatchLandmarks[c]: the store's point of match_lid */
+    int32_t n_proj[MCORB_MAX_CAMS], n_match[MCORB_MAX_CAMS];
+    int32_t n_candidates, reserved;
+} mcorb_track_out;
+/* One frame of fast tracking.  All arithmetic is fp64, one IEEE operation per operator in the order written.
+ * 1. candidates: lids in the caller's order (the reference iterates an unordered_map: unspecified there), skipping -1 and ids
+ *    seen before in this call.
+ * 2. projection (project_, with gtsam's Pose3::transformFrom / transformTo and PinholePose::project2 as recalled -- gtsam is not
+ *    vendored): p0 = R0 * X + t0, an element being (a0 * b0 + a1 * b1 + a2 * b2) + t; per camera q = R^T * (p0 - t), an element
+ *    a0 * b0 + a1 * b1 + a2 * b2.  A landmark with q.z <= 0 in any camera is dropped from all (the try encloses project2; a NaN z
+ *    does not drop).  Otherwise d = 1.0 / q.z, u = q.x * d, v = q.y * d, px = (fx * u + s * v) + u0, py = fy * v + v0, x =
+ *    (float)px, y = (float)py, and the camera is dropped iff x < 0 || x > cols || y < 0 || y > rows in float (both edges and a NaN
+ *    are kept; a NaN x or y is returned as the default quiet NaN 0x7fc00000, whose sign host and device would not agree on).
+ * 3. neighbours: d2 = dx * dx + dy * dy with dx = (double)x - (double)kx (cvflann::L2<double>); the candidates are the keypoints
+ *    with !(d2 > max_d2), the reference's form, less those with a NaN d2, which has no place in an order; of these the
+ *    MCORB_TRACK_KNN smallest under the total order (d2, k) are taken: the exact neighbours, where the reference's kd-tree
+ *    search is approximate, and only existing keypoints, where the reference's zero-initialised row names keypoint 0.
+ * 4. the descriptor gate, over the neighbours in (d2, k) order: best = 10000; a neighbour is taken iff dist < best && dist <
+ *    max_hamming (the reference's 20), so of equal distances the nearer keypoint holds.
+ * 5. the de-duplication (querryEachFrame:380-415), serial per camera in query order over a list of (kp, lid, dist): for a query
+ *    with a match k, the first entry whose keypoint has the same ((int)pt.x, (int)pt.y) is looked up; none: the triple is
+ *    appended; one whose recorded dist is greater: it is erased and the triple appended; otherwise nothing.  (The reference
+ *    compares with bestDists[k], an element of a vector that was only reserved and never written when the entry found is another
+ *    keypoint of the same pixel; here the found entry's own distance is compared.  Keypoint coordinates must convert to int.)
+ * A device store runs 2 in k_track_project and 3 + 4 in k_track_match, in one submission; a host-only store runs the same header
+ * serially; the results are equal bit for bit.  No landmark is changed (the candidate walk uses the store's per-slot stamps, scratch
+ * that no call reads as state).
+ * Before anything runs: MCORB_E_ARG for view->ncams outside 1 .. MCORB_MAX_CAMS, a frame of another camera count, a negative
+ * n_kp, max_hamming or capacity, a NULL array with a non-zero count, an id other than -1 outside the store; MCORB_E_STATE for a
+ * candidate without a point or without a descriptor; MCORB_E_CAP for more candidates than max_candidates.  Afterwards:
+ * MCORB_E_CAP, with every count set and no array written, when n_proj[c] > cap_proj or n_match[c] > cap_match for a camera. */
+int mcorb_lmap_track(mcorb_lmap *m, const mcorb_track_view *view, const mcorb_track_frame *frame, const int32_t *lids, int n_lids,
+                     double max_d2, int max_hamming, mcorb_track_out *out);
+/* a device store's last k_track_project (us[0]) and k_track_match (us[1]) launch, microseconds between HIP events; a call that
+ * launches nothing leaves them */
+int mcorb_lmap_last_track_timing(mcorb_lmap *m, float us[2]);
+
+/* ------------------------------------------------------------------------- */
 /* Host stages exposed for the CPU test-suite (no device needed)              */
 /* ------------------------------------------------------------------------- */
 /* The engine's quad-tree selection, DistributeOctTree's equivalent (ORBextractor.cpp:554-778), run

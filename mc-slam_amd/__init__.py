@@ -1265,6 +1265,87 @@ class LocalMap:
         _lib.check(self.L.mcorb_lmap_last_landmark_timing(self.h, us))
         return us[0], us[1]
 
+    def track(self, view, kps, descs, lids, max_d2=10000.0, max_hamming=20, caps=None):
+        """one frame of fast tracking (FrontEnd::startTrackingModule between the map-entry query and refinePose): Tracking::project_
+        of the landmarks `lids` (the nearest map entries' l_ids back to back; -1 and repeats are skipped) into every camera of
+        view = track_view(...), and Tracking::queryCurrentFrame against the frame -> TrackResult.  kps: per camera the keypoints
+        (image_kps: an n x 2 float array, or keypoint records with x and y); descs: per camera n x 32 bytes; caps: (projected,
+        matches) output sizes per camera, by default what cannot be exceeded; a McorbError of this call carries n_candidates,
+        n_proj and n_match as the call left them"""
+        ncams = len(kps)
+        if not 1 <= ncams <= _lib.MAX_CAMS or len(descs) != ncams:
+            raise ValueError("track: 1 .. %d cameras, one keypoint and one descriptor array each" % _lib.MAX_CAMS)
+        xy = []
+        for k in kps:
+            k = np.asarray(k)
+            xy.append(np.ascontiguousarray(np.stack([k["x"], k["y"]], axis=1) if k.dtype.names else k, np.float32).reshape(-1, 2))
+        ds = [_u8(d).reshape(-1, 32) for d in descs]
+        if any(len(a) != len(d) for a, d in zip(xy, ds)):
+            raise ValueError("track: a camera has another number of descriptors than keypoints")
+        f = _lib.TrackFrame()
+        f.ncams = ncams
+        for c in range(ncams):
+            f.n_kp[c], f.kp_xy[c], f.desc[c] = len(xy[c]), xy[c].ctypes.data, ds[c].ctypes.data
+        lids = np.ascontiguousarray(lids, np.int32).reshape(-1)
+        cap_p, cap_m = caps if caps is not None else (len(lids), len(lids))
+        n1, n2 = ncams * max(cap_p, 1), ncams * max(cap_m, 1)
+        r = dict(proj_lid=np.zeros(n1, np.int32), proj_xy=np.zeros((n1, 2), np.float32), best_kp=np.zeros(n1, np.int32),
+                 best_dist=np.zeros(n1, np.int32), match_kp=np.zeros(n2, np.int32), match_lid=np.zeros(n2, np.int32),
+                 match_dist=np.zeros(n2, np.int32), match_pt=np.zeros((n2, 3)))
+        o = _lib.TrackOut()
+        o.cap_proj, o.cap_match = cap_p, cap_m
+        for k, a in r.items():
+            setattr(o, k, a.ctypes.data)
+        code = self.L.mcorb_lmap_track(self.h, C.byref(view), C.byref(f), lids.ctypes.data, len(lids), float(max_d2),
+                                       int(max_hamming), C.byref(o))
+        n_proj, n_match = list(o.n_proj[:ncams]), list(o.n_match[:ncams])
+        if code != _lib.OK:
+            try:
+                _lib.check(code)
+            except McorbError as e:     # MCORB_E_CAP for a short output comes with every count set
+                e.n_candidates, e.n_proj, e.n_match = o.n_candidates, n_proj, n_match
+                raise
+        out = {k: [r[k][c * cap_p:c * cap_p + n_proj[c]].copy() for c in range(ncams)] for k in ("proj_lid", "proj_xy", "best_kp", "best_dist")}
+        out.update({k: [r[k][c * cap_m:c * cap_m + n_match[c]].copy() for c in range(ncams)]
+                    for k in ("match_kp", "match_lid", "match_dist", "match_pt")})
+        return TrackResult(n_candidates=o.n_candidates, **out)
+
+    def last_track_timing(self):
+        """(microseconds of the last k_track_project launch, of the last k_track_match launch); a device store"""
+        us = (C.c_float * 2)()
+        _lib.check(self.L.mcorb_lmap_last_track_timing(self.h, us))
+        return us[0], us[1]
+
+
+class TrackResult:
+    """what LocalMap.track returns, every member a list with one array per camera.  The projected landmarks in candidate order:
+    proj_lid, proj_xy (the projected keypoint's pt, float32) and, per projected query before the serial part, best_kp (-1: none)
+    and best_dist (10000 with -1).  After the de-duplication, in the reference's order: match_kp (bestMatches as keypoint
+    indices), match_lid (bestMatchLandmarkIds), match_dist and match_pt (bestMatchLandmarks: the store's points).  n_candidates:
+    the distinct landmarks of the call"""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+def track_view(R0, t0, cam_R, cam_t, K_mats, cols, rows):
+    """the view of LocalMap.track: (R0, t0) = cameraRig.c0_T_w, the predicted pose; cam_R / cam_t: per camera the pose of its
+    PinholePose (R_T_mats[i].inverse(), which the caller computes); K_mats: per camera the 3x3 calibration, of which fx, s, u0, fy
+    and v0 are read (Cal3_S2); cols / rows: imgCols / imgRows"""
+    v = _lib.TrackView()
+    v.R0[:] = np.asarray(R0, np.float64).reshape(9).tolist()
+    v.t0[:] = np.asarray(t0, np.float64).reshape(3).tolist()
+    v.ncams, v.cols, v.rows = len(cam_R), int(cols), int(rows)
+    if not 1 <= v.ncams <= _lib.MAX_CAMS or not len(cam_t) == len(K_mats) == v.ncams:
+        raise ValueError("track_view: 1 .. %d cameras, one R, t and K each" % _lib.MAX_CAMS)
+    for c in range(v.ncams):
+        K = np.asarray(K_mats[c], np.float64).reshape(3, 3)
+        cam = v.cams[c]
+        cam.R[:] = np.asarray(cam_R[c], np.float64).reshape(9).tolist()
+        cam.t[:] = np.asarray(cam_t[c], np.float64).reshape(3).tolist()
+        cam.fx, cam.s, cam.u0, cam.fy, cam.v0 = float(K[0, 0]), float(K[0, 1]), float(K[0, 2]), float(K[1, 1]), float(K[1, 2])
+    return v
+
 
 class ObsFrameArrays:
     """the observing keyframe of LocalMap.observe (mcorb_obs_frame); keeps the array the struct points to"""

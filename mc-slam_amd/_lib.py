@@ -18,6 +18,7 @@ ORIENT_NONE, ORIENT_IC_ANGLE = 0, 1
 BOW_TRANSFORM, BOW_MATCH = 1, 2
 OBS_UPDATE, OBS_RECORD = 0, 1
 MAX_LEVELS, MAX_CAMS = 16, 16
+TRACK_KNN, TRACK_TILE = 10, 1024   # MCORB_TRACK_KNN, MCORB_TRACK_TILE
 
 KP_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"),
                      ("response", "<f4"), ("octave", "<i4"), ("class_id", "<i4")])
@@ -63,6 +64,28 @@ class MapOut(C.Structure):
 class ObsFrame(C.Structure):
     _fields_ = [("kf_id", C.c_int32), ("nfeat", C.c_int32), ("ncams", C.c_int32), ("reserved", C.c_int32), ("match_index", C.c_void_p),
                 ("centre_w", C.c_double * 3 * MAX_CAMS)]
+
+
+class TrackCam(C.Structure):
+    _fields_ = [("R", C.c_double * 9), ("t", C.c_double * 3), ("fx", C.c_double), ("fy", C.c_double), ("s", C.c_double),
+                ("u0", C.c_double), ("v0", C.c_double)]
+
+
+class TrackView(C.Structure):
+    _fields_ = [("R0", C.c_double * 9), ("t0", C.c_double * 3), ("ncams", C.c_int32), ("cols", C.c_int32), ("rows", C.c_int32),
+                ("reserved", C.c_int32), ("cams", TrackCam * MAX_CAMS)]
+
+
+class TrackFrame(C.Structure):
+    _fields_ = [("ncams", C.c_int32), ("reserved", C.c_int32), ("n_kp", C.c_int32 * MAX_CAMS), ("kp_xy", C.c_void_p * MAX_CAMS),
+                ("desc", C.c_void_p * MAX_CAMS)]
+
+
+class TrackOut(C.Structure):
+    _fields_ = [("cap_proj", C.c_int32), ("cap_match", C.c_int32), ("proj_lid", C.c_void_p), ("proj_xy", C.c_void_p),
+                ("best_kp", C.c_void_p), ("best_dist", C.c_void_p), ("match_kp", C.c_void_p), ("match_lid", C.c_void_p),
+                ("match_dist", C.c_void_p), ("match_pt", C.c_void_p), ("n_proj", C.c_int32 * MAX_CAMS),
+                ("n_match", C.c_int32 * MAX_CAMS), ("n_candidates", C.c_int32), ("reserved", C.c_int32)]
 
 
 class McorbError(RuntimeError):
@@ -215,6 +238,8 @@ SIGNATURES = {
     "mcorb_lmap_delete": (_i, [_vp, _vp, _i, _vp, _vp, _i, _ip]),
     "mcorb_lmap_observers": (_i, [_vp, _vp, _i, _vp, _i, _ip]),
     "mcorb_lmap_last_landmark_timing": (_i, [_vp, C.POINTER(_f)]),
+    "mcorb_lmap_track": (_i, [_vp, C.POINTER(TrackView), C.POINTER(TrackFrame), _vp, _i, C.c_double, _i, C.POINTER(TrackOut)]),
+    "mcorb_lmap_last_track_timing": (_i, [_vp, C.POINTER(_f)]),
     "mcorb_host_geometry": (_i, [C.POINTER(Params), _i, _i, _vp]),
     "mcorb_synth_rig_frame": (_i, [C.c_uint32, _i, _i, _i, _i, _vp, _i]),
 }

@@ -1,5 +1,6 @@
 // mcorb_kernels.h -- launch wrappers of the gfx950 kernels (mcorb_kernels.hip, mcorb_select_gpu.hip, mcorb_handoff_gpu.hip,
-// mcorb_bow_gpu.hip, mcorb_lf_gpu.hip, mcorb_kfdb_gpu.hip, mcorb_lmap_gpu.hip, mcorb_mapping_gpu.hip).
+// mcorb_bow_gpu.hip, mcorb_lf_gpu.hip, mcorb_kfdb_gpu.hip, mcorb_lmap_gpu.hip, mcorb_mapping_gpu.hip, mcorb_landmark_gpu.hip,
+// mcorb_track_gpu.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <vector>
@@ -7,6 +8,7 @@
 #include "mcorb_common.h"
 #include "mcorb_mapping.h"
 #include "mcorb_signal.h"
+#include "mcorb_track.h"
 #include "mcorb_undistort.h"
 #include "mcorb_undistort_image.h"
 
@@ -175,5 +177,19 @@ void launch_lmap_observe(hipStream_t st, const LmCentres &cen, int ncams, const 
 void launch_lmap_update(hipStream_t st, const LmUpdItem *items, int n, double max_diff, double *geom, LmUpdOut *out);
 // k_lmap_put_rays: nrays[lids[i]] = vals[i], or 0 with vals == NULL; every slot at most once
 void launch_lmap_put_rays(hipStream_t st, const int32_t *lids, const int32_t *vals, int n, int32_t *nrays);
+
+// fast tracking (mcorb_track_gpu.hip).  k_track_project: Tracking::project_ of candidates cand[0 .. n) (slots of geom) into the
+// cameras of view -> camera-major xy[c * n + i] and valid[c * n + i] (0: dropped), and the gathered points into pts (may be NULL)
+constexpr int kTrackProjectT = 256;   // k_track_project's workgroup: one lane per candidate
+void launch_track_project(hipStream_t st, const mcorb_track_view &view, const double *geom, const int *cand, int n, float2 *xy,
+                          uint8_t *valid, double *pts);
+// k_track_match: per camera c < ncams and candidate i with valid[c * n + i], the best keypoint of the frame by position and
+// descriptor -> best[c * n + i]; kp_xy / kp_desc: the cameras' keypoints and descriptors back to back, camera c's from
+// frame.first[c]; lm_desc: the store's descriptors, 32 bytes per slot
+constexpr int kTrackMatchWaves = 4;   // waves of a workgroup, which shares one LDS tile of keypoints
+constexpr int kTrackMatchQ = 4;       // consecutive candidates a wave serves
+constexpr int kTrackMatchT = 64 * kTrackMatchWaves;
+void launch_track_match(hipStream_t st, const TrFrame &frame, int ncams, const float2 *kp_xy, const uint8_t *kp_desc, const uint8_t *lm_desc,
+                        const int *cand, int n, const float2 *xy, const uint8_t *valid, double max_d2, int max_hamming, TrBest *best);
 
 }  // namespace mcorb

@@ -28,13 +28,6 @@
 
 using namespace mcorb;
 
-// a new stamp value; the stamps start over before the counter wraps
-static int next_tick(mcorb_lmap *m)
-{
-    if (m->tick == 0x7fffffff) { std::fill(m->stamp.begin(), m->stamp.end(), 0); m->tick = 0; }
-    return ++m->tick;
-}
-
 // what set and set_desc_from_entry share: ids inside the store, and of an id that occurs twice only the last entry kept (keep[i])
 static int check_batch(mcorb_lmap *m, const int32_t *lids, int n, const char *who, std::vector<int> &keep)
 {
@@ -153,6 +146,9 @@ int mcorb_lmap_create(mcorb_vocab *v, int device, int max_landmarks, int max_can
         TRY(m->ev5.create(hipEventDefault));
         TRY(m->ev6.create(hipEventDefault));
         TRY(m->ev7.create(hipEventDefault));
+        TRY(m->ev8.create(hipEventDefault));
+        TRY(m->ev9.create(hipEventDefault));
+        TRY(m->ev10.create(hipEventDefault));
         TRY(m->best2.create());
         TRY(m->d_geom.alloc(N * 6));
         TRY(m->d_desc.alloc(N * 32));

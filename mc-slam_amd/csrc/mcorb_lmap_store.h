@@ -1,12 +1,14 @@
 // mcorb_lmap_store.h -- the local map object, shared by its search (mcorb_lmap.cpp), by the mapping step that fills it
-// (mcorb_mapping.cpp) and by the calls that keep its landmarks up to date (mcorb_landmark.cpp).
+// (mcorb_mapping.cpp), by the calls that keep its landmarks up to date (mcorb_landmark.cpp) and by fast tracking (mcorb_track.cpp).
 #pragma once
+#include <algorithm>
 #include <mutex>
 #include <string>
 #include <vector>
 
 #include "mcorb_kfdb_store.h"
 #include "mcorb_mapping.h"
+#include "mcorb_track.h"
 
 namespace mcorb {
 constexpr uint8_t kHasPt = 1, kHasNormal = 2, kHasDesc = 4, kMono = 8, kSet = kHasPt | kHasNormal;
@@ -70,7 +72,28 @@ struct mcorb_lmap {
     mcorb::DevBuf<int32_t> d_rays;
     mcorb::Event ev4, ev5, ev6, ev7;
     float us_observe = 0.f, us_update = 0.f;
+    // scratch of mcorb_lmap_track (mcorb_track.cpp), grow-only: the packed input (candidates, then the keypoints and the
+    // descriptors of every camera; one block, one copy), the projections, validity bytes and gathered points, the queries' results
+    mcorb::HostBuf<uint8_t> h_trackin;
+    mcorb::DevBuf<uint8_t> d_trackin;
+    mcorb::DevBuf<float2> d_trackxy;
+    mcorb::HostBuf<float2> h_trackxy;
+    mcorb::DevBuf<uint8_t> d_trackvalid;
+    mcorb::HostBuf<uint8_t> h_trackvalid;
+    mcorb::DevBuf<double> d_trackpt;
+    mcorb::HostBuf<double> h_trackpt;
+    mcorb::DevBuf<mcorb::TrBest> d_trackbest;
+    mcorb::HostBuf<mcorb::TrBest> h_trackbest;
+    mcorb::Event ev8, ev9, ev10;
+    float us_track_project = 0.f, us_track_match = 0.f;
 };
+
+// a new stamp value; the stamps start over before the counter wraps
+inline int next_tick(mcorb_lmap *m)
+{
+    if (m->tick == 0x7fffffff) { std::fill(m->stamp.begin(), m->stamp.end(), 0); m->tick = 0; }
+    return ++m->tick;
+}
 
 inline int check_lmap(const mcorb_lmap *m, const char *who)
 {
