@@ -892,8 +892,9 @@ typedef struct mcorb_track_out {
  *    appended; one whose recorded dist is greater: it is erased and the triple appended; otherwise nothing.  (The reference
  *    compares with bestDists[k], an element of a vector that was only reserved and never written when the entry found is another
  *    keypoint of the same pixel; here the found entry's own distance is compared.  Keypoint coordinates must convert to int.)
- * A device store runs 2 in k_track_project and 3 + 4 in k_track_match, in one submission; a host-only store runs the same header
- * serially; the results are equal bit for bit.  No landmark is changed (the candidate walk uses the store's per-slot stamps, scratch
+ * A device store runs 2 in k_track_project, 3 + 4 in k_track_match and the compaction of every camera's kept candidates, in
+ * candidate order, in k_track_compact, in one submission whose rows land in host-mapped memory; 1 and 5 run on the host.  A
+ * host-only store runs the same header serially; the results are equal bit for bit.  No landmark is changed (the candidate walk uses the store's per-slot stamps, scratch
  * that no call reads as state).
  * Before anything runs: MCORB_E_ARG for view->ncams outside 1 .. MCORB_MAX_CAMS, a frame of another camera count, a negative
  * n_kp, max_hamming or capacity, a NULL array with a non-zero count, an id other than -1 outside the store; MCORB_E_STATE for a
@@ -901,9 +902,26 @@ typedef struct mcorb_track_out {
  * MCORB_E_CAP, with every count set and no array written, when n_proj[c] > cap_proj or n_match[c] > cap_match for a camera. */
 int mcorb_lmap_track(mcorb_lmap *m, const mcorb_track_view *view, const mcorb_track_frame *frame, const int32_t *lids, int n_lids,
                      double max_d2, int max_hamming, mcorb_track_out *out);
+/* mcorb_lmap_track on a frame of a rig slot's last extraction job, read where the job left it: the mcorb_track_frame has ncams =
+ * the rig's cameras, camera c being image frame * ncams + c of the slot, kp_xy that image's image_kps[c][k].pt exactly as
+ * mcorb_rig_get_features returns it (not the undistorted set) and desc its descriptors in the same order.  Every output is bit
+ * for bit what mcorb_lmap_track gives on those host arrays; steps, deviations, error rules and MCORB_E_CAP are those above.
+ * On a device store nothing of the frame crosses PCIe: k_track_points rebuilds the keypoints from the slot's packed selection
+ * words into a buffer of the store, k_track_match reads the slot's descriptors in HBM, and only the candidates go up and the
+ * kept rows come down.  A host-only store (device -1) reads the slot's host records and runs the serial path; no kernel is
+ * launched.  Before anything runs, besides the refusals above: MCORB_E_ARG for a NULL rig, a slot out of range, a view whose
+ * ncams is not the rig's, a rig on another device than a device store; MCORB_E_STATE for a busy slot, frame < 0 or (frame + 1) *
+ * ncams beyond the images of the slot's last finished extraction.  After any refusal n_candidates, n_proj and n_match are zero
+ * and the store is unchanged.  Nothing of the slot is cached: every call reads the slot as it is.  The caller must not submit a
+ * job on the slot during the call (the call reads the slot's buffers on the store's stream). */
+int mcorb_lmap_track_rig_frame(mcorb_lmap *m, const mcorb_track_view *view, mcorb_rig *r, int slot, int frame, const int32_t *lids,
+                               int n_lids, double max_d2, int max_hamming, mcorb_track_out *out);
 /* a device store's last k_track_project (us[0]) and k_track_match (us[1]) launch, microseconds between HIP events; a call that
  * launches nothing leaves them */
 int mcorb_lmap_last_track_timing(mcorb_lmap *m, float us[2]);
+/* the same for all four kernels of the last call: k_track_points (0 after mcorb_lmap_track, which does not run it),
+ * k_track_project, k_track_match, k_track_compact; a call that launches nothing leaves them */
+int mcorb_lmap_last_track_timing4(mcorb_lmap *m, float us[4]);
 
 /* ------------------------------------------------------------------------- */
 /* Host stages exposed for the CPU test-suite (no device needed)              */

@@ -1286,6 +1286,19 @@ class LocalMap:
         f.ncams = ncams
         for c in range(ncams):
             f.n_kp[c], f.kp_xy[c], f.desc[c] = len(xy[c]), xy[c].ctypes.data, ds[c].ctypes.data
+        return self._track(ncams, lids, caps, lambda lids, o: self.L.mcorb_lmap_track(
+            self.h, C.byref(view), C.byref(f), lids.ctypes.data, len(lids), float(max_d2), int(max_hamming), C.byref(o)))
+
+    def track_rig_frame(self, view, rig, frame, lids, slot=0, max_d2=10000.0, max_hamming=20, caps=None):
+        """track() on frame `frame` of the last extraction job of a rig slot, read where the job left it: camera c is image
+        frame * ncams + c, its keypoints image_kps (Rig.features, not the undistorted set) and its descriptors.  On a device store
+        the frame does not cross PCIe.  The result and a McorbError's counts are track()'s, bit for bit what track() gives on the
+        arrays Rig.features returns.  No job may be submitted on the slot during the call"""
+        return self._track(view.ncams, lids, caps, lambda lids, o: self.L.mcorb_lmap_track_rig_frame(
+            self.h, C.byref(view), rig.h_rig if rig is not None else None, slot, frame, lids.ctypes.data, len(lids), float(max_d2),
+            int(max_hamming), C.byref(o)))
+
+    def _track(self, ncams, lids, caps, call):
         lids = np.ascontiguousarray(lids, np.int32).reshape(-1)
         cap_p, cap_m = caps if caps is not None else (len(lids), len(lids))
         n1, n2 = ncams * max(cap_p, 1), ncams * max(cap_m, 1)
@@ -1296,8 +1309,7 @@ class LocalMap:
         o.cap_proj, o.cap_match = cap_p, cap_m
         for k, a in r.items():
             setattr(o, k, a.ctypes.data)
-        code = self.L.mcorb_lmap_track(self.h, C.byref(view), C.byref(f), lids.ctypes.data, len(lids), float(max_d2),
-                                       int(max_hamming), C.byref(o))
+        code = call(lids, o)
         n_proj, n_match = list(o.n_proj[:ncams]), list(o.n_match[:ncams])
         if code != _lib.OK:
             try:
@@ -1315,6 +1327,13 @@ class LocalMap:
         us = (C.c_float * 2)()
         _lib.check(self.L.mcorb_lmap_last_track_timing(self.h, us))
         return us[0], us[1]
+
+    def last_track_timing4(self):
+        """(microseconds of the last k_track_points, k_track_project, k_track_match and k_track_compact launch); k_track_points is
+        0 after track(), which does not run it; a device store"""
+        us = (C.c_float * 4)()
+        _lib.check(self.L.mcorb_lmap_last_track_timing4(self.h, us))
+        return us[0], us[1], us[2], us[3]
 
 
 class TrackResult:

@@ -239,7 +239,9 @@ SIGNATURES = {
     "mcorb_lmap_observers": (_i, [_vp, _vp, _i, _vp, _i, _ip]),
     "mcorb_lmap_last_landmark_timing": (_i, [_vp, C.POINTER(_f)]),
     "mcorb_lmap_track": (_i, [_vp, C.POINTER(TrackView), C.POINTER(TrackFrame), _vp, _i, C.c_double, _i, C.POINTER(TrackOut)]),
+    "mcorb_lmap_track_rig_frame": (_i, [_vp, C.POINTER(TrackView), _vp, _i, _i, _vp, _i, C.c_double, _i, C.POINTER(TrackOut)]),
     "mcorb_lmap_last_track_timing": (_i, [_vp, C.POINTER(_f)]),
+    "mcorb_lmap_last_track_timing4": (_i, [_vp, C.POINTER(_f)]),
     "mcorb_host_geometry": (_i, [C.POINTER(Params), _i, _i, _vp]),
     "mcorb_synth_rig_frame": (_i, [C.c_uint32, _i, _i, _i, _i, _vp, _i]),
 }

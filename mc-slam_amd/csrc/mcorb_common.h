@@ -74,6 +74,11 @@ struct LfView { int32_t cam, kp; float x, y; };
 struct LfCam { double K[9], Rt[12]; };
 struct LfTrackOut { double X[3]; float uv[2]; int32_t accept, rep; };
 
+// fast tracking on a rig slot's frame (mcorb_lmap_track_rig_frame): k_track_points' workgroup, one lane per keypoint of a row of
+// kcap; k_track_compact's workgroup, one lane per candidate, whose prefix sum over the validity bytes before it takes 16 bytes a load
+constexpr int kTrackPointsT = 256;
+constexpr int kTrackCompactT = 256;
+
 // Packed selected keypoint handed back to the device: level (4) | y (14) | x (14), level coordinates.
 __host__ __device__ inline uint32_t pack_sel(int level, int x, int y) { return ((uint32_t)level << 28) | ((uint32_t)y << 14) | (uint32_t)x; }
 __host__ __device__ inline void unpack_sel(uint32_t v, int &level, int &x, int &y)

@@ -191,5 +191,13 @@ constexpr int kTrackMatchQ = 4;       // consecutive candidates a wave serves
 constexpr int kTrackMatchT = 64 * kTrackMatchWaves;
 void launch_track_match(hipStream_t st, const TrFrame &frame, int ncams, const float2 *kp_xy, const uint8_t *kp_desc, const uint8_t *lm_desc,
                         const int *cand, int n, const float2 *xy, const uint8_t *valid, double max_d2, int max_hamming, TrBest *best);
+// k_track_points: pt of the selected keypoints of images img0 .. img0 + ncams of a rig slot (sel / nsel as k_undistort reads them,
+// rows of kcap) -> out[c * kcap + k] for k < min(nsel[img0 + c], kcap): k_track_match's kp_xy with first[c] = c * kcap
+void launch_track_points(hipStream_t st, const uint32_t *sel, const int *nsel, int kcap, int img0, int ncams, const float *scale,
+                         int nlevels, float2 *out);
+// k_track_compact: per camera the candidates with valid[c * n + i], in candidate order -> rows[c * n + 0 .. n_proj[c]) and
+// n_proj[c]; rows / n_proj may be host-mapped pinned memory
+void launch_track_compact(hipStream_t st, int ncams, int n, const uint8_t *valid, const float2 *xy, const TrBest *best, TrRow *rows,
+                          int32_t *n_proj);
 
 }  // namespace mcorb

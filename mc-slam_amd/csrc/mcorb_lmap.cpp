@@ -149,6 +149,8 @@ int mcorb_lmap_create(mcorb_vocab *v, int device, int max_landmarks, int max_can
         TRY(m->ev8.create(hipEventDefault));
         TRY(m->ev9.create(hipEventDefault));
         TRY(m->ev10.create(hipEventDefault));
+        TRY(m->ev11.create(hipEventDefault));
+        TRY(m->ev12.create(hipEventDefault));
         TRY(m->best2.create());
         TRY(m->d_geom.alloc(N * 6));
         TRY(m->d_desc.alloc(N * 32));

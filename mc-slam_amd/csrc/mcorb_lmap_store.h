@@ -72,20 +72,25 @@ struct mcorb_lmap {
     mcorb::DevBuf<int32_t> d_rays;
     mcorb::Event ev4, ev5, ev6, ev7;
     float us_observe = 0.f, us_update = 0.f;
-    // scratch of mcorb_lmap_track (mcorb_track.cpp), grow-only: the packed input (candidates, then the keypoints and the
-    // descriptors of every camera; one block, one copy), the projections, validity bytes and gathered points, the queries' results
+    // scratch of mcorb_lmap_track / mcorb_lmap_track_rig_frame (mcorb_track.cpp), grow-only: the packed input (candidates, then --
+    // host arrays only -- the keypoints and the descriptors of every camera; one block, one copy), a rig slot's keypoints
+    // (k_track_points), the projections, validity bytes and gathered points, the queries' results, and what the host tail reads:
+    // the compacted rows and the counts per camera, host-mapped pinned memory k_track_compact writes
     mcorb::HostBuf<uint8_t> h_trackin;
     mcorb::DevBuf<uint8_t> d_trackin;
+    mcorb::DevBuf<float2> d_trackkp;
     mcorb::DevBuf<float2> d_trackxy;
-    mcorb::HostBuf<float2> h_trackxy;
     mcorb::DevBuf<uint8_t> d_trackvalid;
-    mcorb::HostBuf<uint8_t> h_trackvalid;
     mcorb::DevBuf<double> d_trackpt;
     mcorb::HostBuf<double> h_trackpt;
     mcorb::DevBuf<mcorb::TrBest> d_trackbest;
-    mcorb::HostBuf<mcorb::TrBest> h_trackbest;
-    mcorb::Event ev8, ev9, ev10;
-    float us_track_project = 0.f, us_track_match = 0.f;
+    mcorb::HostBuf<mcorb::TrRow> h_trackrows;
+    mcorb::HostBuf<int32_t> h_tracknproj;
+    mcorb::Event ev8, ev9, ev10, ev11, ev12;   // in front of k_track_project | match | compact | behind it | in front of k_track_points
+    float us_track_points = 0.f, us_track_project = 0.f, us_track_match = 0.f, us_track_compact = 0.f;
+#ifdef MCORB_TRACK_PROF
+    float us_track_phase[5] = {};   // the last call's host phases: candidate walk, submission, wait, de-duplication, output
+#endif
 };
 
 // a new stamp value; the stamps start over before the counter wraps

@@ -4,15 +4,20 @@
 // each projection against the frame's keypoints by image position -- the 10 nearest, a 100 px gate, the best Hamming distance
 // below 20 -- and de-duplicate per keypoint, serially.  Not restated: Tracking::queryPoints, the JSON map, refinePose (OpenGV).
 //
-// The arithmetic is mcorb_track.h.  A device store runs the projection in k_track_project and the neighbour search with the
-// descriptor gate in k_track_match, both in one submission: the candidates, keypoints and descriptors go up as one pinned block
-// in one copy, the points and the landmarks' descriptors are read from the store's slots in HBM.  The host-only store runs the
-// same header serially.  The candidate walk, the compaction in candidate order and the order-dependent de-duplication run on the
-// host in both.  The reference's kd-tree search (FLANN, 4 trees, 64 checks) is approximate and un-vendored: the neighbours here
-// are exact.  The store's landmarks are only read: of the map object the call writes its own scratch and, as mcorb_lmap_search
-// does, the per-slot stamps of the candidate walk (tick / stamp), which no call reads as state.
+// The arithmetic is mcorb_track.h.  A device store runs the projection in k_track_project, the neighbour search with the
+// descriptor gate in k_track_match and the compaction in candidate order in k_track_compact, all in one submission: the points
+// and the landmarks' descriptors are read from the store's slots in HBM, the kept rows land in host-mapped memory, and the one
+// synchronisation is all the host waits for.  The frame comes from host arrays (mcorb_lmap_track: candidates, keypoints and
+// descriptors go up as one pinned block in one copy) or from a rig slot (mcorb_lmap_track_rig_frame: only the candidates go up;
+// k_track_points rebuilds the keypoints from the slot's packed selection words, the descriptors are read where the extraction
+// job left them).  The host-only store runs the same header serially.  Both entries share the argument and candidate checks,
+// the submission and the host tail: the candidate walk and the order-dependent de-duplication run on the host.  The
+// reference's kd-tree search (FLANN, 4 trees, 64 checks) is approximate and un-vendored: the neighbours here are exact.  The
+// store's landmarks are only read: of the map object the call writes its own scratch and, as mcorb_lmap_search does, the
+// per-slot stamps of the candidate walk (tick / stamp), which no call reads as state.
 #include <string.h>
 
+#include <chrono>
 #include <mutex>
 #include <vector>
 
@@ -24,16 +29,55 @@ namespace {
 
 int fail(int code, const char *what) { set_error(std::string("lmap track: ") + what); return code; }
 
+// a camera's keypoints on the host: records of `stride` bytes that begin with pt's two floats -- the caller's packed pairs
+// (mcorb_lmap_track) or a rig slot's keypoint records (mcorb_lmap_track_rig_frame)
+struct KpRows {
+    const uint8_t *base[MCORB_MAX_CAMS];
+    size_t stride;
+    const float *pt(int c, int k) const { return reinterpret_cast<const float *>(base[c] + (size_t)k * stride); }
+};
+
+// the frame of a call.  Both entries: the keypoint count per camera and the host's keypoints.  desc: the host's descriptors, which
+// the host-array entry uploads and a host-only store reads.  slot (the slot entry on a device store): where the kernels find the
+// frame in HBM -- image img0 + c is camera c
+struct Frame {
+    int32_t n_kp[MCORB_MAX_CAMS];
+    KpRows kp;
+    const uint8_t *desc[MCORB_MAX_CAMS];
+    Rig *rig = nullptr;
+    Slot *slot = nullptr;
+    int img0 = 0;
+};
+
+// the host phases of a call, for scripts/track_rate.py: compiled in with -DMCORB_TRACK_PROF only (mcorb_lmap_track_phases)
+struct Phases {
+#ifdef MCORB_TRACK_PROF
+    float *us;
+    std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
+    explicit Phases(mcorb_lmap *m) : us(m->us_track_phase) { for (int k = 0; k < 5; k++) us[k] = 0.f; }
+    void mark(int k)
+    {
+        const auto now = std::chrono::steady_clock::now();
+        us[k] += std::chrono::duration<float, std::micro>(now - t).count();
+        t = now;
+    }
+#else
+    explicit Phases(mcorb_lmap *) {}
+    void mark(int) {}
+#endif
+};
+
 // one query on the host: the MCORB_TRACK_KNN least keys (d2, k) among the keypoints inside the radius, kept in order by
 // insertion, then the descriptor gate over them in that order
-TrBest query_host(float x, float y, const float *kp_xy, const uint8_t *kp_desc, int n_kp, const uint8_t *lm_desc, double max_d2,
+TrBest query_host(float x, float y, const KpRows &kp, int c, const uint8_t *kp_desc, int n_kp, const uint8_t *lm_desc, double max_d2,
                   int max_hamming)
 {
     TrKey top[MCORB_TRACK_KNN];
     int ntop = 0;
     for (int k = 0; k < n_kp; k++) {
         uint64_t d2;
-        if (!tr_d2(x, y, kp_xy[2 * (size_t)k], kp_xy[2 * (size_t)k + 1], max_d2, d2)) continue;
+        const float *p = kp.pt(c, k);
+        if (!tr_d2(x, y, p[0], p[1], max_d2, d2)) continue;
         if (ntop == MCORB_TRACK_KNN && !tr_less(d2, (uint32_t)k, top[ntop - 1].d2, top[ntop - 1].k)) continue;
         int at = ntop < MCORB_TRACK_KNN ? ntop++ : ntop - 1;
         for (; at > 0 && tr_less(d2, (uint32_t)k, top[at - 1].d2, top[at - 1].k); at--) top[at] = top[at - 1];
@@ -48,177 +92,213 @@ TrBest query_host(float x, float y, const float *kp_xy, const uint8_t *kp_desc, 
     return TrBest{(int32_t)top[key & 15u].k, (int32_t)(key >> 4)};
 }
 
+// an entry of the de-duplication's list.  What the search compares, the pixel ((int)pt.x, (int)pt.y) of the entry's keypoint, is
+// kept beside the list as one 64-bit key per entry: the scan reads 8 bytes an entry and stays in the first-level cache
 struct Triple { int32_t kp, lid, dist, cand; };
+inline uint64_t pixel_key(int px, int py) { return ((uint64_t)(uint32_t)px << 32) | (uint32_t)py; }
 
 size_t round32(size_t n) { return (n + 31) & ~(size_t)31; }
 
-}  // namespace
-
-extern "C" {
-
-int mcorb_lmap_track(mcorb_lmap *m, const mcorb_track_view *view, const mcorb_track_frame *frame, const int32_t *lids, int n_lids,
-                     double max_d2, int max_hamming, mcorb_track_out *out)
+void clear_counts(mcorb_track_out *out)
 {
-    TRY(check_lmap(m, "lmap track"));
-    if (!view || !frame || !out || n_lids < 0 || (n_lids && !lids) || max_hamming < 0) return fail(MCORB_E_ARG, "bad argument");
-    const int C = view->ncams;
-    if (C < 1 || C > MCORB_MAX_CAMS) return fail(MCORB_E_ARG, "1 .. MCORB_MAX_CAMS cameras");
-    if (frame->ncams != C) return fail(MCORB_E_ARG, "the frame has another camera count than the view");
-    size_t total_kp = 0;
-    TrFrame tf;
-    memset(&tf, 0, sizeof(tf));
-    for (int c = 0; c < C; c++) {
-        if (frame->n_kp[c] < 0) return fail(MCORB_E_ARG, "a negative keypoint count");
-        if (frame->n_kp[c] && (!frame->kp_xy[c] || !frame->desc[c])) return fail(MCORB_E_ARG, "a camera's keypoints or descriptors are NULL");
-        tf.n_kp[c] = frame->n_kp[c];
-        tf.first[c] = (int32_t)total_kp;
-        total_kp += (size_t)frame->n_kp[c];
-        if (total_kp > 0x7fffffffu) return fail(MCORB_E_ARG, "too many keypoints");
-    }
+    memset(out->n_proj, 0, sizeof(out->n_proj));
+    memset(out->n_match, 0, sizeof(out->n_match));
+    out->n_candidates = 0;
+}
+
+// ---- 1. what both entries refuse before anything runs, the frame apart: the arguments, then -- the caller holds the store's
+// lock -- the candidates ----
+int check_args(const mcorb_track_view *view, const int32_t *lids, int n_lids, int max_hamming, mcorb_track_out *out)
+{
+    if (!view || !out || n_lids < 0 || (n_lids && !lids) || max_hamming < 0) return fail(MCORB_E_ARG, "bad argument");
+    clear_counts(out);
+    if (view->ncams < 1 || view->ncams > MCORB_MAX_CAMS) return fail(MCORB_E_ARG, "1 .. MCORB_MAX_CAMS cameras");
     const int cap_p = out->cap_proj, cap_m = out->cap_match;
     if (cap_p < 0 || cap_m < 0 || (cap_p && (!out->proj_lid || !out->proj_xy || !out->best_kp || !out->best_dist)) ||
         (cap_m && (!out->match_kp || !out->match_lid || !out->match_dist)))
         return fail(MCORB_E_ARG, "an output array is NULL");
-    memset(out->n_proj, 0, sizeof(out->n_proj));
-    memset(out->n_match, 0, sizeof(out->n_match));
-    out->n_candidates = 0;
-    std::lock_guard<std::mutex> lk(m->mu);
+    return MCORB_OK;
+}
 
-    // ---- 1. the candidates; everything that can be refused is refused before anything runs ----
+int candidates_of(mcorb_lmap *m, const int32_t *lids, int n_lids, mcorb_track_out *out, std::vector<int> &cand)
+{
     for (int i = 0; i < n_lids; i++)
         if (lids[i] < -1 || lids[i] >= m->max_landmarks) return fail(MCORB_E_ARG, "landmark id outside the store");
     const int t = next_tick(m);
-    std::vector<int> cand;
     for (int i = 0; i < n_lids; i++) {
         const int l = lids[i];
         if (l == -1 || m->stamp[l] == t) continue;
         m->stamp[l] = t;
         cand.push_back(l);
     }
-    const int nc = (int)cand.size();
     for (int l : cand) {
         if (!(m->flags[l] & kHasPt)) return fail(MCORB_E_STATE, "a candidate landmark has no point");
         if (!(m->flags[l] & kHasDesc)) return fail(MCORB_E_STATE, "a candidate landmark has no descriptor");
     }
-    if (nc > m->max_candidates) return fail(MCORB_E_CAP, "more candidates than max_candidates");
-    out->n_candidates = nc;
-    if (nc == 0) return MCORB_OK;
+    if ((int)cand.size() > m->max_candidates) return fail(MCORB_E_CAP, "more candidates than max_candidates");
+    out->n_candidates = (int)cand.size();
+    return MCORB_OK;
+}
 
-    // ---- 2. per camera and candidate: the projection, whether it is kept, the query's result ----
-    const size_t rows = (size_t)C * nc;
-    const float2 *xy = nullptr;
-    const uint8_t *valid = nullptr;
-    const TrBest *best = nullptr;
-    const double *pts = nullptr;   // [nc][3] on a device store
-    std::vector<float2> hxy;
-    std::vector<uint8_t> hvalid;
-    std::vector<TrBest> hbest;
-    if (m->device < 0) {
-        hxy.assign(rows, make_float2(0.f, 0.f));
-        hvalid.assign(rows, 0);
-        hbest.assign(rows, TrBest{-1, kTrBest0});
-        for (int i = 0; i < nc; i++) {
-            double p0[3];
-            tr_body(view->R0, view->t0, &m->geom[(size_t)cand[i] * 6], p0);
-            if (!tr_in_front(*view, p0)) continue;
-            for (int c = 0; c < C; c++) {
-                const size_t at = (size_t)c * nc + i;
-                float x = 0.f, y = 0.f;
-                if (!tr_pixel(*view, c, p0, x, y)) continue;
-                hxy[at] = make_float2(x, y);
-                hvalid[at] = 1;
-                hbest[at] = query_host(x, y, frame->kp_xy[c], frame->desc[c], frame->n_kp[c], &m->desc[(size_t)cand[i] * 32], max_d2,
-                                       max_hamming);
-            }
-        }
-        xy = hxy.data(); valid = hvalid.data(); best = hbest.data();
-    } else {
-        HIPCHK(hipSetDevice(m->device));
-        hipStream_t st = m->st;
-        const size_t off_xy = round32((size_t)nc * sizeof(int)), off_desc = off_xy + round32(total_kp * 8);
-        const size_t bytes = off_desc + total_kp * 32;
-        TRY(m->h_trackin.grow(bytes, hipHostMallocDefault));
-        TRY(m->d_trackin.grow(bytes));
-        TRY(m->d_trackxy.grow(rows));
-        TRY(m->h_trackxy.grow(rows, hipHostMallocDefault));
-        TRY(m->d_trackvalid.grow(rows));
-        TRY(m->h_trackvalid.grow(rows, hipHostMallocDefault));
-        TRY(m->d_trackbest.grow(rows));
-        TRY(m->h_trackbest.grow(rows, hipHostMallocDefault));
-        const bool want_pts = out->match_pt != nullptr;
-        if (want_pts) {
-            TRY(m->d_trackpt.grow((size_t)nc * 3));
-            TRY(m->h_trackpt.grow((size_t)nc * 3, hipHostMallocDefault));
-        }
-        uint8_t *in = m->h_trackin;
-        memcpy(in, cand.data(), (size_t)nc * sizeof(int));
+// ---- 2. per camera the kept candidates in candidate order: the projection and the query's result ----
+// a host-only store: mcorb_track.h serially
+void rows_on_host(const mcorb_lmap *m, const mcorb_track_view &view, const Frame &f, const std::vector<int> &cand, double max_d2,
+                  int max_hamming, std::vector<TrRow> &rows, int32_t *n_proj)
+{
+    const int C = view.ncams, nc = (int)cand.size();
+    rows.resize((size_t)C * nc);
+    for (int c = 0; c < C; c++) n_proj[c] = 0;
+    for (int i = 0; i < nc; i++) {
+        double p0[3];
+        tr_body(view.R0, view.t0, &m->geom[(size_t)cand[i] * 6], p0);
+        if (!tr_in_front(view, p0)) continue;
         for (int c = 0; c < C; c++) {
-            if (!frame->n_kp[c]) continue;
-            memcpy(in + off_xy + (size_t)tf.first[c] * 8, frame->kp_xy[c], (size_t)frame->n_kp[c] * 8);
-            memcpy(in + off_desc + (size_t)tf.first[c] * 32, frame->desc[c], (size_t)frame->n_kp[c] * 32);
+            float x = 0.f, y = 0.f;
+            if (!tr_pixel(view, c, p0, x, y)) continue;
+            const TrBest b = query_host(x, y, f.kp, c, f.desc[c], f.n_kp[c], &m->desc[(size_t)cand[i] * 32], max_d2, max_hamming);
+            rows[(size_t)c * nc + n_proj[c]++] = TrRow{i, x, y, b.kp, b.dist};
         }
-        HIPCHK(hipMemcpyAsync(m->d_trackin, m->h_trackin, bytes, hipMemcpyHostToDevice, st));
-        const int *d_cand = reinterpret_cast<const int *>(m->d_trackin.get());
-        HIPCHK(hipEventRecord(m->ev8, st));
-        launch_track_project(st, *view, m->d_geom, d_cand, nc, m->d_trackxy, m->d_trackvalid, want_pts ? m->d_trackpt.get() : nullptr);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(m->ev9, st));
-        launch_track_match(st, tf, C, reinterpret_cast<const float2 *>(m->d_trackin.get() + off_xy), m->d_trackin.get() + off_desc,
-                           m->d_desc, d_cand, nc, m->d_trackxy, m->d_trackvalid, max_d2, max_hamming, m->d_trackbest);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(m->ev10, st));
-        HIPCHK(hipMemcpyAsync(m->h_trackxy, m->d_trackxy, rows * sizeof(float2), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(m->h_trackvalid, m->d_trackvalid, rows, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(m->h_trackbest, m->d_trackbest, rows * sizeof(TrBest), hipMemcpyDeviceToHost, st));
-        if (want_pts) HIPCHK(hipMemcpyAsync(m->h_trackpt, m->d_trackpt, (size_t)nc * 3 * sizeof(double), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        float ms = 0.f;
-        ev_elapsed(&ms, m->ev8, m->ev9);
-        m->us_track_project = ms * 1000.f;
-        ev_elapsed(&ms, m->ev9, m->ev10);
-        m->us_track_match = ms * 1000.f;
-        xy = m->h_trackxy; valid = m->h_trackvalid; best = m->h_trackbest;
-        if (want_pts) pts = m->h_trackpt;
     }
+}
 
-    // ---- 3. the projected lists in candidate order, and the de-duplication (querryEachFrame:380-415), serial per camera ----
+// The sel / nsel of the slot's last extraction as a kernel may read them: the job's own view (Slot::ctl, as launch_undistort is
+// given it) -- but a later match job points ctl at the device mirror, which a small host-selected batch never filled: that
+// batch's words are in the host-mapped block
+void slot_sel(const Slot &s, const uint32_t *&sel, const int *&nsel)
+{
+    const bool host_sel = s.host_results && !s.rig->gpu_select;
+    sel = host_sel ? s.hc.sel : s.ctl.sel;
+    nsel = host_sel ? s.hc.nsel : s.ctl.nsel;
+}
+
+// a device store: one submission on the store's stream -- the candidates (and the host arrays' frame) up in one copy,
+// [k_track_points,] k_track_project, k_track_match, k_track_compact, no host step between them -- and one synchronisation.  The
+// rows and counts are in host-mapped memory then; the gathered points (want_pts) come down in the one result copy there is
+int rows_on_device(mcorb_lmap *m, const mcorb_track_view &view, const Frame &f, const std::vector<int> &cand, double max_d2,
+                   int max_hamming, bool want_pts, Phases &ph)
+{
+    const int C = view.ncams, nc = (int)cand.size();
+    const size_t rows = (size_t)C * nc;
+    HIPCHK(hipSetDevice(m->device));
+    hipStream_t st = m->st;
+    TrFrame tf;
+    memset(&tf, 0, sizeof(tf));
+    size_t total_kp = 0;
+    const int kcap = f.slot ? f.rig->geom.kcap : 0;
+    for (int c = 0; c < C; c++) {
+        tf.n_kp[c] = f.n_kp[c];
+        tf.first[c] = f.slot ? c * kcap : (int32_t)total_kp;
+        total_kp += (size_t)f.n_kp[c];
+    }
+    if (f.slot) total_kp = 0;   // nothing of the frame goes up
+    const size_t off_xy = round32((size_t)nc * sizeof(int)), off_desc = off_xy + round32(total_kp * 8);
+    const size_t bytes = off_desc + total_kp * 32;
+    TRY(m->h_trackin.grow(bytes, hipHostMallocDefault));
+    TRY(m->d_trackin.grow(bytes));
+    TRY(m->d_trackxy.grow(rows));
+    TRY(m->d_trackvalid.grow(rows));
+    TRY(m->d_trackbest.grow(rows));
+    TRY(m->h_trackrows.grow(rows, kHostMapped));
+    TRY(m->h_tracknproj.grow(MCORB_MAX_CAMS, kHostMapped));
+    if (f.slot) TRY(m->d_trackkp.grow((size_t)C * kcap));
+    if (want_pts) {
+        TRY(m->d_trackpt.grow((size_t)nc * 3));
+        TRY(m->h_trackpt.grow((size_t)nc * 3, hipHostMallocDefault));
+    }
+    uint8_t *in = m->h_trackin;
+    memcpy(in, cand.data(), (size_t)nc * sizeof(int));
+    if (!f.slot)
+        for (int c = 0; c < C; c++) {
+            if (!f.n_kp[c]) continue;
+            memcpy(in + off_xy + (size_t)tf.first[c] * 8, f.kp.base[c], (size_t)f.n_kp[c] * 8);
+            memcpy(in + off_desc + (size_t)tf.first[c] * 32, f.desc[c], (size_t)f.n_kp[c] * 32);
+        }
+    HIPCHK(hipMemcpyAsync(m->d_trackin, m->h_trackin, bytes, hipMemcpyHostToDevice, st));
+    const int *d_cand = reinterpret_cast<const int *>(m->d_trackin.get());
+    const float2 *kp_xy = reinterpret_cast<const float2 *>(m->d_trackin.get() + off_xy);
+    const uint8_t *kp_desc = m->d_trackin.get() + off_desc;
+    if (f.slot) {
+        const uint32_t *sel;
+        const int *nsel;
+        slot_sel(*f.slot, sel, nsel);
+        HIPCHK(hipEventRecord(m->ev12, st));
+        launch_track_points(st, sel, nsel, kcap, f.img0, C, f.rig->tab.scale, f.rig->tab.nlevels, m->d_trackkp);
+        HIPCHK(hipGetLastError());
+        kp_xy = m->d_trackkp;
+        kp_desc = f.slot->d_desc.get() + (size_t)f.img0 * kcap * 32;
+    }
+    HIPCHK(hipEventRecord(m->ev8, st));
+    launch_track_project(st, view, m->d_geom, d_cand, nc, m->d_trackxy, m->d_trackvalid, want_pts ? m->d_trackpt.get() : nullptr);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(m->ev9, st));
+    launch_track_match(st, tf, C, kp_xy, kp_desc, m->d_desc, d_cand, nc, m->d_trackxy, m->d_trackvalid, max_d2, max_hamming, m->d_trackbest);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(m->ev10, st));
+    launch_track_compact(st, C, nc, m->d_trackvalid, m->d_trackxy, m->d_trackbest, m->h_trackrows, m->h_tracknproj);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(m->ev11, st));
+    if (want_pts) HIPCHK(hipMemcpyAsync(m->h_trackpt, m->d_trackpt, (size_t)nc * 3 * sizeof(double), hipMemcpyDeviceToHost, st));
+    ph.mark(1);
+    HIPCHK(hipStreamSynchronize(st));
+    ph.mark(2);
+    float ms = 0.f;
+    m->us_track_points = 0.f;
+    if (f.slot) {
+        ev_elapsed(&ms, m->ev12, m->ev8);
+        m->us_track_points = ms * 1000.f;
+    }
+    ev_elapsed(&ms, m->ev8, m->ev9);
+    m->us_track_project = ms * 1000.f;
+    ev_elapsed(&ms, m->ev9, m->ev10);
+    m->us_track_match = ms * 1000.f;
+    ev_elapsed(&ms, m->ev10, m->ev11);
+    m->us_track_compact = ms * 1000.f;
+    return MCORB_OK;
+}
+
+// ---- 3. the host tail, over a camera's rows [c * nc, c * nc + n_proj[c]): the projected lists as they are, the de-duplication
+// (querryEachFrame:380-415) over the rows with a match, serial per camera, and the outputs.  pts: [nc][3] of a device store ----
+int finish(const mcorb_lmap *m, int C, const std::vector<int> &cand, const TrRow *rows, const int32_t *n_proj, const KpRows &kp,
+           const double *pts, mcorb_track_out *out, Phases &ph)
+{
+    const int nc = (int)cand.size(), cap_p = out->cap_proj, cap_m = out->cap_match;
     std::vector<std::vector<Triple>> lists((size_t)C);
+    std::vector<uint64_t> keys;   // of the camera's list, entry by entry
     bool is_short = false;
     for (int c = 0; c < C; c++) {
-        const size_t row = (size_t)c * nc;
-        int np = 0;
-        for (int i = 0; i < nc; i++) np += valid[row + i] ? 1 : 0;
-        out->n_proj[c] = np;
+        const TrRow *row = rows + (size_t)c * nc;
+        out->n_proj[c] = n_proj[c];
         std::vector<Triple> &list = lists[c];
-        const float *kps = frame->kp_xy[c];
-        for (int i = 0; i < nc; i++) {
-            if (!valid[row + i] || best[row + i].kp < 0) continue;
-            const TrBest b = best[row + i];
-            const int px = (int)kps[2 * (size_t)b.kp], py = (int)kps[2 * (size_t)b.kp + 1];
+        keys.clear();
+        for (int r = 0; r < n_proj[c]; r++) {
+            if (row[r].kp < 0) continue;
+            const TrRow &b = row[r];
+            const float *p = kp.pt(c, b.kp);
+            const uint64_t key = pixel_key((int)p[0], (int)p[1]);
             size_t at = 0;
-            for (; at < list.size(); at++)
-                if ((int)kps[2 * (size_t)list[at].kp] == px && (int)kps[2 * (size_t)list[at].kp + 1] == py) break;
+            for (const size_t n = keys.size(); at < n && keys[at] != key; at++) {}
             if (at < list.size()) {
                 if (!(list[at].dist > b.dist)) continue;
                 list.erase(list.begin() + (ptrdiff_t)at);
+                keys.erase(keys.begin() + (ptrdiff_t)at);
             }
-            list.push_back(Triple{b.kp, cand[i], b.dist, i});
+            list.push_back(Triple{b.kp, cand[b.i], b.dist, b.i});
+            keys.push_back(key);
         }
         out->n_match[c] = (int32_t)list.size();
-        if (np > cap_p || (int)list.size() > cap_m) is_short = true;
+        if (n_proj[c] > cap_p || (int)list.size() > cap_m) is_short = true;
     }
+    ph.mark(3);
     if (is_short) return fail(MCORB_E_CAP, "output too small");
     for (int c = 0; c < C; c++) {
-        const size_t row = (size_t)c * nc, op = (size_t)c * cap_p, om = (size_t)c * cap_m;
-        int at = 0;
-        for (int i = 0; i < nc; i++) {
-            if (!valid[row + i]) continue;
-            out->proj_lid[op + at] = cand[i];
-            out->proj_xy[2 * (op + at)] = xy[row + i].x;
-            out->proj_xy[2 * (op + at) + 1] = xy[row + i].y;
-            out->best_kp[op + at] = best[row + i].kp;
-            out->best_dist[op + at] = best[row + i].dist;
-            at++;
+        const TrRow *row = rows + (size_t)c * nc;
+        const size_t op = (size_t)c * cap_p, om = (size_t)c * cap_m;
+        for (int r = 0; r < n_proj[c]; r++) {
+            out->proj_lid[op + r] = cand[row[r].i];
+            out->proj_xy[2 * (op + r)] = row[r].x;
+            out->proj_xy[2 * (op + r) + 1] = row[r].y;
+            out->best_kp[op + r] = row[r].kp;
+            out->best_dist[op + r] = row[r].dist;
         }
         for (size_t k = 0; k < lists[c].size(); k++) {
             const Triple &tr = lists[c][k];
@@ -229,7 +309,87 @@ int mcorb_lmap_track(mcorb_lmap *m, const mcorb_track_view *view, const mcorb_tr
                 memcpy(out->match_pt + 3 * (om + k), pts ? pts + 3 * (size_t)tr.cand : &m->geom[(size_t)tr.lid * 6], 3 * sizeof(double));
         }
     }
+    ph.mark(4);
     return MCORB_OK;
+}
+
+// a call from the candidates on, the frame checked: the caller has run check_args
+int track(mcorb_lmap *m, const mcorb_track_view *view, const Frame &f, const int32_t *lids, int n_lids, double max_d2, int max_hamming,
+          mcorb_track_out *out)
+{
+    std::lock_guard<std::mutex> lk(m->mu);
+    Phases ph(m);
+    std::vector<int> cand;
+    TRY(candidates_of(m, lids, n_lids, out, cand));
+    ph.mark(0);
+    if (cand.empty()) return MCORB_OK;
+    if (m->device < 0) {
+        std::vector<TrRow> rows;
+        int32_t n_proj[MCORB_MAX_CAMS];
+        rows_on_host(m, *view, f, cand, max_d2, max_hamming, rows, n_proj);
+        ph.mark(2);
+        return finish(m, view->ncams, cand, rows.data(), n_proj, f.kp, nullptr, out, ph);
+    }
+    const bool want_pts = out->match_pt != nullptr;
+    TRY(rows_on_device(m, *view, f, cand, max_d2, max_hamming, want_pts, ph));
+    return finish(m, view->ncams, cand, m->h_trackrows, m->h_tracknproj, f.kp, want_pts ? m->h_trackpt.get() : nullptr, out, ph);
+}
+
+}  // namespace
+
+extern "C" {
+
+int mcorb_lmap_track(mcorb_lmap *m, const mcorb_track_view *view, const mcorb_track_frame *frame, const int32_t *lids, int n_lids,
+                     double max_d2, int max_hamming, mcorb_track_out *out)
+{
+    TRY(check_lmap(m, "lmap track"));
+    if (!frame) return fail(MCORB_E_ARG, "bad argument");
+    TRY(check_args(view, lids, n_lids, max_hamming, out));
+    const int C = view->ncams;
+    if (frame->ncams != C) return fail(MCORB_E_ARG, "the frame has another camera count than the view");
+    Frame f;
+    f.kp.stride = 2 * sizeof(float);
+    size_t total_kp = 0;
+    for (int c = 0; c < C; c++) {
+        if (frame->n_kp[c] < 0) return fail(MCORB_E_ARG, "a negative keypoint count");
+        if (frame->n_kp[c] && (!frame->kp_xy[c] || !frame->desc[c])) return fail(MCORB_E_ARG, "a camera's keypoints or descriptors are NULL");
+        f.n_kp[c] = frame->n_kp[c];
+        f.kp.base[c] = reinterpret_cast<const uint8_t *>(frame->kp_xy[c]);
+        f.desc[c] = frame->desc[c];
+        total_kp += (size_t)frame->n_kp[c];
+        if (total_kp > 0x7fffffffu) return fail(MCORB_E_ARG, "too many keypoints");
+    }
+    return track(m, view, f, lids, n_lids, max_d2, max_hamming, out);
+}
+
+int mcorb_lmap_track_rig_frame(mcorb_lmap *m, const mcorb_track_view *view, mcorb_rig *r, int slot, int frame, const int32_t *lids,
+                               int n_lids, double max_d2, int max_hamming, mcorb_track_out *out)
+{
+    TRY(check_lmap(m, "lmap track_rig_frame"));
+    TRY(check_args(view, lids, n_lids, max_hamming, out));
+    if (!r || slot < 0 || slot >= (int)r->rig.slots.size()) return fail(MCORB_E_ARG, "no such rig slot");
+    Rig &R = r->rig;
+    const int C = view->ncams;
+    if (R.ncams != C) return fail(MCORB_E_ARG, "the rig has another camera count than the view");
+    if (m->device >= 0 && m->device != R.device) return fail(MCORB_E_ARG, "the rig lives on another device");
+    Slot *s = R.slots[slot].get();
+    {
+        std::lock_guard<std::mutex> lk(s->m);
+        if (s->busy) return fail(MCORB_E_STATE, "slot busy");
+    }
+    if (frame < 0 || ((long long)frame + 1) * C > s->nimg_done) return fail(MCORB_E_STATE, "frame not extracted by the slot's last job");
+    Frame f;
+    f.kp.stride = sizeof(mcorb_keypoint);
+    f.rig = &R;
+    f.slot = m->device >= 0 ? s : nullptr;
+    f.img0 = frame * C;
+    for (int c = 0; c < C; c++) {
+        const std::vector<mcorb_keypoint> &K = s->kps[(size_t)f.img0 + c];
+        f.n_kp[c] = (int32_t)std::min(K.size(), (size_t)R.geom.kcap);
+        f.kp.base[c] = reinterpret_cast<const uint8_t *>(K.data());
+        f.desc[c] = s->h_desc + ((size_t)f.img0 + c) * R.geom.kcap * 32;
+    }
+    return track(m, view, f, lids, n_lids, max_d2, max_hamming, out);
 }
 
 int mcorb_lmap_last_track_timing(mcorb_lmap *m, float us[2])
@@ -241,5 +401,30 @@ int mcorb_lmap_last_track_timing(mcorb_lmap *m, float us[2])
     us[1] = m->us_track_match;
     return MCORB_OK;
 }
+
+int mcorb_lmap_last_track_timing4(mcorb_lmap *m, float us[4])
+{
+    TRY(check_lmap(m, "lmap last_track_timing4"));
+    if (!us) { set_error("lmap last_track_timing4: bad argument"); return MCORB_E_ARG; }
+    std::lock_guard<std::mutex> lk(m->mu);
+    us[0] = m->us_track_points;
+    us[1] = m->us_track_project;
+    us[2] = m->us_track_match;
+    us[3] = m->us_track_compact;
+    return MCORB_OK;
+}
+
+#ifdef MCORB_TRACK_PROF
+// the last call's host phases in microseconds: candidate walk, submission, wait, de-duplication, output.  Not part of the
+// public header: a build with -DMCORB_TRACK_PROF exports it for scripts/track_rate.py
+int mcorb_lmap_track_phases(mcorb_lmap *m, float us[5])
+{
+    TRY(check_lmap(m, "lmap track_phases"));
+    if (!us) { set_error("lmap track_phases: bad argument"); return MCORB_E_ARG; }
+    std::lock_guard<std::mutex> lk(m->mu);
+    memcpy(us, m->us_track_phase, sizeof(m->us_track_phase));
+    return MCORB_OK;
+}
+#endif
 
 }  // extern "C"

@@ -104,5 +104,9 @@ MCORB_TR_HD inline uint32_t tr_gate_key(int dist, int rank, int max_hamming)
 struct TrFrame { int32_t n_kp[MCORB_MAX_CAMS]; int32_t first[MCORB_MAX_CAMS]; };
 // a query's result before the serial part
 struct TrBest { int32_t kp, dist; };
+// a kept (camera, candidate) pair as the host tail walks it: the candidate's place in the call's list, the projected keypoint, the
+// query's result.  A camera's rows are its kept candidates in candidate order, n_proj of them from row c * n (k_track_compact on a
+// device store, the serial path itself on a host-only one)
+struct TrRow { int32_t i; float x, y; int32_t kp, dist; };
 
 }  // namespace mcorb

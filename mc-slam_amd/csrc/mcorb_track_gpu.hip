@@ -1,15 +1,19 @@
 // mcorb_track_gpu.hip -- the kernels of fast tracking on a device store (mcorb_track.cpp): k_track_project (Tracking::project_,
 // MCSlam/src/Tracking.cpp:208-260, for every candidate landmark and camera) and k_track_match (the per-query part of
 // Tracking::querryEachFrame, :329-377: the 10 nearest keypoints by image position, the radius gate, the best Hamming distance).
-// The arithmetic is mcorb_track.h, the code the host-only store runs.  No extraction job runs them and no benchmark leg times them.
+// The arithmetic is mcorb_track.h, the code the host-only store runs.  k_track_points (mcorb_lmap_track_rig_frame only) rebuilds a
+// rig slot's keypoints from their packed selection words; k_track_compact leaves each camera's kept candidates in candidate
+// order, in host-mapped memory.  No extraction job runs them and no benchmark leg times them.
 //
-// The two go out in one submission: k_track_match reads the validity bytes k_track_project wrote, and the host compacts in
-// candidate order after the one synchronisation.  No atomics, no scratch, no workgroup waits on another, and a query's result
-// depends on that query alone, so the launch shape cannot change it.
+// They go out in one submission: k_track_match reads the validity bytes k_track_project wrote and the points k_track_points
+// wrote, k_track_compact reads all three kernels' rows, and the host walks the compacted rows after the one synchronisation.
+// No atomics, no scratch, no workgroup waits on another, and a query's result depends on that query alone, so the launch shape
+// cannot change it.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "mcorb_common.h"
+#include "mcorb_device.h"
 #include "mcorb_kernels.h"
 #include "mcorb_track.h"
 
@@ -164,6 +168,82 @@ void launch_track_match(hipStream_t st, const TrFrame &frame, int ncams, const f
     hipLaunchKernelGGL(k_track_match, dim3((n + per_block - 1) / per_block, ncams), dim3(kTrackMatchT), 0, st, frame, kp_xy,
                        reinterpret_cast<const uint32_t *>(kp_desc), reinterpret_cast<const uint32_t *>(lm_desc), cand, n, xy, valid,
                        max_d2, max_hamming, best);
+}
+
+// One lane per keypoint of a row of kcap, camera c's image being img0 + c of the slot: pt as the host's keypoint record has it
+// (sel_point), for k_track_match's tiles.  A pass of its own: on a small batch sel / nsel are host-mapped memory, which is read
+// here once and not once per workgroup of k_track_match.  The padding of a row (k >= nsel) is not written and never read.
+__global__ __launch_bounds__(kTrackPointsT) void k_track_points(const uint32_t *__restrict__ sel, const int *__restrict__ nsel, int kcap,
+                                                                int img0, UndistScales sc, float2 *__restrict__ out)
+{
+    const int c = blockIdx.y, m = img0 + c, k = blockIdx.x * kTrackPointsT + threadIdx.x;
+    if (k >= min(nsel[m], kcap)) return;
+    out[(size_t)c * kcap + k] = sel_point(sel[(size_t)m * kcap + k], sc);
+}
+
+void launch_track_points(hipStream_t st, const uint32_t *sel, const int *nsel, int kcap, int img0, int ncams, const float *scale,
+                         int nlevels, float2 *out)
+{
+    if (kcap < 1 || ncams < 1) return;
+    hipLaunchKernelGGL(k_track_points, dim3((kcap + kTrackPointsT - 1) / kTrackPointsT, ncams), dim3(kTrackPointsT), 0, st, sel, nsel,
+                       kcap, img0, UndistScales(scale, nlevels), out);
+}
+
+// The ordered stream compaction of camera blockIdx.y's validity bytes (each 0 or 1, as k_track_project writes them).  Workgroup b
+// serves candidates b * 256 .. b * 256 + 255 and counts the kept ones before them itself: valid[c * n .. c * n + b * 256) in
+// 16-byte loads from the first 16-byte boundary of the row on (the up to 15 bytes in front of it and as many behind the last
+// whole load byte by byte), a wave reduction and four partials through LDS -- at most n bytes, from L2, so n * n / 512 per
+// camera.  Its own 256 flags are ranked by a ballot per wave.  No workgroup waits on another; the last one of a camera has the
+// camera's total.
+__global__ __launch_bounds__(kTrackCompactT) void k_track_compact(int n, const uint8_t *__restrict__ valid, const float2 *__restrict__ xy,
+                                                                  const TrBest *__restrict__ best, TrRow *__restrict__ rows,
+                                                                  int32_t *__restrict__ n_proj)
+{
+    __shared__ int before[kTrackCompactT / 64], kept[kTrackCompactT / 64];
+    const int c = blockIdx.y, b = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    if (b * kTrackCompactT >= n) return;   // (uniform over the workgroup)
+    const size_t row = (size_t)c * n;
+    const uint8_t *p = valid + row;
+    const int end = b * kTrackCompactT;    // a multiple of 16: the head and the tail below are 16 bytes together, or none
+    const int head = end ? (int)((16 - (reinterpret_cast<uintptr_t>(p) & 15)) & 15) : 0;
+    const int nvec = (end - head) >> 4, tail = head + (nvec << 4);
+    int s = 0;
+    if (t < head) s = p[t];
+    const uint4 *v = reinterpret_cast<const uint4 *>(p + head);
+    for (int j = t; j < nvec; j += kTrackCompactT) {
+        const uint4 q = v[j];
+        s += __popc(q.x) + __popc(q.y) + __popc(q.z) + __popc(q.w);
+    }
+    if (tail + t < end) s += p[tail + t];
+    for (int o = 32; o >= 1; o >>= 1) s += __shfl_xor(s, o, 64);
+
+    const int i = end + t;
+    const bool keep = i < n && p[i] != 0;
+    const unsigned long long mask = __ballot(keep);
+    if (lane == 0) {
+        before[wave] = s;
+        kept[wave] = __popcll(mask);
+    }
+    __syncthreads();
+    int at = 0, total = 0;
+    for (int w = 0; w < kTrackCompactT / 64; w++) {
+        at += before[w] + (w < wave ? kept[w] : 0);
+        total += before[w] + kept[w];
+    }
+    if (keep) {
+        const float2 q = xy[row + i];
+        const TrBest r = best[row + i];
+        rows[row + lane_rank(mask, at)] = TrRow{i, q.x, q.y, r.kp, r.dist};
+    }
+    if (b == (int)gridDim.x - 1 && t == 0) n_proj[c] = total;
+}
+
+void launch_track_compact(hipStream_t st, int ncams, int n, const uint8_t *valid, const float2 *xy, const TrBest *best, TrRow *rows,
+                          int32_t *n_proj)
+{
+    if (n < 1) return;
+    hipLaunchKernelGGL(k_track_compact, dim3((n + kTrackCompactT - 1) / kTrackCompactT, ncams), dim3(kTrackCompactT), 0, st, n, valid, xy,
+                       best, rows, n_proj);
 }
 
 }  // namespace mcorb

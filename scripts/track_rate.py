@@ -7,7 +7,18 @@ machine and inputs: 5 map entries of 3000 l_ids that name about 10 000 distinct 
              of the queries (8 + 1) and of the results (8);
   host only  the same call on the host-only store, on one thread.  (The reference runs one thread per camera.)
 The two are timed in alternating runs, `reps` each after a warm-up; medians are reported.  bench.py times none of this.
-    python scripts/track_rate.py [--reps 5] [--out profiles/track_rate.json]"""
+    python scripts/track_rate.py [--reps 5] [--out profiles/track_rate.json]
+
+--leg slot: the frame comes from a rig slot (mcorb_lmap_track_rig_frame).  The same rig and counts; the keypoints are those of an
+extraction job on the synthetic rig frame, the landmarks are back-projected from those keypoints through the camera that saw them
+(a quarter behind the rig), their descriptors the keypoints' with up to 24 bits flipped.  Timed in alternating runs:
+  readback_track   Rig.features of the four images, the reshape to n x 2 arrays, LocalMap.track: what a caller does without the
+                   slot entry;
+  track            LocalMap.track on those arrays;
+  track_rig_frame  LocalMap.track_rig_frame (only where the library has it: --tree names a checkout built from another commit,
+                   whose package is imported instead of this one, to time the first two there).
+With a library built with -DMCORB_TRACK_PROF the host phases of the last two are recorded as well.
+    python scripts/track_rate.py --leg slot [--tree DIR] [--reps 5] [--out FILE]"""
 import argparse
 import json
 import os
@@ -74,12 +85,120 @@ def side(mcorb, device, w):
     return lm
 
 
+def slot_workload(mcorb, rig):
+    """-> (view as a dict, points, descriptors, lids, the frame's arrays as Rig.features gives them)"""
+    import track_cases as T
+    rng = np.random.default_rng(37)
+    cams = [T.cam(t=(1.5 * c, 0.0, 0.0), fx=700.0, fy=700.0, u0=COLS / 2, v0=ROWS / 2) for c in range(CAMS)]
+    v = T.view(cams, COLS, ROWS)
+    feats = [rig.features(c) for c in range(CAMS)]
+    pts, desc = [], []
+    for c in range(CAMS):
+        _, k, d = feats[c]
+        z = rng.uniform(2.0, 10.0, len(k))
+        z[rng.random(len(k)) < 0.25] *= -1.0                            # behind the rig: dropped from every camera
+        pts.append(np.stack([(k["x"] - COLS / 2) / 700.0 * z + 1.5 * c, (k["y"] - ROWS / 2) / 700.0 * z, z], axis=1))
+        d = d.copy()
+        flips = rng.integers(0, 256, (len(k), 24))
+        for j in range(24):
+            on = rng.random(len(k)) < 0.5
+            d[on, flips[on, j] // 8] ^= (1 << (flips[on, j] % 8)).astype(np.uint8)
+        desc.append(d)
+    pts, desc = np.concatenate(pts), np.concatenate(desc)
+    n = len(pts)
+    lids = []
+    for e in range(ENTRIES):
+        w = (np.arange(LIDS_PER_ENTRY) * 3 + e * (n - LIDS_PER_ENTRY) // (ENTRIES - 1) + rng.integers(0, 3, LIDS_PER_ENTRY)) % n
+        w[rng.random(LIDS_PER_ENTRY) < 0.05] = -1
+        lids.append(w)
+    return v, pts, desc, np.concatenate(lids).astype(np.int32)
+
+
+def readback(rig):
+    xy, ds = [], []
+    for c in range(CAMS):
+        _, k, d = rig.features(c)
+        xy.append(np.ascontiguousarray(np.stack([k["x"], k["y"]], axis=1), np.float32))
+        ds.append(d)
+    return xy, ds
+
+
+def slot_leg(mcorb, a):
+    import ctypes
+    import kfdb_cases
+    import track_cases as T
+    rig = mcorb.Rig(CAMS, COLS, ROWS, 1, 1, nfeatures=KEYPOINTS)
+    rig.upload([mcorb.synth_rig_frame(0, CAMS, c, COLS, ROWS) for c in range(CAMS)])
+    rig.extract(CAMS)
+    v, pts, desc, lids = slot_workload(mcorb, rig)
+    view = T.to_view(mcorb, v)
+    lm = mcorb.LocalMap(mcorb.ORBVocabulary(device=0).create(**kfdb_cases.vocabulary()), device=0, max_landmarks=len(pts), max_candidates=len(pts))
+    lm.set(np.arange(len(pts), dtype=np.int32), pts, np.zeros_like(pts), desc)
+    xy, ds = readback(rig)
+    has_slot = hasattr(lm, "track_rig_frame")
+    try:
+        phases_fn = lm.L.mcorb_lmap_track_phases
+    except AttributeError:
+        phases_fn = None
+
+    def phases():
+        us = (ctypes.c_float * 5)()
+        phases_fn(lm.h, us)
+        return list(us)
+
+    legs = ["readback_track", "track"] + (["track_rig_frame"] if has_slot else [])
+    t = {k: [] for k in legs}
+    kus = {k: [] for k in legs}
+    ph = {k: [] for k in legs}
+    res, same = {}, True
+    for rep in range(a.reps + 1):                                      # alternating; the first round is the warm-up
+        for k in legs:
+            t0 = time.perf_counter()
+            if k == "readback_track":
+                xy_, ds_ = readback(rig)
+                res[k] = lm.track(view, xy_, ds_, lids)
+            elif k == "track":
+                res[k] = lm.track(view, xy, ds, lids)
+            else:
+                res[k] = lm.track_rig_frame(view, rig, 0, lids)
+            t[k].append((time.perf_counter() - t0) * 1e3)
+            kus[k].append(lm.last_track_timing4() if has_slot else lm.last_track_timing())
+            if phases_fn is not None:
+                ph[k].append(phases())
+        same = same and all(T.as_lists(res[k]) == T.as_lists(res["track"]) for k in legs)
+    r = res["track"]
+    out = {"tree": os.path.abspath(a.tree or ROOT), "cores": len(os.sched_getaffinity(0)), "cameras": CAMS, "image": [COLS, ROWS],
+           "keypoints_per_camera": [len(x) for x in xy], "landmarks": int(len(pts)), "lids": int(len(lids)),
+           "candidates": int(r.n_candidates), "pairs": int(r.n_candidates) * CAMS, "queries_per_camera": [len(p) for p in r.proj_lid],
+           "matched_per_camera": [int((b >= 0).sum()) for b in r.best_kp], "matches_per_camera": [len(m) for m in r.match_kp],
+           "legs_equal": bool(same)}
+    for k in legs:
+        vals = t[k][1:]
+        out["%s_ms" % k] = round(float(np.median(vals)), 3)
+        out["%s_ms_runs" % k] = [round(x, 3) for x in vals]
+        out["%s_kernel_us" % k] = [round(float(np.median([u[i] for u in kus[k][1:]])), 1) for i in range(len(kus[k][0]))]
+        if phases_fn is not None:
+            out["%s_host_phase_us" % k] = dict(zip(("candidate_walk", "submission", "wait", "deduplication", "output"),
+                                                   [round(float(np.median([p[i] for p in ph[k][1:]])), 1) for i in range(5)]))
+    print(json.dumps(out))
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump(out, f, indent=1)
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--leg", default="stores", choices=["stores", "slot"])
+    ap.add_argument("--tree", default=None, help="a checkout whose package is timed instead of this one's (--leg slot)")
     a = ap.parse_args()
+    if a.tree:
+        sys.path.insert(0, os.path.abspath(a.tree))
     import mcorb
+    if a.leg == "slot":
+        slot_leg(mcorb, a)
+        sys.exit(0)
     import track_cases as T
     w = workload()
     view = T.to_view(mcorb, w["view"])
