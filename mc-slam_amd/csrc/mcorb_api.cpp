@@ -371,6 +371,9 @@ static int copy_plane(mcorb_rig *r, int slot, int m, int level, bool blurred, ui
     if (!s->d_blur) {       // reference mode does not even allocate them (k_describe_fused blurs around the keypoints only)
         TRY(s->d_blur.alloc((size_t)r->rig.max_images * g.imgBytes));
         HIPCHK(hipMemset(s->d_blur, 0, (size_t)r->rig.max_images * g.imgBytes));
+        // the fill runs on the null stream and the slot's streams are non-blocking: without this it can still be zeroing the
+        // buffer's head while k_blur below writes it (seen on 308x116 images: the first tile rows of level 0 came back zero)
+        HIPCHK(hipDeviceSynchronize());
     }
     if (!s->blur_valid) {   // ... nor writes them: make them now from the slot's pyramid
         launch_blur(s->st, s->d_pyr, s->d_blur, g, r->rig.max_images);

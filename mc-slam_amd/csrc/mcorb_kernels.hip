@@ -1752,8 +1752,13 @@ void launch_fast(hipStream_t st, const uint8_t *pyr, const Geom &g, int iniTh, i
     const int tileB = (rows * tp + 15) & ~15, scB = ((rows - 4) * tp + 15) & ~15;
     const size_t lds = 16 + (size_t)tileB + 16 + (size_t)scB + 16 + (size_t)cap * 2;
     dim3 grid(g.cells, nimg);
-    if (iniTh < 0) iniTh = 0;   // (pass 1's sign tests rely on thresholds in 0 .. 255; FAST thresholds are)
-    if (minTh < 0) minTh = 0;
+    // Threshold 0 runs as 1.  cv::FAST at 0 also calls a pixel with A = 1 a corner, but its score is A - 1 = 0, and the 3x3 NMS
+    // keeps a corner only where its score EXCEEDS its neighbours', whose score is 0 where they are no corners: it is never
+    // emitted and suppresses nobody, i.e. the keypoints at 0 are the keypoints at 1.  The score map here holds A, not A - 1,
+    // so at 0 such pixels would beat their non-corner neighbours and come out with response 0.  (Also: pass 1's sign tests
+    // rely on thresholds in 0 .. 255.)
+    if (iniTh < 1) iniTh = 1;
+    if (minTh < 1) minTh = 1;
     if (iniTh > 255) iniTh = 255;   // no pixel passes at 255 or above either way
     if (minTh > 255) minTh = 255;
     const auto kern = tp == 48 ? k_fast_cells<48> : tp == 64 ? k_fast_cells<64> : k_fast_cells<80>;

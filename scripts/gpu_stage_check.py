@@ -5,6 +5,7 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 import numpy as np
 import mcorb
 import oracle_lib as O
+import stage_cases as S
 
 W, H, C, N = (int(a) for a in (sys.argv[1:5] + ["1280", "720", "4", "2000"][len(sys.argv) - 1:]))
 imgs = [mcorb.synth_rig_frame(0, C, c, W, H) for c in range(C)]
@@ -16,23 +17,13 @@ ex = O.OracleExtractor(N)
 ok = True
 descs = []
 for c in range(C):
-    mono, k, d = ex(imgs[c])
-    for l in range(8):
-        a = rig.level(c, l); b = ex.level(l)
-        if not np.array_equal(a, b):
-            ok = False; print("cam", c, "level", l, "pyramid mismatch", (a != b).sum())
-        a = rig.level(c, l, blurred=True); b = ex.blurred(l)
-        if b is not None and not np.array_equal(a, b):
-            ok = False; print("cam", c, "level", l, "blur mismatch", (a != b).sum())
-        gx, gy, gr = rig.candidates(c, l); ox, oy, orr = ex.candidates(l)
-        if not (np.array_equal(gx, ox.astype(np.int32)) and np.array_equal(gy, oy.astype(np.int32)) and np.array_equal(gr, orr.astype(np.int32))):
-            ok = False; print("cam", c, "level", l, "candidates mismatch", len(gx), len(ox))
-    m2, k2, d2 = rig.features(c)
-    descs.append(d)
-    same_k = len(k) == len(k2) and all(np.array_equal(k[f], k2[f]) for f in k.dtype.names)
-    same_d = d.shape == d2.shape and np.array_equal(d, d2)
-    print("cam", c, "n", len(k), len(k2), "mono", mono, m2, "kps", same_k, "desc", same_d)
-    ok &= same_k and same_d and mono == m2
+    exp = S.oracle_stages(ex, imgs[c])          # the comparison of tests/test_gpu_stages.py: first differing element per stage
+    diffs = S.diff_image(rig, c, exp)
+    for d in diffs:
+        print("cam", c, d)
+    descs.append(exp["desc"])
+    print("cam", c, "n", len(exp["kps"]), "mono", exp["mono"], "stages equal" if not diffs else "%d stages differ" % len(diffs))
+    ok &= not diffs
 t = time.time(); rig.match(1); print("match ms", (time.time() - t) * 1e3, rig.timing())
 for i in range(C - 1):
     for j in range(i + 1, C):
