@@ -891,11 +891,15 @@ typedef struct mcorb_track_out {
  *    with a match k, the first entry whose keypoint has the same ((int)pt.x, (int)pt.y) is looked up; none: the triple is
  *    appended; one whose recorded dist is greater: it is erased and the triple appended; otherwise nothing.  (The reference
  *    compares with bestDists[k], an element of a vector that was only reserved and never written when the entry found is another
- *    keypoint of the same pixel; here the found entry's own distance is compared.  Keypoint coordinates must convert to int.)
- * A device store runs 2 in k_track_project, 3 + 4 in k_track_match and the compaction of every camera's kept candidates, in
- * candidate order, in k_track_compact, in one submission whose rows land in host-mapped memory; 1 and 5 run on the host.  A
- * host-only store runs the same header serially; the results are equal bit for bit.  No landmark is changed (the candidate walk uses the store's per-slot stamps, scratch
- * that no call reads as state).
+ *    keypoint of the same pixel; here the found entry's own distance is compared.)  (int) of a coordinate is truncation toward
+ *    zero for |v| < 2^31 and INT32_MIN otherwise, a NaN included, so every float has a pixel.  The list never holds two entries
+ *    of one pixel and an entry is replaced only by a strictly smaller distance, the replacement being appended: what is left is,
+ *    per pixel, the query with the least (dist, place in candidate order), and the list holds these in candidate order.
+ * A device store runs 2 in k_track_project, 3 + 4 in k_track_match, the compaction of every camera's kept candidates, in
+ * candidate order, in k_track_compact, and 5 in that closed form in k_track_dedup_min / _win / _emit, in one submission whose
+ * rows and matches land in host-mapped memory; 1 runs on the host.  A host-only store runs the same header serially and keeps
+ * the list of 5 as the reference has it; the results are equal bit for bit.  No landmark is changed (the candidate walk uses the
+ * store's per-slot stamps, scratch that no call reads as state).
  * Before anything runs: MCORB_E_ARG for view->ncams outside 1 .. MCORB_MAX_CAMS, a frame of another camera count, a negative
  * n_kp, max_hamming or capacity, a NULL array with a non-zero count, an id other than -1 outside the store; MCORB_E_STATE for a
  * candidate without a point or without a descriptor; MCORB_E_CAP for more candidates than max_candidates.  Afterwards:
@@ -922,6 +926,26 @@ int mcorb_lmap_last_track_timing(mcorb_lmap *m, float us[2]);
 /* the same for all four kernels of the last call: k_track_points (0 after mcorb_lmap_track, which does not run it),
  * k_track_project, k_track_match, k_track_compact; a call that launches nothing leaves them */
 int mcorb_lmap_last_track_timing4(mcorb_lmap *m, float us[4]);
+/* the four above and, us[4], the de-duplication: the clear of its table and its three kernels */
+int mcorb_lmap_last_track_timing5(mcorb_lmap *m, float us[5]);
+/* The asynchronous pair.  mcorb_lmap_track_submit / mcorb_lmap_track_rig_frame_submit do everything mcorb_lmap_track /
+ * mcorb_lmap_track_rig_frame do up to and excluding the synchronisation -- every refusal above with the same code, the candidate
+ * walk, the copy up, every launch -- and return; want_pts: whether the wait may be given a match_pt.  The caller's arrays (lids,
+ * kp_xy, desc, the view) may be changed or freed as soon as the call returns.  A host-only store runs the serial path to its end
+ * and keeps the result.  A call without candidates is pending too.  A refused submission leaves nothing pending.
+ * mcorb_lmap_track_wait synchronises, reads the event times and writes out (the capacities and arrays of mcorb_lmap_track; a
+ * match_pt after want_pts = 0 is MCORB_E_ARG), with the same MCORB_E_CAP rule: every count set, no array written.  Whatever it
+ * returns, nothing is pending afterwards.  Without a pending call: MCORB_E_STATE.
+ * While a call is pending every other entry on the store -- a second submission included -- returns MCORB_E_STATE and changes
+ * nothing; the mcorb_lmap_last_*timing* calls answer, and mcorb_lmap_destroy waits for the stream first.  Between the submission and
+ * the wait of a slot entry the caller must not submit a job on the slot, as during mcorb_lmap_track_rig_frame; the slot must be
+ * idle at the submission (MCORB_E_STATE).  A store is used by one thread at a time across a pair.
+ * The synchronous entries are a submission and its wait over the same code. */
+int mcorb_lmap_track_submit(mcorb_lmap *m, const mcorb_track_view *view, const mcorb_track_frame *frame, const int32_t *lids, int n_lids,
+                            double max_d2, int max_hamming, int want_pts);
+int mcorb_lmap_track_rig_frame_submit(mcorb_lmap *m, const mcorb_track_view *view, mcorb_rig *r, int slot, int frame, const int32_t *lids,
+                                      int n_lids, double max_d2, int max_hamming, int want_pts);
+int mcorb_lmap_track_wait(mcorb_lmap *m, mcorb_track_out *out);
 
 /* ------------------------------------------------------------------------- */
 /* Host stages exposed for the CPU test-suite (no device needed)              */
@@ -948,6 +972,9 @@ int mcorb_host_geometry(const mcorb_params *p, int w, int h, int32_t *six_per_le
 int mcorb_host_triangulate(const double *x, const double *P, int nv, double X[3]);
 /* the same, also giving the null-vector solver's exit (the codes of mcorb_dev_triangulate_selftest) */
 int mcorb_host_triangulate_branch(const double *x, const double *P, int nv, double X[3], int32_t *branch);
+/* the pixel coordinate of a keypoint coordinate as the de-duplication of mcorb_lmap_track takes it (step 5): truncation toward zero
+ * for |v| < 2^31, INT32_MIN otherwise, a NaN included.  The function the host tail and k_track_dedup_min share */
+int32_t mcorb_host_track_pixel(float v);
 
 /* ------------------------------------------------------------------------- */
 /* Synthetic input; host utility, see csrc/mcorb_synth.c       */

@@ -1272,6 +1272,13 @@ class LocalMap:
         (image_kps: an n x 2 float array, or keypoint records with x and y); descs: per camera n x 32 bytes; caps: (projected,
         matches) output sizes per camera, by default what cannot be exceeded; a McorbError of this call carries n_candidates,
         n_proj and n_match as the call left them"""
+        f, arrays = self._track_frame(kps, descs)     # (arrays: what f points into, alive across the call)
+        return self._track(f.ncams, lids, caps, lambda lids, o: self.L.mcorb_lmap_track(
+            self.h, C.byref(view), C.byref(f), lids.ctypes.data, len(lids), float(max_d2), int(max_hamming), C.byref(o)))
+
+    @staticmethod
+    def _track_frame(kps, descs):
+        """-> (the mcorb_track_frame of track's kps / descs, the arrays it points into)"""
         ncams = len(kps)
         if not 1 <= ncams <= _lib.MAX_CAMS or len(descs) != ncams:
             raise ValueError("track: 1 .. %d cameras, one keypoint and one descriptor array each" % _lib.MAX_CAMS)
@@ -1286,8 +1293,7 @@ class LocalMap:
         f.ncams = ncams
         for c in range(ncams):
             f.n_kp[c], f.kp_xy[c], f.desc[c] = len(xy[c]), xy[c].ctypes.data, ds[c].ctypes.data
-        return self._track(ncams, lids, caps, lambda lids, o: self.L.mcorb_lmap_track(
-            self.h, C.byref(view), C.byref(f), lids.ctypes.data, len(lids), float(max_d2), int(max_hamming), C.byref(o)))
+        return f, (xy, ds)
 
     def track_rig_frame(self, view, rig, frame, lids, slot=0, max_d2=10000.0, max_hamming=20, caps=None):
         """track() on frame `frame` of the last extraction job of a rig slot, read where the job left it: camera c is image
@@ -1300,16 +1306,23 @@ class LocalMap:
 
     def _track(self, ncams, lids, caps, call):
         lids = np.ascontiguousarray(lids, np.int32).reshape(-1)
-        cap_p, cap_m = caps if caps is not None else (len(lids), len(lids))
+        return self._track_out(ncams, len(lids), caps, True, lambda o: call(lids, o))
+
+    def _track_out(self, ncams, n_lids, caps, want_pts, call):
+        """the output arrays of a tracking call, call(mcorb_track_out) -> code, and the TrackResult (or the McorbError with the
+        call's counts)"""
+        cap_p, cap_m = caps if caps is not None else (n_lids, n_lids)
         n1, n2 = ncams * max(cap_p, 1), ncams * max(cap_m, 1)
         r = dict(proj_lid=np.zeros(n1, np.int32), proj_xy=np.zeros((n1, 2), np.float32), best_kp=np.zeros(n1, np.int32),
                  best_dist=np.zeros(n1, np.int32), match_kp=np.zeros(n2, np.int32), match_lid=np.zeros(n2, np.int32),
-                 match_dist=np.zeros(n2, np.int32), match_pt=np.zeros((n2, 3)))
+                 match_dist=np.zeros(n2, np.int32))
+        if want_pts:
+            r["match_pt"] = np.zeros((n2, 3))
         o = _lib.TrackOut()
         o.cap_proj, o.cap_match = cap_p, cap_m
         for k, a in r.items():
             setattr(o, k, a.ctypes.data)
-        code = call(lids, o)
+        code = call(o)
         n_proj, n_match = list(o.n_proj[:ncams]), list(o.n_match[:ncams])
         if code != _lib.OK:
             try:
@@ -1318,9 +1331,35 @@ class LocalMap:
                 e.n_candidates, e.n_proj, e.n_match = o.n_candidates, n_proj, n_match
                 raise
         out = {k: [r[k][c * cap_p:c * cap_p + n_proj[c]].copy() for c in range(ncams)] for k in ("proj_lid", "proj_xy", "best_kp", "best_dist")}
-        out.update({k: [r[k][c * cap_m:c * cap_m + n_match[c]].copy() for c in range(ncams)]
+        out.update({k: [r[k][c * cap_m:c * cap_m + n_match[c]].copy() for c in range(ncams)] if k in r else None
                     for k in ("match_kp", "match_lid", "match_dist", "match_pt")})
         return TrackResult(n_candidates=o.n_candidates, **out)
+
+    def track_submit(self, view, kps, descs, lids, max_d2=10000.0, max_hamming=20, want_pts=True):
+        """track() up to and excluding the wait for the device: every refusal, the candidate walk, the copy up and every launch; then
+        it returns and track_wait() gives the result.  kps, descs, lids and view may be changed at once.  A host-only store runs
+        the whole call here and keeps the result.  Until track_wait() every other call on the store raises MCORB_E_STATE (the
+        last_*timing* calls and close() excepted); a refused submission leaves nothing pending.  want_pts=False: no match_pt"""
+        f, arrays = self._track_frame(kps, descs)     # (arrays: what f points into, alive across the call)
+        lids = np.ascontiguousarray(lids, np.int32).reshape(-1)
+        _lib.check(self.L.mcorb_lmap_track_submit(self.h, C.byref(view), C.byref(f), lids.ctypes.data, len(lids), float(max_d2),
+                                                  int(max_hamming), int(bool(want_pts))))
+        self._submitted = (f.ncams, len(lids), bool(want_pts))
+
+    def track_rig_frame_submit(self, view, rig, frame, lids, slot=0, max_d2=10000.0, max_hamming=20, want_pts=True):
+        """track_rig_frame() as track_submit() is track(): no job may be submitted on the slot until track_wait() has returned"""
+        lids = np.ascontiguousarray(lids, np.int32).reshape(-1)
+        _lib.check(self.L.mcorb_lmap_track_rig_frame_submit(self.h, C.byref(view), rig.h_rig if rig is not None else None, slot, frame,
+                                                            lids.ctypes.data, len(lids), float(max_d2), int(max_hamming),
+                                                            int(bool(want_pts))))
+        self._submitted = (view.ncams, len(lids), bool(want_pts))
+
+    def track_wait(self, caps=None):
+        """the TrackResult of the submitted call (match_pt None after want_pts=False); a McorbError carries the counts as track()'s
+        does.  Whatever happens, nothing is pending afterwards; without a submitted call: MCORB_E_STATE"""
+        ncams, n_lids, want_pts = getattr(self, "_submitted", None) or (1, 0, False)
+        self._submitted = None
+        return self._track_out(ncams, n_lids, caps, want_pts, lambda o: self.L.mcorb_lmap_track_wait(self.h, C.byref(o)))
 
     def last_track_timing(self):
         """(microseconds of the last k_track_project launch, of the last k_track_match launch); a device store"""
@@ -1335,12 +1374,20 @@ class LocalMap:
         _lib.check(self.L.mcorb_lmap_last_track_timing4(self.h, us))
         return us[0], us[1], us[2], us[3]
 
+    def last_track_timing5(self):
+        """last_track_timing4() and, last, the microseconds of the de-duplication: the clear of its table, k_track_dedup_min,
+        k_track_dedup_win and k_track_dedup_emit; a device store"""
+        us = (C.c_float * 5)()
+        _lib.check(self.L.mcorb_lmap_last_track_timing5(self.h, us))
+        return tuple(us)
+
 
 class TrackResult:
-    """what LocalMap.track returns, every member a list with one array per camera.  The projected landmarks in candidate order:
+    """what LocalMap.track and LocalMap.track_wait return, every member a list with one array per camera.  The projected landmarks in candidate order:
     proj_lid, proj_xy (the projected keypoint's pt, float32) and, per projected query before the serial part, best_kp (-1: none)
     and best_dist (10000 with -1).  After the de-duplication, in the reference's order: match_kp (bestMatches as keypoint
-    indices), match_lid (bestMatchLandmarkIds), match_dist and match_pt (bestMatchLandmarks: the store's points).  n_candidates:
+    indices), match_lid (bestMatchLandmarkIds), match_dist and match_pt (bestMatchLandmarks: the store's points; None for a call
+    submitted with want_pts=False).  n_candidates:
     the distinct landmarks of the call"""
 
     def __init__(self, **kw):

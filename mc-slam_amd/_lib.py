@@ -242,6 +242,11 @@ SIGNATURES = {
     "mcorb_lmap_track_rig_frame": (_i, [_vp, C.POINTER(TrackView), _vp, _i, _i, _vp, _i, C.c_double, _i, C.POINTER(TrackOut)]),
     "mcorb_lmap_last_track_timing": (_i, [_vp, C.POINTER(_f)]),
     "mcorb_lmap_last_track_timing4": (_i, [_vp, C.POINTER(_f)]),
+    "mcorb_lmap_last_track_timing5": (_i, [_vp, C.POINTER(_f)]),
+    "mcorb_lmap_track_submit": (_i, [_vp, C.POINTER(TrackView), C.POINTER(TrackFrame), _vp, _i, C.c_double, _i, _i]),
+    "mcorb_lmap_track_rig_frame_submit": (_i, [_vp, C.POINTER(TrackView), _vp, _i, _i, _vp, _i, C.c_double, _i, _i]),
+    "mcorb_lmap_track_wait": (_i, [_vp, C.POINTER(TrackOut)]),
+    "mcorb_host_track_pixel": (C.c_int32, [_f]),
     "mcorb_host_geometry": (_i, [C.POINTER(Params), _i, _i, _vp]),
     "mcorb_synth_rig_frame": (_i, [C.c_uint32, _i, _i, _i, _i, _vp, _i]),
 }

@@ -199,5 +199,12 @@ void launch_track_points(hipStream_t st, const uint32_t *sel, const int *nsel, i
 // n_proj[c]; rows / n_proj may be host-mapped pinned memory
 void launch_track_compact(hipStream_t st, int ncams, int n, const uint8_t *valid, const float2 *xy, const TrBest *best, TrRow *rows,
                           int32_t *n_proj);
+// k_track_dedup_min, k_track_dedup_win, k_track_dedup_emit: per camera, of the candidates with valid[c * n + i] and a match, the one
+// with the least (dist, i) per pixel of the matched keypoint, in candidate order -> matches[c * n + 0 .. n_match[c]) and
+// n_match[c] (may be host-mapped).  owner / val: ncams << tr_dedup_log2(n) slots each, every byte 0xff; slot (int32) and win (bytes):
+// ncams * n each, scratch
+constexpr int kTrackDedupT = 256;     // one lane per (camera, candidate)
+void launch_track_dedup(hipStream_t st, const TrFrame &frame, int ncams, const float2 *kp_xy, int n, const uint8_t *valid, const TrBest *best,
+                        uint32_t *owner, unsigned long long *val, int32_t *slot, uint8_t *win, TrMatch *matches, int32_t *n_match);
 
 }  // namespace mcorb

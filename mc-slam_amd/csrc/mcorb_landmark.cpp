@@ -345,7 +345,7 @@ int mcorb_lmap_observers(mcorb_lmap *m, const int32_t *lids, int n, int32_t *kf_
 
 int mcorb_lmap_last_landmark_timing(mcorb_lmap *m, float us[2])
 {
-    TRY(check_lmap(m, "lmap last_landmark_timing"));
+    TRY(check_lmap_handle(m, "lmap last_landmark_timing"));
     if (!us) return fail(MCORB_E_ARG, "lmap last_landmark_timing", "bad argument");
     std::lock_guard<std::mutex> lk(m->mu);
     us[0] = m->us_observe;

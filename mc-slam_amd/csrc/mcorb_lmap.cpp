@@ -151,6 +151,7 @@ int mcorb_lmap_create(mcorb_vocab *v, int device, int max_landmarks, int max_can
         TRY(m->ev10.create(hipEventDefault));
         TRY(m->ev11.create(hipEventDefault));
         TRY(m->ev12.create(hipEventDefault));
+        TRY(m->ev13.create(hipEventDefault));
         TRY(m->best2.create());
         TRY(m->d_geom.alloc(N * 6));
         TRY(m->d_desc.alloc(N * 32));
@@ -385,7 +386,7 @@ int mcorb_lmap_search(mcorb_lmap *m, const mcorb_lmap_view *view, const int32_t 
 
 int mcorb_lmap_last_timing(mcorb_lmap *m, float us[2], int *n_candidates)
 {
-    TRY(check_lmap(m, "lmap last_timing"));
+    TRY(check_lmap_handle(m, "lmap last_timing"));
     if (!us) { set_error("lmap last_timing: bad argument"); return MCORB_E_ARG; }
     std::lock_guard<std::mutex> lk(m->mu);
     us[0] = m->us_cull;

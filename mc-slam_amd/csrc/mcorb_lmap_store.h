@@ -2,6 +2,7 @@
 // (mcorb_mapping.cpp), by the calls that keep its landmarks up to date (mcorb_landmark.cpp) and by fast tracking (mcorb_track.cpp).
 #pragma once
 #include <algorithm>
+#include <atomic>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -88,6 +89,29 @@ struct mcorb_lmap {
     mcorb::HostBuf<int32_t> h_tracknproj;
     mcorb::Event ev8, ev9, ev10, ev11, ev12;   // in front of k_track_project | match | compact | behind it | in front of k_track_points
     float us_track_points = 0.f, us_track_project = 0.f, us_track_match = 0.f, us_track_compact = 0.f;
+    // the de-duplication on the device: per camera the arg-min table (owner, val: cleared in every submission), per (camera,
+    // candidate) the slot and the winner flag, and what the host reads: the matches and their counts, host-mapped as the rows are
+    mcorb::DevBuf<uint32_t> d_trackowner;
+    mcorb::DevBuf<unsigned long long> d_trackval;
+    mcorb::DevBuf<int32_t> d_trackslot;
+    mcorb::DevBuf<uint8_t> d_trackwin;
+    mcorb::HostBuf<mcorb::TrMatch> h_trackmatch;
+    mcorb::HostBuf<int32_t> h_tracknmatch;
+    mcorb::Event ev13;                         // behind k_track_dedup_emit (ev11 is in front of the table's clear)
+    float us_track_dedup = 0.f;
+    // a tracking call that was submitted and not yet waited for (mcorb_lmap_track_submit .. mcorb_lmap_track_wait).  While
+    // track_pending is set every other entry refuses (check_lmap) and the scratch above belongs to the call.  launched: a
+    // device store has work on its stream; points: k_track_points is part of it.  A host-only store keeps its finished result in
+    // rows / matches
+    struct TrackCall {
+        int ncams = 0;
+        bool launched = false, points = false, want_pts = false;
+        std::vector<int> cand;
+        std::vector<mcorb::TrRow> rows;
+        std::vector<mcorb::TrMatch> matches;
+        int32_t n_proj[MCORB_MAX_CAMS] = {}, n_match[MCORB_MAX_CAMS] = {};
+    } track_call;
+    std::atomic<bool> track_pending{false};
 #ifdef MCORB_TRACK_PROF
     float us_track_phase[5] = {};   // the last call's host phases: candidate walk, submission, wait, de-duplication, output
 #endif
@@ -100,9 +124,21 @@ inline int next_tick(mcorb_lmap *m)
     return ++m->tick;
 }
 
-inline int check_lmap(const mcorb_lmap *m, const char *who)
+// the handle alone: the last_*timing* getters and the tracking pair itself
+inline int check_lmap_handle(const mcorb_lmap *m, const char *who)
 {
     if (!m) { mcorb::set_error(std::string(who) + ": bad argument"); return MCORB_E_ARG; }
+    return MCORB_OK;
+}
+
+// every other entry: no tracking call may be pending on the store
+inline int check_lmap(const mcorb_lmap *m, const char *who)
+{
+    TRY(check_lmap_handle(m, who));
+    if (m->track_pending.load()) {
+        mcorb::set_error(std::string(who) + ": a submitted tracking call has not been waited for");
+        return MCORB_E_STATE;
+    }
     return MCORB_OK;
 }
 

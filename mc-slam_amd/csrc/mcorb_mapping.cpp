@@ -440,7 +440,7 @@ int mcorb_lmap_depths(mcorb_lmap *m, const double Rcw[9], const double tcw[3], c
 
 int mcorb_lmap_last_triangulate_timing(mcorb_lmap *m, float us[2], int *n_launched, int *n_depth)
 {
-    TRY(check_lmap(m, "lmap last_triangulate_timing"));
+    TRY(check_lmap_handle(m, "lmap last_triangulate_timing"));
     if (!us) { set_error("lmap last_triangulate_timing: bad argument"); return MCORB_E_ARG; }
     std::lock_guard<std::mutex> lk(m->mu);
     us[0] = m->us_map_tri;

@@ -6,15 +6,19 @@
 //
 // The arithmetic is mcorb_track.h.  A device store runs the projection in k_track_project, the neighbour search with the
 // descriptor gate in k_track_match and the compaction in candidate order in k_track_compact, all in one submission: the points
-// and the landmarks' descriptors are read from the store's slots in HBM, the kept rows land in host-mapped memory, and the one
-// synchronisation is all the host waits for.  The frame comes from host arrays (mcorb_lmap_track: candidates, keypoints and
+// and the landmarks' descriptors are read from the store's slots in HBM, the kept rows and the matches land in host-mapped
+// memory, and the one synchronisation is all the host waits for.  The frame comes from host arrays (mcorb_lmap_track: candidates, keypoints and
 // descriptors go up as one pinned block in one copy) or from a rig slot (mcorb_lmap_track_rig_frame: only the candidates go up;
 // k_track_points rebuilds the keypoints from the slot's packed selection words, the descriptors are read where the extraction
-// job left them).  The host-only store runs the same header serially.  Both entries share the argument and candidate checks,
-// the submission and the host tail: the candidate walk and the order-dependent de-duplication run on the host.  The
-// reference's kd-tree search (FLANN, 4 trees, 64 checks) is approximate and un-vendored: the neighbours here are exact.  The
-// store's landmarks are only read: of the map object the call writes its own scratch and, as mcorb_lmap_search does, the
-// per-slot stamps of the candidate walk (tick / stamp), which no call reads as state.
+// job left them).  The de-duplication, serial in the reference, is a minimum per pixel and a compaction in candidate order
+// (mcorb_track.h, tr_dedup_value): k_track_dedup_min / _win / _emit run it behind k_track_match in the same submission, so the
+// host's part of a device call is the candidate walk in front and copies behind.  The host-only store runs the same header
+// serially and keeps the reference's list as it is.  Both entries share the argument and candidate checks, the submission and
+// the output.  A call is a submission and a wait: mcorb_lmap_track_submit / _rig_frame_submit return once everything is on the
+// store's stream, mcorb_lmap_track_wait synchronises and writes the outputs, and the synchronous entries are the two over the
+// same body.  The reference's kd-tree search (FLANN, 4 trees, 64 checks) is approximate and un-vendored: the neighbours here are
+// exact.  The store's landmarks are only read: of the map object the call writes its own scratch and, as mcorb_lmap_search
+// does, the per-slot stamps of the candidate walk (tick / stamp), which no call reads as state.
 #include <string.h>
 
 #include <chrono>
@@ -54,7 +58,11 @@ struct Phases {
 #ifdef MCORB_TRACK_PROF
     float *us;
     std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
-    explicit Phases(mcorb_lmap *m) : us(m->us_track_phase) { for (int k = 0; k < 5; k++) us[k] = 0.f; }
+    Phases(mcorb_lmap *m, bool reset) : us(m->us_track_phase)   // a submission starts the call's phases over, its wait adds to them
+    {
+        if (reset)
+            for (int k = 0; k < 5; k++) us[k] = 0.f;
+    }
     void mark(int k)
     {
         const auto now = std::chrono::steady_clock::now();
@@ -62,7 +70,7 @@ struct Phases {
         t = now;
     }
 #else
-    explicit Phases(mcorb_lmap *) {}
+    Phases(mcorb_lmap *, bool) {}
     void mark(int) {}
 #endif
 };
@@ -92,11 +100,6 @@ TrBest query_host(float x, float y, const KpRows &kp, int c, const uint8_t *kp_d
     return TrBest{(int32_t)top[key & 15u].k, (int32_t)(key >> 4)};
 }
 
-// an entry of the de-duplication's list.  What the search compares, the pixel ((int)pt.x, (int)pt.y) of the entry's keypoint, is
-// kept beside the list as one 64-bit key per entry: the scan reads 8 bytes an entry and stays in the first-level cache
-struct Triple { int32_t kp, lid, dist, cand; };
-inline uint64_t pixel_key(int px, int py) { return ((uint64_t)(uint32_t)px << 32) | (uint32_t)py; }
-
 size_t round32(size_t n) { return (n + 31) & ~(size_t)31; }
 
 void clear_counts(mcorb_track_out *out)
@@ -108,11 +111,8 @@ void clear_counts(mcorb_track_out *out)
 
 // ---- 1. what both entries refuse before anything runs, the frame apart: the arguments, then -- the caller holds the store's
 // lock -- the candidates ----
-int check_args(const mcorb_track_view *view, const int32_t *lids, int n_lids, int max_hamming, mcorb_track_out *out)
+int check_out(const mcorb_track_out *out)
 {
-    if (!view || !out || n_lids < 0 || (n_lids && !lids) || max_hamming < 0) return fail(MCORB_E_ARG, "bad argument");
-    clear_counts(out);
-    if (view->ncams < 1 || view->ncams > MCORB_MAX_CAMS) return fail(MCORB_E_ARG, "1 .. MCORB_MAX_CAMS cameras");
     const int cap_p = out->cap_proj, cap_m = out->cap_match;
     if (cap_p < 0 || cap_m < 0 || (cap_p && (!out->proj_lid || !out->proj_xy || !out->best_kp || !out->best_dist)) ||
         (cap_m && (!out->match_kp || !out->match_lid || !out->match_dist)))
@@ -120,8 +120,18 @@ int check_args(const mcorb_track_view *view, const int32_t *lids, int n_lids, in
     return MCORB_OK;
 }
 
-int candidates_of(mcorb_lmap *m, const int32_t *lids, int n_lids, mcorb_track_out *out, std::vector<int> &cand)
+// out: the synchronous entries'; a submission has none (NULL)
+int check_args(const mcorb_track_view *view, const int32_t *lids, int n_lids, int max_hamming, mcorb_track_out *out, bool with_out)
 {
+    if (!view || (with_out && !out) || n_lids < 0 || (n_lids && !lids) || max_hamming < 0) return fail(MCORB_E_ARG, "bad argument");
+    if (out) clear_counts(out);
+    if (view->ncams < 1 || view->ncams > MCORB_MAX_CAMS) return fail(MCORB_E_ARG, "1 .. MCORB_MAX_CAMS cameras");
+    return out ? check_out(out) : MCORB_OK;
+}
+
+int candidates_of(mcorb_lmap *m, const int32_t *lids, int n_lids, std::vector<int> &cand)
+{
+    cand.clear();
     for (int i = 0; i < n_lids; i++)
         if (lids[i] < -1 || lids[i] >= m->max_landmarks) return fail(MCORB_E_ARG, "landmark id outside the store");
     const int t = next_tick(m);
@@ -136,11 +146,11 @@ int candidates_of(mcorb_lmap *m, const int32_t *lids, int n_lids, mcorb_track_ou
         if (!(m->flags[l] & kHasDesc)) return fail(MCORB_E_STATE, "a candidate landmark has no descriptor");
     }
     if ((int)cand.size() > m->max_candidates) return fail(MCORB_E_CAP, "more candidates than max_candidates");
-    out->n_candidates = (int)cand.size();
     return MCORB_OK;
 }
 
-// ---- 2. per camera the kept candidates in candidate order: the projection and the query's result ----
+// ---- 2. per camera the kept candidates in candidate order -- the projection and the query's result -- and the de-duplicated
+// matches ----
 // a host-only store: mcorb_track.h serially
 void rows_on_host(const mcorb_lmap *m, const mcorb_track_view &view, const Frame &f, const std::vector<int> &cand, double max_d2,
                   int max_hamming, std::vector<TrRow> &rows, int32_t *n_proj)
@@ -161,6 +171,38 @@ void rows_on_host(const mcorb_lmap *m, const mcorb_track_view &view, const Frame
     }
 }
 
+// the de-duplication (querryEachFrame:380-415) of a host-only store: the reference's list as it is, serial per camera over the rows
+// with a match -> matches[c * nc + 0 .. n_match[c]).  What the search compares, the pixel of the entry's keypoint, is kept beside
+// the list as one 64-bit key per entry: the scan reads 8 bytes an entry and stays in the first-level cache
+void dedup_on_host(int C, int nc, const TrRow *rows, const int32_t *n_proj, const KpRows &kp, std::vector<TrMatch> &matches, int32_t *n_match)
+{
+    matches.resize((size_t)C * nc);
+    std::vector<TrMatch> list;
+    std::vector<uint64_t> keys;   // of the camera's list, entry by entry
+    for (int c = 0; c < C; c++) {
+        const TrRow *row = rows + (size_t)c * nc;
+        list.clear();
+        keys.clear();
+        for (int r = 0; r < n_proj[c]; r++) {
+            if (row[r].kp < 0) continue;
+            const TrRow &b = row[r];
+            const float *p = kp.pt(c, b.kp);
+            const uint64_t key = tr_pixel_key(p[0], p[1]);
+            size_t at = 0;
+            for (const size_t n = keys.size(); at < n && keys[at] != key; at++) {}
+            if (at < list.size()) {
+                if (!(list[at].dist > b.dist)) continue;
+                list.erase(list.begin() + (ptrdiff_t)at);
+                keys.erase(keys.begin() + (ptrdiff_t)at);
+            }
+            list.push_back(TrMatch{b.i, b.kp, b.dist});
+            keys.push_back(key);
+        }
+        n_match[c] = (int32_t)list.size();
+        std::copy(list.begin(), list.end(), matches.begin() + (ptrdiff_t)((size_t)c * nc));
+    }
+}
+
 // The sel / nsel of the slot's last extraction as a kernel may read them: the job's own view (Slot::ctl, as launch_undistort is
 // given it) -- but a later match job points ctl at the device mirror, which a small host-selected batch never filled: that
 // batch's words are in the host-mapped block
@@ -172,14 +214,19 @@ void slot_sel(const Slot &s, const uint32_t *&sel, const int *&nsel)
 }
 
 // a device store: one submission on the store's stream -- the candidates (and the host arrays' frame) up in one copy,
-// [k_track_points,] k_track_project, k_track_match, k_track_compact, no host step between them -- and one synchronisation.  The
-// rows and counts are in host-mapped memory then; the gathered points (want_pts) come down in the one result copy there is
-int rows_on_device(mcorb_lmap *m, const mcorb_track_view &view, const Frame &f, const std::vector<int> &cand, double max_d2,
-                   int max_hamming, bool want_pts, Phases &ph)
+// [k_track_points,] k_track_project, k_track_match, k_track_compact, the table's clear and the three kernels of the
+// de-duplication, no host step between them.  Once the stream has run them the rows, the matches and their counts are in
+// host-mapped memory; the gathered points (want_pts) come down in the one result copy there is.  Nothing of the caller's is
+// read after this returns: the arrays are in the pinned block
+int submit_on_device(mcorb_lmap *m, const mcorb_track_view &view, const Frame &f, const std::vector<int> &cand, double max_d2,
+                     int max_hamming, bool want_pts)
 {
     const int C = view.ncams, nc = (int)cand.size();
     const size_t rows = (size_t)C * nc;
     HIPCHK(hipSetDevice(m->device));
+    // A stale error of this thread is not this call's (Rig::execute does the same): whatever an earlier, unrelated HIP call left
+    // behind -- another object's destructor, an elapsed-time query -- would otherwise be reported by the checks behind the launches
+    (void)hipGetLastError();
     hipStream_t st = m->st;
     TrFrame tf;
     memset(&tf, 0, sizeof(tf));
@@ -200,6 +247,13 @@ int rows_on_device(mcorb_lmap *m, const mcorb_track_view &view, const Frame &f, 
     TRY(m->d_trackbest.grow(rows));
     TRY(m->h_trackrows.grow(rows, kHostMapped));
     TRY(m->h_tracknproj.grow(MCORB_MAX_CAMS, kHostMapped));
+    const size_t slots = (size_t)C << tr_dedup_log2(nc);
+    TRY(m->d_trackowner.grow(slots));
+    TRY(m->d_trackval.grow(slots));
+    TRY(m->d_trackslot.grow(rows));
+    TRY(m->d_trackwin.grow(rows));
+    TRY(m->h_trackmatch.grow(rows, kHostMapped));
+    TRY(m->h_tracknmatch.grow(MCORB_MAX_CAMS, kHostMapped));
     if (f.slot) TRY(m->d_trackkp.grow((size_t)C * kcap));
     if (want_pts) {
         TRY(m->d_trackpt.grow((size_t)nc * 3));
@@ -237,117 +291,145 @@ int rows_on_device(mcorb_lmap *m, const mcorb_track_view &view, const Frame &f, 
     launch_track_compact(st, C, nc, m->d_trackvalid, m->d_trackxy, m->d_trackbest, m->h_trackrows, m->h_tracknproj);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(m->ev11, st));
+    HIPCHK(hipMemsetAsync(m->d_trackowner, 0xff, slots * sizeof(uint32_t), st));
+    HIPCHK(hipMemsetAsync(m->d_trackval, 0xff, slots * sizeof(unsigned long long), st));
+    launch_track_dedup(st, tf, C, kp_xy, nc, m->d_trackvalid, m->d_trackbest, m->d_trackowner, m->d_trackval, m->d_trackslot, m->d_trackwin,
+                       m->h_trackmatch, m->h_tracknmatch);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(m->ev13, st));
     if (want_pts) HIPCHK(hipMemcpyAsync(m->h_trackpt, m->d_trackpt, (size_t)nc * 3 * sizeof(double), hipMemcpyDeviceToHost, st));
-    ph.mark(1);
-    HIPCHK(hipStreamSynchronize(st));
-    ph.mark(2);
-    float ms = 0.f;
-    m->us_track_points = 0.f;
-    if (f.slot) {
-        ev_elapsed(&ms, m->ev12, m->ev8);
-        m->us_track_points = ms * 1000.f;
-    }
-    ev_elapsed(&ms, m->ev8, m->ev9);
-    m->us_track_project = ms * 1000.f;
-    ev_elapsed(&ms, m->ev9, m->ev10);
-    m->us_track_match = ms * 1000.f;
-    ev_elapsed(&ms, m->ev10, m->ev11);
-    m->us_track_compact = ms * 1000.f;
     return MCORB_OK;
 }
 
-// ---- 3. the host tail, over a camera's rows [c * nc, c * nc + n_proj[c]): the projected lists as they are, the de-duplication
-// (querryEachFrame:380-415) over the rows with a match, serial per camera, and the outputs.  pts: [nc][3] of a device store ----
-int finish(const mcorb_lmap *m, int C, const std::vector<int> &cand, const TrRow *rows, const int32_t *n_proj, const KpRows &kp,
-           const double *pts, mcorb_track_out *out, Phases &ph)
+// ---- 3. a call's two halves, the frame checked; the caller holds the store's lock ----
+// everything up to and excluding the synchronisation: the candidates, then the whole call on a host-only store, the submission on
+// a device store.  A refusal leaves nothing behind: work that a failed submission put on the stream is waited for here
+int submit_body(mcorb_lmap *m, const mcorb_track_view *view, const Frame &f, const int32_t *lids, int n_lids, double max_d2,
+                int max_hamming, bool want_pts, mcorb_track_out *out)
 {
-    const int nc = (int)cand.size(), cap_p = out->cap_proj, cap_m = out->cap_match;
-    std::vector<std::vector<Triple>> lists((size_t)C);
-    std::vector<uint64_t> keys;   // of the camera's list, entry by entry
-    bool is_short = false;
-    for (int c = 0; c < C; c++) {
-        const TrRow *row = rows + (size_t)c * nc;
-        out->n_proj[c] = n_proj[c];
-        std::vector<Triple> &list = lists[c];
-        keys.clear();
-        for (int r = 0; r < n_proj[c]; r++) {
-            if (row[r].kp < 0) continue;
-            const TrRow &b = row[r];
-            const float *p = kp.pt(c, b.kp);
-            const uint64_t key = pixel_key((int)p[0], (int)p[1]);
-            size_t at = 0;
-            for (const size_t n = keys.size(); at < n && keys[at] != key; at++) {}
-            if (at < list.size()) {
-                if (!(list[at].dist > b.dist)) continue;
-                list.erase(list.begin() + (ptrdiff_t)at);
-                keys.erase(keys.begin() + (ptrdiff_t)at);
-            }
-            list.push_back(Triple{b.kp, cand[b.i], b.dist, b.i});
-            keys.push_back(key);
+    Phases ph(m, true);
+    mcorb_lmap::TrackCall &tc = m->track_call;
+    TRY(candidates_of(m, lids, n_lids, tc.cand));
+    if (out) out->n_candidates = (int)tc.cand.size();   // (the synchronous entries: set from here on, whatever follows)
+    ph.mark(0);
+    const int C = view->ncams, nc = (int)tc.cand.size();
+    tc.ncams = C;
+    tc.launched = tc.points = false;
+    tc.want_pts = want_pts;
+    memset(tc.n_proj, 0, sizeof(tc.n_proj));
+    memset(tc.n_match, 0, sizeof(tc.n_match));
+    if (!nc) return MCORB_OK;
+    if (m->device < 0) {
+        rows_on_host(m, *view, f, tc.cand, max_d2, max_hamming, tc.rows, tc.n_proj);
+        ph.mark(2);
+        dedup_on_host(C, nc, tc.rows.data(), tc.n_proj, f.kp, tc.matches, tc.n_match);
+        ph.mark(3);
+        return MCORB_OK;
+    }
+    const int r = submit_on_device(m, *view, f, tc.cand, max_d2, max_hamming, want_pts);
+    if (r != MCORB_OK) {
+        (void)hipStreamSynchronize(m->st);
+        return r;
+    }
+    tc.launched = true;
+    tc.points = f.slot != nullptr;
+    ph.mark(1);
+    return MCORB_OK;
+}
+
+// the synchronisation, the event times and the outputs: per camera the projected lists as the rows have them and the matches,
+// lid = cand[i].  pts: [nc][3] of a device store.  checked: out is a synchronous entry's, which check_args has seen and cleared
+int wait_body(mcorb_lmap *m, mcorb_track_out *out, bool checked)
+{
+    Phases ph(m, false);
+    const mcorb_lmap::TrackCall &tc = m->track_call;
+    const int C = tc.ncams, nc = (int)tc.cand.size();
+    const TrRow *rows = tc.rows.data();
+    const TrMatch *matches = tc.matches.data();
+    const int32_t *n_proj = tc.n_proj, *n_match = tc.n_match;
+    const double *pts = nullptr;
+    if (tc.launched) {
+        HIPCHK(hipSetDevice(m->device));
+        HIPCHK(hipStreamSynchronize(m->st));
+        ph.mark(2);
+        float ms = 0.f;
+        m->us_track_points = 0.f;
+        if (tc.points) {
+            ev_elapsed(&ms, m->ev12, m->ev8);
+            m->us_track_points = ms * 1000.f;
         }
-        out->n_match[c] = (int32_t)list.size();
-        if (n_proj[c] > cap_p || (int)list.size() > cap_m) is_short = true;
+        ev_elapsed(&ms, m->ev8, m->ev9);
+        m->us_track_project = ms * 1000.f;
+        ev_elapsed(&ms, m->ev9, m->ev10);
+        m->us_track_match = ms * 1000.f;
+        ev_elapsed(&ms, m->ev10, m->ev11);
+        m->us_track_compact = ms * 1000.f;
+        ev_elapsed(&ms, m->ev11, m->ev13);
+        m->us_track_dedup = ms * 1000.f;
+        rows = m->h_trackrows;
+        matches = m->h_trackmatch;
+        n_proj = m->h_tracknproj;
+        n_match = m->h_tracknmatch;
+        if (tc.want_pts) pts = m->h_trackpt;
     }
     ph.mark(3);
+    if (!checked) {
+        if (!out) return fail(MCORB_E_ARG, "bad argument");
+        clear_counts(out);
+        TRY(check_out(out));
+    }
+    if (out->match_pt && !tc.want_pts) return fail(MCORB_E_ARG, "match_pt of a call that was submitted without want_pts");
+    out->n_candidates = nc;
+    if (!nc) return MCORB_OK;
+    const int cap_p = out->cap_proj, cap_m = out->cap_match;
+    bool is_short = false;
+    for (int c = 0; c < C; c++) {
+        out->n_proj[c] = n_proj[c];
+        out->n_match[c] = n_match[c];
+        if (n_proj[c] > cap_p || n_match[c] > cap_m) is_short = true;
+    }
     if (is_short) return fail(MCORB_E_CAP, "output too small");
     for (int c = 0; c < C; c++) {
         const TrRow *row = rows + (size_t)c * nc;
+        const TrMatch *mt = matches + (size_t)c * nc;
         const size_t op = (size_t)c * cap_p, om = (size_t)c * cap_m;
         for (int r = 0; r < n_proj[c]; r++) {
-            out->proj_lid[op + r] = cand[row[r].i];
+            out->proj_lid[op + r] = tc.cand[row[r].i];
             out->proj_xy[2 * (op + r)] = row[r].x;
             out->proj_xy[2 * (op + r) + 1] = row[r].y;
             out->best_kp[op + r] = row[r].kp;
             out->best_dist[op + r] = row[r].dist;
         }
-        for (size_t k = 0; k < lists[c].size(); k++) {
-            const Triple &tr = lists[c][k];
-            out->match_kp[om + k] = tr.kp;
-            out->match_lid[om + k] = tr.lid;
-            out->match_dist[om + k] = tr.dist;
+        for (int k = 0; k < n_match[c]; k++) {
+            const int lid = tc.cand[mt[k].i];
+            out->match_kp[om + k] = mt[k].kp;
+            out->match_lid[om + k] = lid;
+            out->match_dist[om + k] = mt[k].dist;
             if (out->match_pt)
-                memcpy(out->match_pt + 3 * (om + k), pts ? pts + 3 * (size_t)tr.cand : &m->geom[(size_t)tr.lid * 6], 3 * sizeof(double));
+                memcpy(out->match_pt + 3 * (om + k), pts ? pts + 3 * (size_t)mt[k].i : &m->geom[(size_t)lid * 6], 3 * sizeof(double));
         }
     }
     ph.mark(4);
     return MCORB_OK;
 }
 
-// a call from the candidates on, the frame checked: the caller has run check_args
+// a call from the candidates on.  out: the synchronous entries', which wait at once; NULL: the call stays pending
 int track(mcorb_lmap *m, const mcorb_track_view *view, const Frame &f, const int32_t *lids, int n_lids, double max_d2, int max_hamming,
-          mcorb_track_out *out)
+          bool want_pts, mcorb_track_out *out)
 {
     std::lock_guard<std::mutex> lk(m->mu);
-    Phases ph(m);
-    std::vector<int> cand;
-    TRY(candidates_of(m, lids, n_lids, out, cand));
-    ph.mark(0);
-    if (cand.empty()) return MCORB_OK;
-    if (m->device < 0) {
-        std::vector<TrRow> rows;
-        int32_t n_proj[MCORB_MAX_CAMS];
-        rows_on_host(m, *view, f, cand, max_d2, max_hamming, rows, n_proj);
-        ph.mark(2);
-        return finish(m, view->ncams, cand, rows.data(), n_proj, f.kp, nullptr, out, ph);
-    }
-    const bool want_pts = out->match_pt != nullptr;
-    TRY(rows_on_device(m, *view, f, cand, max_d2, max_hamming, want_pts, ph));
-    return finish(m, view->ncams, cand, m->h_trackrows, m->h_tracknproj, f.kp, want_pts ? m->h_trackpt.get() : nullptr, out, ph);
+    if (m->track_pending.load()) return fail(MCORB_E_STATE, "a submitted tracking call has not been waited for");
+    TRY(submit_body(m, view, f, lids, n_lids, max_d2, max_hamming, want_pts, out));
+    if (out) return wait_body(m, out, true);
+    m->track_pending.store(true);
+    return MCORB_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int mcorb_lmap_track(mcorb_lmap *m, const mcorb_track_view *view, const mcorb_track_frame *frame, const int32_t *lids, int n_lids,
-                     double max_d2, int max_hamming, mcorb_track_out *out)
+// the frame of the host-array entries
+int frame_of_arrays(const mcorb_track_view *view, const mcorb_track_frame *frame, Frame &f)
 {
-    TRY(check_lmap(m, "lmap track"));
-    if (!frame) return fail(MCORB_E_ARG, "bad argument");
-    TRY(check_args(view, lids, n_lids, max_hamming, out));
     const int C = view->ncams;
     if (frame->ncams != C) return fail(MCORB_E_ARG, "the frame has another camera count than the view");
-    Frame f;
     f.kp.stride = 2 * sizeof(float);
     size_t total_kp = 0;
     for (int c = 0; c < C; c++) {
@@ -359,14 +441,12 @@ int mcorb_lmap_track(mcorb_lmap *m, const mcorb_track_view *view, const mcorb_tr
         total_kp += (size_t)frame->n_kp[c];
         if (total_kp > 0x7fffffffu) return fail(MCORB_E_ARG, "too many keypoints");
     }
-    return track(m, view, f, lids, n_lids, max_d2, max_hamming, out);
+    return MCORB_OK;
 }
 
-int mcorb_lmap_track_rig_frame(mcorb_lmap *m, const mcorb_track_view *view, mcorb_rig *r, int slot, int frame, const int32_t *lids,
-                               int n_lids, double max_d2, int max_hamming, mcorb_track_out *out)
+// the frame of the slot entries: the slot is idle and its last job extracted the frame
+int frame_of_slot(const mcorb_lmap *m, const mcorb_track_view *view, mcorb_rig *r, int slot, int frame, Frame &f)
 {
-    TRY(check_lmap(m, "lmap track_rig_frame"));
-    TRY(check_args(view, lids, n_lids, max_hamming, out));
     if (!r || slot < 0 || slot >= (int)r->rig.slots.size()) return fail(MCORB_E_ARG, "no such rig slot");
     Rig &R = r->rig;
     const int C = view->ncams;
@@ -378,7 +458,6 @@ int mcorb_lmap_track_rig_frame(mcorb_lmap *m, const mcorb_track_view *view, mcor
         if (s->busy) return fail(MCORB_E_STATE, "slot busy");
     }
     if (frame < 0 || ((long long)frame + 1) * C > s->nimg_done) return fail(MCORB_E_STATE, "frame not extracted by the slot's last job");
-    Frame f;
     f.kp.stride = sizeof(mcorb_keypoint);
     f.rig = &R;
     f.slot = m->device >= 0 ? s : nullptr;
@@ -389,12 +468,74 @@ int mcorb_lmap_track_rig_frame(mcorb_lmap *m, const mcorb_track_view *view, mcor
         f.kp.base[c] = reinterpret_cast<const uint8_t *>(K.data());
         f.desc[c] = s->h_desc + ((size_t)f.img0 + c) * R.geom.kcap * 32;
     }
-    return track(m, view, f, lids, n_lids, max_d2, max_hamming, out);
+    return MCORB_OK;
 }
+
+// the two entries, synchronous (out) or a submission (out == NULL)
+int track_arrays(mcorb_lmap *m, const mcorb_track_view *view, const mcorb_track_frame *frame, const int32_t *lids, int n_lids,
+                 double max_d2, int max_hamming, bool want_pts, mcorb_track_out *out, bool with_out)
+{
+    TRY(check_lmap(m, "lmap track"));
+    if (!frame) return fail(MCORB_E_ARG, "bad argument");
+    TRY(check_args(view, lids, n_lids, max_hamming, out, with_out));
+    Frame f;
+    TRY(frame_of_arrays(view, frame, f));
+    return track(m, view, f, lids, n_lids, max_d2, max_hamming, want_pts, out);
+}
+
+int track_slot(mcorb_lmap *m, const mcorb_track_view *view, mcorb_rig *r, int slot, int frame, const int32_t *lids, int n_lids,
+               double max_d2, int max_hamming, bool want_pts, mcorb_track_out *out, bool with_out)
+{
+    TRY(check_lmap(m, "lmap track_rig_frame"));
+    TRY(check_args(view, lids, n_lids, max_hamming, out, with_out));
+    Frame f;
+    TRY(frame_of_slot(m, view, r, slot, frame, f));
+    return track(m, view, f, lids, n_lids, max_d2, max_hamming, want_pts, out);
+}
+
+}  // namespace
+
+extern "C" {
+
+int mcorb_lmap_track(mcorb_lmap *m, const mcorb_track_view *view, const mcorb_track_frame *frame, const int32_t *lids, int n_lids,
+                     double max_d2, int max_hamming, mcorb_track_out *out)
+{
+    return track_arrays(m, view, frame, lids, n_lids, max_d2, max_hamming, out && out->match_pt, out, true);
+}
+
+int mcorb_lmap_track_rig_frame(mcorb_lmap *m, const mcorb_track_view *view, mcorb_rig *r, int slot, int frame, const int32_t *lids,
+                               int n_lids, double max_d2, int max_hamming, mcorb_track_out *out)
+{
+    return track_slot(m, view, r, slot, frame, lids, n_lids, max_d2, max_hamming, out && out->match_pt, out, true);
+}
+
+int mcorb_lmap_track_submit(mcorb_lmap *m, const mcorb_track_view *view, const mcorb_track_frame *frame, const int32_t *lids, int n_lids,
+                            double max_d2, int max_hamming, int want_pts)
+{
+    return track_arrays(m, view, frame, lids, n_lids, max_d2, max_hamming, want_pts != 0, nullptr, false);
+}
+
+int mcorb_lmap_track_rig_frame_submit(mcorb_lmap *m, const mcorb_track_view *view, mcorb_rig *r, int slot, int frame, const int32_t *lids,
+                                      int n_lids, double max_d2, int max_hamming, int want_pts)
+{
+    return track_slot(m, view, r, slot, frame, lids, n_lids, max_d2, max_hamming, want_pts != 0, nullptr, false);
+}
+
+int mcorb_lmap_track_wait(mcorb_lmap *m, mcorb_track_out *out)
+{
+    TRY(check_lmap_handle(m, "lmap track_wait"));
+    std::lock_guard<std::mutex> lk(m->mu);
+    if (!m->track_pending.load()) return fail(MCORB_E_STATE, "no tracking call was submitted");
+    const int r = wait_body(m, out, false);
+    m->track_pending.store(false);
+    return r;
+}
+
+int32_t mcorb_host_track_pixel(float v) { return tr_pixel_coord(v); }
 
 int mcorb_lmap_last_track_timing(mcorb_lmap *m, float us[2])
 {
-    TRY(check_lmap(m, "lmap last_track_timing"));
+    TRY(check_lmap_handle(m, "lmap last_track_timing"));
     if (!us) { set_error("lmap last_track_timing: bad argument"); return MCORB_E_ARG; }
     std::lock_guard<std::mutex> lk(m->mu);
     us[0] = m->us_track_project;
@@ -404,7 +545,7 @@ int mcorb_lmap_last_track_timing(mcorb_lmap *m, float us[2])
 
 int mcorb_lmap_last_track_timing4(mcorb_lmap *m, float us[4])
 {
-    TRY(check_lmap(m, "lmap last_track_timing4"));
+    TRY(check_lmap_handle(m, "lmap last_track_timing4"));
     if (!us) { set_error("lmap last_track_timing4: bad argument"); return MCORB_E_ARG; }
     std::lock_guard<std::mutex> lk(m->mu);
     us[0] = m->us_track_points;
@@ -414,12 +555,25 @@ int mcorb_lmap_last_track_timing4(mcorb_lmap *m, float us[4])
     return MCORB_OK;
 }
 
+int mcorb_lmap_last_track_timing5(mcorb_lmap *m, float us[5])
+{
+    TRY(check_lmap_handle(m, "lmap last_track_timing5"));
+    if (!us) { set_error("lmap last_track_timing5: bad argument"); return MCORB_E_ARG; }
+    std::lock_guard<std::mutex> lk(m->mu);
+    us[0] = m->us_track_points;
+    us[1] = m->us_track_project;
+    us[2] = m->us_track_match;
+    us[3] = m->us_track_compact;
+    us[4] = m->us_track_dedup;
+    return MCORB_OK;
+}
+
 #ifdef MCORB_TRACK_PROF
 // the last call's host phases in microseconds: candidate walk, submission, wait, de-duplication, output.  Not part of the
 // public header: a build with -DMCORB_TRACK_PROF exports it for scripts/track_rate.py
 int mcorb_lmap_track_phases(mcorb_lmap *m, float us[5])
 {
-    TRY(check_lmap(m, "lmap track_phases"));
+    TRY(check_lmap_handle(m, "lmap track_phases"));
     if (!us) { set_error("lmap track_phases: bad argument"); return MCORB_E_ARG; }
     std::lock_guard<std::mutex> lk(m->mu);
     memcpy(us, m->us_track_phase, sizeof(m->us_track_phase));

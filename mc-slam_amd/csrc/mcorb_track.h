@@ -100,6 +100,29 @@ MCORB_TR_HD inline uint32_t tr_gate_key(int dist, int rank, int max_hamming)
     return dist < max_hamming ? (uint32_t)dist * 16u + (uint32_t)rank : kTrNoGate;
 }
 
+// The de-duplication (querryEachFrame:380-415) compares keypoints by their pixel ((int)pt.x, (int)pt.y).  The conversion, defined
+// for every float: truncation toward zero for |v| < 2^31, INT32_MIN otherwise, a NaN included (what an x86-64 cvttss2si gives).
+// The host tail and k_track_dedup_min share it.  Every 64-bit value is the key of some pixel -- (-1, -1) is all ones, (0, 0) is
+// zero -- so no key can stand for "empty"
+MCORB_TR_HD inline int32_t tr_pixel_coord(float v)
+{
+    return v > -2147483648.0f && v < 2147483648.0f ? (int32_t)v : INT32_MIN;
+}
+MCORB_TR_HD inline uint64_t pixel_key(int32_t px, int32_t py) { return ((uint64_t)(uint32_t)px << 32) | (uint32_t)py; }
+MCORB_TR_HD inline uint64_t tr_pixel_key(float x, float y) { return pixel_key(tr_pixel_coord(x), tr_pixel_coord(y)); }
+// What the serial list leaves, in closed form.  The list never holds two entries of one pixel; an entry is replaced only by a
+// strictly smaller distance, and the replacement is appended.  So of the matched queries of one pixel the entry that survives is
+// the one with the least (dist, candidate index) -- tr_dedup_value orders them -- and the final list holds the survivors in
+// ascending candidate index: a segmented arg-min and an ordered stream compaction
+MCORB_TR_HD inline uint64_t tr_dedup_value(int32_t dist, int32_t i) { return ((uint64_t)(uint32_t)dist << 32) | (uint32_t)i; }
+// a device store's arg-min table of one camera has 1 << tr_dedup_log2(n) slots for n candidates: the next power of two >= 2 * n
+inline int tr_dedup_log2(int n)
+{
+    int log2p = 1;
+    while (((size_t)1 << log2p) < 2 * (size_t)n) log2p++;
+    return log2p;
+}
+
 // what k_track_match is told about the frame: per camera the keypoint count and the first keypoint's place in the packed block
 struct TrFrame { int32_t n_kp[MCORB_MAX_CAMS]; int32_t first[MCORB_MAX_CAMS]; };
 // a query's result before the serial part
@@ -108,5 +131,8 @@ struct TrBest { int32_t kp, dist; };
 // query's result.  A camera's rows are its kept candidates in candidate order, n_proj of them from row c * n (k_track_compact on a
 // device store, the serial path itself on a host-only one)
 struct TrRow { int32_t i; float x, y; int32_t kp, dist; };
+// an entry of a camera's de-duplicated list: the candidate's place in the call's list, its keypoint, the distance.  A camera's
+// entries are n_match of them from entry c * n (k_track_dedup_emit on a device store, the serial list on a host-only one)
+struct TrMatch { int32_t i, kp, dist; };
 
 }  // namespace mcorb

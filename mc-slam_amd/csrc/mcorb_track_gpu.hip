@@ -3,12 +3,14 @@
 // Tracking::querryEachFrame, :329-377: the 10 nearest keypoints by image position, the radius gate, the best Hamming distance).
 // The arithmetic is mcorb_track.h, the code the host-only store runs.  k_track_points (mcorb_lmap_track_rig_frame only) rebuilds a
 // rig slot's keypoints from their packed selection words; k_track_compact leaves each camera's kept candidates in candidate
-// order, in host-mapped memory.  No extraction job runs them and no benchmark leg times them.
+// order, in host-mapped memory; k_track_dedup_min / _win / _emit leave each camera's de-duplicated matches there (querryEachFrame
+// :380-415 in closed form).  No extraction job runs them and no benchmark leg times them.
 //
 // They go out in one submission: k_track_match reads the validity bytes k_track_project wrote and the points k_track_points
-// wrote, k_track_compact reads all three kernels' rows, and the host walks the compacted rows after the one synchronisation.
-// No atomics, no scratch, no workgroup waits on another, and a query's result depends on that query alone, so the launch shape
-// cannot change it.
+// wrote, k_track_compact and the de-duplication read the rows of the kernels before them, and the host copies rows and matches
+// out after the one synchronisation.  No scratch, no workgroup waits on another; up to k_track_compact no atomics, and a query's
+// result depends on that query alone, so the launch shape cannot change it.  The de-duplication's atomics are a claim and a
+// minimum, whose results do not depend on arrival order.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -244,6 +246,121 @@ void launch_track_compact(hipStream_t st, int ncams, int n, const uint8_t *valid
     if (n < 1) return;
     hipLaunchKernelGGL(k_track_compact, dim3((n + kTrackCompactT - 1) / kTrackCompactT, ncams), dim3(kTrackCompactT), 0, st, n, valid, xy,
                        best, rows, n_proj);
+}
+
+// ---- the de-duplication (mcorb_track.h, tr_dedup_value): per camera a segmented arg-min over the matched candidates, grouped by
+// the pixel of the matched keypoint, then the winners in candidate order.  Three kernels behind k_track_match in the same
+// submission, on the uncompacted rows (valid, best), one lane per (camera, candidate).
+//
+// Camera c's table is slots [c << log2p, (c + 1) << log2p) of owner / val, 1 << log2p >= 2 * n, both cleared to all ones by one
+// hipMemsetAsync each in front of k_track_dedup_min.  A pixel's slot is the first one of its probe sequence that a candidate of
+// that pixel claimed: the claim is a 32-bit compare-and-swap of kTrNoOwner against the candidate's index (an index is never all
+// ones), a slot is never given back, and a slot's pixel is read through its owner's keypoint, which no kernel here writes -- so no
+// pixel key is stored and none serves as "empty".  Which slot a pixel gets depends on arrival order; what the slot's val ends as,
+// the 64-bit atomicMin over the pixel's values, does not.  The probe loop runs at most 1 << log2p trips whatever memory holds, an
+// owner is followed only to a candidate index and a keypoint index inside their arrays, and a lane that found no slot (the table
+// cannot fill: it has twice the slots there are candidates) takes no part, it does not spin.
+// No workgroup waits on another, no scratch.
+constexpr uint32_t kTrNoOwner = ~0u;
+
+__global__ __launch_bounds__(kTrackDedupT) void k_track_dedup_min(TrFrame frame, const float2 *__restrict__ kp_xy, int n,
+                                                                  const uint8_t *__restrict__ valid, const TrBest *__restrict__ best,
+                                                                  int log2p, uint32_t *__restrict__ owner,
+                                                                  unsigned long long *__restrict__ val, int32_t *__restrict__ slot)
+{
+    const int c = blockIdx.y, i = blockIdx.x * kTrackDedupT + threadIdx.x;
+    if (i >= n) return;
+    const size_t row = (size_t)c * n, tab = (size_t)c << log2p;
+    int mine = -1;
+    if (valid[row + i] != 0 && best[row + i].kp >= 0) {   // (k_track_match wrote best for the valid ones only)
+        const TrBest b = best[row + i];
+        const float2 *kp = kp_xy + frame.first[c];
+        const uint64_t key = tr_pixel_key(kp[b.kp].x, kp[b.kp].y);
+        const uint32_t slots = 1u << log2p;
+        uint32_t s = (uint32_t)((key * 0x9e3779b97f4a7c15ull) >> (64 - log2p));
+        for (uint32_t trip = 0; trip < slots; trip++, s = (s + 1) & (slots - 1)) {
+            const uint32_t o = atomicCAS(&owner[tab + s], kTrNoOwner, (uint32_t)i);
+            if (o != kTrNoOwner) {   // claimed before: by this pixel?
+                // (only a table that was not cleared holds an owner that is no candidate, or one without a match in this call)
+                if (o >= (uint32_t)n) continue;
+                const int okp = best[row + o].kp;
+                if (okp < 0 || okp >= frame.n_kp[c]) continue;
+                const float2 q = kp[okp];
+                if (tr_pixel_key(q.x, q.y) != key) continue;
+            }
+            atomicMin(&val[tab + s], (unsigned long long)tr_dedup_value(b.dist, i));
+            mine = (int)s;
+            break;
+        }
+    }
+    slot[row + i] = mine;
+}
+
+// a candidate is its pixel's entry iff the slot's minimum is its own value
+__global__ __launch_bounds__(kTrackDedupT) void k_track_dedup_win(int n, const TrBest *__restrict__ best, const int32_t *__restrict__ slot,
+                                                                  const unsigned long long *__restrict__ val, int log2p,
+                                                                  uint8_t *__restrict__ win)
+{
+    const int c = blockIdx.y, i = blockIdx.x * kTrackDedupT + threadIdx.x;
+    if (i >= n) return;
+    const size_t row = (size_t)c * n;
+    const int s = slot[row + i];
+    win[row + i] = s >= 0 && val[((size_t)c << log2p) + s] == tr_dedup_value(best[row + i].dist, i) ? 1 : 0;
+}
+
+// The winners in candidate order, ranked the way k_track_compact ranks the validity bytes: workgroup b counts the flags before
+// its own 256 itself, ranks its own by a ballot per wave and waits on nobody; the last workgroup of a camera has the camera's
+// total.  matches and n_match are host-mapped.
+__global__ __launch_bounds__(kTrackDedupT) void k_track_dedup_emit(int n, const uint8_t *__restrict__ win, const TrBest *__restrict__ best,
+                                                                   TrMatch *__restrict__ matches, int32_t *__restrict__ n_match)
+{
+    __shared__ int before[kTrackDedupT / 64], kept[kTrackDedupT / 64];
+    const int c = blockIdx.y, b = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    if (b * kTrackDedupT >= n) return;   // (uniform over the workgroup)
+    const size_t row = (size_t)c * n;
+    const uint8_t *p = win + row;
+    const int end = b * kTrackDedupT;    // a multiple of 16: the head and the tail below are 16 bytes together, or none
+    const int head = end ? (int)((16 - (reinterpret_cast<uintptr_t>(p) & 15)) & 15) : 0;
+    const int nvec = (end - head) >> 4, tail = head + (nvec << 4);
+    int s = 0;
+    if (t < head) s = p[t];
+    const uint4 *v = reinterpret_cast<const uint4 *>(p + head);
+    for (int j = t; j < nvec; j += kTrackDedupT) {
+        const uint4 q = v[j];
+        s += __popc(q.x) + __popc(q.y) + __popc(q.z) + __popc(q.w);
+    }
+    if (tail + t < end) s += p[tail + t];
+    for (int o = 32; o >= 1; o >>= 1) s += __shfl_xor(s, o, 64);
+
+    const int i = end + t;
+    const bool keep = i < n && p[i] != 0;
+    const unsigned long long mask = __ballot(keep);
+    if (lane == 0) {
+        before[wave] = s;
+        kept[wave] = __popcll(mask);
+    }
+    __syncthreads();
+    int at = 0, total = 0;
+    for (int w = 0; w < kTrackDedupT / 64; w++) {
+        at += before[w] + (w < wave ? kept[w] : 0);
+        total += before[w] + kept[w];
+    }
+    if (keep) {
+        const TrBest r = best[row + i];
+        matches[row + lane_rank(mask, at)] = TrMatch{i, r.kp, r.dist};
+    }
+    if (b == (int)gridDim.x - 1 && t == 0) n_match[c] = total;
+}
+
+void launch_track_dedup(hipStream_t st, const TrFrame &frame, int ncams, const float2 *kp_xy, int n, const uint8_t *valid, const TrBest *best,
+                        uint32_t *owner, unsigned long long *val, int32_t *slot, uint8_t *win, TrMatch *matches, int32_t *n_match)
+{
+    if (n < 1) return;
+    const int log2p = tr_dedup_log2(n);
+    const dim3 grid((n + kTrackDedupT - 1) / kTrackDedupT, ncams), block(kTrackDedupT);
+    hipLaunchKernelGGL(k_track_dedup_min, grid, block, 0, st, frame, kp_xy, n, valid, best, log2p, owner, val, slot);
+    hipLaunchKernelGGL(k_track_dedup_win, grid, block, 0, st, n, best, slot, val, log2p, win);
+    hipLaunchKernelGGL(k_track_dedup_emit, grid, block, 0, st, n, win, best, matches, n_match);
 }
 
 }  // namespace mcorb

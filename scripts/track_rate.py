@@ -17,11 +17,26 @@ extraction job on the synthetic rig frame, the landmarks are back-projected from
   track            LocalMap.track on those arrays;
   track_rig_frame  LocalMap.track_rig_frame (only where the library has it: --tree names a checkout built from another commit,
                    whose package is imported instead of this one, to time the first two there).
-With a library built with -DMCORB_TRACK_PROF the host phases of the last two are recorded as well.
-    python scripts/track_rate.py --leg slot [--tree DIR] [--reps 5] [--out FILE]"""
+  submit_wait      LocalMap.track_rig_frame_submit and LocalMap.track_wait (where the library has them), the two timed apart: what
+                   the submission costs the caller's thread and what is left to wait for when nothing is overlapped.
+With a library built with -DMCORB_TRACK_PROF the host phases of the last three are recorded as well.
+    python scripts/track_rate.py --leg slot [--tree DIR] [--reps 5] [--out FILE]
+
+--leg slot_ab --tree PARENT: the slot leg in fresh processes, PARENT's library and this one's alternating, --procs (3) each; the
+pass marks -- in every pair of processes the median of track_rig_frame, and of track, on this tree is below the parent's fastest
+run of the same leg in that pair -- and every process's record go to --out.  --prof-tree DIR adds one process on a checkout of
+this commit built with -DMCORB_TRACK_PROF, for the phases.
+    python scripts/track_rate.py --leg slot_ab --tree PARENT [--prof-tree DIR] [--out profiles/track_dedup_rate.json]
+
+--leg stress: two frames on host arrays that load the de-duplication in opposite ways, the whole call and (where the library has
+last_track_timing5) the kernels: `one_keypoint`, 8000 landmarks whose queries all match the single keypoint of their camera, so
+every atomic of the arg-min lands on one address; `no_radius`, the frame of the default leg with max_d2 = inf, so every query has
+ten neighbours.
+    python scripts/track_rate.py --leg stress [--tree DIR] [--out FILE]"""
 import argparse
 import json
 import os
+import subprocess
 import sys
 import time
 
@@ -135,7 +150,7 @@ def slot_leg(mcorb, a):
     lm = mcorb.LocalMap(mcorb.ORBVocabulary(device=0).create(**kfdb_cases.vocabulary()), device=0, max_landmarks=len(pts), max_candidates=len(pts))
     lm.set(np.arange(len(pts), dtype=np.int32), pts, np.zeros_like(pts), desc)
     xy, ds = readback(rig)
-    has_slot = hasattr(lm, "track_rig_frame")
+    has_slot, has_pair = hasattr(lm, "track_rig_frame"), hasattr(lm, "track_rig_frame_submit")
     try:
         phases_fn = lm.L.mcorb_lmap_track_phases
     except AttributeError:
@@ -146,8 +161,9 @@ def slot_leg(mcorb, a):
         phases_fn(lm.h, us)
         return list(us)
 
-    legs = ["readback_track", "track"] + (["track_rig_frame"] if has_slot else [])
+    legs = ["readback_track", "track"] + (["track_rig_frame"] if has_slot else []) + (["submit_wait"] if has_pair else [])
     t = {k: [] for k in legs}
+    t_submit = []
     kus = {k: [] for k in legs}
     ph = {k: [] for k in legs}
     res, same = {}, True
@@ -159,10 +175,14 @@ def slot_leg(mcorb, a):
                 res[k] = lm.track(view, xy_, ds_, lids)
             elif k == "track":
                 res[k] = lm.track(view, xy, ds, lids)
-            else:
+            elif k == "track_rig_frame":
                 res[k] = lm.track_rig_frame(view, rig, 0, lids)
+            else:
+                lm.track_rig_frame_submit(view, rig, 0, lids)
+                t_submit.append((time.perf_counter() - t0) * 1e3)
+                res[k] = lm.track_wait()
             t[k].append((time.perf_counter() - t0) * 1e3)
-            kus[k].append(lm.last_track_timing4() if has_slot else lm.last_track_timing())
+            kus[k].append(lm.last_track_timing5() if has_pair else lm.last_track_timing4() if has_slot else lm.last_track_timing())
             if phases_fn is not None:
                 ph[k].append(phases())
         same = same and all(T.as_lists(res[k]) == T.as_lists(res["track"]) for k in legs)
@@ -180,6 +200,74 @@ def slot_leg(mcorb, a):
         if phases_fn is not None:
             out["%s_host_phase_us" % k] = dict(zip(("candidate_walk", "submission", "wait", "deduplication", "output"),
                                                    [round(float(np.median([p[i] for p in ph[k][1:]])), 1) for i in range(5)]))
+    if has_pair:
+        out["submit_ms_runs"] = [round(x, 3) for x in t_submit[1:]]
+        out["submit_ms"] = round(float(np.median(t_submit[1:])), 3)
+    print(json.dumps(out))
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump(out, f, indent=1)
+
+
+def child(a, leg, tree):
+    """one fresh process of this script on `tree`'s library -> its record"""
+    cmd = [sys.executable, os.path.abspath(__file__), "--leg", leg, "--reps", str(a.reps)] + (["--tree", tree] if tree else [])
+    return json.loads(subprocess.run(cmd, check=True, capture_output=True, text=True, timeout=180).stdout.strip().splitlines()[-1])
+
+
+def slot_ab_leg(a):
+    pairs = []
+    for _ in range(a.procs):
+        pairs.append({"parent": child(a, "slot", a.tree), "this": child(a, "slot", None)})
+    marks = {}
+    for k in ("track_rig_frame", "track"):
+        marks[k] = [{"this_median_ms": p["this"]["%s_ms" % k], "parent_fastest_ms": min(p["parent"]["%s_ms_runs" % k]),
+                     "met": p["this"]["%s_ms" % k] < min(p["parent"]["%s_ms_runs" % k])} for p in pairs]
+    out = {"pass_marks": marks, "pass_marks_met": all(m["met"] for v in marks.values() for m in v), "pairs": pairs}
+    if a.prof_tree:
+        out["phases"] = child(a, "slot", a.prof_tree)
+    print(json.dumps(out))
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump(out, f, indent=1)
+
+
+def stress_leg(mcorb, a):
+    import kfdb_cases
+    import track_cases as T
+    rng = np.random.default_rng(41)
+    n = 8000
+    frames = {}
+    # every query of a camera matches that camera's one keypoint: landmarks within 35 px of it, descriptors up to 12 bits off
+    d0 = rng.integers(0, 256, 32, dtype=np.uint8)
+    desc = np.repeat(d0[None], n, axis=0)
+    flips = rng.integers(0, 256, (n, 12))
+    for j in range(12):
+        on = rng.random(n) < 0.5
+        desc[on, flips[on, j] // 8] ^= (1 << (flips[on, j] % 8)).astype(np.uint8)
+    pts = np.stack([rng.uniform(600, 650, n), rng.uniform(350, 400, n), np.ones(n)], axis=1)
+    frames["one_keypoint"] = dict(view=T.flat_view(COLS, ROWS, ncams=CAMS), pts=pts, desc=desc, lids=np.arange(n, dtype=np.int32),
+                                  kps=[np.array([[625.0, 375.0]], np.float32)] * CAMS, descs=[d0[None].copy()] * CAMS, kw={})
+    w = workload()
+    w["kw"] = {"max_d2": float("inf")}
+    frames["no_radius"] = w
+    out = {"tree": os.path.abspath(a.tree or ROOT)}
+    for name, w in frames.items():
+        view = T.to_view(mcorb, w["view"])
+        nl = len(w["pts"])
+        lm = mcorb.LocalMap(mcorb.ORBVocabulary(device=0).create(**kfdb_cases.vocabulary()), device=0, max_landmarks=nl, max_candidates=nl)
+        lm.set(np.arange(nl, dtype=np.int32), w["pts"], np.zeros_like(w["pts"]), w["desc"])
+        ts, kus = [], []
+        for rep in range(a.reps + 1):
+            t0 = time.perf_counter()
+            r = lm.track(view, w["kps"], w["descs"], w["lids"], **w["kw"])
+            ts.append((time.perf_counter() - t0) * 1e3)
+            kus.append(lm.last_track_timing5() if hasattr(lm, "last_track_timing5") else lm.last_track_timing())
+        out[name] = {"candidates": int(r.n_candidates), "queries_per_camera": [len(p) for p in r.proj_lid],
+                     "matched_per_camera": [int((b >= 0).sum()) for b in r.best_kp], "matches_per_camera": [len(m) for m in r.match_kp],
+                     "track_ms": round(float(np.median(ts[1:])), 3), "track_ms_runs": [round(x, 3) for x in ts[1:]],
+                     "kernel_us": [round(float(np.median([u[i] for u in kus[1:]])), 1) for i in range(len(kus[0]))]}
+        lm.close()
     print(json.dumps(out))
     if a.out:
         with open(a.out, "w") as f:
@@ -190,14 +278,25 @@ if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--out", default=None)
-    ap.add_argument("--leg", default="stores", choices=["stores", "slot"])
-    ap.add_argument("--tree", default=None, help="a checkout whose package is timed instead of this one's (--leg slot)")
+    ap.add_argument("--leg", default="stores", choices=["stores", "slot", "slot_ab", "stress"])
+    ap.add_argument("--tree", default=None, help="a checkout whose package is timed instead of this one's (--leg slot, stress); "
+                                                 "the parent commit's checkout (--leg slot_ab)")
+    ap.add_argument("--prof-tree", default=None, help="--leg slot_ab: a checkout of this commit built with -DMCORB_TRACK_PROF")
+    ap.add_argument("--procs", type=int, default=3, help="--leg slot_ab: processes per tree")
     a = ap.parse_args()
+    if a.leg == "slot_ab":
+        if not a.tree:
+            ap.error("--leg slot_ab needs --tree PARENT")
+        slot_ab_leg(a)
+        sys.exit(0)
     if a.tree:
         sys.path.insert(0, os.path.abspath(a.tree))
     import mcorb
     if a.leg == "slot":
         slot_leg(mcorb, a)
+        sys.exit(0)
+    if a.leg == "stress":
+        stress_leg(mcorb, a)
         sys.exit(0)
     import track_cases as T
     w = workload()
