@@ -946,6 +946,35 @@ int mcorb_lmap_track_submit(mcorb_lmap *m, const mcorb_track_view *view, const m
 int mcorb_lmap_track_rig_frame_submit(mcorb_lmap *m, const mcorb_track_view *view, mcorb_rig *r, int slot, int frame, const int32_t *lids,
                                       int n_lids, double max_d2, int max_hamming, int want_pts);
 int mcorb_lmap_track_wait(mcorb_lmap *m, mcorb_track_out *out);
+/* The batch: nf frames of a rig slot's last extraction job against the store in one submission with one wait, and nothing on the
+ * host between them.  Frame f of the call is frames[f] of the slot (any order, repeats allowed), seen from views[f], with the ids
+ * lids[lid_first[f] .. lid_first[f + 1]); outs[f] receives, bit for bit, what mcorb_lmap_track_rig_frame returns for (views[f],
+ * frames[f], those ids) on the same store and slot: steps 1 - 5 above hold per frame and frames do not interact -- an id named in
+ * two frames' lists is a candidate of both, and the de-duplication is per frame and camera.  On a device store the candidate
+ * lists, a table with one item per frame and the views go up in one pinned block in one copy; the seven kernels of the single
+ * call run once each over all frames (k_track_*_batch: the frame is the grid's z, a frame's block of every array has the single
+ * call's layout), and the rows, matches and counts of all frames land in host-mapped memory.  A host-only store runs the serial
+ * path frame by frame.
+ * Refused before anything runs -- nothing is pending then, the store is unchanged and every count of every outs[f] is zero:
+ * everything mcorb_lmap_track_rig_frame_submit refuses, for any frame, with that call's code; MCORB_E_ARG for nf < 1, nf >
+ * MCORB_TRACK_MAX_FRAMES, a NULL views, frames or lid_first, a negative or decreasing lid_first, a view whose ncams is not the
+ * rig's; MCORB_E_CAP when one frame has more than max_candidates candidates (the frames together may have more).
+ * There is one pending call per store: a batch is a pending call with a frame count, a single submission one of one frame, and
+ * every rule of the pair above holds.  mcorb_lmap_track_frames_wait serves any pending call: n_outs other than its frame count is
+ * MCORB_E_ARG; mcorb_lmap_track_wait on a pending batch of more than one frame synchronises and returns MCORB_E_STATE.  Whatever
+ * either wait returns, nothing is pending afterwards.  MCORB_E_CAP after the run: when any frame's output is short in any camera,
+ * every count of every frame is set and no array of any frame is written.
+ * After a batch the mcorb_lmap_last_track_timing* calls hold the batch's intervals, each over all its frames; a batch without any
+ * candidate launches nothing and leaves them. */
+#define MCORB_TRACK_MAX_FRAMES 32
+int mcorb_lmap_track_rig_frames_submit(mcorb_lmap *m, const mcorb_track_view *views, mcorb_rig *r, int slot, const int32_t *frames, int nf,
+                                       const int32_t *lids, const int32_t *lid_first /* nf + 1 */, double max_d2, int max_hamming,
+                                       int want_pts);
+int mcorb_lmap_track_frames_wait(mcorb_lmap *m, mcorb_track_out *outs, int n_outs);
+/* the submission and its wait; outs: nf of them */
+int mcorb_lmap_track_rig_frames(mcorb_lmap *m, const mcorb_track_view *views, mcorb_rig *r, int slot, const int32_t *frames, int nf,
+                                const int32_t *lids, const int32_t *lid_first, double max_d2, int max_hamming, int want_pts,
+                                mcorb_track_out *outs);
 
 /* ------------------------------------------------------------------------- */
 /* Host stages exposed for the CPU test-suite (no device needed)              */

@@ -1359,7 +1359,87 @@ class LocalMap:
         does.  Whatever happens, nothing is pending afterwards; without a submitted call: MCORB_E_STATE"""
         ncams, n_lids, want_pts = getattr(self, "_submitted", None) or (1, 0, False)
         self._submitted = None
+        n_lids = max(n_lids) if isinstance(n_lids, list) else n_lids     # (a pending batch: the call fails, MCORB_E_STATE)
         return self._track_out(ncams, n_lids, caps, want_pts, lambda o: self.L.mcorb_lmap_track_wait(self.h, C.byref(o)))
+
+    def track_rig_frames(self, views, rig, frames, lids, slot=0, max_d2=10000.0, max_hamming=20, caps=None):
+        """track_rig_frame() for len(frames) <= TRACK_MAX_FRAMES frames of the slot's last extraction job in one submission and one
+        wait: frame frames[f] (any order, repeats allowed) from views[f] with the ids lids[f] -> a list of TrackResult, each bit
+        for bit what track_rig_frame(views[f], rig, frames[f], lids[f]) returns.  caps: one (projected, matches) pair for every
+        frame, by default what a frame cannot exceed.  A McorbError carries n_candidates, n_proj and n_match as lists with one
+        entry per frame"""
+        va, fa, la, first = self._track_batch(views, frames, lids)
+        return self._track_outs(va[0].ncams, [len(l) for l in lids], caps, True,
+                                lambda o, n: self.L.mcorb_lmap_track_rig_frames(
+                                    self.h, va, rig.h_rig if rig is not None else None, slot, fa.ctypes.data, len(fa), la.ctypes.data,
+                                    first.ctypes.data, float(max_d2), int(max_hamming), 1, o))
+
+    def track_rig_frames_submit(self, views, rig, frames, lids, slot=0, max_d2=10000.0, max_hamming=20, want_pts=True):
+        """track_rig_frames() as track_rig_frame_submit() is track_rig_frame(): one pending call of len(frames) frames, which
+        track_frames_wait() serves; views, frames and lids may be changed at once"""
+        va, fa, la, first = self._track_batch(views, frames, lids)
+        _lib.check(self.L.mcorb_lmap_track_rig_frames_submit(self.h, va, rig.h_rig if rig is not None else None, slot, fa.ctypes.data,
+                                                             len(fa), la.ctypes.data, first.ctypes.data, float(max_d2), int(max_hamming),
+                                                             int(bool(want_pts))))
+        self._submitted = (va[0].ncams, [len(l) for l in lids], bool(want_pts))
+
+    def track_frames_wait(self, caps=None):
+        """the TrackResults of the pending call, one per frame: a list of one after track_submit() / track_rig_frame_submit().  A
+        McorbError carries the counts per frame.  Whatever happens, nothing is pending afterwards; without a submitted call:
+        MCORB_E_STATE"""
+        ncams, n_lids, want_pts = getattr(self, "_submitted", None) or (1, [0], False)
+        self._submitted = None
+        n_lids = n_lids if isinstance(n_lids, list) else [n_lids]
+        return self._track_outs(ncams, n_lids, caps, want_pts, lambda o, n: self.L.mcorb_lmap_track_frames_wait(self.h, o, n))
+
+    @staticmethod
+    def _track_batch(views, frames, lids):
+        """-> (the views as one array, frames and the concatenated ids as int32 arrays, lid_first)"""
+        if not len(views) == len(frames) == len(lids):
+            raise ValueError("track_rig_frames: one view and one id sequence per frame")
+        va = (_lib.TrackView * max(len(views), 1))()
+        for f, v in enumerate(views):
+            C.memmove(C.addressof(va[f]), C.addressof(v), C.sizeof(_lib.TrackView))
+        ls = [np.ascontiguousarray(l, np.int32).reshape(-1) for l in lids]
+        first = np.zeros(len(ls) + 1, np.int32)
+        first[1:] = np.cumsum([len(l) for l in ls])
+        la = np.concatenate(ls + [np.zeros(1, np.int32)])       # (never empty: its address is passed)
+        return va, np.ascontiguousarray(frames, np.int32).reshape(-1), la, first
+
+    def _track_outs(self, ncams, n_lids, caps, want_pts, call):
+        """_track_out for the frames of a batch: call(array of mcorb_track_out, its length) -> code; -> the TrackResult per frame
+        (or the McorbError with the counts per frame)"""
+        nf = len(n_lids)
+        os_ = (_lib.TrackOut * max(nf, 1))()
+        arrays = []
+        for f in range(nf):
+            cap_p, cap_m = caps if caps is not None else (n_lids[f], n_lids[f])
+            n1, n2 = ncams * max(cap_p, 1), ncams * max(cap_m, 1)
+            r = dict(proj_lid=np.zeros(n1, np.int32), proj_xy=np.zeros((n1, 2), np.float32), best_kp=np.zeros(n1, np.int32),
+                     best_dist=np.zeros(n1, np.int32), match_kp=np.zeros(n2, np.int32), match_lid=np.zeros(n2, np.int32),
+                     match_dist=np.zeros(n2, np.int32))
+            if want_pts:
+                r["match_pt"] = np.zeros((n2, 3))
+            os_[f].cap_proj, os_[f].cap_match = cap_p, cap_m
+            for k, a in r.items():
+                setattr(os_[f], k, a.ctypes.data)
+            arrays.append((r, cap_p, cap_m))
+        code = call(os_, nf)
+        n_proj, n_match = [list(os_[f].n_proj[:ncams]) for f in range(nf)], [list(os_[f].n_match[:ncams]) for f in range(nf)]
+        if code != _lib.OK:
+            try:
+                _lib.check(code)
+            except McorbError as e:     # MCORB_E_CAP for a short output comes with every count of every frame set
+                e.n_candidates, e.n_proj, e.n_match = [os_[f].n_candidates for f in range(nf)], n_proj, n_match
+                e.outputs = [r for r, _, _ in arrays]     # (the output arrays as the call left them: unwritten)
+                raise
+        res = []
+        for f, (r, cap_p, cap_m) in enumerate(arrays):
+            out = {k: [r[k][c * cap_p:c * cap_p + n_proj[f][c]].copy() for c in range(ncams)] for k in ("proj_lid", "proj_xy", "best_kp", "best_dist")}
+            out.update({k: [r[k][c * cap_m:c * cap_m + n_match[f][c]].copy() for c in range(ncams)] if k in r else None
+                        for k in ("match_kp", "match_lid", "match_dist", "match_pt")})
+            res.append(TrackResult(n_candidates=os_[f].n_candidates, **out))
+        return res
 
     def last_track_timing(self):
         """(microseconds of the last k_track_project launch, of the last k_track_match launch); a device store"""

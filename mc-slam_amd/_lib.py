@@ -19,6 +19,7 @@ BOW_TRANSFORM, BOW_MATCH = 1, 2
 OBS_UPDATE, OBS_RECORD = 0, 1
 MAX_LEVELS, MAX_CAMS = 16, 16
 TRACK_KNN, TRACK_TILE = 10, 1024   # MCORB_TRACK_KNN, MCORB_TRACK_TILE
+TRACK_MAX_FRAMES = 32               # MCORB_TRACK_MAX_FRAMES
 
 KP_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"),
                      ("response", "<f4"), ("octave", "<i4"), ("class_id", "<i4")])
@@ -246,6 +247,9 @@ SIGNATURES = {
     "mcorb_lmap_track_submit": (_i, [_vp, C.POINTER(TrackView), C.POINTER(TrackFrame), _vp, _i, C.c_double, _i, _i]),
     "mcorb_lmap_track_rig_frame_submit": (_i, [_vp, C.POINTER(TrackView), _vp, _i, _i, _vp, _i, C.c_double, _i, _i]),
     "mcorb_lmap_track_wait": (_i, [_vp, C.POINTER(TrackOut)]),
+    "mcorb_lmap_track_rig_frames_submit": (_i, [_vp, C.POINTER(TrackView), _vp, _i, _vp, _i, _vp, _vp, C.c_double, _i, _i]),
+    "mcorb_lmap_track_frames_wait": (_i, [_vp, C.POINTER(TrackOut), _i]),
+    "mcorb_lmap_track_rig_frames": (_i, [_vp, C.POINTER(TrackView), _vp, _i, _vp, _i, _vp, _vp, C.c_double, _i, _i, C.POINTER(TrackOut)]),
     "mcorb_host_track_pixel": (C.c_int32, [_f]),
     "mcorb_host_geometry": (_i, [C.POINTER(Params), _i, _i, _vp]),
     "mcorb_synth_rig_frame": (_i, [C.c_uint32, _i, _i, _i, _i, _vp, _i]),

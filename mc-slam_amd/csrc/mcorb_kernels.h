@@ -206,5 +206,23 @@ void launch_track_compact(hipStream_t st, int ncams, int n, const uint8_t *valid
 constexpr int kTrackDedupT = 256;     // one lane per (camera, candidate)
 void launch_track_dedup(hipStream_t st, const TrFrame &frame, int ncams, const float2 *kp_xy, int n, const uint8_t *valid, const TrBest *best,
                         uint32_t *owner, unsigned long long *val, int32_t *slot, uint8_t *win, TrMatch *matches, int32_t *n_match);
+// The same seven for the nf frames of mcorb_lmap_track_rig_frames in one launch each, frame blockIdx.z (k_track_*_batch): items[f]
+// (device memory) says where frame f's view, candidates, block of every per-pair array (the single call's layout inside it),
+// de-duplication tables, keypoint rows and descriptors are; max_n: the most candidates of a frame, which sizes the grid's x; views:
+// the call's views, device memory; cand, xy, valid, pts, best, rows, slot, win, matches: the frames' blocks back to back; n_proj /
+// n_match: MCORB_MAX_CAMS counts per frame, written for the frames with a candidate; owner / val: every frame's tables, every byte
+// 0xff; kp: the store's keypoint buffer, nf * ncams rows of kcap; kp_desc: the slot's descriptors, image 0 on
+void launch_track_points_batch(hipStream_t st, const TrBatchItem *items, int nf, const uint32_t *sel, const int *nsel, int kcap, int ncams,
+                               const float *scale, int nlevels, float2 *out);
+void launch_track_project_batch(hipStream_t st, const TrBatchItem *items, int nf, int max_n, const mcorb_track_view *views,
+                                const double *geom, const int *cand, float2 *xy, uint8_t *valid, double *pts);
+void launch_track_match_batch(hipStream_t st, const TrBatchItem *items, int nf, int max_n, int ncams, const float2 *kp_xy,
+                              const uint8_t *kp_desc, const uint8_t *lm_desc, const int *cand, const float2 *xy, const uint8_t *valid,
+                              double max_d2, int max_hamming, TrBest *best);
+void launch_track_compact_batch(hipStream_t st, const TrBatchItem *items, int nf, int max_n, int ncams, const uint8_t *valid,
+                                const float2 *xy, const TrBest *best, TrRow *rows, int32_t *n_proj);
+void launch_track_dedup_batch(hipStream_t st, const TrBatchItem *items, int nf, int max_n, int ncams, const float2 *kp_xy,
+                              const uint8_t *valid, const TrBest *best, uint32_t *owner, unsigned long long *val, int32_t *slot,
+                              uint8_t *win, TrMatch *matches, int32_t *n_match);
 
 }  // namespace mcorb

@@ -76,7 +76,10 @@ struct mcorb_lmap {
     // scratch of mcorb_lmap_track / mcorb_lmap_track_rig_frame (mcorb_track.cpp), grow-only: the packed input (candidates, then --
     // host arrays only -- the keypoints and the descriptors of every camera; one block, one copy), a rig slot's keypoints
     // (k_track_points), the projections, validity bytes and gathered points, the queries' results, and what the host tail reads:
-    // the compacted rows and the counts per camera, host-mapped pinned memory k_track_compact writes
+    // the compacted rows and the counts per camera, host-mapped pinned memory k_track_compact writes.  mcorb_lmap_track_rig_frames
+    // uses the same buffers, sized for all its frames: the pinned block holds the TrBatchItems, the views and every frame's
+    // candidates, a frame's block of every per-pair array begins at ncams * (its first candidate), the counts are MCORB_MAX_CAMS
+    // per frame and the keypoints nf * ncams rows
     mcorb::HostBuf<uint8_t> h_trackin;
     mcorb::DevBuf<uint8_t> d_trackin;
     mcorb::DevBuf<float2> d_trackkp;
@@ -102,14 +105,16 @@ struct mcorb_lmap {
     // a tracking call that was submitted and not yet waited for (mcorb_lmap_track_submit .. mcorb_lmap_track_wait).  While
     // track_pending is set every other entry refuses (check_lmap) and the scratch above belongs to the call.  launched: a
     // device store has work on its stream; points: k_track_points is part of it.  A host-only store keeps its finished result in
-    // rows / matches
+    // rows / matches.  A call has nf frames (one, but for mcorb_lmap_track_rig_frames): frame f's candidates are cand[first[f] ..
+    // first[f + 1]), its block of rows / matches begins at ncams * first[f], its counts at f * MCORB_MAX_CAMS
     struct TrackCall {
-        int ncams = 0;
+        int ncams = 0, nf = 1;
         bool launched = false, points = false, want_pts = false;
         std::vector<int> cand;
+        std::vector<size_t> first;
         std::vector<mcorb::TrRow> rows;
         std::vector<mcorb::TrMatch> matches;
-        int32_t n_proj[MCORB_MAX_CAMS] = {}, n_match[MCORB_MAX_CAMS] = {};
+        std::vector<int32_t> n_proj, n_match;
     } track_call;
     std::atomic<bool> track_pending{false};
 #ifdef MCORB_TRACK_PROF

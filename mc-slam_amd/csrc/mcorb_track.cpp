@@ -16,7 +16,10 @@
 // serially and keeps the reference's list as it is.  Both entries share the argument and candidate checks, the submission and
 // the output.  A call is a submission and a wait: mcorb_lmap_track_submit / _rig_frame_submit return once everything is on the
 // store's stream, mcorb_lmap_track_wait synchronises and writes the outputs, and the synchronous entries are the two over the
-// same body.  The reference's kd-tree search (FLANN, 4 trees, 64 checks) is approximate and un-vendored: the neighbours here are
+// same body.  mcorb_lmap_track_rig_frames is the slot entry for up to MCORB_TRACK_MAX_FRAMES frames of the slot's job in one submission
+// and one wait (section 4 below): every frame's candidates, one table item per frame and the views go up in one copy and the
+// k_track_*_batch kernels take the frame from the grid's z; a pending call has a frame count, one but for a batch, and
+// mcorb_lmap_track_frames_wait serves any.  The reference's kd-tree search (FLANN, 4 trees, 64 checks) is approximate and un-vendored: the neighbours here are
 // exact.  The store's landmarks are only read: of the map object the call writes its own scratch and, as mcorb_lmap_search
 // does, the per-slot stamps of the candidate walk (tick / stamp), which no call reads as state.
 #include <string.h>
@@ -129,9 +132,10 @@ int check_args(const mcorb_track_view *view, const int32_t *lids, int n_lids, in
     return out ? check_out(out) : MCORB_OK;
 }
 
+// appended to cand: a batch's frames follow each other there, each walked with a stamp value of its own
 int candidates_of(mcorb_lmap *m, const int32_t *lids, int n_lids, std::vector<int> &cand)
 {
-    cand.clear();
+    const size_t from = cand.size();
     for (int i = 0; i < n_lids; i++)
         if (lids[i] < -1 || lids[i] >= m->max_landmarks) return fail(MCORB_E_ARG, "landmark id outside the store");
     const int t = next_tick(m);
@@ -141,22 +145,23 @@ int candidates_of(mcorb_lmap *m, const int32_t *lids, int n_lids, std::vector<in
         m->stamp[l] = t;
         cand.push_back(l);
     }
-    for (int l : cand) {
+    for (size_t i = from; i < cand.size(); i++) {
+        const int l = cand[i];
         if (!(m->flags[l] & kHasPt)) return fail(MCORB_E_STATE, "a candidate landmark has no point");
         if (!(m->flags[l] & kHasDesc)) return fail(MCORB_E_STATE, "a candidate landmark has no descriptor");
     }
-    if ((int)cand.size() > m->max_candidates) return fail(MCORB_E_CAP, "more candidates than max_candidates");
+    if (cand.size() - from > (size_t)m->max_candidates) return fail(MCORB_E_CAP, "more candidates than max_candidates");
     return MCORB_OK;
 }
 
 // ---- 2. per camera the kept candidates in candidate order -- the projection and the query's result -- and the de-duplicated
 // matches ----
 // a host-only store: mcorb_track.h serially
-void rows_on_host(const mcorb_lmap *m, const mcorb_track_view &view, const Frame &f, const std::vector<int> &cand, double max_d2,
-                  int max_hamming, std::vector<TrRow> &rows, int32_t *n_proj)
+// (cand, rows: the frame's nc candidates and its block of C * nc rows)
+void rows_on_host(const mcorb_lmap *m, const mcorb_track_view &view, const Frame &f, const int *cand, int nc, double max_d2,
+                  int max_hamming, TrRow *rows, int32_t *n_proj)
 {
-    const int C = view.ncams, nc = (int)cand.size();
-    rows.resize((size_t)C * nc);
+    const int C = view.ncams;
     for (int c = 0; c < C; c++) n_proj[c] = 0;
     for (int i = 0; i < nc; i++) {
         double p0[3];
@@ -174,9 +179,8 @@ void rows_on_host(const mcorb_lmap *m, const mcorb_track_view &view, const Frame
 // the de-duplication (querryEachFrame:380-415) of a host-only store: the reference's list as it is, serial per camera over the rows
 // with a match -> matches[c * nc + 0 .. n_match[c]).  What the search compares, the pixel of the entry's keypoint, is kept beside
 // the list as one 64-bit key per entry: the scan reads 8 bytes an entry and stays in the first-level cache
-void dedup_on_host(int C, int nc, const TrRow *rows, const int32_t *n_proj, const KpRows &kp, std::vector<TrMatch> &matches, int32_t *n_match)
+void dedup_on_host(int C, int nc, const TrRow *rows, const int32_t *n_proj, const KpRows &kp, TrMatch *matches, int32_t *n_match)
 {
-    matches.resize((size_t)C * nc);
     std::vector<TrMatch> list;
     std::vector<uint64_t> keys;   // of the camera's list, entry by entry
     for (int c = 0; c < C; c++) {
@@ -199,7 +203,7 @@ void dedup_on_host(int C, int nc, const TrRow *rows, const int32_t *n_proj, cons
             keys.push_back(key);
         }
         n_match[c] = (int32_t)list.size();
-        std::copy(list.begin(), list.end(), matches.begin() + (ptrdiff_t)((size_t)c * nc));
+        std::copy(list.begin(), list.end(), matches + (size_t)c * nc);
     }
 }
 
@@ -309,20 +313,25 @@ int submit_body(mcorb_lmap *m, const mcorb_track_view *view, const Frame &f, con
 {
     Phases ph(m, true);
     mcorb_lmap::TrackCall &tc = m->track_call;
+    tc.cand.clear();
     TRY(candidates_of(m, lids, n_lids, tc.cand));
     if (out) out->n_candidates = (int)tc.cand.size();   // (the synchronous entries: set from here on, whatever follows)
     ph.mark(0);
     const int C = view->ncams, nc = (int)tc.cand.size();
     tc.ncams = C;
+    tc.nf = 1;
+    tc.first.assign({(size_t)0, (size_t)nc});
     tc.launched = tc.points = false;
     tc.want_pts = want_pts;
-    memset(tc.n_proj, 0, sizeof(tc.n_proj));
-    memset(tc.n_match, 0, sizeof(tc.n_match));
+    tc.n_proj.assign(MCORB_MAX_CAMS, 0);
+    tc.n_match.assign(MCORB_MAX_CAMS, 0);
     if (!nc) return MCORB_OK;
     if (m->device < 0) {
-        rows_on_host(m, *view, f, tc.cand, max_d2, max_hamming, tc.rows, tc.n_proj);
+        tc.rows.resize((size_t)C * nc);
+        tc.matches.resize((size_t)C * nc);
+        rows_on_host(m, *view, f, tc.cand.data(), nc, max_d2, max_hamming, tc.rows.data(), tc.n_proj.data());
         ph.mark(2);
-        dedup_on_host(C, nc, tc.rows.data(), tc.n_proj, f.kp, tc.matches, tc.n_match);
+        dedup_on_host(C, nc, tc.rows.data(), tc.n_proj.data(), f.kp, tc.matches.data(), tc.n_match.data());
         ph.mark(3);
         return MCORB_OK;
     }
@@ -337,16 +346,17 @@ int submit_body(mcorb_lmap *m, const mcorb_track_view *view, const Frame &f, con
     return MCORB_OK;
 }
 
-// the synchronisation, the event times and the outputs: per camera the projected lists as the rows have them and the matches,
-// lid = cand[i].  pts: [nc][3] of a device store.  checked: out is a synchronous entry's, which check_args has seen and cleared
-int wait_body(mcorb_lmap *m, mcorb_track_out *out, bool checked)
+// the synchronisation, the event times and the outputs of the pending call's frames: per camera the projected lists as the rows have
+// them and the matches, lid = cand[i].  pts: [nc][3] of a device store.  checked: outs are a synchronous entry's, which the
+// argument checks have seen and cleared.  single: mcorb_lmap_track_wait, which serves no batch of more than one frame
+int wait_body(mcorb_lmap *m, mcorb_track_out *outs, int n_outs, bool checked, bool single)
 {
     Phases ph(m, false);
     const mcorb_lmap::TrackCall &tc = m->track_call;
-    const int C = tc.ncams, nc = (int)tc.cand.size();
+    const int C = tc.ncams, nf = tc.nf;
     const TrRow *rows = tc.rows.data();
     const TrMatch *matches = tc.matches.data();
-    const int32_t *n_proj = tc.n_proj, *n_match = tc.n_match;
+    const int32_t *n_proj = tc.n_proj.data(), *n_match = tc.n_match.data();
     const double *pts = nullptr;
     if (tc.launched) {
         HIPCHK(hipSetDevice(m->device));
@@ -374,39 +384,55 @@ int wait_body(mcorb_lmap *m, mcorb_track_out *out, bool checked)
     }
     ph.mark(3);
     if (!checked) {
-        if (!out) return fail(MCORB_E_ARG, "bad argument");
-        clear_counts(out);
-        TRY(check_out(out));
+        if (!outs || n_outs < 1) return fail(MCORB_E_ARG, "bad argument");
+        for (int f = 0; f < n_outs; f++) clear_counts(&outs[f]);
+        if (single && nf != 1) return fail(MCORB_E_STATE, "the pending call is a batch: mcorb_lmap_track_frames_wait serves it");
+        if (n_outs != nf) return fail(MCORB_E_ARG, "n_outs is not the pending call's frame count");
+        for (int f = 0; f < nf; f++) TRY(check_out(&outs[f]));
     }
-    if (out->match_pt && !tc.want_pts) return fail(MCORB_E_ARG, "match_pt of a call that was submitted without want_pts");
-    out->n_candidates = nc;
-    if (!nc) return MCORB_OK;
-    const int cap_p = out->cap_proj, cap_m = out->cap_match;
+    for (int f = 0; f < nf; f++)
+        if (outs[f].match_pt && !tc.want_pts) return fail(MCORB_E_ARG, "match_pt of a call that was submitted without want_pts");
+    // every count of every frame, then -- unless one is short -- the arrays
     bool is_short = false;
-    for (int c = 0; c < C; c++) {
-        out->n_proj[c] = n_proj[c];
-        out->n_match[c] = n_match[c];
-        if (n_proj[c] > cap_p || n_match[c] > cap_m) is_short = true;
+    for (int f = 0; f < nf; f++) {
+        mcorb_track_out *out = &outs[f];
+        const int nc = (int)(tc.first[f + 1] - tc.first[f]);
+        out->n_candidates = nc;
+        if (!nc) continue;
+        for (int c = 0; c < C; c++) {
+            const int np = n_proj[f * MCORB_MAX_CAMS + c], nm = n_match[f * MCORB_MAX_CAMS + c];
+            out->n_proj[c] = np;
+            out->n_match[c] = nm;
+            if (np > out->cap_proj || nm > out->cap_match) is_short = true;
+        }
     }
     if (is_short) return fail(MCORB_E_CAP, "output too small");
-    for (int c = 0; c < C; c++) {
-        const TrRow *row = rows + (size_t)c * nc;
-        const TrMatch *mt = matches + (size_t)c * nc;
-        const size_t op = (size_t)c * cap_p, om = (size_t)c * cap_m;
-        for (int r = 0; r < n_proj[c]; r++) {
-            out->proj_lid[op + r] = tc.cand[row[r].i];
-            out->proj_xy[2 * (op + r)] = row[r].x;
-            out->proj_xy[2 * (op + r) + 1] = row[r].y;
-            out->best_kp[op + r] = row[r].kp;
-            out->best_dist[op + r] = row[r].dist;
-        }
-        for (int k = 0; k < n_match[c]; k++) {
-            const int lid = tc.cand[mt[k].i];
-            out->match_kp[om + k] = mt[k].kp;
-            out->match_lid[om + k] = lid;
-            out->match_dist[om + k] = mt[k].dist;
-            if (out->match_pt)
-                memcpy(out->match_pt + 3 * (om + k), pts ? pts + 3 * (size_t)mt[k].i : &m->geom[(size_t)lid * 6], 3 * sizeof(double));
+    for (int f = 0; f < nf; f++) {
+        mcorb_track_out *out = &outs[f];
+        const int nc = (int)(tc.first[f + 1] - tc.first[f]);
+        const int *cand = tc.cand.data() + tc.first[f];
+        const size_t base = (size_t)C * tc.first[f];
+        const double *fpts = pts ? pts + 3 * tc.first[f] : nullptr;
+        const int cap_p = out->cap_proj, cap_m = out->cap_match;
+        for (int c = 0; c < C && nc; c++) {
+            const TrRow *row = rows + base + (size_t)c * nc;
+            const TrMatch *mt = matches + base + (size_t)c * nc;
+            const size_t op = (size_t)c * cap_p, om = (size_t)c * cap_m;
+            for (int r = 0; r < out->n_proj[c]; r++) {
+                out->proj_lid[op + r] = cand[row[r].i];
+                out->proj_xy[2 * (op + r)] = row[r].x;
+                out->proj_xy[2 * (op + r) + 1] = row[r].y;
+                out->best_kp[op + r] = row[r].kp;
+                out->best_dist[op + r] = row[r].dist;
+            }
+            for (int k = 0; k < out->n_match[c]; k++) {
+                const int lid = cand[mt[k].i];
+                out->match_kp[om + k] = mt[k].kp;
+                out->match_lid[om + k] = lid;
+                out->match_dist[om + k] = mt[k].dist;
+                if (out->match_pt)
+                    memcpy(out->match_pt + 3 * (om + k), fpts ? fpts + 3 * (size_t)mt[k].i : &m->geom[(size_t)lid * 6], 3 * sizeof(double));
+            }
         }
     }
     ph.mark(4);
@@ -420,7 +446,7 @@ int track(mcorb_lmap *m, const mcorb_track_view *view, const Frame &f, const int
     std::lock_guard<std::mutex> lk(m->mu);
     if (m->track_pending.load()) return fail(MCORB_E_STATE, "a submitted tracking call has not been waited for");
     TRY(submit_body(m, view, f, lids, n_lids, max_d2, max_hamming, want_pts, out));
-    if (out) return wait_body(m, out, true);
+    if (out) return wait_body(m, out, 1, true, true);
     m->track_pending.store(true);
     return MCORB_OK;
 }
@@ -493,6 +519,189 @@ int track_slot(mcorb_lmap *m, const mcorb_track_view *view, mcorb_rig *r, int sl
     return track(m, view, f, lids, n_lids, max_d2, max_hamming, want_pts, out);
 }
 
+// ---- 4. the batch: nf frames of a slot's last extraction in one submission (mcorb_lmap_track_rig_frames) ----
+// A device store: what submit_on_device puts on the stream, once for all frames -- the _batch kernels take the frame from
+// blockIdx.z.  The pinned block holds the TrBatchItem per frame, the views and the frames' candidates back to back, and goes up in
+// one copy.  Frame f's block of every per-pair array begins at C * first[f] and has the single call's layout; its
+// de-duplication tables have the single call's size and follow the frames' before it
+int submit_frames_on_device(mcorb_lmap *m, const mcorb_track_view *views, const std::vector<Frame> &fr, const int32_t *frames,
+                            const mcorb_lmap::TrackCall &tc, double max_d2, int max_hamming, bool want_pts)
+{
+    const int C = tc.ncams, nf = tc.nf;
+    const size_t total = tc.first[nf], rows = (size_t)C * total;
+    const Frame &f0 = fr[0];
+    const int kcap = f0.rig->geom.kcap;
+    HIPCHK(hipSetDevice(m->device));
+    (void)hipGetLastError();   // (a stale error of this thread is not this call's: submit_on_device)
+    hipStream_t st = m->st;
+    const size_t off_views = round32((size_t)nf * sizeof(TrBatchItem)), off_cand = off_views + round32((size_t)nf * sizeof(mcorb_track_view));
+    const size_t bytes = off_cand + total * sizeof(int);
+    size_t slots = 0;
+    int max_n = 0;
+    for (int f = 0; f < nf; f++) {
+        const int n = (int)(tc.first[f + 1] - tc.first[f]);
+        slots += (size_t)C << tr_dedup_log2(n);
+        max_n = std::max(max_n, n);
+    }
+    TRY(m->h_trackin.grow(bytes, hipHostMallocDefault));
+    TRY(m->d_trackin.grow(bytes));
+    TRY(m->d_trackxy.grow(rows));
+    TRY(m->d_trackvalid.grow(rows));
+    TRY(m->d_trackbest.grow(rows));
+    TRY(m->h_trackrows.grow(rows, kHostMapped));
+    TRY(m->h_tracknproj.grow((size_t)nf * MCORB_MAX_CAMS, kHostMapped));
+    TRY(m->d_trackowner.grow(slots));
+    TRY(m->d_trackval.grow(slots));
+    TRY(m->d_trackslot.grow(rows));
+    TRY(m->d_trackwin.grow(rows));
+    TRY(m->h_trackmatch.grow(rows, kHostMapped));
+    TRY(m->h_tracknmatch.grow((size_t)nf * MCORB_MAX_CAMS, kHostMapped));
+    TRY(m->d_trackkp.grow((size_t)nf * C * kcap));
+    if (want_pts) {
+        TRY(m->d_trackpt.grow(total * 3));
+        TRY(m->h_trackpt.grow(total * 3, hipHostMallocDefault));
+    }
+    uint8_t *in = m->h_trackin;
+    TrBatchItem *items = reinterpret_cast<TrBatchItem *>(in);
+    size_t tab = 0;
+    for (int f = 0; f < nf; f++) {
+        TrBatchItem &it = items[f];
+        memset(&it, 0, sizeof(it));
+        it.view = f;
+        it.n = (int32_t)(tc.first[f + 1] - tc.first[f]);
+        it.log2p = tr_dedup_log2(it.n);
+        it.img0 = frames[f] * C;
+        it.cand_first = tc.first[f];
+        it.rows = (size_t)C * tc.first[f];
+        it.tab = tab;
+        it.kp0 = (size_t)f * C * kcap;
+        it.desc0 = (size_t)it.img0 * kcap;
+        for (int c = 0; c < C; c++) {
+            it.frame.n_kp[c] = fr[f].n_kp[c];
+            it.frame.first[c] = c * kcap;
+        }
+        tab += (size_t)C << it.log2p;
+        if (!it.n)   // no workgroup runs for this frame
+            for (int c = 0; c < MCORB_MAX_CAMS; c++)
+                m->h_tracknproj.get()[(size_t)f * MCORB_MAX_CAMS + c] = m->h_tracknmatch.get()[(size_t)f * MCORB_MAX_CAMS + c] = 0;
+    }
+    memcpy(in + off_views, views, (size_t)nf * sizeof(mcorb_track_view));
+    memcpy(in + off_cand, tc.cand.data(), total * sizeof(int));
+    HIPCHK(hipMemcpyAsync(m->d_trackin, m->h_trackin, bytes, hipMemcpyHostToDevice, st));
+    const TrBatchItem *d_items = reinterpret_cast<const TrBatchItem *>(m->d_trackin.get());
+    const mcorb_track_view *d_views = reinterpret_cast<const mcorb_track_view *>(m->d_trackin.get() + off_views);
+    const int *d_cand = reinterpret_cast<const int *>(m->d_trackin.get() + off_cand);
+    const uint32_t *sel;
+    const int *nsel;
+    slot_sel(*f0.slot, sel, nsel);
+    HIPCHK(hipEventRecord(m->ev12, st));
+    launch_track_points_batch(st, d_items, nf, sel, nsel, kcap, C, f0.rig->tab.scale, f0.rig->tab.nlevels, m->d_trackkp);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(m->ev8, st));
+    launch_track_project_batch(st, d_items, nf, max_n, d_views, m->d_geom, d_cand, m->d_trackxy, m->d_trackvalid,
+                               want_pts ? m->d_trackpt.get() : nullptr);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(m->ev9, st));
+    launch_track_match_batch(st, d_items, nf, max_n, C, m->d_trackkp, f0.slot->d_desc.get(), m->d_desc, d_cand, m->d_trackxy, m->d_trackvalid,
+                             max_d2, max_hamming, m->d_trackbest);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(m->ev10, st));
+    launch_track_compact_batch(st, d_items, nf, max_n, C, m->d_trackvalid, m->d_trackxy, m->d_trackbest, m->h_trackrows, m->h_tracknproj);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(m->ev11, st));
+    HIPCHK(hipMemsetAsync(m->d_trackowner, 0xff, slots * sizeof(uint32_t), st));
+    HIPCHK(hipMemsetAsync(m->d_trackval, 0xff, slots * sizeof(unsigned long long), st));
+    launch_track_dedup_batch(st, d_items, nf, max_n, C, m->d_trackkp, m->d_trackvalid, m->d_trackbest, m->d_trackowner, m->d_trackval,
+                             m->d_trackslot, m->d_trackwin, m->h_trackmatch, m->h_tracknmatch);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(m->ev13, st));
+    if (want_pts) HIPCHK(hipMemcpyAsync(m->h_trackpt, m->d_trackpt, total * 3 * sizeof(double), hipMemcpyDeviceToHost, st));
+    return MCORB_OK;
+}
+
+// the candidates of every frame, one stamp value each, then the call: frame by frame on a host-only store, one submission on a
+// device store.  The caller holds the store's lock
+int submit_frames_body(mcorb_lmap *m, const mcorb_track_view *views, const std::vector<Frame> &fr, const int32_t *frames, int nf,
+                       const int32_t *lids, const int32_t *lid_first, double max_d2, int max_hamming, bool want_pts, mcorb_track_out *outs)
+{
+    Phases ph(m, true);
+    mcorb_lmap::TrackCall &tc = m->track_call;
+    const int C = views[0].ncams;
+    tc.cand.clear();
+    tc.first.assign(1, 0);
+    for (int f = 0; f < nf; f++) {
+        TRY(candidates_of(m, lids + lid_first[f], lid_first[f + 1] - lid_first[f], tc.cand));
+        tc.first.push_back(tc.cand.size());
+    }
+    if (outs)
+        for (int f = 0; f < nf; f++) outs[f].n_candidates = (int)(tc.first[f + 1] - tc.first[f]);
+    ph.mark(0);
+    const size_t total = tc.cand.size();
+    tc.ncams = C;
+    tc.nf = nf;
+    tc.launched = tc.points = false;
+    tc.want_pts = want_pts;
+    tc.n_proj.assign((size_t)nf * MCORB_MAX_CAMS, 0);
+    tc.n_match.assign((size_t)nf * MCORB_MAX_CAMS, 0);
+    if (!total) return MCORB_OK;
+    if (m->device < 0) {
+        tc.rows.resize((size_t)C * total);
+        tc.matches.resize((size_t)C * total);
+        for (int f = 0; f < nf; f++) {
+            const int nc = (int)(tc.first[f + 1] - tc.first[f]);
+            if (!nc) continue;
+            TrRow *rows = tc.rows.data() + (size_t)C * tc.first[f];
+            int32_t *n_proj = tc.n_proj.data() + (size_t)f * MCORB_MAX_CAMS;
+            rows_on_host(m, views[f], fr[f], tc.cand.data() + tc.first[f], nc, max_d2, max_hamming, rows, n_proj);
+            dedup_on_host(C, nc, rows, n_proj, fr[f].kp, tc.matches.data() + (size_t)C * tc.first[f],
+                          tc.n_match.data() + (size_t)f * MCORB_MAX_CAMS);
+        }
+        ph.mark(3);
+        return MCORB_OK;
+    }
+    const int r = submit_frames_on_device(m, views, fr, frames, tc, max_d2, max_hamming, want_pts);
+    if (r != MCORB_OK) {
+        (void)hipStreamSynchronize(m->st);
+        return r;
+    }
+    tc.launched = tc.points = true;
+    ph.mark(1);
+    return MCORB_OK;
+}
+
+// the batched slot entry, synchronous (outs) or a submission (outs == NULL)
+int track_slot_frames(mcorb_lmap *m, const mcorb_track_view *views, mcorb_rig *r, int slot, const int32_t *frames, int nf,
+                      const int32_t *lids, const int32_t *lid_first, double max_d2, int max_hamming, bool want_pts, mcorb_track_out *outs,
+                      bool with_out)
+{
+    if (with_out && outs)
+        for (int f = 0; f < nf; f++) clear_counts(&outs[f]);
+    TRY(check_lmap(m, "lmap track_rig_frames"));
+    if (nf < 1 || nf > MCORB_TRACK_MAX_FRAMES) return fail(MCORB_E_ARG, "1 .. MCORB_TRACK_MAX_FRAMES frames");
+    if (!views || !frames || !lid_first || (with_out && !outs) || max_hamming < 0) return fail(MCORB_E_ARG, "bad argument");
+    if (lid_first[0] < 0) return fail(MCORB_E_ARG, "a negative lid_first");
+    for (int f = 0; f < nf; f++)
+        if (lid_first[f + 1] < lid_first[f]) return fail(MCORB_E_ARG, "lid_first decreases");
+    if (lid_first[nf] > lid_first[0] && !lids) return fail(MCORB_E_ARG, "bad argument");
+    for (int f = 0; f < nf; f++)
+        if (views[f].ncams < 1 || views[f].ncams > MCORB_MAX_CAMS) return fail(MCORB_E_ARG, "1 .. MCORB_MAX_CAMS cameras");
+    if (with_out)
+        for (int f = 0; f < nf; f++) TRY(check_out(&outs[f]));
+    std::vector<Frame> fr((size_t)nf);
+    for (int f = 0; f < nf; f++) TRY(frame_of_slot(m, &views[f], r, slot, frames[f], fr[f]));
+    std::lock_guard<std::mutex> lk(m->mu);
+    if (m->track_pending.load()) return fail(MCORB_E_STATE, "a submitted tracking call has not been waited for");
+    const int rc = submit_frames_body(m, views, fr, frames, nf, lids, lid_first, max_d2, max_hamming, want_pts, with_out ? outs : nullptr);
+    if (rc != MCORB_OK) {
+        if (with_out)
+            for (int f = 0; f < nf; f++) clear_counts(&outs[f]);
+        return rc;
+    }
+    if (with_out) return wait_body(m, outs, nf, true, false);
+    m->track_pending.store(true);
+    return MCORB_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -526,9 +735,32 @@ int mcorb_lmap_track_wait(mcorb_lmap *m, mcorb_track_out *out)
     TRY(check_lmap_handle(m, "lmap track_wait"));
     std::lock_guard<std::mutex> lk(m->mu);
     if (!m->track_pending.load()) return fail(MCORB_E_STATE, "no tracking call was submitted");
-    const int r = wait_body(m, out, false);
+    const int r = wait_body(m, out, 1, false, true);
     m->track_pending.store(false);
     return r;
+}
+
+int mcorb_lmap_track_frames_wait(mcorb_lmap *m, mcorb_track_out *outs, int n_outs)
+{
+    TRY(check_lmap_handle(m, "lmap track_frames_wait"));
+    std::lock_guard<std::mutex> lk(m->mu);
+    if (!m->track_pending.load()) return fail(MCORB_E_STATE, "no tracking call was submitted");
+    const int r = wait_body(m, outs, n_outs, false, false);
+    m->track_pending.store(false);
+    return r;
+}
+
+int mcorb_lmap_track_rig_frames_submit(mcorb_lmap *m, const mcorb_track_view *views, mcorb_rig *r, int slot, const int32_t *frames, int nf,
+                                       const int32_t *lids, const int32_t *lid_first, double max_d2, int max_hamming, int want_pts)
+{
+    return track_slot_frames(m, views, r, slot, frames, nf, lids, lid_first, max_d2, max_hamming, want_pts != 0, nullptr, false);
+}
+
+int mcorb_lmap_track_rig_frames(mcorb_lmap *m, const mcorb_track_view *views, mcorb_rig *r, int slot, const int32_t *frames, int nf,
+                                const int32_t *lids, const int32_t *lid_first, double max_d2, int max_hamming, int want_pts,
+                                mcorb_track_out *outs)
+{
+    return track_slot_frames(m, views, r, slot, frames, nf, lids, lid_first, max_d2, max_hamming, want_pts != 0, outs, true);
 }
 
 int32_t mcorb_host_track_pixel(float v) { return tr_pixel_coord(v); }

@@ -134,5 +134,16 @@ struct TrRow { int32_t i; float x, y; int32_t kp, dist; };
 // an entry of a camera's de-duplicated list: the candidate's place in the call's list, its keypoint, the distance.  A camera's
 // entries are n_match of them from entry c * n (k_track_dedup_emit on a device store, the serial list on a host-only one)
 struct TrMatch { int32_t i, kp, dist; };
+// One frame of a batched slot call (mcorb_lmap_track_rig_frames), as the _batch kernels read it from device memory, frame
+// blockIdx.z: its view's place among the call's views; its n candidates, cand_first candidates into the call's list; rows: where
+// its block of every per-pair array begins, ncams * cand_first -- inside the block the layout is the single call's [c * n + i];
+// tab: where its de-duplication tables begin, ncams << log2p slots; frame: its keypoints in the store's keypoint buffer from kp0
+// on (first[c] = c * kcap, row (f * ncams + c) * kcap overall) and in the slot's descriptors from keypoint desc0 = img0 * kcap on,
+// img0 being its first image of the slot
+struct TrBatchItem {
+    int32_t view, n, log2p, img0;
+    uint64_t cand_first, rows, tab, kp0, desc0;
+    TrFrame frame;
+};
 
 }  // namespace mcorb

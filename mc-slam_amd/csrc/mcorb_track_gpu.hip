@@ -4,7 +4,9 @@
 // The arithmetic is mcorb_track.h, the code the host-only store runs.  k_track_points (mcorb_lmap_track_rig_frame only) rebuilds a
 // rig slot's keypoints from their packed selection words; k_track_compact leaves each camera's kept candidates in candidate
 // order, in host-mapped memory; k_track_dedup_min / _win / _emit leave each camera's de-duplicated matches there (querryEachFrame
-// :380-415 in closed form).  No extraction job runs them and no benchmark leg times them.
+// :380-415 in closed form).  Each kernel's body is a __device__ function that takes the view or frame by reference, the base pointers
+// and n; a k_track_* entry calls it with its kernel arguments (one frame, the single calls), its k_track_*_batch twin with what
+// the TrBatchItem of frame blockIdx.z says (mcorb_lmap_track_rig_frames).  No extraction job runs them and no benchmark leg times them.
 //
 // They go out in one submission: k_track_match reads the validity bytes k_track_project wrote and the points k_track_points
 // wrote, k_track_compact and the de-duplication read the rows of the kernels before them, and the host copies rows and matches
@@ -25,9 +27,8 @@ namespace mcorb {
 // per camera come through the scalar cache.  A lane's own traffic is its 24 bytes of point, gathered by landmark id, and per
 // camera the plain stores of (x, y) and the validity byte, camera-major, so that a camera's row is contiguous for k_track_match;
 // pts (may be NULL) receives the gathered point, for bestMatchLandmarks.
-__global__ __launch_bounds__(kTrackProjectT) void k_track_project(mcorb_track_view view, const double *__restrict__ geom,
-                                                                  const int *__restrict__ cand, int n, float2 *__restrict__ xy,
-                                                                  uint8_t *__restrict__ valid, double *__restrict__ pts)
+__device__ __forceinline__ void track_project(const mcorb_track_view &view, const double *__restrict__ geom, const int *__restrict__ cand,
+                                              int n, float2 *__restrict__ xy, uint8_t *__restrict__ valid, double *__restrict__ pts)
 {
     const int i = blockIdx.x * kTrackProjectT + threadIdx.x;
     if (i >= n) return;
@@ -47,12 +48,43 @@ __global__ __launch_bounds__(kTrackProjectT) void k_track_project(mcorb_track_vi
     }
 }
 
+__global__ __launch_bounds__(kTrackProjectT) void k_track_project(mcorb_track_view view, const double *__restrict__ geom,
+                                                                  const int *__restrict__ cand, int n, float2 *__restrict__ xy,
+                                                                  uint8_t *__restrict__ valid, double *__restrict__ pts)
+{
+    track_project(view, geom, cand, n, xy, valid, pts);
+}
+
+// The _batch entries (mcorb_lmap_track_rig_frames): blockIdx.z is the frame, whose TrBatchItem -- and, here, view -- is read from
+// device memory at an address that is uniform over the wave, so it stays in scalar registers as a kernel argument does.  The
+// grid's x is sized by the frame with the most candidates: a workgroup beyond its own frame's n leaves, uniformly.  A frame's
+// block of every per-pair array begins at item.rows and has the single call's layout, so the bodies are the single call's
+__global__ __launch_bounds__(kTrackProjectT) void k_track_project_batch(const TrBatchItem *__restrict__ items,
+                                                                        const mcorb_track_view *__restrict__ views,
+                                                                        const double *__restrict__ geom, const int *__restrict__ cand,
+                                                                        float2 *__restrict__ xy, uint8_t *__restrict__ valid,
+                                                                        double *__restrict__ pts)
+{
+    const TrBatchItem &it = items[blockIdx.z];
+    if ((int)(blockIdx.x * kTrackProjectT) >= it.n) return;
+    track_project(views[it.view], geom, cand + it.cand_first, it.n, xy + it.rows, valid + it.rows,
+                  pts ? pts + 3 * it.cand_first : nullptr);
+}
+
 void launch_track_project(hipStream_t st, const mcorb_track_view &view, const double *geom, const int *cand, int n, float2 *xy,
                           uint8_t *valid, double *pts)
 {
     if (n < 1) return;
     hipLaunchKernelGGL(k_track_project, dim3((n + kTrackProjectT - 1) / kTrackProjectT), dim3(kTrackProjectT), 0, st, view, geom, cand,
                        n, xy, valid, pts);
+}
+
+void launch_track_project_batch(hipStream_t st, const TrBatchItem *items, int nf, int max_n, const mcorb_track_view *views,
+                                const double *geom, const int *cand, float2 *xy, uint8_t *valid, double *pts)
+{
+    if (nf < 1 || max_n < 1) return;
+    hipLaunchKernelGGL(k_track_project_batch, dim3((max_n + kTrackProjectT - 1) / kTrackProjectT, 1, nf), dim3(kTrackProjectT), 0, st,
+                       items, views, geom, cand, xy, valid, pts);
 }
 
 // A workgroup of kTrackMatchWaves waves serves camera blockIdx.y; a wave serves kTrackMatchQ consecutive candidates.  The
@@ -103,13 +135,11 @@ __device__ __forceinline__ void track_tile_query(const float2 *tile, int tile_n,
     }
 }
 
-__global__ __launch_bounds__(kTrackMatchT) void k_track_match(TrFrame frame, const float2 *__restrict__ kp_xy,
-                                                              const uint32_t *__restrict__ kp_desc, const uint32_t *__restrict__ lm_desc,
-                                                              const int *__restrict__ cand, int n, const float2 *__restrict__ xy,
-                                                              const uint8_t *__restrict__ valid, double max_d2, int max_hamming,
-                                                              TrBest *__restrict__ best)
+__device__ __forceinline__ void track_match(float2 *tile, const TrFrame &frame, const float2 *__restrict__ kp_xy,
+                                            const uint32_t *__restrict__ kp_desc, const uint32_t *__restrict__ lm_desc,
+                                            const int *__restrict__ cand, int n, const float2 *__restrict__ xy,
+                                            const uint8_t *__restrict__ valid, double max_d2, int max_hamming, TrBest *__restrict__ best)
 {
-    __shared__ float2 tile[MCORB_TRACK_TILE];
     const int c = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int n_kp = frame.n_kp[c], first = frame.first[c];
     const int q0 = (blockIdx.x * kTrackMatchWaves + wave) * kTrackMatchQ;
@@ -162,6 +192,29 @@ __global__ __launch_bounds__(kTrackMatchT) void k_track_match(TrFrame frame, con
     }
 }
 
+__global__ __launch_bounds__(kTrackMatchT) void k_track_match(TrFrame frame, const float2 *__restrict__ kp_xy,
+                                                              const uint32_t *__restrict__ kp_desc, const uint32_t *__restrict__ lm_desc,
+                                                              const int *__restrict__ cand, int n, const float2 *__restrict__ xy,
+                                                              const uint8_t *__restrict__ valid, double max_d2, int max_hamming,
+                                                              TrBest *__restrict__ best)
+{
+    __shared__ float2 tile[MCORB_TRACK_TILE];
+    track_match(tile, frame, kp_xy, kp_desc, lm_desc, cand, n, xy, valid, max_d2, max_hamming, best);
+}
+
+__global__ __launch_bounds__(kTrackMatchT) void k_track_match_batch(const TrBatchItem *__restrict__ items, const float2 *__restrict__ kp_xy,
+                                                                    const uint32_t *__restrict__ kp_desc,
+                                                                    const uint32_t *__restrict__ lm_desc, const int *__restrict__ cand,
+                                                                    const float2 *__restrict__ xy, const uint8_t *__restrict__ valid,
+                                                                    double max_d2, int max_hamming, TrBest *__restrict__ best)
+{
+    __shared__ float2 tile[MCORB_TRACK_TILE];
+    const TrBatchItem &it = items[blockIdx.z];
+    if ((int)(blockIdx.x * (kTrackMatchWaves * kTrackMatchQ)) >= it.n) return;
+    track_match(tile, it.frame, kp_xy + it.kp0, kp_desc + it.desc0 * 8, lm_desc, cand + it.cand_first, it.n, xy + it.rows,
+                valid + it.rows, max_d2, max_hamming, best + it.rows);
+}
+
 void launch_track_match(hipStream_t st, const TrFrame &frame, int ncams, const float2 *kp_xy, const uint8_t *kp_desc, const uint8_t *lm_desc,
                         const int *cand, int n, const float2 *xy, const uint8_t *valid, double max_d2, int max_hamming, TrBest *best)
 {
@@ -172,15 +225,42 @@ void launch_track_match(hipStream_t st, const TrFrame &frame, int ncams, const f
                        max_d2, max_hamming, best);
 }
 
+void launch_track_match_batch(hipStream_t st, const TrBatchItem *items, int nf, int max_n, int ncams, const float2 *kp_xy,
+                              const uint8_t *kp_desc, const uint8_t *lm_desc, const int *cand, const float2 *xy, const uint8_t *valid,
+                              double max_d2, int max_hamming, TrBest *best)
+{
+    if (nf < 1 || max_n < 1) return;
+    const int per_block = kTrackMatchWaves * kTrackMatchQ;
+    hipLaunchKernelGGL(k_track_match_batch, dim3((max_n + per_block - 1) / per_block, ncams, nf), dim3(kTrackMatchT), 0, st, items, kp_xy,
+                       reinterpret_cast<const uint32_t *>(kp_desc), reinterpret_cast<const uint32_t *>(lm_desc), cand, xy, valid, max_d2,
+                       max_hamming, best);
+}
+
 // One lane per keypoint of a row of kcap, camera c's image being img0 + c of the slot: pt as the host's keypoint record has it
 // (sel_point), for k_track_match's tiles.  A pass of its own: on a small batch sel / nsel are host-mapped memory, which is read
 // here once and not once per workgroup of k_track_match.  The padding of a row (k >= nsel) is not written and never read.
-__global__ __launch_bounds__(kTrackPointsT) void k_track_points(const uint32_t *__restrict__ sel, const int *__restrict__ nsel, int kcap,
-                                                                int img0, UndistScales sc, float2 *__restrict__ out)
+__device__ __forceinline__ void track_points(const uint32_t *__restrict__ sel, const int *__restrict__ nsel, int kcap, int img0,
+                                             const UndistScales &sc, float2 *__restrict__ out)
 {
     const int c = blockIdx.y, m = img0 + c, k = blockIdx.x * kTrackPointsT + threadIdx.x;
     if (k >= min(nsel[m], kcap)) return;
     out[(size_t)c * kcap + k] = sel_point(sel[(size_t)m * kcap + k], sc);
+}
+
+__global__ __launch_bounds__(kTrackPointsT) void k_track_points(const uint32_t *__restrict__ sel, const int *__restrict__ nsel, int kcap,
+                                                                int img0, UndistScales sc, float2 *__restrict__ out)
+{
+    track_points(sel, nsel, kcap, img0, sc, out);
+}
+
+// frame f's images img0 .. img0 + ncams -> rows (f * ncams + c) * kcap of out, f's kp0 on: a frame named twice is converted twice
+__global__ __launch_bounds__(kTrackPointsT) void k_track_points_batch(const TrBatchItem *__restrict__ items, const uint32_t *__restrict__ sel,
+                                                                      const int *__restrict__ nsel, int kcap, UndistScales sc,
+                                                                      float2 *__restrict__ out)
+{
+    const TrBatchItem &it = items[blockIdx.z];
+    if (it.n < 1) return;   // (no kernel reads the keypoints of a frame without candidates)
+    track_points(sel, nsel, kcap, it.img0, sc, out + it.kp0);
 }
 
 void launch_track_points(hipStream_t st, const uint32_t *sel, const int *nsel, int kcap, int img0, int ncams, const float *scale,
@@ -191,17 +271,24 @@ void launch_track_points(hipStream_t st, const uint32_t *sel, const int *nsel, i
                        kcap, img0, UndistScales(scale, nlevels), out);
 }
 
+void launch_track_points_batch(hipStream_t st, const TrBatchItem *items, int nf, const uint32_t *sel, const int *nsel, int kcap, int ncams,
+                               const float *scale, int nlevels, float2 *out)
+{
+    if (kcap < 1 || ncams < 1 || nf < 1) return;
+    hipLaunchKernelGGL(k_track_points_batch, dim3((kcap + kTrackPointsT - 1) / kTrackPointsT, ncams, nf), dim3(kTrackPointsT), 0, st,
+                       items, sel, nsel, kcap, UndistScales(scale, nlevels), out);
+}
+
 // The ordered stream compaction of camera blockIdx.y's validity bytes (each 0 or 1, as k_track_project writes them).  Workgroup b
 // serves candidates b * 256 .. b * 256 + 255 and counts the kept ones before them itself: valid[c * n .. c * n + b * 256) in
 // 16-byte loads from the first 16-byte boundary of the row on (the up to 15 bytes in front of it and as many behind the last
 // whole load byte by byte), a wave reduction and four partials through LDS -- at most n bytes, from L2, so n * n / 512 per
 // camera.  Its own 256 flags are ranked by a ballot per wave.  No workgroup waits on another; the last one of a camera has the
 // camera's total.
-__global__ __launch_bounds__(kTrackCompactT) void k_track_compact(int n, const uint8_t *__restrict__ valid, const float2 *__restrict__ xy,
-                                                                  const TrBest *__restrict__ best, TrRow *__restrict__ rows,
-                                                                  int32_t *__restrict__ n_proj)
+__device__ __forceinline__ void track_compact(int *before, int *kept, int n, const uint8_t *__restrict__ valid,
+                                              const float2 *__restrict__ xy, const TrBest *__restrict__ best, TrRow *__restrict__ rows,
+                                              int32_t *__restrict__ n_proj)
 {
-    __shared__ int before[kTrackCompactT / 64], kept[kTrackCompactT / 64];
     const int c = blockIdx.y, b = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
     if (b * kTrackCompactT >= n) return;   // (uniform over the workgroup)
     const size_t row = (size_t)c * n;
@@ -237,7 +324,27 @@ __global__ __launch_bounds__(kTrackCompactT) void k_track_compact(int n, const u
         const TrBest r = best[row + i];
         rows[row + lane_rank(mask, at)] = TrRow{i, q.x, q.y, r.kp, r.dist};
     }
-    if (b == (int)gridDim.x - 1 && t == 0) n_proj[c] = total;
+    if (b == (n - 1) / kTrackCompactT && t == 0) n_proj[c] = total;   // (the last workgroup of n, whatever the grid)
+}
+
+__global__ __launch_bounds__(kTrackCompactT) void k_track_compact(int n, const uint8_t *__restrict__ valid, const float2 *__restrict__ xy,
+                                                                  const TrBest *__restrict__ best, TrRow *__restrict__ rows,
+                                                                  int32_t *__restrict__ n_proj)
+{
+    __shared__ int before[kTrackCompactT / 64], kept[kTrackCompactT / 64];
+    track_compact(before, kept, n, valid, xy, best, rows, n_proj);
+}
+
+// n_proj: MCORB_MAX_CAMS counts per frame
+__global__ __launch_bounds__(kTrackCompactT) void k_track_compact_batch(const TrBatchItem *__restrict__ items,
+                                                                        const uint8_t *__restrict__ valid, const float2 *__restrict__ xy,
+                                                                        const TrBest *__restrict__ best, TrRow *__restrict__ rows,
+                                                                        int32_t *__restrict__ n_proj)
+{
+    __shared__ int before[kTrackCompactT / 64], kept[kTrackCompactT / 64];
+    const TrBatchItem &it = items[blockIdx.z];
+    track_compact(before, kept, it.n, valid + it.rows, xy + it.rows, best + it.rows, rows + it.rows,
+                  n_proj + (size_t)blockIdx.z * MCORB_MAX_CAMS);
 }
 
 void launch_track_compact(hipStream_t st, int ncams, int n, const uint8_t *valid, const float2 *xy, const TrBest *best, TrRow *rows,
@@ -246,6 +353,14 @@ void launch_track_compact(hipStream_t st, int ncams, int n, const uint8_t *valid
     if (n < 1) return;
     hipLaunchKernelGGL(k_track_compact, dim3((n + kTrackCompactT - 1) / kTrackCompactT, ncams), dim3(kTrackCompactT), 0, st, n, valid, xy,
                        best, rows, n_proj);
+}
+
+void launch_track_compact_batch(hipStream_t st, const TrBatchItem *items, int nf, int max_n, int ncams, const uint8_t *valid,
+                                const float2 *xy, const TrBest *best, TrRow *rows, int32_t *n_proj)
+{
+    if (nf < 1 || max_n < 1) return;
+    hipLaunchKernelGGL(k_track_compact_batch, dim3((max_n + kTrackCompactT - 1) / kTrackCompactT, ncams, nf), dim3(kTrackCompactT), 0, st,
+                       items, valid, xy, best, rows, n_proj);
 }
 
 // ---- the de-duplication (mcorb_track.h, tr_dedup_value): per camera a segmented arg-min over the matched candidates, grouped by
@@ -263,10 +378,10 @@ void launch_track_compact(hipStream_t st, int ncams, int n, const uint8_t *valid
 // No workgroup waits on another, no scratch.
 constexpr uint32_t kTrNoOwner = ~0u;
 
-__global__ __launch_bounds__(kTrackDedupT) void k_track_dedup_min(TrFrame frame, const float2 *__restrict__ kp_xy, int n,
-                                                                  const uint8_t *__restrict__ valid, const TrBest *__restrict__ best,
-                                                                  int log2p, uint32_t *__restrict__ owner,
-                                                                  unsigned long long *__restrict__ val, int32_t *__restrict__ slot)
+__device__ __forceinline__ void track_dedup_min(const TrFrame &frame, const float2 *__restrict__ kp_xy, int n,
+                                                const uint8_t *__restrict__ valid, const TrBest *__restrict__ best, int log2p,
+                                                uint32_t *__restrict__ owner, unsigned long long *__restrict__ val,
+                                                int32_t *__restrict__ slot)
 {
     const int c = blockIdx.y, i = blockIdx.x * kTrackDedupT + threadIdx.x;
     if (i >= n) return;
@@ -296,10 +411,30 @@ __global__ __launch_bounds__(kTrackDedupT) void k_track_dedup_min(TrFrame frame,
     slot[row + i] = mine;
 }
 
+__global__ __launch_bounds__(kTrackDedupT) void k_track_dedup_min(TrFrame frame, const float2 *__restrict__ kp_xy, int n,
+                                                                  const uint8_t *__restrict__ valid, const TrBest *__restrict__ best,
+                                                                  int log2p, uint32_t *__restrict__ owner,
+                                                                  unsigned long long *__restrict__ val, int32_t *__restrict__ slot)
+{
+    track_dedup_min(frame, kp_xy, n, valid, best, log2p, owner, val, slot);
+}
+
+// frame f's tables are slots [tab, tab + (ncams << log2p)) of owner / val, a table per (frame, camera) of its own size
+__global__ __launch_bounds__(kTrackDedupT) void k_track_dedup_min_batch(const TrBatchItem *__restrict__ items,
+                                                                        const float2 *__restrict__ kp_xy,
+                                                                        const uint8_t *__restrict__ valid, const TrBest *__restrict__ best,
+                                                                        uint32_t *__restrict__ owner, unsigned long long *__restrict__ val,
+                                                                        int32_t *__restrict__ slot)
+{
+    const TrBatchItem &it = items[blockIdx.z];
+    if ((int)(blockIdx.x * kTrackDedupT) >= it.n) return;
+    track_dedup_min(it.frame, kp_xy + it.kp0, it.n, valid + it.rows, best + it.rows, it.log2p, owner + it.tab, val + it.tab,
+                    slot + it.rows);
+}
+
 // a candidate is its pixel's entry iff the slot's minimum is its own value
-__global__ __launch_bounds__(kTrackDedupT) void k_track_dedup_win(int n, const TrBest *__restrict__ best, const int32_t *__restrict__ slot,
-                                                                  const unsigned long long *__restrict__ val, int log2p,
-                                                                  uint8_t *__restrict__ win)
+__device__ __forceinline__ void track_dedup_win(int n, const TrBest *__restrict__ best, const int32_t *__restrict__ slot,
+                                                const unsigned long long *__restrict__ val, int log2p, uint8_t *__restrict__ win)
 {
     const int c = blockIdx.y, i = blockIdx.x * kTrackDedupT + threadIdx.x;
     if (i >= n) return;
@@ -308,13 +443,30 @@ __global__ __launch_bounds__(kTrackDedupT) void k_track_dedup_win(int n, const T
     win[row + i] = s >= 0 && val[((size_t)c << log2p) + s] == tr_dedup_value(best[row + i].dist, i) ? 1 : 0;
 }
 
+__global__ __launch_bounds__(kTrackDedupT) void k_track_dedup_win(int n, const TrBest *__restrict__ best, const int32_t *__restrict__ slot,
+                                                                  const unsigned long long *__restrict__ val, int log2p,
+                                                                  uint8_t *__restrict__ win)
+{
+    track_dedup_win(n, best, slot, val, log2p, win);
+}
+
+__global__ __launch_bounds__(kTrackDedupT) void k_track_dedup_win_batch(const TrBatchItem *__restrict__ items,
+                                                                        const TrBest *__restrict__ best, const int32_t *__restrict__ slot,
+                                                                        const unsigned long long *__restrict__ val,
+                                                                        uint8_t *__restrict__ win)
+{
+    const TrBatchItem &it = items[blockIdx.z];
+    if ((int)(blockIdx.x * kTrackDedupT) >= it.n) return;
+    track_dedup_win(it.n, best + it.rows, slot + it.rows, val + it.tab, it.log2p, win + it.rows);
+}
+
 // The winners in candidate order, ranked the way k_track_compact ranks the validity bytes: workgroup b counts the flags before
 // its own 256 itself, ranks its own by a ballot per wave and waits on nobody; the last workgroup of a camera has the camera's
 // total.  matches and n_match are host-mapped.
-__global__ __launch_bounds__(kTrackDedupT) void k_track_dedup_emit(int n, const uint8_t *__restrict__ win, const TrBest *__restrict__ best,
-                                                                   TrMatch *__restrict__ matches, int32_t *__restrict__ n_match)
+__device__ __forceinline__ void track_dedup_emit(int *before, int *kept, int n, const uint8_t *__restrict__ win,
+                                                 const TrBest *__restrict__ best, TrMatch *__restrict__ matches,
+                                                 int32_t *__restrict__ n_match)
 {
-    __shared__ int before[kTrackDedupT / 64], kept[kTrackDedupT / 64];
     const int c = blockIdx.y, b = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
     if (b * kTrackDedupT >= n) return;   // (uniform over the workgroup)
     const size_t row = (size_t)c * n;
@@ -349,7 +501,24 @@ __global__ __launch_bounds__(kTrackDedupT) void k_track_dedup_emit(int n, const 
         const TrBest r = best[row + i];
         matches[row + lane_rank(mask, at)] = TrMatch{i, r.kp, r.dist};
     }
-    if (b == (int)gridDim.x - 1 && t == 0) n_match[c] = total;
+    if (b == (n - 1) / kTrackDedupT && t == 0) n_match[c] = total;   // (the last workgroup of n, whatever the grid)
+}
+
+__global__ __launch_bounds__(kTrackDedupT) void k_track_dedup_emit(int n, const uint8_t *__restrict__ win, const TrBest *__restrict__ best,
+                                                                   TrMatch *__restrict__ matches, int32_t *__restrict__ n_match)
+{
+    __shared__ int before[kTrackDedupT / 64], kept[kTrackDedupT / 64];
+    track_dedup_emit(before, kept, n, win, best, matches, n_match);
+}
+
+// n_match: MCORB_MAX_CAMS counts per frame
+__global__ __launch_bounds__(kTrackDedupT) void k_track_dedup_emit_batch(const TrBatchItem *__restrict__ items,
+                                                                         const uint8_t *__restrict__ win, const TrBest *__restrict__ best,
+                                                                         TrMatch *__restrict__ matches, int32_t *__restrict__ n_match)
+{
+    __shared__ int before[kTrackDedupT / 64], kept[kTrackDedupT / 64];
+    const TrBatchItem &it = items[blockIdx.z];
+    track_dedup_emit(before, kept, it.n, win + it.rows, best + it.rows, matches + it.rows, n_match + (size_t)blockIdx.z * MCORB_MAX_CAMS);
 }
 
 void launch_track_dedup(hipStream_t st, const TrFrame &frame, int ncams, const float2 *kp_xy, int n, const uint8_t *valid, const TrBest *best,
@@ -361,6 +530,17 @@ void launch_track_dedup(hipStream_t st, const TrFrame &frame, int ncams, const f
     hipLaunchKernelGGL(k_track_dedup_min, grid, block, 0, st, frame, kp_xy, n, valid, best, log2p, owner, val, slot);
     hipLaunchKernelGGL(k_track_dedup_win, grid, block, 0, st, n, best, slot, val, log2p, win);
     hipLaunchKernelGGL(k_track_dedup_emit, grid, block, 0, st, n, win, best, matches, n_match);
+}
+
+void launch_track_dedup_batch(hipStream_t st, const TrBatchItem *items, int nf, int max_n, int ncams, const float2 *kp_xy,
+                              const uint8_t *valid, const TrBest *best, uint32_t *owner, unsigned long long *val, int32_t *slot,
+                              uint8_t *win, TrMatch *matches, int32_t *n_match)
+{
+    if (nf < 1 || max_n < 1) return;
+    const dim3 grid((max_n + kTrackDedupT - 1) / kTrackDedupT, ncams, nf), block(kTrackDedupT);
+    hipLaunchKernelGGL(k_track_dedup_min_batch, grid, block, 0, st, items, kp_xy, valid, best, owner, val, slot);
+    hipLaunchKernelGGL(k_track_dedup_win_batch, grid, block, 0, st, items, best, slot, val, win);
+    hipLaunchKernelGGL(k_track_dedup_emit_batch, grid, block, 0, st, items, win, best, matches, n_match);
 }
 
 }  // namespace mcorb

@@ -28,6 +28,15 @@ run of the same leg in that pair -- and every process's record go to --out.  --p
 this commit built with -DMCORB_TRACK_PROF, for the phases.
     python scripts/track_rate.py --leg slot_ab --tree PARENT [--prof-tree DIR] [--out profiles/track_dedup_rate.json]
 
+--leg batch --tree PARENT: a 32-frame job of the slot leg's frame, 32 distinct views (the predicted pose moved a little per frame),
+the slot leg's 5 x 3000 ids for every frame.  Fresh processes, PARENT's library and this one's alternating, --procs (3) each; in a
+process, alternating runs after a warm-up, in ms per 32 frames: `single` 32 x track_rig_frame, `pair` 32 x (track_rig_frame_submit,
+track_wait), and where the library has them `batch` one track_rig_frames and `batch_submit`, the return time of
+track_rig_frames_submit (its wait follows, untimed); the five kernel intervals of `batch` divided by 32 beside the single call's.
+Pass mark: in every pair of processes the median of `batch` on this tree is below the parent's fastest run of `single` and of
+`pair`.  --prof-tree DIR adds one process on a checkout of this commit built with -DMCORB_TRACK_PROF, for the host phases.
+    python scripts/track_rate.py --leg batch --tree PARENT [--prof-tree DIR] [--out profiles/track_batch_rate.json]
+
 --leg stress: two frames on host arrays that load the de-duplication in opposite ways, the whole call and (where the library has
 last_track_timing5) the kernels: `one_keypoint`, 8000 landmarks whose queries all match the single keypoint of their camera, so
 every atomic of the arg-min lands on one address; `no_radius`, the frame of the default leg with max_d2 = inf, so every query has
@@ -232,6 +241,101 @@ def slot_ab_leg(a):
             json.dump(out, f, indent=1)
 
 
+BATCH_FRAMES = 32
+
+
+def batch_one_leg(mcorb, a):
+    """one process of --leg batch on the imported library -> its record"""
+    import ctypes
+    import kfdb_cases
+    import track_cases as T
+    F = BATCH_FRAMES
+    rig = mcorb.Rig(CAMS, COLS, ROWS, F, 1, nfeatures=KEYPOINTS)
+    rig.upload([mcorb.synth_rig_frame(0, CAMS, c, COLS, ROWS) for c in range(CAMS)] * F)
+    rig.extract(F * CAMS)
+    v, pts, desc, lids = slot_workload(mcorb, rig)
+    views = [T.to_view(mcorb, dict(v, t0=[0.002 * f, -0.001 * f, 0.0005 * f])) for f in range(F)]
+    lm = mcorb.LocalMap(mcorb.ORBVocabulary(device=0).create(**kfdb_cases.vocabulary()), device=0, max_landmarks=len(pts), max_candidates=len(pts))
+    lm.set(np.arange(len(pts), dtype=np.int32), pts, np.zeros_like(pts), desc)
+    has_batch = hasattr(lm, "track_rig_frames")
+    try:
+        phases_fn = lm.L.mcorb_lmap_track_phases
+    except AttributeError:
+        phases_fn = None
+
+    def phases():
+        us = (ctypes.c_float * 5)()
+        phases_fn(lm.h, us)
+        return list(us)
+
+    legs = ["single", "pair"] + (["batch", "batch_submit"] if has_batch else [])
+    t = {k: [] for k in legs}
+    kus = {k: [] for k in ("single", "batch")}
+    ph = {k: [] for k in ("single", "batch")}
+    frames, lidss = list(range(F)), [lids] * F
+    res = {}
+    for rep in range(a.reps + 1):                                      # alternating; the first round is the warm-up
+        for k in legs:
+            t0 = time.perf_counter()
+            if k == "single":
+                res[k] = [lm.track_rig_frame(views[f], rig, f, lids) for f in range(F)]
+            elif k == "pair":
+                res[k] = []
+                for f in range(F):
+                    lm.track_rig_frame_submit(views[f], rig, f, lids)
+                    res[k].append(lm.track_wait())
+            elif k == "batch":
+                res[k] = lm.track_rig_frames(views, rig, frames, lidss)
+            else:
+                lm.track_rig_frames_submit(views, rig, frames, lidss)
+            t[k].append((time.perf_counter() - t0) * 1e3)
+            if k == "batch_submit":
+                res[k] = lm.track_frames_wait()
+            if k in kus:
+                kus[k].append(lm.last_track_timing5())
+                if phases_fn is not None:
+                    ph[k].append(phases())
+    same = all([T.as_lists(r) for r in res[k]] == [T.as_lists(r) for r in res["single"]] for k in legs)
+    r0 = res["single"][0]
+    out = {"tree": os.path.abspath(a.tree or ROOT), "cores": len(os.sched_getaffinity(0)), "cameras": CAMS, "image": [COLS, ROWS],
+           "frames": F, "keypoints_per_camera": [len(rig.features(c)[1]) for c in range(CAMS)], "landmarks": int(len(pts)),
+           "lids_per_frame": int(len(lids)), "candidates_per_frame": int(r0.n_candidates),
+           "queries_per_camera_frame0": [len(p) for p in r0.proj_lid], "matches_per_camera_frame0": [len(m) for m in r0.match_kp],
+           "frames_differ": bool(T.as_lists(res["single"][0])["proj"] != T.as_lists(res["single"][F - 1])["proj"]),
+           "legs_equal": bool(same)}
+    for k in legs:
+        vals = t[k][1:]
+        out["%s_ms_per_32" % k] = round(float(np.median(vals)), 3)
+        out["%s_ms_per_32_runs" % k] = [round(x, 3) for x in vals]
+    for k, div in (("single", 1), ("batch", F)):
+        if kus[k]:                                                     # (single: the last of the 32 calls of a run)
+            out["%s_kernel_us_per_frame" % k] = [round(float(np.median([u[i] for u in kus[k][1:]])) / div, 1) for i in range(5)]
+        if ph[k]:
+            out["%s_host_phase_us" % k] = dict(zip(("candidate_walk", "submission", "wait", "deduplication", "output"),
+                                                   [round(float(np.median([p[i] for p in ph[k][1:]])), 1) for i in range(5)]))
+    print(json.dumps(out))
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump(out, f, indent=1)
+
+
+def batch_leg(a):
+    pairs = []
+    for _ in range(a.procs):
+        pairs.append({"parent": child(a, "batch_one", a.tree), "this": child(a, "batch_one", None)})
+    marks = [{"this_batch_median_ms": p["this"]["batch_ms_per_32"], "parent_single_fastest_ms": min(p["parent"]["single_ms_per_32_runs"]),
+              "parent_pair_fastest_ms": min(p["parent"]["pair_ms_per_32_runs"]),
+              "met": p["this"]["batch_ms_per_32"] < min(p["parent"]["single_ms_per_32_runs"] + p["parent"]["pair_ms_per_32_runs"])}
+             for p in pairs]
+    out = {"pass_mark": marks, "pass_mark_met": all(m["met"] for m in marks), "pairs": pairs}
+    if a.prof_tree:
+        out["phases"] = child(a, "batch_one", a.prof_tree)
+    print(json.dumps(out))
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump(out, f, indent=1)
+
+
 def stress_leg(mcorb, a):
     import kfdb_cases
     import track_cases as T
@@ -278,16 +382,21 @@ if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--out", default=None)
-    ap.add_argument("--leg", default="stores", choices=["stores", "slot", "slot_ab", "stress"])
+    ap.add_argument("--leg", default="stores", choices=["stores", "slot", "slot_ab", "stress", "batch", "batch_one"])
     ap.add_argument("--tree", default=None, help="a checkout whose package is timed instead of this one's (--leg slot, stress); "
-                                                 "the parent commit's checkout (--leg slot_ab)")
-    ap.add_argument("--prof-tree", default=None, help="--leg slot_ab: a checkout of this commit built with -DMCORB_TRACK_PROF")
-    ap.add_argument("--procs", type=int, default=3, help="--leg slot_ab: processes per tree")
+                                                 "the parent commit's checkout (--leg slot_ab, batch)")
+    ap.add_argument("--prof-tree", default=None, help="--leg slot_ab, batch: a checkout of this commit built with -DMCORB_TRACK_PROF")
+    ap.add_argument("--procs", type=int, default=3, help="--leg slot_ab, batch: processes per tree")
     a = ap.parse_args()
     if a.leg == "slot_ab":
         if not a.tree:
             ap.error("--leg slot_ab needs --tree PARENT")
         slot_ab_leg(a)
+        sys.exit(0)
+    if a.leg == "batch":
+        if not a.tree:
+            ap.error("--leg batch needs --tree PARENT")
+        batch_leg(a)
         sys.exit(0)
     if a.tree:
         sys.path.insert(0, os.path.abspath(a.tree))
@@ -297,6 +406,9 @@ if __name__ == "__main__":
         sys.exit(0)
     if a.leg == "stress":
         stress_leg(mcorb, a)
+        sys.exit(0)
+    if a.leg == "batch_one":
+        batch_one_leg(mcorb, a)
         sys.exit(0)
     import track_cases as T
     w = workload()
