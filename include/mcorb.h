@@ -834,7 +834,8 @@ int mcorb_lmap_last_landmark_timing(mcorb_lmap *m, float us[2]);
 /* querryEachFrame (:319-449): the 10 nearest keypoints by image position, the */
 /* 100 px gate, the best Hamming distance below 20 and the serial              */
 /* de-duplication per keypoint.  Tracking::queryPoints, the JSON map and       */
-/* refinePose (OpenGV) stay with the caller.                                   */
+/* refinePose's RANSAC (OpenGV) stay with the caller; the pose refinement      */
+/* behind it is mcorb_lmap_refine_pose, below.                                 */
 /* ------------------------------------------------------------------------- */
 #define MCORB_TRACK_KNN 10      /* the neighbours a projection is compared with (Tracking.cpp:335-345) */
 #define MCORB_TRACK_TILE 1024   /* keypoints per LDS tile of k_track_match; a camera may have any number */
@@ -975,6 +976,83 @@ int mcorb_lmap_track_frames_wait(mcorb_lmap *m, mcorb_track_out *outs, int n_out
 int mcorb_lmap_track_rig_frames(mcorb_lmap *m, const mcorb_track_view *views, mcorb_rig *r, int slot, const int32_t *frames, int nf,
                                 const int32_t *lids, const int32_t *lid_first, double max_d2, int max_hamming, int want_pts,
                                 mcorb_track_out *outs);
+
+/* ------------------------------------------------------------------------- */
+/* The rig pose from a frame's 2D-3D matches: the cost function and the       */
+/* outlier rule of FrontEnd::OptimizePose (MCSlam/src/FrontEnd.cpp:4272-4409)  */
+/* with the RigResectioningFactor (MCSlam/include/MCSlam/                      */
+/* GtsamFactorHelpers.h:48-100), around a stated Levenberg-Marquardt: gtsam's  */
+/* optimizer is not vendored.  The GP3P RANSAC in front of it (OpenGV) stays   */
+/* with the caller: this serves a frame that has a predicted pose.             */
+/* ------------------------------------------------------------------------- */
+#define MCORB_POSE_LANES 256      /* the lanes whose partial sums fix the order of every addition (below) */
+#define MCORB_POSE_NO_OBS 0       /* no observation: the initial pose */
+#define MCORB_POSE_NO_STEP 1      /* no trial was ever accepted in the second round: the initial pose */
+#define MCORB_POSE_CONVERGED 2    /* the second round ended on an accepted step with a small decrease */
+#define MCORB_POSE_MAX_ITER 3     /* the second round ended at max_iterations solves, or when lambda left its bounds */
+/* inv_sigma2: ORBextractor::GetInverseScaleSigmaSquares(); max_iterations: solves per round, 1 .. 100 (the reference sets 25) */
+typedef struct mcorb_pose_params {
+    double inv_sigma2[MCORB_MAX_LEVELS];
+    int32_t nlevels, max_iterations;
+} mcorb_pose_params;
+/* (R, t) = w_T_b, the body's pose in the world after the second round, R row-major; status: MCORB_POSE_*, the second round's;
+ * iterations: the solves of each round; cost_initial: the first round's cost at the initial pose; cost_final: the second round's
+ * at the returned pose, over the observations that round had; n_obs: the observations of the problem */
+typedef struct mcorb_pose_result {
+    double R[9], t[3];
+    double cost_initial, cost_final;
+    int32_t status, iterations[2], n_inliers, n_obs, reserved;
+} mcorb_pose_result;
+/* The pose of a rig from n observations: observation i is the keypoint uv[2 i], uv[2 i + 1] (a KeyPoint::pt) of pyramid level
+ * octave[i] in camera cam[i], of the point pts[3 i ..] or, with lids, the store's point of landmark lids[i] (a device store's
+ * kernel gathers it from HBM); exactly one of lids / pts is non-NULL.  cams: the rig, a mcorb_track_cam read as body_P_sensor and
+ * Cal3_S2; (R, t): the initial w_T_b.  All arithmetic is fp64, one IEEE operation per operator in the order written
+ * (csrc/mcorb_pose.h), with one square root:
+ * - the residual: p_b = R^T (X - t), q = Rc^T (p_b - tc); q.z <= 0 (the reference's form): r = (2 fx, 2 fx) with a zero Jacobian;
+ *   otherwise d = 1.0 / q.z, u = q.x d, v = q.y d, r = ((fx u + s v) + u0 - kx, (fy v + v0) - ky).  The Jacobian is taken w.r.t. the
+ *   right perturbation (omega, upsilon), gtsam's order: Dpi(q) Rc^T [ [p_b]x | -I ].
+ * - Huber at k = the double nearest sqrt(5.991) on a one-pixel sigma: e = sqrt(r.r), w = e <= k ? 1 : k / e, rho = e <= k ?
+ *   0.5 r.r : k (e - 0.5 k).
+ * - the normal equations: the 21 upper entries of H = sum w J^T J, g = sum w J^T r and the cost sum rho over the observations
+ *   that are still in.  Lane l of MCORB_POSE_LANES adds observations l, l + 256, .. in ascending order into +0.0; each block of
+ *   64 lanes folds with strides 32 .. 1, s[l] = s[l] + s[l + stride], and the four block sums combine as (b0 + b1) + (b2 + b3).
+ * - the step: (H + lambda diag(H)) delta = -g by an LDL^T without square roots; a pivot that is not > 0 means no step.  The
+ *   retraction: a = omega / 2, C = ((1 - a.a) I + 2 a a^T + 2 [a]x) / (1 + a.a) (Cayley), R' = R C, t' = t + R upsilon.
+ * - the loop: lambda = 1e-4, halved after an accepted trial, doubled otherwise; a trial is accepted iff its cost is less; a round
+ *   ends on an accepted step whose decrease is < 1e-6 or < 1e-6 * cost, after max_iterations solves, or when lambda leaves
+ *   [1e-16, 1e32].  (gtsam's own schedule, LevenbergMarquardtParams::SetCeresDefaults, is not restated.)
+ * - two rounds, each from the initial pose; after each, an observation with r.r * inv_sigma2[octave] > 5.991 at the round's
+ *   result leaves for good and its inlier flag is 0.
+ * A device store runs all of it in one launch of k_pose_refine, one workgroup of MCORB_POSE_LANES lanes, whose result lands in
+ * host-mapped memory; a host-only store runs the same header serially: the results are equal bit for bit.  inlier (may be NULL):
+ * n flags.  Before anything runs: MCORB_E_ARG for n < 0, ncams outside 1 .. MCORB_MAX_CAMS, nlevels outside 1 ..
+ * MCORB_MAX_LEVELS, max_iterations outside 1 .. 100, a NULL array, a camera index or octave out of range, an id outside the
+ * store, both or neither of lids / pts; MCORB_E_STATE for a landmark without a point and while a tracking call is pending.
+ * The store is unchanged in every case. */
+int mcorb_lmap_refine_pose(mcorb_lmap *m, int n, const int32_t *cam, const float *uv, const int32_t *octave, const int32_t *lids,
+                           const double *pts, int ncams, const mcorb_track_cam *cams, const double *R, const double *t,
+                           const mcorb_pose_params *params, mcorb_pose_result *res, uint8_t *inlier);
+/* a device store's last k_pose_refine launch of mcorb_lmap_refine_pose, microseconds between HIP events; a call without
+ * observations launches nothing and leaves it */
+int mcorb_lmap_last_pose_timing(mcorb_lmap *m, float us[1]);
+/* The refinement behind fast tracking.  params != NULL: from now on every tracking submission on the store -- mcorb_lmap_track,
+ * mcorb_lmap_track_rig_frame, the pair, mcorb_lmap_track_rig_frames -- appends, per frame, the refinement of the view's rig from
+ * the frame's de-duplicated matches, in the same submission: the rig is the view's cameras, the initial pose (R0^T, -(R0^T t0))
+ * (mcorb_pose_of_view), the observations the matches camera by camera in match order, uv the matched keypoint's pt, the point
+ * the store's point of the matched landmark, the octave 0 (querryEachFrame's bestMatches carry none).  The kernel builds that
+ * list on the device and reads nothing from the host.  NULL: off, the default; with it off every tracking entry is exactly what
+ * it is without this call.  MCORB_E_ARG for parameters mcorb_lmap_refine_pose refuses, MCORB_E_STATE while a call is pending. */
+int mcorb_lmap_set_track_refine(mcorb_lmap *m, const mcorb_pose_params *params);
+/* frame f's pose of the last tracking call, after its wait and until the next submission: bit for bit what
+ * mcorb_lmap_refine_pose returns on that frame's match_kp -> pt, match_lid and camera arrays.  flags (may be NULL): cap inlier
+ * flags, MCORB_E_CAP (with out set) when cap < out->n_obs.  MCORB_E_STATE when the last call ran without the option, is pending
+ * or never happened; MCORB_E_ARG for a frame outside the call. */
+int mcorb_lmap_last_track_pose(mcorb_lmap *m, int f, mcorb_pose_result *out, uint8_t *flags, int cap);
+/* w_T_b of a view read as a rig whose body is camera 0's frame: R = R0^T, t = -(R0^T t0), an element -((a0 b0 + a1 b1) + a2 b2) */
+void mcorb_pose_of_view(const mcorb_track_view *view, double R[9], double t[3]);
+/* test hook, host: residual r (n x 2), Jacobian J (n x 2 x 6) and Huber weight w (n) of n observations at the pose (R, t) */
+int mcorb_pose_eval(int ncams, const mcorb_track_cam *cams, int n, const int32_t *cam, const float *uv, const double *pts, const double *R,
+                    const double *t, double *r, double *J, double *w);
 
 /* ------------------------------------------------------------------------- */
 /* Host stages exposed for the CPU test-suite (no device needed)              */

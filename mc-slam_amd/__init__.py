@@ -1462,6 +1462,111 @@ class LocalMap:
         return tuple(us)
 
 
+    # the rig pose from 2D-3D matches (mcorb_lmap_refine_pose): OptimizePose's cost and cull around a stated Levenberg-Marquardt
+    def refine_pose(self, cams, R, t, cam, uv, octave, inv_sigma2, lids=None, pts=None, max_iterations=25):
+        """the pose w_T_b = (R, t) of a rig refined from observations: observation i is the keypoint uv[i] (KeyPoint::pt) of
+        pyramid level octave[i] in camera cam[i] of the store's landmark lids[i] or of the point pts[i] (exactly one of the
+        two).  cams: pose_cams(...) or a track_view (its cameras are the rig); inv_sigma2: GetInverseScaleSigmaSquares(), one
+        per level.  Two rounds from (R, t), each followed by the chi2 > 5.991 cull -> PoseResult.  A device store runs one launch
+        of k_pose_refine; a host-only store the same arithmetic serially, with the same bits"""
+        cam = np.ascontiguousarray(cam, np.int32).reshape(-1)
+        n = len(cam)
+        uv = np.ascontiguousarray(uv, np.float32).reshape(n, 2)
+        octave = np.ascontiguousarray(octave, np.int32).reshape(n)
+        l, lp = self._opt(lids, np.int32, (n,))
+        p, pp = self._opt(pts, np.float64, (n, 3))
+        ncams, ca = _pose_cams(cams)
+        R = np.ascontiguousarray(R, np.float64).reshape(9)
+        t = np.ascontiguousarray(t, np.float64).reshape(3)
+        res, flags = _lib.PoseResultC(), np.zeros(max(n, 1), np.uint8)
+        _lib.check(self.L.mcorb_lmap_refine_pose(self.h, n, cam.ctypes.data, uv.ctypes.data, octave.ctypes.data, lp, pp, ncams, ca,
+                                                 R.ctypes.data, t.ctypes.data, C.byref(pose_params(inv_sigma2, max_iterations)),
+                                                 C.byref(res), flags.ctypes.data))
+        return PoseResult(res, flags[:n])
+
+    def last_pose_timing(self):
+        """microseconds of the last k_pose_refine launch of refine_pose(); a device store"""
+        us = (C.c_float * 1)()
+        _lib.check(self.L.mcorb_lmap_last_pose_timing(self.h, us))
+        return us[0]
+
+    def set_track_refine(self, inv_sigma2=None, max_iterations=25):
+        """inv_sigma2 given: from now on every tracking call on the store -- track, track_rig_frame, the submit / wait pair,
+        track_rig_frames -- also refines, per frame and in the same submission, the pose of the view's rig from the frame's
+        de-duplicated matches (octave 0: bestMatches carry none), read with last_track_pose().  None: off, the default"""
+        _lib.check(self.L.mcorb_lmap_set_track_refine(
+            self.h, None if inv_sigma2 is None else C.byref(pose_params(inv_sigma2, max_iterations))))
+
+    def last_track_pose(self, f=0):
+        """the PoseResult of frame f of the last tracking call, after its wait and until the next submission: bit for bit
+        refine_pose() on that frame's match_kp -> pt, match_lid and camera arrays, from pose_of_view(view).  MCORB_E_STATE when
+        the call ran without set_track_refine(), is pending or never happened"""
+        res = _lib.PoseResultC()
+        _lib.check(self.L.mcorb_lmap_last_track_pose(self.h, f, C.byref(res), None, 0))
+        flags = np.zeros(max(res.n_obs, 1), np.uint8)
+        _lib.check(self.L.mcorb_lmap_last_track_pose(self.h, f, C.byref(res), flags.ctypes.data, res.n_obs))
+        return PoseResult(res, flags[:res.n_obs])
+
+
+class PoseResult:
+    """what LocalMap.refine_pose and LocalMap.last_track_pose return: R (3 x 3), t = w_T_b after the second round; status
+    (POSE_NO_OBS, POSE_NO_STEP, POSE_CONVERGED, POSE_MAX_ITER: the second round's); iterations, the solves of each round;
+    cost_initial (the first round's, at the initial pose) and cost_final (the second round's); n_inliers and inliers, one bool per
+    observation: False once a round's cull took it"""
+
+    def __init__(self, res, flags):
+        self.R = np.array(res.R[:], np.float64).reshape(3, 3)
+        self.t = np.array(res.t[:], np.float64)
+        self.status, self.iterations = res.status, (res.iterations[0], res.iterations[1])
+        self.cost_initial, self.cost_final = res.cost_initial, res.cost_final
+        self.n_inliers, self.n_obs = res.n_inliers, res.n_obs
+        self.inliers = flags.astype(bool)
+
+
+def pose_params(inv_sigma2, max_iterations=25):
+    """mcorb_pose_params: inv_sigma2 = GetInverseScaleSigmaSquares(), one per pyramid level"""
+    s2 = np.asarray(inv_sigma2, np.float64).reshape(-1)
+    p = _lib.PoseParams()
+    p.nlevels, p.max_iterations = len(s2), int(max_iterations)
+    for k in range(min(len(s2), _lib.MAX_LEVELS)):
+        p.inv_sigma2[k] = float(s2[k])
+    return p
+
+
+def pose_cams(cam_R, cam_t, K_mats):
+    """the rig of LocalMap.refine_pose: per camera body_P_sensor = (cam_R, cam_t) and the 3x3 calibration (Cal3_S2: fx, s, u0,
+    fy, v0), as track_view takes them"""
+    return track_view(np.eye(3), np.zeros(3), cam_R, cam_t, K_mats, 0, 0)
+
+
+def _pose_cams(cams):
+    """-> (ncams, the address of the mcorb_track_cam array) of a track_view"""
+    return cams.ncams, C.addressof(cams.cams)
+
+
+def pose_of_view(view):
+    """(R, t) = w_T_b of a track_view read as a rig whose body is camera 0's frame: R0^T, -(R0^T t0)"""
+    R, t = np.zeros(9), np.zeros(3)
+    _lib.load().mcorb_pose_of_view(C.byref(view), R.ctypes.data, t.ctypes.data)
+    return R.reshape(3, 3), t
+
+
+def pose_eval(cams, R, t, cam, uv, pts):
+    """test hook (host): residual r (n x 2), Jacobian J (n x 2 x 6, w.r.t. the right perturbation (omega, upsilon)) and Huber
+    weight w (n) of the observations at the pose (R, t)"""
+    cam = np.ascontiguousarray(cam, np.int32).reshape(-1)
+    n = len(cam)
+    uv = np.ascontiguousarray(uv, np.float32).reshape(n, 2)
+    pts = np.ascontiguousarray(pts, np.float64).reshape(n, 3)
+    R = np.ascontiguousarray(R, np.float64).reshape(9)
+    t = np.ascontiguousarray(t, np.float64).reshape(3)
+    r, J, w = np.zeros((max(n, 1), 2)), np.zeros((max(n, 1), 2, 6)), np.zeros(max(n, 1))
+    ncams, ca = _pose_cams(cams)
+    _lib.check(_lib.load().mcorb_pose_eval(ncams, ca, n, cam.ctypes.data, uv.ctypes.data, pts.ctypes.data, R.ctypes.data, t.ctypes.data,
+                                           r.ctypes.data, J.ctypes.data, w.ctypes.data))
+    return r[:n], J[:n], w[:n]
+
+
 class TrackResult:
     """what LocalMap.track and LocalMap.track_wait return, every member a list with one array per camera.  The projected landmarks in candidate order:
     proj_lid, proj_xy (the projected keypoint's pt, float32) and, per projected query before the serial part, best_kp (-1: none)

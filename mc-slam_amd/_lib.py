@@ -20,6 +20,8 @@ OBS_UPDATE, OBS_RECORD = 0, 1
 MAX_LEVELS, MAX_CAMS = 16, 16
 TRACK_KNN, TRACK_TILE = 10, 1024   # MCORB_TRACK_KNN, MCORB_TRACK_TILE
 TRACK_MAX_FRAMES = 32               # MCORB_TRACK_MAX_FRAMES
+POSE_LANES = 256                    # MCORB_POSE_LANES
+POSE_NO_OBS, POSE_NO_STEP, POSE_CONVERGED, POSE_MAX_ITER = 0, 1, 2, 3   # MCORB_POSE_*
 
 KP_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"),
                      ("response", "<f4"), ("octave", "<i4"), ("class_id", "<i4")])
@@ -87,6 +89,16 @@ class TrackOut(C.Structure):
                 ("best_kp", C.c_void_p), ("best_dist", C.c_void_p), ("match_kp", C.c_void_p), ("match_lid", C.c_void_p),
                 ("match_dist", C.c_void_p), ("match_pt", C.c_void_p), ("n_proj", C.c_int32 * MAX_CAMS),
                 ("n_match", C.c_int32 * MAX_CAMS), ("n_candidates", C.c_int32), ("reserved", C.c_int32)]
+
+
+class PoseParams(C.Structure):
+    _fields_ = [("inv_sigma2", C.c_double * MAX_LEVELS), ("nlevels", C.c_int32), ("max_iterations", C.c_int32)]
+
+
+class PoseResultC(C.Structure):
+    _fields_ = [("R", C.c_double * 9), ("t", C.c_double * 3), ("cost_initial", C.c_double), ("cost_final", C.c_double),
+                ("status", C.c_int32), ("iterations", C.c_int32 * 2), ("n_inliers", C.c_int32), ("n_obs", C.c_int32),
+                ("reserved", C.c_int32)]
 
 
 class McorbError(RuntimeError):
@@ -251,6 +263,12 @@ SIGNATURES = {
     "mcorb_lmap_track_frames_wait": (_i, [_vp, C.POINTER(TrackOut), _i]),
     "mcorb_lmap_track_rig_frames": (_i, [_vp, C.POINTER(TrackView), _vp, _i, _vp, _i, _vp, _vp, C.c_double, _i, _i, C.POINTER(TrackOut)]),
     "mcorb_host_track_pixel": (C.c_int32, [_f]),
+    "mcorb_lmap_refine_pose": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, C.POINTER(PoseParams), C.POINTER(PoseResultC), _vp]),
+    "mcorb_lmap_last_pose_timing": (_i, [_vp, C.POINTER(_f)]),
+    "mcorb_lmap_set_track_refine": (_i, [_vp, C.POINTER(PoseParams)]),
+    "mcorb_lmap_last_track_pose": (_i, [_vp, _i, C.POINTER(PoseResultC), _vp, _i]),
+    "mcorb_pose_of_view": (None, [C.POINTER(TrackView), _vp, _vp]),
+    "mcorb_pose_eval": (_i, [_i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mcorb_host_geometry": (_i, [C.POINTER(Params), _i, _i, _vp]),
     "mcorb_synth_rig_frame": (_i, [C.c_uint32, _i, _i, _i, _i, _vp, _i]),
 }

@@ -1,12 +1,13 @@
 // mcorb_kernels.h -- launch wrappers of the gfx950 kernels (mcorb_kernels.hip, mcorb_select_gpu.hip, mcorb_handoff_gpu.hip,
 // mcorb_bow_gpu.hip, mcorb_lf_gpu.hip, mcorb_kfdb_gpu.hip, mcorb_lmap_gpu.hip, mcorb_mapping_gpu.hip, mcorb_landmark_gpu.hip,
-// mcorb_track_gpu.hip).
+// mcorb_track_gpu.hip, mcorb_pose_gpu.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <vector>
 #include "../../include/mcorb.h"
 #include "mcorb_common.h"
 #include "mcorb_mapping.h"
+#include "mcorb_pose.h"
 #include "mcorb_signal.h"
 #include "mcorb_track.h"
 #include "mcorb_undistort.h"
@@ -224,5 +225,14 @@ void launch_track_compact_batch(hipStream_t st, const TrBatchItem *items, int nf
 void launch_track_dedup_batch(hipStream_t st, const TrBatchItem *items, int nf, int max_n, int ncams, const float2 *kp_xy,
                               const uint8_t *valid, const TrBest *best, uint32_t *owner, unsigned long long *val, int32_t *slot,
                               uint8_t *win, TrMatch *matches, int32_t *n_match);
+
+// the pose refinement (mcorb_pose_gpu.hip).  k_pose_refine: problem blockIdx.x of jobs (device memory), one workgroup of
+// MCORB_POSE_LANES lanes for both rounds.  obs / lids / pts / alive / flags: every problem's block begins at its obs0; pts or lids
+// is NULL (a point is pts[i] or geom's of lids[i]).  A problem with from_track builds its obs and lids itself, from win / best /
+// cand / kp_xy of the tracking submission in front of it (these may be NULL otherwise).  out (one per problem) and flags may be
+// host-mapped
+void launch_pose_refine(hipStream_t st, const PoseJob *jobs, int njobs, PoseObs *obs, int32_t *lids, const double *pts, const double *geom,
+                        uint8_t *alive, const uint8_t *win, const TrBest *best, const int *cand, const float2 *kp_xy,
+                        mcorb_pose_result *out, uint8_t *flags);
 
 }  // namespace mcorb

@@ -152,6 +152,8 @@ int mcorb_lmap_create(mcorb_vocab *v, int device, int max_landmarks, int max_can
         TRY(m->ev11.create(hipEventDefault));
         TRY(m->ev12.create(hipEventDefault));
         TRY(m->ev13.create(hipEventDefault));
+        TRY(m->ev14.create(hipEventDefault));
+        TRY(m->ev15.create(hipEventDefault));
         TRY(m->best2.create());
         TRY(m->d_geom.alloc(N * 6));
         TRY(m->d_desc.alloc(N * 32));

@@ -9,11 +9,24 @@
 
 #include "mcorb_kfdb_store.h"
 #include "mcorb_mapping.h"
+#include "mcorb_pose.h"
 #include "mcorb_track.h"
 
 namespace mcorb {
 constexpr uint8_t kHasPt = 1, kHasNormal = 2, kHasDesc = 4, kMono = 8, kSet = kHasPt | kHasNormal;
 struct LmObs { int32_t kf_id, feat; };   // one observation of a landmark: KFs[i]'s id, featInds[i]
+// the buffers of a k_pose_refine launch (mcorb_pose.cpp), grow-only: the packed input (the PoseJobs, then -- the explicit entry --
+// the observations and their ids or points; one block, one copy), the observation list a tracking submission's prologue builds,
+// the flags of the observations that are still in, and what the host reads: results and inlier flags, host-mapped
+struct PoseBufs {
+    HostBuf<uint8_t> h_in;
+    DevBuf<uint8_t> d_in;
+    DevBuf<PoseObs> d_obs;
+    DevBuf<int32_t> d_lids;
+    DevBuf<uint8_t> d_alive;
+    HostBuf<mcorb_pose_result> h_out;
+    HostBuf<uint8_t> h_flags;
+};
 }  // namespace mcorb
 
 struct mcorb_lmap {
@@ -110,6 +123,9 @@ struct mcorb_lmap {
     struct TrackCall {
         int ncams = 0, nf = 1;
         bool launched = false, points = false, want_pts = false;
+        bool refine = false;                      // the call ran with mcorb_lmap_set_track_refine on: pose / pose_flags hold
+        std::vector<mcorb_pose_result> pose;      // a host-only store's results and those of frames without a launch, per frame
+        std::vector<uint8_t> pose_flags;          // a host-only store's inlier flags, frame f's from ncams * first[f] on
         std::vector<int> cand;
         std::vector<size_t> first;
         std::vector<mcorb::TrRow> rows;
@@ -117,10 +133,32 @@ struct mcorb_lmap {
         std::vector<int32_t> n_proj, n_match;
     } track_call;
     std::atomic<bool> track_pending{false};
+    // the pose refinement (mcorb_pose.cpp): pose_x serves mcorb_lmap_refine_pose, pose_t the refinement behind a tracking
+    // submission (track_refine: mcorb_lmap_set_track_refine), whose results stay readable until the next submission.
+    // track_pose_nf: the frames of the last tracking call if it ran with the option, 0 otherwise
+    mcorb::PoseBufs pose_x, pose_t;
+    mcorb::Event ev14, ev15;                   // in front of and behind k_pose_refine of mcorb_lmap_refine_pose
+    float us_pose = 0.f;
+    bool track_refine = false;
+    mcorb_pose_params track_refine_params = {};
+    int track_pose_nf = 0;
 #ifdef MCORB_TRACK_PROF
     float us_track_phase[5] = {};   // the last call's host phases: candidate walk, submission, wait, de-duplication, output
 #endif
 };
+
+// the pose refinement behind a tracking call (mcorb_pose.cpp); the caller holds the store's lock and has set track_refine_params.
+// pose_track_host: a host-only store, or a frame nothing was launched for -- the observations are the frame's matches, the
+// cameras back to back in match order (kp_base / kp_stride: the frame's keypoint records, which begin with pt), flags: ncams *
+// nc bytes.  pose_track_submit: k_pose_refine for the nf frames of a device submission, behind its de-duplication on the
+// store's stream; first: the frames' places in the call's candidate list (nf + 1), frames / kp0: per frame its TrFrame and the
+// place of its keypoints in kp_xy
+namespace mcorb {
+void pose_track_host(mcorb_lmap *m, const mcorb_track_view &view, const int *cand, int nc, const TrMatch *matches, const int32_t *n_match,
+                     const uint8_t *const *kp_base, size_t kp_stride, mcorb_pose_result &res, uint8_t *flags);
+int pose_track_submit(mcorb_lmap *m, const mcorb_track_view *views, int nf, const size_t *first, const TrFrame *frames, const size_t *kp0,
+                      const float2 *kp_xy, const int *d_cand);
+}  // namespace mcorb
 
 // a new stamp value; the stamps start over before the counter wraps
 inline int next_tick(mcorb_lmap *m)

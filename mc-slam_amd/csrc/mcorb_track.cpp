@@ -301,6 +301,10 @@ int submit_on_device(mcorb_lmap *m, const mcorb_track_view &view, const Frame &f
                        m->h_trackmatch, m->h_tracknmatch);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(m->ev13, st));
+    if (m->track_refine) {   // (mcorb_lmap_set_track_refine: the pose from the frame's matches, in the same submission)
+        const size_t first[2] = {0, (size_t)nc}, kp0 = 0;
+        TRY(pose_track_submit(m, &view, 1, first, &tf, &kp0, kp_xy, d_cand));
+    }
     if (want_pts) HIPCHK(hipMemcpyAsync(m->h_trackpt, m->d_trackpt, (size_t)nc * 3 * sizeof(double), hipMemcpyDeviceToHost, st));
     return MCORB_OK;
 }
@@ -325,7 +329,17 @@ int submit_body(mcorb_lmap *m, const mcorb_track_view *view, const Frame &f, con
     tc.want_pts = want_pts;
     tc.n_proj.assign(MCORB_MAX_CAMS, 0);
     tc.n_match.assign(MCORB_MAX_CAMS, 0);
-    if (!nc) return MCORB_OK;
+    tc.refine = m->track_refine;
+    m->track_pose_nf = 0;
+    if (tc.refine) {
+        tc.pose.assign(1, mcorb_pose_result{});
+        tc.pose_flags.assign((size_t)C * nc, 0);
+    }
+    if (!nc) {
+        if (tc.refine) pose_track_host(m, *view, nullptr, 0, nullptr, tc.n_match.data(), f.kp.base, f.kp.stride, tc.pose[0], nullptr);
+        m->track_pose_nf = tc.refine ? 1 : 0;
+        return MCORB_OK;
+    }
     if (m->device < 0) {
         tc.rows.resize((size_t)C * nc);
         tc.matches.resize((size_t)C * nc);
@@ -333,6 +347,10 @@ int submit_body(mcorb_lmap *m, const mcorb_track_view *view, const Frame &f, con
         ph.mark(2);
         dedup_on_host(C, nc, tc.rows.data(), tc.n_proj.data(), f.kp, tc.matches.data(), tc.n_match.data());
         ph.mark(3);
+        if (tc.refine)
+            pose_track_host(m, *view, tc.cand.data(), nc, tc.matches.data(), tc.n_match.data(), f.kp.base, f.kp.stride, tc.pose[0],
+                            tc.pose_flags.data());
+        m->track_pose_nf = tc.refine ? 1 : 0;
         return MCORB_OK;
     }
     const int r = submit_on_device(m, *view, f, tc.cand, max_d2, max_hamming, want_pts);
@@ -342,6 +360,7 @@ int submit_body(mcorb_lmap *m, const mcorb_track_view *view, const Frame &f, con
     }
     tc.launched = true;
     tc.points = f.slot != nullptr;
+    m->track_pose_nf = tc.refine ? 1 : 0;
     ph.mark(1);
     return MCORB_OK;
 }
@@ -615,6 +634,15 @@ int submit_frames_on_device(mcorb_lmap *m, const mcorb_track_view *views, const 
                              m->d_trackslot, m->d_trackwin, m->h_trackmatch, m->h_tracknmatch);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(m->ev13, st));
+    if (m->track_refine) {   // (one workgroup of k_pose_refine per frame, in the same submission)
+        std::vector<TrFrame> tf((size_t)nf);
+        std::vector<size_t> kp0((size_t)nf);
+        for (int f = 0; f < nf; f++) {
+            tf[f] = items[f].frame;
+            kp0[f] = items[f].kp0;
+        }
+        TRY(pose_track_submit(m, views, nf, tc.first.data(), tf.data(), kp0.data(), m->d_trackkp, d_cand));
+    }
     if (want_pts) HIPCHK(hipMemcpyAsync(m->h_trackpt, m->d_trackpt, total * 3 * sizeof(double), hipMemcpyDeviceToHost, st));
     return MCORB_OK;
 }
@@ -643,19 +671,30 @@ int submit_frames_body(mcorb_lmap *m, const mcorb_track_view *views, const std::
     tc.want_pts = want_pts;
     tc.n_proj.assign((size_t)nf * MCORB_MAX_CAMS, 0);
     tc.n_match.assign((size_t)nf * MCORB_MAX_CAMS, 0);
-    if (!total) return MCORB_OK;
-    if (m->device < 0) {
+    tc.refine = m->track_refine;
+    m->track_pose_nf = 0;
+    if (tc.refine) {
+        tc.pose.assign((size_t)nf, mcorb_pose_result{});
+        tc.pose_flags.assign((size_t)C * total, 0);
+    }
+    if (!total || m->device < 0) {
         tc.rows.resize((size_t)C * total);
         tc.matches.resize((size_t)C * total);
         for (int f = 0; f < nf; f++) {
             const int nc = (int)(tc.first[f + 1] - tc.first[f]);
-            if (!nc) continue;
-            TrRow *rows = tc.rows.data() + (size_t)C * tc.first[f];
-            int32_t *n_proj = tc.n_proj.data() + (size_t)f * MCORB_MAX_CAMS;
-            rows_on_host(m, views[f], fr[f], tc.cand.data() + tc.first[f], nc, max_d2, max_hamming, rows, n_proj);
-            dedup_on_host(C, nc, rows, n_proj, fr[f].kp, tc.matches.data() + (size_t)C * tc.first[f],
-                          tc.n_match.data() + (size_t)f * MCORB_MAX_CAMS);
+            TrMatch *matches = tc.matches.data() + (size_t)C * tc.first[f];
+            int32_t *n_match = tc.n_match.data() + (size_t)f * MCORB_MAX_CAMS;
+            if (nc) {
+                TrRow *rows = tc.rows.data() + (size_t)C * tc.first[f];
+                int32_t *n_proj = tc.n_proj.data() + (size_t)f * MCORB_MAX_CAMS;
+                rows_on_host(m, views[f], fr[f], tc.cand.data() + tc.first[f], nc, max_d2, max_hamming, rows, n_proj);
+                dedup_on_host(C, nc, rows, n_proj, fr[f].kp, matches, n_match);
+            }
+            if (tc.refine)
+                pose_track_host(m, views[f], tc.cand.data() + tc.first[f], nc, matches, n_match, fr[f].kp.base, fr[f].kp.stride, tc.pose[f],
+                                tc.pose_flags.data() + (size_t)C * tc.first[f]);
         }
+        m->track_pose_nf = tc.refine ? nf : 0;
         ph.mark(3);
         return MCORB_OK;
     }
@@ -665,6 +704,7 @@ int submit_frames_body(mcorb_lmap *m, const mcorb_track_view *views, const std::
         return r;
     }
     tc.launched = tc.points = true;
+    m->track_pose_nf = tc.refine ? nf : 0;
     ph.mark(1);
     return MCORB_OK;
 }

@@ -1,0 +1,306 @@
+"""The rig pose refinement on the host-only store (device -1): mcorb_lmap_refine_pose against the plain-Python restatement
+(pose_ref.py) and against answers written out by hand.  Bit for bit, floats as raw bytes, unless a test says otherwise.  No GPU.
+
+On the commit before this call existed every test of this file fails (`python -m pytest tests/test_pose_cpu.py`): LocalMap has
+no refine_pose."""
+import ctypes as C
+import math
+
+import numpy as np
+import pytest
+
+import kfdb_cases as K
+import pose_cases as PC
+import pose_ref as P
+import track_cases as T
+
+
+@pytest.fixture(scope="module")
+def mc():
+    import mcorb
+    return mcorb
+
+
+@pytest.fixture(scope="module")
+def voc(mc):
+    return mc.ORBVocabulary(device=-1).create(**K.vocabulary())
+
+
+@pytest.fixture()
+def lm(mc, voc):
+    assert hasattr(mc.LocalMap, "refine_pose")
+    return mc.LocalMap(voc, device=-1, max_landmarks=4096, max_candidates=1024)
+
+
+@pytest.fixture(scope="module")
+def seeded():
+    """the seeded scene and its restatement, computed once"""
+    cams, truth, init, obs, moved = PC.scene()
+    return cams, truth, init, obs, moved, P.refine(cams, init, obs, PC.INV_SIGMA2)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# the Jacobian (the one comparison of this file with a tolerance)
+# ---------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("ncams", [1, 4])
+def test_jacobian_central_differences(mc, ncams):
+    """mcorb_pose_eval's J against central differences of its r through the Cayley retraction of the restatement: h = 1e-6,
+    pass at 1e-5 * max(1, |J_ij|).  The difference quotient of a 1e3 px value carries about 1e-16 * 1e3 / 1e-6 = 1e-7, and the
+    second-order term of the retraction h^2 * |r''| / 6 is smaller still.  Rigs with skew"""
+    cams, truth, init, obs, _ = PC.scene(ncams, nlm=12, moved=0.0)
+    cam, uv, octave, pts = PC.arrays(obs)
+    cc = PC.to_cams(mc, cams)
+    r0, J, w = mc.pose_eval(cc, init[0], init[1], cam, uv, pts)
+    assert len(obs) >= 10 and set(cam.tolist()) == set(range(ncams))
+    h = 1e-6
+    worst = 0.0
+    for k in range(6):
+        d = [0.0] * 6
+        d[k] = h
+        Rp, tp = P.retract(init, d)
+        d[k] = -h
+        Rm, tm = P.retract(init, d)
+        rp, _, _ = mc.pose_eval(cc, Rp, tp, cam, uv, pts)
+        rm, _, _ = mc.pose_eval(cc, Rm, tm, cam, uv, pts)
+        num = (rp - rm) / (2 * h)
+        for i in range(len(obs)):
+            for a in range(2):
+                err = abs(num[i, a] - J[i, a, k])
+                worst = max(worst, err / max(1.0, abs(J[i, a, k])))
+                assert err <= 1e-5 * max(1.0, abs(J[i, a, k])), (i, a, k, num[i, a], J[i, a, k])
+    print("worst relative difference %.3g" % worst)
+    # and the hook equals the restatement on the bits
+    for i, (c, kx, ky, _, X) in enumerate(obs):
+        r, Jr = P.residual(cams[c], init, X, kx, ky)
+        assert P.same_bits(r, r0[i].tolist()) and P.same_bits(Jr, J[i].tolist()), i
+        assert P.same_bits(P.huber(r)[0], float(w[i])), i
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# rows written out by hand
+# ---------------------------------------------------------------------------------------------------------------------------
+def test_cheirality_rows(mc, lm):
+    """q.z of 0.0, -0.0 and -1e-300 take the reference's branch: r = (2 fx, 2 fx), J = 0; 1e-300 and NaN do not"""
+    obs = PC.z_rows()
+    cam, uv, octave, pts = PC.arrays(obs)
+    r, J, w = mc.pose_eval(PC.to_cams(mc, PC.flat_rig()), PC.EYE, [0.0] * 3, cam, uv, pts)
+    z = [o[4][2] for o in obs]
+    for i in range(len(obs)):
+        rr, Jr = P.residual(PC.flat_rig()[0], PC.IDENT, obs[i][4], obs[i][1], obs[i][2])
+        if z[i] <= 0:
+            assert r[i].tolist() == [2.0, 2.0] and not J[i].any(), (i, z[i])
+        elif z[i] == 1e-300:
+            assert r[i, 0] == 1.0 * (1.0 / 1e-300) - 1.0 and r[i, 1] == 2.0 * (1.0 / 1e-300) - 2.0, i
+        elif z[i] != z[i]:
+            assert np.isnan(r[i]).all(), i
+        if z[i] == z[i]:
+            assert P.same_bits(rr, r[i].tolist()) and P.same_bits(Jr, J[i].tolist()), i
+    assert sum(1 for v in z if v <= 0) == 3 and sum(1 for v in z if v != v) == 1
+    for with_nan in (True, False):
+        o = PC.z_rows(with_nan)
+        ref = P.refine(PC.flat_rig(), PC.IDENT, o, PC.INV_SIGMA2)
+        PC.same(PC.as_ref(PC.refine(mc, lm, PC.flat_rig(), PC.IDENT, o)), ref, "z rows, NaN %s" % with_nan)
+        # an observation behind the rig has chi2 = 8 fx^2 = 8 > 5.991 and leaves; the NaN one never compares greater and stays
+        assert [ref["inliers"][i] for i in range(6, 10)] == [False, False, False, False]
+        if with_nan:
+            assert ref["status"] == P.NO_STEP and ref["inliers"][10] and P.same_bits(ref["R"], PC.EYE)
+
+
+def test_huber_at_k(mc, lm):
+    """e one ulp under k, exactly k and one ulp above: the weight is 1, 1 and k / e < 1"""
+    obs = PC.huber_rows()
+    k = P.HUBER_K
+    cam, uv, octave, pts = PC.arrays(obs)
+    r, J, w = mc.pose_eval(PC.to_cams(mc, PC.flat_rig()), PC.EYE, [0.0] * 3, cam, uv, pts)
+    e = [math.sqrt(v[0] * v[0] + v[1] * v[1]) for v in r.tolist()]
+    assert e == [math.nextafter(k, 0.0), k, math.nextafter(k, 10.0)]
+    assert w[0] == 1.0 and w[1] == 1.0 and w[2] == k / e[2] and w[2] < 1.0
+    for i, o in enumerate(obs):
+        rr, _ = P.residual(PC.flat_rig()[0], PC.IDENT, o[4], o[1], o[2])
+        assert P.same_bits(P.huber(rr)[0], float(w[i]))
+    PC.same(PC.as_ref(PC.refine(mc, lm, PC.flat_rig(), PC.IDENT, obs)), P.refine(PC.flat_rig(), PC.IDENT, obs, PC.INV_SIGMA2), "huber rows")
+
+
+def test_chi2_at_5_991_and_octaves(mc, lm):
+    """chi2 of exactly 5.991 stays, the next double above leaves; octaves with different inv_sigma2"""
+    obs, inv, flags = PC.chi2_rows()
+    assert 4.0 * inv[0] == 5.991 and 4.0 * inv[1] == math.nextafter(5.991, 10.0)
+    ref = P.refine(PC.flat_rig(), PC.IDENT, obs, inv)
+    assert ref["status"] == P.NO_STEP and ref["inliers"] == flags and P.same_bits(ref["R"], PC.EYE)
+    got = PC.refine(mc, lm, PC.flat_rig(), PC.IDENT, obs, inv)
+    PC.same(PC.as_ref(got), ref, "chi2 rows")
+    assert got.inliers.tolist() == flags and got.n_inliers == 4
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# the seeded scene
+# ---------------------------------------------------------------------------------------------------------------------------
+def test_seeded_scene(mc, lm, seeded):
+    """4 cameras, 200 landmarks, projections rounded to float, 20 % of them moved by 50 px, the initial pose off by 0.05 rad and
+    0.2 m.  Every moved observation is culled and every other one kept.  The pose error against the truth, read from the
+    restatement alone: 3.55e-9 rad and 1.24e-8 m (the float rounding of 630 keypoints, about 3e-5 px each); the pass mark is
+    ten times that reading, 3.6e-8 rad and 1.3e-7 m"""
+    cams, truth, init, obs, moved, ref = seeded
+    assert len(obs) > 700 and 0.15 < sum(moved) / len(obs) < 0.25
+    a0, d0 = PC.pose_error(init, truth)
+    assert abs(a0 - 0.05) < 1e-9 and abs(d0 - 0.2) < 1e-9
+    # the restatement alone first
+    assert ref["status"] == P.CONVERGED
+    assert all(ref["inliers"][i] != moved[i] for i in range(len(obs)))
+    ang, dist = PC.pose_error((ref["R"], ref["t"]), truth)
+    print("restatement: %.3g rad, %.3g m" % (ang, dist))
+    assert ang <= 3.6e-8 and dist <= 1.3e-7
+    for form in ("pts", "lids"):
+        got = PC.refine(mc, lm, cams, init, obs, form=form)
+        PC.same(PC.as_ref(got), ref, "seeded scene, " + form)
+        ang, dist = PC.pose_error((got.R.tolist(), got.t.tolist()), truth)
+        assert ang <= 3.6e-8 and dist <= 1.3e-7
+        assert got.n_obs == len(obs) and got.n_inliers == len(obs) - sum(moved)
+
+
+def test_max_iterations(mc, lm, seeded):
+    """1 solve per round ends MAX_ITER; 100 are never used up here"""
+    cams, truth, init, obs, moved, _ = seeded
+    for its in (1, 100):
+        ref = P.refine(cams, init, obs[:120], PC.INV_SIGMA2, its)
+        PC.same(PC.as_ref(PC.refine(mc, lm, cams, init, obs[:120], max_iterations=its)), ref, "max_iterations %d" % its)
+        assert ref["status"] == (P.MAX_ITER if its == 1 else P.CONVERGED) and max(ref["iterations"]) <= its
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# degenerate inputs
+# ---------------------------------------------------------------------------------------------------------------------------
+def test_degenerate(mc, lm, seeded):
+    cams, truth, init, obs, moved, _ = seeded
+    got = PC.refine(mc, lm, cams, init, [])
+    assert got.status == P.NO_OBS and P.same_bits(got.R.tolist(), init[0]) and P.same_bits(got.t.tolist(), init[1])
+    assert got.iterations == (0, 0) and got.n_inliers == 0 and got.n_obs == 0 and got.cost_initial == 0.0 and got.cost_final == 0.0
+    PC.same(PC.as_ref(got), P.refine(cams, init, [], PC.INV_SIGMA2), "no observation")
+    for n in (1, 2, 3):     # an under-determined H is still positive definite with its diagonal damped: steps are taken
+        PC.same(PC.as_ref(PC.refine(mc, lm, cams, init, obs[:n])), P.refine(cams, init, obs[:n], PC.INV_SIGMA2), "%d observations" % n)
+    # one observation that is met exactly: the cost is 0 and nothing is less
+    exact = [(0, 3.0, 4.0, 0, [3.0, 4.0, 1.0])]
+    ref = P.refine(PC.flat_rig(), PC.IDENT, exact, PC.INV_SIGMA2)
+    assert ref["status"] == P.NO_STEP and ref["cost_initial"] == 0.0 and ref["inliers"] == [True]
+    got = PC.refine(mc, lm, PC.flat_rig(), PC.IDENT, exact)
+    PC.same(PC.as_ref(got), ref, "an exact observation")
+    assert P.same_bits(got.R.tolist(), PC.EYE)
+    # all behind the rig: H is zero, no pivot is positive
+    behind = [(c, kx, ky, o, [-v for v in X]) for c, kx, ky, o, X in PC.z_rows(False)[:6]]
+    ref = P.refine(PC.flat_rig(), PC.IDENT, behind, PC.INV_SIGMA2)
+    assert ref["status"] == P.NO_STEP and ref["n_inliers"] == 0 and ref["iterations"] == (25, 25)
+    PC.same(PC.as_ref(PC.refine(mc, lm, PC.flat_rig(), PC.IDENT, behind)), ref, "all behind")
+    # a NaN in the initial pose: every cost is NaN, nothing is accepted, the pose comes back as it went in
+    bad = ([row[:] for row in init[0]], init[1][:])
+    bad[0][1][2] = float("nan")
+    ref = P.refine(cams, bad, obs[:40], PC.INV_SIGMA2)
+    assert ref["status"] == P.NO_STEP and ref["cost_initial"] != ref["cost_initial"]
+    got = PC.refine(mc, lm, cams, bad, obs[:40])
+    PC.same(PC.as_ref(got), ref, "NaN pose")
+    assert P.same_bits(got.R.tolist(), bad[0])
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# refusals
+# ---------------------------------------------------------------------------------------------------------------------------
+def read_back(lm, lids):
+    return [(p.tobytes(), q.tobytes()) for p, q, _, _ in (lm.get(int(l)) for l in lids)]
+
+
+def check_refusals(mc, lm, seeded):
+    cams, truth, init, obs, moved, _ = seeded
+    obs = obs[:20]
+    lids = PC.fill_points(lm, obs)
+    before = read_back(lm, lids)
+    cam, uv, octave, pts = PC.arrays(obs)
+    cc = PC.to_cams(mc, cams)
+
+    def refused(code, pending=False, **kw):
+        a = dict(cams=cc, R=init[0], t=init[1], cam=cam, uv=uv, octave=octave, inv_sigma2=PC.INV_SIGMA2, lids=lids)
+        a.update(kw)
+        with pytest.raises(mc.McorbError) as e:
+            lm.refine_pose(**a)
+        assert e.value.code == code, (kw.keys(), e.value)
+        assert pending or read_back(lm, lids) == before      # (a pending call refuses the read as well: read after the wait)
+
+    bad = cam.copy()
+    bad[7] = 4
+    refused(mc.E_ARG, cam=bad)
+    bad[7] = -1
+    refused(mc.E_ARG, cam=bad)
+    bad = octave.copy()
+    bad[3] = len(PC.INV_SIGMA2)
+    refused(mc.E_ARG, octave=bad)
+    bad[3] = -1
+    refused(mc.E_ARG, octave=bad)
+    bad = lids.copy()
+    bad[5] = 4096
+    refused(mc.E_ARG, lids=bad)
+    bad[5] = -1
+    refused(mc.E_ARG, lids=bad)
+    refused(mc.E_ARG, pts=pts)                      # both
+    refused(mc.E_ARG, lids=None)                    # neither
+    refused(mc.E_ARG, max_iterations=0)
+    refused(mc.E_ARG, max_iterations=101)
+    refused(mc.E_ARG, inv_sigma2=[])
+    refused(mc.E_ARG, inv_sigma2=[1.0] * 17)
+    bad = lids.copy()
+    bad[5] = 3000                                   # a slot that was never set
+    refused(mc.E_STATE, lids=bad)
+    # bad counts, through the C entry
+    res, par = mc._lib.PoseResultC(), mc.pose_params(PC.INV_SIGMA2)
+    R_, t_ = np.eye(3).reshape(9), np.zeros(3)
+    for n, ncams in ((-1, 4), (20, 0), (20, 17)):
+        code = lm.L.mcorb_lmap_refine_pose(lm.h, n, cam.ctypes.data, uv.ctypes.data, octave.ctypes.data, lids.ctypes.data, None, ncams,
+                                           C.addressof(cc.cams), R_.ctypes.data, t_.ctypes.data, C.byref(par), C.byref(res), None)
+        assert code == mc.E_ARG, (n, ncams)
+    assert read_back(lm, lids) == before
+    # while a tracking call is pending
+    v = T.to_view(mc, T.flat_view())
+    lm.track_submit(v, [np.zeros((0, 2), np.float32)], [np.zeros((0, 32), np.uint8)], [])
+    refused(mc.E_STATE, pending=True)
+    with pytest.raises(mc.McorbError) as e:
+        lm.set_track_refine(PC.INV_SIGMA2)
+    assert e.value.code == mc.E_STATE
+    lm.track_wait()
+    assert read_back(lm, lids) == before
+    # and it runs after all that
+    PC.same(PC.as_ref(lm.refine_pose(cc, init[0], init[1], cam, uv, octave, PC.INV_SIGMA2, lids=lids)),
+            P.refine(cams, init, obs, PC.INV_SIGMA2), "after the refusals")
+    assert read_back(lm, lids) == before
+
+
+def test_refusals(mc, lm, seeded):
+    check_refusals(mc, lm, seeded)
+
+
+def test_track_refine_state_rules(mc, lm):
+    """last_track_pose on a host-only store: MCORB_E_STATE before any call, with the option off and while pending; with the
+    option on a call without candidates answers NO_OBS with the view's pose"""
+    v = T.to_view(mc, T.view([T.cam()], 640, 480, R0=PC.rows_of(PC.rot([0, 0, 1], 0.3)), t0=(1.0, 2.0, 3.0)))
+    empty = ([np.zeros((0, 2), np.float32)], [np.zeros((0, 32), np.uint8)], [])
+
+    def state_error():
+        with pytest.raises(mc.McorbError) as e:
+            lm.last_track_pose()
+        assert e.value.code == mc.E_STATE
+
+    state_error()
+    lm.track(v, *empty)
+    state_error()
+    lm.set_track_refine(PC.INV_SIGMA2)
+    state_error()                                   # (the last call still ran without it)
+    lm.track_submit(v, *empty)
+    state_error()
+    lm.track_wait()
+    got = lm.last_track_pose()
+    R_, t_ = mc.pose_of_view(v)
+    want = P.pose_of_view(PC.rows_of(PC.rot([0, 0, 1], 0.3)), [1.0, 2.0, 3.0])
+    assert got.status == P.NO_OBS and P.same_bits(got.R.tolist(), want[0]) and P.same_bits(got.t.tolist(), want[1])
+    assert P.same_bits(R_.tolist(), want[0]) and P.same_bits(t_.tolist(), want[1])
+    with pytest.raises(mc.McorbError) as e:
+        lm.last_track_pose(1)
+    assert e.value.code == mc.E_ARG
+    lm.set_track_refine(None)
+    lm.track(v, *empty)
+    state_error()
