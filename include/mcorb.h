@@ -673,9 +673,10 @@ int mcorb_lmap_last_timing(mcorb_lmap *m, float us[2], int *n_candidates);
 /* Mapping: FrontEnd::triangulateNeighbors (MCSlam/src/FrontEnd.cpp:4856-4899) */
 /* with triangulateMatches (:5758-5953) and getSceneDepthStats (:4838-4853):  */
 /* the still-unassigned inter-frame matches of the current frame against its  */
-/* neighbouring keyframes become new landmarks of the local map.              */
-/* TriangulateNewLandmarks (:6465-6700), insertKeyFrame and the cv::Mat        */
-/* inverses stay with the caller.                                             */
+/* neighbouring keyframes become new landmarks of the local map; and the      */
+/* other half of FrontEnd::mapping (:6421-6463), TriangulateNewLandmarks       */
+/* (:6465-6700), as mcorb_lmap_triangulate_new below.  insertKeyFrame, uv_ref  */
+/* and the cv::Mat inverses stay with the caller.                             */
 /* ------------------------------------------------------------------------- */
 /* one keyframe's observations */
 typedef struct mcorb_map_frame {
@@ -753,6 +754,71 @@ int mcorb_host_map_gates(int n, const double *X, const int32_t *nv1, const int32
 int mcorb_dev_map_gates_selftest(int device, int n, const double *X, const int32_t *nv1, const int32_t *nv, const double *P,
                                  const double *K, const double *centre, const float *kps, const int32_t *octave, const double *F,
                                  const float *inv_sigma2, int nlevels, int32_t *verdict, int32_t *n_rays, double *vals);
+
+/* the outputs of mcorb_lmap_triangulate_new.  The per-match arrays have cap_matches entries (3 x cap_matches for pt3d and normal);
+ * depth_vec has cap_depth. */
+typedef struct mcorb_map_new_out {
+    int32_t cap_matches, cap_depth;  /* in */
+    uint8_t *inliers;                /* triangulation_inliers[i] as the function leaves it: true exactly for a new landmark */
+    uint8_t *verdict;                /* 0 a new landmark, 3 behind a camera at the initial point, 4 chi-square after the refinement,
+                                      * 5 parallax (cos >= 0.99998: NOT an inlier here, unlike triangulate_neighbours' window), 6 the
+                                      * current feature had a landmark already, 8 degenerate (an initial point that is not finite) */
+    int32_t *new_lid;                /* the new landmark's id, or -1 */
+    double *pt3d, *normal;           /* of the new landmark (zero where new_lid is -1) */
+    double *dist;                    /* norm(X - cur->twc), for verdicts 0 and 5, else zero */
+    float *cos_parallax;             /* the reference's float, for verdicts 0 and 5, else zero */
+    int32_t *iterations;             /* solves of the refinement, for verdicts 0, 4 and 5, else zero */
+    double *cost_initial, *cost_final; /* 0.5 * sum |r|^2 at the initial point and at the result, for verdicts 0, 4 and 5 */
+    double *depth_vec;               /* dist of the new landmarks in the order they were made (:6616) */
+    double avg_depth;                /* out: their sum, added in that order (:6617; the reference never divides it) */
+    int32_t n_rays_hist[MCORB_MAX_CAMS]; /* out: [views of the current feature - 1] per new landmark (:6687) */
+    int32_t n_by_verdict[9];         /* out: matches per verdict */
+    int32_t n_matches, n_depth, n_triangulated, next_lid;   /* out; next_lid: the first id not given out */
+} mcorb_map_new_out;
+/* FrontEnd::TriangulateNewLandmarks (:6465-6700): the current frame's new_inter_matches against the previous keyframe become new
+ * landmarks.  cur / lids_cur, prev / lids_prev: the two frames (mcorb_map_frame, as above) and their lIds; match_query /
+ * match_train: queryIdx into prev's features, trainIdx into cur's; K, inv_sigma2, nlevels, next_lid as above.
+ * Matches in order: verdict 6 when lids_cur[t] != -1 -- only the current frame's id is tested (:6486), so lids_prev[q] is
+ * overwritten by a later landmark, as in the reference.  Otherwise the views of both features (getDataForGTSAMTriangulation,
+ * :4802-4827: prev's first, cameras ascending; the camera is proj and K with skew 0), then
+ *   the initial point: the DLT of triangulate_neighbours on normalised coordinates.  Stated deviation: gtsam's triangulateSafe
+ *     runs its DLT on pixel coordinates through an SVD with a rank test at 0.001; degenerate is here "a component is not finite"
+ *     (verdict 8).  p.z <= 0 in any view at the initial point is verdict 3; the distance and reprojection thresholds are off (-1, 0);
+ *   the refinement: TriangulationFactor<PinholeCamera<Cal3_S2>> with unit noise, recalled as the tracking and pose sections recall
+ *     gtsam: r = (fx u + u0 - kx, fy v + v0 - ky), and r = (2 fx, 2 fx) with a zero Jacobian when p.z <= 0 (throwCheirality is
+ *     false by default, so the reference's catch at :6577 is dead and a point that ends behind a camera fails the chi-square gate).
+ *     Stated deviations: p = P[:, :3] X + P[:, 3] instead of gtsam's transformTo (rounding level), and a stated Levenberg-Marquardt
+ *     schedule with the reference's parameters (:6529-6538) in place of gtsam's: lambda 1, factor 10, (H + lambda I) delta = -g by a
+ *     3 x 3 LDL^T, a trial accepted iff the cost falls, the end on an accepted decrease <= 1.0 or <= 1e-5 * cost, after 50 solves,
+ *     or when lambda > 1e5; the result is the last accepted point or the initial one;
+ *   the cull: the first view with |r|^2 * inv_sigma2[octave] > 5.991 at the result is verdict 4 (a NaN passes);
+ *   the parallax: dist = norm(X - cur->twc), dist1 = (float)norm(X - prev->twc), cos = (float)(dot / (dist1 * dist)); cos >= 0.99998
+ *     is verdict 5 and inliers false; there is no lower bound and a NaN makes a landmark.
+ * A new landmark takes the next id, written to both lIds; dist is appended to depth_vec and added to avg_depth; its point, its
+ * normal (updateNormal for prev, then for cur, as above) and n_rays go into slot id of the map.  All arithmetic is fp64 (float where
+ * stated) with separate multiplies and adds.  A device store computes the per-match part in k_map_refine_new, one lane per match
+ * whose current feature is free on entry, and moves the accepted records into their slots device to device; a host-only store
+ * runs the same code serially; the results are equal bit for bit (a NaN that is returned is the default quiet NaN).
+ * MCORB_E_ARG, MCORB_E_CAP and MCORB_E_STATE (a pending tracking call) as for mcorb_lmap_triangulate_neighbours, before anything
+ * runs and with the store and both lIds untouched. */
+int mcorb_lmap_triangulate_new(mcorb_lmap *m, const mcorb_map_frame *cur, int32_t *lids_cur, const mcorb_map_frame *prev, int32_t *lids_prev,
+                               const int32_t *match_query, const int32_t *match_train, int n_matches, const double *K,
+                               const float *inv_sigma2, int nlevels, int32_t next_lid, mcorb_map_new_out *out);
+/* a device store's last k_map_refine_new launches (both instances), microseconds between HIP events, and the matches that were
+ * launched (may be NULL); a call with nothing to launch launches nothing and leaves both */
+int mcorb_lmap_last_triangulate_new_timing(mcorb_lmap *m, float us[1], int *n_launched);
+/* test hooks: everything of a match after the DLT -- the degenerate and behind tests at X0, the refinement, the cull, the parallax
+ * and the normal -- for n cases on the host and in one launch on the device.  Views as for mcorb_host_map_gates; X0, twc_cur and
+ * twc_prev 3 doubles per case.  verdict / n_rays / solves / cosp: n entries; vals: 9 per case (X, normal, dist, cost_initial,
+ * cost_final). */
+int mcorb_host_map_refine(int n, const double *X0, const int32_t *nv1, const int32_t *nv, const double *P, const double *K,
+                          const double *centre, const float *kps, const int32_t *octave, const double *twc_cur, const double *twc_prev,
+                          const float *inv_sigma2, int nlevels, int32_t *verdict, int32_t *n_rays, int32_t *solves, float *cosp,
+                          double *vals);
+int mcorb_dev_map_refine_selftest(int device, int n, const double *X0, const int32_t *nv1, const int32_t *nv, const double *P,
+                                  const double *K, const double *centre, const float *kps, const int32_t *octave, const double *twc_cur,
+                                  const double *twc_prev, const float *inv_sigma2, int nlevels, int32_t *verdict, int32_t *n_rays,
+                                  int32_t *solves, float *cosp, double *vals);
 
 /* ------------------------------------------------------------------------- */
 /* Landmarks: the local map kept up to date as keyframes are inserted --      */

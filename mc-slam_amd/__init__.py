@@ -1040,6 +1040,17 @@ class TriangulationResult:
         self.__dict__.update(kw)
 
 
+class NewLandmarksResult:
+    """what LocalMap.triangulate_new returns.  Per match: inliers (true exactly for a new landmark), verdict (0 landmark, 3 behind a
+    camera at the initial point, 4 chi-square, 5 parallax, 6 the current feature had a landmark already, 8 degenerate), new_lid
+    (-1: none), pt3d, normal, dist, cos_parallax (float32), iterations, cost_initial, cost_final; depth_vec in the order the
+    landmarks were made, avg_depth (their sum), n_rays_hist, n_by_verdict, n_triangulated, next_lid; lids_cur and lids_prev as the
+    call leaves them"""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
 class LocalMap:
     """FrontEnd::searchLocalMap2 (MCSlam/src/FrontEnd.cpp:4901-5223) up to the camera-filtered matches (mcorb_lmap): a store of
     landmarks (slot = lId: pt3D, normal, the latest observation's descriptor and mono flag) and the search of a frame held in a
@@ -1172,6 +1183,48 @@ class LocalMap:
                                    cos_parallax=r["cos_parallax"][:total].copy(), neigh_skipped=r["neigh_skipped"][:S].copy(),
                                    depth_vec=r["depth_vec"][:nd].copy(), n_triangulated=o.n_triangulated, next_lid=o.next_lid,
                                    lids_cur=lc, lids_neigh=ln, offsets=offsets)
+
+    def triangulate_new(self, cur, lids_cur, prev, lids_prev, matches, K_mats, inv_sigma2, next_lid, caps=None):
+        """FrontEnd::TriangulateNewLandmarks (FrontEnd.cpp:6465-6700) -> NewLandmarksResult; the new landmarks' points, normals and
+        ray counts are stored in their slots.  cur / prev: map_frame(...) of the current frame and of the previous keyframe;
+        lids_cur / lids_prev: their lIds (copied: the result holds the updated arrays); matches: an n x 2 array (queryIdx into
+        prev, trainIdx into cur); K_mats: per camera (the skew is not read); inv_sigma2: GetInverseScaleSigmaSquares(); caps:
+        (matches, depth_vec) output sizes, by default what cannot be exceeded"""
+        nc = cur.struct.ncams
+        lc, lp = np.array(lids_cur, np.int32).reshape(-1), np.array(lids_prev, np.int32).reshape(-1)
+        assert len(lc) == cur.struct.nfeat and len(lp) == prev.struct.nfeat
+        self.map_new_lids = lc, lp   # (what the call reads and writes: a refused call leaves them as they came in)
+        ms = np.asarray(matches, np.int32).reshape(-1, 2)
+        mq, mt = np.ascontiguousarray(ms[:, 0]), np.ascontiguousarray(ms[:, 1])
+        total = len(ms)
+        cap_m, cap_d = caps if caps is not None else (total, total)
+        Kc = np.ascontiguousarray(K_mats, np.float64).reshape(nc, 9)
+        sig = np.ascontiguousarray(inv_sigma2, np.float32).reshape(-1)
+        n1, n3 = max(cap_m, 1), 3 * max(cap_m, 1)
+        r = dict(inliers=np.zeros(n1, np.uint8), verdict=np.zeros(n1, np.uint8), new_lid=np.zeros(n1, np.int32), pt3d=np.zeros(n3),
+                 normal=np.zeros(n3), dist=np.zeros(n1), cos_parallax=np.zeros(n1, np.float32), iterations=np.zeros(n1, np.int32),
+                 cost_initial=np.zeros(n1), cost_final=np.zeros(n1), depth_vec=np.zeros(max(cap_d, 1)))
+        o = self.map_new_out = _lib.MapNewOut()
+        o.cap_matches, o.cap_depth = cap_m, cap_d
+        for k, a in r.items():
+            setattr(o, k, a.ctypes.data)
+        _lib.check(self.L.mcorb_lmap_triangulate_new(self.h, C.byref(cur.struct), lc.ctypes.data, C.byref(prev.struct), lp.ctypes.data,
+                                                     mq.ctypes.data, mt.ctypes.data, total, Kc.ctypes.data, sig.ctypes.data, len(sig),
+                                                     int(next_lid), C.byref(o)))
+        cut = lambda k, w=1: r[k][:w * total].copy()
+        return NewLandmarksResult(inliers=r["inliers"][:total].astype(bool), verdict=cut("verdict"), new_lid=cut("new_lid"),
+                                  pt3d=cut("pt3d", 3).reshape(-1, 3), normal=cut("normal", 3).reshape(-1, 3), dist=cut("dist"),
+                                  cos_parallax=cut("cos_parallax"), iterations=cut("iterations"), cost_initial=cut("cost_initial"),
+                                  cost_final=cut("cost_final"), depth_vec=r["depth_vec"][:o.n_depth].copy(), avg_depth=o.avg_depth,
+                                  n_rays_hist=np.array(o.n_rays_hist[:], np.int32), n_by_verdict=np.array(o.n_by_verdict[:], np.int32),
+                                  n_triangulated=o.n_triangulated, next_lid=o.next_lid, lids_cur=lc, lids_prev=lp)
+
+    def last_triangulate_new_timing(self):
+        """(microseconds of the last k_map_refine_new launches, matches launched); a device store"""
+        us = (C.c_float * 1)()
+        n = C.c_int()
+        _lib.check(self.L.mcorb_lmap_last_triangulate_new_timing(self.h, us, C.byref(n)))
+        return us[0], n.value
 
     def depths(self, Rcw, tcw, lids):
         """getSceneDepthStats' depthVec before its sort: z of Rcw * pt3D + tcw for the landmarks `lids`"""
@@ -1642,6 +1695,32 @@ def map_gates(X, nv1, nv, P, K, centre, kps, octave, F, inv_sigma2, device=None)
     L = _lib.load()
     _lib.check(L.mcorb_host_map_gates(*args) if device is None else L.mcorb_dev_map_gates_selftest(device, *args))
     return verdict[:n], rays[:n], vals[:n, 0].copy(), vals[:n, 1].copy(), vals[:n, 2:].copy()
+
+
+def map_refine(X0, nv1, nv, P, K, centre, kps, octave, twc_cur, twc_prev, inv_sigma2, device=None):
+    """the test hooks mcorb_host_map_refine (device None) / mcorb_dev_map_refine_selftest: everything of a match of
+    LocalMap.triangulate_new after the DLT for n cases with caller-given X0 -> (verdict, n_rays, solves, cos (float32), X, normal,
+    dist, cost_initial, cost_final).  Views back to back as for map_gates; per case X0 (3), nv1, nv, twc_cur (3), twc_prev (3)"""
+    X0 = np.ascontiguousarray(X0, np.float64).reshape(-1, 3)
+    n = len(X0)
+    nv1, nv = np.ascontiguousarray(nv1, np.int32).reshape(-1), np.ascontiguousarray(nv, np.int32).reshape(-1)
+    P, K = np.ascontiguousarray(P, np.float64).reshape(-1, 12), np.ascontiguousarray(K, np.float64).reshape(-1, 9)
+    centre, kps = np.ascontiguousarray(centre, np.float64).reshape(-1, 3), np.ascontiguousarray(kps, np.float32).reshape(-1, 2)
+    octave = np.ascontiguousarray(octave, np.int32).reshape(-1)
+    tc, tp = np.ascontiguousarray(twc_cur, np.float64).reshape(-1, 3), np.ascontiguousarray(twc_prev, np.float64).reshape(-1, 3)
+    sig = np.ascontiguousarray(inv_sigma2, np.float32).reshape(-1)
+    V = int(nv.sum()) if len(nv) == n else -1
+    if not (len(nv1) == len(tc) == len(tp) == n and len(P) == len(K) == len(centre) == len(kps) == len(octave) == V):
+        raise ValueError("map_refine: array lengths do not fit the view counts")
+    m = max(n, 1)
+    verdict, rays, solves, cosp, vals = np.zeros(m, np.int32), np.zeros(m, np.int32), np.zeros(m, np.int32), np.zeros(m, np.float32), np.zeros((m, 9))
+    args = (n, X0.ctypes.data, nv1.ctypes.data, nv.ctypes.data, P.ctypes.data, K.ctypes.data, centre.ctypes.data, kps.ctypes.data,
+            octave.ctypes.data, tc.ctypes.data, tp.ctypes.data, sig.ctypes.data, len(sig), verdict.ctypes.data, rays.ctypes.data,
+            solves.ctypes.data, cosp.ctypes.data, vals.ctypes.data)
+    L = _lib.load()
+    _lib.check(L.mcorb_host_map_refine(*args) if device is None else L.mcorb_dev_map_refine_selftest(device, *args))
+    return (verdict[:n], rays[:n], solves[:n], cosp[:n], vals[:n, 0:3].copy(), vals[:n, 3:6].copy(), vals[:n, 6].copy(),
+            vals[:n, 7].copy(), vals[:n, 8].copy())
 
 
 class DescriptorBlock:

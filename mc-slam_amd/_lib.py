@@ -64,6 +64,15 @@ class MapOut(C.Structure):
                 ("n_depth", C.c_int32), ("n_triangulated", C.c_int32), ("next_lid", C.c_int32)]
 
 
+class MapNewOut(C.Structure):
+    _fields_ = [("cap_matches", C.c_int32), ("cap_depth", C.c_int32), ("inliers", C.c_void_p), ("verdict", C.c_void_p),
+                ("new_lid", C.c_void_p), ("pt3d", C.c_void_p), ("normal", C.c_void_p), ("dist", C.c_void_p),
+                ("cos_parallax", C.c_void_p), ("iterations", C.c_void_p), ("cost_initial", C.c_void_p), ("cost_final", C.c_void_p),
+                ("depth_vec", C.c_void_p), ("avg_depth", C.c_double), ("n_rays_hist", C.c_int32 * MAX_CAMS),
+                ("n_by_verdict", C.c_int32 * 9), ("n_matches", C.c_int32), ("n_depth", C.c_int32), ("n_triangulated", C.c_int32),
+                ("next_lid", C.c_int32)]
+
+
 class ObsFrame(C.Structure):
     _fields_ = [("kf_id", C.c_int32), ("nfeat", C.c_int32), ("ncams", C.c_int32), ("reserved", C.c_int32), ("match_index", C.c_void_p),
                 ("centre_w", C.c_double * 3 * MAX_CAMS)]
@@ -242,6 +251,11 @@ SIGNATURES = {
                                                C.POINTER(MapOut)]),
     "mcorb_lmap_depths": (_i, [_vp, _vp, _vp, _vp, _i, _vp]),
     "mcorb_lmap_last_triangulate_timing": (_i, [_vp, C.POINTER(_f), _ip, _ip]),
+    "mcorb_lmap_triangulate_new": (_i, [_vp, C.POINTER(MapFrame), _vp, C.POINTER(MapFrame), _vp, _vp, _vp, _i, _vp, _vp, _i, _i,
+                                        C.POINTER(MapNewOut)]),
+    "mcorb_lmap_last_triangulate_new_timing": (_i, [_vp, C.POINTER(_f), _ip]),
+    "mcorb_host_map_refine": (_i, [_i] + [_vp] * 11 + [_i] + [_vp] * 5),
+    "mcorb_dev_map_refine_selftest": (_i, [_i, _i] + [_vp] * 11 + [_i] + [_vp] * 5),
     "mcorb_host_map_gates": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
     "mcorb_dev_map_gates_selftest": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
     "mcorb_lmap_set_rays": (_i, [_vp, _vp, _i, _vp]),

@@ -6,7 +6,7 @@
 #include <vector>
 #include "../../include/mcorb.h"
 #include "mcorb_common.h"
-#include "mcorb_mapping.h"
+#include "mcorb_mapping_new.h"
 #include "mcorb_pose.h"
 #include "mcorb_signal.h"
 #include "mcorb_track.h"
@@ -169,6 +169,11 @@ void launch_map_depth(hipStream_t st, const double Rcw[9], const double tcw[3], 
 void launch_map_put(hipStream_t st, const MapOut *rec, const int2 *put, int n, double *geom, int32_t *nrays);
 // the gates of n caller-given cases (mcorb_dev_map_gates_selftest); every pointer of c is device memory
 void launch_map_gates(hipStream_t st, const MapGateCases &c, int n, MapOut *out);
+// k_map_refine_new: one lane per match of TriangulateNewLandmarks, k_map_triangulate's blocks and two instances; a.blocks[0 ..
+// nblocks_small) hold matches of at most 4 views
+void launch_map_refine_new(hipStream_t st, const MapNewArgs &n, int nblocks_small, int nblocks_any);
+// everything after the DLT for n caller-given cases (mcorb_dev_map_refine_selftest); every pointer of c is device memory
+void launch_map_refine_cases(hipStream_t st, const MapRefineCases &c, int n, MapOut *out, MapNewExtra *extra);
 
 
 // the landmarks' life (mcorb_landmark_gpu.hip).  k_lmap_observe: one lane per item of one round of mcorb_lmap_observe -- no two

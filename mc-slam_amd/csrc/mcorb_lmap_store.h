@@ -8,7 +8,7 @@
 #include <vector>
 
 #include "mcorb_kfdb_store.h"
-#include "mcorb_mapping.h"
+#include "mcorb_mapping_new.h"
 #include "mcorb_pose.h"
 #include "mcorb_track.h"
 
@@ -69,6 +69,12 @@ struct mcorb_lmap {
     mcorb::Event ev2, ev3;
     float us_map_depth = 0.f, us_map_tri = 0.f;
     int last_map_launched = 0, last_map_depth = 0;
+    // mcorb_lmap_triangulate_new (mcorb_mapping.cpp) shares the scratch above (ev2 / ev3 around its kernel) and adds the second
+    // half of its records
+    mcorb::HostBuf<mcorb::MapNewExtra> h_mapextra;
+    mcorb::DevBuf<mcorb::MapNewExtra> d_mapextra;
+    float us_map_new = 0.f;
+    int last_map_new_launched = 0;
     // the landmarks' life (mcorb_landmark.cpp).  n_rays: the host's copy of every slot's ray count (a device store's kernels read
     // and write d_nrays); obs: per slot the observations (kf_id, feat) in the order they were added (KFs / featInds); occ: per
     // slot how often a batch has named it so far, zero between calls

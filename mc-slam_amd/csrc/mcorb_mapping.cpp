@@ -1,6 +1,6 @@
 // mcorb_mapping.cpp -- FrontEnd::triangulateNeighbors (MCSlam/src/FrontEnd.cpp:4856-4899) with triangulateMatches (:5758-5953) and
 // getSceneDepthStats (:4838-4853): the still-unassigned inter-frame matches of the current frame against its neighbouring keyframes
-// become new landmarks of the local map (mcorb_lmap_store.h).  Not restated: TriangulateNewLandmarks (:6465-6700), insertKeyFrame
+// become new landmarks of the local map (mcorb_lmap_store.h).  Not restated: insertKeyFrame
 // and the cv::Mat inverses; the caller passes cur_T_ref * pose.inv() per camera, W_T_cur's translation per camera and F21.
 //
 // The per-match arithmetic is mcorb_mapping.h.  A device store runs it for every match whose two features have no landmark on
@@ -10,6 +10,10 @@
 // every later match of either feature.  An id is only ever set, never cleared, so a match that is assigned on entry is skipped in
 // the walk too and needs no record.  The accepted points, normals and ray counts go from the records into their slots device to
 // device (k_map_put); the frames carry no keyframe id, so the caller registers the two observations (mcorb_lmap_observe).
+//
+// mcorb_lmap_triangulate_new is the other half of FrontEnd::mapping: TriangulateNewLandmarks (:6465-6700) on the current frame's
+// new_inter_matches against the previous keyframe.  Its per-match arithmetic is mcorb_mapping_new.h (k_map_refine_new on a device
+// store); its walk tests the current frame's id alone, so the previous keyframe's id is overwritten by a later landmark.
 #include <math.h>
 #include <string.h>
 
@@ -44,7 +48,9 @@ struct Layout {
     }
 };
 
-int bad(const char *what) { set_error(std::string("lmap triangulate_neighbours: ") + what); return MCORB_E_ARG; }
+// the entry that is checking its arguments (one call at a time per thread)
+thread_local const char *g_who = "lmap triangulate_neighbours";
+int bad(const char *what) { set_error(std::string(g_who) + ": " + what); return MCORB_E_ARG; }
 
 // a frame's arrays: camera count, indices inside the keypoint lists
 int check_frame(const mcorb_map_frame &f, int ncams)
@@ -130,6 +136,20 @@ void gates_out(const MapOut *o, int n, int32_t *verdict, int32_t *n_rays, double
     }
 }
 
+// vals: 9 per case (X, normal, dist, cost_initial, cost_final)
+void refine_out(const MapOut *o, const MapNewExtra *e, int n, int32_t *verdict, int32_t *n_rays, int32_t *solves, float *cosp, double *vals)
+{
+    for (int i = 0; i < n; i++) {
+        verdict[i] = o[i].verdict;
+        n_rays[i] = o[i].n_rays;
+        solves[i] = e[i].solves;
+        cosp[i] = e[i].cos;
+        double *v = vals + 9 * (size_t)i;
+        for (int k = 0; k < 3; k++) { v[k] = o[i].X[k]; v[3 + k] = o[i].normal[k]; }
+        v[6] = o[i].dist2; v[7] = e[i].cost_initial; v[8] = e[i].cost_final;
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -140,6 +160,7 @@ int mcorb_lmap_triangulate_neighbours(mcorb_lmap *m, const mcorb_map_frame *cur,
                                       const double *K, const float *inv_sigma2, int nlevels, const double Rcw[9], const double tcw[3],
                                       int32_t next_lid, mcorb_map_out *out)
 {
+    g_who = "lmap triangulate_neighbours";
     if (out) { out->n_matches = out->n_depth = out->n_triangulated = 0; out->next_lid = next_lid; }
     TRY(check_lmap(m, "lmap triangulate_neighbours"));
     if (!cur || !out || n_neigh < 0 || !K || !inv_sigma2 || nlevels < 1 || !Rcw || !tcw || next_lid < 0 || out->cap_matches < 0 ||
@@ -499,6 +520,290 @@ int mcorb_dev_map_gates_selftest(int device, int n, const double *X, const int32
     std::vector<MapOut> o(N);
     HIPCHK(hipMemcpy(o.data(), d_out, N * sizeof(MapOut), hipMemcpyDeviceToHost));
     gates_out(o.data(), n, verdict, n_rays, vals);
+    return MCORB_OK;
+}
+
+int mcorb_lmap_triangulate_new(mcorb_lmap *m, const mcorb_map_frame *cur, int32_t *lids_cur, const mcorb_map_frame *prev, int32_t *lids_prev,
+                               const int32_t *match_query, const int32_t *match_train, int n_matches, const double *K,
+                               const float *inv_sigma2, int nlevels, int32_t next_lid, mcorb_map_new_out *out)
+{
+    g_who = "lmap triangulate_new";
+    if (out) {
+        out->n_matches = out->n_depth = out->n_triangulated = 0;
+        out->next_lid = next_lid;
+        out->avg_depth = 0.0;
+        memset(out->n_rays_hist, 0, sizeof(out->n_rays_hist));
+        memset(out->n_by_verdict, 0, sizeof(out->n_by_verdict));
+    }
+    TRY(check_lmap(m, "lmap triangulate_new"));
+    if (!cur || !prev || !out || n_matches < 0 || !K || !inv_sigma2 || nlevels < 1 || next_lid < 0 || out->cap_matches < 0 ||
+        out->cap_depth < 0 || (cur->nfeat && !lids_cur) || (prev->nfeat && !lids_prev) || (n_matches && (!match_query || !match_train)))
+        return bad("bad argument");
+    const int C = cur->ncams;
+    if (C < 1 || C > MCORB_MAX_CAMS) return bad("1 .. MCORB_MAX_CAMS cameras");
+    std::lock_guard<std::mutex> lk(m->mu);
+
+    // ---- 1. everything that can be refused is refused before anything runs ----
+    TRY(check_frame(*cur, C));
+    TRY(check_frame(*prev, C));
+    for (int i = 0; i < cur->nfeat; i++)
+        if (lids_cur[i] < -1 || lids_cur[i] >= m->max_landmarks) return bad("landmark id outside the store");
+    for (int i = 0; i < prev->nfeat; i++)
+        if (lids_prev[i] < -1 || lids_prev[i] >= m->max_landmarks) return bad("landmark id outside the store");
+    const size_t total = (size_t)n_matches;
+    std::vector<uint8_t> nviews(total, 0), nviews_cur(total, 0);
+    for (int j = 0; j < n_matches; j++) {
+        const int q = match_query[j], t = match_train[j];
+        if (q < 0 || q >= prev->nfeat || t < 0 || t >= cur->nfeat) return bad("match index outside a frame");
+        const int v1 = views_of(*prev, q, nlevels), v2 = views_of(*cur, t, nlevels);
+        if (v1 < 0 || v2 < 0) return bad("octave outside nlevels");
+        if (v1 < 1 || v2 < 1) return bad("a matched feature without a view");
+        if (v1 + v2 > MCORB_MAX_CAMS) return bad("a match of more than MCORB_MAX_CAMS views in total (the solver's design limit)");
+        nviews[j] = (uint8_t)(v1 + v2);
+        nviews_cur[j] = (uint8_t)v2;
+    }
+    out->n_matches = n_matches;
+    if (n_matches > out->cap_matches) { set_error("lmap triangulate_new: output too small"); return MCORB_E_CAP; }
+    if (total && (!out->inliers || !out->verdict || !out->new_lid || !out->pt3d || !out->normal || !out->dist || !out->cos_parallax ||
+                  !out->iterations || !out->cost_initial || !out->cost_final))
+        return bad("bad argument");
+
+    // ---- 2. the matches whose current feature is free on entry, by view count: blocks of one wave, <= 4 views first ----
+    const bool dev = m->device >= 0;
+    std::vector<int32_t> item_of(total, -1);
+    std::vector<MapItem> items;
+    std::vector<MapBlock> blocks;
+    int nblocks_small = 0;
+    if (dev) {
+        std::vector<int> order;
+        for (int pass = 0; pass < 2; pass++) {   // 0: at most 4 views, 1: the rest
+            order.clear();
+            for (int j = 0; j < n_matches; j++) {
+                if ((nviews[j] <= 4) != (pass == 0) || lids_cur[match_train[j]] != -1) continue;
+                order.push_back(j);
+            }
+            std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return nviews[a] < nviews[b]; });
+            for (size_t k = 0; k < order.size(); k++) {
+                if (k % kMapBlock == 0)
+                    blocks.push_back(MapBlock{0, (int32_t)items.size(), (int32_t)std::min<size_t>(kMapBlock, order.size() - k)});
+                const int j = order[k];
+                item_of[j] = (int32_t)items.size();
+                items.push_back(MapItem{match_query[j], match_train[j], (int32_t)items.size()});
+            }
+            if (pass == 0) nblocks_small = (int)blocks.size();
+        }
+    }
+    const int nitems = (int)items.size();
+
+    // ---- 3. the packed input: the current frame, then the previous keyframe ----
+    Layout L;
+    size_t nmi = ((size_t)cur->nfeat + (size_t)prev->nfeat) * C, nkp = 0;
+    for (int c = 0; c < C; c++) nkp += (size_t)cur->nkps[c] + (size_t)prev->nkps[c];
+    if (nmi > 0x7fffffff || nkp > 0x7fffffff) return bad("frames too large");
+    L.frames = 0;
+    L.F = align8(L.frames + 2 * sizeof(MapFrameDev));
+    L.K = L.F;
+    L.sig = L.K + (size_t)C * 9 * sizeof(double);
+    L.mi = align8(L.sig + (size_t)nlevels * sizeof(float));
+    L.kp = align8(L.mi + nmi * sizeof(int32_t));
+    L.blocks = align8(L.kp + nkp * sizeof(MapKp));
+    L.items = align8(L.blocks + blocks.size() * sizeof(MapBlock));
+    L.zlids = L.total = align8(L.items + items.size() * sizeof(MapItem));
+    std::vector<uint8_t> host_block;
+    uint8_t *base;
+    if (dev && nitems) {
+        HIPCHK(hipSetDevice(m->device));
+        TRY(m->h_mapin.grow(L.total, hipHostMallocDefault));
+        TRY(m->d_mapin.grow(L.total));
+        base = m->h_mapin;
+    } else {
+        host_block.resize(L.total);
+        base = host_block.data();
+    }
+    {
+        MapFrameDev *fr = (MapFrameDev *)(base + L.frames);
+        size_t mi_at = 0, kp_at = 0;
+        pack_frame(*cur, fr[0], (int32_t *)(base + L.mi), mi_at, (MapKp *)(base + L.kp), kp_at);
+        pack_frame(*prev, fr[1], (int32_t *)(base + L.mi), mi_at, (MapKp *)(base + L.kp), kp_at);
+        memcpy(base + L.K, K, (size_t)C * 9 * sizeof(double));
+        memcpy(base + L.sig, inv_sigma2, (size_t)nlevels * sizeof(float));
+        if (!blocks.empty()) memcpy(base + L.blocks, blocks.data(), blocks.size() * sizeof(MapBlock));
+        if (!items.empty()) memcpy(base + L.items, items.data(), items.size() * sizeof(MapItem));
+    }
+    MapNewArgs na;
+    for (int k = 0; k < 3; k++) { na.twc_cur[k] = cur->twc[k]; na.twc_prev[k] = prev->twc[k]; }
+
+    // ---- 4. the records: one submission ----
+    if (dev && nitems) {
+        hipStream_t st = m->st;
+        TRY(m->h_mapout.grow((size_t)nitems, hipHostMallocDefault));
+        TRY(m->d_mapout.grow((size_t)nitems));
+        TRY(m->h_mapextra.grow((size_t)nitems, hipHostMallocDefault));
+        TRY(m->d_mapextra.grow((size_t)nitems));
+        na.a = L.args(m->d_mapin, m->d_mapout, C);
+        na.extra = m->d_mapextra;
+        HIPCHK(hipMemcpyAsync(m->d_mapin, m->h_mapin, L.total, hipMemcpyHostToDevice, st));
+        HIPCHK(hipEventRecord(m->ev2, st));
+        launch_map_refine_new(st, na, nblocks_small, (int)blocks.size() - nblocks_small);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(m->ev3, st));
+        HIPCHK(hipMemcpyAsync(m->h_mapout, m->d_mapout, (size_t)nitems * sizeof(MapOut), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(m->h_mapextra, m->d_mapextra, (size_t)nitems * sizeof(MapNewExtra), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        float ms = 0.f;
+        ev_elapsed(&ms, m->ev2, m->ev3);
+        m->us_map_new = ms * 1000.f;
+        m->last_map_new_launched = nitems;
+    }
+
+    // ---- 5. the walk (:6476-6491, :6673-6690): matches in order, only the current frame's id is tested ----
+    std::vector<int32_t> lc(lids_cur, lids_cur + cur->nfeat), lp(lids_prev, lids_prev + prev->nfeat);
+    std::vector<MapOut> rec(total);
+    std::vector<MapNewExtra> ext(total);
+    std::vector<int32_t> acc_match;
+    int32_t by_verdict[9] = {0}, hist[MCORB_MAX_CAMS] = {0};
+    double avg = 0.0;
+    na.a = L.args(base, nullptr, C);
+    for (int j = 0; j < n_matches; j++) {
+        const int q = match_query[j], t = match_train[j];
+        new_clear(rec[j], ext[j]);
+        if (lc[t] != -1) { rec[j].verdict = kMapAssigned; by_verdict[kMapAssigned]++; continue; }
+        if (dev) { rec[j] = m->h_mapout[item_of[j]]; ext[j] = m->h_mapextra[item_of[j]]; }
+        else {
+            na.a.out = &rec[j];
+            na.extra = &ext[j];
+            const MapItem it{q, t, 0};
+            if (nviews[j] <= 4) map_new_item<false>(na, it); else map_new_item<true>(na, it);
+        }
+        by_verdict[rec[j].verdict]++;
+        if (rec[j].verdict != kMapLandmark) continue;
+        lp[q] = lc[t] = next_lid + (int32_t)acc_match.size();
+        acc_match.push_back(j);
+        avg += rec[j].dist2;
+        hist[nviews_cur[j] - 1]++;
+    }
+    const int ntri = (int)acc_match.size();
+    out->n_depth = out->n_triangulated = ntri;
+    if (ntri && (size_t)next_lid + (size_t)ntri > (size_t)m->max_landmarks) {
+        set_error("lmap triangulate_new: new landmark ids beyond max_landmarks");
+        return MCORB_E_CAP;
+    }
+    if (ntri > out->cap_depth) { set_error("lmap triangulate_new: output too small"); return MCORB_E_CAP; }
+    if (ntri && !out->depth_vec) return bad("bad argument");
+
+    // ---- 6. the new landmarks into their slots, then the caller's arrays ----
+    if (dev && ntri) {
+        hipStream_t st = m->st;
+        TRY(m->h_mapput.grow((size_t)ntri, hipHostMallocDefault));
+        TRY(m->d_mapput.grow((size_t)ntri));
+        for (int k = 0; k < ntri; k++) m->h_mapput[k] = make_int2(item_of[acc_match[k]], next_lid + k);
+        HIPCHK(hipMemcpyAsync(m->d_mapput, m->h_mapput, (size_t)ntri * sizeof(int2), hipMemcpyHostToDevice, st));
+        launch_map_put(st, m->d_mapout, m->d_mapput, ntri, m->d_geom, m->d_nrays);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(st));
+    } else {
+        for (int k = 0; k < ntri; k++) {
+            double *g = &m->geom[(size_t)(next_lid + k) * 6];
+            memcpy(g, rec[acc_match[k]].X, 3 * sizeof(double));
+            memcpy(g + 3, rec[acc_match[k]].normal, 3 * sizeof(double));
+        }
+    }
+    for (int k = 0; k < ntri; k++) {
+        m->flags[next_lid + k] |= kSet;
+        m->n_rays[next_lid + k] = rec[acc_match[k]].n_rays;
+    }
+    for (size_t i = 0; i < total; i++) {
+        const MapOut &o = rec[i];
+        const bool lm = o.verdict == kMapLandmark;
+        out->verdict[i] = (uint8_t)o.verdict;
+        out->inliers[i] = lm;
+        out->new_lid[i] = -1;
+        out->dist[i] = o.dist2;
+        out->cos_parallax[i] = ext[i].cos;
+        out->iterations[i] = ext[i].solves;
+        out->cost_initial[i] = ext[i].cost_initial;
+        out->cost_final[i] = ext[i].cost_final;
+        for (int k = 0; k < 3; k++) { out->pt3d[3 * i + k] = lm ? o.X[k] : 0.0; out->normal[3 * i + k] = lm ? o.normal[k] : 0.0; }
+    }
+    for (int k = 0; k < ntri; k++) {
+        out->new_lid[acc_match[k]] = next_lid + k;
+        out->depth_vec[k] = rec[acc_match[k]].dist2;
+    }
+    out->avg_depth = avg;
+    memcpy(out->n_rays_hist, hist, sizeof(hist));
+    memcpy(out->n_by_verdict, by_verdict, sizeof(by_verdict));
+    if (cur->nfeat) memcpy(lids_cur, lc.data(), lc.size() * sizeof(int32_t));
+    if (prev->nfeat) memcpy(lids_prev, lp.data(), lp.size() * sizeof(int32_t));
+    out->next_lid = next_lid + ntri;
+    return MCORB_OK;
+}
+
+int mcorb_lmap_last_triangulate_new_timing(mcorb_lmap *m, float us[1], int *n_launched)
+{
+    TRY(check_lmap_handle(m, "lmap last_triangulate_new_timing"));
+    if (!us) { set_error("lmap last_triangulate_new_timing: bad argument"); return MCORB_E_ARG; }
+    std::lock_guard<std::mutex> lk(m->mu);
+    us[0] = m->us_map_new;
+    if (n_launched) *n_launched = m->last_map_new_launched;
+    return MCORB_OK;
+}
+
+int mcorb_host_map_refine(int n, const double *X0, const int32_t *nv1, const int32_t *nv, const double *P, const double *K,
+                          const double *centre, const float *kps, const int32_t *octave, const double *twc_cur, const double *twc_prev,
+                          const float *inv_sigma2, int nlevels, int32_t *verdict, int32_t *n_rays, int32_t *solves, float *cosp,
+                          double *vals)
+{
+    std::vector<int32_t> voff;
+    TRY(check_gate_cases(X0, nv1, nv, P, K, centre, kps, octave, twc_cur, inv_sigma2, nlevels, n, voff));
+    if (!twc_prev || !verdict || !n_rays || !solves || !cosp || !vals) { set_error("map refine: bad argument"); return MCORB_E_ARG; }
+    const MapRefineCases c{X0, nv1, nv, voff.data(), P, K, centre, kps, octave, twc_cur, twc_prev, inv_sigma2};
+    std::vector<MapOut> o((size_t)n);
+    std::vector<MapNewExtra> e((size_t)n);
+    for (int i = 0; i < n; i++) map_refine_case(c, i, o[i], e[i]);
+    refine_out(o.data(), e.data(), n, verdict, n_rays, solves, cosp, vals);
+    return MCORB_OK;
+}
+
+int mcorb_dev_map_refine_selftest(int device, int n, const double *X0, const int32_t *nv1, const int32_t *nv, const double *P,
+                                  const double *K, const double *centre, const float *kps, const int32_t *octave, const double *twc_cur,
+                                  const double *twc_prev, const float *inv_sigma2, int nlevels, int32_t *verdict, int32_t *n_rays,
+                                  int32_t *solves, float *cosp, double *vals)
+{
+    std::vector<int32_t> voff;
+    TRY(check_gate_cases(X0, nv1, nv, P, K, centre, kps, octave, twc_cur, inv_sigma2, nlevels, n, voff));
+    if (!twc_prev || !verdict || !n_rays || !solves || !cosp || !vals) { set_error("map refine: bad argument"); return MCORB_E_ARG; }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) { set_error("no usable HIP device"); return MCORB_E_NODEVICE; }
+    HIPCHK(hipSetDevice(device));
+    const size_t N = (size_t)n, V = (size_t)voff[n];
+    DevBuf<double> d_X, d_P, d_K, d_c, d_tc, d_tp;
+    DevBuf<int32_t> d_nv1, d_nv, d_voff, d_oct;
+    DevBuf<float> d_kps, d_sig;
+    DevBuf<MapOut> d_out;
+    DevBuf<MapNewExtra> d_ext;
+    TRY(d_X.alloc(N * 3)); TRY(d_P.alloc(V * 12)); TRY(d_K.alloc(V * 9)); TRY(d_c.alloc(V * 3)); TRY(d_tc.alloc(N * 3)); TRY(d_tp.alloc(N * 3));
+    TRY(d_nv1.alloc(N)); TRY(d_nv.alloc(N)); TRY(d_voff.alloc(N + 1)); TRY(d_oct.alloc(V));
+    TRY(d_kps.alloc(V * 2)); TRY(d_sig.alloc((size_t)nlevels)); TRY(d_out.alloc(N)); TRY(d_ext.alloc(N));
+    HIPCHK(hipMemcpy(d_X, X0, N * 3 * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_P, P, V * 12 * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_K, K, V * 9 * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_c, centre, V * 3 * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_tc, twc_cur, N * 3 * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_tp, twc_prev, N * 3 * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_nv1, nv1, N * sizeof(int32_t), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_nv, nv, N * sizeof(int32_t), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_voff, voff.data(), (N + 1) * sizeof(int32_t), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_oct, octave, V * sizeof(int32_t), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_kps, kps, V * 2 * sizeof(float), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_sig, inv_sigma2, (size_t)nlevels * sizeof(float), hipMemcpyHostToDevice));
+    const MapRefineCases c{d_X, d_nv1, d_nv, d_voff, d_P, d_K, d_c, d_kps, d_oct, d_tc, d_tp, d_sig};
+    launch_map_refine_cases(nullptr, c, n, d_out, d_ext);
+    HIPCHK(hipGetLastError());
+    std::vector<MapOut> o(N);
+    std::vector<MapNewExtra> e(N);
+    HIPCHK(hipMemcpy(o.data(), d_out, N * sizeof(MapOut), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(e.data(), d_ext, N * sizeof(MapNewExtra), hipMemcpyDeviceToHost));
+    refine_out(o.data(), e.data(), n, verdict, n_rays, solves, cosp, vals);
     return MCORB_OK;
 }
 

@@ -12,11 +12,16 @@
 // the launch shape cannot change it.  Two instances, as k_lf_tracks has: matches of at most 4 views in total (2 views is almost
 // every match of a non-overlapping rig) without the run-time-shaped solver, and the general one, whose 48 x 20 design lives in
 // scratch.  The solver's arrays are indexed by run-time pivots, so both keep them in scratch (DESIGN.md section 9d has the figures).
+//
+// k_map_refine_new (mcorb_lmap_triangulate_new): one match of FrontEnd::TriangulateNewLandmarks (:6465-6700) per lane, the same block
+// record, tables and two instances; after the DLT a lane runs its own 3-unknown Levenberg-Marquardt (mcorb_mapping_new.h) with X, H,
+// g, the trial, lambda and the costs in registers, and every pass walks the lane's views again from MapViews.  Lanes of a wave leave
+// the loop after different numbers of solves and the wave runs until its slowest lane ends; 50 solves bound it (section 9h).
 #include <hip/hip_runtime.h>
 
 #include "mcorb_common.h"
 #include "mcorb_kernels.h"
-#include "mcorb_mapping.h"
+#include "mcorb_mapping_new.h"
 
 namespace mcorb {
 
@@ -32,6 +37,20 @@ void launch_map_triangulate(hipStream_t st, const MapArgs &a, int nblocks_small,
 {
     if (nblocks_small > 0) hipLaunchKernelGGL(k_map_triangulate<false>, dim3(nblocks_small), dim3(kMapBlock), 0, st, a, 0);
     if (nblocks_any > 0) hipLaunchKernelGGL(k_map_triangulate<true>, dim3(nblocks_any), dim3(kMapBlock), 0, st, a, nblocks_small);
+}
+
+template <bool kAnyViews>
+__global__ __launch_bounds__(kMapBlock) void k_map_refine_new(MapNewArgs n, int block0)
+{
+    const MapBlock b = n.a.blocks[block0 + blockIdx.x];
+    if ((int)threadIdx.x >= b.count) return;
+    map_new_item<kAnyViews>(n, n.a.items[b.first + threadIdx.x]);
+}
+
+void launch_map_refine_new(hipStream_t st, const MapNewArgs &n, int nblocks_small, int nblocks_any)
+{
+    if (nblocks_small > 0) hipLaunchKernelGGL(k_map_refine_new<false>, dim3(nblocks_small), dim3(kMapBlock), 0, st, n, 0);
+    if (nblocks_any > 0) hipLaunchKernelGGL(k_map_refine_new<true>, dim3(nblocks_any), dim3(kMapBlock), 0, st, n, nblocks_small);
 }
 
 // the pose (12 doubles) is a kernel argument: scalar registers
@@ -90,6 +109,25 @@ void launch_map_gates(hipStream_t st, const MapGateCases &c, int n, MapOut *out)
 {
     if (n < 1) return;
     hipLaunchKernelGGL(k_map_gates, dim3((n + kMapBlock - 1) / kMapBlock), dim3(kMapBlock), 0, st, c, n, out);
+}
+
+// mcorb_dev_map_refine_selftest: case i has nv[i] views (the first nv1[i] the previous keyframe's) starting at view voff[i]
+__global__ __launch_bounds__(kMapBlock) void k_map_refine_cases(MapRefineCases c, int n, MapOut *__restrict__ out,
+                                                                MapNewExtra *__restrict__ extra)
+{
+    const int i = blockIdx.x * kMapBlock + threadIdx.x;
+    if (i >= n) return;
+    MapOut o;
+    MapNewExtra e;
+    map_refine_case(c, i, o, e);
+    out[i] = o;
+    extra[i] = e;
+}
+
+void launch_map_refine_cases(hipStream_t st, const MapRefineCases &c, int n, MapOut *out, MapNewExtra *extra)
+{
+    if (n < 1) return;
+    hipLaunchKernelGGL(k_map_refine_cases, dim3((n + kMapBlock - 1) / kMapBlock), dim3(kMapBlock), 0, st, c, n, out, extra);
 }
 
 }  // namespace mcorb
