@@ -899,9 +899,9 @@ int mcorb_lmap_last_landmark_timing(mcorb_lmap *m, float us[2]);
 /* camera from the predicted pose, and Tracking::queryCurrentFrame /           */
 /* querryEachFrame (:319-449): the 10 nearest keypoints by image position, the */
 /* 100 px gate, the best Hamming distance below 20 and the serial              */
-/* de-duplication per keypoint.  Tracking::queryPoints, the JSON map and       */
-/* refinePose's RANSAC (OpenGV) stay with the caller; the pose refinement      */
-/* behind it is mcorb_lmap_refine_pose, below.                                 */
+/* de-duplication per keypoint.  Tracking::queryPoints and the JSON map stay   */
+/* with the caller; refinePose's RANSAC is mcorb_lmap_ransac_pose and the pose */
+/* refinement behind it mcorb_lmap_refine_pose, both below.                    */
 /* ------------------------------------------------------------------------- */
 #define MCORB_TRACK_KNN 10      /* the neighbours a projection is compared with (Tracking.cpp:335-345) */
 #define MCORB_TRACK_TILE 1024   /* keypoints per LDS tile of k_track_match; a camera may have any number */
@@ -1048,8 +1048,8 @@ int mcorb_lmap_track_rig_frames(mcorb_lmap *m, const mcorb_track_view *views, mc
 /* outlier rule of FrontEnd::OptimizePose (MCSlam/src/FrontEnd.cpp:4272-4409)  */
 /* with the RigResectioningFactor (MCSlam/include/MCSlam/                      */
 /* GtsamFactorHelpers.h:48-100), around a stated Levenberg-Marquardt: gtsam's  */
-/* optimizer is not vendored.  The GP3P RANSAC in front of it (OpenGV) stays   */
-/* with the caller: this serves a frame that has a predicted pose.             */
+/* optimizer is not vendored.  This serves a frame that has a predicted pose;  */
+/* the RANSAC in front of it is mcorb_lmap_ransac_pose, further below.         */
 /* ------------------------------------------------------------------------- */
 #define MCORB_POSE_LANES 256      /* the lanes whose partial sums fix the order of every addition (below) */
 #define MCORB_POSE_NO_OBS 0       /* no observation: the initial pose */
@@ -1119,6 +1119,89 @@ void mcorb_pose_of_view(const mcorb_track_view *view, double R[9], double t[3]);
 /* test hook, host: residual r (n x 2), Jacobian J (n x 2 x 6) and Huber weight w (n) of n observations at the pose (R, t) */
 int mcorb_pose_eval(int ncams, const mcorb_track_cam *cams, int n, const int32_t *cam, const float *uv, const double *pts, const double *R,
                     const double *t, double *r, double *J, double *w);
+
+/* ------------------------------------------------------------------------- */
+/* The absolute rig pose by RANSAC in front of the refinement: the consensus   */
+/* step every matcher of the reference ends in -- OpenGV's sac::Ransac<        */
+/* AbsolutePoseSacProblem>(GP3P) as FrontEnd::absolutePoseFromGP3P (MCSlam/src/ */
+/* FrontEnd.cpp:4660-4798), FrontEnd::refinePose (:1691-1786), LoopCloser::     */
+/* checkAbsolutePose and Relocalization::checkAbsolutePose call it.  OpenGV is */
+/* not vendored: its reprojection distance is recalled, and three things are   */
+/* stated instead of OpenGV's -- the draws, the minimal solver and the absence */
+/* of the adaptive stop.                                */
+/* ------------------------------------------------------------------------- */
+#define MCORB_SAC_MAX_ITERATIONS 1024
+#define MCORB_SAC_OK 0            /* a hypothesis won */
+#define MCORB_SAC_NO_OBS 1        /* an empty consensus set: the identity, nothing ran */
+#define MCORB_SAC_NO_MODEL 2      /* no hypothesis had a model: the identity, every flag 0 */
+/* threshold: on 1 - cos(angle between the bearing and the point's direction); the reference's is mcorb_sac_threshold(K[0](0, 2)).
+ * max_iterations: the hypotheses, 1 .. MCORB_SAC_MAX_ITERATIONS (the reference sets 100), all of them examined.  seed: of the draws */
+typedef struct mcorb_sac_params {
+    double threshold;
+    uint64_t seed;
+    int32_t max_iterations, reserved;
+} mcorb_sac_params;
+/* (R, t): the final w_T_b, R row-major; status: MCORB_SAC_*; used: 0 = the RANSAC's model, 1 = the refinement's result; n_inliers:
+ * the inlier matches of the answer; n_matches: the matches.  The RANSAC's own: (sac_R, sac_t), sac_n_inliers, best_hypothesis (-1:
+ * none), sample (the winner's four observations, the first three the solver's, the fourth the disambiguating one), n_models (the
+ * hypotheses that had a model), n_consensus (the size of the consensus set).  refine: with refine_params the mcorb_pose_result of
+ * the refinement from (sac_R, sac_t), zero otherwise */
+typedef struct mcorb_sac_result {
+    double R[9], t[3];
+    double sac_R[9], sac_t[3];
+    int32_t status, used, n_inliers, n_matches;
+    int32_t sac_n_inliers, best_hypothesis, sample[4], n_models, n_consensus;
+    mcorb_pose_result refine;
+} mcorb_sac_result;
+/* The pose of a rig from n observations without a predicted pose.  The observations, the rig and (R, t) = w_T_b are those of
+ * mcorb_lmap_refine_pose.  match (may be NULL: every observation is its own match): non-decreasing match indices, so that a
+ * match's observations are contiguous.  The consensus set is the first observation of each match (the reference's break at
+ * :4704); the refinement uses all.  All arithmetic is fp64, one IEEE operation per operator in the order written
+ * (csrc/mcorb_sac.h), + - * /, comparisons and sqrt:
+ * - the bearing: y = (v - v0) / fy, x = ((u - u0) - s y) / fx, f = (x, y, 1) / sqrt((x x + y y) + 1).
+ * - the score (OpenGV's reprojection distance, recalled): q the point in the camera's frame as the refinement computes it,
+ *   score = 1 - ((f.x q.x + f.y q.y) + f.z q.z) / sqrt((q.x q.x + q.y q.y) + q.z q.z); an inlier iff score < threshold (a NaN
+ *   is none).
+ * - the draws (stated): draw j of hypothesis h is the splitmix64 finaliser of seed + 0x9E3779B97F4A7C15 (1 + 16 h + j).  Draw 0
+ *   mod S picks a consensus observation, whose camera c is the hypothesis's; draws 1 .. 15 mod S_c pick three more from camera
+ *   c's consensus observations in input order, a draw equal to an earlier member being dropped.  S_c < 4 or no fourth member
+ *   after 16 draws: no model.
+ * - the solver (stated): a central P3P in camera c on the first three members -- Grunert's quartic solved after Ferrari, the
+ *   camera-frame points aligned to the world's by orthonormal triads, w_T_b = w_T_c (b_T_c)^-1 -- the fourth member picking the
+ *   solution with the smallest score (a tie: the lowest root index; a NaN never).  Not OpenGV's generalized GP3P, which samples
+ *   across cameras.
+ * - the consensus: a hypothesis's count is the number of inliers of its model over the consensus set; the largest count wins, a
+ *   tie goes to the lowest h.  All max_iterations hypotheses are examined (stated: OpenGV's adaptive stop returns the best of a
+ *   prefix).
+ * With refine_params (absolutePoseFromGP3P when initialized, :4771-4795) mcorb_lmap_refine_pose's refinement runs over all n
+ * observations from the RANSAC's pose -- bit for bit that call on the same observations from (sac_R, sac_t) -- a match being an
+ * inlier of it iff all its observations are, and the rule of :4786 follows: if the RANSAC's inlier matches outnumber the
+ * refinement's, the RANSAC's pose and flags are the answer (used = 0), otherwise the refinement's (used = 1).  With status
+ * MCORB_SAC_NO_OBS or MCORB_SAC_NO_MODEL used is 0.
+ * A device store runs k_sac_hypotheses, k_sac_score and k_sac_pick (and k_pose_refine behind them) in one submission with one
+ * wait; a host-only store runs the same header serially: the results are equal bit for bit.  inlier (may be NULL): one flag per
+ * match.  Before anything runs, the store unchanged: everything mcorb_lmap_refine_pose refuses (the octaves are checked against
+ * refine_params' levels, or MCORB_MAX_LEVELS without), MCORB_E_ARG for a threshold that is not finite and positive,
+ * max_iterations outside 1 .. MCORB_SAC_MAX_ITERATIONS, a match array that decreases or is negative; MCORB_E_STATE while a
+ * tracking call is pending. */
+int mcorb_lmap_ransac_pose(mcorb_lmap *m, int n, const int32_t *cam, const float *uv, const int32_t *octave, const int32_t *match,
+                           const int32_t *lids, const double *pts, int ncams, const mcorb_track_cam *cams,
+                           const mcorb_sac_params *params, const mcorb_pose_params *refine_params, mcorb_sac_result *res,
+                           uint8_t *inlier);
+/* a device store's last k_sac_hypotheses (us[0]), k_sac_score (us[1]) and k_sac_pick (us[2]) launch, microseconds between HIP
+ * events, and its hypotheses; a call with an empty consensus set launches nothing and leaves them */
+int mcorb_lmap_last_ransac_timing(mcorb_lmap *m, float us[3], int *n_hyp);
+/* test hook: the counts of all hypotheses of the last call that ran any, and whether each had a model (a hypothesis without one
+ * has count 0); a device store copies them down from where k_sac_score left them.  MCORB_E_CAP (with n_hyp set) when cap < n_hyp */
+int mcorb_lmap_last_ransac_counts(mcorb_lmap *m, int32_t *count, int32_t *valid, int cap, int *n_hyp);
+/* the reference's threshold: 1 - cos(atan(sqrt(2) * 0.5 / K00_02)) */
+double mcorb_sac_threshold(double K00_02);
+/* test hook, host: the rig poses (at most 4; R as 9, t as 3 doubles each) of the minimal solver on three observations of camera
+ * cam -- keypoints uv (3 x 2), points pts (3 x 3) -> the count */
+int mcorb_sac_solve(const mcorb_track_cam *cam, const float *uv, const double *pts, double *R, double *t);
+/* test hook, host: the scores of n observations at the pose (R, t); a NaN is the default quiet NaN */
+int mcorb_sac_eval(int ncams, const mcorb_track_cam *cams, int n, const int32_t *cam, const float *uv, const double *pts, const double *R,
+                   const double *t, double *score);
 
 /* ------------------------------------------------------------------------- */
 /* Host stages exposed for the CPU test-suite (no device needed)              */

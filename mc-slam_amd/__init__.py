@@ -1543,6 +1543,43 @@ class LocalMap:
         _lib.check(self.L.mcorb_lmap_last_pose_timing(self.h, us))
         return us[0]
 
+    # the absolute rig pose by RANSAC in front of the refinement (mcorb_lmap_ransac_pose)
+    def ransac_pose(self, cams, cam, uv, octave, threshold, lids=None, pts=None, match=None, max_iterations=100, seed=0, refine=None):
+        """the pose w_T_b of a rig from observations without a predicted pose: the consensus step of
+        FrontEnd::absolutePoseFromGP3P.  The observations and cams are refine_pose()'s; match: non-decreasing match indices (None:
+        every observation its own match) -- the consensus set is the first observation of each match; threshold: on 1 - cos of
+        the reprojection angle, sac_threshold(K[0](0, 2)) in the reference; max_iterations hypotheses, all examined; seed: of the
+        draws.  refine: pose_params(...) -- the refinement over all observations from the RANSAC's pose and the reference's rule
+        between the two.  -> SacResult.  A device store runs k_sac_hypotheses, k_sac_score, k_sac_pick (and k_pose_refine) in one
+        submission; a host-only store the same arithmetic serially, with the same bits"""
+        cam = np.ascontiguousarray(cam, np.int32).reshape(-1)
+        n = len(cam)
+        uv = np.ascontiguousarray(uv, np.float32).reshape(n, 2)
+        octave = np.ascontiguousarray(octave, np.int32).reshape(n)
+        l, lp = self._opt(lids, np.int32, (n,))
+        p, pp = self._opt(pts, np.float64, (n, 3))
+        mt, mp = self._opt(match, np.int32, (n,))
+        ncams, ca = _pose_cams(cams)
+        par = _lib.SacParams()
+        par.threshold, par.seed, par.max_iterations = float(threshold), int(seed) & 0xFFFFFFFFFFFFFFFF, int(max_iterations)
+        res, flags = _lib.SacResultC(), np.zeros(max(n, 1), np.uint8)
+        _lib.check(self.L.mcorb_lmap_ransac_pose(self.h, n, cam.ctypes.data, uv.ctypes.data, octave.ctypes.data, mp, lp, pp, ncams, ca,
+                                                 C.byref(par), None if refine is None else C.byref(refine), C.byref(res),
+                                                 flags.ctypes.data))
+        return SacResult(res, flags[:res.n_matches], refine is not None)
+
+    def last_ransac_timing(self):
+        """((us of k_sac_hypotheses, k_sac_score, k_sac_pick), hypotheses) of the last ransac_pose() launch; a device store"""
+        us, nh = (C.c_float * 3)(), C.c_int(0)
+        _lib.check(self.L.mcorb_lmap_last_ransac_timing(self.h, us, C.byref(nh)))
+        return tuple(us), nh.value
+
+    def last_ransac_counts(self):
+        """test hook: (counts, has a model) of all hypotheses of the last ransac_pose() that ran any"""
+        count, valid, nh = np.zeros(1024, np.int32), np.zeros(1024, np.int32), C.c_int(0)
+        _lib.check(self.L.mcorb_lmap_last_ransac_counts(self.h, count.ctypes.data, valid.ctypes.data, 1024, C.byref(nh)))
+        return count[:nh.value], valid[:nh.value].astype(bool)
+
     def set_track_refine(self, inv_sigma2=None, max_iterations=25):
         """inv_sigma2 given: from now on every tracking call on the store -- track, track_rig_frame, the submit / wait pair,
         track_rig_frames -- also refines, per frame and in the same submission, the pose of the view's rig from the frame's
@@ -1574,6 +1611,60 @@ class PoseResult:
         self.cost_initial, self.cost_final = res.cost_initial, res.cost_final
         self.n_inliers, self.n_obs = res.n_inliers, res.n_obs
         self.inliers = flags.astype(bool)
+
+
+class SacResult:
+    """what LocalMap.ransac_pose returns: R (3 x 3), t = the final w_T_b; status (SAC_OK, SAC_NO_OBS, SAC_NO_MODEL); used (0: the
+    RANSAC's model, 1: the refinement's result); n_inliers and inliers, one bool per match, of the answer; n_matches.  The
+    RANSAC's own: sac_R, sac_t, sac_n_inliers, best_hypothesis (-1: none), sample (the winner's four observations), n_models,
+    n_consensus.  refine: the refinement's PoseResult (inliers per observation are not kept), None without it"""
+
+    def __init__(self, res, flags, refined):
+        self.R = np.array(res.R[:], np.float64).reshape(3, 3)
+        self.t = np.array(res.t[:], np.float64)
+        self.sac_R = np.array(res.sac_R[:], np.float64).reshape(3, 3)
+        self.sac_t = np.array(res.sac_t[:], np.float64)
+        self.status, self.used, self.n_inliers, self.n_matches = res.status, res.used, res.n_inliers, res.n_matches
+        self.sac_n_inliers, self.best_hypothesis, self.sample = res.sac_n_inliers, res.best_hypothesis, tuple(res.sample[:])
+        self.n_models, self.n_consensus = res.n_models, res.n_consensus
+        self.inliers = flags.astype(bool)
+        self.refine = PoseResult(res.refine, np.zeros(0, np.uint8)) if refined else None
+
+
+SAC_OK, SAC_NO_OBS, SAC_NO_MODEL = 0, 1, 2
+
+
+def sac_threshold(K00_02):
+    """the reference's RANSAC threshold: 1 - cos(atan(sqrt(2) * 0.5 / K[0](0, 2)))"""
+    return _lib.load().mcorb_sac_threshold(float(K00_02))
+
+
+def sac_solve(cams, cam, uv, pts):
+    """test hook (host): the rig poses (at most 4) of the minimal solver on three observations of camera cam -- keypoints uv
+    (3 x 2), points pts (3 x 3) -> [(R 3 x 3, t)]"""
+    uv = np.ascontiguousarray(uv, np.float32).reshape(3, 2)
+    pts = np.ascontiguousarray(pts, np.float64).reshape(3, 3)
+    ncams, ca = _pose_cams(cams)
+    assert 0 <= cam < ncams
+    R, t = np.zeros((4, 9)), np.zeros((4, 3))
+    k = _lib.load().mcorb_sac_solve(ca + int(cam) * C.sizeof(_lib.TrackCam), uv.ctypes.data, pts.ctypes.data, R.ctypes.data, t.ctypes.data)
+    _lib.check(min(k, 0))
+    return [(R[i].reshape(3, 3).copy(), t[i].copy()) for i in range(k)]
+
+
+def sac_eval(cams, R, t, cam, uv, pts):
+    """test hook (host): the scores (n) of the observations at the pose (R, t)"""
+    cam = np.ascontiguousarray(cam, np.int32).reshape(-1)
+    n = len(cam)
+    uv = np.ascontiguousarray(uv, np.float32).reshape(n, 2)
+    pts = np.ascontiguousarray(pts, np.float64).reshape(n, 3)
+    R = np.ascontiguousarray(R, np.float64).reshape(9)
+    t = np.ascontiguousarray(t, np.float64).reshape(3)
+    score = np.zeros(max(n, 1))
+    ncams, ca = _pose_cams(cams)
+    _lib.check(_lib.load().mcorb_sac_eval(ncams, ca, n, cam.ctypes.data, uv.ctypes.data, pts.ctypes.data, R.ctypes.data, t.ctypes.data,
+                                          score.ctypes.data))
+    return score[:n]
 
 
 def pose_params(inv_sigma2, max_iterations=25):

@@ -110,6 +110,17 @@ class PoseResultC(C.Structure):
                 ("reserved", C.c_int32)]
 
 
+class SacParams(C.Structure):
+    _fields_ = [("threshold", C.c_double), ("seed", C.c_uint64), ("max_iterations", C.c_int32), ("reserved", C.c_int32)]
+
+
+class SacResultC(C.Structure):
+    _fields_ = [("R", C.c_double * 9), ("t", C.c_double * 3), ("sac_R", C.c_double * 9), ("sac_t", C.c_double * 3),
+                ("status", C.c_int32), ("used", C.c_int32), ("n_inliers", C.c_int32), ("n_matches", C.c_int32),
+                ("sac_n_inliers", C.c_int32), ("best_hypothesis", C.c_int32), ("sample", C.c_int32 * 4), ("n_models", C.c_int32),
+                ("n_consensus", C.c_int32), ("refine", PoseResultC)]
+
+
 class McorbError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("mcorb error %d: %s" % (code, msg))
@@ -283,6 +294,13 @@ SIGNATURES = {
     "mcorb_lmap_last_track_pose": (_i, [_vp, _i, C.POINTER(PoseResultC), _vp, _i]),
     "mcorb_pose_of_view": (None, [C.POINTER(TrackView), _vp, _vp]),
     "mcorb_pose_eval": (_i, [_i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mcorb_lmap_ransac_pose": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, C.POINTER(SacParams), C.POINTER(PoseParams),
+                                    C.POINTER(SacResultC), _vp]),
+    "mcorb_lmap_last_ransac_timing": (_i, [_vp, C.POINTER(_f), C.POINTER(_i)]),
+    "mcorb_lmap_last_ransac_counts": (_i, [_vp, _vp, _vp, _i, C.POINTER(_i)]),
+    "mcorb_sac_threshold": (C.c_double, [C.c_double]),
+    "mcorb_sac_solve": (_i, [_vp, _vp, _vp, _vp, _vp]),
+    "mcorb_sac_eval": (_i, [_i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mcorb_host_geometry": (_i, [C.POINTER(Params), _i, _i, _vp]),
     "mcorb_synth_rig_frame": (_i, [C.c_uint32, _i, _i, _i, _i, _vp, _i]),
 }

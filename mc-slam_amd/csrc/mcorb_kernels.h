@@ -1,6 +1,6 @@
 // mcorb_kernels.h -- launch wrappers of the gfx950 kernels (mcorb_kernels.hip, mcorb_select_gpu.hip, mcorb_handoff_gpu.hip,
 // mcorb_bow_gpu.hip, mcorb_lf_gpu.hip, mcorb_kfdb_gpu.hip, mcorb_lmap_gpu.hip, mcorb_mapping_gpu.hip, mcorb_landmark_gpu.hip,
-// mcorb_track_gpu.hip, mcorb_pose_gpu.hip).
+// mcorb_track_gpu.hip, mcorb_pose_gpu.hip, mcorb_sac_gpu.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <vector>
@@ -8,6 +8,7 @@
 #include "mcorb_common.h"
 #include "mcorb_mapping_new.h"
 #include "mcorb_pose.h"
+#include "mcorb_sac.h"
 #include "mcorb_signal.h"
 #include "mcorb_track.h"
 #include "mcorb_undistort.h"
@@ -239,5 +240,32 @@ void launch_track_dedup_batch(hipStream_t st, const TrBatchItem *items, int nf, 
 void launch_pose_refine(hipStream_t st, const PoseJob *jobs, int njobs, PoseObs *obs, int32_t *lids, const double *pts, const double *geom,
                         uint8_t *alive, const uint8_t *win, const TrBest *best, const int *cand, const float2 *kp_xy,
                         mcorb_pose_result *out, uint8_t *flags);
+
+// the RANSAC in front of it (mcorb_sac_gpu.hip), three launches.  job, obs, lids | pts, cons / cam_first / cam_cons (the
+// consensus observations in input order, and camera by camera) and is_first (per observation: the first of its match) are device
+// memory.  k_sac_hypotheses: one lane per hypothesis, models[H].  k_sac_score: a workgroup per (tile of kSacTile consensus
+// observations, block of kSacHypBlock hypotheses), integer adds into count[H], which the caller has zeroed on the stream.
+// k_sac_pick: the winner, the flags of all n observations (host-mapped), the record out (host-mapped) and, with pose_job, the
+// winner's pose into pose_job->init for the launch_pose_refine behind it
+#ifndef MCORB_SAC_HYP_BLOCK
+#define MCORB_SAC_HYP_BLOCK 8   // measured against 32 and 128 (make EXTRA=-DMCORB_SAC_HYP_BLOCK=..)
+#endif
+constexpr int kSacTile = 256, kSacHypBlock = MCORB_SAC_HYP_BLOCK;
+struct SacArgs {
+    const SacJob *job;
+    const PoseObs *obs;
+    const int32_t *lids;
+    const double *pts, *geom;
+    const int32_t *cons, *cam_first, *cam_cons;
+    const uint8_t *is_first;
+    SacModel *models;
+    int32_t *count;
+    SacOut *out;
+    uint8_t *flags;
+    PoseJob *pose_job;
+};
+void launch_sac_hypotheses(hipStream_t st, const SacArgs &a, int H);
+void launch_sac_score(hipStream_t st, const SacArgs &a, int S, int H);
+void launch_sac_pick(hipStream_t st, const SacArgs &a, int n);
 
 }  // namespace mcorb

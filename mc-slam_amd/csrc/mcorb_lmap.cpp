@@ -154,6 +154,10 @@ int mcorb_lmap_create(mcorb_vocab *v, int device, int max_landmarks, int max_can
         TRY(m->ev13.create(hipEventDefault));
         TRY(m->ev14.create(hipEventDefault));
         TRY(m->ev15.create(hipEventDefault));
+        TRY(m->ev16.create(hipEventDefault));
+        TRY(m->ev17.create(hipEventDefault));
+        TRY(m->ev18.create(hipEventDefault));
+        TRY(m->ev19.create(hipEventDefault));
         TRY(m->best2.create());
         TRY(m->d_geom.alloc(N * 6));
         TRY(m->d_desc.alloc(N * 32));

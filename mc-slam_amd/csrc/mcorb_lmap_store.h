@@ -10,6 +10,7 @@
 #include "mcorb_kfdb_store.h"
 #include "mcorb_mapping_new.h"
 #include "mcorb_pose.h"
+#include "mcorb_sac.h"
 #include "mcorb_track.h"
 
 namespace mcorb {
@@ -26,6 +27,19 @@ struct PoseBufs {
     DevBuf<uint8_t> d_alive;
     HostBuf<mcorb_pose_result> h_out;
     HostBuf<uint8_t> h_flags;
+};
+// the buffers of a mcorb_lmap_ransac_pose submission (mcorb_sac.cpp), grow-only: the packed input (the PoseJob of the
+// refinement behind it, the SacJob, the observations, their ids or points, the consensus lists and the first-of-match bytes;
+// one block, one copy), the models and counts of the hypotheses, and what the host reads: the pick's record and the flags per
+// observation, host-mapped.  The refinement's own buffers are `pose`
+struct SacBufs {
+    HostBuf<uint8_t> h_in;
+    DevBuf<uint8_t> d_in;
+    DevBuf<SacModel> d_models;
+    DevBuf<int32_t> d_count;
+    HostBuf<SacOut> h_out;
+    HostBuf<uint8_t> h_flags;
+    PoseBufs pose;
 };
 }  // namespace mcorb
 
@@ -148,6 +162,12 @@ struct mcorb_lmap {
     bool track_refine = false;
     mcorb_pose_params track_refine_params = {};
     int track_pose_nf = 0;
+    // the RANSAC in front of the refinement (mcorb_sac.cpp): ev16 .. ev19 around k_sac_hypotheses, k_sac_score and k_sac_pick
+    mcorb::SacBufs sac;
+    mcorb::Event ev16, ev17, ev18, ev19;
+    float us_sac[3] = {0.f, 0.f, 0.f};
+    int sac_last_hyp = 0;                      // the hypotheses of the last call that ran any (either kind of store)
+    std::vector<int32_t> sac_host_count, sac_host_valid;   // a host-only store's last counts, for mcorb_lmap_last_ransac_counts
 #ifdef MCORB_TRACK_PROF
     float us_track_phase[5] = {};   // the last call's host phases: candidate walk, submission, wait, de-duplication, output
 #endif
@@ -164,6 +184,10 @@ void pose_track_host(mcorb_lmap *m, const mcorb_track_view &view, const int *can
                      const uint8_t *const *kp_base, size_t kp_stride, mcorb_pose_result &res, uint8_t *flags);
 int pose_track_submit(mcorb_lmap *m, const mcorb_track_view *views, int nf, const size_t *first, const TrFrame *frames, const size_t *kp0,
                       const float2 *kp_xy, const int *d_cand);
+// shared with mcorb_sac.cpp: a refinement problem's job, its serial run, and the checks of its parameters
+void pose_job_init(PoseJob &job, const mcorb_pose_params &p, int ncams, const mcorb_track_cam *cams, const PoseState &init);
+void pose_run_host(const PoseJob &job, const PoseObs *obs, const double *pts, int n, uint8_t *alive, mcorb_pose_result &res);
+int pose_check_params(const mcorb_pose_params *p);
 }  // namespace mcorb
 
 // a new stamp value; the stamps start over before the counter wraps

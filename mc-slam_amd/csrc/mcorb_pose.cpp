@@ -4,7 +4,7 @@
 // (mcorb_track.cpp calls pose_track_submit / pose_track_host), whose kernel builds the observations from the frame's matches on
 // the device.  A device store runs a problem in one launch of k_pose_refine (mcorb_pose_gpu.hip), the result in host-mapped
 // memory: one synchronisation, no copy down.  A host-only store runs the header serially, lane by lane in the order the
-// workgroup adds, so the two agree bit for bit.  Not restated: gtsam's optimizer and the GP3P RANSAC (OpenGV) in front of it.
+// workgroup adds, so the two agree bit for bit.  Not restated: gtsam's optimizer.  The RANSAC in front of it is mcorb_sac.cpp.
 #include <math.h>
 #include <string.h>
 
@@ -53,6 +53,8 @@ struct HostPass {
 }  // namespace
 
 namespace mcorb {
+
+int pose_check_params(const mcorb_pose_params *p) { return check_params(p); }
 
 void pose_job_init(PoseJob &job, const mcorb_pose_params &p, int ncams, const mcorb_track_cam *cams, const PoseState &init)
 {
