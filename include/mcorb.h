@@ -1131,15 +1131,18 @@ int mcorb_pose_eval(int ncams, const mcorb_track_cam *cams, int n, const int32_t
 /* of the adaptive stop.                                */
 /* ------------------------------------------------------------------------- */
 #define MCORB_SAC_MAX_ITERATIONS 1024
+#define MCORB_SAC_SOLVER_CENTRAL 0 /* all four samples from one camera, a central P3P there: what a zero-filled struct selects */
+#define MCORB_SAC_SOLVER_RIG 1     /* the samples from any cameras, a generalized solver on the rig's rays */
 #define MCORB_SAC_OK 0            /* a hypothesis won */
 #define MCORB_SAC_NO_OBS 1        /* an empty consensus set: the identity, nothing ran */
 #define MCORB_SAC_NO_MODEL 2      /* no hypothesis had a model: the identity, every flag 0 */
 /* threshold: on 1 - cos(angle between the bearing and the point's direction); the reference's is mcorb_sac_threshold(K[0](0, 2)).
- * max_iterations: the hypotheses, 1 .. MCORB_SAC_MAX_ITERATIONS (the reference sets 100), all of them examined.  seed: of the draws */
+ * max_iterations: the hypotheses, 1 .. MCORB_SAC_MAX_ITERATIONS (the reference sets 100), all of them examined.  seed: of the
+ * draws.  solver: MCORB_SAC_SOLVER_* (the field was `reserved` and zero: the struct's size and layout are what they were) */
 typedef struct mcorb_sac_params {
     double threshold;
     uint64_t seed;
-    int32_t max_iterations, reserved;
+    int32_t max_iterations, solver;
 } mcorb_sac_params;
 /* (R, t): the final w_T_b, R row-major; status: MCORB_SAC_*; used: 0 = the RANSAC's model, 1 = the refinement's result; n_inliers:
  * the inlier matches of the answer; n_matches: the matches.  The RANSAC's own: (sac_R, sac_t), sac_n_inliers, best_hypothesis (-1:
@@ -1170,6 +1173,14 @@ typedef struct mcorb_sac_result {
  *   camera-frame points aligned to the world's by orthonormal triads, w_T_b = w_T_c (b_T_c)^-1 -- the fourth member picking the
  *   solution with the smallest score (a tie: the lowest root index; a NaN never).  Not OpenGV's generalized GP3P, which samples
  *   across cameras.
+ * - with solver MCORB_SAC_SOLVER_RIG (stated as well) the sample and the solver are the rig's: all 16 draws mod S pick from the
+ *   whole consensus set in input order, a draw equal to an earlier member being dropped, fewer than four members after them: no
+ *   model -- so a camera needs no four observations of its own.  Observation i is the body-frame ray c_i + l d_i (c_i the
+ *   camera's centre, d_i = R_i f_i); Grunert's quartic on (d_i, P_i) gives at most four starts (l_1, l_2, l_3), each takes 20
+ *   Newton steps on |B_i - B_j|^2 = |P_i - P_j|^2, B_i = c_i + l_i d_i (the 3 x 3 solve by cofactors), and the triads of (B_i)
+ *   and (P_i) give w_T_b directly; a pose is kept iff its three points score below 1e-12 in their own cameras, and the fourth
+ *   member, scored in its own camera, picks as above.  At most 4 of the problem's up to 8 solutions are found, those that
+ *   continue the central ones; this is not OpenGV's GP3P either, and it is not pinned against it.
  * - the consensus: a hypothesis's count is the number of inliers of its model over the consensus set; the largest count wins, a
  *   tie goes to the lowest h.  All max_iterations hypotheses are examined (stated: OpenGV's adaptive stop returns the best of a
  *   prefix).
@@ -1182,13 +1193,14 @@ typedef struct mcorb_sac_result {
  * wait; a host-only store runs the same header serially: the results are equal bit for bit.  inlier (may be NULL): one flag per
  * match.  Before anything runs, the store unchanged: everything mcorb_lmap_refine_pose refuses (the octaves are checked against
  * refine_params' levels, or MCORB_MAX_LEVELS without), MCORB_E_ARG for a threshold that is not finite and positive,
- * max_iterations outside 1 .. MCORB_SAC_MAX_ITERATIONS, a match array that decreases or is negative; MCORB_E_STATE while a
- * tracking call is pending. */
+ * max_iterations outside 1 .. MCORB_SAC_MAX_ITERATIONS, a solver that is not one of MCORB_SAC_SOLVER_*, a match array that
+ * decreases or is negative; MCORB_E_STATE while a tracking call is pending.  With MCORB_SAC_SOLVER_RIG a device store runs
+ * k_sac_hypotheses_rig in k_sac_hypotheses' place. */
 int mcorb_lmap_ransac_pose(mcorb_lmap *m, int n, const int32_t *cam, const float *uv, const int32_t *octave, const int32_t *match,
                            const int32_t *lids, const double *pts, int ncams, const mcorb_track_cam *cams,
                            const mcorb_sac_params *params, const mcorb_pose_params *refine_params, mcorb_sac_result *res,
                            uint8_t *inlier);
-/* a device store's last k_sac_hypotheses (us[0]), k_sac_score (us[1]) and k_sac_pick (us[2]) launch, microseconds between HIP
+/* a device store's last k_sac_hypotheses or k_sac_hypotheses_rig (us[0]), k_sac_score (us[1]) and k_sac_pick (us[2]) launch, microseconds between HIP
  * events, and its hypotheses; a call with an empty consensus set launches nothing and leaves them */
 int mcorb_lmap_last_ransac_timing(mcorb_lmap *m, float us[3], int *n_hyp);
 /* test hook: the counts of all hypotheses of the last call that ran any, and whether each had a model (a hypothesis without one
@@ -1199,6 +1211,8 @@ double mcorb_sac_threshold(double K00_02);
 /* test hook, host: the rig poses (at most 4; R as 9, t as 3 doubles each) of the minimal solver on three observations of camera
  * cam -- keypoints uv (3 x 2), points pts (3 x 3) -> the count */
 int mcorb_sac_solve(const mcorb_track_cam *cam, const float *uv, const double *pts, double *R, double *t);
+/* test hook, host: the same of the rig solver on three observations of cameras cam[3] of the rig cams[ncams] */
+int mcorb_sac_solve_rig(int ncams, const mcorb_track_cam *cams, const int32_t *cam, const float *uv, const double *pts, double *R, double *t);
 /* test hook, host: the scores of n observations at the pose (R, t); a NaN is the default quiet NaN */
 int mcorb_sac_eval(int ncams, const mcorb_track_cam *cams, int n, const int32_t *cam, const float *uv, const double *pts, const double *R,
                    const double *t, double *score);

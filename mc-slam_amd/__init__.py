@@ -1544,14 +1544,18 @@ class LocalMap:
         return us[0]
 
     # the absolute rig pose by RANSAC in front of the refinement (mcorb_lmap_ransac_pose)
-    def ransac_pose(self, cams, cam, uv, octave, threshold, lids=None, pts=None, match=None, max_iterations=100, seed=0, refine=None):
+    def ransac_pose(self, cams, cam, uv, octave, threshold, lids=None, pts=None, match=None, max_iterations=100, seed=0, refine=None,
+                    solver="central"):
         """the pose w_T_b of a rig from observations without a predicted pose: the consensus step of
         FrontEnd::absolutePoseFromGP3P.  The observations and cams are refine_pose()'s; match: non-decreasing match indices (None:
         every observation its own match) -- the consensus set is the first observation of each match; threshold: on 1 - cos of
         the reprojection angle, sac_threshold(K[0](0, 2)) in the reference; max_iterations hypotheses, all examined; seed: of the
         draws.  refine: pose_params(...) -- the refinement over all observations from the RANSAC's pose and the reference's rule
-        between the two.  -> SacResult.  A device store runs k_sac_hypotheses, k_sac_score, k_sac_pick (and k_pose_refine) in one
-        submission; a host-only store the same arithmetic serially, with the same bits"""
+        between the two.  solver: "central" -- a hypothesis's four samples come from one camera, which therefore needs four
+        consensus observations of its own -- or "rig": the samples come from any cameras and a generalized solver works on the
+        rig's rays (k_sac_hypotheses_rig), so matches spread thinly over many cameras still give a pose.  -> SacResult.  A device
+        store runs k_sac_hypotheses, k_sac_score, k_sac_pick (and k_pose_refine) in one submission; a host-only store the same
+        arithmetic serially, with the same bits"""
         cam = np.ascontiguousarray(cam, np.int32).reshape(-1)
         n = len(cam)
         uv = np.ascontiguousarray(uv, np.float32).reshape(n, 2)
@@ -1562,6 +1566,7 @@ class LocalMap:
         ncams, ca = _pose_cams(cams)
         par = _lib.SacParams()
         par.threshold, par.seed, par.max_iterations = float(threshold), int(seed) & 0xFFFFFFFFFFFFFFFF, int(max_iterations)
+        par.solver = SAC_SOLVERS[solver] if isinstance(solver, str) else int(solver)     # (a number goes through as it is, to be refused)
         res, flags = _lib.SacResultC(), np.zeros(max(n, 1), np.uint8)
         _lib.check(self.L.mcorb_lmap_ransac_pose(self.h, n, cam.ctypes.data, uv.ctypes.data, octave.ctypes.data, mp, lp, pp, ncams, ca,
                                                  C.byref(par), None if refine is None else C.byref(refine), C.byref(res),
@@ -1569,7 +1574,7 @@ class LocalMap:
         return SacResult(res, flags[:res.n_matches], refine is not None)
 
     def last_ransac_timing(self):
-        """((us of k_sac_hypotheses, k_sac_score, k_sac_pick), hypotheses) of the last ransac_pose() launch; a device store"""
+        """((us of k_sac_hypotheses or k_sac_hypotheses_rig, k_sac_score, k_sac_pick), hypotheses) of the last ransac_pose() launch; a device store"""
         us, nh = (C.c_float * 3)(), C.c_int(0)
         _lib.check(self.L.mcorb_lmap_last_ransac_timing(self.h, us, C.byref(nh)))
         return tuple(us), nh.value
@@ -1632,6 +1637,8 @@ class SacResult:
 
 
 SAC_OK, SAC_NO_OBS, SAC_NO_MODEL = 0, 1, 2
+SAC_SOLVER_CENTRAL, SAC_SOLVER_RIG = 0, 1
+SAC_SOLVERS = {"central": SAC_SOLVER_CENTRAL, "rig": SAC_SOLVER_RIG}
 
 
 def sac_threshold(K00_02):
@@ -1648,6 +1655,19 @@ def sac_solve(cams, cam, uv, pts):
     assert 0 <= cam < ncams
     R, t = np.zeros((4, 9)), np.zeros((4, 3))
     k = _lib.load().mcorb_sac_solve(ca + int(cam) * C.sizeof(_lib.TrackCam), uv.ctypes.data, pts.ctypes.data, R.ctypes.data, t.ctypes.data)
+    _lib.check(min(k, 0))
+    return [(R[i].reshape(3, 3).copy(), t[i].copy()) for i in range(k)]
+
+
+def sac_solve_rig(cams, cam, uv, pts):
+    """test hook (host): the rig poses (at most 4) of the rig solver on three observations of cameras cam (3) -- keypoints uv
+    (3 x 2), points pts (3 x 3) -> [(R 3 x 3, t)]"""
+    cam = np.ascontiguousarray(cam, np.int32).reshape(3)
+    uv = np.ascontiguousarray(uv, np.float32).reshape(3, 2)
+    pts = np.ascontiguousarray(pts, np.float64).reshape(3, 3)
+    ncams, ca = _pose_cams(cams)
+    R, t = np.zeros((4, 9)), np.zeros((4, 3))
+    k = _lib.load().mcorb_sac_solve_rig(ncams, ca, cam.ctypes.data, uv.ctypes.data, pts.ctypes.data, R.ctypes.data, t.ctypes.data)
     _lib.check(min(k, 0))
     return [(R[i].reshape(3, 3).copy(), t[i].copy()) for i in range(k)]
 

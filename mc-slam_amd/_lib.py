@@ -111,7 +111,7 @@ class PoseResultC(C.Structure):
 
 
 class SacParams(C.Structure):
-    _fields_ = [("threshold", C.c_double), ("seed", C.c_uint64), ("max_iterations", C.c_int32), ("reserved", C.c_int32)]
+    _fields_ = [("threshold", C.c_double), ("seed", C.c_uint64), ("max_iterations", C.c_int32), ("solver", C.c_int32)]
 
 
 class SacResultC(C.Structure):
@@ -300,6 +300,7 @@ SIGNATURES = {
     "mcorb_lmap_last_ransac_counts": (_i, [_vp, _vp, _vp, _i, C.POINTER(_i)]),
     "mcorb_sac_threshold": (C.c_double, [C.c_double]),
     "mcorb_sac_solve": (_i, [_vp, _vp, _vp, _vp, _vp]),
+    "mcorb_sac_solve_rig": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mcorb_sac_eval": (_i, [_i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mcorb_host_geometry": (_i, [C.POINTER(Params), _i, _i, _vp]),
     "mcorb_synth_rig_frame": (_i, [C.c_uint32, _i, _i, _i, _i, _vp, _i]),

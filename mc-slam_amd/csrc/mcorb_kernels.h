@@ -243,7 +243,8 @@ void launch_pose_refine(hipStream_t st, const PoseJob *jobs, int njobs, PoseObs 
 
 // the RANSAC in front of it (mcorb_sac_gpu.hip), three launches.  job, obs, lids | pts, cons / cam_first / cam_cons (the
 // consensus observations in input order, and camera by camera) and is_first (per observation: the first of its match) are device
-// memory.  k_sac_hypotheses: one lane per hypothesis, models[H].  k_sac_score: a workgroup per (tile of kSacTile consensus
+// memory.  k_sac_hypotheses: one lane per hypothesis, models[H]; with MCORB_SAC_SOLVER_RIG k_sac_hypotheses_rig in its place, four
+// lanes per hypothesis (cam_first and cam_cons are not read).  k_sac_score: a workgroup per (tile of kSacTile consensus
 // observations, block of kSacHypBlock hypotheses), integer adds into count[H], which the caller has zeroed on the stream.
 // k_sac_pick: the winner, the flags of all n observations (host-mapped), the record out (host-mapped) and, with pose_job, the
 // winner's pose into pose_job->init for the launch_pose_refine behind it
@@ -265,6 +266,7 @@ struct SacArgs {
     PoseJob *pose_job;
 };
 void launch_sac_hypotheses(hipStream_t st, const SacArgs &a, int H);
+void launch_sac_hypotheses_rig(hipStream_t st, const SacArgs &a, int H);
 void launch_sac_score(hipStream_t st, const SacArgs &a, int S, int H);
 void launch_sac_pick(hipStream_t st, const SacArgs &a, int n);
 

@@ -1,7 +1,8 @@
 // mcorb_sac.cpp -- the absolute rig pose by RANSAC in front of the refinement: mcorb_lmap_ransac_pose, the consensus step of
 // FrontEnd::absolutePoseFromGP3P (MCSlam/src/FrontEnd.cpp:4660-4798) with the refinement and the rule of :4771-4795 behind it.
-// A device store runs k_sac_hypotheses, k_sac_score, k_sac_pick (mcorb_sac_gpu.hip) and, when asked, k_pose_refine in one
-// submission on the store's stream with one wait; the records land in host-mapped memory.  A host-only store runs the header
+// A device store runs k_sac_hypotheses (k_sac_hypotheses_rig with MCORB_SAC_SOLVER_RIG), k_sac_score, k_sac_pick
+// (mcorb_sac_gpu.hip) and, when asked, k_pose_refine in one submission on the store's stream with one wait; the records land in
+// host-mapped memory.  A host-only store runs the header
 // (mcorb_sac.h) serially, so the two agree bit for bit.  Stated rather than OpenGV's: the draws, the minimal solver, no adaptive
 // stop.
 #include <math.h>
@@ -61,6 +62,8 @@ int mcorb_lmap_ransac_pose(mcorb_lmap *m, int n, const int32_t *cam, const float
     if (!(params->threshold > 0) || !sac_finite(params->threshold)) return fail(MCORB_E_ARG, "a threshold that is not finite and positive");
     if (params->max_iterations < 1 || params->max_iterations > MCORB_SAC_MAX_ITERATIONS)
         return fail(MCORB_E_ARG, "1 .. MCORB_SAC_MAX_ITERATIONS iterations");
+    if (params->solver != MCORB_SAC_SOLVER_CENTRAL && params->solver != MCORB_SAC_SOLVER_RIG)
+        return fail(MCORB_E_ARG, "a solver that is not one of MCORB_SAC_SOLVER_*");
     if ((lids != nullptr) == (pts != nullptr)) return fail(MCORB_E_ARG, "exactly one of lids and pts");
     const int nlevels = refine_params ? refine_params->nlevels : MCORB_MAX_LEVELS;
     for (int i = 0; i < n; i++) {
@@ -87,6 +90,7 @@ int mcorb_lmap_ransac_pose(mcorb_lmap *m, int n, const int32_t *cam, const float
     job.n = n;
     job.S = S;
     job.H = H;
+    job.solver = params->solver;
     PoseJob pjob;
     const PoseState ident = PoseState{{1, 0, 0, 0, 1, 0, 0, 0, 1}, {0, 0, 0}};
     if (refine_params) {
@@ -182,7 +186,10 @@ int mcorb_lmap_ransac_pose(mcorb_lmap *m, int n, const int32_t *cam, const float
         a.flags = b.h_flags;
         a.pose_job = refine_params ? reinterpret_cast<PoseJob *>(d) : nullptr;
         HIPCHK(hipEventRecord(m->ev16, st));
-        launch_sac_hypotheses(st, a, H);
+        if (job.solver == MCORB_SAC_SOLVER_RIG)
+            launch_sac_hypotheses_rig(st, a, H);
+        else
+            launch_sac_hypotheses(st, a, H);
         hipError_t launched = hipGetLastError();
         HIPCHK(hipEventRecord(m->ev17, st));
         launch_sac_score(st, a, S, H);
@@ -299,6 +306,27 @@ int mcorb_sac_solve(const mcorb_track_cam *cam, const float *uv, const double *p
     double f[3][3];
     for (int k = 0; k < 3; k++) sac_bearing(*cam, uv[2 * k], uv[2 * k + 1], f[k]);
     sac_solve(*cam, f[0], f[1], f[2], pts, pts + 3, pts + 6, collect);
+    return collect.n;
+}
+
+int mcorb_sac_solve_rig(int ncams, const mcorb_track_cam *cams, const int32_t *cam, const float *uv, const double *pts, double *R, double *t)
+{
+    if (ncams < 1 || ncams > MCORB_MAX_CAMS || !cams || !cam || !uv || !pts || !R || !t) return fail(MCORB_E_ARG, "bad argument");
+    for (int k = 0; k < 3; k++)
+        if (cam[k] < 0 || cam[k] >= ncams) return fail(MCORB_E_ARG, "a camera index outside the rig");
+    struct Collect {
+        double *R, *t;
+        int n;
+        void operator()(const PoseState &P)
+        {
+            memcpy(R + 9 * n, P.R, sizeof(P.R));
+            memcpy(t + 3 * n, P.t, sizeof(P.t));
+            n++;
+        }
+    } collect{R, t, 0};
+    double f[3][3];
+    for (int k = 0; k < 3; k++) sac_bearing(cams[cam[k]], uv[2 * k], uv[2 * k + 1], f[k]);
+    sac_solve_rig(cams, cam[0], cam[1], cam[2], f[0], f[1], f[2], pts, pts + 3, pts + 6, collect);
     return collect.n;
 }
 

@@ -1,7 +1,11 @@
 // mcorb_sac_gpu.hip -- the absolute rig pose by RANSAC of mcorb_sac.h on a device store (mcorb_sac.cpp): three launches on the
 // store's stream, no workgroup waits on another.
 //   k_sac_hypotheses   one lane per hypothesis: the draws, the four points (from the store's geometry by id, or given), the
-//                      minimal solver and the disambiguation; a model record per hypothesis
+//                      central minimal solver and the disambiguation; a model record per hypothesis
+//   k_sac_hypotheses_rig   the same with the rig solver (MCORB_SAC_SOLVER_RIG), four lanes per hypothesis: the lanes of a quad
+//                      compute the sample, the points and the quartic redundantly, then lane k takes root k -- Newton, pose,
+//                      self-check, the fourth point's score -- and two xor-shuffle steps over the quad pick by (score, k) with
+//                      the header's rule; the winning lane, or lane 0 without a model, writes the record
 //   k_sac_score        the hot path, H x S reprojections: a workgroup owns a tile of kSacTile consensus observations, whose
 //                      bearing, point and camera each lane computes once and keeps in registers, and a block of kSacHypBlock
 //                      hypotheses, whose models it reads at uniform addresses; per model a ballot and a population count per
@@ -47,8 +51,72 @@ __global__ __launch_bounds__(64) void k_sac_hypotheses(const SacJob *__restrict_
     const int h = blockIdx.x * 64 + threadIdx.x;
     if (h >= job->H) return;
     const SacPoint point{lids, pts, geom};
-    sac_hypothesis(*job, h, obs, point, cons, cam_first, cam_cons, models[h]);
+    sac_hypothesis_central(*job, h, obs, point, cons, cam_first, cam_cons, models[h]);
 }
+
+// Four lanes per hypothesis, 16 hypotheses per wave.  A quad's lanes hold the same h, so everything up to the quartic is the same
+// in all four and every branch on it is uniform over the quad; the shuffles stay inside the quad.  Quads beyond H compute
+// hypothesis H - 1 again and write nothing.
+__global__ __launch_bounds__(64) void k_sac_hypotheses_rig(const SacJob *__restrict__ job, const PoseObs *__restrict__ obs,
+                                                           const int32_t *__restrict__ lids, const double *__restrict__ pts,
+                                                           const double *__restrict__ geom, const int32_t *__restrict__ cons,
+                                                           SacModel *__restrict__ models)
+{
+    const int t = blockIdx.x * 64 + threadIdx.x, k = t & 3, H = job->H;
+    const bool live = (t >> 2) < H;
+    const int h = live ? t >> 2 : H - 1;
+    const SacPoint point{lids, pts, geom};
+    int32_t s0, s1, s2, s3;
+    const bool ok = sac_sample_rig(job->seed, h, job->S, cons, s0, s1, s2, s3);
+    PoseState P = PoseState{};
+    double score = 0.0;
+    bool has = false;
+    if (ok) {
+        const PoseObs o0 = obs[s0], o1 = obs[s1], o2 = obs[s2], o3 = obs[s3];
+        const mcorb_track_cam &c0 = job->cams[o0.cam], &c1 = job->cams[o1.cam], &c2 = job->cams[o2.cam], &c3 = job->cams[o3.cam];
+        double X0[3], X1[3], X2[3], X3[3], f1[3], f2[3], f3[3], f4[3];
+        point(s0, X0);
+        point(s1, X1);
+        point(s2, X2);
+        point(s3, X3);
+        sac_bearing(c0, o0.u, o0.v, f1);
+        sac_bearing(c1, o1.u, o1.v, f2);
+        sac_bearing(c2, o2.u, o2.v, f3);
+        sac_bearing(c3, o3.u, o3.v, f4);
+        SacRig G;
+        sac_rig_prepare(c0, c1, c2, f1, f2, f3, X0, X1, X2, G);
+        has = sac_rig_root(G, k, c0, c1, c2, f1, f2, f3, X0, X1, X2, P);
+        score = sac_score(c3, P, X3, f4);
+        has = has && score == score;   // (a NaN never wins)
+    }
+    int kb = k, hb = has ? 1 : 0;
+    double sb = score;
+#pragma unroll
+    for (int step = 1; step <= 2; step <<= 1) {
+        const int ko = __shfl_xor(kb, step, 64), ho = __shfl_xor(hb, step, 64);
+        const double so = __shfl_xor(sb, step, 64);
+        const bool beats = sac_root_beats(ho != 0, so, ko, hb != 0, sb, kb);
+        kb = beats ? ko : kb;
+        hb = beats ? ho : hb;
+        sb = beats ? so : sb;
+    }
+    const bool writer = hb ? k == kb : k == 0;
+    if (live && writer) sac_write_model(models[h], hb != 0, P, s0, s1, s2, s3);
+}
+
+#ifdef MCORB_SAC_RIG_ONE_LANE
+// the experiment k_sac_hypotheses_rig was measured against: one lane per hypothesis, the four roots in turn
+__global__ __launch_bounds__(64) void k_sac_hypotheses_rig1(const SacJob *__restrict__ job, const PoseObs *__restrict__ obs,
+                                                            const int32_t *__restrict__ lids, const double *__restrict__ pts,
+                                                            const double *__restrict__ geom, const int32_t *__restrict__ cons,
+                                                            SacModel *__restrict__ models)
+{
+    const int h = blockIdx.x * 64 + threadIdx.x;
+    if (h >= job->H) return;
+    const SacPoint point{lids, pts, geom};
+    sac_hypothesis_rig(*job, h, obs, point, cons, models[h]);
+}
+#endif
 
 __global__ __launch_bounds__(kSacTile) void k_sac_score(const SacJob *__restrict__ job, const PoseObs *__restrict__ obs,
                                                         const int32_t *__restrict__ lids, const double *__restrict__ pts,
@@ -160,6 +228,15 @@ void launch_sac_hypotheses(hipStream_t st, const SacArgs &a, int H)
 {
     hipLaunchKernelGGL(k_sac_hypotheses, dim3((H + 63) / 64), dim3(64), 0, st, a.job, a.obs, a.lids, a.pts, a.geom, a.cons, a.cam_first,
                        a.cam_cons, a.models);
+}
+
+void launch_sac_hypotheses_rig(hipStream_t st, const SacArgs &a, int H)
+{
+#ifdef MCORB_SAC_RIG_ONE_LANE
+    hipLaunchKernelGGL(k_sac_hypotheses_rig1, dim3((H + 63) / 64), dim3(64), 0, st, a.job, a.obs, a.lids, a.pts, a.geom, a.cons, a.models);
+#else
+    hipLaunchKernelGGL(k_sac_hypotheses_rig, dim3((4 * H + 63) / 64), dim3(64), 0, st, a.job, a.obs, a.lids, a.pts, a.geom, a.cons, a.models);
+#endif
 }
 
 void launch_sac_score(hipStream_t st, const SacArgs &a, int S, int H)

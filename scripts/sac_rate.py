@@ -15,7 +15,17 @@ stores agree bit for bit.
 `pose_rate.py --leg ab --tree PARENT`, from which the one guard is computed: refine_pose's whole call (refine_device) on this
 commit's library must not exceed the parent's slowest run by more than the parent's spread of medians.
 
-    python scripts/sac_rate.py --leg all [--guard profiles/pose_rate_ab.json] [--out profiles/sac_rate.json]"""
+--solver rig: every leg with solver="rig" (k_sac_hypotheses_rig in k_sac_hypotheses' place) -> profiles/sac_rate_rig.json.
+--tree DIR (--leg one): DIR's package and library are timed instead of this checkout's -- a checkout of another commit, or a copy
+of the package beside a library built with other switches.  With --leg all:
+  --parent DIR      the parent commit's checkout: its library and this one's alternate, --procs processes each, with the
+                    central solver; the guard is that ransac_pose's whole call on the device store (sac_device) on this commit's
+                    library must not exceed the parent's slowest run by more than the parent's spread of medians
+  --alt NAME=DIR    (repeatable) a library built with other switches -- MCORB_SAC_RIG_ONE_LANE, MCORB_SAC_RIG_NEWTON=8 --
+                    alternating with this one's, --procs processes each, with --solver
+
+    python scripts/sac_rate.py --leg all [--guard profiles/pose_rate_ab.json] [--out profiles/sac_rate.json]
+    python scripts/sac_rate.py --leg all --solver rig --parent PARENT [--alt one_lane=DIR] --out profiles/sac_rate_rig.json"""
 import argparse
 import json
 import math
@@ -69,7 +79,8 @@ def frame(mcorb):
 def one_leg(mcorb, a):
     view, lm, lm_host, cam, uv, octave, lids, moved, thr = frame(mcorb)
     refine = mcorb.pose_params(INV_SIGMA2)
-    out = {"cores": len(os.sched_getaffinity(0)), "matches": int(len(cam)), "moved": int(moved.sum()), "threshold": thr,
+    kw = {} if a.solver == "central" else {"solver": a.solver}      # (a checkout from before the solvers has no such argument)
+    out = {"solver": a.solver, "cores": len(os.sched_getaffinity(0)), "matches": int(len(cam)), "moved": int(moved.sum()), "threshold": thr,
            "grid": {"tile": TILE, "hypothesis_block": HYP_BLOCK}, "runs": {}}
     for H in (100, 1024):
         legs = ["sac_device", "sac_host", "sac_refine_device", "sac_then_refine"]
@@ -79,13 +90,13 @@ def one_leg(mcorb, a):
             for k in legs:
                 t0 = time.perf_counter()
                 if k == "sac_device":
-                    res[k] = lm.ransac_pose(view, cam, uv, octave, thr, lids=lids, max_iterations=H)
+                    res[k] = lm.ransac_pose(view, cam, uv, octave, thr, lids=lids, max_iterations=H, **kw)
                 elif k == "sac_host":
-                    res[k] = lm_host.ransac_pose(view, cam, uv, octave, thr, lids=lids, max_iterations=H)
+                    res[k] = lm_host.ransac_pose(view, cam, uv, octave, thr, lids=lids, max_iterations=H, **kw)
                 elif k == "sac_refine_device":
-                    res[k] = lm.ransac_pose(view, cam, uv, octave, thr, lids=lids, max_iterations=H, refine=refine)
+                    res[k] = lm.ransac_pose(view, cam, uv, octave, thr, lids=lids, max_iterations=H, refine=refine, **kw)
                 else:
-                    s = lm.ransac_pose(view, cam, uv, octave, thr, lids=lids, max_iterations=H)
+                    s = lm.ransac_pose(view, cam, uv, octave, thr, lids=lids, max_iterations=H, **kw)
                     res[k] = lm.refine_pose(view, s.sac_R, s.sac_t, cam, uv, octave, INV_SIGMA2, lids=lids)
                 t[k].append((time.perf_counter() - t0) * 1e3)
                 if k == "sac_device":
@@ -110,8 +121,9 @@ def one_leg(mcorb, a):
     print(json.dumps(out))
 
 
-def child(a):
-    cmd = [sys.executable, os.path.abspath(__file__), "--leg", "one", "--reps", str(a.reps), "--hyp-block", str(a.hyp_block)]
+def child(a, tree=None, solver=None):
+    cmd = [sys.executable, os.path.abspath(__file__), "--leg", "one", "--reps", str(a.reps), "--hyp-block", str(a.hyp_block), "--solver",
+           solver or a.solver] + (["--tree", tree] if tree else [])
     return json.loads(subprocess.run(cmd, check=True, capture_output=True, text=True, timeout=400).stdout.strip().splitlines()[-1])
 
 
@@ -128,6 +140,24 @@ def guard_of(path):
             "met": bool(max(tm) <= slowest + spread)}
 
 
+def parent_guard(a):
+    """the parent's library and this one's alternating with the central solver -> the guard on ransac_pose's whole call"""
+    pairs = [{"parent": child(a, a.parent, "central"), "this": child(a, None, "central")} for _ in range(a.procs)]
+    out = {"leg": "ransac_pose with the central solver, the whole call on the device store", "met": True}
+    for H in ("100", "1024"):
+        pm = [p["parent"]["runs"][H]["sac_device_ms"] for p in pairs]
+        slowest = max(x for p in pairs for x in p["parent"]["runs"][H]["sac_device_ms_runs"])
+        spread = max(pm) - min(pm)
+        tm = [p["this"]["runs"][H]["sac_device_ms"] for p in pairs]
+        out[H] = {"parent_medians_ms": pm, "parent_slowest_run_ms": slowest, "parent_spread_of_medians_ms": round(spread, 3),
+                  "this_medians_ms": tm, "limit_ms": round(slowest + spread, 3), "met": bool(max(tm) <= slowest + spread),
+                  "parent_k_sac_hypotheses_us": [p["parent"]["runs"][H]["k_sac_hypotheses_us"] for p in pairs],
+                  "this_k_sac_hypotheses_us": [p["this"]["runs"][H]["k_sac_hypotheses_us"] for p in pairs]}
+        out["met"] = out["met"] and out[H]["met"]
+    out["pairs"] = pairs
+    return out
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
@@ -135,16 +165,27 @@ if __name__ == "__main__":
     ap.add_argument("--leg", default="one", choices=["one", "all"])
     ap.add_argument("--guard", default=None, help="a record of pose_rate.py --leg ab --tree PARENT")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--solver", default="central", choices=["central", "rig"])
+    ap.add_argument("--tree", default=None, help="--leg one: a checkout whose package and library are timed instead of this one's")
+    ap.add_argument("--parent", default=None, help="--leg all: the parent commit's checkout, for the guard on the central solver")
+    ap.add_argument("--alt", action="append", default=[], help="--leg all: NAME=DIR, a library built with other switches")
     ap.add_argument("--hyp-block", type=int, default=HYP_BLOCK, help="the library's MCORB_SAC_HYP_BLOCK, when it was built with another")
     a = ap.parse_args()
     HYP_BLOCK = a.hyp_block
     if a.leg == "one":
+        if a.tree:
+            sys.path.insert(0, os.path.abspath(a.tree))
         import mcorb
         one_leg(mcorb, a)
         sys.exit(0)
     out = {"processes": [child(a) for _ in range(a.procs)]}
     if a.guard:
         out["regression_guard"] = guard_of(a.guard)
+    if a.parent:
+        out["central_solver_guard"] = parent_guard(a)
+    for alt in a.alt:
+        name, tree = alt.split("=", 1)
+        out.setdefault("alternates", {})[name] = [{"alternate": child(a, tree), "this": child(a)} for _ in range(a.procs)]
     print(json.dumps(out))
     if a.out:
         with open(a.out, "w") as f:
