@@ -462,13 +462,6 @@ private:
     int finish_match(Slot &s, const Job &j);
 };
 
-// Elapsed milliseconds between two events of a finished job; 0 when either was not recorded on a stream (a job that ran from its
-// captured graph holds them as graph nodes).  A failed query must not stay behind as the thread's "last error".
-static inline void ev_elapsed(float *ms, hipEvent_t a, hipEvent_t b)
-{
-    if (hipEventElapsedTime(ms, a, b) != hipSuccess) { *ms = 0.f; (void)hipGetLastError(); }
-}
-
 // k-NN rows as the API hands them out: (idx0, idx1) and (d0, d1) per query
 inline void decode_rows(const KnnRow *rows, int nq, int32_t *idx, int32_t *dist)
 {

@@ -1,5 +1,6 @@
-// mcorb_hip.h -- the one place where HIP buffers, events and streams are acquired and released: the error macros and four
-// move-only owners.  No shared ownership, no allocator policy: an owner holds one handle and its destructor releases it.
+// mcorb_hip.h -- the one place where HIP buffers, events and streams are acquired and released: the error macros, four
+// move-only owners and the events around the pieces of a submission (Spans).  No shared ownership, no allocator policy: an owner
+// holds one handle and its destructor releases it.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -97,6 +98,36 @@ public:
         reset();
         HIPCHK(hipEventCreateWithFlags(&h_, flags));
         return MCORB_OK;
+    }
+};
+
+// Elapsed milliseconds between two events of a finished job; 0 when either was not recorded on a stream (a job that ran from its
+// captured graph holds them as graph nodes).  A failed query must not stay behind as the thread's "last error".
+static inline void ev_elapsed(float *ms, hipEvent_t a, hipEvent_t b)
+{
+    if (hipEventElapsedTime(ms, a, b) != hipSuccess) { *ms = 0.f; (void)hipGetLastError(); }
+}
+
+// N + 1 events around N consecutive pieces of a submission: mark(st, i) records event i, so piece i runs between marks i and
+// i + 1.  read(), after the synchronisation: us[i] = the microseconds of piece i by ev_elapsed's rule; the pieces below `from`
+// did not run in this submission (their first events were not marked) and read 0
+template <int N>
+struct Spans {
+    Event ev[N + 1];
+    float us[N] = {};
+    int create()
+    {
+        for (Event &e : ev) TRY(e.create(hipEventDefault));
+        return MCORB_OK;
+    }
+    int mark(hipStream_t st, int i) { HIPCHK(hipEventRecord(ev[i], st)); return MCORB_OK; }
+    void read(int from = 0)
+    {
+        for (int i = 0; i < N; i++) {
+            float ms = 0.f;
+            if (i >= from) ev_elapsed(&ms, ev[i], ev[i + 1]);
+            us[i] = ms * 1000.f;
+        }
     }
 };
 

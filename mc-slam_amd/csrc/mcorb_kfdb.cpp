@@ -266,17 +266,15 @@ static int run_score(mcorb_kfdb *db, const BowArrays &store, const BowArrays &qu
     TRY(db->h_shared.grow(nout, hipHostMallocDefault));
     hipStream_t st = db->st;
     HIPCHK(hipMemcpyAsync(db->d_ctl, ctl.data(), ctl.size() * sizeof(int), hipMemcpyHostToDevice, st));
-    HIPCHK(hipEventRecord(db->ev0, st));
+    TRY(db->score.mark(st, 0));
     launch_kfdb_score(st, store.ids, store.vals, store.n, db->max_words, query.ids, query.vals, query.n, db->d_ctl, db->d_ctl + nq,
                       against ? db->d_ctl + 2 * (size_t)nq : nullptr, nq, max_limit, os, db->d_raw, db->d_shared);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(db->ev1, st));
+    TRY(db->score.mark(st, 1));
     HIPCHK(hipMemcpyAsync(db->h_raw, db->d_raw, nout * sizeof(double), hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(db->h_shared, db->d_shared, nout * sizeof(int), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));   // (also covers the pageable control array)
-    float ms = 0.f;
-    ev_elapsed(&ms, db->ev0, db->ev1);
-    db->us_score = ms * 1000.f;
+    db->score.read();
     return MCORB_OK;
 }
 
@@ -319,11 +317,7 @@ static double score_host(const HostEntry &a, const HostEntry &b)
     return -s / 2.0;
 }
 
-int Best2Search::create()
-{
-    TRY(ev0.create(hipEventDefault));
-    return ev1.create(hipEventDefault);
-}
+int Best2Search::create() { return launch.create(); }
 
 void Best2Search::reset()
 {
@@ -360,15 +354,14 @@ int Best2Search::run(hipStream_t st, const uint8_t *desc_a, const int *feats_a, 
     TRY(h_mtab.grow(items.size(), hipHostMallocDefault));
     HIPCHK(hipMemcpyAsync(d_items, items.data(), items.size() * sizeof(int2), hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(d_recs, recs.data(), recs.size() * sizeof(int4), hipMemcpyHostToDevice, st));
-    HIPCHK(hipEventRecord(ev0, st));
+    TRY(launch.mark(st, 0));
     launch_kfdb_best2(st, desc_a, feats_a, desc_b, desc_stride, feats_b, feats_stride, d_items, (int)items.size(), d_recs, d_mtab);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(ev1, st));
+    TRY(launch.mark(st, 1));
     HIPCHK(hipMemcpyAsync(h_mtab, d_mtab, items.size() * sizeof(int4), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));   // (also covers the pageable item and record lists)
-    float ms = 0.f;
-    ev_elapsed(&ms, ev0, ev1);
-    *us = ms * 1000.f;
+    launch.read();
+    *us = launch.us[0];
     std::vector<uint32_t> mA, mB;
     std::vector<double> mD;
     for (size_t b = 0; b < nb; b++)
@@ -406,8 +399,7 @@ int mcorb_kfdb_create(const mcorb_vocab *v, int device, int max_entries, int max
         HIPCHK(hipSetDevice(device));
         const size_t E = (size_t)max_entries, W = (size_t)max_words, F = (size_t)max_feats;
         TRY(db->st.create(hipStreamNonBlocking));
-        TRY(db->ev0.create(hipEventDefault));
-        TRY(db->ev1.create(hipEventDefault));
+        TRY(db->score.create());
         TRY(db->best2.create());
         TRY(db->d_ids.alloc(E * W));
         TRY(db->d_vals.alloc(E * W));
@@ -642,7 +634,7 @@ int mcorb_kfdb_last_timing(mcorb_kfdb *db, float us[2])
     TRY(check_db(db, "kfdb last_timing"));
     if (!us) { set_error("kfdb last_timing: bad argument"); return MCORB_E_ARG; }
     std::lock_guard<std::mutex> lk(db->mu);
-    us[0] = db->us_score;
+    us[0] = db->score.us[0];
     us[1] = db->us_best2;
     return MCORB_OK;
 }

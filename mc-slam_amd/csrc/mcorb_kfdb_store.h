@@ -40,7 +40,7 @@ struct Best2Search {
     DevBuf<int2> d_items;
     DevBuf<int4> d_recs, d_mtab;   // (grow-only, like h_mtab)
     HostBuf<int4> h_mtab;
-    Event ev0, ev1;
+    Spans<1> launch;                           // around k_kfdb_best2
     std::vector<int2> items;                   // {position in A's feature list, record}, B by B and node by node
     std::vector<int4> recs;                    // a node A shares with a B: {B's set, first position, count, -} in B's feature list
     std::vector<int> first_item, first_rec;    // per record: its first item; per B: its first record
@@ -72,7 +72,7 @@ struct mcorb_kfdb {
     std::vector<mcorb::HostEntry> probes;
     // device database: the store, strided per entry
     mcorb::Stream st;
-    mcorb::Event ev0, ev1;
+    mcorb::Spans<1> score;                      // around the scoring kernel of a query
     mcorb::DevBuf<uint32_t> d_ids, d_nodes;     // [max_words], [max_feats]
     mcorb::DevBuf<double> d_vals;               // [max_words]
     mcorb::DevBuf<int> d_nbow;                  // one per entry
@@ -100,7 +100,7 @@ struct mcorb_kfdb {
     mcorb::HostBuf<int> h_knnctl, h_mcount;     // {setmap[2], pair}
     mcorb::HostBuf<mcorb::KnnRow> h_rows;
     mcorb::HostBuf<uint32_t> h_mlist;
-    float us_score = 0.f, us_best2 = 0.f, us_best2p = 0.f;   // the last launch of each kernel, between HIP events
+    float us_best2 = 0.f, us_best2p = 0.f;      // the last k_kfdb_best2 launch of a feature-match call and of a probe call
 };
 
 namespace mcorb {

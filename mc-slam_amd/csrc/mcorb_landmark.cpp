@@ -34,16 +34,16 @@ int check_ids(const mcorb_lmap *m, const int32_t *lids, int n, const char *who)
 }
 
 // the rounds of a batch: order[] lists the items round by round (batch order inside a round), first[r] is round r's first entry
-// (first.size() - 1 rounds), nth[i] is how often lids[i] occurred before item i.  Leaves m->occ zero.
+// (first.size() - 1 rounds), nth[i] is how often lids[i] occurred before item i.  Leaves m->life.occ zero.
 void cut_rounds(mcorb_lmap *m, const int32_t *lids, int n, std::vector<int> &order, std::vector<int> &first, std::vector<int> &nth)
 {
     nth.resize((size_t)n);
     int rounds = 0;
     for (int i = 0; i < n; i++) {
-        nth[i] = m->occ[lids[i]]++;
+        nth[i] = m->life.occ[lids[i]]++;
         rounds = std::max(rounds, nth[i] + 1);
     }
-    for (int i = 0; i < n; i++) m->occ[lids[i]] = 0;
+    for (int i = 0; i < n; i++) m->life.occ[lids[i]] = 0;
     first.assign((size_t)rounds + 1, 0);
     for (int i = 0; i < n; i++) first[nth[i] + 1]++;
     for (int r = 0; r < rounds; r++) first[r + 1] += first[r];
@@ -57,8 +57,8 @@ void keep_last(mcorb_lmap *m, const int32_t *lids, int n, std::vector<int> &keep
 {
     keep.assign(lids, lids + n);
     for (int i = n - 1; i >= 0; i--)
-        if (m->occ[lids[i]]++) keep[i] = -1;
-    for (int i = 0; i < n; i++) m->occ[lids[i]] = 0;
+        if (m->life.occ[lids[i]]++) keep[i] = -1;
+    for (int i = 0; i < n; i++) m->life.occ[lids[i]] = 0;
 }
 
 }  // namespace
@@ -82,16 +82,16 @@ int mcorb_lmap_set_rays(mcorb_lmap *m, const int32_t *lids, int n, const int32_t
         keep_last(m, lids, n, keep);
         HIPCHK(hipSetDevice(m->device));
         hipStream_t st = m->st;
-        TRY(m->h_rays.grow(2 * (size_t)n, hipHostMallocDefault));
-        TRY(m->d_rays.grow(2 * (size_t)n));
+        TRY(m->life.h_rays.grow(2 * (size_t)n, hipHostMallocDefault));
+        TRY(m->life.d_rays.grow(2 * (size_t)n));
         int k = 0;
         for (int i = 0; i < n; i++)
             if (keep[i] >= 0) k++;
         int at = 0;
         for (int i = 0; i < n; i++)
-            if (keep[i] >= 0) { m->h_rays[at] = lids[i]; m->h_rays[k + at] = n_rays[i]; at++; }
-        HIPCHK(hipMemcpyAsync(m->d_rays, m->h_rays, 2 * (size_t)k * sizeof(int32_t), hipMemcpyHostToDevice, st));
-        launch_lmap_put_rays(st, m->d_rays, m->d_rays + k, k, m->d_nrays);
+            if (keep[i] >= 0) { m->life.h_rays[at] = lids[i]; m->life.h_rays[k + at] = n_rays[i]; at++; }
+        HIPCHK(hipMemcpyAsync(m->life.d_rays, m->life.h_rays, 2 * (size_t)k * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        launch_lmap_put_rays(st, m->life.d_rays, m->life.d_rays + k, k, m->d_nrays);
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(st));
     }
@@ -179,34 +179,30 @@ int mcorb_lmap_observe(mcorb_lmap *m, const mcorb_obs_frame *frame, const int32_
         HIPCHK(hipSetDevice(m->device));
         hipStream_t st = m->st;
         if (update) {
-            TRY(m->h_obsitems.grow((size_t)n, hipHostMallocDefault));
-            TRY(m->d_obsitems.grow((size_t)n));
-            for (int k = 0; k < n; k++) m->h_obsitems[k] = LmObsItem{lids[order[k]], mask[order[k]]};
-            HIPCHK(hipMemcpyAsync(m->d_obsitems, m->h_obsitems, (size_t)n * sizeof(LmObsItem), hipMemcpyHostToDevice, st));
-            HIPCHK(hipEventRecord(m->ev4, st));
+            TRY(m->life.h_obsitems.grow((size_t)n, hipHostMallocDefault));
+            TRY(m->life.d_obsitems.grow((size_t)n));
+            for (int k = 0; k < n; k++) m->life.h_obsitems[k] = LmObsItem{lids[order[k]], mask[order[k]]};
+            HIPCHK(hipMemcpyAsync(m->life.d_obsitems, m->life.h_obsitems, (size_t)n * sizeof(LmObsItem), hipMemcpyHostToDevice, st));
+            TRY(m->life.observe.mark(st, 0));
             for (size_t r = 0; r + 1 < first.size(); r++) {
-                launch_lmap_observe(st, cen, C, m->d_obsitems + first[r], first[r + 1] - first[r], m->d_geom, m->d_nrays);
+                launch_lmap_observe(st, cen, C, m->life.d_obsitems + first[r], first[r + 1] - first[r], m->d_geom, m->d_nrays);
                 HIPCHK(hipGetLastError());
             }
-            HIPCHK(hipEventRecord(m->ev5, st));
+            TRY(m->life.observe.mark(st, 1));
         }
         if (entry >= 0) {
             std::vector<int> keep;
             keep_last(m, lids, n, keep);
-            TRY(m->d_blids.grow((size_t)n));
-            TRY(m->d_brows.grow((size_t)n));
-            HIPCHK(hipMemcpyAsync(m->d_blids, keep.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, st));
-            HIPCHK(hipMemcpyAsync(m->d_brows, feats, (size_t)n * sizeof(int), hipMemcpyHostToDevice, st));
-            launch_lmap_put(st, m->d_blids, n, nullptr, nullptr, place_of(db, entry, false).desc, m->d_brows, m->d_geom, m->d_desc);
+            TRY(m->batch.upload(m->batch.d_lids, keep.data(), (size_t)n, st));
+            TRY(m->batch.upload(m->batch.d_rows, feats, (size_t)n, st));
+            launch_lmap_put(st, m->batch.d_lids, n, nullptr, nullptr, place_of(db, entry, false).desc, m->batch.d_rows, m->d_geom, m->d_desc);
             HIPCHK(hipGetLastError());
             HIPCHK(hipStreamSynchronize(st));   // (also covers the pageable lists)
         } else if (update) {
             HIPCHK(hipStreamSynchronize(st));
         }
         if (update) {
-            float ms = 0.f;
-            ev_elapsed(&ms, m->ev4, m->ev5);
-            m->us_observe = ms * 1000.f;
+            m->life.observe.read();
             // the host's copy of the ray counts: the integer part of lm_observe, in batch order
             for (int i = 0; i < n; i++) {
                 int32_t &nr = m->n_rays[lids[i]];
@@ -251,32 +247,30 @@ int mcorb_lmap_update_points(mcorb_lmap *m, const int32_t *lids, int n, const do
     cut_rounds(m, lids, n, order, first, nth);
     HIPCHK(hipSetDevice(m->device));
     hipStream_t st = m->st;
-    TRY(m->h_upditems.grow((size_t)n, hipHostMallocDefault));
-    TRY(m->d_upditems.grow((size_t)n));
-    TRY(m->h_updout.grow((size_t)n, hipHostMallocDefault));
-    TRY(m->d_updout.grow((size_t)n));
+    TRY(m->life.h_upditems.grow((size_t)n, hipHostMallocDefault));
+    TRY(m->life.d_upditems.grow((size_t)n));
+    TRY(m->life.h_updout.grow((size_t)n, hipHostMallocDefault));
+    TRY(m->life.d_updout.grow((size_t)n));
     for (int k = 0; k < n; k++) {
         const int i = order[k];
-        LmUpdItem &it = m->h_upditems[k];
+        LmUpdItem &it = m->life.h_upditems[k];
         it.lid = lids[i];
         it.idx = i;
         memcpy(it.p, pt_new + 3 * (size_t)i, 3 * sizeof(double));
     }
-    HIPCHK(hipMemcpyAsync(m->d_upditems, m->h_upditems, (size_t)n * sizeof(LmUpdItem), hipMemcpyHostToDevice, st));
-    HIPCHK(hipEventRecord(m->ev6, st));
+    HIPCHK(hipMemcpyAsync(m->life.d_upditems, m->life.h_upditems, (size_t)n * sizeof(LmUpdItem), hipMemcpyHostToDevice, st));
+    TRY(m->life.update.mark(st, 0));
     for (size_t r = 0; r + 1 < first.size(); r++) {
-        launch_lmap_update(st, m->d_upditems + first[r], first[r + 1] - first[r], max_diff, m->d_geom, m->d_updout);
+        launch_lmap_update(st, m->life.d_upditems + first[r], first[r + 1] - first[r], max_diff, m->d_geom, m->life.d_updout);
         HIPCHK(hipGetLastError());
     }
-    HIPCHK(hipEventRecord(m->ev7, st));
-    HIPCHK(hipMemcpyAsync(m->h_updout, m->d_updout, (size_t)n * sizeof(LmUpdOut), hipMemcpyDeviceToHost, st));
+    TRY(m->life.update.mark(st, 1));
+    HIPCHK(hipMemcpyAsync(m->life.h_updout, m->life.d_updout, (size_t)n * sizeof(LmUpdOut), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
-    float ms = 0.f;
-    ev_elapsed(&ms, m->ev6, m->ev7);
-    m->us_update = ms * 1000.f;
+    m->life.update.read();
     for (int i = 0; i < n; i++) {
-        if (updated) updated[i] = m->h_updout[i].updated ? 1 : 0;
-        if (diff_norm) diff_norm[i] = m->h_updout[i].diff_norm;
+        if (updated) updated[i] = m->life.h_updout[i].updated ? 1 : 0;
+        if (diff_norm) diff_norm[i] = m->life.h_updout[i].diff_norm;
     }
     return MCORB_OK;
 }
@@ -291,8 +285,8 @@ int mcorb_lmap_delete(mcorb_lmap *m, const int32_t *lids, int n, int32_t *kfs, i
     TRY(check_ids(m, lids, n, who));
     bool twice = false;
     for (int i = 0; i < n; i++)
-        if (m->occ[lids[i]]++) twice = true;
-    for (int i = 0; i < n; i++) m->occ[lids[i]] = 0;
+        if (m->life.occ[lids[i]]++) twice = true;
+    for (int i = 0; i < n; i++) m->life.occ[lids[i]] = 0;
     if (twice) return fail(MCORB_E_ARG, who, "a landmark id twice in the batch");
     size_t total = 0;
     for (int i = 0; i < n; i++) {
@@ -305,9 +299,9 @@ int mcorb_lmap_delete(mcorb_lmap *m, const int32_t *lids, int n, int32_t *kfs, i
     if (m->device >= 0) {
         HIPCHK(hipSetDevice(m->device));
         hipStream_t st = m->st;
-        TRY(m->d_rays.grow((size_t)n));
-        HIPCHK(hipMemcpyAsync(m->d_rays, lids, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, st));
-        launch_lmap_put_rays(st, m->d_rays, nullptr, n, m->d_nrays);
+        TRY(m->life.d_rays.grow((size_t)n));
+        HIPCHK(hipMemcpyAsync(m->life.d_rays, lids, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        launch_lmap_put_rays(st, m->life.d_rays, nullptr, n, m->d_nrays);
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(st));   // (also covers the pageable list)
     }
@@ -348,8 +342,8 @@ int mcorb_lmap_last_landmark_timing(mcorb_lmap *m, float us[2])
     TRY(check_lmap_handle(m, "lmap last_landmark_timing"));
     if (!us) return fail(MCORB_E_ARG, "lmap last_landmark_timing", "bad argument");
     std::lock_guard<std::mutex> lk(m->mu);
-    us[0] = m->us_observe;
-    us[1] = m->us_update;
+    us[0] = m->life.observe.us[0];
+    us[1] = m->life.update.us[0];
     return MCORB_OK;
 }
 

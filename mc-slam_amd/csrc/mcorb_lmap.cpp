@@ -49,27 +49,17 @@ static int put_device(mcorb_lmap *m, const std::vector<int> &keep, const double 
     const size_t n = keep.size();
     HIPCHK(hipSetDevice(m->device));
     hipStream_t st = m->st;
-    TRY(m->d_blids.grow(n));
-    HIPCHK(hipMemcpyAsync(m->d_blids, keep.data(), n * sizeof(int), hipMemcpyHostToDevice, st));
-    if (pt3d) {
-        TRY(m->d_bpt.grow(n * 3));
-        HIPCHK(hipMemcpyAsync(m->d_bpt, pt3d, n * 3 * sizeof(double), hipMemcpyHostToDevice, st));
-    }
-    if (normal) {
-        TRY(m->d_bnormal.grow(n * 3));
-        HIPCHK(hipMemcpyAsync(m->d_bnormal, normal, n * 3 * sizeof(double), hipMemcpyHostToDevice, st));
-    }
+    mcorb_lmap::Batch &b = m->batch;
+    TRY(b.upload(b.d_lids, keep.data(), n, st));
+    if (pt3d) TRY(b.upload(b.d_pt, pt3d, n * 3, st));
+    if (normal) TRY(b.upload(b.d_normal, normal, n * 3, st));
     if (desc) {
-        TRY(m->d_bdesc.grow(n * 32));
-        HIPCHK(hipMemcpyAsync(m->d_bdesc, desc, n * 32, hipMemcpyHostToDevice, st));
-        src_desc = m->d_bdesc;
+        TRY(b.upload(b.d_desc, desc, n * 32, st));
+        src_desc = b.d_desc;
     }
-    if (rows) {
-        TRY(m->d_brows.grow(n));
-        HIPCHK(hipMemcpyAsync(m->d_brows, rows, n * sizeof(int), hipMemcpyHostToDevice, st));
-    }
-    launch_lmap_put(st, m->d_blids, (int)n, pt3d ? m->d_bpt.get() : nullptr, normal ? m->d_bnormal.get() : nullptr, src_desc,
-                    rows ? m->d_brows.get() : nullptr, m->d_geom, m->d_desc);
+    if (rows) TRY(b.upload(b.d_rows, rows, n, st));
+    launch_lmap_put(st, b.d_lids, (int)n, pt3d ? b.d_pt.get() : nullptr, normal ? b.d_normal.get() : nullptr, src_desc,
+                    rows ? b.d_rows.get() : nullptr, m->d_geom, m->d_desc);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(st));   // (also covers the pageable host arrays)
     return MCORB_OK;
@@ -128,7 +118,7 @@ int mcorb_lmap_create(mcorb_vocab *v, int device, int max_landmarks, int max_can
     m->stamp.assign((size_t)max_landmarks, 0);
     m->n_rays.assign((size_t)max_landmarks, 0);
     m->obs.resize((size_t)max_landmarks);
-    m->occ.assign((size_t)max_landmarks, 0);
+    m->life.occ.assign((size_t)max_landmarks, 0);
     if (device < 0) {
         m->geom.assign((size_t)max_landmarks * 6, 0.0);
         m->desc.assign((size_t)max_landmarks * 32, 0);
@@ -138,39 +128,20 @@ int mcorb_lmap_create(mcorb_vocab *v, int device, int max_landmarks, int max_can
         HIPCHK(hipSetDevice(device));
         const size_t N = (size_t)max_landmarks, C = (size_t)max_candidates;
         TRY(m->st.create(hipStreamNonBlocking));
-        TRY(m->ev0.create(hipEventDefault));
-        TRY(m->ev1.create(hipEventDefault));
-        TRY(m->ev2.create(hipEventDefault));
-        TRY(m->ev3.create(hipEventDefault));
-        TRY(m->ev4.create(hipEventDefault));
-        TRY(m->ev5.create(hipEventDefault));
-        TRY(m->ev6.create(hipEventDefault));
-        TRY(m->ev7.create(hipEventDefault));
-        TRY(m->ev8.create(hipEventDefault));
-        TRY(m->ev9.create(hipEventDefault));
-        TRY(m->ev10.create(hipEventDefault));
-        TRY(m->ev11.create(hipEventDefault));
-        TRY(m->ev12.create(hipEventDefault));
-        TRY(m->ev13.create(hipEventDefault));
-        TRY(m->ev14.create(hipEventDefault));
-        TRY(m->ev15.create(hipEventDefault));
-        TRY(m->ev16.create(hipEventDefault));
-        TRY(m->ev17.create(hipEventDefault));
-        TRY(m->ev18.create(hipEventDefault));
-        TRY(m->ev19.create(hipEventDefault));
-        TRY(m->best2.create());
+        TRY(m->search.create(C));
+        TRY(m->map.neigh.create());
+        TRY(m->map.refine_new.create());
+        TRY(m->life.observe.create());
+        TRY(m->life.update.create());
+        TRY(m->track.chain.create());
+        TRY(m->pose.refine.create());
+        TRY(m->sac.kernels.create());
         TRY(m->d_geom.alloc(N * 6));
         TRY(m->d_desc.alloc(N * 32));
         HIPCHK(hipMemset(m->d_geom, 0, N * 6 * sizeof(double)));
         HIPCHK(hipMemset(m->d_desc, 0, N * 32));
         TRY(m->d_nrays.alloc(N));
         HIPCHK(hipMemset(m->d_nrays, 0, N * sizeof(int32_t)));
-        TRY(m->d_view.alloc(1));
-        TRY(m->d_cand.alloc(C));
-        TRY(m->d_afeats.alloc(C));
-        TRY(m->d_masks.alloc(C));
-        TRY(m->h_masks.alloc(C, hipHostMallocDefault));
-        TRY(m->d_adesc.alloc(C * 32));
     }
     *out = m.release();
     return MCORB_OK;
@@ -310,7 +281,7 @@ int mcorb_lmap_search(mcorb_lmap *m, const mcorb_lmap_view *view, const int32_t 
     if (nc > m->max_candidates) { set_error("lmap search: more candidates than max_candidates"); return MCORB_E_CAP; }
     for (int l : cand)
         if ((m->flags[l] & kSet) != kSet) { set_error("lmap search: a candidate landmark was never set"); return MCORB_E_STATE; }
-    m->last_candidates = nc;
+    m->search.last_candidates = nc;
 
     // 2. the frustum test (:5000-5027) and the accepted landmarks in candidate order
     std::vector<int> acc;          // slots
@@ -323,19 +294,17 @@ int mcorb_lmap_search(mcorb_lmap *m, const mcorb_lmap_view *view, const int32_t 
         }
     } else if (nc) {
         HIPCHK(hipSetDevice(m->device));
-        HIPCHK(hipMemcpyAsync(m->d_view, view, sizeof(mcorb_lmap_view), hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(m->d_cand, cand.data(), (size_t)nc * sizeof(int), hipMemcpyHostToDevice, st));
-        HIPCHK(hipEventRecord(m->ev0, st));
-        launch_lmap_cull(st, m->d_view, m->d_geom, m->d_cand, nc, m->d_masks);
+        HIPCHK(hipMemcpyAsync(m->search.d_view, view, sizeof(mcorb_lmap_view), hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(m->search.d_cand, cand.data(), (size_t)nc * sizeof(int), hipMemcpyHostToDevice, st));
+        TRY(m->search.cull.mark(st, 0));
+        launch_lmap_cull(st, m->search.d_view, m->d_geom, m->search.d_cand, nc, m->search.d_masks);
         HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(m->ev1, st));
-        HIPCHK(hipMemcpyAsync(m->h_masks, m->d_masks, (size_t)nc * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        TRY(m->search.cull.mark(st, 1));
+        HIPCHK(hipMemcpyAsync(m->search.h_masks, m->search.d_masks, (size_t)nc * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));   // (also covers the pageable view and candidate list)
-        float ms = 0.f;
-        ev_elapsed(&ms, m->ev0, m->ev1);
-        m->us_cull = ms * 1000.f;
+        m->search.cull.read();
         for (int i = 0; i < nc; i++)
-            if (m->h_masks[i]) { acc.push_back(cand[i]); masks.push_back(m->h_masks[i]); }
+            if (m->search.h_masks[i]) { acc.push_back(cand[i]); masks.push_back(m->search.h_masks[i]); }
     }
     const int na = (int)acc.size();
     for (int l : acc)
@@ -352,18 +321,18 @@ int mcorb_lmap_search(mcorb_lmap *m, const mcorb_lmap_view *view, const int32_t 
         A.nodes = fv.fv_nodes; A.offs = fv.fv_offsets; A.feats = fv.fv_feats;
         matches_host(A, db->probes[probe], max_neighbor_ratio, i1, i2);
     } else if (na) {
-        HIPCHK(hipMemcpyAsync(m->d_cand, acc.data(), (size_t)na * sizeof(int), hipMemcpyHostToDevice, st));
-        launch_kfdb_gather(st, m->d_desc, m->d_cand, na, m->d_adesc);
+        HIPCHK(hipMemcpyAsync(m->search.d_cand, acc.data(), (size_t)na * sizeof(int), hipMemcpyHostToDevice, st));
+        launch_kfdb_gather(st, m->d_desc, m->search.d_cand, na, m->search.d_adesc);
         HIPCHK(hipGetLastError());
-        TRY(vocab_feature_vector(m->voc, m->d_adesc, na, levelsup, st, fv));
+        TRY(vocab_feature_vector(m->voc, m->search.d_adesc, na, levelsup, st, fv));
         // A: the gathered rows and their FeatureVector; B: the probe, with its own base as set 0
         const Place pb = place_of(db, probe, true);
         std::vector<std::vector<uint32_t>> r1, r2;
-        m->best2.reset();
-        m->best2.add_b(fv.fv_nodes, fv.fv_offsets, db->pmirror[probe], 0);
-        if (!m->best2.items.empty())   // (the run's synchronisation covers the pageable list)
-            HIPCHK(hipMemcpyAsync(m->d_afeats, fv.fv_feats.data(), fv.fv_feats.size() * sizeof(int), hipMemcpyHostToDevice, st));
-        TRY(m->best2.run(st, m->d_adesc, m->d_afeats, pb.desc, 0, pb.feats, 0, max_neighbor_ratio, r1, r2, &m->us_best2));
+        m->search.best2.reset();
+        m->search.best2.add_b(fv.fv_nodes, fv.fv_offsets, db->pmirror[probe], 0);
+        if (!m->search.best2.items.empty())   // (the run's synchronisation covers the pageable list)
+            HIPCHK(hipMemcpyAsync(m->search.d_afeats, fv.fv_feats.data(), fv.fv_feats.size() * sizeof(int), hipMemcpyHostToDevice, st));
+        TRY(m->search.best2.run(st, m->search.d_adesc, m->search.d_afeats, pb.desc, 0, pb.feats, 0, max_neighbor_ratio, r1, r2, &m->search.us_best2));
         i1.swap(r1[0]); i2.swap(r2[0]);
     }
 
@@ -395,9 +364,9 @@ int mcorb_lmap_last_timing(mcorb_lmap *m, float us[2], int *n_candidates)
     TRY(check_lmap_handle(m, "lmap last_timing"));
     if (!us) { set_error("lmap last_timing: bad argument"); return MCORB_E_ARG; }
     std::lock_guard<std::mutex> lk(m->mu);
-    us[0] = m->us_cull;
-    us[1] = m->us_best2;
-    if (n_candidates) *n_candidates = m->last_candidates;
+    us[0] = m->search.cull.us[0];
+    us[1] = m->search.us_best2;
+    if (n_candidates) *n_candidates = m->search.last_candidates;
     return MCORB_OK;
 }
 

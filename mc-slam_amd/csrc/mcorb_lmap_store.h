@@ -9,6 +9,7 @@
 
 #include "mcorb_kfdb_store.h"
 #include "mcorb_mapping_new.h"
+#include "mcorb_pack.h"
 #include "mcorb_pose.h"
 #include "mcorb_sac.h"
 #include "mcorb_track.h"
@@ -16,30 +17,29 @@
 namespace mcorb {
 constexpr uint8_t kHasPt = 1, kHasNormal = 2, kHasDesc = 4, kMono = 8, kSet = kHasPt | kHasNormal;
 struct LmObs { int32_t kf_id, feat; };   // one observation of a landmark: KFs[i]'s id, featInds[i]
+
+// a packed input (mcorb_pack.h) on both sides, grow-only: the pinned block the host fills and its place on the device, one copy
+struct Staged {
+    HostBuf<uint8_t> h;
+    DevBuf<uint8_t> d;
+    int reserve(size_t bytes) { TRY(h.grow(bytes, hipHostMallocDefault)); return d.grow(bytes); }
+    int upload(hipStream_t st, size_t bytes) { HIPCHK(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, st)); return MCORB_OK; }
+    template <class T> T *host(size_t off) const { return reinterpret_cast<T *>(h.get() + off); }
+    template <class T> T *dev(size_t off) const { return reinterpret_cast<T *>(d.get() + off); }
+};
+
 // the buffers of a k_pose_refine launch (mcorb_pose.cpp), grow-only: the packed input (the PoseJobs, then -- the explicit entry --
-// the observations and their ids or points; one block, one copy), the observation list a tracking submission's prologue builds,
-// the flags of the observations that are still in, and what the host reads: results and inlier flags, host-mapped
+// the observations and their ids or points: ObsLayout), the observation list a tracking submission's prologue builds, the flags
+// of the observations that are still in, and what the host reads: results and inlier flags, host-mapped
 struct PoseBufs {
-    HostBuf<uint8_t> h_in;
-    DevBuf<uint8_t> d_in;
+    Staged in;
     DevBuf<PoseObs> d_obs;
     DevBuf<int32_t> d_lids;
     DevBuf<uint8_t> d_alive;
     HostBuf<mcorb_pose_result> h_out;
     HostBuf<uint8_t> h_flags;
-};
-// the buffers of a mcorb_lmap_ransac_pose submission (mcorb_sac.cpp), grow-only: the packed input (the PoseJob of the
-// refinement behind it, the SacJob, the observations, their ids or points, the consensus lists and the first-of-match bytes;
-// one block, one copy), the models and counts of the hypotheses, and what the host reads: the pick's record and the flags per
-// observation, host-mapped.  The refinement's own buffers are `pose`
-struct SacBufs {
-    HostBuf<uint8_t> h_in;
-    DevBuf<uint8_t> d_in;
-    DevBuf<SacModel> d_models;
-    DevBuf<int32_t> d_count;
-    HostBuf<SacOut> h_out;
-    HostBuf<uint8_t> h_flags;
-    PoseBufs pose;
+    // the explicit entries: a problem of n observations whose input is elsewhere
+    int reserve(size_t n) { TRY(d_alive.grow(n)); TRY(h_out.grow(1, kHostMapped)); return h_flags.grow(n, kHostMapped); }
 };
 }  // namespace mcorb
 
@@ -50,93 +50,105 @@ struct mcorb_lmap {
     std::vector<uint8_t> flags;      // per slot
     std::vector<int> stamp;          // per slot: the last search (or batch) that saw it
     int tick = 0;
+    // n_rays: the host's copy of every slot's ray count (a device store's kernels read and write d_nrays); obs: per slot the
+    // observations (kf_id, feat) in the order they were added (KFs / featInds)
+    std::vector<int32_t> n_rays;
+    std::vector<std::vector<mcorb::LmObs>> obs;
     // host-only store
     std::vector<double> geom;        // [max_landmarks][6]: pt3D, normal
     std::vector<uint8_t> desc;       // [max_landmarks][32]
     // device store
     mcorb::Stream st;
-    mcorb::Event ev0, ev1;
     mcorb::DevBuf<double> d_geom;
     mcorb::DevBuf<uint8_t> d_desc;
-    mcorb::DevBuf<mcorb_lmap_view> d_view;
-    // scratch of a batch (grow-only) and of a search (max_candidates)
-    mcorb::DevBuf<int> d_blids, d_brows;
-    mcorb::DevBuf<double> d_bpt, d_bnormal;
-    mcorb::DevBuf<uint8_t> d_bdesc;
-    mcorb::DevBuf<int> d_cand, d_afeats;
-    mcorb::DevBuf<uint32_t> d_masks;
-    mcorb::HostBuf<uint32_t> h_masks;
-    mcorb::DevBuf<uint8_t> d_adesc;         // the accepted rows, gathered
-    mcorb::Best2Search best2;
-    float us_cull = 0.f, us_best2 = 0.f;
-    int last_candidates = 0;
-    // scratch of mcorb_lmap_triangulate_neighbours (mcorb_mapping.cpp), grow-only: the packed input (one block, one copy), the
-    // result records, the depth list and the write-back list
-    mcorb::HostBuf<uint8_t> h_mapin;
-    mcorb::DevBuf<uint8_t> d_mapin;
-    mcorb::HostBuf<mcorb::MapOut> h_mapout;
-    mcorb::DevBuf<mcorb::MapOut> d_mapout;
-    mcorb::HostBuf<double> h_mapz;
-    mcorb::DevBuf<double> d_mapz;
-    mcorb::HostBuf<int2> h_mapput;
-    mcorb::DevBuf<int2> d_mapput;
-    mcorb::Event ev2, ev3;
-    float us_map_depth = 0.f, us_map_tri = 0.f;
-    int last_map_launched = 0, last_map_depth = 0;
-    // mcorb_lmap_triangulate_new (mcorb_mapping.cpp) shares the scratch above (ev2 / ev3 around its kernel) and adds the second
-    // half of its records
-    mcorb::HostBuf<mcorb::MapNewExtra> h_mapextra;
-    mcorb::DevBuf<mcorb::MapNewExtra> d_mapextra;
-    float us_map_new = 0.f;
-    int last_map_new_launched = 0;
-    // the landmarks' life (mcorb_landmark.cpp).  n_rays: the host's copy of every slot's ray count (a device store's kernels read
-    // and write d_nrays); obs: per slot the observations (kf_id, feat) in the order they were added (KFs / featInds); occ: per
-    // slot how often a batch has named it so far, zero between calls
-    std::vector<int32_t> n_rays;
-    std::vector<std::vector<mcorb::LmObs>> obs;
-    std::vector<int32_t> occ;
     mcorb::DevBuf<int32_t> d_nrays;
-    mcorb::HostBuf<mcorb::LmObsItem> h_obsitems;
-    mcorb::DevBuf<mcorb::LmObsItem> d_obsitems;
-    mcorb::HostBuf<mcorb::LmUpdItem> h_upditems;
-    mcorb::DevBuf<mcorb::LmUpdItem> d_upditems;
-    mcorb::HostBuf<mcorb::LmUpdOut> h_updout;
-    mcorb::DevBuf<mcorb::LmUpdOut> d_updout;
-    mcorb::HostBuf<int32_t> h_rays;        // a batch of (slot, n_rays) pairs for k_lmap_put_rays: slots, then values
-    mcorb::DevBuf<int32_t> d_rays;
-    mcorb::Event ev4, ev5, ev6, ev7;
-    float us_observe = 0.f, us_update = 0.f;
-    // scratch of mcorb_lmap_track / mcorb_lmap_track_rig_frame (mcorb_track.cpp), grow-only: the packed input (candidates, then --
-    // host arrays only -- the keypoints and the descriptors of every camera; one block, one copy), a rig slot's keypoints
-    // (k_track_points), the projections, validity bytes and gathered points, the queries' results, and what the host tail reads:
-    // the compacted rows and the counts per camera, host-mapped pinned memory k_track_compact writes.  mcorb_lmap_track_rig_frames
-    // uses the same buffers, sized for all its frames: the pinned block holds the TrBatchItems, the views and every frame's
-    // candidates, a frame's block of every per-pair array begins at ncams * (its first candidate), the counts are MCORB_MAX_CAMS
-    // per frame and the keypoints nf * ncams rows
-    mcorb::HostBuf<uint8_t> h_trackin;
-    mcorb::DevBuf<uint8_t> d_trackin;
-    mcorb::DevBuf<float2> d_trackkp;
-    mcorb::DevBuf<float2> d_trackxy;
-    mcorb::DevBuf<uint8_t> d_trackvalid;
-    mcorb::DevBuf<double> d_trackpt;
-    mcorb::HostBuf<double> h_trackpt;
-    mcorb::DevBuf<mcorb::TrBest> d_trackbest;
-    mcorb::HostBuf<mcorb::TrRow> h_trackrows;
-    mcorb::HostBuf<int32_t> h_tracknproj;
-    mcorb::Event ev8, ev9, ev10, ev11, ev12;   // in front of k_track_project | match | compact | behind it | in front of k_track_points
-    float us_track_points = 0.f, us_track_project = 0.f, us_track_match = 0.f, us_track_compact = 0.f;
-    // the de-duplication on the device: per camera the arg-min table (owner, val: cleared in every submission), per (camera,
-    // candidate) the slot and the winner flag, and what the host reads: the matches and their counts, host-mapped as the rows are
-    mcorb::DevBuf<uint32_t> d_trackowner;
-    mcorb::DevBuf<unsigned long long> d_trackval;
-    mcorb::DevBuf<int32_t> d_trackslot;
-    mcorb::DevBuf<uint8_t> d_trackwin;
-    mcorb::HostBuf<mcorb::TrMatch> h_trackmatch;
-    mcorb::HostBuf<int32_t> h_tracknmatch;
-    mcorb::Event ev13;                         // behind k_track_dedup_emit (ev11 is in front of the table's clear)
-    float us_track_dedup = 0.f;
+
+    // scratch of a search (mcorb_lmap.cpp), max_candidates each
+    struct Search {
+        mcorb::DevBuf<mcorb_lmap_view> d_view;
+        mcorb::DevBuf<int> d_cand, d_afeats;
+        mcorb::DevBuf<uint32_t> d_masks;
+        mcorb::HostBuf<uint32_t> h_masks;
+        mcorb::DevBuf<uint8_t> d_adesc;         // the accepted rows, gathered
+        mcorb::Best2Search best2;
+        mcorb::Spans<1> cull;                   // around k_lmap_cull
+        float us_best2 = 0.f;
+        int last_candidates = 0;
+        int create(size_t C)
+        {
+            TRY(cull.create());
+            TRY(best2.create());
+            TRY(d_view.alloc(1));
+            TRY(d_cand.alloc(C));
+            TRY(d_afeats.alloc(C));
+            TRY(d_masks.alloc(C));
+            TRY(h_masks.alloc(C, hipHostMallocDefault));
+            return d_adesc.alloc(C * 32);
+        }
+    } search;
+
+    // a batch of slots on the device (grow-only): what put_device (mcorb_lmap.cpp), mcorb_lmap_observe and mcorb_lmap_depths upload
+    struct Batch {
+        mcorb::DevBuf<int> d_lids, d_rows;
+        mcorb::DevBuf<double> d_pt, d_normal;
+        mcorb::DevBuf<uint8_t> d_desc;
+        // src[0 .. n) into d on st (pageable memory: the caller's synchronisation covers it)
+        template <class T>
+        static int upload(mcorb::DevBuf<T> &d, const T *src, size_t n, hipStream_t st)
+        {
+            TRY(d.grow(n));
+            HIPCHK(hipMemcpyAsync(d, src, n * sizeof(T), hipMemcpyHostToDevice, st));
+            return MCORB_OK;
+        }
+    } batch;
+
+    // scratch of mcorb_lmap_triangulate_neighbours and mcorb_lmap_triangulate_new (mcorb_mapping.cpp), grow-only: the packed input
+    // (MapLayout), the result records -- the second half of triangulate_new's in `extra` --, the depth list and the write-back list
+    struct Mapping {
+        mcorb::Staged in;
+        mcorb::HostBuf<mcorb::MapOut> h_out;
+        mcorb::DevBuf<mcorb::MapOut> d_out;
+        mcorb::HostBuf<mcorb::MapNewExtra> h_extra;
+        mcorb::DevBuf<mcorb::MapNewExtra> d_extra;
+        mcorb::HostBuf<double> h_z;
+        mcorb::DevBuf<double> d_z;
+        mcorb::HostBuf<int2> h_put;
+        mcorb::DevBuf<int2> d_put;
+        enum { kDepth, kTriangulate };
+        mcorb::Spans<2> neigh;                  // triangulate_neighbours: k_map_depth, then k_map_triangulate
+        mcorb::Spans<1> refine_new;             // triangulate_new: k_map_refine_new
+        int last_launched = 0, last_depth = 0, last_new_launched = 0;
+        // a call of nitems records and nz depths; extra: triangulate_new's
+        int reserve(size_t bytes, size_t nitems, size_t nz, bool extra)
+        {
+            TRY(in.reserve(bytes));
+            TRY(h_out.grow(nitems, hipHostMallocDefault));
+            TRY(d_out.grow(nitems));
+            if (extra) {
+                TRY(h_extra.grow(nitems, hipHostMallocDefault));
+                TRY(d_extra.grow(nitems));
+            }
+            TRY(h_z.grow(nz, hipHostMallocDefault));
+            return d_z.grow(nz);
+        }
+    } map;
+
+    // the landmarks' life (mcorb_landmark.cpp).  occ: per slot how often a batch has named it so far, zero between calls
+    struct Life {
+        std::vector<int32_t> occ;
+        mcorb::HostBuf<mcorb::LmObsItem> h_obsitems;
+        mcorb::DevBuf<mcorb::LmObsItem> d_obsitems;
+        mcorb::HostBuf<mcorb::LmUpdItem> h_upditems;
+        mcorb::DevBuf<mcorb::LmUpdItem> d_upditems;
+        mcorb::HostBuf<mcorb::LmUpdOut> h_updout;
+        mcorb::DevBuf<mcorb::LmUpdOut> d_updout;
+        mcorb::HostBuf<int32_t> h_rays;        // a batch of (slot, n_rays) pairs for k_lmap_put_rays: slots, then values
+        mcorb::DevBuf<int32_t> d_rays;
+        mcorb::Spans<1> observe, update;       // around the rounds of k_lmap_observe / k_lmap_update
+    } life;
+
     // a tracking call that was submitted and not yet waited for (mcorb_lmap_track_submit .. mcorb_lmap_track_wait).  While
-    // track_pending is set every other entry refuses (check_lmap) and the scratch above belongs to the call.  launched: a
+    // track.pending is set every other entry refuses (check_lmap) and the tracking scratch belongs to the call.  launched: a
     // device store has work on its stream; points: k_track_points is part of it.  A host-only store keeps its finished result in
     // rows / matches.  A call has nf frames (one, but for mcorb_lmap_track_rig_frames): frame f's candidates are cand[first[f] ..
     // first[f + 1]), its block of rows / matches begins at ncams * first[f], its counts at f * MCORB_MAX_CAMS
@@ -151,26 +163,96 @@ struct mcorb_lmap {
         std::vector<mcorb::TrRow> rows;
         std::vector<mcorb::TrMatch> matches;
         std::vector<int32_t> n_proj, n_match;
-    } track_call;
-    std::atomic<bool> track_pending{false};
-    // the pose refinement (mcorb_pose.cpp): pose_x serves mcorb_lmap_refine_pose, pose_t the refinement behind a tracking
-    // submission (track_refine: mcorb_lmap_set_track_refine), whose results stay readable until the next submission.
-    // track_pose_nf: the frames of the last tracking call if it ran with the option, 0 otherwise
-    mcorb::PoseBufs pose_x, pose_t;
-    mcorb::Event ev14, ev15;                   // in front of and behind k_pose_refine of mcorb_lmap_refine_pose
-    float us_pose = 0.f;
-    bool track_refine = false;
-    mcorb_pose_params track_refine_params = {};
-    int track_pose_nf = 0;
-    // the RANSAC in front of the refinement (mcorb_sac.cpp): ev16 .. ev19 around k_sac_hypotheses, k_sac_score and k_sac_pick
-    mcorb::SacBufs sac;
-    mcorb::Event ev16, ev17, ev18, ev19;
-    float us_sac[3] = {0.f, 0.f, 0.f};
-    int sac_last_hyp = 0;                      // the hypotheses of the last call that ran any (either kind of store)
-    std::vector<int32_t> sac_host_count, sac_host_valid;   // a host-only store's last counts, for mcorb_lmap_last_ransac_counts
+    };
+
+    // scratch of mcorb_lmap_track / mcorb_lmap_track_rig_frame (mcorb_track.cpp), grow-only: the packed input (TrackLayout: the
+    // candidates, then -- host arrays only -- the keypoints and the descriptors of every camera), a rig slot's keypoints
+    // (k_track_points), the projections, validity bytes and gathered points, the queries' results, and what the host tail reads:
+    // the compacted rows and the counts per camera, host-mapped pinned memory k_track_compact writes.  mcorb_lmap_track_rig_frames
+    // uses the same buffers, sized for all its frames: the pinned block is a TrackBatchLayout, a frame's block of every per-pair
+    // array begins at ncams * (its first candidate), the counts are MCORB_MAX_CAMS per frame and the keypoints nf * ncams rows
+    struct Tracking {
+        mcorb::Staged in;
+        mcorb::DevBuf<float2> d_kp, d_xy;
+        mcorb::DevBuf<uint8_t> d_valid;
+        mcorb::DevBuf<double> d_pt;
+        mcorb::HostBuf<double> h_pt;
+        mcorb::DevBuf<mcorb::TrBest> d_best;
+        mcorb::HostBuf<mcorb::TrRow> h_rows;
+        mcorb::HostBuf<int32_t> h_nproj;
+        // the de-duplication on the device: per camera the arg-min table (owner, val: cleared in every submission), per (camera,
+        // candidate) the slot and the winner flag, and what the host reads: the matches and their counts, host-mapped as the rows are
+        mcorb::DevBuf<uint32_t> d_owner;
+        mcorb::DevBuf<unsigned long long> d_val;
+        mcorb::DevBuf<int32_t> d_slot;
+        mcorb::DevBuf<uint8_t> d_win;
+        mcorb::HostBuf<mcorb::TrMatch> h_match;
+        mcorb::HostBuf<int32_t> h_nmatch;
+        // a submission's pieces in stream order: [k_track_points,] k_track_project, _match, _compact, the table's clear with the
+        // three kernels of the de-duplication
+        enum { kPoints, kProject, kMatch, kCompact, kDedup };
+        mcorb::Spans<5> chain;
+        TrackCall call;
+        std::atomic<bool> pending{false};
+        // mcorb_lmap_set_track_refine: the pose refinement behind every submission (pose.t), whose results stay readable until the
+        // next one.  pose_nf: the frames of the last tracking call if it ran with the option, 0 otherwise
+        bool refine = false;
+        mcorb_pose_params refine_params = {};
+        int pose_nf = 0;
 #ifdef MCORB_TRACK_PROF
-    float us_track_phase[5] = {};   // the last call's host phases: candidate walk, submission, wait, de-duplication, output
+        float us_phase[5] = {};   // the last call's host phases: candidate walk, submission, wait, de-duplication, output
 #endif
+        // a submission of nf frames: `bytes` of input, rows = ncams * candidates, `slots` table entries, kp keypoint rows of a
+        // rig slot, pts gathered points (0: none wanted)
+        int reserve(size_t bytes, size_t rows, size_t nf, size_t slots, size_t kp, size_t pts)
+        {
+            TRY(in.reserve(bytes));
+            TRY(d_xy.grow(rows));
+            TRY(d_valid.grow(rows));
+            TRY(d_best.grow(rows));
+            TRY(h_rows.grow(rows, mcorb::kHostMapped));
+            TRY(h_nproj.grow(nf * MCORB_MAX_CAMS, mcorb::kHostMapped));
+            TRY(d_owner.grow(slots));
+            TRY(d_val.grow(slots));
+            TRY(d_slot.grow(rows));
+            TRY(d_win.grow(rows));
+            TRY(h_match.grow(rows, mcorb::kHostMapped));
+            TRY(h_nmatch.grow(nf * MCORB_MAX_CAMS, mcorb::kHostMapped));
+            TRY(d_kp.grow(kp));
+            TRY(d_pt.grow(pts * 3));
+            return h_pt.grow(pts * 3, hipHostMallocDefault);
+        }
+    } track;
+
+    // the pose refinement (mcorb_pose.cpp): x serves mcorb_lmap_refine_pose, t the refinement behind a tracking submission
+    struct Pose {
+        mcorb::PoseBufs x, t;
+        mcorb::Spans<1> refine;                 // around k_pose_refine of mcorb_lmap_refine_pose
+    } pose;
+
+    // the RANSAC in front of the refinement (mcorb_sac.cpp), grow-only: the packed input (ObsLayout with its RANSAC part), the
+    // models and counts of the hypotheses, and what the host reads: the pick's record and the flags per observation, host-mapped.
+    // `pose`: the buffers of the refinement behind it, whose input is part of `in`
+    struct Sac {
+        mcorb::Staged in;
+        mcorb::DevBuf<mcorb::SacModel> d_models;
+        mcorb::DevBuf<int32_t> d_count;
+        mcorb::HostBuf<mcorb::SacOut> h_out;
+        mcorb::HostBuf<uint8_t> h_flags;
+        mcorb::PoseBufs pose;
+        mcorb::Spans<3> kernels;                // k_sac_hypotheses[_rig], k_sac_score, k_sac_pick
+        int last_hyp = 0;                       // the hypotheses of the last call that ran any (either kind of store)
+        std::vector<int32_t> host_count, host_valid;   // a host-only store's last counts, for mcorb_lmap_last_ransac_counts
+        int reserve(size_t bytes, size_t n, size_t H, bool refine)
+        {
+            TRY(in.reserve(bytes));
+            TRY(d_models.grow(H));
+            TRY(d_count.grow(H));
+            TRY(h_out.grow(1, mcorb::kHostMapped));
+            TRY(h_flags.grow(n, mcorb::kHostMapped));
+            return refine ? pose.reserve(n) : MCORB_OK;
+        }
+    } sac;
 };
 
 // the pose refinement behind a tracking call (mcorb_pose.cpp); the caller holds the store's lock and has set track_refine_params.
@@ -188,6 +270,26 @@ int pose_track_submit(mcorb_lmap *m, const mcorb_track_view *views, int nf, cons
 void pose_job_init(PoseJob &job, const mcorb_pose_params &p, int ncams, const mcorb_track_cam *cams, const PoseState &init);
 void pose_run_host(const PoseJob &job, const PoseObs *obs, const double *pts, int n, uint8_t *alive, mcorb_pose_result &res);
 int pose_check_params(const mcorb_pose_params *p);
+// The observation input of mcorb_lmap_refine_pose and mcorb_lmap_ransac_pose (mcorb_pose.cpp): observation i is the keypoint
+// uv[i] of level octave[i] in camera cam[i], of landmark lids[i] or of the point pts[i].  who: the entry's error prefix.
+// obs_check: the arguments, before the lock (nlevels: what an octave may reach; match: ransac_pose's indices or NULL);
+// obs_check_locked: no tracking call is pending and every landmark has a point.  obs_gather: the observations and their points
+// for the serial run.  obs_stage: the observations and their ids or points into a pinned ObsLayout block; obs_enqueue_refine:
+// k_pose_refine on the block's PoseJob, observations and ids or points, the rest of the problem in b
+struct ObsInput {
+    int n;
+    const int32_t *cam;
+    const float *uv;
+    const int32_t *octave, *lids;
+    const double *pts;
+    int ncams;
+    const mcorb_track_cam *cams;
+};
+int obs_check(const mcorb_lmap *m, const ObsInput &in, int nlevels, const int32_t *match, const char *who);
+int obs_check_locked(const mcorb_lmap *m, const ObsInput &in, const char *who);
+void obs_gather(const mcorb_lmap *m, const ObsInput &in, std::vector<PoseObs> &obs, std::vector<double> &X);
+void obs_stage(const ObsInput &in, const ObsLayout &L, const Staged &s);
+void obs_enqueue_refine(const mcorb_lmap *m, const ObsInput &in, const ObsLayout &L, const Staged &s, const PoseBufs &b);
 }  // namespace mcorb
 
 // a new stamp value; the stamps start over before the counter wraps
@@ -208,7 +310,7 @@ inline int check_lmap_handle(const mcorb_lmap *m, const char *who)
 inline int check_lmap(const mcorb_lmap *m, const char *who)
 {
     TRY(check_lmap_handle(m, who));
-    if (m->track_pending.load()) {
+    if (m->track.pending.load()) {
         mcorb::set_error(std::string(who) + ": a submitted tracking call has not been waited for");
         return MCORB_E_STATE;
     }

@@ -26,28 +26,6 @@ using namespace mcorb;
 
 namespace {
 
-size_t align8(size_t x) { return (x + 7) & ~(size_t)7; }
-
-// the packed input of a call (mcorb_mapping.h): offsets into one block
-struct Layout {
-    size_t frames = 0, F = 0, K = 0, sig = 0, mi = 0, kp = 0, blocks = 0, items = 0, zlids = 0, total = 0;
-    MapArgs args(uint8_t *base, MapOut *out, int ncams) const
-    {
-        MapArgs a;
-        a.frames = (const MapFrameDev *)(base + frames);
-        a.mi = (const int32_t *)(base + mi);
-        a.kp = (const MapKp *)(base + kp);
-        a.F = (const double *)(base + F);
-        a.K = (const double *)(base + K);
-        a.inv_sigma2 = (const float *)(base + sig);
-        a.blocks = (const MapBlock *)(base + blocks);
-        a.items = (const MapItem *)(base + items);
-        a.out = out;
-        a.ncams = ncams;
-        return a;
-    }
-};
-
 // the entry that is checking its arguments (one call at a time per thread)
 thread_local const char *g_who = "lmap triangulate_neighbours";
 int bad(const char *what) { set_error(std::string(g_who) + ": " + what); return MCORB_E_ARG; }
@@ -97,6 +75,137 @@ void pack_frame(const mcorb_map_frame &f, MapFrameDev &d, int32_t *mi, size_t &m
         }
         kp_at += (size_t)f.nkps[c];
     }
+}
+
+// a frame's lIds: -1 or a slot of the store
+int check_lids(const mcorb_lmap *m, const mcorb_map_frame &f, const int32_t *lids)
+{
+    for (int i = 0; i < f.nfeat; i++)
+        if (lids[i] < -1 || lids[i] >= m->max_landmarks) return bad("landmark id outside the store");
+    return MCORB_OK;
+}
+
+// the views of a match of feature q of `other` (a neighbour, the previous keyframe) with feature t of the current frame:
+// nv = their count in both frames, nv_cur = in the current frame alone
+int count_views(const mcorb_map_frame &other, const mcorb_map_frame &cur, int q, int t, int nlevels, uint8_t &nv, uint8_t &nv_cur)
+{
+    if (q < 0 || q >= other.nfeat || t < 0 || t >= cur.nfeat) return bad("match index outside a frame");
+    const int v1 = views_of(other, q, nlevels), v2 = views_of(cur, t, nlevels);
+    if (v1 < 0 || v2 < 0) return bad("octave outside nlevels");
+    if (v1 < 1 || v2 < 1) return bad("a matched feature without a view");
+    if (v1 + v2 > MCORB_MAX_CAMS) return bad("a match of more than MCORB_MAX_CAMS views in total (the solver's design limit)");
+    nv = (uint8_t)(v1 + v2);
+    nv_cur = (uint8_t)v2;
+    return MCORB_OK;
+}
+
+// The matches that need a record, as a device store's kernels take them: per segment (a neighbour; the previous keyframe is
+// segment 0) by view count, in blocks of one wave, the matches of at most 4 views first.  Segment s's matches are query[s] /
+// train[s][0 .. n[s]) and lie at moff[s] in nviews and item_of; wanted(s, j): match j of segment s needs a record
+struct MapWork {
+    std::vector<int32_t> item_of;
+    std::vector<MapItem> items;
+    std::vector<MapBlock> blocks;
+    int nblocks_small = 0;
+    template <class Wanted>
+    void order(int nseg, const int32_t *const *query, const int32_t *const *train, const int32_t *n, const size_t *moff,
+               const uint8_t *nviews, Wanted wanted)
+    {
+        std::vector<int> order;
+        for (int pass = 0; pass < 2; pass++) {   // 0: at most 4 views, 1: the rest
+            for (int s = 0; s < nseg; s++) {
+                const uint8_t *nv = nviews + moff[s];
+                order.clear();
+                for (int j = 0; j < n[s]; j++)
+                    if ((nv[j] <= 4) == (pass == 0) && wanted(s, j)) order.push_back(j);
+                std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return nv[a] < nv[b]; });
+                for (size_t k = 0; k < order.size(); k++) {
+                    if (k % kMapBlock == 0)
+                        blocks.push_back(MapBlock{s, (int32_t)items.size(), (int32_t)std::min<size_t>(kMapBlock, order.size() - k)});
+                    const int j = order[k];
+                    item_of[moff[s] + j] = (int32_t)items.size();
+                    items.push_back(MapItem{query[s][j], train[s][j], (int32_t)items.size()});
+                }
+            }
+            if (pass == 0) nblocks_small = (int)blocks.size();
+        }
+    }
+};
+
+// what a frame adds to the packed input: match indices and keypoints
+void count_frame(const mcorb_map_frame &f, size_t &nmi, size_t &nkp)
+{
+    nmi += (size_t)f.nfeat * f.ncams;
+    for (int c = 0; c < f.ncams; c++) nkp += (size_t)f.nkps[c];
+}
+
+// The packed input of a call: a device store's pinned block, reserved with the records (nitems), the depths (nz) and, with
+// `extra`, triangulate_new's second halves; a host vector otherwise.  Filled with the frames (the current one first), K, the
+// level table, the blocks and the items
+int map_block(mcorb_lmap *m, bool on_device, const MapLayout &L, const MapWork &w, size_t nz, bool extra, const mcorb_map_frame *cur,
+              const mcorb_map_frame *others, int n_others, const double *K, const float *inv_sigma2, int nlevels,
+              std::vector<uint8_t> &host_block, uint8_t *&base)
+{
+    if (on_device) {
+        HIPCHK(hipSetDevice(m->device));
+        TRY(m->map.reserve(L.p.total, w.items.size(), nz, extra));
+        base = m->map.in.h;
+    } else {
+        host_block.resize(L.p.total);
+        base = host_block.data();
+    }
+    MapFrameDev *fr = (MapFrameDev *)(base + L.frames);
+    int32_t *mi = (int32_t *)(base + L.mi);
+    MapKp *kp = (MapKp *)(base + L.kp);
+    size_t mi_at = 0, kp_at = 0;
+    pack_frame(*cur, fr[0], mi, mi_at, kp, kp_at);
+    for (int s = 0; s < n_others; s++) pack_frame(others[s], fr[1 + s], mi, mi_at, kp, kp_at);
+    memcpy(base + L.K, K, (size_t)cur->ncams * 9 * sizeof(double));
+    memcpy(base + L.sig, inv_sigma2, (size_t)nlevels * sizeof(float));
+    if (!w.blocks.empty()) memcpy(base + L.blocks, w.blocks.data(), w.blocks.size() * sizeof(MapBlock));
+    if (!w.items.empty()) memcpy(base + L.items, w.items.data(), w.items.size() * sizeof(MapItem));
+    return MCORB_OK;
+}
+
+// what both entries refuse once the walk has counted the new landmarks
+template <class Out>
+int check_new_ids(const mcorb_lmap *m, int32_t next_lid, int ntri, Out *out)
+{
+    out->n_depth = out->n_triangulated = ntri;
+    if (ntri && (size_t)next_lid + (size_t)ntri > (size_t)m->max_landmarks) {
+        set_error(std::string(g_who) + ": new landmark ids beyond max_landmarks");
+        return MCORB_E_CAP;
+    }
+    if (ntri > out->cap_depth) { set_error(std::string(g_who) + ": output too small"); return MCORB_E_CAP; }
+    if (ntri && !out->depth_vec) return bad("bad argument");
+    return MCORB_OK;
+}
+
+// The new landmarks into slots next_lid .. next_lid + ntri: landmark k's record is recs[rec_of[k]] on the host; a device store
+// copies point, normal and ray count from record item_of[k] of d_out device to device (k_map_put)
+int put_landmarks(mcorb_lmap *m, bool on_device, int32_t next_lid, int ntri, const MapOut *recs, const int32_t *rec_of, const int32_t *item_of)
+{
+    if (on_device && ntri) {
+        hipStream_t st = m->st;
+        TRY(m->map.h_put.grow((size_t)ntri, hipHostMallocDefault));
+        TRY(m->map.d_put.grow((size_t)ntri));
+        for (int k = 0; k < ntri; k++) m->map.h_put[k] = make_int2(item_of[k], next_lid + k);
+        HIPCHK(hipMemcpyAsync(m->map.d_put, m->map.h_put, (size_t)ntri * sizeof(int2), hipMemcpyHostToDevice, st));
+        launch_map_put(st, m->map.d_out, m->map.d_put, ntri, m->d_geom, m->d_nrays);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(st));
+    } else {
+        for (int k = 0; k < ntri; k++) {
+            double *g = &m->geom[(size_t)(next_lid + k) * 6];
+            memcpy(g, recs[rec_of[k]].X, 3 * sizeof(double));
+            memcpy(g + 3, recs[rec_of[k]].normal, 3 * sizeof(double));
+        }
+    }
+    for (int k = 0; k < ntri; k++) {
+        m->flags[next_lid + k] |= kSet;
+        m->n_rays[next_lid + k] = recs[rec_of[k]].n_rays;
+    }
+    return MCORB_OK;
 }
 
 double norm3(const double a[3], const double b[3])   // cv::norm(a - b)
@@ -150,6 +259,37 @@ void refine_out(const MapOut *o, const MapNewExtra *e, int n, int32_t *verdict, 
     }
 }
 
+
+template <class T>
+int to_device(DevBuf<T> &d, const T *src, size_t n)
+{
+    TRY(d.alloc(n));
+    HIPCHK(hipMemcpy(d, src, n * sizeof(T), hipMemcpyHostToDevice));
+    return MCORB_OK;
+}
+
+// the case arrays the two selftests share, on the device: n cases of voff[n] views in all
+struct CasesDev {
+    DevBuf<double> X, P, K, c;
+    DevBuf<int32_t> nv1, nv, voff, oct;
+    DevBuf<float> kps, sig;
+    int upload(int n, const std::vector<int32_t> &voff_h, const double *X_h, const int32_t *nv1_h, const int32_t *nv_h, const double *P_h,
+               const double *K_h, const double *centre, const float *kps_h, const int32_t *octave, const float *inv_sigma2, int nlevels)
+    {
+        const size_t N = (size_t)n, V = (size_t)voff_h[n];
+        TRY(to_device(X, X_h, N * 3));
+        TRY(to_device(P, P_h, V * 12));
+        TRY(to_device(K, K_h, V * 9));
+        TRY(to_device(c, centre, V * 3));
+        TRY(to_device(nv1, nv1_h, N));
+        TRY(to_device(nv, nv_h, N));
+        TRY(to_device(voff, voff_h.data(), N + 1));
+        TRY(to_device(oct, octave, V));
+        TRY(to_device(kps, kps_h, V * 2));
+        return to_device(sig, inv_sigma2, (size_t)nlevels);
+    }
+};
+
 }  // namespace
 
 extern "C" {
@@ -173,8 +313,7 @@ int mcorb_lmap_triangulate_neighbours(mcorb_lmap *m, const mcorb_map_frame *cur,
 
     // ---- 1. everything that can be refused is refused before anything runs ----
     TRY(check_frame(*cur, C));
-    for (int i = 0; i < cur->nfeat; i++)
-        if (lids_cur[i] < -1 || lids_cur[i] >= m->max_landmarks) return bad("landmark id outside the store");
+    TRY(check_lids(m, *cur, lids_cur));
     std::vector<size_t> moff((size_t)n_neigh + 1, 0);
     size_t nz = 0;
     for (int s = 0; s < n_neigh; s++) {
@@ -183,9 +322,9 @@ int mcorb_lmap_triangulate_neighbours(mcorb_lmap *m, const mcorb_map_frame *cur,
         if (n_matches[s] < 0 || (n_matches[s] && (!match_query[s] || !match_train[s])) || !F21[s] || (f.nfeat && !lids_neigh[s]))
             return bad("bad argument");
         moff[s + 1] = moff[s] + (size_t)n_matches[s];
+        TRY(check_lids(m, f, lids_neigh[s]));
         for (int i = 0; i < f.nfeat; i++) {
             const int l = lids_neigh[s][i];
-            if (l < -1 || l >= m->max_landmarks) return bad("landmark id outside the store");
             if (l == -1) continue;
             if (!(m->flags[l] & kHasPt)) { set_error("lmap triangulate_neighbours: a neighbour's landmark was never set"); return MCORB_E_STATE; }
             nz++;
@@ -196,136 +335,67 @@ int mcorb_lmap_triangulate_neighbours(mcorb_lmap *m, const mcorb_map_frame *cur,
     std::vector<uint8_t> nviews(total, 0);
     for (int s = 0; s < n_neigh; s++)
         for (int j = 0; j < n_matches[s]; j++) {
-            const int q = match_query[s][j], t = match_train[s][j];
-            if (q < 0 || q >= neigh[s].nfeat || t < 0 || t >= cur->nfeat) return bad("match index outside a frame");
-            const int v1 = views_of(neigh[s], q, nlevels), v2 = views_of(*cur, t, nlevels);
-            if (v1 < 0 || v2 < 0) return bad("octave outside nlevels");
-            if (v1 < 1 || v2 < 1) return bad("a matched feature without a view");
-            if (v1 + v2 > MCORB_MAX_CAMS) return bad("a match of more than MCORB_MAX_CAMS views in total (the solver's design limit)");
-            nviews[moff[s] + j] = (uint8_t)(v1 + v2);
+            uint8_t nv_cur;
+            TRY(count_views(neigh[s], *cur, match_query[s][j], match_train[s][j], nlevels, nviews[moff[s] + j], nv_cur));
         }
     out->n_matches = (int32_t)total;
     if (total > (size_t)out->cap_matches) { set_error("lmap triangulate_neighbours: output too small"); return MCORB_E_CAP; }
     if (total && (!out->inliers || !out->verdict || !out->new_lid || !out->pt3d || !out->normal || !out->dist2 || !out->cos_parallax))
         return bad("bad argument");
 
-    // ---- 2. the matches that need a record, per neighbour by view count: blocks of one wave, <= 4 views first ----
+    // ---- 2. the matches that need a record: both features are free on entry ----
     const bool dev = m->device >= 0;
-    std::vector<int32_t> item_of(total, -1);
-    std::vector<MapItem> items;
-    std::vector<MapBlock> blocks;
-    int nblocks_small = 0;
-    if (dev) {
-        std::vector<int> order;
-        for (int pass = 0; pass < 2; pass++) {   // 0: at most 4 views, 1: the rest
-            for (int s = 0; s < n_neigh; s++) {
-                order.clear();
-                for (int j = 0; j < n_matches[s]; j++) {
-                    const int nv = nviews[moff[s] + j];
-                    if ((nv <= 4) != (pass == 0)) continue;
-                    if (lids_neigh[s][match_query[s][j]] != -1 || lids_cur[match_train[s][j]] != -1) continue;
-                    order.push_back(j);
-                }
-                std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return nviews[moff[s] + a] < nviews[moff[s] + b]; });
-                for (size_t k = 0; k < order.size(); k++) {
-                    if (k % kMapBlock == 0)
-                        blocks.push_back(MapBlock{s, (int32_t)items.size(), (int32_t)std::min<size_t>(kMapBlock, order.size() - k)});
-                    const int j = order[k];
-                    item_of[moff[s] + j] = (int32_t)items.size();
-                    items.push_back(MapItem{match_query[s][j], match_train[s][j], (int32_t)items.size()});
-                }
-            }
-            if (pass == 0) nblocks_small = (int)blocks.size();
-        }
-    }
+    MapWork w;
+    w.item_of.assign(total, -1);
+    if (dev)
+        w.order(n_neigh, match_query, match_train, n_matches, moff.data(), nviews.data(),
+                [&](int s, int j) { return lids_neigh[s][match_query[s][j]] == -1 && lids_cur[match_train[s][j]] == -1; });
+    const std::vector<int32_t> &item_of = w.item_of;
 
-    // ---- 3. the packed input ----
-    Layout L;
-    size_t nmi = (size_t)cur->nfeat * C, nkp = 0;
-    for (int c = 0; c < C; c++) nkp += (size_t)cur->nkps[c];
-    for (int s = 0; s < n_neigh; s++) {
-        nmi += (size_t)neigh[s].nfeat * C;
-        for (int c = 0; c < C; c++) nkp += (size_t)neigh[s].nkps[c];
-    }
+    // ---- 3. the packed input: the current frame, the neighbours, their F tables and the landmarks whose depth is taken ----
+    size_t nmi = 0, nkp = 0;
+    count_frame(*cur, nmi, nkp);
+    for (int s = 0; s < n_neigh; s++) count_frame(neigh[s], nmi, nkp);
     if (nmi > 0x7fffffff || nkp > 0x7fffffff) return bad("frames too large");
-    L.frames = 0;
-    L.F = align8(L.frames + (size_t)(1 + n_neigh) * sizeof(MapFrameDev));
-    L.K = L.F + (size_t)n_neigh * C * C * 9 * sizeof(double);
-    L.sig = L.K + (size_t)C * 9 * sizeof(double);
-    L.mi = align8(L.sig + (size_t)nlevels * sizeof(float));
-    L.kp = align8(L.mi + nmi * sizeof(int32_t));
-    L.blocks = align8(L.kp + nkp * sizeof(MapKp));
-    L.items = align8(L.blocks + blocks.size() * sizeof(MapBlock));
-    L.zlids = align8(L.items + items.size() * sizeof(MapItem));
-    L.total = align8(L.zlids + nz * sizeof(int32_t));
+    const MapLayout L((size_t)(1 + n_neigh), (size_t)n_neigh * C * C * 9, (size_t)C, (size_t)nlevels, nmi, nkp, w.blocks.size(), w.items.size(), nz);
     std::vector<uint8_t> host_block;
     uint8_t *base;
-    if (dev) {
-        HIPCHK(hipSetDevice(m->device));
-        TRY(m->h_mapin.grow(L.total, hipHostMallocDefault));
-        TRY(m->d_mapin.grow(L.total));
-        base = m->h_mapin;
-    } else {
-        host_block.resize(L.total);
-        base = host_block.data();
-    }
-    {
-        MapFrameDev *fr = (MapFrameDev *)(base + L.frames);
-        int32_t *mi = (int32_t *)(base + L.mi);
-        MapKp *kp = (MapKp *)(base + L.kp);
-        size_t mi_at = 0, kp_at = 0;
-        pack_frame(*cur, fr[0], mi, mi_at, kp, kp_at);
-        for (int s = 0; s < n_neigh; s++) {
-            pack_frame(neigh[s], fr[1 + s], mi, mi_at, kp, kp_at);
-            memcpy(base + L.F + (size_t)s * C * C * 9 * sizeof(double), F21[s], (size_t)C * C * 9 * sizeof(double));
-        }
-        memcpy(base + L.K, K, (size_t)C * 9 * sizeof(double));
-        memcpy(base + L.sig, inv_sigma2, (size_t)nlevels * sizeof(float));
-        if (!blocks.empty()) memcpy(base + L.blocks, blocks.data(), blocks.size() * sizeof(MapBlock));
-        if (!items.empty()) memcpy(base + L.items, items.data(), items.size() * sizeof(MapItem));
-        int32_t *zl = (int32_t *)(base + L.zlids);
-        size_t at = 0;
-        for (int s = 0; s < n_neigh; s++)
-            for (int i = 0; i < neigh[s].nfeat; i++)
-                if (lids_neigh[s][i] != -1) zl[at++] = lids_neigh[s][i];
+    TRY(map_block(m, dev, L, w, nz, false, cur, neigh, n_neigh, K, inv_sigma2, nlevels, host_block, base));
+    int32_t *zl = (int32_t *)(base + L.zlids);
+    for (int s = 0; s < n_neigh; s++) {
+        memcpy(base + L.F + (size_t)s * C * C * 9 * sizeof(double), F21[s], (size_t)C * C * 9 * sizeof(double));
+        for (int i = 0; i < neigh[s].nfeat; i++)
+            if (lids_neigh[s][i] != -1) *zl++ = lids_neigh[s][i];
     }
 
     // ---- 4. the depths of the neighbours' landmarks and the records ----
     std::vector<double> z_host;
     const double *z = nullptr;
-    const int nitems = (int)items.size();
+    const int nitems = (int)w.items.size();
     if (dev) {
         hipStream_t st = m->st;
-        TRY(m->h_mapz.grow(nz, hipHostMallocDefault));
-        TRY(m->d_mapz.grow(nz));
-        TRY(m->h_mapout.grow((size_t)nitems, hipHostMallocDefault));
-        TRY(m->d_mapout.grow((size_t)nitems));
-        HIPCHK(hipMemcpyAsync(m->d_mapin, m->h_mapin, L.total, hipMemcpyHostToDevice, st));
-        HIPCHK(hipEventRecord(m->ev0, st));
-        launch_map_depth(st, Rcw, tcw, m->d_geom, (const int *)(m->d_mapin.get() + L.zlids), (int)nz, m->d_mapz);
+        mcorb_lmap::Mapping &b = m->map;
+        TRY(b.in.upload(st, L.p.total));
+        TRY(b.neigh.mark(st, b.kDepth));
+        launch_map_depth(st, Rcw, tcw, m->d_geom, b.in.dev<const int>(L.zlids), (int)nz, b.d_z);
         HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(m->ev1, st));
-        HIPCHK(hipEventRecord(m->ev2, st));
-        launch_map_triangulate(st, L.args(m->d_mapin, m->d_mapout, C), nblocks_small, (int)blocks.size() - nblocks_small);
+        TRY(b.neigh.mark(st, b.kTriangulate));
+        launch_map_triangulate(st, L.args(b.in.d, b.d_out, C), w.nblocks_small, (int)w.blocks.size() - w.nblocks_small);
         HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(m->ev3, st));
-        if (nz) HIPCHK(hipMemcpyAsync(m->h_mapz, m->d_mapz, nz * sizeof(double), hipMemcpyDeviceToHost, st));
-        if (nitems) HIPCHK(hipMemcpyAsync(m->h_mapout, m->d_mapout, (size_t)nitems * sizeof(MapOut), hipMemcpyDeviceToHost, st));
+        TRY(b.neigh.mark(st, b.kTriangulate + 1));
+        if (nz) HIPCHK(hipMemcpyAsync(b.h_z, b.d_z, nz * sizeof(double), hipMemcpyDeviceToHost, st));
+        if (nitems) HIPCHK(hipMemcpyAsync(b.h_out, b.d_out, (size_t)nitems * sizeof(MapOut), hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
-        float ms = 0.f;
-        ev_elapsed(&ms, m->ev0, m->ev1);
-        m->us_map_depth = ms * 1000.f;
-        ev_elapsed(&ms, m->ev2, m->ev3);
-        m->us_map_tri = ms * 1000.f;
-        z = m->h_mapz;
+        b.neigh.read();
+        z = b.h_z;
     } else {
         z_host.resize(nz);
-        const int32_t *zl = (const int32_t *)(base + L.zlids);
+        zl = (int32_t *)(base + L.zlids);
         for (size_t i = 0; i < nz; i++) z_host[i] = map_depth(Rcw, tcw, &m->geom[(size_t)zl[i] * 6]);
         z = z_host.data();
     }
-    m->last_map_launched = nitems;
-    m->last_map_depth = (int)nz;
+    m->map.last_launched = nitems;
+    m->map.last_depth = (int)nz;
 
     // ---- 5. the baseline gate (:4868-4873) and the walk (:5809-5945), neighbours in order, matches in order ----
     std::vector<int32_t> lc(lids_cur, lids_cur + cur->nfeat);
@@ -358,7 +428,7 @@ int mcorb_lmap_triangulate_neighbours(mcorb_lmap *m, const mcorb_map_frame *cur,
             if (ln[s][q] != -1 || lc[t] != -1) { verdict[i] = kMapAssigned; continue; }
             MapOut o_host;
             const MapOut *o;
-            if (dev) o = &m->h_mapout[item_of[i]];
+            if (dev) o = &m->map.h_out[item_of[i]];
             else {
                 MapArgs a = ha;
                 a.out = &o_host;
@@ -378,36 +448,11 @@ int mcorb_lmap_triangulate_neighbours(mcorb_lmap *m, const mcorb_map_frame *cur,
         }
     }
     const int ntri = (int)acc_match.size();
-    out->n_depth = out->n_triangulated = ntri;
-    if (ntri && (size_t)next_lid + (size_t)ntri > (size_t)m->max_landmarks) {
-        set_error("lmap triangulate_neighbours: new landmark ids beyond max_landmarks");
-        return MCORB_E_CAP;
-    }
-    if (ntri > out->cap_depth) { set_error("lmap triangulate_neighbours: output too small"); return MCORB_E_CAP; }
-    if (ntri && !out->depth_vec) return bad("bad argument");
+    TRY(check_new_ids(m, next_lid, ntri, out));
 
     // ---- 6. the new landmarks into their slots, then the caller's arrays ----
-    const MapOut *recs = dev ? m->h_mapout.get() : rec_host.data();
-    if (dev && ntri) {
-        hipStream_t st = m->st;
-        TRY(m->h_mapput.grow((size_t)ntri, hipHostMallocDefault));
-        TRY(m->d_mapput.grow((size_t)ntri));
-        for (int k = 0; k < ntri; k++) m->h_mapput[k] = make_int2(acc_rec[k], next_lid + k);
-        HIPCHK(hipMemcpyAsync(m->d_mapput, m->h_mapput, (size_t)ntri * sizeof(int2), hipMemcpyHostToDevice, st));
-        launch_map_put(st, m->d_mapout, m->d_mapput, ntri, m->d_geom, m->d_nrays);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipStreamSynchronize(st));
-    } else {
-        for (int k = 0; k < ntri; k++) {
-            double *g = &m->geom[(size_t)(next_lid + k) * 6];
-            memcpy(g, recs[acc_rec[k]].X, 3 * sizeof(double));
-            memcpy(g + 3, recs[acc_rec[k]].normal, 3 * sizeof(double));
-        }
-    }
-    for (int k = 0; k < ntri; k++) {
-        m->flags[next_lid + k] |= kSet;
-        m->n_rays[next_lid + k] = recs[acc_rec[k]].n_rays;
-    }
+    const MapOut *recs = dev ? m->map.h_out.get() : rec_host.data();
+    TRY(put_landmarks(m, dev, next_lid, ntri, recs, acc_rec.data(), acc_rec.data()));
     for (size_t i = 0; i < total; i++) {
         out->verdict[i] = verdict[i];
         out->inliers[i] = verdict[i] == kMapLandmark || verdict[i] == kMapParallax;
@@ -449,12 +494,11 @@ int mcorb_lmap_depths(mcorb_lmap *m, const double Rcw[9], const double tcw[3], c
     }
     HIPCHK(hipSetDevice(m->device));
     hipStream_t st = m->st;
-    TRY(m->d_blids.grow((size_t)n));
-    TRY(m->d_mapz.grow((size_t)n));
-    HIPCHK(hipMemcpyAsync(m->d_blids, lids, (size_t)n * sizeof(int), hipMemcpyHostToDevice, st));
-    launch_map_depth(st, Rcw, tcw, m->d_geom, m->d_blids, n, m->d_mapz);
+    TRY(m->map.d_z.grow((size_t)n));
+    TRY(m->batch.upload(m->batch.d_lids, lids, (size_t)n, st));
+    launch_map_depth(st, Rcw, tcw, m->d_geom, m->batch.d_lids, n, m->map.d_z);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(z, m->d_mapz, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(z, m->map.d_z, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));   // (also covers the pageable arrays)
     return MCORB_OK;
 }
@@ -464,10 +508,10 @@ int mcorb_lmap_last_triangulate_timing(mcorb_lmap *m, float us[2], int *n_launch
     TRY(check_lmap_handle(m, "lmap last_triangulate_timing"));
     if (!us) { set_error("lmap last_triangulate_timing: bad argument"); return MCORB_E_ARG; }
     std::lock_guard<std::mutex> lk(m->mu);
-    us[0] = m->us_map_tri;
-    us[1] = m->us_map_depth;
-    if (n_launched) *n_launched = m->last_map_launched;
-    if (n_depth) *n_depth = m->last_map_depth;
+    us[0] = m->map.neigh.us[mcorb_lmap::Mapping::kTriangulate];
+    us[1] = m->map.neigh.us[mcorb_lmap::Mapping::kDepth];
+    if (n_launched) *n_launched = m->map.last_launched;
+    if (n_depth) *n_depth = m->map.last_depth;
     return MCORB_OK;
 }
 
@@ -495,26 +539,14 @@ int mcorb_dev_map_gates_selftest(int device, int n, const double *X, const int32
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) { set_error("no usable HIP device"); return MCORB_E_NODEVICE; }
     HIPCHK(hipSetDevice(device));
-    const size_t N = (size_t)n, V = (size_t)voff[n];
-    DevBuf<double> d_X, d_P, d_K, d_c, d_F;
-    DevBuf<int32_t> d_nv1, d_nv, d_voff, d_oct;
-    DevBuf<float> d_kps, d_sig;
+    const size_t N = (size_t)n;
+    CasesDev d;
+    DevBuf<double> d_F;
     DevBuf<MapOut> d_out;
-    TRY(d_X.alloc(N * 3)); TRY(d_P.alloc(V * 12)); TRY(d_K.alloc(V * 9)); TRY(d_c.alloc(V * 3)); TRY(d_F.alloc(N * 9));
-    TRY(d_nv1.alloc(N)); TRY(d_nv.alloc(N)); TRY(d_voff.alloc(N + 1)); TRY(d_oct.alloc(V));
-    TRY(d_kps.alloc(V * 2)); TRY(d_sig.alloc((size_t)nlevels)); TRY(d_out.alloc(N));
-    HIPCHK(hipMemcpy(d_X, X, N * 3 * sizeof(double), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d_P, P, V * 12 * sizeof(double), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d_K, K, V * 9 * sizeof(double), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d_c, centre, V * 3 * sizeof(double), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d_F, F, N * 9 * sizeof(double), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d_nv1, nv1, N * sizeof(int32_t), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d_nv, nv, N * sizeof(int32_t), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d_voff, voff.data(), (N + 1) * sizeof(int32_t), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d_oct, octave, V * sizeof(int32_t), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d_kps, kps, V * 2 * sizeof(float), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d_sig, inv_sigma2, (size_t)nlevels * sizeof(float), hipMemcpyHostToDevice));
-    const MapGateCases c{d_X, d_nv1, d_nv, d_voff, d_P, d_K, d_c, d_kps, d_oct, d_F, d_sig};
+    TRY(d.upload(n, voff, X, nv1, nv, P, K, centre, kps, octave, inv_sigma2, nlevels));
+    TRY(to_device(d_F, F, N * 9));
+    TRY(d_out.alloc(N));
+    const MapGateCases c{d.X, d.nv1, d.nv, d.voff, d.P, d.K, d.c, d.kps, d.oct, d_F, d.sig};
     launch_map_gates(nullptr, c, n, d_out);
     HIPCHK(hipGetLastError());
     std::vector<MapOut> o(N);
@@ -546,114 +578,54 @@ int mcorb_lmap_triangulate_new(mcorb_lmap *m, const mcorb_map_frame *cur, int32_
     // ---- 1. everything that can be refused is refused before anything runs ----
     TRY(check_frame(*cur, C));
     TRY(check_frame(*prev, C));
-    for (int i = 0; i < cur->nfeat; i++)
-        if (lids_cur[i] < -1 || lids_cur[i] >= m->max_landmarks) return bad("landmark id outside the store");
-    for (int i = 0; i < prev->nfeat; i++)
-        if (lids_prev[i] < -1 || lids_prev[i] >= m->max_landmarks) return bad("landmark id outside the store");
+    TRY(check_lids(m, *cur, lids_cur));
+    TRY(check_lids(m, *prev, lids_prev));
     const size_t total = (size_t)n_matches;
     std::vector<uint8_t> nviews(total, 0), nviews_cur(total, 0);
-    for (int j = 0; j < n_matches; j++) {
-        const int q = match_query[j], t = match_train[j];
-        if (q < 0 || q >= prev->nfeat || t < 0 || t >= cur->nfeat) return bad("match index outside a frame");
-        const int v1 = views_of(*prev, q, nlevels), v2 = views_of(*cur, t, nlevels);
-        if (v1 < 0 || v2 < 0) return bad("octave outside nlevels");
-        if (v1 < 1 || v2 < 1) return bad("a matched feature without a view");
-        if (v1 + v2 > MCORB_MAX_CAMS) return bad("a match of more than MCORB_MAX_CAMS views in total (the solver's design limit)");
-        nviews[j] = (uint8_t)(v1 + v2);
-        nviews_cur[j] = (uint8_t)v2;
-    }
+    for (int j = 0; j < n_matches; j++) TRY(count_views(*prev, *cur, match_query[j], match_train[j], nlevels, nviews[j], nviews_cur[j]));
     out->n_matches = n_matches;
     if (n_matches > out->cap_matches) { set_error("lmap triangulate_new: output too small"); return MCORB_E_CAP; }
     if (total && (!out->inliers || !out->verdict || !out->new_lid || !out->pt3d || !out->normal || !out->dist || !out->cos_parallax ||
                   !out->iterations || !out->cost_initial || !out->cost_final))
         return bad("bad argument");
 
-    // ---- 2. the matches whose current feature is free on entry, by view count: blocks of one wave, <= 4 views first ----
+    // ---- 2. the matches that need a record: the current feature is free on entry ----
     const bool dev = m->device >= 0;
-    std::vector<int32_t> item_of(total, -1);
-    std::vector<MapItem> items;
-    std::vector<MapBlock> blocks;
-    int nblocks_small = 0;
-    if (dev) {
-        std::vector<int> order;
-        for (int pass = 0; pass < 2; pass++) {   // 0: at most 4 views, 1: the rest
-            order.clear();
-            for (int j = 0; j < n_matches; j++) {
-                if ((nviews[j] <= 4) != (pass == 0) || lids_cur[match_train[j]] != -1) continue;
-                order.push_back(j);
-            }
-            std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return nviews[a] < nviews[b]; });
-            for (size_t k = 0; k < order.size(); k++) {
-                if (k % kMapBlock == 0)
-                    blocks.push_back(MapBlock{0, (int32_t)items.size(), (int32_t)std::min<size_t>(kMapBlock, order.size() - k)});
-                const int j = order[k];
-                item_of[j] = (int32_t)items.size();
-                items.push_back(MapItem{match_query[j], match_train[j], (int32_t)items.size()});
-            }
-            if (pass == 0) nblocks_small = (int)blocks.size();
-        }
-    }
-    const int nitems = (int)items.size();
+    MapWork w;
+    w.item_of.assign(total, -1);
+    const size_t moff[2] = {0, total};
+    if (dev) w.order(1, &match_query, &match_train, &n_matches, moff, nviews.data(), [&](int, int j) { return lids_cur[match_train[j]] == -1; });
+    const std::vector<int32_t> &item_of = w.item_of;
+    const int nitems = (int)w.items.size();
 
     // ---- 3. the packed input: the current frame, then the previous keyframe ----
-    Layout L;
-    size_t nmi = ((size_t)cur->nfeat + (size_t)prev->nfeat) * C, nkp = 0;
-    for (int c = 0; c < C; c++) nkp += (size_t)cur->nkps[c] + (size_t)prev->nkps[c];
+    size_t nmi = 0, nkp = 0;
+    count_frame(*cur, nmi, nkp);
+    count_frame(*prev, nmi, nkp);
     if (nmi > 0x7fffffff || nkp > 0x7fffffff) return bad("frames too large");
-    L.frames = 0;
-    L.F = align8(L.frames + 2 * sizeof(MapFrameDev));
-    L.K = L.F;
-    L.sig = L.K + (size_t)C * 9 * sizeof(double);
-    L.mi = align8(L.sig + (size_t)nlevels * sizeof(float));
-    L.kp = align8(L.mi + nmi * sizeof(int32_t));
-    L.blocks = align8(L.kp + nkp * sizeof(MapKp));
-    L.items = align8(L.blocks + blocks.size() * sizeof(MapBlock));
-    L.zlids = L.total = align8(L.items + items.size() * sizeof(MapItem));
+    const MapLayout L(2, 0, (size_t)C, (size_t)nlevels, nmi, nkp, w.blocks.size(), w.items.size(), 0);
     std::vector<uint8_t> host_block;
     uint8_t *base;
-    if (dev && nitems) {
-        HIPCHK(hipSetDevice(m->device));
-        TRY(m->h_mapin.grow(L.total, hipHostMallocDefault));
-        TRY(m->d_mapin.grow(L.total));
-        base = m->h_mapin;
-    } else {
-        host_block.resize(L.total);
-        base = host_block.data();
-    }
-    {
-        MapFrameDev *fr = (MapFrameDev *)(base + L.frames);
-        size_t mi_at = 0, kp_at = 0;
-        pack_frame(*cur, fr[0], (int32_t *)(base + L.mi), mi_at, (MapKp *)(base + L.kp), kp_at);
-        pack_frame(*prev, fr[1], (int32_t *)(base + L.mi), mi_at, (MapKp *)(base + L.kp), kp_at);
-        memcpy(base + L.K, K, (size_t)C * 9 * sizeof(double));
-        memcpy(base + L.sig, inv_sigma2, (size_t)nlevels * sizeof(float));
-        if (!blocks.empty()) memcpy(base + L.blocks, blocks.data(), blocks.size() * sizeof(MapBlock));
-        if (!items.empty()) memcpy(base + L.items, items.data(), items.size() * sizeof(MapItem));
-    }
+    TRY(map_block(m, dev && nitems, L, w, 0, true, cur, prev, 1, K, inv_sigma2, nlevels, host_block, base));
     MapNewArgs na;
     for (int k = 0; k < 3; k++) { na.twc_cur[k] = cur->twc[k]; na.twc_prev[k] = prev->twc[k]; }
 
     // ---- 4. the records: one submission ----
     if (dev && nitems) {
         hipStream_t st = m->st;
-        TRY(m->h_mapout.grow((size_t)nitems, hipHostMallocDefault));
-        TRY(m->d_mapout.grow((size_t)nitems));
-        TRY(m->h_mapextra.grow((size_t)nitems, hipHostMallocDefault));
-        TRY(m->d_mapextra.grow((size_t)nitems));
-        na.a = L.args(m->d_mapin, m->d_mapout, C);
-        na.extra = m->d_mapextra;
-        HIPCHK(hipMemcpyAsync(m->d_mapin, m->h_mapin, L.total, hipMemcpyHostToDevice, st));
-        HIPCHK(hipEventRecord(m->ev2, st));
-        launch_map_refine_new(st, na, nblocks_small, (int)blocks.size() - nblocks_small);
+        mcorb_lmap::Mapping &b = m->map;
+        na.a = L.args(b.in.d, b.d_out, C);
+        na.extra = b.d_extra;
+        TRY(b.in.upload(st, L.p.total));
+        TRY(b.refine_new.mark(st, 0));
+        launch_map_refine_new(st, na, w.nblocks_small, (int)w.blocks.size() - w.nblocks_small);
         HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(m->ev3, st));
-        HIPCHK(hipMemcpyAsync(m->h_mapout, m->d_mapout, (size_t)nitems * sizeof(MapOut), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(m->h_mapextra, m->d_mapextra, (size_t)nitems * sizeof(MapNewExtra), hipMemcpyDeviceToHost, st));
+        TRY(b.refine_new.mark(st, 1));
+        HIPCHK(hipMemcpyAsync(b.h_out, b.d_out, (size_t)nitems * sizeof(MapOut), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(b.h_extra, b.d_extra, (size_t)nitems * sizeof(MapNewExtra), hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
-        float ms = 0.f;
-        ev_elapsed(&ms, m->ev2, m->ev3);
-        m->us_map_new = ms * 1000.f;
-        m->last_map_new_launched = nitems;
+        b.refine_new.read();
+        b.last_new_launched = nitems;
     }
 
     // ---- 5. the walk (:6476-6491, :6673-6690): matches in order, only the current frame's id is tested ----
@@ -668,7 +640,7 @@ int mcorb_lmap_triangulate_new(mcorb_lmap *m, const mcorb_map_frame *cur, int32_
         const int q = match_query[j], t = match_train[j];
         new_clear(rec[j], ext[j]);
         if (lc[t] != -1) { rec[j].verdict = kMapAssigned; by_verdict[kMapAssigned]++; continue; }
-        if (dev) { rec[j] = m->h_mapout[item_of[j]]; ext[j] = m->h_mapextra[item_of[j]]; }
+        if (dev) { rec[j] = m->map.h_out[item_of[j]]; ext[j] = m->map.h_extra[item_of[j]]; }
         else {
             na.a.out = &rec[j];
             na.extra = &ext[j];
@@ -683,35 +655,12 @@ int mcorb_lmap_triangulate_new(mcorb_lmap *m, const mcorb_map_frame *cur, int32_
         hist[nviews_cur[j] - 1]++;
     }
     const int ntri = (int)acc_match.size();
-    out->n_depth = out->n_triangulated = ntri;
-    if (ntri && (size_t)next_lid + (size_t)ntri > (size_t)m->max_landmarks) {
-        set_error("lmap triangulate_new: new landmark ids beyond max_landmarks");
-        return MCORB_E_CAP;
-    }
-    if (ntri > out->cap_depth) { set_error("lmap triangulate_new: output too small"); return MCORB_E_CAP; }
-    if (ntri && !out->depth_vec) return bad("bad argument");
+    TRY(check_new_ids(m, next_lid, ntri, out));
 
     // ---- 6. the new landmarks into their slots, then the caller's arrays ----
-    if (dev && ntri) {
-        hipStream_t st = m->st;
-        TRY(m->h_mapput.grow((size_t)ntri, hipHostMallocDefault));
-        TRY(m->d_mapput.grow((size_t)ntri));
-        for (int k = 0; k < ntri; k++) m->h_mapput[k] = make_int2(item_of[acc_match[k]], next_lid + k);
-        HIPCHK(hipMemcpyAsync(m->d_mapput, m->h_mapput, (size_t)ntri * sizeof(int2), hipMemcpyHostToDevice, st));
-        launch_map_put(st, m->d_mapout, m->d_mapput, ntri, m->d_geom, m->d_nrays);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipStreamSynchronize(st));
-    } else {
-        for (int k = 0; k < ntri; k++) {
-            double *g = &m->geom[(size_t)(next_lid + k) * 6];
-            memcpy(g, rec[acc_match[k]].X, 3 * sizeof(double));
-            memcpy(g + 3, rec[acc_match[k]].normal, 3 * sizeof(double));
-        }
-    }
-    for (int k = 0; k < ntri; k++) {
-        m->flags[next_lid + k] |= kSet;
-        m->n_rays[next_lid + k] = rec[acc_match[k]].n_rays;
-    }
+    std::vector<int32_t> acc_item((size_t)ntri);
+    for (int k = 0; k < ntri; k++) acc_item[k] = item_of[acc_match[k]];
+    TRY(put_landmarks(m, dev, next_lid, ntri, rec.data(), acc_match.data(), acc_item.data()));
     for (size_t i = 0; i < total; i++) {
         const MapOut &o = rec[i];
         const bool lm = o.verdict == kMapLandmark;
@@ -743,8 +692,8 @@ int mcorb_lmap_last_triangulate_new_timing(mcorb_lmap *m, float us[1], int *n_la
     TRY(check_lmap_handle(m, "lmap last_triangulate_new_timing"));
     if (!us) { set_error("lmap last_triangulate_new_timing: bad argument"); return MCORB_E_ARG; }
     std::lock_guard<std::mutex> lk(m->mu);
-    us[0] = m->us_map_new;
-    if (n_launched) *n_launched = m->last_map_new_launched;
+    us[0] = m->map.refine_new.us[0];
+    if (n_launched) *n_launched = m->map.last_new_launched;
     return MCORB_OK;
 }
 
@@ -775,28 +724,17 @@ int mcorb_dev_map_refine_selftest(int device, int n, const double *X0, const int
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) { set_error("no usable HIP device"); return MCORB_E_NODEVICE; }
     HIPCHK(hipSetDevice(device));
-    const size_t N = (size_t)n, V = (size_t)voff[n];
-    DevBuf<double> d_X, d_P, d_K, d_c, d_tc, d_tp;
-    DevBuf<int32_t> d_nv1, d_nv, d_voff, d_oct;
-    DevBuf<float> d_kps, d_sig;
+    const size_t N = (size_t)n;
+    CasesDev d;
+    DevBuf<double> d_tc, d_tp;
     DevBuf<MapOut> d_out;
     DevBuf<MapNewExtra> d_ext;
-    TRY(d_X.alloc(N * 3)); TRY(d_P.alloc(V * 12)); TRY(d_K.alloc(V * 9)); TRY(d_c.alloc(V * 3)); TRY(d_tc.alloc(N * 3)); TRY(d_tp.alloc(N * 3));
-    TRY(d_nv1.alloc(N)); TRY(d_nv.alloc(N)); TRY(d_voff.alloc(N + 1)); TRY(d_oct.alloc(V));
-    TRY(d_kps.alloc(V * 2)); TRY(d_sig.alloc((size_t)nlevels)); TRY(d_out.alloc(N)); TRY(d_ext.alloc(N));
-    HIPCHK(hipMemcpy(d_X, X0, N * 3 * sizeof(double), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d_P, P, V * 12 * sizeof(double), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d_K, K, V * 9 * sizeof(double), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d_c, centre, V * 3 * sizeof(double), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d_tc, twc_cur, N * 3 * sizeof(double), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d_tp, twc_prev, N * 3 * sizeof(double), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d_nv1, nv1, N * sizeof(int32_t), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d_nv, nv, N * sizeof(int32_t), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d_voff, voff.data(), (N + 1) * sizeof(int32_t), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d_oct, octave, V * sizeof(int32_t), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d_kps, kps, V * 2 * sizeof(float), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d_sig, inv_sigma2, (size_t)nlevels * sizeof(float), hipMemcpyHostToDevice));
-    const MapRefineCases c{d_X, d_nv1, d_nv, d_voff, d_P, d_K, d_c, d_kps, d_oct, d_tc, d_tp, d_sig};
+    TRY(d.upload(n, voff, X0, nv1, nv, P, K, centre, kps, octave, inv_sigma2, nlevels));
+    TRY(to_device(d_tc, twc_cur, N * 3));
+    TRY(to_device(d_tp, twc_prev, N * 3));
+    TRY(d_out.alloc(N));
+    TRY(d_ext.alloc(N));
+    const MapRefineCases c{d.X, d.nv1, d.nv, d.voff, d.P, d.K, d.c, d.kps, d.oct, d_tc, d_tp, d.sig};
     launch_map_refine_cases(nullptr, c, n, d_out, d_ext);
     HIPCHK(hipGetLastError());
     std::vector<MapOut> o(N);

@@ -1,0 +1,78 @@
+// mcorb_pack.h -- the packed inputs of the local map's calls: every call that uploads several arrays puts them into one pinned
+// block and copies it once (Staged, mcorb_lmap_store.h).  Pack hands out the items' offsets; the layouts below are the blocks the
+// library builds, one per call.  No HIP here: tests/cpp/test_pack_sanitize.cpp includes this file from a plain g++ program.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+#include "mcorb_mapping.h"
+#include "mcorb_sac.h"
+
+namespace mcorb {
+
+// offsets into one block, item by item: every item begins at a multiple of kAlign, an item of no elements takes no space
+struct Pack {
+    static constexpr size_t kAlign = 32;
+    size_t total = 0;
+    template <class T>
+    size_t add(size_t n)
+    {
+        const size_t off = total;
+        total += (n * sizeof(T) + kAlign - 1) & ~(kAlign - 1);
+        return off;
+    }
+};
+
+// The layouts: a Pack and the offsets of its items, added in the order the members are declared (total: p.total).
+// mcorb_lmap_refine_pose and mcorb_lmap_ransac_pose: the PoseJob of the refinement, the observations and their ids (lids) or
+// points; sac: the SacJob and the lists the draws index (S consensus observations, ncams + 1 firsts, a byte per observation)
+struct ObsLayout {
+    Pack p;
+    size_t pose_job, sac_job, obs, pt, cons, cam_first, cam_cons, is_first;
+    ObsLayout(size_t n, bool lids, bool sac, size_t S, size_t ncams)
+        : pose_job(p.add<PoseJob>(1)), sac_job(p.add<SacJob>(sac ? 1 : 0)), obs(p.add<PoseObs>(n)),
+          pt(lids ? p.add<int32_t>(n) : p.add<double>(3 * n)), cons(p.add<int32_t>(sac ? S : 0)),
+          cam_first(p.add<int32_t>(sac ? ncams + 1 : 0)), cam_cons(p.add<int32_t>(sac ? S : 0)), is_first(p.add<uint8_t>(sac ? n : 0)) {}
+};
+
+// a tracking submission of one frame: the candidates, then -- host arrays only -- the keypoints (x, y) and descriptors of all cameras
+struct TrackLayout {
+    Pack p;
+    size_t cand, xy, desc;
+    TrackLayout(size_t nc, size_t total_kp) : cand(p.add<int32_t>(nc)), xy(p.add<float>(2 * total_kp)), desc(p.add<uint8_t>(32 * total_kp)) {}
+};
+
+// a tracking submission of nf frames of a rig slot: a TrBatchItem and a view per frame, then every frame's candidates
+struct TrackBatchLayout {
+    Pack p;
+    size_t items, views, cand;
+    TrackBatchLayout(size_t nf, size_t ncand) : items(p.add<TrBatchItem>(nf)), views(p.add<mcorb_track_view>(nf)), cand(p.add<int32_t>(ncand)) {}
+};
+
+// the two mapping entries (mcorb_mapping.h): nframes frames, nF doubles of F tables (none: mcorb_lmap_triangulate_new), K per
+// camera, the level table, the frames' match indices and keypoints, the blocks and items, and the nz landmarks whose depth is taken
+struct MapLayout {
+    Pack p;
+    size_t frames, F, K, sig, mi, kp, blocks, items, zlids;
+    MapLayout(size_t nframes, size_t nF, size_t ncams, size_t nlevels, size_t nmi, size_t nkp, size_t nblocks, size_t nitems, size_t nz)
+        : frames(p.add<MapFrameDev>(nframes)), F(p.add<double>(nF)), K(p.add<double>(ncams * 9)), sig(p.add<float>(nlevels)),
+          mi(p.add<int32_t>(nmi)), kp(p.add<MapKp>(nkp)), blocks(p.add<MapBlock>(nblocks)), items(p.add<MapItem>(nitems)),
+          zlids(p.add<int32_t>(nz)) {}
+    MapArgs args(uint8_t *base, MapOut *out, int ncams) const
+    {
+        MapArgs a;
+        a.frames = (const MapFrameDev *)(base + frames);
+        a.mi = (const int32_t *)(base + mi);
+        a.kp = (const MapKp *)(base + kp);
+        a.F = (const double *)(base + F);
+        a.K = (const double *)(base + K);
+        a.inv_sigma2 = (const float *)(base + sig);
+        a.blocks = (const MapBlock *)(base + blocks);
+        a.items = (const MapItem *)(base + items);
+        a.out = out;
+        a.ncams = ncams;
+        return a;
+    }
+};
+
+}  // namespace mcorb

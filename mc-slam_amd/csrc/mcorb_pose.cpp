@@ -19,16 +19,6 @@ namespace {
 
 int fail(int code, const char *what) { set_error(std::string("lmap pose: ") + what); return code; }
 
-size_t round32(size_t n) { return (n + 31) & ~(size_t)31; }
-
-int check_params(const mcorb_pose_params *p)
-{
-    if (!p) return fail(MCORB_E_ARG, "bad argument");
-    if (p->nlevels < 1 || p->nlevels > MCORB_MAX_LEVELS) return fail(MCORB_E_ARG, "1 .. MCORB_MAX_LEVELS levels");
-    if (p->max_iterations < 1 || p->max_iterations > 100) return fail(MCORB_E_ARG, "1 .. 100 iterations");
-    return MCORB_OK;
-}
-
 // the serial pass of a host-only store: lane l adds observations l, l + 256, .. and the lanes fold as the workgroup does
 struct HostPass {
     const PoseJob &job;
@@ -54,7 +44,13 @@ struct HostPass {
 
 namespace mcorb {
 
-int pose_check_params(const mcorb_pose_params *p) { return check_params(p); }
+int pose_check_params(const mcorb_pose_params *p)
+{
+    if (!p) return fail(MCORB_E_ARG, "bad argument");
+    if (p->nlevels < 1 || p->nlevels > MCORB_MAX_LEVELS) return fail(MCORB_E_ARG, "1 .. MCORB_MAX_LEVELS levels");
+    if (p->max_iterations < 1 || p->max_iterations > 100) return fail(MCORB_E_ARG, "1 .. 100 iterations");
+    return MCORB_OK;
+}
 
 void pose_job_init(PoseJob &job, const mcorb_pose_params &p, int ncams, const mcorb_track_cam *cams, const PoseState &init)
 {
@@ -94,13 +90,71 @@ void pose_run_host(const PoseJob &job, const PoseObs *obs, const double *pts, in
     for (int i = 0; i < n; i++) res.n_inliers += alive[i];
 }
 
+// ---- the observation input of the two explicit entries (mcorb_lmap_refine_pose, mcorb_lmap_ransac_pose) ----
+static int obs_fail(const char *who, int code, const char *what) { set_error(std::string(who) + what); return code; }
+
+int obs_check(const mcorb_lmap *m, const ObsInput &in, int nlevels, const int32_t *match, const char *who)
+{
+    const int n = in.n;
+    if (n < 0 || !in.cams || (n && (!in.cam || !in.uv || !in.octave))) return obs_fail(who, MCORB_E_ARG, "bad argument");
+    if (in.ncams < 1 || in.ncams > MCORB_MAX_CAMS) return obs_fail(who, MCORB_E_ARG, "1 .. MCORB_MAX_CAMS cameras");
+    if ((in.lids != nullptr) == (in.pts != nullptr)) return obs_fail(who, MCORB_E_ARG, "exactly one of lids and pts");
+    for (int i = 0; i < n; i++) {
+        if (in.cam[i] < 0 || in.cam[i] >= in.ncams) return obs_fail(who, MCORB_E_ARG, "a camera index outside the rig");
+        if (in.octave[i] < 0 || in.octave[i] >= nlevels) return obs_fail(who, MCORB_E_ARG, "an octave outside the levels");
+        if (in.lids && (in.lids[i] < 0 || in.lids[i] >= m->max_landmarks)) return obs_fail(who, MCORB_E_ARG, "landmark id outside the store");
+        if (match && (match[i] < 0 || (i && match[i] < match[i - 1])))
+            return obs_fail(who, MCORB_E_ARG, "a match index that is negative or decreases");
+    }
+    return MCORB_OK;
+}
+
+int obs_check_locked(const mcorb_lmap *m, const ObsInput &in, const char *who)
+{
+    if (m->track.pending.load()) return obs_fail(who, MCORB_E_STATE, "a submitted tracking call has not been waited for");
+    if (in.lids)
+        for (int i = 0; i < in.n; i++)
+            if (!(m->flags[in.lids[i]] & kHasPt)) return obs_fail(who, MCORB_E_STATE, "a landmark has no point");
+    return MCORB_OK;
+}
+
+static void obs_rows(const ObsInput in, PoseObs *obs)   // (by value: the stores to obs cannot be stores to its fields)
+{
+    for (int i = 0; i < in.n; i++) obs[i] = PoseObs{in.uv[2 * i], in.uv[2 * i + 1], in.cam[i], in.octave[i]};
+}
+
+void obs_gather(const mcorb_lmap *m, const ObsInput &in, std::vector<PoseObs> &obs, std::vector<double> &X)
+{
+    obs.resize((size_t)in.n);
+    X.resize((size_t)in.n * 3);
+    obs_rows(in, obs.data());
+    for (int i = 0; i < in.n; i++)
+        memcpy(&X[3 * (size_t)i], in.lids ? &m->geom[(size_t)in.lids[i] * 6] : in.pts + 3 * (size_t)i, 3 * sizeof(double));
+}
+
+void obs_stage(const ObsInput &in, const ObsLayout &L, const Staged &s)
+{
+    obs_rows(in, s.host<PoseObs>(L.obs));
+    if (in.lids)
+        memcpy(s.host<int32_t>(L.pt), in.lids, (size_t)in.n * sizeof(int32_t));
+    else
+        memcpy(s.host<double>(L.pt), in.pts, (size_t)in.n * 3 * sizeof(double));
+}
+
+void obs_enqueue_refine(const mcorb_lmap *m, const ObsInput &in, const ObsLayout &L, const Staged &s, const PoseBufs &b)
+{
+    launch_pose_refine(m->st, s.dev<const PoseJob>(L.pose_job), 1, s.dev<PoseObs>(L.obs), in.lids ? s.dev<int32_t>(L.pt) : nullptr,
+                       in.lids ? nullptr : s.dev<const double>(L.pt), m->d_geom, b.d_alive, nullptr, nullptr, nullptr, nullptr, b.h_out,
+                       b.h_flags);
+}
+
 // ---- behind a tracking call (mcorb_track.cpp; the caller holds the store's lock) ----
 // the job of frame f of the pending call: the rig and the initial pose of its view
 static void track_job(const mcorb_lmap *m, const mcorb_track_view &view, PoseJob &job)
 {
     PoseState init;
     pose_of_view(view.R0, view.t0, init);
-    pose_job_init(job, m->track_refine_params, view.ncams, view.cams, init);
+    pose_job_init(job, m->track.refine_params, view.ncams, view.cams, init);
 }
 
 // a host-only store, or a frame for which nothing was launched: the observations from the frame's matches (cand, matches and
@@ -128,18 +182,17 @@ void pose_track_host(mcorb_lmap *m, const mcorb_track_view &view, const int *can
 int pose_track_submit(mcorb_lmap *m, const mcorb_track_view *views, int nf, const size_t *first, const TrFrame *frames, const size_t *kp0,
                       const float2 *kp_xy, const int *d_cand)
 {
-    PoseBufs &b = m->pose_t;
+    PoseBufs &b = m->pose.t;
     const int C = views[0].ncams;
     const size_t rows = (size_t)C * first[nf];
     const size_t bytes = (size_t)nf * sizeof(PoseJob);
-    TRY(b.h_in.grow(bytes, hipHostMallocDefault));
-    TRY(b.d_in.grow(bytes));
+    TRY(b.in.reserve(bytes));
     TRY(b.d_obs.grow(rows));
     TRY(b.d_lids.grow(rows));
     TRY(b.d_alive.grow(rows));
     TRY(b.h_out.grow((size_t)nf, kHostMapped));
     TRY(b.h_flags.grow(rows, kHostMapped));
-    PoseJob *jobs = reinterpret_cast<PoseJob *>(b.h_in.get());
+    PoseJob *jobs = b.in.host<PoseJob>(0);
     for (int f = 0; f < nf; f++) {
         PoseJob &job = jobs[f];
         track_job(m, views[f], job);
@@ -151,9 +204,9 @@ int pose_track_submit(mcorb_lmap *m, const mcorb_track_view *views, int nf, cons
         job.kp0 = kp0[f];
         job.frame = frames[f];
     }
-    HIPCHK(hipMemcpyAsync(b.d_in, b.h_in, bytes, hipMemcpyHostToDevice, m->st));
-    launch_pose_refine(m->st, reinterpret_cast<const PoseJob *>(b.d_in.get()), nf, b.d_obs, b.d_lids, nullptr, m->d_geom, b.d_alive,
-                       m->d_trackwin, m->d_trackbest, d_cand, kp_xy, b.h_out, b.h_flags);
+    TRY(b.in.upload(m->st, bytes));
+    launch_pose_refine(m->st, b.in.dev<const PoseJob>(0), nf, b.d_obs, b.d_lids, nullptr, m->d_geom, b.d_alive,
+                       m->track.d_win, m->track.d_best, d_cand, kp_xy, b.h_out, b.h_flags);
     HIPCHK(hipGetLastError());
     return MCORB_OK;
 }
@@ -166,21 +219,14 @@ int mcorb_lmap_refine_pose(mcorb_lmap *m, int n, const int32_t *cam, const float
                            const double *pts, int ncams, const mcorb_track_cam *cams, const double *R, const double *t,
                            const mcorb_pose_params *params, mcorb_pose_result *res, uint8_t *inlier)
 {
+    const char *who = "lmap pose: ";
     TRY(check_lmap(m, "lmap refine_pose"));
-    if (n < 0 || !cams || !R || !t || !res || (n && (!cam || !uv || !octave))) return fail(MCORB_E_ARG, "bad argument");
-    if (ncams < 1 || ncams > MCORB_MAX_CAMS) return fail(MCORB_E_ARG, "1 .. MCORB_MAX_CAMS cameras");
-    TRY(check_params(params));
-    if ((lids != nullptr) == (pts != nullptr)) return fail(MCORB_E_ARG, "exactly one of lids and pts");
-    for (int i = 0; i < n; i++) {
-        if (cam[i] < 0 || cam[i] >= ncams) return fail(MCORB_E_ARG, "a camera index outside the rig");
-        if (octave[i] < 0 || octave[i] >= params->nlevels) return fail(MCORB_E_ARG, "an octave outside the levels");
-        if (lids && (lids[i] < 0 || lids[i] >= m->max_landmarks)) return fail(MCORB_E_ARG, "landmark id outside the store");
-    }
+    if (!R || !t || !res) return fail(MCORB_E_ARG, "bad argument");
+    TRY(pose_check_params(params));
+    const ObsInput in{n, cam, uv, octave, lids, pts, ncams, cams};
+    TRY(obs_check(m, in, params->nlevels, nullptr, who));
     std::lock_guard<std::mutex> lk(m->mu);
-    if (m->track_pending.load()) return fail(MCORB_E_STATE, "a submitted tracking call has not been waited for");
-    if (lids)
-        for (int i = 0; i < n; i++)
-            if (!(m->flags[lids[i]] & kHasPt)) return fail(MCORB_E_STATE, "a landmark has no point");
+    TRY(obs_check_locked(m, in, who));
     PoseJob job;
     PoseState init;
     memcpy(init.R, R, sizeof(init.R));
@@ -188,49 +234,31 @@ int mcorb_lmap_refine_pose(mcorb_lmap *m, int n, const int32_t *cam, const float
     pose_job_init(job, *params, ncams, cams, init);
     job.n = n;
     if (m->device < 0 || n == 0) {
-        std::vector<PoseObs> obs((size_t)n);
-        std::vector<double> X((size_t)n * 3);
+        std::vector<PoseObs> obs;
+        std::vector<double> X;
         std::vector<uint8_t> alive((size_t)n);
-        for (int i = 0; i < n; i++) {
-            obs[i] = PoseObs{uv[2 * i], uv[2 * i + 1], cam[i], octave[i]};
-            memcpy(&X[3 * (size_t)i], lids ? &m->geom[(size_t)lids[i] * 6] : pts + 3 * (size_t)i, 3 * sizeof(double));
-        }
+        obs_gather(m, in, obs, X);
         pose_run_host(job, obs.data(), X.data(), n, alive.data(), *res);
         if (inlier && n) memcpy(inlier, alive.data(), (size_t)n);
         return MCORB_OK;
     }
-    PoseBufs &b = m->pose_x;
+    PoseBufs &b = m->pose.x;
     HIPCHK(hipSetDevice(m->device));
     (void)hipGetLastError();   // (a stale error of this thread is not this call's)
-    const size_t off_obs = round32(sizeof(PoseJob)), off_pt = off_obs + round32((size_t)n * sizeof(PoseObs));
-    const size_t bytes = off_pt + (size_t)n * (lids ? sizeof(int32_t) : 3 * sizeof(double));
-    TRY(b.h_in.grow(bytes, hipHostMallocDefault));
-    TRY(b.d_in.grow(bytes));
-    TRY(b.d_alive.grow((size_t)n));
-    TRY(b.h_out.grow(1, kHostMapped));
-    TRY(b.h_flags.grow((size_t)n, kHostMapped));
-    uint8_t *in = b.h_in;
-    memcpy(in, &job, sizeof(job));
-    PoseObs *obs = reinterpret_cast<PoseObs *>(in + off_obs);
-    for (int i = 0; i < n; i++) obs[i] = PoseObs{uv[2 * i], uv[2 * i + 1], cam[i], octave[i]};
-    if (lids)
-        memcpy(in + off_pt, lids, (size_t)n * sizeof(int32_t));
-    else
-        memcpy(in + off_pt, pts, (size_t)n * 3 * sizeof(double));
+    const ObsLayout L((size_t)n, lids != nullptr, false, 0, 0);
+    TRY(b.in.reserve(L.p.total));
+    TRY(b.reserve((size_t)n));
+    *b.in.host<PoseJob>(L.pose_job) = job;
+    obs_stage(in, L, b.in);
     hipStream_t st = m->st;
-    HIPCHK(hipMemcpyAsync(b.d_in, b.h_in, bytes, hipMemcpyHostToDevice, st));
-    uint8_t *d = b.d_in.get();
-    HIPCHK(hipEventRecord(m->ev14, st));
-    launch_pose_refine(st, reinterpret_cast<const PoseJob *>(d), 1, reinterpret_cast<PoseObs *>(d + off_obs),
-                       lids ? reinterpret_cast<int32_t *>(d + off_pt) : nullptr, lids ? nullptr : reinterpret_cast<const double *>(d + off_pt),
-                       m->d_geom, b.d_alive, nullptr, nullptr, nullptr, nullptr, b.h_out, b.h_flags);
+    TRY(b.in.upload(st, L.p.total));
+    TRY(m->pose.refine.mark(st, 0));
+    obs_enqueue_refine(m, in, L, b.in, b);
     const hipError_t launched = hipGetLastError();
-    HIPCHK(hipEventRecord(m->ev15, st));
+    TRY(m->pose.refine.mark(st, 1));
     HIPCHK(hipStreamSynchronize(st));
     HIPCHK(launched);
-    float ms = 0.f;
-    ev_elapsed(&ms, m->ev14, m->ev15);
-    m->us_pose = ms * 1000.f;
+    m->pose.refine.read();
     *res = *b.h_out.get();
     if (inlier) memcpy(inlier, b.h_flags.get(), (size_t)n);
     return MCORB_OK;
@@ -241,18 +269,18 @@ int mcorb_lmap_last_pose_timing(mcorb_lmap *m, float us[1])
     TRY(check_lmap_handle(m, "lmap last_pose_timing"));
     if (!us) return fail(MCORB_E_ARG, "bad argument");
     std::lock_guard<std::mutex> lk(m->mu);
-    us[0] = m->us_pose;
+    us[0] = m->pose.refine.us[0];
     return MCORB_OK;
 }
 
 int mcorb_lmap_set_track_refine(mcorb_lmap *m, const mcorb_pose_params *params)
 {
     TRY(check_lmap(m, "lmap set_track_refine"));
-    if (params) TRY(check_params(params));
+    if (params) TRY(pose_check_params(params));
     std::lock_guard<std::mutex> lk(m->mu);
-    if (m->track_pending.load()) return fail(MCORB_E_STATE, "a submitted tracking call has not been waited for");
-    m->track_refine = params != nullptr;
-    if (params) m->track_refine_params = *params;
+    if (m->track.pending.load()) return fail(MCORB_E_STATE, "a submitted tracking call has not been waited for");
+    m->track.refine = params != nullptr;
+    if (params) m->track.refine_params = *params;
     return MCORB_OK;
 }
 
@@ -261,15 +289,15 @@ int mcorb_lmap_last_track_pose(mcorb_lmap *m, int f, mcorb_pose_result *out, uin
     TRY(check_lmap_handle(m, "lmap last_track_pose"));
     if (!out || cap < 0 || (cap && !flags)) return fail(MCORB_E_ARG, "bad argument");
     std::lock_guard<std::mutex> lk(m->mu);
-    if (m->track_pending.load()) return fail(MCORB_E_STATE, "the tracking call has not been waited for");
-    if (!m->track_pose_nf) return fail(MCORB_E_STATE, "the last tracking call ran without mcorb_lmap_set_track_refine, or there was none");
-    const mcorb_lmap::TrackCall &tc = m->track_call;
-    if (f < 0 || f >= m->track_pose_nf) return fail(MCORB_E_ARG, "a frame outside the call");
+    if (m->track.pending.load()) return fail(MCORB_E_STATE, "the tracking call has not been waited for");
+    if (!m->track.pose_nf) return fail(MCORB_E_STATE, "the last tracking call ran without mcorb_lmap_set_track_refine, or there was none");
+    const mcorb_lmap::TrackCall &tc = m->track.call;
+    if (f < 0 || f >= m->track.pose_nf) return fail(MCORB_E_ARG, "a frame outside the call");
     const size_t at = (size_t)tc.ncams * tc.first[f];
     const uint8_t *src;
     if (tc.launched) {
-        *out = m->pose_t.h_out.get()[f];
-        src = m->pose_t.h_flags.get() + at;
+        *out = m->pose.t.h_out.get()[f];
+        src = m->pose.t.h_flags.get() + at;
     } else {
         *out = tc.pose[f];
         src = tc.pose_flags.data() + at;

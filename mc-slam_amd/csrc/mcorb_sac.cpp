@@ -19,8 +19,6 @@ namespace {
 
 int fail(int code, const char *what) { set_error(std::string("lmap ransac_pose: ") + what); return code; }
 
-size_t round32(size_t n) { return (n + 31) & ~(size_t)31; }
-
 // the lists the draws index: the consensus observations in input order, and camera by camera
 struct SacLists {
     std::vector<int32_t> cons, cam_first, cam_cons;
@@ -46,6 +44,18 @@ void make_lists(int n, const int32_t *cam, const int32_t *match, int ncams, SacL
     for (int32_t i : L.cons) L.cam_cons[at[cam[i]]++] = i;
 }
 
+// what the solver hooks hand to sac_solve / sac_solve_rig: the poses, appended to the caller's arrays
+struct Collect {
+    double *R, *t;
+    int n;
+    void operator()(const PoseState &P)
+    {
+        memcpy(R + 9 * n, P.R, sizeof(P.R));
+        memcpy(t + 3 * n, P.t, sizeof(P.t));
+        n++;
+    }
+};
+
 }  // namespace
 
 extern "C" {
@@ -55,32 +65,23 @@ int mcorb_lmap_ransac_pose(mcorb_lmap *m, int n, const int32_t *cam, const float
                            const mcorb_sac_params *params, const mcorb_pose_params *refine_params, mcorb_sac_result *res,
                            uint8_t *inlier)
 {
+    const char *who = "lmap ransac_pose: ";
     TRY(check_lmap(m, "lmap ransac_pose"));
-    if (n < 0 || !cams || !params || !res || (n && (!cam || !uv || !octave))) return fail(MCORB_E_ARG, "bad argument");
-    if (ncams < 1 || ncams > MCORB_MAX_CAMS) return fail(MCORB_E_ARG, "1 .. MCORB_MAX_CAMS cameras");
+    if (!params || !res) return fail(MCORB_E_ARG, "bad argument");
     if (refine_params) TRY(pose_check_params(refine_params));
     if (!(params->threshold > 0) || !sac_finite(params->threshold)) return fail(MCORB_E_ARG, "a threshold that is not finite and positive");
     if (params->max_iterations < 1 || params->max_iterations > MCORB_SAC_MAX_ITERATIONS)
         return fail(MCORB_E_ARG, "1 .. MCORB_SAC_MAX_ITERATIONS iterations");
     if (params->solver != MCORB_SAC_SOLVER_CENTRAL && params->solver != MCORB_SAC_SOLVER_RIG)
         return fail(MCORB_E_ARG, "a solver that is not one of MCORB_SAC_SOLVER_*");
-    if ((lids != nullptr) == (pts != nullptr)) return fail(MCORB_E_ARG, "exactly one of lids and pts");
-    const int nlevels = refine_params ? refine_params->nlevels : MCORB_MAX_LEVELS;
-    for (int i = 0; i < n; i++) {
-        if (cam[i] < 0 || cam[i] >= ncams) return fail(MCORB_E_ARG, "a camera index outside the rig");
-        if (octave[i] < 0 || octave[i] >= nlevels) return fail(MCORB_E_ARG, "an octave outside the levels");
-        if (lids && (lids[i] < 0 || lids[i] >= m->max_landmarks)) return fail(MCORB_E_ARG, "landmark id outside the store");
-        if (match && (match[i] < 0 || (i && match[i] < match[i - 1]))) return fail(MCORB_E_ARG, "a match index that is negative or decreases");
-    }
+    const ObsInput in{n, cam, uv, octave, lids, pts, ncams, cams};
+    TRY(obs_check(m, in, refine_params ? refine_params->nlevels : MCORB_MAX_LEVELS, match, who));
     std::lock_guard<std::mutex> lk(m->mu);
-    if (m->track_pending.load()) return fail(MCORB_E_STATE, "a submitted tracking call has not been waited for");
-    if (lids)
-        for (int i = 0; i < n; i++)
-            if (!(m->flags[lids[i]] & kHasPt)) return fail(MCORB_E_STATE, "a landmark has no point");
+    TRY(obs_check_locked(m, in, who));
 
-    SacLists L;
-    make_lists(n, cam, match, ncams, L);
-    const int S = (int)L.cons.size(), H = params->max_iterations;
+    SacLists lists;
+    make_lists(n, cam, match, ncams, lists);
+    const int S = (int)lists.cons.size(), H = params->max_iterations;
     SacJob job;
     memset(&job, 0, sizeof(job));
     memcpy(job.cams, cams, (size_t)ncams * sizeof(mcorb_track_cam));
@@ -103,12 +104,9 @@ int mcorb_lmap_ransac_pose(mcorb_lmap *m, int n, const int32_t *cam, const float
     memset(&pres, 0, sizeof(pres));
     std::vector<uint8_t> sac_flags((size_t)n), ref_flags((size_t)n);
     if (m->device < 0 || S == 0) {
-        std::vector<PoseObs> obs((size_t)n);
-        std::vector<double> X((size_t)n * 3);
-        for (int i = 0; i < n; i++) {
-            obs[i] = PoseObs{uv[2 * i], uv[2 * i + 1], cam[i], octave[i]};
-            memcpy(&X[3 * (size_t)i], lids ? &m->geom[(size_t)lids[i] * 6] : pts + 3 * (size_t)i, 3 * sizeof(double));
-        }
+        std::vector<PoseObs> obs;
+        std::vector<double> X;
+        obs_gather(m, in, obs, X);
         if (S == 0) {
             memset(&out, 0, sizeof(out));
             memcpy(out.R, ident.R, sizeof(out.R));
@@ -119,12 +117,12 @@ int mcorb_lmap_ransac_pose(mcorb_lmap *m, int n, const int32_t *cam, const float
             std::vector<SacModel> models((size_t)H);
             std::vector<int32_t> count((size_t)H);
             std::vector<double> f((size_t)S * 3);
-            sac_run_serial(job, obs.data(), X.data(), L.cons.data(), L.cam_first.data(), L.cam_cons.data(), models.data(), count.data(),
-                           f.data(), out, sac_flags.data());
-            m->sac_host_count = count;
-            m->sac_host_valid.resize((size_t)H);
-            for (int h = 0; h < H; h++) m->sac_host_valid[h] = models[h].valid;
-            m->sac_last_hyp = H;
+            sac_run_serial(job, obs.data(), X.data(), lists.cons.data(), lists.cam_first.data(), lists.cam_cons.data(), models.data(),
+                           count.data(), f.data(), out, sac_flags.data());
+            m->sac.host_count = count;
+            m->sac.host_valid.resize((size_t)H);
+            for (int h = 0; h < H; h++) m->sac.host_valid[h] = models[h].valid;
+            m->sac.last_hyp = H;
         }
         if (refine_params) {
             memcpy(pjob.init.R, out.R, sizeof(out.R));
@@ -132,88 +130,57 @@ int mcorb_lmap_ransac_pose(mcorb_lmap *m, int n, const int32_t *cam, const float
             pose_run_host(pjob, obs.data(), X.data(), n, ref_flags.data(), pres);
         }
     } else {
-        SacBufs &b = m->sac;
+        mcorb_lmap::Sac &b = m->sac;
         HIPCHK(hipSetDevice(m->device));
         (void)hipGetLastError();   // (a stale error of this thread is not this call's)
-        const size_t off_job = round32(sizeof(PoseJob)), off_obs = off_job + round32(sizeof(SacJob));
-        const size_t off_pt = off_obs + round32((size_t)n * sizeof(PoseObs));
-        const size_t off_cons = off_pt + round32((size_t)n * (lids ? sizeof(int32_t) : 3 * sizeof(double)));
-        const size_t off_camfirst = off_cons + round32((size_t)S * sizeof(int32_t));
-        const size_t off_camcons = off_camfirst + round32(((size_t)ncams + 1) * sizeof(int32_t));
-        const size_t off_first = off_camcons + round32((size_t)S * sizeof(int32_t));
-        const size_t bytes = off_first + (size_t)n;
-        TRY(b.h_in.grow(bytes, hipHostMallocDefault));
-        TRY(b.d_in.grow(bytes));
-        TRY(b.d_models.grow((size_t)H));
-        TRY(b.d_count.grow((size_t)H));
-        TRY(b.h_out.grow(1, kHostMapped));
-        TRY(b.h_flags.grow((size_t)n, kHostMapped));
-        if (refine_params) {
-            TRY(b.pose.d_alive.grow((size_t)n));
-            TRY(b.pose.h_out.grow(1, kHostMapped));
-            TRY(b.pose.h_flags.grow((size_t)n, kHostMapped));
-        }
-        uint8_t *in = b.h_in;
-        if (refine_params) memcpy(in, &pjob, sizeof(pjob));
-        memcpy(in + off_job, &job, sizeof(job));
-        PoseObs *obs = reinterpret_cast<PoseObs *>(in + off_obs);
-        for (int i = 0; i < n; i++) obs[i] = PoseObs{uv[2 * i], uv[2 * i + 1], cam[i], octave[i]};
-        if (lids)
-            memcpy(in + off_pt, lids, (size_t)n * sizeof(int32_t));
-        else
-            memcpy(in + off_pt, pts, (size_t)n * 3 * sizeof(double));
-        memcpy(in + off_cons, L.cons.data(), (size_t)S * sizeof(int32_t));
-        memcpy(in + off_camfirst, L.cam_first.data(), ((size_t)ncams + 1) * sizeof(int32_t));
-        memcpy(in + off_camcons, L.cam_cons.data(), (size_t)S * sizeof(int32_t));
-        memcpy(in + off_first, L.is_first.data(), (size_t)n);
+        const ObsLayout L((size_t)n, lids != nullptr, true, (size_t)S, (size_t)ncams);
+        TRY(b.reserve(L.p.total, (size_t)n, (size_t)H, refine_params != nullptr));
+        if (refine_params) *b.in.host<PoseJob>(L.pose_job) = pjob;
+        *b.in.host<SacJob>(L.sac_job) = job;
+        obs_stage(in, L, b.in);
+        memcpy(b.in.host<int32_t>(L.cons), lists.cons.data(), (size_t)S * sizeof(int32_t));
+        memcpy(b.in.host<int32_t>(L.cam_first), lists.cam_first.data(), ((size_t)ncams + 1) * sizeof(int32_t));
+        memcpy(b.in.host<int32_t>(L.cam_cons), lists.cam_cons.data(), (size_t)S * sizeof(int32_t));
+        memcpy(b.in.host<uint8_t>(L.is_first), lists.is_first.data(), (size_t)n);
         hipStream_t st = m->st;
-        HIPCHK(hipMemcpyAsync(b.d_in, b.h_in, bytes, hipMemcpyHostToDevice, st));
+        TRY(b.in.upload(st, L.p.total));
         HIPCHK(hipMemsetAsync(b.d_count, 0, (size_t)H * sizeof(int32_t), st));
-        uint8_t *d = b.d_in.get();
         SacArgs a;
-        a.job = reinterpret_cast<const SacJob *>(d + off_job);
-        a.obs = reinterpret_cast<const PoseObs *>(d + off_obs);
-        a.lids = lids ? reinterpret_cast<const int32_t *>(d + off_pt) : nullptr;
-        a.pts = lids ? nullptr : reinterpret_cast<const double *>(d + off_pt);
+        a.job = b.in.dev<const SacJob>(L.sac_job);
+        a.obs = b.in.dev<const PoseObs>(L.obs);
+        a.lids = lids ? b.in.dev<const int32_t>(L.pt) : nullptr;
+        a.pts = lids ? nullptr : b.in.dev<const double>(L.pt);
         a.geom = m->d_geom;
-        a.cons = reinterpret_cast<const int32_t *>(d + off_cons);
-        a.cam_first = reinterpret_cast<const int32_t *>(d + off_camfirst);
-        a.cam_cons = reinterpret_cast<const int32_t *>(d + off_camcons);
-        a.is_first = d + off_first;
+        a.cons = b.in.dev<const int32_t>(L.cons);
+        a.cam_first = b.in.dev<const int32_t>(L.cam_first);
+        a.cam_cons = b.in.dev<const int32_t>(L.cam_cons);
+        a.is_first = b.in.dev<const uint8_t>(L.is_first);
         a.models = b.d_models;
         a.count = b.d_count;
         a.out = b.h_out;
         a.flags = b.h_flags;
-        a.pose_job = refine_params ? reinterpret_cast<PoseJob *>(d) : nullptr;
-        HIPCHK(hipEventRecord(m->ev16, st));
+        a.pose_job = refine_params ? b.in.dev<PoseJob>(L.pose_job) : nullptr;
+        TRY(b.kernels.mark(st, 0));
         if (job.solver == MCORB_SAC_SOLVER_RIG)
             launch_sac_hypotheses_rig(st, a, H);
         else
             launch_sac_hypotheses(st, a, H);
         hipError_t launched = hipGetLastError();
-        HIPCHK(hipEventRecord(m->ev17, st));
+        TRY(b.kernels.mark(st, 1));
         launch_sac_score(st, a, S, H);
         if (launched == hipSuccess) launched = hipGetLastError();
-        HIPCHK(hipEventRecord(m->ev18, st));
+        TRY(b.kernels.mark(st, 2));
         launch_sac_pick(st, a, n);
         if (launched == hipSuccess) launched = hipGetLastError();
-        HIPCHK(hipEventRecord(m->ev19, st));
+        TRY(b.kernels.mark(st, 3));
         if (refine_params) {
-            launch_pose_refine(st, reinterpret_cast<const PoseJob *>(d), 1, reinterpret_cast<PoseObs *>(d + off_obs),
-                               lids ? reinterpret_cast<int32_t *>(d + off_pt) : nullptr, a.pts, m->d_geom, b.pose.d_alive, nullptr, nullptr,
-                               nullptr, nullptr, b.pose.h_out, b.pose.h_flags);
+            obs_enqueue_refine(m, in, L, b.in, b.pose);
             if (launched == hipSuccess) launched = hipGetLastError();
         }
         HIPCHK(hipStreamSynchronize(st));
         HIPCHK(launched);
-        float ms = 0.f;
-        ev_elapsed(&ms, m->ev16, m->ev17);
-        m->us_sac[0] = ms * 1000.f;
-        ev_elapsed(&ms, m->ev17, m->ev18);
-        m->us_sac[1] = ms * 1000.f;
-        ev_elapsed(&ms, m->ev18, m->ev19);
-        m->us_sac[2] = ms * 1000.f;
-        m->sac_last_hyp = H;
+        b.kernels.read();
+        b.last_hyp = H;
         out = *b.h_out.get();
         memcpy(sac_flags.data(), b.h_flags.get(), (size_t)n);
         if (refine_params) {
@@ -240,7 +207,7 @@ int mcorb_lmap_ransac_pose(mcorb_lmap *m, int n, const int32_t *cam, const float
     if (refine_params)
         for (int k = 0; k < nm; k++) {
             uint8_t all = 1;
-            for (int i = L.match_first[k]; i < L.match_first[k + 1]; i++) all &= ref_flags[i];
+            for (int i = lists.match_first[k]; i < lists.match_first[k + 1]; i++) all &= ref_flags[i];
             ref_match[k] = all;
             ref_in += all;
         }
@@ -250,7 +217,7 @@ int mcorb_lmap_ransac_pose(mcorb_lmap *m, int n, const int32_t *cam, const float
     memcpy(res->t, use_refine ? pres.t : out.t, sizeof(res->t));
     res->n_inliers = use_refine ? ref_in : out.n_inliers;
     if (inlier)
-        for (int k = 0; k < nm; k++) inlier[k] = use_refine ? ref_match[k] : sac_flags[L.match_first[k]];
+        for (int k = 0; k < nm; k++) inlier[k] = use_refine ? ref_match[k] : sac_flags[lists.match_first[k]];
     return MCORB_OK;
 }
 
@@ -259,8 +226,8 @@ int mcorb_lmap_last_ransac_timing(mcorb_lmap *m, float us[3], int *n_hyp)
     TRY(check_lmap_handle(m, "lmap last_ransac_timing"));
     if (!us) return fail(MCORB_E_ARG, "bad argument");
     std::lock_guard<std::mutex> lk(m->mu);
-    for (int k = 0; k < 3; k++) us[k] = m->us_sac[k];
-    if (n_hyp) *n_hyp = m->sac_last_hyp;
+    for (int k = 0; k < 3; k++) us[k] = m->sac.kernels.us[k];
+    if (n_hyp) *n_hyp = m->sac.last_hyp;
     return MCORB_OK;
 }
 
@@ -269,13 +236,13 @@ int mcorb_lmap_last_ransac_counts(mcorb_lmap *m, int32_t *count, int32_t *valid,
     TRY(check_lmap(m, "lmap last_ransac_counts"));
     if (cap < 0 || !n_hyp || (cap && (!count || !valid))) return fail(MCORB_E_ARG, "bad argument");
     std::lock_guard<std::mutex> lk(m->mu);
-    const int H = m->sac_last_hyp;
+    const int H = m->sac.last_hyp;
     *n_hyp = H;
     if (cap < H) return fail(MCORB_E_CAP, "arrays too small");
     if (m->device < 0) {
         for (int h = 0; h < H; h++) {
-            count[h] = m->sac_host_count[h];
-            valid[h] = m->sac_host_valid[h];
+            count[h] = m->sac.host_count[h];
+            valid[h] = m->sac.host_valid[h];
         }
         return MCORB_OK;
     }
@@ -293,16 +260,7 @@ double mcorb_sac_threshold(double K00_02) { return 1.0 - cos(atan(sqrt(2.0) * 0.
 int mcorb_sac_solve(const mcorb_track_cam *cam, const float *uv, const double *pts, double *R, double *t)
 {
     if (!cam || !uv || !pts || !R || !t) return fail(MCORB_E_ARG, "bad argument");
-    struct Collect {
-        double *R, *t;
-        int n;
-        void operator()(const PoseState &P)
-        {
-            memcpy(R + 9 * n, P.R, sizeof(P.R));
-            memcpy(t + 3 * n, P.t, sizeof(P.t));
-            n++;
-        }
-    } collect{R, t, 0};
+    Collect collect{R, t, 0};
     double f[3][3];
     for (int k = 0; k < 3; k++) sac_bearing(*cam, uv[2 * k], uv[2 * k + 1], f[k]);
     sac_solve(*cam, f[0], f[1], f[2], pts, pts + 3, pts + 6, collect);
@@ -314,16 +272,7 @@ int mcorb_sac_solve_rig(int ncams, const mcorb_track_cam *cams, const int32_t *c
     if (ncams < 1 || ncams > MCORB_MAX_CAMS || !cams || !cam || !uv || !pts || !R || !t) return fail(MCORB_E_ARG, "bad argument");
     for (int k = 0; k < 3; k++)
         if (cam[k] < 0 || cam[k] >= ncams) return fail(MCORB_E_ARG, "a camera index outside the rig");
-    struct Collect {
-        double *R, *t;
-        int n;
-        void operator()(const PoseState &P)
-        {
-            memcpy(R + 9 * n, P.R, sizeof(P.R));
-            memcpy(t + 3 * n, P.t, sizeof(P.t));
-            n++;
-        }
-    } collect{R, t, 0};
+    Collect collect{R, t, 0};
     double f[3][3];
     for (int k = 0; k < 3; k++) sac_bearing(cams[cam[k]], uv[2 * k], uv[2 * k + 1], f[k]);
     sac_solve_rig(cams, cam[0], cam[1], cam[2], f[0], f[1], f[2], pts, pts + 3, pts + 6, collect);

@@ -34,6 +34,8 @@ using namespace mcorb;
 
 namespace {
 
+using TK = mcorb_lmap::Tracking;
+
 int fail(int code, const char *what) { set_error(std::string("lmap track: ") + what); return code; }
 
 // a camera's keypoints on the host: records of `stride` bytes that begin with pt's two floats -- the caller's packed pairs
@@ -61,7 +63,7 @@ struct Phases {
 #ifdef MCORB_TRACK_PROF
     float *us;
     std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
-    Phases(mcorb_lmap *m, bool reset) : us(m->us_track_phase)   // a submission starts the call's phases over, its wait adds to them
+    Phases(mcorb_lmap *m, bool reset) : us(m->track.us_phase)   // a submission starts the call's phases over, its wait adds to them
     {
         if (reset)
             for (int k = 0; k < 5; k++) us[k] = 0.f;
@@ -102,8 +104,6 @@ TrBest query_host(float x, float y, const KpRows &kp, int c, const uint8_t *kp_d
     if (key == kTrNoGate) return TrBest{-1, kTrBest0};
     return TrBest{(int32_t)top[key & 15u].k, (int32_t)(key >> 4)};
 }
-
-size_t round32(size_t n) { return (n + 31) & ~(size_t)31; }
 
 void clear_counts(mcorb_track_out *out)
 {
@@ -242,102 +242,90 @@ int submit_on_device(mcorb_lmap *m, const mcorb_track_view &view, const Frame &f
         total_kp += (size_t)f.n_kp[c];
     }
     if (f.slot) total_kp = 0;   // nothing of the frame goes up
-    const size_t off_xy = round32((size_t)nc * sizeof(int)), off_desc = off_xy + round32(total_kp * 8);
-    const size_t bytes = off_desc + total_kp * 32;
-    TRY(m->h_trackin.grow(bytes, hipHostMallocDefault));
-    TRY(m->d_trackin.grow(bytes));
-    TRY(m->d_trackxy.grow(rows));
-    TRY(m->d_trackvalid.grow(rows));
-    TRY(m->d_trackbest.grow(rows));
-    TRY(m->h_trackrows.grow(rows, kHostMapped));
-    TRY(m->h_tracknproj.grow(MCORB_MAX_CAMS, kHostMapped));
+    const TrackLayout L((size_t)nc, total_kp);
     const size_t slots = (size_t)C << tr_dedup_log2(nc);
-    TRY(m->d_trackowner.grow(slots));
-    TRY(m->d_trackval.grow(slots));
-    TRY(m->d_trackslot.grow(rows));
-    TRY(m->d_trackwin.grow(rows));
-    TRY(m->h_trackmatch.grow(rows, kHostMapped));
-    TRY(m->h_tracknmatch.grow(MCORB_MAX_CAMS, kHostMapped));
-    if (f.slot) TRY(m->d_trackkp.grow((size_t)C * kcap));
-    if (want_pts) {
-        TRY(m->d_trackpt.grow((size_t)nc * 3));
-        TRY(m->h_trackpt.grow((size_t)nc * 3, hipHostMallocDefault));
-    }
-    uint8_t *in = m->h_trackin;
-    memcpy(in, cand.data(), (size_t)nc * sizeof(int));
+    TK &t = m->track;
+    TRY(t.reserve(L.p.total, rows, 1, slots, f.slot ? (size_t)C * kcap : 0, want_pts ? (size_t)nc : 0));
+    memcpy(t.in.host<int>(L.cand), cand.data(), (size_t)nc * sizeof(int));
     if (!f.slot)
         for (int c = 0; c < C; c++) {
             if (!f.n_kp[c]) continue;
-            memcpy(in + off_xy + (size_t)tf.first[c] * 8, f.kp.base[c], (size_t)f.n_kp[c] * 8);
-            memcpy(in + off_desc + (size_t)tf.first[c] * 32, f.desc[c], (size_t)f.n_kp[c] * 32);
+            memcpy(t.in.host<uint8_t>(L.xy) + (size_t)tf.first[c] * 8, f.kp.base[c], (size_t)f.n_kp[c] * 8);
+            memcpy(t.in.host<uint8_t>(L.desc) + (size_t)tf.first[c] * 32, f.desc[c], (size_t)f.n_kp[c] * 32);
         }
-    HIPCHK(hipMemcpyAsync(m->d_trackin, m->h_trackin, bytes, hipMemcpyHostToDevice, st));
-    const int *d_cand = reinterpret_cast<const int *>(m->d_trackin.get());
-    const float2 *kp_xy = reinterpret_cast<const float2 *>(m->d_trackin.get() + off_xy);
-    const uint8_t *kp_desc = m->d_trackin.get() + off_desc;
+    TRY(t.in.upload(st, L.p.total));
+    const int *d_cand = t.in.dev<const int>(L.cand);
+    const float2 *kp_xy = t.in.dev<const float2>(L.xy);
+    const uint8_t *kp_desc = t.in.dev<const uint8_t>(L.desc);
     if (f.slot) {
         const uint32_t *sel;
         const int *nsel;
         slot_sel(*f.slot, sel, nsel);
-        HIPCHK(hipEventRecord(m->ev12, st));
-        launch_track_points(st, sel, nsel, kcap, f.img0, C, f.rig->tab.scale, f.rig->tab.nlevels, m->d_trackkp);
+        TRY(t.chain.mark(st, TK::kPoints));
+        launch_track_points(st, sel, nsel, kcap, f.img0, C, f.rig->tab.scale, f.rig->tab.nlevels, t.d_kp);
         HIPCHK(hipGetLastError());
-        kp_xy = m->d_trackkp;
+        kp_xy = t.d_kp;
         kp_desc = f.slot->d_desc.get() + (size_t)f.img0 * kcap * 32;
     }
-    HIPCHK(hipEventRecord(m->ev8, st));
-    launch_track_project(st, view, m->d_geom, d_cand, nc, m->d_trackxy, m->d_trackvalid, want_pts ? m->d_trackpt.get() : nullptr);
+    TRY(t.chain.mark(st, TK::kProject));
+    launch_track_project(st, view, m->d_geom, d_cand, nc, t.d_xy, t.d_valid, want_pts ? t.d_pt.get() : nullptr);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(m->ev9, st));
-    launch_track_match(st, tf, C, kp_xy, kp_desc, m->d_desc, d_cand, nc, m->d_trackxy, m->d_trackvalid, max_d2, max_hamming, m->d_trackbest);
+    TRY(t.chain.mark(st, TK::kMatch));
+    launch_track_match(st, tf, C, kp_xy, kp_desc, m->d_desc, d_cand, nc, t.d_xy, t.d_valid, max_d2, max_hamming, t.d_best);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(m->ev10, st));
-    launch_track_compact(st, C, nc, m->d_trackvalid, m->d_trackxy, m->d_trackbest, m->h_trackrows, m->h_tracknproj);
+    TRY(t.chain.mark(st, TK::kCompact));
+    launch_track_compact(st, C, nc, t.d_valid, t.d_xy, t.d_best, t.h_rows, t.h_nproj);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(m->ev11, st));
-    HIPCHK(hipMemsetAsync(m->d_trackowner, 0xff, slots * sizeof(uint32_t), st));
-    HIPCHK(hipMemsetAsync(m->d_trackval, 0xff, slots * sizeof(unsigned long long), st));
-    launch_track_dedup(st, tf, C, kp_xy, nc, m->d_trackvalid, m->d_trackbest, m->d_trackowner, m->d_trackval, m->d_trackslot, m->d_trackwin,
-                       m->h_trackmatch, m->h_tracknmatch);
+    TRY(t.chain.mark(st, TK::kDedup));
+    HIPCHK(hipMemsetAsync(t.d_owner, 0xff, slots * sizeof(uint32_t), st));
+    HIPCHK(hipMemsetAsync(t.d_val, 0xff, slots * sizeof(unsigned long long), st));
+    launch_track_dedup(st, tf, C, kp_xy, nc, t.d_valid, t.d_best, t.d_owner, t.d_val, t.d_slot, t.d_win, t.h_match, t.h_nmatch);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(m->ev13, st));
-    if (m->track_refine) {   // (mcorb_lmap_set_track_refine: the pose from the frame's matches, in the same submission)
+    TRY(t.chain.mark(st, TK::kDedup + 1));
+    if (t.refine) {   // (mcorb_lmap_set_track_refine: the pose from the frame's matches, in the same submission)
         const size_t first[2] = {0, (size_t)nc}, kp0 = 0;
         TRY(pose_track_submit(m, &view, 1, first, &tf, &kp0, kp_xy, d_cand));
     }
-    if (want_pts) HIPCHK(hipMemcpyAsync(m->h_trackpt, m->d_trackpt, (size_t)nc * 3 * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (want_pts) HIPCHK(hipMemcpyAsync(t.h_pt, t.d_pt, (size_t)nc * 3 * sizeof(double), hipMemcpyDeviceToHost, st));
     return MCORB_OK;
 }
 
 // ---- 3. a call's two halves, the frame checked; the caller holds the store's lock ----
+// the state of a call of nf frames whose candidates (cand, first) are in place: nothing launched, every count zero
+void begin_call(mcorb_lmap *m, int C, int nf, bool want_pts)
+{
+    mcorb_lmap::TrackCall &tc = m->track.call;
+    tc.ncams = C;
+    tc.nf = nf;
+    tc.launched = tc.points = false;
+    tc.want_pts = want_pts;
+    tc.n_proj.assign((size_t)nf * MCORB_MAX_CAMS, 0);
+    tc.n_match.assign((size_t)nf * MCORB_MAX_CAMS, 0);
+    tc.refine = m->track.refine;
+    m->track.pose_nf = 0;
+    if (tc.refine) {
+        tc.pose.assign((size_t)nf, mcorb_pose_result{});
+        tc.pose_flags.assign((size_t)C * tc.cand.size(), 0);
+    }
+}
+
 // everything up to and excluding the synchronisation: the candidates, then the whole call on a host-only store, the submission on
 // a device store.  A refusal leaves nothing behind: work that a failed submission put on the stream is waited for here
 int submit_body(mcorb_lmap *m, const mcorb_track_view *view, const Frame &f, const int32_t *lids, int n_lids, double max_d2,
                 int max_hamming, bool want_pts, mcorb_track_out *out)
 {
     Phases ph(m, true);
-    mcorb_lmap::TrackCall &tc = m->track_call;
+    mcorb_lmap::TrackCall &tc = m->track.call;
     tc.cand.clear();
     TRY(candidates_of(m, lids, n_lids, tc.cand));
     if (out) out->n_candidates = (int)tc.cand.size();   // (the synchronous entries: set from here on, whatever follows)
     ph.mark(0);
     const int C = view->ncams, nc = (int)tc.cand.size();
-    tc.ncams = C;
-    tc.nf = 1;
     tc.first.assign({(size_t)0, (size_t)nc});
-    tc.launched = tc.points = false;
-    tc.want_pts = want_pts;
-    tc.n_proj.assign(MCORB_MAX_CAMS, 0);
-    tc.n_match.assign(MCORB_MAX_CAMS, 0);
-    tc.refine = m->track_refine;
-    m->track_pose_nf = 0;
-    if (tc.refine) {
-        tc.pose.assign(1, mcorb_pose_result{});
-        tc.pose_flags.assign((size_t)C * nc, 0);
-    }
+    begin_call(m, C, 1, want_pts);
     if (!nc) {
         if (tc.refine) pose_track_host(m, *view, nullptr, 0, nullptr, tc.n_match.data(), f.kp.base, f.kp.stride, tc.pose[0], nullptr);
-        m->track_pose_nf = tc.refine ? 1 : 0;
+        m->track.pose_nf = tc.refine ? 1 : 0;
         return MCORB_OK;
     }
     if (m->device < 0) {
@@ -350,7 +338,7 @@ int submit_body(mcorb_lmap *m, const mcorb_track_view *view, const Frame &f, con
         if (tc.refine)
             pose_track_host(m, *view, tc.cand.data(), nc, tc.matches.data(), tc.n_match.data(), f.kp.base, f.kp.stride, tc.pose[0],
                             tc.pose_flags.data());
-        m->track_pose_nf = tc.refine ? 1 : 0;
+        m->track.pose_nf = tc.refine ? 1 : 0;
         return MCORB_OK;
     }
     const int r = submit_on_device(m, *view, f, tc.cand, max_d2, max_hamming, want_pts);
@@ -360,7 +348,7 @@ int submit_body(mcorb_lmap *m, const mcorb_track_view *view, const Frame &f, con
     }
     tc.launched = true;
     tc.points = f.slot != nullptr;
-    m->track_pose_nf = tc.refine ? 1 : 0;
+    m->track.pose_nf = tc.refine ? 1 : 0;
     ph.mark(1);
     return MCORB_OK;
 }
@@ -371,7 +359,7 @@ int submit_body(mcorb_lmap *m, const mcorb_track_view *view, const Frame &f, con
 int wait_body(mcorb_lmap *m, mcorb_track_out *outs, int n_outs, bool checked, bool single)
 {
     Phases ph(m, false);
-    const mcorb_lmap::TrackCall &tc = m->track_call;
+    const mcorb_lmap::TrackCall &tc = m->track.call;
     const int C = tc.ncams, nf = tc.nf;
     const TrRow *rows = tc.rows.data();
     const TrMatch *matches = tc.matches.data();
@@ -381,25 +369,12 @@ int wait_body(mcorb_lmap *m, mcorb_track_out *outs, int n_outs, bool checked, bo
         HIPCHK(hipSetDevice(m->device));
         HIPCHK(hipStreamSynchronize(m->st));
         ph.mark(2);
-        float ms = 0.f;
-        m->us_track_points = 0.f;
-        if (tc.points) {
-            ev_elapsed(&ms, m->ev12, m->ev8);
-            m->us_track_points = ms * 1000.f;
-        }
-        ev_elapsed(&ms, m->ev8, m->ev9);
-        m->us_track_project = ms * 1000.f;
-        ev_elapsed(&ms, m->ev9, m->ev10);
-        m->us_track_match = ms * 1000.f;
-        ev_elapsed(&ms, m->ev10, m->ev11);
-        m->us_track_compact = ms * 1000.f;
-        ev_elapsed(&ms, m->ev11, m->ev13);
-        m->us_track_dedup = ms * 1000.f;
-        rows = m->h_trackrows;
-        matches = m->h_trackmatch;
-        n_proj = m->h_tracknproj;
-        n_match = m->h_tracknmatch;
-        if (tc.want_pts) pts = m->h_trackpt;
+        m->track.chain.read(tc.points ? TK::kPoints : TK::kProject);
+        rows = m->track.h_rows;
+        matches = m->track.h_match;
+        n_proj = m->track.h_nproj;
+        n_match = m->track.h_nmatch;
+        if (tc.want_pts) pts = m->track.h_pt;
     }
     ph.mark(3);
     if (!checked) {
@@ -463,10 +438,10 @@ int track(mcorb_lmap *m, const mcorb_track_view *view, const Frame &f, const int
           bool want_pts, mcorb_track_out *out)
 {
     std::lock_guard<std::mutex> lk(m->mu);
-    if (m->track_pending.load()) return fail(MCORB_E_STATE, "a submitted tracking call has not been waited for");
+    if (m->track.pending.load()) return fail(MCORB_E_STATE, "a submitted tracking call has not been waited for");
     TRY(submit_body(m, view, f, lids, n_lids, max_d2, max_hamming, want_pts, out));
     if (out) return wait_body(m, out, 1, true, true);
-    m->track_pending.store(true);
+    m->track.pending.store(true);
     return MCORB_OK;
 }
 
@@ -553,8 +528,7 @@ int submit_frames_on_device(mcorb_lmap *m, const mcorb_track_view *views, const 
     HIPCHK(hipSetDevice(m->device));
     (void)hipGetLastError();   // (a stale error of this thread is not this call's: submit_on_device)
     hipStream_t st = m->st;
-    const size_t off_views = round32((size_t)nf * sizeof(TrBatchItem)), off_cand = off_views + round32((size_t)nf * sizeof(mcorb_track_view));
-    const size_t bytes = off_cand + total * sizeof(int);
+    const TrackBatchLayout L((size_t)nf, total);
     size_t slots = 0;
     int max_n = 0;
     for (int f = 0; f < nf; f++) {
@@ -562,26 +536,9 @@ int submit_frames_on_device(mcorb_lmap *m, const mcorb_track_view *views, const 
         slots += (size_t)C << tr_dedup_log2(n);
         max_n = std::max(max_n, n);
     }
-    TRY(m->h_trackin.grow(bytes, hipHostMallocDefault));
-    TRY(m->d_trackin.grow(bytes));
-    TRY(m->d_trackxy.grow(rows));
-    TRY(m->d_trackvalid.grow(rows));
-    TRY(m->d_trackbest.grow(rows));
-    TRY(m->h_trackrows.grow(rows, kHostMapped));
-    TRY(m->h_tracknproj.grow((size_t)nf * MCORB_MAX_CAMS, kHostMapped));
-    TRY(m->d_trackowner.grow(slots));
-    TRY(m->d_trackval.grow(slots));
-    TRY(m->d_trackslot.grow(rows));
-    TRY(m->d_trackwin.grow(rows));
-    TRY(m->h_trackmatch.grow(rows, kHostMapped));
-    TRY(m->h_tracknmatch.grow((size_t)nf * MCORB_MAX_CAMS, kHostMapped));
-    TRY(m->d_trackkp.grow((size_t)nf * C * kcap));
-    if (want_pts) {
-        TRY(m->d_trackpt.grow(total * 3));
-        TRY(m->h_trackpt.grow(total * 3, hipHostMallocDefault));
-    }
-    uint8_t *in = m->h_trackin;
-    TrBatchItem *items = reinterpret_cast<TrBatchItem *>(in);
+    TK &t = m->track;
+    TRY(t.reserve(L.p.total, rows, (size_t)nf, slots, (size_t)nf * C * kcap, want_pts ? total : 0));
+    TrBatchItem *items = t.in.host<TrBatchItem>(L.items);
     size_t tab = 0;
     for (int f = 0; f < nf; f++) {
         TrBatchItem &it = items[f];
@@ -602,48 +559,46 @@ int submit_frames_on_device(mcorb_lmap *m, const mcorb_track_view *views, const 
         tab += (size_t)C << it.log2p;
         if (!it.n)   // no workgroup runs for this frame
             for (int c = 0; c < MCORB_MAX_CAMS; c++)
-                m->h_tracknproj.get()[(size_t)f * MCORB_MAX_CAMS + c] = m->h_tracknmatch.get()[(size_t)f * MCORB_MAX_CAMS + c] = 0;
+                t.h_nproj.get()[(size_t)f * MCORB_MAX_CAMS + c] = t.h_nmatch.get()[(size_t)f * MCORB_MAX_CAMS + c] = 0;
     }
-    memcpy(in + off_views, views, (size_t)nf * sizeof(mcorb_track_view));
-    memcpy(in + off_cand, tc.cand.data(), total * sizeof(int));
-    HIPCHK(hipMemcpyAsync(m->d_trackin, m->h_trackin, bytes, hipMemcpyHostToDevice, st));
-    const TrBatchItem *d_items = reinterpret_cast<const TrBatchItem *>(m->d_trackin.get());
-    const mcorb_track_view *d_views = reinterpret_cast<const mcorb_track_view *>(m->d_trackin.get() + off_views);
-    const int *d_cand = reinterpret_cast<const int *>(m->d_trackin.get() + off_cand);
+    memcpy(t.in.host<mcorb_track_view>(L.views), views, (size_t)nf * sizeof(mcorb_track_view));
+    memcpy(t.in.host<int>(L.cand), tc.cand.data(), total * sizeof(int));
+    TRY(t.in.upload(st, L.p.total));
+    const TrBatchItem *d_items = t.in.dev<const TrBatchItem>(L.items);
+    const mcorb_track_view *d_views = t.in.dev<const mcorb_track_view>(L.views);
+    const int *d_cand = t.in.dev<const int>(L.cand);
     const uint32_t *sel;
     const int *nsel;
     slot_sel(*f0.slot, sel, nsel);
-    HIPCHK(hipEventRecord(m->ev12, st));
-    launch_track_points_batch(st, d_items, nf, sel, nsel, kcap, C, f0.rig->tab.scale, f0.rig->tab.nlevels, m->d_trackkp);
+    TRY(t.chain.mark(st, TK::kPoints));
+    launch_track_points_batch(st, d_items, nf, sel, nsel, kcap, C, f0.rig->tab.scale, f0.rig->tab.nlevels, t.d_kp);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(m->ev8, st));
-    launch_track_project_batch(st, d_items, nf, max_n, d_views, m->d_geom, d_cand, m->d_trackxy, m->d_trackvalid,
-                               want_pts ? m->d_trackpt.get() : nullptr);
+    TRY(t.chain.mark(st, TK::kProject));
+    launch_track_project_batch(st, d_items, nf, max_n, d_views, m->d_geom, d_cand, t.d_xy, t.d_valid, want_pts ? t.d_pt.get() : nullptr);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(m->ev9, st));
-    launch_track_match_batch(st, d_items, nf, max_n, C, m->d_trackkp, f0.slot->d_desc.get(), m->d_desc, d_cand, m->d_trackxy, m->d_trackvalid,
-                             max_d2, max_hamming, m->d_trackbest);
+    TRY(t.chain.mark(st, TK::kMatch));
+    launch_track_match_batch(st, d_items, nf, max_n, C, t.d_kp, f0.slot->d_desc.get(), m->d_desc, d_cand, t.d_xy, t.d_valid, max_d2,
+                             max_hamming, t.d_best);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(m->ev10, st));
-    launch_track_compact_batch(st, d_items, nf, max_n, C, m->d_trackvalid, m->d_trackxy, m->d_trackbest, m->h_trackrows, m->h_tracknproj);
+    TRY(t.chain.mark(st, TK::kCompact));
+    launch_track_compact_batch(st, d_items, nf, max_n, C, t.d_valid, t.d_xy, t.d_best, t.h_rows, t.h_nproj);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(m->ev11, st));
-    HIPCHK(hipMemsetAsync(m->d_trackowner, 0xff, slots * sizeof(uint32_t), st));
-    HIPCHK(hipMemsetAsync(m->d_trackval, 0xff, slots * sizeof(unsigned long long), st));
-    launch_track_dedup_batch(st, d_items, nf, max_n, C, m->d_trackkp, m->d_trackvalid, m->d_trackbest, m->d_trackowner, m->d_trackval,
-                             m->d_trackslot, m->d_trackwin, m->h_trackmatch, m->h_tracknmatch);
+    TRY(t.chain.mark(st, TK::kDedup));
+    HIPCHK(hipMemsetAsync(t.d_owner, 0xff, slots * sizeof(uint32_t), st));
+    HIPCHK(hipMemsetAsync(t.d_val, 0xff, slots * sizeof(unsigned long long), st));
+    launch_track_dedup_batch(st, d_items, nf, max_n, C, t.d_kp, t.d_valid, t.d_best, t.d_owner, t.d_val, t.d_slot, t.d_win, t.h_match, t.h_nmatch);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(m->ev13, st));
-    if (m->track_refine) {   // (one workgroup of k_pose_refine per frame, in the same submission)
+    TRY(t.chain.mark(st, TK::kDedup + 1));
+    if (t.refine) {   // (one workgroup of k_pose_refine per frame, in the same submission)
         std::vector<TrFrame> tf((size_t)nf);
         std::vector<size_t> kp0((size_t)nf);
         for (int f = 0; f < nf; f++) {
             tf[f] = items[f].frame;
             kp0[f] = items[f].kp0;
         }
-        TRY(pose_track_submit(m, views, nf, tc.first.data(), tf.data(), kp0.data(), m->d_trackkp, d_cand));
+        TRY(pose_track_submit(m, views, nf, tc.first.data(), tf.data(), kp0.data(), t.d_kp, d_cand));
     }
-    if (want_pts) HIPCHK(hipMemcpyAsync(m->h_trackpt, m->d_trackpt, total * 3 * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (want_pts) HIPCHK(hipMemcpyAsync(t.h_pt, t.d_pt, total * 3 * sizeof(double), hipMemcpyDeviceToHost, st));
     return MCORB_OK;
 }
 
@@ -653,7 +608,7 @@ int submit_frames_body(mcorb_lmap *m, const mcorb_track_view *views, const std::
                        const int32_t *lids, const int32_t *lid_first, double max_d2, int max_hamming, bool want_pts, mcorb_track_out *outs)
 {
     Phases ph(m, true);
-    mcorb_lmap::TrackCall &tc = m->track_call;
+    mcorb_lmap::TrackCall &tc = m->track.call;
     const int C = views[0].ncams;
     tc.cand.clear();
     tc.first.assign(1, 0);
@@ -665,18 +620,7 @@ int submit_frames_body(mcorb_lmap *m, const mcorb_track_view *views, const std::
         for (int f = 0; f < nf; f++) outs[f].n_candidates = (int)(tc.first[f + 1] - tc.first[f]);
     ph.mark(0);
     const size_t total = tc.cand.size();
-    tc.ncams = C;
-    tc.nf = nf;
-    tc.launched = tc.points = false;
-    tc.want_pts = want_pts;
-    tc.n_proj.assign((size_t)nf * MCORB_MAX_CAMS, 0);
-    tc.n_match.assign((size_t)nf * MCORB_MAX_CAMS, 0);
-    tc.refine = m->track_refine;
-    m->track_pose_nf = 0;
-    if (tc.refine) {
-        tc.pose.assign((size_t)nf, mcorb_pose_result{});
-        tc.pose_flags.assign((size_t)C * total, 0);
-    }
+    begin_call(m, C, nf, want_pts);
     if (!total || m->device < 0) {
         tc.rows.resize((size_t)C * total);
         tc.matches.resize((size_t)C * total);
@@ -694,7 +638,7 @@ int submit_frames_body(mcorb_lmap *m, const mcorb_track_view *views, const std::
                 pose_track_host(m, views[f], tc.cand.data() + tc.first[f], nc, matches, n_match, fr[f].kp.base, fr[f].kp.stride, tc.pose[f],
                                 tc.pose_flags.data() + (size_t)C * tc.first[f]);
         }
-        m->track_pose_nf = tc.refine ? nf : 0;
+        m->track.pose_nf = tc.refine ? nf : 0;
         ph.mark(3);
         return MCORB_OK;
     }
@@ -704,7 +648,7 @@ int submit_frames_body(mcorb_lmap *m, const mcorb_track_view *views, const std::
         return r;
     }
     tc.launched = tc.points = true;
-    m->track_pose_nf = tc.refine ? nf : 0;
+    m->track.pose_nf = tc.refine ? nf : 0;
     ph.mark(1);
     return MCORB_OK;
 }
@@ -730,7 +674,7 @@ int track_slot_frames(mcorb_lmap *m, const mcorb_track_view *views, mcorb_rig *r
     std::vector<Frame> fr((size_t)nf);
     for (int f = 0; f < nf; f++) TRY(frame_of_slot(m, &views[f], r, slot, frames[f], fr[f]));
     std::lock_guard<std::mutex> lk(m->mu);
-    if (m->track_pending.load()) return fail(MCORB_E_STATE, "a submitted tracking call has not been waited for");
+    if (m->track.pending.load()) return fail(MCORB_E_STATE, "a submitted tracking call has not been waited for");
     const int rc = submit_frames_body(m, views, fr, frames, nf, lids, lid_first, max_d2, max_hamming, want_pts, with_out ? outs : nullptr);
     if (rc != MCORB_OK) {
         if (with_out)
@@ -738,7 +682,7 @@ int track_slot_frames(mcorb_lmap *m, const mcorb_track_view *views, mcorb_rig *r
         return rc;
     }
     if (with_out) return wait_body(m, outs, nf, true, false);
-    m->track_pending.store(true);
+    m->track.pending.store(true);
     return MCORB_OK;
 }
 
@@ -770,24 +714,22 @@ int mcorb_lmap_track_rig_frame_submit(mcorb_lmap *m, const mcorb_track_view *vie
     return track_slot(m, view, r, slot, frame, lids, n_lids, max_d2, max_hamming, want_pts != 0, nullptr, false);
 }
 
-int mcorb_lmap_track_wait(mcorb_lmap *m, mcorb_track_out *out)
+// the wait of a pending call.  single: mcorb_lmap_track_wait
+static int wait_pending(mcorb_lmap *m, const char *who, mcorb_track_out *outs, int n_outs, bool single)
 {
-    TRY(check_lmap_handle(m, "lmap track_wait"));
+    TRY(check_lmap_handle(m, who));
     std::lock_guard<std::mutex> lk(m->mu);
-    if (!m->track_pending.load()) return fail(MCORB_E_STATE, "no tracking call was submitted");
-    const int r = wait_body(m, out, 1, false, true);
-    m->track_pending.store(false);
+    if (!m->track.pending.load()) return fail(MCORB_E_STATE, "no tracking call was submitted");
+    const int r = wait_body(m, outs, n_outs, false, single);
+    m->track.pending.store(false);
     return r;
 }
 
+int mcorb_lmap_track_wait(mcorb_lmap *m, mcorb_track_out *out) { return wait_pending(m, "lmap track_wait", out, 1, true); }
+
 int mcorb_lmap_track_frames_wait(mcorb_lmap *m, mcorb_track_out *outs, int n_outs)
 {
-    TRY(check_lmap_handle(m, "lmap track_frames_wait"));
-    std::lock_guard<std::mutex> lk(m->mu);
-    if (!m->track_pending.load()) return fail(MCORB_E_STATE, "no tracking call was submitted");
-    const int r = wait_body(m, outs, n_outs, false, false);
-    m->track_pending.store(false);
-    return r;
+    return wait_pending(m, "lmap track_frames_wait", outs, n_outs, false);
 }
 
 int mcorb_lmap_track_rig_frames_submit(mcorb_lmap *m, const mcorb_track_view *views, mcorb_rig *r, int slot, const int32_t *frames, int nf,
@@ -805,40 +747,19 @@ int mcorb_lmap_track_rig_frames(mcorb_lmap *m, const mcorb_track_view *views, mc
 
 int32_t mcorb_host_track_pixel(float v) { return tr_pixel_coord(v); }
 
-int mcorb_lmap_last_track_timing(mcorb_lmap *m, float us[2])
+// n spans of the last submission's chain from `first` on
+static int chain_timing(mcorb_lmap *m, const char *who, float *us, int first, int n)
 {
-    TRY(check_lmap_handle(m, "lmap last_track_timing"));
-    if (!us) { set_error("lmap last_track_timing: bad argument"); return MCORB_E_ARG; }
+    TRY(check_lmap_handle(m, who));
+    if (!us) { set_error(std::string(who) + ": bad argument"); return MCORB_E_ARG; }
     std::lock_guard<std::mutex> lk(m->mu);
-    us[0] = m->us_track_project;
-    us[1] = m->us_track_match;
+    for (int k = 0; k < n; k++) us[k] = m->track.chain.us[first + k];
     return MCORB_OK;
 }
 
-int mcorb_lmap_last_track_timing4(mcorb_lmap *m, float us[4])
-{
-    TRY(check_lmap_handle(m, "lmap last_track_timing4"));
-    if (!us) { set_error("lmap last_track_timing4: bad argument"); return MCORB_E_ARG; }
-    std::lock_guard<std::mutex> lk(m->mu);
-    us[0] = m->us_track_points;
-    us[1] = m->us_track_project;
-    us[2] = m->us_track_match;
-    us[3] = m->us_track_compact;
-    return MCORB_OK;
-}
-
-int mcorb_lmap_last_track_timing5(mcorb_lmap *m, float us[5])
-{
-    TRY(check_lmap_handle(m, "lmap last_track_timing5"));
-    if (!us) { set_error("lmap last_track_timing5: bad argument"); return MCORB_E_ARG; }
-    std::lock_guard<std::mutex> lk(m->mu);
-    us[0] = m->us_track_points;
-    us[1] = m->us_track_project;
-    us[2] = m->us_track_match;
-    us[3] = m->us_track_compact;
-    us[4] = m->us_track_dedup;
-    return MCORB_OK;
-}
+int mcorb_lmap_last_track_timing(mcorb_lmap *m, float us[2]) { return chain_timing(m, "lmap last_track_timing", us, TK::kProject, 2); }
+int mcorb_lmap_last_track_timing4(mcorb_lmap *m, float us[4]) { return chain_timing(m, "lmap last_track_timing4", us, TK::kPoints, 4); }
+int mcorb_lmap_last_track_timing5(mcorb_lmap *m, float us[5]) { return chain_timing(m, "lmap last_track_timing5", us, TK::kPoints, 5); }
 
 #ifdef MCORB_TRACK_PROF
 // the last call's host phases in microseconds: candidate walk, submission, wait, de-duplication, output.  Not part of the
@@ -848,7 +769,7 @@ int mcorb_lmap_track_phases(mcorb_lmap *m, float us[5])
     TRY(check_lmap_handle(m, "lmap track_phases"));
     if (!us) { set_error("lmap track_phases: bad argument"); return MCORB_E_ARG; }
     std::lock_guard<std::mutex> lk(m->mu);
-    memcpy(us, m->us_track_phase, sizeof(m->us_track_phase));
+    memcpy(us, m->track.us_phase, sizeof(m->track.us_phase));
     return MCORB_OK;
 }
 #endif

@@ -1,0 +1,185 @@
+"""Every call of the local map that keeps scratch of its own, one after the other on ONE device store and on a host-only twin:
+track from host arrays, track_rig_frames (2 frames), refine_pose, ransac_pose with its refinement (both solvers),
+triangulate_new, triangulate_neighbours (2 neighbours), observe / update_points and search -- three times over, small, about four
+times larger, small again, so that every grow-only buffer is grown by one call and then used again, by that call and, where the
+buffers are shared, by the others.  Every result equals the twin's bit for bit (floats as raw bytes); after each call its timing
+getter gives a finite, non-negative number for every span that ran, and the span of k_track_points reads exactly 0 for the frame
+from host arrays -- also right behind a rig slot's frames.  What this is aimed at: two calls on one buffer, or a group's reserve
+given one call site's counts at the other.  2 cameras, tens of landmarks, a few hundred keypoints, 16 .. 64 hypotheses."""
+import math
+
+import numpy as np
+import pytest
+
+import kfdb_cases as K
+import landmark_cases as Lc
+import lmap_cases as Lm
+import mapping_cases as Mc
+import mapping_new_cases as Nc
+import pose_cases as PC
+import sac_cases as SC
+import sac_rig_cases as SR
+import track_cases as T
+from test_gpu_track_batch import extracted, frame_landmarks, shifted
+from test_lmap_cpu import make, same_result, scene_landmarks
+
+pytestmark = pytest.mark.gpu
+
+C = 2
+MAXL = 8192
+# where each call keeps its landmarks: (host-array tracking, the rig frames', refine_pose, ransac_pose central / rig, the neighbours' old
+# landmarks are the scene's own 3000 .., new ids of triangulate_neighbours / triangulate_new, observe, search)
+AT = dict(track=0, frames=600, pose=1300, sac=1800, sac_rig=2400, neigh_new=4200, new_new=5200, observe=6200, search=7400)
+#        landmarks twins  per_cam  pose  sac  thin  hyp  neighbours      old  new  observe  search
+SIZES = [(40, 20, 8, 12, 20, 3, 16, (16, 12), 8, 24, 30, 60),
+         (160, 80, 32, 48, 80, 12, 64, (64, 48), 32, 96, 120, 240),
+         (40, 20, 8, 12, 20, 3, 16, (16, 12), 8, 24, 30, 60)]
+
+
+@pytest.fixture(scope="module")
+def mc():
+    import mcorb
+    return mcorb
+
+
+def moved(store, lids, off):
+    return {l + off: v for l, v in store.items()}, [l if l < 0 else l + off for l in lids]
+
+
+def spans_ok(us):
+    us = [us] if isinstance(us, float) else list(us)
+    assert all(math.isfinite(u) and u >= 0.0 for u in us), us
+    return us
+
+
+def same_fields(a, b, fields, what):
+    for f in fields:
+        x, y = np.asarray(getattr(a, f)), np.asarray(getattr(b, f))
+        assert x.shape == y.shape and x.dtype == y.dtype and x.tobytes() == y.tobytes(), (what, f)
+
+
+def same_sac(a, b, what):
+    same_fields(a, b, ("R", "t", "sac_R", "sac_t", "inliers", "sample"), what)
+    for f in ("status", "used", "n_inliers", "n_matches", "sac_n_inliers", "best_hypothesis", "n_models", "n_consensus"):
+        assert getattr(a, f) == getattr(b, f), (what, f)
+    same_fields(a.refine, b.refine, ("R", "t", "cost_initial", "cost_final", "iterations"), what + ", refinement")
+    assert (a.refine.status, a.refine.n_inliers, a.refine.n_obs) == (b.refine.status, b.refine.n_inliers, b.refine.n_obs), what
+
+
+def frames_of_the_slot(mc, both, rig, rnd, per_cam, what):
+    fstore, lidss = frame_landmarks(np.random.default_rng(200 + rnd), rig, range(2), per_cam=per_cam)
+    fstore = {l + AT["frames"]: v_ for l, v_ in fstore.items()}
+    lidss = [[l if l < 0 else l + AT["frames"] for l in ls] for ls in lidss]
+    views = [T.to_view(mc, shifted(rig, t)) for t in ((0, 0), (2, -1))]
+    got = []
+    for lm in both:
+        T.fill(lm, fstore)
+        got.append([T.as_lists(r) for r in lm.track_rig_frames(views, rig, [0, 1], lidss)])
+    for f in range(2):
+        T.same(got[0][f], got[1][f], what + "track_rig_frames, frame %d" % f)
+        assert sum(len(m) for m in got[0][f]["matches"]) > 0
+    us = spans_ok(both[0].last_track_timing5())
+    assert us[0] > 0 and us[4] > 0
+
+
+
+def one_round(mc, lm_d, db_d, lm_h, db_h, rig, rnd, size):
+    nl, ntw, per_cam, npose, nsac, nthin, hyp, nneigh, nold, nnew, nobs, nsearch = size
+    both = (lm_d, lm_h)
+    what = "round %d, " % rnd
+
+    # track from host arrays
+    v, store, kps, descs, lids = T.scene(C, seed=rnd, n_landmarks=nl, n_twins=ntw)
+    store, lids = moved(store, lids, AT["track"])
+    xy, ds = T.kp_arrays(kps, descs)
+    got = []
+    for lm in both:
+        T.fill(lm, store)
+        got.append(T.as_lists(lm.track(T.to_view(mc, v), xy, ds, lids)))
+    T.same(got[0], got[1], what + "track")
+    assert sum(len(m) for m in got[0]["matches"]) > 0 and got[0]["n_candidates"] == len(store)
+    us = spans_ok(lm_d.last_track_timing5())
+    assert us[0] == 0.0, "k_track_points did not run for a frame from host arrays"
+    assert us[1] > 0 and us[2] > 0
+
+    # two frames of the rig slot's job in one submission
+    frames_of_the_slot(mc, both, rig, rnd, per_cam, what)
+
+    # refine_pose, ids and points
+    cams, truth, init, obs, _ = PC.scene(C, nlm=npose, seed=5 + rnd)
+    for form in ("lids", "pts"):
+        got = [PC.as_ref(PC.refine(mc, lm, cams, init, obs, form=form, first_lid=AT["pose"])) for lm in both]
+        PC.same(got[0], got[1], what + "refine_pose, " + form)
+        assert got[0]["n_inliers"] > 0
+        spans_ok(lm_d.last_pose_timing())
+    # ransac_pose with its refinement, both solvers
+    cams, truth, obs, match, _ = SC.scene(C, nlm=nsac, seed=3 + rnd, per_match=2)
+    got = [SC.run(mc, lm, cams, obs, match=match, max_iterations=hyp, refine=(PC.INV_SIGMA2,), form="lids", first_lid=AT["sac"]) for lm in both]
+    same_sac(got[0], got[1], what + "ransac_pose, central")
+    assert got[0].status == mc.SAC_OK
+    us, nh = lm_d.last_ransac_timing()
+    assert nh == hyp and len(spans_ok(us)) == 3
+    cams, truth, obs, match, _ = SR.thin_scene(C, per_cam=nthin, seed=3 + rnd)
+    got = [SR.run(mc, lm, cams, obs, max_iterations=hyp, refine=(PC.INV_SIGMA2,), form="lids", first_lid=AT["sac_rig"]) for lm in both]
+    same_sac(got[0], got[1], what + "ransac_pose, rig")
+    assert got[0].status == mc.SAC_OK
+    spans_ok(lm_d.last_ransac_timing()[0])
+
+    # triangulate_new
+    sc = Nc.scene(C, n=nnew, seed=1 + rnd)
+    sc["next_lid"] = AT["new_new"] + 300 * rnd
+    got = [Nc.run_scene(mc, lm, sc) for lm in both]
+    Nc.same(got[0], got[1], what + "triangulate_new")
+    assert got[0].n_triangulated > 0
+    us, launched = lm_d.last_triangulate_new_timing()
+    assert launched > 0 and spans_ok(us)
+
+    # triangulate_neighbours, two neighbours
+    sc = Mc.scene(C, sizes=nneigh, seed=1 + rnd, n_old=nold)
+    sc["next_lid"] = AT["neigh_new"] + 300 * rnd
+    got = []
+    for lm in both:
+        Mc.fill_store(lm, sc["store"])
+        got.append(Mc.run_scene(mc, lm, sc))
+    same_fields(got[0], got[1], ("inliers", "verdict", "new_lid", "pt3d", "normal", "dist2", "cos_parallax", "neigh_skipped", "depth_vec",
+                                 "lids_cur"), what + "triangulate_neighbours")
+    assert got[0].n_triangulated == got[1].n_triangulated > 0 and got[0].next_lid == got[1].next_lid
+    for a, b in zip(got[0].lids_neigh, got[1].lids_neigh):
+        assert a.tolist() == b.tolist()
+    us_tri, us_depth, launched, depths = lm_d.last_triangulate_timing()
+    assert launched > 0 and depths > 0 and spans_ok((us_tri, us_depth))
+
+    # observe and update_points: both stores against the restatement, which makes them equal
+    lid0 = AT["observe"] + 200 * rnd
+    b = Lc.batch(nobs, C, rnd, lid0=lid0)
+    Lc.run_batch(mc, list(both), *b, lid0=lid0)
+    lids = b[4]
+    new = b[0][lids - lid0] + np.random.default_rng(rnd).choice([0.5, 4.9, 5.1, 8.0], (len(lids), 1)) * np.array([[0.6, 0.0, 0.8]])
+    got = [lm.update_points(lids, new) for lm in both]
+    assert got[0][0].tolist() == got[1][0].tolist() and got[0][1].tobytes() == got[1][1].tobytes() and 0 < got[0][0].sum() < len(lids)
+    assert Lc.snapshot(lm_d, lids) == Lc.snapshot(lm_h, lids)
+    spans_ok(lm_d.last_landmark_timing())
+
+    # search
+    view, land, probe, cur = scene_landmarks(C, nsearch, seed=rnd)
+    land = (AT["search"] + np.arange(nsearch, dtype=np.int32),) + tuple(land[1:])
+    got = []
+    for lm, db in ((lm_d, db_d), (lm_h, db_h)):
+        lm.set(*land)
+        got.append(lm.search(Lm.to_view(mc, view), land[0], [], db, 0, *cur, levelsup=K.LEVELSUP))
+    same_result(got[0], got[1], what + "search")
+    assert len(got[0].new_lids) > 0
+    us = lm_d.last_timing()
+    assert us[2] == nsearch and spans_ok(us[:2])
+
+
+def test_every_call_three_times_on_one_store(mc):
+    vocs = mc.ORBVocabulary().create(**K.vocabulary()), mc.ORBVocabulary(device=-1).create(**K.vocabulary())
+    probe = scene_landmarks(C, 8)[2]
+    (lm_d, db_d), (lm_h, db_h) = [make(mc, voc, dev, probe, max_landmarks=MAXL, max_candidates=1024) for voc, dev in zip(vocs, (0, -1))]
+    rig = extracted(mc, C, 320, 240, 2, 300)
+    try:
+        for rnd, size in enumerate(SIZES):
+            one_round(mc, lm_d, db_d, lm_h, db_h, rig, rnd, size)
+    finally:
+        rig.close()
