@@ -1019,8 +1019,8 @@ int mcorb_lmap_track_wait(mcorb_lmap *m, mcorb_track_out *out);
  * frames[f], those ids) on the same store and slot: steps 1 - 5 above hold per frame and frames do not interact -- an id named in
  * two frames' lists is a candidate of both, and the de-duplication is per frame and camera.  On a device store the candidate
  * lists, a table with one item per frame and the views go up in one pinned block in one copy; the seven kernels of the single
- * call run once each over all frames (k_track_*_batch: the frame is the grid's z, a frame's block of every array has the single
- * call's layout), and the rows, matches and counts of all frames land in host-mapped memory.  A host-only store runs the serial
+ * call run once each over all frames (the frame is the grid's z, a frame's block of every array has the single call's layout: a
+ * single call is this with nf = 1), and the rows, matches and counts of all frames land in host-mapped memory.  A host-only store runs the serial
  * path frame by frame.
  * Refused before anything runs -- nothing is pending then, the store is unchanged and every count of every outs[f] is zero:
  * everything mcorb_lmap_track_rig_frame_submit refuses, for any frame, with that call's code; MCORB_E_ARG for nf < 1, nf >

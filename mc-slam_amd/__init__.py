@@ -1359,34 +1359,16 @@ class LocalMap:
 
     def _track(self, ncams, lids, caps, call):
         lids = np.ascontiguousarray(lids, np.int32).reshape(-1)
-        return self._track_out(ncams, len(lids), caps, True, lambda o: call(lids, o))
+        return self._track_one(ncams, len(lids), caps, True, lambda o, n: call(lids, o[0]))
 
-    def _track_out(self, ncams, n_lids, caps, want_pts, call):
-        """the output arrays of a tracking call, call(mcorb_track_out) -> code, and the TrackResult (or the McorbError with the
-        call's counts)"""
-        cap_p, cap_m = caps if caps is not None else (n_lids, n_lids)
-        n1, n2 = ncams * max(cap_p, 1), ncams * max(cap_m, 1)
-        r = dict(proj_lid=np.zeros(n1, np.int32), proj_xy=np.zeros((n1, 2), np.float32), best_kp=np.zeros(n1, np.int32),
-                 best_dist=np.zeros(n1, np.int32), match_kp=np.zeros(n2, np.int32), match_lid=np.zeros(n2, np.int32),
-                 match_dist=np.zeros(n2, np.int32))
-        if want_pts:
-            r["match_pt"] = np.zeros((n2, 3))
-        o = _lib.TrackOut()
-        o.cap_proj, o.cap_match = cap_p, cap_m
-        for k, a in r.items():
-            setattr(o, k, a.ctypes.data)
-        code = call(o)
-        n_proj, n_match = list(o.n_proj[:ncams]), list(o.n_match[:ncams])
-        if code != _lib.OK:
-            try:
-                _lib.check(code)
-            except McorbError as e:     # MCORB_E_CAP for a short output comes with every count set
-                e.n_candidates, e.n_proj, e.n_match = o.n_candidates, n_proj, n_match
-                raise
-        out = {k: [r[k][c * cap_p:c * cap_p + n_proj[c]].copy() for c in range(ncams)] for k in ("proj_lid", "proj_xy", "best_kp", "best_dist")}
-        out.update({k: [r[k][c * cap_m:c * cap_m + n_match[c]].copy() for c in range(ncams)] if k in r else None
-                    for k in ("match_kp", "match_lid", "match_dist", "match_pt")})
-        return TrackResult(n_candidates=o.n_candidates, **out)
+    def _track_one(self, ncams, n_lids, caps, want_pts, call):
+        """_track_outs for the single entries: the one frame's TrackResult, a McorbError's counts as those of that frame"""
+        try:
+            return self._track_outs(ncams, [n_lids], caps, want_pts, call)[0]
+        except McorbError as e:
+            if hasattr(e, "n_candidates"):
+                e.n_candidates, e.n_proj, e.n_match = e.n_candidates[0], e.n_proj[0], e.n_match[0]
+            raise
 
     def track_submit(self, view, kps, descs, lids, max_d2=10000.0, max_hamming=20, want_pts=True):
         """track() up to and excluding the wait for the device: every refusal, the candidate walk, the copy up and every launch; then
@@ -1413,7 +1395,7 @@ class LocalMap:
         ncams, n_lids, want_pts = getattr(self, "_submitted", None) or (1, 0, False)
         self._submitted = None
         n_lids = max(n_lids) if isinstance(n_lids, list) else n_lids     # (a pending batch: the call fails, MCORB_E_STATE)
-        return self._track_out(ncams, n_lids, caps, want_pts, lambda o: self.L.mcorb_lmap_track_wait(self.h, C.byref(o)))
+        return self._track_one(ncams, n_lids, caps, want_pts, lambda o, n: self.L.mcorb_lmap_track_wait(self.h, o))
 
     def track_rig_frames(self, views, rig, frames, lids, slot=0, max_d2=10000.0, max_hamming=20, caps=None):
         """track_rig_frame() for len(frames) <= TRACK_MAX_FRAMES frames of the slot's last extraction job in one submission and one
@@ -1460,8 +1442,8 @@ class LocalMap:
         return va, np.ascontiguousarray(frames, np.int32).reshape(-1), la, first
 
     def _track_outs(self, ncams, n_lids, caps, want_pts, call):
-        """_track_out for the frames of a batch: call(array of mcorb_track_out, its length) -> code; -> the TrackResult per frame
-        (or the McorbError with the counts per frame)"""
+        """the output arrays of a tracking call of len(n_lids) frames, call(array of mcorb_track_out, its length) -> code, and the
+        TrackResult per frame (or the McorbError with the call's counts per frame)"""
         nf = len(n_lids)
         os_ = (_lib.TrackOut * max(nf, 1))()
         arrays = []

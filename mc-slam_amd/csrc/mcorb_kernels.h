@@ -185,52 +185,43 @@ void launch_lmap_update(hipStream_t st, const LmUpdItem *items, int n, double ma
 // k_lmap_put_rays: nrays[lids[i]] = vals[i], or 0 with vals == NULL; every slot at most once
 void launch_lmap_put_rays(hipStream_t st, const int32_t *lids, const int32_t *vals, int n, int32_t *nrays);
 
-// fast tracking (mcorb_track_gpu.hip).  k_track_project: Tracking::project_ of candidates cand[0 .. n) (slots of geom) into the
-// cameras of view -> camera-major xy[c * n + i] and valid[c * n + i] (0: dropped), and the gathered points into pts (may be NULL)
+// fast tracking (mcorb_track_gpu.hip): seven kernels, five launches, each once per call for its nf frames, frame blockIdx.z.
+// items[f] (device memory; TrItem, mcorb_track.h) says where frame f's view, candidates, block of every per-pair array,
+// de-duplication tables, keypoints and descriptors are; max_n: the most candidates of a frame, which sizes the grid's x; cand, xy,
+// valid, pts, best, rows, slot, win, matches: the frames' blocks back to back, [c * n + i] inside a frame's.
+// k_track_project: Tracking::project_ of a frame's candidates (slots of geom) into the cameras of its view (views: device
+// memory) -> camera-major xy and valid (0: dropped), and the gathered points into pts (may be NULL)
 constexpr int kTrackProjectT = 256;   // k_track_project's workgroup: one lane per candidate
-void launch_track_project(hipStream_t st, const mcorb_track_view &view, const double *geom, const int *cand, int n, float2 *xy,
-                          uint8_t *valid, double *pts);
+void launch_track_project(hipStream_t st, const TrItem *items, int nf, int max_n, const mcorb_track_view *views, const double *geom,
+                          const int *cand, float2 *xy, uint8_t *valid, double *pts);
 // k_track_match: per camera c < ncams and candidate i with valid[c * n + i], the best keypoint of the frame by position and
-// descriptor -> best[c * n + i]; kp_xy / kp_desc: the cameras' keypoints and descriptors back to back, camera c's from
-// frame.first[c]; lm_desc: the store's descriptors, 32 bytes per slot
+// descriptor -> best[c * n + i]; kp_xy / kp_desc: the keypoints and descriptors the items' kp0 / desc0 and frame.first[c] count
+// in (the store's keypoint buffer and the slot's descriptors, or the uploaded host arrays); lm_desc: the store's descriptors,
+// 32 bytes per slot
 constexpr int kTrackMatchWaves = 4;   // waves of a workgroup, which shares one LDS tile of keypoints
 constexpr int kTrackMatchQ = 4;       // consecutive candidates a wave serves
 constexpr int kTrackMatchT = 64 * kTrackMatchWaves;
-void launch_track_match(hipStream_t st, const TrFrame &frame, int ncams, const float2 *kp_xy, const uint8_t *kp_desc, const uint8_t *lm_desc,
-                        const int *cand, int n, const float2 *xy, const uint8_t *valid, double max_d2, int max_hamming, TrBest *best);
-// k_track_points: pt of the selected keypoints of images img0 .. img0 + ncams of a rig slot (sel / nsel as k_undistort reads them,
-// rows of kcap) -> out[c * kcap + k] for k < min(nsel[img0 + c], kcap): k_track_match's kp_xy with first[c] = c * kcap
-void launch_track_points(hipStream_t st, const uint32_t *sel, const int *nsel, int kcap, int img0, int ncams, const float *scale,
-                         int nlevels, float2 *out);
+void launch_track_match(hipStream_t st, const TrItem *items, int nf, int max_n, int ncams, const float2 *kp_xy, const uint8_t *kp_desc,
+                        const uint8_t *lm_desc, const int *cand, const float2 *xy, const uint8_t *valid, double max_d2, int max_hamming,
+                        TrBest *best);
+// k_track_points (a rig slot's frames): pt of the selected keypoints of images img0 .. img0 + ncams of the slot (sel / nsel as
+// k_undistort reads them, rows of kcap) -> out[kp0 + c * kcap + k] for k < min(nsel[img0 + c], kcap): k_track_match's kp_xy with
+// first[c] = c * kcap; a frame without candidates is skipped
+void launch_track_points(hipStream_t st, const TrItem *items, int nf, int max_n, const uint32_t *sel, const int *nsel, int kcap, int ncams,
+                         const float *scale, int nlevels, float2 *out);
 // k_track_compact: per camera the candidates with valid[c * n + i], in candidate order -> rows[c * n + 0 .. n_proj[c]) and
-// n_proj[c]; rows / n_proj may be host-mapped pinned memory
-void launch_track_compact(hipStream_t st, int ncams, int n, const uint8_t *valid, const float2 *xy, const TrBest *best, TrRow *rows,
-                          int32_t *n_proj);
+// n_proj[c]; n_proj: MCORB_MAX_CAMS counts per frame, written for the frames with a candidate; rows / n_proj may be host-mapped
+// pinned memory
+void launch_track_compact(hipStream_t st, const TrItem *items, int nf, int max_n, int ncams, const uint8_t *valid, const float2 *xy,
+                          const TrBest *best, TrRow *rows, int32_t *n_proj);
 // k_track_dedup_min, k_track_dedup_win, k_track_dedup_emit: per camera, of the candidates with valid[c * n + i] and a match, the one
 // with the least (dist, i) per pixel of the matched keypoint, in candidate order -> matches[c * n + 0 .. n_match[c]) and
-// n_match[c] (may be host-mapped).  owner / val: ncams << tr_dedup_log2(n) slots each, every byte 0xff; slot (int32) and win (bytes):
-// ncams * n each, scratch
+// n_match[c] (as n_proj; may be host-mapped).  owner / val: every frame's tables, ncams << tr_dedup_log2(n) slots from the item's
+// tab on, every byte 0xff; slot (int32) and win (bytes): scratch, laid out as valid
 constexpr int kTrackDedupT = 256;     // one lane per (camera, candidate)
-void launch_track_dedup(hipStream_t st, const TrFrame &frame, int ncams, const float2 *kp_xy, int n, const uint8_t *valid, const TrBest *best,
-                        uint32_t *owner, unsigned long long *val, int32_t *slot, uint8_t *win, TrMatch *matches, int32_t *n_match);
-// The same seven for the nf frames of mcorb_lmap_track_rig_frames in one launch each, frame blockIdx.z (k_track_*_batch): items[f]
-// (device memory) says where frame f's view, candidates, block of every per-pair array (the single call's layout inside it),
-// de-duplication tables, keypoint rows and descriptors are; max_n: the most candidates of a frame, which sizes the grid's x; views:
-// the call's views, device memory; cand, xy, valid, pts, best, rows, slot, win, matches: the frames' blocks back to back; n_proj /
-// n_match: MCORB_MAX_CAMS counts per frame, written for the frames with a candidate; owner / val: every frame's tables, every byte
-// 0xff; kp: the store's keypoint buffer, nf * ncams rows of kcap; kp_desc: the slot's descriptors, image 0 on
-void launch_track_points_batch(hipStream_t st, const TrBatchItem *items, int nf, const uint32_t *sel, const int *nsel, int kcap, int ncams,
-                               const float *scale, int nlevels, float2 *out);
-void launch_track_project_batch(hipStream_t st, const TrBatchItem *items, int nf, int max_n, const mcorb_track_view *views,
-                                const double *geom, const int *cand, float2 *xy, uint8_t *valid, double *pts);
-void launch_track_match_batch(hipStream_t st, const TrBatchItem *items, int nf, int max_n, int ncams, const float2 *kp_xy,
-                              const uint8_t *kp_desc, const uint8_t *lm_desc, const int *cand, const float2 *xy, const uint8_t *valid,
-                              double max_d2, int max_hamming, TrBest *best);
-void launch_track_compact_batch(hipStream_t st, const TrBatchItem *items, int nf, int max_n, int ncams, const uint8_t *valid,
-                                const float2 *xy, const TrBest *best, TrRow *rows, int32_t *n_proj);
-void launch_track_dedup_batch(hipStream_t st, const TrBatchItem *items, int nf, int max_n, int ncams, const float2 *kp_xy,
-                              const uint8_t *valid, const TrBest *best, uint32_t *owner, unsigned long long *val, int32_t *slot,
-                              uint8_t *win, TrMatch *matches, int32_t *n_match);
+void launch_track_dedup(hipStream_t st, const TrItem *items, int nf, int max_n, int ncams, const float2 *kp_xy, const uint8_t *valid,
+                        const TrBest *best, uint32_t *owner, unsigned long long *val, int32_t *slot, uint8_t *win, TrMatch *matches,
+                        int32_t *n_match);
 
 // the pose refinement (mcorb_pose_gpu.hip).  k_pose_refine: problem blockIdx.x of jobs (device memory), one workgroup of
 // MCORB_POSE_LANES lanes for both rounds.  obs / lids / pts / alive / flags: every problem's block begins at its obs0; pts or lids

@@ -29,7 +29,7 @@
 using namespace mcorb;
 
 // what set and set_desc_from_entry share: ids inside the store, and of an id that occurs twice only the last entry kept (keep[i])
-static int check_batch(mcorb_lmap *m, const int32_t *lids, int n, const char *who, std::vector<int> &keep)
+static int check_set_ids(mcorb_lmap *m, const int32_t *lids, int n, const char *who, std::vector<int> &keep)
 {
     for (int i = 0; i < n; i++)
         if (lids[i] < 0 || lids[i] >= m->max_landmarks) { set_error(std::string(who) + ": landmark id outside the store"); return MCORB_E_ARG; }
@@ -161,7 +161,7 @@ int mcorb_lmap_set(mcorb_lmap *m, const int32_t *lids, int n, const double *pt3d
     if (n < 0 || (n && !lids)) { set_error("lmap set: bad argument"); return MCORB_E_ARG; }
     std::lock_guard<std::mutex> lk(m->mu);
     std::vector<int> keep;
-    TRY(check_batch(m, lids, n, "lmap set", keep));
+    TRY(check_set_ids(m, lids, n, "lmap set", keep));
     const uint8_t given = (pt3d ? kHasPt : 0) | (normal ? kHasNormal : 0);
     for (int i = 0; i < n; i++)
         if (((m->flags[lids[i]] | given) & kSet) != kSet) {
@@ -200,7 +200,7 @@ int mcorb_lmap_set_desc_from_entry(mcorb_lmap *m, mcorb_kfdb *db, int entry, con
     for (int i = 0; i < n; i++)
         if (feats[i] < 0 || feats[i] >= ndesc) { set_error("lmap set_desc_from_entry: feature index outside the entry"); return MCORB_E_ARG; }
     std::vector<int> keep;
-    TRY(check_batch(m, lids, n, "lmap set_desc_from_entry", keep));
+    TRY(check_set_ids(m, lids, n, "lmap set_desc_from_entry", keep));
     if (n == 0) return MCORB_OK;
     if (m->device < 0) {
         const uint8_t *src = db->entries[entry].desc.data();

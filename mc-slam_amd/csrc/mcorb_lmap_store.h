@@ -165,12 +165,12 @@ struct mcorb_lmap {
         std::vector<int32_t> n_proj, n_match;
     };
 
-    // scratch of mcorb_lmap_track / mcorb_lmap_track_rig_frame (mcorb_track.cpp), grow-only: the packed input (TrackLayout: the
-    // candidates, then -- host arrays only -- the keypoints and the descriptors of every camera), a rig slot's keypoints
-    // (k_track_points), the projections, validity bytes and gathered points, the queries' results, and what the host tail reads:
-    // the compacted rows and the counts per camera, host-mapped pinned memory k_track_compact writes.  mcorb_lmap_track_rig_frames
-    // uses the same buffers, sized for all its frames: the pinned block is a TrackBatchLayout, a frame's block of every per-pair
-    // array begins at ncams * (its first candidate), the counts are MCORB_MAX_CAMS per frame and the keypoints nf * ncams rows
+    // scratch of a tracking call of nf frames (mcorb_track.cpp; nf = 1 but for mcorb_lmap_track_rig_frames), grow-only: the packed
+    // input (TrackLayout: a TrItem and a view per frame, the frames' candidates, then -- host arrays only -- the keypoints and the
+    // descriptors of every camera), a rig slot's keypoints (k_track_points, nf * ncams rows), the projections, validity bytes and
+    // gathered points, the queries' results, and what the host tail reads: the compacted rows and the counts, MCORB_MAX_CAMS per
+    // frame, host-mapped pinned memory k_track_compact writes.  A frame's block of every per-pair array begins at ncams * (its
+    // first candidate)
     struct Tracking {
         mcorb::Staged in;
         mcorb::DevBuf<float2> d_kp, d_xy;
@@ -259,13 +259,12 @@ struct mcorb_lmap {
 // pose_track_host: a host-only store, or a frame nothing was launched for -- the observations are the frame's matches, the
 // cameras back to back in match order (kp_base / kp_stride: the frame's keypoint records, which begin with pt), flags: ncams *
 // nc bytes.  pose_track_submit: k_pose_refine for the nf frames of a device submission, behind its de-duplication on the
-// store's stream; first: the frames' places in the call's candidate list (nf + 1), frames / kp0: per frame its TrFrame and the
-// place of its keypoints in kp_xy
+// store's stream; items: the submission's TrItems on the host, which say where a frame's candidates, rows and keypoints in
+// kp_xy are
 namespace mcorb {
 void pose_track_host(mcorb_lmap *m, const mcorb_track_view &view, const int *cand, int nc, const TrMatch *matches, const int32_t *n_match,
                      const uint8_t *const *kp_base, size_t kp_stride, mcorb_pose_result &res, uint8_t *flags);
-int pose_track_submit(mcorb_lmap *m, const mcorb_track_view *views, int nf, const size_t *first, const TrFrame *frames, const size_t *kp0,
-                      const float2 *kp_xy, const int *d_cand);
+int pose_track_submit(mcorb_lmap *m, const mcorb_track_view *views, const TrItem *items, int nf, const float2 *kp_xy, const int *d_cand);
 // shared with mcorb_sac.cpp: a refinement problem's job, its serial run, and the checks of its parameters
 void pose_job_init(PoseJob &job, const mcorb_pose_params &p, int ncams, const mcorb_track_cam *cams, const PoseState &init);
 void pose_run_host(const PoseJob &job, const PoseObs *obs, const double *pts, int n, uint8_t *alive, mcorb_pose_result &res);

@@ -35,18 +35,14 @@ struct ObsLayout {
           cam_first(p.add<int32_t>(sac ? ncams + 1 : 0)), cam_cons(p.add<int32_t>(sac ? S : 0)), is_first(p.add<uint8_t>(sac ? n : 0)) {}
 };
 
-// a tracking submission of one frame: the candidates, then -- host arrays only -- the keypoints (x, y) and descriptors of all cameras
+// a tracking submission of nf frames: a TrItem and a view per frame, every frame's candidates, then -- host arrays only -- the
+// keypoints (x, y) and descriptors of all cameras
 struct TrackLayout {
     Pack p;
-    size_t cand, xy, desc;
-    TrackLayout(size_t nc, size_t total_kp) : cand(p.add<int32_t>(nc)), xy(p.add<float>(2 * total_kp)), desc(p.add<uint8_t>(32 * total_kp)) {}
-};
-
-// a tracking submission of nf frames of a rig slot: a TrBatchItem and a view per frame, then every frame's candidates
-struct TrackBatchLayout {
-    Pack p;
-    size_t items, views, cand;
-    TrackBatchLayout(size_t nf, size_t ncand) : items(p.add<TrBatchItem>(nf)), views(p.add<mcorb_track_view>(nf)), cand(p.add<int32_t>(ncand)) {}
+    size_t items, views, cand, xy, desc;
+    TrackLayout(size_t nf, size_t ncand, size_t total_kp)
+        : items(p.add<TrItem>(nf)), views(p.add<mcorb_track_view>(nf)), cand(p.add<int32_t>(ncand)), xy(p.add<float>(2 * total_kp)),
+          desc(p.add<uint8_t>(32 * total_kp)) {}
 };
 
 // the two mapping entries (mcorb_mapping.h): nframes frames, nF doubles of F tables (none: mcorb_lmap_triangulate_new), K per

@@ -177,14 +177,13 @@ void pose_track_host(mcorb_lmap *m, const mcorb_track_view &view, const int *can
     pose_run_host(job, obs.data(), pts.data(), (int)obs.size(), flags, res);
 }
 
-// a device store: k_pose_refine for the nf frames of the submission, behind its de-duplication on the store's stream.  first:
-// the frames' places in the call's candidate list (nf + 1); frames: per frame its TrFrame and keypoint base (kp0) in kp_xy
-int pose_track_submit(mcorb_lmap *m, const mcorb_track_view *views, int nf, const size_t *first, const TrFrame *frames, const size_t *kp0,
-                      const float2 *kp_xy, const int *d_cand)
+// a device store: k_pose_refine for the nf frames of the submission, behind its de-duplication on the store's stream.  items:
+// the submission's, on the host -- a frame's candidates, block of the per-pair arrays and keypoints in kp_xy are where they say
+int pose_track_submit(mcorb_lmap *m, const mcorb_track_view *views, const TrItem *items, int nf, const float2 *kp_xy, const int *d_cand)
 {
     PoseBufs &b = m->pose.t;
     const int C = views[0].ncams;
-    const size_t rows = (size_t)C * first[nf];
+    const size_t rows = (size_t)C * (items[nf - 1].cand_first + (size_t)items[nf - 1].n);
     const size_t bytes = (size_t)nf * sizeof(PoseJob);
     TRY(b.in.reserve(bytes));
     TRY(b.d_obs.grow(rows));
@@ -195,14 +194,15 @@ int pose_track_submit(mcorb_lmap *m, const mcorb_track_view *views, int nf, cons
     PoseJob *jobs = b.in.host<PoseJob>(0);
     for (int f = 0; f < nf; f++) {
         PoseJob &job = jobs[f];
+        const TrItem &it = items[f];
         track_job(m, views[f], job);
         job.from_track = 1;
-        job.n_cand = (int32_t)(first[f + 1] - first[f]);
+        job.n_cand = it.n;
         job.n = C * job.n_cand;
-        job.cand_first = first[f];
-        job.obs0 = job.rows = (size_t)C * first[f];
-        job.kp0 = kp0[f];
-        job.frame = frames[f];
+        job.cand_first = it.cand_first;
+        job.obs0 = job.rows = it.rows;
+        job.kp0 = it.kp0;
+        job.frame = it.frame;
     }
     TRY(b.in.upload(m->st, bytes));
     launch_pose_refine(m->st, b.in.dev<const PoseJob>(0), nf, b.d_obs, b.d_lids, nullptr, m->d_geom, b.d_alive,

@@ -38,7 +38,7 @@ struct PoseObs { float u, v; int32_t cam, octave; };
 
 // One problem as k_pose_refine reads it from device memory.  obs0: where its observations begin in the obs / lids / pts / alive /
 // flag arrays.  from_track: the observations are not given but built by the kernel's prologue from a tracking submission's
-// frame -- its n_cand candidates from cand_first on, its block of the per-pair arrays at rows (the layout of TrBatchItem), its
+// frame -- its n_cand candidates from cand_first on, its block of the per-pair arrays at rows (the layout of TrItem), its
 // keypoints from kp0 on with frame.first[c] -- and n is then the capacity, ncams * n_cand
 struct PoseJob {
     PoseState init;

@@ -13,13 +13,13 @@
 // job left them).  The de-duplication, serial in the reference, is a minimum per pixel and a compaction in candidate order
 // (mcorb_track.h, tr_dedup_value): k_track_dedup_min / _win / _emit run it behind k_track_match in the same submission, so the
 // host's part of a device call is the candidate walk in front and copies behind.  The host-only store runs the same header
-// serially and keeps the reference's list as it is.  Both entries share the argument and candidate checks, the submission and
+// serially and keeps the reference's list as it is.  All entries share the candidate checks, the submission and
 // the output.  A call is a submission and a wait: mcorb_lmap_track_submit / _rig_frame_submit return once everything is on the
 // store's stream, mcorb_lmap_track_wait synchronises and writes the outputs, and the synchronous entries are the two over the
-// same body.  mcorb_lmap_track_rig_frames is the slot entry for up to MCORB_TRACK_MAX_FRAMES frames of the slot's job in one submission
-// and one wait (section 4 below): every frame's candidates, one table item per frame and the views go up in one copy and the
-// k_track_*_batch kernels take the frame from the grid's z; a pending call has a frame count, one but for a batch, and
-// mcorb_lmap_track_frames_wait serves any.  The reference's kd-tree search (FLANN, 4 trees, 64 checks) is approximate and un-vendored: the neighbours here are
+// same body.  Every call is a call of nf frames, one but for mcorb_lmap_track_rig_frames, the slot entry for up to
+// MCORB_TRACK_MAX_FRAMES frames of the slot's job in one submission and one wait: every frame's candidates, one TrItem per frame
+// and the views go up in one copy and the kernels take the frame from the grid's z (submit_on_device, the one function that
+// launches them); a pending call has a frame count and mcorb_lmap_track_frames_wait serves any.  The reference's kd-tree search (FLANN, 4 trees, 64 checks) is approximate and un-vendored: the neighbours here are
 // exact.  The store's landmarks are only read: of the map object the call writes its own scratch and, as mcorb_lmap_search
 // does, the per-slot stamps of the candidate walk (tick / stamp), which no call reads as state.
 #include <string.h>
@@ -46,7 +46,7 @@ struct KpRows {
     const float *pt(int c, int k) const { return reinterpret_cast<const float *>(base[c] + (size_t)k * stride); }
 };
 
-// the frame of a call.  Both entries: the keypoint count per camera and the host's keypoints.  desc: the host's descriptors, which
+// a frame of a call.  Every entry: the keypoint count per camera and the host's keypoints.  desc: the host's descriptors, which
 // the host-array entry uploads and a host-only store reads.  slot (the slot entry on a device store): where the kernels find the
 // frame in HBM -- image img0 + c is camera c
 struct Frame {
@@ -112,7 +112,7 @@ void clear_counts(mcorb_track_out *out)
     out->n_candidates = 0;
 }
 
-// ---- 1. what both entries refuse before anything runs, the frame apart: the arguments, then -- the caller holds the store's
+// ---- 1. what the entries refuse before anything runs, the frame apart: the arguments, then -- the caller holds the store's
 // lock -- the candidates ----
 int check_out(const mcorb_track_out *out)
 {
@@ -217,80 +217,104 @@ void slot_sel(const Slot &s, const uint32_t *&sel, const int *&nsel)
     nsel = host_sel ? s.hc.nsel : s.ctl.nsel;
 }
 
-// a device store: one submission on the store's stream -- the candidates (and the host arrays' frame) up in one copy,
-// [k_track_points,] k_track_project, k_track_match, k_track_compact, the table's clear and the three kernels of the
-// de-duplication, no host step between them.  Once the stream has run them the rows, the matches and their counts are in
-// host-mapped memory; the gathered points (want_pts) come down in the one result copy there is.  Nothing of the caller's is
-// read after this returns: the arrays are in the pinned block
-int submit_on_device(mcorb_lmap *m, const mcorb_track_view &view, const Frame &f, const std::vector<int> &cand, double max_d2,
+// a device store: the nf frames of a call in one submission on the store's stream -- one pinned block up in one copy (a TrItem
+// and a view per frame, the frames' candidates back to back and, host arrays only, the frame), then [k_track_points,]
+// k_track_project, k_track_match, k_track_compact, the tables' clear and the three kernels of the de-duplication, each once for all
+// frames (the frame is the grid's z), no host step between them.  Frame f's block of every per-pair array begins at C * first[f]
+// and is laid out [c * n + i] inside; its de-duplication tables have their own size and follow the frames' before it.  Once the
+// stream has run them the rows, the matches and their counts are in host-mapped memory; the gathered points (want_pts) come down
+// in the one result copy there is.  Nothing of the caller's is read after this returns: the arrays are in the pinned block
+int submit_on_device(mcorb_lmap *m, const mcorb_track_view *views, const Frame *fr, int nf, const mcorb_lmap::TrackCall &tc, double max_d2,
                      int max_hamming, bool want_pts)
 {
-    const int C = view.ncams, nc = (int)cand.size();
-    const size_t rows = (size_t)C * nc;
+    const int C = tc.ncams;
+    const size_t total = tc.first[nf], rows = (size_t)C * total;
+    Slot *slot = fr[0].slot;   // (a call's frames are all a rig slot's or all host arrays)
+    const int kcap = slot ? fr[0].rig->geom.kcap : 0;
     HIPCHK(hipSetDevice(m->device));
     // A stale error of this thread is not this call's (Rig::execute does the same): whatever an earlier, unrelated HIP call left
     // behind -- another object's destructor, an elapsed-time query -- would otherwise be reported by the checks behind the launches
     (void)hipGetLastError();
     hipStream_t st = m->st;
-    TrFrame tf;
-    memset(&tf, 0, sizeof(tf));
-    size_t total_kp = 0;
-    const int kcap = f.slot ? f.rig->geom.kcap : 0;
-    for (int c = 0; c < C; c++) {
-        tf.n_kp[c] = f.n_kp[c];
-        tf.first[c] = f.slot ? c * kcap : (int32_t)total_kp;
-        total_kp += (size_t)f.n_kp[c];
+    size_t slots = 0, total_kp = 0;   // (total_kp: of host arrays, which go up)
+    int max_n = 0;
+    for (int f = 0; f < nf; f++) {
+        const int n = (int)(tc.first[f + 1] - tc.first[f]);
+        slots += (size_t)C << tr_dedup_log2(n);
+        max_n = std::max(max_n, n);
+        for (int c = 0; c < C && !slot; c++) total_kp += (size_t)fr[f].n_kp[c];
     }
-    if (f.slot) total_kp = 0;   // nothing of the frame goes up
-    const TrackLayout L((size_t)nc, total_kp);
-    const size_t slots = (size_t)C << tr_dedup_log2(nc);
+    const TrackLayout L((size_t)nf, total, total_kp);
     TK &t = m->track;
-    TRY(t.reserve(L.p.total, rows, 1, slots, f.slot ? (size_t)C * kcap : 0, want_pts ? (size_t)nc : 0));
-    memcpy(t.in.host<int>(L.cand), cand.data(), (size_t)nc * sizeof(int));
-    if (!f.slot)
+    TRY(t.reserve(L.p.total, rows, (size_t)nf, slots, slot ? (size_t)nf * C * kcap : 0, want_pts ? total : 0));
+    TrItem *items = t.in.host<TrItem>(L.items);
+    size_t tab = 0, kp = 0;
+    for (int f = 0; f < nf; f++) {
+        TrItem &it = items[f];
+        memset(&it, 0, sizeof(it));
+        it.view = f;
+        it.n = (int32_t)(tc.first[f + 1] - tc.first[f]);
+        it.log2p = tr_dedup_log2(it.n);
+        it.img0 = fr[f].img0;
+        it.cand_first = tc.first[f];
+        it.rows = (size_t)C * tc.first[f];
+        it.tab = tab;
+        it.kp0 = slot ? (size_t)f * C * kcap : 0;
+        it.desc0 = slot ? (size_t)it.img0 * kcap : 0;
         for (int c = 0; c < C; c++) {
-            if (!f.n_kp[c]) continue;
-            memcpy(t.in.host<uint8_t>(L.xy) + (size_t)tf.first[c] * 8, f.kp.base[c], (size_t)f.n_kp[c] * 8);
-            memcpy(t.in.host<uint8_t>(L.desc) + (size_t)tf.first[c] * 32, f.desc[c], (size_t)f.n_kp[c] * 32);
+            const int32_t n_kp = it.frame.n_kp[c] = fr[f].n_kp[c];
+            it.frame.first[c] = slot ? c * kcap : (int32_t)kp;
+            if (!slot && n_kp) {
+                memcpy(t.in.host<uint8_t>(L.xy) + kp * 8, fr[f].kp.base[c], (size_t)n_kp * 8);
+                memcpy(t.in.host<uint8_t>(L.desc) + kp * 32, fr[f].desc[c], (size_t)n_kp * 32);
+                kp += (size_t)n_kp;
+            }
         }
+        tab += (size_t)C << it.log2p;
+        if (!it.n)   // no workgroup runs for this frame
+            for (int c = 0; c < MCORB_MAX_CAMS; c++)
+                t.h_nproj.get()[(size_t)f * MCORB_MAX_CAMS + c] = t.h_nmatch.get()[(size_t)f * MCORB_MAX_CAMS + c] = 0;
+    }
+    memcpy(t.in.host<mcorb_track_view>(L.views), views, (size_t)nf * sizeof(mcorb_track_view));
+    memcpy(t.in.host<int>(L.cand), tc.cand.data(), total * sizeof(int));
     TRY(t.in.upload(st, L.p.total));
+    const TrItem *d_items = t.in.dev<const TrItem>(L.items);
+    const mcorb_track_view *d_views = t.in.dev<const mcorb_track_view>(L.views);
     const int *d_cand = t.in.dev<const int>(L.cand);
     const float2 *kp_xy = t.in.dev<const float2>(L.xy);
     const uint8_t *kp_desc = t.in.dev<const uint8_t>(L.desc);
-    if (f.slot) {
+    if (slot) {
         const uint32_t *sel;
         const int *nsel;
-        slot_sel(*f.slot, sel, nsel);
+        slot_sel(*slot, sel, nsel);
         TRY(t.chain.mark(st, TK::kPoints));
-        launch_track_points(st, sel, nsel, kcap, f.img0, C, f.rig->tab.scale, f.rig->tab.nlevels, t.d_kp);
+        launch_track_points(st, d_items, nf, max_n, sel, nsel, kcap, C, fr[0].rig->tab.scale, fr[0].rig->tab.nlevels, t.d_kp);
         HIPCHK(hipGetLastError());
         kp_xy = t.d_kp;
-        kp_desc = f.slot->d_desc.get() + (size_t)f.img0 * kcap * 32;
+        kp_desc = slot->d_desc.get();
     }
     TRY(t.chain.mark(st, TK::kProject));
-    launch_track_project(st, view, m->d_geom, d_cand, nc, t.d_xy, t.d_valid, want_pts ? t.d_pt.get() : nullptr);
+    launch_track_project(st, d_items, nf, max_n, d_views, m->d_geom, d_cand, t.d_xy, t.d_valid, want_pts ? t.d_pt.get() : nullptr);
     HIPCHK(hipGetLastError());
     TRY(t.chain.mark(st, TK::kMatch));
-    launch_track_match(st, tf, C, kp_xy, kp_desc, m->d_desc, d_cand, nc, t.d_xy, t.d_valid, max_d2, max_hamming, t.d_best);
+    launch_track_match(st, d_items, nf, max_n, C, kp_xy, kp_desc, m->d_desc, d_cand, t.d_xy, t.d_valid, max_d2, max_hamming, t.d_best);
     HIPCHK(hipGetLastError());
     TRY(t.chain.mark(st, TK::kCompact));
-    launch_track_compact(st, C, nc, t.d_valid, t.d_xy, t.d_best, t.h_rows, t.h_nproj);
+    launch_track_compact(st, d_items, nf, max_n, C, t.d_valid, t.d_xy, t.d_best, t.h_rows, t.h_nproj);
     HIPCHK(hipGetLastError());
     TRY(t.chain.mark(st, TK::kDedup));
     HIPCHK(hipMemsetAsync(t.d_owner, 0xff, slots * sizeof(uint32_t), st));
     HIPCHK(hipMemsetAsync(t.d_val, 0xff, slots * sizeof(unsigned long long), st));
-    launch_track_dedup(st, tf, C, kp_xy, nc, t.d_valid, t.d_best, t.d_owner, t.d_val, t.d_slot, t.d_win, t.h_match, t.h_nmatch);
+    launch_track_dedup(st, d_items, nf, max_n, C, kp_xy, t.d_valid, t.d_best, t.d_owner, t.d_val, t.d_slot, t.d_win, t.h_match, t.h_nmatch);
     HIPCHK(hipGetLastError());
     TRY(t.chain.mark(st, TK::kDedup + 1));
-    if (t.refine) {   // (mcorb_lmap_set_track_refine: the pose from the frame's matches, in the same submission)
-        const size_t first[2] = {0, (size_t)nc}, kp0 = 0;
-        TRY(pose_track_submit(m, &view, 1, first, &tf, &kp0, kp_xy, d_cand));
-    }
-    if (want_pts) HIPCHK(hipMemcpyAsync(t.h_pt, t.d_pt, (size_t)nc * 3 * sizeof(double), hipMemcpyDeviceToHost, st));
+    // (mcorb_lmap_set_track_refine: the pose from each frame's matches, one workgroup of k_pose_refine per frame, in the same submission)
+    if (t.refine) TRY(pose_track_submit(m, views, items, nf, kp_xy, d_cand));
+    if (want_pts) HIPCHK(hipMemcpyAsync(t.h_pt, t.d_pt, total * 3 * sizeof(double), hipMemcpyDeviceToHost, st));
     return MCORB_OK;
 }
 
-// ---- 3. a call's two halves, the frame checked; the caller holds the store's lock ----
+// ---- 3. a call's two halves, the frames checked; the caller holds the store's lock ----
 // the state of a call of nf frames whose candidates (cand, first) are in place: nothing launched, every count zero
 void begin_call(mcorb_lmap *m, int C, int nf, bool want_pts)
 {
@@ -309,46 +333,57 @@ void begin_call(mcorb_lmap *m, int C, int nf, bool want_pts)
     }
 }
 
-// everything up to and excluding the synchronisation: the candidates, then the whole call on a host-only store, the submission on
-// a device store.  A refusal leaves nothing behind: work that a failed submission put on the stream is waited for here
-int submit_body(mcorb_lmap *m, const mcorb_track_view *view, const Frame &f, const int32_t *lids, int n_lids, double max_d2,
-                int max_hamming, bool want_pts, mcorb_track_out *out)
+// everything up to and excluding the synchronisation: the candidates of every frame (frame f's ids are lids[lid_first[f] ..
+// lid_first[f + 1])), one stamp value each, then the whole call frame by frame on a host-only store -- and when no frame has a
+// candidate, which leaves the stream untouched --, the one submission on a device store.  A refusal leaves nothing behind: work
+// that a failed submission put on the stream is waited for here.  outs: the synchronous entries'
+int submit_body(mcorb_lmap *m, const mcorb_track_view *views, const Frame *fr, int nf, const int32_t *lids, const int32_t *lid_first,
+                double max_d2, int max_hamming, bool want_pts, mcorb_track_out *outs)
 {
     Phases ph(m, true);
     mcorb_lmap::TrackCall &tc = m->track.call;
+    const int C = views[0].ncams;
     tc.cand.clear();
-    TRY(candidates_of(m, lids, n_lids, tc.cand));
-    if (out) out->n_candidates = (int)tc.cand.size();   // (the synchronous entries: set from here on, whatever follows)
+    tc.first.assign(1, 0);
+    for (int f = 0; f < nf; f++) {
+        TRY(candidates_of(m, lids + lid_first[f], lid_first[f + 1] - lid_first[f], tc.cand));
+        tc.first.push_back(tc.cand.size());
+    }
+    if (outs)   // (set from here on, whatever follows)
+        for (int f = 0; f < nf; f++) outs[f].n_candidates = (int)(tc.first[f + 1] - tc.first[f]);
     ph.mark(0);
-    const int C = view->ncams, nc = (int)tc.cand.size();
-    tc.first.assign({(size_t)0, (size_t)nc});
-    begin_call(m, C, 1, want_pts);
-    if (!nc) {
-        if (tc.refine) pose_track_host(m, *view, nullptr, 0, nullptr, tc.n_match.data(), f.kp.base, f.kp.stride, tc.pose[0], nullptr);
-        m->track.pose_nf = tc.refine ? 1 : 0;
+    const size_t total = tc.cand.size();
+    begin_call(m, C, nf, want_pts);
+    if (!total || m->device < 0) {
+        tc.rows.resize((size_t)C * total);
+        tc.matches.resize((size_t)C * total);
+        for (int f = 0; f < nf; f++) {
+            const int nc = (int)(tc.first[f + 1] - tc.first[f]);
+            TrMatch *matches = tc.matches.data() + (size_t)C * tc.first[f];
+            int32_t *n_match = tc.n_match.data() + (size_t)f * MCORB_MAX_CAMS;
+            if (nc) {
+                TrRow *rows = tc.rows.data() + (size_t)C * tc.first[f];
+                int32_t *n_proj = tc.n_proj.data() + (size_t)f * MCORB_MAX_CAMS;
+                rows_on_host(m, views[f], fr[f], tc.cand.data() + tc.first[f], nc, max_d2, max_hamming, rows, n_proj);
+                ph.mark(2);
+                dedup_on_host(C, nc, rows, n_proj, fr[f].kp, matches, n_match);
+                ph.mark(3);
+            }
+            if (tc.refine)
+                pose_track_host(m, views[f], tc.cand.data() + tc.first[f], nc, matches, n_match, fr[f].kp.base, fr[f].kp.stride, tc.pose[f],
+                                tc.pose_flags.data() + (size_t)C * tc.first[f]);
+        }
+        m->track.pose_nf = tc.refine ? nf : 0;
         return MCORB_OK;
     }
-    if (m->device < 0) {
-        tc.rows.resize((size_t)C * nc);
-        tc.matches.resize((size_t)C * nc);
-        rows_on_host(m, *view, f, tc.cand.data(), nc, max_d2, max_hamming, tc.rows.data(), tc.n_proj.data());
-        ph.mark(2);
-        dedup_on_host(C, nc, tc.rows.data(), tc.n_proj.data(), f.kp, tc.matches.data(), tc.n_match.data());
-        ph.mark(3);
-        if (tc.refine)
-            pose_track_host(m, *view, tc.cand.data(), nc, tc.matches.data(), tc.n_match.data(), f.kp.base, f.kp.stride, tc.pose[0],
-                            tc.pose_flags.data());
-        m->track.pose_nf = tc.refine ? 1 : 0;
-        return MCORB_OK;
-    }
-    const int r = submit_on_device(m, *view, f, tc.cand, max_d2, max_hamming, want_pts);
+    const int r = submit_on_device(m, views, fr, nf, tc, max_d2, max_hamming, want_pts);
     if (r != MCORB_OK) {
         (void)hipStreamSynchronize(m->st);
         return r;
     }
     tc.launched = true;
-    tc.points = f.slot != nullptr;
-    m->track.pose_nf = tc.refine ? 1 : 0;
+    tc.points = fr[0].slot != nullptr;
+    m->track.pose_nf = tc.refine ? nf : 0;
     ph.mark(1);
     return MCORB_OK;
 }
@@ -433,14 +468,19 @@ int wait_body(mcorb_lmap *m, mcorb_track_out *outs, int n_outs, bool checked, bo
     return MCORB_OK;
 }
 
-// a call from the candidates on.  out: the synchronous entries', which wait at once; NULL: the call stays pending
-int track(mcorb_lmap *m, const mcorb_track_view *view, const Frame &f, const int32_t *lids, int n_lids, double max_d2, int max_hamming,
-          bool want_pts, mcorb_track_out *out)
+// a call of nf checked frames from the lock on.  outs: the synchronous entries', nf of them, which wait at once; NULL: the call
+// stays pending.  After a failure every count of every outs[f] is zero
+int track(mcorb_lmap *m, const mcorb_track_view *views, const Frame *fr, int nf, const int32_t *lids, const int32_t *lid_first, double max_d2,
+          int max_hamming, bool want_pts, mcorb_track_out *outs)
 {
     std::lock_guard<std::mutex> lk(m->mu);
     if (m->track.pending.load()) return fail(MCORB_E_STATE, "a submitted tracking call has not been waited for");
-    TRY(submit_body(m, view, f, lids, n_lids, max_d2, max_hamming, want_pts, out));
-    if (out) return wait_body(m, out, 1, true, true);
+    const int rc = submit_body(m, views, fr, nf, lids, lid_first, max_d2, max_hamming, want_pts, outs);
+    if (rc != MCORB_OK) {
+        for (int f = 0; f < nf && outs; f++) clear_counts(&outs[f]);
+        return rc;
+    }
+    if (outs) return wait_body(m, outs, nf, true, false);
     m->track.pending.store(true);
     return MCORB_OK;
 }
@@ -491,7 +531,7 @@ int frame_of_slot(const mcorb_lmap *m, const mcorb_track_view *view, mcorb_rig *
     return MCORB_OK;
 }
 
-// the two entries, synchronous (out) or a submission (out == NULL)
+// the three entries, synchronous (out) or a submission (out == NULL): their own argument checks, then track()
 int track_arrays(mcorb_lmap *m, const mcorb_track_view *view, const mcorb_track_frame *frame, const int32_t *lids, int n_lids,
                  double max_d2, int max_hamming, bool want_pts, mcorb_track_out *out, bool with_out)
 {
@@ -500,7 +540,8 @@ int track_arrays(mcorb_lmap *m, const mcorb_track_view *view, const mcorb_track_
     TRY(check_args(view, lids, n_lids, max_hamming, out, with_out));
     Frame f;
     TRY(frame_of_arrays(view, frame, f));
-    return track(m, view, f, lids, n_lids, max_d2, max_hamming, want_pts, out);
+    const int32_t lid_first[2] = {0, n_lids};
+    return track(m, view, &f, 1, lids, lid_first, max_d2, max_hamming, want_pts, out);
 }
 
 int track_slot(mcorb_lmap *m, const mcorb_track_view *view, mcorb_rig *r, int slot, int frame, const int32_t *lids, int n_lids,
@@ -510,150 +551,11 @@ int track_slot(mcorb_lmap *m, const mcorb_track_view *view, mcorb_rig *r, int sl
     TRY(check_args(view, lids, n_lids, max_hamming, out, with_out));
     Frame f;
     TRY(frame_of_slot(m, view, r, slot, frame, f));
-    return track(m, view, f, lids, n_lids, max_d2, max_hamming, want_pts, out);
+    const int32_t lid_first[2] = {0, n_lids};
+    return track(m, view, &f, 1, lids, lid_first, max_d2, max_hamming, want_pts, out);
 }
 
-// ---- 4. the batch: nf frames of a slot's last extraction in one submission (mcorb_lmap_track_rig_frames) ----
-// A device store: what submit_on_device puts on the stream, once for all frames -- the _batch kernels take the frame from
-// blockIdx.z.  The pinned block holds the TrBatchItem per frame, the views and the frames' candidates back to back, and goes up in
-// one copy.  Frame f's block of every per-pair array begins at C * first[f] and has the single call's layout; its
-// de-duplication tables have the single call's size and follow the frames' before it
-int submit_frames_on_device(mcorb_lmap *m, const mcorb_track_view *views, const std::vector<Frame> &fr, const int32_t *frames,
-                            const mcorb_lmap::TrackCall &tc, double max_d2, int max_hamming, bool want_pts)
-{
-    const int C = tc.ncams, nf = tc.nf;
-    const size_t total = tc.first[nf], rows = (size_t)C * total;
-    const Frame &f0 = fr[0];
-    const int kcap = f0.rig->geom.kcap;
-    HIPCHK(hipSetDevice(m->device));
-    (void)hipGetLastError();   // (a stale error of this thread is not this call's: submit_on_device)
-    hipStream_t st = m->st;
-    const TrackBatchLayout L((size_t)nf, total);
-    size_t slots = 0;
-    int max_n = 0;
-    for (int f = 0; f < nf; f++) {
-        const int n = (int)(tc.first[f + 1] - tc.first[f]);
-        slots += (size_t)C << tr_dedup_log2(n);
-        max_n = std::max(max_n, n);
-    }
-    TK &t = m->track;
-    TRY(t.reserve(L.p.total, rows, (size_t)nf, slots, (size_t)nf * C * kcap, want_pts ? total : 0));
-    TrBatchItem *items = t.in.host<TrBatchItem>(L.items);
-    size_t tab = 0;
-    for (int f = 0; f < nf; f++) {
-        TrBatchItem &it = items[f];
-        memset(&it, 0, sizeof(it));
-        it.view = f;
-        it.n = (int32_t)(tc.first[f + 1] - tc.first[f]);
-        it.log2p = tr_dedup_log2(it.n);
-        it.img0 = frames[f] * C;
-        it.cand_first = tc.first[f];
-        it.rows = (size_t)C * tc.first[f];
-        it.tab = tab;
-        it.kp0 = (size_t)f * C * kcap;
-        it.desc0 = (size_t)it.img0 * kcap;
-        for (int c = 0; c < C; c++) {
-            it.frame.n_kp[c] = fr[f].n_kp[c];
-            it.frame.first[c] = c * kcap;
-        }
-        tab += (size_t)C << it.log2p;
-        if (!it.n)   // no workgroup runs for this frame
-            for (int c = 0; c < MCORB_MAX_CAMS; c++)
-                t.h_nproj.get()[(size_t)f * MCORB_MAX_CAMS + c] = t.h_nmatch.get()[(size_t)f * MCORB_MAX_CAMS + c] = 0;
-    }
-    memcpy(t.in.host<mcorb_track_view>(L.views), views, (size_t)nf * sizeof(mcorb_track_view));
-    memcpy(t.in.host<int>(L.cand), tc.cand.data(), total * sizeof(int));
-    TRY(t.in.upload(st, L.p.total));
-    const TrBatchItem *d_items = t.in.dev<const TrBatchItem>(L.items);
-    const mcorb_track_view *d_views = t.in.dev<const mcorb_track_view>(L.views);
-    const int *d_cand = t.in.dev<const int>(L.cand);
-    const uint32_t *sel;
-    const int *nsel;
-    slot_sel(*f0.slot, sel, nsel);
-    TRY(t.chain.mark(st, TK::kPoints));
-    launch_track_points_batch(st, d_items, nf, sel, nsel, kcap, C, f0.rig->tab.scale, f0.rig->tab.nlevels, t.d_kp);
-    HIPCHK(hipGetLastError());
-    TRY(t.chain.mark(st, TK::kProject));
-    launch_track_project_batch(st, d_items, nf, max_n, d_views, m->d_geom, d_cand, t.d_xy, t.d_valid, want_pts ? t.d_pt.get() : nullptr);
-    HIPCHK(hipGetLastError());
-    TRY(t.chain.mark(st, TK::kMatch));
-    launch_track_match_batch(st, d_items, nf, max_n, C, t.d_kp, f0.slot->d_desc.get(), m->d_desc, d_cand, t.d_xy, t.d_valid, max_d2,
-                             max_hamming, t.d_best);
-    HIPCHK(hipGetLastError());
-    TRY(t.chain.mark(st, TK::kCompact));
-    launch_track_compact_batch(st, d_items, nf, max_n, C, t.d_valid, t.d_xy, t.d_best, t.h_rows, t.h_nproj);
-    HIPCHK(hipGetLastError());
-    TRY(t.chain.mark(st, TK::kDedup));
-    HIPCHK(hipMemsetAsync(t.d_owner, 0xff, slots * sizeof(uint32_t), st));
-    HIPCHK(hipMemsetAsync(t.d_val, 0xff, slots * sizeof(unsigned long long), st));
-    launch_track_dedup_batch(st, d_items, nf, max_n, C, t.d_kp, t.d_valid, t.d_best, t.d_owner, t.d_val, t.d_slot, t.d_win, t.h_match, t.h_nmatch);
-    HIPCHK(hipGetLastError());
-    TRY(t.chain.mark(st, TK::kDedup + 1));
-    if (t.refine) {   // (one workgroup of k_pose_refine per frame, in the same submission)
-        std::vector<TrFrame> tf((size_t)nf);
-        std::vector<size_t> kp0((size_t)nf);
-        for (int f = 0; f < nf; f++) {
-            tf[f] = items[f].frame;
-            kp0[f] = items[f].kp0;
-        }
-        TRY(pose_track_submit(m, views, nf, tc.first.data(), tf.data(), kp0.data(), t.d_kp, d_cand));
-    }
-    if (want_pts) HIPCHK(hipMemcpyAsync(t.h_pt, t.d_pt, total * 3 * sizeof(double), hipMemcpyDeviceToHost, st));
-    return MCORB_OK;
-}
-
-// the candidates of every frame, one stamp value each, then the call: frame by frame on a host-only store, one submission on a
-// device store.  The caller holds the store's lock
-int submit_frames_body(mcorb_lmap *m, const mcorb_track_view *views, const std::vector<Frame> &fr, const int32_t *frames, int nf,
-                       const int32_t *lids, const int32_t *lid_first, double max_d2, int max_hamming, bool want_pts, mcorb_track_out *outs)
-{
-    Phases ph(m, true);
-    mcorb_lmap::TrackCall &tc = m->track.call;
-    const int C = views[0].ncams;
-    tc.cand.clear();
-    tc.first.assign(1, 0);
-    for (int f = 0; f < nf; f++) {
-        TRY(candidates_of(m, lids + lid_first[f], lid_first[f + 1] - lid_first[f], tc.cand));
-        tc.first.push_back(tc.cand.size());
-    }
-    if (outs)
-        for (int f = 0; f < nf; f++) outs[f].n_candidates = (int)(tc.first[f + 1] - tc.first[f]);
-    ph.mark(0);
-    const size_t total = tc.cand.size();
-    begin_call(m, C, nf, want_pts);
-    if (!total || m->device < 0) {
-        tc.rows.resize((size_t)C * total);
-        tc.matches.resize((size_t)C * total);
-        for (int f = 0; f < nf; f++) {
-            const int nc = (int)(tc.first[f + 1] - tc.first[f]);
-            TrMatch *matches = tc.matches.data() + (size_t)C * tc.first[f];
-            int32_t *n_match = tc.n_match.data() + (size_t)f * MCORB_MAX_CAMS;
-            if (nc) {
-                TrRow *rows = tc.rows.data() + (size_t)C * tc.first[f];
-                int32_t *n_proj = tc.n_proj.data() + (size_t)f * MCORB_MAX_CAMS;
-                rows_on_host(m, views[f], fr[f], tc.cand.data() + tc.first[f], nc, max_d2, max_hamming, rows, n_proj);
-                dedup_on_host(C, nc, rows, n_proj, fr[f].kp, matches, n_match);
-            }
-            if (tc.refine)
-                pose_track_host(m, views[f], tc.cand.data() + tc.first[f], nc, matches, n_match, fr[f].kp.base, fr[f].kp.stride, tc.pose[f],
-                                tc.pose_flags.data() + (size_t)C * tc.first[f]);
-        }
-        m->track.pose_nf = tc.refine ? nf : 0;
-        ph.mark(3);
-        return MCORB_OK;
-    }
-    const int r = submit_frames_on_device(m, views, fr, frames, tc, max_d2, max_hamming, want_pts);
-    if (r != MCORB_OK) {
-        (void)hipStreamSynchronize(m->st);
-        return r;
-    }
-    tc.launched = tc.points = true;
-    m->track.pose_nf = tc.refine ? nf : 0;
-    ph.mark(1);
-    return MCORB_OK;
-}
-
-// the batched slot entry, synchronous (outs) or a submission (outs == NULL)
+// nf frames of a slot's last extraction (mcorb_lmap_track_rig_frames)
 int track_slot_frames(mcorb_lmap *m, const mcorb_track_view *views, mcorb_rig *r, int slot, const int32_t *frames, int nf,
                       const int32_t *lids, const int32_t *lid_first, double max_d2, int max_hamming, bool want_pts, mcorb_track_out *outs,
                       bool with_out)
@@ -673,17 +575,7 @@ int track_slot_frames(mcorb_lmap *m, const mcorb_track_view *views, mcorb_rig *r
         for (int f = 0; f < nf; f++) TRY(check_out(&outs[f]));
     std::vector<Frame> fr((size_t)nf);
     for (int f = 0; f < nf; f++) TRY(frame_of_slot(m, &views[f], r, slot, frames[f], fr[f]));
-    std::lock_guard<std::mutex> lk(m->mu);
-    if (m->track.pending.load()) return fail(MCORB_E_STATE, "a submitted tracking call has not been waited for");
-    const int rc = submit_frames_body(m, views, fr, frames, nf, lids, lid_first, max_d2, max_hamming, want_pts, with_out ? outs : nullptr);
-    if (rc != MCORB_OK) {
-        if (with_out)
-            for (int f = 0; f < nf; f++) clear_counts(&outs[f]);
-        return rc;
-    }
-    if (with_out) return wait_body(m, outs, nf, true, false);
-    m->track.pending.store(true);
-    return MCORB_OK;
+    return track(m, views, fr.data(), nf, lids, lid_first, max_d2, max_hamming, want_pts, with_out ? outs : nullptr);
 }
 
 }  // namespace

@@ -134,13 +134,15 @@ struct TrRow { int32_t i; float x, y; int32_t kp, dist; };
 // an entry of a camera's de-duplicated list: the candidate's place in the call's list, its keypoint, the distance.  A camera's
 // entries are n_match of them from entry c * n (k_track_dedup_emit on a device store, the serial list on a host-only one)
 struct TrMatch { int32_t i, kp, dist; };
-// One frame of a batched slot call (mcorb_lmap_track_rig_frames), as the _batch kernels read it from device memory, frame
-// blockIdx.z: its view's place among the call's views; its n candidates, cand_first candidates into the call's list; rows: where
-// its block of every per-pair array begins, ncams * cand_first -- inside the block the layout is the single call's [c * n + i];
-// tab: where its de-duplication tables begin, ncams << log2p slots; frame: its keypoints in the store's keypoint buffer from kp0
-// on (first[c] = c * kcap, row (f * ncams + c) * kcap overall) and in the slot's descriptors from keypoint desc0 = img0 * kcap on,
-// img0 being its first image of the slot
-struct TrBatchItem {
+// One frame of a tracking call -- any entry, 1 .. MCORB_TRACK_MAX_FRAMES of them -- as the kernels read it from device memory,
+// frame blockIdx.z: its view's place among the call's views; its n candidates, cand_first candidates into the call's list; rows:
+// where its block of every per-pair array begins, ncams * cand_first -- inside the block the layout is [c * n + i]; tab: where
+// its de-duplication tables begin, ncams << log2p slots; frame: camera c's n_kp[c] keypoints from kp0 + first[c] on in the
+// kp_xy the kernels are given, their descriptors from keypoint desc0 + first[c] on in kp_desc.  A rig slot's frame: kp_xy is the
+// store's keypoint buffer, first[c] = c * kcap and kp0 = (f * ncams) * kcap, k_track_points' rows of img0, its first image of
+// the slot; kp_desc is the slot's descriptors, desc0 = img0 * kcap.  A host-array frame: kp_xy and kp_desc are the uploaded
+// block's, first[c] is the running keypoint count, kp0 = desc0 = 0 and img0 is not read
+struct TrItem {
     int32_t view, n, log2p, img0;
     uint64_t cand_first, rows, tab, kp0, desc0;
     TrFrame frame;

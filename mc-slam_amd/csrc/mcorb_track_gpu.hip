@@ -1,12 +1,17 @@
 // mcorb_track_gpu.hip -- the kernels of fast tracking on a device store (mcorb_track.cpp): k_track_project (Tracking::project_,
 // MCSlam/src/Tracking.cpp:208-260, for every candidate landmark and camera) and k_track_match (the per-query part of
 // Tracking::querryEachFrame, :329-377: the 10 nearest keypoints by image position, the radius gate, the best Hamming distance).
-// The arithmetic is mcorb_track.h, the code the host-only store runs.  k_track_points (mcorb_lmap_track_rig_frame only) rebuilds a
+// The arithmetic is mcorb_track.h, the code the host-only store runs.  k_track_points (the rig slot entries only) rebuilds a
 // rig slot's keypoints from their packed selection words; k_track_compact leaves each camera's kept candidates in candidate
 // order, in host-mapped memory; k_track_dedup_min / _win / _emit leave each camera's de-duplicated matches there (querryEachFrame
 // :380-415 in closed form).  Each kernel's body is a __device__ function that takes the view or frame by reference, the base pointers
-// and n; a k_track_* entry calls it with its kernel arguments (one frame, the single calls), its k_track_*_batch twin with what
-// the TrBatchItem of frame blockIdx.z says (mcorb_lmap_track_rig_frames).  No extraction job runs them and no benchmark leg times them.
+// and n; its one k_track_* entry calls it with what the TrItem of frame blockIdx.z says (mcorb_track.h), for every tracking call:
+// a single call is a call of one frame, a grid whose z is 1.  No extraction job runs them and no benchmark leg times them.
+//
+// blockIdx.z is the frame, whose TrItem -- and, in k_track_project, view -- is read from device memory at an address that is
+// uniform over the wave, so it stays in scalar registers as a kernel argument does.  The grid's x is sized by the frame with the
+// most candidates: a workgroup beyond its own frame's n leaves, uniformly (none does in a call of one frame).  A frame's block of
+// every per-pair array begins at item.rows and has the layout [c * n + i] inside, which is all a body sees.
 //
 // They go out in one submission: k_track_match reads the validity bytes k_track_project wrote and the points k_track_points
 // wrote, k_track_compact and the de-duplication read the rows of the kernels before them, and the host copies rows and matches
@@ -23,8 +28,8 @@
 
 namespace mcorb {
 
-// One lane per candidate, the cameras looped inside.  The view is a kernel argument, uniform for the launch: its 12 + 17 doubles
-// per camera come through the scalar cache.  A lane's own traffic is its 24 bytes of point, gathered by landmark id, and per
+// One lane per candidate, the cameras looped inside.  The view is uniform for the workgroup: its 12 + 17 doubles per camera come
+// through the scalar cache.  A lane's own traffic is its 24 bytes of point, gathered by landmark id, and per
 // camera the plain stores of (x, y) and the validity byte, camera-major, so that a camera's row is contiguous for k_track_match;
 // pts (may be NULL) receives the gathered point, for bestMatchLandmarks.
 __device__ __forceinline__ void track_project(const mcorb_track_view &view, const double *__restrict__ geom, const int *__restrict__ cand,
@@ -48,43 +53,23 @@ __device__ __forceinline__ void track_project(const mcorb_track_view &view, cons
     }
 }
 
-__global__ __launch_bounds__(kTrackProjectT) void k_track_project(mcorb_track_view view, const double *__restrict__ geom,
-                                                                  const int *__restrict__ cand, int n, float2 *__restrict__ xy,
-                                                                  uint8_t *__restrict__ valid, double *__restrict__ pts)
+__global__ __launch_bounds__(kTrackProjectT) void k_track_project(const TrItem *__restrict__ items, const mcorb_track_view *__restrict__ views,
+                                                                  const double *__restrict__ geom, const int *__restrict__ cand,
+                                                                  float2 *__restrict__ xy, uint8_t *__restrict__ valid,
+                                                                  double *__restrict__ pts)
 {
-    track_project(view, geom, cand, n, xy, valid, pts);
-}
-
-// The _batch entries (mcorb_lmap_track_rig_frames): blockIdx.z is the frame, whose TrBatchItem -- and, here, view -- is read from
-// device memory at an address that is uniform over the wave, so it stays in scalar registers as a kernel argument does.  The
-// grid's x is sized by the frame with the most candidates: a workgroup beyond its own frame's n leaves, uniformly.  A frame's
-// block of every per-pair array begins at item.rows and has the single call's layout, so the bodies are the single call's
-__global__ __launch_bounds__(kTrackProjectT) void k_track_project_batch(const TrBatchItem *__restrict__ items,
-                                                                        const mcorb_track_view *__restrict__ views,
-                                                                        const double *__restrict__ geom, const int *__restrict__ cand,
-                                                                        float2 *__restrict__ xy, uint8_t *__restrict__ valid,
-                                                                        double *__restrict__ pts)
-{
-    const TrBatchItem &it = items[blockIdx.z];
+    const TrItem &it = items[blockIdx.z];
     if ((int)(blockIdx.x * kTrackProjectT) >= it.n) return;
     track_project(views[it.view], geom, cand + it.cand_first, it.n, xy + it.rows, valid + it.rows,
                   pts ? pts + 3 * it.cand_first : nullptr);
 }
 
-void launch_track_project(hipStream_t st, const mcorb_track_view &view, const double *geom, const int *cand, int n, float2 *xy,
-                          uint8_t *valid, double *pts)
-{
-    if (n < 1) return;
-    hipLaunchKernelGGL(k_track_project, dim3((n + kTrackProjectT - 1) / kTrackProjectT), dim3(kTrackProjectT), 0, st, view, geom, cand,
-                       n, xy, valid, pts);
-}
-
-void launch_track_project_batch(hipStream_t st, const TrBatchItem *items, int nf, int max_n, const mcorb_track_view *views,
-                                const double *geom, const int *cand, float2 *xy, uint8_t *valid, double *pts)
+void launch_track_project(hipStream_t st, const TrItem *items, int nf, int max_n, const mcorb_track_view *views, const double *geom,
+                          const int *cand, float2 *xy, uint8_t *valid, double *pts)
 {
     if (nf < 1 || max_n < 1) return;
-    hipLaunchKernelGGL(k_track_project_batch, dim3((max_n + kTrackProjectT - 1) / kTrackProjectT, 1, nf), dim3(kTrackProjectT), 0, st,
-                       items, views, geom, cand, xy, valid, pts);
+    hipLaunchKernelGGL(k_track_project, dim3((max_n + kTrackProjectT - 1) / kTrackProjectT, 1, nf), dim3(kTrackProjectT), 0, st, items,
+                       views, geom, cand, xy, valid, pts);
 }
 
 // A workgroup of kTrackMatchWaves waves serves camera blockIdx.y; a wave serves kTrackMatchQ consecutive candidates.  The
@@ -192,46 +177,26 @@ __device__ __forceinline__ void track_match(float2 *tile, const TrFrame &frame, 
     }
 }
 
-__global__ __launch_bounds__(kTrackMatchT) void k_track_match(TrFrame frame, const float2 *__restrict__ kp_xy,
+__global__ __launch_bounds__(kTrackMatchT) void k_track_match(const TrItem *__restrict__ items, const float2 *__restrict__ kp_xy,
                                                               const uint32_t *__restrict__ kp_desc, const uint32_t *__restrict__ lm_desc,
-                                                              const int *__restrict__ cand, int n, const float2 *__restrict__ xy,
+                                                              const int *__restrict__ cand, const float2 *__restrict__ xy,
                                                               const uint8_t *__restrict__ valid, double max_d2, int max_hamming,
                                                               TrBest *__restrict__ best)
 {
     __shared__ float2 tile[MCORB_TRACK_TILE];
-    track_match(tile, frame, kp_xy, kp_desc, lm_desc, cand, n, xy, valid, max_d2, max_hamming, best);
-}
-
-__global__ __launch_bounds__(kTrackMatchT) void k_track_match_batch(const TrBatchItem *__restrict__ items, const float2 *__restrict__ kp_xy,
-                                                                    const uint32_t *__restrict__ kp_desc,
-                                                                    const uint32_t *__restrict__ lm_desc, const int *__restrict__ cand,
-                                                                    const float2 *__restrict__ xy, const uint8_t *__restrict__ valid,
-                                                                    double max_d2, int max_hamming, TrBest *__restrict__ best)
-{
-    __shared__ float2 tile[MCORB_TRACK_TILE];
-    const TrBatchItem &it = items[blockIdx.z];
+    const TrItem &it = items[blockIdx.z];
     if ((int)(blockIdx.x * (kTrackMatchWaves * kTrackMatchQ)) >= it.n) return;
     track_match(tile, it.frame, kp_xy + it.kp0, kp_desc + it.desc0 * 8, lm_desc, cand + it.cand_first, it.n, xy + it.rows,
                 valid + it.rows, max_d2, max_hamming, best + it.rows);
 }
 
-void launch_track_match(hipStream_t st, const TrFrame &frame, int ncams, const float2 *kp_xy, const uint8_t *kp_desc, const uint8_t *lm_desc,
-                        const int *cand, int n, const float2 *xy, const uint8_t *valid, double max_d2, int max_hamming, TrBest *best)
-{
-    if (n < 1) return;
-    const int per_block = kTrackMatchWaves * kTrackMatchQ;
-    hipLaunchKernelGGL(k_track_match, dim3((n + per_block - 1) / per_block, ncams), dim3(kTrackMatchT), 0, st, frame, kp_xy,
-                       reinterpret_cast<const uint32_t *>(kp_desc), reinterpret_cast<const uint32_t *>(lm_desc), cand, n, xy, valid,
-                       max_d2, max_hamming, best);
-}
-
-void launch_track_match_batch(hipStream_t st, const TrBatchItem *items, int nf, int max_n, int ncams, const float2 *kp_xy,
-                              const uint8_t *kp_desc, const uint8_t *lm_desc, const int *cand, const float2 *xy, const uint8_t *valid,
-                              double max_d2, int max_hamming, TrBest *best)
+void launch_track_match(hipStream_t st, const TrItem *items, int nf, int max_n, int ncams, const float2 *kp_xy, const uint8_t *kp_desc,
+                        const uint8_t *lm_desc, const int *cand, const float2 *xy, const uint8_t *valid, double max_d2, int max_hamming,
+                        TrBest *best)
 {
     if (nf < 1 || max_n < 1) return;
     const int per_block = kTrackMatchWaves * kTrackMatchQ;
-    hipLaunchKernelGGL(k_track_match_batch, dim3((max_n + per_block - 1) / per_block, ncams, nf), dim3(kTrackMatchT), 0, st, items, kp_xy,
+    hipLaunchKernelGGL(k_track_match, dim3((max_n + per_block - 1) / per_block, ncams, nf), dim3(kTrackMatchT), 0, st, items, kp_xy,
                        reinterpret_cast<const uint32_t *>(kp_desc), reinterpret_cast<const uint32_t *>(lm_desc), cand, xy, valid, max_d2,
                        max_hamming, best);
 }
@@ -247,52 +212,38 @@ __device__ __forceinline__ void track_points(const uint32_t *__restrict__ sel, c
     out[(size_t)c * kcap + k] = sel_point(sel[(size_t)m * kcap + k], sc);
 }
 
-__global__ __launch_bounds__(kTrackPointsT) void k_track_points(const uint32_t *__restrict__ sel, const int *__restrict__ nsel, int kcap,
-                                                                int img0, UndistScales sc, float2 *__restrict__ out)
-{
-    track_points(sel, nsel, kcap, img0, sc, out);
-}
-
 // frame f's images img0 .. img0 + ncams -> rows (f * ncams + c) * kcap of out, f's kp0 on: a frame named twice is converted twice
-__global__ __launch_bounds__(kTrackPointsT) void k_track_points_batch(const TrBatchItem *__restrict__ items, const uint32_t *__restrict__ sel,
-                                                                      const int *__restrict__ nsel, int kcap, UndistScales sc,
-                                                                      float2 *__restrict__ out)
+__global__ __launch_bounds__(kTrackPointsT) void k_track_points(const TrItem *__restrict__ items, const uint32_t *__restrict__ sel,
+                                                                const int *__restrict__ nsel, int kcap, UndistScales sc,
+                                                                float2 *__restrict__ out)
 {
-    const TrBatchItem &it = items[blockIdx.z];
+    const TrItem &it = items[blockIdx.z];
     if (it.n < 1) return;   // (no kernel reads the keypoints of a frame without candidates)
     track_points(sel, nsel, kcap, it.img0, sc, out + it.kp0);
 }
 
-void launch_track_points(hipStream_t st, const uint32_t *sel, const int *nsel, int kcap, int img0, int ncams, const float *scale,
-                         int nlevels, float2 *out)
+// (rig slots' frames only: the keypoints of a host-array frame are uploaded)
+void launch_track_points(hipStream_t st, const TrItem *items, int nf, int max_n, const uint32_t *sel, const int *nsel, int kcap, int ncams,
+                         const float *scale, int nlevels, float2 *out)
 {
-    if (kcap < 1 || ncams < 1) return;
-    hipLaunchKernelGGL(k_track_points, dim3((kcap + kTrackPointsT - 1) / kTrackPointsT, ncams), dim3(kTrackPointsT), 0, st, sel, nsel,
-                       kcap, img0, UndistScales(scale, nlevels), out);
+    if (kcap < 1 || ncams < 1 || nf < 1 || max_n < 1) return;
+    hipLaunchKernelGGL(k_track_points, dim3((kcap + kTrackPointsT - 1) / kTrackPointsT, ncams, nf), dim3(kTrackPointsT), 0, st, items,
+                       sel, nsel, kcap, UndistScales(scale, nlevels), out);
 }
 
-void launch_track_points_batch(hipStream_t st, const TrBatchItem *items, int nf, const uint32_t *sel, const int *nsel, int kcap, int ncams,
-                               const float *scale, int nlevels, float2 *out)
-{
-    if (kcap < 1 || ncams < 1 || nf < 1) return;
-    hipLaunchKernelGGL(k_track_points_batch, dim3((kcap + kTrackPointsT - 1) / kTrackPointsT, ncams, nf), dim3(kTrackPointsT), 0, st,
-                       items, sel, nsel, kcap, UndistScales(scale, nlevels), out);
-}
+// The ordered stream compaction of a row of n flags (each 0 or 1), the part k_track_compact and k_track_dedup_emit share.
+// Workgroup b serves flags b * 256 .. b * 256 + 255 and counts the set ones before them itself: p[0 .. b * 256) in 16-byte loads
+// from the first 16-byte boundary of the row on (the up to 15 bytes in front of it and as many behind the last whole load byte by
+// byte), a wave reduction and four partials through LDS (before, kept: one int per wave) -- at most n bytes, from L2, so
+// n * n / 512 per row.  Its own 256 flags are ranked by a ballot per wave.  No workgroup waits on another.  -> keep: this lane's
+// flag i = b * 256 + t is set; at: its place among the row's set flags; total: the set flags up to and including this
+// workgroup's, the row's count in its last workgroup.  Every lane of the workgroup calls it (it synchronises)
+static_assert(kTrackCompactT == kTrackDedupT, "track_rank serves both with one workgroup size");
+struct TrRank { bool keep; int at, total; };
 
-// The ordered stream compaction of camera blockIdx.y's validity bytes (each 0 or 1, as k_track_project writes them).  Workgroup b
-// serves candidates b * 256 .. b * 256 + 255 and counts the kept ones before them itself: valid[c * n .. c * n + b * 256) in
-// 16-byte loads from the first 16-byte boundary of the row on (the up to 15 bytes in front of it and as many behind the last
-// whole load byte by byte), a wave reduction and four partials through LDS -- at most n bytes, from L2, so n * n / 512 per
-// camera.  Its own 256 flags are ranked by a ballot per wave.  No workgroup waits on another; the last one of a camera has the
-// camera's total.
-__device__ __forceinline__ void track_compact(int *before, int *kept, int n, const uint8_t *__restrict__ valid,
-                                              const float2 *__restrict__ xy, const TrBest *__restrict__ best, TrRow *__restrict__ rows,
-                                              int32_t *__restrict__ n_proj)
+__device__ __forceinline__ TrRank track_rank(const uint8_t *__restrict__ p, int n, int *before, int *kept)
 {
-    const int c = blockIdx.y, b = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    if (b * kTrackCompactT >= n) return;   // (uniform over the workgroup)
-    const size_t row = (size_t)c * n;
-    const uint8_t *p = valid + row;
+    const int b = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int end = b * kTrackCompactT;    // a multiple of 16: the head and the tail below are 16 bytes together, or none
     const int head = end ? (int)((16 - (reinterpret_cast<uintptr_t>(p) & 15)) & 15) : 0;
     const int nvec = (end - head) >> 4, tail = head + (nvec << 4);
@@ -319,48 +270,45 @@ __device__ __forceinline__ void track_compact(int *before, int *kept, int n, con
         at += before[w] + (w < wave ? kept[w] : 0);
         total += before[w] + kept[w];
     }
-    if (keep) {
-        const float2 q = xy[row + i];
-        const TrBest r = best[row + i];
-        rows[row + lane_rank(mask, at)] = TrRow{i, q.x, q.y, r.kp, r.dist};
-    }
-    if (b == (n - 1) / kTrackCompactT && t == 0) n_proj[c] = total;   // (the last workgroup of n, whatever the grid)
+    return TrRank{keep, lane_rank(mask, at), total};
 }
 
-__global__ __launch_bounds__(kTrackCompactT) void k_track_compact(int n, const uint8_t *__restrict__ valid, const float2 *__restrict__ xy,
-                                                                  const TrBest *__restrict__ best, TrRow *__restrict__ rows,
-                                                                  int32_t *__restrict__ n_proj)
+// camera blockIdx.y's validity bytes (as k_track_project writes them) -> its kept candidates in candidate order; the last
+// workgroup of a camera has the camera's total.
+__device__ __forceinline__ void track_compact(int *before, int *kept, int n, const uint8_t *__restrict__ valid,
+                                              const float2 *__restrict__ xy, const TrBest *__restrict__ best, TrRow *__restrict__ rows,
+                                              int32_t *__restrict__ n_proj)
 {
-    __shared__ int before[kTrackCompactT / 64], kept[kTrackCompactT / 64];
-    track_compact(before, kept, n, valid, xy, best, rows, n_proj);
+    const int c = blockIdx.y, b = blockIdx.x;
+    if (b * kTrackCompactT >= n) return;   // (uniform over the workgroup)
+    const size_t row = (size_t)c * n;
+    const TrRank k = track_rank(valid + row, n, before, kept);
+    if (k.keep) {
+        const int i = b * kTrackCompactT + threadIdx.x;
+        const float2 q = xy[row + i];
+        const TrBest r = best[row + i];
+        rows[row + k.at] = TrRow{i, q.x, q.y, r.kp, r.dist};
+    }
+    if (b == (n - 1) / kTrackCompactT && threadIdx.x == 0) n_proj[c] = k.total;   // (the last workgroup of n, whatever the grid)
 }
 
 // n_proj: MCORB_MAX_CAMS counts per frame
-__global__ __launch_bounds__(kTrackCompactT) void k_track_compact_batch(const TrBatchItem *__restrict__ items,
-                                                                        const uint8_t *__restrict__ valid, const float2 *__restrict__ xy,
-                                                                        const TrBest *__restrict__ best, TrRow *__restrict__ rows,
-                                                                        int32_t *__restrict__ n_proj)
+__global__ __launch_bounds__(kTrackCompactT) void k_track_compact(const TrItem *__restrict__ items, const uint8_t *__restrict__ valid,
+                                                                  const float2 *__restrict__ xy, const TrBest *__restrict__ best,
+                                                                  TrRow *__restrict__ rows, int32_t *__restrict__ n_proj)
 {
     __shared__ int before[kTrackCompactT / 64], kept[kTrackCompactT / 64];
-    const TrBatchItem &it = items[blockIdx.z];
+    const TrItem &it = items[blockIdx.z];
     track_compact(before, kept, it.n, valid + it.rows, xy + it.rows, best + it.rows, rows + it.rows,
                   n_proj + (size_t)blockIdx.z * MCORB_MAX_CAMS);
 }
 
-void launch_track_compact(hipStream_t st, int ncams, int n, const uint8_t *valid, const float2 *xy, const TrBest *best, TrRow *rows,
-                          int32_t *n_proj)
-{
-    if (n < 1) return;
-    hipLaunchKernelGGL(k_track_compact, dim3((n + kTrackCompactT - 1) / kTrackCompactT, ncams), dim3(kTrackCompactT), 0, st, n, valid, xy,
-                       best, rows, n_proj);
-}
-
-void launch_track_compact_batch(hipStream_t st, const TrBatchItem *items, int nf, int max_n, int ncams, const uint8_t *valid,
-                                const float2 *xy, const TrBest *best, TrRow *rows, int32_t *n_proj)
+void launch_track_compact(hipStream_t st, const TrItem *items, int nf, int max_n, int ncams, const uint8_t *valid, const float2 *xy,
+                          const TrBest *best, TrRow *rows, int32_t *n_proj)
 {
     if (nf < 1 || max_n < 1) return;
-    hipLaunchKernelGGL(k_track_compact_batch, dim3((max_n + kTrackCompactT - 1) / kTrackCompactT, ncams, nf), dim3(kTrackCompactT), 0, st,
-                       items, valid, xy, best, rows, n_proj);
+    hipLaunchKernelGGL(k_track_compact, dim3((max_n + kTrackCompactT - 1) / kTrackCompactT, ncams, nf), dim3(kTrackCompactT), 0, st, items,
+                       valid, xy, best, rows, n_proj);
 }
 
 // ---- the de-duplication (mcorb_track.h, tr_dedup_value): per camera a segmented arg-min over the matched candidates, grouped by
@@ -411,22 +359,13 @@ __device__ __forceinline__ void track_dedup_min(const TrFrame &frame, const floa
     slot[row + i] = mine;
 }
 
-__global__ __launch_bounds__(kTrackDedupT) void k_track_dedup_min(TrFrame frame, const float2 *__restrict__ kp_xy, int n,
-                                                                  const uint8_t *__restrict__ valid, const TrBest *__restrict__ best,
-                                                                  int log2p, uint32_t *__restrict__ owner,
-                                                                  unsigned long long *__restrict__ val, int32_t *__restrict__ slot)
-{
-    track_dedup_min(frame, kp_xy, n, valid, best, log2p, owner, val, slot);
-}
-
 // frame f's tables are slots [tab, tab + (ncams << log2p)) of owner / val, a table per (frame, camera) of its own size
-__global__ __launch_bounds__(kTrackDedupT) void k_track_dedup_min_batch(const TrBatchItem *__restrict__ items,
-                                                                        const float2 *__restrict__ kp_xy,
-                                                                        const uint8_t *__restrict__ valid, const TrBest *__restrict__ best,
-                                                                        uint32_t *__restrict__ owner, unsigned long long *__restrict__ val,
-                                                                        int32_t *__restrict__ slot)
+__global__ __launch_bounds__(kTrackDedupT) void k_track_dedup_min(const TrItem *__restrict__ items, const float2 *__restrict__ kp_xy,
+                                                                  const uint8_t *__restrict__ valid, const TrBest *__restrict__ best,
+                                                                  uint32_t *__restrict__ owner, unsigned long long *__restrict__ val,
+                                                                  int32_t *__restrict__ slot)
 {
-    const TrBatchItem &it = items[blockIdx.z];
+    const TrItem &it = items[blockIdx.z];
     if ((int)(blockIdx.x * kTrackDedupT) >= it.n) return;
     track_dedup_min(it.frame, kp_xy + it.kp0, it.n, valid + it.rows, best + it.rows, it.log2p, owner + it.tab, val + it.tab,
                     slot + it.rows);
@@ -443,104 +382,52 @@ __device__ __forceinline__ void track_dedup_win(int n, const TrBest *__restrict_
     win[row + i] = s >= 0 && val[((size_t)c << log2p) + s] == tr_dedup_value(best[row + i].dist, i) ? 1 : 0;
 }
 
-__global__ __launch_bounds__(kTrackDedupT) void k_track_dedup_win(int n, const TrBest *__restrict__ best, const int32_t *__restrict__ slot,
-                                                                  const unsigned long long *__restrict__ val, int log2p,
-                                                                  uint8_t *__restrict__ win)
+__global__ __launch_bounds__(kTrackDedupT) void k_track_dedup_win(const TrItem *__restrict__ items, const TrBest *__restrict__ best,
+                                                                  const int32_t *__restrict__ slot,
+                                                                  const unsigned long long *__restrict__ val, uint8_t *__restrict__ win)
 {
-    track_dedup_win(n, best, slot, val, log2p, win);
-}
-
-__global__ __launch_bounds__(kTrackDedupT) void k_track_dedup_win_batch(const TrBatchItem *__restrict__ items,
-                                                                        const TrBest *__restrict__ best, const int32_t *__restrict__ slot,
-                                                                        const unsigned long long *__restrict__ val,
-                                                                        uint8_t *__restrict__ win)
-{
-    const TrBatchItem &it = items[blockIdx.z];
+    const TrItem &it = items[blockIdx.z];
     if ((int)(blockIdx.x * kTrackDedupT) >= it.n) return;
     track_dedup_win(it.n, best + it.rows, slot + it.rows, val + it.tab, it.log2p, win + it.rows);
 }
 
-// The winners in candidate order, ranked the way k_track_compact ranks the validity bytes: workgroup b counts the flags before
-// its own 256 itself, ranks its own by a ballot per wave and waits on nobody; the last workgroup of a camera has the camera's
-// total.  matches and n_match are host-mapped.
+// The winners in candidate order, ranked the way k_track_compact ranks the validity bytes (track_rank); the last workgroup of a
+// camera has the camera's total.  matches and n_match are host-mapped.
 __device__ __forceinline__ void track_dedup_emit(int *before, int *kept, int n, const uint8_t *__restrict__ win,
                                                  const TrBest *__restrict__ best, TrMatch *__restrict__ matches,
                                                  int32_t *__restrict__ n_match)
 {
-    const int c = blockIdx.y, b = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int c = blockIdx.y, b = blockIdx.x;
     if (b * kTrackDedupT >= n) return;   // (uniform over the workgroup)
     const size_t row = (size_t)c * n;
-    const uint8_t *p = win + row;
-    const int end = b * kTrackDedupT;    // a multiple of 16: the head and the tail below are 16 bytes together, or none
-    const int head = end ? (int)((16 - (reinterpret_cast<uintptr_t>(p) & 15)) & 15) : 0;
-    const int nvec = (end - head) >> 4, tail = head + (nvec << 4);
-    int s = 0;
-    if (t < head) s = p[t];
-    const uint4 *v = reinterpret_cast<const uint4 *>(p + head);
-    for (int j = t; j < nvec; j += kTrackDedupT) {
-        const uint4 q = v[j];
-        s += __popc(q.x) + __popc(q.y) + __popc(q.z) + __popc(q.w);
-    }
-    if (tail + t < end) s += p[tail + t];
-    for (int o = 32; o >= 1; o >>= 1) s += __shfl_xor(s, o, 64);
-
-    const int i = end + t;
-    const bool keep = i < n && p[i] != 0;
-    const unsigned long long mask = __ballot(keep);
-    if (lane == 0) {
-        before[wave] = s;
-        kept[wave] = __popcll(mask);
-    }
-    __syncthreads();
-    int at = 0, total = 0;
-    for (int w = 0; w < kTrackDedupT / 64; w++) {
-        at += before[w] + (w < wave ? kept[w] : 0);
-        total += before[w] + kept[w];
-    }
-    if (keep) {
+    const TrRank k = track_rank(win + row, n, before, kept);
+    if (k.keep) {
+        const int i = b * kTrackDedupT + threadIdx.x;
         const TrBest r = best[row + i];
-        matches[row + lane_rank(mask, at)] = TrMatch{i, r.kp, r.dist};
+        matches[row + k.at] = TrMatch{i, r.kp, r.dist};
     }
-    if (b == (n - 1) / kTrackDedupT && t == 0) n_match[c] = total;   // (the last workgroup of n, whatever the grid)
-}
-
-__global__ __launch_bounds__(kTrackDedupT) void k_track_dedup_emit(int n, const uint8_t *__restrict__ win, const TrBest *__restrict__ best,
-                                                                   TrMatch *__restrict__ matches, int32_t *__restrict__ n_match)
-{
-    __shared__ int before[kTrackDedupT / 64], kept[kTrackDedupT / 64];
-    track_dedup_emit(before, kept, n, win, best, matches, n_match);
+    if (b == (n - 1) / kTrackDedupT && threadIdx.x == 0) n_match[c] = k.total;   // (the last workgroup of n, whatever the grid)
 }
 
 // n_match: MCORB_MAX_CAMS counts per frame
-__global__ __launch_bounds__(kTrackDedupT) void k_track_dedup_emit_batch(const TrBatchItem *__restrict__ items,
-                                                                         const uint8_t *__restrict__ win, const TrBest *__restrict__ best,
-                                                                         TrMatch *__restrict__ matches, int32_t *__restrict__ n_match)
+__global__ __launch_bounds__(kTrackDedupT) void k_track_dedup_emit(const TrItem *__restrict__ items, const uint8_t *__restrict__ win,
+                                                                   const TrBest *__restrict__ best, TrMatch *__restrict__ matches,
+                                                                   int32_t *__restrict__ n_match)
 {
     __shared__ int before[kTrackDedupT / 64], kept[kTrackDedupT / 64];
-    const TrBatchItem &it = items[blockIdx.z];
+    const TrItem &it = items[blockIdx.z];
     track_dedup_emit(before, kept, it.n, win + it.rows, best + it.rows, matches + it.rows, n_match + (size_t)blockIdx.z * MCORB_MAX_CAMS);
 }
 
-void launch_track_dedup(hipStream_t st, const TrFrame &frame, int ncams, const float2 *kp_xy, int n, const uint8_t *valid, const TrBest *best,
-                        uint32_t *owner, unsigned long long *val, int32_t *slot, uint8_t *win, TrMatch *matches, int32_t *n_match)
-{
-    if (n < 1) return;
-    const int log2p = tr_dedup_log2(n);
-    const dim3 grid((n + kTrackDedupT - 1) / kTrackDedupT, ncams), block(kTrackDedupT);
-    hipLaunchKernelGGL(k_track_dedup_min, grid, block, 0, st, frame, kp_xy, n, valid, best, log2p, owner, val, slot);
-    hipLaunchKernelGGL(k_track_dedup_win, grid, block, 0, st, n, best, slot, val, log2p, win);
-    hipLaunchKernelGGL(k_track_dedup_emit, grid, block, 0, st, n, win, best, matches, n_match);
-}
-
-void launch_track_dedup_batch(hipStream_t st, const TrBatchItem *items, int nf, int max_n, int ncams, const float2 *kp_xy,
-                              const uint8_t *valid, const TrBest *best, uint32_t *owner, unsigned long long *val, int32_t *slot,
-                              uint8_t *win, TrMatch *matches, int32_t *n_match)
+void launch_track_dedup(hipStream_t st, const TrItem *items, int nf, int max_n, int ncams, const float2 *kp_xy, const uint8_t *valid,
+                        const TrBest *best, uint32_t *owner, unsigned long long *val, int32_t *slot, uint8_t *win, TrMatch *matches,
+                        int32_t *n_match)
 {
     if (nf < 1 || max_n < 1) return;
     const dim3 grid((max_n + kTrackDedupT - 1) / kTrackDedupT, ncams, nf), block(kTrackDedupT);
-    hipLaunchKernelGGL(k_track_dedup_min_batch, grid, block, 0, st, items, kp_xy, valid, best, owner, val, slot);
-    hipLaunchKernelGGL(k_track_dedup_win_batch, grid, block, 0, st, items, best, slot, val, win);
-    hipLaunchKernelGGL(k_track_dedup_emit_batch, grid, block, 0, st, items, win, best, matches, n_match);
+    hipLaunchKernelGGL(k_track_dedup_min, grid, block, 0, st, items, kp_xy, valid, best, owner, val, slot);
+    hipLaunchKernelGGL(k_track_dedup_win, grid, block, 0, st, items, best, slot, val, win);
+    hipLaunchKernelGGL(k_track_dedup_emit, grid, block, 0, st, items, win, best, matches, n_match);
 }
 
 }  // namespace mcorb

@@ -1,6 +1,6 @@
 // The packed-input layouts of the local map's calls (mcorb_pack.h) as a stand-alone program under the sanitizers:
 //   g++ -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=all -I mc-slam_amd/csrc tests/cpp/test_pack_sanitize.cpp
-// The six blocks the library builds -- pose, RANSAC, a tracking frame, a tracking batch, the two mapping entries -- with the
+// The five blocks the library builds -- pose, RANSAC, a tracking call, the two mapping entries -- with the
 // library's item types and small counts, zero-count items and a zero-size whole among them.  Every offset is a multiple of 32,
 // no two items overlap, and the total covers the last item: every item is written end to end, with a value of its own, into a
 // std::vector<uint8_t>(total), which the address sanitizer bounds, and read back.  Prints "bad=0".
@@ -56,16 +56,12 @@ static void obs(const char *name, size_t n, bool lids, bool sac, size_t S, size_
            {L.cam_first, sac ? (ncams + 1) * sizeof(int32_t) : 0}, {L.cam_cons, sac ? S * sizeof(int32_t) : 0}, {L.is_first, sac ? n : 0}});
 }
 
-static void track(const char *name, size_t nc, size_t total_kp)
+static void track(const char *name, size_t nf, size_t ncand, size_t total_kp)
 {
-    const TrackLayout L(nc, total_kp);
-    check(name, L.p.total, {{L.cand, nc * sizeof(int32_t)}, {L.xy, total_kp * 2 * sizeof(float)}, {L.desc, total_kp * 32}});
-}
-
-static void batch(const char *name, size_t nf, size_t ncand)
-{
-    const TrackBatchLayout L(nf, ncand);
-    check(name, L.p.total, {{L.items, nf * sizeof(TrBatchItem)}, {L.views, nf * sizeof(mcorb_track_view)}, {L.cand, ncand * sizeof(int32_t)}});
+    const TrackLayout L(nf, ncand, total_kp);
+    check(name, L.p.total,
+          {{L.items, nf * sizeof(TrItem)}, {L.views, nf * sizeof(mcorb_track_view)}, {L.cand, ncand * sizeof(int32_t)},
+           {L.xy, total_kp * 2 * sizeof(float)}, {L.desc, total_kp * 32}});
 }
 
 static void map(const char *name, size_t nframes, size_t nF, size_t C, size_t nlevels, size_t nmi, size_t nkp, size_t nb, size_t ni, size_t nz)
@@ -94,12 +90,13 @@ int main()
     obs("sac, ids", 9, true, true, 4, 2);
     obs("sac, points, 16 cameras", 33, false, true, 33, 16);
     obs("sac, one camera", 3, false, true, 1, 1);
-    track("track, a rig slot's frame", 13, 0);
-    track("track, host arrays", 13, 21);
-    track("track, one candidate and one keypoint", 1, 1);
-    batch("batch, one frame", 1, 3);
-    batch("batch, five frames", 5, 77);
-    batch("batch, a frame without candidates", 2, 0);
+    track("track, a rig slot's frame", 1, 13, 0);
+    track("track, host arrays", 1, 13, 21);
+    track("track, one candidate and one keypoint", 1, 1, 1);
+    track("track, one frame of a slot", 1, 3, 0);
+    track("track, five frames", 5, 77, 0);
+    track("track, frames without candidates", 2, 0, 0);
+    track("track, 32 frames", 32, 32 * 257 + 1, 0);
     map("neighbours", 3, 2 * 2 * 2 * 9, 2, 8, 40, 55, 3, 70, 11);
     map("neighbours, none", 1, 0, 1, 1, 4, 4, 0, 0, 0);
     map("neighbours, host-only (no blocks)", 2, 9, 1, 8, 6, 9, 0, 0, 5);

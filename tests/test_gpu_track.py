@@ -230,3 +230,42 @@ def test_timing(mc, vocs):
     assert us[0] > 0 and us[1] > 0
     lm.track(T.to_view(mc, T.flat_view()), [xy], [ds], [-1, -1])              # no candidate: nothing is launched
     assert lm.last_track_timing() == us
+
+
+@pytest.mark.parametrize("refine", [False, True])
+def test_host_arrays_with_an_empty_camera_in_the_middle(mc, vocs, refine):
+    """host arrays through the frame's item: cameras of 5, 0 and 1025 keypoints, so that first[c], the running keypoint count,
+    repeats (5, 5) and the last camera has one keypoint in a second LDS tile of k_track_match; 257 candidates, one past a workgroup
+    of k_track_compact and of the de-duplication.  The device store against the host-only store in every field of the
+    TrackResult, without and with set_track_refine (then last_track_pose too)"""
+    import pose_cases as PC
+    rng = np.random.default_rng(257)
+    n = 257
+    store = crowd(rng, n)
+    for l in (1, 2, 3, 4, 5, 7):                                              # (none behind: crowd puts every ninth there)
+        store[l] = ((100.0 + 150.0 * l, 90.0 * l, 1.0), store[l][1])
+    v = T.flat_view(ncams=3)
+    k0 = np.array([store[l][0][:2] for l in (1, 2, 3, 4, 5)], np.float32) + 0.25
+    d0 = np.array([store[l][1] for l in (1, 2, 3, 4, 5)], np.uint8)
+    k2, d2 = keypoints(rng, 1025)
+    x7, y7 = store[7][0][:2]
+    k2[:1024][np.hypot(k2[:1024, 0] - x7, k2[:1024, 1] - y7) < 3] += 5
+    k2[1024], d2[1024] = (x7 + 0.5, y7), store[7][1]                           # the second tile's one keypoint: landmark 7's match
+    xy, ds = T.kp_arrays([k0, np.zeros((0, 2), np.float32), k2], [d0, np.zeros((0, 32), np.uint8), d2])
+    lids = list(rng.permutation(n))
+    lms = stores(mc, vocs, store)
+    got, poses = [], []
+    for lm in lms:
+        lm.set_track_refine(PC.INV_SIGMA2 if refine else None)
+        got.append(T.as_lists(lm.track(T.to_view(mc, v), xy, ds, lids)))
+        if refine:
+            poses.append(PC.as_ref(lm.last_track_pose()))
+        lm.set_track_refine(None)
+    T.same(got[0], got[1], "device store against host-only store")
+    assert got[0] == got[1]
+    assert got[0]["n_candidates"] == n and len(got[0]["proj"][1]) > n // 2
+    assert len(got[0]["matches"][0]) == 5 and got[0]["matches"][1] == [] and all(b == (-1, 10000) for b in got[0]["best"][1])
+    assert (1024, 7, 0) in got[0]["matches"][2] and len(got[0]["matches"][2]) > 20
+    if refine:
+        PC.same(poses[0], poses[1], "last_track_pose, device store against host-only store")
+        assert len(poses[0]["inliers"]) == sum(len(m) for m in got[0]["matches"]) and 0 < poses[0]["n_inliers"] < len(poses[0]["inliers"])

@@ -1,5 +1,5 @@
 """Fast tracking of all frames of a rig slot's job in one submission (LocalMap.track_rig_frames, track_rig_frames_submit,
-track_frames_wait: the seven k_track_*_batch kernels, the frame in the grid's z).  Frame f of a batched call must be, bit for bit,
+track_frames_wait: the seven k_track_* kernels, the frame in the grid's z).  Frame f of a batched call must be, bit for bit,
 what track_rig_frame gives for (views[f], frames[f], lids[f]) on the device store, what it gives on a host-only store, and what
 the restatement (track_ref.py) gives on the frame read back with Rig.features; the batch on a host-only store must give the same
 again.  Floats as raw bytes, every integer and list, no tolerance and no excluded case.  assert_not_vacuous runs on the
@@ -187,7 +187,7 @@ def test_keypoint_extremes(mc, vocs):
 
 @pytest.mark.parametrize("C", [1, 4])
 def test_small_batch(mc, vocs, C):
-    """a one-frame job is a small batch, whose selection words may live in host-mapped memory, which k_track_points_batch reads
+    """a one-frame job is a small batch, whose selection words may live in host-mapped memory, which k_track_points reads
     there; a match job that follows points the slot's control view at the device mirror, which such a batch never filled (a rig
     of one camera has no pair to match)"""
     rig = extracted(mc, C, W, H, 1, 300)

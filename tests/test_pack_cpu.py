@@ -8,7 +8,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_layouts_under_asan_ubsan(tmp_path):
-    """tests/cpp/test_pack_sanitize.cpp (its own main, plain g++, -fsanitize=address,undefined): the six blocks the library
+    """tests/cpp/test_pack_sanitize.cpp (its own main, plain g++, -fsanitize=address,undefined): the five blocks the library
     builds, with its item types -- every offset a multiple of 32, no overlap, the total covering the last item, an item of no
     elements taking no space; every item is written end to end into a vector of `total` bytes.  No report, bad=0"""
     exe = str(tmp_path / "test_pack_sanitize")
