@@ -1218,6 +1218,80 @@ int mcorb_sac_eval(int ncams, const mcorb_track_cam *cams, int n, const int32_t 
                    const double *t, double *score);
 
 /* ------------------------------------------------------------------------- */
+/* The relative rig pose between two frames by RANSAC on 2D-2D matches: the    */
+/* estimator the reference's front end selects by default (FrontEnd.h:623,     */
+/* SEVENTEEN_PT) -- OpenGV's sac::Ransac<NoncentralRelativePoseSacProblem>     */
+/* (SEVENTEENPT) as FrontEnd::poseFromSeventeenPt (MCSlam/src/FrontEnd.cpp:    */
+/* 4532-4657, 10000 iterations) and LoopCloser::checkEssentialMatrix           */
+/* (LoopCloser.cpp:353-446, 2000 iterations).  It needs no landmarks.  OpenGV  */
+/* is not in the tree: its distance is recalled; the draws, the linear solver  */
+/* and the absence of the adaptive stop are stated.     */
+/* ------------------------------------------------------------------------- */
+#define MCORB_REL_MAX_ITERATIONS 16384
+#define MCORB_REL_SAMPLE 17
+#define MCORB_REL_OK 0            /* a hypothesis won */
+#define MCORB_REL_NO_OBS 1        /* no matches: the identity, nothing ran */
+#define MCORB_REL_NO_MODEL 2      /* no hypothesis had a model (fewer than 17 matches, a central rig): the identity, every flag 0 */
+/* threshold: on the sum over both views of 1 - cos(angle between the bearing and the triangulated point's direction); the
+ * reference's is mcorb_rel_threshold(K[0](0, 2)).  max_iterations: the hypotheses, 1 .. MCORB_REL_MAX_ITERATIONS (the reference
+ * sets 10000, its loop closer 2000), all of them examined.  seed: of the draws */
+typedef struct mcorb_rel_params {
+    double threshold;
+    uint64_t seed;
+    int32_t max_iterations, reserved;
+} mcorb_rel_params;
+/* (R, t) = b1_T_b2, R row-major: X_b1 = R X_b2 + t, the reference's T before `WTp * T` (:4646); status: MCORB_REL_*; n_inliers: the
+ * winner's inlier matches; n_matches: n; best_hypothesis (-1: none); sample: the winner's 17 matches in draw order; n_models: the
+ * hypotheses that had a model */
+typedef struct mcorb_rel_result {
+    double R[9], t[3];
+    int32_t status, n_inliers, n_matches, best_hypothesis, sample[MCORB_REL_SAMPLE], n_models;
+} mcorb_rel_result;
+/* The pose of a rig's second frame in its first from n 2D-2D matches.  Match i is the keypoint uv1[i] (KeyPoint::pt) in camera
+ * cam1[i] of frame 1 and uv2[i] in camera cam2[i] of frame 2: the first camera of each frame's IntraMatch (the breaks at :4559,
+ * :4576), which the caller passes.  The rig is mcorb_lmap_refine_pose's.  All arithmetic is fp64, one IEEE operation per operator
+ * in the order written (csrc/mcorb_rel.h), + - * /, comparisons and sqrt:
+ * - the rays: f the bearing of mcorb_lmap_ransac_pose (with s = 0 the reference's :4551-4557), d = cams[cam].R f, c = cams[cam].t,
+ *   m = c x d.
+ * - the sample: 17 distinct matches by a partial Fisher-Yates walk without rejection.  Draw j = 0 .. 16 of hypothesis h is the
+ *   splitmix64 finaliser of seed + 0x9E3779B97F4A7C15 (1 + 32 h + j); idx = draw mod (n - j); the earlier picks are walked in
+ *   ascending order and idx steps over each that is <= it; member j is idx.  n < 17: no model.
+ * - the solver (stated: Li, Hartley and Kim's linear method on the generalized epipolar constraint d1^T E d2 + d1^T R m2 + m1^T R
+ *   d2 = 0, E = [t]x R): the R part's nine columns are projected out of the E part's, E is the null vector of what remains, the two
+ *   rotations of E are read off in closed form and polished, t follows by least squares with its scale, the candidate with the
+ *   smaller residual wins, and a model whose translation scale is not observable (a central rig) is no model (csrc/mcorb_rel.h,
+ *   rel_solve17).
+ * - the score (OpenGV's distance of the non-central relative problem, recalled): with a = d1, b = R d2, w = (R c2 + t) - c1 the
+ *   midpoint P1 of the rays' closest points, P2 = P1 - w, and (1 - a.P1 / |P1|) + (1 - b.P2 / (|P2| |b|)); a match is an inlier
+ *   iff score < threshold, strictly; a NaN is no inlier.
+ * - the consensus: the largest inlier count over all n matches wins, a tie goes to the lowest hypothesis, a hypothesis without a
+ *   model never wins; all max_iterations hypotheses are examined (no adaptive stop).
+ * A device store runs k_rel_hypotheses, k_rel_score and k_rel_pick in one submission on its stream with one wait; a host-only
+ * store runs the same header serially: the results are equal bit for bit.  The store's landmarks are neither read nor written.
+ * inlier (may be NULL): one flag per match.  Refused before anything runs: MCORB_E_ARG for a NULL, n < 0, ncams outside 1 ..
+ * MCORB_MAX_CAMS, a camera outside the rig, a threshold that is not finite and positive, max_iterations outside 1 ..
+ * MCORB_REL_MAX_ITERATIONS; MCORB_E_STATE while a tracking call is pending. */
+int mcorb_lmap_relative_pose(mcorb_lmap *m, int n, const int32_t *cam1, const float *uv1, const int32_t *cam2, const float *uv2, int ncams,
+                             const mcorb_track_cam *cams, const mcorb_rel_params *params, mcorb_rel_result *res, uint8_t *inlier);
+/* a device store's last k_rel_hypotheses (us[0]), k_rel_score (us[1]) and k_rel_pick (us[2]) launch, microseconds between HIP
+ * events, and its hypotheses; a call without matches launches nothing and leaves them */
+int mcorb_lmap_last_relative_timing(mcorb_lmap *m, float us[3], int *n_hyp);
+/* test hook: the counts of all hypotheses of the last call that ran any, and whether each had a model (a hypothesis without one
+ * has count 0); a device store copies them down from where k_rel_score left them.  MCORB_E_CAP (with n_hyp set) when cap < n_hyp */
+int mcorb_lmap_last_relative_counts(mcorb_lmap *m, int32_t *count, int32_t *valid, int cap, int *n_hyp);
+/* the reference's threshold (:4604): 2 * mcorb_sac_threshold(K00_02) */
+double mcorb_rel_threshold(double K00_02);
+/* test hook, host: the solver on 17 matches (cam1[17], uv1 17 x 2, cam2[17], uv2 17 x 2) of the rig cams[ncams] -> 1 with (R as 9,
+ * t as 3 doubles) = b1_T_b2, 0 without a model, or a negative error.  The hooks take the keypoints in double: a float's value
+ * gives the bits mcorb_lmap_relative_pose computes from that float, and a test can state a problem without rounding in either
+ * frame */
+int mcorb_rel_solve(int ncams, const mcorb_track_cam *cams, const int32_t *cam1, const double *uv1, const int32_t *cam2, const double *uv2,
+                    double *R, double *t);
+/* test hook, host: the scores of n matches at the pose (R, t); a NaN is the default quiet NaN */
+int mcorb_rel_eval(int ncams, const mcorb_track_cam *cams, int n, const int32_t *cam1, const double *uv1, const int32_t *cam2,
+                   const double *uv2, const double *R, const double *t, double *score);
+
+/* ------------------------------------------------------------------------- */
 /* Host stages exposed for the CPU test-suite (no device needed)              */
 /* ------------------------------------------------------------------------- */
 /* The engine's quad-tree selection, DistributeOctTree's equivalent (ORBextractor.cpp:554-778), run

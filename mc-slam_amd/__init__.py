@@ -1567,6 +1567,40 @@ class LocalMap:
         _lib.check(self.L.mcorb_lmap_last_ransac_counts(self.h, count.ctypes.data, valid.ctypes.data, 1024, C.byref(nh)))
         return count[:nh.value], valid[:nh.value].astype(bool)
 
+    # the relative rig pose between two frames by RANSAC on 2D-2D matches (mcorb_lmap_relative_pose)
+    def relative_pose(self, cams, cam1, uv1, cam2, uv2, threshold, max_iterations=10000, seed=0):
+        """the pose b1_T_b2 of a rig's second frame in its first from 2D-2D matches, without landmarks: the consensus step of
+        FrontEnd::poseFromSeventeenPt and LoopCloser::checkEssentialMatrix.  Match i is the keypoint uv1[i] in camera cam1[i] of
+        frame 1 and uv2[i] in camera cam2[i] of frame 2; cams: pose_cams(...) or a track_view; threshold: on the sum over both
+        views of 1 - cos of the angle to the triangulated midpoint, rel_threshold(K[0](0, 2)) in the reference; max_iterations
+        hypotheses of 17 matches each (1 .. REL_MAX_ITERATIONS), all examined; seed: of the draws.  -> RelResult.  A device store
+        runs k_rel_hypotheses, k_rel_score and k_rel_pick in one submission; a host-only store the same arithmetic serially, with
+        the same bits.  The store's landmarks are not touched"""
+        cam1 = np.ascontiguousarray(cam1, np.int32).reshape(-1)
+        n = len(cam1)
+        cam2 = np.ascontiguousarray(cam2, np.int32).reshape(n)
+        uv1 = np.ascontiguousarray(uv1, np.float32).reshape(n, 2)
+        uv2 = np.ascontiguousarray(uv2, np.float32).reshape(n, 2)
+        ncams, ca = _pose_cams(cams)
+        par = _lib.RelParams()
+        par.threshold, par.seed, par.max_iterations = float(threshold), int(seed) & 0xFFFFFFFFFFFFFFFF, int(max_iterations)
+        res, flags = _lib.RelResultC(), np.zeros(max(n, 1), np.uint8)
+        _lib.check(self.L.mcorb_lmap_relative_pose(self.h, n, cam1.ctypes.data, uv1.ctypes.data, cam2.ctypes.data, uv2.ctypes.data, ncams, ca,
+                                                   C.byref(par), C.byref(res), flags.ctypes.data))
+        return RelResult(res, flags[:n])
+
+    def last_relative_timing(self):
+        """((us of k_rel_hypotheses, k_rel_score, k_rel_pick), hypotheses) of the last relative_pose() launch; a device store"""
+        us, nh = (C.c_float * 3)(), C.c_int(0)
+        _lib.check(self.L.mcorb_lmap_last_relative_timing(self.h, us, C.byref(nh)))
+        return tuple(us), nh.value
+
+    def last_relative_counts(self):
+        """test hook: (counts, has a model) of all hypotheses of the last relative_pose() that ran any"""
+        count, valid, nh = np.zeros(REL_MAX_ITERATIONS, np.int32), np.zeros(REL_MAX_ITERATIONS, np.int32), C.c_int(0)
+        _lib.check(self.L.mcorb_lmap_last_relative_counts(self.h, count.ctypes.data, valid.ctypes.data, REL_MAX_ITERATIONS, C.byref(nh)))
+        return count[:nh.value], valid[:nh.value].astype(bool)
+
     def set_track_refine(self, inv_sigma2=None, max_iterations=25):
         """inv_sigma2 given: from now on every tracking call on the store -- track, track_rig_frame, the submit / wait pair,
         track_rig_frames -- also refines, per frame and in the same submission, the pose of the view's rig from the frame's
@@ -1621,6 +1655,60 @@ class SacResult:
 SAC_OK, SAC_NO_OBS, SAC_NO_MODEL = 0, 1, 2
 SAC_SOLVER_CENTRAL, SAC_SOLVER_RIG = 0, 1
 SAC_SOLVERS = {"central": SAC_SOLVER_CENTRAL, "rig": SAC_SOLVER_RIG}
+
+
+class RelResult:
+    """what LocalMap.relative_pose returns: R (3 x 3), t = b1_T_b2 (X_b1 = R X_b2 + t; the identity without a winner); status
+    (REL_OK, REL_NO_OBS, REL_NO_MODEL); n_inliers and inliers, one bool per match; n_matches; best_hypothesis (-1: none); sample
+    (the winner's 17 matches in draw order); n_models"""
+
+    def __init__(self, res, flags):
+        self.R = np.array(res.R[:], np.float64).reshape(3, 3)
+        self.t = np.array(res.t[:], np.float64)
+        self.status, self.n_inliers, self.n_matches = res.status, res.n_inliers, res.n_matches
+        self.best_hypothesis, self.sample, self.n_models = res.best_hypothesis, tuple(res.sample[:]), res.n_models
+        self.inliers = flags.astype(bool)
+
+
+REL_OK, REL_NO_OBS, REL_NO_MODEL = 0, 1, 2
+REL_MAX_ITERATIONS, REL_SAMPLE = 16384, 17
+
+
+def rel_threshold(K00_02):
+    """the reference's threshold of the relative problem: 2 * sac_threshold(K[0](0, 2))"""
+    return _lib.load().mcorb_rel_threshold(float(K00_02))
+
+
+def _rel_arrays(cam1, uv1, cam2, uv2):
+    """the hooks' inputs: the keypoints go down as doubles (a float's value gives the bits relative_pose computes from it)"""
+    cam1 = np.ascontiguousarray(cam1, np.int32).reshape(-1)
+    n = len(cam1)
+    return (n, cam1, np.ascontiguousarray(uv1, np.float64).reshape(n, 2), np.ascontiguousarray(cam2, np.int32).reshape(n),
+            np.ascontiguousarray(uv2, np.float64).reshape(n, 2))
+
+
+def rel_solve(cams, cam1, uv1, cam2, uv2):
+    """test hook (host): the 17-point solver on 17 matches -> (R 3 x 3, t) = b1_T_b2, or None without a model"""
+    n, cam1, uv1, cam2, uv2 = _rel_arrays(cam1, uv1, cam2, uv2)
+    assert n == REL_SAMPLE
+    ncams, ca = _pose_cams(cams)
+    R, t = np.zeros(9), np.zeros(3)
+    k = _lib.load().mcorb_rel_solve(ncams, ca, cam1.ctypes.data, uv1.ctypes.data, cam2.ctypes.data, uv2.ctypes.data, R.ctypes.data,
+                                    t.ctypes.data)
+    _lib.check(min(k, 0))
+    return (R.reshape(3, 3), t) if k else None
+
+
+def rel_eval(cams, R, t, cam1, uv1, cam2, uv2):
+    """test hook (host): the scores (n) of the matches at the pose (R, t) = b1_T_b2"""
+    n, cam1, uv1, cam2, uv2 = _rel_arrays(cam1, uv1, cam2, uv2)
+    R = np.ascontiguousarray(R, np.float64).reshape(9)
+    t = np.ascontiguousarray(t, np.float64).reshape(3)
+    score = np.zeros(max(n, 1))
+    ncams, ca = _pose_cams(cams)
+    _lib.check(_lib.load().mcorb_rel_eval(ncams, ca, n, cam1.ctypes.data, uv1.ctypes.data, cam2.ctypes.data, uv2.ctypes.data, R.ctypes.data,
+                                          t.ctypes.data, score.ctypes.data))
+    return score[:n]
 
 
 def sac_threshold(K00_02):

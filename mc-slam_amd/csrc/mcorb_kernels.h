@@ -1,6 +1,6 @@
 // mcorb_kernels.h -- launch wrappers of the gfx950 kernels (mcorb_kernels.hip, mcorb_select_gpu.hip, mcorb_handoff_gpu.hip,
 // mcorb_bow_gpu.hip, mcorb_lf_gpu.hip, mcorb_kfdb_gpu.hip, mcorb_lmap_gpu.hip, mcorb_mapping_gpu.hip, mcorb_landmark_gpu.hip,
-// mcorb_track_gpu.hip, mcorb_pose_gpu.hip, mcorb_sac_gpu.hip).
+// mcorb_track_gpu.hip, mcorb_pose_gpu.hip, mcorb_sac_gpu.hip, mcorb_rel_gpu.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <vector>
@@ -8,6 +8,7 @@
 #include "mcorb_common.h"
 #include "mcorb_mapping_new.h"
 #include "mcorb_pose.h"
+#include "mcorb_rel.h"
 #include "mcorb_sac.h"
 #include "mcorb_signal.h"
 #include "mcorb_track.h"
@@ -260,5 +261,25 @@ void launch_sac_hypotheses(hipStream_t st, const SacArgs &a, int H);
 void launch_sac_hypotheses_rig(hipStream_t st, const SacArgs &a, int H);
 void launch_sac_score(hipStream_t st, const SacArgs &a, int S, int H);
 void launch_sac_pick(hipStream_t st, const SacArgs &a, int n);
+
+// the relative pose between two frames by RANSAC (mcorb_rel_gpu.hip), three launches.  job and obs (the S matches) are device
+// memory.  k_rel_hypotheses: one lane per hypothesis, models[H].  k_rel_score: a workgroup per (tile of kRelTile matches, block of
+// kRelHypBlock hypotheses), integer adds into count[H], which the caller has zeroed on the stream.  k_rel_pick: the winner, the
+// flags of all S matches (host-mapped) and the record out (host-mapped)
+#ifndef MCORB_REL_HYP_BLOCK
+#define MCORB_REL_HYP_BLOCK 32   // measured against 8 and 128 (make EXTRA=-DMCORB_REL_HYP_BLOCK=..)
+#endif
+constexpr int kRelTile = 256, kRelHypBlock = MCORB_REL_HYP_BLOCK;
+struct RelArgs {
+    const RelJob *job;
+    const RelObs *obs;
+    RelModel *models;
+    int32_t *count;
+    RelOut *out;
+    uint8_t *flags;
+};
+void launch_rel_hypotheses(hipStream_t st, const RelArgs &a, int H);
+void launch_rel_score(hipStream_t st, const RelArgs &a, int S, int H);
+void launch_rel_pick(hipStream_t st, const RelArgs &a, int S);
 
 }  // namespace mcorb

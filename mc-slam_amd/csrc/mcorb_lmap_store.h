@@ -11,6 +11,7 @@
 #include "mcorb_mapping_new.h"
 #include "mcorb_pack.h"
 #include "mcorb_pose.h"
+#include "mcorb_rel.h"
 #include "mcorb_sac.h"
 #include "mcorb_track.h"
 
@@ -253,6 +254,27 @@ struct mcorb_lmap {
             return refine ? pose.reserve(n) : MCORB_OK;
         }
     } sac;
+
+    // the relative pose between two frames by RANSAC (mcorb_rel.cpp), grow-only: the packed input (RelLayout), the models and
+    // counts of the hypotheses, and what the host reads: the pick's record and the flags per match, host-mapped
+    struct Rel {
+        mcorb::Staged in;
+        mcorb::DevBuf<mcorb::RelModel> d_models;
+        mcorb::DevBuf<int32_t> d_count;
+        mcorb::HostBuf<mcorb::RelOut> h_out;
+        mcorb::HostBuf<uint8_t> h_flags;
+        mcorb::Spans<3> kernels;                // k_rel_hypotheses, k_rel_score, k_rel_pick
+        int last_hyp = 0;                       // the hypotheses of the last call that ran any (either kind of store)
+        std::vector<int32_t> host_count, host_valid;   // a host-only store's last counts, for mcorb_lmap_last_relative_counts
+        int reserve(size_t bytes, size_t n, size_t H)
+        {
+            TRY(in.reserve(bytes));
+            TRY(d_models.grow(H));
+            TRY(d_count.grow(H));
+            TRY(h_out.grow(1, mcorb::kHostMapped));
+            return h_flags.grow(n, mcorb::kHostMapped);
+        }
+    } rel;
 };
 
 // the pose refinement behind a tracking call (mcorb_pose.cpp); the caller holds the store's lock and has set track_refine_params.

@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "mcorb_mapping.h"
+#include "mcorb_rel.h"
 #include "mcorb_sac.h"
 
 namespace mcorb {
@@ -33,6 +34,13 @@ struct ObsLayout {
         : pose_job(p.add<PoseJob>(1)), sac_job(p.add<SacJob>(sac ? 1 : 0)), obs(p.add<PoseObs>(n)),
           pt(lids ? p.add<int32_t>(n) : p.add<double>(3 * n)), cons(p.add<int32_t>(sac ? S : 0)),
           cam_first(p.add<int32_t>(sac ? ncams + 1 : 0)), cam_cons(p.add<int32_t>(sac ? S : 0)), is_first(p.add<uint8_t>(sac ? n : 0)) {}
+};
+
+// mcorb_lmap_relative_pose: the RelJob and the n matches
+struct RelLayout {
+    Pack p;
+    size_t job, obs;
+    explicit RelLayout(size_t n) : job(p.add<RelJob>(1)), obs(p.add<RelObs>(n)) {}
 };
 
 // a tracking submission of nf frames: a TrItem and a view per frame, every frame's candidates, then -- host arrays only -- the

@@ -1,0 +1,194 @@
+// mcorb_rel.cpp -- the relative rig pose between two frames by RANSAC: mcorb_lmap_relative_pose, the consensus step of
+// FrontEnd::poseFromSeventeenPt (MCSlam/src/FrontEnd.cpp:4532-4657) and LoopCloser::checkEssentialMatrix (LoopCloser.cpp:353-446).
+// A device store runs k_rel_hypotheses, k_rel_score and k_rel_pick (mcorb_rel_gpu.hip) in one submission on the store's stream
+// with one wait; the records land in host-mapped memory.  A host-only store runs the header (mcorb_rel.h) serially, so the two
+// agree bit for bit.  Stated rather than OpenGV's: the draws, the linear solver, no adaptive stop.
+#include <math.h>
+#include <string.h>
+
+#include <mutex>
+#include <vector>
+
+#include "mcorb_lmap_store.h"
+
+using namespace mcorb;
+
+namespace {
+
+int fail(int code, const char *what) { set_error(std::string("lmap relative_pose: ") + what); return code; }
+
+int check_cams(int n, const int32_t *cam1, const int32_t *cam2, int ncams)
+{
+    for (int i = 0; i < n; i++)
+        if (cam1[i] < 0 || cam1[i] >= ncams || cam2[i] < 0 || cam2[i] >= ncams) return fail(MCORB_E_ARG, "a camera index outside the rig");
+    return MCORB_OK;
+}
+
+void fill_obs(RelObs *obs, int n, const int32_t *cam1, const float *uv1, const int32_t *cam2, const float *uv2)
+{
+    for (int i = 0; i < n; i++) obs[i] = RelObs{uv1[2 * i], uv1[2 * i + 1], uv2[2 * i], uv2[2 * i + 1], cam1[i], cam2[i]};
+}
+
+}  // namespace
+
+extern "C" {
+
+int mcorb_lmap_relative_pose(mcorb_lmap *m, int n, const int32_t *cam1, const float *uv1, const int32_t *cam2, const float *uv2, int ncams,
+                             const mcorb_track_cam *cams, const mcorb_rel_params *params, mcorb_rel_result *res, uint8_t *inlier)
+{
+    TRY(check_lmap(m, "lmap relative_pose"));
+    if (!params || !res || !cams || n < 0 || ncams < 1 || ncams > MCORB_MAX_CAMS || (n && (!cam1 || !uv1 || !cam2 || !uv2)))
+        return fail(MCORB_E_ARG, "bad argument");
+    if (!(params->threshold > 0) || !sac_finite(params->threshold)) return fail(MCORB_E_ARG, "a threshold that is not finite and positive");
+    if (params->max_iterations < 1 || params->max_iterations > MCORB_REL_MAX_ITERATIONS)
+        return fail(MCORB_E_ARG, "1 .. MCORB_REL_MAX_ITERATIONS iterations");
+    TRY(check_cams(n, cam1, cam2, ncams));
+    std::lock_guard<std::mutex> lk(m->mu);
+    if (m->track.pending.load()) return fail(MCORB_E_STATE, "a submitted tracking call has not been waited for");
+
+    const int S = n, H = params->max_iterations;
+    RelJob job;
+    memset(&job, 0, sizeof(job));
+    memcpy(job.cams, cams, (size_t)ncams * sizeof(mcorb_track_cam));
+    job.threshold = params->threshold;
+    job.seed = params->seed;
+    job.ncams = ncams;
+    job.S = S;
+    job.H = H;
+
+    RelOut out;
+    std::vector<uint8_t> flags((size_t)n);
+    mcorb_lmap::Rel &b = m->rel;
+    if (S == 0) {
+        memset(&out, 0, sizeof(out));
+        out.R[0] = out.R[4] = out.R[8] = 1.0;
+        out.status = MCORB_REL_NO_OBS;
+        out.best = -1;
+        for (int j = 0; j < kRelSample; j++) out.sample[j] = -1;
+    } else if (m->device < 0) {
+        std::vector<RelObs> obs((size_t)n);
+        fill_obs(obs.data(), n, cam1, uv1, cam2, uv2);
+        std::vector<RelModel> models((size_t)H);
+        std::vector<int32_t> count((size_t)H);
+        std::vector<RelRays> rays((size_t)S);
+        rel_run_serial(job, obs.data(), models.data(), count.data(), rays.data(), out, flags.data());
+        b.host_valid.resize((size_t)H);
+        for (int h = 0; h < H; h++) b.host_valid[h] = models[h].valid;
+        b.host_count.swap(count);
+        b.last_hyp = H;
+    } else {
+        HIPCHK(hipSetDevice(m->device));
+        (void)hipGetLastError();   // (a stale error of this thread is not this call's)
+        const RelLayout L((size_t)n);
+        TRY(b.reserve(L.p.total, (size_t)n, (size_t)H));
+        *b.in.host<RelJob>(L.job) = job;
+        fill_obs(b.in.host<RelObs>(L.obs), n, cam1, uv1, cam2, uv2);
+        hipStream_t st = m->st;
+        TRY(b.in.upload(st, L.p.total));
+        HIPCHK(hipMemsetAsync(b.d_count, 0, (size_t)H * sizeof(int32_t), st));
+        RelArgs a;
+        a.job = b.in.dev<const RelJob>(L.job);
+        a.obs = b.in.dev<const RelObs>(L.obs);
+        a.models = b.d_models;
+        a.count = b.d_count;
+        a.out = b.h_out;
+        a.flags = b.h_flags;
+        TRY(b.kernels.mark(st, 0));
+        launch_rel_hypotheses(st, a, H);
+        hipError_t launched = hipGetLastError();
+        TRY(b.kernels.mark(st, 1));
+        launch_rel_score(st, a, S, H);
+        if (launched == hipSuccess) launched = hipGetLastError();
+        TRY(b.kernels.mark(st, 2));
+        launch_rel_pick(st, a, S);
+        if (launched == hipSuccess) launched = hipGetLastError();
+        TRY(b.kernels.mark(st, 3));
+        HIPCHK(hipStreamSynchronize(st));
+        HIPCHK(launched);
+        b.kernels.read();
+        b.last_hyp = H;
+        out = *b.h_out.get();
+        memcpy(flags.data(), b.h_flags.get(), (size_t)n);
+    }
+
+    memset(res, 0, sizeof(*res));
+    memcpy(res->R, out.R, sizeof(out.R));
+    memcpy(res->t, out.t, sizeof(out.t));
+    res->status = out.status;
+    res->n_inliers = out.n_inliers;
+    res->n_matches = n;
+    res->best_hypothesis = out.best;
+    memcpy(res->sample, out.sample, sizeof(res->sample));
+    res->n_models = out.n_models;
+    if (inlier && n) memcpy(inlier, flags.data(), (size_t)n);
+    return MCORB_OK;
+}
+
+int mcorb_lmap_last_relative_timing(mcorb_lmap *m, float us[3], int *n_hyp)
+{
+    TRY(check_lmap_handle(m, "lmap last_relative_timing"));
+    if (!us) return fail(MCORB_E_ARG, "bad argument");
+    std::lock_guard<std::mutex> lk(m->mu);
+    for (int k = 0; k < 3; k++) us[k] = m->rel.kernels.us[k];
+    if (n_hyp) *n_hyp = m->rel.last_hyp;
+    return MCORB_OK;
+}
+
+int mcorb_lmap_last_relative_counts(mcorb_lmap *m, int32_t *count, int32_t *valid, int cap, int *n_hyp)
+{
+    TRY(check_lmap(m, "lmap last_relative_counts"));
+    if (cap < 0 || !n_hyp || (cap && (!count || !valid))) return fail(MCORB_E_ARG, "bad argument");
+    std::lock_guard<std::mutex> lk(m->mu);
+    const int H = m->rel.last_hyp;
+    *n_hyp = H;
+    if (cap < H) return fail(MCORB_E_CAP, "arrays too small");
+    if (m->device < 0) {
+        for (int h = 0; h < H; h++) {
+            count[h] = m->rel.host_count[h];
+            valid[h] = m->rel.host_valid[h];
+        }
+        return MCORB_OK;
+    }
+    if (!H) return MCORB_OK;
+    HIPCHK(hipSetDevice(m->device));
+    std::vector<RelModel> models((size_t)H);
+    HIPCHK(hipMemcpy(count, m->rel.d_count, (size_t)H * sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(models.data(), m->rel.d_models, (size_t)H * sizeof(RelModel), hipMemcpyDeviceToHost));
+    for (int h = 0; h < H; h++) valid[h] = models[h].valid;
+    return MCORB_OK;
+}
+
+double mcorb_rel_threshold(double K00_02) { return 2.0 * mcorb_sac_threshold(K00_02); }
+
+int mcorb_rel_solve(int ncams, const mcorb_track_cam *cams, const int32_t *cam1, const double *uv1, const int32_t *cam2, const double *uv2,
+                    double *R, double *t)
+{
+    if (ncams < 1 || ncams > MCORB_MAX_CAMS || !cams || !cam1 || !uv1 || !cam2 || !uv2 || !R || !t) return fail(MCORB_E_ARG, "bad argument");
+    TRY(check_cams(kRelSample, cam1, cam2, ncams));
+    RelRays rays[kRelSample];
+    for (int j = 0; j < kRelSample; j++) rel_rays_d(cams, cam1[j], uv1 + 2 * j, cam2[j], uv2 + 2 * j, rays[j]);
+    PoseState P;
+    const bool ok = rel_solve17(rays, P);
+    memcpy(R, P.R, sizeof(P.R));
+    memcpy(t, P.t, sizeof(P.t));
+    return ok ? 1 : 0;
+}
+
+int mcorb_rel_eval(int ncams, const mcorb_track_cam *cams, int n, const int32_t *cam1, const double *uv1, const int32_t *cam2,
+                   const double *uv2, const double *R, const double *t, double *score)
+{
+    if (n < 0 || ncams < 1 || ncams > MCORB_MAX_CAMS || !cams || !R || !t || (n && (!cam1 || !uv1 || !cam2 || !uv2 || !score)))
+        return fail(MCORB_E_ARG, "bad argument");
+    TRY(check_cams(n, cam1, cam2, ncams));
+    PoseState P;
+    memcpy(P.R, R, sizeof(P.R));
+    memcpy(P.t, t, sizeof(P.t));
+    for (int i = 0; i < n; i++) {
+        RelRays r;
+        rel_rays_d(cams, cam1[i], uv1 + 2 * (size_t)i, cam2[i], uv2 + 2 * (size_t)i, r);
+        score[i] = pose_default_nan(rel_score(P, r));
+    }
+    return MCORB_OK;
+}
+
+}  // extern "C"

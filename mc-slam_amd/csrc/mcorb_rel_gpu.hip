@@ -1,0 +1,145 @@
+// mcorb_rel_gpu.hip -- the relative rig pose between two frames by RANSAC of mcorb_rel.h on a device store (mcorb_rel.cpp): three
+// launches on the store's stream, no workgroup waits on another.
+//   k_rel_hypotheses   one lane per hypothesis: the 17 draws, the rays of the sample, the linear solver (its designs, the
+//                      Gram-Schmidt basis and null_vector's factorisation are private arrays, so they live in scratch); a model
+//                      record per hypothesis
+//   k_rel_score        the hot path, H x S two-view midpoint triangulations with two angles each: a workgroup owns a tile of
+//                      kRelTile matches, whose four ray vectors each lane computes once and keeps in registers, and a block of
+//                      kRelHypBlock hypotheses, whose models it reads at uniform addresses; per model a ballot and a population
+//                      count per wave into integer counts in LDS, then one integer atomicAdd per (workgroup, hypothesis) into
+//                      count[H].  The additions are integer: the result does not depend on their order
+//   k_rel_pick         every workgroup finds the arg-max of count[H] for itself and writes the winner's flags for its tile of
+//                      matches; workgroup 0 writes the record to host-mapped memory
+// The arithmetic is the header's, so the host-only store gives the same bits.  No extraction job runs this and no benchmark leg
+// times it.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "mcorb_common.h"
+#include "mcorb_device.h"
+#include "mcorb_kernels.h"
+#include "mcorb_rel.h"
+
+namespace mcorb {
+
+static_assert(kRelTile == 4 * 64, "four waves");
+static_assert(kRelHypBlock <= kRelTile, "a lane per hypothesis of the block adds its count");
+
+__global__ __launch_bounds__(64) void k_rel_hypotheses(const RelJob *__restrict__ job, const RelObs *__restrict__ obs,
+                                                       RelModel *__restrict__ models)
+{
+    const int h = blockIdx.x * 64 + threadIdx.x;
+    if (h >= job->H) return;
+    rel_hypothesis(*job, h, obs, models[h]);
+}
+
+__global__ __launch_bounds__(kRelTile) void k_rel_score(const RelJob *__restrict__ job, const RelObs *__restrict__ obs,
+                                                        const RelModel *__restrict__ models, int32_t *__restrict__ count)
+{
+    __shared__ int32_t cnt[kRelHypBlock];
+    const int t = threadIdx.x, lane = t & 63;
+    const int S = job->S, H = job->H;
+    const int k = blockIdx.x * kRelTile + t;
+    const bool in = k < S;
+    const double threshold = job->threshold;
+    RelRays r;
+    rel_rays(job->cams, obs[in ? k : 0], r);   // (S >= 1: a lane beyond the matches scores match 0 and counts nothing)
+    if (t < kRelHypBlock) cnt[t] = 0;
+    __syncthreads();
+    const int h0 = blockIdx.y * kRelHypBlock, h1 = min(H, h0 + kRelHypBlock);
+    for (int h = h0; h < h1; h++) {
+        const RelModel &M = models[h];   // (uniform over the workgroup)
+        if (!M.valid) continue;
+        PoseState P;
+#pragma unroll
+        for (int j = 0; j < 9; j++) P.R[j] = M.R[j];
+#pragma unroll
+        for (int j = 0; j < 3; j++) P.t[j] = M.t[j];
+        const bool inl = in && sac_is_inlier(rel_score(P, r), threshold);
+        const unsigned long long mask = __ballot(inl);
+        if (lane == 0 && mask) atomicAdd(&cnt[h - h0], __popcll(mask));
+    }
+    __syncthreads();
+    if (t < h1 - h0 && cnt[t]) atomicAdd(&count[h0 + t], cnt[t]);
+}
+
+__global__ __launch_bounds__(kRelTile) void k_rel_pick(const RelJob *__restrict__ job, const RelObs *__restrict__ obs,
+                                                       const RelModel *__restrict__ models, const int32_t *__restrict__ count, RelOut *out,
+                                                       uint8_t *flags)
+{
+    __shared__ unsigned long long wkey[4];
+    __shared__ int32_t wmodels[4];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int S = job->S, H = job->H;
+    unsigned long long key = 0;
+    int32_t nm = 0;
+    for (int h = t; h < H; h += kRelTile) {
+        const int32_t valid = models[h].valid;
+        const unsigned long long kh = rel_key(valid, count[h], h);
+        key = kh > key ? kh : key;
+        nm += valid;
+    }
+    for (int s = 32; s >= 1; s >>= 1) {
+        const unsigned long long other = __shfl_xor(key, s, 64);
+        key = other > key ? other : key;
+        nm += __shfl_xor(nm, s, 64);
+    }
+    if (lane == 0) {
+        wkey[wave] = key;
+        wmodels[wave] = nm;
+    }
+    __syncthreads();
+    key = wkey[0];
+    for (int w = 1; w < 4; w++) key = wkey[w] > key ? wkey[w] : key;
+    const int best = rel_key_hypothesis(key);   // (the same in every lane)
+    PoseState P;
+#pragma unroll
+    for (int j = 0; j < 9; j++) P.R[j] = (j % 4 == 0) ? 1.0 : 0.0;
+#pragma unroll
+    for (int j = 0; j < 3; j++) P.t[j] = 0.0;
+    if (best >= 0) {
+        const RelModel &M = models[best];
+#pragma unroll
+        for (int j = 0; j < 9; j++) P.R[j] = M.R[j];
+#pragma unroll
+        for (int j = 0; j < 3; j++) P.t[j] = M.t[j];
+    }
+    const int i = blockIdx.x * kRelTile + t;
+    if (i < S) {
+        uint8_t flag = 0;
+        if (best >= 0) {
+            RelRays r;
+            rel_rays(job->cams, obs[i], r);
+            flag = sac_is_inlier(rel_score(P, r), job->threshold) ? 1 : 0;
+        }
+        flags[i] = flag;
+    }
+    if (blockIdx.x == 0 && t == 0) {
+        for (int j = 0; j < 9; j++) out->R[j] = P.R[j];
+        for (int j = 0; j < 3; j++) out->t[j] = P.t[j];
+        out->status = best >= 0 ? MCORB_REL_OK : MCORB_REL_NO_MODEL;
+        out->n_inliers = best >= 0 ? count[best] : 0;
+        out->best = best;
+        out->n_models = (wmodels[0] + wmodels[1]) + (wmodels[2] + wmodels[3]);
+        for (int j = 0; j < kRelSample; j++) out->sample[j] = best >= 0 ? models[best].sample[j] : -1;
+        for (int j = 0; j < 3; j++) out->pad[j] = 0;
+    }
+}
+
+void launch_rel_hypotheses(hipStream_t st, const RelArgs &a, int H)
+{
+    hipLaunchKernelGGL(k_rel_hypotheses, dim3((H + 63) / 64), dim3(64), 0, st, a.job, a.obs, a.models);
+}
+
+void launch_rel_score(hipStream_t st, const RelArgs &a, int S, int H)
+{
+    hipLaunchKernelGGL(k_rel_score, dim3((S + kRelTile - 1) / kRelTile, (H + kRelHypBlock - 1) / kRelHypBlock), dim3(kRelTile), 0, st, a.job,
+                       a.obs, a.models, a.count);
+}
+
+void launch_rel_pick(hipStream_t st, const RelArgs &a, int S)
+{
+    hipLaunchKernelGGL(k_rel_pick, dim3((S + kRelTile - 1) / kRelTile), dim3(kRelTile), 0, st, a.job, a.obs, a.models, a.count, a.out, a.flags);
+}
+
+}  // namespace mcorb
