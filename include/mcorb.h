@@ -1292,6 +1292,83 @@ int mcorb_rel_eval(int ncams, const mcorb_track_cam *cams, int n, const int32_t 
                    const double *uv2, const double *R, const double *t, double *score);
 
 /* ------------------------------------------------------------------------- */
+/* The rig pose between two frames from 3D-3D correspondences: the third       */
+/* estimator of FrontEnd::estimatePoseLF, PC_ALIGN (MCSlam/src/FrontEnd.cpp:   */
+/* 4421-4440), FrontEnd::poseFromPCAlignment (:4441-4530).  Its live code is   */
+/* OpenGV's point_cloud::optimize_nonlinear over all correspondences (mode 0); */
+/* what its SAC argument is for is commented out there: sac::Ransac<           */
+/* PointCloudSacProblem> (mode 1).  OpenGV is not in the tree: its distance    */
+/* and sample size are recalled; the draws, the solver (Horn's closed form)    */
+/* and the absence of the adaptive stop are stated.     */
+/* ------------------------------------------------------------------------- */
+#define MCORB_ALIGN_MAX_ITERATIONS 16384
+#define MCORB_ALIGN_SAMPLE 3
+#define MCORB_ALIGN_OK 0            /* there is an answer */
+#define MCORB_ALIGN_NO_OBS 1        /* no pairs: the identity, nothing ran */
+#define MCORB_ALIGN_NO_MODEL 2      /* mode 0: the fit is not valid; mode 1: no hypothesis had a model (fewer than 3 pairs, collinear
+                                       points): the identity, every flag 0, mean_error 0 */
+#define MCORB_ALIGN_MODE_ALL 0      /* the least-squares fit over all pairs: the reference's live code */
+#define MCORB_ALIGN_MODE_SAC 1      /* RANSAC on samples of three pairs: the reference's commented code */
+#define MCORB_ALIGN_USED_SAC 0      /* the answer is the winning hypothesis (also: there is no answer) */
+#define MCORB_ALIGN_USED_FIT 1      /* the answer is a least-squares fit: mode 0's, or mode 1's refit over the winner's inliers */
+/* threshold: mode 1's, on |p1 - (R p2 + t)| in the points' unit (the reference's is 0.2); inlier_dist: the reference's verdict on
+ * the same distance with the answer (0.1 there), both modes; seed: of the draws; max_iterations: mode 1's hypotheses, 1 ..
+ * MCORB_ALIGN_MAX_ITERATIONS (the reference's 100), all examined; mode: MCORB_ALIGN_MODE_*; refit: mode 1 -- non-zero: the answer is
+ * the least-squares fit over the winner's inliers at `threshold` where that fit is valid */
+typedef struct mcorb_align_params {
+    double threshold, inlier_dist;
+    uint64_t seed;
+    int32_t max_iterations, mode, refit, reserved;
+} mcorb_align_params;
+/* (R, t) = b1_T_b2 of the answer, R row-major: X_1 = R X_2 + t, the reference's T (:4509-4514); (sac_R, sac_t): mode 1's winning
+ * hypothesis (the identity in mode 0 and without one); mean_error: the mean of |p1 - (R p2 + t)| over all n pairs with the answer
+ * (a NaN is the default quiet NaN); status: MCORB_ALIGN_*; used: MCORB_ALIGN_USED_*; n_inliers: the pairs with distance <
+ * inlier_dist, what the reference returns; n_matches: n; sac_n_inliers: the winner's count at `threshold`; best_hypothesis (-1:
+ * none); sample: the winner's three pairs in draw order; n_models: the hypotheses that had a model */
+typedef struct mcorb_align_result {
+    double R[9], t[3], sac_R[9], sac_t[3], mean_error;
+    int32_t status, used, n_inliers, n_matches, sac_n_inliers, best_hypothesis, sample[MCORB_ALIGN_SAMPLE], n_models;
+} mcorb_align_result;
+/* The pose of a rig's second frame in its first from n pairs of triangulated points.  Pair i is pts2[i] (lf_cur->points_3D[m.
+ * trainIdx]) and either pts1[i] (lf_prev->points_3D[m.queryIdx]) or the point of the store's landmark lids1[i] (map->getLandmark(
+ * l_id)->pt3D, :4447-4455): exactly one of lids1 and pts1 is given; points are 3 doubles each.  All arithmetic is fp64, one IEEE
+ * operation per operator in the order written (csrc/mcorb_align.h), + - * /, comparisons and sqrt:
+ * - the distance of a pair at a pose: |p1 - (R p2 + t)|; an inlier iff distance < the limit, strictly; a NaN is no inlier.
+ * - align_fit over a set of pairs (stated; Horn's unit-quaternion absolute orientation): the centroids, then M = sum (p2 - c2)
+ *   (p1 - c1)^T, each sum in a fixed order -- member i in lane i mod 256, each lane in ascending i, the lanes folded per block of 64
+ *   with strides 32 .. 1 and the four blocks as (b0 + b1) + (b2 + b3); the eigenvector of the largest eigenvalue of Horn's
+ *   symmetric 4 x 4 matrix by six sweeps of cyclic Jacobi; R from that quaternion, t = c1 - R c2.  Not valid: fewer than 3
+ *   members, a number that is not finite, or l1 - l2 <= 1e-12 (l1 - l4) of the eigenvalues (collinear members).
+ * - mode 0: align_fit over all pairs.
+ * - mode 1: hypothesis h draws 3 distinct pairs by mcorb_lmap_relative_pose's walk on the draws j = 0 .. 2 (the splitmix64
+ *   finaliser of seed + 0x9E3779B97F4A7C15 (1 + 32 h + j)); its model is align_fit on them; the largest count over all n pairs at
+ *   `threshold` wins, a tie goes to the lowest hypothesis, a hypothesis without a model never wins; no adaptive stop.  With
+ *   refit the answer is align_fit over the winner's inliers, or the winner where that fit is not valid.
+ * - then the reference's verdict at inlier_dist with the answer: the flags, their count, the mean distance.
+ * A device store runs k_align_hypotheses, k_align_score, k_align_pick and k_align_fit (mode 0: k_align_fit alone) in one
+ * submission on its stream with one wait and reads lids1's points from its own landmark array on the device; a host-only store
+ * runs the same header serially: the results are equal bit for bit.  The store's landmarks are never written.  inlier (may be
+ * NULL): one flag per pair.  Refused before anything runs, the store unchanged: MCORB_E_ARG for a NULL, both or neither of lids1
+ * and pts1, n < 0, a lid that is not a slot with a point, a threshold or inlier_dist that is not finite and positive,
+ * max_iterations outside 1 .. MCORB_ALIGN_MAX_ITERATIONS in mode 1, an unknown mode; MCORB_E_STATE while a tracking call is
+ * pending. */
+int mcorb_lmap_align_pose(mcorb_lmap *m, int n, const int32_t *lids1, const double *pts1, const double *pts2,
+                          const mcorb_align_params *params, mcorb_align_result *res, uint8_t *inlier);
+/* a device store's last k_align_hypotheses (us[0]), k_align_score (us[1]), k_align_pick (us[2]) and k_align_fit (us[3]) launch,
+ * microseconds between HIP events, and the hypotheses of the last mode-1 launch; a call without pairs launches nothing and leaves
+ * them; mode 0 leaves us[0 .. 2] and the hypotheses and sets us[3] */
+int mcorb_lmap_last_align_timing(mcorb_lmap *m, float us[4], int *n_hyp);
+/* test hook: the counts of all hypotheses of the last mode-1 call that ran any, and whether each had a model; a device store
+ * copies them down from where k_align_score left them.  MCORB_E_CAP (with n_hyp set) when cap < n_hyp */
+int mcorb_lmap_last_align_counts(mcorb_lmap *m, int32_t *count, int32_t *valid, int cap, int *n_hyp);
+/* test hook, host: align_fit over the pairs i of (p1, p2: n x 3 doubles) with member[i] != 0 (member NULL: all) -> 1 with (R as
+ * 9, t as 3 doubles) = b1_T_b2, 0 when the fit is not valid (R, t are then what it computed), or a negative error.  gap (may be
+ * NULL): (l1 - l2) / (l1 - l4) of Horn's matrix */
+int mcorb_align_solve(int n, const double *p1, const double *p2, const uint8_t *member, double *R, double *t, double *gap);
+/* test hook, host: the distances of n pairs at the pose (R, t); a NaN is the default quiet NaN */
+int mcorb_align_eval(int n, const double *p1, const double *p2, const double *R, const double *t, double *dist);
+
+/* ------------------------------------------------------------------------- */
 /* Host stages exposed for the CPU test-suite (no device needed)              */
 /* ------------------------------------------------------------------------- */
 /* The engine's quad-tree selection, DistributeOctTree's equivalent (ORBextractor.cpp:554-778), run

@@ -1601,6 +1601,44 @@ class LocalMap:
         _lib.check(self.L.mcorb_lmap_last_relative_counts(self.h, count.ctypes.data, valid.ctypes.data, REL_MAX_ITERATIONS, C.byref(nh)))
         return count[:nh.value], valid[:nh.value].astype(bool)
 
+    # the rig pose between two frames from 3D-3D pairs (mcorb_lmap_align_pose)
+    def align_pose(self, pts2, pts1=None, lids1=None, mode="sac", threshold=0.2, inlier_dist=0.1, max_iterations=100, seed=0, refit=True):
+        """the pose b1_T_b2 of a rig's second frame in its first from pairs of triangulated points: FrontEnd::poseFromPCAlignment,
+        the PC_ALIGN estimator.  Pair i is pts2[i] of frame 2 and pts1[i] of frame 1, or the point of the store's landmark
+        lids1[i] (exactly one of the two).  mode "all": the least-squares fit over all pairs (the reference's live code); "sac":
+        max_iterations hypotheses of 3 pairs each (1 .. ALIGN_MAX_ITERATIONS), all examined, counted at `threshold` on |p1 - (R p2
+        + t)|, and with refit the least-squares fit over the winner's inliers (the reference's commented code takes the winner:
+        refit=False).  inlier_dist: the reference's verdict with the answer.  The defaults are the reference's values.  ->
+        AlignResult.  A device store runs k_align_hypotheses, k_align_score, k_align_pick and k_align_fit ("all": k_align_fit
+        alone) in one submission; a host-only store the same arithmetic serially, with the same bits.  The store's landmarks
+        are not written"""
+        pts2 = np.ascontiguousarray(pts2, np.float64).reshape(-1, 3)
+        n = len(pts2)
+        # (no pairs: one row of zeros each, so that "exactly one of pts1 and lids1" is still said by a pointer that is not NULL)
+        pts2 = pts2 if n else np.zeros((1, 3))
+        l, lp = self._opt(lids1 if n or lids1 is None else np.zeros(1, np.int32), np.int32, (max(n, 1),))
+        p, pp = self._opt(pts1 if n or pts1 is None else np.zeros((1, 3)), np.float64, (max(n, 1), 3))
+        par = _lib.AlignParams()
+        par.threshold, par.inlier_dist, par.seed = float(threshold), float(inlier_dist), int(seed) & 0xFFFFFFFFFFFFFFFF
+        par.max_iterations, par.refit = int(max_iterations), int(bool(refit))
+        par.mode = ALIGN_MODES[mode] if isinstance(mode, str) else int(mode)     # (a number goes through as it is, to be refused)
+        res, flags = _lib.AlignResultC(), np.zeros(max(n, 1), np.uint8)
+        _lib.check(self.L.mcorb_lmap_align_pose(self.h, n, lp, pp, pts2.ctypes.data, C.byref(par), C.byref(res), flags.ctypes.data))
+        return AlignResult(res, flags[:n])
+
+    def last_align_timing(self):
+        """((us of k_align_hypotheses, k_align_score, k_align_pick, k_align_fit), hypotheses) of the last align_pose() launches;
+        mode "all" sets the last of the four only; a device store"""
+        us, nh = (C.c_float * 4)(), C.c_int(0)
+        _lib.check(self.L.mcorb_lmap_last_align_timing(self.h, us, C.byref(nh)))
+        return tuple(us), nh.value
+
+    def last_align_counts(self):
+        """test hook: (counts, has a model) of all hypotheses of the last mode-"sac" align_pose() that ran any"""
+        count, valid, nh = np.zeros(ALIGN_MAX_ITERATIONS, np.int32), np.zeros(ALIGN_MAX_ITERATIONS, np.int32), C.c_int(0)
+        _lib.check(self.L.mcorb_lmap_last_align_counts(self.h, count.ctypes.data, valid.ctypes.data, ALIGN_MAX_ITERATIONS, C.byref(nh)))
+        return count[:nh.value], valid[:nh.value].astype(bool)
+
     def set_track_refine(self, inv_sigma2=None, max_iterations=25):
         """inv_sigma2 given: from now on every tracking call on the store -- track, track_rig_frame, the submit / wait pair,
         track_rig_frames -- also refines, per frame and in the same submission, the pose of the view's rig from the frame's
@@ -1672,6 +1710,60 @@ class RelResult:
 
 REL_OK, REL_NO_OBS, REL_NO_MODEL = 0, 1, 2
 REL_MAX_ITERATIONS, REL_SAMPLE = 16384, 17
+
+
+class AlignResult:
+    """what LocalMap.align_pose returns: R (3 x 3), t = b1_T_b2 of the answer (X_1 = R X_2 + t; the identity without one); status
+    (ALIGN_OK, ALIGN_NO_OBS, ALIGN_NO_MODEL); used (ALIGN_USED_SAC: the winning hypothesis, ALIGN_USED_FIT: a least-squares fit);
+    n_inliers and inliers, one bool per pair, at inlier_dist with the answer; mean_error, the mean distance over all pairs;
+    n_matches.  The hypotheses' own (mode "sac"): sac_R, sac_t, sac_n_inliers (at threshold), best_hypothesis (-1: none), sample
+    (the winner's three pairs in draw order), n_models"""
+
+    def __init__(self, res, flags):
+        self.R = np.array(res.R[:], np.float64).reshape(3, 3)
+        self.t = np.array(res.t[:], np.float64)
+        self.sac_R = np.array(res.sac_R[:], np.float64).reshape(3, 3)
+        self.sac_t = np.array(res.sac_t[:], np.float64)
+        self.mean_error = res.mean_error
+        self.status, self.used, self.n_inliers, self.n_matches = res.status, res.used, res.n_inliers, res.n_matches
+        self.sac_n_inliers, self.best_hypothesis, self.sample = res.sac_n_inliers, res.best_hypothesis, tuple(res.sample[:])
+        self.n_models = res.n_models
+        self.inliers = flags.astype(bool)
+
+
+ALIGN_OK, ALIGN_NO_OBS, ALIGN_NO_MODEL = 0, 1, 2
+ALIGN_MODE_ALL, ALIGN_MODE_SAC = 0, 1
+ALIGN_MODES = {"all": ALIGN_MODE_ALL, "sac": ALIGN_MODE_SAC}
+ALIGN_USED_SAC, ALIGN_USED_FIT = 0, 1
+ALIGN_MAX_ITERATIONS, ALIGN_SAMPLE = 16384, 3
+
+
+def align_solve(p1, p2, member=None, with_gap=False):
+    """test hook (host): the closed-form least-squares rigid fit over the pairs (p1[i], p2[i]) with member[i] (None: all) -> (R 3 x
+    3, t) = b1_T_b2, or None when the fit is not valid; with_gap: -> (that, (l1 - l2) / (l1 - l4) of Horn's matrix)"""
+    p1 = np.ascontiguousarray(p1, np.float64).reshape(-1, 3)
+    n = len(p1)
+    p2 = np.ascontiguousarray(p2, np.float64).reshape(n, 3)
+    mem = None if member is None else np.ascontiguousarray(member, np.uint8).reshape(n)
+    R, t, gap = np.zeros(9), np.zeros(3), C.c_double(0.0)
+    k = _lib.load().mcorb_align_solve(n, p1.ctypes.data if n else None, p2.ctypes.data if n else None,
+                                      None if mem is None else mem.ctypes.data, R.ctypes.data, t.ctypes.data, C.addressof(gap))
+    _lib.check(min(k, 0))
+    pose = (R.reshape(3, 3), t) if k else None
+    return (pose, gap.value) if with_gap else pose
+
+
+def align_eval(R, t, p1, p2):
+    """test hook (host): the distances |p1 - (R p2 + t)| (n) of the pairs at the pose (R, t)"""
+    p1 = np.ascontiguousarray(p1, np.float64).reshape(-1, 3)
+    n = len(p1)
+    p2 = np.ascontiguousarray(p2, np.float64).reshape(n, 3)
+    R = np.ascontiguousarray(R, np.float64).reshape(9)
+    t = np.ascontiguousarray(t, np.float64).reshape(3)
+    dist = np.zeros(max(n, 1))
+    _lib.check(_lib.load().mcorb_align_eval(n, p1.ctypes.data if n else None, p2.ctypes.data if n else None, R.ctypes.data, t.ctypes.data,
+                                            dist.ctypes.data))
+    return dist[:n]
 
 
 def rel_threshold(K00_02):

@@ -123,6 +123,18 @@ class RelResultC(C.Structure):
                 ("best_hypothesis", C.c_int32), ("sample", C.c_int32 * 17), ("n_models", C.c_int32)]
 
 
+class AlignParams(C.Structure):
+    _fields_ = [("threshold", C.c_double), ("inlier_dist", C.c_double), ("seed", C.c_uint64), ("max_iterations", C.c_int32),
+                ("mode", C.c_int32), ("refit", C.c_int32), ("reserved", C.c_int32)]
+
+
+class AlignResultC(C.Structure):
+    _fields_ = [("R", C.c_double * 9), ("t", C.c_double * 3), ("sac_R", C.c_double * 9), ("sac_t", C.c_double * 3),
+                ("mean_error", C.c_double), ("status", C.c_int32), ("used", C.c_int32), ("n_inliers", C.c_int32),
+                ("n_matches", C.c_int32), ("sac_n_inliers", C.c_int32), ("best_hypothesis", C.c_int32), ("sample", C.c_int32 * 3),
+                ("n_models", C.c_int32)]
+
+
 class SacResultC(C.Structure):
     _fields_ = [("R", C.c_double * 9), ("t", C.c_double * 3), ("sac_R", C.c_double * 9), ("sac_t", C.c_double * 3),
                 ("status", C.c_int32), ("used", C.c_int32), ("n_inliers", C.c_int32), ("n_matches", C.c_int32),
@@ -317,6 +329,11 @@ SIGNATURES = {
     "mcorb_rel_threshold": (C.c_double, [C.c_double]),
     "mcorb_rel_solve": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mcorb_rel_eval": (_i, [_i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mcorb_lmap_align_pose": (_i, [_vp, _i, _vp, _vp, _vp, C.POINTER(AlignParams), C.POINTER(AlignResultC), _vp]),
+    "mcorb_lmap_last_align_timing": (_i, [_vp, C.POINTER(_f), C.POINTER(_i)]),
+    "mcorb_lmap_last_align_counts": (_i, [_vp, _vp, _vp, _i, C.POINTER(_i)]),
+    "mcorb_align_solve": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mcorb_align_eval": (_i, [_i, _vp, _vp, _vp, _vp, _vp]),
     "mcorb_host_geometry": (_i, [C.POINTER(Params), _i, _i, _vp]),
     "mcorb_synth_rig_frame": (_i, [C.c_uint32, _i, _i, _i, _i, _vp, _i]),
 }

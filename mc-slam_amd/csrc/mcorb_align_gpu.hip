@@ -1,0 +1,282 @@
+// mcorb_align_gpu.hip -- the rig pose between two frames from 3D-3D pairs of mcorb_align.h on a device store (mcorb_align.cpp):
+// four launches on the store's stream in mode 1, one in mode 0, no workgroup waits on another.
+//   k_align_hypotheses  one lane per hypothesis: the three draws, Horn's closed form on the three pairs (the Jacobi pairs and the
+//                       4 x 4 indices are compile-time constants: N and V are registers); a model record per hypothesis
+//   k_align_score       H x n distances: a workgroup owns a tile of kAlignTile pairs, which each lane keeps in registers, and a
+//                       block of kAlignHypBlock hypotheses, whose models it reads at uniform addresses; per model a ballot and a
+//                       population count per wave into integer counts in LDS, then one integer atomicAdd per (workgroup,
+//                       hypothesis) into count[H].  The additions are integer: the result does not depend on their order
+//   k_align_pick        every workgroup finds the arg-max of count[H] for itself and writes the winner's flags at the threshold for
+//                       its tile of pairs into member[n]; workgroup 0 writes the winner's record, both to device memory
+//   k_align_fit         ONE workgroup of 256: the two fold-ordered passes over the members (mode 0: all pairs), lane 0 solves,
+//                       then the workgroup strides over the n pairs for the verdict's flags, count and mean distance and writes
+//                       the record to host-mapped memory.  One workgroup is deliberate: the sums are floating-point and their
+//                       order is part of the definition; a grid-wide reduction would need a wait between workgroups or an
+//                       atomic whose order the hardware picks
+// The arithmetic is the header's, so the host-only store gives the same bits.  No extraction job runs this and no benchmark leg
+// times it.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "mcorb_common.h"
+#include "mcorb_device.h"
+#include "mcorb_kernels.h"
+#include "mcorb_align.h"
+
+namespace mcorb {
+
+static_assert(kAlignTile == 4 * 64 && kAlignTile == kAlignLanes, "four waves, a lane of the fold each");
+static_assert(kAlignHypBlock <= kAlignTile, "a lane per hypothesis of the block adds its count");
+
+// the pairs as a lane reads them: frame 1's point is given or the store's landmark's
+struct AlignSrc {
+    const double *p1, *p2;
+    const int32_t *lids1;
+    const double *geom;
+    __device__ __forceinline__ void operator()(int i, double a[3], double b[3]) const
+    {
+        const double *p = p1 ? p1 + 3 * (size_t)i : geom + 6 * (size_t)lids1[i];
+        const double *q = p2 + 3 * (size_t)i;
+        a[0] = p[0], a[1] = p[1], a[2] = p[2];
+        b[0] = q[0], b[1] = q[1], b[2] = q[2];
+    }
+};
+
+__device__ __forceinline__ void align_load(PoseState &P, const double *R, const double *t)
+{
+#pragma unroll
+    for (int j = 0; j < 9; j++) P.R[j] = R[j];
+#pragma unroll
+    for (int j = 0; j < 3; j++) P.t[j] = t[j];
+}
+
+__global__ __launch_bounds__(64) void k_align_hypotheses(const AlignJob *__restrict__ job, AlignSrc src, AlignModel *__restrict__ models)
+{
+    const int h = blockIdx.x * 64 + threadIdx.x;
+    if (h >= job->H) return;
+    align_hypothesis(*job, h, src, models[h]);
+}
+
+__global__ __launch_bounds__(kAlignTile) void k_align_score(const AlignJob *__restrict__ job, AlignSrc src,
+                                                            const AlignModel *__restrict__ models, int32_t *__restrict__ count)
+{
+    __shared__ int32_t cnt[kAlignHypBlock];
+    const int t = threadIdx.x, lane = t & 63;
+    const int n = job->n, H = job->H;
+    const int i = blockIdx.x * kAlignTile + t;
+    const bool in = i < n;
+    const double threshold = job->threshold;
+    double p1[3], p2[3];
+    src(in ? i : 0, p1, p2);   // (n >= 1: a lane beyond the pairs scores pair 0 and counts nothing)
+    if (t < kAlignHypBlock) cnt[t] = 0;
+    __syncthreads();
+    const int h0 = blockIdx.y * kAlignHypBlock, h1 = min(H, h0 + kAlignHypBlock);
+    for (int h = h0; h < h1; h++) {
+        const AlignModel &M = models[h];   // (uniform over the workgroup)
+        if (!M.valid) continue;
+        PoseState P;
+        align_load(P, M.R, M.t);
+        const bool inl = in && sac_is_inlier(align_dist(P, p1, p2), threshold);
+        const unsigned long long mask = __ballot(inl);
+        if (lane == 0 && mask) atomicAdd(&cnt[h - h0], __popcll(mask));
+    }
+    __syncthreads();
+    if (t < h1 - h0 && cnt[t]) atomicAdd(&count[h0 + t], cnt[t]);
+}
+
+__global__ __launch_bounds__(kAlignTile) void k_align_pick(const AlignJob *__restrict__ job, AlignSrc src,
+                                                           const AlignModel *__restrict__ models, const int32_t *__restrict__ count,
+                                                           AlignPick *__restrict__ pick, uint8_t *__restrict__ member)
+{
+    __shared__ unsigned long long wkey[4];
+    __shared__ int32_t wmodels[4];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int n = job->n, H = job->H;
+    unsigned long long key = 0;
+    int32_t nm = 0;
+    for (int h = t; h < H; h += kAlignTile) {
+        const int32_t valid = models[h].valid;
+        const unsigned long long kh = rel_key(valid, count[h], h);
+        key = kh > key ? kh : key;
+        nm += valid;
+    }
+    for (int s = 32; s >= 1; s >>= 1) {
+        const unsigned long long other = __shfl_xor(key, s, 64);
+        key = other > key ? other : key;
+        nm += __shfl_xor(nm, s, 64);
+    }
+    if (lane == 0) {
+        wkey[wave] = key;
+        wmodels[wave] = nm;
+    }
+    __syncthreads();
+    key = wkey[0];
+    for (int w = 1; w < 4; w++) key = wkey[w] > key ? wkey[w] : key;
+    const int best = rel_key_hypothesis(key);   // (the same in every lane)
+    PoseState P;
+    align_identity(P);
+    if (best >= 0) align_load(P, models[best].R, models[best].t);
+    const int i = blockIdx.x * kAlignTile + t;
+    if (i < n) {
+        uint8_t flag = 0;
+        if (best >= 0) {
+            double p1[3], p2[3];
+            src(i, p1, p2);
+            flag = sac_is_inlier(align_dist(P, p1, p2), job->threshold) ? 1 : 0;
+        }
+        member[i] = flag;
+    }
+    if (blockIdx.x == 0 && t == 0) {
+        for (int j = 0; j < 9; j++) pick->R[j] = P.R[j];
+        for (int j = 0; j < 3; j++) pick->t[j] = P.t[j];
+        pick->best = best;
+        pick->count = best >= 0 ? count[best] : 0;
+        pick->n_models = (wmodels[0] + wmodels[1]) + (wmodels[2] + wmodels[3]);
+        for (int j = 0; j < kAlignSample; j++) pick->sample[j] = best >= 0 ? models[best].sample[j] : -1;
+    }
+}
+
+// the fold of the lanes' K sums: a wave's by shuffles with strides 32 .. 1 (lane 0 holds s[l] + s[l + stride] of pose_fold), the
+// four waves' through LDS as (b0 + b1) + (b2 + b3) -> the same bits in every lane.  part: [4][K] of LDS, free again on return
+template <int K>
+__device__ __forceinline__ void align_fold_wg(double s[K], double (*part)[kAlignSums2], double S[K])
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int stride = kAlignBlock / 2; stride >= 1; stride >>= 1)
+#pragma unroll
+        for (int k = 0; k < K; k++) s[k] = s[k] + __shfl_down(s[k], stride, 64);
+    if (lane == 0)
+#pragma unroll
+        for (int k = 0; k < K; k++) part[wave][k] = s[k];
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < K; k++) S[k] = (part[0][k] + part[1][k]) + (part[2][k] + part[3][k]);
+    __syncthreads();
+}
+
+__global__ __launch_bounds__(kAlignTile) void k_align_fit(const AlignJob *__restrict__ job, AlignSrc src, const AlignPick *pick,
+                                                          const uint8_t *member, AlignOut *out, uint8_t *flags)
+{
+    __shared__ double part[kAlignBlocks][kAlignSums2];
+    __shared__ int32_t wcnt[kAlignBlocks];
+    __shared__ double fitted[12];
+    __shared__ int32_t fit_ok;
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int n = job->n;
+    const bool all = job->mode == MCORB_ALIGN_MODE_ALL;
+    PoseState win, ans;
+    align_identity(win);
+    int best = -1, sac_count = 0, n_models = 0;
+    if (!all) {
+        align_load(win, pick->R, pick->t);
+        best = pick->best;
+        sac_count = pick->count;
+        n_models = pick->n_models;
+    }
+    ans = win;
+    bool have = best >= 0;
+    int used = MCORB_ALIGN_USED_SAC;
+    if (all || (have && job->refit)) {   // (uniform over the workgroup)
+        // pass 1: the coordinate sums and the members
+        double s[kAlignSums2], S[kAlignSums2], c1[3], c2[3];
+#pragma unroll
+        for (int k = 0; k < kAlignSums2; k++) s[k] = 0.0;
+        int mine = 0;
+        for (int i = t; i < n; i += kAlignTile) {
+            if (!all && !member[i]) continue;
+            double p1[3], p2[3];
+            src(i, p1, p2);
+            align_add1(p1, p2, s);
+            mine++;
+        }
+        for (int st = 32; st >= 1; st >>= 1) mine += __shfl_xor(mine, st, 64);
+        if (lane == 0) wcnt[wave] = mine;
+        align_fold_wg<kAlignSums1>(s, part, S);   // (its barriers cover wcnt)
+        const int cnt = (wcnt[0] + wcnt[1]) + (wcnt[2] + wcnt[3]);
+        align_centroids(S, cnt, c1, c2);
+        // pass 2: M
+#pragma unroll
+        for (int k = 0; k < kAlignSums2; k++) s[k] = 0.0;
+        for (int i = t; i < n; i += kAlignTile) {
+            if (!all && !member[i]) continue;
+            double p1[3], p2[3];
+            src(i, p1, p2);
+            align_add2(p1, p2, c1, c2, s);
+        }
+        align_fold_wg<kAlignSums2>(s, part, S);
+        if (t == 0) {
+            PoseState P;
+            const bool ok = align_from_sums(S, c1, c2, cnt, P, nullptr);
+#pragma unroll
+            for (int j = 0; j < 9; j++) fitted[j] = P.R[j];
+#pragma unroll
+            for (int j = 0; j < 3; j++) fitted[9 + j] = P.t[j];
+            fit_ok = ok ? 1 : 0;
+        }
+        __syncthreads();
+        if (fit_ok) {
+            align_load(ans, fitted, fitted + 9);
+            used = MCORB_ALIGN_USED_FIT;
+            have = true;
+        }
+    }
+    // the verdict: the flags, their count, the fold-ordered sum of the distances
+    double d[1] = {0.0}, D[1];
+    int inl = 0;
+    const double inlier_dist = job->inlier_dist;
+    for (int i = t; i < n; i += kAlignTile) {
+        uint8_t flag = 0;
+        if (have) {
+            double p1[3], p2[3];
+            src(i, p1, p2);
+            const double di = align_dist(ans, p1, p2);
+            flag = sac_is_inlier(di, inlier_dist) ? 1 : 0;
+            d[0] = d[0] + di;
+        }
+        flags[i] = flag;
+        inl += flag;
+    }
+    for (int st = 32; st >= 1; st >>= 1) inl += __shfl_xor(inl, st, 64);
+    if (lane == 0) wcnt[wave] = inl;
+    align_fold_wg<1>(d, part, D);
+    if (t == 0) {
+        for (int j = 0; j < 9; j++) out->R[j] = ans.R[j], out->sac_R[j] = win.R[j];
+        for (int j = 0; j < 3; j++) out->t[j] = ans.t[j], out->sac_t[j] = win.t[j];
+        out->mean_error = have ? pose_default_nan(D[0] / (double)n) : 0.0;
+        out->status = have ? MCORB_ALIGN_OK : MCORB_ALIGN_NO_MODEL;
+        out->used = used;
+        out->n_inliers = (wcnt[0] + wcnt[1]) + (wcnt[2] + wcnt[3]);
+        out->sac_n_inliers = sac_count;
+        out->best = best;
+        out->n_models = n_models;
+        for (int j = 0; j < kAlignSample; j++) out->sample[j] = all ? -1 : pick->sample[j];
+        out->pad = 0;
+    }
+}
+
+static AlignSrc src_of(const AlignArgs &a) { return AlignSrc{a.p1, a.p2, a.lids1, a.geom}; }
+
+void launch_align_hypotheses(hipStream_t st, const AlignArgs &a, int H)
+{
+    hipLaunchKernelGGL(k_align_hypotheses, dim3((H + 63) / 64), dim3(64), 0, st, a.job, src_of(a), a.models);
+}
+
+void launch_align_score(hipStream_t st, const AlignArgs &a, int n, int H)
+{
+    hipLaunchKernelGGL(k_align_score, dim3((n + kAlignTile - 1) / kAlignTile, (H + kAlignHypBlock - 1) / kAlignHypBlock), dim3(kAlignTile), 0,
+                       st, a.job, src_of(a), a.models, a.count);
+}
+
+void launch_align_pick(hipStream_t st, const AlignArgs &a, int n)
+{
+    hipLaunchKernelGGL(k_align_pick, dim3((n + kAlignTile - 1) / kAlignTile), dim3(kAlignTile), 0, st, a.job, src_of(a), a.models, a.count,
+                       a.pick, a.member);
+}
+
+void launch_align_fit(hipStream_t st, const AlignArgs &a)
+{
+    hipLaunchKernelGGL(k_align_fit, dim3(1), dim3(kAlignTile), 0, st, a.job, src_of(a), a.pick, a.member, a.out, a.flags);
+}
+
+}  // namespace mcorb

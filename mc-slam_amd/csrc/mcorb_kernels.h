@@ -1,10 +1,11 @@
 // mcorb_kernels.h -- launch wrappers of the gfx950 kernels (mcorb_kernels.hip, mcorb_select_gpu.hip, mcorb_handoff_gpu.hip,
 // mcorb_bow_gpu.hip, mcorb_lf_gpu.hip, mcorb_kfdb_gpu.hip, mcorb_lmap_gpu.hip, mcorb_mapping_gpu.hip, mcorb_landmark_gpu.hip,
-// mcorb_track_gpu.hip, mcorb_pose_gpu.hip, mcorb_sac_gpu.hip, mcorb_rel_gpu.hip).
+// mcorb_track_gpu.hip, mcorb_pose_gpu.hip, mcorb_sac_gpu.hip, mcorb_rel_gpu.hip, mcorb_align_gpu.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <vector>
 #include "../../include/mcorb.h"
+#include "mcorb_align.h"
 #include "mcorb_common.h"
 #include "mcorb_mapping_new.h"
 #include "mcorb_pose.h"
@@ -281,5 +282,29 @@ struct RelArgs {
 void launch_rel_hypotheses(hipStream_t st, const RelArgs &a, int H);
 void launch_rel_score(hipStream_t st, const RelArgs &a, int S, int H);
 void launch_rel_pick(hipStream_t st, const RelArgs &a, int S);
+
+// the pose between two frames from 3D-3D pairs (mcorb_align_gpu.hip).  job, p2 and p1 or lids1 (the n pairs; lids1: frame 1's
+// points are geom's, 6 doubles per slot) are device memory.  Mode 1: k_align_hypotheses -- one lane per hypothesis, models[H];
+// k_align_score -- a workgroup per (tile of kAlignTile pairs, block of kAlignHypBlock hypotheses), integer adds into count[H],
+// which the caller has zeroed on the stream; k_align_pick -- the winner into pick and its flags at the threshold into member[n],
+// both device memory; then k_align_fit, which mode 0 launches alone: one workgroup -- the refit over member (mode 0: the fit over
+// all pairs), the verdict's flags (host-mapped) and the record out (host-mapped)
+constexpr int kAlignTile = 256, kAlignHypBlock = 32;
+struct AlignArgs {
+    const AlignJob *job;
+    const double *p1, *p2;
+    const int32_t *lids1;
+    const double *geom;
+    AlignModel *models;
+    int32_t *count;
+    AlignPick *pick;
+    uint8_t *member;
+    AlignOut *out;
+    uint8_t *flags;
+};
+void launch_align_hypotheses(hipStream_t st, const AlignArgs &a, int H);
+void launch_align_score(hipStream_t st, const AlignArgs &a, int n, int H);
+void launch_align_pick(hipStream_t st, const AlignArgs &a, int n);
+void launch_align_fit(hipStream_t st, const AlignArgs &a);
 
 }  // namespace mcorb

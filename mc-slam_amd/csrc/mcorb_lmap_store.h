@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "mcorb_kfdb_store.h"
+#include "mcorb_align.h"
 #include "mcorb_mapping_new.h"
 #include "mcorb_pack.h"
 #include "mcorb_pose.h"
@@ -275,6 +276,33 @@ struct mcorb_lmap {
             return h_flags.grow(n, mcorb::kHostMapped);
         }
     } rel;
+
+    // the pose between two frames from 3D-3D pairs (mcorb_align.cpp), grow-only: the packed input (AlignLayout), the models and
+    // counts of the hypotheses, the winner and its members for the refit, and what the host reads: k_align_fit's record and the
+    // flags per pair, host-mapped
+    struct Align {
+        mcorb::Staged in;
+        mcorb::DevBuf<mcorb::AlignModel> d_models;
+        mcorb::DevBuf<int32_t> d_count;
+        mcorb::DevBuf<mcorb::AlignPick> d_pick;
+        mcorb::DevBuf<uint8_t> d_member;
+        mcorb::HostBuf<mcorb::AlignOut> h_out;
+        mcorb::HostBuf<uint8_t> h_flags;
+        mcorb::Spans<3> sac;                    // k_align_hypotheses, k_align_score, k_align_pick (mode 1)
+        mcorb::Spans<1> fit;                    // k_align_fit
+        int last_hyp = 0;                       // the hypotheses of the last mode-1 call that ran any (either kind of store)
+        std::vector<int32_t> host_count, host_valid;   // a host-only store's last counts, for mcorb_lmap_last_align_counts
+        int reserve(size_t bytes, size_t n, size_t H)
+        {
+            TRY(in.reserve(bytes));
+            TRY(d_models.grow(H));
+            TRY(d_count.grow(H));
+            TRY(d_pick.grow(1));
+            TRY(d_member.grow(n));
+            TRY(h_out.grow(1, mcorb::kHostMapped));
+            return h_flags.grow(n, mcorb::kHostMapped);
+        }
+    } align;
 };
 
 // the pose refinement behind a tracking call (mcorb_pose.cpp); the caller holds the store's lock and has set track_refine_params.

@@ -5,6 +5,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "mcorb_align.h"
 #include "mcorb_mapping.h"
 #include "mcorb_rel.h"
 #include "mcorb_sac.h"
@@ -41,6 +42,13 @@ struct RelLayout {
     Pack p;
     size_t job, obs;
     explicit RelLayout(size_t n) : job(p.add<RelJob>(1)), obs(p.add<RelObs>(n)) {}
+};
+
+// mcorb_lmap_align_pose: the AlignJob, frame 1's points or their landmark ids (lids), frame 2's points
+struct AlignLayout {
+    Pack p;
+    size_t job, p1, p2;
+    AlignLayout(size_t n, bool lids) : job(p.add<AlignJob>(1)), p1(lids ? p.add<int32_t>(n) : p.add<double>(3 * n)), p2(p.add<double>(3 * n)) {}
 };
 
 // a tracking submission of nf frames: a TrItem and a view per frame, every frame's candidates, then -- host arrays only -- the

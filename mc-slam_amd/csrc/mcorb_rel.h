@@ -65,13 +65,15 @@ MCORB_POSE_HD uint64_t rel_draw(uint64_t seed, int h, int j)
 
 // The sample of hypothesis h: 17 distinct members of 0 .. S - 1 by a partial Fisher-Yates walk, without rejection.  Draw j mod
 // (S - j) is an index into the members not yet picked: the earlier picks are walked in ascending order and the index steps over
-// each that is <= it.  sample: in draw order.  false: S < 17 (every member -1)
-MCORB_POSE_HD bool rel_sample(uint64_t seed, int h, int S, int32_t sample[kRelSample])
+// each that is <= it.  sample: in draw order.  false: S < 17 (every member -1).  rel_sample_k: the same walk on K draws, which
+// mcorb_align.h takes three of
+template <int K>
+MCORB_POSE_HD bool rel_sample_k(uint64_t seed, int h, int S, int32_t sample[K])
 {
-    int32_t sorted[kRelSample];
-    for (int j = 0; j < kRelSample; j++) sample[j] = -1;
-    if (S < kRelSample) return false;
-    for (int j = 0; j < kRelSample; j++) {
+    int32_t sorted[K];
+    for (int j = 0; j < K; j++) sample[j] = -1;
+    if (S < K) return false;
+    for (int j = 0; j < K; j++) {
         int32_t idx = (int32_t)(rel_draw(seed, h, j) % (uint64_t)(S - j));
         for (int k = 0; k < j; k++) idx += sorted[k] <= idx ? 1 : 0;
         sample[j] = idx;
@@ -83,6 +85,10 @@ MCORB_POSE_HD bool rel_sample(uint64_t seed, int h, int S, int32_t sample[kRelSa
         sorted[p] = idx;
     }
     return true;
+}
+MCORB_POSE_HD bool rel_sample(uint64_t seed, int h, int S, int32_t sample[kRelSample])
+{
+    return rel_sample_k<kRelSample>(seed, h, S, sample);
 }
 
 MCORB_POSE_HD void rel_cross(const double a[3], const double b[3], double c[3])
