@@ -821,6 +821,98 @@ int mcorb_dev_map_refine_selftest(int device, int n, const double *X0, const int
                                   int32_t *solves, float *cosp, double *vals);
 
 /* ------------------------------------------------------------------------- */
+/* Map initialization: FrontEnd::initialization (MCSlam/src/FrontEnd.cpp       */
+/* :2481-2860) from the pose between the first two rig frames to the first     */
+/* landmarks, lines :2633-2839.  The MIN_FEATS and first-frame arms, the        */
+/* choice of lf_prev, the matchers and estimators (mcorb_lmap_ransac_pose,      */
+/* _relative_pose, _align_pose), the one-camera findEssentialMat / recoverPose  */
+/* arm, insertKeyFrame, numTrackedLMs, uv_ref, the trial counter and the 4x4    */
+/* inverses stay with the caller.                                              */
+/* ------------------------------------------------------------------------- */
+#define MCORB_INIT_MAX_MATCHES 16384
+#define MCORB_INIT_DONE 0       /* initialised: the landmarks are stored */
+#define MCORB_INIT_BASELINE 1   /* norm(t) <= min_baseline: nothing ran */
+#define MCORB_INIT_PARALLAX 2   /* parllaxVec empty or its median >= 0.99998 (a NaN included) */
+#define MCORB_INIT_FEW 3        /* num_triangulated <= 50 */
+/* the outputs of mcorb_lmap_initialize.  The per-match arrays have cap_matches entries (3 x cap_matches for pt3d and normal). */
+typedef struct mcorb_init_result {
+    int32_t cap_matches;             /* in */
+    int32_t status;                  /* out: MCORB_INIT_* */
+    uint8_t *inliers;                /* in: the estimator's flags, inter_matches' then mono_matches' (:2637); out: as the loop
+                                      * leaves them -- true exactly for verdict 0 */
+    uint8_t *verdict;                /* 0 a landmark candidate, 3 behind a camera, 4 reprojection error (chi-square), 5 cos >=
+                                      * 0.99998 or NaN (NOT an inlier here: :2752), 9 the flag was clear on entry */
+    int32_t *new_lid;                /* the new landmark's id, or -1 (always -1 unless status is MCORB_INIT_DONE) */
+    double *pt3d;                    /* verdict 0: the point -- the stored (scaled) one when status is DONE; else zero */
+    double *normal;                  /* of the stored landmark (zero where new_lid is -1) */
+    double *dist2, *cos_parallax;    /* for verdicts 0 and 5, else zero; a NaN is the default quiet NaN */
+    double parallax, median_scene_depth;   /* out: :2761-2772, both 0.0 unless parllaxVec and depthVec are both non-empty */
+    double t_out[3];                 /* out: t, or t * (1.0 / median_scene_depth) when scaled */
+    int32_t n_matches, n_initial_inliers, n_parallax, n_triangulated;   /* out: n, the flags set on entry, parllaxVec.size(),
+                                                                         * num_triangulated = depthVec.size() */
+    int32_t scaled, next_lid;        /* out: 1 when pose and points were scaled; the first id not given out */
+} mcorb_init_result;
+/* prev / lids_prev: lf_prev with proj = rows of prev_T_ref * lf_prev->pose.inv() (:2640-2648) and its centre_w; cur / lids_cur:
+ * currentFrame with proj = rows of cur_T_ref * T.inv() (:2649-2656); cur->centre_w and both twc are not read.  R, t: T's rotation
+ * (row-major) and translation.  cam_centre_body: ncams x 3, per camera the translation column of cur_T_ref.inv().  match_query /
+ * match_train / n: inter_matches followed by mono_matches (:2636; queryIdx into prev's features, trainIdx into cur's), n <=
+ * MCORB_INIT_MAX_MATCHES.  K, inv_sigma2, nlevels, next_lid as for mcorb_lmap_triangulate_neighbours.  min_baseline: the caller's
+ * kf_translation_threshold * 0.5.
+ *   1. (:2633) sqrt(t0 * t0 + t1 * t1 + t2 * t2) > min_baseline, or status BASELINE: nothing runs, every output but status,
+ *      n_matches, t_out (= t) and next_lid is left alone.
+ *   2. (:2665-2757) Per match with its flag set: the views of both features (get3D_2DCorrs: prev's first, cameras ascending), the
+ *      DLT of triangulate_neighbours on them -- there is no epipolar gate here --, per view in order p.z < 0 (verdict 3) and err *
+ *      inv_sigma2[octave] > 5.991 (verdict 4), which clear the flag at the first such view (a NaN z is not behind, a NaN err
+ *      passes); otherwise cos = dot / (dist1 * dist2) joins parllaxVec, and cos < 0.99998 alone -- no lower bound -- makes the
+ *      match a landmark candidate (verdict 0) whose dist2 joins depthVec; otherwise, a NaN included, verdict 5 and the flag is
+ *      cleared.  A match whose flag is clear on entry is verdict 9 and untouched.
+ *   3. (:2761-2772) With both vectors non-empty, parallax and median_scene_depth are element size / 2 of the sorted vectors.
+ *      std::sort over a NaN is undefined in the reference; stated: the order is that of the usual monotone 64-bit key of a
+ *      double's bits after the default-NaN rule, so a NaN sorts after +inf.
+ *   4. (:2776, :2783) Initialised iff parllaxVec is non-empty, parallax < 0.99998 and num_triangulated > 50; otherwise status
+ *      PARALLAX or FEW: nothing is stored, both lIds arrays stay as they were, the outputs are as the loop left them.
+ *   5. (:2785-2790, :2816-2818) When ncams == 1 || n < 50 -- the second arm cannot hold together with num_triangulated > 50 and
+ *      is restated as written --: s = 1.0 / median_scene_depth, t_out = t * s and every accepted point is X * s (cv::MatExpr's
+ *      division by a scalar).
+ *   6. (:2807-2832) The accepted matches in match order take ids next_lid, next_lid + 1, ..; lids_prev[q] and lids_cur[t] are
+ *      set in that order with no "already assigned" test, so a later match overwrites.  Slot id takes the (scaled) point, the
+ *      normal of Landmark(pt, lf_prev, ..) then addLfFrame(currentFrame, ..) on that point -- prev's views with prev->centre_w,
+ *      cur's views with centres computed here as the translation column of [R | t_out] * cur_T_ref.inv(), per row ((R_i0 c0 +
+ *      R_i1 c1) + R_i2 c2) + t_out_i -- and n_rays; flags: point and normal set, no descriptor yet.  The observation lists stay
+ *      the caller's (mcorb_lmap_observe with MCORB_OBS_RECORD for both frames), as after mcorb_lmap_triangulate_neighbours.
+ * All arithmetic is fp64 (float where the reference has float) with separate multiplies and adds.  A device store runs
+ * k_init_triangulate, k_init_select and k_init_put in one submission with one wait; a host-only store runs the same header
+ * serially; the results are equal bit for bit.
+ * Refused before anything runs, the store and both lIds arrays untouched: MCORB_E_ARG for what mcorb_lmap_triangulate_neighbours
+ * refuses (a NULL, a frame with another camera count, an index outside a frame or its keypoints, an octave outside [0, nlevels),
+ * a matched feature without a view, a match of more than MCORB_MAX_CAMS views, an id outside [-1, max_landmarks)) and for n >
+ * MCORB_INIT_MAX_MATCHES; MCORB_E_CAP (n_matches set) for cap_matches < n or when next_lid + the number of flags set on entry --
+ * the most ids the call can give out -- exceeds max_landmarks; MCORB_E_STATE while a tracking call is pending. */
+int mcorb_lmap_initialize(mcorb_lmap *m, const mcorb_map_frame *prev, int32_t *lids_prev, const mcorb_map_frame *cur, int32_t *lids_cur,
+                          const double R[9], const double t[3], const double *cam_centre_body, const int32_t *match_query,
+                          const int32_t *match_train, int n, const double *K, const float *inv_sigma2, int nlevels, int32_t next_lid,
+                          double min_baseline, mcorb_init_result *out);
+/* a device store's last k_init_triangulate launches (us[0], both instances), k_init_select (us[1]) and k_init_put (us[2]),
+ * microseconds between HIP events, and the matches that were launched (may be NULL); a call that ends with BASELINE launches
+ * nothing and leaves them */
+int mcorb_lmap_last_initialize_timing(mcorb_lmap *m, float us[3], int *n_launched);
+/* test hooks: everything of mcorb_lmap_initialize but the triangulation and the store, for n caller-given cases that stand for
+ * the n matches of one call, on the host and in one submission of k_init_select and k_init_put on the device.  Views as for
+ * mcorb_host_map_gates, but centre is centre_w for a view of prev and the camera's cam_centre_body for a view of cur; X 3 doubles
+ * per case.  inliers: in and out.  verdict / n_rays / lid_offset: n entries (lid_offset: the id an accepted case takes, counted
+ * from 0, or -1); vals: 8 per case (pt3d, normal, dist2, cos).  res: every scalar of mcorb_init_result (its arrays are not
+ * touched; next_lid counts from 0). */
+int mcorb_host_init_cases(int n, const double *X, const int32_t *nv1, const int32_t *nv, const double *P, const double *K,
+                          const double *centre, const float *kps, const int32_t *octave, const float *inv_sigma2, int nlevels,
+                          int ncams, const double R[9], const double t[3], double min_baseline, uint8_t *inliers, int32_t *verdict,
+                          int32_t *n_rays, int32_t *lid_offset, double *vals, mcorb_init_result *res);
+int mcorb_dev_init_cases_selftest(int device, int n, const double *X, const int32_t *nv1, const int32_t *nv, const double *P,
+                                  const double *K, const double *centre, const float *kps, const int32_t *octave,
+                                  const float *inv_sigma2, int nlevels, int ncams, const double R[9], const double t[3],
+                                  double min_baseline, uint8_t *inliers, int32_t *verdict, int32_t *n_rays, int32_t *lid_offset,
+                                  double *vals, mcorb_init_result *res);
+
+/* ------------------------------------------------------------------------- */
 /* Landmarks: the local map kept up to date as keyframes are inserted --      */
 /* Landmark::addLfFrame with updateNormal(frame, featInd)                     */
 /* (MCSlam/src/GlobalMap.cpp:24-74, constructor :6-14; FrontEnd.cpp:6326-6335, */

@@ -16,8 +16,8 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import (E_ARG, E_CAP, E_EMPTY, E_HIP, E_NODEVICE, E_OVERFLOW, E_SIZE, E_STATE, KP_DTYPE, OBS_RECORD, OBS_UPDATE, OK,
-                   ORIENT_IC_ANGLE, ORIENT_NONE, McorbError, Params, default_params)
+from ._lib import (E_ARG, E_CAP, E_EMPTY, E_HIP, E_NODEVICE, E_OVERFLOW, E_SIZE, E_STATE, INIT_BASELINE, INIT_DONE, INIT_FEW,
+                   INIT_MAX_MATCHES, INIT_PARALLAX, KP_DTYPE, OBS_RECORD, OBS_UPDATE, OK, ORIENT_IC_ANGLE, ORIENT_NONE, McorbError, Params, default_params)
 from .synth import synth_rig_frame, synth_rig_frame_numpy
 
 TH_HIGH = 100   # ORBextractor.h:26
@@ -1051,6 +1051,23 @@ class NewLandmarksResult:
         self.__dict__.update(kw)
 
 
+class InitResult:
+    """what LocalMap.initialize and init_cases return.  status (INIT_DONE, INIT_BASELINE, INIT_PARALLAX, INIT_FEW); per match:
+    inliers (as the loop leaves them: true exactly for verdict 0), verdict (0 a landmark candidate, 3 behind a camera, 4
+    chi-square, 5 cos >= 0.99998 or NaN, 9 the flag was clear on entry), new_lid (-1: none), pt3d (the stored, scaled point when
+    status is INIT_DONE), normal, dist2, cos_parallax; parallax and median_scene_depth (the two medians), t_out, scaled,
+    n_initial_inliers, n_parallax, n_triangulated, next_lid; lids_prev and lids_cur as the call leaves them"""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+def _init_scalars(o):
+    return dict(status=o.status, parallax=o.parallax, median_scene_depth=o.median_scene_depth, t_out=np.array(o.t_out[:]),
+                n_matches=o.n_matches, n_initial_inliers=o.n_initial_inliers, n_parallax=o.n_parallax,
+                n_triangulated=o.n_triangulated, scaled=bool(o.scaled), next_lid=o.next_lid)
+
+
 class LocalMap:
     """FrontEnd::searchLocalMap2 (MCSlam/src/FrontEnd.cpp:4901-5223) up to the camera-filtered matches (mcorb_lmap): a store of
     landmarks (slot = lId: pt3D, normal, the latest observation's descriptor and mono flag) and the search of a frame held in a
@@ -1218,6 +1235,54 @@ class LocalMap:
                                   cost_final=cut("cost_final"), depth_vec=r["depth_vec"][:o.n_depth].copy(), avg_depth=o.avg_depth,
                                   n_rays_hist=np.array(o.n_rays_hist[:], np.int32), n_by_verdict=np.array(o.n_by_verdict[:], np.int32),
                                   n_triangulated=o.n_triangulated, next_lid=o.next_lid, lids_cur=lc, lids_prev=lp)
+
+    def initialize(self, prev, lids_prev, cur, lids_cur, R, t, cam_centre_body, matches, inliers, K_mats, inv_sigma2, next_lid,
+                   min_baseline, cap=None):
+        """FrontEnd::initialization from the pose between the first two rig frames to the first landmarks (FrontEnd.cpp:2633-2839)
+        -> InitResult; with status INIT_DONE the landmarks' points, normals and ray counts are stored in their slots.  prev / cur:
+        map_frame(...) of lf_prev (proj = prev_T_ref * lf_prev->pose.inv(), its centre_w) and of the current frame (proj =
+        cur_T_ref * T.inv(); its centre_w and both twc are not read); lids_prev / lids_cur: their lIds (copied: the result holds
+        the updated arrays); R, t: T; cam_centre_body: per camera the translation column of cur_T_ref.inv(); matches: an n x 2
+        array (queryIdx into prev, trainIdx into cur), inter_matches then mono_matches; inliers: the estimator's flags in that
+        order; min_baseline: kf_translation_threshold * 0.5; cap: the per-match output size, by default n.  The ids are refused
+        (E_CAP, before anything runs) when next_lid + the number of flags set on entry exceeds max_landmarks: the most ids the
+        call can give out, not the number it does give out"""
+        nc = cur.struct.ncams
+        lp, lc = np.array(lids_prev, np.int32).reshape(-1), np.array(lids_cur, np.int32).reshape(-1)
+        assert len(lc) == cur.struct.nfeat and len(lp) == prev.struct.nfeat
+        self.init_lids = lp, lc   # (what the call reads and writes: a refused call leaves them as they came in)
+        ms = np.asarray(matches, np.int32).reshape(-1, 2)
+        mq, mt = np.ascontiguousarray(ms[:, 0]), np.ascontiguousarray(ms[:, 1])
+        total = len(ms)
+        cap = total if cap is None else cap
+        Kc = np.ascontiguousarray(K_mats, np.float64).reshape(nc, 9)
+        sig = np.ascontiguousarray(inv_sigma2, np.float32).reshape(-1)
+        Rr, tt = np.ascontiguousarray(R, np.float64).reshape(9), np.ascontiguousarray(t, np.float64).reshape(3)
+        cb = np.ascontiguousarray(cam_centre_body, np.float64).reshape(nc, 3)
+        n1, n3 = max(cap, total, 1), 3 * max(cap, total, 1)
+        r = dict(inliers=np.zeros(n1, np.uint8), verdict=np.zeros(n1, np.uint8), new_lid=np.full(n1, -1, np.int32), pt3d=np.zeros(n3),
+                 normal=np.zeros(n3), dist2=np.zeros(n1), cos_parallax=np.zeros(n1))
+        fl = np.asarray(inliers).reshape(-1) != 0
+        assert len(fl) == total
+        r["inliers"][:total] = fl
+        o = self.init_out = _lib.InitResultC()
+        o.cap_matches = cap
+        for k, a in r.items():
+            setattr(o, k, a.ctypes.data)
+        _lib.check(self.L.mcorb_lmap_initialize(self.h, C.byref(prev.struct), lp.ctypes.data, C.byref(cur.struct), lc.ctypes.data,
+                                                Rr.ctypes.data, tt.ctypes.data, cb.ctypes.data, mq.ctypes.data, mt.ctypes.data, total,
+                                                Kc.ctypes.data, sig.ctypes.data, len(sig), int(next_lid), float(min_baseline), C.byref(o)))
+        cut = lambda k, w=1: r[k][:w * total].copy()
+        return InitResult(inliers=r["inliers"][:total].astype(bool), verdict=cut("verdict"), new_lid=cut("new_lid"),
+                          pt3d=cut("pt3d", 3).reshape(-1, 3), normal=cut("normal", 3).reshape(-1, 3), dist2=cut("dist2"),
+                          cos_parallax=cut("cos_parallax"), lids_prev=lp, lids_cur=lc, **_init_scalars(o))
+
+    def last_initialize_timing(self):
+        """(microseconds of the last k_init_triangulate launches, of k_init_select, of k_init_put, matches launched); a device store"""
+        us = (C.c_float * 3)()
+        n = C.c_int()
+        _lib.check(self.L.mcorb_lmap_last_initialize_timing(self.h, us, C.byref(n)))
+        return us[0], us[1], us[2], n.value
 
     def last_triangulate_new_timing(self):
         """(microseconds of the last k_map_refine_new launches, matches launched); a device store"""
@@ -1968,6 +2033,35 @@ def map_gates(X, nv1, nv, P, K, centre, kps, octave, F, inv_sigma2, device=None)
     L = _lib.load()
     _lib.check(L.mcorb_host_map_gates(*args) if device is None else L.mcorb_dev_map_gates_selftest(device, *args))
     return verdict[:n], rays[:n], vals[:n, 0].copy(), vals[:n, 1].copy(), vals[:n, 2:].copy()
+
+
+def init_cases(X, nv1, nv, P, K, centre, kps, octave, inv_sigma2, ncams, R, t, min_baseline, inliers, device=None):
+    """the test hooks mcorb_host_init_cases (device None) / mcorb_dev_init_cases_selftest: everything of LocalMap.initialize but
+    the triangulation and the store, the n cases standing for the n matches of one call -> InitResult (new_lid counts from 0).
+    Views back to back as for map_gates, but centre is centre_w for a view of prev and cam_centre_body for a view of cur"""
+    X = np.ascontiguousarray(X, np.float64).reshape(-1, 3)
+    n = len(X)
+    nv1, nv = np.ascontiguousarray(nv1, np.int32).reshape(-1), np.ascontiguousarray(nv, np.int32).reshape(-1)
+    P, K = np.ascontiguousarray(P, np.float64).reshape(-1, 12), np.ascontiguousarray(K, np.float64).reshape(-1, 9)
+    centre, kps = np.ascontiguousarray(centre, np.float64).reshape(-1, 3), np.ascontiguousarray(kps, np.float32).reshape(-1, 2)
+    octave = np.ascontiguousarray(octave, np.int32).reshape(-1)
+    sig = np.ascontiguousarray(inv_sigma2, np.float32).reshape(-1)
+    Rr, tt = np.ascontiguousarray(R, np.float64).reshape(9), np.ascontiguousarray(t, np.float64).reshape(3)
+    fl = np.ascontiguousarray(np.asarray(inliers).reshape(-1) != 0, np.uint8)
+    V = int(nv.sum()) if len(nv) == n else -1
+    if not (len(nv1) == len(fl) == n and len(P) == len(K) == len(centre) == len(kps) == len(octave) == V):
+        raise ValueError("init_cases: array lengths do not fit the view counts")
+    m = max(n, 1)
+    verdict, rays, off, vals = np.zeros(m, np.int32), np.zeros(m, np.int32), np.full(m, -1, np.int32), np.zeros((m, 8))
+    o = _lib.InitResultC()
+    args = (n, X.ctypes.data, nv1.ctypes.data, nv.ctypes.data, P.ctypes.data, K.ctypes.data, centre.ctypes.data, kps.ctypes.data,
+            octave.ctypes.data, sig.ctypes.data, len(sig), int(ncams), Rr.ctypes.data, tt.ctypes.data, float(min_baseline), fl.ctypes.data,
+            verdict.ctypes.data, rays.ctypes.data, off.ctypes.data, vals.ctypes.data, C.byref(o))
+    L = _lib.load()
+    _lib.check(L.mcorb_host_init_cases(*args) if device is None else L.mcorb_dev_init_cases_selftest(device, *args))
+    return InitResult(inliers=fl[:n].astype(bool), verdict=verdict[:n].astype(np.uint8), new_lid=off[:n], n_rays=rays[:n],
+                      pt3d=vals[:n, 0:3].copy(), normal=vals[:n, 3:6].copy(), dist2=vals[:n, 6].copy(), cos_parallax=vals[:n, 7].copy(),
+                      **_init_scalars(o))
 
 
 def map_refine(X0, nv1, nv, P, K, centre, kps, octave, twc_cur, twc_prev, inv_sigma2, device=None):

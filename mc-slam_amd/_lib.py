@@ -21,6 +21,8 @@ MAX_LEVELS, MAX_CAMS = 16, 16
 TRACK_KNN, TRACK_TILE = 10, 1024   # MCORB_TRACK_KNN, MCORB_TRACK_TILE
 TRACK_MAX_FRAMES = 32               # MCORB_TRACK_MAX_FRAMES
 POSE_LANES = 256                    # MCORB_POSE_LANES
+INIT_MAX_MATCHES = 16384           # MCORB_INIT_MAX_MATCHES
+INIT_DONE, INIT_BASELINE, INIT_PARALLAX, INIT_FEW = 0, 1, 2, 3   # MCORB_INIT_*
 POSE_NO_OBS, POSE_NO_STEP, POSE_CONVERGED, POSE_MAX_ITER = 0, 1, 2, 3   # MCORB_POSE_*
 
 KP_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"),
@@ -71,6 +73,14 @@ class MapNewOut(C.Structure):
                 ("depth_vec", C.c_void_p), ("avg_depth", C.c_double), ("n_rays_hist", C.c_int32 * MAX_CAMS),
                 ("n_by_verdict", C.c_int32 * 9), ("n_matches", C.c_int32), ("n_depth", C.c_int32), ("n_triangulated", C.c_int32),
                 ("next_lid", C.c_int32)]
+
+
+class InitResultC(C.Structure):
+    _fields_ = [("cap_matches", C.c_int32), ("status", C.c_int32), ("inliers", C.c_void_p), ("verdict", C.c_void_p),
+                ("new_lid", C.c_void_p), ("pt3d", C.c_void_p), ("normal", C.c_void_p), ("dist2", C.c_void_p),
+                ("cos_parallax", C.c_void_p), ("parallax", C.c_double), ("median_scene_depth", C.c_double), ("t_out", C.c_double * 3),
+                ("n_matches", C.c_int32), ("n_initial_inliers", C.c_int32), ("n_parallax", C.c_int32), ("n_triangulated", C.c_int32),
+                ("scaled", C.c_int32), ("next_lid", C.c_int32)]
 
 
 class ObsFrame(C.Structure):
@@ -288,6 +298,13 @@ SIGNATURES = {
     "mcorb_lmap_last_triangulate_new_timing": (_i, [_vp, C.POINTER(_f), _ip]),
     "mcorb_host_map_refine": (_i, [_i] + [_vp] * 11 + [_i] + [_vp] * 5),
     "mcorb_dev_map_refine_selftest": (_i, [_i, _i] + [_vp] * 11 + [_i] + [_vp] * 5),
+    "mcorb_lmap_initialize": (_i, [_vp, C.POINTER(MapFrame), _vp, C.POINTER(MapFrame), _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i,
+                                   C.c_int32, C.c_double, C.POINTER(InitResultC)]),
+    "mcorb_lmap_last_initialize_timing": (_i, [_vp, C.POINTER(_f), _ip]),
+    "mcorb_host_init_cases": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, C.c_double, _vp, _vp, _vp, _vp, _vp,
+                                   C.POINTER(InitResultC)]),
+    "mcorb_dev_init_cases_selftest": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, C.c_double, _vp, _vp, _vp,
+                                           _vp, _vp, C.POINTER(InitResultC)]),
     "mcorb_host_map_gates": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
     "mcorb_dev_map_gates_selftest": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
     "mcorb_lmap_set_rays": (_i, [_vp, _vp, _i, _vp]),

@@ -7,6 +7,7 @@
 #include "../../include/mcorb.h"
 #include "mcorb_align.h"
 #include "mcorb_common.h"
+#include "mcorb_init.h"
 #include "mcorb_mapping_new.h"
 #include "mcorb_pose.h"
 #include "mcorb_rel.h"
@@ -306,5 +307,32 @@ void launch_align_hypotheses(hipStream_t st, const AlignArgs &a, int H);
 void launch_align_score(hipStream_t st, const AlignArgs &a, int n, int H);
 void launch_align_pick(hipStream_t st, const AlignArgs &a, int n);
 void launch_align_fit(hipStream_t st, const AlignArgs &a);
+
+// map initialization (mcorb_init_gpu.hip, mcorb_init.h).  k_init_triangulate: k_map_triangulate's blocks and two instances over
+// the matches whose flag is set, one MapOut to a.out[match]; k_init_select: one workgroup -- the sizes and medians of parllaxVec
+// and depthVec into *sel, every match's id offset (the accepted matches before it) into offset, keys: 2 * n words of scratch;
+// k_init_put: one lane per match -- the verdict and the scale from *sel, the stored point, normal and n_rays of an accepted match
+// into slot job.next_lid + offset of geom / nrays, every match's record into h_rec and the call's record into *h_call (both
+// host-mapped).  The views of a match come from the packed block (a, query, train) or, for the self-test, from cases
+struct InitPutArgs {
+    InitJob job;
+    MapArgs a;
+    const int32_t *query, *train;
+    InitGateCases cases;
+    const MapOut *rec;
+    const uint8_t *flags;
+    const int32_t *offset;
+    const InitSel *sel;
+    MapOut *h_rec;
+    InitCall *h_call;
+    double *geom;
+    int32_t *nrays;
+};
+constexpr int kInitSelectT = 1024, kInitPutT = 256;
+void launch_init_triangulate(hipStream_t st, const MapArgs &a, int nblocks_small, int nblocks_any);
+void launch_init_select(hipStream_t st, const MapOut *rec, const uint8_t *flags, int n, uint64_t *keys, int32_t *offset, InitSel *sel);
+void launch_init_put(hipStream_t st, const InitPutArgs &p, bool from_cases);
+// init_after of n caller-given cases (mcorb_dev_init_cases_selftest); every pointer of c is device memory
+void launch_init_gates(hipStream_t st, const InitGateCases &c, int n, MapOut *out);
 
 }  // namespace mcorb

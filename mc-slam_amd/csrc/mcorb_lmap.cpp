@@ -139,6 +139,7 @@ int mcorb_lmap_create(mcorb_vocab *v, int device, int max_landmarks, int max_can
         TRY(m->rel.kernels.create());
         TRY(m->align.sac.create());
         TRY(m->align.fit.create());
+        TRY(m->init.kernels.create());
         TRY(m->d_geom.alloc(N * 6));
         TRY(m->d_desc.alloc(N * 32));
         HIPCHK(hipMemset(m->d_geom, 0, N * 6 * sizeof(double)));

@@ -1,5 +1,6 @@
 // mcorb_lmap_store.h -- the local map object, shared by its search (mcorb_lmap.cpp), by the mapping step that fills it
-// (mcorb_mapping.cpp), by the calls that keep its landmarks up to date (mcorb_landmark.cpp) and by fast tracking (mcorb_track.cpp).
+// (mcorb_mapping.cpp), by the map initialization (mcorb_init.cpp), by the calls that keep its landmarks up to date
+// (mcorb_landmark.cpp) and by fast tracking (mcorb_track.cpp).
 #pragma once
 #include <algorithm>
 #include <atomic>
@@ -9,6 +10,7 @@
 
 #include "mcorb_kfdb_store.h"
 #include "mcorb_align.h"
+#include "mcorb_init.h"
 #include "mcorb_mapping_new.h"
 #include "mcorb_pack.h"
 #include "mcorb_pose.h"
@@ -303,6 +305,31 @@ struct mcorb_lmap {
             return h_flags.grow(n, mcorb::kHostMapped);
         }
     } align;
+
+    // scratch of mcorb_lmap_initialize (mcorb_init.cpp), grow-only: the packed input (InitLayout), k_init_triangulate's records,
+    // k_init_select's keys, id offsets and result, and what the host reads: every match's record and the call's, host-mapped
+    struct Init {
+        mcorb::Staged in;
+        mcorb::DevBuf<mcorb::MapOut> d_rec;
+        mcorb::DevBuf<uint64_t> d_keys;
+        mcorb::DevBuf<int32_t> d_offset;
+        mcorb::DevBuf<mcorb::InitSel> d_sel;
+        mcorb::HostBuf<mcorb::MapOut> h_rec;
+        mcorb::HostBuf<mcorb::InitCall> h_call;
+        enum { kTriangulate, kSelect, kPut };
+        mcorb::Spans<3> kernels;                // k_init_triangulate (both instances), k_init_select, k_init_put
+        int last_launched = 0;
+        int reserve(size_t bytes, size_t n)
+        {
+            TRY(in.reserve(bytes));
+            TRY(d_rec.grow(n));
+            TRY(d_keys.grow(2 * n));
+            TRY(d_offset.grow(n));
+            TRY(d_sel.grow(1));
+            TRY(h_rec.grow(n, mcorb::kHostMapped));
+            return h_call.grow(1, mcorb::kHostMapped);
+        }
+    } init;
 };
 
 // the pose refinement behind a tracking call (mcorb_pose.cpp); the caller holds the store's lock and has set track_refine_params.
@@ -339,6 +366,48 @@ int obs_check_locked(const mcorb_lmap *m, const ObsInput &in, const char *who);
 void obs_gather(const mcorb_lmap *m, const ObsInput &in, std::vector<PoseObs> &obs, std::vector<double> &X);
 void obs_stage(const ObsInput &in, const ObsLayout &L, const Staged &s);
 void obs_enqueue_refine(const mcorb_lmap *m, const ObsInput &in, const ObsLayout &L, const Staged &s, const PoseBufs &b);
+
+// shared by mcorb_mapping.cpp and mcorb_init.cpp (defined in the former).  map_who: the entry whose arguments the checks below
+// name in their errors; map_check_frame: a frame's arrays and its lIds; map_count_views: the views of a match of feature q of
+// `other` with feature t of `cur`; map_count_frame / map_pack_frame: what a frame adds to a packed input, and the frame into it
+void map_who(const char *who);
+int map_check_frame(const mcorb_lmap *m, const mcorb_map_frame &f, int ncams, const int32_t *lids);
+int map_count_views(const mcorb_map_frame &other, const mcorb_map_frame &cur, int q, int t, int nlevels, uint8_t &nv);
+void map_count_frame(const mcorb_map_frame &f, size_t &nmi, size_t &nkp);
+void map_pack_frame(const mcorb_map_frame &f, MapFrameDev &d, int32_t *mi, size_t &mi_at, MapKp *kp, size_t &kp_at);
+
+// The matches that need a record, as a device store's kernels take them: per segment (a neighbour; the previous keyframe is
+// segment 0) by view count, in blocks of one wave, the matches of at most 4 views first.  Segment s's matches are query[s] /
+// train[s][0 .. n[s]) and lie at moff[s] in nviews and item_of; wanted(s, j): match j of segment s needs a record
+struct MapWork {
+    std::vector<int32_t> item_of;
+    std::vector<MapItem> items;
+    std::vector<MapBlock> blocks;
+    int nblocks_small = 0;
+    template <class Wanted>
+    void order(int nseg, const int32_t *const *query, const int32_t *const *train, const int32_t *n, const size_t *moff,
+               const uint8_t *nviews, Wanted wanted)
+    {
+        std::vector<int> order;
+        for (int pass = 0; pass < 2; pass++) {   // 0: at most 4 views, 1: the rest
+            for (int s = 0; s < nseg; s++) {
+                const uint8_t *nv = nviews + moff[s];
+                order.clear();
+                for (int j = 0; j < n[s]; j++)
+                    if ((nv[j] <= 4) == (pass == 0) && wanted(s, j)) order.push_back(j);
+                std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return nv[a] < nv[b]; });
+                for (size_t k = 0; k < order.size(); k++) {
+                    if (k % kMapBlock == 0)
+                        blocks.push_back(MapBlock{s, (int32_t)items.size(), (int32_t)std::min<size_t>(kMapBlock, order.size() - k)});
+                    const int j = order[k];
+                    item_of[moff[s] + j] = (int32_t)items.size();
+                    items.push_back(MapItem{query[s][j], train[s][j], (int32_t)items.size()});
+                }
+            }
+            if (pass == 0) nblocks_small = (int)blocks.size();
+        }
+    }
+};
 }  // namespace mcorb
 
 // a new stamp value; the stamps start over before the counter wraps

@@ -99,39 +99,6 @@ int count_views(const mcorb_map_frame &other, const mcorb_map_frame &cur, int q,
     return MCORB_OK;
 }
 
-// The matches that need a record, as a device store's kernels take them: per segment (a neighbour; the previous keyframe is
-// segment 0) by view count, in blocks of one wave, the matches of at most 4 views first.  Segment s's matches are query[s] /
-// train[s][0 .. n[s]) and lie at moff[s] in nviews and item_of; wanted(s, j): match j of segment s needs a record
-struct MapWork {
-    std::vector<int32_t> item_of;
-    std::vector<MapItem> items;
-    std::vector<MapBlock> blocks;
-    int nblocks_small = 0;
-    template <class Wanted>
-    void order(int nseg, const int32_t *const *query, const int32_t *const *train, const int32_t *n, const size_t *moff,
-               const uint8_t *nviews, Wanted wanted)
-    {
-        std::vector<int> order;
-        for (int pass = 0; pass < 2; pass++) {   // 0: at most 4 views, 1: the rest
-            for (int s = 0; s < nseg; s++) {
-                const uint8_t *nv = nviews + moff[s];
-                order.clear();
-                for (int j = 0; j < n[s]; j++)
-                    if ((nv[j] <= 4) == (pass == 0) && wanted(s, j)) order.push_back(j);
-                std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return nv[a] < nv[b]; });
-                for (size_t k = 0; k < order.size(); k++) {
-                    if (k % kMapBlock == 0)
-                        blocks.push_back(MapBlock{s, (int32_t)items.size(), (int32_t)std::min<size_t>(kMapBlock, order.size() - k)});
-                    const int j = order[k];
-                    item_of[moff[s] + j] = (int32_t)items.size();
-                    items.push_back(MapItem{query[s][j], train[s][j], (int32_t)items.size()});
-                }
-            }
-            if (pass == 0) nblocks_small = (int)blocks.size();
-        }
-    }
-};
-
 // what a frame adds to the packed input: match indices and keypoints
 void count_frame(const mcorb_map_frame &f, size_t &nmi, size_t &nkp)
 {
@@ -291,6 +258,26 @@ struct CasesDev {
 };
 
 }  // namespace
+
+// what mcorb_init.cpp shares with the two entries above (mcorb_lmap_store.h)
+namespace mcorb {
+void map_who(const char *who) { g_who = who; }
+int map_check_frame(const mcorb_lmap *m, const mcorb_map_frame &f, int ncams, const int32_t *lids)
+{
+    TRY(check_frame(f, ncams));
+    return check_lids(m, f, lids);
+}
+int map_count_views(const mcorb_map_frame &other, const mcorb_map_frame &cur, int q, int t, int nlevels, uint8_t &nv)
+{
+    uint8_t nv_cur;
+    return count_views(other, cur, q, t, nlevels, nv, nv_cur);
+}
+void map_count_frame(const mcorb_map_frame &f, size_t &nmi, size_t &nkp) { count_frame(f, nmi, nkp); }
+void map_pack_frame(const mcorb_map_frame &f, MapFrameDev &d, int32_t *mi, size_t &mi_at, MapKp *kp, size_t &kp_at)
+{
+    pack_frame(f, d, mi, mi_at, kp, kp_at);
+}
+}  // namespace mcorb
 
 extern "C" {
 

@@ -100,10 +100,10 @@ MCORB_TRI_HD inline void map_rays(const MapViews &v, int i0, int i1, const doubl
     for (int i = i0; i < i1; i++) lm_ray_add(X, v.centre[i], acc);
 }
 
-// everything after the triangulation: the per-view gates, the parallax window, the normal of the new landmark
-MCORB_TRI_HD inline void map_after(const MapViews &v, const double X[3], const float *inv_sigma2, MapOut &o)
+// the per-view gates (:5885-5913; FrontEnd::initialization has the same loop, :2702-2724): 0 when X passes every view, otherwise
+// kMapBehind or kMapChi2 of the first view that rejects
+MCORB_TRI_HD inline int map_view_gates(const MapViews &v, const double X[3], const float *inv_sigma2)
 {
-    for (int k = 0; k < 3; k++) o.X[k] = X[k];
     for (int i = 0; i < v.nv; i++) {
         const double *P = v.P[i], *K = v.K[i];
         double p[3], q[3];
@@ -112,7 +112,7 @@ MCORB_TRI_HD inline void map_after(const MapViews &v, const double X[3], const f
             for (int k = 0; k < 3; k++) s += P[4 * r + k] * X[k];
             p[r] = s + P[4 * r + 3];
         }
-        if (p[2] < 0) { o.verdict = kMapBehind; return; }
+        if (p[2] < 0) return kMapBehind;
         for (int r = 0; r < 3; r++) {
             double s = 0.0;
             for (int k = 0; k < 3; k++) s += K[3 * r + k] * p[k];
@@ -122,8 +122,17 @@ MCORB_TRI_HD inline void map_after(const MapViews &v, const double X[3], const f
         const double kx = (double)v.kx[i], ky = (double)v.ky[i];
         double err = (ex - kx) * (ex - kx) + (ey - ky) * (ey - ky);
         err = err * (double)inv_sigma2[v.octave[i]];
-        if (err > 5.991) { o.verdict = kMapChi2; return; }
+        if (err > 5.991) return kMapChi2;
     }
+    return kMapLandmark;
+}
+
+// everything after the triangulation: the per-view gates, the parallax window, the normal of the new landmark
+MCORB_TRI_HD inline void map_after(const MapViews &v, const double X[3], const float *inv_sigma2, MapOut &o)
+{
+    for (int k = 0; k < 3; k++) o.X[k] = X[k];
+    const int gate = map_view_gates(v, X, inv_sigma2);
+    if (gate != kMapLandmark) { o.verdict = gate; return; }
     double o1[3], o2[3], n1[3], n2[3];
     map_centre(v.P[0], o1);
     map_centre(v.P[v.nv1], o2);

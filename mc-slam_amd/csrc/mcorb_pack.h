@@ -87,4 +87,14 @@ struct MapLayout {
     }
 };
 
+// mcorb_lmap_initialize: a MapLayout of two frames (the current one first) without F tables and depths, then the n matches'
+// flags on entry and their queryIdx / trainIdx
+struct InitLayout {
+    MapLayout m;
+    size_t flags, query, train;
+    InitLayout(size_t ncams, size_t nlevels, size_t nmi, size_t nkp, size_t nblocks, size_t nitems, size_t n)
+        : m(2, 0, ncams, nlevels, nmi, nkp, nblocks, nitems, 0), flags(m.p.add<uint8_t>(n)), query(m.p.add<int32_t>(n)),
+          train(m.p.add<int32_t>(n)) {}
+};
+
 }  // namespace mcorb
