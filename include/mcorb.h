@@ -826,7 +826,8 @@ int mcorb_dev_map_refine_selftest(int device, int n, const double *X0, const int
 /* landmarks, lines :2633-2839.  The MIN_FEATS and first-frame arms, the        */
 /* choice of lf_prev, the matchers and estimators (mcorb_lmap_ransac_pose,      */
 /* _relative_pose, _align_pose), the one-camera findEssentialMat / recoverPose  */
-/* arm, insertKeyFrame, numTrackedLMs, uv_ref, the trial counter and the 4x4    */
+/* arm (mcorb_lmap_essential_pose gives its T and flags), insertKeyFrame,       */
+/* numTrackedLMs, uv_ref, the trial counter and the 4x4                         */
 /* inverses stay with the caller.                                              */
 /* ------------------------------------------------------------------------- */
 #define MCORB_INIT_MAX_MATCHES 16384
@@ -1459,6 +1460,83 @@ int mcorb_lmap_last_align_counts(mcorb_lmap *m, int32_t *count, int32_t *valid, 
 int mcorb_align_solve(int n, const double *p1, const double *p2, const uint8_t *member, double *R, double *t, double *gap);
 /* test hook, host: the distances of n pairs at the pose (R, t); a NaN is the default quiet NaN */
 int mcorb_align_eval(int n, const double *p1, const double *p2, const double *R, const double *t, double *dist);
+
+/* ------------------------------------------------------------------------- */
+/* The pose of one camera between two frames from 2D-2D matches: what the      */
+/* reference gets from cv::findEssentialMat(..., RANSAC, prob, thr, mask) and  */
+/* cv::recoverPose(...) in the one-camera arm of its bootstrap (MCSlam/src/    */
+/* FrontEnd.cpp:2591-2628) and at six more places (:2105, :3023, :6842, :6959, */
+/* :7142, :7172).  OpenCV is not in the tree: the Sampson distance and         */
+/* recoverPose's cheirality vote are recalled; the draws, the minimal solver,  */
+/* the absence of the adaptive stop, the triangulation inside the vote and the */
+/* rotations from E are stated.                         */
+/* ------------------------------------------------------------------------- */
+#define MCORB_ESS_MAX_ITERATIONS 16384
+#define MCORB_ESS_SAMPLE 5
+#define MCORB_ESS_MAX_ROOTS 10     /* the models of a hypothesis: slot 10 h + c is root c of hypothesis h */
+#define MCORB_ESS_OK 0            /* a model won */
+#define MCORB_ESS_NO_OBS 1        /* no matches: the identity, nothing ran */
+#define MCORB_ESS_NO_MODEL 2      /* no hypothesis had a model (fewer than 5 matches among the causes): the identity, every flag 0 */
+/* threshold_px: findEssentialMat's, in pixels (the reference passes 1.0 or 0.5); distance_thresh: recoverPose's, in units of the
+ * baseline (OpenCV's default is 50); seed: of the draws; max_iterations: the hypotheses, 1 .. MCORB_ESS_MAX_ITERATIONS, all of
+ * them examined (the reference's `prob` has no counterpart; OpenCV's cap is 1000) */
+typedef struct mcorb_ess_params {
+    double threshold_px, distance_thresh;
+    uint64_t seed;
+    int32_t max_iterations, reserved;
+} mcorb_ess_params;
+/* (R, t) = c1_T_c2, R row-major: X_c1 = R X_c2 + t with |t| = 1, what :2620-2625 put into T (the identity without a winner); E:
+ * the winning model, x1^T E x2 = 0 on normalised points, |E|_F^2 = 2; status: MCORB_ESS_*; n_matches: n; n_ransac_inliers: the
+ * winner's count at the threshold; n_inliers: those of them that pass the winning candidate's depth test, the flags set;
+ * best_hypothesis, best_root (-1: none); sample: the winner's five matches in draw order; n_models: the (hypothesis, root) slots
+ * that had a model; cheirality: the four candidates' counts in the order (R+, t^), (R-, t^), (R+, -t^), (R-, -t^) */
+typedef struct mcorb_ess_result {
+    double R[9], t[3], E[9];
+    int32_t status, n_matches, n_ransac_inliers, n_inliers, best_hypothesis, best_root, sample[MCORB_ESS_SAMPLE], n_models, cheirality[4],
+        reserved;
+} mcorb_ess_result;
+/* The pose of a camera's second frame in its first from n matches: uv1[i] (KeyPoint::pt) in frame 1, uv2[i] in frame 2.  Of cam
+ * only fx, fy, s, u0, v0 are read.  All arithmetic is fp64, one IEEE operation per operator in the order written
+ * (csrc/mcorb_ess.h), + - * /, comparisons and sqrt:
+ * - the points: y = (v - v0) / fy, x = ((u - u0) - s y) / fx; the bearing is (x, y, 1) / sqrt((x x + y y) + 1).
+ * - the sample: 5 distinct matches by mcorb_lmap_relative_pose's walk on the draws j = 0 .. 4.  n < 5: no model.
+ * - the solver (stated): an orthonormal basis X, Y, Z, W of the null space of the five rows vec(d1 d2^T); the ten cubics of E = x X
+ *   + y Y + z Z + W (2 E E^T E - tr(E E^T) E and det E) as a 10 x 10 matrix C(z) over x^3, x^2 y, x y^2, y^3, x^2, x y, y^2, x, y, 1;
+ *   det C(z) at 11 fixed nodes by LU with partial pivoting and a constant 11 x 11 table for its 11 coefficients; the real roots
+ *   by the chain of derivatives with 48 bisections per bracket; per root, in ascending z, (x, y) from C(z) and three Gauss-Newton
+ *   steps on the ten cubics; the model is kept iff it is finite and its residuals on the sample's five rows and on the ten
+ *   cubics are below 1e-9.  At most 10 models per hypothesis.
+ * - the score (OpenCV's Sampson distance, recalled): r = x1^T E x2, a = E x2, b = E^T x1, err = r r / (a0 a0 + a1 a1 + b0 b0 + b1
+ *   b1); a match is an inlier iff err < (threshold_px / ((fx + fy) / 2))^2, strictly; a NaN is no inlier.
+ * - the consensus: the largest count over all n matches wins, a tie goes to the lowest hypothesis, then to the lowest root.
+ * - the pose (recoverPose's vote, recalled; the rotations and the triangulation stated): t^ the longest cross product of E's
+ *   columns, R+- = cof(E) -+ [t^]x E with three polar steps; over the winner's inliers each of the four candidates counts the
+ *   matches whose midpoint of mcorb_lmap_relative_pose's score has z strictly inside (0, distance_thresh) in both cameras; the
+ *   largest count wins, a tie goes to the lowest candidate; the flags are the inliers that pass the winner's test.
+ * A device store runs k_ess_hypotheses, k_ess_score, k_ess_pick and k_ess_finish in one submission on its stream with one wait;
+ * a host-only store runs the same header serially: the results are equal bit for bit.  The store's landmarks are neither read
+ * nor written.  inlier (may be NULL): one flag per match.  Refused before anything runs: MCORB_E_ARG for a NULL, n < 0, a
+ * threshold, distance or focal length that is not finite and positive, max_iterations outside 1 .. MCORB_ESS_MAX_ITERATIONS;
+ * MCORB_E_STATE while a tracking call is pending. */
+int mcorb_lmap_essential_pose(mcorb_lmap *m, int n, const float *uv1, const float *uv2, const mcorb_track_cam *cam,
+                              const mcorb_ess_params *params, mcorb_ess_result *res, uint8_t *inlier);
+/* a device store's last k_ess_hypotheses (us[0]), k_ess_score (us[1]), k_ess_pick (us[2]) and k_ess_finish (us[3]) launch,
+ * microseconds between HIP events, and its hypotheses; a call without matches launches nothing and leaves them */
+int mcorb_lmap_last_essential_timing(mcorb_lmap *m, float us[4], int *n_hyp);
+/* test hook: the counts of all 10 n_hyp slots of the last call that ran any, whether each had a model (a slot without one has
+ * count 0) and (models may be NULL) their E, 9 doubles per slot; a device store copies them down from where its kernels left
+ * them.  MCORB_E_CAP (with n_slots set) when cap < n_slots */
+int mcorb_lmap_last_essential_counts(mcorb_lmap *m, int32_t *count, int32_t *valid, double *models, int cap, int *n_slots);
+/* test hook, host: the solver on 5 matches (uv1, uv2: 5 x 2) -> the number of models, their E (9 doubles each, at most 10) in E
+ * and (z may be NULL) the root each came from before its Gauss-Newton steps, ascending; or a negative error.  The hooks take the
+ * keypoints in double: a float's value gives the bits mcorb_lmap_essential_pose computes from that float */
+int mcorb_ess_solve(const mcorb_track_cam *cam, const double *uv1, const double *uv2, double *E, double *z);
+/* test hook, host: the Sampson values of n matches at E; a NaN is the default quiet NaN */
+int mcorb_ess_eval(const mcorb_track_cam *cam, int n, const double *uv1, const double *uv2, const double *E, double *err);
+/* test hook, host: the four candidates of E -- Rp, Rm (9 doubles each) and t^ -- and, where n > 0, the depths of the n matches in
+ * both cameras under each: depth[(4 i + c) * 2 + {0, 1}] */
+int mcorb_ess_decompose(const double *E, double *Rp, double *Rm, double *t, const mcorb_track_cam *cam, int n, const double *uv1,
+                        const double *uv2, double *depth);
 
 /* ------------------------------------------------------------------------- */
 /* Host stages exposed for the CPU test-suite (no device needed)              */

@@ -1666,6 +1666,46 @@ class LocalMap:
         _lib.check(self.L.mcorb_lmap_last_relative_counts(self.h, count.ctypes.data, valid.ctypes.data, REL_MAX_ITERATIONS, C.byref(nh)))
         return count[:nh.value], valid[:nh.value].astype(bool)
 
+    # the pose of one camera between two frames by five-point RANSAC (mcorb_lmap_essential_pose)
+    def essential_pose(self, cam, uv1, uv2, threshold_px=1.0, distance_thresh=50.0, max_iterations=1000, seed=0):
+        """the pose c1_T_c2 of one camera's second frame in its first from 2D-2D matches, |t| = 1, without landmarks: what the
+        reference takes from cv::findEssentialMat(..., RANSAC, prob, thr, mask) and cv::recoverPose in the one-camera arm of its
+        bootstrap.  Match i is the keypoint uv1[i] of frame 1 and uv2[i] of frame 2; cam: pose_cams(...) or a track_view, whose
+        camera 0's calibration is read; threshold_px: on the Sampson distance, in pixels (the reference's 1.0 or 0.5);
+        distance_thresh: recoverPose's; max_iterations hypotheses of 5 matches each (1 .. ESS_MAX_ITERATIONS), all examined, up to
+        10 models each; seed: of the draws.  -> EssentialResult, whose (R, t) and inliers LocalMap.initialize takes for a rig of
+        one camera.  A device store runs k_ess_hypotheses, k_ess_score, k_ess_pick and k_ess_finish in one submission; a host-only
+        store the same arithmetic serially, with the same bits.  The store's landmarks are not touched"""
+        uv1 = np.ascontiguousarray(uv1, np.float32).reshape(-1, 2)
+        n = len(uv1)
+        uv2 = np.ascontiguousarray(uv2, np.float32).reshape(n, 2)
+        par = _lib.EssParams()
+        par.threshold_px, par.distance_thresh = float(threshold_px), float(distance_thresh)
+        par.seed, par.max_iterations = int(seed) & 0xFFFFFFFFFFFFFFFF, int(max_iterations)
+        res, flags = _lib.EssResultC(), np.zeros(max(n, 1), np.uint8)
+        _lib.check(self.L.mcorb_lmap_essential_pose(self.h, n, uv1.ctypes.data, uv2.ctypes.data, _pose_cams(cam)[1], C.byref(par),
+                                                    C.byref(res), flags.ctypes.data))
+        return EssentialResult(res, flags[:n])
+
+    def last_essential_timing(self):
+        """((us of k_ess_hypotheses, k_ess_score, k_ess_pick, k_ess_finish), hypotheses) of the last essential_pose() launch; a
+        device store"""
+        us, nh = (C.c_float * 4)(), C.c_int(0)
+        _lib.check(self.L.mcorb_lmap_last_essential_timing(self.h, us, C.byref(nh)))
+        return tuple(us), nh.value
+
+    def last_essential_counts(self):
+        """test hook: (counts, has a model, E 9 doubles) of all (hypothesis, root) slots of the last essential_pose() that ran
+        any; slot 10 h + c is root c of hypothesis h"""
+        ns = C.c_int(0)
+        code = self.L.mcorb_lmap_last_essential_counts(self.h, None, None, None, 0, C.byref(ns))
+        if code != E_CAP:
+            _lib.check(code)
+        cap = max(ns.value, 1)
+        count, valid, models = np.zeros(cap, np.int32), np.zeros(cap, np.int32), np.zeros((cap, 9))
+        _lib.check(self.L.mcorb_lmap_last_essential_counts(self.h, count.ctypes.data, valid.ctypes.data, models.ctypes.data, cap, C.byref(ns)))
+        return count[:ns.value], valid[:ns.value].astype(bool), models[:ns.value]
+
     # the rig pose between two frames from 3D-3D pairs (mcorb_lmap_align_pose)
     def align_pose(self, pts2, pts1=None, lids1=None, mode="sac", threshold=0.2, inlier_dist=0.1, max_iterations=100, seed=0, refit=True):
         """the pose b1_T_b2 of a rig's second frame in its first from pairs of triangulated points: FrontEnd::poseFromPCAlignment,
@@ -1777,6 +1817,28 @@ REL_OK, REL_NO_OBS, REL_NO_MODEL = 0, 1, 2
 REL_MAX_ITERATIONS, REL_SAMPLE = 16384, 17
 
 
+class EssentialResult:
+    """what LocalMap.essential_pose returns: R (3 x 3), t = c1_T_c2 (X_c1 = R X_c2 + t, |t| = 1; the identity without a winner); E
+    (3 x 3), the winning model, x1^T E x2 = 0 on normalised points; status (ESS_OK, ESS_NO_OBS, ESS_NO_MODEL); n_matches;
+    n_ransac_inliers, the winner's count at the threshold; n_inliers and inliers, one bool per match: those of them that pass
+    the winning candidate's depth test; best_hypothesis, best_root (-1: none); sample (the winner's five matches in draw order);
+    n_models; cheirality, the four candidates' counts"""
+
+    def __init__(self, res, flags):
+        self.R = np.array(res.R[:], np.float64).reshape(3, 3)
+        self.t = np.array(res.t[:], np.float64)
+        self.E = np.array(res.E[:], np.float64).reshape(3, 3)
+        self.status, self.n_matches = res.status, res.n_matches
+        self.n_ransac_inliers, self.n_inliers = res.n_ransac_inliers, res.n_inliers
+        self.best_hypothesis, self.best_root, self.sample = res.best_hypothesis, res.best_root, tuple(res.sample[:])
+        self.n_models, self.cheirality = res.n_models, tuple(res.cheirality[:])
+        self.inliers = flags.astype(bool)
+
+
+ESS_OK, ESS_NO_OBS, ESS_NO_MODEL = 0, 1, 2
+ESS_MAX_ITERATIONS, ESS_SAMPLE, ESS_MAX_ROOTS = 16384, 5, 10
+
+
 class AlignResult:
     """what LocalMap.align_pose returns: R (3 x 3), t = b1_T_b2 of the answer (X_1 = R X_2 + t; the identity without one); status
     (ALIGN_OK, ALIGN_NO_OBS, ALIGN_NO_MODEL); used (ALIGN_USED_SAC: the winning hypothesis, ALIGN_USED_FIT: a least-squares fit);
@@ -1866,6 +1928,45 @@ def rel_eval(cams, R, t, cam1, uv1, cam2, uv2):
     _lib.check(_lib.load().mcorb_rel_eval(ncams, ca, n, cam1.ctypes.data, uv1.ctypes.data, cam2.ctypes.data, uv2.ctypes.data, R.ctypes.data,
                                           t.ctypes.data, score.ctypes.data))
     return score[:n]
+
+
+def ess_solve(cam, uv1, uv2, with_roots=False):
+    """test hook (host): the five-point solver on 5 matches (keypoints as doubles) -> [E 3 x 3], at most 10, in ascending order of
+    the root z each began from; with_roots: -> (that, [z])"""
+    uv1 = np.ascontiguousarray(uv1, np.float64).reshape(5, 2)
+    uv2 = np.ascontiguousarray(uv2, np.float64).reshape(5, 2)
+    E, z = np.zeros((10, 9)), np.zeros(10)
+    k = _lib.load().mcorb_ess_solve(_pose_cams(cam)[1], uv1.ctypes.data, uv2.ctypes.data, E.ctypes.data, z.ctypes.data)
+    _lib.check(min(k, 0))
+    models = [E[i].reshape(3, 3).copy() for i in range(k)]
+    return (models, z[:k].tolist()) if with_roots else models
+
+
+def ess_eval(cam, E, uv1, uv2):
+    """test hook (host): the Sampson values (n) of the matches at E"""
+    uv1 = np.ascontiguousarray(uv1, np.float64).reshape(-1, 2)
+    n = len(uv1)
+    uv2 = np.ascontiguousarray(uv2, np.float64).reshape(n, 2)
+    E = np.ascontiguousarray(E, np.float64).reshape(9)
+    err = np.zeros(max(n, 1))
+    _lib.check(_lib.load().mcorb_ess_eval(_pose_cams(cam)[1], n, uv1.ctypes.data, uv2.ctypes.data, E.ctypes.data, err.ctypes.data))
+    return err[:n]
+
+
+def ess_decompose(E, cam=None, uv1=None, uv2=None):
+    """test hook (host): the four candidates of E -> (R+ 3 x 3, R- 3 x 3, t^): (R+, t^), (R-, t^), (R+, -t^), (R-, -t^); with cam and
+    matches: -> (that, depths n x 4 x 2: each match's z in camera 1 and camera 2 under each candidate)"""
+    E = np.ascontiguousarray(E, np.float64).reshape(9)
+    Rp, Rm, t = np.zeros(9), np.zeros(9), np.zeros(3)
+    n, depth, a1, a2, ca = 0, np.zeros(8), None, None, None
+    if cam is not None:
+        uv1 = np.ascontiguousarray(uv1, np.float64).reshape(-1, 2)
+        n = len(uv1)
+        uv2 = np.ascontiguousarray(uv2, np.float64).reshape(n, 2)
+        depth, a1, a2, ca = np.zeros((max(n, 1), 4, 2)), uv1.ctypes.data, uv2.ctypes.data, _pose_cams(cam)[1]
+    _lib.check(_lib.load().mcorb_ess_decompose(E.ctypes.data, Rp.ctypes.data, Rm.ctypes.data, t.ctypes.data, ca, n, a1, a2, depth.ctypes.data))
+    cands = (Rp.reshape(3, 3), Rm.reshape(3, 3), t)
+    return cands if cam is None else (cands, depth[:n])
 
 
 def sac_threshold(K00_02):

@@ -133,6 +133,17 @@ class RelResultC(C.Structure):
                 ("best_hypothesis", C.c_int32), ("sample", C.c_int32 * 17), ("n_models", C.c_int32)]
 
 
+class EssParams(C.Structure):
+    _fields_ = [("threshold_px", C.c_double), ("distance_thresh", C.c_double), ("seed", C.c_uint64), ("max_iterations", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class EssResultC(C.Structure):
+    _fields_ = [("R", C.c_double * 9), ("t", C.c_double * 3), ("E", C.c_double * 9), ("status", C.c_int32), ("n_matches", C.c_int32),
+                ("n_ransac_inliers", C.c_int32), ("n_inliers", C.c_int32), ("best_hypothesis", C.c_int32), ("best_root", C.c_int32),
+                ("sample", C.c_int32 * 5), ("n_models", C.c_int32), ("cheirality", C.c_int32 * 4), ("reserved", C.c_int32)]
+
+
 class AlignParams(C.Structure):
     _fields_ = [("threshold", C.c_double), ("inlier_dist", C.c_double), ("seed", C.c_uint64), ("max_iterations", C.c_int32),
                 ("mode", C.c_int32), ("refit", C.c_int32), ("reserved", C.c_int32)]
@@ -346,6 +357,12 @@ SIGNATURES = {
     "mcorb_rel_threshold": (C.c_double, [C.c_double]),
     "mcorb_rel_solve": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mcorb_rel_eval": (_i, [_i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mcorb_lmap_essential_pose": (_i, [_vp, _i, _vp, _vp, _vp, C.POINTER(EssParams), C.POINTER(EssResultC), _vp]),
+    "mcorb_lmap_last_essential_timing": (_i, [_vp, C.POINTER(_f), C.POINTER(_i)]),
+    "mcorb_lmap_last_essential_counts": (_i, [_vp, _vp, _vp, _vp, _i, C.POINTER(_i)]),
+    "mcorb_ess_solve": (_i, [_vp, _vp, _vp, _vp, _vp]),
+    "mcorb_ess_eval": (_i, [_vp, _i, _vp, _vp, _vp, _vp]),
+    "mcorb_ess_decompose": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
     "mcorb_lmap_align_pose": (_i, [_vp, _i, _vp, _vp, _vp, C.POINTER(AlignParams), C.POINTER(AlignResultC), _vp]),
     "mcorb_lmap_last_align_timing": (_i, [_vp, C.POINTER(_f), C.POINTER(_i)]),
     "mcorb_lmap_last_align_counts": (_i, [_vp, _vp, _vp, _i, C.POINTER(_i)]),

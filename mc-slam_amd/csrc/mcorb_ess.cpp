@@ -1,0 +1,236 @@
+// mcorb_ess.cpp -- the pose of one camera between two frames from 2D-2D matches: mcorb_lmap_essential_pose, what the reference
+// gets from cv::findEssentialMat and cv::recoverPose in the one-camera arm of its bootstrap (MCSlam/src/FrontEnd.cpp:2591-2628).
+// A device store runs k_ess_hypotheses, k_ess_score, k_ess_pick and k_ess_finish (mcorb_ess_gpu.hip) in one submission on the
+// store's stream with one wait; the record and the flags land in host-mapped memory.  A host-only store runs the header
+// (mcorb_ess.h) serially, so the two agree bit for bit.  Recalled from OpenCV: the Sampson distance and the cheirality vote;
+// stated: the draws, the five-point solver, no adaptive stop, the midpoint inside the vote, the rotations from E (DESIGN.md
+// section 9m).
+#include <math.h>
+#include <string.h>
+
+#include <mutex>
+#include <vector>
+
+#include "mcorb_lmap_store.h"
+
+using namespace mcorb;
+
+namespace {
+
+int fail(int code, const char *what) { set_error(std::string("lmap essential_pose: ") + what); return code; }
+
+bool positive(double v) { return v > 0 && sac_finite(v); }
+
+void fill_job(EssJob &job, const mcorb_track_cam &cam)
+{
+    memset(&job, 0, sizeof(job));
+    job.fx = cam.fx;
+    job.fy = cam.fy;
+    job.s = cam.s;
+    job.u0 = cam.u0;
+    job.v0 = cam.v0;
+}
+
+void fill_obs(EssObs *obs, int n, const float *uv1, const float *uv2)
+{
+    for (int i = 0; i < n; i++) obs[i] = EssObs{uv1[2 * i], uv1[2 * i + 1], uv2[2 * i], uv2[2 * i + 1]};
+}
+
+}  // namespace
+
+extern "C" {
+
+int mcorb_lmap_essential_pose(mcorb_lmap *m, int n, const float *uv1, const float *uv2, const mcorb_track_cam *cam,
+                              const mcorb_ess_params *params, mcorb_ess_result *res, uint8_t *inlier)
+{
+    TRY(check_lmap(m, "lmap essential_pose"));
+    if (!params || !res || !cam || n < 0 || (n && (!uv1 || !uv2))) return fail(MCORB_E_ARG, "bad argument");
+    if (!positive(params->threshold_px)) return fail(MCORB_E_ARG, "a threshold that is not finite and positive");
+    if (!positive(params->distance_thresh)) return fail(MCORB_E_ARG, "a distance that is not finite and positive");
+    if (!positive(cam->fx) || !positive(cam->fy)) return fail(MCORB_E_ARG, "a focal length that is not finite and positive");
+    if (params->max_iterations < 1 || params->max_iterations > MCORB_ESS_MAX_ITERATIONS)
+        return fail(MCORB_E_ARG, "1 .. MCORB_ESS_MAX_ITERATIONS iterations");
+    std::lock_guard<std::mutex> lk(m->mu);
+    if (m->track.pending.load()) return fail(MCORB_E_STATE, "a submitted tracking call has not been waited for");
+
+    const int S = n, H = params->max_iterations;
+    const size_t slots = (size_t)H * kEssRoots;
+    EssJob job;
+    fill_job(job, *cam);
+    const double thr = params->threshold_px / ((cam->fx + cam->fy) / 2.0);
+    job.threshold2 = thr * thr;
+    job.distance = params->distance_thresh;
+    job.seed = params->seed;
+    job.S = S;
+    job.H = H;
+
+    EssOut out;
+    std::vector<uint8_t> flags((size_t)n);
+    mcorb_lmap::Ess &b = m->ess;
+    if (S == 0) {
+        memset(&out, 0, sizeof(out));
+        out.R[0] = out.R[4] = out.R[8] = 1.0;
+        out.status = MCORB_ESS_NO_OBS;
+        out.best_hypothesis = out.best_root = -1;
+        for (int j = 0; j < kEssSample; j++) out.sample[j] = -1;
+    } else if (m->device < 0) {
+        std::vector<EssObs> obs((size_t)n);
+        fill_obs(obs.data(), n, uv1, uv2);
+        std::vector<int32_t> samples((size_t)H * kEssSample), count(slots);
+        std::vector<EssPt> pts((size_t)S);
+        b.host_models.resize(slots);
+        ess_run_serial(job, obs.data(), b.host_models.data(), samples.data(), count.data(), pts.data(), out, flags.data());
+        b.host_count.swap(count);
+        b.last_hyp = H;
+    } else {
+        HIPCHK(hipSetDevice(m->device));
+        (void)hipGetLastError();   // (a stale error of this thread is not this call's)
+        const EssLayout L((size_t)n);
+        TRY(b.reserve(L.p.total, (size_t)n, (size_t)H));
+        *b.in.host<EssJob>(L.job) = job;
+        fill_obs(b.in.host<EssObs>(L.obs), n, uv1, uv2);
+        hipStream_t st = m->st;
+        TRY(b.in.upload(st, L.p.total));
+        HIPCHK(hipMemsetAsync(b.d_count, 0, (slots + 4) * sizeof(int32_t), st));   // (the four votes lie behind the counts)
+        EssArgs a;
+        a.job = b.in.dev<const EssJob>(L.job);
+        a.obs = b.in.dev<const EssObs>(L.obs);
+        a.models = b.d_models;
+        a.samples = b.d_samples;
+        a.valid = b.d_valid;
+        a.count = b.d_count;
+        a.cheir = b.d_count.get() + slots;
+        a.pick = b.d_pick;
+        a.out = b.h_out;
+        a.flags = b.h_flags;
+        TRY(b.kernels.mark(st, 0));
+        launch_ess_hypotheses(st, a, H);
+        hipError_t launched = hipGetLastError();
+        TRY(b.kernels.mark(st, 1));
+        launch_ess_score(st, a, S, H);
+        if (launched == hipSuccess) launched = hipGetLastError();
+        TRY(b.kernels.mark(st, 2));
+        launch_ess_pick(st, a, S);
+        if (launched == hipSuccess) launched = hipGetLastError();
+        TRY(b.kernels.mark(st, 3));
+        launch_ess_finish(st, a, S);
+        if (launched == hipSuccess) launched = hipGetLastError();
+        TRY(b.kernels.mark(st, 4));
+        HIPCHK(hipStreamSynchronize(st));
+        HIPCHK(launched);
+        b.kernels.read();
+        b.last_hyp = H;
+        out = *b.h_out.get();
+        memcpy(flags.data(), b.h_flags.get(), (size_t)n);
+    }
+
+    memset(res, 0, sizeof(*res));
+    memcpy(res->R, out.R, sizeof(out.R));
+    memcpy(res->t, out.t, sizeof(out.t));
+    memcpy(res->E, out.E, sizeof(out.E));
+    res->status = out.status;
+    res->n_matches = n;
+    res->n_ransac_inliers = out.n_ransac_inliers;
+    res->n_inliers = out.n_inliers;
+    res->best_hypothesis = out.best_hypothesis;
+    res->best_root = out.best_root;
+    memcpy(res->sample, out.sample, sizeof(res->sample));
+    res->n_models = out.n_models;
+    memcpy(res->cheirality, out.cheirality, sizeof(res->cheirality));
+    if (inlier && n) memcpy(inlier, flags.data(), (size_t)n);
+    return MCORB_OK;
+}
+
+int mcorb_lmap_last_essential_timing(mcorb_lmap *m, float us[4], int *n_hyp)
+{
+    TRY(check_lmap_handle(m, "lmap last_essential_timing"));
+    if (!us) return fail(MCORB_E_ARG, "bad argument");
+    std::lock_guard<std::mutex> lk(m->mu);
+    for (int k = 0; k < 4; k++) us[k] = m->ess.kernels.us[k];
+    if (n_hyp) *n_hyp = m->ess.last_hyp;
+    return MCORB_OK;
+}
+
+int mcorb_lmap_last_essential_counts(mcorb_lmap *m, int32_t *count, int32_t *valid, double *models, int cap, int *n_slots)
+{
+    TRY(check_lmap(m, "lmap last_essential_counts"));
+    if (cap < 0 || !n_slots || (cap && (!count || !valid))) return fail(MCORB_E_ARG, "bad argument");
+    std::lock_guard<std::mutex> lk(m->mu);
+    const int N = m->ess.last_hyp * kEssRoots;
+    *n_slots = N;
+    if (cap < N) return fail(MCORB_E_CAP, "arrays too small");
+    if (!N) return MCORB_OK;
+    std::vector<EssModel> copy;
+    const EssModel *M = m->ess.host_models.data();
+    if (m->device < 0) {
+        memcpy(count, m->ess.host_count.data(), (size_t)N * sizeof(int32_t));
+    } else {
+        HIPCHK(hipSetDevice(m->device));
+        copy.resize((size_t)N);
+        HIPCHK(hipMemcpy(count, m->ess.d_count, (size_t)N * sizeof(int32_t), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(copy.data(), m->ess.d_models, (size_t)N * sizeof(EssModel), hipMemcpyDeviceToHost));
+        M = copy.data();
+    }
+    for (int s = 0; s < N; s++) {
+        valid[s] = M[s].valid;
+        if (models) memcpy(models + 9 * (size_t)s, M[s].E, sizeof(M[s].E));
+    }
+    return MCORB_OK;
+}
+
+int mcorb_ess_solve(const mcorb_track_cam *cam, const double *uv1, const double *uv2, double *E, double *z)
+{
+    if (!cam || !uv1 || !uv2 || !E) return fail(MCORB_E_ARG, "bad argument");
+    EssJob job;
+    fill_job(job, *cam);
+    double d1[kEssSample][3], d2[kEssSample][3];
+    for (int j = 0; j < kEssSample; j++) {
+        EssPt p;
+        ess_point(job, uv1[2 * j], uv1[2 * j + 1], uv2[2 * j], uv2[2 * j + 1], p);
+        ess_bearing(p.x1, p.y1, d1[j]);
+        ess_bearing(p.x2, p.y2, d2[j]);
+    }
+    return ess_solve5(d1, d2, E, z);
+}
+
+int mcorb_ess_eval(const mcorb_track_cam *cam, int n, const double *uv1, const double *uv2, const double *E, double *err)
+{
+    if (!cam || n < 0 || !E || (n && (!uv1 || !uv2 || !err))) return fail(MCORB_E_ARG, "bad argument");
+    EssJob job;
+    fill_job(job, *cam);
+    for (int i = 0; i < n; i++) {
+        EssPt p;
+        ess_point(job, uv1[2 * (size_t)i], uv1[2 * (size_t)i + 1], uv2[2 * (size_t)i], uv2[2 * (size_t)i + 1], p);
+        err[i] = pose_default_nan(ess_sampson(E, p));
+    }
+    return MCORB_OK;
+}
+
+int mcorb_ess_decompose(const double *E, double *Rp, double *Rm, double *t, const mcorb_track_cam *cam, int n, const double *uv1,
+                        const double *uv2, double *depth)
+{
+    if (!E || !Rp || !Rm || !t || n < 0 || (n && (!cam || !uv1 || !uv2 || !depth))) return fail(MCORB_E_ARG, "bad argument");
+    EssPick P;
+    memset(&P, 0, sizeof(P));
+    ess_decompose(E, P.Rp, P.Rm, P.t);
+    memcpy(Rp, P.Rp, sizeof(P.Rp));
+    memcpy(Rm, P.Rm, sizeof(P.Rm));
+    memcpy(t, P.t, sizeof(P.t));
+    if (!n) return MCORB_OK;
+    EssJob job;
+    fill_job(job, *cam);
+    for (int i = 0; i < n; i++) {
+        EssPt p;
+        ess_point(job, uv1[2 * (size_t)i], uv1[2 * (size_t)i + 1], uv2[2 * (size_t)i], uv2[2 * (size_t)i + 1], p);
+        for (int c = 0; c < 4; c++) {
+            const double tc[3] = {c < 2 ? P.t[0] : -P.t[0], c < 2 ? P.t[1] : -P.t[1], c < 2 ? P.t[2] : -P.t[2]};
+            double z1, z2;
+            ess_depths((c & 1) ? P.Rm : P.Rp, tc, p, z1, z2);
+            depth[(4 * (size_t)i + c) * 2] = pose_default_nan(z1);
+            depth[(4 * (size_t)i + c) * 2 + 1] = pose_default_nan(z2);
+        }
+    }
+    return MCORB_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,269 @@
+// mcorb_ess_gpu.hip -- the pose of one camera between two frames by five-point RANSAC of mcorb_ess.h on a device store
+// (mcorb_ess.cpp): four launches on the store's stream, no workgroup waits on another, no result depends on the launch shape.
+//   k_ess_hypotheses   kEssLanes = 16 lanes per hypothesis, four hypotheses per wave, a workgroup of one wave.  The lanes of a
+//                      group only move values through LDS; every chain of operations is one function of the header, so the
+//                      host-only store gives the same bits.  Lane 0: the draws, the bearings, the null-space basis.  Lane k <
+//                      10: cubic k into the group's 10 x 20 table.  Lane j < 11: det C(z) at node j -- the pivoted LU indexes
+//                      its rows at run time, so its 10 x 10 matrix is a private array in scratch --, then coefficient j of the
+//                      polynomial.  The derivative chain: per level, lane i takes bracket i and lane 0 gathers the roots found.
+//                      Lane r < 10: the model of root r into its slot
+//   k_ess_score        the hot path, 10 H x S Sampson distances: a workgroup owns a tile of kEssTile matches, whose normalised
+//                      points each lane computes once, and a block of kEssSlotBlock slots, whose models it reads at uniform
+//                      addresses; per model a ballot and a population count per wave into integer counts in LDS, then one
+//                      integer atomicAdd per (workgroup, slot).  Slots without a model are skipped uniformly
+//   k_ess_pick         every workgroup finds the arg-max of the slots' keys for itself, forms the four candidates from the
+//                      winner -- the same bits in every workgroup -- and adds its matches' four votes to four integers;
+//                      workgroup 0 leaves the winner and its candidates for k_ess_finish
+//   k_ess_finish       reads the four votes, writes the flags of its tile; workgroup 0 writes the record to host-mapped memory
+// No extraction job runs this and no benchmark leg times it.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "mcorb_common.h"
+#include "mcorb_device.h"
+#include "mcorb_ess.h"
+#include "mcorb_kernels.h"
+
+namespace mcorb {
+
+static_assert(kEssTile == 4 * 64, "four waves");
+static_assert(kEssSlotBlock <= kEssTile, "a lane per slot of the block adds its count");
+static_assert(kEssLanes >= kEssNodes && kEssLanes >= kEssRoots + 1 && 64 % kEssLanes == 0, "a lane per node, per bracket and per root");
+
+// what the lanes of one hypothesis share
+struct EssGroup {
+    double B[36], table[200], d1[kEssSample][3], d2[kEssSample][3];
+    double det[kEssNodes], poly[kEssNodes], crit[kEssRoots], found[kEssRoots + 1], E[9 * kEssRoots];
+    int32_t has[kEssRoots + 1], sample[kEssSample], m, ok;
+};
+
+__global__ __launch_bounds__(64) void k_ess_hypotheses(const EssJob *__restrict__ job, const EssObs *__restrict__ obs,
+                                                       EssModel *__restrict__ models, int32_t *__restrict__ valid,
+                                                       int32_t *__restrict__ samples)
+{
+    constexpr int kGroups = 64 / kEssLanes;
+    __shared__ EssGroup groups[kGroups];
+    EssGroup &G = groups[threadIdx.x / kEssLanes];
+    const int lane = threadIdx.x % kEssLanes;
+    const int h = blockIdx.x * kGroups + threadIdx.x / kEssLanes;
+    const bool act = h < job->H;   // (a group beyond the hypotheses goes through every barrier and touches nothing)
+
+    if (act && lane == 0) {
+        int32_t smp[kEssSample];
+        G.ok = ess_sample(*job, h, obs, smp, G.d1, G.d2) ? 1 : 0;
+        for (int j = 0; j < kEssSample; j++) G.sample[j] = smp[j];
+        ess_basis(G.d1, G.d2, G.B);
+        G.m = 0;
+    }
+    __syncthreads();
+    if (act && lane < 10) ess_cubic(G.B, lane, G.table + 20 * lane);
+    __syncthreads();
+    if (act && lane < kEssNodes) G.det[lane] = ess_det_at(G.table, lane, 1.0);
+    __syncthreads();
+    if (act && lane < kEssNodes) G.poly[lane] = ess_coefficient(G.det, lane);
+    __syncthreads();
+    // the second pass at the roots' scale, which every lane works out for itself
+    double rho = 1.0;
+    if (act) {
+        const double ends[kEssNodes] = {G.poly[0], 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, G.poly[10]};
+        rho = ess_scale(ends);
+    }
+    if (act && lane < kEssNodes) G.det[lane] = ess_det_at(G.table, lane, rho);
+    __syncthreads();
+    if (act && lane < kEssNodes) G.poly[lane] = ess_coefficient(G.det, lane);
+    __syncthreads();
+    // ess_real_roots, a bracket per lane
+    const bool chain = act && G.ok && sac_finite(G.poly[10]) && G.poly[10] != 0.0;
+    for (int L = 9; L >= 0; L--) {
+        const int n = 10 - L;
+        const int m = chain ? G.m : 0;   // (<= n - 1: level L + 1 had at most n - 1 brackets)
+        if (chain && lane <= m) {
+            double p[kEssNodes], q[kEssNodes], crit[kEssRoots], bound, r;
+            for (int j = 0; j < kEssNodes; j++) p[j] = G.poly[j];
+            for (int j = 0; j < kEssRoots; j++) crit[j] = j < m ? G.crit[j] : 0.0;
+            ess_level(p, L, q, bound);
+            const bool got = ess_interval(q, n, crit, m, bound, lane, r);
+            G.has[lane] = got ? 1 : 0;
+            G.found[lane] = r;
+        }
+        __syncthreads();
+        if (chain && lane == 0) {
+            int found = 0;
+            for (int i = 0; i <= m; i++)
+                if (G.has[i]) G.crit[found++] = G.found[i];
+            G.m = found;
+        }
+        __syncthreads();
+    }
+    const int nr = chain ? G.m : 0;
+    // the models, compacted in root order as ess_hypothesis leaves them: lane r keeps its E, lane 0 writes the slots
+    double E[9];
+    bool kept = false;
+    if (act && lane < nr) kept = ess_root_model(G.table, G.B, G.d1, G.d2, rho * G.crit[lane], E);
+    if (act && lane < kEssRoots) {
+        G.has[lane] = kept ? 1 : 0;
+        for (int k = 0; k < 9; k++) G.E[9 * lane + k] = 0.0;
+    }
+    __syncthreads();
+    if (act && lane < kEssRoots && kept) {
+        int at = 0;
+        for (int i = 0; i < lane; i++) at += G.has[i];
+        for (int k = 0; k < 9; k++) G.E[9 * at + k] = E[k];
+    }
+    __syncthreads();
+    if (act && lane < kEssRoots) {
+        int n = 0;
+        for (int i = 0; i < kEssRoots; i++) n += G.has[i];
+        double M[9];
+        for (int k = 0; k < 9; k++) M[k] = G.E[9 * (lane < n ? lane : 0) + k];
+        ess_write_model(models[(size_t)kEssRoots * h + lane], lane < n, M);
+        valid[(size_t)kEssRoots * h + lane] = lane < n ? 1 : 0;
+    }
+    if (act && lane < kEssSample) samples[(size_t)kEssSample * h + lane] = G.sample[lane];
+}
+
+__device__ __forceinline__ void ess_point_of(const EssJob &job, const EssObs &o, EssPt &p)
+{
+    ess_point(job, (double)o.u1, (double)o.v1, (double)o.u2, (double)o.v2, p);
+}
+
+__global__ __launch_bounds__(kEssTile) void k_ess_score(const EssJob *__restrict__ job, const EssObs *__restrict__ obs,
+                                                        const EssModel *__restrict__ models, int32_t *__restrict__ count)
+{
+    __shared__ int32_t cnt[kEssSlotBlock];
+    const int t = threadIdx.x, lane = t & 63;
+    const int S = job->S, N = job->H * kEssRoots;
+    const int k = blockIdx.x * kEssTile + t;
+    const bool in = k < S;
+    const double threshold2 = job->threshold2;
+    EssPt p;
+    ess_point_of(*job, obs[in ? k : 0], p);   // (S >= 1: a lane beyond the matches scores match 0 and counts nothing)
+    if (t < kEssSlotBlock) cnt[t] = 0;
+    __syncthreads();
+    const int s0 = blockIdx.y * kEssSlotBlock, s1 = min(N, s0 + kEssSlotBlock);
+    for (int s = s0; s < s1; s++) {
+        const EssModel &M = models[s];   // (uniform over the workgroup)
+        if (!M.valid) continue;
+        double E[9];
+#pragma unroll
+        for (int j = 0; j < 9; j++) E[j] = M.E[j];
+        const bool inl = in && sac_is_inlier(ess_sampson(E, p), threshold2);
+        const unsigned long long mask = __ballot(inl);
+        if (lane == 0 && mask) atomicAdd(&cnt[s - s0], __popcll(mask));
+    }
+    __syncthreads();
+    if (t < s1 - s0 && cnt[t]) atomicAdd(&count[s0 + t], cnt[t]);
+}
+
+__global__ __launch_bounds__(kEssTile) void k_ess_pick(const EssJob *__restrict__ job, const EssObs *__restrict__ obs,
+                                                       const EssModel *__restrict__ models, const int32_t *__restrict__ valid,
+                                                       const int32_t *__restrict__ count,
+                                                       int32_t *__restrict__ cheir, EssPick *__restrict__ pick)
+{
+    __shared__ unsigned long long wkey[4];
+    __shared__ int32_t wmodels[4], votes[4];
+    __shared__ EssPick P;
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int S = job->S, N = job->H * kEssRoots;
+    unsigned long long key = 0;
+    int32_t nm = 0;
+    // (eight trips' loads at a time: a trip alone waits out two loads' latency, 390 times at 10 000 hypotheses)
+    for (int s0 = t; s0 < N; s0 += 8 * kEssTile) {
+        int32_t v[8], c[8];
+#pragma unroll
+        for (int u = 0; u < 8; u++) {
+            const int s = s0 + u * kEssTile;
+            v[u] = s < N ? valid[s] : 0;   // (models[s].valid, read densely)
+            c[u] = s < N ? count[s] : 0;
+        }
+#pragma unroll
+        for (int u = 0; u < 8; u++) {
+            const unsigned long long ks = ess_key(v[u], c[u], s0 + u * kEssTile);
+            key = ks > key ? ks : key;
+            nm += v[u];
+        }
+    }
+    for (int s = 32; s >= 1; s >>= 1) {
+        const unsigned long long other = __shfl_xor(key, s, 64);
+        key = other > key ? other : key;
+        nm += __shfl_xor(nm, s, 64);
+    }
+    if (lane == 0) {
+        wkey[wave] = key;
+        wmodels[wave] = nm;
+    }
+    if (t < 4) votes[t] = 0;
+    __syncthreads();
+    if (t == 0) {
+        key = wkey[0];
+        for (int w = 1; w < 4; w++) key = wkey[w] > key ? wkey[w] : key;
+        ess_pick(models, count, ess_key_slot(key), (wmodels[0] + wmodels[1]) + (wmodels[2] + wmodels[3]), P);
+    }
+    __syncthreads();
+    const int i = blockIdx.x * kEssTile + t;
+    bool pass[4] = {false, false, false, false};
+    if (i < S && P.slot >= 0) {
+        EssPt p;
+        ess_point_of(*job, obs[i], p);
+        if (sac_is_inlier(ess_sampson(P.E, p), job->threshold2)) {
+#pragma unroll
+            for (int c = 0; c < 4; c++) pass[c] = ess_candidate_passes(P, c, p, job->distance);
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < 4; c++) {
+        const unsigned long long mask = __ballot(pass[c]);
+        if (lane == 0 && mask) atomicAdd(&votes[c], __popcll(mask));
+    }
+    __syncthreads();
+    if (t < 4 && votes[t]) atomicAdd(&cheir[t], votes[t]);
+    if (blockIdx.x == 0 && t == 0) *pick = P;
+}
+
+__global__ __launch_bounds__(kEssTile) void k_ess_finish(const EssJob *__restrict__ job, const EssObs *__restrict__ obs,
+                                                         const EssPick *__restrict__ pick, const int32_t *__restrict__ cheir,
+                                                         const int32_t *__restrict__ samples, EssOut *out, uint8_t *flags)
+{
+    __shared__ EssPick P;
+    const int t = threadIdx.x;
+    if (t == 0) P = *pick;
+    __syncthreads();
+    const int32_t votes[4] = {cheir[0], cheir[1], cheir[2], cheir[3]};
+    const int w = ess_vote(votes);
+    const int i = blockIdx.x * kEssTile + t;
+    if (i < job->S) {
+        uint8_t flag = 0;
+        if (P.slot >= 0) {
+            EssPt p;
+            ess_point_of(*job, obs[i], p);
+            flag = sac_is_inlier(ess_sampson(P.E, p), job->threshold2) && ess_candidate_passes(P, w, p, job->distance) ? 1 : 0;
+        }
+        flags[i] = flag;
+    }
+    if (blockIdx.x == 0 && t == 0) ess_finish(P, votes, samples, *out);
+}
+
+void launch_ess_hypotheses(hipStream_t st, const EssArgs &a, int H)
+{
+    constexpr int kGroups = 64 / kEssLanes;
+    hipLaunchKernelGGL(k_ess_hypotheses, dim3((H + kGroups - 1) / kGroups), dim3(64), 0, st, a.job, a.obs, a.models, a.valid, a.samples);
+}
+
+void launch_ess_score(hipStream_t st, const EssArgs &a, int S, int H)
+{
+    hipLaunchKernelGGL(k_ess_score, dim3((S + kEssTile - 1) / kEssTile, (H * kEssRoots + kEssSlotBlock - 1) / kEssSlotBlock), dim3(kEssTile), 0,
+                       st, a.job, a.obs, a.models, a.count);
+}
+
+void launch_ess_pick(hipStream_t st, const EssArgs &a, int S)
+{
+    hipLaunchKernelGGL(k_ess_pick, dim3((S + kEssTile - 1) / kEssTile), dim3(kEssTile), 0, st, a.job, a.obs, a.models, a.valid, a.count, a.cheir, a.pick);
+}
+
+void launch_ess_finish(hipStream_t st, const EssArgs &a, int S)
+{
+    hipLaunchKernelGGL(k_ess_finish, dim3((S + kEssTile - 1) / kEssTile), dim3(kEssTile), 0, st, a.job, a.obs, a.pick, a.cheir, a.samples, a.out,
+                       a.flags);
+}
+
+}  // namespace mcorb

@@ -1,6 +1,6 @@
 // mcorb_kernels.h -- launch wrappers of the gfx950 kernels (mcorb_kernels.hip, mcorb_select_gpu.hip, mcorb_handoff_gpu.hip,
 // mcorb_bow_gpu.hip, mcorb_lf_gpu.hip, mcorb_kfdb_gpu.hip, mcorb_lmap_gpu.hip, mcorb_mapping_gpu.hip, mcorb_landmark_gpu.hip,
-// mcorb_track_gpu.hip, mcorb_pose_gpu.hip, mcorb_sac_gpu.hip, mcorb_rel_gpu.hip, mcorb_align_gpu.hip).
+// mcorb_track_gpu.hip, mcorb_pose_gpu.hip, mcorb_sac_gpu.hip, mcorb_rel_gpu.hip, mcorb_ess_gpu.hip, mcorb_align_gpu.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <vector>
@@ -10,6 +10,7 @@
 #include "mcorb_init.h"
 #include "mcorb_mapping_new.h"
 #include "mcorb_pose.h"
+#include "mcorb_ess.h"
 #include "mcorb_rel.h"
 #include "mcorb_sac.h"
 #include "mcorb_signal.h"
@@ -283,6 +284,27 @@ struct RelArgs {
 void launch_rel_hypotheses(hipStream_t st, const RelArgs &a, int H);
 void launch_rel_score(hipStream_t st, const RelArgs &a, int S, int H);
 void launch_rel_pick(hipStream_t st, const RelArgs &a, int S);
+
+// the pose of one camera between two frames by five-point RANSAC (mcorb_ess_gpu.hip), four launches.  job and obs (the S
+// matches) are device memory.  k_ess_hypotheses: kEssLanes lanes per hypothesis, four hypotheses per wave; models[10 H] (slot 10 h
+// + c is root c of hypothesis h), valid[10 H] (the models' flags once more, densely, for k_ess_pick's walk) and samples[5 H].  k_ess_score: a workgroup per (tile of kEssTile matches, block of kEssSlotBlock
+// slots), integer adds into count[10 H], which the caller has zeroed on the stream together with cheir[4].  k_ess_pick: the winner
+// and its four candidates into pick, the candidates' votes over the winner's inliers into cheir.  k_ess_finish: the flags of
+// all S matches and the record out (both host-mapped)
+constexpr int kEssTile = 256, kEssSlotBlock = 40, kEssLanes = 16;
+struct EssArgs {
+    const EssJob *job;
+    const EssObs *obs;
+    EssModel *models;
+    int32_t *samples, *valid, *count, *cheir;
+    EssPick *pick;
+    EssOut *out;
+    uint8_t *flags;
+};
+void launch_ess_hypotheses(hipStream_t st, const EssArgs &a, int H);
+void launch_ess_score(hipStream_t st, const EssArgs &a, int S, int H);
+void launch_ess_pick(hipStream_t st, const EssArgs &a, int S);
+void launch_ess_finish(hipStream_t st, const EssArgs &a, int S);
 
 // the pose between two frames from 3D-3D pairs (mcorb_align_gpu.hip).  job, p2 and p1 or lids1 (the n pairs; lids1: frame 1's
 // points are geom's, 6 doubles per slot) are device memory.  Mode 1: k_align_hypotheses -- one lane per hypothesis, models[H];

@@ -10,6 +10,7 @@
 
 #include "mcorb_kfdb_store.h"
 #include "mcorb_align.h"
+#include "mcorb_ess.h"
 #include "mcorb_init.h"
 #include "mcorb_mapping_new.h"
 #include "mcorb_pack.h"
@@ -305,6 +306,33 @@ struct mcorb_lmap {
             return h_flags.grow(n, mcorb::kHostMapped);
         }
     } align;
+
+    // the pose of one camera between two frames by five-point RANSAC (mcorb_ess.cpp), grow-only: the packed input (EssLayout), the
+    // model of every (hypothesis, root) slot, the hypotheses' samples, the slots' valid flags once more as a dense array, the slots' counts with the four votes behind them, the
+    // winner and its candidates, and what the host reads: k_ess_finish's record and the flags per match, host-mapped
+    struct Ess {
+        mcorb::Staged in;
+        mcorb::DevBuf<mcorb::EssModel> d_models;
+        mcorb::DevBuf<int32_t> d_samples, d_valid, d_count;
+        mcorb::DevBuf<mcorb::EssPick> d_pick;
+        mcorb::HostBuf<mcorb::EssOut> h_out;
+        mcorb::HostBuf<uint8_t> h_flags;
+        mcorb::Spans<4> kernels;                // k_ess_hypotheses, k_ess_score, k_ess_pick, k_ess_finish
+        int last_hyp = 0;                       // the hypotheses of the last call that ran any (either kind of store)
+        std::vector<int32_t> host_count;        // a host-only store's last counts and models, for mcorb_lmap_last_essential_counts
+        std::vector<mcorb::EssModel> host_models;
+        int reserve(size_t bytes, size_t n, size_t H)
+        {
+            TRY(in.reserve(bytes));
+            TRY(d_models.grow(H * mcorb::kEssRoots));
+            TRY(d_samples.grow(H * mcorb::kEssSample));
+            TRY(d_valid.grow(H * mcorb::kEssRoots));
+            TRY(d_count.grow(H * mcorb::kEssRoots + 4));
+            TRY(d_pick.grow(1));
+            TRY(h_out.grow(1, mcorb::kHostMapped));
+            return h_flags.grow(n, mcorb::kHostMapped);
+        }
+    } ess;
 
     // scratch of mcorb_lmap_initialize (mcorb_init.cpp), grow-only: the packed input (InitLayout), k_init_triangulate's records,
     // k_init_select's keys, id offsets and result, and what the host reads: every match's record and the call's, host-mapped

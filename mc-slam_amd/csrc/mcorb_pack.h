@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "mcorb_align.h"
+#include "mcorb_ess.h"
 #include "mcorb_mapping.h"
 #include "mcorb_rel.h"
 #include "mcorb_sac.h"
@@ -42,6 +43,13 @@ struct RelLayout {
     Pack p;
     size_t job, obs;
     explicit RelLayout(size_t n) : job(p.add<RelJob>(1)), obs(p.add<RelObs>(n)) {}
+};
+
+// mcorb_lmap_essential_pose: the EssJob and the n matches
+struct EssLayout {
+    Pack p;
+    size_t job, obs;
+    explicit EssLayout(size_t n) : job(p.add<EssJob>(1)), obs(p.add<EssObs>(n)) {}
 };
 
 // mcorb_lmap_align_pose: the AlignJob, frame 1's points or their landmark ids (lids), frame 2's points
