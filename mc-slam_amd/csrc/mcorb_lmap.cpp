@@ -147,6 +147,10 @@ int mcorb_lmap_create(mcorb_vocab *v, int device, int max_landmarks, int max_can
         HIPCHK(hipMemset(m->d_desc, 0, N * 32));
         TRY(m->d_nrays.alloc(N));
         HIPCHK(hipMemset(m->d_nrays, 0, N * sizeof(int32_t)));
+        // the fills run on the null stream and the store's stream is non-blocking, i.e. NOT ordered against it: without this a fill
+        // that is still queued can zero what the first set() after the create has just put (seen once in a whole run of the GPU
+        // suite as a neighbour skipped for its depths on a store created, filled and used at once: test_gpu_mapping.py, 1 match)
+        HIPCHK(hipStreamSynchronize(nullptr));
     }
     *out = m.release();
     return MCORB_OK;

@@ -1,6 +1,7 @@
 """Every call of the local map that keeps scratch of its own, one after the other on ONE device store and on a host-only twin:
 track from host arrays, track_rig_frames (2 frames), refine_pose, ransac_pose with its refinement (both solvers),
-triangulate_new, triangulate_neighbours (2 neighbours), observe / update_points and search -- three times over, small, about four
+triangulate_new, triangulate_neighbours (2 neighbours), observe / update_points, search, relative_pose, align_pose (mode 1 from
+points, mode 0 from landmark ids), essential_pose and initialize -- three times over, small, about four
 times larger, small again, so that every grow-only buffer is grown by one call and then used again, by that call and, where the
 buffers are shared, by the others.  Every result equals the twin's bit for bit (floats as raw bytes); after each call its timing
 getter gives a finite, non-negative number for every span that ran, and the span of k_track_points reads exactly 0 for the frame
@@ -11,15 +12,22 @@ import math
 import numpy as np
 import pytest
 
+import align_cases as AC
+import align_ref as AR
+import ess_cases as EC
+import init_cases as Ic
+import init_ref as IR
 import kfdb_cases as K
 import landmark_cases as Lc
 import lmap_cases as Lm
 import mapping_cases as Mc
 import mapping_new_cases as Nc
 import pose_cases as PC
+import rel_cases as RC
 import sac_cases as SC
 import sac_rig_cases as SR
 import track_cases as T
+from test_gpu_init import same as same_init, same_store as same_init_store
 from test_gpu_track_batch import extracted, frame_landmarks, shifted
 from test_lmap_cpu import make, same_result, scene_landmarks
 
@@ -28,8 +36,10 @@ pytestmark = pytest.mark.gpu
 C = 2
 MAXL = 8192
 # where each call keeps its landmarks: (host-array tracking, the rig frames', refine_pose, ransac_pose central / rig, the neighbours' old
-# landmarks are the scene's own 3000 .., new ids of triangulate_neighbours / triangulate_new, observe, search)
-AT = dict(track=0, frames=600, pose=1300, sac=1800, sac_rig=2400, neigh_new=4200, new_new=5200, observe=6200, search=7400)
+# landmarks are the scene's own 3000 .., new ids of triangulate_neighbours / triangulate_new, observe, search, align_pose's frame-1
+# points, initialize's new ids: 160 per round)
+AT = dict(track=0, frames=600, pose=1300, sac=1800, sac_rig=2400, neigh_new=4200, new_new=5200, observe=6200, search=7400, align=2600,
+          init=7700)
 #        landmarks twins  per_cam  pose  sac  thin  hyp  neighbours      old  new  observe  search
 SIZES = [(40, 20, 8, 12, 20, 3, 16, (16, 12), 8, 24, 30, 60),
          (160, 80, 32, 48, 80, 12, 64, (64, 48), 32, 96, 120, 240),
@@ -171,6 +181,57 @@ def one_round(mc, lm_d, db_d, lm_h, db_h, rig, rnd, size):
     assert len(got[0].new_lids) > 0
     us = lm_d.last_timing()
     assert us[2] == nsearch and spans_ok(us[:2])
+
+    # relative_pose: as many matches as the tracking scene has landmarks
+    cams, truth, matches, _ = RC.scene(C, nl, 5 + rnd, moved=0.0)
+    got = [RC.run(mc, lm, cams, matches, max_iterations=hyp, seed=rnd) for lm in both]
+    same_fields(got[0], got[1], ("R", "t", "inliers", "sample"), what + "relative_pose")
+    for f in ("status", "n_inliers", "n_matches", "best_hypothesis", "n_models"):
+        assert getattr(got[0], f) == getattr(got[1], f), (what, "relative_pose", f)
+    assert got[0].status == mc.REL_OK and got[0].n_inliers > 17
+    us, nh = lm_d.last_relative_timing()
+    assert nh == hyp and len(spans_ok(us)) == 3
+
+    # align_pose: mode 1 from points, mode 0 from the store's landmarks
+    truth, p1, p2, _ = AC.scene(n=nobs, seed=7 + rnd, moved=nobs // 10)
+    got = [AC.run(mc, lm, p1, p2, max_iterations=hyp, seed=rnd) for lm in both]
+    AC.same_results(got[0], got[1], what + "align_pose, sac")
+    assert got[0].status == AR.OK and got[0].used == AR.USED_FIT and got[0].n_inliers > 3 and math.isfinite(got[0].mean_error)
+    us, nh = lm_d.last_align_timing()
+    assert nh == hyp and len(spans_ok(us)) == 4
+    lids = AT["align"] + np.arange(nobs, dtype=np.int32)
+    got = []
+    for lm in both:
+        lm.set(lids, p1, np.zeros_like(p1))
+        got.append(AC.run(mc, lm, None, p2, mode=AR.ALL, lids1=lids))
+    AC.same_results(got[0], got[1], what + "align_pose, all, lids1")
+    AC.same_results(got[0], AC.run(mc, lm_h, p1, p2, mode=AR.ALL), what + "align_pose, all, lids1 against pts1")
+    assert got[0].status == AR.OK and math.isfinite(got[0].mean_error)
+    spans_ok(lm_d.last_align_timing()[0])
+
+    # essential_pose
+    truth, matches, _ = EC.scene("general", n=nl, seed=9 + rnd, noise=0.1)
+    got = [EC.run(mc, lm, matches, max_iterations=hyp, seed=rnd) for lm in both]
+    EC.same_stores(got[0], got[1], what + "essential_pose")
+    assert got[0].status == mc.ESS_OK and got[0].n_inliers > 5
+    for x, y in zip(lm_d.last_essential_counts(), lm_h.last_essential_counts()):
+        assert x.tobytes() == y.tobytes(), what + "essential_pose, the slots"
+    us, nh = lm_d.last_essential_timing()
+    assert nh == hyp and len(spans_ok(us)) == 4
+
+    # initialize: init_cases.py's two-camera scene, its ids in a range of its own
+    sc = Ic.scene(C, n=nsearch, seed=3 + rnd)
+    sc["next_lid"] = AT["init"] + 160 * rnd
+    sc["prev"]["lids"][sc["prev"]["lids"] == 7] = sc["next_lid"] + 159
+    got = [Ic.run_scene(mc, lm, sc) for lm in both]
+    same_init(got[0], got[1], what + "initialize")
+    new = got[0].new_lid[got[0].new_lid >= 0]
+    assert got[0].status == (IR.DONE if nsearch >= 240 else IR.FEW), "the large round initializes, the small ones have too few matches"
+    assert len(new) == (got[0].n_triangulated if got[0].status == IR.DONE else 0)
+    assert len(new) == 0 or (sc["next_lid"] <= new.min() and new.max() < sc["next_lid"] + 159)
+    same_init_store(lm_d, lm_h, new, what + "initialize")
+    us = lm_d.last_initialize_timing()
+    assert us[3] == int(sc["flags"].sum()) and spans_ok(us[:3])
 
 
 def test_every_call_three_times_on_one_store(mc):
