@@ -1384,6 +1384,52 @@ int mcorb_rel_solve(int ncams, const mcorb_track_cam *cams, const int32_t *cam1,
 int mcorb_rel_eval(int ncams, const mcorb_track_cam *cams, int n, const int32_t *cam1, const double *uv1, const int32_t *cam2,
                    const double *uv2, const double *R, const double *t, double *score);
 
+/* The polish of the winner over its inliers: opt-in, mcorb_lmap_relative_pose itself is as it was.  Stated, not recalled: OpenGV's
+ * optimizeModelCoefficients for this problem is not in the tree and the reference does not call it.
+ * rounds: 1 .. MCORB_REL_POLISH_ROUNDS; max_iterations: the solves of a round, 1 .. MCORB_REL_POLISH_MAX_ITERATIONS */
+#define MCORB_REL_POLISH_ROUNDS 2
+#define MCORB_REL_POLISH_MAX_ITERATIONS 100
+typedef struct mcorb_rel_polish_params {
+    int32_t rounds, max_iterations;
+} mcorb_rel_polish_params;
+/* a round: its members, the solves it took and its MCORB_POSE_* status, the cost (the sum over the members of 2 score / threshold;
+ * a NaN is the default quiet NaN) at its start and its end, the inliers of all matches at its result, and whether that result
+ * replaced the current pose (n_inliers >= the current count) */
+typedef struct mcorb_rel_polish_round {
+    double cost_initial, cost_final;
+    int32_t n_members, iterations, status, n_inliers, accepted, reserved;
+} mcorb_rel_polish_round;
+/* (R, t) and n_inliers: the RANSAC winner's, what mcorb_lmap_relative_pose returns; round[k]: zero for a round that did not run;
+ * rounds_run: the rounds that ran, a refused one included */
+typedef struct mcorb_rel_polish {
+    double R[9], t[3];
+    mcorb_rel_polish_round round[MCORB_REL_POLISH_ROUNDS];
+    int32_t n_inliers, rounds_run;
+} mcorb_rel_polish;
+/* mcorb_lmap_relative_pose followed by the polish (csrc/mcorb_rel.h), fp64, one IEEE operation per operator in the order written:
+ * - the residual of a match at a pose: with the score's a, b, w, P1 and P2 the 6-vector (a - P1 / |P1|, b / |b| - P2 / |P2|) / sqrt(
+ *   threshold); its squared length is 2 score / threshold.
+ * - the Jacobian: forward differences through the Cayley retraction of mcorb_lmap_refine_pose, h = 2^-20 per unknown.
+ * - a round: mcorb_lmap_refine_pose's Levenberg-Marquardt (its damping, schedule and stops) from the current pose over the round's
+ *   members, the 28 sums added in the tree of 256 lanes; then all n matches are scored at the result, and it replaces the current
+ *   pose, flags and count iff its count is at least the current count -- otherwise polishing ends.  Round 1's members are the
+ *   winner's inliers, round 2's are round 1's.
+ * res->R, t, n_inliers and the flags are the accepted pose's; best_hypothesis, sample and n_models stay the winner's.  Without a
+ * winner (MCORB_REL_NO_OBS, MCORB_REL_NO_MODEL) no round runs.  A device store runs k_rel_hypotheses, k_rel_score, k_rel_pick and
+ * k_rel_fit (one workgroup) in one submission with one wait; a host-only store gives the same bits.  Refused before anything runs:
+ * what mcorb_lmap_relative_pose refuses, a NULL pp or polish, rounds or max_iterations outside their ranges */
+int mcorb_lmap_relative_pose_polished(mcorb_lmap *m, int n, const int32_t *cam1, const float *uv1, const int32_t *cam2, const float *uv2,
+                                      int ncams, const mcorb_track_cam *cams, const mcorb_rel_params *params,
+                                      const mcorb_rel_polish_params *pp, mcorb_rel_result *res, uint8_t *inlier, mcorb_rel_polish *polish);
+/* mcorb_lmap_last_relative_timing with us[3]: k_rel_fit of the last polished call (0 before one) */
+int mcorb_lmap_last_relative_timing4(mcorb_lmap *m, float us[4], int *n_hyp);
+/* test hook, host: the polish of the given pose (R, t) over the given members (member[n], nonzero: in) of n matches, keypoints in
+ * double as in the other mcorb_rel_* hooks.  The current count and flags are those of (R, t) at the threshold over all n matches.
+ * -> the polish record (its R, t, n_inliers: the pose handed in and its count), the accepted pose and its flags (inlier[n]) */
+int mcorb_rel_polish_run(int ncams, const mcorb_track_cam *cams, int n, const int32_t *cam1, const double *uv1, const int32_t *cam2,
+                         const double *uv2, const uint8_t *member, const double *R, const double *t, double threshold,
+                         const mcorb_rel_polish_params *pp, mcorb_rel_polish *polish, double *R_out, double *t_out, uint8_t *inlier);
+
 /* ------------------------------------------------------------------------- */
 /* The rig pose between two frames from 3D-3D correspondences: the third       */
 /* estimator of FrontEnd::estimatePoseLF, PC_ALIGN (MCSlam/src/FrontEnd.cpp:   */

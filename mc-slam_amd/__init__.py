@@ -1660,6 +1660,34 @@ class LocalMap:
         _lib.check(self.L.mcorb_lmap_last_relative_timing(self.h, us, C.byref(nh)))
         return tuple(us), nh.value
 
+    def relative_pose_polished(self, cams, cam1, uv1, cam2, uv2, threshold, max_iterations=10000, seed=0, rounds=2, polish_iterations=10):
+        """relative_pose followed by the polish of the winner over its inliers: `rounds` (1 .. 2) rounds of refine_pose's
+        Levenberg-Marquardt, at most polish_iterations (1 .. 100) solves each, on the residual (a - P1 / |P1|, b / |b| - P2 / |P2|)
+        / sqrt(threshold) of the members; after a round all matches are scored at its result, which replaces the current pose,
+        flags and count iff its count is at least the current one.  -> (RelResult, RelPolish): the result's R, t, n_inliers and
+        inliers are the accepted pose's, best_hypothesis, sample and n_models the winner's.  A device store adds k_rel_fit to
+        the submission; a host-only store gives the same bits"""
+        cam1 = np.ascontiguousarray(cam1, np.int32).reshape(-1)
+        n = len(cam1)
+        cam2 = np.ascontiguousarray(cam2, np.int32).reshape(n)
+        uv1 = np.ascontiguousarray(uv1, np.float32).reshape(n, 2)
+        uv2 = np.ascontiguousarray(uv2, np.float32).reshape(n, 2)
+        ncams, ca = _pose_cams(cams)
+        par, pp = _lib.RelParams(), _lib.RelPolishParams(int(rounds), int(polish_iterations))
+        par.threshold, par.seed, par.max_iterations = float(threshold), int(seed) & 0xFFFFFFFFFFFFFFFF, int(max_iterations)
+        res, rec, flags = _lib.RelResultC(), _lib.RelPolishC(), np.zeros(max(n, 1), np.uint8)
+        _lib.check(self.L.mcorb_lmap_relative_pose_polished(self.h, n, cam1.ctypes.data, uv1.ctypes.data, cam2.ctypes.data, uv2.ctypes.data,
+                                                            ncams, ca, C.byref(par), C.byref(pp), C.byref(res), flags.ctypes.data,
+                                                            C.byref(rec)))
+        return RelResult(res, flags[:n]), RelPolish(rec)
+
+    def last_relative_timing4(self):
+        """((us of k_rel_hypotheses, k_rel_score, k_rel_pick of the last relative call, k_rel_fit of the last polished one),
+        hypotheses); a device store"""
+        us, nh = (C.c_float * 4)(), C.c_int(0)
+        _lib.check(self.L.mcorb_lmap_last_relative_timing4(self.h, us, C.byref(nh)))
+        return tuple(us), nh.value
+
     def last_relative_counts(self):
         """test hook: (counts, has a model) of all hypotheses of the last relative_pose() that ran any"""
         count, valid, nh = np.zeros(REL_MAX_ITERATIONS, np.int32), np.zeros(REL_MAX_ITERATIONS, np.int32), C.c_int(0)
@@ -1815,6 +1843,21 @@ class RelResult:
 
 REL_OK, REL_NO_OBS, REL_NO_MODEL = 0, 1, 2
 REL_MAX_ITERATIONS, REL_SAMPLE = 16384, 17
+REL_POLISH_ROUNDS, REL_POLISH_MAX_ITERATIONS = 2, 100
+
+
+class RelPolish:
+    """the polish record of LocalMap.relative_pose_polished and rel_polish: R (3 x 3), t and n_inliers of the pose the polish began
+    from (the RANSAC winner's); rounds_run; rounds: per round that ran a dict of n_members, iterations, status (POSE_*),
+    cost_initial, cost_final, n_inliers (of all matches at the round's result) and accepted"""
+
+    def __init__(self, rec):
+        self.R = np.array(rec.R[:], np.float64).reshape(3, 3)
+        self.t = np.array(rec.t[:], np.float64)
+        self.n_inliers, self.rounds_run = rec.n_inliers, rec.rounds_run
+        self.rounds = [dict(n_members=q.n_members, iterations=q.iterations, status=q.status, cost_initial=q.cost_initial,
+                            cost_final=q.cost_final, n_inliers=q.n_inliers, accepted=bool(q.accepted))
+                       for q in rec.round[:rec.rounds_run]]
 
 
 class EssentialResult:
@@ -1928,6 +1971,22 @@ def rel_eval(cams, R, t, cam1, uv1, cam2, uv2):
     _lib.check(_lib.load().mcorb_rel_eval(ncams, ca, n, cam1.ctypes.data, uv1.ctypes.data, cam2.ctypes.data, uv2.ctypes.data, R.ctypes.data,
                                           t.ctypes.data, score.ctypes.data))
     return score[:n]
+
+
+def rel_polish(cams, R, t, cam1, uv1, cam2, uv2, member, threshold, rounds=2, polish_iterations=10):
+    """test hook (host): the polish of the pose (R, t) = b1_T_b2 over the matches with member[i], keypoints as doubles; the
+    current count and flags are the pose's own over all matches -> (R 3 x 3, t, inliers, RelPolish) of the accepted pose"""
+    n, cam1, uv1, cam2, uv2 = _rel_arrays(cam1, uv1, cam2, uv2)
+    R = np.ascontiguousarray(R, np.float64).reshape(9)
+    t = np.ascontiguousarray(t, np.float64).reshape(3)
+    member = np.ascontiguousarray(member, np.uint8).reshape(n)
+    ncams, ca = _pose_cams(cams)
+    pp, rec = _lib.RelPolishParams(int(rounds), int(polish_iterations)), _lib.RelPolishC()
+    Ro, to, flags = np.zeros(9), np.zeros(3), np.zeros(max(n, 1), np.uint8)
+    _lib.check(_lib.load().mcorb_rel_polish_run(ncams, ca, n, cam1.ctypes.data, uv1.ctypes.data, cam2.ctypes.data, uv2.ctypes.data,
+                                                member.ctypes.data, R.ctypes.data, t.ctypes.data, float(threshold), C.byref(pp),
+                                                C.byref(rec), Ro.ctypes.data, to.ctypes.data, flags.ctypes.data))
+    return Ro.reshape(3, 3), to, flags[:n].astype(bool), RelPolish(rec)
 
 
 def ess_solve(cam, uv1, uv2, with_roots=False):

@@ -133,6 +133,20 @@ class RelResultC(C.Structure):
                 ("best_hypothesis", C.c_int32), ("sample", C.c_int32 * 17), ("n_models", C.c_int32)]
 
 
+class RelPolishParams(C.Structure):
+    _fields_ = [("rounds", C.c_int32), ("max_iterations", C.c_int32)]
+
+
+class RelPolishRoundC(C.Structure):
+    _fields_ = [("cost_initial", C.c_double), ("cost_final", C.c_double), ("n_members", C.c_int32), ("iterations", C.c_int32),
+                ("status", C.c_int32), ("n_inliers", C.c_int32), ("accepted", C.c_int32), ("reserved", C.c_int32)]
+
+
+class RelPolishC(C.Structure):
+    _fields_ = [("R", C.c_double * 9), ("t", C.c_double * 3), ("round", RelPolishRoundC * 2), ("n_inliers", C.c_int32),
+                ("rounds_run", C.c_int32)]
+
+
 class EssParams(C.Structure):
     _fields_ = [("threshold_px", C.c_double), ("distance_thresh", C.c_double), ("seed", C.c_uint64), ("max_iterations", C.c_int32),
                 ("reserved", C.c_int32)]
@@ -357,6 +371,11 @@ SIGNATURES = {
     "mcorb_rel_threshold": (C.c_double, [C.c_double]),
     "mcorb_rel_solve": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mcorb_rel_eval": (_i, [_i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mcorb_lmap_relative_pose_polished": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _vp, C.POINTER(RelParams), C.POINTER(RelPolishParams),
+                                               C.POINTER(RelResultC), _vp, C.POINTER(RelPolishC)]),
+    "mcorb_lmap_last_relative_timing4": (_i, [_vp, C.POINTER(_f), C.POINTER(_i)]),
+    "mcorb_rel_polish_run": (_i, [_i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_double, C.POINTER(RelPolishParams),
+                                  C.POINTER(RelPolishC), _vp, _vp, _vp]),
     "mcorb_lmap_essential_pose": (_i, [_vp, _i, _vp, _vp, _vp, C.POINTER(EssParams), C.POINTER(EssResultC), _vp]),
     "mcorb_lmap_last_essential_timing": (_i, [_vp, C.POINTER(_f), C.POINTER(_i)]),
     "mcorb_lmap_last_essential_counts": (_i, [_vp, _vp, _vp, _vp, _i, C.POINTER(_i)]),

@@ -284,6 +284,20 @@ struct RelArgs {
 void launch_rel_hypotheses(hipStream_t st, const RelArgs &a, int H);
 void launch_rel_score(hipStream_t st, const RelArgs &a, int S, int H);
 void launch_rel_pick(hipStream_t st, const RelArgs &a, int S);
+// the polish behind a pick whose out and flags are device memory (pick; member[0 .. S)): k_rel_fit, one workgroup -- the rounds of
+// mcorb_rel.h over the members, member[S .. 2 S) the other set of flags, then the accepted record, its flags and the polish
+// record to host-mapped memory
+struct RelFitArgs {
+    const RelJob *job;
+    const RelObs *obs;
+    const RelOut *pick;
+    uint8_t *member;
+    int32_t rounds, max_iterations;
+    RelOut *out;
+    uint8_t *flags;
+    RelPolish *polish;
+};
+void launch_rel_fit(hipStream_t st, const RelFitArgs &a);
 
 // the pose of one camera between two frames by five-point RANSAC (mcorb_ess_gpu.hip), four launches.  job and obs (the S
 // matches) are device memory.  k_ess_hypotheses: kEssLanes lanes per hypothesis, four hypotheses per wave; models[10 H] (slot 10 h

@@ -278,6 +278,18 @@ struct mcorb_lmap {
             TRY(h_out.grow(1, mcorb::kHostMapped));
             return h_flags.grow(n, mcorb::kHostMapped);
         }
+        // mcorb_lmap_relative_pose_polished: the pick's record and flags stay in device memory (d_member: the current flags and
+        // the other set, 2 n), k_rel_fit writes h_out, h_flags and the polish record
+        mcorb::DevBuf<mcorb::RelOut> d_pick;
+        mcorb::DevBuf<uint8_t> d_member;
+        mcorb::HostBuf<mcorb::RelPolish> h_polish;
+        mcorb::Spans<1> fit;                    // k_rel_fit
+        int reserve_polish(size_t n)
+        {
+            TRY(d_pick.grow(1));
+            TRY(d_member.grow(2 * n));
+            return h_polish.grow(1, mcorb::kHostMapped);
+        }
     } rel;
 
     // the pose between two frames from 3D-3D pairs (mcorb_align.cpp), grow-only: the packed input (AlignLayout), the models and

@@ -7,7 +7,8 @@
 // before R) and the absence of the adaptive stop.  Same conventions as mcorb_sac.h: no HIP dependency -- the host-only store
 // (mcorb_rel.cpp) and k_rel_hypotheses / k_rel_score / k_rel_pick (mcorb_rel_gpu.hip) run the same code -- compiled with
 // -ffp-contract=off, fp64, one IEEE operation per operator in the order written, only + - * /, comparisons and sqrt (and what
-// null_vector uses), every loop bounded by a count whatever the data holds.
+// null_vector uses), every loop bounded by a count whatever the data holds.  The second half of the file is the opt-in polish of
+// the winner over its inliers (rel_polish_serial, k_rel_fit), a fourth stated thing.
 //   The unknown is (R, t) = b1_T_b2: X_b1 = R X_b2 + t.  Observation i is a keypoint in camera cam1 of frame 1 and one in camera
 //   cam2 of frame 2; each is the body-frame ray c + l d, c = cams[cam].t, d = cams[cam].R f with f the bearing of mcorb_sac.h, and
 //   m = c x d its moment.
@@ -463,6 +464,175 @@ inline void rel_run_serial(const RelJob &job, const RelObs *obs, RelModel *model
     out.n_models = n_models;
     for (int j = 0; j < kRelSample; j++) out.sample[j] = best >= 0 ? models[best].sample[j] : -1;
     for (int j = 0; j < 3; j++) out.pad[j] = 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// The polish of the winner over its inliers (mcorb_lmap_relative_pose_polished): mcorb_pose.h's Levenberg-Marquardt -- pose_round,
+// pose_solve, pose_retract -- on a cost that is stated here (OpenGV's optimizeModelCoefficients for this problem is not in the
+// tree and the reference does not call it).
+//   the residual of a match at P   with rel_score's a, b = R d2, w, P1 and P2 = P1 - w the 6-vector
+//                                  (a - P1 / |P1|, b / |b| - P2 / |P2|) * (1 / sqrt(threshold)): its squared length is 2 score /
+//                                  threshold, so an inlier adds less than 2 to the cost and pose_round's absolute stop at 1e-6
+//                                  is on the scale of the inlier test.  A NaN residual makes the cost NaN: the trial is rejected
+//   the Jacobian                   forward differences through pose_retract itself: column k is (r(retract(P, h e_k)) - r(P)) *
+//                                  2^20 with h = 2^-20; the six perturbed poses are computed once per pass (rel_fit_poses)
+//   the sums                       mcorb_pose.h's 28: J^T J, J^T r and the cost r.r; match i goes to lane i mod 256 in ascending
+//                                  i, the lanes fold as pose_fold
+//   the rounds                     one or two: pose_round over the members from the current pose, then all S matches are scored
+//                                  at the result with rel_score < threshold; the result replaces the current pose, flags and
+//                                  count iff its count is at least the current one, otherwise polishing ends.  Round 1's members
+//                                  are the winner's flags, round 2's are round 1's
+constexpr int kRelFitPoses = 7;                         // P and its six perturbations
+constexpr double kRelFitH = 1.0 / 1048576.0, kRelFitInvH = 1048576.0;
+constexpr int kRelFitRounds = MCORB_REL_POLISH_ROUNDS, kRelFitMaxIterations = MCORB_REL_POLISH_MAX_ITERATIONS;
+
+// what the polished path's k_rel_fit leaves for the host next to the RelOut: the layout of mcorb_rel_polish
+typedef mcorb_rel_polish RelPolish;
+
+// pose k of a pass: P itself (k = 0) or retract(P, h e_(k - 1)).  k may be a run-time value: nothing is indexed by it
+MCORB_POSE_HD void rel_fit_pose(const PoseState &P, int k, PoseState &Q)
+{
+    const double delta[6] = {k == 1 ? kRelFitH : 0.0, k == 2 ? kRelFitH : 0.0, k == 3 ? kRelFitH : 0.0,
+                             k == 4 ? kRelFitH : 0.0, k == 5 ? kRelFitH : 0.0, k == 6 ? kRelFitH : 0.0};
+    PoseState T;
+    pose_retract(P, delta, T);
+#pragma unroll
+    for (int j = 0; j < 9; j++) Q.R[j] = k == 0 ? P.R[j] : T.R[j];
+#pragma unroll
+    for (int j = 0; j < 3; j++) Q.t[j] = k == 0 ? P.t[j] : T.t[j];
+}
+
+// 1 / sqrt(threshold), the scale of the residual
+MCORB_POSE_HD double rel_fit_scale(double threshold) { return 1.0 / __builtin_sqrt(threshold); }
+
+MCORB_POSE_HD void rel_residual(const PoseState &P, const RelRays &r, double scale, double res[6])
+{
+    double b[3], Rc[3], w[3], P1[3], P2[3];
+    rel_rot(P.R, r.d2, b);
+    rel_rot(P.R, r.c2, Rc);
+    const double *a = r.d1;
+#pragma unroll
+    for (int i = 0; i < 3; i++) w[i] = (Rc[i] + P.t[i]) - r.c1[i];
+    const double aa = sac_dot(a, a), ab = sac_dot(a, b), bb = sac_dot(b, b), aw = sac_dot(a, w), bw = sac_dot(b, w);
+    const double det = ab * ab - aa * bb;
+    const double lambda = (ab * bw - bb * aw) / det;
+    const double mu = (aa * bw - ab * aw) / det;
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+        P1[i] = 0.5 * ((lambda * a[i]) + (w[i] + mu * b[i]));
+        P2[i] = P1[i] - w[i];
+    }
+    const double n1 = __builtin_sqrt(sac_dot(P1, P1)), n2 = __builtin_sqrt(sac_dot(P2, P2)), nb = __builtin_sqrt(bb);
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+        res[i] = (a[i] - P1[i] / n1) * scale;
+        res[3 + i] = (b[i] / nb - P2[i] / n2) * scale;
+    }
+}
+
+// one member into a lane's 28 sums.  poses: the kRelFitPoses poses of the pass (LDS on the device), read at constant indices;
+// s[k]: the sums, an array or k_rel_fit's column of LDS
+template <class Sums>
+MCORB_POSE_HD void rel_fit_add(const PoseState *poses, const RelRays &r, double scale, Sums &s)
+{
+    double r0[6], J[6][6];   // J[k]: column k
+    rel_residual(poses[0], r, scale, r0);
+#pragma unroll
+    for (int k = 0; k < 6; k++) {
+        double rk[6];
+        rel_residual(poses[1 + k], r, scale, rk);
+#pragma unroll
+        for (int c = 0; c < 6; c++) J[k][c] = (rk[c] - r0[c]) * kRelFitInvH;
+    }
+    int at = 0;
+#pragma unroll
+    for (int i = 0; i < 6; i++)
+#pragma unroll
+        for (int j = i; j < 6; j++, at++) {
+            double acc = J[i][0] * J[j][0];
+#pragma unroll
+            for (int c = 1; c < 6; c++) acc = acc + J[i][c] * J[j][c];
+            s[at] = s[at] + acc;
+        }
+#pragma unroll
+    for (int i = 0; i < 6; i++) {
+        double acc = J[i][0] * r0[0];
+#pragma unroll
+        for (int c = 1; c < 6; c++) acc = acc + J[i][c] * r0[c];
+        s[kPoseG + i] = s[kPoseG + i] + acc;
+    }
+    double e2 = r0[0] * r0[0];
+#pragma unroll
+    for (int c = 1; c < 6; c++) e2 = e2 + r0[c] * r0[c];
+    s[kPoseCost] = s[kPoseCost] + e2;
+}
+
+// a polish record before any round: the winner's pose and count, every round empty
+MCORB_POSE_HD void rel_polish_begin(RelPolish &rec, const PoseState &win, int32_t count)
+{
+    for (int j = 0; j < 9; j++) rec.R[j] = win.R[j];
+    for (int j = 0; j < 3; j++) rec.t[j] = win.t[j];
+    for (int k = 0; k < kRelFitRounds; k++) {
+        mcorb_rel_polish_round &q = rec.round[k];
+        q.cost_initial = q.cost_final = 0.0;
+        q.n_members = q.iterations = q.status = q.n_inliers = q.accepted = q.reserved = 0;
+    }
+    rec.n_inliers = count;
+    rec.rounds_run = 0;
+}
+
+// a pass of the serial run: the fold-ordered sums at P over the members
+struct RelFitSerialPass {
+    const RelRays *rays;
+    const uint8_t *member;
+    int S;
+    double scale;
+    double (*lanes)[kPoseSums];   // [MCORB_POSE_LANES]
+    void operator()(const PoseState &P, double sums[kPoseSums])
+    {
+        PoseState poses[kRelFitPoses];
+        for (int k = 0; k < kRelFitPoses; k++) rel_fit_pose(P, k, poses[k]);
+        for (int l = 0; l < MCORB_POSE_LANES; l++) {
+            for (int k = 0; k < kPoseSums; k++) lanes[l][k] = 0.0;
+            for (int i = l; i < S; i += MCORB_POSE_LANES)
+                if (member[i]) rel_fit_add(poses, rays[i], scale, lanes[l]);
+        }
+        pose_fold(lanes, sums);
+    }
+};
+
+// The rounds, serially: what a host-only store runs behind rel_run_serial, and the hook.  pose / count / flags: the current
+// ones (the winner's) in, the accepted ones out; member: round 1's members, S bytes, overwritten; scratch (S bytes) and lanes
+// are the caller's
+inline void rel_polish_serial(const RelRays *rays, int S, double threshold, int rounds, int max_iterations, PoseState &pose, int32_t &count,
+                              uint8_t *flags, uint8_t *member, uint8_t *scratch, double (*lanes)[kPoseSums], RelPolish &rec)
+{
+    static_assert(MCORB_POSE_LANES == 256, "match i is lane i mod 256's");
+    RelFitSerialPass pass{rays, member, S, rel_fit_scale(threshold), lanes};
+    rel_polish_begin(rec, pose, count);
+    for (int round = 0; round < rounds; round++) {
+        mcorb_rel_polish_round &q = rec.round[round];
+        int32_t members = 0;
+        for (int i = 0; i < S; i++) members += member[i] ? 1 : 0;
+        PoseState cand;
+        double c0, c1;
+        pose_round(pass, pose, max_iterations, cand, q.iterations, q.status, c0, c1);
+        int32_t n = 0;
+        for (int i = 0; i < S; i++) {
+            scratch[i] = sac_is_inlier(rel_score(cand, rays[i]), threshold) ? 1 : 0;
+            n += scratch[i];
+        }
+        q.cost_initial = pose_default_nan(c0);
+        q.cost_final = pose_default_nan(c1);
+        q.n_members = members;
+        q.n_inliers = n;
+        q.accepted = n >= count ? 1 : 0;
+        rec.rounds_run = round + 1;
+        if (!q.accepted) break;
+        pose = cand;
+        count = n;
+        for (int i = 0; i < S; i++) flags[i] = member[i] = scratch[i];
+    }
 }
 
 }  // namespace mcorb

@@ -10,6 +10,10 @@
 //                      count[H].  The additions are integer: the result does not depend on their order
 //   k_rel_pick         every workgroup finds the arg-max of count[H] for itself and writes the winner's flags for its tile of
 //                      matches; workgroup 0 writes the record to host-mapped memory
+//   k_rel_fit          the polished call only, behind a k_rel_pick whose record and flags stay in device memory: ONE workgroup of
+//                      256 -- the rounds of the header's polish (pose_round over the members, the 28 sums folded as k_pose_refine
+//                      folds them, then all S matches scored at the result), and the accepted record, its flags and the polish
+//                      record to host-mapped memory
 // The arithmetic is the header's, so the host-only store gives the same bits.  No extraction job runs this and no benchmark leg
 // times it.
 #include <hip/hip_runtime.h>
@@ -24,6 +28,7 @@ namespace mcorb {
 
 static_assert(kRelTile == 4 * 64, "four waves");
 static_assert(kRelHypBlock <= kRelTile, "a lane per hypothesis of the block adds its count");
+static_assert(kRelTile == MCORB_POSE_LANES && kPoseBlocks == 4, "k_rel_fit: a lane of the fold each");
 
 __global__ __launch_bounds__(64) void k_rel_hypotheses(const RelJob *__restrict__ job, const RelObs *__restrict__ obs,
                                                        RelModel *__restrict__ models)
@@ -124,6 +129,155 @@ __global__ __launch_bounds__(kRelTile) void k_rel_pick(const RelJob *__restrict_
         for (int j = 0; j < kRelSample; j++) out->sample[j] = best >= 0 ? models[best].sample[j] : -1;
         for (int j = 0; j < 3; j++) out->pad[j] = 0;
     }
+}
+
+// a lane's 28 sums while it walks its members: column threadIdx.x of acc[28][256] in LDS, touched by that lane alone.  In
+// registers they would be live through the seven residual evaluations of every member and the kernel would spill
+struct RelFitLaneSums {
+    double *base;
+    __device__ __forceinline__ double &operator[](int k) const { return base[k * kRelTile]; }
+};
+
+// a pass of k_rel_fit: the 28 sums at P over the members, the same bits in every lane.  Lanes 0 .. 6 leave P and its six
+// perturbations in LDS, every lane reads them at uniform addresses; lane l adds members l, l + 256, .. into its column of acc,
+// takes the 28 into registers, and the workgroup folds as k_pose_refine does.  Both barriers are met by every lane; poses and
+// part are written again only behind a barrier that every lane reaches after it has read them
+struct RelFitPass {
+    const RelJob *job;
+    const RelObs *obs;
+    const uint8_t *member;
+    int S;
+    double scale;
+    PoseState *poses;
+    double (*part)[kPoseSums];
+    double (*acc)[kRelTile];
+    __device__ __forceinline__ void operator()(const PoseState &P, double sums[kPoseSums])
+    {
+        const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+        if (t < kRelFitPoses) {
+            PoseState Q;
+            rel_fit_pose(P, t, Q);
+#pragma unroll
+            for (int j = 0; j < 9; j++) poses[t].R[j] = Q.R[j];
+#pragma unroll
+            for (int j = 0; j < 3; j++) poses[t].t[j] = Q.t[j];
+        }
+        __syncthreads();
+        const RelFitLaneSums mine{&acc[0][t]};
+#pragma unroll
+        for (int k = 0; k < kPoseSums; k++) mine[k] = 0.0;
+        for (int i = t; i < S; i += kRelTile) {
+            if (!member[i]) continue;
+            RelRays r;
+            rel_rays(job->cams, obs[i], r);
+            rel_fit_add(poses, r, scale, mine);
+        }
+        double s[kPoseSums];
+#pragma unroll
+        for (int k = 0; k < kPoseSums; k++) s[k] = mine[k];
+#pragma unroll
+        for (int stride = kPoseBlock / 2; stride >= 1; stride >>= 1)
+#pragma unroll
+            for (int k = 0; k < kPoseSums; k++) s[k] = s[k] + __shfl_down(s[k], stride, 64);
+        if (lane == 0)
+#pragma unroll
+            for (int k = 0; k < kPoseSums; k++) part[wave][k] = s[k];
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < kPoseSums; k++) sums[k] = (part[0][k] + part[1][k]) + (part[2][k] + part[3][k]);
+    }
+};
+
+// the workgroup's sum of an integer, the same in every lane; wcnt is free again on return
+__device__ __forceinline__ int rel_fit_total(int v, int32_t *wcnt)
+{
+    for (int s = 32; s >= 1; s >>= 1) v += __shfl_xor(v, s, 64);
+    if ((threadIdx.x & 63) == 0) wcnt[threadIdx.x >> 6] = v;
+    __syncthreads();
+    const int total = (wcnt[0] + wcnt[1]) + (wcnt[2] + wcnt[3]);
+    __syncthreads();
+    return total;
+}
+
+// ONE workgroup, for k_align_fit's reason: the sums are floating-point and their order is part of the definition.  pick and
+// member[0 .. S) are what k_rel_pick left in device memory; nothing host-mapped is read.  Every lane holds the same pose, count
+// and verdicts, so the rounds' control flow is uniform; a match's flags are read and written by the one lane that serves it
+__global__ __launch_bounds__(kRelTile) void k_rel_fit(const RelJob *__restrict__ job, const RelObs *__restrict__ obs, const RelOut *pick,
+                                                      uint8_t *member, int rounds, int max_iterations, RelOut *out, uint8_t *flags,
+                                                      RelPolish *polish)
+{
+    __shared__ PoseState poses[kRelFitPoses];
+    __shared__ double part[kPoseBlocks][kPoseSums];
+    __shared__ double acc[kPoseSums][kRelTile];
+    __shared__ int32_t wcnt[kPoseBlocks];
+    const int t = threadIdx.x;
+    const int S = job->S;
+    const double threshold = job->threshold;
+    PoseState cur;
+#pragma unroll
+    for (int j = 0; j < 9; j++) cur.R[j] = pick->R[j];
+#pragma unroll
+    for (int j = 0; j < 3; j++) cur.t[j] = pick->t[j];
+    int32_t count = pick->n_inliers;
+    uint8_t *curf = member, *other = member + S;
+    if (t == 0) rel_polish_begin(*polish, cur, count);
+    if (pick->best >= 0) {   // (uniform over the workgroup)
+        RelFitPass pass{job, obs, curf, S, rel_fit_scale(threshold), poses, part, acc};
+        for (int round = 0; round < rounds; round++) {
+            pass.member = curf;
+            int mine = 0;
+            for (int i = t; i < S; i += kRelTile) mine += curf[i] ? 1 : 0;
+            const int members = rel_fit_total(mine, wcnt);
+            PoseState cand;
+            double c0, c1;
+            int32_t its, status;
+            pose_round(pass, cur, max_iterations, cand, its, status, c0, c1);
+            int in = 0;
+            for (int i = t; i < S; i += kRelTile) {
+                RelRays r;
+                rel_rays(job->cams, obs[i], r);
+                const uint8_t flag = sac_is_inlier(rel_score(cand, r), threshold) ? 1 : 0;
+                other[i] = flag;
+                in += flag;
+            }
+            const int n = rel_fit_total(in, wcnt);
+            const bool accepted = n >= count;
+            if (t == 0) {
+                mcorb_rel_polish_round &q = polish->round[round];
+                q.cost_initial = pose_default_nan(c0);
+                q.cost_final = pose_default_nan(c1);
+                q.n_members = members;
+                q.iterations = its;
+                q.status = status;
+                q.n_inliers = n;
+                q.accepted = accepted ? 1 : 0;
+                polish->rounds_run = round + 1;
+            }
+            if (!accepted) break;
+            cur = cand;
+            count = n;
+            uint8_t *swap = curf;
+            curf = other;
+            other = swap;
+        }
+    }
+    for (int i = t; i < S; i += kRelTile) flags[i] = curf[i];
+    if (t == 0) {
+        for (int j = 0; j < 9; j++) out->R[j] = cur.R[j];
+        for (int j = 0; j < 3; j++) out->t[j] = cur.t[j];
+        out->status = pick->status;
+        out->n_inliers = count;
+        out->best = pick->best;
+        out->n_models = pick->n_models;
+        for (int j = 0; j < kRelSample; j++) out->sample[j] = pick->sample[j];
+        for (int j = 0; j < 3; j++) out->pad[j] = 0;
+    }
+}
+
+void launch_rel_fit(hipStream_t st, const RelFitArgs &a)
+{
+    hipLaunchKernelGGL(k_rel_fit, dim3(1), dim3(kRelTile), 0, st, a.job, a.obs, a.pick, a.member, a.rounds, a.max_iterations, a.out, a.flags,
+                       a.polish);
 }
 
 void launch_rel_hypotheses(hipStream_t st, const RelArgs &a, int H)
