@@ -1584,6 +1584,62 @@ int mcorb_ess_eval(const mcorb_track_cam *cam, int n, const double *uv1, const d
 int mcorb_ess_decompose(const double *E, double *Rp, double *Rm, double *t, const mcorb_track_cam *cam, int n, const double *uv1,
                         const double *uv2, double *depth);
 
+/* The polish of the winner over its inliers: opt-in, mcorb_lmap_essential_pose itself is as it was.  Stated, not recalled: OpenCV
+ * has no such step behind recoverPose and the reference calls none (deviation 6).
+ * rounds: 1 .. MCORB_ESS_POLISH_ROUNDS; max_iterations: the solves of a round, 1 .. MCORB_ESS_POLISH_MAX_ITERATIONS */
+#define MCORB_ESS_POLISH_ROUNDS 2
+#define MCORB_ESS_POLISH_MAX_ITERATIONS 100
+typedef struct mcorb_ess_polish_params {
+    int32_t rounds, max_iterations;
+} mcorb_ess_polish_params;
+/* a round: its members, the solves it took and its MCORB_POSE_* status, the cost (the sum over the members of err / thr^2; a NaN is
+ * the default quiet NaN) at its start and its end, the matches within the threshold (n_ransac_inliers) and those of them that
+ * pass the depth test (n_inliers) of all matches at its result, and whether that result replaced the current pose (n_inliers >=
+ * the current n_inliers) */
+typedef struct mcorb_ess_polish_round {
+    double cost_initial, cost_final;
+    int32_t n_members, iterations, status, n_ransac_inliers, n_inliers, accepted;
+} mcorb_ess_polish_round;
+/* R, t, E and both counts: the RANSAC winner's, what mcorb_lmap_essential_pose returns; round[k]: zero for a round that did not
+ * run; rounds_run: the rounds that ran, a refused one included */
+typedef struct mcorb_ess_polish {
+    double R[9], t[3], E[9];
+    mcorb_ess_polish_round round[MCORB_ESS_POLISH_ROUNDS];
+    int32_t n_ransac_inliers, n_inliers, rounds_run, reserved;
+} mcorb_ess_polish;
+/* mcorb_lmap_essential_pose followed by the polish (csrc/mcorb_ess_polish.h), fp64, one IEEE operation per operator in the order
+ * written:
+ * - the unknowns: five, delta[0 .. 2] a rotation and delta[3 .. 4] a move of t in its tangent plane (the Sampson value does not
+ *   depend on |t|).  The retraction: R' = R C(delta[0 .. 2]) with mcorb_lmap_refine_pose's Cayley matrix, t' = u / |u| with u = (t +
+ *   delta[3] b1) + delta[4] b2, b1 = (t x e_k) / |t x e_k| for the smallest |t_k| (the first of equals), b2 = t x b1.
+ * - the residual of a match: with E = [t]x R and the score's r, a, b: (r / sqrt(((a0 a0 + a1 a1) + b0 b0) + b1 b1)) * (1 / thr), thr =
+ *   threshold_px / ((fx + fy) / 2); its square is err / thr^2.
+ * - the Jacobian: forward differences through the retraction, h = 2^-20 per unknown.
+ * - the solve: mcorb_lmap_refine_pose's on five unknowns; with fewer than five members (fewer residuals than unknowns) it is
+ *   refused whatever the damping, and the round ends in MCORB_POSE_NO_STEP.
+ * - a round: mcorb_lmap_refine_pose's Levenberg-Marquardt (its damping, schedule and stops) on the five unknowns from the current
+ *   pose over the round's members, the 21 sums added in the tree of 256 lanes; then all n matches are tested at the result (err <
+ *   thr^2, strictly, and the depths strictly inside (0, distance_thresh) in both cameras), and it replaces the current pose, E,
+ *   flags and both counts iff its n_inliers is at least the current one -- otherwise polishing ends.  Round 1's members are the
+ *   winner's flags, round 2's are round 1's.  The four-candidate vote is not run again.
+ * res->R, t, E, n_ransac_inliers, n_inliers and the flags are the accepted pose's (E = [t]x R after an accepted round);
+ * cheirality, best_hypothesis, best_root, sample and n_models stay the winner's.  Without a winner (MCORB_ESS_NO_OBS,
+ * MCORB_ESS_NO_MODEL) no round runs.  A device store runs k_ess_hypotheses, k_ess_score, k_ess_pick, k_ess_finish and k_ess_fit (one
+ * workgroup) in one submission with one wait; a host-only store gives the same bits.  Refused before anything runs: what
+ * mcorb_lmap_essential_pose refuses, a NULL pp or polish, rounds or max_iterations outside their ranges */
+int mcorb_lmap_essential_pose_polished(mcorb_lmap *m, int n, const float *uv1, const float *uv2, const mcorb_track_cam *cam,
+                                       const mcorb_ess_params *params, const mcorb_ess_polish_params *pp, mcorb_ess_result *res,
+                                       uint8_t *inlier, mcorb_ess_polish *polish);
+/* mcorb_lmap_last_essential_timing with us[4]: k_ess_fit of the last polished call (0 before one) */
+int mcorb_lmap_last_essential_timing5(mcorb_lmap *m, float us[5], int *n_hyp);
+/* test hook, host: the polish of the given pose (R, t), |t| = 1, over the given members (member[n], nonzero: in) of n matches,
+ * keypoints in double as in the other mcorb_ess_* hooks.  The current counts and flags are those of (R, t) itself over all n matches
+ * (E = [t]x R).  -> the polish record (its R, t, E and counts: the pose handed in and its own), the accepted pose, its E and its
+ * flags (inlier[n]) */
+int mcorb_ess_polish_run(const mcorb_track_cam *cam, int n, const double *uv1, const double *uv2, const uint8_t *member, const double *R,
+                         const double *t, double threshold_px, double distance_thresh, const mcorb_ess_polish_params *pp,
+                         mcorb_ess_polish *polish, double *R_out, double *t_out, double *E_out, uint8_t *inlier);
+
 /* ------------------------------------------------------------------------- */
 /* Host stages exposed for the CPU test-suite (no device needed)              */
 /* ------------------------------------------------------------------------- */

@@ -1722,6 +1722,33 @@ class LocalMap:
         _lib.check(self.L.mcorb_lmap_last_essential_timing(self.h, us, C.byref(nh)))
         return tuple(us), nh.value
 
+    def essential_pose_polished(self, cam, uv1, uv2, threshold_px=1.0, distance_thresh=50.0, max_iterations=1000, seed=0, rounds=2,
+                                polish_iterations=10):
+        """essential_pose followed by the polish of the winner over its inliers: `rounds` (1 .. 2) rounds of refine_pose's
+        Levenberg-Marquardt on five unknowns (a rotation and a move of t on the unit sphere), at most polish_iterations (1 .. 100)
+        solves each, on the Sampson residual r / sqrt(a0 a0 + a1 a1 + b0 b0 + b1 b1) / thr of the members at E = [t]x R; after a round
+        all matches are tested at its result (the threshold and the depth test), which replaces the current pose, E, flags and
+        counts iff its n_inliers is at least the current one.  -> (EssentialResult, EssentialPolish): the result's R, t, E,
+        n_ransac_inliers, n_inliers and inliers are the accepted pose's; cheirality, best_hypothesis, best_root, sample and n_models
+        the winner's.  A device store adds k_ess_fit to the submission; a host-only store gives the same bits"""
+        uv1 = np.ascontiguousarray(uv1, np.float32).reshape(-1, 2)
+        n = len(uv1)
+        uv2 = np.ascontiguousarray(uv2, np.float32).reshape(n, 2)
+        par, pp = _lib.EssParams(), _lib.EssPolishParams(int(rounds), int(polish_iterations))
+        par.threshold_px, par.distance_thresh = float(threshold_px), float(distance_thresh)
+        par.seed, par.max_iterations = int(seed) & 0xFFFFFFFFFFFFFFFF, int(max_iterations)
+        res, rec, flags = _lib.EssResultC(), _lib.EssPolishC(), np.zeros(max(n, 1), np.uint8)
+        _lib.check(self.L.mcorb_lmap_essential_pose_polished(self.h, n, uv1.ctypes.data, uv2.ctypes.data, _pose_cams(cam)[1], C.byref(par),
+                                                             C.byref(pp), C.byref(res), flags.ctypes.data, C.byref(rec)))
+        return EssentialResult(res, flags[:n]), EssentialPolish(rec)
+
+    def last_essential_timing5(self):
+        """((us of k_ess_hypotheses, k_ess_score, k_ess_pick, k_ess_finish of the last essential call, k_ess_fit of the last polished
+        one), hypotheses); a device store"""
+        us, nh = (C.c_float * 5)(), C.c_int(0)
+        _lib.check(self.L.mcorb_lmap_last_essential_timing5(self.h, us, C.byref(nh)))
+        return tuple(us), nh.value
+
     def last_essential_counts(self):
         """test hook: (counts, has a model, E 9 doubles) of all (hypothesis, root) slots of the last essential_pose() that ran
         any; slot 10 h + c is root c of hypothesis h"""
@@ -1880,6 +1907,23 @@ class EssentialResult:
 
 ESS_OK, ESS_NO_OBS, ESS_NO_MODEL = 0, 1, 2
 ESS_MAX_ITERATIONS, ESS_SAMPLE, ESS_MAX_ROOTS = 16384, 5, 10
+ESS_POLISH_ROUNDS, ESS_POLISH_MAX_ITERATIONS = 2, 100
+
+
+class EssentialPolish:
+    """the polish record of LocalMap.essential_pose_polished and ess_polish_run: R (3 x 3), t, E (3 x 3), n_ransac_inliers and
+    n_inliers of the pose the polish began from (the RANSAC winner's); rounds_run; rounds: per round that ran a dict of n_members,
+    iterations, status (POSE_*), cost_initial, cost_final, n_ransac_inliers and n_inliers (of all matches at the round's result)
+    and accepted"""
+
+    def __init__(self, rec):
+        self.R = np.array(rec.R[:], np.float64).reshape(3, 3)
+        self.t = np.array(rec.t[:], np.float64)
+        self.E = np.array(rec.E[:], np.float64).reshape(3, 3)
+        self.n_ransac_inliers, self.n_inliers, self.rounds_run = rec.n_ransac_inliers, rec.n_inliers, rec.rounds_run
+        self.rounds = [dict(n_members=q.n_members, iterations=q.iterations, status=q.status, cost_initial=q.cost_initial,
+                            cost_final=q.cost_final, n_ransac_inliers=q.n_ransac_inliers, n_inliers=q.n_inliers, accepted=bool(q.accepted))
+                       for q in rec.round[:rec.rounds_run]]
 
 
 class AlignResult:
@@ -2026,6 +2070,24 @@ def ess_decompose(E, cam=None, uv1=None, uv2=None):
     _lib.check(_lib.load().mcorb_ess_decompose(E.ctypes.data, Rp.ctypes.data, Rm.ctypes.data, t.ctypes.data, ca, n, a1, a2, depth.ctypes.data))
     cands = (Rp.reshape(3, 3), Rm.reshape(3, 3), t)
     return cands if cam is None else (cands, depth[:n])
+
+
+def ess_polish_run(cam, R, t, uv1, uv2, member, threshold_px=1.0, distance_thresh=50.0, rounds=2, polish_iterations=10):
+    """test hook (host): the polish of the pose (R, t) = c1_T_c2, |t| = 1, over the matches with member[i], keypoints as doubles; the
+    current counts and flags are the pose's own over all matches -> (R 3 x 3, t, E 3 x 3, inliers, EssentialPolish) of the accepted
+    pose"""
+    uv1 = np.ascontiguousarray(uv1, np.float64).reshape(-1, 2)
+    n = len(uv1)
+    uv2 = np.ascontiguousarray(uv2, np.float64).reshape(n, 2)
+    R = np.ascontiguousarray(R, np.float64).reshape(9)
+    t = np.ascontiguousarray(t, np.float64).reshape(3)
+    member = np.ascontiguousarray(member, np.uint8).reshape(n)
+    pp, rec = _lib.EssPolishParams(int(rounds), int(polish_iterations)), _lib.EssPolishC()
+    Ro, to, Eo, flags = np.zeros(9), np.zeros(3), np.zeros(9), np.zeros(max(n, 1), np.uint8)
+    _lib.check(_lib.load().mcorb_ess_polish_run(_pose_cams(cam)[1], n, uv1.ctypes.data, uv2.ctypes.data, member.ctypes.data, R.ctypes.data,
+                                                t.ctypes.data, float(threshold_px), float(distance_thresh), C.byref(pp), C.byref(rec),
+                                                Ro.ctypes.data, to.ctypes.data, Eo.ctypes.data, flags.ctypes.data))
+    return Ro.reshape(3, 3), to, Eo.reshape(3, 3), flags[:n].astype(bool), EssentialPolish(rec)
 
 
 def sac_threshold(K00_02):

@@ -158,6 +158,20 @@ class EssResultC(C.Structure):
                 ("sample", C.c_int32 * 5), ("n_models", C.c_int32), ("cheirality", C.c_int32 * 4), ("reserved", C.c_int32)]
 
 
+class EssPolishParams(C.Structure):
+    _fields_ = [("rounds", C.c_int32), ("max_iterations", C.c_int32)]
+
+
+class EssPolishRoundC(C.Structure):
+    _fields_ = [("cost_initial", C.c_double), ("cost_final", C.c_double), ("n_members", C.c_int32), ("iterations", C.c_int32),
+                ("status", C.c_int32), ("n_ransac_inliers", C.c_int32), ("n_inliers", C.c_int32), ("accepted", C.c_int32)]
+
+
+class EssPolishC(C.Structure):
+    _fields_ = [("R", C.c_double * 9), ("t", C.c_double * 3), ("E", C.c_double * 9), ("round", EssPolishRoundC * 2),
+                ("n_ransac_inliers", C.c_int32), ("n_inliers", C.c_int32), ("rounds_run", C.c_int32), ("reserved", C.c_int32)]
+
+
 class AlignParams(C.Structure):
     _fields_ = [("threshold", C.c_double), ("inlier_dist", C.c_double), ("seed", C.c_uint64), ("max_iterations", C.c_int32),
                 ("mode", C.c_int32), ("refit", C.c_int32), ("reserved", C.c_int32)]
@@ -379,6 +393,11 @@ SIGNATURES = {
     "mcorb_lmap_essential_pose": (_i, [_vp, _i, _vp, _vp, _vp, C.POINTER(EssParams), C.POINTER(EssResultC), _vp]),
     "mcorb_lmap_last_essential_timing": (_i, [_vp, C.POINTER(_f), C.POINTER(_i)]),
     "mcorb_lmap_last_essential_counts": (_i, [_vp, _vp, _vp, _vp, _i, C.POINTER(_i)]),
+    "mcorb_lmap_essential_pose_polished": (_i, [_vp, _i, _vp, _vp, _vp, C.POINTER(EssParams), C.POINTER(EssPolishParams),
+                                                C.POINTER(EssResultC), _vp, C.POINTER(EssPolishC)]),
+    "mcorb_lmap_last_essential_timing5": (_i, [_vp, C.POINTER(_f), C.POINTER(_i)]),
+    "mcorb_ess_polish_run": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, C.c_double, C.c_double, C.POINTER(EssPolishParams),
+                                  C.POINTER(EssPolishC), _vp, _vp, _vp, _vp]),
     "mcorb_ess_solve": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "mcorb_ess_eval": (_i, [_vp, _i, _vp, _vp, _vp, _vp]),
     "mcorb_ess_decompose": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp]),

@@ -4,7 +4,9 @@
 // store's stream with one wait; the record and the flags land in host-mapped memory.  A host-only store runs the header
 // (mcorb_ess.h) serially, so the two agree bit for bit.  Recalled from OpenCV: the Sampson distance and the cheirality vote;
 // stated: the draws, the five-point solver, no adaptive stop, the midpoint inside the vote, the rotations from E (DESIGN.md
-// section 9m).
+// section 9m).  mcorb_lmap_essential_pose_polished is the same submission with k_ess_finish's record and flags kept in device memory
+// and k_ess_fit behind it: the polish of the winner over its inliers (mcorb_ess_polish.h), stated too.  mcorb_lmap_essential_pose
+// itself is as it was.
 #include <math.h>
 #include <string.h>
 
@@ -34,6 +36,39 @@ void fill_job(EssJob &job, const mcorb_track_cam &cam)
 void fill_obs(EssObs *obs, int n, const float *uv1, const float *uv2)
 {
     for (int i = 0; i < n; i++) obs[i] = EssObs{uv1[2 * i], uv1[2 * i + 1], uv2[2 * i], uv2[2 * i + 1]};
+}
+
+int check_polish(const mcorb_ess_polish_params *pp)
+{
+    if (pp->rounds < 1 || pp->rounds > MCORB_ESS_POLISH_ROUNDS) return fail(MCORB_E_ARG, "1 .. MCORB_ESS_POLISH_ROUNDS rounds");
+    if (pp->max_iterations < 1 || pp->max_iterations > MCORB_ESS_POLISH_MAX_ITERATIONS)
+        return fail(MCORB_E_ARG, "1 .. MCORB_ESS_POLISH_MAX_ITERATIONS polish iterations");
+    return MCORB_OK;
+}
+
+// the polish record of a call in which no round runs
+void begin_record(EssPolish &rec, const EssOut &out)
+{
+    PoseState P;
+    memcpy(P.R, out.R, sizeof(P.R));
+    memcpy(P.t, out.t, sizeof(P.t));
+    ess_polish_begin(rec, P, out.E, out.n_ransac_inliers, out.n_inliers);
+}
+
+// ess_polish_serial with its scratch, on a record: out's pose, E and counts and the flags are the current ones in, the accepted
+// ones out; member: round 1's members, a copy the rounds overwrite
+void polish_host(const EssPt *pts, int S, double threshold2, double distance, double inv_thr, const mcorb_ess_polish_params &pp, EssOut &out,
+                 uint8_t *flags, std::vector<uint8_t> member, EssPolish &rec)
+{
+    std::vector<uint8_t> scratch((size_t)S);
+    std::vector<double> lanes((size_t)MCORB_POSE_LANES * kEssFitSums);
+    PoseState P;
+    memcpy(P.R, out.R, sizeof(P.R));
+    memcpy(P.t, out.t, sizeof(P.t));
+    ess_polish_serial(pts, S, threshold2, distance, inv_thr, pp.rounds, pp.max_iterations, P, out.E, out.n_ransac_inliers, out.n_inliers, flags,
+                      member.data(), scratch.data(), reinterpret_cast<double (*)[kEssFitSums]>(lanes.data()), rec);
+    memcpy(out.R, P.R, sizeof(P.R));
+    memcpy(out.t, P.t, sizeof(P.t));
 }
 
 }  // namespace
@@ -148,6 +183,178 @@ int mcorb_lmap_last_essential_timing(mcorb_lmap *m, float us[4], int *n_hyp)
     std::lock_guard<std::mutex> lk(m->mu);
     for (int k = 0; k < 4; k++) us[k] = m->ess.kernels.us[k];
     if (n_hyp) *n_hyp = m->ess.last_hyp;
+    return MCORB_OK;
+}
+
+int mcorb_lmap_essential_pose_polished(mcorb_lmap *m, int n, const float *uv1, const float *uv2, const mcorb_track_cam *cam,
+                                       const mcorb_ess_params *params, const mcorb_ess_polish_params *pp, mcorb_ess_result *res,
+                                       uint8_t *inlier, mcorb_ess_polish *polish)
+{
+    TRY(check_lmap(m, "lmap essential_pose_polished"));
+    if (!params || !pp || !res || !polish || !cam || n < 0 || (n && (!uv1 || !uv2))) return fail(MCORB_E_ARG, "bad argument");
+    if (!positive(params->threshold_px)) return fail(MCORB_E_ARG, "a threshold that is not finite and positive");
+    if (!positive(params->distance_thresh)) return fail(MCORB_E_ARG, "a distance that is not finite and positive");
+    if (!positive(cam->fx) || !positive(cam->fy)) return fail(MCORB_E_ARG, "a focal length that is not finite and positive");
+    if (params->max_iterations < 1 || params->max_iterations > MCORB_ESS_MAX_ITERATIONS)
+        return fail(MCORB_E_ARG, "1 .. MCORB_ESS_MAX_ITERATIONS iterations");
+    TRY(check_polish(pp));
+    std::lock_guard<std::mutex> lk(m->mu);
+    if (m->track.pending.load()) return fail(MCORB_E_STATE, "a submitted tracking call has not been waited for");
+
+    const int S = n, H = params->max_iterations;
+    const size_t slots = (size_t)H * kEssRoots;
+    EssJob job;
+    fill_job(job, *cam);
+    const double thr = params->threshold_px / ((cam->fx + cam->fy) / 2.0);
+    job.threshold2 = thr * thr;
+    job.distance = params->distance_thresh;
+    job.seed = params->seed;
+    job.S = S;
+    job.H = H;
+    const double inv_thr = ess_fit_scale(params->threshold_px, cam->fx, cam->fy);
+
+    EssOut out;
+    EssPolish rec;
+    std::vector<uint8_t> flags((size_t)n);
+    mcorb_lmap::Ess &b = m->ess;
+    if (S == 0) {
+        memset(&out, 0, sizeof(out));
+        out.R[0] = out.R[4] = out.R[8] = 1.0;
+        out.status = MCORB_ESS_NO_OBS;
+        out.best_hypothesis = out.best_root = -1;
+        for (int j = 0; j < kEssSample; j++) out.sample[j] = -1;
+        begin_record(rec, out);
+    } else if (m->device < 0) {
+        std::vector<EssObs> obs((size_t)n);
+        fill_obs(obs.data(), n, uv1, uv2);
+        std::vector<int32_t> samples((size_t)H * kEssSample), count(slots);
+        std::vector<EssPt> pts((size_t)S);
+        b.host_models.resize(slots);
+        ess_run_serial(job, obs.data(), b.host_models.data(), samples.data(), count.data(), pts.data(), out, flags.data());
+        b.host_count.swap(count);
+        b.last_hyp = H;
+        if (out.status == MCORB_ESS_OK)
+            polish_host(pts.data(), S, job.threshold2, job.distance, inv_thr, *pp, out, flags.data(), flags, rec);
+        else
+            begin_record(rec, out);
+    } else {
+        HIPCHK(hipSetDevice(m->device));
+        (void)hipGetLastError();   // (a stale error of this thread is not this call's)
+        const EssLayout L((size_t)n);
+        TRY(b.reserve(L.p.total, (size_t)n, (size_t)H));
+        TRY(b.reserve_polish((size_t)n));
+        *b.in.host<EssJob>(L.job) = job;
+        fill_obs(b.in.host<EssObs>(L.obs), n, uv1, uv2);
+        hipStream_t st = m->st;
+        TRY(b.in.upload(st, L.p.total));
+        HIPCHK(hipMemsetAsync(b.d_count, 0, (slots + 4) * sizeof(int32_t), st));   // (the four votes lie behind the counts)
+        EssArgs a;
+        a.job = b.in.dev<const EssJob>(L.job);
+        a.obs = b.in.dev<const EssObs>(L.obs);
+        a.models = b.d_models;
+        a.samples = b.d_samples;
+        a.valid = b.d_valid;
+        a.count = b.d_count;
+        a.cheir = b.d_count.get() + slots;
+        a.pick = b.d_pick;
+        a.out = b.d_out;        // (k_ess_finish's record and flags stay in device memory: k_ess_fit reads nothing across the link)
+        a.flags = b.d_member;
+        const EssFitArgs f{a.job, a.obs, b.d_out, b.d_member, pp->rounds, pp->max_iterations, inv_thr, b.h_out, b.h_flags, b.h_polish};
+        TRY(b.kernels.mark(st, 0));
+        launch_ess_hypotheses(st, a, H);
+        hipError_t launched = hipGetLastError();
+        TRY(b.kernels.mark(st, 1));
+        launch_ess_score(st, a, S, H);
+        if (launched == hipSuccess) launched = hipGetLastError();
+        TRY(b.kernels.mark(st, 2));
+        launch_ess_pick(st, a, S);
+        if (launched == hipSuccess) launched = hipGetLastError();
+        TRY(b.kernels.mark(st, 3));
+        launch_ess_finish(st, a, S);
+        if (launched == hipSuccess) launched = hipGetLastError();
+        TRY(b.kernels.mark(st, 4));
+        TRY(b.fit.mark(st, 0));
+        launch_ess_fit(st, f);
+        if (launched == hipSuccess) launched = hipGetLastError();
+        TRY(b.fit.mark(st, 1));
+        HIPCHK(hipStreamSynchronize(st));
+        HIPCHK(launched);
+        b.kernels.read();
+        b.fit.read();
+        b.last_hyp = H;
+        out = *b.h_out.get();
+        rec = *b.h_polish.get();
+        memcpy(flags.data(), b.h_flags.get(), (size_t)n);
+    }
+
+    memset(res, 0, sizeof(*res));
+    memcpy(res->R, out.R, sizeof(out.R));
+    memcpy(res->t, out.t, sizeof(out.t));
+    memcpy(res->E, out.E, sizeof(out.E));
+    res->status = out.status;
+    res->n_matches = n;
+    res->n_ransac_inliers = out.n_ransac_inliers;
+    res->n_inliers = out.n_inliers;
+    res->best_hypothesis = out.best_hypothesis;
+    res->best_root = out.best_root;
+    memcpy(res->sample, out.sample, sizeof(res->sample));
+    res->n_models = out.n_models;
+    memcpy(res->cheirality, out.cheirality, sizeof(res->cheirality));
+    *polish = rec;
+    if (inlier && n) memcpy(inlier, flags.data(), (size_t)n);
+    return MCORB_OK;
+}
+
+int mcorb_lmap_last_essential_timing5(mcorb_lmap *m, float us[5], int *n_hyp)
+{
+    TRY(check_lmap_handle(m, "lmap last_essential_timing5"));
+    if (!us) return fail(MCORB_E_ARG, "bad argument");
+    std::lock_guard<std::mutex> lk(m->mu);
+    for (int k = 0; k < 4; k++) us[k] = m->ess.kernels.us[k];
+    us[4] = m->ess.fit.us[0];
+    if (n_hyp) *n_hyp = m->ess.last_hyp;
+    return MCORB_OK;
+}
+
+int mcorb_ess_polish_run(const mcorb_track_cam *cam, int n, const double *uv1, const double *uv2, const uint8_t *member, const double *R,
+                         const double *t, double threshold_px, double distance_thresh, const mcorb_ess_polish_params *pp,
+                         mcorb_ess_polish *polish, double *R_out, double *t_out, double *E_out, uint8_t *inlier)
+{
+    if (!cam || n < 0 || !R || !t || !pp || !polish || !R_out || !t_out || !E_out || (n && (!uv1 || !uv2 || !member || !inlier)))
+        return fail(MCORB_E_ARG, "bad argument");
+    if (!positive(threshold_px)) return fail(MCORB_E_ARG, "a threshold that is not finite and positive");
+    if (!positive(distance_thresh)) return fail(MCORB_E_ARG, "a distance that is not finite and positive");
+    if (!positive(cam->fx) || !positive(cam->fy)) return fail(MCORB_E_ARG, "a focal length that is not finite and positive");
+    TRY(check_polish(pp));
+    EssJob job;
+    fill_job(job, *cam);
+    const double thr = threshold_px / ((cam->fx + cam->fy) / 2.0);
+    job.threshold2 = thr * thr;
+    job.distance = distance_thresh;
+    std::vector<EssPt> pts((size_t)n);
+    for (int i = 0; i < n; i++) ess_point(job, uv1[2 * (size_t)i], uv1[2 * (size_t)i + 1], uv2[2 * (size_t)i], uv2[2 * (size_t)i + 1], pts[i]);
+    EssOut out;
+    memset(&out, 0, sizeof(out));
+    memcpy(out.R, R, sizeof(out.R));
+    memcpy(out.t, t, sizeof(out.t));
+    PoseState P;
+    memcpy(P.R, R, sizeof(P.R));
+    memcpy(P.t, t, sizeof(P.t));
+    ess_fit_E(P, out.E);
+    std::vector<uint8_t> flags((size_t)n), mem((size_t)n);
+    for (int i = 0; i < n; i++) {
+        bool within, flag;
+        ess_fit_test(P, out.E, pts[i], job.threshold2, job.distance, within, flag);
+        flags[i] = flag ? 1 : 0;
+        out.n_ransac_inliers += within ? 1 : 0;
+        out.n_inliers += flag ? 1 : 0;
+        mem[i] = member[i] ? 1 : 0;
+    }
+    polish_host(pts.data(), n, job.threshold2, job.distance, ess_fit_scale(threshold_px, cam->fx, cam->fy), *pp, out, flags.data(), mem, *polish);
+    memcpy(R_out, out.R, sizeof(out.R));
+    memcpy(t_out, out.t, sizeof(out.t));
+    memcpy(E_out, out.E, sizeof(out.E));
+    if (n) memcpy(inlier, flags.data(), (size_t)n);
     return MCORB_OK;
 }
 

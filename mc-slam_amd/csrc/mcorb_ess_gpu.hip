@@ -15,6 +15,10 @@
 //                      winner -- the same bits in every workgroup -- and adds its matches' four votes to four integers;
 //                      workgroup 0 leaves the winner and its candidates for k_ess_finish
 //   k_ess_finish       reads the four votes, writes the flags of its tile; workgroup 0 writes the record to host-mapped memory
+//   k_ess_fit          the polished call only, behind a k_ess_finish whose record and flags stay in device memory: ONE workgroup of
+//                      256 -- the rounds of mcorb_ess_polish.h (ess_fit_round over the members, the 21 sums folded as
+//                      k_pose_refine folds them, then all S matches tested at the result), and the accepted record, its flags
+//                      and the polish record to host-mapped memory
 // No extraction job runs this and no benchmark leg times it.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -28,6 +32,7 @@ namespace mcorb {
 
 static_assert(kEssTile == 4 * 64, "four waves");
 static_assert(kEssSlotBlock <= kEssTile, "a lane per slot of the block adds its count");
+static_assert(kEssTile == MCORB_POSE_LANES && kPoseBlocks == 4, "k_ess_fit: a lane of the fold each");
 static_assert(kEssLanes >= kEssNodes && kEssLanes >= kEssRoots + 1 && 64 % kEssLanes == 0, "a lane per node, per bracket and per root");
 
 // what the lanes of one hypothesis share
@@ -241,6 +246,166 @@ __global__ __launch_bounds__(kEssTile) void k_ess_finish(const EssJob *__restric
         flags[i] = flag;
     }
     if (blockIdx.x == 0 && t == 0) ess_finish(P, votes, samples, *out);
+}
+
+// a pass of k_ess_fit: the 21 sums at P over the members, the same bits in every lane.  Lanes 0 .. 5 leave E of P and of its five
+// perturbations in LDS; every lane takes the 54 numbers into registers at uniform addresses (broadcasts), walks members t, t + 256,
+// .. with its 21 sums in registers, and the workgroup folds as k_pose_refine does.  A member's EssPt is computed again from its
+// EssObs in every pass, as k_ess_score does it: four divisions next to the six residuals' six divisions and six square roots,
+// against a buffer of 32 bytes per match that would follow n and be read back in its place.  Both barriers are met by every lane;
+// Es and part are written again only behind a barrier that every lane reaches after it has read them
+struct EssFitPass {
+    const EssJob *job;
+    const EssObs *obs;
+    const uint8_t *member;
+    int S;
+    double inv_thr;
+    double (*Es)[9];
+    double (*part)[kEssFitSums];
+    __device__ __forceinline__ void operator()(const PoseState &P, double sums[kEssFitSums])
+    {
+        const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+        if (t < kEssFitPoses) {
+            PoseState Q;
+            double E[9];
+            ess_fit_pose(P, t, Q);
+            ess_fit_E(Q, E);
+#pragma unroll
+            for (int j = 0; j < 9; j++) Es[t][j] = E[j];
+        }
+        __syncthreads();
+        double E[kEssFitPoses][9], s[kEssFitSums];
+#pragma unroll
+        for (int k = 0; k < kEssFitPoses; k++)
+#pragma unroll
+            for (int j = 0; j < 9; j++) E[k][j] = Es[k][j];
+#pragma unroll
+        for (int k = 0; k < kEssFitSums; k++) s[k] = 0.0;
+        for (int i = t; i < S; i += kEssTile) {
+            if (!member[i]) continue;
+            EssPt p;
+            ess_point_of(*job, obs[i], p);
+            ess_fit_add(E, p, inv_thr, s);
+        }
+#pragma unroll
+        for (int stride = kPoseBlock / 2; stride >= 1; stride >>= 1)
+#pragma unroll
+            for (int k = 0; k < kEssFitSums; k++) s[k] = s[k] + __shfl_down(s[k], stride, 64);
+        if (lane == 0)
+#pragma unroll
+            for (int k = 0; k < kEssFitSums; k++) part[wave][k] = s[k];
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < kEssFitSums; k++) sums[k] = (part[0][k] + part[1][k]) + (part[2][k] + part[3][k]);
+    }
+};
+
+// the workgroup's sum of an integer, the same in every lane; wcnt is free again on return
+__device__ __forceinline__ int ess_fit_total(int v, int32_t *wcnt)
+{
+    for (int s = 32; s >= 1; s >>= 1) v += __shfl_xor(v, s, 64);
+    if ((threadIdx.x & 63) == 0) wcnt[threadIdx.x >> 6] = v;
+    __syncthreads();
+    const int total = (wcnt[0] + wcnt[1]) + (wcnt[2] + wcnt[3]);
+    __syncthreads();
+    return total;
+}
+
+// The polished call only, behind a k_ess_finish whose record and flags stay in device memory.  ONE workgroup, for k_align_fit's
+// reason: the sums are floating-point and their order is part of the definition.  pick and member[0 .. S) are what k_ess_finish
+// left; nothing host-mapped is read.  Every lane holds the same pose, counts and verdicts, so the rounds' control flow is uniform;
+// a match's flags are read and written by the one lane that serves it, in member[0 .. S) and member[S .. 2 S), which swap on
+// acceptance
+__global__ __launch_bounds__(kEssTile) void k_ess_fit(const EssJob *__restrict__ job, const EssObs *__restrict__ obs, const EssOut *pick,
+                                                      uint8_t *member, int rounds, int max_iterations, double inv_thr, EssOut *out,
+                                                      uint8_t *flags, EssPolish *polish)
+{
+    __shared__ double Es[kEssFitPoses][9];
+    __shared__ double part[kPoseBlocks][kEssFitSums];
+    __shared__ int32_t wcnt[kPoseBlocks];
+    const int t = threadIdx.x;
+    const int S = job->S;
+    const double threshold2 = job->threshold2, distance = job->distance;
+    PoseState cur;
+    double E[9];
+#pragma unroll
+    for (int j = 0; j < 9; j++) cur.R[j] = pick->R[j];
+#pragma unroll
+    for (int j = 0; j < 3; j++) cur.t[j] = pick->t[j];
+#pragma unroll
+    for (int j = 0; j < 9; j++) E[j] = pick->E[j];
+    int32_t n_ransac = pick->n_ransac_inliers, count = pick->n_inliers;
+    uint8_t *curf = member, *other = member + S;
+    if (t == 0) ess_polish_begin(*polish, cur, E, n_ransac, count);
+    if (pick->status == MCORB_ESS_OK) {   // (uniform over the workgroup)
+        EssFitPass pass{job, obs, curf, S, inv_thr, Es, part};
+        for (int round = 0; round < rounds; round++) {
+            pass.member = curf;
+            int mine = 0;
+            for (int i = t; i < S; i += kEssTile) mine += curf[i] ? 1 : 0;
+            const int members = ess_fit_total(mine, wcnt);
+            PoseState cand;
+            double c0, c1, Ec[9];
+            int32_t its, status;
+            ess_fit_round(pass, cur, members, max_iterations, cand, its, status, c0, c1);
+            ess_fit_E(cand, Ec);
+            int within_mine = 0, in = 0;
+            for (int i = t; i < S; i += kEssTile) {
+                EssPt p;
+                ess_point_of(*job, obs[i], p);
+                bool within, flag;
+                ess_fit_test(cand, Ec, p, threshold2, distance, within, flag);
+                other[i] = flag ? 1 : 0;
+                within_mine += within ? 1 : 0;
+                in += flag ? 1 : 0;
+            }
+            const int nr = ess_fit_total(within_mine, wcnt);
+            const int n = ess_fit_total(in, wcnt);
+            const bool accepted = n >= count;
+            if (t == 0) {
+                mcorb_ess_polish_round &q = polish->round[round];
+                q.cost_initial = pose_default_nan(c0);
+                q.cost_final = pose_default_nan(c1);
+                q.n_members = members;
+                q.iterations = its;
+                q.status = status;
+                q.n_ransac_inliers = nr;
+                q.n_inliers = n;
+                q.accepted = accepted ? 1 : 0;
+                polish->rounds_run = round + 1;
+            }
+            if (!accepted) break;
+            cur = cand;
+#pragma unroll
+            for (int j = 0; j < 9; j++) E[j] = Ec[j];
+            n_ransac = nr;
+            count = n;
+            uint8_t *swap = curf;
+            curf = other;
+            other = swap;
+        }
+    }
+    for (int i = t; i < S; i += kEssTile) flags[i] = curf[i];
+    if (t == 0) {
+        for (int j = 0; j < 9; j++) out->R[j] = cur.R[j];
+        for (int j = 0; j < 3; j++) out->t[j] = cur.t[j];
+        for (int j = 0; j < 9; j++) out->E[j] = E[j];
+        out->status = pick->status;
+        out->n_ransac_inliers = n_ransac;
+        out->n_inliers = count;
+        out->best_hypothesis = pick->best_hypothesis;
+        out->best_root = pick->best_root;
+        for (int j = 0; j < kEssSample; j++) out->sample[j] = pick->sample[j];
+        out->n_models = pick->n_models;
+        for (int c = 0; c < 4; c++) out->cheirality[c] = pick->cheirality[c];
+        out->pad = 0;
+    }
+}
+
+void launch_ess_fit(hipStream_t st, const EssFitArgs &a)
+{
+    hipLaunchKernelGGL(k_ess_fit, dim3(1), dim3(kEssTile), 0, st, a.job, a.obs, a.pick, a.member, a.rounds, a.max_iterations, a.inv_thr, a.out,
+                       a.flags, a.polish);
 }
 
 void launch_ess_hypotheses(hipStream_t st, const EssArgs &a, int H)

@@ -11,6 +11,7 @@
 #include "mcorb_mapping_new.h"
 #include "mcorb_pose.h"
 #include "mcorb_ess.h"
+#include "mcorb_ess_polish.h"
 #include "mcorb_rel.h"
 #include "mcorb_sac.h"
 #include "mcorb_signal.h"
@@ -319,6 +320,21 @@ void launch_ess_hypotheses(hipStream_t st, const EssArgs &a, int H);
 void launch_ess_score(hipStream_t st, const EssArgs &a, int S, int H);
 void launch_ess_pick(hipStream_t st, const EssArgs &a, int S);
 void launch_ess_finish(hipStream_t st, const EssArgs &a, int S);
+// the polish behind a k_ess_finish whose out and flags are device memory (pick; member[0 .. S)): k_ess_fit, one workgroup -- the
+// rounds of mcorb_ess_polish.h over the members, member[S .. 2 S) the other set of flags, then the accepted record, its flags and
+// the polish record to host-mapped memory.  inv_thr: ess_fit_scale of the call
+struct EssFitArgs {
+    const EssJob *job;
+    const EssObs *obs;
+    const EssOut *pick;
+    uint8_t *member;
+    int32_t rounds, max_iterations;
+    double inv_thr;
+    EssOut *out;
+    uint8_t *flags;
+    EssPolish *polish;
+};
+void launch_ess_fit(hipStream_t st, const EssFitArgs &a);
 
 // the pose between two frames from 3D-3D pairs (mcorb_align_gpu.hip).  job, p2 and p1 or lids1 (the n pairs; lids1: frame 1's
 // points are geom's, 6 doubles per slot) are device memory.  Mode 1: k_align_hypotheses -- one lane per hypothesis, models[H];

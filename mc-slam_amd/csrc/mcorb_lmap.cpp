@@ -139,6 +139,7 @@ int mcorb_lmap_create(mcorb_vocab *v, int device, int max_landmarks, int max_can
         TRY(m->rel.kernels.create());
         TRY(m->rel.fit.create());
         TRY(m->ess.kernels.create());
+        TRY(m->ess.fit.create());
         TRY(m->align.sac.create());
         TRY(m->align.fit.create());
         TRY(m->init.kernels.create());

@@ -344,6 +344,18 @@ struct mcorb_lmap {
             TRY(h_out.grow(1, mcorb::kHostMapped));
             return h_flags.grow(n, mcorb::kHostMapped);
         }
+        // mcorb_lmap_essential_pose_polished: k_ess_finish's record and flags stay in device memory (d_member: the current flags
+        // and the other set, 2 n), k_ess_fit writes h_out, h_flags and the polish record
+        mcorb::DevBuf<mcorb::EssOut> d_out;
+        mcorb::DevBuf<uint8_t> d_member;
+        mcorb::HostBuf<mcorb::EssPolish> h_polish;
+        mcorb::Spans<1> fit;                    // k_ess_fit
+        int reserve_polish(size_t n)
+        {
+            TRY(d_out.grow(1));
+            TRY(d_member.grow(2 * n));
+            return h_polish.grow(1, mcorb::kHostMapped);
+        }
     } ess;
 
     // scratch of mcorb_lmap_initialize (mcorb_init.cpp), grow-only: the packed input (InitLayout), k_init_triangulate's records,
