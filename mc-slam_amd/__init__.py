@@ -1641,6 +1641,10 @@ class LocalMap:
         hypotheses of 17 matches each (1 .. REL_MAX_ITERATIONS), all examined; seed: of the draws.  -> RelResult.  A device store
         runs k_rel_hypotheses, k_rel_score and k_rel_pick in one submission; a host-only store the same arithmetic serially, with
         the same bits.  The store's landmarks are not touched"""
+        return self._relative(cams, cam1, uv1, cam2, uv2, threshold, max_iterations, seed)
+
+    def _relative(self, cams, cam1, uv1, cam2, uv2, threshold, max_iterations, seed, polish=None):
+        """relative_pose, or with polish = (rounds, polish_iterations) relative_pose_polished: the arrays, the parameters, the call"""
         cam1 = np.ascontiguousarray(cam1, np.int32).reshape(-1)
         n = len(cam1)
         cam2 = np.ascontiguousarray(cam2, np.int32).reshape(n)
@@ -1650,9 +1654,13 @@ class LocalMap:
         par = _lib.RelParams()
         par.threshold, par.seed, par.max_iterations = float(threshold), int(seed) & 0xFFFFFFFFFFFFFFFF, int(max_iterations)
         res, flags = _lib.RelResultC(), np.zeros(max(n, 1), np.uint8)
-        _lib.check(self.L.mcorb_lmap_relative_pose(self.h, n, cam1.ctypes.data, uv1.ctypes.data, cam2.ctypes.data, uv2.ctypes.data, ncams, ca,
-                                                   C.byref(par), C.byref(res), flags.ctypes.data))
-        return RelResult(res, flags[:n])
+        matches = (self.h, n, cam1.ctypes.data, uv1.ctypes.data, cam2.ctypes.data, uv2.ctypes.data, ncams, ca, C.byref(par))
+        if polish is None:
+            _lib.check(self.L.mcorb_lmap_relative_pose(*matches, C.byref(res), flags.ctypes.data))
+            return RelResult(res, flags[:n])
+        pp, rec = _lib.RelPolishParams(int(polish[0]), int(polish[1])), _lib.RelPolishC()
+        _lib.check(self.L.mcorb_lmap_relative_pose_polished(*matches, C.byref(pp), C.byref(res), flags.ctypes.data, C.byref(rec)))
+        return RelResult(res, flags[:n]), RelPolish(rec)
 
     def last_relative_timing(self):
         """((us of k_rel_hypotheses, k_rel_score, k_rel_pick), hypotheses) of the last relative_pose() launch; a device store"""
@@ -1667,19 +1675,7 @@ class LocalMap:
         flags and count iff its count is at least the current one.  -> (RelResult, RelPolish): the result's R, t, n_inliers and
         inliers are the accepted pose's, best_hypothesis, sample and n_models the winner's.  A device store adds k_rel_fit to
         the submission; a host-only store gives the same bits"""
-        cam1 = np.ascontiguousarray(cam1, np.int32).reshape(-1)
-        n = len(cam1)
-        cam2 = np.ascontiguousarray(cam2, np.int32).reshape(n)
-        uv1 = np.ascontiguousarray(uv1, np.float32).reshape(n, 2)
-        uv2 = np.ascontiguousarray(uv2, np.float32).reshape(n, 2)
-        ncams, ca = _pose_cams(cams)
-        par, pp = _lib.RelParams(), _lib.RelPolishParams(int(rounds), int(polish_iterations))
-        par.threshold, par.seed, par.max_iterations = float(threshold), int(seed) & 0xFFFFFFFFFFFFFFFF, int(max_iterations)
-        res, rec, flags = _lib.RelResultC(), _lib.RelPolishC(), np.zeros(max(n, 1), np.uint8)
-        _lib.check(self.L.mcorb_lmap_relative_pose_polished(self.h, n, cam1.ctypes.data, uv1.ctypes.data, cam2.ctypes.data, uv2.ctypes.data,
-                                                            ncams, ca, C.byref(par), C.byref(pp), C.byref(res), flags.ctypes.data,
-                                                            C.byref(rec)))
-        return RelResult(res, flags[:n]), RelPolish(rec)
+        return self._relative(cams, cam1, uv1, cam2, uv2, threshold, max_iterations, seed, (rounds, polish_iterations))
 
     def last_relative_timing4(self):
         """((us of k_rel_hypotheses, k_rel_score, k_rel_pick of the last relative call, k_rel_fit of the last polished one),
@@ -1704,6 +1700,10 @@ class LocalMap:
         10 models each; seed: of the draws.  -> EssentialResult, whose (R, t) and inliers LocalMap.initialize takes for a rig of
         one camera.  A device store runs k_ess_hypotheses, k_ess_score, k_ess_pick and k_ess_finish in one submission; a host-only
         store the same arithmetic serially, with the same bits.  The store's landmarks are not touched"""
+        return self._essential(cam, uv1, uv2, threshold_px, distance_thresh, max_iterations, seed)
+
+    def _essential(self, cam, uv1, uv2, threshold_px, distance_thresh, max_iterations, seed, polish=None):
+        """essential_pose, or with polish = (rounds, polish_iterations) essential_pose_polished: the arrays, the parameters, the call"""
         uv1 = np.ascontiguousarray(uv1, np.float32).reshape(-1, 2)
         n = len(uv1)
         uv2 = np.ascontiguousarray(uv2, np.float32).reshape(n, 2)
@@ -1711,9 +1711,13 @@ class LocalMap:
         par.threshold_px, par.distance_thresh = float(threshold_px), float(distance_thresh)
         par.seed, par.max_iterations = int(seed) & 0xFFFFFFFFFFFFFFFF, int(max_iterations)
         res, flags = _lib.EssResultC(), np.zeros(max(n, 1), np.uint8)
-        _lib.check(self.L.mcorb_lmap_essential_pose(self.h, n, uv1.ctypes.data, uv2.ctypes.data, _pose_cams(cam)[1], C.byref(par),
-                                                    C.byref(res), flags.ctypes.data))
-        return EssentialResult(res, flags[:n])
+        matches = (self.h, n, uv1.ctypes.data, uv2.ctypes.data, _pose_cams(cam)[1], C.byref(par))
+        if polish is None:
+            _lib.check(self.L.mcorb_lmap_essential_pose(*matches, C.byref(res), flags.ctypes.data))
+            return EssentialResult(res, flags[:n])
+        pp, rec = _lib.EssPolishParams(int(polish[0]), int(polish[1])), _lib.EssPolishC()
+        _lib.check(self.L.mcorb_lmap_essential_pose_polished(*matches, C.byref(pp), C.byref(res), flags.ctypes.data, C.byref(rec)))
+        return EssentialResult(res, flags[:n]), EssentialPolish(rec)
 
     def last_essential_timing(self):
         """((us of k_ess_hypotheses, k_ess_score, k_ess_pick, k_ess_finish), hypotheses) of the last essential_pose() launch; a
@@ -1731,16 +1735,7 @@ class LocalMap:
         counts iff its n_inliers is at least the current one.  -> (EssentialResult, EssentialPolish): the result's R, t, E,
         n_ransac_inliers, n_inliers and inliers are the accepted pose's; cheirality, best_hypothesis, best_root, sample and n_models
         the winner's.  A device store adds k_ess_fit to the submission; a host-only store gives the same bits"""
-        uv1 = np.ascontiguousarray(uv1, np.float32).reshape(-1, 2)
-        n = len(uv1)
-        uv2 = np.ascontiguousarray(uv2, np.float32).reshape(n, 2)
-        par, pp = _lib.EssParams(), _lib.EssPolishParams(int(rounds), int(polish_iterations))
-        par.threshold_px, par.distance_thresh = float(threshold_px), float(distance_thresh)
-        par.seed, par.max_iterations = int(seed) & 0xFFFFFFFFFFFFFFFF, int(max_iterations)
-        res, rec, flags = _lib.EssResultC(), _lib.EssPolishC(), np.zeros(max(n, 1), np.uint8)
-        _lib.check(self.L.mcorb_lmap_essential_pose_polished(self.h, n, uv1.ctypes.data, uv2.ctypes.data, _pose_cams(cam)[1], C.byref(par),
-                                                             C.byref(pp), C.byref(res), flags.ctypes.data, C.byref(rec)))
-        return EssentialResult(res, flags[:n]), EssentialPolish(rec)
+        return self._essential(cam, uv1, uv2, threshold_px, distance_thresh, max_iterations, seed, (rounds, polish_iterations))
 
     def last_essential_timing5(self):
         """((us of k_ess_hypotheses, k_ess_score, k_ess_pick, k_ess_finish of the last essential call, k_ess_fit of the last polished

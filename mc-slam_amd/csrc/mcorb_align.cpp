@@ -18,8 +18,6 @@ namespace {
 
 int fail(int code, const char *what) { set_error(std::string("lmap align_pose: ") + what); return code; }
 
-bool positive(double x) { return x > 0 && sac_finite(x); }
-
 }  // namespace
 
 extern "C" {
@@ -58,11 +56,9 @@ int mcorb_lmap_align_pose(mcorb_lmap *m, int n, const int32_t *lids1, const doub
     std::vector<uint8_t> flags((size_t)n);
     mcorb_lmap::Align &b = m->align;
     if (n == 0) {
-        memset(&out, 0, sizeof(out));
-        out.R[0] = out.R[4] = out.R[8] = out.sac_R[0] = out.sac_R[4] = out.sac_R[8] = 1.0;
-        out.status = MCORB_ALIGN_NO_OBS;
+        no_obs(out, MCORB_ALIGN_NO_OBS);
+        out.sac_R[0] = out.sac_R[4] = out.sac_R[8] = 1.0;
         out.best = -1;
-        for (int j = 0; j < kAlignSample; j++) out.sample[j] = -1;
     } else if (m->device < 0) {
         std::vector<double> gathered;
         const double *p1 = pts1;
@@ -107,26 +103,17 @@ int mcorb_lmap_align_pose(mcorb_lmap *m, int n, const int32_t *lids1, const doub
         a.member = b.d_member;
         a.out = b.h_out;
         a.flags = b.h_flags;
-        hipError_t launched = hipSuccess;
+        if (sac) HIPCHK(hipMemsetAsync(b.d_count, 0, (size_t)H * sizeof(int32_t), st));
+        Submission sub(st);
         if (sac) {
-            HIPCHK(hipMemsetAsync(b.d_count, 0, (size_t)H * sizeof(int32_t), st));
-            TRY(b.sac.mark(st, 0));
-            launch_align_hypotheses(st, a, H);
-            launched = hipGetLastError();
-            TRY(b.sac.mark(st, 1));
-            launch_align_score(st, a, n, H);
-            if (launched == hipSuccess) launched = hipGetLastError();
-            TRY(b.sac.mark(st, 2));
-            launch_align_pick(st, a, n);
-            if (launched == hipSuccess) launched = hipGetLastError();
-            TRY(b.sac.mark(st, 3));
+            sub.run(b.sac, 0, [&] { launch_align_hypotheses(st, a, H); });
+            sub.run(b.sac, 1, [&] { launch_align_score(st, a, n, H); });
+            sub.run(b.sac, 2, [&] { launch_align_pick(st, a, n); });
+            sub.mark(b.sac, 3);
         }
-        TRY(b.fit.mark(st, 0));
-        launch_align_fit(st, a);
-        if (launched == hipSuccess) launched = hipGetLastError();
-        TRY(b.fit.mark(st, 1));
-        HIPCHK(hipStreamSynchronize(st));
-        HIPCHK(launched);
+        sub.run(b.fit, 0, [&] { launch_align_fit(st, a); });
+        sub.mark(b.fit, 1);
+        TRY(sub.wait());
         if (sac) {
             b.sac.read();
             b.last_hyp = H;
@@ -167,26 +154,8 @@ int mcorb_lmap_last_align_timing(mcorb_lmap *m, float us[4], int *n_hyp)
 
 int mcorb_lmap_last_align_counts(mcorb_lmap *m, int32_t *count, int32_t *valid, int cap, int *n_hyp)
 {
-    TRY(check_lmap(m, "lmap last_align_counts"));
-    if (cap < 0 || !n_hyp || (cap && (!count || !valid))) return fail(MCORB_E_ARG, "bad argument");
-    std::lock_guard<std::mutex> lk(m->mu);
-    const int H = m->align.last_hyp;
-    *n_hyp = H;
-    if (cap < H) return fail(MCORB_E_CAP, "arrays too small");
-    if (m->device < 0) {
-        for (int h = 0; h < H; h++) {
-            count[h] = m->align.host_count[h];
-            valid[h] = m->align.host_valid[h];
-        }
-        return MCORB_OK;
-    }
-    if (!H) return MCORB_OK;
-    HIPCHK(hipSetDevice(m->device));
-    std::vector<AlignModel> models((size_t)H);
-    HIPCHK(hipMemcpy(count, m->align.d_count, (size_t)H * sizeof(int32_t), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(models.data(), m->align.d_models, (size_t)H * sizeof(AlignModel), hipMemcpyDeviceToHost));
-    for (int h = 0; h < H; h++) valid[h] = models[h].valid;
-    return MCORB_OK;
+    return last_counts<AlignModel>(m, &mcorb_lmap::align, 1, "lmap last_align_counts", fail, count, valid, cap, n_hyp, host_valid_array,
+                                   each_nothing);
 }
 
 int mcorb_align_solve(int n, const double *p1, const double *p2, const uint8_t *member, double *R, double *t, double *gap)

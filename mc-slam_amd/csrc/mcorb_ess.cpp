@@ -4,9 +4,9 @@
 // store's stream with one wait; the record and the flags land in host-mapped memory.  A host-only store runs the header
 // (mcorb_ess.h) serially, so the two agree bit for bit.  Recalled from OpenCV: the Sampson distance and the cheirality vote;
 // stated: the draws, the five-point solver, no adaptive stop, the midpoint inside the vote, the rotations from E (DESIGN.md
-// section 9m).  mcorb_lmap_essential_pose_polished is the same submission with k_ess_finish's record and flags kept in device memory
-// and k_ess_fit behind it: the polish of the winner over its inliers (mcorb_ess_polish.h), stated too.  mcorb_lmap_essential_pose
-// itself is as it was.
+// section 9m).  mcorb_lmap_essential_pose_polished is the same call (essential_pose below, with polish parameters) with
+// k_ess_finish's record and flags kept in device memory and k_ess_fit behind it: the polish of the winner over its inliers
+// (mcorb_ess_polish.h), stated too.  A plain call touches none of the polish's buffers.
 #include <math.h>
 #include <string.h>
 
@@ -20,8 +20,6 @@ using namespace mcorb;
 namespace {
 
 int fail(int code, const char *what) { set_error(std::string("lmap essential_pose: ") + what); return code; }
-
-bool positive(double v) { return v > 0 && sac_finite(v); }
 
 void fill_job(EssJob &job, const mcorb_track_cam &cam)
 {
@@ -71,20 +69,20 @@ void polish_host(const EssPt *pts, int S, double threshold2, double distance, do
     memcpy(out.t, P.t, sizeof(P.t));
 }
 
-}  // namespace
-
-extern "C" {
-
-int mcorb_lmap_essential_pose(mcorb_lmap *m, int n, const float *uv1, const float *uv2, const mcorb_track_cam *cam,
-                              const mcorb_ess_params *params, mcorb_ess_result *res, uint8_t *inlier)
+// both entries; who: the entry's name in check_lmap's errors.  pp: the polish parameters and polish, its record, or neither: a plain
+// call, whose k_ess_finish writes the host-mapped record and flags itself
+int essential_pose(mcorb_lmap *m, const char *who, int n, const float *uv1, const float *uv2, const mcorb_track_cam *cam,
+                   const mcorb_ess_params *params, const mcorb_ess_polish_params *pp, mcorb_ess_result *res, uint8_t *inlier,
+                   mcorb_ess_polish *polish)
 {
-    TRY(check_lmap(m, "lmap essential_pose"));
+    TRY(check_lmap(m, who));
     if (!params || !res || !cam || n < 0 || (n && (!uv1 || !uv2))) return fail(MCORB_E_ARG, "bad argument");
     if (!positive(params->threshold_px)) return fail(MCORB_E_ARG, "a threshold that is not finite and positive");
     if (!positive(params->distance_thresh)) return fail(MCORB_E_ARG, "a distance that is not finite and positive");
     if (!positive(cam->fx) || !positive(cam->fy)) return fail(MCORB_E_ARG, "a focal length that is not finite and positive");
     if (params->max_iterations < 1 || params->max_iterations > MCORB_ESS_MAX_ITERATIONS)
         return fail(MCORB_E_ARG, "1 .. MCORB_ESS_MAX_ITERATIONS iterations");
+    if (pp) TRY(check_polish(pp));
     std::lock_guard<std::mutex> lk(m->mu);
     if (m->track.pending.load()) return fail(MCORB_E_STATE, "a submitted tracking call has not been waited for");
 
@@ -98,16 +96,16 @@ int mcorb_lmap_essential_pose(mcorb_lmap *m, int n, const float *uv1, const floa
     job.seed = params->seed;
     job.S = S;
     job.H = H;
+    const double inv_thr = ess_fit_scale(params->threshold_px, cam->fx, cam->fy);   // (the polish's)
 
     EssOut out;
+    EssPolish rec;
     std::vector<uint8_t> flags((size_t)n);
     mcorb_lmap::Ess &b = m->ess;
     if (S == 0) {
-        memset(&out, 0, sizeof(out));
-        out.R[0] = out.R[4] = out.R[8] = 1.0;
-        out.status = MCORB_ESS_NO_OBS;
+        no_obs(out, MCORB_ESS_NO_OBS);
         out.best_hypothesis = out.best_root = -1;
-        for (int j = 0; j < kEssSample; j++) out.sample[j] = -1;
+        if (pp) begin_record(rec, out);
     } else if (m->device < 0) {
         std::vector<EssObs> obs((size_t)n);
         fill_obs(obs.data(), n, uv1, uv2);
@@ -117,11 +115,16 @@ int mcorb_lmap_essential_pose(mcorb_lmap *m, int n, const float *uv1, const floa
         ess_run_serial(job, obs.data(), b.host_models.data(), samples.data(), count.data(), pts.data(), out, flags.data());
         b.host_count.swap(count);
         b.last_hyp = H;
+        if (pp && out.status == MCORB_ESS_OK)
+            polish_host(pts.data(), S, job.threshold2, job.distance, inv_thr, *pp, out, flags.data(), flags, rec);
+        else if (pp)
+            begin_record(rec, out);
     } else {
         HIPCHK(hipSetDevice(m->device));
         (void)hipGetLastError();   // (a stale error of this thread is not this call's)
         const EssLayout L((size_t)n);
         TRY(b.reserve(L.p.total, (size_t)n, (size_t)H));
+        if (pp) TRY(b.reserve_polish((size_t)n));
         *b.in.host<EssJob>(L.job) = job;
         fill_obs(b.in.host<EssObs>(L.obs), n, uv1, uv2);
         hipStream_t st = m->st;
@@ -136,26 +139,26 @@ int mcorb_lmap_essential_pose(mcorb_lmap *m, int n, const float *uv1, const floa
         a.count = b.d_count;
         a.cheir = b.d_count.get() + slots;
         a.pick = b.d_pick;
-        a.out = b.h_out;
-        a.flags = b.h_flags;
-        TRY(b.kernels.mark(st, 0));
-        launch_ess_hypotheses(st, a, H);
-        hipError_t launched = hipGetLastError();
-        TRY(b.kernels.mark(st, 1));
-        launch_ess_score(st, a, S, H);
-        if (launched == hipSuccess) launched = hipGetLastError();
-        TRY(b.kernels.mark(st, 2));
-        launch_ess_pick(st, a, S);
-        if (launched == hipSuccess) launched = hipGetLastError();
-        TRY(b.kernels.mark(st, 3));
-        launch_ess_finish(st, a, S);
-        if (launched == hipSuccess) launched = hipGetLastError();
-        TRY(b.kernels.mark(st, 4));
-        HIPCHK(hipStreamSynchronize(st));
-        HIPCHK(launched);
+        // (polished: k_ess_finish's record and flags stay in device memory, k_ess_fit reads nothing across the link)
+        a.out = pp ? b.d_out.get() : b.h_out.get();
+        a.flags = pp ? b.d_member.get() : b.h_flags.get();
+        Submission sub(st);
+        sub.run(b.kernels, 0, [&] { launch_ess_hypotheses(st, a, H); });
+        sub.run(b.kernels, 1, [&] { launch_ess_score(st, a, S, H); });
+        sub.run(b.kernels, 2, [&] { launch_ess_pick(st, a, S); });
+        sub.run(b.kernels, 3, [&] { launch_ess_finish(st, a, S); });
+        sub.mark(b.kernels, 4);
+        if (pp) {
+            const EssFitArgs f{a.job, a.obs, b.d_out, b.d_member, pp->rounds, pp->max_iterations, inv_thr, b.h_out, b.h_flags, b.h_polish};
+            sub.run(b.fit, 0, [&] { launch_ess_fit(st, f); });
+            sub.mark(b.fit, 1);
+        }
+        TRY(sub.wait());
         b.kernels.read();
+        if (pp) b.fit.read();
         b.last_hyp = H;
         out = *b.h_out.get();
+        if (pp) rec = *b.h_polish.get();
         memcpy(flags.data(), b.h_flags.get(), (size_t)n);
     }
 
@@ -172,8 +175,19 @@ int mcorb_lmap_essential_pose(mcorb_lmap *m, int n, const float *uv1, const floa
     memcpy(res->sample, out.sample, sizeof(res->sample));
     res->n_models = out.n_models;
     memcpy(res->cheirality, out.cheirality, sizeof(res->cheirality));
+    if (pp) *polish = rec;
     if (inlier && n) memcpy(inlier, flags.data(), (size_t)n);
     return MCORB_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mcorb_lmap_essential_pose(mcorb_lmap *m, int n, const float *uv1, const float *uv2, const mcorb_track_cam *cam,
+                              const mcorb_ess_params *params, mcorb_ess_result *res, uint8_t *inlier)
+{
+    return essential_pose(m, "lmap essential_pose", n, uv1, uv2, cam, params, nullptr, res, inlier, nullptr);
 }
 
 int mcorb_lmap_last_essential_timing(mcorb_lmap *m, float us[4], int *n_hyp)
@@ -191,118 +205,8 @@ int mcorb_lmap_essential_pose_polished(mcorb_lmap *m, int n, const float *uv1, c
                                        uint8_t *inlier, mcorb_ess_polish *polish)
 {
     TRY(check_lmap(m, "lmap essential_pose_polished"));
-    if (!params || !pp || !res || !polish || !cam || n < 0 || (n && (!uv1 || !uv2))) return fail(MCORB_E_ARG, "bad argument");
-    if (!positive(params->threshold_px)) return fail(MCORB_E_ARG, "a threshold that is not finite and positive");
-    if (!positive(params->distance_thresh)) return fail(MCORB_E_ARG, "a distance that is not finite and positive");
-    if (!positive(cam->fx) || !positive(cam->fy)) return fail(MCORB_E_ARG, "a focal length that is not finite and positive");
-    if (params->max_iterations < 1 || params->max_iterations > MCORB_ESS_MAX_ITERATIONS)
-        return fail(MCORB_E_ARG, "1 .. MCORB_ESS_MAX_ITERATIONS iterations");
-    TRY(check_polish(pp));
-    std::lock_guard<std::mutex> lk(m->mu);
-    if (m->track.pending.load()) return fail(MCORB_E_STATE, "a submitted tracking call has not been waited for");
-
-    const int S = n, H = params->max_iterations;
-    const size_t slots = (size_t)H * kEssRoots;
-    EssJob job;
-    fill_job(job, *cam);
-    const double thr = params->threshold_px / ((cam->fx + cam->fy) / 2.0);
-    job.threshold2 = thr * thr;
-    job.distance = params->distance_thresh;
-    job.seed = params->seed;
-    job.S = S;
-    job.H = H;
-    const double inv_thr = ess_fit_scale(params->threshold_px, cam->fx, cam->fy);
-
-    EssOut out;
-    EssPolish rec;
-    std::vector<uint8_t> flags((size_t)n);
-    mcorb_lmap::Ess &b = m->ess;
-    if (S == 0) {
-        memset(&out, 0, sizeof(out));
-        out.R[0] = out.R[4] = out.R[8] = 1.0;
-        out.status = MCORB_ESS_NO_OBS;
-        out.best_hypothesis = out.best_root = -1;
-        for (int j = 0; j < kEssSample; j++) out.sample[j] = -1;
-        begin_record(rec, out);
-    } else if (m->device < 0) {
-        std::vector<EssObs> obs((size_t)n);
-        fill_obs(obs.data(), n, uv1, uv2);
-        std::vector<int32_t> samples((size_t)H * kEssSample), count(slots);
-        std::vector<EssPt> pts((size_t)S);
-        b.host_models.resize(slots);
-        ess_run_serial(job, obs.data(), b.host_models.data(), samples.data(), count.data(), pts.data(), out, flags.data());
-        b.host_count.swap(count);
-        b.last_hyp = H;
-        if (out.status == MCORB_ESS_OK)
-            polish_host(pts.data(), S, job.threshold2, job.distance, inv_thr, *pp, out, flags.data(), flags, rec);
-        else
-            begin_record(rec, out);
-    } else {
-        HIPCHK(hipSetDevice(m->device));
-        (void)hipGetLastError();   // (a stale error of this thread is not this call's)
-        const EssLayout L((size_t)n);
-        TRY(b.reserve(L.p.total, (size_t)n, (size_t)H));
-        TRY(b.reserve_polish((size_t)n));
-        *b.in.host<EssJob>(L.job) = job;
-        fill_obs(b.in.host<EssObs>(L.obs), n, uv1, uv2);
-        hipStream_t st = m->st;
-        TRY(b.in.upload(st, L.p.total));
-        HIPCHK(hipMemsetAsync(b.d_count, 0, (slots + 4) * sizeof(int32_t), st));   // (the four votes lie behind the counts)
-        EssArgs a;
-        a.job = b.in.dev<const EssJob>(L.job);
-        a.obs = b.in.dev<const EssObs>(L.obs);
-        a.models = b.d_models;
-        a.samples = b.d_samples;
-        a.valid = b.d_valid;
-        a.count = b.d_count;
-        a.cheir = b.d_count.get() + slots;
-        a.pick = b.d_pick;
-        a.out = b.d_out;        // (k_ess_finish's record and flags stay in device memory: k_ess_fit reads nothing across the link)
-        a.flags = b.d_member;
-        const EssFitArgs f{a.job, a.obs, b.d_out, b.d_member, pp->rounds, pp->max_iterations, inv_thr, b.h_out, b.h_flags, b.h_polish};
-        TRY(b.kernels.mark(st, 0));
-        launch_ess_hypotheses(st, a, H);
-        hipError_t launched = hipGetLastError();
-        TRY(b.kernels.mark(st, 1));
-        launch_ess_score(st, a, S, H);
-        if (launched == hipSuccess) launched = hipGetLastError();
-        TRY(b.kernels.mark(st, 2));
-        launch_ess_pick(st, a, S);
-        if (launched == hipSuccess) launched = hipGetLastError();
-        TRY(b.kernels.mark(st, 3));
-        launch_ess_finish(st, a, S);
-        if (launched == hipSuccess) launched = hipGetLastError();
-        TRY(b.kernels.mark(st, 4));
-        TRY(b.fit.mark(st, 0));
-        launch_ess_fit(st, f);
-        if (launched == hipSuccess) launched = hipGetLastError();
-        TRY(b.fit.mark(st, 1));
-        HIPCHK(hipStreamSynchronize(st));
-        HIPCHK(launched);
-        b.kernels.read();
-        b.fit.read();
-        b.last_hyp = H;
-        out = *b.h_out.get();
-        rec = *b.h_polish.get();
-        memcpy(flags.data(), b.h_flags.get(), (size_t)n);
-    }
-
-    memset(res, 0, sizeof(*res));
-    memcpy(res->R, out.R, sizeof(out.R));
-    memcpy(res->t, out.t, sizeof(out.t));
-    memcpy(res->E, out.E, sizeof(out.E));
-    res->status = out.status;
-    res->n_matches = n;
-    res->n_ransac_inliers = out.n_ransac_inliers;
-    res->n_inliers = out.n_inliers;
-    res->best_hypothesis = out.best_hypothesis;
-    res->best_root = out.best_root;
-    memcpy(res->sample, out.sample, sizeof(res->sample));
-    res->n_models = out.n_models;
-    memcpy(res->cheirality, out.cheirality, sizeof(res->cheirality));
-    *polish = rec;
-    if (inlier && n) memcpy(inlier, flags.data(), (size_t)n);
-    return MCORB_OK;
+    if (!pp || !polish) return fail(MCORB_E_ARG, "bad argument");
+    return essential_pose(m, "lmap essential_pose_polished", n, uv1, uv2, cam, params, pp, res, inlier, polish);
 }
 
 int mcorb_lmap_last_essential_timing5(mcorb_lmap *m, float us[5], int *n_hyp)
@@ -360,29 +264,10 @@ int mcorb_ess_polish_run(const mcorb_track_cam *cam, int n, const double *uv1, c
 
 int mcorb_lmap_last_essential_counts(mcorb_lmap *m, int32_t *count, int32_t *valid, double *models, int cap, int *n_slots)
 {
-    TRY(check_lmap(m, "lmap last_essential_counts"));
-    if (cap < 0 || !n_slots || (cap && (!count || !valid))) return fail(MCORB_E_ARG, "bad argument");
-    std::lock_guard<std::mutex> lk(m->mu);
-    const int N = m->ess.last_hyp * kEssRoots;
-    *n_slots = N;
-    if (cap < N) return fail(MCORB_E_CAP, "arrays too small");
-    if (!N) return MCORB_OK;
-    std::vector<EssModel> copy;
-    const EssModel *M = m->ess.host_models.data();
-    if (m->device < 0) {
-        memcpy(count, m->ess.host_count.data(), (size_t)N * sizeof(int32_t));
-    } else {
-        HIPCHK(hipSetDevice(m->device));
-        copy.resize((size_t)N);
-        HIPCHK(hipMemcpy(count, m->ess.d_count, (size_t)N * sizeof(int32_t), hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(copy.data(), m->ess.d_models, (size_t)N * sizeof(EssModel), hipMemcpyDeviceToHost));
-        M = copy.data();
-    }
-    for (int s = 0; s < N; s++) {
-        valid[s] = M[s].valid;
-        if (models) memcpy(models + 9 * (size_t)s, M[s].E, sizeof(M[s].E));
-    }
-    return MCORB_OK;
+    const auto copy_out = [&](int s, const EssModel &M) { if (models) memcpy(models + 9 * (size_t)s, M.E, sizeof(M.E)); };
+    const auto host_valid = [&](const mcorb_lmap::Ess &b, int s) { copy_out(s, b.host_models[s]); return b.host_models[s].valid; };
+    return last_counts<EssModel>(m, &mcorb_lmap::ess, kEssRoots, "lmap last_essential_counts", fail, count, valid, cap, n_slots, host_valid,
+                                 copy_out);
 }
 
 int mcorb_ess_solve(const mcorb_track_cam *cam, const double *uv1, const double *uv2, double *E, double *z)

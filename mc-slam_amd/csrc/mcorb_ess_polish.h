@@ -231,16 +231,6 @@ MCORB_POSE_HD void ess_fit_round(Pass &pass, const PoseState &init, int members,
     cost_final = cost;
 }
 
-// the fold of the lanes' sums, host side: pose_fold's tree on 21 sums
-inline void ess_fit_fold(double s[MCORB_POSE_LANES][kEssFitSums], double S[kEssFitSums])
-{
-    for (int b = 0; b < kPoseBlocks; b++)
-        for (int stride = kPoseBlock / 2; stride >= 1; stride >>= 1)
-            for (int l = 0; l < stride; l++)
-                for (int k = 0; k < kEssFitSums; k++) s[b * kPoseBlock + l][k] = s[b * kPoseBlock + l][k] + s[b * kPoseBlock + l + stride][k];
-    for (int k = 0; k < kEssFitSums; k++) S[k] = (s[0][k] + s[kPoseBlock][k]) + (s[2 * kPoseBlock][k] + s[3 * kPoseBlock][k]);
-}
-
 // a match at a round's result: whether it is within the threshold, and whether it is flagged (that and the depth test)
 MCORB_POSE_HD void ess_fit_test(const PoseState &P, const double *E, const EssPt &p, double threshold2, double distance, bool &within, bool &flag)
 {
@@ -290,7 +280,7 @@ struct EssFitSerialPass {
             for (int i = l; i < S; i += MCORB_POSE_LANES)
                 if (member[i]) ess_fit_add(E, pts[i], inv_thr, lanes[l]);
         }
-        ess_fit_fold(lanes, sums);
+        pose_fold(lanes, sums);
     }
 };
 

@@ -131,6 +131,46 @@ struct Spans {
     }
 };
 
+// A chain of kernels on one stream with one wait.  run(spans, i, launch): mark event i of spans, then launch; run(launch): a
+// piece between no marks; mark(spans, i): the event behind the last piece.  From the first piece on nothing returns before the
+// wait: the first failed launch (hipGetLastError after each) and the first failed mark are kept, and wait() reports, in this
+// order, a failed synchronisation, the launch, the mark -- so no kernel of the chain still reads the call's pinned input or
+// writes its host-mapped records when the caller has its error.  A stale error of the thread is the caller's to discard first.
+class Submission {
+public:
+    explicit Submission(hipStream_t stream) : st(stream) {}
+    template <int N>
+    void mark(Spans<N> &spans, int i)
+    {
+        if (marked != MCORB_OK) return;
+        marked = spans.mark(st, i);
+        if (marked != MCORB_OK) (void)hipGetLastError();   // (the event's error is not the next launch's)
+    }
+    template <class Launch>
+    void run(Launch &&launch)
+    {
+        launch();
+        if (launched == hipSuccess) launched = hipGetLastError();
+    }
+    template <int N, class Launch>
+    void run(Spans<N> &spans, int i, Launch &&launch)
+    {
+        mark(spans, i);
+        run(launch);
+    }
+    int wait()
+    {
+        HIPCHK(hipStreamSynchronize(st));
+        HIPCHK(launched);
+        return marked;
+    }
+
+private:
+    hipStream_t st;
+    hipError_t launched = hipSuccess;
+    int marked = MCORB_OK;
+};
+
 class Stream : public Owner<hipStream_t, hipStreamDestroy> {
 public:
     int create(unsigned flags)

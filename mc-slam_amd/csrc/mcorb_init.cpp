@@ -55,6 +55,21 @@ int check_cases(int n, const double *X, const int32_t *nv1, const int32_t *nv, c
     return MCORB_OK;
 }
 
+// the chain of both device entries on st with its wait: `records` (k_init_triangulate, or the cases' k_init_gates), k_init_select
+// and k_init_put on the records p.rec of n matches, the events of `kernels` around them
+template <class Records>
+int submit(hipStream_t st, Spans<3> &kernels, Records records, const InitPutArgs &p, int n, uint64_t *keys, int32_t *offset, InitSel *sel,
+           bool from_cases)
+{
+    typedef mcorb_lmap::Init I;
+    Submission sub(st);
+    sub.run(kernels, I::kTriangulate, records);
+    sub.run(kernels, I::kSelect, [&] { launch_init_select(st, p.rec, p.flags, n, keys, offset, sel); });
+    sub.run(kernels, I::kPut, [&] { launch_init_put(st, p, from_cases); });
+    sub.mark(kernels, I::kPut + 1);
+    return sub.wait();
+}
+
 void job_init(InitJob &job, const double *R, const double *t, int n, int ncams, int32_t next_lid, const uint8_t *flags)
 {
     memset(&job, 0, sizeof(job));
@@ -206,21 +221,10 @@ int mcorb_lmap_initialize(mcorb_lmap *m, const mcorb_map_frame *prev, int32_t *l
         p.h_call = b.h_call;
         p.geom = m->d_geom;
         p.nrays = m->d_nrays;
-        // from the first launch on nothing returns before the wait: a failed launch or event is kept and reported after it, so that
-        // no kernel of this call still writes the store or the host-mapped records when the caller has its error
-        int marked = b.kernels.mark(st, b.kTriangulate);
-        launch_init_triangulate(st, p.a, w.nblocks_small, (int)w.blocks.size() - w.nblocks_small);
-        hipError_t launched = hipGetLastError();
-        if (marked == MCORB_OK) marked = b.kernels.mark(st, b.kSelect);
-        launch_init_select(st, b.d_rec, p.flags, n, b.d_keys, b.d_offset, b.d_sel);
-        if (launched == hipSuccess) launched = hipGetLastError();
-        if (marked == MCORB_OK) marked = b.kernels.mark(st, b.kPut);
-        launch_init_put(st, p, false);
-        if (launched == hipSuccess) launched = hipGetLastError();
-        if (marked == MCORB_OK) marked = b.kernels.mark(st, b.kPut + 1);
-        HIPCHK(hipStreamSynchronize(st));
-        HIPCHK(launched);
-        TRY(marked);
+        // (nothing returns between the first launch and the wait, so no kernel of this call still writes the store or the
+        // host-mapped records when the caller has its error: Submission)
+        const auto triangulate = [&] { launch_init_triangulate(st, p.a, w.nblocks_small, (int)w.blocks.size() - w.nblocks_small); };
+        TRY(submit(st, b.kernels, triangulate, p, n, b.d_keys, b.d_offset, b.d_sel, false));
         b.kernels.read();
         b.last_launched = (int)w.items.size();
         call = *b.h_call.get();
@@ -350,13 +354,9 @@ int mcorb_dev_init_cases_selftest(int device, int n, const double *X, const int3
     p.h_call = h_call;
     p.geom = d_geom;
     p.nrays = d_nrays;
-    launch_init_gates(nullptr, p.cases, n, d_rec);
-    HIPCHK(hipGetLastError());
-    launch_init_select(nullptr, d_rec, d_flags, n, d_keys, d_offset, d_sel);
-    HIPCHK(hipGetLastError());
-    launch_init_put(nullptr, p, true);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipDeviceSynchronize());
+    Spans<3> kernels;
+    TRY(kernels.create());
+    TRY(submit(nullptr, kernels, [&] { launch_init_gates(nullptr, p.cases, n, d_rec); }, p, n, d_keys, d_offset, d_sel, true));
     cases_out(h_rec.get(), *h_call.get(), n, inliers, verdict, n_rays, lid_offset, vals, res);
     return MCORB_OK;
 }

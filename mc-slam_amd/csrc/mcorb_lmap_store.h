@@ -2,6 +2,8 @@
 // (mcorb_mapping.cpp), by the map initialization (mcorb_init.cpp), by the calls that keep its landmarks up to date
 // (mcorb_landmark.cpp) and by fast tracking (mcorb_track.cpp).
 #pragma once
+#include <string.h>
+
 #include <algorithm>
 #include <atomic>
 #include <mutex>
@@ -46,6 +48,19 @@ struct PoseBufs {
     // the explicit entries: a problem of n observations whose input is elsewhere
     int reserve(size_t n) { TRY(d_alive.grow(n)); TRY(h_out.grow(1, kHostMapped)); return h_flags.grow(n, kHostMapped); }
 };
+
+// what the pose estimators' entries share (mcorb_sac.cpp, _rel, _align, _ess).  positive: a threshold, distance or focal length
+// an entry accepts.  no_obs: the record of a call without observations -- the identity, no sample; the caller sets its
+// "no winner" fields
+inline bool positive(double v) { return v > 0 && sac_finite(v); }
+template <class Out>
+void no_obs(Out &out, int32_t status)
+{
+    memset(&out, 0, sizeof(out));
+    out.R[0] = out.R[4] = out.R[8] = 1.0;
+    out.status = status;
+    for (int32_t &s : out.sample) s = -1;
+}
 }  // namespace mcorb
 
 struct mcorb_lmap {
@@ -487,3 +502,38 @@ inline int check_lmap(const mcorb_lmap *m, const char *who)
     return MCORB_OK;
 }
 
+// mcorb_lmap_last_*_counts: the count and the valid flag of every slot (per_hyp of them per hypothesis) of the last call of
+// m->*bufs that ran any hypotheses, a device store's from d_count and d_models.  who / fail: the entry's name and its error.
+// host_valid(b, s): a host-only store's flag of slot s (host_valid_array: where the store keeps them as host_valid); each(s,
+// model): what else the entry hands out per slot of a device store (each_nothing)
+inline const auto host_valid_array = [](const auto &b, int s) { return b.host_valid[s]; };
+inline const auto each_nothing = [](int, const auto &) {};
+template <class Model, class Bufs, class HostValid, class Each>
+int last_counts(mcorb_lmap *m, Bufs mcorb_lmap::*bufs, int per_hyp, const char *who, int (*fail)(int, const char *), int32_t *count,
+                int32_t *valid, int cap, int *n_slots, HostValid host_valid, Each each)
+{
+    TRY(check_lmap(m, who));
+    if (cap < 0 || !n_slots || (cap && (!count || !valid))) return fail(MCORB_E_ARG, "bad argument");
+    std::lock_guard<std::mutex> lk(m->mu);
+    const Bufs &b = m->*bufs;
+    const int N = b.last_hyp * per_hyp;
+    *n_slots = N;
+    if (cap < N) return fail(MCORB_E_CAP, "arrays too small");
+    if (!N) return MCORB_OK;
+    if (m->device < 0) {
+        for (int s = 0; s < N; s++) {
+            count[s] = b.host_count[s];
+            valid[s] = host_valid(b, s);
+        }
+        return MCORB_OK;
+    }
+    HIPCHK(hipSetDevice(m->device));
+    std::vector<Model> models((size_t)N);
+    HIPCHK(hipMemcpy(count, b.d_count, (size_t)N * sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(models.data(), b.d_models, (size_t)N * sizeof(Model), hipMemcpyDeviceToHost));
+    for (int s = 0; s < N; s++) {
+        valid[s] = models[s].valid;
+        each(s, models[s]);
+    }
+    return MCORB_OK;
+}

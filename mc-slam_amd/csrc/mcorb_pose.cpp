@@ -252,12 +252,10 @@ int mcorb_lmap_refine_pose(mcorb_lmap *m, int n, const int32_t *cam, const float
     obs_stage(in, L, b.in);
     hipStream_t st = m->st;
     TRY(b.in.upload(st, L.p.total));
-    TRY(m->pose.refine.mark(st, 0));
-    obs_enqueue_refine(m, in, L, b.in, b);
-    const hipError_t launched = hipGetLastError();
-    TRY(m->pose.refine.mark(st, 1));
-    HIPCHK(hipStreamSynchronize(st));
-    HIPCHK(launched);
+    Submission sub(st);
+    sub.run(m->pose.refine, 0, [&] { obs_enqueue_refine(m, in, L, b.in, b); });
+    sub.mark(m->pose.refine, 1);
+    TRY(sub.wait());
     m->pose.refine.read();
     *res = *b.h_out.get();
     if (inlier) memcpy(inlier, b.h_flags.get(), (size_t)n);

@@ -275,15 +275,17 @@ MCORB_POSE_HD void pose_round(Pass &pass, const PoseState &init, int max_iterati
     cost_final = cost;
 }
 
-// the fold of the lanes' sums, host side: s[lane][k].  Each block of 64 lanes folds with strides 32 .. 1, s[l] = s[l] + s[l +
-// stride], and the four block sums combine as (b0 + b1) + (b2 + b3) -- what the wave shuffles and the LDS of k_pose_refine do
-inline void pose_fold(double s[MCORB_POSE_LANES][kPoseSums], double S[kPoseSums])
+// the fold of the lanes' K sums, host side: s[lane][k].  Each block of 64 lanes folds with strides 32 .. 1, s[l] = s[l] + s[l +
+// stride], and the four block sums combine as (b0 + b1) + (b2 + b3) -- what the wave shuffles and the LDS of k_pose_refine (28
+// sums), k_rel_fit (28) and k_ess_fit (21) do
+template <int K>
+inline void pose_fold(double s[MCORB_POSE_LANES][K], double S[K])
 {
     for (int b = 0; b < kPoseBlocks; b++)
         for (int stride = kPoseBlock / 2; stride >= 1; stride >>= 1)
             for (int l = 0; l < stride; l++)
-                for (int k = 0; k < kPoseSums; k++) s[b * kPoseBlock + l][k] = s[b * kPoseBlock + l][k] + s[b * kPoseBlock + l + stride][k];
-    for (int k = 0; k < kPoseSums; k++) S[k] = (s[0][k] + s[kPoseBlock][k]) + (s[2 * kPoseBlock][k] + s[3 * kPoseBlock][k]);
+                for (int k = 0; k < K; k++) s[b * kPoseBlock + l][k] = s[b * kPoseBlock + l][k] + s[b * kPoseBlock + l + stride][k];
+    for (int k = 0; k < K; k++) S[k] = (s[0][k] + s[kPoseBlock][k]) + (s[2 * kPoseBlock][k] + s[3 * kPoseBlock][k]);
 }
 
 }  // namespace mcorb

@@ -3,8 +3,9 @@
 // A device store runs k_rel_hypotheses, k_rel_score and k_rel_pick (mcorb_rel_gpu.hip) in one submission on the store's stream
 // with one wait; the records land in host-mapped memory.  A host-only store runs the header (mcorb_rel.h) serially, so the two
 // agree bit for bit.  Stated rather than OpenGV's: the draws, the linear solver, no adaptive stop.
-// mcorb_lmap_relative_pose_polished is the same submission with the pick's record and flags kept in device memory and k_rel_fit
-// behind it: the polish of the winner over its inliers, stated too.  mcorb_lmap_relative_pose itself is as it was.
+// mcorb_lmap_relative_pose_polished is the same call (relative_pose below, with polish parameters) with the pick's record and
+// flags kept in device memory and k_rel_fit behind it: the polish of the winner over its inliers, stated too.  A plain call
+// touches none of the polish's buffers.
 #include <math.h>
 #include <string.h>
 
@@ -49,122 +50,19 @@ void polish_host(const RelRays *rays, int S, double threshold, const mcorb_rel_p
                       reinterpret_cast<double (*)[kPoseSums]>(lanes.data()), rec);
 }
 
-}  // namespace
-
-extern "C" {
-
-int mcorb_lmap_relative_pose(mcorb_lmap *m, int n, const int32_t *cam1, const float *uv1, const int32_t *cam2, const float *uv2, int ncams,
-                             const mcorb_track_cam *cams, const mcorb_rel_params *params, mcorb_rel_result *res, uint8_t *inlier)
+// both entries; who: the entry's name in check_lmap's errors.  pp: the polish parameters and polish, its record, or neither: a plain
+// call, whose pick writes the host-mapped record and flags itself
+int relative_pose(mcorb_lmap *m, const char *who, int n, const int32_t *cam1, const float *uv1, const int32_t *cam2, const float *uv2,
+                  int ncams, const mcorb_track_cam *cams, const mcorb_rel_params *params, const mcorb_rel_polish_params *pp,
+                  mcorb_rel_result *res, uint8_t *inlier, mcorb_rel_polish *polish)
 {
-    TRY(check_lmap(m, "lmap relative_pose"));
+    TRY(check_lmap(m, who));
     if (!params || !res || !cams || n < 0 || ncams < 1 || ncams > MCORB_MAX_CAMS || (n && (!cam1 || !uv1 || !cam2 || !uv2)))
         return fail(MCORB_E_ARG, "bad argument");
-    if (!(params->threshold > 0) || !sac_finite(params->threshold)) return fail(MCORB_E_ARG, "a threshold that is not finite and positive");
+    if (!positive(params->threshold)) return fail(MCORB_E_ARG, "a threshold that is not finite and positive");
     if (params->max_iterations < 1 || params->max_iterations > MCORB_REL_MAX_ITERATIONS)
         return fail(MCORB_E_ARG, "1 .. MCORB_REL_MAX_ITERATIONS iterations");
-    TRY(check_cams(n, cam1, cam2, ncams));
-    std::lock_guard<std::mutex> lk(m->mu);
-    if (m->track.pending.load()) return fail(MCORB_E_STATE, "a submitted tracking call has not been waited for");
-
-    const int S = n, H = params->max_iterations;
-    RelJob job;
-    memset(&job, 0, sizeof(job));
-    memcpy(job.cams, cams, (size_t)ncams * sizeof(mcorb_track_cam));
-    job.threshold = params->threshold;
-    job.seed = params->seed;
-    job.ncams = ncams;
-    job.S = S;
-    job.H = H;
-
-    RelOut out;
-    std::vector<uint8_t> flags((size_t)n);
-    mcorb_lmap::Rel &b = m->rel;
-    if (S == 0) {
-        memset(&out, 0, sizeof(out));
-        out.R[0] = out.R[4] = out.R[8] = 1.0;
-        out.status = MCORB_REL_NO_OBS;
-        out.best = -1;
-        for (int j = 0; j < kRelSample; j++) out.sample[j] = -1;
-    } else if (m->device < 0) {
-        std::vector<RelObs> obs((size_t)n);
-        fill_obs(obs.data(), n, cam1, uv1, cam2, uv2);
-        std::vector<RelModel> models((size_t)H);
-        std::vector<int32_t> count((size_t)H);
-        std::vector<RelRays> rays((size_t)S);
-        rel_run_serial(job, obs.data(), models.data(), count.data(), rays.data(), out, flags.data());
-        b.host_valid.resize((size_t)H);
-        for (int h = 0; h < H; h++) b.host_valid[h] = models[h].valid;
-        b.host_count.swap(count);
-        b.last_hyp = H;
-    } else {
-        HIPCHK(hipSetDevice(m->device));
-        (void)hipGetLastError();   // (a stale error of this thread is not this call's)
-        const RelLayout L((size_t)n);
-        TRY(b.reserve(L.p.total, (size_t)n, (size_t)H));
-        *b.in.host<RelJob>(L.job) = job;
-        fill_obs(b.in.host<RelObs>(L.obs), n, cam1, uv1, cam2, uv2);
-        hipStream_t st = m->st;
-        TRY(b.in.upload(st, L.p.total));
-        HIPCHK(hipMemsetAsync(b.d_count, 0, (size_t)H * sizeof(int32_t), st));
-        RelArgs a;
-        a.job = b.in.dev<const RelJob>(L.job);
-        a.obs = b.in.dev<const RelObs>(L.obs);
-        a.models = b.d_models;
-        a.count = b.d_count;
-        a.out = b.h_out;
-        a.flags = b.h_flags;
-        TRY(b.kernels.mark(st, 0));
-        launch_rel_hypotheses(st, a, H);
-        hipError_t launched = hipGetLastError();
-        TRY(b.kernels.mark(st, 1));
-        launch_rel_score(st, a, S, H);
-        if (launched == hipSuccess) launched = hipGetLastError();
-        TRY(b.kernels.mark(st, 2));
-        launch_rel_pick(st, a, S);
-        if (launched == hipSuccess) launched = hipGetLastError();
-        TRY(b.kernels.mark(st, 3));
-        HIPCHK(hipStreamSynchronize(st));
-        HIPCHK(launched);
-        b.kernels.read();
-        b.last_hyp = H;
-        out = *b.h_out.get();
-        memcpy(flags.data(), b.h_flags.get(), (size_t)n);
-    }
-
-    memset(res, 0, sizeof(*res));
-    memcpy(res->R, out.R, sizeof(out.R));
-    memcpy(res->t, out.t, sizeof(out.t));
-    res->status = out.status;
-    res->n_inliers = out.n_inliers;
-    res->n_matches = n;
-    res->best_hypothesis = out.best;
-    memcpy(res->sample, out.sample, sizeof(res->sample));
-    res->n_models = out.n_models;
-    if (inlier && n) memcpy(inlier, flags.data(), (size_t)n);
-    return MCORB_OK;
-}
-
-int mcorb_lmap_last_relative_timing(mcorb_lmap *m, float us[3], int *n_hyp)
-{
-    TRY(check_lmap_handle(m, "lmap last_relative_timing"));
-    if (!us) return fail(MCORB_E_ARG, "bad argument");
-    std::lock_guard<std::mutex> lk(m->mu);
-    for (int k = 0; k < 3; k++) us[k] = m->rel.kernels.us[k];
-    if (n_hyp) *n_hyp = m->rel.last_hyp;
-    return MCORB_OK;
-}
-
-int mcorb_lmap_relative_pose_polished(mcorb_lmap *m, int n, const int32_t *cam1, const float *uv1, const int32_t *cam2, const float *uv2,
-                                      int ncams, const mcorb_track_cam *cams, const mcorb_rel_params *params,
-                                      const mcorb_rel_polish_params *pp, mcorb_rel_result *res, uint8_t *inlier, mcorb_rel_polish *polish)
-{
-    TRY(check_lmap(m, "lmap relative_pose_polished"));
-    if (!params || !pp || !res || !polish || !cams || n < 0 || ncams < 1 || ncams > MCORB_MAX_CAMS || (n && (!cam1 || !uv1 || !cam2 || !uv2)))
-        return fail(MCORB_E_ARG, "bad argument");
-    if (!(params->threshold > 0) || !sac_finite(params->threshold)) return fail(MCORB_E_ARG, "a threshold that is not finite and positive");
-    if (params->max_iterations < 1 || params->max_iterations > MCORB_REL_MAX_ITERATIONS)
-        return fail(MCORB_E_ARG, "1 .. MCORB_REL_MAX_ITERATIONS iterations");
-    TRY(check_polish(pp));
+    if (pp) TRY(check_polish(pp));
     TRY(check_cams(n, cam1, cam2, ncams));
     std::lock_guard<std::mutex> lk(m->mu);
     if (m->track.pending.load()) return fail(MCORB_E_STATE, "a submitted tracking call has not been waited for");
@@ -184,12 +82,9 @@ int mcorb_lmap_relative_pose_polished(mcorb_lmap *m, int n, const int32_t *cam1,
     std::vector<uint8_t> flags((size_t)n);
     mcorb_lmap::Rel &b = m->rel;
     if (S == 0) {
-        memset(&out, 0, sizeof(out));
-        out.R[0] = out.R[4] = out.R[8] = 1.0;
-        out.status = MCORB_REL_NO_OBS;
+        no_obs(out, MCORB_REL_NO_OBS);
         out.best = -1;
-        for (int j = 0; j < kRelSample; j++) out.sample[j] = -1;
-        rel_polish_begin(rec, PoseState{{1, 0, 0, 0, 1, 0, 0, 0, 1}, {0, 0, 0}}, 0);
+        if (pp) rel_polish_begin(rec, PoseState{{1, 0, 0, 0, 1, 0, 0, 0, 1}, {0, 0, 0}}, 0);
     } else if (m->device < 0) {
         std::vector<RelObs> obs((size_t)n);
         fill_obs(obs.data(), n, cam1, uv1, cam2, uv2);
@@ -201,22 +96,24 @@ int mcorb_lmap_relative_pose_polished(mcorb_lmap *m, int n, const int32_t *cam1,
         for (int h = 0; h < H; h++) b.host_valid[h] = models[h].valid;
         b.host_count.swap(count);
         b.last_hyp = H;
-        PoseState P;
-        memcpy(P.R, out.R, sizeof(P.R));
-        memcpy(P.t, out.t, sizeof(P.t));
-        if (out.best >= 0) {
-            polish_host(rays.data(), S, job.threshold, *pp, P, out.n_inliers, flags.data(), flags, rec);
-            memcpy(out.R, P.R, sizeof(P.R));
-            memcpy(out.t, P.t, sizeof(P.t));
-        } else {
-            rel_polish_begin(rec, P, out.n_inliers);
+        if (pp) {
+            PoseState P;
+            memcpy(P.R, out.R, sizeof(P.R));
+            memcpy(P.t, out.t, sizeof(P.t));
+            if (out.best >= 0) {
+                polish_host(rays.data(), S, job.threshold, *pp, P, out.n_inliers, flags.data(), flags, rec);
+                memcpy(out.R, P.R, sizeof(P.R));
+                memcpy(out.t, P.t, sizeof(P.t));
+            } else {
+                rel_polish_begin(rec, P, out.n_inliers);
+            }
         }
     } else {
         HIPCHK(hipSetDevice(m->device));
         (void)hipGetLastError();   // (a stale error of this thread is not this call's)
         const RelLayout L((size_t)n);
         TRY(b.reserve(L.p.total, (size_t)n, (size_t)H));
-        TRY(b.reserve_polish((size_t)n));
+        if (pp) TRY(b.reserve_polish((size_t)n));
         *b.in.host<RelJob>(L.job) = job;
         fill_obs(b.in.host<RelObs>(L.obs), n, cam1, uv1, cam2, uv2);
         hipStream_t st = m->st;
@@ -227,30 +124,25 @@ int mcorb_lmap_relative_pose_polished(mcorb_lmap *m, int n, const int32_t *cam1,
         a.obs = b.in.dev<const RelObs>(L.obs);
         a.models = b.d_models;
         a.count = b.d_count;
-        a.out = b.d_pick;       // (the pick's record and flags stay in device memory: k_rel_fit reads nothing across the link)
-        a.flags = b.d_member;
-        const RelFitArgs f{a.job, a.obs, b.d_pick, b.d_member, pp->rounds, pp->max_iterations, b.h_out, b.h_flags, b.h_polish};
-        TRY(b.kernels.mark(st, 0));
-        launch_rel_hypotheses(st, a, H);
-        hipError_t launched = hipGetLastError();
-        TRY(b.kernels.mark(st, 1));
-        launch_rel_score(st, a, S, H);
-        if (launched == hipSuccess) launched = hipGetLastError();
-        TRY(b.kernels.mark(st, 2));
-        launch_rel_pick(st, a, S);
-        if (launched == hipSuccess) launched = hipGetLastError();
-        TRY(b.kernels.mark(st, 3));
-        TRY(b.fit.mark(st, 0));
-        launch_rel_fit(st, f);
-        if (launched == hipSuccess) launched = hipGetLastError();
-        TRY(b.fit.mark(st, 1));
-        HIPCHK(hipStreamSynchronize(st));
-        HIPCHK(launched);
+        // (polished: the pick's record and flags stay in device memory, k_rel_fit reads nothing across the link)
+        a.out = pp ? b.d_pick.get() : b.h_out.get();
+        a.flags = pp ? b.d_member.get() : b.h_flags.get();
+        Submission sub(st);
+        sub.run(b.kernels, 0, [&] { launch_rel_hypotheses(st, a, H); });
+        sub.run(b.kernels, 1, [&] { launch_rel_score(st, a, S, H); });
+        sub.run(b.kernels, 2, [&] { launch_rel_pick(st, a, S); });
+        sub.mark(b.kernels, 3);
+        if (pp) {
+            const RelFitArgs f{a.job, a.obs, b.d_pick, b.d_member, pp->rounds, pp->max_iterations, b.h_out, b.h_flags, b.h_polish};
+            sub.run(b.fit, 0, [&] { launch_rel_fit(st, f); });
+            sub.mark(b.fit, 1);
+        }
+        TRY(sub.wait());
         b.kernels.read();
-        b.fit.read();
+        if (pp) b.fit.read();
         b.last_hyp = H;
         out = *b.h_out.get();
-        rec = *b.h_polish.get();
+        if (pp) rec = *b.h_polish.get();
         memcpy(flags.data(), b.h_flags.get(), (size_t)n);
     }
 
@@ -263,9 +155,38 @@ int mcorb_lmap_relative_pose_polished(mcorb_lmap *m, int n, const int32_t *cam1,
     res->best_hypothesis = out.best;
     memcpy(res->sample, out.sample, sizeof(res->sample));
     res->n_models = out.n_models;
-    *polish = rec;
+    if (pp) *polish = rec;
     if (inlier && n) memcpy(inlier, flags.data(), (size_t)n);
     return MCORB_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mcorb_lmap_relative_pose(mcorb_lmap *m, int n, const int32_t *cam1, const float *uv1, const int32_t *cam2, const float *uv2, int ncams,
+                             const mcorb_track_cam *cams, const mcorb_rel_params *params, mcorb_rel_result *res, uint8_t *inlier)
+{
+    return relative_pose(m, "lmap relative_pose", n, cam1, uv1, cam2, uv2, ncams, cams, params, nullptr, res, inlier, nullptr);
+}
+
+int mcorb_lmap_last_relative_timing(mcorb_lmap *m, float us[3], int *n_hyp)
+{
+    TRY(check_lmap_handle(m, "lmap last_relative_timing"));
+    if (!us) return fail(MCORB_E_ARG, "bad argument");
+    std::lock_guard<std::mutex> lk(m->mu);
+    for (int k = 0; k < 3; k++) us[k] = m->rel.kernels.us[k];
+    if (n_hyp) *n_hyp = m->rel.last_hyp;
+    return MCORB_OK;
+}
+
+int mcorb_lmap_relative_pose_polished(mcorb_lmap *m, int n, const int32_t *cam1, const float *uv1, const int32_t *cam2, const float *uv2,
+                                      int ncams, const mcorb_track_cam *cams, const mcorb_rel_params *params,
+                                      const mcorb_rel_polish_params *pp, mcorb_rel_result *res, uint8_t *inlier, mcorb_rel_polish *polish)
+{
+    TRY(check_lmap(m, "lmap relative_pose_polished"));
+    if (!pp || !polish) return fail(MCORB_E_ARG, "bad argument");
+    return relative_pose(m, "lmap relative_pose_polished", n, cam1, uv1, cam2, uv2, ncams, cams, params, pp, res, inlier, polish);
 }
 
 int mcorb_lmap_last_relative_timing4(mcorb_lmap *m, float us[4], int *n_hyp)
@@ -286,7 +207,7 @@ int mcorb_rel_polish_run(int ncams, const mcorb_track_cam *cams, int n, const in
     if (n < 0 || ncams < 1 || ncams > MCORB_MAX_CAMS || !cams || !R || !t || !pp || !polish || !R_out || !t_out ||
         (n && (!cam1 || !uv1 || !cam2 || !uv2 || !member || !inlier)))
         return fail(MCORB_E_ARG, "bad argument");
-    if (!(threshold > 0) || !sac_finite(threshold)) return fail(MCORB_E_ARG, "a threshold that is not finite and positive");
+    if (!positive(threshold)) return fail(MCORB_E_ARG, "a threshold that is not finite and positive");
     TRY(check_polish(pp));
     TRY(check_cams(n, cam1, cam2, ncams));
     std::vector<RelRays> rays((size_t)n);
@@ -310,26 +231,8 @@ int mcorb_rel_polish_run(int ncams, const mcorb_track_cam *cams, int n, const in
 
 int mcorb_lmap_last_relative_counts(mcorb_lmap *m, int32_t *count, int32_t *valid, int cap, int *n_hyp)
 {
-    TRY(check_lmap(m, "lmap last_relative_counts"));
-    if (cap < 0 || !n_hyp || (cap && (!count || !valid))) return fail(MCORB_E_ARG, "bad argument");
-    std::lock_guard<std::mutex> lk(m->mu);
-    const int H = m->rel.last_hyp;
-    *n_hyp = H;
-    if (cap < H) return fail(MCORB_E_CAP, "arrays too small");
-    if (m->device < 0) {
-        for (int h = 0; h < H; h++) {
-            count[h] = m->rel.host_count[h];
-            valid[h] = m->rel.host_valid[h];
-        }
-        return MCORB_OK;
-    }
-    if (!H) return MCORB_OK;
-    HIPCHK(hipSetDevice(m->device));
-    std::vector<RelModel> models((size_t)H);
-    HIPCHK(hipMemcpy(count, m->rel.d_count, (size_t)H * sizeof(int32_t), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(models.data(), m->rel.d_models, (size_t)H * sizeof(RelModel), hipMemcpyDeviceToHost));
-    for (int h = 0; h < H; h++) valid[h] = models[h].valid;
-    return MCORB_OK;
+    return last_counts<RelModel>(m, &mcorb_lmap::rel, 1, "lmap last_relative_counts", fail, count, valid, cap, n_hyp, host_valid_array,
+                                 each_nothing);
 }
 
 double mcorb_rel_threshold(double K00_02) { return 2.0 * mcorb_sac_threshold(K00_02); }

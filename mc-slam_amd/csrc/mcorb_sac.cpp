@@ -69,7 +69,7 @@ int mcorb_lmap_ransac_pose(mcorb_lmap *m, int n, const int32_t *cam, const float
     TRY(check_lmap(m, "lmap ransac_pose"));
     if (!params || !res) return fail(MCORB_E_ARG, "bad argument");
     if (refine_params) TRY(pose_check_params(refine_params));
-    if (!(params->threshold > 0) || !sac_finite(params->threshold)) return fail(MCORB_E_ARG, "a threshold that is not finite and positive");
+    if (!positive(params->threshold)) return fail(MCORB_E_ARG, "a threshold that is not finite and positive");
     if (params->max_iterations < 1 || params->max_iterations > MCORB_SAC_MAX_ITERATIONS)
         return fail(MCORB_E_ARG, "1 .. MCORB_SAC_MAX_ITERATIONS iterations");
     if (params->solver != MCORB_SAC_SOLVER_CENTRAL && params->solver != MCORB_SAC_SOLVER_RIG)
@@ -108,11 +108,8 @@ int mcorb_lmap_ransac_pose(mcorb_lmap *m, int n, const int32_t *cam, const float
         std::vector<double> X;
         obs_gather(m, in, obs, X);
         if (S == 0) {
-            memset(&out, 0, sizeof(out));
-            memcpy(out.R, ident.R, sizeof(out.R));
-            out.status = MCORB_SAC_NO_OBS;
+            no_obs(out, MCORB_SAC_NO_OBS);
             out.best = -1;
-            for (int j = 0; j < 4; j++) out.sample[j] = -1;
         } else {
             std::vector<SacModel> models((size_t)H);
             std::vector<int32_t> count((size_t)H);
@@ -160,25 +157,18 @@ int mcorb_lmap_ransac_pose(mcorb_lmap *m, int n, const int32_t *cam, const float
         a.out = b.h_out;
         a.flags = b.h_flags;
         a.pose_job = refine_params ? b.in.dev<PoseJob>(L.pose_job) : nullptr;
-        TRY(b.kernels.mark(st, 0));
-        if (job.solver == MCORB_SAC_SOLVER_RIG)
-            launch_sac_hypotheses_rig(st, a, H);
-        else
-            launch_sac_hypotheses(st, a, H);
-        hipError_t launched = hipGetLastError();
-        TRY(b.kernels.mark(st, 1));
-        launch_sac_score(st, a, S, H);
-        if (launched == hipSuccess) launched = hipGetLastError();
-        TRY(b.kernels.mark(st, 2));
-        launch_sac_pick(st, a, n);
-        if (launched == hipSuccess) launched = hipGetLastError();
-        TRY(b.kernels.mark(st, 3));
-        if (refine_params) {
-            obs_enqueue_refine(m, in, L, b.in, b.pose);
-            if (launched == hipSuccess) launched = hipGetLastError();
-        }
-        HIPCHK(hipStreamSynchronize(st));
-        HIPCHK(launched);
+        Submission sub(st);
+        sub.run(b.kernels, 0, [&] {
+            if (job.solver == MCORB_SAC_SOLVER_RIG)
+                launch_sac_hypotheses_rig(st, a, H);
+            else
+                launch_sac_hypotheses(st, a, H);
+        });
+        sub.run(b.kernels, 1, [&] { launch_sac_score(st, a, S, H); });
+        sub.run(b.kernels, 2, [&] { launch_sac_pick(st, a, n); });
+        sub.mark(b.kernels, 3);
+        if (refine_params) sub.run([&] { obs_enqueue_refine(m, in, L, b.in, b.pose); });
+        TRY(sub.wait());
         b.kernels.read();
         b.last_hyp = H;
         out = *b.h_out.get();
@@ -233,26 +223,8 @@ int mcorb_lmap_last_ransac_timing(mcorb_lmap *m, float us[3], int *n_hyp)
 
 int mcorb_lmap_last_ransac_counts(mcorb_lmap *m, int32_t *count, int32_t *valid, int cap, int *n_hyp)
 {
-    TRY(check_lmap(m, "lmap last_ransac_counts"));
-    if (cap < 0 || !n_hyp || (cap && (!count || !valid))) return fail(MCORB_E_ARG, "bad argument");
-    std::lock_guard<std::mutex> lk(m->mu);
-    const int H = m->sac.last_hyp;
-    *n_hyp = H;
-    if (cap < H) return fail(MCORB_E_CAP, "arrays too small");
-    if (m->device < 0) {
-        for (int h = 0; h < H; h++) {
-            count[h] = m->sac.host_count[h];
-            valid[h] = m->sac.host_valid[h];
-        }
-        return MCORB_OK;
-    }
-    if (!H) return MCORB_OK;
-    HIPCHK(hipSetDevice(m->device));
-    std::vector<SacModel> models((size_t)H);
-    HIPCHK(hipMemcpy(count, m->sac.d_count, (size_t)H * sizeof(int32_t), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(models.data(), m->sac.d_models, (size_t)H * sizeof(SacModel), hipMemcpyDeviceToHost));
-    for (int h = 0; h < H; h++) valid[h] = models[h].valid;
-    return MCORB_OK;
+    return last_counts<SacModel>(m, &mcorb_lmap::sac, 1, "lmap last_ransac_counts", fail, count, valid, cap, n_hyp, host_valid_array,
+                                 each_nothing);
 }
 
 double mcorb_sac_threshold(double K00_02) { return 1.0 - cos(atan(sqrt(2.0) * 0.5 / K00_02)); }

@@ -153,3 +153,12 @@ def same_counts(lm, ref, what=""):
     count, valid = lm.last_relative_counts()
     assert valid.tolist() == [m is not None for m in ref["models"]], (what, "models")
     assert count.tolist() == [c or 0 for c in ref["counts"]], (what, "counts")
+
+
+def same_stores(a, b, what=""):
+    """two results of the library (device store, host-only store), doubles as raw bytes"""
+    for k in ("R", "t"):
+        assert getattr(a, k).tobytes() == getattr(b, k).tobytes(), (what, k)
+    for k in ("status", "n_matches", "n_inliers", "best_hypothesis", "sample", "n_models"):
+        assert getattr(a, k) == getattr(b, k), (what, k)
+    assert a.inliers.tolist() == b.inliers.tolist(), what

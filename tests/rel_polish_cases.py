@@ -44,6 +44,16 @@ def same(got, pol, ref, rp, what=""):
     same_record(pol, rp, what)
 
 
+def same_polish(a, b, what=""):
+    """two RelPolish records of the library, doubles as raw bytes"""
+    for k in ("R", "t"):
+        assert getattr(a, k).tobytes() == getattr(b, k).tobytes(), (what, k)
+    assert (a.n_inliers, a.rounds_run) == (b.n_inliers, b.rounds_run), what
+    for q, r in zip(a.rounds, b.rounds):
+        assert {k: (RR.bits(v) if isinstance(v, float) else v) for k, v in q.items()} == \
+               {k: (RR.bits(v) if isinstance(v, float) else v) for k, v in r.items()}, what
+
+
 def hook(mc, cams, matches, pose, member, threshold=RC.THRESHOLD, rounds=2, polish_iterations=10, what=""):
     """mcorb_rel_polish_run against the restatement on the bits -> (R, t, inliers, RelPolish, the restatement's dict)"""
     rays = [RR.rays_of(cams, m) for m in matches]

@@ -137,6 +137,31 @@ def test_bootstrap_on_the_device_store(mc, lms):
     test_bootstrap_end_to_end(mc, lms[0])
 
 
+def test_polished_first_on_fresh_stores(mc, big):
+    """a device store and a host-only store that never ran a plain call: polished, plain, polished, plain at 5, 65, 257 and 6
+    matches, so the polish's buffers are allocated before any plain call and every buffer grows between calls of the other kind.
+    After every call the two stores hold the same bytes: result, flags, polish record, counts and models; a plain call leaves
+    k_ess_fit's timing as the polished call before it left it"""
+    matches = big["general"]
+    vocs = mc.ORBVocabulary().create(**K.vocabulary()), mc.ORBVocabulary(device=-1).create(**K.vocabulary())
+    dev, host = [mc.LocalMap(voc, device=d, max_landmarks=4096, max_candidates=1024) for voc, d in zip(vocs, (0, -1))]
+    fit_us = None
+    for size, polished in ((5, True), (65, False), (257, True), (6, False)):
+        what = "%d matches, %s" % (size, "polished" if polished else "plain")
+        if polished:
+            (a, pa), (b, pb) = [EPC.run(mc, lm, matches[:size], max_iterations=HYP, rounds=2, polish_iterations=10) for lm in (dev, host)]
+            EPC.same_polish(pa, pb, what)
+            fit_us = dev.last_essential_timing5()[0][4]
+            assert fit_us > 0, what
+        else:
+            a, b = [EC.run(mc, lm, matches[:size], max_iterations=HYP) for lm in (dev, host)]
+            assert dev.last_essential_timing5()[0][4] == fit_us, what
+        EC.same_stores(a, b, what)
+        assert a.n_matches == size and dev.last_essential_timing5()[1] == HYP, what
+        ca, cb = dev.last_essential_counts(), host.last_essential_counts()
+        assert len(ca[0]) == 10 * HYP and all(x.tobytes() == y.tobytes() for x, y in zip(ca, cb)), (what, "counts")
+
+
 def test_between_two_tracking_submissions(mc, big):
     """a store with landmarks: a tracking submission, refused while it is pending, the polished call, a second submission -- both
     tracking results are the synchronous call's and the polished call is the restatement's"""

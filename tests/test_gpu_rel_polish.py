@@ -107,6 +107,31 @@ def test_relative_pose_is_what_it_was(mc, lms, big):
     RC.same_counts(lms[0], ref, "after")
 
 
+def test_polished_first_on_fresh_stores(mc, big):
+    """a device store and a host-only store that never ran a plain call: polished, plain, polished, plain at 17, 65, 257 and 18
+    matches, so the polish's buffers are allocated before any plain call and every buffer grows between calls of the other kind.
+    After every call the two stores hold the same bytes: result, flags, polish record, counts; a plain call leaves k_rel_fit's
+    timing as the polished call before it left it"""
+    cams, truth, matches, moved = big
+    vocs = mc.ORBVocabulary().create(**K.vocabulary()), mc.ORBVocabulary(device=-1).create(**K.vocabulary())
+    dev, host = [mc.LocalMap(voc, device=d, max_landmarks=4096, max_candidates=1024) for voc, d in zip(vocs, (0, -1))]
+    fit_us = None
+    for size, polished in ((17, True), (65, False), (257, True), (18, False)):
+        what = "%d matches, %s" % (size, "polished" if polished else "plain")
+        if polished:
+            (a, pa), (b, pb) = [RPC.run(mc, lm, cams, matches[:size], max_iterations=64, rounds=2, polish_iterations=10) for lm in (dev, host)]
+            RPC.same_polish(pa, pb, what)
+            fit_us = dev.last_relative_timing4()[0][3]
+            assert fit_us > 0, what
+        else:
+            a, b = [RC.run(mc, lm, cams, matches[:size], max_iterations=64) for lm in (dev, host)]
+            assert dev.last_relative_timing4()[0][3] == fit_us, what
+        RC.same_stores(a, b, what)
+        assert a.n_matches == size and dev.last_relative_timing4()[1] == 64, what
+        (ca, va), (cb, vb) = dev.last_relative_counts(), host.last_relative_counts()
+        assert len(ca) == 64 and ca.tolist() == cb.tolist() and va.tolist() == vb.tolist(), (what, "counts")
+
+
 def test_between_two_tracking_submissions(mc, big):
     """a store with landmarks: a tracking submission, refused while it is pending, the polished call, a second submission -- both
     tracking results are the synchronous call's and the polished call is the restatement's"""
