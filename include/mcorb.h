@@ -1214,6 +1214,80 @@ int mcorb_pose_eval(int ncams, const mcorb_track_cam *cams, int n, const int32_t
                     const double *t, double *r, double *J, double *w);
 
 /* ------------------------------------------------------------------------- */
+/* Local bundle adjustment: rig keyframes and landmarks together, with the     */
+/* projection factor of the reference's back end (MCSlam/src/Backend.cpp:      */
+/* 1380-1393, 1426-1440) around the Levenberg-Marquardt stated above, the      */
+/* landmarks eliminated by the Schur complement.        */
+/* ------------------------------------------------------------------------- */
+#define MCORB_BA_MAX_KF 16           /* keyframes of a window */
+#define MCORB_BA_MAX_LANDMARKS 65536
+#define MCORB_BA_MAX_OBS (1 << 20)
+#define MCORB_BA_NO_OBS 0            /* no observation: the initial state */
+#define MCORB_BA_NO_STEP 1           /* no trial was ever accepted: the initial state, on the bits */
+#define MCORB_BA_CONVERGED 2         /* the loop ended on an accepted step with a small decrease */
+#define MCORB_BA_MAX_ITER 3          /* the loop ended at max_iterations solves, or when lambda left its bounds */
+/* sigma: per pyramid level what the reference hands noiseModel::Isotropic::Sigma(2, .) -- GetInverseScaleSigmaSquares()[octave]
+ * as it stands there, or MeasurementNoiseSigma on every level; the call whitens by 1.0 / sigma[octave] and does not judge the
+ * value.  max_iterations: solves, 1 .. 100 */
+typedef struct mcorb_ba_params {
+    double sigma[MCORB_MAX_LEVELS];
+    int32_t nlevels, max_iterations;
+} mcorb_ba_params;
+/* status: MCORB_BA_*; iterations: the solves taken; cost_initial / cost_final: the cost at the initial and at the returned state
+ * (a NaN is the default quiet NaN); n_inliers: the observations whose whitened r.r is not > 5.991 at the returned state */
+typedef struct mcorb_ba_result {
+    double cost_initial, cost_final;
+    int32_t status, iterations, n_inliers, n_obs;
+} mcorb_ba_result;
+/* A window of nkf keyframes (1 .. MCORB_BA_MAX_KF) of one rig and nlm landmarks (0 .. MCORB_BA_MAX_LANDMARKS), adjusted together
+ * over nobs observations (0 .. MCORB_BA_MAX_OBS).  Keyframe k has the pose w_T_b = (kf_R[9 k ..] row-major, kf_t[3 k ..]) and is
+ * held when fixed[k] != 0: the fixed keyframes hold the gauge (the reference's pose prior is not restated).  The rig is
+ * mcorb_lmap_refine_pose's.  Landmark j's point is pts[3 j ..] or, with lids, the store's point of lids[j] (exactly one of the two
+ * is non-NULL).  Observation i is the keypoint uv[2 i], uv[2 i + 1] of level octave[i] in camera obs_cam[i] of keyframe obs_kf[i],
+ * of landmark obs_lm[i], an index into the call's landmark list.  All arithmetic is fp64, one IEEE operation per operator in the
+ * order written (csrc/mcorb_ba.h):
+ * - the observations are sorted stably by (landmark, keyframe); "in order" means that order.
+ * - an observation: r and the pose Jacobian J are mcorb_lmap_refine_pose's; the point Jacobian is JX = Dpi(q) M, M = Rc^T R^T, an
+ *   entry of M (a0 b0 + a1 b1) + a2 b2, a row of JX (D0 M0 + D1 M1) + D2 M2 (the second row has no D0 term), zero behind the
+ *   camera.  r, J and JX are multiplied by 1.0 / sigma[octave]; Huber at the double nearest sqrt(5.991) on the whitened r.
+ * - per landmark, in order into +0.0: V = sum w JX^T JX (6 entries), gp = sum w JX^T r, cost = sum rho and, per free keyframe
+ *   that sees it (a view), U = sum w J^T J (21), g = sum w J^T r (6), W = sum w J^T JX (6 x 3); a term is w (x0 y0 + x1 y1).  An
+ *   observation in a fixed keyframe adds to V, gp and the cost only.
+ * - V' = V with d + lambda d on the diagonal, by a 3 x 3 LDL^T written out; a pivot that is not > 0 makes the landmark inactive
+ *   for this solve: it adds nothing to the reduced system and does not move.
+ * - the reduced system over the free keyframes that have an observation, ascending: U_a = fold U_aj, E_ab = fold W_aj V'^-1
+ *   W_bj^T (a <= b), rhs_a = fold (g_aj - W_aj V'^-1 gp_j), a product entry (x0 y0 + x1 y1) + x2 y2; fold is
+ *   mcorb_lmap_refine_pose's tree over the landmarks (lane l of 256 adds landmarks l, l + 256, ..).  S_aa = (U_a + lambda
+ *   diag(U_a)) - E_aa, S_ab = -E_ab; S delta = -rhs by mcorb_lmap_refine_pose's LDL^T on 6 x (free keyframes) unknowns, every dot
+ *   product subtracted in ascending order; a pivot that is not > 0 means no step.  Without a free keyframe only the points move.
+ * - per active landmark: tt = gp + sum over its free keyframes, ascending, of W^T delta_a; X' = X + V'^-1 (-tt).  The poses
+ *   retract as mcorb_lmap_refine_pose's.
+ * - the loop, its constants and the status are mcorb_lmap_refine_pose's round on the whole state; cost = fold cost_j.
+ * R_out (9 nkf), t_out (3 nkf), pts_out (3 nlm): the returned state (fixed keyframes and landmarks nobody observes as they
+ * came).  inlier (may be NULL): nobs flags in the caller's order.  A device store runs a chain of kernels in one submission
+ * with one wait (the loop's record lives in device memory; the kernels queued behind its end return at once); a host-only store
+ * runs the same header serially: the results are equal bit for bit.  A call without observations launches nothing.  Before
+ * anything runs: MCORB_E_ARG for a count outside its range, a NULL array, kf / cam / lm / octave out of range, an id outside the
+ * store, both or neither of lids / pts, a sigma that is not > 0, nlevels outside 1 .. MCORB_MAX_LEVELS, max_iterations outside
+ * 1 .. 100; MCORB_E_STATE for a landmark without a point and while a tracking call is pending.  The store is unchanged in every
+ * case: the caller applies mcorb_lmap_update_points. */
+int mcorb_lmap_bundle_adjust(mcorb_lmap *m, int nkf, const double *kf_R, const double *kf_t, const uint8_t *fixed, int ncams,
+                             const mcorb_track_cam *cams, int nlm, const int32_t *lids, const double *pts, int nobs,
+                             const int32_t *obs_kf, const int32_t *obs_cam, const int32_t *obs_lm, const float *uv,
+                             const int32_t *octave, const mcorb_ba_params *params, double *R_out, double *t_out, double *pts_out,
+                             mcorb_ba_result *res, uint8_t *inlier);
+/* a device store's last chain, microseconds between HIP events: [0] the copy-in, the first linearization and its cost, [1] ..
+ * [4] k_ba_schur, k_ba_solve, k_ba_update and k_ba_accept of the first iteration, [5] every later iteration together (those
+ * queued behind the end included), [6] the final pass.  launches_idle (may be NULL): the launches that were queued behind the
+ * end.  A call without observations launches nothing and leaves both */
+#define MCORB_BA_SPANS 7
+int mcorb_lmap_last_ba_timing(mcorb_lmap *m, float us[MCORB_BA_SPANS], int32_t *launches_idle);
+/* test hook, host: per observation the whitened residual r (n x 2), Jacobians J (n x 2 x 6) and JX (n x 2 x 3) and the Huber
+ * weight w (n) at the pose (R, t) and the point pts[3 i ..], with inv_s = 1.0 / sigma[i] */
+int mcorb_ba_eval(int ncams, const mcorb_track_cam *cams, int n, const int32_t *cam, const float *uv, const double *pts,
+                  const double *sigma, const double *R, const double *t, double *r, double *J, double *JX, double *w);
+
+/* ------------------------------------------------------------------------- */
 /* The absolute rig pose by RANSAC in front of the refinement: the consensus   */
 /* step every matcher of the reference ends in -- OpenGV's sac::Ransac<        */
 /* AbsolutePoseSacProblem>(GP3P) as FrontEnd::absolutePoseFromGP3P (MCSlam/src/ */

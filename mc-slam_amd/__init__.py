@@ -1590,6 +1590,47 @@ class LocalMap:
         _lib.check(self.L.mcorb_lmap_last_pose_timing(self.h, us))
         return us[0]
 
+    # local bundle adjustment over rig keyframes and landmarks (mcorb_lmap_bundle_adjust)
+    def bundle_adjust(self, cams, kf_R, kf_t, fixed, obs_kf, obs_cam, obs_lm, uv, octave, sigma, lids=None, pts=None, max_iterations=25):
+        """a window of keyframes of one rig and landmarks adjusted together: keyframe k has the pose w_T_b = (kf_R[k], kf_t[k])
+        and is held when fixed[k] (the fixed keyframes hold the gauge); landmark j's point is pts[j] or the store's point of
+        lids[j] (exactly one of the two); observation i is the keypoint uv[i] of level octave[i] in camera obs_cam[i] of keyframe
+        obs_kf[i], of landmark obs_lm[i] (an index into the call's landmark list).  cams: refine_pose's; sigma: per level what
+        the back end hands Isotropic::Sigma.  The factor is the back end's projection factor with Huber at sqrt(5.991); the
+        optimizer is refine_pose's Levenberg-Marquardt on the whole state, the landmarks eliminated by the Schur complement ->
+        BAResult.  A device store runs a chain of kernels in one submission; a host-only store the same arithmetic serially, with
+        the same bits.  The store is not written: apply update_points(lids, result.pts, ...)"""
+        kf_R = np.ascontiguousarray(kf_R, np.float64)
+        nkf = kf_R.size // 9
+        kf_R = kf_R.reshape(nkf, 9)
+        kf_t = np.ascontiguousarray(kf_t, np.float64).reshape(nkf, 3)
+        fixed = np.ascontiguousarray(np.asarray(fixed).astype(bool), np.uint8).reshape(nkf)
+        obs_kf = np.ascontiguousarray(obs_kf, np.int32).reshape(-1)
+        n = len(obs_kf)
+        obs_cam = np.ascontiguousarray(obs_cam, np.int32).reshape(n)
+        obs_lm = np.ascontiguousarray(obs_lm, np.int32).reshape(n)
+        uv = np.ascontiguousarray(uv, np.float32).reshape(n, 2)
+        octave = np.ascontiguousarray(octave, np.int32).reshape(n)
+        nlm = len(lids) if lids is not None else (np.asarray(pts).size // 3 if pts is not None else 0)
+        l, lp = self._opt(lids, np.int32, (nlm,))
+        p, pp = self._opt(pts, np.float64, (nlm, 3))
+        ncams, ca = _pose_cams(cams)
+        R_out, t_out, pts_out = np.zeros((nkf, 3, 3)), np.zeros((nkf, 3)), np.zeros((max(nlm, 1), 3))
+        res, flags = _lib.BAResultC(), np.zeros(max(n, 1), np.uint8)
+        _lib.check(self.L.mcorb_lmap_bundle_adjust(self.h, nkf, kf_R.ctypes.data, kf_t.ctypes.data, fixed.ctypes.data, ncams, ca, nlm, lp, pp,
+                                                   n, obs_kf.ctypes.data, obs_cam.ctypes.data, obs_lm.ctypes.data, uv.ctypes.data,
+                                                   octave.ctypes.data, C.byref(ba_params(sigma, max_iterations)), R_out.ctypes.data,
+                                                   t_out.ctypes.data, pts_out.ctypes.data, C.byref(res), flags.ctypes.data))
+        return BAResult(res, R_out, t_out, pts_out[:nlm], flags[:n])
+
+    def last_ba_timing(self):
+        """(us, launches_idle) of the last bundle_adjust() chain of a device store: us = microseconds of the copy-in with the first
+        linearization, of k_ba_schur, k_ba_solve, k_ba_update and k_ba_accept of the first iteration, of all later iterations
+        together and of the final pass; launches_idle: the launches that were queued behind the loop's end"""
+        us, idle = (C.c_float * _lib.BA_SPANS)(), C.c_int32()
+        _lib.check(self.L.mcorb_lmap_last_ba_timing(self.h, us, C.byref(idle)))
+        return tuple(us), idle.value
+
     # the absolute rig pose by RANSAC in front of the refinement (mcorb_lmap_ransac_pose)
     def ransac_pose(self, cams, cam, uv, octave, threshold, lids=None, pts=None, match=None, max_iterations=100, seed=0, refine=None,
                     solver="central"):
@@ -1825,6 +1866,23 @@ class PoseResult:
         self.cost_initial, self.cost_final = res.cost_initial, res.cost_final
         self.n_inliers, self.n_obs = res.n_inliers, res.n_obs
         self.inliers = flags.astype(bool)
+
+
+class BAResult:
+    """what LocalMap.bundle_adjust returns: R (nkf x 3 x 3), t (nkf x 3) and pts (nlm x 3), the returned state; status (BA_NO_OBS,
+    BA_NO_STEP, BA_CONVERGED, BA_MAX_ITER); iterations, the solves taken; cost_initial and cost_final; n_inliers and inliers, one
+    bool per observation in the caller's order: False where the whitened r.r > 5.991 at the returned state"""
+
+    def __init__(self, res, R, t, pts, flags):
+        self.R, self.t, self.pts = R, t, pts
+        self.status, self.iterations = res.status, res.iterations
+        self.cost_initial, self.cost_final = res.cost_initial, res.cost_final
+        self.n_inliers, self.n_obs = res.n_inliers, res.n_obs
+        self.inliers = flags.astype(bool)
+
+
+BA_NO_OBS, BA_NO_STEP, BA_CONVERGED, BA_MAX_ITER = 0, 1, 2, 3
+BA_MAX_KF = 16
 
 
 class SacResult:
@@ -2173,6 +2231,33 @@ def pose_eval(cams, R, t, cam, uv, pts):
     _lib.check(_lib.load().mcorb_pose_eval(ncams, ca, n, cam.ctypes.data, uv.ctypes.data, pts.ctypes.data, R.ctypes.data, t.ctypes.data,
                                            r.ctypes.data, J.ctypes.data, w.ctypes.data))
     return r[:n], J[:n], w[:n]
+
+
+def ba_params(sigma, max_iterations=25):
+    """mcorb_ba_params: sigma per pyramid level, as the back end hands it to Isotropic::Sigma"""
+    s = np.asarray(sigma, np.float64).reshape(-1)
+    p = _lib.BAParams()
+    p.nlevels, p.max_iterations = len(s), int(max_iterations)
+    for k in range(min(len(s), _lib.MAX_LEVELS)):
+        p.sigma[k] = float(s[k])
+    return p
+
+
+def ba_eval(cams, R, t, cam, uv, pts, sigma):
+    """test hook (host): whitened residual r (n x 2), Jacobians J (n x 2 x 6, by the pose's right perturbation) and JX (n x 2 x 3,
+    by the point) and Huber weight w (n) of the observations at the pose (R, t); sigma: one per observation"""
+    cam = np.ascontiguousarray(cam, np.int32).reshape(-1)
+    n = len(cam)
+    uv = np.ascontiguousarray(uv, np.float32).reshape(n, 2)
+    pts = np.ascontiguousarray(pts, np.float64).reshape(n, 3)
+    sigma = np.ascontiguousarray(np.broadcast_to(np.asarray(sigma, np.float64), (n,)))
+    R = np.ascontiguousarray(R, np.float64).reshape(9)
+    t = np.ascontiguousarray(t, np.float64).reshape(3)
+    r, J, JX, w = np.zeros((max(n, 1), 2)), np.zeros((max(n, 1), 2, 6)), np.zeros((max(n, 1), 2, 3)), np.zeros(max(n, 1))
+    ncams, ca = _pose_cams(cams)
+    _lib.check(_lib.load().mcorb_ba_eval(ncams, ca, n, cam.ctypes.data, uv.ctypes.data, pts.ctypes.data, sigma.ctypes.data, R.ctypes.data,
+                                         t.ctypes.data, r.ctypes.data, J.ctypes.data, JX.ctypes.data, w.ctypes.data))
+    return r[:n], J[:n], JX[:n], w[:n]
 
 
 class TrackResult:

@@ -120,6 +120,18 @@ class PoseResultC(C.Structure):
                 ("reserved", C.c_int32)]
 
 
+class BAParams(C.Structure):
+    _fields_ = [("sigma", C.c_double * MAX_LEVELS), ("nlevels", C.c_int32), ("max_iterations", C.c_int32)]
+
+
+class BAResultC(C.Structure):
+    _fields_ = [("cost_initial", C.c_double), ("cost_final", C.c_double), ("status", C.c_int32), ("iterations", C.c_int32),
+                ("n_inliers", C.c_int32), ("n_obs", C.c_int32)]
+
+
+BA_SPANS = 7
+
+
 class SacParams(C.Structure):
     _fields_ = [("threshold", C.c_double), ("seed", C.c_uint64), ("max_iterations", C.c_int32), ("solver", C.c_int32)]
 
@@ -371,6 +383,10 @@ SIGNATURES = {
     "mcorb_lmap_last_track_pose": (_i, [_vp, _i, C.POINTER(PoseResultC), _vp, _i]),
     "mcorb_pose_of_view": (None, [C.POINTER(TrackView), _vp, _vp]),
     "mcorb_pose_eval": (_i, [_i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mcorb_lmap_bundle_adjust": (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, C.POINTER(BAParams),
+                                      _vp, _vp, _vp, C.POINTER(BAResultC), _vp]),
+    "mcorb_lmap_last_ba_timing": (_i, [_vp, C.POINTER(_f), C.POINTER(C.c_int32)]),
+    "mcorb_ba_eval": (_i, [_i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mcorb_lmap_ransac_pose": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, C.POINTER(SacParams), C.POINTER(PoseParams),
                                     C.POINTER(SacResultC), _vp]),
     "mcorb_lmap_last_ransac_timing": (_i, [_vp, C.POINTER(_f), C.POINTER(_i)]),

@@ -6,6 +6,7 @@
 #include <vector>
 #include "../../include/mcorb.h"
 #include "mcorb_align.h"
+#include "mcorb_ba.h"
 #include "mcorb_common.h"
 #include "mcorb_init.h"
 #include "mcorb_mapping_new.h"
@@ -236,6 +237,20 @@ void launch_track_dedup(hipStream_t st, const TrItem *items, int nf, int max_n, 
 void launch_pose_refine(hipStream_t st, const PoseJob *jobs, int njobs, PoseObs *obs, int32_t *lids, const double *pts, const double *geom,
                         uint8_t *alive, const uint8_t *win, const TrBest *best, const int *cand, const float2 *kp_xy,
                         mcorb_pose_result *out, uint8_t *flags);
+
+// the local bundle adjustment (mcorb_ba_gpu.hip): the kernels of one chain, in stream order -- k_ba_begin (the state and the
+// record), then per iteration k_ba_linearize (one lane per landmark; returns at once unless the state moved), k_ba_schur (one
+// workgroup per keyframe pair and per keyframe of the system), k_ba_solve (one workgroup), k_ba_update (one lane per landmark:
+// the back-substitution and the trial's cost), k_ba_accept (one workgroup; first: the fold of the initial cost in front of
+// iteration 0), and at the end k_ba_flags with k_ba_result.  Every kernel but the first and the last two returns at once when
+// the record says the loop is over
+void launch_ba_begin(hipStream_t st, const BaArgs &a);
+void launch_ba_linearize(hipStream_t st, const BaArgs &a);
+void launch_ba_schur(hipStream_t st, const BaArgs &a);
+void launch_ba_solve(hipStream_t st, const BaArgs &a);
+void launch_ba_update(hipStream_t st, const BaArgs &a);
+void launch_ba_accept(hipStream_t st, const BaArgs &a, bool first);
+void launch_ba_final(hipStream_t st, const BaArgs &a);
 
 // the RANSAC in front of it (mcorb_sac_gpu.hip), three launches.  job, obs, lids | pts, cons / cam_first / cam_cons (the
 // consensus observations in input order, and camera by camera) and is_first (per observation: the first of its match) are device

@@ -250,6 +250,41 @@ struct mcorb_lmap {
         mcorb::Spans<1> refine;                 // around k_pose_refine of mcorb_lmap_refine_pose
     } pose;
 
+    // the local bundle adjustment (mcorb_ba.cpp), grow-only: the packed input (BaLayout); both halves of the state (poses:
+    // MCORB_BA_MAX_KF each, points: nlm x 3 each), the landmarks' V, gp and cost, the views, the folded sums of the keyframes and
+    // the pairs, the step, the loop's record; and what the host reads, host-mapped: the result with the poses, the points, the flags
+    struct Ba {
+        mcorb::Staged in;
+        mcorb::DevBuf<mcorb::PoseState> d_poses;
+        mcorb::DevBuf<double> d_pts, d_V, d_gp, d_cost, d_views, d_diag, d_pairs, d_delta;
+        mcorb::DevBuf<mcorb::BaRecord> d_rec;
+        mcorb::DevBuf<int32_t> d_count;         // k_ba_flags' inliers per workgroup
+        mcorb::HostBuf<mcorb::BaOut> h_out;
+        mcorb::HostBuf<double> h_pts;
+        mcorb::HostBuf<uint8_t> h_flags;
+        enum { kBegin, kSchur, kSolve, kUpdate, kAccept, kRest, kFinal };
+        mcorb::Spans<MCORB_BA_SPANS> chain;
+        int last_idle = 0;                      // the launches of the last chain that were queued behind the loop's end
+        int reserve(size_t bytes, size_t nlm, size_t nobs, size_t nviews)
+        {
+            TRY(in.reserve(bytes));
+            TRY(d_poses.grow(2 * MCORB_BA_MAX_KF));
+            TRY(d_pts.grow(2 * 3 * nlm));
+            TRY(d_V.grow(6 * nlm));
+            TRY(d_gp.grow(3 * nlm));
+            TRY(d_cost.grow(nlm));
+            TRY(d_views.grow((size_t)mcorb::kBaView * nviews + 1));
+            TRY(d_diag.grow((size_t)mcorb::kBaDiag * MCORB_BA_MAX_KF));
+            TRY(d_pairs.grow((size_t)mcorb::kBaPair * mcorb::kBaMaxPairs));
+            TRY(d_delta.grow(mcorb::kBaMaxN));
+            TRY(d_rec.grow(1));
+            TRY(d_count.grow(std::max(nobs, 3 * nlm) / 256 + 1));
+            TRY(h_out.grow(1, mcorb::kHostMapped));
+            TRY(h_pts.grow(3 * nlm + 1, mcorb::kHostMapped));
+            return h_flags.grow(nobs, mcorb::kHostMapped);
+        }
+    } ba;
+
     // the RANSAC in front of the refinement (mcorb_sac.cpp), grow-only: the packed input (ObsLayout with its RANSAC part), the
     // models and counts of the hypotheses, and what the host reads: the pick's record and the flags per observation, host-mapped.
     // `pose`: the buffers of the refinement behind it, whose input is part of `in`

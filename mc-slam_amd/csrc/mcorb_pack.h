@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "mcorb_align.h"
+#include "mcorb_ba.h"
 #include "mcorb_ess.h"
 #include "mcorb_mapping.h"
 #include "mcorb_rel.h"
@@ -57,6 +58,17 @@ struct AlignLayout {
     Pack p;
     size_t job, p1, p2;
     AlignLayout(size_t n, bool lids) : job(p.add<AlignJob>(1)), p1(lids ? p.add<int32_t>(n) : p.add<double>(3 * n)), p2(p.add<double>(3 * n)) {}
+};
+
+// mcorb_lmap_bundle_adjust: the BaJob, the keyframes' poses, the landmarks' ids (lids) or points, the sorted observations and the
+// per-landmark tables (BaPlan)
+struct BaLayout {
+    Pack p;
+    size_t job, poses, pt, obs, obs_first, view_first, slot;
+    BaLayout(size_t nkf, size_t nlm, size_t nobs, bool lids)
+        : job(p.add<BaJob>(1)), poses(p.add<PoseState>(nkf)), pt(lids ? p.add<int32_t>(nlm) : p.add<double>(3 * nlm)),
+          obs(p.add<BaObs>(nobs)), obs_first(p.add<int32_t>(nlm + 1)), view_first(p.add<int32_t>(nlm + 1)),
+          slot(p.add<int8_t>(nlm * MCORB_BA_MAX_KF)) {}
 };
 
 // a tracking submission of nf frames: a TrItem and a view per frame, every frame's candidates, then -- host arrays only -- the
