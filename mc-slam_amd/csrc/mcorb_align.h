@@ -20,10 +20,9 @@ namespace mcorb {
 constexpr int kAlignSample = MCORB_ALIGN_SAMPLE;   // the pairs of a minimal sample
 constexpr int kAlignSweeps = 6;                    // cyclic Jacobi sweeps over the six pairs of Horn's 4 x 4 matrix
 constexpr double kAlignGap = 1e-12;                // a fit is kept iff l1 - l2 > kAlignGap (l1 - l4): the members are not collinear
-constexpr int kAlignLanes = 256, kAlignBlock = 64, kAlignBlocks = kAlignLanes / kAlignBlock;
-static_assert(kAlignBlocks == 4, "the four block sums combine as (b0 + b1) + (b2 + b3)");
+constexpr int kAlignLanes = MCORB_POSE_LANES;   // the sums fold as mcorb_pose.h's pose_fold states
 static_assert(kAlignSample == 3, "align_fit3 is written out for three pairs");
-static_assert(MCORB_ALIGN_MAX_ITERATIONS == MCORB_REL_MAX_ITERATIONS, "rel_key holds every hypothesis index");
+static_assert(MCORB_ALIGN_MAX_ITERATIONS == MCORB_REL_MAX_ITERATIONS, "kRelKeyBits holds every hypothesis index");
 
 // a hypothesis's model: b1_T_b2, whether there is one, and the pairs it was drawn from in draw order (-1: not drawn)
 struct AlignModel {
@@ -52,13 +51,6 @@ struct AlignOut {
     int32_t status, used, n_inliers, sac_n_inliers, best, n_models, sample[kAlignSample], pad;
 };
 
-MCORB_POSE_HD void align_identity(PoseState &P)
-{
-#pragma unroll
-    for (int j = 0; j < 9; j++) P.R[j] = (j % 4 == 0) ? 1.0 : 0.0;
-#pragma unroll
-    for (int j = 0; j < 3; j++) P.t[j] = 0.0;
-}
 
 // the SAC problem's distance (recalled) and the reference's delta.norm() (:4499-4503): |p1 - (R p2 + t)|
 MCORB_POSE_HD double align_dist(const PoseState &P, const double p1[3], const double p2[3])
@@ -107,17 +99,6 @@ MCORB_POSE_HD void align_add2(const double p1[3], const double p2[3], const doub
     s[6] = s[6] + a2 * b0;
     s[7] = s[7] + a2 * b1;
     s[8] = s[8] + a2 * b2;
-}
-
-// the fold of 256 lanes' sums, host side: what the wave shuffles and the LDS of k_align_fit do
-template <int K>
-inline void align_fold(double s[kAlignLanes][K], double S[K])
-{
-    for (int b = 0; b < kAlignBlocks; b++)
-        for (int stride = kAlignBlock / 2; stride >= 1; stride >>= 1)
-            for (int l = 0; l < stride; l++)
-                for (int k = 0; k < K; k++) s[b * kAlignBlock + l][k] = s[b * kAlignBlock + l][k] + s[b * kAlignBlock + l + stride][k];
-    for (int k = 0; k < K; k++) S[k] = (s[0][k] + s[kAlignBlock][k]) + (s[2 * kAlignBlock][k] + s[3 * kAlignBlock][k]);
 }
 
 // the fold with lanes 0, 1 and 2 occupied by one member each, written out: a lane's sum is 0.0 + a, the empty lanes add + 0.0,
@@ -277,7 +258,7 @@ inline bool align_fit_host(int n, const double *p1, const double *p2, const uint
         align_add1(p1 + 3 * (size_t)i, p2 + 3 * (size_t)i, lanes[i % kAlignLanes]);
         cnt++;
     }
-    align_fold<kAlignSums2>(lanes, S);
+    pose_fold<kAlignSums2>(lanes, S);
     align_centroids(S, cnt, c1, c2);
     for (int l = 0; l < kAlignLanes; l++)
         for (int k = 0; k < kAlignSums2; k++) lanes[l][k] = 0.0;
@@ -285,7 +266,7 @@ inline bool align_fit_host(int n, const double *p1, const double *p2, const uint
         if (member && !member[i]) continue;
         align_add2(p1 + 3 * (size_t)i, p2 + 3 * (size_t)i, c1, c2, lanes[i % kAlignLanes]);
     }
-    align_fold<kAlignSums2>(lanes, M);
+    pose_fold<kAlignSums2>(lanes, M);
     return align_from_sums(M, c1, c2, cnt, out, gap);
 }
 
@@ -347,7 +328,7 @@ inline void align_verdict_host(const AlignJob &job, const double *p1, const doub
         out.n_inliers += flags[i];
         lanes[i % kAlignLanes][0] = lanes[i % kAlignLanes][0] + d;
     }
-    align_fold<1>(lanes, S);
+    pose_fold<1>(lanes, S);
     out.mean_error = have ? pose_default_nan(S[0] / (double)job.n) : 0.0;
 }
 
@@ -358,8 +339,8 @@ inline void align_run_serial(const AlignJob &job, const double *p1, const double
 {
     const int n = job.n;
     PoseState win, ans;
-    align_identity(win);
-    align_identity(ans);
+    pose_identity(win);
+    pose_identity(ans);
     bool have = false;
     out.used = MCORB_ALIGN_USED_SAC;
     out.sac_n_inliers = 0;
@@ -375,28 +356,23 @@ inline void align_run_serial(const AlignJob &job, const double *p1, const double
         out.used = have ? MCORB_ALIGN_USED_FIT : MCORB_ALIGN_USED_SAC;
     } else {
         const AlignHostPoint point{p1, p2};
-        uint64_t key = 0;
         for (int h = 0; h < job.H; h++) {
             AlignModel &M = models[h];
             align_hypothesis(job, h, point, M);
             count[h] = 0;
-            if (M.valid) {
-                PoseState P;
-                for (int j = 0; j < 9; j++) P.R[j] = M.R[j];
-                for (int j = 0; j < 3; j++) P.t[j] = M.t[j];
-                for (int i = 0; i < n; i++)
-                    count[h] += sac_is_inlier(align_dist(P, p1 + 3 * (size_t)i, p2 + 3 * (size_t)i), job.threshold) ? 1 : 0;
-            }
-            const uint64_t kh = rel_key(M.valid, count[h], h);
-            key = kh > key ? kh : key;
-            out.n_models += M.valid;
+            if (!M.valid) continue;
+            PoseState P;
+            pose_load(P, M.R, M.t);
+            for (int i = 0; i < n; i++)
+                count[h] += sac_is_inlier(align_dist(P, p1 + 3 * (size_t)i, p2 + 3 * (size_t)i), job.threshold) ? 1 : 0;
         }
-        const int best = rel_key_hypothesis(key);
+        const ConsensusBest won = consensus_best<kRelKeyBits>(job.H, [&](int h) { return models[h].valid; }, [&](int h) { return count[h]; });
+        const int best = consensus_key_index<kRelKeyBits>(won.key);
         out.best = best;
+        out.n_models = won.n_models;
         if (best >= 0) {
             have = true;
-            for (int j = 0; j < 9; j++) win.R[j] = models[best].R[j];
-            for (int j = 0; j < 3; j++) win.t[j] = models[best].t[j];
+            pose_load(win, models[best].R, models[best].t);
             for (int j = 0; j < kAlignSample; j++) out.sample[j] = models[best].sample[j];
             out.sac_n_inliers = count[best];
             ans = win;

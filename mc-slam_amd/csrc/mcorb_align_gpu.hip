@@ -3,16 +3,16 @@
 //   k_align_hypotheses  one lane per hypothesis: the three draws, Horn's closed form on the three pairs (the Jacobi pairs and the
 //                       4 x 4 indices are compile-time constants: N and V are registers); a model record per hypothesis
 //   k_align_score       H x n distances: a workgroup owns a tile of kAlignTile pairs, which each lane keeps in registers, and a
-//                       block of kAlignHypBlock hypotheses, whose models it reads at uniform addresses; per model a ballot and a
-//                       population count per wave into integer counts in LDS, then one integer atomicAdd per (workgroup,
-//                       hypothesis) into count[H].  The additions are integer: the result does not depend on their order
-//   k_align_pick        every workgroup finds the arg-max of count[H] for itself and writes the winner's flags at the threshold for
-//                       its tile of pairs into member[n]; workgroup 0 writes the winner's record, both to device memory
-//   k_align_fit         ONE workgroup of 256: the two fold-ordered passes over the members (mode 0: all pairs), lane 0 solves,
-//                       then the workgroup strides over the n pairs for the verdict's flags, count and mean distance and writes
-//                       the record to host-mapped memory.  One workgroup is deliberate: the sums are floating-point and their
-//                       order is part of the definition; a grid-wide reduction would need a wait between workgroups or an
-//                       atomic whose order the hardware picks
+//                       block of kAlignHypBlock hypotheses, whose models it reads at uniform addresses: consensus_count
+//                       (mcorb_consensus.h)
+//   k_align_pick        every workgroup finds the arg-max of count[H] for itself (consensus_best_wg) and writes the winner's flags
+//                       at the threshold for its tile of pairs into member[n]; workgroup 0 writes the winner's record, both to
+//                       device memory
+//   k_align_fit         ONE workgroup of 256: the two passes over the members (mode 0: all pairs), folded in order by wg_fold of
+//                       mcorb_device.h, lane 0 solves, then the workgroup strides over the n pairs for the verdict's flags, count
+//                       and mean distance and writes the record to host-mapped memory.  One workgroup is deliberate: the sums are
+//                       floating-point and their order is part of the definition; a grid-wide reduction would need a wait between
+//                       workgroups or an atomic whose order the hardware picks
 // The arithmetic is the header's, so the host-only store gives the same bits.  No extraction job runs this and no benchmark leg
 // times it.
 #include <hip/hip_runtime.h>
@@ -25,8 +25,7 @@
 
 namespace mcorb {
 
-static_assert(kAlignTile == 4 * 64 && kAlignTile == kAlignLanes, "four waves, a lane of the fold each");
-static_assert(kAlignHypBlock <= kAlignTile, "a lane per hypothesis of the block adds its count");
+static_assert(kAlignTile == kWgLanes && kAlignTile == kAlignLanes, "mcorb_device.h's workgroup, a lane of pose_fold each");
 
 // the pairs as a lane reads them: frame 1's point is given or the store's landmark's
 struct AlignSrc {
@@ -42,14 +41,6 @@ struct AlignSrc {
     }
 };
 
-__device__ __forceinline__ void align_load(PoseState &P, const double *R, const double *t)
-{
-#pragma unroll
-    for (int j = 0; j < 9; j++) P.R[j] = R[j];
-#pragma unroll
-    for (int j = 0; j < 3; j++) P.t[j] = t[j];
-}
-
 __global__ __launch_bounds__(64) void k_align_hypotheses(const AlignJob *__restrict__ job, AlignSrc src, AlignModel *__restrict__ models)
 {
     const int h = blockIdx.x * 64 + threadIdx.x;
@@ -61,27 +52,19 @@ __global__ __launch_bounds__(kAlignTile) void k_align_score(const AlignJob *__re
                                                             const AlignModel *__restrict__ models, int32_t *__restrict__ count)
 {
     __shared__ int32_t cnt[kAlignHypBlock];
-    const int t = threadIdx.x, lane = t & 63;
-    const int n = job->n, H = job->H;
-    const int i = blockIdx.x * kAlignTile + t;
+    const int n = job->n;
+    const int i = blockIdx.x * kAlignTile + threadIdx.x;
     const bool in = i < n;
     const double threshold = job->threshold;
     double p1[3], p2[3];
     src(in ? i : 0, p1, p2);   // (n >= 1: a lane beyond the pairs scores pair 0 and counts nothing)
-    if (t < kAlignHypBlock) cnt[t] = 0;
-    __syncthreads();
-    const int h0 = blockIdx.y * kAlignHypBlock, h1 = min(H, h0 + kAlignHypBlock);
-    for (int h = h0; h < h1; h++) {
-        const AlignModel &M = models[h];   // (uniform over the workgroup)
-        if (!M.valid) continue;
-        PoseState P;
-        align_load(P, M.R, M.t);
-        const bool inl = in && sac_is_inlier(align_dist(P, p1, p2), threshold);
-        const unsigned long long mask = __ballot(inl);
-        if (lane == 0 && mask) atomicAdd(&cnt[h - h0], __popcll(mask));
-    }
-    __syncthreads();
-    if (t < h1 - h0 && cnt[t]) atomicAdd(&count[h0 + t], cnt[t]);
+    consensus_count<kAlignHypBlock>(
+        job->H, count, cnt, [&](int h) { return models[h].valid; },   // (uniform over the workgroup)
+        [&](int h) {
+            PoseState P;
+            pose_load(P, models[h].R, models[h].t);
+            return in && sac_is_inlier(align_dist(P, p1, p2), threshold);
+        });
 }
 
 __global__ __launch_bounds__(kAlignTile) void k_align_pick(const AlignJob *__restrict__ job, AlignSrc src,
@@ -90,32 +73,14 @@ __global__ __launch_bounds__(kAlignTile) void k_align_pick(const AlignJob *__res
 {
     __shared__ unsigned long long wkey[4];
     __shared__ int32_t wmodels[4];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int n = job->n, H = job->H;
-    unsigned long long key = 0;
-    int32_t nm = 0;
-    for (int h = t; h < H; h += kAlignTile) {
-        const int32_t valid = models[h].valid;
-        const unsigned long long kh = rel_key(valid, count[h], h);
-        key = kh > key ? kh : key;
-        nm += valid;
-    }
-    for (int s = 32; s >= 1; s >>= 1) {
-        const unsigned long long other = __shfl_xor(key, s, 64);
-        key = other > key ? other : key;
-        nm += __shfl_xor(nm, s, 64);
-    }
-    if (lane == 0) {
-        wkey[wave] = key;
-        wmodels[wave] = nm;
-    }
-    __syncthreads();
-    key = wkey[0];
-    for (int w = 1; w < 4; w++) key = wkey[w] > key ? wkey[w] : key;
-    const int best = rel_key_hypothesis(key);   // (the same in every lane)
+    const int t = threadIdx.x;
+    const int n = job->n;
+    int32_t n_models;
+    const int best = consensus_best_wg<kRelKeyBits, 1>(   // (the same in every lane)
+        job->H, [&](int h) { return models[h].valid; }, [&](int h) { return count[h]; }, wkey, wmodels, n_models);
     PoseState P;
-    align_identity(P);
-    if (best >= 0) align_load(P, models[best].R, models[best].t);
+    pose_identity(P);
+    if (best >= 0) pose_load(P, models[best].R, models[best].t);
     const int i = blockIdx.x * kAlignTile + t;
     if (i < n) {
         uint8_t flag = 0;
@@ -131,45 +96,27 @@ __global__ __launch_bounds__(kAlignTile) void k_align_pick(const AlignJob *__res
         for (int j = 0; j < 3; j++) pick->t[j] = P.t[j];
         pick->best = best;
         pick->count = best >= 0 ? count[best] : 0;
-        pick->n_models = (wmodels[0] + wmodels[1]) + (wmodels[2] + wmodels[3]);
+        pick->n_models = n_models;
         for (int j = 0; j < kAlignSample; j++) pick->sample[j] = best >= 0 ? models[best].sample[j] : -1;
     }
 }
 
-// the fold of the lanes' K sums: a wave's by shuffles with strides 32 .. 1 (lane 0 holds s[l] + s[l + stride] of pose_fold), the
-// four waves' through LDS as (b0 + b1) + (b2 + b3) -> the same bits in every lane.  part: [4][K] of LDS, free again on return
-template <int K>
-__device__ __forceinline__ void align_fold_wg(double s[K], double (*part)[kAlignSums2], double S[K])
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int stride = kAlignBlock / 2; stride >= 1; stride >>= 1)
-#pragma unroll
-        for (int k = 0; k < K; k++) s[k] = s[k] + __shfl_down(s[k], stride, 64);
-    if (lane == 0)
-#pragma unroll
-        for (int k = 0; k < K; k++) part[wave][k] = s[k];
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < K; k++) S[k] = (part[0][k] + part[1][k]) + (part[2][k] + part[3][k]);
-    __syncthreads();
-}
-
+// The folds are wg_fold's (mcorb_device.h), with a barrier behind each before part and wcnt are written again.
 __global__ __launch_bounds__(kAlignTile) void k_align_fit(const AlignJob *__restrict__ job, AlignSrc src, const AlignPick *pick,
                                                           const uint8_t *member, AlignOut *out, uint8_t *flags)
 {
-    __shared__ double part[kAlignBlocks][kAlignSums2];
-    __shared__ int32_t wcnt[kAlignBlocks];
+    __shared__ double part[kWgWaves][kAlignSums2];
+    __shared__ int32_t wcnt[kWgWaves];
     __shared__ double fitted[12];
     __shared__ int32_t fit_ok;
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int n = job->n;
     const bool all = job->mode == MCORB_ALIGN_MODE_ALL;
     PoseState win, ans;
-    align_identity(win);
+    pose_identity(win);
     int best = -1, sac_count = 0, n_models = 0;
     if (!all) {
-        align_load(win, pick->R, pick->t);
+        pose_load(win, pick->R, pick->t);
         best = pick->best;
         sac_count = pick->count;
         n_models = pick->n_models;
@@ -190,10 +137,11 @@ __global__ __launch_bounds__(kAlignTile) void k_align_fit(const AlignJob *__rest
             align_add1(p1, p2, s);
             mine++;
         }
-        for (int st = 32; st >= 1; st >>= 1) mine += __shfl_xor(mine, st, 64);
+        mine = wave_total(mine);
         if (lane == 0) wcnt[wave] = mine;
-        align_fold_wg<kAlignSums1>(s, part, S);   // (its barriers cover wcnt)
-        const int cnt = (wcnt[0] + wcnt[1]) + (wcnt[2] + wcnt[3]);
+        wg_fold<kAlignSums1>(s, part, S);   // (its barrier and the next cover wcnt)
+        __syncthreads();
+        const int cnt = wg_combine(wcnt);
         align_centroids(S, cnt, c1, c2);
         // pass 2: M
 #pragma unroll
@@ -204,7 +152,8 @@ __global__ __launch_bounds__(kAlignTile) void k_align_fit(const AlignJob *__rest
             src(i, p1, p2);
             align_add2(p1, p2, c1, c2, s);
         }
-        align_fold_wg<kAlignSums2>(s, part, S);
+        wg_fold<kAlignSums2>(s, part, S);
+        __syncthreads();
         if (t == 0) {
             PoseState P;
             const bool ok = align_from_sums(S, c1, c2, cnt, P, nullptr);
@@ -216,7 +165,7 @@ __global__ __launch_bounds__(kAlignTile) void k_align_fit(const AlignJob *__rest
         }
         __syncthreads();
         if (fit_ok) {
-            align_load(ans, fitted, fitted + 9);
+            pose_load(ans, fitted, fitted + 9);
             used = MCORB_ALIGN_USED_FIT;
             have = true;
         }
@@ -237,16 +186,16 @@ __global__ __launch_bounds__(kAlignTile) void k_align_fit(const AlignJob *__rest
         flags[i] = flag;
         inl += flag;
     }
-    for (int st = 32; st >= 1; st >>= 1) inl += __shfl_xor(inl, st, 64);
+    inl = wave_total(inl);
     if (lane == 0) wcnt[wave] = inl;
-    align_fold_wg<1>(d, part, D);
+    wg_fold<1>(d, part, D);   // (its barrier covers wcnt; nothing in LDS is written again)
     if (t == 0) {
         for (int j = 0; j < 9; j++) out->R[j] = ans.R[j], out->sac_R[j] = win.R[j];
         for (int j = 0; j < 3; j++) out->t[j] = ans.t[j], out->sac_t[j] = win.t[j];
         out->mean_error = have ? pose_default_nan(D[0] / (double)n) : 0.0;
         out->status = have ? MCORB_ALIGN_OK : MCORB_ALIGN_NO_MODEL;
         out->used = used;
-        out->n_inliers = (wcnt[0] + wcnt[1]) + (wcnt[2] + wcnt[3]);
+        out->n_inliers = wg_combine(wcnt);
         out->sac_n_inliers = sac_count;
         out->best = best;
         out->n_models = n_models;

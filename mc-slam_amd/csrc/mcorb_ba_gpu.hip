@@ -8,7 +8,7 @@
 //   k_ba_linearize   one lane per landmark: its observations in order -> V, gp, cost and its views (45 sums each); a lane holds
 //                    one view's sums in registers at a time.  Returns at once when the state has not moved since the last one
 //   k_ba_schur       one workgroup of 256 lanes per keyframe pair a <= b of the system (E_ab, 36 sums) and one per keyframe
-//                    (U_a and rhs_a, 27 sums): fold_j by wave shuffles and LDS, k_pose_refine's tree
+//                    (U_a and rhs_a, 27 sums): fold_j by wg_fold_waves and wg_combine of mcorb_device.h, k_pose_refine's tree
 //   k_ba_solve       one workgroup: S in LDS as a packed triangle, the LDL^T column by column (lane i computes L[i][j], every dot
 //                    product in ascending k), the forward substitution the same way, the backward one by lane 0 (its dot
 //                    products ascend while its rows descend); then the free poses retract into the trial half
@@ -31,7 +31,7 @@ namespace mcorb {
 constexpr int kBaT = MCORB_POSE_LANES;   // the fold's workgroup
 constexpr int kBaLmT = 64;               // the per-landmark kernels: one wave per workgroup, so that few landmarks still spread
 constexpr int kBaSolveT = 128;           // k_ba_solve: a lane per unknown (96 at most)
-static_assert(kBaT == 4 * 64 && kBaSolveT >= kBaMaxN, "four waves fold; a lane per unknown");
+static_assert(kBaT == kWgLanes && kBaSolveT >= kBaMaxN, "the workgroup of mcorb_device.h's reductions; a lane per unknown");
 
 __global__ __launch_bounds__(kBaT) void k_ba_begin(const BaArgs a)
 {
@@ -76,21 +76,12 @@ __global__ __launch_bounds__(kBaLmT) void k_ba_linearize(const BaArgs a)
     a.cost[j] = cost;
 }
 
-// the lanes' K sums -> out[K]: a wave folds with shuffles (strides 32 .. 1), lane 0 of each wave leaves the wave's sums in LDS
-// and, behind the barrier, lane k < K combines the four as (b0 + b1) + (b2 + b3)
+// the lanes' K sums -> out[K]: wg_fold's tree, but behind the barrier lane k < K alone combines the four waves' sum k
 template <int K>
 __device__ __forceinline__ void ba_fold_out(double s[K], double (*part)[K], double *out)
 {
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-#pragma unroll
-    for (int stride = 32; stride >= 1; stride >>= 1)
-#pragma unroll
-        for (int k = 0; k < K; k++) s[k] = s[k] + __shfl_down(s[k], stride, 64);
-    if (lane == 0)
-#pragma unroll
-        for (int k = 0; k < K; k++) part[wave][k] = s[k];
-    __syncthreads();
-    if (t < K) out[t] = (part[0][t] + part[1][t]) + (part[2][t] + part[3][t]);
+    wg_fold_waves<K>(s, part);
+    if (threadIdx.x < K) out[threadIdx.x] = wg_combine(part, threadIdx.x);
 }
 
 __global__ __launch_bounds__(kBaT) void k_ba_schur(const BaArgs a)
@@ -271,10 +262,10 @@ __global__ __launch_bounds__(kBaT) void k_ba_flags(const BaArgs a)
         in = ba_inlier(*a.job, a.poses + MCORB_BA_MAX_KF * cur, o, X);
         a.flags[o.orig] = (uint8_t)in;
     }
-    for (int o = 32; o >= 1; o >>= 1) in += __shfl_xor(in, o, 64);
+    in = wave_total(in);
     if ((threadIdx.x & 63) == 0) cnt[threadIdx.x >> 6] = in;
     __syncthreads();
-    if (threadIdx.x == 0) a.count[blockIdx.x] = (cnt[0] + cnt[1]) + (cnt[2] + cnt[3]);
+    if (threadIdx.x == 0) a.count[blockIdx.x] = wg_combine(cnt);
 }
 
 __global__ __launch_bounds__(kBaT) void k_ba_result(const BaArgs a, int nblocks)
@@ -284,7 +275,7 @@ __global__ __launch_bounds__(kBaT) void k_ba_result(const BaArgs a, int nblocks)
     const int t = threadIdx.x;
     int in = 0;
     for (int b = t; b < nblocks; b += kBaT) in += a.count[b];
-    for (int o = 32; o >= 1; o >>= 1) in += __shfl_xor(in, o, 64);
+    in = wave_total(in);
     if ((t & 63) == 0) cnt[t >> 6] = in;
     __syncthreads();
     if (t < a.nkf) {   // (member by member: a local copy's tail would live in scratch)
@@ -298,7 +289,7 @@ __global__ __launch_bounds__(kBaT) void k_ba_result(const BaArgs a, int nblocks)
     res.cost_final = pose_default_nan(r.cost);
     res.status = ba_status(r);
     res.iterations = r.solves;
-    res.n_inliers = (cnt[0] + cnt[1]) + (cnt[2] + cnt[3]);
+    res.n_inliers = wg_combine(cnt);
     res.n_obs = a.nobs;
 }
 

@@ -26,6 +26,65 @@ __device__ __forceinline__ void wave_lds_sync()
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
 }
+
+// The workgroup reductions of the pose estimators' kernels: a workgroup of kWgLanes = four waves of 64.  The LDS is the caller's and
+// is passed in.  The order of the additions below is part of the numeric contract (mcorb_pose.h's pose_fold states it for the host):
+// this is its one place on the device.
+constexpr int kWgLanes = 256, kWgWaves = 4;
+
+// the four waves' values of slot k, combined as (b0 + b1) + (b2 + b3)
+template <int KP>
+__device__ __forceinline__ double wg_combine(double (*part)[KP], int k) { return (part[0][k] + part[1][k]) + (part[2][k] + part[3][k]); }
+__device__ __forceinline__ int wg_combine(const int32_t *w) { return (w[0] + w[1]) + (w[2] + w[3]); }
+
+// a wave's fold of its lanes' K sums by shuffles with strides 32 .. 1: lane 0 holds s[l] + s[l + stride] of pose_fold
+template <int K>
+__device__ __forceinline__ void wave_fold(double s[K])
+{
+#pragma unroll
+    for (int stride = 32; stride >= 1; stride >>= 1)
+#pragma unroll
+        for (int k = 0; k < K; k++) s[k] = s[k] + __shfl_down(s[k], stride, 64);
+}
+// wave_fold, then lane 0 of each wave leaves the wave's sums in part[wave][0 .. K) and the workgroup meets at a barrier.
+// part: [4][KP] of LDS, KP >= K
+template <int K, int KP>
+__device__ __forceinline__ void wg_fold_waves(double s[K], double (*part)[KP])
+{
+    static_assert(K <= KP, "part holds a wave's K sums");
+    wave_fold<K>(s);
+    if (lane_id() == 0)
+#pragma unroll
+        for (int k = 0; k < K; k++) part[threadIdx.x >> 6][k] = s[k];
+    __syncthreads();
+}
+// the fold of the lanes' K sums -> S, the same bits in every lane.  No barrier behind the reads of part: the caller writes part
+// again only behind a barrier that every lane reaches after this returns
+template <int K, int KP>
+__device__ __forceinline__ void wg_fold(double s[K], double (*part)[KP], double S[K])
+{
+    wg_fold_waves<K>(s, part);
+#pragma unroll
+    for (int k = 0; k < K; k++) S[k] = wg_combine(part, k);
+}
+
+// the wave's sum of an integer, in every lane
+__device__ __forceinline__ int wave_total(int v)
+{
+    for (int s = 32; s >= 1; s >>= 1) v += __shfl_xor(v, s, 64);
+    return v;
+}
+// the workgroup's sum of an integer, the same in every lane; wcnt: [4] of LDS, free again on return
+__device__ __forceinline__ int wg_total(int v, int32_t *wcnt)
+{
+    v = wave_total(v);
+    if (lane_id() == 0) wcnt[threadIdx.x >> 6] = v;
+    __syncthreads();
+    const int total = wg_combine(wcnt);
+    __syncthreads();
+    return total;
+}
+
 // XCD-aware work index: workgroups b and b+8 share an XCD (and its L2) under the observed round-robin
 // placement, so give each XCD one contiguous eighth of the work items -- spatial neighbours (cells or
 // tiles that re-read the same 64-B lines for their halos) then hit in the same L2.  Bijective for any n;

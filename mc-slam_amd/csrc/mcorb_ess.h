@@ -25,8 +25,8 @@ constexpr int kEssNodes = 11;                  // the values of det C(z) that gi
 constexpr int kEssBisect = 48;                 // halvings of a bracket of the derivative chain
 constexpr int kEssPolish = 3;                  // Gauss-Newton steps on (x, y, z) against the ten cubics
 constexpr double kEssSelf = 1e-9;              // a model is kept iff its five rows and its ten cubics are below this
-constexpr int kEssKeyHyp = 14, kEssKeyRoot = 4;
-static_assert((1 << kEssKeyHyp) == MCORB_ESS_MAX_ITERATIONS && kEssRoots <= (1 << kEssKeyRoot), "the key holds every slot");
+constexpr int kEssKeyBits = 18;
+static_assert(MCORB_ESS_MAX_ITERATIONS * kEssRoots <= (1 << kEssKeyBits), "the key holds every slot");
 
 // a match as the kernels read it
 struct EssObs { float u1, v1, u2, v2; };
@@ -585,22 +585,8 @@ MCORB_POSE_HD bool ess_candidate_passes(const EssPick &P, int c, const EssPt &p,
     return ess_in_front(z1, z2, distance);
 }
 
-// the winner among the slots: the largest count of those with a model, a tie to the lowest hypothesis, then to the lowest root.
-// As a key that a maximum picks: (count + 1) << 18 | (16383 - h) << 4 | (15 - c) for a model, 0 without one
-MCORB_POSE_HD uint64_t ess_key(int32_t valid, int32_t count, int slot)
-{
-    const int h = slot / kEssRoots, c = slot % kEssRoots;
-    return valid ? (((uint64_t)count + 1) << (kEssKeyHyp + kEssKeyRoot)) | ((uint64_t)((1 << kEssKeyHyp) - 1 - h) << kEssKeyRoot) |
-                       (uint64_t)((1 << kEssKeyRoot) - 1 - c)
-                 : 0;
-}
-MCORB_POSE_HD int ess_key_slot(uint64_t key)
-{
-    if (!key) return -1;
-    const int h = (1 << kEssKeyHyp) - 1 - (int)((key >> kEssKeyRoot) & ((1 << kEssKeyHyp) - 1));
-    const int c = (1 << kEssKeyRoot) - 1 - (int)(key & ((1 << kEssKeyRoot) - 1));
-    return h * kEssRoots + c;
-}
+// the winner among the slots: the largest count of those with a model, a tie to the lowest hypothesis, then to the lowest root --
+// the order by slot = h * kEssRoots + c, so consensus_key (mcorb_consensus.h) over the slot
 
 // what k_ess_pick writes once the winner is known
 MCORB_POSE_HD void ess_pick(const EssModel *models, const int32_t *count, int slot, int n_models, EssPick &P)
@@ -649,8 +635,6 @@ inline void ess_run_serial(const EssJob &job, const EssObs *obs, EssModel *model
                            uint8_t *flags)
 {
     for (int k = 0; k < job.S; k++) ess_point(job, (double)obs[k].u1, (double)obs[k].v1, (double)obs[k].u2, (double)obs[k].v2, pts[k]);
-    uint64_t key = 0;
-    int n_models = 0;
     for (int h = 0; h < job.H; h++) {
         ess_hypothesis(job, h, obs, models + kEssRoots * h, samples + kEssSample * h);
         for (int c = 0; c < kEssRoots; c++) {
@@ -659,13 +643,12 @@ inline void ess_run_serial(const EssJob &job, const EssObs *obs, EssModel *model
             count[slot] = 0;
             if (M.valid)
                 for (int k = 0; k < job.S; k++) count[slot] += sac_is_inlier(ess_sampson(M.E, pts[k]), job.threshold2) ? 1 : 0;
-            const uint64_t ks = ess_key(M.valid, count[slot], slot);
-            key = ks > key ? ks : key;
-            n_models += M.valid;
         }
     }
+    const ConsensusBest won =
+        consensus_best<kEssKeyBits>(job.H * kEssRoots, [&](int s) { return models[s].valid; }, [&](int s) { return count[s]; });
     EssPick P;
-    ess_pick(models, count, ess_key_slot(key), n_models, P);
+    ess_pick(models, count, consensus_key_index<kEssKeyBits>(won.key), won.n_models, P);
     int32_t cheir[4] = {0, 0, 0, 0};
     if (P.slot >= 0)
         for (int k = 0; k < job.S; k++)

@@ -9,15 +9,14 @@
 //                      Lane r < 10: the model of root r into its slot
 //   k_ess_score        the hot path, 10 H x S Sampson distances: a workgroup owns a tile of kEssTile matches, whose normalised
 //                      points each lane computes once, and a block of kEssSlotBlock slots, whose models it reads at uniform
-//                      addresses; per model a ballot and a population count per wave into integer counts in LDS, then one
-//                      integer atomicAdd per (workgroup, slot).  Slots without a model are skipped uniformly
-//   k_ess_pick         every workgroup finds the arg-max of the slots' keys for itself, forms the four candidates from the
-//                      winner -- the same bits in every workgroup -- and adds its matches' four votes to four integers;
+//                      addresses: consensus_count (mcorb_consensus.h).  Slots without a model are skipped uniformly
+//   k_ess_pick         every workgroup finds the arg-max of the slots' keys for itself (consensus_best_wg), forms the four candidates
+//                      from the winner -- the same bits in every workgroup -- and adds its matches' four votes to four integers;
 //                      workgroup 0 leaves the winner and its candidates for k_ess_finish
 //   k_ess_finish       reads the four votes, writes the flags of its tile; workgroup 0 writes the record to host-mapped memory
 //   k_ess_fit          the polished call only, behind a k_ess_finish whose record and flags stay in device memory: ONE workgroup of
-//                      256 -- the rounds of mcorb_ess_polish.h (ess_fit_round over the members, the 21 sums folded as
-//                      k_pose_refine folds them, then all S matches tested at the result), and the accepted record, its flags
+//                      256 -- the rounds of mcorb_ess_polish.h (ess_fit_round over the members, the 21 sums folded by wg_fold of
+//                      mcorb_device.h, then all S matches tested at the result), and the accepted record, its flags
 //                      and the polish record to host-mapped memory
 // No extraction job runs this and no benchmark leg times it.
 #include <hip/hip_runtime.h>
@@ -30,9 +29,7 @@
 
 namespace mcorb {
 
-static_assert(kEssTile == 4 * 64, "four waves");
-static_assert(kEssSlotBlock <= kEssTile, "a lane per slot of the block adds its count");
-static_assert(kEssTile == MCORB_POSE_LANES && kPoseBlocks == 4, "k_ess_fit: a lane of the fold each");
+static_assert(kEssTile == kWgLanes && kEssTile == MCORB_POSE_LANES, "mcorb_device.h's workgroup, a lane of pose_fold each");
 static_assert(kEssLanes >= kEssNodes && kEssLanes >= kEssRoots + 1 && 64 % kEssLanes == 0, "a lane per node, per bracket and per root");
 
 // what the lanes of one hypothesis share
@@ -136,28 +133,20 @@ __global__ __launch_bounds__(kEssTile) void k_ess_score(const EssJob *__restrict
                                                         const EssModel *__restrict__ models, int32_t *__restrict__ count)
 {
     __shared__ int32_t cnt[kEssSlotBlock];
-    const int t = threadIdx.x, lane = t & 63;
-    const int S = job->S, N = job->H * kEssRoots;
-    const int k = blockIdx.x * kEssTile + t;
+    const int S = job->S;
+    const int k = blockIdx.x * kEssTile + threadIdx.x;
     const bool in = k < S;
     const double threshold2 = job->threshold2;
     EssPt p;
     ess_point_of(*job, obs[in ? k : 0], p);   // (S >= 1: a lane beyond the matches scores match 0 and counts nothing)
-    if (t < kEssSlotBlock) cnt[t] = 0;
-    __syncthreads();
-    const int s0 = blockIdx.y * kEssSlotBlock, s1 = min(N, s0 + kEssSlotBlock);
-    for (int s = s0; s < s1; s++) {
-        const EssModel &M = models[s];   // (uniform over the workgroup)
-        if (!M.valid) continue;
-        double E[9];
+    consensus_count<kEssSlotBlock>(
+        job->H * kEssRoots, count, cnt, [&](int s) { return models[s].valid; },   // (uniform over the workgroup)
+        [&](int s) {
+            double E[9];
 #pragma unroll
-        for (int j = 0; j < 9; j++) E[j] = M.E[j];
-        const bool inl = in && sac_is_inlier(ess_sampson(E, p), threshold2);
-        const unsigned long long mask = __ballot(inl);
-        if (lane == 0 && mask) atomicAdd(&cnt[s - s0], __popcll(mask));
-    }
-    __syncthreads();
-    if (t < s1 - s0 && cnt[t]) atomicAdd(&count[s0 + t], cnt[t]);
+            for (int j = 0; j < 9; j++) E[j] = models[s].E[j];
+            return in && sac_is_inlier(ess_sampson(E, p), threshold2);
+        });
 }
 
 __global__ __launch_bounds__(kEssTile) void k_ess_pick(const EssJob *__restrict__ job, const EssObs *__restrict__ obs,
@@ -168,42 +157,15 @@ __global__ __launch_bounds__(kEssTile) void k_ess_pick(const EssJob *__restrict_
     __shared__ unsigned long long wkey[4];
     __shared__ int32_t wmodels[4], votes[4];
     __shared__ EssPick P;
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int S = job->S, N = job->H * kEssRoots;
-    unsigned long long key = 0;
-    int32_t nm = 0;
-    // (eight trips' loads at a time: a trip alone waits out two loads' latency, 390 times at 10 000 hypotheses)
-    for (int s0 = t; s0 < N; s0 += 8 * kEssTile) {
-        int32_t v[8], c[8];
-#pragma unroll
-        for (int u = 0; u < 8; u++) {
-            const int s = s0 + u * kEssTile;
-            v[u] = s < N ? valid[s] : 0;   // (models[s].valid, read densely)
-            c[u] = s < N ? count[s] : 0;
-        }
-#pragma unroll
-        for (int u = 0; u < 8; u++) {
-            const unsigned long long ks = ess_key(v[u], c[u], s0 + u * kEssTile);
-            key = ks > key ? ks : key;
-            nm += v[u];
-        }
-    }
-    for (int s = 32; s >= 1; s >>= 1) {
-        const unsigned long long other = __shfl_xor(key, s, 64);
-        key = other > key ? other : key;
-        nm += __shfl_xor(nm, s, 64);
-    }
-    if (lane == 0) {
-        wkey[wave] = key;
-        wmodels[wave] = nm;
-    }
+    const int t = threadIdx.x, lane = t & 63;
+    const int S = job->S;
     if (t < 4) votes[t] = 0;
-    __syncthreads();
-    if (t == 0) {
-        key = wkey[0];
-        for (int w = 1; w < 4; w++) key = wkey[w] > key ? wkey[w] : key;
-        ess_pick(models, count, ess_key_slot(key), (wmodels[0] + wmodels[1]) + (wmodels[2] + wmodels[3]), P);
-    }
+    // (eight trips' loads at a time: a trip alone waits out two loads' latency, 390 times at 10 000 hypotheses)
+    int32_t n_models;
+    const int slot = consensus_best_wg<kEssKeyBits, 8>(
+        job->H * kEssRoots, [&](int s) { return valid[s]; },   // (models[s].valid, read densely)
+        [&](int s) { return count[s]; }, wkey, wmodels, n_models);
+    if (t == 0) ess_pick(models, count, slot, n_models, P);
     __syncthreads();
     const int i = blockIdx.x * kEssTile + t;
     bool pass[4] = {false, false, false, false};
@@ -250,10 +212,10 @@ __global__ __launch_bounds__(kEssTile) void k_ess_finish(const EssJob *__restric
 
 // a pass of k_ess_fit: the 21 sums at P over the members, the same bits in every lane.  Lanes 0 .. 5 leave E of P and of its five
 // perturbations in LDS; every lane takes the 54 numbers into registers at uniform addresses (broadcasts), walks members t, t + 256,
-// .. with its 21 sums in registers, and the workgroup folds as k_pose_refine does.  A member's EssPt is computed again from its
+// .. with its 21 sums in registers, and the workgroup folds them (wg_fold).  A member's EssPt is computed again from its
 // EssObs in every pass, as k_ess_score does it: four divisions next to the six residuals' six divisions and six square roots,
 // against a buffer of 32 bytes per match that would follow n and be read back in its place.  Both barriers are met by every lane;
-// Es and part are written again only behind a barrier that every lane reaches after it has read them
+// Es and part are written again only behind a barrier that every lane reaches after it has read them: the next pass's first
 struct EssFitPass {
     const EssJob *job;
     const EssObs *obs;
@@ -264,7 +226,7 @@ struct EssFitPass {
     double (*part)[kEssFitSums];
     __device__ __forceinline__ void operator()(const PoseState &P, double sums[kEssFitSums])
     {
-        const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+        const int t = threadIdx.x;
         if (t < kEssFitPoses) {
             PoseState Q;
             double E[9];
@@ -287,29 +249,9 @@ struct EssFitPass {
             ess_point_of(*job, obs[i], p);
             ess_fit_add(E, p, inv_thr, s);
         }
-#pragma unroll
-        for (int stride = kPoseBlock / 2; stride >= 1; stride >>= 1)
-#pragma unroll
-            for (int k = 0; k < kEssFitSums; k++) s[k] = s[k] + __shfl_down(s[k], stride, 64);
-        if (lane == 0)
-#pragma unroll
-            for (int k = 0; k < kEssFitSums; k++) part[wave][k] = s[k];
-        __syncthreads();
-#pragma unroll
-        for (int k = 0; k < kEssFitSums; k++) sums[k] = (part[0][k] + part[1][k]) + (part[2][k] + part[3][k]);
+        wg_fold<kEssFitSums>(s, part, sums);
     }
 };
-
-// the workgroup's sum of an integer, the same in every lane; wcnt is free again on return
-__device__ __forceinline__ int ess_fit_total(int v, int32_t *wcnt)
-{
-    for (int s = 32; s >= 1; s >>= 1) v += __shfl_xor(v, s, 64);
-    if ((threadIdx.x & 63) == 0) wcnt[threadIdx.x >> 6] = v;
-    __syncthreads();
-    const int total = (wcnt[0] + wcnt[1]) + (wcnt[2] + wcnt[3]);
-    __syncthreads();
-    return total;
-}
 
 // The polished call only, behind a k_ess_finish whose record and flags stay in device memory.  ONE workgroup, for k_align_fit's
 // reason: the sums are floating-point and their order is part of the definition.  pick and member[0 .. S) are what k_ess_finish
@@ -329,7 +271,7 @@ __global__ __launch_bounds__(kEssTile) void k_ess_fit(const EssJob *__restrict__
     PoseState cur;
     double E[9];
 #pragma unroll
-    for (int j = 0; j < 9; j++) cur.R[j] = pick->R[j];
+    for (int j = 0; j < 9; j++) cur.R[j] = pick->R[j];   // (not pose_load, as in k_rel_fit)
 #pragma unroll
     for (int j = 0; j < 3; j++) cur.t[j] = pick->t[j];
 #pragma unroll
@@ -343,7 +285,7 @@ __global__ __launch_bounds__(kEssTile) void k_ess_fit(const EssJob *__restrict__
             pass.member = curf;
             int mine = 0;
             for (int i = t; i < S; i += kEssTile) mine += curf[i] ? 1 : 0;
-            const int members = ess_fit_total(mine, wcnt);
+            const int members = wg_total(mine, wcnt);
             PoseState cand;
             double c0, c1, Ec[9];
             int32_t its, status;
@@ -359,8 +301,8 @@ __global__ __launch_bounds__(kEssTile) void k_ess_fit(const EssJob *__restrict__
                 within_mine += within ? 1 : 0;
                 in += flag ? 1 : 0;
             }
-            const int nr = ess_fit_total(within_mine, wcnt);
-            const int n = ess_fit_total(in, wcnt);
+            const int nr = wg_total(within_mine, wcnt);
+            const int n = wg_total(in, wcnt);
             const bool accepted = n >= count;
             if (t == 0) {
                 mcorb_ess_polish_round &q = polish->round[round];

@@ -28,6 +28,22 @@ namespace mcorb {
 // (R, t) = w_T_b, the body's pose in the world, R row-major
 struct PoseState { double R[9], t[3]; };
 
+// a model's R[9], t[3] into a PoseState, and the pose of a call without a model: copies of doubles, no arithmetic
+MCORB_POSE_HD void pose_load(PoseState &P, const double *R, const double *t)
+{
+#pragma unroll
+    for (int j = 0; j < 9; j++) P.R[j] = R[j];
+#pragma unroll
+    for (int j = 0; j < 3; j++) P.t[j] = t[j];
+}
+MCORB_POSE_HD void pose_identity(PoseState &P)
+{
+#pragma unroll
+    for (int j = 0; j < 9; j++) P.R[j] = (j % 4 == 0) ? 1.0 : 0.0;
+#pragma unroll
+    for (int j = 0; j < 3; j++) P.t[j] = 0.0;
+}
+
 // the 28 sums of a pass: the 21 upper entries of H row by row, the 6 of g, the cost
 constexpr int kPoseSums = 28, kPoseG = 21, kPoseCost = 27;
 constexpr int kPoseBlock = 64, kPoseBlocks = MCORB_POSE_LANES / kPoseBlock;

@@ -1,8 +1,7 @@
 // mcorb_pose_gpu.hip -- k_pose_refine: the rig pose refinement of mcorb_pose.h on a device store (mcorb_pose.cpp), both rounds of
 // FrontEnd::OptimizePose (MCSlam/src/FrontEnd.cpp:4361-4400) in one launch.  One workgroup of MCORB_POSE_LANES lanes per problem.
-// A pass over the observations re-reads them from L2: lane l adds observations l, l + 256, .. into its 28 sums, a wave folds them
-// with shuffles (strides 32 .. 1), lane 0 of each wave leaves the wave's sums in LDS and, behind the workgroup barrier, every lane
-// combines the four as (b0 + b1) + (b2 + b3) -- the tree mcorb_pose.h states, so the host-only store gives the same bits.  Every
+// A pass over the observations re-reads them from L2: lane l adds observations l, l + 256, .. into its 28 sums and the workgroup
+// folds them by wg_fold of mcorb_device.h -- the tree mcorb_pose.h states, so the host-only store gives the same bits.  Every
 // lane then solves the 6 x 6 system and retracts for itself: all lanes hold the same pose, take the same branches and meet at the
 // same barriers.  The barrier is the only synchronisation: no workgroup waits on another, no atomics, no scratch.  An
 // observation's flag is read and written by the one lane that serves it.  No extraction job runs this and no benchmark leg
@@ -18,7 +17,7 @@
 namespace mcorb {
 
 constexpr int kPoseT = MCORB_POSE_LANES;
-static_assert(kPoseT == 4 * 64, "four waves");
+static_assert(kPoseT == kWgLanes, "the workgroup of mcorb_device.h's reductions");
 
 // the observations of one problem as a lane reads them
 struct PoseSrc {
@@ -45,7 +44,6 @@ struct PosePass {
     int half;
     __device__ __forceinline__ void operator()(const PoseState &P, double S[kPoseSums])
     {
-        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
         double s[kPoseSums];
 #pragma unroll
         for (int k = 0; k < kPoseSums; k++) s[k] = 0.0;
@@ -56,16 +54,7 @@ struct PosePass {
             src.point(i, X);
             pose_add(src.job->cams[o.cam], P, X, o.u, o.v, src.job->huber_k, s);
         }
-#pragma unroll
-        for (int stride = kPoseBlock / 2; stride >= 1; stride >>= 1)
-#pragma unroll
-            for (int k = 0; k < kPoseSums; k++) s[k] = s[k] + __shfl_down(s[k], stride, 64);
-        if (lane == 0)
-#pragma unroll
-            for (int k = 0; k < kPoseSums; k++) part[half][wave][k] = s[k];
-        __syncthreads();
-#pragma unroll
-        for (int k = 0; k < kPoseSums; k++) S[k] = (part[half][0][k] + part[half][1][k]) + (part[half][2][k] + part[half][3][k]);
+        wg_fold<kPoseSums>(s, part[half], S);
         half ^= 1;
     }
 };
@@ -181,12 +170,11 @@ __global__ __launch_bounds__(kPoseT) void k_pose_refine(const PoseJob *__restric
         flags[i] = a;
         in += a;
     }
-    for (int o = 32; o >= 1; o >>= 1) in += __shfl_xor(in, o, 64);
+    in = wave_total(in);
     if ((t & 63) == 0) cnt[t >> 6] = in;
     __syncthreads();
     if (t == 0)
-        pose_write(res, pose, pose_default_nan(cost_initial), pose_default_nan(cost_final), status, its0, its1,
-                   (cnt[0] + cnt[1]) + (cnt[2] + cnt[3]), n);
+        pose_write(res, pose, pose_default_nan(cost_initial), pose_default_nan(cost_final), status, its0, its1, wg_combine(cnt), n);
 }
 
 void launch_pose_refine(hipStream_t st, const PoseJob *jobs, int njobs, PoseObs *obs, int32_t *lids, const double *pts, const double *geom,

@@ -420,48 +420,31 @@ MCORB_POSE_HD void rel_hypothesis(const RelJob &job, int h, const RelObs *obs, R
     rel_write_model(M, ok, P, sample);
 }
 
-// the winner among H hypotheses: the largest count of those with a model, a tie to the lowest h.  As a key that a maximum picks:
-// (count + 1) << 14 | (16383 - h) for a model, 0 without one
-MCORB_POSE_HD uint64_t rel_key(int32_t valid, int32_t count, int h)
-{
-    return valid ? (((uint64_t)count + 1) << kRelKeyBits) | (uint64_t)((1 << kRelKeyBits) - 1 - h) : 0;
-}
-MCORB_POSE_HD int rel_key_hypothesis(uint64_t key) { return key ? (1 << kRelKeyBits) - 1 - (int)(key & ((1 << kRelKeyBits) - 1)) : -1; }
-
 // The three kernels, serially: what a host-only store runs (mcorb_rel.cpp).  models[H], count[H] and rays[S] are the caller's
 // scratch; flags: S, written.  job.S >= 1
 inline void rel_run_serial(const RelJob &job, const RelObs *obs, RelModel *models, int32_t *count, RelRays *rays, RelOut &out, uint8_t *flags)
 {
     for (int k = 0; k < job.S; k++) rel_rays(job.cams, obs[k], rays[k]);
-    uint64_t key = 0;
-    int n_models = 0;
+    PoseState P;
     for (int h = 0; h < job.H; h++) {
         RelModel &M = models[h];
         rel_hypothesis(job, h, obs, M);
         count[h] = 0;
-        if (M.valid) {
-            PoseState P;
-            for (int j = 0; j < 9; j++) P.R[j] = M.R[j];
-            for (int j = 0; j < 3; j++) P.t[j] = M.t[j];
-            for (int k = 0; k < job.S; k++) count[h] += sac_is_inlier(rel_score(P, rays[k]), job.threshold) ? 1 : 0;
-        }
-        const uint64_t kh = rel_key(M.valid, count[h], h);
-        key = kh > key ? kh : key;
-        n_models += M.valid;
+        if (!M.valid) continue;
+        pose_load(P, M.R, M.t);
+        for (int k = 0; k < job.S; k++) count[h] += sac_is_inlier(rel_score(P, rays[k]), job.threshold) ? 1 : 0;
     }
-    const int best = rel_key_hypothesis(key);
-    PoseState P = PoseState{{1, 0, 0, 0, 1, 0, 0, 0, 1}, {0, 0, 0}};
-    if (best >= 0) {
-        for (int j = 0; j < 9; j++) P.R[j] = models[best].R[j];
-        for (int j = 0; j < 3; j++) P.t[j] = models[best].t[j];
-    }
+    const ConsensusBest won = consensus_best<kRelKeyBits>(job.H, [&](int h) { return models[h].valid; }, [&](int h) { return count[h]; });
+    const int best = consensus_key_index<kRelKeyBits>(won.key);
+    pose_identity(P);
+    if (best >= 0) pose_load(P, models[best].R, models[best].t);
     for (int k = 0; k < job.S; k++) flags[k] = best >= 0 && sac_is_inlier(rel_score(P, rays[k]), job.threshold) ? 1 : 0;
     for (int j = 0; j < 9; j++) out.R[j] = P.R[j];
     for (int j = 0; j < 3; j++) out.t[j] = P.t[j];
     out.status = best >= 0 ? MCORB_REL_OK : MCORB_REL_NO_MODEL;
     out.n_inliers = best >= 0 ? count[best] : 0;
     out.best = best;
-    out.n_models = n_models;
+    out.n_models = won.n_models;
     for (int j = 0; j < kRelSample; j++) out.sample[j] = best >= 0 ? models[best].sample[j] : -1;
     for (int j = 0; j < 3; j++) out.pad[j] = 0;
 }

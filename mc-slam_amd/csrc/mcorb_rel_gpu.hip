@@ -5,14 +5,12 @@
 //                      record per hypothesis
 //   k_rel_score        the hot path, H x S two-view midpoint triangulations with two angles each: a workgroup owns a tile of
 //                      kRelTile matches, whose four ray vectors each lane computes once and keeps in registers, and a block of
-//                      kRelHypBlock hypotheses, whose models it reads at uniform addresses; per model a ballot and a population
-//                      count per wave into integer counts in LDS, then one integer atomicAdd per (workgroup, hypothesis) into
-//                      count[H].  The additions are integer: the result does not depend on their order
-//   k_rel_pick         every workgroup finds the arg-max of count[H] for itself and writes the winner's flags for its tile of
-//                      matches; workgroup 0 writes the record to host-mapped memory
+//                      kRelHypBlock hypotheses, whose models it reads at uniform addresses: consensus_count (mcorb_consensus.h)
+//   k_rel_pick         every workgroup finds the arg-max of count[H] for itself (consensus_best_wg) and writes the winner's flags
+//                      for its tile of matches; workgroup 0 writes the record to host-mapped memory
 //   k_rel_fit          the polished call only, behind a k_rel_pick whose record and flags stay in device memory: ONE workgroup of
-//                      256 -- the rounds of the header's polish (pose_round over the members, the 28 sums folded as k_pose_refine
-//                      folds them, then all S matches scored at the result), and the accepted record, its flags and the polish
+//                      256 -- the rounds of the header's polish (pose_round over the members, the 28 sums folded by wg_fold of
+//                      mcorb_device.h, then all S matches scored at the result), and the accepted record, its flags and the polish
 //                      record to host-mapped memory
 // The arithmetic is the header's, so the host-only store gives the same bits.  No extraction job runs this and no benchmark leg
 // times it.
@@ -26,9 +24,7 @@
 
 namespace mcorb {
 
-static_assert(kRelTile == 4 * 64, "four waves");
-static_assert(kRelHypBlock <= kRelTile, "a lane per hypothesis of the block adds its count");
-static_assert(kRelTile == MCORB_POSE_LANES && kPoseBlocks == 4, "k_rel_fit: a lane of the fold each");
+static_assert(kRelTile == kWgLanes && kRelTile == MCORB_POSE_LANES, "mcorb_device.h's workgroup, a lane of pose_fold each");
 
 __global__ __launch_bounds__(64) void k_rel_hypotheses(const RelJob *__restrict__ job, const RelObs *__restrict__ obs,
                                                        RelModel *__restrict__ models)
@@ -42,30 +38,19 @@ __global__ __launch_bounds__(kRelTile) void k_rel_score(const RelJob *__restrict
                                                         const RelModel *__restrict__ models, int32_t *__restrict__ count)
 {
     __shared__ int32_t cnt[kRelHypBlock];
-    const int t = threadIdx.x, lane = t & 63;
-    const int S = job->S, H = job->H;
-    const int k = blockIdx.x * kRelTile + t;
+    const int S = job->S;
+    const int k = blockIdx.x * kRelTile + threadIdx.x;
     const bool in = k < S;
     const double threshold = job->threshold;
     RelRays r;
     rel_rays(job->cams, obs[in ? k : 0], r);   // (S >= 1: a lane beyond the matches scores match 0 and counts nothing)
-    if (t < kRelHypBlock) cnt[t] = 0;
-    __syncthreads();
-    const int h0 = blockIdx.y * kRelHypBlock, h1 = min(H, h0 + kRelHypBlock);
-    for (int h = h0; h < h1; h++) {
-        const RelModel &M = models[h];   // (uniform over the workgroup)
-        if (!M.valid) continue;
-        PoseState P;
-#pragma unroll
-        for (int j = 0; j < 9; j++) P.R[j] = M.R[j];
-#pragma unroll
-        for (int j = 0; j < 3; j++) P.t[j] = M.t[j];
-        const bool inl = in && sac_is_inlier(rel_score(P, r), threshold);
-        const unsigned long long mask = __ballot(inl);
-        if (lane == 0 && mask) atomicAdd(&cnt[h - h0], __popcll(mask));
-    }
-    __syncthreads();
-    if (t < h1 - h0 && cnt[t]) atomicAdd(&count[h0 + t], cnt[t]);
+    consensus_count<kRelHypBlock>(
+        job->H, count, cnt, [&](int h) { return models[h].valid; },   // (uniform over the workgroup)
+        [&](int h) {
+            PoseState P;
+            pose_load(P, models[h].R, models[h].t);
+            return in && sac_is_inlier(rel_score(P, r), threshold);
+        });
 }
 
 __global__ __launch_bounds__(kRelTile) void k_rel_pick(const RelJob *__restrict__ job, const RelObs *__restrict__ obs,
@@ -74,41 +59,14 @@ __global__ __launch_bounds__(kRelTile) void k_rel_pick(const RelJob *__restrict_
 {
     __shared__ unsigned long long wkey[4];
     __shared__ int32_t wmodels[4];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int S = job->S, H = job->H;
-    unsigned long long key = 0;
-    int32_t nm = 0;
-    for (int h = t; h < H; h += kRelTile) {
-        const int32_t valid = models[h].valid;
-        const unsigned long long kh = rel_key(valid, count[h], h);
-        key = kh > key ? kh : key;
-        nm += valid;
-    }
-    for (int s = 32; s >= 1; s >>= 1) {
-        const unsigned long long other = __shfl_xor(key, s, 64);
-        key = other > key ? other : key;
-        nm += __shfl_xor(nm, s, 64);
-    }
-    if (lane == 0) {
-        wkey[wave] = key;
-        wmodels[wave] = nm;
-    }
-    __syncthreads();
-    key = wkey[0];
-    for (int w = 1; w < 4; w++) key = wkey[w] > key ? wkey[w] : key;
-    const int best = rel_key_hypothesis(key);   // (the same in every lane)
+    const int t = threadIdx.x;
+    const int S = job->S;
+    int32_t n_models;
+    const int best = consensus_best_wg<kRelKeyBits, 1>(   // (the same in every lane)
+        job->H, [&](int h) { return models[h].valid; }, [&](int h) { return count[h]; }, wkey, wmodels, n_models);
     PoseState P;
-#pragma unroll
-    for (int j = 0; j < 9; j++) P.R[j] = (j % 4 == 0) ? 1.0 : 0.0;
-#pragma unroll
-    for (int j = 0; j < 3; j++) P.t[j] = 0.0;
-    if (best >= 0) {
-        const RelModel &M = models[best];
-#pragma unroll
-        for (int j = 0; j < 9; j++) P.R[j] = M.R[j];
-#pragma unroll
-        for (int j = 0; j < 3; j++) P.t[j] = M.t[j];
-    }
+    pose_identity(P);
+    if (best >= 0) pose_load(P, models[best].R, models[best].t);
     const int i = blockIdx.x * kRelTile + t;
     if (i < S) {
         uint8_t flag = 0;
@@ -125,7 +83,7 @@ __global__ __launch_bounds__(kRelTile) void k_rel_pick(const RelJob *__restrict_
         out->status = best >= 0 ? MCORB_REL_OK : MCORB_REL_NO_MODEL;
         out->n_inliers = best >= 0 ? count[best] : 0;
         out->best = best;
-        out->n_models = (wmodels[0] + wmodels[1]) + (wmodels[2] + wmodels[3]);
+        out->n_models = n_models;
         for (int j = 0; j < kRelSample; j++) out->sample[j] = best >= 0 ? models[best].sample[j] : -1;
         for (int j = 0; j < 3; j++) out->pad[j] = 0;
     }
@@ -140,8 +98,8 @@ struct RelFitLaneSums {
 
 // a pass of k_rel_fit: the 28 sums at P over the members, the same bits in every lane.  Lanes 0 .. 6 leave P and its six
 // perturbations in LDS, every lane reads them at uniform addresses; lane l adds members l, l + 256, .. into its column of acc,
-// takes the 28 into registers, and the workgroup folds as k_pose_refine does.  Both barriers are met by every lane; poses and
-// part are written again only behind a barrier that every lane reaches after it has read them
+// takes the 28 into registers, and the workgroup folds them (wg_fold).  Both barriers are met by every lane; poses and part are
+// written again only behind a barrier that every lane reaches after it has read them: the next pass's first
 struct RelFitPass {
     const RelJob *job;
     const RelObs *obs;
@@ -153,14 +111,11 @@ struct RelFitPass {
     double (*acc)[kRelTile];
     __device__ __forceinline__ void operator()(const PoseState &P, double sums[kPoseSums])
     {
-        const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+        const int t = threadIdx.x;
         if (t < kRelFitPoses) {
             PoseState Q;
             rel_fit_pose(P, t, Q);
-#pragma unroll
-            for (int j = 0; j < 9; j++) poses[t].R[j] = Q.R[j];
-#pragma unroll
-            for (int j = 0; j < 3; j++) poses[t].t[j] = Q.t[j];
+            pose_load(poses[t], Q.R, Q.t);
         }
         __syncthreads();
         const RelFitLaneSums mine{&acc[0][t]};
@@ -175,29 +130,9 @@ struct RelFitPass {
         double s[kPoseSums];
 #pragma unroll
         for (int k = 0; k < kPoseSums; k++) s[k] = mine[k];
-#pragma unroll
-        for (int stride = kPoseBlock / 2; stride >= 1; stride >>= 1)
-#pragma unroll
-            for (int k = 0; k < kPoseSums; k++) s[k] = s[k] + __shfl_down(s[k], stride, 64);
-        if (lane == 0)
-#pragma unroll
-            for (int k = 0; k < kPoseSums; k++) part[wave][k] = s[k];
-        __syncthreads();
-#pragma unroll
-        for (int k = 0; k < kPoseSums; k++) sums[k] = (part[0][k] + part[1][k]) + (part[2][k] + part[3][k]);
+        wg_fold<kPoseSums>(s, part, sums);
     }
 };
-
-// the workgroup's sum of an integer, the same in every lane; wcnt is free again on return
-__device__ __forceinline__ int rel_fit_total(int v, int32_t *wcnt)
-{
-    for (int s = 32; s >= 1; s >>= 1) v += __shfl_xor(v, s, 64);
-    if ((threadIdx.x & 63) == 0) wcnt[threadIdx.x >> 6] = v;
-    __syncthreads();
-    const int total = (wcnt[0] + wcnt[1]) + (wcnt[2] + wcnt[3]);
-    __syncthreads();
-    return total;
-}
 
 // ONE workgroup, for k_align_fit's reason: the sums are floating-point and their order is part of the definition.  pick and
 // member[0 .. S) are what k_rel_pick left in device memory; nothing host-mapped is read.  Every lane holds the same pose, count
@@ -215,7 +150,7 @@ __global__ __launch_bounds__(kRelTile) void k_rel_fit(const RelJob *__restrict__
     const double threshold = job->threshold;
     PoseState cur;
 #pragma unroll
-    for (int j = 0; j < 9; j++) cur.R[j] = pick->R[j];
+    for (int j = 0; j < 9; j++) cur.R[j] = pick->R[j];   // (not pose_load: at 256 VGPRs the kernel spilled with it)
 #pragma unroll
     for (int j = 0; j < 3; j++) cur.t[j] = pick->t[j];
     int32_t count = pick->n_inliers;
@@ -227,7 +162,7 @@ __global__ __launch_bounds__(kRelTile) void k_rel_fit(const RelJob *__restrict__
             pass.member = curf;
             int mine = 0;
             for (int i = t; i < S; i += kRelTile) mine += curf[i] ? 1 : 0;
-            const int members = rel_fit_total(mine, wcnt);
+            const int members = wg_total(mine, wcnt);
             PoseState cand;
             double c0, c1;
             int32_t its, status;
@@ -240,7 +175,7 @@ __global__ __launch_bounds__(kRelTile) void k_rel_fit(const RelJob *__restrict__
                 other[i] = flag;
                 in += flag;
             }
-            const int n = rel_fit_total(in, wcnt);
+            const int n = wg_total(in, wcnt);
             const bool accepted = n >= count;
             if (t == 0) {
                 mcorb_rel_polish_round &q = polish->round[round];

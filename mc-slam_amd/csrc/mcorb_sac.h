@@ -10,6 +10,7 @@
 #pragma once
 #include <stdint.h>
 
+#include "mcorb_consensus.h"
 #include "mcorb_pose.h"
 
 namespace mcorb {
@@ -550,13 +551,9 @@ MCORB_POSE_HD void sac_hypothesis(const SacJob &job, int h, const PoseObs *obs, 
         sac_hypothesis_central(job, h, obs, point, cons, cam_first, cam_cons, M);
 }
 
-// the winner among H hypotheses: the largest count of those with a model, a tie to the lowest h.  As a key that a maximum picks:
-// (count + 1) << 10 | (1023 - h) for a model, 0 without one
-MCORB_POSE_HD uint64_t sac_key(int32_t valid, int32_t count, int h)
-{
-    return valid ? (((uint64_t)count + 1) << 10) | (uint64_t)(1023 - h) : 0;
-}
-MCORB_POSE_HD int sac_key_hypothesis(uint64_t key) { return key ? 1023 - (int)(key & 1023) : -1; }
+// the winner among H hypotheses: consensus_key (mcorb_consensus.h) over h
+constexpr int kSacKeyBits = 10;
+static_assert((1 << kSacKeyBits) == MCORB_SAC_MAX_ITERATIONS, "the key holds every hypothesis index");
 
 // The three kernels, serially: what a host-only store runs (mcorb_sac.cpp).  X: the n points, gathered; models[H], count[H] and
 // f[3 S] are the caller's scratch; flags: n, written
@@ -577,31 +574,22 @@ inline void sac_run_serial(const SacJob &job, const PoseObs *obs, const double *
         const PoseObs &o = obs[cons[k]];
         sac_bearing(job.cams[o.cam], o.u, o.v, f + 3 * (size_t)k);
     }
-    uint64_t key = 0;
-    int n_models = 0;
+    PoseState P;
     for (int h = 0; h < job.H; h++) {
         SacModel &M = models[h];
         sac_hypothesis(job, h, obs, point, cons, cam_first, cam_cons, M);
         count[h] = 0;
-        if (M.valid) {
-            PoseState P;
-            for (int j = 0; j < 9; j++) P.R[j] = M.R[j];
-            for (int j = 0; j < 3; j++) P.t[j] = M.t[j];
-            for (int k = 0; k < job.S; k++) {
-                const int i = cons[k];
-                count[h] += sac_is_inlier(sac_score(job.cams[obs[i].cam], P, X + 3 * (size_t)i, f + 3 * (size_t)k), job.threshold) ? 1 : 0;
-            }
+        if (!M.valid) continue;
+        pose_load(P, M.R, M.t);
+        for (int k = 0; k < job.S; k++) {
+            const int i = cons[k];
+            count[h] += sac_is_inlier(sac_score(job.cams[obs[i].cam], P, X + 3 * (size_t)i, f + 3 * (size_t)k), job.threshold) ? 1 : 0;
         }
-        const uint64_t kh = sac_key(M.valid, count[h], h);
-        key = kh > key ? kh : key;
-        n_models += M.valid;
     }
-    const int best = sac_key_hypothesis(key);
-    PoseState P = PoseState{{1, 0, 0, 0, 1, 0, 0, 0, 1}, {0, 0, 0}};
-    if (best >= 0) {
-        for (int j = 0; j < 9; j++) P.R[j] = models[best].R[j];
-        for (int j = 0; j < 3; j++) P.t[j] = models[best].t[j];
-    }
+    const ConsensusBest won = consensus_best<kSacKeyBits>(job.H, [&](int h) { return models[h].valid; }, [&](int h) { return count[h]; });
+    const int best = consensus_key_index<kSacKeyBits>(won.key);
+    pose_identity(P);
+    if (best >= 0) pose_load(P, models[best].R, models[best].t);
     for (int i = 0; i < job.n; i++) flags[i] = 0;
     if (best >= 0)
         for (int k = 0; k < job.S; k++) {
@@ -613,7 +601,7 @@ inline void sac_run_serial(const SacJob &job, const PoseObs *obs, const double *
     out.status = best >= 0 ? MCORB_SAC_OK : MCORB_SAC_NO_MODEL;
     out.n_inliers = best >= 0 ? count[best] : 0;
     out.best = best;
-    out.n_models = n_models;
+    out.n_models = won.n_models;
     for (int j = 0; j < 4; j++) out.sample[j] = best >= 0 ? models[best].sample[j] : -1;
 }
 

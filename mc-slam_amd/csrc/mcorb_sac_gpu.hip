@@ -8,11 +8,9 @@
 //                      the header's rule; the winning lane, or lane 0 without a model, writes the record
 //   k_sac_score        the hot path, H x S reprojections: a workgroup owns a tile of kSacTile consensus observations, whose
 //                      bearing, point and camera each lane computes once and keeps in registers, and a block of kSacHypBlock
-//                      hypotheses, whose models it reads at uniform addresses; per model a ballot and a population count per
-//                      wave into integer counts in LDS, then one integer atomicAdd per (workgroup, hypothesis) into count[H].
-//                      The additions are integer: the result does not depend on their order
-//   k_sac_pick         every workgroup finds the arg-max of count[H] for itself and writes the winner's flags for its tile of
-//                      all n observations (0 outside the consensus set); workgroup 0 writes the record to host-mapped memory
+//                      hypotheses, whose models it reads at uniform addresses: consensus_count (mcorb_consensus.h)
+//   k_sac_pick         every workgroup finds the arg-max of count[H] for itself (consensus_best_wg) and writes the winner's flags
+//                      for its tile of all n observations (0 outside the consensus set); workgroup 0 writes the record to host-mapped memory
 //                      and, when a refinement follows, the pose into the PoseJob k_pose_refine reads
 // The arithmetic is the header's, so the host-only store gives the same bits.  No extraction job runs this and no benchmark leg
 // times it.
@@ -26,8 +24,7 @@
 
 namespace mcorb {
 
-static_assert(kSacTile == 4 * 64, "four waves");
-static_assert(kSacHypBlock <= kSacTile, "a lane per hypothesis of the block adds its count");
+static_assert(kSacTile == kWgLanes, "the workgroup of mcorb_device.h's reductions");
 
 // an observation's point: given, or the store's of its id
 struct SacPoint {
@@ -124,9 +121,8 @@ __global__ __launch_bounds__(kSacTile) void k_sac_score(const SacJob *__restrict
                                                         const SacModel *__restrict__ models, int32_t *__restrict__ count)
 {
     __shared__ int32_t cnt[kSacHypBlock];
-    const int t = threadIdx.x, lane = t & 63;
-    const int S = job->S, H = job->H;
-    const int k = blockIdx.x * kSacTile + t;
+    const int S = job->S;
+    const int k = blockIdx.x * kSacTile + threadIdx.x;
     const bool in = k < S;
     const int i = cons[in ? k : 0];   // (S >= 1: a lane beyond the set scores observation cons[0] and counts nothing)
     const PoseObs o = obs[i];
@@ -135,23 +131,13 @@ __global__ __launch_bounds__(kSacTile) void k_sac_score(const SacJob *__restrict
     double f[3], X[3];
     sac_bearing(cam, o.u, o.v, f);
     SacPoint{lids, pts, geom}(i, X);
-    if (t < kSacHypBlock) cnt[t] = 0;
-    __syncthreads();
-    const int h0 = blockIdx.y * kSacHypBlock, h1 = min(H, h0 + kSacHypBlock);
-    for (int h = h0; h < h1; h++) {
-        const SacModel &M = models[h];   // (uniform over the workgroup: scalar loads)
-        if (!M.valid) continue;
-        PoseState P;
-#pragma unroll
-        for (int j = 0; j < 9; j++) P.R[j] = M.R[j];
-#pragma unroll
-        for (int j = 0; j < 3; j++) P.t[j] = M.t[j];
-        const bool inl = in && sac_is_inlier(sac_score(cam, P, X, f), threshold);
-        const unsigned long long mask = __ballot(inl);
-        if (lane == 0 && mask) atomicAdd(&cnt[h - h0], __popcll(mask));
-    }
-    __syncthreads();
-    if (t < h1 - h0 && cnt[t]) atomicAdd(&count[h0 + t], cnt[t]);
+    consensus_count<kSacHypBlock>(
+        job->H, count, cnt, [&](int h) { return models[h].valid; },   // (uniform over the workgroup: scalar loads)
+        [&](int h) {
+            PoseState P;
+            pose_load(P, models[h].R, models[h].t);
+            return in && sac_is_inlier(sac_score(cam, P, X, f), threshold);
+        });
 }
 
 __global__ __launch_bounds__(kSacTile) void k_sac_pick(const SacJob *__restrict__ job, const PoseObs *__restrict__ obs,
@@ -162,41 +148,14 @@ __global__ __launch_bounds__(kSacTile) void k_sac_pick(const SacJob *__restrict_
 {
     __shared__ unsigned long long wkey[4];
     __shared__ int32_t wmodels[4];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int n = job->n, H = job->H;
-    unsigned long long key = 0;
-    int32_t nm = 0;
-    for (int h = t; h < H; h += kSacTile) {
-        const int32_t valid = models[h].valid;
-        const unsigned long long kh = sac_key(valid, count[h], h);
-        key = kh > key ? kh : key;
-        nm += valid;
-    }
-    for (int s = 32; s >= 1; s >>= 1) {
-        const unsigned long long other = __shfl_xor(key, s, 64);
-        key = other > key ? other : key;
-        nm += __shfl_xor(nm, s, 64);
-    }
-    if (lane == 0) {
-        wkey[wave] = key;
-        wmodels[wave] = nm;
-    }
-    __syncthreads();
-    key = wkey[0];
-    for (int w = 1; w < 4; w++) key = wkey[w] > key ? wkey[w] : key;
-    const int best = sac_key_hypothesis(key);   // (the same in every lane)
+    const int t = threadIdx.x;
+    const int n = job->n;
+    int32_t n_models;
+    const int best = consensus_best_wg<kSacKeyBits, 1>(   // (the same in every lane)
+        job->H, [&](int h) { return models[h].valid; }, [&](int h) { return count[h]; }, wkey, wmodels, n_models);
     PoseState P;
-#pragma unroll
-    for (int j = 0; j < 9; j++) P.R[j] = (j % 4 == 0) ? 1.0 : 0.0;
-#pragma unroll
-    for (int j = 0; j < 3; j++) P.t[j] = 0.0;
-    if (best >= 0) {
-        const SacModel &M = models[best];
-#pragma unroll
-        for (int j = 0; j < 9; j++) P.R[j] = M.R[j];
-#pragma unroll
-        for (int j = 0; j < 3; j++) P.t[j] = M.t[j];
-    }
+    pose_identity(P);
+    if (best >= 0) pose_load(P, models[best].R, models[best].t);
     const int i = blockIdx.x * kSacTile + t;
     if (i < n) {
         uint8_t flag = 0;
@@ -215,7 +174,7 @@ __global__ __launch_bounds__(kSacTile) void k_sac_pick(const SacJob *__restrict_
         out->status = best >= 0 ? MCORB_SAC_OK : MCORB_SAC_NO_MODEL;
         out->n_inliers = best >= 0 ? count[best] : 0;
         out->best = best;
-        out->n_models = (wmodels[0] + wmodels[1]) + (wmodels[2] + wmodels[3]);
+        out->n_models = n_models;
         for (int j = 0; j < 4; j++) out->sample[j] = best >= 0 ? models[best].sample[j] : -1;
         if (pose_job) {
             for (int j = 0; j < 9; j++) pose_job->init.R[j] = P.R[j];
