@@ -1068,6 +1068,20 @@ def _init_scalars(o):
                 n_triangulated=o.n_triangulated, scaled=bool(o.scaled), next_lid=o.next_lid)
 
 
+def _map_outputs(o, cap, total, per_match, **other):
+    """the output arrays of LocalMap.triangulate_neighbours, .triangulate_new and .initialize, their addresses written into the
+    ctypes record o: per match inliers, verdict, new_lid, pt3d, normal (3 wide) and the call's own `per_match` (name -> dtype),
+    max(cap, 1) rows each; `other`: name -> (dtype, size), max(size, 1) elements -> (the arrays by name, cut(name): the
+    array's rows of the call's `total` matches, copied)"""
+    spec = dict(inliers=np.uint8, verdict=np.uint8, new_lid=np.int32, **per_match)
+    r = {k: np.zeros(max(cap, 1), t) for k, t in spec.items()}
+    r.update(pt3d=np.zeros(3 * max(cap, 1)), normal=np.zeros(3 * max(cap, 1)))
+    r.update({k: np.zeros(max(size, 1), t) for k, (t, size) in other.items()})
+    for k, a in r.items():
+        setattr(o, k, a.ctypes.data)
+    return r, lambda k: r[k][:(3 if k in ("pt3d", "normal") else 1) * total].copy()
+
+
 class LocalMap:
     """FrontEnd::searchLocalMap2 (MCSlam/src/FrontEnd.cpp:4901-5223) up to the camera-filtered matches (mcorb_lmap): a store of
     landmarks (slot = lId: pt3D, normal, the latest observation's descriptor and mono flag) and the search of a frame held in a
@@ -1182,23 +1196,17 @@ class LocalMap:
         Rc, tc = np.ascontiguousarray(Rcw, np.float64).reshape(9), np.ascontiguousarray(tcw, np.float64).reshape(3)
         frames = (_lib.MapFrame * max(S, 1))(*[f.struct for f in neigh])
         vpp = lambda arrs: (C.c_void_p * max(S, 1))(*[a.ctypes.data for a in arrs])
-        n1, n3 = max(cap_m, 1), 3 * max(cap_m, 1)
-        r = dict(inliers=np.zeros(n1, np.uint8), verdict=np.zeros(n1, np.uint8), new_lid=np.zeros(n1, np.int32), pt3d=np.zeros(n3),
-                 normal=np.zeros(n3), dist2=np.zeros(n1), cos_parallax=np.zeros(n1), neigh_skipped=np.zeros(max(S, 1), np.uint8),
-                 depth_vec=np.zeros(max(cap_d, 1)))
         o = self.map_out = _lib.MapOut()
         o.cap_matches, o.cap_depth = cap_m, cap_d
-        for k, a in r.items():
-            setattr(o, k, a.ctypes.data)
+        r, cut = _map_outputs(o, cap_m, total, dict(dist2=np.float64, cos_parallax=np.float64), neigh_skipped=(np.uint8, S),
+                              depth_vec=(np.float64, cap_d))
         _lib.check(self.L.mcorb_lmap_triangulate_neighbours(self.h, C.byref(cur.struct), lc.ctypes.data, frames, vpp(ln), S, vpp(Fs),
                                                             vpp(mq), vpp(mt), nm.ctypes.data, Kc.ctypes.data, sig.ctypes.data, len(sig),
                                                             Rc.ctypes.data, tc.ctypes.data, int(next_lid), C.byref(o)))
-        nd = o.n_depth
-        return TriangulationResult(inliers=r["inliers"][:total].astype(bool), verdict=r["verdict"][:total].copy(),
-                                   new_lid=r["new_lid"][:total].copy(), pt3d=r["pt3d"][:3 * total].reshape(-1, 3).copy(),
-                                   normal=r["normal"][:3 * total].reshape(-1, 3).copy(), dist2=r["dist2"][:total].copy(),
-                                   cos_parallax=r["cos_parallax"][:total].copy(), neigh_skipped=r["neigh_skipped"][:S].copy(),
-                                   depth_vec=r["depth_vec"][:nd].copy(), n_triangulated=o.n_triangulated, next_lid=o.next_lid,
+        return TriangulationResult(inliers=cut("inliers").astype(bool), verdict=cut("verdict"), new_lid=cut("new_lid"),
+                                   pt3d=cut("pt3d").reshape(-1, 3), normal=cut("normal").reshape(-1, 3), dist2=cut("dist2"),
+                                   cos_parallax=cut("cos_parallax"), neigh_skipped=r["neigh_skipped"][:S].copy(),
+                                   depth_vec=r["depth_vec"][:o.n_depth].copy(), n_triangulated=o.n_triangulated, next_lid=o.next_lid,
                                    lids_cur=lc, lids_neigh=ln, offsets=offsets)
 
     def triangulate_new(self, cur, lids_cur, prev, lids_prev, matches, K_mats, inv_sigma2, next_lid, caps=None):
@@ -1217,20 +1225,15 @@ class LocalMap:
         cap_m, cap_d = caps if caps is not None else (total, total)
         Kc = np.ascontiguousarray(K_mats, np.float64).reshape(nc, 9)
         sig = np.ascontiguousarray(inv_sigma2, np.float32).reshape(-1)
-        n1, n3 = max(cap_m, 1), 3 * max(cap_m, 1)
-        r = dict(inliers=np.zeros(n1, np.uint8), verdict=np.zeros(n1, np.uint8), new_lid=np.zeros(n1, np.int32), pt3d=np.zeros(n3),
-                 normal=np.zeros(n3), dist=np.zeros(n1), cos_parallax=np.zeros(n1, np.float32), iterations=np.zeros(n1, np.int32),
-                 cost_initial=np.zeros(n1), cost_final=np.zeros(n1), depth_vec=np.zeros(max(cap_d, 1)))
         o = self.map_new_out = _lib.MapNewOut()
         o.cap_matches, o.cap_depth = cap_m, cap_d
-        for k, a in r.items():
-            setattr(o, k, a.ctypes.data)
+        r, cut = _map_outputs(o, cap_m, total, dict(dist=np.float64, cos_parallax=np.float32, iterations=np.int32, cost_initial=np.float64,
+                                                    cost_final=np.float64), depth_vec=(np.float64, cap_d))
         _lib.check(self.L.mcorb_lmap_triangulate_new(self.h, C.byref(cur.struct), lc.ctypes.data, C.byref(prev.struct), lp.ctypes.data,
                                                      mq.ctypes.data, mt.ctypes.data, total, Kc.ctypes.data, sig.ctypes.data, len(sig),
                                                      int(next_lid), C.byref(o)))
-        cut = lambda k, w=1: r[k][:w * total].copy()
-        return NewLandmarksResult(inliers=r["inliers"][:total].astype(bool), verdict=cut("verdict"), new_lid=cut("new_lid"),
-                                  pt3d=cut("pt3d", 3).reshape(-1, 3), normal=cut("normal", 3).reshape(-1, 3), dist=cut("dist"),
+        return NewLandmarksResult(inliers=cut("inliers").astype(bool), verdict=cut("verdict"), new_lid=cut("new_lid"),
+                                  pt3d=cut("pt3d").reshape(-1, 3), normal=cut("normal").reshape(-1, 3), dist=cut("dist"),
                                   cos_parallax=cut("cos_parallax"), iterations=cut("iterations"), cost_initial=cut("cost_initial"),
                                   cost_final=cut("cost_final"), depth_vec=r["depth_vec"][:o.n_depth].copy(), avg_depth=o.avg_depth,
                                   n_rays_hist=np.array(o.n_rays_hist[:], np.int32), n_by_verdict=np.array(o.n_by_verdict[:], np.int32),
@@ -1259,22 +1262,18 @@ class LocalMap:
         sig = np.ascontiguousarray(inv_sigma2, np.float32).reshape(-1)
         Rr, tt = np.ascontiguousarray(R, np.float64).reshape(9), np.ascontiguousarray(t, np.float64).reshape(3)
         cb = np.ascontiguousarray(cam_centre_body, np.float64).reshape(nc, 3)
-        n1, n3 = max(cap, total, 1), 3 * max(cap, total, 1)
-        r = dict(inliers=np.zeros(n1, np.uint8), verdict=np.zeros(n1, np.uint8), new_lid=np.full(n1, -1, np.int32), pt3d=np.zeros(n3),
-                 normal=np.zeros(n3), dist2=np.zeros(n1), cos_parallax=np.zeros(n1))
+        o = self.init_out = _lib.InitResultC()
+        o.cap_matches = cap
+        r, cut = _map_outputs(o, max(cap, total), total, dict(dist2=np.float64, cos_parallax=np.float64))
         fl = np.asarray(inliers).reshape(-1) != 0
         assert len(fl) == total
         r["inliers"][:total] = fl
-        o = self.init_out = _lib.InitResultC()
-        o.cap_matches = cap
-        for k, a in r.items():
-            setattr(o, k, a.ctypes.data)
+        r["new_lid"][:] = -1
         _lib.check(self.L.mcorb_lmap_initialize(self.h, C.byref(prev.struct), lp.ctypes.data, C.byref(cur.struct), lc.ctypes.data,
                                                 Rr.ctypes.data, tt.ctypes.data, cb.ctypes.data, mq.ctypes.data, mt.ctypes.data, total,
                                                 Kc.ctypes.data, sig.ctypes.data, len(sig), int(next_lid), float(min_baseline), C.byref(o)))
-        cut = lambda k, w=1: r[k][:w * total].copy()
-        return InitResult(inliers=r["inliers"][:total].astype(bool), verdict=cut("verdict"), new_lid=cut("new_lid"),
-                          pt3d=cut("pt3d", 3).reshape(-1, 3), normal=cut("normal", 3).reshape(-1, 3), dist2=cut("dist2"),
+        return InitResult(inliers=cut("inliers").astype(bool), verdict=cut("verdict"), new_lid=cut("new_lid"),
+                          pt3d=cut("pt3d").reshape(-1, 3), normal=cut("normal").reshape(-1, 3), dist2=cut("dist2"),
                           cos_parallax=cut("cos_parallax"), lids_prev=lp, lids_cur=lc, **_init_scalars(o))
 
     def last_initialize_timing(self):
@@ -2315,23 +2314,31 @@ def obs_frame(kf_id, lf, centres_w):
     return ObsFrameArrays(kf_id, mi, centres_w)
 
 
+def _hook_cases(who, X, nv1, nv, P, K, centre, kps, octave, inv_sigma2, per_case):
+    """the cases of a test hook (map_gates, init_cases, map_refine), contiguous and checked: the views back to back and the
+    hook's own `per_case` arrays, a row per case -> (n, the leading arguments of the C entry: n and the pointers of X .. octave,
+    what they point to (the caller holds it across the call), inv_sigma2 as float32)"""
+    X = np.ascontiguousarray(X, np.float64).reshape(-1, 3)
+    n = len(X)
+    nv1, nv = np.ascontiguousarray(nv1, np.int32).reshape(-1), np.ascontiguousarray(nv, np.int32).reshape(-1)
+    views = [np.ascontiguousarray(P, np.float64).reshape(-1, 12), np.ascontiguousarray(K, np.float64).reshape(-1, 9),
+             np.ascontiguousarray(centre, np.float64).reshape(-1, 3), np.ascontiguousarray(kps, np.float32).reshape(-1, 2),
+             np.ascontiguousarray(octave, np.int32).reshape(-1)]
+    V = int(nv.sum()) if len(nv) == n else -1
+    if not (all(len(a) == n for a in [nv1, *per_case]) and all(len(a) == V for a in views)):
+        raise ValueError(who + ": array lengths do not fit the view counts")
+    keep = [X, nv1, nv] + views
+    return n, (n,) + tuple(a.ctypes.data for a in keep), keep, np.ascontiguousarray(inv_sigma2, np.float32).reshape(-1)
+
+
 def map_gates(X, nv1, nv, P, K, centre, kps, octave, F, inv_sigma2, device=None):
     """the test hooks mcorb_host_map_gates (device None) / mcorb_dev_map_gates_selftest: everything of a match but the
     triangulation for n cases with caller-given X -> (verdict, n_rays, dist2, cos, normal).  Views back to back: P (V x 12),
     K (V x 9), centre (V x 3), kps (V x 2 float32), octave (V); per case X (3), nv1, nv, F (9)"""
-    X = np.ascontiguousarray(X, np.float64).reshape(-1, 3)
-    n = len(X)
-    nv1, nv = np.ascontiguousarray(nv1, np.int32).reshape(-1), np.ascontiguousarray(nv, np.int32).reshape(-1)
-    P, K = np.ascontiguousarray(P, np.float64).reshape(-1, 12), np.ascontiguousarray(K, np.float64).reshape(-1, 9)
-    centre, kps = np.ascontiguousarray(centre, np.float64).reshape(-1, 3), np.ascontiguousarray(kps, np.float32).reshape(-1, 2)
-    octave, F = np.ascontiguousarray(octave, np.int32).reshape(-1), np.ascontiguousarray(F, np.float64).reshape(-1, 9)
-    sig = np.ascontiguousarray(inv_sigma2, np.float32).reshape(-1)
-    V = int(nv.sum()) if len(nv) == n else -1
-    if not (len(nv1) == len(F) == n and len(P) == len(K) == len(centre) == len(kps) == len(octave) == V):
-        raise ValueError("map_gates: array lengths do not fit the view counts")
+    F = np.ascontiguousarray(F, np.float64).reshape(-1, 9)
+    n, cases, _keep, sig = _hook_cases("map_gates", X, nv1, nv, P, K, centre, kps, octave, inv_sigma2, [F])
     verdict, rays, vals = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32), np.zeros((max(n, 1), 5))
-    args = (n, X.ctypes.data, nv1.ctypes.data, nv.ctypes.data, P.ctypes.data, K.ctypes.data, centre.ctypes.data, kps.ctypes.data,
-            octave.ctypes.data, F.ctypes.data, sig.ctypes.data, len(sig), verdict.ctypes.data, rays.ctypes.data, vals.ctypes.data)
+    args = cases + (F.ctypes.data, sig.ctypes.data, len(sig), verdict.ctypes.data, rays.ctypes.data, vals.ctypes.data)
     L = _lib.load()
     _lib.check(L.mcorb_host_map_gates(*args) if device is None else L.mcorb_dev_map_gates_selftest(device, *args))
     return verdict[:n], rays[:n], vals[:n, 0].copy(), vals[:n, 1].copy(), vals[:n, 2:].copy()
@@ -2341,24 +2348,14 @@ def init_cases(X, nv1, nv, P, K, centre, kps, octave, inv_sigma2, ncams, R, t, m
     """the test hooks mcorb_host_init_cases (device None) / mcorb_dev_init_cases_selftest: everything of LocalMap.initialize but
     the triangulation and the store, the n cases standing for the n matches of one call -> InitResult (new_lid counts from 0).
     Views back to back as for map_gates, but centre is centre_w for a view of prev and cam_centre_body for a view of cur"""
-    X = np.ascontiguousarray(X, np.float64).reshape(-1, 3)
-    n = len(X)
-    nv1, nv = np.ascontiguousarray(nv1, np.int32).reshape(-1), np.ascontiguousarray(nv, np.int32).reshape(-1)
-    P, K = np.ascontiguousarray(P, np.float64).reshape(-1, 12), np.ascontiguousarray(K, np.float64).reshape(-1, 9)
-    centre, kps = np.ascontiguousarray(centre, np.float64).reshape(-1, 3), np.ascontiguousarray(kps, np.float32).reshape(-1, 2)
-    octave = np.ascontiguousarray(octave, np.int32).reshape(-1)
-    sig = np.ascontiguousarray(inv_sigma2, np.float32).reshape(-1)
     Rr, tt = np.ascontiguousarray(R, np.float64).reshape(9), np.ascontiguousarray(t, np.float64).reshape(3)
     fl = np.ascontiguousarray(np.asarray(inliers).reshape(-1) != 0, np.uint8)
-    V = int(nv.sum()) if len(nv) == n else -1
-    if not (len(nv1) == len(fl) == n and len(P) == len(K) == len(centre) == len(kps) == len(octave) == V):
-        raise ValueError("init_cases: array lengths do not fit the view counts")
+    n, cases, _keep, sig = _hook_cases("init_cases", X, nv1, nv, P, K, centre, kps, octave, inv_sigma2, [fl])
     m = max(n, 1)
     verdict, rays, off, vals = np.zeros(m, np.int32), np.zeros(m, np.int32), np.full(m, -1, np.int32), np.zeros((m, 8))
     o = _lib.InitResultC()
-    args = (n, X.ctypes.data, nv1.ctypes.data, nv.ctypes.data, P.ctypes.data, K.ctypes.data, centre.ctypes.data, kps.ctypes.data,
-            octave.ctypes.data, sig.ctypes.data, len(sig), int(ncams), Rr.ctypes.data, tt.ctypes.data, float(min_baseline), fl.ctypes.data,
-            verdict.ctypes.data, rays.ctypes.data, off.ctypes.data, vals.ctypes.data, C.byref(o))
+    args = cases + (sig.ctypes.data, len(sig), int(ncams), Rr.ctypes.data, tt.ctypes.data, float(min_baseline), fl.ctypes.data,
+                    verdict.ctypes.data, rays.ctypes.data, off.ctypes.data, vals.ctypes.data, C.byref(o))
     L = _lib.load()
     _lib.check(L.mcorb_host_init_cases(*args) if device is None else L.mcorb_dev_init_cases_selftest(device, *args))
     return InitResult(inliers=fl[:n].astype(bool), verdict=verdict[:n].astype(np.uint8), new_lid=off[:n], n_rays=rays[:n],
@@ -2370,22 +2367,12 @@ def map_refine(X0, nv1, nv, P, K, centre, kps, octave, twc_cur, twc_prev, inv_si
     """the test hooks mcorb_host_map_refine (device None) / mcorb_dev_map_refine_selftest: everything of a match of
     LocalMap.triangulate_new after the DLT for n cases with caller-given X0 -> (verdict, n_rays, solves, cos (float32), X, normal,
     dist, cost_initial, cost_final).  Views back to back as for map_gates; per case X0 (3), nv1, nv, twc_cur (3), twc_prev (3)"""
-    X0 = np.ascontiguousarray(X0, np.float64).reshape(-1, 3)
-    n = len(X0)
-    nv1, nv = np.ascontiguousarray(nv1, np.int32).reshape(-1), np.ascontiguousarray(nv, np.int32).reshape(-1)
-    P, K = np.ascontiguousarray(P, np.float64).reshape(-1, 12), np.ascontiguousarray(K, np.float64).reshape(-1, 9)
-    centre, kps = np.ascontiguousarray(centre, np.float64).reshape(-1, 3), np.ascontiguousarray(kps, np.float32).reshape(-1, 2)
-    octave = np.ascontiguousarray(octave, np.int32).reshape(-1)
     tc, tp = np.ascontiguousarray(twc_cur, np.float64).reshape(-1, 3), np.ascontiguousarray(twc_prev, np.float64).reshape(-1, 3)
-    sig = np.ascontiguousarray(inv_sigma2, np.float32).reshape(-1)
-    V = int(nv.sum()) if len(nv) == n else -1
-    if not (len(nv1) == len(tc) == len(tp) == n and len(P) == len(K) == len(centre) == len(kps) == len(octave) == V):
-        raise ValueError("map_refine: array lengths do not fit the view counts")
+    n, cases, _keep, sig = _hook_cases("map_refine", X0, nv1, nv, P, K, centre, kps, octave, inv_sigma2, [tc, tp])
     m = max(n, 1)
     verdict, rays, solves, cosp, vals = np.zeros(m, np.int32), np.zeros(m, np.int32), np.zeros(m, np.int32), np.zeros(m, np.float32), np.zeros((m, 9))
-    args = (n, X0.ctypes.data, nv1.ctypes.data, nv.ctypes.data, P.ctypes.data, K.ctypes.data, centre.ctypes.data, kps.ctypes.data,
-            octave.ctypes.data, tc.ctypes.data, tp.ctypes.data, sig.ctypes.data, len(sig), verdict.ctypes.data, rays.ctypes.data,
-            solves.ctypes.data, cosp.ctypes.data, vals.ctypes.data)
+    args = cases + (tc.ctypes.data, tp.ctypes.data, sig.ctypes.data, len(sig), verdict.ctypes.data, rays.ctypes.data,
+                    solves.ctypes.data, cosp.ctypes.data, vals.ctypes.data)
     L = _lib.load()
     _lib.check(L.mcorb_host_map_refine(*args) if device is None else L.mcorb_dev_map_refine_selftest(device, *args))
     return (verdict[:n], rays[:n], solves[:n], cosp[:n], vals[:n, 0:3].copy(), vals[:n, 3:6].copy(), vals[:n, 6].copy(),

@@ -17,9 +17,6 @@ using namespace mcorb;
 
 namespace {
 
-const char *const kWho = "lmap initialize";
-int fail(int code, const char *what) { set_error(std::string(kWho) + ": " + what); return code; }
-
 void call_out(const InitCall &c, int n, mcorb_init_result *out)
 {
     out->status = c.status;
@@ -34,25 +31,17 @@ void call_out(const InitCall &c, int n, mcorb_init_result *out)
     out->next_lid = c.next_lid;
 }
 
-int check_cases(int n, const double *X, const int32_t *nv1, const int32_t *nv, const double *P, const double *K, const double *centre,
-                const float *kps, const int32_t *octave, const float *inv_sigma2, int nlevels, int ncams, const double *R, const double *t,
-                const uint8_t *inliers, const int32_t *verdict, const int32_t *n_rays, const int32_t *lid_offset, const double *vals,
-                const mcorb_init_result *res, std::vector<int32_t> &voff)
+// what both hooks refuse: their own arguments, then check_cases
+int check_init_cases(MapCases &c, int nlevels, int n, int ncams, const double *R, const double *t, const uint8_t *inliers,
+                     const int32_t *verdict, const int32_t *n_rays, const int32_t *lid_offset, const double *vals,
+                     const mcorb_init_result *res, std::vector<int32_t> &voff)
 {
-    if (!X || !nv1 || !nv || !P || !K || !centre || !kps || !octave || !inv_sigma2 || nlevels < 1 || n < 1 || n > MCORB_INIT_MAX_MATCHES ||
-        ncams < 1 || ncams > MCORB_MAX_CAMS || !R || !t || !inliers || !verdict || !n_rays || !lid_offset || !vals || !res) {
+    if (n > MCORB_INIT_MAX_MATCHES || ncams < 1 || ncams > MCORB_MAX_CAMS || !R || !t || !inliers || !verdict || !n_rays || !lid_offset ||
+        !vals || !res) {
         set_error("init cases: bad argument");
         return MCORB_E_ARG;
     }
-    voff.resize((size_t)n + 1);
-    voff[0] = 0;
-    for (int i = 0; i < n; i++) {
-        if (nv1[i] < 1 || nv[i] <= nv1[i] || nv[i] > MCORB_MAX_CAMS) { set_error("init cases: view counts out of range"); return MCORB_E_ARG; }
-        voff[i + 1] = voff[i] + nv[i];
-    }
-    for (int w = 0; w < voff[n]; w++)
-        if (octave[w] < 0 || octave[w] >= nlevels) { set_error("init cases: octave outside nlevels"); return MCORB_E_ARG; }
-    return MCORB_OK;
+    return check_cases("init cases", c, nlevels, n, voff);
 }
 
 // the chain of both device entries on st with its wait: `records` (k_init_triangulate, or the cases' k_init_gates), k_init_select
@@ -107,14 +96,6 @@ void cases_out(const MapOut *recs, const InitCall &call, int n, uint8_t *inliers
     call_out(call, n, res);
 }
 
-template <class T>
-int to_device(DevBuf<T> &d, const T *src, size_t n)
-{
-    TRY(d.alloc(n));
-    HIPCHK(hipMemcpy(d, src, n * sizeof(T), hipMemcpyHostToDevice));
-    return MCORB_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -124,28 +105,36 @@ int mcorb_lmap_initialize(mcorb_lmap *m, const mcorb_map_frame *prev, int32_t *l
                           const int32_t *match_train, int n, const double *K, const float *inv_sigma2, int nlevels, int32_t next_lid,
                           double min_baseline, mcorb_init_result *out)
 {
-    map_who(kWho);
-    TRY(check_lmap(m, kWho));
+    const char *const who = "lmap initialize";
+    TRY(check_lmap(m, who));
+    MapCall mc{who, m->max_landmarks, cur ? cur->ncams : 0, nlevels};
     if (!prev || !cur || !out || !R || !t || !cam_centre_body || n < 0 || !K || !inv_sigma2 || nlevels < 1 || next_lid < 0 ||
         out->cap_matches < 0 || (cur->nfeat && !lids_cur) || (prev->nfeat && !lids_prev) || (n && (!match_query || !match_train)))
-        return fail(MCORB_E_ARG, "bad argument");
-    const int C = cur->ncams;
-    if (C < 1 || C > MCORB_MAX_CAMS) return fail(MCORB_E_ARG, "1 .. MCORB_MAX_CAMS cameras");
-    if (n > MCORB_INIT_MAX_MATCHES) return fail(MCORB_E_ARG, "more than MCORB_INIT_MAX_MATCHES matches");
+        return mc.bad("bad argument");
+    const int C = mc.C;
+    if (C < 1 || C > MCORB_MAX_CAMS) return mc.bad("1 .. MCORB_MAX_CAMS cameras");
+    if (n > MCORB_INIT_MAX_MATCHES) return mc.bad("more than MCORB_INIT_MAX_MATCHES matches");
     std::lock_guard<std::mutex> lk(m->mu);
 
     // ---- 1. everything that can be refused is refused before anything runs ----
-    TRY(map_check_frame(m, *cur, C, lids_cur));
-    TRY(map_check_frame(m, *prev, C, lids_prev));
+    TRY(mc.check_frame(*cur));
+    TRY(mc.check_lids(*cur, lids_cur));
+    TRY(mc.check_frame(*prev));
+    TRY(mc.check_lids(*prev, lids_prev));
+    mc.add(*cur);
+    mc.add(*prev);
     std::vector<uint8_t> nviews((size_t)n, 0);
-    for (int j = 0; j < n; j++) TRY(map_count_views(*prev, *cur, match_query[j], match_train[j], nlevels, nviews[j]));
+    for (int j = 0; j < n; j++) {
+        uint8_t nv_cur;
+        TRY(mc.count_views(*prev, match_query[j], match_train[j], nviews[j], nv_cur));
+    }
     out->n_matches = n;
-    if (n > out->cap_matches) return fail(MCORB_E_CAP, "output too small");
+    if (n > out->cap_matches) return mc.fail(MCORB_E_CAP, "output too small");
     if (n && (!out->inliers || !out->verdict || !out->new_lid || !out->pt3d || !out->normal || !out->dist2 || !out->cos_parallax))
-        return fail(MCORB_E_ARG, "bad argument");
+        return mc.bad("bad argument");
     InitJob job;
     job_init(job, R, t, n, C, next_lid, out->inliers);
-    if ((size_t)next_lid + (size_t)job.n_initial > (size_t)m->max_landmarks) return fail(MCORB_E_CAP, "new landmark ids beyond max_landmarks");
+    if ((size_t)next_lid + (size_t)job.n_initial > (size_t)m->max_landmarks) return mc.fail(MCORB_E_CAP, "new landmark ids beyond max_landmarks");
 
     // ---- 2. the baseline gate (:2633) ----
     if (!init_baseline(t, min_baseline)) {
@@ -157,7 +146,7 @@ int mcorb_lmap_initialize(mcorb_lmap *m, const mcorb_map_frame *prev, int32_t *l
     const bool dev = m->device >= 0;
     std::vector<uint8_t> flags(out->inliers, out->inliers + n);
     for (uint8_t &f : flags) f = f ? 1 : 0;
-    MapWork w;
+    MapWork &w = mc.w;
     w.item_of.assign((size_t)n, -1);
     const size_t moff[2] = {0, (size_t)n};
     if (dev) {
@@ -166,12 +155,9 @@ int mcorb_lmap_initialize(mcorb_lmap *m, const mcorb_map_frame *prev, int32_t *l
             if (w.item_of[j] >= 0) w.items[w.item_of[j]].rec = j;
     }
 
-    // ---- 4. the packed input: the current frame (its centres: cam_centre_body), then prev ----
-    size_t nmi = 0, nkp = 0;
-    map_count_frame(*cur, nmi, nkp);
-    map_count_frame(*prev, nmi, nkp);
-    if (nmi > 0x7fffffff || nkp > 0x7fffffff) return fail(MCORB_E_ARG, "frames too large");
-    const InitLayout L((size_t)C, (size_t)nlevels, nmi, nkp, w.blocks.size(), w.items.size(), (size_t)n);
+    // ---- 4. the packed input: the current frame (its centres: cam_centre_body), then prev; the flags and the matches ----
+    TRY(mc.fits());
+    const InitLayout L((size_t)C, (size_t)nlevels, mc.nmi, mc.nkp, w.blocks.size(), w.items.size(), (size_t)n);
     mcorb_lmap::Init &b = m->init;
     std::vector<uint8_t> host_block;
     uint8_t *base;
@@ -184,21 +170,8 @@ int mcorb_lmap_initialize(mcorb_lmap *m, const mcorb_map_frame *prev, int32_t *l
         host_block.resize(L.m.p.total);
         base = host_block.data();
     }
-    MapFrameDev *fr = (MapFrameDev *)(base + L.m.frames);
-    size_t mi_at = 0, kp_at = 0;
-    map_pack_frame(*cur, fr[0], (int32_t *)(base + L.m.mi), mi_at, (MapKp *)(base + L.m.kp), kp_at);
-    map_pack_frame(*prev, fr[1], (int32_t *)(base + L.m.mi), mi_at, (MapKp *)(base + L.m.kp), kp_at);
-    memset(fr[0].centre, 0, sizeof(fr[0].centre));
-    memcpy(fr[0].centre, cam_centre_body, (size_t)C * 3 * sizeof(double));
-    memcpy(base + L.m.K, K, (size_t)C * 9 * sizeof(double));
-    memcpy(base + L.m.sig, inv_sigma2, (size_t)nlevels * sizeof(float));
-    if (!w.blocks.empty()) memcpy(base + L.m.blocks, w.blocks.data(), w.blocks.size() * sizeof(MapBlock));
-    if (!w.items.empty()) memcpy(base + L.m.items, w.items.data(), w.items.size() * sizeof(MapItem));
-    if (n) {
-        memcpy(base + L.flags, flags.data(), (size_t)n);
-        memcpy(base + L.query, match_query, (size_t)n * sizeof(int32_t));
-        memcpy(base + L.train, match_train, (size_t)n * sizeof(int32_t));
-    }
+    mc.pack(base, L.m, K, inv_sigma2);
+    mc.pack_init(base, L, cam_centre_body, flags.data(), match_query, match_train, (size_t)n);
 
     // ---- 5. the records, the medians, the verdict and the landmarks ----
     std::vector<MapOut> host_recs;
@@ -273,13 +246,12 @@ int mcorb_host_init_cases(int n, const double *X, const int32_t *nv1, const int3
                           int ncams, const double R[9], const double t[3], double min_baseline, uint8_t *inliers, int32_t *verdict,
                           int32_t *n_rays, int32_t *lid_offset, double *vals, mcorb_init_result *res)
 {
+    MapCases c{X, nv1, nv, nullptr, P, K, centre, kps, octave, inv_sigma2};
     std::vector<int32_t> voff;
-    TRY(check_cases(n, X, nv1, nv, P, K, centre, kps, octave, inv_sigma2, nlevels, ncams, R, t, inliers, verdict, n_rays, lid_offset, vals,
-                    res, voff));
+    TRY(check_init_cases(c, nlevels, n, ncams, R, t, inliers, verdict, n_rays, lid_offset, vals, res, voff));
     if (!init_baseline(t, min_baseline)) { baseline_out(t, n, 0, res); return MCORB_OK; }
     InitJob job;
     job_init(job, R, t, n, ncams, 0, inliers);
-    const InitGateCases c{X, nv1, nv, voff.data(), P, K, centre, kps, octave, inv_sigma2};
     std::vector<MapOut> recs((size_t)n);
     std::vector<uint8_t> flags((size_t)n);
     for (int i = 0; i < n; i++) {
@@ -290,7 +262,7 @@ int mcorb_host_init_cases(int n, const double *X, const int32_t *nv1, const int3
     std::vector<double> geom((size_t)n * 6);
     std::vector<int32_t> rays((size_t)n);
     InitCall call;
-    init_finish_serial(job, flags.data(), recs.data(), [&](int i, MapViews &v) { init_case_views(c, i, v); }, call, geom.data(), rays.data());
+    init_finish_serial(job, flags.data(), recs.data(), [&](int i, MapViews &v) { map_case_views(c, i, v); }, call, geom.data(), rays.data());
     cases_out(recs.data(), call, n, inliers, verdict, n_rays, lid_offset, vals, res);
     return MCORB_OK;
 }
@@ -301,37 +273,28 @@ int mcorb_dev_init_cases_selftest(int device, int n, const double *X, const int3
                                   double min_baseline, uint8_t *inliers, int32_t *verdict, int32_t *n_rays, int32_t *lid_offset,
                                   double *vals, mcorb_init_result *res)
 {
+    MapCases c{X, nv1, nv, nullptr, P, K, centre, kps, octave, inv_sigma2};
     std::vector<int32_t> voff;
-    TRY(check_cases(n, X, nv1, nv, P, K, centre, kps, octave, inv_sigma2, nlevels, ncams, R, t, inliers, verdict, n_rays, lid_offset, vals,
-                    res, voff));
+    TRY(check_init_cases(c, nlevels, n, ncams, R, t, inliers, verdict, n_rays, lid_offset, vals, res, voff));
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) { set_error("no usable HIP device"); return MCORB_E_NODEVICE; }
     if (!init_baseline(t, min_baseline)) { baseline_out(t, n, 0, res); return MCORB_OK; }
     HIPCHK(hipSetDevice(device));
     InitJob job;
     job_init(job, R, t, n, ncams, 0, inliers);
-    const size_t N = (size_t)n, V = (size_t)voff[n];
+    const size_t N = (size_t)n;
     std::vector<uint8_t> flags(N);
     for (int i = 0; i < n; i++) flags[i] = inliers[i] ? 1 : 0;
-    DevBuf<double> d_X, d_P, d_K, d_c, d_geom;
-    DevBuf<int32_t> d_nv1, d_nv, d_voff, d_oct, d_offset, d_nrays;
-    DevBuf<float> d_kps, d_sig;
+    CasesDev d;
+    DevBuf<double> d_geom;
+    DevBuf<int32_t> d_offset, d_nrays;
     DevBuf<uint8_t> d_flags;
     DevBuf<MapOut> d_rec;
     DevBuf<uint64_t> d_keys;
     DevBuf<InitSel> d_sel;
     HostBuf<MapOut> h_rec;
     HostBuf<InitCall> h_call;
-    TRY(to_device(d_X, X, N * 3));
-    TRY(to_device(d_P, P, V * 12));
-    TRY(to_device(d_K, K, V * 9));
-    TRY(to_device(d_c, centre, V * 3));
-    TRY(to_device(d_nv1, nv1, N));
-    TRY(to_device(d_nv, nv, N));
-    TRY(to_device(d_voff, voff.data(), N + 1));
-    TRY(to_device(d_oct, octave, V));
-    TRY(to_device(d_kps, kps, V * 2));
-    TRY(to_device(d_sig, inv_sigma2, (size_t)nlevels));
+    TRY(d.upload(n, c, nlevels));
     TRY(to_device(d_flags, flags.data(), N));
     TRY(d_rec.alloc(N));
     TRY(d_keys.alloc(2 * N));
@@ -345,7 +308,7 @@ int mcorb_dev_init_cases_selftest(int device, int n, const double *X, const int3
     InitPutArgs p;
     memset(&p, 0, sizeof(p));
     p.job = job;
-    p.cases = InitGateCases{d_X, d_nv1, d_nv, d_voff, d_P, d_K, d_c, d_kps, d_oct, d_sig};
+    p.cases = d.cases();
     p.rec = d_rec;
     p.flags = d_flags;
     p.offset = d_offset;

@@ -84,50 +84,29 @@ MCORB_TRI_HD inline void init_after(const MapViews &v, const double X[3], const 
     for (int k = 0; k < 3; k++) o.X[k] = X[k];
     const int gate = map_view_gates(v, X, inv_sigma2);
     if (gate != kMapLandmark) { o.verdict = gate; return; }
-    double o1[3], o2[3], n1[3], n2[3];
-    map_centre(v.P[0], o1);
-    map_centre(v.P[v.nv1], o2);
-    for (int k = 0; k < 3; k++) { n1[k] = X[k] - o1[k]; n2[k] = X[k] - o2[k]; }
-    double s1 = 0.0, s2 = 0.0, dot = 0.0;
-    for (int k = 0; k < 3; k++) s1 += n1[k] * n1[k];
-    for (int k = 0; k < 3; k++) s2 += n2[k] * n2[k];
-    for (int k = 0; k < 3; k++) dot += n1[k] * n2[k];
-    const double dist1 = sqrt(s1), dist2 = sqrt(s2);
-    const double cosp = dot / (dist1 * dist2);
+    double dist2, cosp;
+    map_parallax(v, X, dist2, cosp);
     o.dist2 = lm_default_nan(dist2);
     o.cos = lm_default_nan(cosp);
     o.verdict = cosp < 0.99998 ? kMapLandmark : kMapParallax;
 }
 
-// one flagged match from the views to the parallax test.  kAnyViews = false: nv <= 4 only, as triangulate<false>
+// one flagged match from the views to the parallax test
 template <bool kAnyViews>
 MCORB_TRI_HD inline void init_match(const MapViews &v, const float *inv_sigma2, MapOut &o)
 {
     map_clear(o);
-    double xx[2 * MCORB_MAX_CAMS], X[3];
-    for (int i = 0; i < v.nv; i++) {
-        const double *K = v.K[i];
-        xx[2 * i] = ((double)v.kx[i] - K[2]) / K[0];
-        xx[2 * i + 1] = ((double)v.ky[i] - K[5]) / K[4];
-    }
-    triangulate<kAnyViews>(xx, v.P, v.nv, X);
+    double X[3];
+    map_dlt<kAnyViews>(v, X);
     init_after(v, X, inv_sigma2, o);
 }
 
-// the views of a match of the packed block: frames[1] is prev, frames[0] is cur, whose `centre` holds cam_centre_body
-MCORB_TRI_HD inline void init_gather(const MapArgs &a, int q, int t, MapViews &v)
-{
-    v.nv = 0;
-    map_gather(a, a.frames[1], q, v);
-    v.nv1 = v.nv;
-    map_gather(a, a.frames[0], t, v);
-}
-
+// the views of a match are map_gather_pair's: frames[1] is prev, frames[0] is cur, whose `centre` holds cam_centre_body
 template <bool kAnyViews>
 MCORB_TRI_HD inline void init_item(const MapArgs &a, const MapItem &it)
 {
     MapViews v;
-    init_gather(a, it.q, it.t, v);
+    map_gather_pair(a, it.q, it.t, v);
     MapOut o;
     init_match<kAnyViews>(v, a.inv_sigma2, o);
     a.out[it.rec] = o;
@@ -255,42 +234,18 @@ inline void init_run_serial(const InitJob &job, const MapArgs &a, const int32_t 
         map_clear(recs[i]);
         if (!flags[i]) continue;
         MapViews v;
-        init_gather(a, query[i], train[i], v);
+        map_gather_pair(a, query[i], train[i], v);
         if (v.nv <= 4) init_match<false>(v, a.inv_sigma2, recs[i]); else init_match<true>(v, a.inv_sigma2, recs[i]);
     }
-    init_finish_serial(job, flags, recs, [&](int i, MapViews &v) { init_gather(a, query[i], train[i], v); }, call, geom, n_rays);
+    init_finish_serial(job, flags, recs, [&](int i, MapViews &v) { map_gather_pair(a, query[i], train[i], v); }, call, geom, n_rays);
 }
 
 // the test hooks (mcorb_host_init_cases, mcorb_dev_init_cases_selftest): everything but the triangulation for caller-given X and
-// views.  Case i has nv[i] views, the first nv1[i] prev's, starting at view voff[i]; centre: centre_w for a view of prev, the
-// camera's cam_centre_body for a view of cur
-struct InitGateCases {
-    const double *X;            // 3 per case
-    const int32_t *nv1, *nv, *voff;
-    const double *P, *K, *centre;   // 12, 9, 3 per view
-    const float *kps;           // 2 per view
-    const int32_t *octave;      // per view
-    const float *inv_sigma2;
-};
-
-MCORB_TRI_HD inline void init_case_views(const InitGateCases &c, int i, MapViews &v)
-{
-    v.nv = c.nv[i];
-    v.nv1 = c.nv1[i];
-    for (int j = 0; j < v.nv; j++) {
-        const size_t w = (size_t)c.voff[i] + j;
-        v.P[j] = c.P + 12 * w;
-        v.K[j] = c.K + 9 * w;
-        v.centre[j] = c.centre + 3 * w;
-        v.kx[j] = c.kps[2 * w]; v.ky[j] = c.kps[2 * w + 1];
-        v.octave[j] = c.octave[w];
-    }
-}
-
-MCORB_TRI_HD inline void init_gate_case(const InitGateCases &c, int i, MapOut &o)
+// views (MapCases); centre: centre_w for a view of prev, the camera's cam_centre_body for a view of cur
+MCORB_TRI_HD inline void init_gate_case(const MapCases &c, int i, MapOut &o)
 {
     MapViews v;
-    init_case_views(c, i, v);
+    map_case_views(c, i, v);
     map_clear(o);
     init_after(v, c.X + 3 * (size_t)i, c.inv_sigma2, o);
 }

@@ -26,9 +26,8 @@ namespace mcorb {
 template <bool kAnyViews>
 __global__ __launch_bounds__(kMapBlock) void k_init_triangulate(MapArgs a, int block0)
 {
-    const MapBlock b = a.blocks[block0 + blockIdx.x];
-    if ((int)threadIdx.x >= b.count) return;
-    init_item<kAnyViews>(a, a.items[b.first + threadIdx.x]);
+    MapBlock b;
+    if (map_lane(a, block0, b)) init_item<kAnyViews>(a, a.items[b.first + threadIdx.x]);
 }
 
 void launch_init_triangulate(hipStream_t st, const MapArgs &a, int nblocks_small, int nblocks_any)
@@ -151,8 +150,8 @@ __global__ __launch_bounds__(kInitPutT) void k_init_put(InitPutArgs p)
     if (flag) {
         o = p.rec[i];
         if (o.verdict == kMapLandmark && call.status == kInitDone) {
-            if (kCases) init_case_views(p.cases, i, v);
-            else init_gather(p.a, p.query[i], p.train[i], v);
+            if (kCases) map_case_views(p.cases, i, v);
+            else map_gather_pair(p.a, p.query[i], p.train[i], v);
         }
     }
     if (init_finish(v, p.job, call, s, flag, o)) {
@@ -171,7 +170,7 @@ void launch_init_put(hipStream_t st, const InitPutArgs &p, bool from_cases)
     else hipLaunchKernelGGL(k_init_put<false>, dim3(nb), dim3(kInitPutT), 0, st, p);
 }
 
-__global__ __launch_bounds__(kMapBlock) void k_init_gates(InitGateCases c, int n, MapOut *__restrict__ out)
+__global__ __launch_bounds__(kMapBlock) void k_init_gates(MapCases c, int n, MapOut *__restrict__ out)
 {
     const int i = blockIdx.x * kMapBlock + threadIdx.x;
     if (i >= n) return;
@@ -180,7 +179,7 @@ __global__ __launch_bounds__(kMapBlock) void k_init_gates(InitGateCases c, int n
     out[i] = o;
 }
 
-void launch_init_gates(hipStream_t st, const InitGateCases &c, int n, MapOut *out)
+void launch_init_gates(hipStream_t st, const MapCases &c, int n, MapOut *out)
 {
     if (n < 1) return;
     hipLaunchKernelGGL(k_init_gates, dim3((n + kMapBlock - 1) / kMapBlock), dim3(kMapBlock), 0, st, c, n, out);

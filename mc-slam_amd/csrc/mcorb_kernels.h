@@ -168,7 +168,6 @@ void launch_lmap_put(hipStream_t st, const int *lids, int n, const double *pt, c
 // the mapping step's kernels (mcorb_mapping_gpu.hip).  k_map_triangulate: one lane per inter-frame match, one wave per block
 // record of a.blocks -- first nblocks_small records of matches with at most 4 views (the instance without the run-time-shaped
 // solver), then nblocks_any of the rest -- one MapOut to a.out[item.rec]
-constexpr int kMapBlock = 64;
 void launch_map_triangulate(hipStream_t st, const MapArgs &a, int nblocks_small, int nblocks_any);
 // k_map_depth: z[i] = row 2 of Rcw * pt3D(lids[i]) + tcw (getSceneDepthStats)
 void launch_map_depth(hipStream_t st, const double Rcw[9], const double tcw[3], const double *geom, const int *lids, int n, double *z);
@@ -385,7 +384,7 @@ struct InitPutArgs {
     InitJob job;
     MapArgs a;
     const int32_t *query, *train;
-    InitGateCases cases;
+    MapCases cases;
     const MapOut *rec;
     const uint8_t *flags;
     const int32_t *offset;
@@ -400,6 +399,6 @@ void launch_init_triangulate(hipStream_t st, const MapArgs &a, int nblocks_small
 void launch_init_select(hipStream_t st, const MapOut *rec, const uint8_t *flags, int n, uint64_t *keys, int32_t *offset, InitSel *sel);
 void launch_init_put(hipStream_t st, const InitPutArgs &p, bool from_cases);
 // init_after of n caller-given cases (mcorb_dev_init_cases_selftest); every pointer of c is device memory
-void launch_init_gates(hipStream_t st, const InitGateCases &c, int n, MapOut *out);
+void launch_init_gates(hipStream_t st, const MapCases &c, int n, MapOut *out);
 
 }  // namespace mcorb

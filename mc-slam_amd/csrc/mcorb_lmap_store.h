@@ -14,8 +14,8 @@
 #include "mcorb_align.h"
 #include "mcorb_ess.h"
 #include "mcorb_init.h"
+#include "mcorb_map_host.h"
 #include "mcorb_mapping_new.h"
-#include "mcorb_pack.h"
 #include "mcorb_pose.h"
 #include "mcorb_rel.h"
 #include "mcorb_sac.h"
@@ -469,46 +469,35 @@ void obs_gather(const mcorb_lmap *m, const ObsInput &in, std::vector<PoseObs> &o
 void obs_stage(const ObsInput &in, const ObsLayout &L, const Staged &s);
 void obs_enqueue_refine(const mcorb_lmap *m, const ObsInput &in, const ObsLayout &L, const Staged &s, const PoseBufs &b);
 
-// shared by mcorb_mapping.cpp and mcorb_init.cpp (defined in the former).  map_who: the entry whose arguments the checks below
-// name in their errors; map_check_frame: a frame's arrays and its lIds; map_count_views: the views of a match of feature q of
-// `other` with feature t of `cur`; map_count_frame / map_pack_frame: what a frame adds to a packed input, and the frame into it
-void map_who(const char *who);
-int map_check_frame(const mcorb_lmap *m, const mcorb_map_frame &f, int ncams, const int32_t *lids);
-int map_count_views(const mcorb_map_frame &other, const mcorb_map_frame &cur, int q, int t, int nlevels, uint8_t &nv);
-void map_count_frame(const mcorb_map_frame &f, size_t &nmi, size_t &nkp);
-void map_pack_frame(const mcorb_map_frame &f, MapFrameDev &d, int32_t *mi, size_t &mi_at, MapKp *kp, size_t &kp_at);
+// shared by the test hooks of mcorb_mapping.cpp and mcorb_init.cpp.  to_device: src[0 .. n) into a fresh d
+template <class T>
+int to_device(DevBuf<T> &d, const T *src, size_t n)
+{
+    TRY(d.alloc(n));
+    HIPCHK(hipMemcpy(d, src, n * sizeof(T), hipMemcpyHostToDevice));
+    return MCORB_OK;
+}
 
-// The matches that need a record, as a device store's kernels take them: per segment (a neighbour; the previous keyframe is
-// segment 0) by view count, in blocks of one wave, the matches of at most 4 views first.  Segment s's matches are query[s] /
-// train[s][0 .. n[s]) and lie at moff[s] in nviews and item_of; wanted(s, j): match j of segment s needs a record
-struct MapWork {
-    std::vector<int32_t> item_of;
-    std::vector<MapItem> items;
-    std::vector<MapBlock> blocks;
-    int nblocks_small = 0;
-    template <class Wanted>
-    void order(int nseg, const int32_t *const *query, const int32_t *const *train, const int32_t *n, const size_t *moff,
-               const uint8_t *nviews, Wanted wanted)
+// the cases of a self-test on the device: the n checked cases h (check_cases: voff[n] views in all) and the level table
+struct CasesDev {
+    DevBuf<double> X, P, K, c;
+    DevBuf<int32_t> nv1, nv, voff, oct;
+    DevBuf<float> kps, sig;
+    int upload(int n, const MapCases &h, int nlevels)
     {
-        std::vector<int> order;
-        for (int pass = 0; pass < 2; pass++) {   // 0: at most 4 views, 1: the rest
-            for (int s = 0; s < nseg; s++) {
-                const uint8_t *nv = nviews + moff[s];
-                order.clear();
-                for (int j = 0; j < n[s]; j++)
-                    if ((nv[j] <= 4) == (pass == 0) && wanted(s, j)) order.push_back(j);
-                std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return nv[a] < nv[b]; });
-                for (size_t k = 0; k < order.size(); k++) {
-                    if (k % kMapBlock == 0)
-                        blocks.push_back(MapBlock{s, (int32_t)items.size(), (int32_t)std::min<size_t>(kMapBlock, order.size() - k)});
-                    const int j = order[k];
-                    item_of[moff[s] + j] = (int32_t)items.size();
-                    items.push_back(MapItem{query[s][j], train[s][j], (int32_t)items.size()});
-                }
-            }
-            if (pass == 0) nblocks_small = (int)blocks.size();
-        }
+        const size_t N = (size_t)n, V = (size_t)h.voff[n];
+        TRY(to_device(X, h.X, N * 3));
+        TRY(to_device(P, h.P, V * 12));
+        TRY(to_device(K, h.K, V * 9));
+        TRY(to_device(c, h.centre, V * 3));
+        TRY(to_device(nv1, h.nv1, N));
+        TRY(to_device(nv, h.nv, N));
+        TRY(to_device(voff, h.voff, N + 1));
+        TRY(to_device(oct, h.octave, V));
+        TRY(to_device(kps, h.kps, V * 2));
+        return to_device(sig, h.inv_sigma2, (size_t)nlevels);
     }
+    MapCases cases() const { return MapCases{X, nv1, nv, voff, P, K, c, kps, oct, sig}; }
 };
 }  // namespace mcorb
 

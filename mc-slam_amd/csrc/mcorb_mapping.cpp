@@ -26,125 +26,32 @@ using namespace mcorb;
 
 namespace {
 
-// the entry that is checking its arguments (one call at a time per thread)
-thread_local const char *g_who = "lmap triangulate_neighbours";
-int bad(const char *what) { set_error(std::string(g_who) + ": " + what); return MCORB_E_ARG; }
-
-// a frame's arrays: camera count, indices inside the keypoint lists
-int check_frame(const mcorb_map_frame &f, int ncams)
-{
-    if (f.ncams != ncams || f.nfeat < 0 || !f.nkps || !f.kps_undist || (f.nfeat && !f.match_index)) return bad("bad frame");
-    for (int c = 0; c < ncams; c++)
-        if (f.nkps[c] < 0 || (f.nkps[c] && !f.kps_undist[c])) return bad("bad frame");
-    for (size_t i = 0; i < (size_t)f.nfeat * ncams; i++) {
-        const int k = f.match_index[i];
-        if (k < -1 || k >= f.nkps[i % ncams]) return bad("match index outside a frame's keypoints");
-    }
-    return MCORB_OK;
-}
-
-// the views of a feature: their count, or -1 for an octave outside [0, nlevels)
-int views_of(const mcorb_map_frame &f, int feat, int nlevels)
-{
-    int nv = 0;
-    for (int c = 0; c < f.ncams; c++) {
-        const int k = f.match_index[(size_t)feat * f.ncams + c];
-        if (k == -1) continue;
-        const int o = f.kps_undist[c][k].octave;
-        if (o < 0 || o >= nlevels) return -1;
-        nv++;
-    }
-    return nv;
-}
-
-void pack_frame(const mcorb_map_frame &f, MapFrameDev &d, int32_t *mi, size_t &mi_at, MapKp *kp, size_t &kp_at)
-{
-    memcpy(d.proj, f.proj, sizeof(d.proj));
-    memcpy(d.centre, f.centre_w, sizeof(d.centre));
-    d.mi_off = (int32_t)mi_at;
-    d.pad = 0;
-    const size_t nmi = (size_t)f.nfeat * f.ncams;
-    if (nmi) memcpy(mi + mi_at, f.match_index, nmi * sizeof(int32_t));
-    mi_at += nmi;
-    for (int c = 0; c < MCORB_MAX_CAMS; c++) {
-        d.kp_off[c] = (int32_t)kp_at;
-        if (c >= f.ncams) continue;
-        for (int k = 0; k < f.nkps[c]; k++) {
-            const mcorb_keypoint &s = f.kps_undist[c][k];
-            kp[kp_at + k] = MapKp{s.x, s.y, s.octave};
-        }
-        kp_at += (size_t)f.nkps[c];
-    }
-}
-
-// a frame's lIds: -1 or a slot of the store
-int check_lids(const mcorb_lmap *m, const mcorb_map_frame &f, const int32_t *lids)
-{
-    for (int i = 0; i < f.nfeat; i++)
-        if (lids[i] < -1 || lids[i] >= m->max_landmarks) return bad("landmark id outside the store");
-    return MCORB_OK;
-}
-
-// the views of a match of feature q of `other` (a neighbour, the previous keyframe) with feature t of the current frame:
-// nv = their count in both frames, nv_cur = in the current frame alone
-int count_views(const mcorb_map_frame &other, const mcorb_map_frame &cur, int q, int t, int nlevels, uint8_t &nv, uint8_t &nv_cur)
-{
-    if (q < 0 || q >= other.nfeat || t < 0 || t >= cur.nfeat) return bad("match index outside a frame");
-    const int v1 = views_of(other, q, nlevels), v2 = views_of(cur, t, nlevels);
-    if (v1 < 0 || v2 < 0) return bad("octave outside nlevels");
-    if (v1 < 1 || v2 < 1) return bad("a matched feature without a view");
-    if (v1 + v2 > MCORB_MAX_CAMS) return bad("a match of more than MCORB_MAX_CAMS views in total (the solver's design limit)");
-    nv = (uint8_t)(v1 + v2);
-    nv_cur = (uint8_t)v2;
-    return MCORB_OK;
-}
-
-// what a frame adds to the packed input: match indices and keypoints
-void count_frame(const mcorb_map_frame &f, size_t &nmi, size_t &nkp)
-{
-    nmi += (size_t)f.nfeat * f.ncams;
-    for (int c = 0; c < f.ncams; c++) nkp += (size_t)f.nkps[c];
-}
-
-// The packed input of a call: a device store's pinned block, reserved with the records (nitems), the depths (nz) and, with
-// `extra`, triangulate_new's second halves; a host vector otherwise.  Filled with the frames (the current one first), K, the
-// level table, the blocks and the items
-int map_block(mcorb_lmap *m, bool on_device, const MapLayout &L, const MapWork &w, size_t nz, bool extra, const mcorb_map_frame *cur,
-              const mcorb_map_frame *others, int n_others, const double *K, const float *inv_sigma2, int nlevels,
-              std::vector<uint8_t> &host_block, uint8_t *&base)
+// Where a call packs its input, and the input packed (MapCall::pack): a device store's pinned block, reserved with the records
+// (the call's items), the depths (nz) and, with `extra`, triangulate_new's second halves; a host vector otherwise
+int map_block(mcorb_lmap *m, bool on_device, const MapCall &mc, const MapLayout &L, size_t nz, bool extra, const double *K,
+              const float *inv_sigma2, std::vector<uint8_t> &host_block, uint8_t *&base)
 {
     if (on_device) {
         HIPCHK(hipSetDevice(m->device));
-        TRY(m->map.reserve(L.p.total, w.items.size(), nz, extra));
+        (void)hipGetLastError();   // (a stale error of this thread is not this call's)
+        TRY(m->map.reserve(L.p.total, mc.w.items.size(), nz, extra));
         base = m->map.in.h;
     } else {
         host_block.resize(L.p.total);
         base = host_block.data();
     }
-    MapFrameDev *fr = (MapFrameDev *)(base + L.frames);
-    int32_t *mi = (int32_t *)(base + L.mi);
-    MapKp *kp = (MapKp *)(base + L.kp);
-    size_t mi_at = 0, kp_at = 0;
-    pack_frame(*cur, fr[0], mi, mi_at, kp, kp_at);
-    for (int s = 0; s < n_others; s++) pack_frame(others[s], fr[1 + s], mi, mi_at, kp, kp_at);
-    memcpy(base + L.K, K, (size_t)cur->ncams * 9 * sizeof(double));
-    memcpy(base + L.sig, inv_sigma2, (size_t)nlevels * sizeof(float));
-    if (!w.blocks.empty()) memcpy(base + L.blocks, w.blocks.data(), w.blocks.size() * sizeof(MapBlock));
-    if (!w.items.empty()) memcpy(base + L.items, w.items.data(), w.items.size() * sizeof(MapItem));
+    mc.pack(base, L, K, inv_sigma2);
     return MCORB_OK;
 }
 
 // what both entries refuse once the walk has counted the new landmarks
 template <class Out>
-int check_new_ids(const mcorb_lmap *m, int32_t next_lid, int ntri, Out *out)
+int check_new_ids(const MapCall &mc, int32_t next_lid, int ntri, Out *out)
 {
     out->n_depth = out->n_triangulated = ntri;
-    if (ntri && (size_t)next_lid + (size_t)ntri > (size_t)m->max_landmarks) {
-        set_error(std::string(g_who) + ": new landmark ids beyond max_landmarks");
-        return MCORB_E_CAP;
-    }
-    if (ntri > out->cap_depth) { set_error(std::string(g_who) + ": output too small"); return MCORB_E_CAP; }
-    if (ntri && !out->depth_vec) return bad("bad argument");
+    if (ntri && (size_t)next_lid + (size_t)ntri > (size_t)mc.max_landmarks) return mc.fail(MCORB_E_CAP, "new landmark ids beyond max_landmarks");
+    if (ntri > out->cap_depth) return mc.fail(MCORB_E_CAP, "output too small");
+    if (ntri && !out->depth_vec) return mc.bad("bad argument");
     return MCORB_OK;
 }
 
@@ -154,13 +61,14 @@ int put_landmarks(mcorb_lmap *m, bool on_device, int32_t next_lid, int ntri, con
 {
     if (on_device && ntri) {
         hipStream_t st = m->st;
-        TRY(m->map.h_put.grow((size_t)ntri, hipHostMallocDefault));
-        TRY(m->map.d_put.grow((size_t)ntri));
-        for (int k = 0; k < ntri; k++) m->map.h_put[k] = make_int2(item_of[k], next_lid + k);
-        HIPCHK(hipMemcpyAsync(m->map.d_put, m->map.h_put, (size_t)ntri * sizeof(int2), hipMemcpyHostToDevice, st));
-        launch_map_put(st, m->map.d_out, m->map.d_put, ntri, m->d_geom, m->d_nrays);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipStreamSynchronize(st));
+        mcorb_lmap::Mapping &b = m->map;
+        TRY(b.h_put.grow((size_t)ntri, hipHostMallocDefault));
+        TRY(b.d_put.grow((size_t)ntri));
+        for (int k = 0; k < ntri; k++) b.h_put[k] = make_int2(item_of[k], next_lid + k);
+        Submission sub(st);
+        sub.run([&] { (void)hipMemcpyAsync(b.d_put, b.h_put, (size_t)ntri * sizeof(int2), hipMemcpyHostToDevice, st); });
+        sub.run([&] { launch_map_put(st, b.d_out, b.d_put, ntri, m->d_geom, m->d_nrays); });
+        TRY(sub.wait());
     } else {
         for (int k = 0; k < ntri; k++) {
             double *g = &m->geom[(size_t)(next_lid + k) * 6];
@@ -182,23 +90,12 @@ double norm3(const double a[3], const double b[3])   // cv::norm(a - b)
     return sqrt(s);
 }
 
-int check_gate_cases(const double *X, const int32_t *nv1, const int32_t *nv, const double *P, const double *K, const double *centre,
-                     const float *kps, const int32_t *octave, const double *F, const float *inv_sigma2, int nlevels, int n,
-                     std::vector<int32_t> &voff)
+// what the four hooks refuse: check_cases with the gates' prefix (the refine hooks report theirs under it too); per: the hook's
+// own array per case (F, twc_cur)
+int check_gate_cases(MapCases &c, const double *per, int nlevels, int n, std::vector<int32_t> &voff)
 {
-    if (!X || !nv1 || !nv || !P || !K || !centre || !kps || !octave || !F || !inv_sigma2 || nlevels < 1 || n < 1) {
-        set_error("map gates: bad argument");
-        return MCORB_E_ARG;
-    }
-    voff.resize((size_t)n + 1);
-    voff[0] = 0;
-    for (int i = 0; i < n; i++) {
-        if (nv1[i] < 1 || nv[i] <= nv1[i] || nv[i] > MCORB_MAX_CAMS) { set_error("map gates: view counts out of range"); return MCORB_E_ARG; }
-        voff[i + 1] = voff[i] + nv[i];
-    }
-    for (int w = 0; w < voff[n]; w++)
-        if (octave[w] < 0 || octave[w] >= nlevels) { set_error("map gates: octave outside nlevels"); return MCORB_E_ARG; }
-    return MCORB_OK;
+    if (!per) { set_error("map gates: bad argument"); return MCORB_E_ARG; }
+    return check_cases("map gates", c, nlevels, n, voff);
 }
 
 void gates_out(const MapOut *o, int n, int32_t *verdict, int32_t *n_rays, double *vals)
@@ -226,58 +123,7 @@ void refine_out(const MapOut *o, const MapNewExtra *e, int n, int32_t *verdict, 
     }
 }
 
-
-template <class T>
-int to_device(DevBuf<T> &d, const T *src, size_t n)
-{
-    TRY(d.alloc(n));
-    HIPCHK(hipMemcpy(d, src, n * sizeof(T), hipMemcpyHostToDevice));
-    return MCORB_OK;
-}
-
-// the case arrays the two selftests share, on the device: n cases of voff[n] views in all
-struct CasesDev {
-    DevBuf<double> X, P, K, c;
-    DevBuf<int32_t> nv1, nv, voff, oct;
-    DevBuf<float> kps, sig;
-    int upload(int n, const std::vector<int32_t> &voff_h, const double *X_h, const int32_t *nv1_h, const int32_t *nv_h, const double *P_h,
-               const double *K_h, const double *centre, const float *kps_h, const int32_t *octave, const float *inv_sigma2, int nlevels)
-    {
-        const size_t N = (size_t)n, V = (size_t)voff_h[n];
-        TRY(to_device(X, X_h, N * 3));
-        TRY(to_device(P, P_h, V * 12));
-        TRY(to_device(K, K_h, V * 9));
-        TRY(to_device(c, centre, V * 3));
-        TRY(to_device(nv1, nv1_h, N));
-        TRY(to_device(nv, nv_h, N));
-        TRY(to_device(voff, voff_h.data(), N + 1));
-        TRY(to_device(oct, octave, V));
-        TRY(to_device(kps, kps_h, V * 2));
-        return to_device(sig, inv_sigma2, (size_t)nlevels);
-    }
-};
-
 }  // namespace
-
-// what mcorb_init.cpp shares with the two entries above (mcorb_lmap_store.h)
-namespace mcorb {
-void map_who(const char *who) { g_who = who; }
-int map_check_frame(const mcorb_lmap *m, const mcorb_map_frame &f, int ncams, const int32_t *lids)
-{
-    TRY(check_frame(f, ncams));
-    return check_lids(m, f, lids);
-}
-int map_count_views(const mcorb_map_frame &other, const mcorb_map_frame &cur, int q, int t, int nlevels, uint8_t &nv)
-{
-    uint8_t nv_cur;
-    return count_views(other, cur, q, t, nlevels, nv, nv_cur);
-}
-void map_count_frame(const mcorb_map_frame &f, size_t &nmi, size_t &nkp) { count_frame(f, nmi, nkp); }
-void map_pack_frame(const mcorb_map_frame &f, MapFrameDev &d, int32_t *mi, size_t &mi_at, MapKp *kp, size_t &kp_at)
-{
-    pack_frame(f, d, mi, mi_at, kp, kp_at);
-}
-}  // namespace mcorb
 
 extern "C" {
 
@@ -287,33 +133,36 @@ int mcorb_lmap_triangulate_neighbours(mcorb_lmap *m, const mcorb_map_frame *cur,
                                       const double *K, const float *inv_sigma2, int nlevels, const double Rcw[9], const double tcw[3],
                                       int32_t next_lid, mcorb_map_out *out)
 {
-    g_who = "lmap triangulate_neighbours";
+    const char *const who = "lmap triangulate_neighbours";
     if (out) { out->n_matches = out->n_depth = out->n_triangulated = 0; out->next_lid = next_lid; }
-    TRY(check_lmap(m, "lmap triangulate_neighbours"));
+    TRY(check_lmap(m, who));
+    MapCall mc{who, m->max_landmarks, cur ? cur->ncams : 0, nlevels};
     if (!cur || !out || n_neigh < 0 || !K || !inv_sigma2 || nlevels < 1 || !Rcw || !tcw || next_lid < 0 || out->cap_matches < 0 ||
         out->cap_depth < 0 || (cur->nfeat && !lids_cur) || (n_neigh && (!neigh || !lids_neigh || !F21 || !match_query || !match_train ||
         !n_matches || !out->neigh_skipped)))
-        return bad("bad argument");
-    const int C = cur->ncams;
-    if (C < 1 || C > MCORB_MAX_CAMS) return bad("1 .. MCORB_MAX_CAMS cameras");
+        return mc.bad("bad argument");
+    const int C = mc.C;
+    if (C < 1 || C > MCORB_MAX_CAMS) return mc.bad("1 .. MCORB_MAX_CAMS cameras");
     std::lock_guard<std::mutex> lk(m->mu);
 
     // ---- 1. everything that can be refused is refused before anything runs ----
-    TRY(check_frame(*cur, C));
-    TRY(check_lids(m, *cur, lids_cur));
+    TRY(mc.check_frame(*cur));
+    TRY(mc.check_lids(*cur, lids_cur));
+    mc.add(*cur);
     std::vector<size_t> moff((size_t)n_neigh + 1, 0);
     size_t nz = 0;
     for (int s = 0; s < n_neigh; s++) {
         const mcorb_map_frame &f = neigh[s];
-        TRY(check_frame(f, C));
+        TRY(mc.check_frame(f));
         if (n_matches[s] < 0 || (n_matches[s] && (!match_query[s] || !match_train[s])) || !F21[s] || (f.nfeat && !lids_neigh[s]))
-            return bad("bad argument");
+            return mc.bad("bad argument");
         moff[s + 1] = moff[s] + (size_t)n_matches[s];
-        TRY(check_lids(m, f, lids_neigh[s]));
+        TRY(mc.check_lids(f, lids_neigh[s]));
+        mc.add(f);
         for (int i = 0; i < f.nfeat; i++) {
             const int l = lids_neigh[s][i];
             if (l == -1) continue;
-            if (!(m->flags[l] & kHasPt)) { set_error("lmap triangulate_neighbours: a neighbour's landmark was never set"); return MCORB_E_STATE; }
+            if (!(m->flags[l] & kHasPt)) return mc.fail(MCORB_E_STATE, "a neighbour's landmark was never set");
             nz++;
         }
     }
@@ -323,16 +172,16 @@ int mcorb_lmap_triangulate_neighbours(mcorb_lmap *m, const mcorb_map_frame *cur,
     for (int s = 0; s < n_neigh; s++)
         for (int j = 0; j < n_matches[s]; j++) {
             uint8_t nv_cur;
-            TRY(count_views(neigh[s], *cur, match_query[s][j], match_train[s][j], nlevels, nviews[moff[s] + j], nv_cur));
+            TRY(mc.count_views(neigh[s], match_query[s][j], match_train[s][j], nviews[moff[s] + j], nv_cur));
         }
     out->n_matches = (int32_t)total;
-    if (total > (size_t)out->cap_matches) { set_error("lmap triangulate_neighbours: output too small"); return MCORB_E_CAP; }
+    if (total > (size_t)out->cap_matches) return mc.fail(MCORB_E_CAP, "output too small");
     if (total && (!out->inliers || !out->verdict || !out->new_lid || !out->pt3d || !out->normal || !out->dist2 || !out->cos_parallax))
-        return bad("bad argument");
+        return mc.bad("bad argument");
 
     // ---- 2. the matches that need a record: both features are free on entry ----
     const bool dev = m->device >= 0;
-    MapWork w;
+    MapWork &w = mc.w;
     w.item_of.assign(total, -1);
     if (dev)
         w.order(n_neigh, match_query, match_train, n_matches, moff.data(), nviews.data(),
@@ -340,14 +189,11 @@ int mcorb_lmap_triangulate_neighbours(mcorb_lmap *m, const mcorb_map_frame *cur,
     const std::vector<int32_t> &item_of = w.item_of;
 
     // ---- 3. the packed input: the current frame, the neighbours, their F tables and the landmarks whose depth is taken ----
-    size_t nmi = 0, nkp = 0;
-    count_frame(*cur, nmi, nkp);
-    for (int s = 0; s < n_neigh; s++) count_frame(neigh[s], nmi, nkp);
-    if (nmi > 0x7fffffff || nkp > 0x7fffffff) return bad("frames too large");
-    const MapLayout L((size_t)(1 + n_neigh), (size_t)n_neigh * C * C * 9, (size_t)C, (size_t)nlevels, nmi, nkp, w.blocks.size(), w.items.size(), nz);
+    TRY(mc.fits());
+    const MapLayout L = mc.layout((size_t)n_neigh * C * C * 9, nz);
     std::vector<uint8_t> host_block;
     uint8_t *base;
-    TRY(map_block(m, dev, L, w, nz, false, cur, neigh, n_neigh, K, inv_sigma2, nlevels, host_block, base));
+    TRY(map_block(m, dev, mc, L, nz, false, K, inv_sigma2, host_block, base));
     int32_t *zl = (int32_t *)(base + L.zlids);
     for (int s = 0; s < n_neigh; s++) {
         memcpy(base + L.F + (size_t)s * C * C * 9 * sizeof(double), F21[s], (size_t)C * C * 9 * sizeof(double));
@@ -355,24 +201,24 @@ int mcorb_lmap_triangulate_neighbours(mcorb_lmap *m, const mcorb_map_frame *cur,
             if (lids_neigh[s][i] != -1) *zl++ = lids_neigh[s][i];
     }
 
-    // ---- 4. the depths of the neighbours' landmarks and the records ----
+    // ---- 4. the depths of the neighbours' landmarks and the records: one submission ----
     std::vector<double> z_host;
     const double *z = nullptr;
     const int nitems = (int)w.items.size();
     if (dev) {
         hipStream_t st = m->st;
         mcorb_lmap::Mapping &b = m->map;
+        // (nothing returns between the first launch and the wait, so no kernel of this call still reads the pinned input when
+        // the caller has its error: Submission.  The upload is the chain's first piece: nothing is queued when it fails)
+        Submission sub(st);
         TRY(b.in.upload(st, L.p.total));
-        TRY(b.neigh.mark(st, b.kDepth));
-        launch_map_depth(st, Rcw, tcw, m->d_geom, b.in.dev<const int>(L.zlids), (int)nz, b.d_z);
-        HIPCHK(hipGetLastError());
-        TRY(b.neigh.mark(st, b.kTriangulate));
-        launch_map_triangulate(st, L.args(b.in.d, b.d_out, C), w.nblocks_small, (int)w.blocks.size() - w.nblocks_small);
-        HIPCHK(hipGetLastError());
-        TRY(b.neigh.mark(st, b.kTriangulate + 1));
-        if (nz) HIPCHK(hipMemcpyAsync(b.h_z, b.d_z, nz * sizeof(double), hipMemcpyDeviceToHost, st));
-        if (nitems) HIPCHK(hipMemcpyAsync(b.h_out, b.d_out, (size_t)nitems * sizeof(MapOut), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
+        sub.run(b.neigh, b.kDepth, [&] { launch_map_depth(st, Rcw, tcw, m->d_geom, b.in.dev<const int>(L.zlids), (int)nz, b.d_z); });
+        sub.run(b.neigh, b.kTriangulate,
+                [&] { launch_map_triangulate(st, L.args(b.in.d, b.d_out, C), w.nblocks_small, (int)w.blocks.size() - w.nblocks_small); });
+        sub.mark(b.neigh, b.kTriangulate + 1);
+        if (nz) sub.run([&] { (void)hipMemcpyAsync(b.h_z, b.d_z, nz * sizeof(double), hipMemcpyDeviceToHost, st); });
+        if (nitems) sub.run([&] { (void)hipMemcpyAsync(b.h_out, b.d_out, (size_t)nitems * sizeof(MapOut), hipMemcpyDeviceToHost, st); });
+        TRY(sub.wait());
         b.neigh.read();
         z = b.h_z;
     } else {
@@ -435,7 +281,7 @@ int mcorb_lmap_triangulate_neighbours(mcorb_lmap *m, const mcorb_map_frame *cur,
         }
     }
     const int ntri = (int)acc_match.size();
-    TRY(check_new_ids(m, next_lid, ntri, out));
+    TRY(check_new_ids(mc, next_lid, ntri, out));
 
     // ---- 6. the new landmarks into their slots, then the caller's arrays ----
     const MapOut *recs = dev ? m->map.h_out.get() : rec_host.data();
@@ -480,14 +326,14 @@ int mcorb_lmap_depths(mcorb_lmap *m, const double Rcw[9], const double tcw[3], c
         return MCORB_OK;
     }
     HIPCHK(hipSetDevice(m->device));
+    (void)hipGetLastError();   // (a stale error of this thread is not this call's)
     hipStream_t st = m->st;
     TRY(m->map.d_z.grow((size_t)n));
+    Submission sub(st);   // (its wait also covers the pageable arrays)
     TRY(m->batch.upload(m->batch.d_lids, lids, (size_t)n, st));
-    launch_map_depth(st, Rcw, tcw, m->d_geom, m->batch.d_lids, n, m->map.d_z);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(z, m->map.d_z, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));   // (also covers the pageable arrays)
-    return MCORB_OK;
+    sub.run([&] { launch_map_depth(st, Rcw, tcw, m->d_geom, m->batch.d_lids, n, m->map.d_z); });
+    sub.run([&] { (void)hipMemcpyAsync(z, m->map.d_z, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st); });
+    return sub.wait();
 }
 
 int mcorb_lmap_last_triangulate_timing(mcorb_lmap *m, float us[2], int *n_launched, int *n_depth)
@@ -506,10 +352,11 @@ int mcorb_host_map_gates(int n, const double *X, const int32_t *nv1, const int32
                          const double *centre, const float *kps, const int32_t *octave, const double *F, const float *inv_sigma2,
                          int nlevels, int32_t *verdict, int32_t *n_rays, double *vals)
 {
+    MapCases h{X, nv1, nv, nullptr, P, K, centre, kps, octave, inv_sigma2};
     std::vector<int32_t> voff;
-    TRY(check_gate_cases(X, nv1, nv, P, K, centre, kps, octave, F, inv_sigma2, nlevels, n, voff));
+    TRY(check_gate_cases(h, F, nlevels, n, voff));
     if (!verdict || !n_rays || !vals) { set_error("map gates: bad argument"); return MCORB_E_ARG; }
-    const MapGateCases c{X, nv1, nv, voff.data(), P, K, centre, kps, octave, F, inv_sigma2};
+    const MapGateCases c{h, F};
     std::vector<MapOut> o((size_t)n);
     for (int i = 0; i < n; i++) map_gate_case(c, i, o[i]);
     gates_out(o.data(), n, verdict, n_rays, vals);
@@ -520,8 +367,9 @@ int mcorb_dev_map_gates_selftest(int device, int n, const double *X, const int32
                                  const double *K, const double *centre, const float *kps, const int32_t *octave, const double *F,
                                  const float *inv_sigma2, int nlevels, int32_t *verdict, int32_t *n_rays, double *vals)
 {
+    MapCases h{X, nv1, nv, nullptr, P, K, centre, kps, octave, inv_sigma2};
     std::vector<int32_t> voff;
-    TRY(check_gate_cases(X, nv1, nv, P, K, centre, kps, octave, F, inv_sigma2, nlevels, n, voff));
+    TRY(check_gate_cases(h, F, nlevels, n, voff));
     if (!verdict || !n_rays || !vals) { set_error("map gates: bad argument"); return MCORB_E_ARG; }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) { set_error("no usable HIP device"); return MCORB_E_NODEVICE; }
@@ -530,10 +378,10 @@ int mcorb_dev_map_gates_selftest(int device, int n, const double *X, const int32
     CasesDev d;
     DevBuf<double> d_F;
     DevBuf<MapOut> d_out;
-    TRY(d.upload(n, voff, X, nv1, nv, P, K, centre, kps, octave, inv_sigma2, nlevels));
+    TRY(d.upload(n, h, nlevels));
     TRY(to_device(d_F, F, N * 9));
     TRY(d_out.alloc(N));
-    const MapGateCases c{d.X, d.nv1, d.nv, d.voff, d.P, d.K, d.c, d.kps, d.oct, d_F, d.sig};
+    const MapGateCases c{d.cases(), d_F};
     launch_map_gates(nullptr, c, n, d_out);
     HIPCHK(hipGetLastError());
     std::vector<MapOut> o(N);
@@ -546,7 +394,7 @@ int mcorb_lmap_triangulate_new(mcorb_lmap *m, const mcorb_map_frame *cur, int32_
                                const int32_t *match_query, const int32_t *match_train, int n_matches, const double *K,
                                const float *inv_sigma2, int nlevels, int32_t next_lid, mcorb_map_new_out *out)
 {
-    g_who = "lmap triangulate_new";
+    const char *const who = "lmap triangulate_new";
     if (out) {
         out->n_matches = out->n_depth = out->n_triangulated = 0;
         out->next_lid = next_lid;
@@ -554,31 +402,34 @@ int mcorb_lmap_triangulate_new(mcorb_lmap *m, const mcorb_map_frame *cur, int32_
         memset(out->n_rays_hist, 0, sizeof(out->n_rays_hist));
         memset(out->n_by_verdict, 0, sizeof(out->n_by_verdict));
     }
-    TRY(check_lmap(m, "lmap triangulate_new"));
+    TRY(check_lmap(m, who));
+    MapCall mc{who, m->max_landmarks, cur ? cur->ncams : 0, nlevels};
     if (!cur || !prev || !out || n_matches < 0 || !K || !inv_sigma2 || nlevels < 1 || next_lid < 0 || out->cap_matches < 0 ||
         out->cap_depth < 0 || (cur->nfeat && !lids_cur) || (prev->nfeat && !lids_prev) || (n_matches && (!match_query || !match_train)))
-        return bad("bad argument");
-    const int C = cur->ncams;
-    if (C < 1 || C > MCORB_MAX_CAMS) return bad("1 .. MCORB_MAX_CAMS cameras");
+        return mc.bad("bad argument");
+    const int C = mc.C;
+    if (C < 1 || C > MCORB_MAX_CAMS) return mc.bad("1 .. MCORB_MAX_CAMS cameras");
     std::lock_guard<std::mutex> lk(m->mu);
 
     // ---- 1. everything that can be refused is refused before anything runs ----
-    TRY(check_frame(*cur, C));
-    TRY(check_frame(*prev, C));
-    TRY(check_lids(m, *cur, lids_cur));
-    TRY(check_lids(m, *prev, lids_prev));
+    TRY(mc.check_frame(*cur));
+    TRY(mc.check_frame(*prev));
+    TRY(mc.check_lids(*cur, lids_cur));
+    TRY(mc.check_lids(*prev, lids_prev));
+    mc.add(*cur);
+    mc.add(*prev);
     const size_t total = (size_t)n_matches;
     std::vector<uint8_t> nviews(total, 0), nviews_cur(total, 0);
-    for (int j = 0; j < n_matches; j++) TRY(count_views(*prev, *cur, match_query[j], match_train[j], nlevels, nviews[j], nviews_cur[j]));
+    for (int j = 0; j < n_matches; j++) TRY(mc.count_views(*prev, match_query[j], match_train[j], nviews[j], nviews_cur[j]));
     out->n_matches = n_matches;
-    if (n_matches > out->cap_matches) { set_error("lmap triangulate_new: output too small"); return MCORB_E_CAP; }
+    if (n_matches > out->cap_matches) return mc.fail(MCORB_E_CAP, "output too small");
     if (total && (!out->inliers || !out->verdict || !out->new_lid || !out->pt3d || !out->normal || !out->dist || !out->cos_parallax ||
                   !out->iterations || !out->cost_initial || !out->cost_final))
-        return bad("bad argument");
+        return mc.bad("bad argument");
 
     // ---- 2. the matches that need a record: the current feature is free on entry ----
     const bool dev = m->device >= 0;
-    MapWork w;
+    MapWork &w = mc.w;
     w.item_of.assign(total, -1);
     const size_t moff[2] = {0, total};
     if (dev) w.order(1, &match_query, &match_train, &n_matches, moff, nviews.data(), [&](int, int j) { return lids_cur[match_train[j]] == -1; });
@@ -586,14 +437,11 @@ int mcorb_lmap_triangulate_new(mcorb_lmap *m, const mcorb_map_frame *cur, int32_
     const int nitems = (int)w.items.size();
 
     // ---- 3. the packed input: the current frame, then the previous keyframe ----
-    size_t nmi = 0, nkp = 0;
-    count_frame(*cur, nmi, nkp);
-    count_frame(*prev, nmi, nkp);
-    if (nmi > 0x7fffffff || nkp > 0x7fffffff) return bad("frames too large");
-    const MapLayout L(2, 0, (size_t)C, (size_t)nlevels, nmi, nkp, w.blocks.size(), w.items.size(), 0);
+    TRY(mc.fits());
+    const MapLayout L = mc.layout(0, 0);
     std::vector<uint8_t> host_block;
     uint8_t *base;
-    TRY(map_block(m, dev && nitems, L, w, 0, true, cur, prev, 1, K, inv_sigma2, nlevels, host_block, base));
+    TRY(map_block(m, dev && nitems, mc, L, 0, true, K, inv_sigma2, host_block, base));
     MapNewArgs na;
     for (int k = 0; k < 3; k++) { na.twc_cur[k] = cur->twc[k]; na.twc_prev[k] = prev->twc[k]; }
 
@@ -603,14 +451,13 @@ int mcorb_lmap_triangulate_new(mcorb_lmap *m, const mcorb_map_frame *cur, int32_
         mcorb_lmap::Mapping &b = m->map;
         na.a = L.args(b.in.d, b.d_out, C);
         na.extra = b.d_extra;
+        Submission sub(st);   // (as in mcorb_lmap_triangulate_neighbours)
         TRY(b.in.upload(st, L.p.total));
-        TRY(b.refine_new.mark(st, 0));
-        launch_map_refine_new(st, na, w.nblocks_small, (int)w.blocks.size() - w.nblocks_small);
-        HIPCHK(hipGetLastError());
-        TRY(b.refine_new.mark(st, 1));
-        HIPCHK(hipMemcpyAsync(b.h_out, b.d_out, (size_t)nitems * sizeof(MapOut), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(b.h_extra, b.d_extra, (size_t)nitems * sizeof(MapNewExtra), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
+        sub.run(b.refine_new, 0, [&] { launch_map_refine_new(st, na, w.nblocks_small, (int)w.blocks.size() - w.nblocks_small); });
+        sub.mark(b.refine_new, 1);
+        sub.run([&] { (void)hipMemcpyAsync(b.h_out, b.d_out, (size_t)nitems * sizeof(MapOut), hipMemcpyDeviceToHost, st); });
+        sub.run([&] { (void)hipMemcpyAsync(b.h_extra, b.d_extra, (size_t)nitems * sizeof(MapNewExtra), hipMemcpyDeviceToHost, st); });
+        TRY(sub.wait());
         b.refine_new.read();
         b.last_new_launched = nitems;
     }
@@ -642,7 +489,7 @@ int mcorb_lmap_triangulate_new(mcorb_lmap *m, const mcorb_map_frame *cur, int32_
         hist[nviews_cur[j] - 1]++;
     }
     const int ntri = (int)acc_match.size();
-    TRY(check_new_ids(m, next_lid, ntri, out));
+    TRY(check_new_ids(mc, next_lid, ntri, out));
 
     // ---- 6. the new landmarks into their slots, then the caller's arrays ----
     std::vector<int32_t> acc_item((size_t)ntri);
@@ -689,10 +536,11 @@ int mcorb_host_map_refine(int n, const double *X0, const int32_t *nv1, const int
                           const float *inv_sigma2, int nlevels, int32_t *verdict, int32_t *n_rays, int32_t *solves, float *cosp,
                           double *vals)
 {
+    MapCases h{X0, nv1, nv, nullptr, P, K, centre, kps, octave, inv_sigma2};
     std::vector<int32_t> voff;
-    TRY(check_gate_cases(X0, nv1, nv, P, K, centre, kps, octave, twc_cur, inv_sigma2, nlevels, n, voff));
+    TRY(check_gate_cases(h, twc_cur, nlevels, n, voff));
     if (!twc_prev || !verdict || !n_rays || !solves || !cosp || !vals) { set_error("map refine: bad argument"); return MCORB_E_ARG; }
-    const MapRefineCases c{X0, nv1, nv, voff.data(), P, K, centre, kps, octave, twc_cur, twc_prev, inv_sigma2};
+    const MapRefineCases c{h, twc_cur, twc_prev};
     std::vector<MapOut> o((size_t)n);
     std::vector<MapNewExtra> e((size_t)n);
     for (int i = 0; i < n; i++) map_refine_case(c, i, o[i], e[i]);
@@ -705,8 +553,9 @@ int mcorb_dev_map_refine_selftest(int device, int n, const double *X0, const int
                                   const double *twc_prev, const float *inv_sigma2, int nlevels, int32_t *verdict, int32_t *n_rays,
                                   int32_t *solves, float *cosp, double *vals)
 {
+    MapCases h{X0, nv1, nv, nullptr, P, K, centre, kps, octave, inv_sigma2};
     std::vector<int32_t> voff;
-    TRY(check_gate_cases(X0, nv1, nv, P, K, centre, kps, octave, twc_cur, inv_sigma2, nlevels, n, voff));
+    TRY(check_gate_cases(h, twc_cur, nlevels, n, voff));
     if (!twc_prev || !verdict || !n_rays || !solves || !cosp || !vals) { set_error("map refine: bad argument"); return MCORB_E_ARG; }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) { set_error("no usable HIP device"); return MCORB_E_NODEVICE; }
@@ -716,12 +565,12 @@ int mcorb_dev_map_refine_selftest(int device, int n, const double *X0, const int
     DevBuf<double> d_tc, d_tp;
     DevBuf<MapOut> d_out;
     DevBuf<MapNewExtra> d_ext;
-    TRY(d.upload(n, voff, X0, nv1, nv, P, K, centre, kps, octave, inv_sigma2, nlevels));
+    TRY(d.upload(n, h, nlevels));
     TRY(to_device(d_tc, twc_cur, N * 3));
     TRY(to_device(d_tp, twc_prev, N * 3));
     TRY(d_out.alloc(N));
     TRY(d_ext.alloc(N));
-    const MapRefineCases c{d.X, d.nv1, d.nv, d.voff, d.P, d.K, d.c, d.kps, d.oct, d_tc, d_tp, d.sig};
+    const MapRefineCases c{d.cases(), d_tc, d_tp};
     launch_map_refine_cases(nullptr, c, n, d_out, d_ext);
     HIPCHK(hipGetLastError());
     std::vector<MapOut> o(N);

@@ -127,12 +127,10 @@ MCORB_TRI_HD inline int map_view_gates(const MapViews &v, const double X[3], con
     return kMapLandmark;
 }
 
-// everything after the triangulation: the per-view gates, the parallax window, the normal of the new landmark
-MCORB_TRI_HD inline void map_after(const MapViews &v, const double X[3], const float *inv_sigma2, MapOut &o)
+// the two rays of the parallax tests (:5918-5926; FrontEnd::initialization has the same lines, :2731-2745): n1 = X - o1 and
+// n2 = X - o2 from the first view of each frame; dist2 = |n2| and cos = dot / (dist1 * dist2), as they come
+MCORB_TRI_HD inline void map_parallax(const MapViews &v, const double X[3], double &dist2, double &cosp)
 {
-    for (int k = 0; k < 3; k++) o.X[k] = X[k];
-    const int gate = map_view_gates(v, X, inv_sigma2);
-    if (gate != kMapLandmark) { o.verdict = gate; return; }
     double o1[3], o2[3], n1[3], n2[3];
     map_centre(v.P[0], o1);
     map_centre(v.P[v.nv1], o2);
@@ -141,35 +139,57 @@ MCORB_TRI_HD inline void map_after(const MapViews &v, const double X[3], const f
     for (int k = 0; k < 3; k++) s1 += n1[k] * n1[k];
     for (int k = 0; k < 3; k++) s2 += n2[k] * n2[k];
     for (int k = 0; k < 3; k++) dot += n1[k] * n2[k];
-    const double dist1 = sqrt(s1), dist2 = sqrt(s2);
-    const double cosp = dot / (dist1 * dist2);
-    o.dist2 = dist2;
-    o.cos = cosp;
-    if (!(cosp < 0.99998 && cosp > 0.5)) { o.verdict = kMapParallax; return; }
-    // Landmark(pt3d, prev_kf, ..): KFs.size() == 1, normal = rays / n_rays; addLfFrame(currentFrame, ..): size 2,
-    // normal = (normal * n_rays + rays) / (n_rays + rays')
+    const double dist1 = sqrt(s1);
+    dist2 = sqrt(s2);
+    cosp = dot / (dist1 * dist2);
+}
+
+// a new landmark's normal and ray count: Landmark(pt3d, prev_kf, ..) -- KFs.size() == 1, normal = rays / n_rays -- over views
+// [0, nv1), then addLfFrame(currentFrame, ..) -- size 2, normal = (normal * n_rays + rays) / (n_rays + rays') -- over [nv1, nv)
+MCORB_TRI_HD inline void map_new_normal(const MapViews &v, const double X[3], double normal[3], int32_t &n_rays)
+{
     double acc[3];
     map_rays(v, 0, v.nv1, X, acc);
-    lm_normal_first(acc, v.nv1, o.normal, o.n_rays);
+    lm_normal_first(acc, v.nv1, normal, n_rays);
     map_rays(v, v.nv1, v.nv, X, acc);
-    lm_normal_add(acc, v.nv - v.nv1, o.normal, o.n_rays);
+    lm_normal_add(acc, v.nv - v.nv1, normal, n_rays);
+}
+
+// everything after the triangulation: the per-view gates, the parallax window, the normal of the new landmark
+MCORB_TRI_HD inline void map_after(const MapViews &v, const double X[3], const float *inv_sigma2, MapOut &o)
+{
+    for (int k = 0; k < 3; k++) o.X[k] = X[k];
+    const int gate = map_view_gates(v, X, inv_sigma2);
+    if (gate != kMapLandmark) { o.verdict = gate; return; }
+    map_parallax(v, X, o.dist2, o.cos);
+    if (!(o.cos < 0.99998 && o.cos > 0.5)) { o.verdict = kMapParallax; return; }
+    map_new_normal(v, X, o.normal, o.n_rays);
     o.verdict = kMapLandmark;
 }
 
-// one match from the epipolar gate to the normal.  kAnyViews = false: nv <= 4 only, as triangulate<false>
+// the DLT of a match's views (:5881): x = (pt.x - K02) / K00, y = (pt.y - K12) / K11, then mcorb::triangulate.  kAnyViews = false:
+// nv <= 4 only, as triangulate<false>
 template <bool kAnyViews>
-MCORB_TRI_HD inline void map_match(const MapViews &v, const double *F, const float *inv_sigma2, MapOut &o)
+MCORB_TRI_HD inline void map_dlt(const MapViews &v, double X[3])
 {
-    map_clear(o);
-    o.verdict = map_epipolar(v, F);
-    if (o.verdict != kMapLandmark) return;
-    double xx[2 * MCORB_MAX_CAMS], X[3];
+    double xx[2 * MCORB_MAX_CAMS];
     for (int i = 0; i < v.nv; i++) {
         const double *K = v.K[i];
         xx[2 * i] = ((double)v.kx[i] - K[2]) / K[0];
         xx[2 * i + 1] = ((double)v.ky[i] - K[5]) / K[4];
     }
     triangulate<kAnyViews>(xx, v.P, v.nv, X);
+}
+
+// one match from the epipolar gate to the normal
+template <bool kAnyViews>
+MCORB_TRI_HD inline void map_match(const MapViews &v, const double *F, const float *inv_sigma2, MapOut &o)
+{
+    map_clear(o);
+    o.verdict = map_epipolar(v, F);
+    if (o.verdict != kMapLandmark) return;
+    double X[3];
+    map_dlt<kAnyViews>(v, X);
     map_after(v, X, inv_sigma2, o);
 }
 
@@ -182,7 +202,8 @@ struct MapFrameDev {            // one keyframe
     int32_t mi_off, pad;              // the frame's match_index (nfeat x ncams) in the int pool
 };
 struct MapItem { int32_t q, t, rec; };           // neighbour feature, current feature, output record
-struct MapBlock { int32_t seg, first, count; };  // one wave: neighbour, first item, items (<= 64)
+constexpr int kMapBlock = 64;                    // the lanes of a workgroup of the block kernels: one wave
+struct MapBlock { int32_t seg, first, count; };  // one wave: neighbour, first item, items (<= kMapBlock)
 
 struct MapArgs {
     const MapFrameDev *frames;   // [0] the current frame, [1 + s] neighbour s
@@ -216,6 +237,15 @@ MCORB_TRI_HD inline int map_gather(const MapArgs &a, const MapFrameDev &f, int f
     return first;
 }
 
+// the views of a match of feature q of frames[1] (the previous keyframe, prev) with feature t of frames[0] (the current frame)
+MCORB_TRI_HD inline void map_gather_pair(const MapArgs &a, int q, int t, MapViews &v)
+{
+    v.nv = 0;
+    map_gather(a, a.frames[1], q, v);
+    v.nv1 = v.nv;
+    map_gather(a, a.frames[0], t, v);
+}
+
 template <bool kAnyViews>
 MCORB_TRI_HD inline void map_item(const MapArgs &a, int seg, const MapItem &it)
 {
@@ -230,21 +260,31 @@ MCORB_TRI_HD inline void map_item(const MapArgs &a, int seg, const MapItem &it)
     a.out[it.rec] = o;
 }
 
-// the gates' test hooks (mcorb_host_map_gates, mcorb_dev_map_gates_selftest): everything but the triangulation for caller-given
-// X, views and constants.  Case i has nv[i] views, the first nv1[i] the neighbour's, starting at view voff[i]
-struct MapGateCases {
+#ifdef __HIPCC__
+// the block kernels (k_map_triangulate, k_map_refine_new, k_init_triangulate): the wave's block record; false for a lane without
+// an item, whose item is otherwise a.items[b.first + threadIdx.x]
+__device__ inline bool map_lane(const MapArgs &a, int block0, MapBlock &b)
+{
+    b = a.blocks[block0 + blockIdx.x];
+    return (int)threadIdx.x < b.count;
+}
+#endif
+
+// the cases of the test hooks (mcorb_host_* / mcorb_dev_*_selftest of the gates, of map_refine and of the initialization):
+// everything but the triangulation for caller-given points, views and constants.  Case i has nv[i] views, the first nv1[i] the
+// neighbour's (the previous keyframe's), starting at view voff[i]
+struct MapCases {
     const double *X;            // 3 per case
     const int32_t *nv1, *nv, *voff;
     const double *P, *K, *centre;   // 12, 9, 3 per view
     const float *kps;           // 2 per view
     const int32_t *octave;      // per view
-    const double *F;            // 9 per case
     const float *inv_sigma2;
 };
+struct MapGateCases : MapCases { const double *F; };   // 9 per case
 
-MCORB_TRI_HD inline void map_gate_case(const MapGateCases &c, int i, MapOut &o)
+MCORB_TRI_HD inline void map_case_views(const MapCases &c, int i, MapViews &v)
 {
-    MapViews v;
     v.nv = c.nv[i];
     v.nv1 = c.nv1[i];
     for (int j = 0; j < v.nv; j++) {
@@ -255,6 +295,12 @@ MCORB_TRI_HD inline void map_gate_case(const MapGateCases &c, int i, MapOut &o)
         v.kx[j] = c.kps[2 * w]; v.ky[j] = c.kps[2 * w + 1];
         v.octave[j] = c.octave[w];
     }
+}
+
+MCORB_TRI_HD inline void map_gate_case(const MapGateCases &c, int i, MapOut &o)
+{
+    MapViews v;
+    map_case_views(c, i, v);
     map_clear(o);
     o.verdict = map_epipolar(v, c.F + 9 * (size_t)i);
     if (o.verdict == kMapLandmark) map_after(v, c.X + 3 * (size_t)i, c.inv_sigma2, o);

@@ -28,9 +28,8 @@ namespace mcorb {
 template <bool kAnyViews>
 __global__ __launch_bounds__(kMapBlock) void k_map_triangulate(MapArgs a, int block0)
 {
-    const MapBlock b = a.blocks[block0 + blockIdx.x];
-    if ((int)threadIdx.x >= b.count) return;
-    map_item<kAnyViews>(a, b.seg, a.items[b.first + threadIdx.x]);
+    MapBlock b;
+    if (map_lane(a, block0, b)) map_item<kAnyViews>(a, b.seg, a.items[b.first + threadIdx.x]);
 }
 
 void launch_map_triangulate(hipStream_t st, const MapArgs &a, int nblocks_small, int nblocks_any)
@@ -42,9 +41,8 @@ void launch_map_triangulate(hipStream_t st, const MapArgs &a, int nblocks_small,
 template <bool kAnyViews>
 __global__ __launch_bounds__(kMapBlock) void k_map_refine_new(MapNewArgs n, int block0)
 {
-    const MapBlock b = n.a.blocks[block0 + blockIdx.x];
-    if ((int)threadIdx.x >= b.count) return;
-    map_new_item<kAnyViews>(n, n.a.items[b.first + threadIdx.x]);
+    MapBlock b;
+    if (map_lane(n.a, block0, b)) map_new_item<kAnyViews>(n, n.a.items[b.first + threadIdx.x]);
 }
 
 void launch_map_refine_new(hipStream_t st, const MapNewArgs &n, int nblocks_small, int nblocks_any)

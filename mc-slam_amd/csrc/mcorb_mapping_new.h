@@ -9,7 +9,7 @@
 // Per match, in order:
 //   views            the previous keyframe's views of queryIdx, cameras ascending, then the current frame's of trainIdx (map_gather);
 //                    a view's camera is its frame's proj row (world to camera) and K with skew 0: K[1] is not read
-//   initial point    X0 = mcorb::triangulate on x = ((kx - K02) / K00, (ky - K12) / K11), as map_match calls it; a component of X0
+//   initial point    X0 = mcorb::triangulate on x = ((kx - K02) / K00, (ky - K12) / K11), as map_match calls it (map_dlt); a component of X0
 //                    that is not finite: verdict 8; p.z <= 0 in any view at X0 (a NaN does not take it): verdict 3
 //   factor           p = P[:, :3] * X + P[:, 3] (sum over k from 0.0, then the addend); d = 1.0 / p.z, u = p.x d, v = p.y d;
 //                    r = ((fx u + u0) - kx, (fy v + v0) - ky); J = Dpi * P[:, :3], Dpi = ((fx d, 0, -((fx u) d)), (0, fy d,
@@ -25,7 +25,7 @@
 //   parallax         ray = X - cur->twc, dist = sqrt of three squares added in order; ray1 = X - prev->twc, dist1 = (float)sqrt(..);
 //                    cos = (float)(dot / ((double)dist1 * dist)); (double)cos >= 0.99998 (a NaN passes): verdict 5, not an inlier
 //   landmark         the point is X; normal and n_rays are lm_normal_first over the previous keyframe's views, then lm_normal_add over
-//                    the current frame's (map_after's last lines)
+//                    the current frame's (map_new_normal)
 // Doubles that leave a record go through lm_default_nan: the host and the device give a NaN different signs.
 #pragma once
 #include "mcorb_mapping.h"
@@ -211,11 +211,7 @@ MCORB_TRI_HD inline void map_refine(const MapViews &v, const double X0[3], const
     e.cos = new_default_nan(cosp);
     o.cos = (double)e.cos;
     if ((double)cosp >= 0.99998) { o.verdict = kMapParallax; return; }
-    double acc[3];
-    map_rays(v, 0, v.nv1, X, acc);
-    lm_normal_first(acc, v.nv1, o.normal, o.n_rays);
-    map_rays(v, v.nv1, v.nv, X, acc);
-    lm_normal_add(acc, v.nv - v.nv1, o.normal, o.n_rays);
+    map_new_normal(v, X, o.normal, o.n_rays);
     for (int k = 0; k < 3; k++) o.normal[k] = lm_default_nan(o.normal[k]);
     o.verdict = kMapLandmark;
 }
@@ -234,17 +230,9 @@ MCORB_TRI_HD inline void map_new_item(const MapNewArgs &n, const MapItem &it)
 {
     const MapArgs &a = n.a;
     MapViews v;
-    v.nv = 0;
-    map_gather(a, a.frames[1], it.q, v);
-    v.nv1 = v.nv;
-    map_gather(a, a.frames[0], it.t, v);
-    double xx[2 * MCORB_MAX_CAMS], X0[3];
-    for (int i = 0; i < v.nv; i++) {
-        const double *K = v.K[i];
-        xx[2 * i] = ((double)v.kx[i] - K[2]) / K[0];
-        xx[2 * i + 1] = ((double)v.ky[i] - K[5]) / K[4];
-    }
-    triangulate<kAnyViews>(xx, v.P, v.nv, X0);
+    map_gather_pair(a, it.q, it.t, v);
+    double X0[3];
+    map_dlt<kAnyViews>(v, X0);
     MapOut o;
     MapNewExtra e;
     map_refine(v, X0, n.twc_cur, n.twc_prev, a.inv_sigma2, o, e);
@@ -252,32 +240,15 @@ MCORB_TRI_HD inline void map_new_item(const MapNewArgs &n, const MapItem &it)
     n.extra[it.rec] = e;
 }
 
-// the test hooks (mcorb_host_map_refine, mcorb_dev_map_refine_selftest): everything after the DLT for caller-given X0, views, the
-// two twc and the constants.  Case i has nv[i] views, the first nv1[i] the previous keyframe's, starting at view voff[i]
-struct MapRefineCases {
-    const double *X0;           // 3 per case
-    const int32_t *nv1, *nv, *voff;
-    const double *P, *K, *centre;   // 12, 9, 3 per view
-    const float *kps;           // 2 per view
-    const int32_t *octave;      // per view
-    const double *twc_cur, *twc_prev;   // 3 per case
-    const float *inv_sigma2;
-};
+// the test hooks (mcorb_host_map_refine, mcorb_dev_map_refine_selftest): everything after the DLT for caller-given X0 (MapCases'
+// X), views, the two twc (3 per case each) and the constants
+struct MapRefineCases : MapCases { const double *twc_cur, *twc_prev; };
 
 MCORB_TRI_HD inline void map_refine_case(const MapRefineCases &c, int i, MapOut &o, MapNewExtra &e)
 {
     MapViews v;
-    v.nv = c.nv[i];
-    v.nv1 = c.nv1[i];
-    for (int j = 0; j < v.nv; j++) {
-        const size_t w = (size_t)c.voff[i] + j;
-        v.P[j] = c.P + 12 * w;
-        v.K[j] = c.K + 9 * w;
-        v.centre[j] = c.centre + 3 * w;
-        v.kx[j] = c.kps[2 * w]; v.ky[j] = c.kps[2 * w + 1];
-        v.octave[j] = c.octave[w];
-    }
-    map_refine(v, c.X0 + 3 * (size_t)i, c.twc_cur + 3 * (size_t)i, c.twc_prev + 3 * (size_t)i, c.inv_sigma2, o, e);
+    map_case_views(c, i, v);
+    map_refine(v, c.X + 3 * (size_t)i, c.twc_cur + 3 * (size_t)i, c.twc_prev + 3 * (size_t)i, c.inv_sigma2, o, e);
 }
 
 }  // namespace mcorb

@@ -11,14 +11,18 @@ multiplies the noise and divides the table, as the tests' scene does, so that a 
                share reported is 1 - sum(work) / sum(wave cost) over the call's blocks as the host cuts them.
     The two sides are timed in alternating runs, `reps` each after a warm-up; medians are reported.
   --leg guard [--tree T]
-    mcorb_lmap_triangulate_neighbours' whole call on mapping_rate.py's frame (device store), `reps` runs after a warm-up, on this
-    tree's library or on the one of checkout T.
+    the whole call on a device store of the three triangulation entries, `reps` runs after a warm-up each, on this tree's library
+    or on the one of checkout T: mcorb_lmap_triangulate_neighbours on mapping_rate.py's frame, mcorb_lmap_triangulate_new on this
+    script's frame at --scale 1 and 16, mcorb_lmap_initialize on init_rate.py's rig at 300 and 3 000 matches.  Next to the times
+    of a call: the digest of everything it returns and of the landmarks it stored.
   --leg ab --tree PARENT
-    the regression guard: --procs pairs of fresh processes of --leg guard, the parent's alternating with this commit's.  This
-    commit's median must not exceed the parent's slowest run plus the parent's own spread of medians across its processes.
+    the regression guard: --procs pairs of fresh processes of --leg guard, the parent's alternating with this commit's.  Per call
+    this commit's medians must not exceed the parent's slowest run plus the parent's own spread of medians across its processes,
+    and every digest must be the same in all processes of both trees: the script fails otherwise.
 bench.py times none of this.
     python scripts/mapping_new_rate.py [--reps 5] [--out profiles/mapping_new_rate.json]"""
 import argparse
+import hashlib
 import json
 import os
 import subprocess
@@ -55,9 +59,8 @@ def workload(scale=1.0):
 
 
 def side(mcorb, device, sc):
-    import kfdb_cases
     import mapping_cases as Mc
-    lm = mcorb.LocalMap(mcorb.ORBVocabulary(device=device).create(**kfdb_cases.vocabulary()), device=device, max_landmarks=MAXLM, max_candidates=16)
+    lm = new_store(mcorb, device)
     args = (Mc.to_frame(mcorb, sc["cur"]), sc["cur"]["lids"], Mc.to_frame(mcorb, sc["prev"]), sc["prev"]["lids"], sc["matches"], sc["K"],
             sc["inv_sigma2"], sc["next_lid"])
     return lm, (lambda: lm.triangulate_new(*args))
@@ -112,35 +115,68 @@ def one_leg(mcorb, a):
     return res
 
 
-def guard_leg(mcorb, a):
+def new_store(mcorb, device):
+    import kfdb_cases
+    return mcorb.LocalMap(mcorb.ORBVocabulary(device=device).create(**kfdb_cases.vocabulary()), device=device, max_landmarks=MAXLM, max_candidates=16)
+
+
+def digest(lm, res):
+    """everything a call returned (none of it is a time) and the landmarks it stored"""
+    h = hashlib.sha256()
+    for k, v in sorted(vars(res).items()):
+        for x in (v if isinstance(v, list) else [v]):
+            h.update(k.encode() + np.ascontiguousarray(x).tobytes())
+    for lid in res.new_lid[res.new_lid >= 0]:
+        pt, normal, _, _ = lm.get(int(lid))
+        h.update(pt.tobytes() + normal.tobytes() + np.array([lm.observations(int(lid))[0]], np.int64).tobytes())
+    return h.hexdigest()
+
+
+def guard_calls(mcorb):
+    """name -> (store, call) of the five guarded calls, each on a device store of its own"""
+    import init_cases as Ic
+    import init_rate
     import mapping_rate
-    sc = mapping_rate.workload()
-    lm, f = mapping_rate.side(mcorb, 0, sc)
-    f()
-    runs = []
-    for _ in range(a.reps):
-        t0 = time.perf_counter()
-        f()
-        runs.append((time.perf_counter() - t0) * 1e3)
-    return {"triangulate_neighbours_call_ms": round(float(np.median(runs)), 3), "triangulate_neighbours_call_ms_runs": [round(x, 3) for x in runs]}
+    calls = {"triangulate_neighbours": mapping_rate.side(mcorb, 0, mapping_rate.workload())}
+    for scale in (1, 16):
+        calls["triangulate_new_scale_%d" % scale] = side(mcorb, 0, workload(float(scale)))
+    for n in (300, 3000):
+        lm, sc = new_store(mcorb, 0), Ic.scene(init_rate.CAMS, n=n, seed=17)
+        calls["initialize_%d" % n] = (lm, (lambda lm=lm, sc=sc: Ic.run_scene(mcorb, lm, sc)))
+    return calls
+
+
+def guard_leg(mcorb, a):
+    out = {}
+    for name, (lm, f) in guard_calls(mcorb).items():
+        first = f()                                                 # (also the warm-up)
+        runs = []
+        for _ in range(a.reps):
+            t0 = time.perf_counter()
+            f()
+            runs.append((time.perf_counter() - t0) * 1e3)
+        out[name] = {"call_ms": round(float(np.median(runs)), 3), "call_ms_runs": [round(x, 3) for x in runs], "digest": digest(lm, first)}
+    return out
 
 
 def child(a, tree):
     """one fresh process of --leg guard on `tree`'s library -> its record"""
     cmd = [sys.executable, os.path.abspath(__file__), "--leg", "guard", "--reps", str(a.reps)] + (["--tree", tree] if tree else [])
-    return json.loads(subprocess.run(cmd, check=True, capture_output=True, text=True, timeout=240).stdout.strip().splitlines()[-1])
+    return json.loads(subprocess.run(cmd, check=True, capture_output=True, text=True, timeout=600).stdout.strip().splitlines()[-1])
 
 
 def ab_leg(a):
     pairs = [{"parent": child(a, a.tree), "this": child(a, None)} for _ in range(a.procs)]
-    key = "triangulate_neighbours_call_ms"
-    pm = [p["parent"][key] for p in pairs]
-    slowest = max(x for p in pairs for x in p["parent"][key + "_runs"])
-    spread = max(pm) - min(pm)
-    tm = [p["this"][key] for p in pairs]
-    return {"regression_guard": {"parent_medians_ms": pm, "parent_slowest_run_ms": slowest, "parent_spread_of_medians_ms": round(spread, 3),
-                                 "this_medians_ms": tm, "limit_ms": round(slowest + spread, 3), "met": bool(max(tm) <= slowest + spread)},
-            "pairs": pairs}
+    guard = {}
+    for name in pairs[0]["parent"]:
+        assert len({p[t][name]["digest"] for p in pairs for t in p}) == 1, "the results of %s differ between the trees or the processes" % name
+        pm = [p["parent"][name]["call_ms"] for p in pairs]
+        slowest = max(x for p in pairs for x in p["parent"][name]["call_ms_runs"])
+        spread = max(pm) - min(pm)
+        tm = [p["this"][name]["call_ms"] for p in pairs]
+        guard[name] = {"parent_medians_ms": pm, "parent_slowest_run_ms": slowest, "parent_spread_of_medians_ms": round(spread, 3),
+                       "this_medians_ms": tm, "limit_ms": round(slowest + spread, 3), "met": bool(max(tm) <= slowest + spread)}
+    return {"regression_guard": guard, "equal_bytes_across_trees_and_processes": True, "pairs": pairs}
 
 
 if __name__ == "__main__":
@@ -166,3 +202,5 @@ if __name__ == "__main__":
     if a.out:
         with open(a.out, "w") as f:
             json.dump(out, f, indent=1)
+    if a.leg == "ab" and not all(g["met"] for g in out["regression_guard"].values()):
+        sys.exit("a call is slower than the parent's limit")
