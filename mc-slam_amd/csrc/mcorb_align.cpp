@@ -90,7 +90,6 @@ int mcorb_lmap_align_pose(mcorb_lmap *m, int n, const int32_t *lids1, const doub
             memcpy(b.in.host<double>(L.p1), pts1, (size_t)n * 3 * sizeof(double));
         memcpy(b.in.host<double>(L.p2), pts2, (size_t)n * 3 * sizeof(double));
         hipStream_t st = m->st;
-        TRY(b.in.upload(st, L.p.total));
         AlignArgs a;
         a.job = b.in.dev<const AlignJob>(L.job);
         a.p1 = lids1 ? nullptr : b.in.dev<const double>(L.p1);
@@ -103,9 +102,10 @@ int mcorb_lmap_align_pose(mcorb_lmap *m, int n, const int32_t *lids1, const doub
         a.member = b.d_member;
         a.out = b.h_out;
         a.flags = b.h_flags;
-        if (sac) HIPCHK(hipMemsetAsync(b.d_count, 0, (size_t)H * sizeof(int32_t), st));
         Submission sub(st);
+        b.in.upload(sub, L.p.total);
         if (sac) {
+            sub.fill(b.d_count, 0, (size_t)H * sizeof(int32_t));
             sub.run(b.sac, 0, [&] { launch_align_hypotheses(st, a, H); });
             sub.run(b.sac, 1, [&] { launch_align_score(st, a, n, H); });
             sub.run(b.sac, 2, [&] { launch_align_pick(st, a, n); });

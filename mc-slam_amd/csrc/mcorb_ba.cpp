@@ -152,8 +152,8 @@ int mcorb_lmap_bundle_adjust(mcorb_lmap *m, int nkf, const double *kf_R, const d
     a.nsys = job.nsys;
     a.max_iterations = job.max_iterations;
     hipStream_t st = m->st;
-    TRY(b.in.upload(st, L.p.total));
     Submission sub(st);
+    b.in.upload(sub, L.p.total);
     using B = mcorb_lmap::Ba;
     sub.run(b.chain, B::kBegin, [&] { launch_ba_begin(st, a); });
     sub.run([&] { launch_ba_linearize(st, a); });

@@ -260,7 +260,20 @@ static void descend_host(const mcorb_vocab *v, const uint8_t *desc, int n, int n
     }
 }
 
-int mcorb::vocab_feature_vector(mcorb_vocab *v, const uint8_t *desc, int n, int levelsup, hipStream_t st, BowImageOut &o)
+// k_bow_descend over n descriptors in device memory, the results' way back to h_out and the wait, one submission on st behind
+// what `before` queues; the scratch is reserved (ensure_scratch).  nid_level <= 0: the feature vector is keyed by the root (node 0)
+static int descend(hipStream_t st, mcorb_vocab *v, const uint8_t *d_desc, int n, int nid_level, const Pieces &before = nullptr)
+{
+    Submission sub(st);
+    if (before) before(sub);
+    sub.run([&] {
+        launch_bow_descend(st, d_desc, n, v->d_child_start, v->d_child_count, v->d_child_desc, v->d_child_id, v->d_word_id, v->d_weight, nid_level, v->d_out);
+    });
+    sub.copy(v->h_out, v->d_out, (size_t)n * sizeof(mcorb::BowRes), hipMemcpyDeviceToHost);
+    return sub.wait();
+}
+
+int mcorb::vocab_feature_vector(mcorb_vocab *v, const uint8_t *desc, int n, int levelsup, hipStream_t st, BowImageOut &o, const Pieces &before)
 {
     BowList bow;
     std::map<uint32_t, std::vector<int32_t>> fv;
@@ -271,10 +284,7 @@ int mcorb::vocab_feature_vector(mcorb_vocab *v, const uint8_t *desc, int n, int 
     } else if (n > 0) {
         std::lock_guard<std::mutex> scratch_lock(v->scratch_mu);
         TRY(ensure_scratch(v, n));
-        launch_bow_descend(st, desc, n, v->d_child_start, v->d_child_count, v->d_child_desc, v->d_child_id, v->d_word_id, v->d_weight, v->L - levelsup, v->d_out);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(v->h_out, v->d_out, (size_t)n * sizeof(mcorb::BowRes), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
+        TRY(descend(st, v, desc, n, v->L - levelsup, before));
         assemble(v, v->h_out, n, bow, fv);
     }
     to_image_out(bow, fv, o);
@@ -345,11 +355,7 @@ static int transform_device(mcorb_vocab *v, const uint8_t *d_desc, int n, int le
     BowList bow;
     std::map<uint32_t, std::vector<int32_t>> fv;
     if (n > 0) {
-        const int nid_level = v->L - levelsup;   // <= 0: the feature vector is keyed by the root (node 0)
-        launch_bow_descend(st, d_desc, n, v->d_child_start, v->d_child_count, v->d_child_desc, v->d_child_id, v->d_word_id, v->d_weight, nid_level, v->d_out);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(v->h_out, v->d_out, (size_t)n * sizeof(mcorb::BowRes), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
+        TRY(descend(st, v, d_desc, n, v->L - levelsup));
         assemble(v, v->h_out, n, bow, fv);
     }
     return emit(bow, fv, bow_ids, bow_vals, bow_cap, nbow, fv_nodes, fv_offsets, fv_cap, nfv, fv_feats, feat_cap);
@@ -361,7 +367,7 @@ int mcorb_vocab_transform(mcorb_vocab *v, const uint8_t *desc, int n, int levels
 {
     if (!v || n < 0 || (n && !desc)) { set_error("transform: bad argument"); return MCORB_E_ARG; }
     if (v->device < 0) { set_error("transform: a host-only vocabulary (device -1) has no device tables"); return MCORB_E_NODEVICE; }
-    HIPCHK(hipSetDevice(v->device));
+    TRY(use_device(v->device));
     std::lock_guard<std::mutex> scratch_lock(v->scratch_mu);
     int st = ensure_scratch(v, std::max(n, 1));
     if (st != MCORB_OK) return st;
@@ -389,7 +395,7 @@ extern "C" int mcorb_rig_transform_image(mcorb_rig *r, int slot, int m, mcorb_vo
     }
     if (m < 0 || m >= s->nimg_done) { set_error("image index out of range"); return MCORB_E_ARG; }
     if (v->device != r->rig.device) { set_error("vocabulary lives on another device"); return MCORB_E_ARG; }
-    HIPCHK(hipSetDevice(v->device));
+    TRY(use_device(v->device));
     const int n = s->hc.nsel[m];
     std::lock_guard<std::mutex> scratch_lock(v->scratch_mu);
     int st = ensure_scratch(v, std::max(n, 1));
@@ -412,16 +418,12 @@ extern "C" int mcorb_rig_transform_images(mcorb_rig *r, int slot, int img0, int 
     }
     if (img0 < 0 || img0 + nimg > s->nimg_done) { set_error("image index out of range"); return MCORB_E_ARG; }
     if (v->device != R.device) { set_error("vocabulary lives on another device"); return MCORB_E_ARG; }
-    HIPCHK(hipSetDevice(v->device));
+    TRY(use_device(v->device));
     const int kcap = R.geom.kcap;
     std::lock_guard<std::mutex> scratch_lock(v->scratch_mu);
     int st = ensure_scratch(v, nimg * kcap);
     if (st != MCORB_OK) return st;
-    launch_bow_descend(s->st, s->d_desc + (size_t)img0 * kcap * 32, nimg * kcap, v->d_child_start, v->d_child_count, v->d_child_desc,
-                       v->d_child_id, v->d_word_id, v->d_weight, v->L - levelsup, v->d_out);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(v->h_out, v->d_out, (size_t)nimg * kcap * sizeof(mcorb::BowRes), hipMemcpyDeviceToHost, s->st));
-    HIPCHK(hipStreamSynchronize(s->st));
+    TRY(descend(s->st, v, s->d_desc + (size_t)img0 * kcap * 32, nimg * kcap, v->L - levelsup));
     if ((int)s->bowvec.size() < R.max_images) { s->bowvec.resize(R.max_images); s->bowvec_ok.assign(R.max_images, 0); }
     R.pool->parallel_for(nimg, [&](int i, int) {
         BowList bow;
@@ -608,7 +610,7 @@ extern "C" int mcorb_rig_match_bow_frames(mcorb_rig *r, int slot, int frame0, in
     const int C = R.ncams, kcap = R.geom.kcap, npairs = C * (C - 1) / 2;
     if (frame0 < 0 || (frame0 + nframes) * C > s->nimg_done) { set_error("match_bow: frames not extracted"); return MCORB_E_STATE; }
     if (v->device != R.device) { set_error("vocabulary lives on another device"); return MCORB_E_ARG; }
-    HIPCHK(hipSetDevice(R.device));
+    TRY(use_device(R.device));
     const int img0 = frame0 * C, nimg = nframes * C;
     std::vector<const mcorb_keypoint *> kdef;   // the rig's own undistorted set for rows the caller leaves NULL (undistortion set)
     bool kneed = !y_undist;
@@ -627,11 +629,7 @@ extern "C" int mcorb_rig_match_bow_frames(mcorb_rig *r, int slot, int frame0, in
     std::lock_guard<std::mutex> scratch_lock(v->scratch_mu);
     int st = ensure_scratch(v, nimg * kcap);
     if (st != MCORB_OK) return st;
-    launch_bow_descend(s->st, s->d_desc + (size_t)img0 * kcap * 32, nimg * kcap, v->d_child_start, v->d_child_count, v->d_child_desc,
-                       v->d_child_id, v->d_word_id, v->d_weight, v->L - levelsup, v->d_out);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(v->h_out, v->d_out, (size_t)nimg * kcap * sizeof(mcorb::BowRes), hipMemcpyDeviceToHost, s->st));
-    HIPCHK(hipStreamSynchronize(s->st));
+    TRY(descend(s->st, v, s->d_desc + (size_t)img0 * kcap * 32, nimg * kcap, v->L - levelsup));
     const auto T1 = now();
 
     // 2. per frame: FeatureVectors (addFeature for every non-stopped word, in feature order; the BowVector half of
@@ -698,16 +696,16 @@ extern "C" int mcorb_rig_match_bow_frames(mcorb_rig *r, int slot, int frame0, in
     TRY(v->d_mtab.grow(std::max<size_t>(tab_n, 1)));
     TRY(v->h_mtab.grow(std::max<size_t>(tab_n, 1), hipHostMallocDefault));
     int *d_slot_of = v->d_mi, *d_node_feats = d_slot_of + (size_t)nimg * kcap, *d_nfeat = d_node_feats + (size_t)nimg * kcap, *d_rgbase = d_nfeat + nimg;
-    HIPCHK(hipMemcpyAsync(d_slot_of, h_slot_of.data(), h_slot_of.size() * sizeof(int), hipMemcpyHostToDevice, s->st));
-    HIPCHK(hipMemcpyAsync(d_node_feats, h_node_feats.data(), h_node_feats.size() * sizeof(int), hipMemcpyHostToDevice, s->st));
-    HIPCHK(hipMemcpyAsync(d_nfeat, h_nfeat.data(), nimg * sizeof(int), hipMemcpyHostToDevice, s->st));
-    HIPCHK(hipMemcpyAsync(d_rgbase, h_rgbase.data(), (nframes + 1) * sizeof(int), hipMemcpyHostToDevice, s->st));
-    HIPCHK(hipMemcpyAsync(v->d_my, h_yv.data(), h_yv.size() * sizeof(float), hipMemcpyHostToDevice, s->st));
-    HIPCHK(hipMemcpyAsync(v->d_mrg, h_rg.data(), h_rg.size() * sizeof(int2), hipMemcpyHostToDevice, s->st));
-    launch_bow_best2(s->st, s->d_desc, img0, kcap, C, nframes, v->d_my, d_slot_of, v->d_mrg, d_rgbase, d_node_feats, d_nfeat, v->d_mtab);
-    HIPCHK(hipGetLastError());
-    if (tab_n) HIPCHK(hipMemcpyAsync(v->h_mtab, v->d_mtab, tab_n * sizeof(int4), hipMemcpyDeviceToHost, s->st));
-    HIPCHK(hipStreamSynchronize(s->st));   // also covers the pageable host vectors above
+    Submission sub(s->st);   // (its wait also covers the pageable host vectors above)
+    sub.copy(d_slot_of, h_slot_of.data(), h_slot_of.size() * sizeof(int), hipMemcpyHostToDevice);
+    sub.copy(d_node_feats, h_node_feats.data(), h_node_feats.size() * sizeof(int), hipMemcpyHostToDevice);
+    sub.copy(d_nfeat, h_nfeat.data(), nimg * sizeof(int), hipMemcpyHostToDevice);
+    sub.copy(d_rgbase, h_rgbase.data(), (nframes + 1) * sizeof(int), hipMemcpyHostToDevice);
+    sub.copy(v->d_my, h_yv.data(), h_yv.size() * sizeof(float), hipMemcpyHostToDevice);
+    sub.copy(v->d_mrg, h_rg.data(), h_rg.size() * sizeof(int2), hipMemcpyHostToDevice);
+    sub.run([&] { launch_bow_best2(s->st, s->d_desc, img0, kcap, C, nframes, v->d_my, d_slot_of, v->d_mrg, d_rgbase, d_node_feats, d_nfeat, v->d_mtab); });
+    sub.copy(v->h_mtab, v->d_mtab, tab_n * sizeof(int4), hipMemcpyDeviceToHost);
+    TRY(sub.wait());
     const auto T3 = now();
 
     // 4. per frame: the reference's serial walk over common nodes (:647-929), reading best/second-best from the table

@@ -484,8 +484,10 @@ void bow_assemble(int weighting, int scoring, const BowRes *res, int n, BowImage
 // scoring type (DBoW2's enum) and device (-1: a host-only vocabulary) of a vocabulary (mcorb_bow.cpp), for the keyframe database
 void vocab_props(const ::mcorb_vocab *v, int &scoring, int &device);
 // transform(desc, levelsup)'s descent and assembly for the local map (mcorb_lmap.cpp): desc is n rows in device memory, descended by
-// k_bow_descend on st -- or, for a host-only vocabulary, n host rows descended by the same walk on the host
-int vocab_feature_vector(::mcorb_vocab *v, const uint8_t *desc, int n, int levelsup, hipStream_t st, BowImageOut &o);
+// k_bow_descend on st -- or, for a host-only vocabulary, n host rows descended by the same walk on the host.  before: what the
+// caller queues in front of the descent (the gather that fills desc), behind the scratch's grows; NOT called for a host-only
+// vocabulary or n == 0, where nothing is queued
+int vocab_feature_vector(::mcorb_vocab *v, const uint8_t *desc, int n, int levelsup, hipStream_t st, BowImageOut &o, const Pieces &before = nullptr);
 
 }  // namespace mcorb
 

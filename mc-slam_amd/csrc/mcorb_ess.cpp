@@ -128,8 +128,6 @@ int essential_pose(mcorb_lmap *m, const char *who, int n, const float *uv1, cons
         *b.in.host<EssJob>(L.job) = job;
         fill_obs(b.in.host<EssObs>(L.obs), n, uv1, uv2);
         hipStream_t st = m->st;
-        TRY(b.in.upload(st, L.p.total));
-        HIPCHK(hipMemsetAsync(b.d_count, 0, (slots + 4) * sizeof(int32_t), st));   // (the four votes lie behind the counts)
         EssArgs a;
         a.job = b.in.dev<const EssJob>(L.job);
         a.obs = b.in.dev<const EssObs>(L.obs);
@@ -143,6 +141,8 @@ int essential_pose(mcorb_lmap *m, const char *who, int n, const float *uv1, cons
         a.out = pp ? b.d_out.get() : b.h_out.get();
         a.flags = pp ? b.d_member.get() : b.h_flags.get();
         Submission sub(st);
+        b.in.upload(sub, L.p.total);
+        sub.fill(b.d_count, 0, (slots + 4) * sizeof(int32_t));   // (the four votes lie behind the counts)
         sub.run(b.kernels, 0, [&] { launch_ess_hypotheses(st, a, H); });
         sub.run(b.kernels, 1, [&] { launch_ess_score(st, a, S, H); });
         sub.run(b.kernels, 2, [&] { launch_ess_pick(st, a, S); });

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 
+#include <functional>
 #include <string>
 #include <utility>
 
@@ -29,6 +30,14 @@ void set_error(const std::string &msg);
     } while (0)
 
 namespace mcorb {
+
+// how a call begins on its device: a stale error of this thread is not this call's
+static inline int use_device(int device)
+{
+    HIPCHK(hipSetDevice(device));
+    (void)hipGetLastError();
+    return MCORB_OK;
+}
 
 // what the four owners share: handle H (null = empty), released with Release(H); n_ is the element count of a buffer
 template <typename H, auto Release>
@@ -108,8 +117,8 @@ static inline void ev_elapsed(float *ms, hipEvent_t a, hipEvent_t b)
     if (hipEventElapsedTime(ms, a, b) != hipSuccess) { *ms = 0.f; (void)hipGetLastError(); }
 }
 
-// N + 1 events around N consecutive pieces of a submission: mark(st, i) records event i, so piece i runs between marks i and
-// i + 1.  read(), after the synchronisation: us[i] = the microseconds of piece i by ev_elapsed's rule; the pieces below `from`
+// N + 1 events around N consecutive pieces of a submission: Submission::mark(spans, i) records event i, so piece i runs between
+// marks i and i + 1.  read(), after the synchronisation: us[i] = the microseconds of piece i by ev_elapsed's rule; the pieces below `from`
 // did not run in this submission (their first events were not marked) and read 0
 template <int N>
 struct Spans {
@@ -120,7 +129,6 @@ struct Spans {
         for (Event &e : ev) TRY(e.create(hipEventDefault));
         return MCORB_OK;
     }
-    int mark(hipStream_t st, int i) { HIPCHK(hipEventRecord(ev[i], st)); return MCORB_OK; }
     void read(int from = 0)
     {
         for (int i = 0; i < N; i++) {
@@ -131,26 +139,31 @@ struct Spans {
     }
 };
 
-// A chain of kernels on one stream with one wait.  run(spans, i, launch): mark event i of spans, then launch; run(launch): a
-// piece between no marks; mark(spans, i): the event behind the last piece.  From the first piece on nothing returns before the
-// wait: the first failed launch (hipGetLastError after each) and the first failed mark are kept, and wait() reports, in this
-// order, a failed synchronisation, the launch, the mark -- so no kernel of the chain still reads the call's pinned input or
-// writes its host-mapped records when the caller has its error.  A stale error of the thread is the caller's to discard first.
+// A chain of pieces on one stream with one wait.  A piece is a launch (run), a copy, a fill or a mark: run(spans, i, launch)
+// marks event i of spans, then launches; run(launch) is a launch between no marks; mark(spans, i) the event behind the last
+// piece; copy / fill of 0 bytes queue nothing.  From the first piece on nothing returns before the wait, and after the first
+// piece that fails nothing more is queued: later pieces do nothing and their launch is not called, so no kernel runs behind a
+// failed upload of its input.  wait() synchronises once if a piece was attempted and reports a failed synchronisation first,
+// otherwise the first failed piece by its kind -- so nothing of the chain still reads the call's input (pinned or pageable) or
+// writes its host-mapped records when the caller has its error.  failed() reads the state without waiting (the tracking pair
+// waits elsewhere when nothing failed).  A Submission without a piece does not synchronise: mcorb_lmap_observe with nothing to
+// do, knn2_frames with an empty side and a search without candidates rely on it.  A stale error of the thread is the caller's
+// to discard first; buffers are grown before the first piece.
 class Submission {
 public:
     explicit Submission(hipStream_t stream) : st(stream) {}
+    bool failed() const { return err != hipSuccess; }
     template <int N>
     void mark(Spans<N> &spans, int i)
     {
-        if (marked != MCORB_OK) return;
-        marked = spans.mark(st, i);
-        if (marked != MCORB_OK) (void)hipGetLastError();   // (the event's error is not the next launch's)
+        if (!failed()) note("mark", hipEventRecord(spans.ev[i], st));
     }
     template <class Launch>
     void run(Launch &&launch)
     {
+        if (failed()) return;
         launch();
-        if (launched == hipSuccess) launched = hipGetLastError();
+        note("launch", hipGetLastError());
     }
     template <int N, class Launch>
     void run(Spans<N> &spans, int i, Launch &&launch)
@@ -158,18 +171,46 @@ public:
         mark(spans, i);
         run(launch);
     }
+    void copy(void *dst, const void *src, size_t bytes, hipMemcpyKind kind)
+    {
+        if (bytes && !failed()) note("copy", hipMemcpyAsync(dst, src, bytes, kind, st));
+    }
+    void fill(void *dst, int value, size_t bytes)
+    {
+        if (bytes && !failed()) note("fill", hipMemsetAsync(dst, value, bytes, st));
+    }
     int wait()
     {
-        HIPCHK(hipStreamSynchronize(st));
-        HIPCHK(launched);
-        return marked;
+        if (attempted) {
+            attempted = false;
+            const hipError_t e = hipStreamSynchronize(st);
+            if (e != hipSuccess) return fail("synchronisation", e);
+        }
+        return failed() ? fail(piece, err) : MCORB_OK;
     }
 
 private:
+    void note(const char *kind, hipError_t e)
+    {
+        attempted = true;
+        if (e == hipSuccess) return;
+        err = e;
+        piece = kind;
+        (void)hipGetLastError();   // (this piece's error is not the next call's)
+    }
+    static int fail(const char *kind, hipError_t e)
+    {
+        set_error(std::string("submission: ") + kind + " failed: " + hipGetErrorString(e));
+        return MCORB_E_HIP;
+    }
     hipStream_t st;
-    hipError_t launched = hipSuccess;
-    int marked = MCORB_OK;
+    bool attempted = false;
+    hipError_t err = hipSuccess;
+    const char *piece = "";
 };
+// what a caller hands a function that opens the Submission itself, to be queued first: behind the function's grows, in front of
+// its own pieces.  It is called only if the function queues anything: each function that takes one says when it does not
+using Pieces = std::function<void(Submission &)>;
 
 class Stream : public Owner<hipStream_t, hipStreamDestroy> {
 public:

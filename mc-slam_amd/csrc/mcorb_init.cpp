@@ -44,14 +44,13 @@ int check_init_cases(MapCases &c, int nlevels, int n, int ncams, const double *R
     return check_cases("init cases", c, nlevels, n, voff);
 }
 
-// the chain of both device entries on st with its wait: `records` (k_init_triangulate, or the cases' k_init_gates), k_init_select
+// the chain of both device entries on st with its wait, behind what the caller has queued on sub: `records` (k_init_triangulate, or the cases' k_init_gates), k_init_select
 // and k_init_put on the records p.rec of n matches, the events of `kernels` around them
 template <class Records>
-int submit(hipStream_t st, Spans<3> &kernels, Records records, const InitPutArgs &p, int n, uint64_t *keys, int32_t *offset, InitSel *sel,
+int submit(Submission &sub, hipStream_t st, Spans<3> &kernels, Records records, const InitPutArgs &p, int n, uint64_t *keys, int32_t *offset, InitSel *sel,
            bool from_cases)
 {
     typedef mcorb_lmap::Init I;
-    Submission sub(st);
     sub.run(kernels, I::kTriangulate, records);
     sub.run(kernels, I::kSelect, [&] { launch_init_select(st, p.rec, p.flags, n, keys, offset, sel); });
     sub.run(kernels, I::kPut, [&] { launch_init_put(st, p, from_cases); });
@@ -179,7 +178,6 @@ int mcorb_lmap_initialize(mcorb_lmap *m, const mcorb_map_frame *prev, int32_t *l
     InitCall call;
     if (dev) {
         hipStream_t st = m->st;
-        TRY(b.in.upload(st, L.m.p.total));
         InitPutArgs p;
         memset(&p, 0, sizeof(p));
         p.job = job;
@@ -197,7 +195,9 @@ int mcorb_lmap_initialize(mcorb_lmap *m, const mcorb_map_frame *prev, int32_t *l
         // (nothing returns between the first launch and the wait, so no kernel of this call still writes the store or the
         // host-mapped records when the caller has its error: Submission)
         const auto triangulate = [&] { launch_init_triangulate(st, p.a, w.nblocks_small, (int)w.blocks.size() - w.nblocks_small); };
-        TRY(submit(st, b.kernels, triangulate, p, n, b.d_keys, b.d_offset, b.d_sel, false));
+        Submission sub(st);
+        b.in.upload(sub, L.m.p.total);
+        TRY(submit(sub, st, b.kernels, triangulate, p, n, b.d_keys, b.d_offset, b.d_sel, false));
         b.kernels.read();
         b.last_launched = (int)w.items.size();
         call = *b.h_call.get();
@@ -319,7 +319,8 @@ int mcorb_dev_init_cases_selftest(int device, int n, const double *X, const int3
     p.nrays = d_nrays;
     Spans<3> kernels;
     TRY(kernels.create());
-    TRY(submit(nullptr, kernels, [&] { launch_init_gates(nullptr, p.cases, n, d_rec); }, p, n, d_keys, d_offset, d_sel, true));
+    Submission sub(nullptr);
+    TRY(submit(sub, nullptr, kernels, [&] { launch_init_gates(nullptr, p.cases, n, d_rec); }, p, n, d_keys, d_offset, d_sel, true));
     cases_out(h_rec.get(), *h_call.get(), n, inliers, verdict, n_rays, lid_offset, vals, res);
     return MCORB_OK;
 }

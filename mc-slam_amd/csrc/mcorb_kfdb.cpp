@@ -81,21 +81,18 @@ static int check_vectors(const mcorb_kfdb *db, const Vectors &v, int ndesc, bool
     return MCORB_OK;
 }
 
-// a frame's BowVector, FeatureVector and descriptor count to its place in the store, on `st` (the descriptors are the caller's)
-static int store_vectors(const Place &p, const Vectors &v, const int &ndesc, hipStream_t st)
+// a frame's BowVector, FeatureVector and descriptor count to its place in the store, pieces of sub (the descriptors are the caller's)
+static void store_vectors(Submission &sub, const Place &p, const Vectors &v, const int &ndesc)
 {
-    if (v.nbow) {
-        HIPCHK(hipMemcpyAsync(p.ids, v.bow_ids, (size_t)v.nbow * 4, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(p.vals, v.bow_vals, (size_t)v.nbow * 8, hipMemcpyHostToDevice, st));
-    }
-    HIPCHK(hipMemcpyAsync(p.nbow, &v.nbow, sizeof(int), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(p.ndesc, &ndesc, sizeof(int), hipMemcpyHostToDevice, st));
+    sub.copy(p.ids, v.bow_ids, (size_t)v.nbow * 4, hipMemcpyHostToDevice);
+    sub.copy(p.vals, v.bow_vals, (size_t)v.nbow * 8, hipMemcpyHostToDevice);
+    sub.copy(p.nbow, &v.nbow, sizeof(int), hipMemcpyHostToDevice);
+    sub.copy(p.ndesc, &ndesc, sizeof(int), hipMemcpyHostToDevice);
     if (v.nfv) {
-        HIPCHK(hipMemcpyAsync(p.nodes, v.fv_nodes, (size_t)v.nfv * 4, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(p.offs, v.fv_offsets, (size_t)(v.nfv + 1) * 4, hipMemcpyHostToDevice, st));
+        sub.copy(p.nodes, v.fv_nodes, (size_t)v.nfv * 4, hipMemcpyHostToDevice);
+        sub.copy(p.offs, v.fv_offsets, (size_t)(v.nfv + 1) * 4, hipMemcpyHostToDevice);
     }
-    if (v.nff) HIPCHK(hipMemcpyAsync(p.feats, v.fv_feats, (size_t)v.nff * 4, hipMemcpyHostToDevice, st));
-    return MCORB_OK;
+    sub.copy(p.feats, v.fv_feats, (size_t)v.nff * 4, hipMemcpyHostToDevice);
 }
 
 static Mirror mirror_of(const Vectors &v, int ndesc)
@@ -147,19 +144,19 @@ static int put_frame(mcorb_kfdb *db, int probe, const Vectors &v, const uint8_t 
         db->n++;
         return MCORB_OK;
     }
-    HIPCHK(hipSetDevice(db->device));
+    TRY(use_device(db->device));
     hipStream_t st = s ? (hipStream_t)s->st : (hipStream_t)db->st;
     const Place p = place_of(db, probe < 0 ? db->n : probe, probe >= 0);
-    TRY(store_vectors(p, v, ndesc, st));
+    if (ndesc && o) TRY(db->d_src.grow((size_t)db->max_feats));
+    Submission sub(st);   // (its wait also covers the pageable vectors and the two counts)
+    store_vectors(sub, p, v, ndesc);
     if (ndesc && o) {
-        TRY(db->d_src.grow((size_t)db->max_feats));
-        HIPCHK(hipMemcpyAsync(db->d_src, o->src.data(), (size_t)ndesc * sizeof(int), hipMemcpyHostToDevice, st));
-        launch_kfdb_gather(st, s->d_desc, db->d_src, ndesc, p.desc);
-        HIPCHK(hipGetLastError());
-    } else if (ndesc) {
-        HIPCHK(hipMemcpyAsync(p.desc, desc, (size_t)ndesc * 32, hipMemcpyHostToDevice, st));
+        sub.copy(db->d_src, o->src.data(), (size_t)ndesc * sizeof(int), hipMemcpyHostToDevice);
+        sub.run([&] { launch_kfdb_gather(st, s->d_desc, db->d_src, ndesc, p.desc); });
+    } else {
+        sub.copy(p.desc, desc, (size_t)ndesc * 32, hipMemcpyHostToDevice);
     }
-    HIPCHK(hipStreamSynchronize(st));
+    TRY(sub.wait());
     if (probe >= 0) {
         db->pmirror[probe] = mirror_of(v, ndesc);
         db->probe_set[probe] = 1;
@@ -243,9 +240,10 @@ static BowArrays scratch_bow(const mcorb_kfdb *db) { return BowArrays{db->d_qids
 
 // k_kfdb_score for nq queries; sel[q]: the vector of `query` that is query q.  With against != nullptr query q is held against
 // the single vector against[q] of `store` instead of the entries below its limit.  raw / shared of (q, x) land at h_raw /
-// h_shared[q * stride_out + x].
+// h_shared[q * stride_out + x].  before: what the caller queues in front (mcorb_kfdb_query's vector), behind the grows;
+// NOT called when no query has an entry below its limit, where nothing is queued.
 static int run_score(mcorb_kfdb *db, const BowArrays &store, const BowArrays &query, const int *sel, const int *limit, const int *against,
-                     int nq, int *stride_out)
+                     int nq, int *stride_out, const Pieces &before = nullptr)
 {
     const int os = std::max(against ? 1 : db->n, 1);
     *stride_out = os;
@@ -265,15 +263,17 @@ static int run_score(mcorb_kfdb *db, const BowArrays &store, const BowArrays &qu
     TRY(db->h_raw.grow(nout, hipHostMallocDefault));
     TRY(db->h_shared.grow(nout, hipHostMallocDefault));
     hipStream_t st = db->st;
-    HIPCHK(hipMemcpyAsync(db->d_ctl, ctl.data(), ctl.size() * sizeof(int), hipMemcpyHostToDevice, st));
-    TRY(db->score.mark(st, 0));
-    launch_kfdb_score(st, store.ids, store.vals, store.n, db->max_words, query.ids, query.vals, query.n, db->d_ctl, db->d_ctl + nq,
-                      against ? db->d_ctl + 2 * (size_t)nq : nullptr, nq, max_limit, os, db->d_raw, db->d_shared);
-    HIPCHK(hipGetLastError());
-    TRY(db->score.mark(st, 1));
-    HIPCHK(hipMemcpyAsync(db->h_raw, db->d_raw, nout * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(db->h_shared, db->d_shared, nout * sizeof(int), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));   // (also covers the pageable control array)
+    Submission sub(st);   // (its wait also covers the pageable control array)
+    if (before) before(sub);
+    sub.copy(db->d_ctl, ctl.data(), ctl.size() * sizeof(int), hipMemcpyHostToDevice);
+    sub.run(db->score, 0, [&] {
+        launch_kfdb_score(st, store.ids, store.vals, store.n, db->max_words, query.ids, query.vals, query.n, db->d_ctl, db->d_ctl + nq,
+                          against ? db->d_ctl + 2 * (size_t)nq : nullptr, nq, max_limit, os, db->d_raw, db->d_shared);
+    });
+    sub.mark(db->score, 1);
+    sub.copy(db->h_raw, db->d_raw, nout * sizeof(double), hipMemcpyDeviceToHost);
+    sub.copy(db->h_shared, db->d_shared, nout * sizeof(int), hipMemcpyDeviceToHost);
+    TRY(sub.wait());
     db->score.read();
     return MCORB_OK;
 }
@@ -342,7 +342,7 @@ void Best2Search::add_b(const std::vector<uint32_t> &a_nodes, const std::vector<
 
 int Best2Search::run(hipStream_t st, const uint8_t *desc_a, const int *feats_a, const uint8_t *desc_b, size_t desc_stride,
                      const int *feats_b, size_t feats_stride, double max_neighbor_ratio, std::vector<std::vector<uint32_t>> &i1,
-                     std::vector<std::vector<uint32_t>> &i2, float *us)
+                     std::vector<std::vector<uint32_t>> &i2, float *us, const Pieces &before)
 {
     const size_t nb = first_rec.size() - 1;
     i1.assign(nb, {}); i2.assign(nb, {});
@@ -352,14 +352,16 @@ int Best2Search::run(hipStream_t st, const uint8_t *desc_a, const int *feats_a, 
     TRY(d_recs.grow(recs.size()));
     TRY(d_mtab.grow(items.size()));
     TRY(h_mtab.grow(items.size(), hipHostMallocDefault));
-    HIPCHK(hipMemcpyAsync(d_items, items.data(), items.size() * sizeof(int2), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_recs, recs.data(), recs.size() * sizeof(int4), hipMemcpyHostToDevice, st));
-    TRY(launch.mark(st, 0));
-    launch_kfdb_best2(st, desc_a, feats_a, desc_b, desc_stride, feats_b, feats_stride, d_items, (int)items.size(), d_recs, d_mtab);
-    HIPCHK(hipGetLastError());
-    TRY(launch.mark(st, 1));
-    HIPCHK(hipMemcpyAsync(h_mtab, d_mtab, items.size() * sizeof(int4), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));   // (also covers the pageable item and record lists)
+    Submission sub(st);   // (its wait also covers the pageable item and record lists)
+    if (before) before(sub);
+    sub.copy(d_items, items.data(), items.size() * sizeof(int2), hipMemcpyHostToDevice);
+    sub.copy(d_recs, recs.data(), recs.size() * sizeof(int4), hipMemcpyHostToDevice);
+    sub.run(launch, 0, [&] {
+        launch_kfdb_best2(st, desc_a, feats_a, desc_b, desc_stride, feats_b, feats_stride, d_items, (int)items.size(), d_recs, d_mtab);
+    });
+    sub.mark(launch, 1);
+    sub.copy(h_mtab, d_mtab, items.size() * sizeof(int4), hipMemcpyDeviceToHost);
+    TRY(sub.wait());
     launch.read();
     *us = launch.us[0];
     std::vector<uint32_t> mA, mB;
@@ -526,13 +528,14 @@ int mcorb_kfdb_query(mcorb_kfdb *db, const uint32_t *bow_ids, const double *bow_
         if (bow_ids[i] <= bow_ids[i - 1]) { set_error("kfdb query: BowVector word ids must ascend"); return MCORB_E_ARG; }
     const int limit = limit_of(max_id, db->n);
     if (nbow && limit) {
-        HIPCHK(hipSetDevice(db->device));
-        HIPCHK(hipMemcpyAsync(db->d_qids, bow_ids, (size_t)nbow * 4, hipMemcpyHostToDevice, db->st));
-        HIPCHK(hipMemcpyAsync(db->d_qvals, bow_vals, (size_t)nbow * 8, hipMemcpyHostToDevice, db->st));
-        HIPCHK(hipMemcpyAsync(db->d_qn, &nbow, sizeof(int), hipMemcpyHostToDevice, db->st));
+        TRY(use_device(db->device));
         const int sel = 0;
         int stride = 1;
-        TRY(run_score(db, entry_bows(db), scratch_bow(db), &sel, &limit, nullptr, 1, &stride));
+        TRY(run_score(db, entry_bows(db), scratch_bow(db), &sel, &limit, nullptr, 1, &stride, [&](Submission &sub) {
+            sub.copy(db->d_qids, bow_ids, (size_t)nbow * 4, hipMemcpyHostToDevice);
+            sub.copy(db->d_qvals, bow_vals, (size_t)nbow * 8, hipMemcpyHostToDevice);
+            sub.copy(db->d_qn, &nbow, sizeof(int), hipMemcpyHostToDevice);
+        }));
         list_of(db, 0, stride, limit, ret);
     }
     return finish_query(ret, max_results, ids, scores, cap, n_out);
@@ -554,7 +557,7 @@ static int query_stored(mcorb_kfdb *db, bool probe, const char *who, const int32
     std::vector<int> limit(nq);
     int status = MCORB_OK, stride = 1;
     if (db->device >= 0) {
-        HIPCHK(hipSetDevice(db->device));
+        TRY(use_device(db->device));
         for (int q = 0; q < nq; q++) limit[q] = limit_of(max_ids[q], db->n);
         TRY(run_score(db, entry_bows(db), probe ? probe_bows(db) : entry_bows(db), sel, limit.data(), nullptr, nq, &stride));
     }
@@ -590,7 +593,7 @@ static int score_stored(mcorb_kfdb *db, int entry, int b, bool probe, const char
         return MCORB_OK;
     }
     // the entry is the query, b's store the one it is held against
-    HIPCHK(hipSetDevice(db->device));
+    TRY(use_device(db->device));
     const int one = 1;
     int stride = 1;
     TRY(run_score(db, probe ? probe_bows(db) : entry_bows(db), entry_bows(db), &entry, &one, &b, 1, &stride));
@@ -616,7 +619,7 @@ int mcorb_kfdb_feature_matches(mcorb_kfdb *db, int best_entry, int curr_entry, d
     if (db->device < 0) {
         matches_host(db->entries[best_entry], db->entries[curr_entry], max_neighbor_ratio, i1[0], i2[0]);
     } else {
-        HIPCHK(hipSetDevice(db->device));
+        TRY(use_device(db->device));
         const Mirror &A = db->mirror[best_entry];
         const Place pa = place_of(db, best_entry, false), pb = place_of(db, curr_entry, false);
         db->best2.reset();
@@ -738,7 +741,7 @@ int mcorb_kfdb_probe_feature_matches(mcorb_kfdb *db, int entry, const int32_t *p
         for (int p = 0; p < np; p++) matches_host(db->entries[entry], db->probes[probes[p]], max_neighbor_ratio, i1[p], i2[p]);
     } else {
         // the probe store as the B sets, probe by probe: the order the kernel's lanes share B rows in
-        HIPCHK(hipSetDevice(db->device));
+        TRY(use_device(db->device));
         const Mirror &A = db->mirror[entry];
         const Place pa = place_of(db, entry, false), p0 = place_of(db, 0, true);
         db->best2.reset();
@@ -780,7 +783,7 @@ static int knn2_frames(mcorb_kfdb *db, int entry, int probe, int na, int nb, std
     }
     const int kc = db->fstride;
     if (kc > 65535) { set_error("kfdb probe_inter_matches_bf: max_feats above 65535 (the k-NN table's 16-bit train index)"); return MCORB_E_SIZE; }
-    HIPCHK(hipSetDevice(db->device));
+    TRY(use_device(db->device));
     if (!db->h_rows.size()) {
         TRY(db->d_exp.alloc((size_t)2 * kc * kKnnExpandBytes));
         TRY(db->d_lcounts.alloc(2));
@@ -794,10 +797,12 @@ static int knn2_frames(mcorb_kfdb *db, int entry, int probe, int na, int nb, std
     db->h_knnctl[1] = db->max_entries + probe;
     db->h_knnctl[2] = 0;                            // the pair (query, train)
     db->h_knnctl[3] = 1;
-    launch_knn2(db->st, db->d_desc, db->d_ndesc, db->h_knnctl, 2, reinterpret_cast<const int2 *>(db->h_knnctl + 2), 1, kc, db->d_exp, db->d_lcounts,
-                db->d_part, 75.f, 0.85f, db->h_rows, db->h_mlist, db->h_mcount, nullptr, nullptr);   // (the accept flag is not read)
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(db->st));
+    Submission sub(db->st);
+    sub.run([&] {
+        launch_knn2(db->st, db->d_desc, db->d_ndesc, db->h_knnctl, 2, reinterpret_cast<const int2 *>(db->h_knnctl + 2), 1, kc, db->d_exp,
+                    db->d_lcounts, db->d_part, 75.f, 0.85f, db->h_rows, db->h_mlist, db->h_mcount, nullptr, nullptr);   // (the accept flag is not read)
+    });
+    TRY(sub.wait());
     for (int q = 0; q < na; q++) {
         const KnnRow &k = db->h_rows[q];
         rows[q] = int4{knn_idx0(k), knn_d0(k), knn_idx1(k), knn_d1(k)};

@@ -52,9 +52,11 @@ struct Best2Search {
     // One upload, one k_kfdb_best2 launch on st (none without items), one copy back, one synchronisation; then the acceptance
     // record by record.  desc_a / feats_a: A's rows and feature list; desc_b / feats_b: set 0 of the B store, its sets desc_stride
     // bytes and feats_stride ints apart.  i1[b] / i2[b]: the matches of the b-th B; *us: the launch between the events, if any.
+    // before: what the caller queues in front of the upload (mcorb_lmap_search's feature list), behind the grows; NOT called
+    // without items, where nothing is queued.
     int run(hipStream_t st, const uint8_t *desc_a, const int *feats_a, const uint8_t *desc_b, size_t desc_stride, const int *feats_b,
             size_t feats_stride, double max_neighbor_ratio, std::vector<std::vector<uint32_t>> &i1,
-            std::vector<std::vector<uint32_t>> &i2, float *us);
+            std::vector<std::vector<uint32_t>> &i2, float *us, const Pieces &before = nullptr);
 };
 
 }  // namespace mcorb

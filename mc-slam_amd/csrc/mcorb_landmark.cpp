@@ -80,7 +80,7 @@ int mcorb_lmap_set_rays(mcorb_lmap *m, const int32_t *lids, int n, const int32_t
     if (m->device >= 0) {
         std::vector<int> keep;
         keep_last(m, lids, n, keep);
-        HIPCHK(hipSetDevice(m->device));
+        TRY(use_device(m->device));
         hipStream_t st = m->st;
         TRY(m->life.h_rays.grow(2 * (size_t)n, hipHostMallocDefault));
         TRY(m->life.d_rays.grow(2 * (size_t)n));
@@ -90,10 +90,10 @@ int mcorb_lmap_set_rays(mcorb_lmap *m, const int32_t *lids, int n, const int32_t
         int at = 0;
         for (int i = 0; i < n; i++)
             if (keep[i] >= 0) { m->life.h_rays[at] = lids[i]; m->life.h_rays[k + at] = n_rays[i]; at++; }
-        HIPCHK(hipMemcpyAsync(m->life.d_rays, m->life.h_rays, 2 * (size_t)k * sizeof(int32_t), hipMemcpyHostToDevice, st));
-        launch_lmap_put_rays(st, m->life.d_rays, m->life.d_rays + k, k, m->d_nrays);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipStreamSynchronize(st));
+        Submission sub(st);
+        sub.copy(m->life.d_rays, m->life.h_rays, 2 * (size_t)k * sizeof(int32_t), hipMemcpyHostToDevice);
+        sub.run([&] { launch_lmap_put_rays(st, m->life.d_rays, m->life.d_rays + k, k, m->d_nrays); });
+        TRY(sub.wait());
     }
     for (int i = 0; i < n; i++) m->n_rays[lids[i]] = n_rays[i];
     return MCORB_OK;
@@ -176,31 +176,33 @@ int mcorb_lmap_observe(mcorb_lmap *m, const mcorb_obs_frame *frame, const int32_
             for (int i = 0; i < n; i++) memcpy(&m->desc[(size_t)lids[i] * 32], src + (size_t)feats[i] * 32, 32);
         }
     } else {
-        HIPCHK(hipSetDevice(m->device));
+        TRY(use_device(m->device));
         hipStream_t st = m->st;
+        std::vector<int> keep;
         if (update) {
             TRY(m->life.h_obsitems.grow((size_t)n, hipHostMallocDefault));
             TRY(m->life.d_obsitems.grow((size_t)n));
             for (int k = 0; k < n; k++) m->life.h_obsitems[k] = LmObsItem{lids[order[k]], mask[order[k]]};
-            HIPCHK(hipMemcpyAsync(m->life.d_obsitems, m->life.h_obsitems, (size_t)n * sizeof(LmObsItem), hipMemcpyHostToDevice, st));
-            TRY(m->life.observe.mark(st, 0));
-            for (size_t r = 0; r + 1 < first.size(); r++) {
-                launch_lmap_observe(st, cen, C, m->life.d_obsitems + first[r], first[r + 1] - first[r], m->d_geom, m->d_nrays);
-                HIPCHK(hipGetLastError());
-            }
-            TRY(m->life.observe.mark(st, 1));
         }
         if (entry >= 0) {
-            std::vector<int> keep;
+            TRY(m->batch.reserve((size_t)n, false, false, false, true));
             keep_last(m, lids, n, keep);
-            TRY(m->batch.upload(m->batch.d_lids, keep.data(), (size_t)n, st));
-            TRY(m->batch.upload(m->batch.d_rows, feats, (size_t)n, st));
-            launch_lmap_put(st, m->batch.d_lids, n, nullptr, nullptr, place_of(db, entry, false).desc, m->batch.d_rows, m->d_geom, m->d_desc);
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipStreamSynchronize(st));   // (also covers the pageable lists)
-        } else if (update) {
-            HIPCHK(hipStreamSynchronize(st));
         }
+        Submission sub(st);   // (no piece, no wait: update off and no entry; its wait also covers the pageable lists)
+        if (update) {
+            sub.copy(m->life.d_obsitems, m->life.h_obsitems, (size_t)n * sizeof(LmObsItem), hipMemcpyHostToDevice);
+            sub.mark(m->life.observe, 0);
+            for (size_t r = 0; r + 1 < first.size(); r++)
+                sub.run([&] { launch_lmap_observe(st, cen, C, m->life.d_obsitems + first[r], first[r + 1] - first[r], m->d_geom, m->d_nrays); });
+            sub.mark(m->life.observe, 1);
+        }
+        if (entry >= 0) {
+            m->batch.upload(sub, m->batch.d_lids, keep.data(), (size_t)n);
+            m->batch.upload(sub, m->batch.d_rows, feats, (size_t)n);
+            const uint8_t *rows = place_of(db, entry, false).desc;
+            sub.run([&] { launch_lmap_put(st, m->batch.d_lids, n, nullptr, nullptr, rows, m->batch.d_rows, m->d_geom, m->d_desc); });
+        }
+        TRY(sub.wait());
         if (update) {
             m->life.observe.read();
             // the host's copy of the ray counts: the integer part of lm_observe, in batch order
@@ -245,7 +247,7 @@ int mcorb_lmap_update_points(mcorb_lmap *m, const int32_t *lids, int n, const do
     }
     std::vector<int> order, first, nth;
     cut_rounds(m, lids, n, order, first, nth);
-    HIPCHK(hipSetDevice(m->device));
+    TRY(use_device(m->device));
     hipStream_t st = m->st;
     TRY(m->life.h_upditems.grow((size_t)n, hipHostMallocDefault));
     TRY(m->life.d_upditems.grow((size_t)n));
@@ -258,15 +260,14 @@ int mcorb_lmap_update_points(mcorb_lmap *m, const int32_t *lids, int n, const do
         it.idx = i;
         memcpy(it.p, pt_new + 3 * (size_t)i, 3 * sizeof(double));
     }
-    HIPCHK(hipMemcpyAsync(m->life.d_upditems, m->life.h_upditems, (size_t)n * sizeof(LmUpdItem), hipMemcpyHostToDevice, st));
-    TRY(m->life.update.mark(st, 0));
-    for (size_t r = 0; r + 1 < first.size(); r++) {
-        launch_lmap_update(st, m->life.d_upditems + first[r], first[r + 1] - first[r], max_diff, m->d_geom, m->life.d_updout);
-        HIPCHK(hipGetLastError());
-    }
-    TRY(m->life.update.mark(st, 1));
-    HIPCHK(hipMemcpyAsync(m->life.h_updout, m->life.d_updout, (size_t)n * sizeof(LmUpdOut), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    Submission sub(st);
+    sub.copy(m->life.d_upditems, m->life.h_upditems, (size_t)n * sizeof(LmUpdItem), hipMemcpyHostToDevice);
+    sub.mark(m->life.update, 0);
+    for (size_t r = 0; r + 1 < first.size(); r++)
+        sub.run([&] { launch_lmap_update(st, m->life.d_upditems + first[r], first[r + 1] - first[r], max_diff, m->d_geom, m->life.d_updout); });
+    sub.mark(m->life.update, 1);
+    sub.copy(m->life.h_updout, m->life.d_updout, (size_t)n * sizeof(LmUpdOut), hipMemcpyDeviceToHost);
+    TRY(sub.wait());
     m->life.update.read();
     for (int i = 0; i < n; i++) {
         if (updated) updated[i] = m->life.h_updout[i].updated ? 1 : 0;
@@ -297,13 +298,13 @@ int mcorb_lmap_delete(mcorb_lmap *m, const int32_t *lids, int n, int32_t *kfs, i
     if (total > (size_t)cap) return fail(MCORB_E_CAP, who, "output too small");
     if (n == 0) return MCORB_OK;
     if (m->device >= 0) {
-        HIPCHK(hipSetDevice(m->device));
+        TRY(use_device(m->device));
         hipStream_t st = m->st;
         TRY(m->life.d_rays.grow((size_t)n));
-        HIPCHK(hipMemcpyAsync(m->life.d_rays, lids, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, st));
-        launch_lmap_put_rays(st, m->life.d_rays, nullptr, n, m->d_nrays);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipStreamSynchronize(st));   // (also covers the pageable list)
+        Submission sub(st);   // (its wait also covers the pageable list)
+        sub.copy(m->life.d_rays, lids, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice);
+        sub.run([&] { launch_lmap_put_rays(st, m->life.d_rays, nullptr, n, m->d_nrays); });
+        TRY(sub.wait());
     }
     size_t at = 0;
     for (int i = 0; i < n; i++) {

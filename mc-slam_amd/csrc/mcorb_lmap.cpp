@@ -47,22 +47,21 @@ static int put_device(mcorb_lmap *m, const std::vector<int> &keep, const double 
                       const uint8_t *src_desc, const int32_t *rows)
 {
     const size_t n = keep.size();
-    HIPCHK(hipSetDevice(m->device));
+    TRY(use_device(m->device));
     hipStream_t st = m->st;
     mcorb_lmap::Batch &b = m->batch;
-    TRY(b.upload(b.d_lids, keep.data(), n, st));
-    if (pt3d) TRY(b.upload(b.d_pt, pt3d, n * 3, st));
-    if (normal) TRY(b.upload(b.d_normal, normal, n * 3, st));
-    if (desc) {
-        TRY(b.upload(b.d_desc, desc, n * 32, st));
-        src_desc = b.d_desc;
-    }
-    if (rows) TRY(b.upload(b.d_rows, rows, n, st));
-    launch_lmap_put(st, b.d_lids, (int)n, pt3d ? b.d_pt.get() : nullptr, normal ? b.d_normal.get() : nullptr, src_desc,
-                    rows ? b.d_rows.get() : nullptr, m->d_geom, m->d_desc);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(st));   // (also covers the pageable host arrays)
-    return MCORB_OK;
+    TRY(b.reserve(n, pt3d, normal, desc, rows));
+    Submission sub(st);   // (its wait also covers the pageable host arrays; an absent array is a copy of 0 bytes)
+    b.upload(sub, b.d_lids, keep.data(), n);
+    b.upload(sub, b.d_pt, pt3d, pt3d ? n * 3 : 0);
+    b.upload(sub, b.d_normal, normal, normal ? n * 3 : 0);
+    b.upload(sub, b.d_desc, desc, desc ? n * 32 : 0);
+    b.upload(sub, b.d_rows, rows, rows ? n : 0);
+    sub.run([&] {
+        launch_lmap_put(st, b.d_lids, (int)n, pt3d ? b.d_pt.get() : nullptr, normal ? b.d_normal.get() : nullptr, desc ? b.d_desc.get() : src_desc,
+                        rows ? b.d_rows.get() : nullptr, m->d_geom, m->d_desc);
+    });
+    return sub.wait();
 }
 
 // the frustum test of one landmark on the host (:5000-5027), with 3x3 * 3x1 products as cv::Mat's gemm evaluates them
@@ -305,15 +304,14 @@ int mcorb_lmap_search(mcorb_lmap *m, const mcorb_lmap_view *view, const int32_t 
             if (cmids) { acc.push_back(l); masks.push_back(cmids); }
         }
     } else if (nc) {
-        HIPCHK(hipSetDevice(m->device));
-        HIPCHK(hipMemcpyAsync(m->search.d_view, view, sizeof(mcorb_lmap_view), hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(m->search.d_cand, cand.data(), (size_t)nc * sizeof(int), hipMemcpyHostToDevice, st));
-        TRY(m->search.cull.mark(st, 0));
-        launch_lmap_cull(st, m->search.d_view, m->d_geom, m->search.d_cand, nc, m->search.d_masks);
-        HIPCHK(hipGetLastError());
-        TRY(m->search.cull.mark(st, 1));
-        HIPCHK(hipMemcpyAsync(m->search.h_masks, m->search.d_masks, (size_t)nc * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));   // (also covers the pageable view and candidate list)
+        TRY(use_device(m->device));
+        Submission sub(st);   // (its wait also covers the pageable view and candidate list)
+        sub.copy(m->search.d_view, view, sizeof(mcorb_lmap_view), hipMemcpyHostToDevice);
+        sub.copy(m->search.d_cand, cand.data(), (size_t)nc * sizeof(int), hipMemcpyHostToDevice);
+        sub.run(m->search.cull, 0, [&] { launch_lmap_cull(st, m->search.d_view, m->d_geom, m->search.d_cand, nc, m->search.d_masks); });
+        sub.mark(m->search.cull, 1);
+        sub.copy(m->search.h_masks, m->search.d_masks, (size_t)nc * sizeof(uint32_t), hipMemcpyDeviceToHost);
+        TRY(sub.wait());
         m->search.cull.read();
         for (int i = 0; i < nc; i++)
             if (m->search.h_masks[i]) { acc.push_back(cand[i]); masks.push_back(m->search.h_masks[i]); }
@@ -333,18 +331,19 @@ int mcorb_lmap_search(mcorb_lmap *m, const mcorb_lmap_view *view, const int32_t 
         A.nodes = fv.fv_nodes; A.offs = fv.fv_offsets; A.feats = fv.fv_feats;
         matches_host(A, db->probes[probe], max_neighbor_ratio, i1, i2);
     } else if (na) {
-        HIPCHK(hipMemcpyAsync(m->search.d_cand, acc.data(), (size_t)na * sizeof(int), hipMemcpyHostToDevice, st));
-        launch_kfdb_gather(st, m->d_desc, m->search.d_cand, na, m->search.d_adesc);
-        HIPCHK(hipGetLastError());
-        TRY(vocab_feature_vector(m->voc, m->search.d_adesc, na, levelsup, st, fv));
+        TRY(vocab_feature_vector(m->voc, m->search.d_adesc, na, levelsup, st, fv, [&](Submission &sub) {
+            sub.copy(m->search.d_cand, acc.data(), (size_t)na * sizeof(int), hipMemcpyHostToDevice);
+            sub.run([&] { launch_kfdb_gather(st, m->d_desc, m->search.d_cand, na, m->search.d_adesc); });
+        }));
         // A: the gathered rows and their FeatureVector; B: the probe, with its own base as set 0
         const Place pb = place_of(db, probe, true);
         std::vector<std::vector<uint32_t>> r1, r2;
         m->search.best2.reset();
         m->search.best2.add_b(fv.fv_nodes, fv.fv_offsets, db->pmirror[probe], 0);
-        if (!m->search.best2.items.empty())   // (the run's synchronisation covers the pageable list)
-            HIPCHK(hipMemcpyAsync(m->search.d_afeats, fv.fv_feats.data(), fv.fv_feats.size() * sizeof(int), hipMemcpyHostToDevice, st));
-        TRY(m->search.best2.run(st, m->search.d_adesc, m->search.d_afeats, pb.desc, 0, pb.feats, 0, max_neighbor_ratio, r1, r2, &m->search.us_best2));
+        const Pieces afeats = [&](Submission &sub) {   // (none without items; the run's wait covers the pageable list)
+            sub.copy(m->search.d_afeats, fv.fv_feats.data(), fv.fv_feats.size() * sizeof(int), hipMemcpyHostToDevice);
+        };
+        TRY(m->search.best2.run(st, m->search.d_adesc, m->search.d_afeats, pb.desc, 0, pb.feats, 0, max_neighbor_ratio, r1, r2, &m->search.us_best2, afeats));
         i1.swap(r1[0]); i2.swap(r2[0]);
     }
 

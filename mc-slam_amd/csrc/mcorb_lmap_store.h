@@ -30,7 +30,7 @@ struct Staged {
     HostBuf<uint8_t> h;
     DevBuf<uint8_t> d;
     int reserve(size_t bytes) { TRY(h.grow(bytes, hipHostMallocDefault)); return d.grow(bytes); }
-    int upload(hipStream_t st, size_t bytes) { HIPCHK(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, st)); return MCORB_OK; }
+    void upload(Submission &sub, size_t bytes) const { sub.copy(d, h, bytes, hipMemcpyHostToDevice); }
     template <class T> T *host(size_t off) const { return reinterpret_cast<T *>(h.get() + off); }
     template <class T> T *dev(size_t off) const { return reinterpret_cast<T *>(d.get() + off); }
 };
@@ -47,6 +47,16 @@ struct PoseBufs {
     HostBuf<uint8_t> h_flags;
     // the explicit entries: a problem of n observations whose input is elsewhere
     int reserve(size_t n) { TRY(d_alive.grow(n)); TRY(h_out.grow(1, kHostMapped)); return h_flags.grow(n, kHostMapped); }
+    // the refinement behind a tracking submission of nf frames and `rows` = ncams * candidates pairs, whose jobs are the input
+    int reserve_track(size_t nf, size_t rows)
+    {
+        TRY(in.reserve(nf * sizeof(PoseJob)));
+        TRY(d_obs.grow(rows));
+        TRY(d_lids.grow(rows));
+        TRY(d_alive.grow(rows));
+        TRY(h_out.grow(nf, kHostMapped));
+        return h_flags.grow(rows, kHostMapped);
+    }
 };
 
 // what the pose estimators' entries share (mcorb_sac.cpp, _rel, _align, _ess).  positive: a threshold, distance or focal length
@@ -112,13 +122,20 @@ struct mcorb_lmap {
         mcorb::DevBuf<int> d_lids, d_rows;
         mcorb::DevBuf<double> d_pt, d_normal;
         mcorb::DevBuf<uint8_t> d_desc;
-        // src[0 .. n) into d on st (pageable memory: the caller's synchronisation covers it)
-        template <class T>
-        static int upload(mcorb::DevBuf<T> &d, const T *src, size_t n, hipStream_t st)
+        // room for n slots, before the chain: the ids, and the arrays a call sends with them
+        int reserve(size_t n, bool pt, bool normal, bool desc, bool rows)
         {
-            TRY(d.grow(n));
-            HIPCHK(hipMemcpyAsync(d, src, n * sizeof(T), hipMemcpyHostToDevice, st));
-            return MCORB_OK;
+            TRY(d_lids.grow(n));
+            if (pt) TRY(d_pt.grow(n * 3));
+            if (normal) TRY(d_normal.grow(n * 3));
+            if (desc) TRY(d_desc.grow(n * 32));
+            return rows ? d_rows.grow(n) : MCORB_OK;
+        }
+        // src[0 .. n) into d (pageable memory: the submission's wait covers it)
+        template <class T>
+        static void upload(mcorb::Submission &sub, const mcorb::DevBuf<T> &d, const T *src, size_t n)
+        {
+            sub.copy(d, src, n * sizeof(T), hipMemcpyHostToDevice);
         }
     } batch;
 
@@ -437,13 +454,14 @@ struct mcorb_lmap {
 // the pose refinement behind a tracking call (mcorb_pose.cpp); the caller holds the store's lock and has set track_refine_params.
 // pose_track_host: a host-only store, or a frame nothing was launched for -- the observations are the frame's matches, the
 // cameras back to back in match order (kp_base / kp_stride: the frame's keypoint records, which begin with pt), flags: ncams *
-// nc bytes.  pose_track_submit: k_pose_refine for the nf frames of a device submission, behind its de-duplication on the
+// nc bytes.  pose_track_submit: k_pose_refine for the nf frames of a device submission, a piece of it behind its de-duplication on the
 // store's stream; items: the submission's TrItems on the host, which say where a frame's candidates, rows and keypoints in
 // kp_xy are
 namespace mcorb {
 void pose_track_host(mcorb_lmap *m, const mcorb_track_view &view, const int *cand, int nc, const TrMatch *matches, const int32_t *n_match,
                      const uint8_t *const *kp_base, size_t kp_stride, mcorb_pose_result &res, uint8_t *flags);
-int pose_track_submit(mcorb_lmap *m, const mcorb_track_view *views, const TrItem *items, int nf, const float2 *kp_xy, const int *d_cand);
+void pose_track_submit(Submission &sub, mcorb_lmap *m, const mcorb_track_view *views, const TrItem *items, int nf, const float2 *kp_xy,
+                       const int *d_cand);
 // shared with mcorb_sac.cpp: a refinement problem's job, its serial run, and the checks of its parameters
 void pose_job_init(PoseJob &job, const mcorb_pose_params &p, int ncams, const mcorb_track_cam *cams, const PoseState &init);
 void pose_run_host(const PoseJob &job, const PoseObs *obs, const double *pts, int n, uint8_t *alive, mcorb_pose_result &res);

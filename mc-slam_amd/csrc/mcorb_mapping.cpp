@@ -66,7 +66,7 @@ int put_landmarks(mcorb_lmap *m, bool on_device, int32_t next_lid, int ntri, con
         TRY(b.d_put.grow((size_t)ntri));
         for (int k = 0; k < ntri; k++) b.h_put[k] = make_int2(item_of[k], next_lid + k);
         Submission sub(st);
-        sub.run([&] { (void)hipMemcpyAsync(b.d_put, b.h_put, (size_t)ntri * sizeof(int2), hipMemcpyHostToDevice, st); });
+        sub.copy(b.d_put, b.h_put, (size_t)ntri * sizeof(int2), hipMemcpyHostToDevice);
         sub.run([&] { launch_map_put(st, b.d_out, b.d_put, ntri, m->d_geom, m->d_nrays); });
         TRY(sub.wait());
     } else {
@@ -211,13 +211,13 @@ int mcorb_lmap_triangulate_neighbours(mcorb_lmap *m, const mcorb_map_frame *cur,
         // (nothing returns between the first launch and the wait, so no kernel of this call still reads the pinned input when
         // the caller has its error: Submission.  The upload is the chain's first piece: nothing is queued when it fails)
         Submission sub(st);
-        TRY(b.in.upload(st, L.p.total));
+        b.in.upload(sub, L.p.total);
         sub.run(b.neigh, b.kDepth, [&] { launch_map_depth(st, Rcw, tcw, m->d_geom, b.in.dev<const int>(L.zlids), (int)nz, b.d_z); });
         sub.run(b.neigh, b.kTriangulate,
                 [&] { launch_map_triangulate(st, L.args(b.in.d, b.d_out, C), w.nblocks_small, (int)w.blocks.size() - w.nblocks_small); });
         sub.mark(b.neigh, b.kTriangulate + 1);
-        if (nz) sub.run([&] { (void)hipMemcpyAsync(b.h_z, b.d_z, nz * sizeof(double), hipMemcpyDeviceToHost, st); });
-        if (nitems) sub.run([&] { (void)hipMemcpyAsync(b.h_out, b.d_out, (size_t)nitems * sizeof(MapOut), hipMemcpyDeviceToHost, st); });
+        sub.copy(b.h_z, b.d_z, nz * sizeof(double), hipMemcpyDeviceToHost);
+        sub.copy(b.h_out, b.d_out, (size_t)nitems * sizeof(MapOut), hipMemcpyDeviceToHost);
         TRY(sub.wait());
         b.neigh.read();
         z = b.h_z;
@@ -329,10 +329,11 @@ int mcorb_lmap_depths(mcorb_lmap *m, const double Rcw[9], const double tcw[3], c
     (void)hipGetLastError();   // (a stale error of this thread is not this call's)
     hipStream_t st = m->st;
     TRY(m->map.d_z.grow((size_t)n));
+    TRY(m->batch.reserve((size_t)n, false, false, false, false));
     Submission sub(st);   // (its wait also covers the pageable arrays)
-    TRY(m->batch.upload(m->batch.d_lids, lids, (size_t)n, st));
+    m->batch.upload(sub, m->batch.d_lids, lids, (size_t)n);
     sub.run([&] { launch_map_depth(st, Rcw, tcw, m->d_geom, m->batch.d_lids, n, m->map.d_z); });
-    sub.run([&] { (void)hipMemcpyAsync(z, m->map.d_z, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st); });
+    sub.copy(z, m->map.d_z, (size_t)n * sizeof(double), hipMemcpyDeviceToHost);
     return sub.wait();
 }
 
@@ -452,11 +453,11 @@ int mcorb_lmap_triangulate_new(mcorb_lmap *m, const mcorb_map_frame *cur, int32_
         na.a = L.args(b.in.d, b.d_out, C);
         na.extra = b.d_extra;
         Submission sub(st);   // (as in mcorb_lmap_triangulate_neighbours)
-        TRY(b.in.upload(st, L.p.total));
+        b.in.upload(sub, L.p.total);
         sub.run(b.refine_new, 0, [&] { launch_map_refine_new(st, na, w.nblocks_small, (int)w.blocks.size() - w.nblocks_small); });
         sub.mark(b.refine_new, 1);
-        sub.run([&] { (void)hipMemcpyAsync(b.h_out, b.d_out, (size_t)nitems * sizeof(MapOut), hipMemcpyDeviceToHost, st); });
-        sub.run([&] { (void)hipMemcpyAsync(b.h_extra, b.d_extra, (size_t)nitems * sizeof(MapNewExtra), hipMemcpyDeviceToHost, st); });
+        sub.copy(b.h_out, b.d_out, (size_t)nitems * sizeof(MapOut), hipMemcpyDeviceToHost);
+        sub.copy(b.h_extra, b.d_extra, (size_t)nitems * sizeof(MapNewExtra), hipMemcpyDeviceToHost);
         TRY(sub.wait());
         b.refine_new.read();
         b.last_new_launched = nitems;

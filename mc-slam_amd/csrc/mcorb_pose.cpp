@@ -177,20 +177,14 @@ void pose_track_host(mcorb_lmap *m, const mcorb_track_view &view, const int *can
     pose_run_host(job, obs.data(), pts.data(), (int)obs.size(), flags, res);
 }
 
-// a device store: k_pose_refine for the nf frames of the submission, behind its de-duplication on the store's stream.  items:
+// a device store: k_pose_refine for the nf frames of the submission sub, behind its de-duplication on the store's stream; the
+// buffers are reserved (PoseBufs::reserve_track).  items:
 // the submission's, on the host -- a frame's candidates, block of the per-pair arrays and keypoints in kp_xy are where they say
-int pose_track_submit(mcorb_lmap *m, const mcorb_track_view *views, const TrItem *items, int nf, const float2 *kp_xy, const int *d_cand)
+void pose_track_submit(Submission &sub, mcorb_lmap *m, const mcorb_track_view *views, const TrItem *items, int nf, const float2 *kp_xy,
+                       const int *d_cand)
 {
-    PoseBufs &b = m->pose.t;
+    const PoseBufs &b = m->pose.t;
     const int C = views[0].ncams;
-    const size_t rows = (size_t)C * (items[nf - 1].cand_first + (size_t)items[nf - 1].n);
-    const size_t bytes = (size_t)nf * sizeof(PoseJob);
-    TRY(b.in.reserve(bytes));
-    TRY(b.d_obs.grow(rows));
-    TRY(b.d_lids.grow(rows));
-    TRY(b.d_alive.grow(rows));
-    TRY(b.h_out.grow((size_t)nf, kHostMapped));
-    TRY(b.h_flags.grow(rows, kHostMapped));
     PoseJob *jobs = b.in.host<PoseJob>(0);
     for (int f = 0; f < nf; f++) {
         PoseJob &job = jobs[f];
@@ -204,11 +198,11 @@ int pose_track_submit(mcorb_lmap *m, const mcorb_track_view *views, const TrItem
         job.kp0 = it.kp0;
         job.frame = it.frame;
     }
-    TRY(b.in.upload(m->st, bytes));
-    launch_pose_refine(m->st, b.in.dev<const PoseJob>(0), nf, b.d_obs, b.d_lids, nullptr, m->d_geom, b.d_alive,
-                       m->track.d_win, m->track.d_best, d_cand, kp_xy, b.h_out, b.h_flags);
-    HIPCHK(hipGetLastError());
-    return MCORB_OK;
+    b.in.upload(sub, (size_t)nf * sizeof(PoseJob));
+    sub.run([&] {
+        launch_pose_refine(m->st, b.in.dev<const PoseJob>(0), nf, b.d_obs, b.d_lids, nullptr, m->d_geom, b.d_alive, m->track.d_win,
+                           m->track.d_best, d_cand, kp_xy, b.h_out, b.h_flags);
+    });
 }
 
 }  // namespace mcorb
@@ -251,8 +245,8 @@ int mcorb_lmap_refine_pose(mcorb_lmap *m, int n, const int32_t *cam, const float
     *b.in.host<PoseJob>(L.pose_job) = job;
     obs_stage(in, L, b.in);
     hipStream_t st = m->st;
-    TRY(b.in.upload(st, L.p.total));
     Submission sub(st);
+    b.in.upload(sub, L.p.total);
     sub.run(m->pose.refine, 0, [&] { obs_enqueue_refine(m, in, L, b.in, b); });
     sub.mark(m->pose.refine, 1);
     TRY(sub.wait());

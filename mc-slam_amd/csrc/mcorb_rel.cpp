@@ -117,8 +117,6 @@ int relative_pose(mcorb_lmap *m, const char *who, int n, const int32_t *cam1, co
         *b.in.host<RelJob>(L.job) = job;
         fill_obs(b.in.host<RelObs>(L.obs), n, cam1, uv1, cam2, uv2);
         hipStream_t st = m->st;
-        TRY(b.in.upload(st, L.p.total));
-        HIPCHK(hipMemsetAsync(b.d_count, 0, (size_t)H * sizeof(int32_t), st));
         RelArgs a;
         a.job = b.in.dev<const RelJob>(L.job);
         a.obs = b.in.dev<const RelObs>(L.obs);
@@ -128,6 +126,8 @@ int relative_pose(mcorb_lmap *m, const char *who, int n, const int32_t *cam1, co
         a.out = pp ? b.d_pick.get() : b.h_out.get();
         a.flags = pp ? b.d_member.get() : b.h_flags.get();
         Submission sub(st);
+        b.in.upload(sub, L.p.total);
+        sub.fill(b.d_count, 0, (size_t)H * sizeof(int32_t));
         sub.run(b.kernels, 0, [&] { launch_rel_hypotheses(st, a, H); });
         sub.run(b.kernels, 1, [&] { launch_rel_score(st, a, S, H); });
         sub.run(b.kernels, 2, [&] { launch_rel_pick(st, a, S); });

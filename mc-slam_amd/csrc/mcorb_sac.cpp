@@ -140,8 +140,6 @@ int mcorb_lmap_ransac_pose(mcorb_lmap *m, int n, const int32_t *cam, const float
         memcpy(b.in.host<int32_t>(L.cam_cons), lists.cam_cons.data(), (size_t)S * sizeof(int32_t));
         memcpy(b.in.host<uint8_t>(L.is_first), lists.is_first.data(), (size_t)n);
         hipStream_t st = m->st;
-        TRY(b.in.upload(st, L.p.total));
-        HIPCHK(hipMemsetAsync(b.d_count, 0, (size_t)H * sizeof(int32_t), st));
         SacArgs a;
         a.job = b.in.dev<const SacJob>(L.sac_job);
         a.obs = b.in.dev<const PoseObs>(L.obs);
@@ -158,6 +156,8 @@ int mcorb_lmap_ransac_pose(mcorb_lmap *m, int n, const int32_t *cam, const float
         a.flags = b.h_flags;
         a.pose_job = refine_params ? b.in.dev<PoseJob>(L.pose_job) : nullptr;
         Submission sub(st);
+        b.in.upload(sub, L.p.total);
+        sub.fill(b.d_count, 0, (size_t)H * sizeof(int32_t));
         sub.run(b.kernels, 0, [&] {
             if (job.solver == MCORB_SAC_SOLVER_RIG)
                 launch_sac_hypotheses_rig(st, a, H);

@@ -231,10 +231,9 @@ int submit_on_device(mcorb_lmap *m, const mcorb_track_view *views, const Frame *
     const size_t total = tc.first[nf], rows = (size_t)C * total;
     Slot *slot = fr[0].slot;   // (a call's frames are all a rig slot's or all host arrays)
     const int kcap = slot ? fr[0].rig->geom.kcap : 0;
-    HIPCHK(hipSetDevice(m->device));
-    // A stale error of this thread is not this call's (Rig::execute does the same): whatever an earlier, unrelated HIP call left
-    // behind -- another object's destructor, an elapsed-time query -- would otherwise be reported by the checks behind the launches
-    (void)hipGetLastError();
+    // (a stale error of this thread is not this call's, as in Rig::execute: whatever an earlier, unrelated HIP call left behind --
+    // another object's destructor, an elapsed-time query -- would otherwise be reported by the checks behind the launches)
+    TRY(use_device(m->device));
     hipStream_t st = m->st;
     size_t slots = 0, total_kp = 0;   // (total_kp: of host arrays, which go up)
     int max_n = 0;
@@ -247,6 +246,7 @@ int submit_on_device(mcorb_lmap *m, const mcorb_track_view *views, const Frame *
     const TrackLayout L((size_t)nf, total, total_kp);
     TK &t = m->track;
     TRY(t.reserve(L.p.total, rows, (size_t)nf, slots, slot ? (size_t)nf * C * kcap : 0, want_pts ? total : 0));
+    if (t.refine) TRY(m->pose.t.reserve_track((size_t)nf, rows));
     TrItem *items = t.in.host<TrItem>(L.items);
     size_t tab = 0, kp = 0;
     for (int f = 0; f < nf; f++) {
@@ -277,7 +277,8 @@ int submit_on_device(mcorb_lmap *m, const mcorb_track_view *views, const Frame *
     }
     memcpy(t.in.host<mcorb_track_view>(L.views), views, (size_t)nf * sizeof(mcorb_track_view));
     memcpy(t.in.host<int>(L.cand), tc.cand.data(), total * sizeof(int));
-    TRY(t.in.upload(st, L.p.total));
+    Submission sub(st);   // (from here on nothing returns before a wait: this one's after a failed piece, wait_body's otherwise)
+    t.in.upload(sub, L.p.total);
     const TrItem *d_items = t.in.dev<const TrItem>(L.items);
     const mcorb_track_view *d_views = t.in.dev<const mcorb_track_view>(L.views);
     const int *d_cand = t.in.dev<const int>(L.cand);
@@ -287,31 +288,29 @@ int submit_on_device(mcorb_lmap *m, const mcorb_track_view *views, const Frame *
         const uint32_t *sel;
         const int *nsel;
         slot_sel(*slot, sel, nsel);
-        TRY(t.chain.mark(st, TK::kPoints));
-        launch_track_points(st, d_items, nf, max_n, sel, nsel, kcap, C, fr[0].rig->tab.scale, fr[0].rig->tab.nlevels, t.d_kp);
-        HIPCHK(hipGetLastError());
+        sub.run(t.chain, TK::kPoints,
+                [&] { launch_track_points(st, d_items, nf, max_n, sel, nsel, kcap, C, fr[0].rig->tab.scale, fr[0].rig->tab.nlevels, t.d_kp); });
         kp_xy = t.d_kp;
         kp_desc = slot->d_desc.get();
     }
-    TRY(t.chain.mark(st, TK::kProject));
-    launch_track_project(st, d_items, nf, max_n, d_views, m->d_geom, d_cand, t.d_xy, t.d_valid, want_pts ? t.d_pt.get() : nullptr);
-    HIPCHK(hipGetLastError());
-    TRY(t.chain.mark(st, TK::kMatch));
-    launch_track_match(st, d_items, nf, max_n, C, kp_xy, kp_desc, m->d_desc, d_cand, t.d_xy, t.d_valid, max_d2, max_hamming, t.d_best);
-    HIPCHK(hipGetLastError());
-    TRY(t.chain.mark(st, TK::kCompact));
-    launch_track_compact(st, d_items, nf, max_n, C, t.d_valid, t.d_xy, t.d_best, t.h_rows, t.h_nproj);
-    HIPCHK(hipGetLastError());
-    TRY(t.chain.mark(st, TK::kDedup));
-    HIPCHK(hipMemsetAsync(t.d_owner, 0xff, slots * sizeof(uint32_t), st));
-    HIPCHK(hipMemsetAsync(t.d_val, 0xff, slots * sizeof(unsigned long long), st));
-    launch_track_dedup(st, d_items, nf, max_n, C, kp_xy, t.d_valid, t.d_best, t.d_owner, t.d_val, t.d_slot, t.d_win, t.h_match, t.h_nmatch);
-    HIPCHK(hipGetLastError());
-    TRY(t.chain.mark(st, TK::kDedup + 1));
+    sub.run(t.chain, TK::kProject, [&] {
+        launch_track_project(st, d_items, nf, max_n, d_views, m->d_geom, d_cand, t.d_xy, t.d_valid, want_pts ? t.d_pt.get() : nullptr);
+    });
+    sub.run(t.chain, TK::kMatch, [&] {
+        launch_track_match(st, d_items, nf, max_n, C, kp_xy, kp_desc, m->d_desc, d_cand, t.d_xy, t.d_valid, max_d2, max_hamming, t.d_best);
+    });
+    sub.run(t.chain, TK::kCompact, [&] { launch_track_compact(st, d_items, nf, max_n, C, t.d_valid, t.d_xy, t.d_best, t.h_rows, t.h_nproj); });
+    sub.mark(t.chain, TK::kDedup);
+    sub.fill(t.d_owner, 0xff, slots * sizeof(uint32_t));
+    sub.fill(t.d_val, 0xff, slots * sizeof(unsigned long long));
+    sub.run([&] {
+        launch_track_dedup(st, d_items, nf, max_n, C, kp_xy, t.d_valid, t.d_best, t.d_owner, t.d_val, t.d_slot, t.d_win, t.h_match, t.h_nmatch);
+    });
+    sub.mark(t.chain, TK::kDedup + 1);
     // (mcorb_lmap_set_track_refine: the pose from each frame's matches, one workgroup of k_pose_refine per frame, in the same submission)
-    if (t.refine) TRY(pose_track_submit(m, views, items, nf, kp_xy, d_cand));
-    if (want_pts) HIPCHK(hipMemcpyAsync(t.h_pt, t.d_pt, total * 3 * sizeof(double), hipMemcpyDeviceToHost, st));
-    return MCORB_OK;
+    if (t.refine) pose_track_submit(sub, m, views, items, nf, kp_xy, d_cand);
+    if (want_pts) sub.copy(t.h_pt, t.d_pt, total * 3 * sizeof(double), hipMemcpyDeviceToHost);
+    return sub.failed() ? sub.wait() : MCORB_OK;
 }
 
 // ---- 3. a call's two halves, the frames checked; the caller holds the store's lock ----
@@ -335,8 +334,8 @@ void begin_call(mcorb_lmap *m, int C, int nf, bool want_pts)
 
 // everything up to and excluding the synchronisation: the candidates of every frame (frame f's ids are lids[lid_first[f] ..
 // lid_first[f + 1])), one stamp value each, then the whole call frame by frame on a host-only store -- and when no frame has a
-// candidate, which leaves the stream untouched --, the one submission on a device store.  A refusal leaves nothing behind: work
-// that a failed submission put on the stream is waited for here.  outs: the synchronous entries'
+// candidate, which leaves the stream untouched --, the one submission on a device store.  A refusal leaves nothing behind: a
+// submission with a failed piece waits for what it had queued (Submission).  outs: the synchronous entries'
 int submit_body(mcorb_lmap *m, const mcorb_track_view *views, const Frame *fr, int nf, const int32_t *lids, const int32_t *lid_first,
                 double max_d2, int max_hamming, bool want_pts, mcorb_track_out *outs)
 {
@@ -376,11 +375,7 @@ int submit_body(mcorb_lmap *m, const mcorb_track_view *views, const Frame *fr, i
         m->track.pose_nf = tc.refine ? nf : 0;
         return MCORB_OK;
     }
-    const int r = submit_on_device(m, views, fr, nf, tc, max_d2, max_hamming, want_pts);
-    if (r != MCORB_OK) {
-        (void)hipStreamSynchronize(m->st);
-        return r;
-    }
+    TRY(submit_on_device(m, views, fr, nf, tc, max_d2, max_hamming, want_pts));
     tc.launched = true;
     tc.points = fr[0].slot != nullptr;
     m->track.pose_nf = tc.refine ? nf : 0;

@@ -69,6 +69,8 @@ def main():
            "batched_32_frames": {"transform_ms_per_rig_frame": round(float(np.median(bt[5:])) * 1e3, 4),
                                  "bow_guided_match_ms_per_rig_frame": round(float(np.median(bm[5:])) * 1e3, 4)},
            "tracks": int(len(tr)), "keypoints_per_camera": int(len(rig.features(0)[1]))}
+    # the fastest and the slowest of the 15 timed runs of each figure, in the order of the figures above
+    out["ms_min_max"] = [[round(min(t[5:]) * 1e3, 4), round(max(t[5:]) * 1e3, 4)] for t in (tt, tm, bt, bm)]
     print(json.dumps(out))
 
 

@@ -30,12 +30,15 @@ def bow(rng):
     return ids, v / v.sum()
 
 
-def median_ms(fn, reps):
+def median_ms(fn, reps, min_max=None):
+    """the median of reps runs; min_max: a list that receives the fastest and the slowest run, as the other rate scripts print them"""
     t = []
     for _ in range(reps):
         t0 = time.perf_counter()
         fn()
         t.append(time.perf_counter() - t0)
+    if min_max is not None:
+        min_max[:] = [round(min(t) * 1e3, 3), round(max(t) * 1e3, 3)]
     return float(np.median(t)) * 1e3
 
 
@@ -62,11 +65,12 @@ def query_leg(mcorb, n_entries, nq, reps):
         dev.query_entries(ents, max_ids, 50)
         kus.append(dev.timing()[0])
     k_us = float(np.median(kus))
+    mm = []
     alg = 4.0 * stored * nq        # the ids of every eligible entry, per query (+ 8 B per shared word: ~90 x 8 B per pair, < 7 %)
     return {"entries": n_entries, "queries_per_call": nq, "stored_words": stored, "device_equals_host": bool(same),
             "entries_listed_per_query": round(shared / nq, 1), "k_kfdb_score_us": round(k_us, 1),
             "algorithmic_MB": round(alg / 1e6, 1), "k_kfdb_score_GBps": round(alg / (k_us * 1e-6) / 1e9, 1),
-            "device_call_ms": round(median_ms(lambda: dev.query_entries(ents, max_ids, 50), reps), 3),
+            "device_call_ms": round(median_ms(lambda: dev.query_entries(ents, max_ids, 50), reps, mm), 3), "device_call_ms_min_max": mm,
             "host_only_call_ms": round(median_ms(lambda: host.query_entries(ents, max_ids, 50), max(2, reps // 2)), 3)}
 
 
@@ -93,10 +97,11 @@ def match_leg(mcorb, reps, n=3000, nodes=100):
     for _ in range(reps):
         dev.featureMatchesBow(0, 1)
         kus.append(dev.timing()[1])
+    mm = []
     return {"features": n, "nodes": nodes, "matches": int(len(got[0])),
             "device_equals_host": bool(np.array_equal(got[0], want[0]) and np.array_equal(got[1], want[1])),
             "k_kfdb_best2_us": round(float(np.median(kus)), 1),
-            "device_call_ms": round(median_ms(lambda: dev.featureMatchesBow(0, 1), reps), 3),
+            "device_call_ms": round(median_ms(lambda: dev.featureMatchesBow(0, 1), reps, mm), 3), "device_call_ms_min_max": mm,
             "host_only_call_ms": round(median_ms(lambda: host.featureMatchesBow(0, 1), reps), 3)}
 
 

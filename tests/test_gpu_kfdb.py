@@ -72,6 +72,26 @@ def test_query_equals_host_only(qdbs):
         same(g, h)
 
 
+def test_entries_without_words_or_descriptors(mc, voc):
+    """add with nbow = 0 beside descriptors, with ndesc = 0 beside words, and with neither: the copies of 0 bytes are not queued,
+    the counts are; entries, queries and scores equal the host-only database's"""
+    full = K.keyframe(65, 14)
+    w = full[0][0][:1]
+    kfs = [((np.zeros(0, np.uint32), np.zeros(0)), {}, full[2][:5]),             # no word, five descriptors
+           ((w, np.array([0.5])), {}, np.zeros((0, 32), np.uint8)),              # one word, no descriptor
+           ((np.zeros(0, np.uint32), np.zeros(0)), {}, np.zeros((0, 32), np.uint8)), full]
+    dev, host = pair(mc, voc, kfs)
+    for i, (bow, fv, desc) in enumerate(kfs):
+        (ids, vals), gfv, gdesc = dev.entry(i)
+        assert np.array_equal(ids, bow[0]) and vals.tobytes() == np.asarray(bow[1], np.float64).tobytes(), i
+        assert sorted(gfv) == sorted(fv) and np.array_equal(gdesc, desc), i
+    for q in [kf[0] for kf in kfs]:
+        same(dev.query(q, -1, -1), host.query(q, -1, -1))
+    for a, b in itertools.product(range(4), range(4)):
+        assert dev.score(a, b) == host.score(a, b), (a, b)
+    assert len(dev.query(kfs[1][0], -1, -1)[0]) == 2 and len(dev.query(kfs[0][0], -1, -1)[0]) == 0
+
+
 def test_score_equals_host_only(qdbs):
     dev, host = qdbs
     n = dev.size()

@@ -118,6 +118,41 @@ def test_repeated_ids_across_workgroups(mc, vocs):
     assert 0.05 * n < sum(not w[0] for w in want) < 0.6 * n
 
 
+def test_batches_where_a_chain_shrinks(mc, vocs):
+    """the calls whose submission shrinks to one piece or to none, device against host-only, bit for bit: observe that records
+    only (no kernel, no entry: nothing is queued), one item, and every id twice; update_points, set_rays and delete with one item
+    and with every id twice (delete refuses that on both, and nothing changes)"""
+    rng = np.random.default_rng(41)
+    ncams, n = 4, 6
+    pts = Lc.random_points(rng, n)
+    lids = np.arange(20, 20 + n, dtype=np.int32)
+    fr = [Lc.random_frame(rng, 1 + k, ncams, 30, blind=0.0) for k in range(3)]
+    twice = np.concatenate([lids, lids[::-1]])
+    step = {len(sel): rng.choice([0.5, 8.0], (len(sel), 1)) for sel in (lids[:1], twice)}
+    out = []
+    for lm in stores(mc, vocs):
+        lm.set(lids, pts, np.zeros_like(pts))
+        got = [lm.observe(to_obs(mc, fr[0]), lids[:1], [3]).tolist()]                              # one item
+        got.append(lm.observe(to_obs(mc, fr[1]), lids, np.arange(n), mode=mc.OBS_RECORD).tolist())   # nothing queued
+        got.append(lm.observe(to_obs(mc, fr[1]), lids[:1], [7], mode=mc.OBS_RECORD).tolist())
+        got.append(lm.observe(to_obs(mc, fr[2]), twice, np.arange(2 * n)).tolist())                # every id twice
+        got.append(Lc.snapshot(lm, lids))
+        for sel in (lids[:1], twice):
+            new = pts[sel - 20] + step[len(sel)]
+            upd, diff = lm.update_points(sel, new)
+            got.append((upd.tolist(), bits(diff)))
+            lm.set_rays(sel, np.arange(len(sel)) + 2)
+            got.append(Lc.snapshot(lm, lids))
+        Lc.expect(mc, mc.E_ARG, lambda: lm.delete(twice))
+        got.append(Lc.snapshot(lm, lids))
+        got.append(lm.delete(lids[:1]))
+        Lc.expect(mc, mc.E_STATE, lambda: lm.get(int(lids[0])))
+        got.append(Lc.snapshot(lm, lids[1:]))
+        out.append(got)
+    assert out[0] == out[1]
+    assert out[0][3][:n] != out[0][3][n:] and len(out[0][-2]) == 5
+
+
 def test_gate_values_in_one_launch(mc, vocs):
     """every gate row of the CPU file; the rows of one max_diff share a launch"""
     both = stores(mc, vocs)

@@ -104,6 +104,27 @@ def test_sized_nodes_and_branches(mc, vocs):
         assert len(got.ind1) > 5
 
 
+def test_searches_whose_second_half_shrinks(mc, vocs):
+    """the cull accepts nothing (every candidate behind the camera: no gather, no descent, no search) and the accepted landmarks
+    share no FeatureVector node with the probe (the gather and the descent run, k_kfdb_best2 has no item), for 1 and 65
+    candidates: the device equals the host-only store, and a search with matches behind them is not disturbed"""
+    d, node = Lc.pool()
+    nodes = sorted(set(node.tolist()))
+    A, B = d[node == nodes[0]][:65], d[node == nodes[1]][:40]
+    view, land = Lc.front_store(A, lid0=7)
+    behind = (land[0], land[1] * np.array([1.0, 1.0, -1.0]), land[2], land[3], land[4])
+    v = Lc.to_view(mc, view)
+    for landmarks, probe, accepted, matches in ((behind, Lc.probe_of(A), False, False), (land, Lc.probe_of(B), True, False),
+                                                (land, Lc.probe_of(A), True, True)):
+        (lm_d, db_d), (lm_h, db_h) = both(mc, vocs, probe, landmarks)
+        nb = len(probe[2])
+        for n in (1, 65):
+            got = lm_d.search(v, land[0][:n], [], db_d, 0, *free(nb), levelsup=K.LEVELSUP)
+            same_result(got, lm_h.search(v, land[0][:n], [], db_h, 0, *free(nb), levelsup=K.LEVELSUP), n)
+            assert len(got.new_lids) == (n if accepted else 0) and lm_d.last_timing()[2] == n
+            assert (len(got.ind1) > 0) == matches
+
+
 def test_rig_frames_entry_to_store_and_probe(mc):
     """set_desc_from_entry from an entry written by add_rig_frame, a search whose probe was set by set_probe_rig_frame, and the
     entry and the probe read back unchanged after it"""

@@ -154,6 +154,13 @@ def test_candidate_counts_257_0_1(mc, vocs):
     rig.close()
 
 
+def test_last_frame_without_candidates(mc, job3):
+    """a 2-frame batch whose second frame has no candidate: the submission's rows end with the first frame's"""
+    rig, store, lidss, lms = job3
+    got = check(mc, lms, rig, [shifted(rig, t) for t in SHIFTS[:2]], [0, 1], [lidss[0], [-1]], store, vacuous_ok=(1,))
+    assert got[0]["n_candidates"] > 0 and got[1]["n_candidates"] == 0 and got[1]["proj"] == [[]] * 4 and got[1]["matches"] == [[]] * 4
+
+
 def test_keypoint_extremes(mc, vocs):
     """a 2-frame job whose first frame has a camera without keypoints (an all-zero image), one with a handful (a blank image with
     one patch) and one with more than one LDS tile of k_track_match; a landmark's match is a keypoint of the second tile"""

@@ -146,8 +146,8 @@ def test_three_frames_in_one_call(mc, job3):
 
 
 def test_frames_without_matches(mc, job3):
-    """no candidate at all (nothing is launched), candidates that are all behind the rig, and an empty frame in the middle of a
-    batch: NO_OBS with the view's pose"""
+    """no candidate at all (nothing is launched), candidates that are all behind the rig, an empty frame in the middle of a
+    batch and one at the end of a 2-frame batch (the refinement's rows end with the first frame's): NO_OBS with the view's pose"""
     rig, lms, store = job3["rig"], job3["lms"], job3["store"]
     behind = [l for l, ((x, y, z), d) in store.items() if z < 0]
     assert len(behind) >= 4
@@ -165,6 +165,10 @@ def test_frames_without_matches(mc, job3):
         assert lm.last_track_pose(1).status == P.NO_OBS
         for f in (0, 2):
             PC.same(PC.as_ref(lm.last_track_pose(f)), job3["refs"][f], "frame %d beside an empty one" % f)
+        two = lm.track_rig_frames(views[:2], rig, [0, 1], [job3["lidss"][0], [-1]])
+        assert two[1].n_candidates == 0 and lm.last_track_pose(1).status == P.NO_OBS
+        T.same(T.as_lists(two[0]), T.ref_lists(job3["tracked"][0], store), "frame 0 in front of an empty last frame")
+        PC.same(PC.as_ref(lm.last_track_pose(0)), job3["refs"][0], "frame 0 in front of an empty last frame")
         lm.track_rig_frames(views, rig, [0, 1, 2], [[], [], []])
         assert [lm.last_track_pose(f).status for f in range(3)] == [P.NO_OBS] * 3
         lm.set_track_refine(None)
