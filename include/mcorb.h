@@ -1380,6 +1380,21 @@ double mcorb_sac_threshold(double K00_02);
 int mcorb_sac_solve(const mcorb_track_cam *cam, const float *uv, const double *pts, double *R, double *t);
 /* test hook, host: the same of the rig solver on three observations of cameras cam[3] of the rig cams[ncams] */
 int mcorb_sac_solve_rig(int ncams, const mcorb_track_cam *cams, const int32_t *cam, const float *uv, const double *pts, double *R, double *t);
+/* test hook, host: the rig solver on four observations of cameras cam[4] -- the three of mcorb_sac_solve_rig and the fourth,
+ * disambiguating one -- -> the count and the poses as mcorb_sac_solve_rig gives them, mask: bit k set iff root k of the quartic
+ * has a pose, best: the root whose pose the estimator takes by the fourth point's score (-1: none) and that pose (zero without) */
+int mcorb_host_sac_rig_roots(int ncams, const mcorb_track_cam *cams, const int32_t *cam, const float *uv, const double *pts, double *R, double *t,
+                             int32_t *mask, int32_t *best, double *best_R, double *best_t);
+/* test hook, device: mcorb_sac_solve on n problems in one launch, a lane each -- cam[n], uv (n x 3 x 2), pts (n x 3 x 3) -> count[n]
+ * and R (n x 4 x 9), t (n x 4 x 3), zero behind a problem's count.  n == 0 launches nothing */
+int mcorb_dev_sac_solve_selftest(int device, int n, const mcorb_track_cam *cam, const float *uv, const double *pts, int32_t *count, double *R,
+                                 double *t);
+/* test hook, device: mcorb_host_sac_rig_roots on n problems in one launch of k_sac_hypotheses_rig's shape and body, a quad each --
+ * problem i has the rig cams[ncams i ..], cam (n x 4), uv (n x 4 x 2), pts (n x 4 x 3) -> count[n], R (n x 4 x 9), t (n x 4 x 3),
+ * zero behind a problem's count, mask[n], best[n], best_R (n x 9), best_t (n x 3).  Refuses what mcorb_sac_solve_rig refuses */
+int mcorb_dev_sac_solve_rig_selftest(int device, int n, int ncams, const mcorb_track_cam *cams, const int32_t *cam, const float *uv,
+                                     const double *pts, int32_t *count, double *R, double *t, int32_t *mask, int32_t *best, double *best_R,
+                                     double *best_t);
 /* test hook, host: the scores of n observations at the pose (R, t); a NaN is the default quiet NaN */
 int mcorb_sac_eval(int ncams, const mcorb_track_cam *cams, int n, const int32_t *cam, const float *uv, const double *pts, const double *R,
                    const double *t, double *score);
@@ -1454,6 +1469,11 @@ double mcorb_rel_threshold(double K00_02);
  * frame */
 int mcorb_rel_solve(int ncams, const mcorb_track_cam *cams, const int32_t *cam1, const double *uv1, const int32_t *cam2, const double *uv2,
                     double *R, double *t);
+/* test hook, device: mcorb_rel_solve on n problems in one launch, a lane each -- problem i has the rig cams[ncams i ..], cam1 and
+ * cam2 (n x 17), uv1 and uv2 (n x 17 x 2) -> count[n] (1 or 0), R (n x 9), t (n x 3), zero without a model.  Refuses what
+ * mcorb_rel_solve refuses; n == 0 launches nothing */
+int mcorb_dev_rel_solve_selftest(int device, int n, int ncams, const mcorb_track_cam *cams, const int32_t *cam1, const double *uv1,
+                                 const int32_t *cam2, const double *uv2, int32_t *count, double *R, double *t);
 /* test hook, host: the scores of n matches at the pose (R, t); a NaN is the default quiet NaN */
 int mcorb_rel_eval(int ncams, const mcorb_track_cam *cams, int n, const int32_t *cam1, const double *uv1, const int32_t *cam2,
                    const double *uv2, const double *R, const double *t, double *score);
@@ -1576,8 +1596,13 @@ int mcorb_lmap_last_align_timing(mcorb_lmap *m, float us[4], int *n_hyp);
 int mcorb_lmap_last_align_counts(mcorb_lmap *m, int32_t *count, int32_t *valid, int cap, int *n_hyp);
 /* test hook, host: align_fit over the pairs i of (p1, p2: n x 3 doubles) with member[i] != 0 (member NULL: all) -> 1 with (R as
  * 9, t as 3 doubles) = b1_T_b2, 0 when the fit is not valid (R, t are then what it computed), or a negative error.  gap (may be
- * NULL): (l1 - l2) / (l1 - l4) of Horn's matrix */
+ * NULL): (l1 - l2) / (l1 - l4) of Horn's matrix, a NaN as the default quiet NaN */
 int mcorb_align_solve(int n, const double *p1, const double *p2, const uint8_t *member, double *R, double *t, double *gap);
+/* test hook, device: mcorb_align_solve on n problems in one launch, a workgroup of k_align_fit's shape and fit passes each --
+ * problem i has npairs[i] pairs, the problems' pairs back to back in p1, p2 and member (one byte a pair; none may be NULL unless
+ * no problem has a pair) -> valid[n], R (n x 9), t (n x 3), zero without a valid fit, gap[n].  n == 0 launches nothing */
+int mcorb_dev_align_solve_selftest(int device, int n, const int32_t *npairs, const double *p1, const double *p2, const uint8_t *member,
+                                   int32_t *valid, double *R, double *t, double *gap);
 /* test hook, host: the distances of n pairs at the pose (R, t); a NaN is the default quiet NaN */
 int mcorb_align_eval(int n, const double *p1, const double *p2, const double *R, const double *t, double *dist);
 
@@ -1651,6 +1676,11 @@ int mcorb_lmap_last_essential_counts(mcorb_lmap *m, int32_t *count, int32_t *val
  * and (z may be NULL) the root each came from before its Gauss-Newton steps, ascending; or a negative error.  The hooks take the
  * keypoints in double: a float's value gives the bits mcorb_lmap_essential_pose computes from that float */
 int mcorb_ess_solve(const mcorb_track_cam *cam, const double *uv1, const double *uv2, double *E, double *z);
+/* test hook, device: mcorb_ess_solve on n problems in one launch of k_ess_hypotheses' shape and body, sixteen lanes a problem and
+ * four problems a workgroup -- cam[n], uv1 and uv2 (n x 5 x 2) -> count[n], E (n x 10 x 9) and z (n x 10), zero behind a
+ * problem's count.  n == 0 launches nothing */
+int mcorb_dev_ess_solve_selftest(int device, int n, const mcorb_track_cam *cam, const double *uv1, const double *uv2, int32_t *count, double *E,
+                                 double *z);
 /* test hook, host: the Sampson values of n matches at E; a NaN is the default quiet NaN */
 int mcorb_ess_eval(const mcorb_track_cam *cam, int n, const double *uv1, const double *uv2, const double *E, double *err);
 /* test hook, host: the four candidates of E -- Rp, Rm (9 doubles each) and t^ -- and, where n > 0, the depths of the n matches in

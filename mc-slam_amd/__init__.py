@@ -2173,6 +2173,130 @@ def sac_solve_rig(cams, cam, uv, pts):
     return [(R[i].reshape(3, 3).copy(), t[i].copy()) for i in range(k)]
 
 
+def sac_rig_roots(cams, cam, uv, pts):
+    """test hook (host): the rig solver on four observations of cameras cam (4) -- the three of sac_solve_rig and the fourth,
+    disambiguating one -> ([(R 3 x 3, t)] as sac_solve_rig gives them, mask: bit k set iff root k has a pose, best: the root the
+    estimator takes (-1: none), (R 3 x 3, t) of that root, zero without)"""
+    cam = np.ascontiguousarray(cam, np.int32).reshape(4)
+    uv = np.ascontiguousarray(uv, np.float32).reshape(4, 2)
+    pts = np.ascontiguousarray(pts, np.float64).reshape(4, 3)
+    ncams, ca = _pose_cams(cams)
+    R, t, Rb, tb = np.zeros((4, 9)), np.zeros((4, 3)), np.zeros(9), np.zeros(3)
+    mask, best = np.zeros(1, np.int32), np.zeros(1, np.int32)
+    k = _lib.load().mcorb_host_sac_rig_roots(ncams, ca, cam.ctypes.data, uv.ctypes.data, pts.ctypes.data, R.ctypes.data, t.ctypes.data,
+                                             mask.ctypes.data, best.ctypes.data, Rb.ctypes.data, tb.ctypes.data)
+    _lib.check(min(k, 0))
+    return [(R[i].reshape(3, 3).copy(), t[i].copy()) for i in range(k)], int(mask[0]), int(best[0]), (Rb.reshape(3, 3), tb)
+
+
+_CAM_DOUBLES = C.sizeof(_lib.TrackCam) // 8
+
+
+def _cam_rows(view):
+    """the cameras of a track_view as doubles, ncams x 17"""
+    return np.frombuffer(view.cams, np.float64).reshape(_lib.MAX_CAMS, _CAM_DOUBLES)[:view.ncams]
+
+
+def _rig_table(rigs):
+    """the rigs of n problems -> (ncams: the largest rig's, n x ncams x 17 doubles, smaller rigs padded with zeros)"""
+    ncams = max([r.ncams for r in rigs], default=1)
+    table = np.zeros((len(rigs), ncams, _CAM_DOUBLES))
+    for i, r in enumerate(rigs):
+        table[i, :r.ncams] = _cam_rows(r)
+    return ncams, table
+
+
+def _own_rig(rigs, *cams):
+    """the entries check a camera index against the table's one ncams, the largest rig's: an index outside a problem's own,
+    smaller rig would read a camera of zeros there, so it is refused here as the host hooks refuse it"""
+    own = np.array([r.ncams for r in rigs], np.int64).reshape(len(rigs), 1)
+    if len(rigs) and any((np.asarray(c).reshape(len(rigs), -1) >= own).any() for c in cams):
+        raise McorbError(E_ARG, "a camera index outside the rig")
+
+
+def _p(a):
+    return a.ctypes.data if a.size else None
+
+
+def dev_sac_solve(rigs, cam, uv, pts, device=0):
+    """test hook (device): sac_solve on n problems in one launch -- problem i: camera cam[i] of rigs[i], uv (n x 3 x 2), pts (n x 3 x
+    3) -> (count n, R n x 4 x 9, t n x 4 x 3), zero behind a problem's count"""
+    n = len(rigs)
+    cam = np.ascontiguousarray(cam, np.int64).reshape(n)
+    uv = np.ascontiguousarray(uv, np.float32).reshape(n, 3, 2)
+    pts = np.ascontiguousarray(pts, np.float64).reshape(n, 3, 3)
+    cams = np.zeros((n, _CAM_DOUBLES))
+    for i, r in enumerate(rigs):
+        assert 0 <= cam[i] < r.ncams
+        cams[i] = _cam_rows(r)[cam[i]]
+    count, R, t = np.zeros(n, np.int32), np.zeros((n, 4, 9)), np.zeros((n, 4, 3))
+    _lib.check(_lib.load().mcorb_dev_sac_solve_selftest(int(device), n, _p(cams), _p(uv), _p(pts), _p(count), _p(R), _p(t)))
+    return count, R, t
+
+
+def dev_sac_solve_rig(rigs, cam, uv, pts, device=0):
+    """test hook (device): sac_rig_roots on n problems in one launch of the rig hypotheses kernel's shape and body -- problem i:
+    cameras cam[i] (4) of rigs[i], uv (n x 4 x 2), pts (n x 4 x 3) -> (count n, R n x 4 x 9, t n x 4 x 3, mask n, best n, best_R n x
+    9, best_t n x 3)"""
+    n = len(rigs)
+    cam = np.ascontiguousarray(cam, np.int32).reshape(n, 4)
+    uv = np.ascontiguousarray(uv, np.float32).reshape(n, 4, 2)
+    pts = np.ascontiguousarray(pts, np.float64).reshape(n, 4, 3)
+    _own_rig(rigs, cam)
+    ncams, cams = _rig_table(rigs)
+    count, mask, best = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.int32)
+    R, t, Rb, tb = np.zeros((n, 4, 9)), np.zeros((n, 4, 3)), np.zeros((n, 9)), np.zeros((n, 3))
+    _lib.check(_lib.load().mcorb_dev_sac_solve_rig_selftest(int(device), n, ncams, _p(cams), _p(cam), _p(uv), _p(pts), _p(count), _p(R),
+                                                            _p(t), _p(mask), _p(best), _p(Rb), _p(tb)))
+    return count, R, t, mask, best, Rb, tb
+
+
+def dev_rel_solve(rigs, cam1, uv1, cam2, uv2, device=0):
+    """test hook (device): rel_solve on n problems in one launch -- problem i: 17 matches of rigs[i], cam1 and cam2 (n x 17), uv1
+    and uv2 (n x 17 x 2, doubles) -> (count n, R n x 9, t n x 3), zero without a model"""
+    n = len(rigs)
+    cam1 = np.ascontiguousarray(cam1, np.int32).reshape(n, REL_SAMPLE)
+    cam2 = np.ascontiguousarray(cam2, np.int32).reshape(n, REL_SAMPLE)
+    uv1 = np.ascontiguousarray(uv1, np.float64).reshape(n, REL_SAMPLE, 2)
+    uv2 = np.ascontiguousarray(uv2, np.float64).reshape(n, REL_SAMPLE, 2)
+    _own_rig(rigs, cam1, cam2)
+    ncams, cams = _rig_table(rigs)
+    count, R, t = np.zeros(n, np.int32), np.zeros((n, 9)), np.zeros((n, 3))
+    _lib.check(_lib.load().mcorb_dev_rel_solve_selftest(int(device), n, ncams, _p(cams), _p(cam1), _p(uv1), _p(cam2), _p(uv2), _p(count),
+                                                        _p(R), _p(t)))
+    return count, R, t
+
+
+def dev_ess_solve(rigs, uv1, uv2, device=0):
+    """test hook (device): ess_solve on n problems in one launch of the essential hypotheses kernel's shape and body -- problem i:
+    camera 0 of rigs[i], uv1 and uv2 (n x 5 x 2, doubles) -> (count n, E n x 10 x 9, z n x 10), zero behind a problem's count"""
+    n = len(rigs)
+    uv1 = np.ascontiguousarray(uv1, np.float64).reshape(n, 5, 2)
+    uv2 = np.ascontiguousarray(uv2, np.float64).reshape(n, 5, 2)
+    cams = np.zeros((n, _CAM_DOUBLES))
+    for i, r in enumerate(rigs):
+        cams[i] = _cam_rows(r)[0]
+    count, E, z = np.zeros(n, np.int32), np.zeros((n, 10, 9)), np.zeros((n, 10))
+    _lib.check(_lib.load().mcorb_dev_ess_solve_selftest(int(device), n, _p(cams), _p(uv1), _p(uv2), _p(count), _p(E), _p(z)))
+    return count, E, z
+
+
+def dev_align_solve(problems, device=0):
+    """test hook (device): align_solve on n problems in one launch, a workgroup each -- problems: [(p1 k x 3, p2 k x 3, member k or
+    None: all)] -> (valid n, R n x 9, t n x 3, gap n), R and t zero without a valid fit"""
+    n = len(problems)
+    npairs = np.array([len(np.asarray(p[0]).reshape(-1, 3)) for p in problems], np.int32).reshape(n)
+    p1 = np.concatenate([np.asarray(p[0], np.float64).reshape(-1, 3) for p in problems] + [np.zeros((0, 3))])
+    p2 = np.concatenate([np.asarray(p[1], np.float64).reshape(-1, 3) for p in problems] + [np.zeros((0, 3))])
+    member = np.concatenate([np.ones(k, np.uint8) if p[2] is None else (np.asarray(p[2]).reshape(k) != 0).astype(np.uint8)
+                             for p, k in zip(problems, npairs)] + [np.zeros(0, np.uint8)])
+    p1, p2, member = np.ascontiguousarray(p1), np.ascontiguousarray(p2), np.ascontiguousarray(member)
+    valid, R, t, gap = np.zeros(n, np.int32), np.zeros((n, 9)), np.zeros((n, 3)), np.zeros(n)
+    _lib.check(_lib.load().mcorb_dev_align_solve_selftest(int(device), n, _p(npairs), _p(p1), _p(p2), _p(member), _p(valid), _p(R), _p(t),
+                                                          _p(gap)))
+    return valid, R, t, gap
+
+
 def sac_eval(cams, R, t, cam, uv, pts):
     """test hook (host): the scores (n) of the observations at the pose (R, t)"""
     cam = np.ascontiguousarray(cam, np.int32).reshape(-1)

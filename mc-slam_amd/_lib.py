@@ -395,6 +395,12 @@ SIGNATURES = {
     "mcorb_sac_solve": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "mcorb_sac_solve_rig": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mcorb_sac_eval": (_i, [_i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mcorb_host_sac_rig_roots": (_i, [_i] + [_vp] * 10),
+    "mcorb_dev_sac_solve_selftest": (_i, [_i, _i] + [_vp] * 6),
+    "mcorb_dev_sac_solve_rig_selftest": (_i, [_i, _i, _i] + [_vp] * 11),
+    "mcorb_dev_rel_solve_selftest": (_i, [_i, _i, _i] + [_vp] * 8),
+    "mcorb_dev_ess_solve_selftest": (_i, [_i, _i] + [_vp] * 6),
+    "mcorb_dev_align_solve_selftest": (_i, [_i, _i] + [_vp] * 8),
     "mcorb_lmap_relative_pose": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _vp, C.POINTER(RelParams), C.POINTER(RelResultC), _vp]),
     "mcorb_lmap_last_relative_timing": (_i, [_vp, C.POINTER(_f), C.POINTER(_i)]),
     "mcorb_lmap_last_relative_counts": (_i, [_vp, _vp, _vp, _i, C.POINTER(_i)]),

@@ -164,9 +164,51 @@ int mcorb_align_solve(int n, const double *p1, const double *p2, const uint8_t *
     PoseState P;
     int cnt;
     const bool ok = align_fit_host(n, p1, p2, member, P, cnt, gap);
+    if (gap) *gap = pose_default_nan(*gap);   // (returned to the caller: the device twin's bits)
     memcpy(R, P.R, sizeof(P.R));
     memcpy(t, P.t, sizeof(P.t));
     return ok ? 1 : 0;
+}
+
+int mcorb_dev_align_solve_selftest(int device, int n, const int32_t *npairs, const double *p1, const double *p2, const uint8_t *member,
+                                   int32_t *valid, double *R, double *t, double *gap)
+{
+    if (n < 0 || (n && (!npairs || !valid || !R || !t || !gap))) return fail(MCORB_E_ARG, "bad argument");
+    const size_t N = (size_t)n;
+    std::vector<int32_t> first(N);
+    size_t total = 0;
+    for (size_t i = 0; i < N; i++) {
+        if (npairs[i] < 0 || total + (size_t)npairs[i] > 0x7fffffffu) return fail(MCORB_E_ARG, "a pair count out of range");
+        first[i] = (int32_t)total;
+        total += (size_t)npairs[i];
+    }
+    if (total && (!p1 || !p2 || !member)) return fail(MCORB_E_ARG, "bad argument");
+    if (n == 0) return MCORB_OK;
+    TRY(selftest_device(device));
+    const size_t T = total ? total : 1;   // (problems without pairs read nothing)
+    DevBuf<double> d_p1, d_p2, d_R, d_t, d_gap;
+    DevBuf<uint8_t> d_member;
+    DevBuf<int32_t> d_first, d_cnt, d_valid;
+    TRY(zeroed(d_p1, 3 * T));
+    TRY(zeroed(d_p2, 3 * T));
+    TRY(zeroed(d_member, T));
+    if (total) {
+        HIPCHK(hipMemcpy(d_p1, p1, 3 * total * sizeof(double), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(d_p2, p2, 3 * total * sizeof(double), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(d_member, member, total, hipMemcpyHostToDevice));
+    }
+    TRY(to_device(d_first, first.data(), N));
+    TRY(to_device(d_cnt, npairs, N));
+    TRY(d_valid.alloc(N));
+    TRY(d_R.alloc(N * 9));
+    TRY(d_t.alloc(N * 3));
+    TRY(d_gap.alloc(N));
+    launch_align_solve_selftest(nullptr, d_p1, d_p2, d_member, d_first, d_cnt, n, d_R, d_t, d_gap, d_valid);
+    HIPCHK(hipGetLastError());
+    TRY(from_device(valid, d_valid, N));
+    TRY(from_device(R, d_R, N * 9));
+    TRY(from_device(t, d_t, N * 3));
+    return from_device(gap, d_gap, N);
 }
 
 int mcorb_align_eval(int n, const double *p1, const double *p2, const double *R, const double *t, double *dist)

@@ -101,7 +101,79 @@ __global__ __launch_bounds__(kAlignTile) void k_align_pick(const AlignJob *__res
     }
 }
 
-// The folds are wg_fold's (mcorb_device.h), with a barrier behind each before part and wcnt are written again.
+// The two passes of a fit by one workgroup of kAlignTile over the members of n pairs (member null: all of them) -> their count;
+// M: the nine sums of pass 2 and c1, c2: the centroids, the same bits in every lane, for align_from_sums.  The folds are wg_fold's
+// (mcorb_device.h), with a barrier behind each before part and wcnt are written again.  k_align_fit and k_align_solve_selftest
+// both fit through this
+__device__ __forceinline__ int align_fit_sums(const AlignSrc &src, int n, const uint8_t *member, double (*part)[kAlignSums2], int32_t *wcnt,
+                                              double M[kAlignSums2], double c1[3], double c2[3])
+{
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    // pass 1: the coordinate sums and the members
+    double s[kAlignSums2];
+#pragma unroll
+    for (int k = 0; k < kAlignSums2; k++) s[k] = 0.0;
+    int mine = 0;
+    for (int i = t; i < n; i += kAlignTile) {
+        if (member && !member[i]) continue;
+        double p1[3], p2[3];
+        src(i, p1, p2);
+        align_add1(p1, p2, s);
+        mine++;
+    }
+    mine = wave_total(mine);
+    if (lane == 0) wcnt[wave] = mine;
+    wg_fold<kAlignSums1>(s, part, M);   // (its barrier and the next cover wcnt)
+    __syncthreads();
+    const int cnt = wg_combine(wcnt);
+    align_centroids(M, cnt, c1, c2);
+    // pass 2: M
+#pragma unroll
+    for (int k = 0; k < kAlignSums2; k++) s[k] = 0.0;
+    for (int i = t; i < n; i += kAlignTile) {
+        if (member && !member[i]) continue;
+        double p1[3], p2[3];
+        src(i, p1, p2);
+        align_add2(p1, p2, c1, c2, s);
+    }
+    wg_fold<kAlignSums2>(s, part, M);
+    __syncthreads();
+    return cnt;
+}
+
+// mcorb_dev_align_solve_selftest: a workgroup of k_align_fit's shape per problem -- problem b has cnt[b] pairs from pair first[b]
+// on in p1, p2 and member -- the fit's two passes, then lane 0's align_from_sums with the gap.  R and t are zero without a
+// valid fit; the gap is written either way, a NaN as the default quiet NaN
+__global__ __launch_bounds__(kAlignTile) void k_align_solve_selftest(const double *__restrict__ p1, const double *__restrict__ p2,
+                                                                     const uint8_t *__restrict__ member, const int32_t *__restrict__ first,
+                                                                     const int32_t *__restrict__ cnt, double *__restrict__ R,
+                                                                     double *__restrict__ tr, double *__restrict__ gap,
+                                                                     int32_t *__restrict__ valid)
+{
+    __shared__ double part[kWgWaves][kAlignSums2];
+    __shared__ int32_t wcnt[kWgWaves];
+    const int b = blockIdx.x;
+    const size_t at = (size_t)first[b];
+    const AlignSrc src{p1 + 3 * at, p2 + 3 * at, nullptr, nullptr};
+    double S[kAlignSums2], c1[3], c2[3];
+    const int members = align_fit_sums(src, cnt[b], member + at, part, wcnt, S, c1, c2);
+    if (threadIdx.x == 0) {
+        PoseState P;
+        double g = 0.0;
+        const bool ok = align_from_sums(S, c1, c2, members, P, &g);
+        for (int j = 0; j < 9; j++) R[9 * (size_t)b + j] = ok ? P.R[j] : 0.0;
+        for (int j = 0; j < 3; j++) tr[3 * (size_t)b + j] = ok ? P.t[j] : 0.0;
+        gap[b] = pose_default_nan(g);
+        valid[b] = ok ? 1 : 0;
+    }
+}
+
+void launch_align_solve_selftest(hipStream_t st, const double *p1, const double *p2, const uint8_t *member, const int32_t *first,
+                                  const int32_t *cnt, int n, double *R, double *t, double *gap, int32_t *valid)
+{
+    hipLaunchKernelGGL(k_align_solve_selftest, dim3(n), dim3(kAlignTile), 0, st, p1, p2, member, first, cnt, R, t, gap, valid);
+}
+
 __global__ __launch_bounds__(kAlignTile) void k_align_fit(const AlignJob *__restrict__ job, AlignSrc src, const AlignPick *pick,
                                                           const uint8_t *member, AlignOut *out, uint8_t *flags)
 {
@@ -125,35 +197,8 @@ __global__ __launch_bounds__(kAlignTile) void k_align_fit(const AlignJob *__rest
     bool have = best >= 0;
     int used = MCORB_ALIGN_USED_SAC;
     if (all || (have && job->refit)) {   // (uniform over the workgroup)
-        // pass 1: the coordinate sums and the members
-        double s[kAlignSums2], S[kAlignSums2], c1[3], c2[3];
-#pragma unroll
-        for (int k = 0; k < kAlignSums2; k++) s[k] = 0.0;
-        int mine = 0;
-        for (int i = t; i < n; i += kAlignTile) {
-            if (!all && !member[i]) continue;
-            double p1[3], p2[3];
-            src(i, p1, p2);
-            align_add1(p1, p2, s);
-            mine++;
-        }
-        mine = wave_total(mine);
-        if (lane == 0) wcnt[wave] = mine;
-        wg_fold<kAlignSums1>(s, part, S);   // (its barrier and the next cover wcnt)
-        __syncthreads();
-        const int cnt = wg_combine(wcnt);
-        align_centroids(S, cnt, c1, c2);
-        // pass 2: M
-#pragma unroll
-        for (int k = 0; k < kAlignSums2; k++) s[k] = 0.0;
-        for (int i = t; i < n; i += kAlignTile) {
-            if (!all && !member[i]) continue;
-            double p1[3], p2[3];
-            src(i, p1, p2);
-            align_add2(p1, p2, c1, c2, s);
-        }
-        wg_fold<kAlignSums2>(s, part, S);
-        __syncthreads();
+        double S[kAlignSums2], c1[3], c2[3];
+        const int cnt = align_fit_sums(src, n, all ? nullptr : member, part, wcnt, S, c1, c2);
         if (t == 0) {
             PoseState P;
             const bool ok = align_from_sums(S, c1, c2, cnt, P, nullptr);

@@ -285,6 +285,43 @@ int mcorb_ess_solve(const mcorb_track_cam *cam, const double *uv1, const double 
     return ess_solve5(d1, d2, E, z);
 }
 
+int mcorb_dev_ess_solve_selftest(int device, int n, const mcorb_track_cam *cam, const double *uv1, const double *uv2, int32_t *count, double *E,
+                                 double *z)
+{
+    if (n < 0 || (n && (!cam || !uv1 || !uv2 || !count || !E || !z))) return fail(MCORB_E_ARG, "bad argument");
+    if (n == 0) return MCORB_OK;
+    TRY(selftest_device(device));
+    const size_t N = (size_t)n, slots = N * kEssRoots;
+    std::vector<EssJob> jobs(N);
+    for (size_t i = 0; i < N; i++) fill_job(jobs[i], cam[i]);
+    DevBuf<EssJob> d_jobs;
+    DevBuf<double> d_uv1, d_uv2, d_z;
+    DevBuf<EssModel> d_models;
+    DevBuf<int32_t> d_valid;
+    TRY(to_device(d_jobs, jobs.data(), N));
+    TRY(to_device(d_uv1, uv1, N * 2 * kEssSample));
+    TRY(to_device(d_uv2, uv2, N * 2 * kEssSample));
+    TRY(d_models.alloc(slots));
+    TRY(d_valid.alloc(slots));
+    TRY(d_z.alloc(slots));
+    launch_ess_solve_selftest(nullptr, d_jobs, d_uv1, d_uv2, n, d_models, d_valid, d_z);
+    HIPCHK(hipGetLastError());
+    std::vector<EssModel> models(slots);
+    std::vector<int32_t> valid(slots);
+    TRY(from_device(models.data(), d_models, slots));
+    TRY(from_device(valid.data(), d_valid, slots));
+    TRY(from_device(z, d_z, slots));
+    for (size_t i = 0; i < N; i++) {
+        count[i] = 0;
+        for (int c = 0; c < kEssRoots; c++) {
+            const EssModel &M = models[kEssRoots * i + c];
+            memcpy(E + 9 * (kEssRoots * i + c), M.E, sizeof(M.E));   // (zero without a model)
+            count[i] += valid[kEssRoots * i + c] ? 1 : 0;           // (the dense flags k_ess_pick walks)
+        }
+    }
+    return MCORB_OK;
+}
+
 int mcorb_ess_eval(const mcorb_track_cam *cam, int n, const double *uv1, const double *uv2, const double *E, double *err)
 {
     if (!cam || n < 0 || !E || (n && (!uv1 || !uv2 || !err))) return fail(MCORB_E_ARG, "bad argument");

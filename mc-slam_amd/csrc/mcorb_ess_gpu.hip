@@ -6,7 +6,8 @@
 //                      10: cubic k into the group's 10 x 20 table.  Lane j < 11: det C(z) at node j -- the pivoted LU indexes
 //                      its rows at run time, so its 10 x 10 matrix is a private array in scratch --, then coefficient j of the
 //                      polynomial.  The derivative chain: per level, lane i takes bracket i and lane 0 gathers the roots found.
-//                      Lane r < 10: the model of root r into its slot
+//                      Lane r < 10: the model of root r into its slot.  Everything behind the sample is ess_group_models, which
+//                      k_ess_solve_selftest (mcorb_dev_ess_solve_selftest) runs on caller-given problems in the same launch shape
 //   k_ess_score        the hot path, 10 H x S Sampson distances: a workgroup owns a tile of kEssTile matches, whose normalised
 //                      points each lane computes once, and a block of kEssSlotBlock slots, whose models it reads at uniform
 //                      addresses: consensus_count (mcorb_consensus.h).  Slots without a model are skipped uniformly
@@ -39,21 +40,15 @@ struct EssGroup {
     int32_t has[kEssRoots + 1], sample[kEssSample], m, ok;
 };
 
-__global__ __launch_bounds__(64) void k_ess_hypotheses(const EssJob *__restrict__ job, const EssObs *__restrict__ obs,
-                                                       EssModel *__restrict__ models, int32_t *__restrict__ valid,
-                                                       int32_t *__restrict__ samples)
+// Everything of a hypothesis behind its sample, for the sixteen lanes of its group: G.d1, G.d2 and G.ok are lane 0's, written
+// before the call (the first barrier here covers them).  The slots go to models and valid at kEssRoots * h; z (null in a call):
+// the root each kept model began from, rho * G.crit[lane], compacted by the same prefix as its E, 0 behind the models.
+// k_ess_hypotheses feeds it from ess_sample, k_ess_solve_selftest from problem h of a table.  Every lane of the workgroup calls
+// it -- a group beyond the hypotheses (act false) goes through every barrier and touches nothing
+__device__ __forceinline__ void ess_group_models(EssGroup &G, int lane, int h, bool act, EssModel *__restrict__ models,
+                                                 int32_t *__restrict__ valid, double *__restrict__ z)
 {
-    constexpr int kGroups = 64 / kEssLanes;
-    __shared__ EssGroup groups[kGroups];
-    EssGroup &G = groups[threadIdx.x / kEssLanes];
-    const int lane = threadIdx.x % kEssLanes;
-    const int h = blockIdx.x * kGroups + threadIdx.x / kEssLanes;
-    const bool act = h < job->H;   // (a group beyond the hypotheses goes through every barrier and touches nothing)
-
     if (act && lane == 0) {
-        int32_t smp[kEssSample];
-        G.ok = ess_sample(*job, h, obs, smp, G.d1, G.d2) ? 1 : 0;
-        for (int j = 0; j < kEssSample; j++) G.sample[j] = smp[j];
         ess_basis(G.d1, G.d2, G.B);
         G.m = 0;
     }
@@ -111,6 +106,7 @@ __global__ __launch_bounds__(64) void k_ess_hypotheses(const EssJob *__restrict_
         int at = 0;
         for (int i = 0; i < lane; i++) at += G.has[i];
         for (int k = 0; k < 9; k++) G.E[9 * at + k] = E[k];
+        if (z) z[(size_t)kEssRoots * h + at] = rho * G.crit[lane];
     }
     __syncthreads();
     if (act && lane < kEssRoots) {
@@ -120,8 +116,55 @@ __global__ __launch_bounds__(64) void k_ess_hypotheses(const EssJob *__restrict_
         for (int k = 0; k < 9; k++) M[k] = G.E[9 * (lane < n ? lane : 0) + k];
         ess_write_model(models[(size_t)kEssRoots * h + lane], lane < n, M);
         valid[(size_t)kEssRoots * h + lane] = lane < n ? 1 : 0;
+        if (z && lane >= n) z[(size_t)kEssRoots * h + lane] = 0.0;
     }
+}
+
+__global__ __launch_bounds__(64) void k_ess_hypotheses(const EssJob *__restrict__ job, const EssObs *__restrict__ obs,
+                                                       EssModel *__restrict__ models, int32_t *__restrict__ valid,
+                                                       int32_t *__restrict__ samples)
+{
+    constexpr int kGroups = 64 / kEssLanes;
+    __shared__ EssGroup groups[kGroups];
+    EssGroup &G = groups[threadIdx.x / kEssLanes];
+    const int lane = threadIdx.x % kEssLanes;
+    const int h = blockIdx.x * kGroups + threadIdx.x / kEssLanes;
+    const bool act = h < job->H;
+
+    if (act && lane == 0) {
+        int32_t smp[kEssSample];
+        G.ok = ess_sample(*job, h, obs, smp, G.d1, G.d2) ? 1 : 0;
+        for (int j = 0; j < kEssSample; j++) G.sample[j] = smp[j];
+    }
+    ess_group_models(G, lane, h, act, models, valid, nullptr);
     if (act && lane < kEssSample) samples[(size_t)kEssSample * h + lane] = G.sample[lane];
+}
+
+// mcorb_dev_ess_solve_selftest: problem h of a table in place of a hypothesis's sample -- its camera in jobs[h], its five matches
+// as doubles, the bearings as mcorb_ess_solve forms them -- in k_ess_hypotheses' launch shape, so neighbouring problems share a
+// workgroup and its EssGroup array as neighbouring hypotheses do
+__global__ __launch_bounds__(64) void k_ess_solve_selftest(const EssJob *__restrict__ jobs, const double *__restrict__ uv1,
+                                                           const double *__restrict__ uv2, int n, EssModel *__restrict__ models,
+                                                           int32_t *__restrict__ valid, double *__restrict__ z)
+{
+    constexpr int kGroups = 64 / kEssLanes;
+    __shared__ EssGroup groups[kGroups];
+    EssGroup &G = groups[threadIdx.x / kEssLanes];
+    const int lane = threadIdx.x % kEssLanes;
+    const int h = blockIdx.x * kGroups + threadIdx.x / kEssLanes;
+    const bool act = h < n;
+
+    if (act && lane == 0) {
+        const double *a = uv1 + 2 * (size_t)kEssSample * h, *b = uv2 + 2 * (size_t)kEssSample * h;
+        for (int j = 0; j < kEssSample; j++) {
+            EssPt p;
+            ess_point(jobs[h], a[2 * j], a[2 * j + 1], b[2 * j], b[2 * j + 1], p);
+            ess_bearing(p.x1, p.y1, G.d1[j]);
+            ess_bearing(p.x2, p.y2, G.d2[j]);
+        }
+        G.ok = 1;
+    }
+    ess_group_models(G, lane, h, act, models, valid, z);
 }
 
 __device__ __forceinline__ void ess_point_of(const EssJob &job, const EssObs &o, EssPt &p)
@@ -354,6 +397,13 @@ void launch_ess_hypotheses(hipStream_t st, const EssArgs &a, int H)
 {
     constexpr int kGroups = 64 / kEssLanes;
     hipLaunchKernelGGL(k_ess_hypotheses, dim3((H + kGroups - 1) / kGroups), dim3(64), 0, st, a.job, a.obs, a.models, a.valid, a.samples);
+}
+
+void launch_ess_solve_selftest(hipStream_t st, const EssJob *jobs, const double *uv1, const double *uv2, int n, EssModel *models, int32_t *valid,
+                                double *z)
+{
+    constexpr int kGroups = 64 / kEssLanes;
+    hipLaunchKernelGGL(k_ess_solve_selftest, dim3((n + kGroups - 1) / kGroups), dim3(64), 0, st, jobs, uv1, uv2, n, models, valid, z);
 }
 
 void launch_ess_score(hipStream_t st, const EssArgs &a, int S, int H)

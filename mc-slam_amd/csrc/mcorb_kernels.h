@@ -374,6 +374,23 @@ void launch_align_score(hipStream_t st, const AlignArgs &a, int n, int H);
 void launch_align_pick(hipStream_t st, const AlignArgs &a, int n);
 void launch_align_fit(hipStream_t st, const AlignArgs &a);
 
+// The minimal solvers on n caller-given problems, one launch each (mcorb_dev_*_solve_selftest); every pointer is device memory.
+// Each kernel runs the text its estimator's hypotheses kernel runs behind the sample, in that kernel's launch shape: a lane per
+// problem (sac, rel), a quad per problem (sac rig: cams[n][ncams], obs and pts four per problem, the fourth the disambiguating
+// one), sixteen lanes per problem and four problems per workgroup (ess: jobs[n] carry the cameras), a workgroup of kAlignTile
+// per problem (align: problem b is pairs first[b] .. first[b] + cnt[b]).  R and t of sac and sac rig hold four slots a
+// problem and are zeroed by the caller; every other output is written whole
+void launch_sac_solve_selftest(hipStream_t st, const mcorb_track_cam *cams, const float *uv, const double *pts, int n, double *R, double *t,
+                               int32_t *count);
+void launch_sac_solve_rig_selftest(hipStream_t st, const mcorb_track_cam *cams, int ncams, const PoseObs *obs, const double *pts, int n, double *R,
+                                   double *t, int32_t *count, int32_t *mask, int32_t *best, SacModel *win);
+void launch_rel_solve_selftest(hipStream_t st, const mcorb_track_cam *cams, int ncams, const int32_t *cam1, const double *uv1, const int32_t *cam2,
+                               const double *uv2, int n, double *R, double *t, int32_t *count);
+void launch_ess_solve_selftest(hipStream_t st, const EssJob *jobs, const double *uv1, const double *uv2, int n, EssModel *models, int32_t *valid,
+                               double *z);
+void launch_align_solve_selftest(hipStream_t st, const double *p1, const double *p2, const uint8_t *member, const int32_t *first,
+                                 const int32_t *cnt, int n, double *R, double *t, double *gap, int32_t *valid);
+
 // map initialization (mcorb_init_gpu.hip, mcorb_init.h).  k_init_triangulate: k_map_triangulate's blocks and two instances over
 // the matches whose flag is set, one MapOut to a.out[match]; k_init_select: one workgroup -- the sizes and medians of parllaxVec
 // and depthVec into *sel, every match's id offset (the accepted matches before it) into offset, keys: 2 * n words of scratch;

@@ -496,6 +496,33 @@ int to_device(DevBuf<T> &d, const T *src, size_t n)
     return MCORB_OK;
 }
 
+// from_device: d[0 .. n) into dst, behind everything queued on the null stream
+template <class T>
+int from_device(T *dst, const DevBuf<T> &d, size_t n)
+{
+    HIPCHK(hipMemcpy(dst, d, n * sizeof(T), hipMemcpyDeviceToHost));
+    return MCORB_OK;
+}
+
+// zeroed(d, n): a fresh d of n zero elements
+template <class T>
+int zeroed(DevBuf<T> &d, size_t n)
+{
+    TRY(d.alloc(n));
+    HIPCHK(hipMemset(d, 0, n * sizeof(T)));
+    return MCORB_OK;
+}
+
+// the device of a self-test entry, made current
+inline int selftest_device(int device)
+{
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) { set_error("no usable HIP device"); return MCORB_E_NODEVICE; }
+    HIPCHK(hipSetDevice(device));
+    (void)hipGetLastError();   // (a stale error of this thread is not this call's)
+    return MCORB_OK;
+}
+
 // the cases of a self-test on the device: the n checked cases h (check_cases: voff[n] views in all) and the level table
 struct CasesDev {
     DevBuf<double> X, P, K, c;

@@ -251,6 +251,33 @@ int mcorb_rel_solve(int ncams, const mcorb_track_cam *cams, const int32_t *cam1,
     return ok ? 1 : 0;
 }
 
+int mcorb_dev_rel_solve_selftest(int device, int n, int ncams, const mcorb_track_cam *cams, const int32_t *cam1, const double *uv1,
+                                 const int32_t *cam2, const double *uv2, int32_t *count, double *R, double *t)
+{
+    if (n < 0 || ncams < 1 || ncams > MCORB_MAX_CAMS || (n && (!cams || !cam1 || !uv1 || !cam2 || !uv2 || !count || !R || !t)))
+        return fail(MCORB_E_ARG, "bad argument");
+    const size_t N = (size_t)n, M = N * kRelSample;
+    for (size_t i = 0; i < N; i++) TRY(check_cams(kRelSample, cam1 + kRelSample * i, cam2 + kRelSample * i, ncams));
+    if (n == 0) return MCORB_OK;
+    TRY(selftest_device(device));
+    DevBuf<mcorb_track_cam> d_cams;
+    DevBuf<int32_t> d_cam1, d_cam2, d_count;
+    DevBuf<double> d_uv1, d_uv2, d_R, d_t;
+    TRY(to_device(d_cams, cams, N * (size_t)ncams));
+    TRY(to_device(d_cam1, cam1, M));
+    TRY(to_device(d_cam2, cam2, M));
+    TRY(to_device(d_uv1, uv1, 2 * M));
+    TRY(to_device(d_uv2, uv2, 2 * M));
+    TRY(d_count.alloc(N));
+    TRY(d_R.alloc(N * 9));
+    TRY(d_t.alloc(N * 3));
+    launch_rel_solve_selftest(nullptr, d_cams, ncams, d_cam1, d_uv1, d_cam2, d_uv2, n, d_R, d_t, d_count);
+    HIPCHK(hipGetLastError());
+    TRY(from_device(count, d_count, N));
+    TRY(from_device(R, d_R, N * 9));
+    return from_device(t, d_t, N * 3);
+}
+
 int mcorb_rel_eval(int ncams, const mcorb_track_cam *cams, int n, const int32_t *cam1, const double *uv1, const int32_t *cam2,
                    const double *uv2, const double *R, const double *t, double *score)
 {

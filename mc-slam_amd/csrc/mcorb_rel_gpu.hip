@@ -34,6 +34,33 @@ __global__ __launch_bounds__(64) void k_rel_hypotheses(const RelJob *__restrict_
     rel_hypothesis(*job, h, obs, models[h]);
 }
 
+// mcorb_dev_rel_solve_selftest: rel_solve17 of the header, as k_rel_hypotheses' rel_hypothesis calls it, on problem h of a table,
+// one lane each: its rig at cams + ncams h, its 17 matches with keypoints as doubles (rel_rays_d, as mcorb_rel_solve forms the
+// rays).  Without a model the slot is zero
+__global__ __launch_bounds__(64) void k_rel_solve_selftest(const mcorb_track_cam *__restrict__ cams, int ncams, const int32_t *__restrict__ cam1,
+                                                           const double *__restrict__ uv1, const int32_t *__restrict__ cam2,
+                                                           const double *__restrict__ uv2, int n, double *__restrict__ R,
+                                                           double *__restrict__ tr, int32_t *__restrict__ count)
+{
+    const int h = blockIdx.x * 64 + threadIdx.x;
+    if (h >= n) return;
+    const size_t at = (size_t)kRelSample * h;
+    RelRays rays[kRelSample];
+    for (int j = 0; j < kRelSample; j++)
+        rel_rays_d(cams + (size_t)ncams * h, cam1[at + j], uv1 + 2 * (at + j), cam2[at + j], uv2 + 2 * (at + j), rays[j]);
+    PoseState P;
+    const bool ok = rel_solve17(rays, P);
+    for (int j = 0; j < 9; j++) R[9 * (size_t)h + j] = ok ? P.R[j] : 0.0;
+    for (int j = 0; j < 3; j++) tr[3 * (size_t)h + j] = ok ? P.t[j] : 0.0;
+    count[h] = ok ? 1 : 0;
+}
+
+void launch_rel_solve_selftest(hipStream_t st, const mcorb_track_cam *cams, int ncams, const int32_t *cam1, const double *uv1, const int32_t *cam2,
+                                const double *uv2, int n, double *R, double *t, int32_t *count)
+{
+    hipLaunchKernelGGL(k_rel_solve_selftest, dim3((n + 63) / 64), dim3(64), 0, st, cams, ncams, cam1, uv1, cam2, uv2, n, R, t, count);
+}
+
 __global__ __launch_bounds__(kRelTile) void k_rel_score(const RelJob *__restrict__ job, const RelObs *__restrict__ obs,
                                                         const RelModel *__restrict__ models, int32_t *__restrict__ count)
 {

@@ -251,6 +251,108 @@ int mcorb_sac_solve_rig(int ncams, const mcorb_track_cam *cams, const int32_t *c
     return collect.n;
 }
 
+int mcorb_host_sac_rig_roots(int ncams, const mcorb_track_cam *cams, const int32_t *cam, const float *uv, const double *pts, double *R, double *t,
+                             int32_t *mask, int32_t *best, double *best_R, double *best_t)
+{
+    if (ncams < 1 || ncams > MCORB_MAX_CAMS || !cams || !cam || !uv || !pts || !R || !t || !mask || !best || !best_R || !best_t)
+        return fail(MCORB_E_ARG, "bad argument");
+    for (int k = 0; k < 4; k++)
+        if (cam[k] < 0 || cam[k] >= ncams) return fail(MCORB_E_ARG, "a camera index outside the rig");
+    const mcorb_track_cam &c0 = cams[cam[0]], &c1 = cams[cam[1]], &c2 = cams[cam[2]], &c3 = cams[cam[3]];
+    double f[4][3];
+    for (int k = 0; k < 4; k++) sac_bearing(cams[cam[k]], uv[2 * k], uv[2 * k + 1], f[k]);
+    SacRig G;
+    sac_rig_prepare(c0, c1, c2, f[0], f[1], f[2], pts, pts + 3, pts + 6, G);
+    Collect collect{R, t, 0};
+    PoseState Pb = PoseState{};
+    bool hb = false;
+    double sb = 0.0;
+    int kb = 0;
+    *mask = 0;
+    for (int k = 0; k < 4; k++) {
+        PoseState P;
+        const bool root = sac_rig_root(G, k, c0, c1, c2, f[0], f[1], f[2], pts, pts + 3, pts + 6, P);
+        const double score = sac_score(c3, P, pts + 9, f[3]);
+        const bool has = root && score == score;
+        if (root) {
+            collect(P);
+            *mask |= 1 << k;
+        }
+        if (sac_root_beats(has, score, k, hb, sb, kb)) hb = true, sb = score, kb = k, Pb = P;
+    }
+    *best = hb ? kb : -1;
+    for (int j = 0; j < 9; j++) best_R[j] = hb ? Pb.R[j] : 0.0;
+    for (int j = 0; j < 3; j++) best_t[j] = hb ? Pb.t[j] : 0.0;
+    return collect.n;
+}
+
+int mcorb_dev_sac_solve_selftest(int device, int n, const mcorb_track_cam *cam, const float *uv, const double *pts, int32_t *count, double *R,
+                                 double *t)
+{
+    if (n < 0 || (n && (!cam || !uv || !pts || !count || !R || !t))) return fail(MCORB_E_ARG, "bad argument");
+    if (n == 0) return MCORB_OK;
+    TRY(selftest_device(device));
+    const size_t N = (size_t)n;
+    DevBuf<mcorb_track_cam> d_cam;
+    DevBuf<float> d_uv;
+    DevBuf<double> d_pts, d_R, d_t;
+    DevBuf<int32_t> d_count;
+    TRY(to_device(d_cam, cam, N));
+    TRY(to_device(d_uv, uv, N * 6));
+    TRY(to_device(d_pts, pts, N * 9));
+    TRY(zeroed(d_R, N * 36));
+    TRY(zeroed(d_t, N * 12));
+    TRY(d_count.alloc(N));
+    launch_sac_solve_selftest(nullptr, d_cam, d_uv, d_pts, n, d_R, d_t, d_count);
+    HIPCHK(hipGetLastError());
+    TRY(from_device(count, d_count, N));
+    TRY(from_device(R, d_R, N * 36));
+    return from_device(t, d_t, N * 12);
+}
+
+int mcorb_dev_sac_solve_rig_selftest(int device, int n, int ncams, const mcorb_track_cam *cams, const int32_t *cam, const float *uv,
+                                     const double *pts, int32_t *count, double *R, double *t, int32_t *mask, int32_t *best, double *best_R,
+                                     double *best_t)
+{
+    if (n < 0 || ncams < 1 || ncams > MCORB_MAX_CAMS ||
+        (n && (!cams || !cam || !uv || !pts || !count || !R || !t || !mask || !best || !best_R || !best_t)))
+        return fail(MCORB_E_ARG, "bad argument");
+    const size_t N = (size_t)n;
+    for (size_t i = 0; i < 4 * N; i++)
+        if (cam[i] < 0 || cam[i] >= ncams) return fail(MCORB_E_ARG, "a camera index outside the rig");
+    if (n == 0) return MCORB_OK;
+    TRY(selftest_device(device));
+    std::vector<PoseObs> obs(4 * N);
+    for (size_t i = 0; i < 4 * N; i++) obs[i] = PoseObs{uv[2 * i], uv[2 * i + 1], cam[i], 0};
+    DevBuf<mcorb_track_cam> d_cams;
+    DevBuf<PoseObs> d_obs;
+    DevBuf<double> d_pts, d_R, d_t;
+    DevBuf<int32_t> d_count, d_mask, d_best;
+    DevBuf<SacModel> d_win;
+    TRY(to_device(d_cams, cams, N * (size_t)ncams));
+    TRY(to_device(d_obs, obs.data(), 4 * N));
+    TRY(to_device(d_pts, pts, N * 12));
+    TRY(zeroed(d_R, N * 36));
+    TRY(zeroed(d_t, N * 12));
+    TRY(d_count.alloc(N));
+    TRY(d_mask.alloc(N));
+    TRY(d_best.alloc(N));
+    TRY(d_win.alloc(N));
+    launch_sac_solve_rig_selftest(nullptr, d_cams, ncams, d_obs, d_pts, n, d_R, d_t, d_count, d_mask, d_best, d_win);
+    HIPCHK(hipGetLastError());
+    std::vector<SacModel> win(N);
+    TRY(from_device(win.data(), d_win, N));
+    for (size_t i = 0; i < N; i++) {
+        memcpy(best_R + 9 * i, win[i].R, sizeof(win[i].R));
+        memcpy(best_t + 3 * i, win[i].t, sizeof(win[i].t));
+    }
+    TRY(from_device(count, d_count, N));
+    TRY(from_device(mask, d_mask, N));
+    TRY(from_device(best, d_best, N));
+    TRY(from_device(R, d_R, N * 36));
+    return from_device(t, d_t, N * 12);
+}
+
 int mcorb_sac_eval(int ncams, const mcorb_track_cam *cams, int n, const int32_t *cam, const float *uv, const double *pts, const double *R,
                    const double *t, double *score)
 {

@@ -14,7 +14,9 @@ fewer outcomes; the named lines stay.
     python scripts/header_coverage.py --inputs existing     the inputs of the family's tests/test_gpu_*.py, rebuilt from the same
                                                             *_cases.py calls (rows that need the library: a host-only store)
     python scripts/header_coverage.py --inputs hostile      the tables of tests/hostile_cases.py
-    python scripts/header_coverage.py                       both, and what the tables reach that the existing inputs do not
+    python scripts/header_coverage.py --inputs hooks        the rows of tests/solver_hook_cases.py that no scene holds
+    python scripts/header_coverage.py                       all three, what the tables reach that the existing inputs do not, and
+                                                            what the hooks' rows reach that neither does
 
 writes profiles/header_coverage.txt (-o: elsewhere).  tests/test_hostile_cpu.py uses coverage() and the lists of docs/design/09n."""
 import argparse
@@ -111,6 +113,34 @@ def inputs_hostile():
     for name, cams, obs, match, kw in HC.sac_rows():
         out["sac"].append((name, blob_sac(cams, obs, match, H=HC.H, **kw)))
         out["sac_rig"].append((name, blob_sac(cams, obs, match, H=HC.H, rig=True, **kw)))
+    return out
+
+
+def inputs_hooks():
+    """-> {program: [(name, problem)]}: the rows of tests/solver_hook_cases.py that no scene holds -- the hostile rows that are not
+    a sample cut out of a table of hostile_cases.py, which inputs_hostile() runs whole -- each as a scene of its sample's size and
+    a few hypotheses, whose samples are then permutations of the problem (the keypoints as floats, as the programs read them; the
+    central solver's fourth observation is its first again).  align: the fit over the members, mode 0, and the hypotheses"""
+    import solver_hook_cases as H
+    out = {k: [] for k in PROGRAMS}
+
+    def new(rows):
+        return [r for r in rows if r[1] and ", h " not in r[0] and not r[0].endswith(", all pairs")]
+    for name, _, five in new(H.ess_table()):
+        out["ess"].append((name, blob_ess(five, max_iterations=4)))
+    for name, _, cams, seventeen in new(H.rel_table()):
+        out["rel"].append((name, blob_rel(cams, seventeen, H=2)))
+    for name, _, p1, p2, member in new(H.align_table()):
+        keep = slice(None) if member is None else np.asarray(member, bool)
+        for mode in (0, 1):
+            blob = blob_align(np.asarray(p1)[keep], np.asarray(p2)[keep], mode=mode, max_iterations=4)
+            if blob is not None:
+                out["align"].append(("%s, mode %d" % (name, mode), blob))
+    for name, _, cams, c, uv, X in new(H.sac_table()):
+        obs = [(c, p[0], p[1], 0, x) for p, x in zip(uv, X)]
+        out["sac"].append((name, blob_sac(cams, obs + obs[:1], H=4)))
+    for name, _, cams, ci, uv, X in new(H.rig_table()):
+        out["sac_rig"].append((name, blob_sac(cams, [(c, p[0], p[1], 0, x) for c, p, x in zip(ci, uv, X)], H=4, rig=True)))
     return out
 
 
@@ -331,10 +361,10 @@ def read(dirs):
 
 
 def coverage(which):
-    """which: "existing" or "hostile" -> read()'s dict after a fresh build run on that set"""
+    """which: "existing", "hostile" or "hooks" -> read()'s dict after a fresh build run on that set"""
     with tempfile.TemporaryDirectory() as tmp:
         dirs = build(tmp)
-        run(dirs, inputs_existing() if which == "existing" else inputs_hostile())
+        run(dirs, {"existing": inputs_existing, "hostile": inputs_hostile, "hooks": inputs_hooks}[which]())
         return read(dirs)
 
 
@@ -356,7 +386,7 @@ def report(results):
             out.append("%s, inputs %s: %d of %d outcomes taken, %d never:" % (h, which, len(res[h]) - len(miss), len(res[h]), len(miss)))
             out += ["    " + name_of(k) for k in miss]
             out.append("")
-        if len(results) == 2:
+        if "existing" in results and "hostile" in results:
             e, t = results["existing"][h], results["hostile"][h]
             reached = sorted(k for k in never(e) if t.get(k, 0) > 0)
             still = sorted(k for k in never(e) if t.get(k, 0) == 0)
@@ -365,15 +395,23 @@ def report(results):
             out.append("%s: taken by neither (%d):" % (h, len(still)))
             out += ["    " + name_of(k) for k in still]
             out.append("")
+            if "hooks" in results:
+                k3 = results["hooks"][h]
+                more = [k for k in still if k3.get(k, 0) > 0]
+                out.append("%s: taken by neither, taken by the solver hooks' rows (%d):" % (h, len(more)))
+                out += ["    " + name_of(k) for k in more]
+                out.append("%s: taken by none of the three (%d):" % (h, len(still) - len(more)))
+                out += ["    " + name_of(k) for k in still if k not in more]
+                out.append("")
     return "\n".join(out)
 
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
-    ap.add_argument("--inputs", choices=("existing", "hostile", "both"), default="both")
+    ap.add_argument("--inputs", choices=("existing", "hostile", "hooks", "all"), default="all")
     ap.add_argument("-o", "--output", default=os.path.join(ROOT, "profiles", "header_coverage.txt"))
     args = ap.parse_args()
-    results = {w: coverage(w) for w in (("existing", "hostile") if args.inputs == "both" else (args.inputs,))}
+    results = {w: coverage(w) for w in (("existing", "hostile", "hooks") if args.inputs == "all" else (args.inputs,))}
     text = report(results)
     with open(args.output, "w") as f:
         f.write(text + "\n")
