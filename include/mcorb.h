@@ -1288,6 +1288,83 @@ int mcorb_ba_eval(int ncams, const mcorb_track_cam *cams, int n, const int32_t *
                   const double *sigma, const double *R, const double *t, double *r, double *J, double *JX, double *w);
 
 /* ------------------------------------------------------------------------- */
+/* Re-triangulation after the back end moved keyframes: the loop at the end of */
+/* Backend::UpdateVariables_SmartFactors (MCSlam/src/Backend.cpp:3577-3663) --  */
+/* every landmark seen in a moved keyframe is triangulated again from all of   */
+/* its observations (triangulateSafe / triangulatePoint3), then updated        */
+/* (GlobalMap::updateLandmark) or deleted.              */
+/* ------------------------------------------------------------------------- */
+#define MCORB_RETRI_MAX_KF 1024      /* keyframes of a call: a landmark's smart factor spans more than a BA window */
+#define MCORB_RETRI_REPORT 0         /* mode: the store stays as it is */
+#define MCORB_RETRI_APPLY 1          /* mode: valid points are written through updateLandmark's gate, failed landmarks deleted */
+#define MCORB_RETRI_NOT_SELECTED 0   /* no observation in a moved keyframe */
+#define MCORB_RETRI_FEW_VIEWS 1      /* selected, fewer than two observations (:3605): left alone */
+#define MCORB_RETRI_VALID_UPDATED 2  /* valid, and diff_norm < max_diff */
+#define MCORB_RETRI_VALID_REJECTED 3 /* valid, and updateLandmark's gate refused the point */
+#define MCORB_RETRI_DEGENERATE 4     /* rank < 3, or a component of the point is not finite */
+#define MCORB_RETRI_BEHIND 5
+#define MCORB_RETRI_FAR 6
+#define MCORB_RETRI_OUTLIER 7
+#define MCORB_RETRI_VERDICTS 8
+/* rank_tol: gtsam's TriangulationParameters::rankTolerance (1.0 by default; on pixel-scale rows, which are not normalised);
+ * landmark_distance_threshold, dynamic_outlier_threshold: a value <= 0 (or NaN) disables the check, the reference's setting;
+ * max_diff: GlobalMap::updateLandmark's gate (5.0 in the reference); mode: MCORB_RETRI_REPORT or MCORB_RETRI_APPLY */
+typedef struct mcorb_retri_params {
+    double rank_tol, landmark_distance_threshold, dynamic_outlier_threshold, max_diff;
+    int32_t mode, reserved;
+} mcorb_retri_params;
+/* counts: the landmarks per verdict; n_pairs: the (kf, feat) pairs of the landmarks with a failed verdict (DEGENERATE, BEHIND,
+ * FAR, OUTLIER) -- written and deleted in MCORB_RETRI_APPLY mode, counted in both; launched: 1 when the kernels ran */
+typedef struct mcorb_retri_result {
+    int32_t counts[MCORB_RETRI_VERDICTS];
+    int32_t n_pairs, launched;
+} mcorb_retri_result;
+/* The arrays are mcorb_lmap_bundle_adjust's: nkf keyframes (1 .. MCORB_RETRI_MAX_KF) with the poses w_T_b = (kf_R[9 k ..] row-major,
+ * kf_t[3 k ..]) after the optimisation and moved[k] != 0 where the caller found the pose moved (Backend.cpp:3550-3554 stays the
+ * caller's), the rig of mcorb_lmap_refine_pose, nlm landmarks (0 .. MCORB_BA_MAX_LANDMARKS) by store id, duplicate-free, and nobs
+ * observations (0 .. MCORB_BA_MAX_OBS): the keypoint uv[2 i], uv[2 i + 1] in camera obs_cam[i] of keyframe obs_kf[i], of landmark
+ * obs_lm[i], an index into lids.  All arithmetic is fp64, one IEEE operation per operator in the order written
+ * (csrc/mcorb_retri.h):
+ * - a landmark is selected iff one of its observations lies in a keyframe with moved != 0; the observations are sorted stably by
+ *   (landmark, keyframe, camera), "in order" means that order; a selected landmark with fewer than two is MCORB_RETRI_FEW_VIEWS.
+ * - a view, once per (keyframe, camera): R_cw = Rc^T R^T with an entry (a0 b0 + a1 b1) + a2 b2, t_cw = Rc^T (R^T (0 - t) - tc)
+ *   as mcorb_lmap_refine_pose forms a camera-frame point, the centre (R tc)_r + t_r, and P = K [R_cw | t_cw] with K = (fx s u0;
+ *   0 fy v0; 0 0 1), an entry (k0 m0 + k1 m1) + k2 m2.
+ * - per observation the rows a = u P[2] - P[0] and b = v P[2] - P[1]; G = sum (a a^T + b b^T), 10 sums of terms a_i a_j + b_i b_j:
+ *   lane l of 16 adds the landmark's observations l, l + 16, .. ascending into +0.0, the 16 sums fold with strides 8, 4, 2, 1
+ *   (s[l] = s[l] + s[l + stride]).
+ * - six cyclic Jacobi sweeps over the pairs (0,1) (0,2) (0,3) (1,2) (1,3) (2,3) of the 4 x 4 G with mcorb_lmap_align_pose's
+ *   rotation; v = the eigenvector of the smallest diagonal entry (the first of equals), X = v[0..2] * (1.0 / v[3]); lambda_3 =
+ *   the smallest of the other three.  MCORB_RETRI_DEGENERATE iff not sqrt(max(lambda_3, 0)) > rank_tol, or a component of X is
+ *   not finite.
+ * - over the observations in order: far iff landmark_distance_threshold > 0 and |X - centre| > it, else behind iff z <= 0 with
+ *   (x, y, z) = P (X, 1), each ((p0 X0 + p1 X1) + p2 X2) + p3; the first observation that fails names MCORB_RETRI_FAR or _BEHIND.
+ *   Otherwise MCORB_RETRI_OUTLIER iff dynamic_outlier_threshold > 0 and not max |(x / z - u, y / z - v)| <= it (a NaN norm
+ *   counts as +inf).
+ * - a valid point goes through mcorb_lmap_update_points' rule: diff_norm = |pt - X| (a NaN is the default quiet NaN), VALID_UPDATED
+ *   iff diff_norm < max_diff.  Normal, ray count and observations are untouched.
+ * Per landmark: pts_out[3 j ..] (X; zeros for NOT_SELECTED and FEW_VIEWS; a NaN component is the default quiet NaN), diff_norm[j]
+ * (zero unless valid), n_views[j] (its observations in the call) and verdict[j]; any of the four may be NULL.  MCORB_RETRI_APPLY
+ * writes the VALID_UPDATED points into the store and deletes the landmarks with a failed verdict as mcorb_lmap_delete does, in
+ * lids order: their (kf_id, feat) pairs go to kfs / feats (cap entries) and res->n_pairs counts them; more than cap gives
+ * MCORB_E_CAP with the count in res->n_pairs and the store unchanged.  (A cap below the pairs of all named landmarks makes the
+ * call run its kernels twice, the first time in report mode to count.)  In that mode every landmark must also have a normal, as
+ * mcorb_lmap_delete asks.  A device store runs k_retri_views and k_retri_solve in one submission with one wait; a host-only store
+ * runs the same header landmark by landmark: the results are equal bit for bit.  A call with no observation in a moved keyframe
+ * launches nothing: every landmark is NOT_SELECTED.  Before anything runs, with the store unchanged: MCORB_E_ARG for a count
+ * outside its range, a NULL array, kf / cam / lm out of range, an id outside the store or twice in lids, an unknown mode, a
+ * rank_tol or max_diff that is NaN; MCORB_E_STATE for a landmark without a point and while a tracking call is pending. */
+int mcorb_lmap_retriangulate(mcorb_lmap *m, int nkf, const double *kf_R, const double *kf_t, const uint8_t *moved, int ncams,
+                             const mcorb_track_cam *cams, int nlm, const int32_t *lids, int nobs, const int32_t *obs_kf,
+                             const int32_t *obs_cam, const int32_t *obs_lm, const float *uv, const mcorb_retri_params *params,
+                             double *pts_out, double *diff_norm, int32_t *n_views, int32_t *verdict, mcorb_retri_result *res,
+                             int32_t *kfs, int32_t *feats, int cap);
+/* a device store's last chain, microseconds between HIP events: [0] k_retri_views, [1] k_retri_solve.  A call that launches
+ * nothing leaves them */
+#define MCORB_RETRI_SPANS 2
+int mcorb_lmap_last_retri_timing(mcorb_lmap *m, float us[MCORB_RETRI_SPANS]);
+
+/* ------------------------------------------------------------------------- */
 /* The absolute rig pose by RANSAC in front of the refinement: the consensus   */
 /* step every matcher of the reference ends in -- OpenGV's sac::Ransac<        */
 /* AbsolutePoseSacProblem>(GP3P) as FrontEnd::absolutePoseFromGP3P (MCSlam/src/ */

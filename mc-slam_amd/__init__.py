@@ -1630,6 +1630,58 @@ class LocalMap:
         _lib.check(self.L.mcorb_lmap_last_ba_timing(self.h, us, C.byref(idle)))
         return tuple(us), idle.value
 
+    # re-triangulation after the back end moved keyframes (mcorb_lmap_retriangulate)
+    def retriangulate(self, cams, kf_R, kf_t, moved, lids, obs_kf, obs_cam, obs_lm, uv, rank_tol=1.0, landmark_distance_threshold=-1.0,
+                      dynamic_outlier_threshold=-1.0, max_diff=5.0, apply=False, cap=None):
+        """the end of Backend::UpdateVariables_SmartFactors: every landmark of lids (store ids, duplicate-free) with an
+        observation in a keyframe with moved[k] is triangulated again from all of its observations -- the arrays are
+        bundle_adjust's, the poses those after the optimisation -- by the DLT on K [R | t] rows through a Gram matrix and Jacobi
+        sweeps, then checked as triangulateSafe checks it (rank_tol; the two thresholds are off when <= 0) and put through
+        updateLandmark's gate max_diff -> RetriResult.  apply=False leaves the store as it is; apply=True writes the
+        VALID_UPDATED points and deletes the landmarks with a failed verdict, whose (kf_id, feat) pairs come back as delete()'s
+        do (cap: room for them; None: asked for by a first call, as delete() does).  A device store runs two kernels in one
+        submission; a host-only store the same arithmetic serially, with the same bits"""
+        kf_R = np.ascontiguousarray(kf_R, np.float64)
+        nkf = kf_R.size // 9
+        kf_R = kf_R.reshape(nkf, 9)
+        kf_t = np.ascontiguousarray(kf_t, np.float64).reshape(nkf, 3)
+        moved = np.ascontiguousarray(np.asarray(moved).astype(bool), np.uint8).reshape(nkf)
+        lids = np.ascontiguousarray(lids, np.int32).reshape(-1)
+        nlm = len(lids)
+        obs_kf = np.ascontiguousarray(obs_kf, np.int32).reshape(-1)
+        n = len(obs_kf)
+        obs_cam = np.ascontiguousarray(obs_cam, np.int32).reshape(n)
+        obs_lm = np.ascontiguousarray(obs_lm, np.int32).reshape(n)
+        uv = np.ascontiguousarray(uv, np.float32).reshape(n, 2)
+        ncams, ca = _pose_cams(cams)
+        par = _lib.RetriParams(float(rank_tol), float(landmark_distance_threshold), float(dynamic_outlier_threshold), float(max_diff),
+                               RETRI_APPLY if apply else RETRI_REPORT, 0)
+        pts, diff = np.zeros((max(nlm, 1), 3)), np.zeros(max(nlm, 1))
+        nv, verdict = np.zeros(max(nlm, 1), np.int32), np.zeros(max(nlm, 1), np.int32)
+        res = _lib.RetriResultC()
+
+        def call(kfs, feats, room):
+            return self.L.mcorb_lmap_retriangulate(self.h, nkf, kf_R.ctypes.data, kf_t.ctypes.data, moved.ctypes.data, ncams, ca, nlm,
+                                                   lids.ctypes.data, n, obs_kf.ctypes.data, obs_cam.ctypes.data, obs_lm.ctypes.data,
+                                                   uv.ctypes.data, C.byref(par), pts.ctypes.data, diff.ctypes.data, nv.ctypes.data,
+                                                   verdict.ctypes.data, C.byref(res), kfs, feats, room)
+        if cap is None:
+            code = call(None, None, 0)
+            if code != _lib.E_CAP or not apply:
+                _lib.check(code)
+                return RetriResult(res, pts[:nlm], diff[:nlm], nv[:nlm], verdict[:nlm], [])
+            cap = res.n_pairs
+        kfs, feats = np.zeros(max(cap, 1), np.int32), np.zeros(max(cap, 1), np.int32)
+        _lib.check(call(kfs.ctypes.data, feats.ctypes.data, cap))
+        k = res.n_pairs if apply else 0
+        return RetriResult(res, pts[:nlm], diff[:nlm], nv[:nlm], verdict[:nlm], list(zip(kfs[:k].tolist(), feats[:k].tolist())))
+
+    def last_retri_timing(self):
+        """microseconds of k_retri_views and of k_retri_solve in the last retriangulate() of a device store that launched them"""
+        us = (C.c_float * _lib.RETRI_SPANS)()
+        _lib.check(self.L.mcorb_lmap_last_retri_timing(self.h, us))
+        return tuple(us)
+
     # the absolute rig pose by RANSAC in front of the refinement (mcorb_lmap_ransac_pose)
     def ransac_pose(self, cams, cam, uv, octave, threshold, lids=None, pts=None, match=None, max_iterations=100, seed=0, refine=None,
                     solver="central"):
@@ -1882,6 +1934,23 @@ class BAResult:
 
 BA_NO_OBS, BA_NO_STEP, BA_CONVERGED, BA_MAX_ITER = 0, 1, 2, 3
 BA_MAX_KF = 16
+
+
+class RetriResult:
+    """what LocalMap.retriangulate returns, per landmark of lids: pts (nlm x 3), diff_norm, n_views and verdict (RETRI_*); counts,
+    the landmarks per verdict; n_pairs, the (kf_id, feat) pairs of the landmarks with a failed verdict, and pairs, those pairs
+    when the call deleted them (apply=True); launched, whether the kernels ran"""
+
+    def __init__(self, res, pts, diff_norm, n_views, verdict, pairs):
+        self.pts, self.diff_norm, self.n_views, self.verdict = pts, diff_norm, n_views, verdict
+        self.counts, self.n_pairs, self.launched = list(res.counts), res.n_pairs, bool(res.launched)
+        self.pairs = pairs
+
+
+RETRI_REPORT, RETRI_APPLY = 0, 1
+(RETRI_NOT_SELECTED, RETRI_FEW_VIEWS, RETRI_VALID_UPDATED, RETRI_VALID_REJECTED, RETRI_DEGENERATE, RETRI_BEHIND, RETRI_FAR,
+ RETRI_OUTLIER) = range(8)
+RETRI_MAX_KF = 1024
 
 
 class SacResult:

@@ -132,6 +132,18 @@ class BAResultC(C.Structure):
 BA_SPANS = 7
 
 
+class RetriParams(C.Structure):
+    _fields_ = [("rank_tol", C.c_double), ("landmark_distance_threshold", C.c_double), ("dynamic_outlier_threshold", C.c_double),
+                ("max_diff", C.c_double), ("mode", C.c_int32), ("reserved", C.c_int32)]
+
+
+RETRI_VERDICTS, RETRI_SPANS = 8, 2
+
+
+class RetriResultC(C.Structure):
+    _fields_ = [("counts", C.c_int32 * RETRI_VERDICTS), ("n_pairs", C.c_int32), ("launched", C.c_int32)]
+
+
 class SacParams(C.Structure):
     _fields_ = [("threshold", C.c_double), ("seed", C.c_uint64), ("max_iterations", C.c_int32), ("solver", C.c_int32)]
 
@@ -387,6 +399,9 @@ SIGNATURES = {
                                       _vp, _vp, _vp, C.POINTER(BAResultC), _vp]),
     "mcorb_lmap_last_ba_timing": (_i, [_vp, C.POINTER(_f), C.POINTER(C.c_int32)]),
     "mcorb_ba_eval": (_i, [_i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mcorb_lmap_retriangulate": (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, C.POINTER(RetriParams), _vp, _vp, _vp,
+                                      _vp, C.POINTER(RetriResultC), _vp, _vp, _i]),
+    "mcorb_lmap_last_retri_timing": (_i, [_vp, C.POINTER(_f)]),
     "mcorb_lmap_ransac_pose": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, C.POINTER(SacParams), C.POINTER(PoseParams),
                                     C.POINTER(SacResultC), _vp]),
     "mcorb_lmap_last_ransac_timing": (_i, [_vp, C.POINTER(_f), C.POINTER(_i)]),

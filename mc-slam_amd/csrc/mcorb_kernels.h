@@ -7,6 +7,7 @@
 #include "../../include/mcorb.h"
 #include "mcorb_align.h"
 #include "mcorb_ba.h"
+#include "mcorb_retri.h"
 #include "mcorb_common.h"
 #include "mcorb_init.h"
 #include "mcorb_mapping_new.h"
@@ -250,6 +251,12 @@ void launch_ba_solve(hipStream_t st, const BaArgs &a);
 void launch_ba_update(hipStream_t st, const BaArgs &a);
 void launch_ba_accept(hipStream_t st, const BaArgs &a, bool first);
 void launch_ba_final(hipStream_t st, const BaArgs &a);
+
+// the re-triangulation of landmarks after the back end moved keyframes (mcorb_retri_gpu.hip): k_retri_views (one lane per
+// (keyframe, camera) of the keyframes that have an observation: 15 doubles), then k_retri_solve (16 lanes per landmark: the
+// selection, G and its fold, the Jacobi, the checks, the gated store into the HBM point, the record into host-mapped memory)
+void launch_retri_views(hipStream_t st, const RetriArgs &a);
+void launch_retri_solve(hipStream_t st, const RetriArgs &a);
 
 // the RANSAC in front of it (mcorb_sac_gpu.hip), three launches.  job, obs, lids | pts, cons / cam_first / cam_cons (the
 // consensus observations in input order, and camera by camera) and is_first (per observation: the first of its match) are device

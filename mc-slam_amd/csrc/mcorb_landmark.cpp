@@ -63,6 +63,29 @@ void keep_last(mcorb_lmap *m, const int32_t *lids, int n, std::vector<int> &keep
 
 }  // namespace
 
+int mcorb::lmap_delete_checked(mcorb_lmap *m, const int32_t *lids, int n, int32_t *kfs, int32_t *feats)
+{
+    if (n == 0) return MCORB_OK;
+    if (m->device >= 0) {
+        TRY(use_device(m->device));
+        hipStream_t st = m->st;
+        TRY(m->life.d_rays.grow((size_t)n));
+        Submission sub(st);   // (its wait also covers the pageable list)
+        sub.copy(m->life.d_rays, lids, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice);
+        sub.run([&] { launch_lmap_put_rays(st, m->life.d_rays, nullptr, n, m->d_nrays); });
+        TRY(sub.wait());
+    }
+    size_t at = 0;
+    for (int i = 0; i < n; i++) {
+        std::vector<LmObs> &o = m->obs[lids[i]];
+        for (const LmObs &x : o) { kfs[at] = x.kf_id; feats[at] = x.feat; at++; }
+        std::vector<LmObs>().swap(o);
+        m->flags[lids[i]] = 0;
+        m->n_rays[lids[i]] = 0;
+    }
+    return MCORB_OK;
+}
+
 extern "C" {
 
 int mcorb_lmap_set_rays(mcorb_lmap *m, const int32_t *lids, int n, const int32_t *n_rays)
@@ -296,25 +319,7 @@ int mcorb_lmap_delete(mcorb_lmap *m, const int32_t *lids, int n, int32_t *kfs, i
     }
     if (n_out) *n_out = (int)total;
     if (total > (size_t)cap) return fail(MCORB_E_CAP, who, "output too small");
-    if (n == 0) return MCORB_OK;
-    if (m->device >= 0) {
-        TRY(use_device(m->device));
-        hipStream_t st = m->st;
-        TRY(m->life.d_rays.grow((size_t)n));
-        Submission sub(st);   // (its wait also covers the pageable list)
-        sub.copy(m->life.d_rays, lids, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice);
-        sub.run([&] { launch_lmap_put_rays(st, m->life.d_rays, nullptr, n, m->d_nrays); });
-        TRY(sub.wait());
-    }
-    size_t at = 0;
-    for (int i = 0; i < n; i++) {
-        std::vector<LmObs> &o = m->obs[lids[i]];
-        for (const LmObs &x : o) { kfs[at] = x.kf_id; feats[at] = x.feat; at++; }
-        std::vector<LmObs>().swap(o);
-        m->flags[lids[i]] = 0;
-        m->n_rays[lids[i]] = 0;
-    }
-    return MCORB_OK;
+    return lmap_delete_checked(m, lids, n, kfs, feats);
 }
 
 int mcorb_lmap_observers(mcorb_lmap *m, const int32_t *lids, int n, int32_t *kf_ids, int cap, int *n_out)

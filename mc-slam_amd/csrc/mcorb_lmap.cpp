@@ -135,6 +135,7 @@ int mcorb_lmap_create(mcorb_vocab *v, int device, int max_landmarks, int max_can
         TRY(m->track.chain.create());
         TRY(m->pose.refine.create());
         TRY(m->ba.chain.create());
+        TRY(m->retri.chain.create());
         TRY(m->sac.kernels.create());
         TRY(m->rel.kernels.create());
         TRY(m->rel.fit.create());

@@ -18,6 +18,7 @@
 #include "mcorb_mapping_new.h"
 #include "mcorb_pose.h"
 #include "mcorb_rel.h"
+#include "mcorb_retri.h"
 #include "mcorb_sac.h"
 #include "mcorb_track.h"
 
@@ -302,6 +303,22 @@ struct mcorb_lmap {
         }
     } ba;
 
+    // the re-triangulation after the back end moved keyframes (mcorb_retri.cpp), grow-only: the packed input (RetriLayout), the
+    // view table, and what the host reads: a record per landmark, host-mapped
+    struct Retri {
+        mcorb::Staged in;
+        mcorb::DevBuf<double> d_views;
+        mcorb::HostBuf<mcorb::RetriOut> h_out;
+        enum { kViews, kSolve };
+        mcorb::Spans<MCORB_RETRI_SPANS> chain;  // k_retri_views, k_retri_solve
+        int reserve(size_t bytes, size_t nviews, size_t nlm)
+        {
+            TRY(in.reserve(bytes));
+            TRY(d_views.grow((size_t)mcorb::kRetriView * nviews + 1));
+            return h_out.grow(nlm, mcorb::kHostMapped);
+        }
+    } retri;
+
     // the RANSAC in front of the refinement (mcorb_sac.cpp), grow-only: the packed input (ObsLayout with its RANSAC part), the
     // models and counts of the hypotheses, and what the host reads: the pick's record and the flags per observation, host-mapped.
     // `pose`: the buffers of the refinement behind it, whose input is part of `in`
@@ -486,6 +503,10 @@ int obs_check_locked(const mcorb_lmap *m, const ObsInput &in, const char *who);
 void obs_gather(const mcorb_lmap *m, const ObsInput &in, std::vector<PoseObs> &obs, std::vector<double> &X);
 void obs_stage(const ObsInput &in, const ObsLayout &L, const Staged &s);
 void obs_enqueue_refine(const mcorb_lmap *m, const ObsInput &in, const ObsLayout &L, const Staged &s, const PoseBufs &b);
+
+// the body of mcorb_lmap_delete behind its checks (mcorb_landmark.cpp), shared with mcorb_lmap_retriangulate: the caller holds the
+// store's lock, the ids are inside the store, duplicate-free and of slots that were set, and kfs / feats hold every pair
+int lmap_delete_checked(mcorb_lmap *m, const int32_t *lids, int n, int32_t *kfs, int32_t *feats);
 
 // shared by the test hooks of mcorb_mapping.cpp and mcorb_init.cpp.  to_device: src[0 .. n) into a fresh d
 template <class T>

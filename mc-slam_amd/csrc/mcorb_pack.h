@@ -10,6 +10,7 @@
 #include "mcorb_ess.h"
 #include "mcorb_mapping.h"
 #include "mcorb_rel.h"
+#include "mcorb_retri.h"
 #include "mcorb_sac.h"
 
 namespace mcorb {
@@ -69,6 +70,16 @@ struct BaLayout {
         : job(p.add<BaJob>(1)), poses(p.add<PoseState>(nkf)), pt(lids ? p.add<int32_t>(nlm) : p.add<double>(3 * nlm)),
           obs(p.add<BaObs>(nobs)), obs_first(p.add<int32_t>(nlm + 1)), view_first(p.add<int32_t>(nlm + 1)),
           slot(p.add<int8_t>(nlm * MCORB_BA_MAX_KF)) {}
+};
+
+// mcorb_lmap_retriangulate: the job, the poses and moved flags of the keyframes that have an observation, the landmarks' ids, the
+// sorted observations and the landmarks' spans
+struct RetriLayout {
+    Pack p;
+    size_t job, poses, moved, lids, obs, obs_first;
+    RetriLayout(size_t nslots, size_t nlm, size_t nobs)
+        : job(p.add<RetriJob>(1)), poses(p.add<PoseState>(nslots)), moved(p.add<uint8_t>(nslots)), lids(p.add<int32_t>(nlm)),
+          obs(p.add<RetriObs>(nobs)), obs_first(p.add<int32_t>(nlm + 1)) {}
 };
 
 // a tracking submission of nf frames: a TrItem and a view per frame, every frame's candidates, then -- host arrays only -- the
