@@ -157,6 +157,10 @@ MCORB_TRI_HD inline void init_store(const MapViews &v, const double R[9], const 
         lm_ray_add(o.X, w, acc);
     }
     lm_normal_add(acc, v.nv - v.nv1, o.normal, o.n_rays);
+    for (int k = 0; k < 3; k++) {   // (as dist2 and cos above: the host and the device give a NaN different signs)
+        o.X[k] = lm_default_nan(o.X[k]);
+        o.normal[k] = lm_default_nan(o.normal[k]);
+    }
 }
 
 // what a match returns once the verdict is known: rec is k_init_triangulate's record (ignored for a clear flag).  Returns true

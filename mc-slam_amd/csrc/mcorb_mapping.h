@@ -155,15 +155,21 @@ MCORB_TRI_HD inline void map_new_normal(const MapViews &v, const double X[3], do
     lm_normal_add(acc, v.nv - v.nv1, normal, n_rays);
 }
 
-// everything after the triangulation: the per-view gates, the parallax window, the normal of the new landmark
+// everything after the triangulation: the per-view gates, the parallax window, the normal of the new landmark.  Doubles that
+// leave the record go through lm_default_nan, as mcorb_mapping_new.h's and mcorb_init.h's do: the host and the device give a NaN
+// different signs
 MCORB_TRI_HD inline void map_after(const MapViews &v, const double X[3], const float *inv_sigma2, MapOut &o)
 {
-    for (int k = 0; k < 3; k++) o.X[k] = X[k];
+    for (int k = 0; k < 3; k++) o.X[k] = lm_default_nan(X[k]);
     const int gate = map_view_gates(v, X, inv_sigma2);
     if (gate != kMapLandmark) { o.verdict = gate; return; }
-    map_parallax(v, X, o.dist2, o.cos);
-    if (!(o.cos < 0.99998 && o.cos > 0.5)) { o.verdict = kMapParallax; return; }
+    double dist2, cosp;
+    map_parallax(v, X, dist2, cosp);
+    o.dist2 = lm_default_nan(dist2);
+    o.cos = lm_default_nan(cosp);
+    if (!(cosp < 0.99998 && cosp > 0.5)) { o.verdict = kMapParallax; return; }
     map_new_normal(v, X, o.normal, o.n_rays);
+    for (int k = 0; k < 3; k++) o.normal[k] = lm_default_nan(o.normal[k]);
     o.verdict = kMapLandmark;
 }
 

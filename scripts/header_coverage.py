@@ -18,7 +18,15 @@ fewer outcomes; the named lines stay.
     python scripts/header_coverage.py                       all three, what the tables reach that the existing inputs do not, and
                                                             what the hooks' rows reach that neither does
 
-writes profiles/header_coverage.txt (-o: elsewhere).  tests/test_hostile_cpu.py uses coverage() and the lists of docs/design/09n."""
+writes profiles/header_coverage.txt (-o: elsewhere).  tests/test_hostile_cpu.py uses coverage() and the lists of docs/design/09n.
+
+The same for the back end's and mapping's headers (BACKEND_HEADERS: mcorb_ba.h, mcorb_retri.h, mcorb_pose.h, mcorb_mapping.h,
+mcorb_mapping_new.h, mcorb_init.h, mcorb_triangulate.h) with the serial programs test_ba_sanitize.cpp, test_retri_sanitize.cpp,
+test_pose_sanitize.cpp, test_init_sanitize.cpp, test_mapping_new_sanitize.cpp and test_mapping_sanitize.cpp: `existing` is what
+tests/test_gpu_{ba,retri,pose,init,mapping_new,mapping}.py hand
+their calls, `hostile` the tables of tests/hostile_backend_cases.py; these programs take whole scenes, so the rows that only a
+hook can state (a caller-given point) are in neither.  tests/test_hostile_backend_cpu.py uses coverage(which, "backend") and the
+lists of docs/design/09q."""
 import argparse
 import math
 import os
@@ -39,6 +47,11 @@ HEADERS = ("mcorb_sac.h", "mcorb_rel.h", "mcorb_align.h", "mcorb_ess.h")
 PROGRAMS = dict(sac="test_sac_sanitize.cpp", sac_rig="test_sac_rig_sanitize.cpp", rel="test_rel_sanitize.cpp", align="test_align_sanitize.cpp",
                 ess="test_ess_sanitize.cpp")
 FLAGS = ["-O0", "--coverage", "-std=c++17", "-ffp-contract=off", "-I" + os.path.join(ROOT, "mc-slam_amd", "csrc")]
+BACKEND_HEADERS = ("mcorb_ba.h", "mcorb_retri.h", "mcorb_pose.h", "mcorb_mapping.h", "mcorb_mapping_new.h", "mcorb_init.h", "mcorb_triangulate.h")
+BACKEND_PROGRAMS = dict(ba="test_ba_sanitize.cpp", retri="test_retri_sanitize.cpp", pose="test_pose_sanitize.cpp", init="test_init_sanitize.cpp",
+                        new="test_mapping_new_sanitize.cpp", neigh="test_mapping_sanitize.cpp")
+# how a program is called and what says that it ran: (arguments after the problem file, text its output must hold)
+CALLS = dict(init=(["out.bin"], None), new=([], None))
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -297,12 +310,262 @@ def inputs_existing():
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
+# the back end's and mapping's programs
+# ---------------------------------------------------------------------------------------------------------------------------
+def _poses(poses):
+    return np.array([p[0] for p in poses], np.float64).tobytes() + np.array([p[1] for p in poses], np.float64).tobytes()
+
+
+def blob_ba(sc, max_iterations=25):
+    """test_ba_sanitize.cpp's problem of a scene of ba_cases.py, or None without a landmark or an observation"""
+    import ba_cases as BC
+    if not sc["obs"] or not sc["pts"]:
+        return None
+    kf, cam, olm, uv, octave = BC.arrays(sc["obs"])
+    blob = struct.pack("<6i", len(sc["poses"]), len(sc["cams"]), len(sc["pts"]), len(kf), len(sc["sigma"]), max_iterations)
+    blob += np.array(sc["sigma"], np.float64).tobytes() + _cams(sc["cams"]) + _poses(sc["poses"])
+    blob += np.array(sc["fixed"], np.uint8).tobytes() + np.array(sc["pts"], np.float64).tobytes()
+    return blob + kf.tobytes() + cam.tobytes() + olm.tobytes() + uv.tobytes() + octave.tobytes()
+
+
+def blob_retri(sc, rank_tol=1.0, landmark_distance_threshold=-1.0, dynamic_outlier_threshold=-1.0, max_diff=5.0):
+    """test_retri_sanitize.cpp's problem of a scene of retri_cases.py (the program runs in apply mode)"""
+    import retri_cases as RC
+    if not sc["obs"] or not sc["pts"]:
+        return None
+    kf, cam, olm, uv = RC.arrays(sc["obs"])
+    blob = struct.pack("<4i4d", len(sc["poses"]), len(sc["cams"]), len(sc["pts"]), len(kf), rank_tol, landmark_distance_threshold,
+                       dynamic_outlier_threshold, max_diff)
+    blob += _cams(sc["cams"]) + _poses(sc["poses"]) + np.array(sc["moved"], np.uint8).tobytes() + np.array(sc["pts"], np.float64).tobytes()
+    return blob + kf.tobytes() + cam.tobytes() + olm.tobytes() + uv.tobytes()
+
+
+def blob_pose(cams, init, obs, inv_sigma2=None, max_iterations=25):
+    """test_pose_sanitize.cpp's problem of the arguments of pose_cases.refine, or None without an observation"""
+    import pose_cases as PC
+    if not obs:
+        return None
+    inv_sigma2 = PC.INV_SIGMA2 if inv_sigma2 is None else inv_sigma2
+    cam, uv, octave, pts = PC.arrays(obs)
+    blob = struct.pack("<4i", len(cams), len(obs), len(inv_sigma2), max_iterations) + np.array(inv_sigma2, np.float64).tobytes() + _cams(cams)
+    return blob + _poses([init]) + cam.tobytes() + uv.tobytes() + octave.tobytes() + pts.tobytes()
+
+
+def _frame(fr):
+    out = np.ascontiguousarray(fr["match_index"], np.int32).tobytes() + np.ascontiguousarray(fr["proj"], np.float64).tobytes()
+    out += np.ascontiguousarray(fr["centre_w"], np.float64).tobytes() + np.array([len(k) for k in fr["kps"]], np.int32).tobytes()
+    for k in fr["kps"]:
+        out += np.stack([k["x"], k["y"]], axis=1).astype(np.float32).tobytes() + k["octave"].astype(np.int32).tobytes()
+    return out
+
+
+def blob_neigh(sc):
+    """test_mapping_sanitize.cpp's problem of a scene of mapping_cases.py (the points of the neighbours' landmarks from the
+    scene's store), or None without a neighbour"""
+    if not sc["neigh"]:
+        return None
+    f64 = lambda a: np.ascontiguousarray(a, np.float64).tobytes()
+    i32 = lambda a: np.ascontiguousarray(a, np.int32).tobytes()
+    frame = lambda fr: f64(fr["twc"]) + _frame(fr) + i32(fr["lids"])
+    blob = struct.pack("<5i", sc["ncams"], len(sc["neigh"]), len(sc["inv_sigma2"]), sc["next_lid"], len(sc["cur"]["match_index"]))
+    blob += f64(sc["K"]) + np.ascontiguousarray(sc["inv_sigma2"], np.float32).tobytes() + f64(sc["Rcw"]) + f64(sc["tcw"]) + frame(sc["cur"])
+    for fr, F, m in zip(sc["neigh"], sc["F21"], sc["matches"]):
+        m = np.asarray(m, np.int32).reshape(-1, 2)
+        blob += struct.pack("<2i", len(fr["match_index"]), len(m)) + frame(fr)
+        blob += b"".join(f64(sc["store"][int(l)]) for l in fr["lids"] if l != -1) + f64(F) + i32(m[:, 0]) + i32(m[:, 1])
+    return blob
+
+
+def blob_init(sc):
+    """test_init_sanitize.cpp's problem of a scene of init_cases.py, or None where the call ends before its loop (no match, no
+    baseline)"""
+    import init_ref as IR
+    n = len(sc["matches"])
+    if not n or not IR.baseline_ok(sc["t"], sc["min_baseline"]):
+        return None
+    blob = np.array([sc["ncams"], n, len(sc["inv_sigma2"]), sc["next_lid"], len(sc["prev"]["match_index"]), len(sc["cur"]["match_index"])],
+                    np.int32).tobytes()
+    for a in (sc["R"], sc["t"], sc["body"], sc["K"]):
+        blob += np.ascontiguousarray(a, np.float64).tobytes()
+    blob += np.ascontiguousarray(sc["inv_sigma2"], np.float32).tobytes() + sc["matches"].astype(np.int32).tobytes()
+    return blob + np.asarray(sc["flags"]).astype(np.uint8).tobytes() + _frame(sc["cur"]) + _frame(sc["prev"])
+
+
+def blob_new(sc):
+    """test_mapping_new_sanitize.cpp's scene file of a scene of mapping_new_cases.py: the program runs every match it is given,
+    so the matches the walk skips (a current feature that has a landmark, on entry or from an earlier match) are left out"""
+    lids, keep = sc["cur"]["lids"].copy(), []
+    for q, t in np.asarray(sc["matches"]).reshape(-1, 2).tolist():
+        if lids[t] == -1:
+            keep.append((q, t))
+            lids[t] = 0
+    if not keep:
+        return None
+    num = lambda a: " ".join(repr(float(x)) for x in np.asarray(a, np.float64).reshape(-1))
+    out = ["%d %d" % (sc["ncams"], len(sc["inv_sigma2"])), num(sc["K"]), num(sc["inv_sigma2"])]
+    for fr in (sc["cur"], sc["prev"]):
+        out.append(num(fr["twc"]))
+        for c in range(sc["ncams"]):
+            out.append(num(fr["proj"][c]) + " " + num(fr["centre_w"][c]))
+        for kps in fr["kps"]:
+            out.append("%d %s" % (len(kps), " ".join("%r %r %d" % (float(k["x"]), float(k["y"]), k["octave"]) for k in kps)))
+        out.append("%d" % len(fr["match_index"]))
+        out.append(" ".join(str(int(v)) for v in np.asarray(fr["match_index"]).reshape(-1)))
+    out.append("%d" % len(keep))
+    out.append(" ".join("%d %d" % m for m in keep))
+    return ("\n".join(out) + "\n").encode()
+
+
+def backend_hostile():
+    """-> {program: [(name, problem)]}: the rows of tests/hostile_backend_cases.py that these programs can read"""
+    import hostile_backend_cases as HB
+    out = {k: [] for k in BACKEND_PROGRAMS}
+    for name, sc, kw in HB.ba_rows():
+        out["ba"].append((name, blob_ba(sc, kw.get("max_iterations", HB.BA_ITERATIONS))))
+    for name, sc, kw in HB.retri_rows():
+        out["retri"].append((name, blob_retri(sc, **kw)))
+    for name, cams, init, obs, kw in HB.pose_rows():
+        out["pose"].append((name, blob_pose(cams, init, obs, **kw)))
+    for name, sc, kw in HB.init_rows():
+        out["init"].append((name, blob_init(sc)))
+    for name, sc, kw in HB.new_rows():
+        out["new"].append((name, blob_new(sc)))
+    for name, sc, kw in HB.neigh_rows():
+        out["neigh"].append((name, blob_neigh(sc)))
+    return {k: [(name, b) for name, b in v if b is not None] for k, v in out.items()}
+
+
+def backend_existing():
+    """-> {program: [(name, problem)]}: what tests/test_gpu_{ba,retri,init,mapping_new}.py hand their calls (a call that launches
+    nothing has no problem file; the hooks' hand-built cases give the point, which these programs compute)"""
+    import ba_cases as BC
+    import init_cases as Ic
+    import mapping_cases as Mc
+    import mapping_new_cases as Nc
+    import pose_cases as PC
+    import retri_cases as RC
+    import test_retri_cpu as TR
+    out = {k: [] for k in BACKEND_PROGRAMS}
+    # ---- test_gpu_ba.py
+    add = lambda name, sc, its=25: out["ba"].append((name, blob_ba(sc, its)))
+    for n in (1, 63, 64, 65, 255, 256, 257, 1025):
+        add("%d landmarks" % n, BC.scene(nlm=n, seed=30 + n % 7, max_views=3), 3 if n == 1025 else 25)
+    for nkf in (1, 2, 3, 16):
+        add("%d keyframes" % nkf, BC.scene(nkf=nkf, nlm=40, nfixed={1: 0, 2: 1, 3: 1, 16: 2}[nkf], seed=40 + nkf, spacing=0.3 if nkf < 16 else 0.1),
+            4 if nkf == 16 else 25)
+    for ncams in (1, 4, 16):
+        add("%d cameras" % ncams, BC.scene(ncams=ncams, nlm=60, seed=50 + ncams, skew=0.2))
+    for with_nan in (True, False):
+        for extra in ((), (1,)):
+            add("z and Huber rows", BC.hand_scene(PC.z_rows(with_nan) + BC.huber_rows(1.0), fixed=not extra, extra_kf=extra))
+    for sg in (1.0, 0.25):
+        add("Huber rows", BC.hand_scene(BC.huber_rows(sg), sigma=(sg,)))
+    rows, sigma, flags = BC.chi2_rows()
+    add("chi2 rows", BC.hand_scene(rows, sigma=sigma))
+    for name, sc, check in BC.degenerate():
+        add(name, sc)
+    for its in (1, 100):
+        add("max_iterations %d" % its, BC.scene(nlm=30, seed=21), its)
+    sc = BC.scene(nlm=50, seed=23)
+    add("before the points move", sc)
+    add("after", dict(sc, pts=(np.array(sc["pts"]) + np.random.default_rng(3).normal(scale=0.02, size=(len(sc["pts"]), 3))).tolist()))
+    add("the timing's scene", BC.scene(nlm=100, seed=24))
+    # ---- test_gpu_retri.py
+    add = lambda name, sc, **kw: out["retri"].append((name, blob_retri(sc, **kw)))
+    add("view counts", RC.synth(17, 16, RC.VIEW_COUNTS * 2, seed=60, skew=0.1))
+    for n in RC.LANDMARK_COUNTS:
+        add("%d landmarks" % n, RC.synth(6, 2, [2 + j % 4 for j in range(n)], seed=70 + n, moved=[k % 3 == 0 for k in range(6)]))
+    for nkf in (1, 17, 1024):
+        used = {1: [0], 17: [2, 9, 16], 1024: [3, 500, 1023]}[nkf]
+        add("%d keyframes" % nkf, RC.synth(nkf, 4, [min(v, 4 * len(used)) for v in (1, 2, 3, 4, 5, 6, 4, 3)], seed=80 + nkf % 7, used_kfs=used,
+                                           moved=[k == used[-1] for k in range(nkf)]))
+    for ncams in (1, 4, 16):
+        add("%d cameras" % ncams, RC.synth(5, ncams, [2 + j % 4 for j in range(20)], seed=90 + ncams, skew=0.3 if ncams == 4 else 0.0))
+    add("exact scene", RC.exact_scene(pt=(3.0, 4.0, 0.0)))
+    for max_diff in (5.0, math.nextafter(5.0, 10.0), 0.0, math.inf):
+        add("max_diff", RC.exact_scene(pt=(3.0, 4.0, 0.0)), max_diff=max_diff)
+    add("NaN point", RC.exact_scene(pt=(float("nan"), 0.0, 0.0)), max_diff=math.nextafter(5.0, 10.0))
+    for extra in (RC.AT_ORIGIN, RC.AT_ORIGIN_MINUS):
+        add("z of zero", RC.exact_scene(extra=[extra]))
+    sc = RC.synth(4, 2, [3, 6], seed=7)
+    want = RC.ref(sc, detail=True)
+    for j in (0, 1):
+        for tol in (want["s3"][j], math.nextafter(want["s3"][j], 0.0), math.nextafter(want["s3"][j], math.inf)):
+            add("rank_tol at sqrt(lambda_3)", sc, rank_tol=tol)
+        for thr in (want["emax"][j], math.nextafter(want["emax"][j], 0.0)):
+            add("outlier threshold at the largest error", sc, dynamic_outlier_threshold=thr)
+    add("the apply scene", TR.apply_scene())
+    add("apply writes the point", RC.synth(4, 2, [3, 4, 5, 2] * 20, seed=13))
+    add("the timing's scene", RC.synth(4, 2, [3] * 100, seed=14))
+    sc = BC.scene(nlm=60, seed=21)
+    add("a bundle adjustment's scene", RC.from_ba(sc))
+    add("a bundle adjustment's scene, thresholds on", RC.from_ba(sc), landmark_distance_threshold=50.0, dynamic_outlier_threshold=3.0)
+    # ---- test_gpu_pose.py
+    add = lambda name, *a, **kw: out["pose"].append((name, blob_pose(*a, **kw)))
+    cams, truth, init, obs, moved = PC.scene(4, nlm=280, seed=9)
+    for n in (1, 5, 6, 63, 64, 65, 255, 256, 257, 1025, 2, 3):
+        add("%d observations" % n, cams, init, obs[:n])
+    for its in (1, 100):
+        add("max_iterations %d" % its, cams, init, obs[:130], max_iterations=its)
+    bad = ([row[:] for row in init[0]], init[1][:])
+    bad[0][1][2] = float("nan")
+    add("a NaN initial pose", cams, bad, obs[:70])
+    for ncams in (1, 4, 16):
+        c, truth, i0, o, moved = PC.scene(ncams, nlm=max(20, 160 // ncams), seed=20 + ncams)
+        add("%d cameras" % ncams, c, i0, o)
+    for with_nan in (True, False):
+        add("z and Huber rows", PC.flat_rig(), PC.IDENT, PC.z_rows(with_nan) + PC.huber_rows())
+    add("Huber rows", PC.flat_rig(), PC.IDENT, PC.huber_rows())
+    o, inv, flags = PC.chi2_rows()
+    add("chi2 rows", PC.flat_rig(), PC.IDENT, o, inv_sigma2=inv)
+    add("an exact observation", PC.flat_rig(), PC.IDENT, [(0, 3.0, 4.0, 0, [3.0, 4.0, 1.0])])
+    add("all behind the rig", PC.flat_rig(), PC.IDENT, [(c, kx, ky, o_, [-v for v in X]) for c, kx, ky, o_, X in PC.z_rows(False)[:6]])
+    # ---- test_gpu_init.py
+    big = Ic.scene(4, n=1100, seed=3)
+    for third in (False, True):
+        for n in (1, 51, 63, 64, 65, 255, 256, 257, 1025):
+            out["init"].append(("%d matches" % n, blob_init(Ic.cut(big, n, third))))
+    for ncams in (1, 4, 8):
+        out["init"].append(("%d cameras" % ncams, blob_init(Ic.scene(ncams))))
+    # ---- test_gpu_mapping_new.py
+    for n in (1, 63, 64, 65, 256, 257):
+        out["new"].append(("%d matches" % n, blob_new(Nc.scene(4, n=n, seed=n + 1))))
+    for ncams in (1, 4, 8):
+        out["new"].append(("%d cameras" % ncams, blob_new(Nc.scene(ncams))))
+    # ---- test_gpu_mapping.py: its scenes (the gate cases are a hook's: the point is given)
+    add = lambda name, sc: out["neigh"].append((name, blob_neigh(sc)))
+    for n in (1, 63, 64, 65, 256, 257):
+        add("%d matches" % n, Mc.scene(4, sizes=(n,), seed=n + 1, zero_f=None))
+    for sizes in ((257,), (100, 157), (60, 0, 97, 50, 50)):
+        sc = Mc.scene(4, sizes=sizes, seed=11, zero_f=None)
+        if len(sizes) == 5:
+            sc["neigh"][3]["twc"] = sc["cur"]["twc"].copy()
+        add("segments %s" % (sizes,), sc)
+    add("the random scene", Mc.scene(4, sizes=(300, 300, 300), seed=3))
+    rng = np.random.default_rng(4)     # (test_view_counts_in_one_call's scene: 2 .. 16 views)
+    Ks, rigT = Mc.make_rig(8, rng)
+    cur = Mc.FrameBuilder(Mc.frame_geometry(Mc.T4(Mc.rot(0.02, -0.01, 0.03), np.zeros(3)), rigT), Ks)
+    nb = Mc.FrameBuilder(Mc.frame_geometry(Mc.T4(Mc.rot(-0.03, 0.05, 0.0), np.array([1.1, 0.05, -0.1])), rigT), Ks)
+    nb.add(np.array([0.0, 0.0, 5.0]), [0], rng, lid=900)
+    ms = []
+    for i in range(150):
+        a, b = [(1, 1), (2, 1), (2, 2), (4, 4), (8, 8)][i % 5]
+        X = np.array([rng.uniform(-2, 2), rng.uniform(-1.5, 1.5), rng.uniform(3, 15)])
+        ms.append((nb.add(X, sorted(rng.choice(8, a, replace=False).tolist()), rng), cur.add(X, sorted(rng.choice(8, b, replace=False).tolist()), rng)))
+    F = np.array([[Mc.fundamental(cur.g["full"][cc], nb.g["full"][cn], Ks[cc], Ks[cn]) for cn in range(8)] for cc in range(8)])
+    Tcw = np.linalg.inv(cur.g["pose"])
+    add("view counts", dict(ncams=8, K=np.array(Ks), inv_sigma2=Mc.INV_SIGMA2, cur=cur.done(), neigh=[nb.done()], F21=[F],
+                            store={900: np.array([0.0, 0.0, 5.0])}, matches=[np.array(ms, np.int32)], Rcw=Tcw[:3, :3], tcw=Tcw[:3, 3], next_lid=0))
+    return {k: [(name, b) for name, b in v if b is not None] for k, v in out.items()}
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
 # build, run, read
 # ---------------------------------------------------------------------------------------------------------------------------
-def build(tmp):
-    """the five programs, each in a directory of its own under tmp (its .gcno and .gcda live there) -> {program: directory}"""
+def build(tmp, programs=PROGRAMS):
+    """the programs, each in a directory of its own under tmp (its .gcno and .gcda live there) -> {program: directory}"""
     dirs = {}
-    for prog, src in PROGRAMS.items():
+    for prog, src in programs.items():
         d = os.path.join(tmp, prog)
         os.makedirs(d)
         subprocess.check_call(["g++"] + FLAGS + ["-c", os.path.join(ROOT, "tests", "cpp", src), "-o", "prog.o"], cwd=d)
@@ -317,22 +580,25 @@ def run(dirs, inputs):
         for name, blob in problems:
             with open(os.path.join(d, "in.bin"), "wb") as f:
                 f.write(blob)
-            got = subprocess.run([os.path.join(d, "prog"), "in.bin", "out.bin"], cwd=d, capture_output=True, text=True, timeout=600)
-            assert got.returncode == 0 and "bad=0" in got.stdout, (prog, name, got.returncode, got.stdout, got.stderr)
+            more, says = CALLS.get(prog, (["out.bin"], "bad=0"))
+            got = subprocess.run([os.path.join(d, "prog"), "in.bin"] + more, cwd=d, capture_output=True, text=True, timeout=600)
+            ran = says in got.stdout if says is not None else not got.stderr and \
+                (os.path.getsize(os.path.join(d, "out.bin")) > 0 if more else got.stdout.count("\n") > 0)
+            assert got.returncode == 0 and ran, (prog, name, got.returncode, got.stdout[-300:], got.stderr[-300:])
 
 
 LINE = re.compile(r"^\s*([^:]+):\s*(\d+):(.*)$")
 BRANCH = re.compile(r"^branch\s+(\d+)\s+(never executed|taken (\d+))(.*)$")
 
 
-def read(dirs):
+def read(dirs, headers=HEADERS):
     """gcov -b -c in every program's directory -> {header: {(line text, occurrence, outcome): times taken, summed over the
     programs and over the instantiations of a template}}; an outcome in code that never ran counts as not taken.  The edge
     gcov marks (throw) at a call of a function that is not noexcept is no outcome of the arithmetic and is left out"""
-    taken, throws = {h: {} for h in HEADERS}, {h: set() for h in HEADERS}
+    taken, throws = {h: {} for h in headers}, {h: set() for h in headers}
     for prog, d in dirs.items():
         subprocess.run(["gcov", "-b", "-c", "prog.gcno"], cwd=d, check=True, capture_output=True)
-        for h in HEADERS:
+        for h in headers:
             path = os.path.join(d, h + ".gcov")
             if not os.path.exists(path):
                 continue
@@ -357,12 +623,17 @@ def read(dirs):
                 taken[h][key] = taken[h].get(key, 0) + cnt
                 if (ln, k) in thrown:
                     throws[h].add(key)
-    return {h: {k: v for k, v in taken[h].items() if k not in throws[h]} for h in HEADERS}
+    return {h: {k: v for k, v in taken[h].items() if k not in throws[h]} for h in headers}
 
 
-def coverage(which):
-    """which: "existing", "hostile" or "hooks" -> read()'s dict after a fresh build run on that set"""
+def coverage(which, group="pose"):
+    """which: "existing", "hostile" or "hooks"; group: "pose" (HEADERS) or "backend" (BACKEND_HEADERS, no hooks) -> read()'s dict
+    after a fresh build run on that set"""
     with tempfile.TemporaryDirectory() as tmp:
+        if group == "backend":
+            dirs = build(tmp, BACKEND_PROGRAMS)
+            run(dirs, {"existing": backend_existing, "hostile": backend_hostile}[which]())
+            return read(dirs, BACKEND_HEADERS)
         dirs = build(tmp)
         run(dirs, {"existing": inputs_existing, "hostile": inputs_hostile, "hooks": inputs_hooks}[which]())
         return read(dirs)
@@ -376,11 +647,11 @@ def never(taken):
     return sorted(k for k, v in taken.items() if v == 0)
 
 
-def report(results):
+def report(results, headers=HEADERS, head=True):
     """results: {which: coverage(which)} -> the text of profiles/header_coverage.txt"""
     out = ["header_coverage.py: branch outcomes (gcov -b -c, g++ -O0 --coverage -ffp-contract=off) of the serial programs of tests/cpp.",
-           "An outcome is `source line  [gcov's index on the line]`.", ""]
-    for h in HEADERS:
+           "An outcome is `source line  [gcov's index on the line]`.", ""] if head else []
+    for h in headers:
         for which, res in results.items():
             miss = never(res[h])
             out.append("%s, inputs %s: %d of %d outcomes taken, %d never:" % (h, which, len(res[h]) - len(miss), len(res[h]), len(miss)))
@@ -412,7 +683,8 @@ def main():
     ap.add_argument("-o", "--output", default=os.path.join(ROOT, "profiles", "header_coverage.txt"))
     args = ap.parse_args()
     results = {w: coverage(w) for w in (("existing", "hostile", "hooks") if args.inputs == "all" else (args.inputs,))}
-    text = report(results)
+    backend = {w: coverage(w, "backend") for w in (("existing", "hostile") if args.inputs == "all" else (args.inputs,)) if w != "hooks"}
+    text = report(results) + "\n" + report(backend, BACKEND_HEADERS, head=False)
     with open(args.output, "w") as f:
         f.write(text + "\n")
     print(text)

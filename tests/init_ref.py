@@ -155,8 +155,11 @@ def run_cases(cases, flags, R, t, ncams, min_baseline):
     return finish(recs, flags, [c["views"] for c in cases], [c["nv1"] for c in cases], R, t, ncams, 0)
 
 
-def initialize(prev, lids_prev, cur, lids_cur, R, t, cam_centre_body, matches, inliers, K, inv_sigma2, next_lid, min_baseline):
-    """the whole call; prev / cur: mapping_cases frames (cur's centre_w is not read) -> finish's dict with lids_prev / lids_cur"""
+def initialize(prev, lids_prev, cur, lids_cur, R, t, cam_centre_body, matches, inliers, K, inv_sigma2, next_lid, min_baseline,
+               triangulate=MR.triangulate):
+    """the whole call; prev / cur: mapping_cases frames (cur's centre_w is not read) -> finish's dict with lids_prev / lids_cur.
+    triangulate(views) -> X: by default mapping_ref's SVD; with the library's DLT in its place (mapping_new_ref.initial_point)
+    everything behind the point compares bit for bit"""
     lp, lc = [int(l) for l in lids_prev], [int(l) for l in lids_cur]
     if not baseline_ok(t, min_baseline):
         return dict(status=BASELINE, lids_prev=lp, lids_cur=lc)
@@ -166,7 +169,7 @@ def initialize(prev, lids_prev, cur, lids_cur, R, t, cam_centre_body, matches, i
         v1, v2 = MR.views_of(prev, q, K), MR.views_of(cur_body, tr, K)
         views.append(v1 + v2)
         nv1s.append(len(v1))
-        recs.append(gates(v1 + v2, len(v1), MR.triangulate(v1 + v2), inv_sigma2) if f else None)
+        recs.append(gates(v1 + v2, len(v1), triangulate(v1 + v2), inv_sigma2) if f else None)
     out = finish(recs, [bool(f) for f in inliers], views, nv1s, R, t, len(K), next_lid)
     if out["status"] == DONE:
         for (q, tr), lid in zip(np.asarray(matches).reshape(-1, 2).tolist(), out["new_lid"]):

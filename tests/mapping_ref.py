@@ -152,7 +152,7 @@ def after(views, nv1, X, inv_sigma2):
     return r
 
 
-def match(neigh, q, cur, t, F_table, K, inv_sigma2):
+def match(neigh, q, cur, t, F_table, K, inv_sigma2, triangulate=triangulate):
     """one match from :5826 to :5937; F_table[c_cur][c_neigh]"""
     v1, v2 = views_of(neigh, q, K), views_of(cur, t, K)
     F = np.asarray(F_table).reshape(len(K), len(K), 3, 3)[v2[0]["cam"]][v1[0]["cam"]]
@@ -172,10 +172,13 @@ def depth_z(Rcw, tcw, pt):
     return s + float(tcw[2])
 
 
-def triangulate_neighbours(store, cur, lids_cur, neigh, lids_neigh, F21, matches, K, inv_sigma2, Rcw, tcw, next_lid):
-    """store: lid -> pt3D of the landmarks that exist.  -> dict of per-match lists (neighbours back to back) and the rest"""
+def triangulate_neighbours(store, cur, lids_cur, neigh, lids_neigh, F21, matches, K, inv_sigma2, Rcw, tcw, next_lid, triangulate=triangulate):
+    """store: lid -> pt3D of the landmarks that exist.  -> dict of per-match lists (neighbours back to back) and the rest.
+    triangulate(views) -> X: by default the SVD above; with the library's DLT in its place (mapping_new_ref.initial_point)
+    everything behind the point compares bit for bit"""
     lc = [int(l) for l in lids_cur]
-    out = dict(verdict=[], inliers=[], new_lid=[], pt3d=[], normal=[], near=[], skipped=[], depth_vec=[], lids_neigh=[], new={})
+    out = dict(verdict=[], inliers=[], new_lid=[], pt3d=[], normal=[], near=[], skipped=[], depth_vec=[], lids_neigh=[], new={}, dist2=[],
+               cos=[])
     twc = [float(v) for v in cur["twc"]]
     for s, kf in enumerate(neigh):
         ln = [int(l) for l in lids_neigh[s]]
@@ -199,11 +202,13 @@ def triangulate_neighbours(store, cur, lids_cur, neigh, lids_neigh, F21, matches
             elif ln[q] != -1 or lc[t] != -1:
                 v = 6
             else:
-                r = match(kf, q, cur, t, F21[s], K, inv_sigma2)
+                r = match(kf, q, cur, t, F21[s], K, inv_sigma2, triangulate)
                 v = r["verdict"]
             out["verdict"].append(v)
             out["inliers"].append(v in (0, 5))
             out["near"].append(bool(r and r["near"]))
+            out["dist2"].append(r["dist2"] if r else 0.0)      # (0.0 where the match did not come to the parallax window)
+            out["cos"].append(r["cos"] if r else 0.0)
             if v == 0:
                 ln[q] = lc[t] = next_lid
                 out["new"][next_lid] = (r["X"], r["normal"])

@@ -1,8 +1,9 @@
 """Every call of the local map that keeps scratch of its own, one after the other on ONE device store and on a host-only twin:
 track from host arrays, track_rig_frames (2 frames), refine_pose, ransac_pose with its refinement (both solvers),
 triangulate_new, triangulate_neighbours (2 neighbours), observe / update_points, search, relative_pose, align_pose (mode 1 from
-points, mode 0 from landmark ids), essential_pose and initialize -- three times over, small, about four
-times larger, small again, so that every grow-only buffer is grown by one call and then used again, by that call and, where the
+points, mode 0 from landmark ids), essential_pose and initialize, bundle_adjust (points and landmark ids), retriangulate (report,
+apply, a search over the survivors), and relative_pose_polished and essential_pose_polished right behind their unpolished calls
+(they share `in`, `h_out` and `h_flags` with them) -- three times over, small, about four times larger, small again, so that every grow-only buffer is grown by one call and then used again, by that call and, where the
 buffers are shared, by the others.  Every result equals the twin's bit for bit (floats as raw bytes); after each call its timing
 getter gives a finite, non-negative number for every span that ran, and the span of k_track_points reads exactly 0 for the frame
 from host arrays -- also right behind a rig slot's frames.  What this is aimed at: two calls on one buffer, or a group's reserve
@@ -14,7 +15,10 @@ import pytest
 
 import align_cases as AC
 import align_ref as AR
+import ba_cases as BC
+import ba_ref as B
 import ess_cases as EC
+import ess_polish_cases as EPC
 import init_cases as Ic
 import init_ref as IR
 import kfdb_cases as K
@@ -24,12 +28,16 @@ import mapping_cases as Mc
 import mapping_new_cases as Nc
 import pose_cases as PC
 import rel_cases as RC
+import rel_polish_cases as RPC
+import retri_cases as RTC
+import retri_ref as RT
 import sac_cases as SC
 import sac_rig_cases as SR
 import track_cases as T
 from test_gpu_init import same as same_init, same_store as same_init_store
 from test_gpu_track_batch import extracted, frame_landmarks, shifted
 from test_lmap_cpu import make, same_result, scene_landmarks
+from test_retri_cpu import record_observations
 
 pytestmark = pytest.mark.gpu
 
@@ -37,9 +45,9 @@ C = 2
 MAXL = 8192
 # where each call keeps its landmarks: (host-array tracking, the rig frames', refine_pose, ransac_pose central / rig, the neighbours' old
 # landmarks are the scene's own 3000 .., new ids of triangulate_neighbours / triangulate_new, observe, search, align_pose's frame-1
-# points, initialize's new ids: 160 per round)
+# points, initialize's new ids: 160 per round, bundle_adjust's points, retriangulate's landmarks: 150 per round)
 AT = dict(track=0, frames=600, pose=1300, sac=1800, sac_rig=2400, neigh_new=4200, new_new=5200, observe=6200, search=7400, align=2600,
-          init=7700)
+          init=7700, ba=6750, retri=6920)
 #        landmarks twins  per_cam  pose  sac  thin  hyp  neighbours      old  new  observe  search
 SIZES = [(40, 20, 8, 12, 20, 3, 16, (16, 12), 8, 24, 30, 60),
          (160, 80, 32, 48, 80, 12, 64, (64, 48), 32, 96, 120, 240),
@@ -191,6 +199,16 @@ def one_round(mc, lm_d, db_d, lm_h, db_h, rig, rnd, size):
     assert got[0].status == mc.REL_OK and got[0].n_inliers > 17
     us, nh = lm_d.last_relative_timing()
     assert nh == hyp and len(spans_ok(us)) == 3
+    # .. and its polish on the same matches: the same `in`, `h_out` and `h_flags`, the polish's own scratch behind them
+    plain = got
+    got = [RPC.run(mc, lm, cams, matches, max_iterations=hyp, seed=rnd) for lm in both]
+    same_fields(got[0][0], got[1][0], ("R", "t", "inliers", "sample"), what + "relative_pose_polished")
+    for f in ("status", "n_inliers", "n_matches", "best_hypothesis", "n_models"):
+        assert getattr(got[0][0], f) == getattr(got[1][0], f), (what, "relative_pose_polished", f)
+    RPC.same_polish(got[0][1], got[1][1], what + "relative_pose_polished")
+    assert got[0][0].status == mc.REL_OK and got[0][1].R.tobytes() == plain[0].R.tobytes() and got[0][1].rounds_run >= 1, "the polish began from the winner"
+    us, nh = lm_d.last_relative_timing4()
+    assert nh == hyp and len(spans_ok(us)) == 4 and us[3] > 0
 
     # align_pose: mode 1 from points, mode 0 from the store's landmarks
     truth, p1, p2, _ = AC.scene(n=nobs, seed=7 + rnd, moved=nobs // 10)
@@ -218,6 +236,13 @@ def one_round(mc, lm_d, db_d, lm_h, db_h, rig, rnd, size):
         assert x.tobytes() == y.tobytes(), what + "essential_pose, the slots"
     us, nh = lm_d.last_essential_timing()
     assert nh == hyp and len(spans_ok(us)) == 4
+    # .. and its polish on the same matches
+    got = [EPC.run(mc, lm, matches, max_iterations=hyp, seed=rnd) for lm in both]
+    EC.same_stores(got[0][0], got[1][0], what + "essential_pose_polished")
+    EPC.same_polish(got[0][1], got[1][1], what + "essential_pose_polished")
+    assert got[0][0].status == mc.ESS_OK and got[0][1].rounds_run >= 1
+    us, nh = lm_d.last_essential_timing5()
+    assert nh == hyp and len(spans_ok(us)) == 5 and us[4] > 0
 
     # initialize: init_cases.py's two-camera scene, its ids in a range of its own
     sc = Ic.scene(C, n=nsearch, seed=3 + rnd)
@@ -232,6 +257,51 @@ def one_round(mc, lm_d, db_d, lm_h, db_h, rig, rnd, size):
     same_init_store(lm_d, lm_h, new, what + "initialize")
     us = lm_d.last_initialize_timing()
     assert us[3] == int(sc["flags"].sum()) and spans_ok(us[:3])
+
+    # bundle_adjust, points and ids: as many landmarks as the tracking scene
+    sc = BC.scene(nkf=4, ncams=C, nlm=nl, nfixed=2, seed=30 + rnd, max_views=3)
+    for form in ("pts", "lids"):
+        got = [BC.run(mc, lm, sc, max_iterations=6, form=form, first_lid=AT["ba"]) for lm in both]
+        same_fields(got[0], got[1], ("R", "t", "pts", "inliers", "cost_initial", "cost_final"), what + "bundle_adjust, " + form)
+        for f in ("status", "iterations", "n_inliers", "n_obs"):
+            assert getattr(got[0], f) == getattr(got[1], f), (what, "bundle_adjust", form, f)
+        assert got[0].status in (B.CONVERGED, B.MAX_ITER) and got[0].cost_final < got[0].cost_initial and got[0].n_obs == len(sc["obs"])
+        us, idle = lm_d.last_ba_timing()
+        assert len(spans_ok(us)) == 7 and us[0] > 0
+
+    # retriangulate: report, apply with a cap that holds every pair, a search over the survivors.  The landmarks are a search
+    # scene's, with descriptors; every second one keeps that scene's point, far from where its views put it (VALID_REJECTED: it
+    # stays where the search sees it), every fifth has a NaN keypoint (DEGENERATE: apply deletes it)
+    view, land, probe, cur = scene_landmarks(C, nobs, seed=10 + rnd)
+    lids = AT["retri"] + 150 * rnd + np.arange(nobs, dtype=np.int32)
+    sc = RTC.synth(4, C, [2 + j % 4 for j in range(nobs)], seed=20 + rnd)
+    sc["pts"] = [land[1][j].tolist() if j % 2 else p for j, p in enumerate(sc["pts"])]
+    for j in range(2, nobs, 5):
+        i = next(i for i, o in enumerate(sc["obs"]) if o[2] == j)
+        sc["obs"][i] = sc["obs"][i][:3] + (float("nan"), 1.0)
+    fields = ("pts", "diff_norm", "n_views", "verdict")
+    for lm in both:
+        lm.set(lids, np.array(sc["pts"]), *land[2:])
+        record_observations(mc, lm, lids)
+    got = [RTC.run(mc, lm, sc, lids=lids) for lm in both]
+    same_fields(got[0], got[1], fields, what + "retriangulate, report")
+    assert got[0].counts == got[1].counts and got[0].n_pairs == got[1].n_pairs > 0 and got[0].launched
+    assert min(got[0].counts[v] for v in (RT.VALID_UPDATED, RT.VALID_REJECTED, RT.DEGENERATE)) > 0, got[0].counts
+    assert Lc.snapshot(lm_d, lids) == Lc.snapshot(lm_h, lids)
+    assert len(spans_ok(lm_d.last_retri_timing())) == 2
+    report = got[0]
+    got = [RTC.run(mc, lm, sc, lids=lids, apply=True, cap=2 * nobs) for lm in both]
+    same_fields(got[0], got[1], fields, what + "retriangulate, apply")
+    same_fields(got[0], report, fields, what + "retriangulate, apply against report")
+    assert got[0].counts == got[1].counts and got[0].pairs == got[1].pairs and len(got[0].pairs) == got[0].n_pairs == report.n_pairs
+    alive = lids[[v not in RT.FAILED for v in got[0].verdict.tolist()]]
+    assert 0 < len(alive) < nobs and Lc.snapshot(lm_d, alive) == Lc.snapshot(lm_h, alive)
+    spans_ok(lm_d.last_retri_timing())
+    got = [lm.search(Lm.to_view(mc, view), alive, [], db, 0, *cur, levelsup=K.LEVELSUP) for lm, db in ((lm_d, db_d), (lm_h, db_h))]
+    same_result(got[0], got[1], what + "search over the survivors")
+    assert len(got[0].new_lids) > 0 and set(got[0].new_lids.tolist()) <= set(alive.tolist())
+    us = lm_d.last_timing()
+    assert us[2] == len(alive) and spans_ok(us[:2])
 
 
 def test_every_call_three_times_on_one_store(mc):

@@ -273,11 +273,11 @@ def test_a_rejected_root_between_two_kept_ones(mc, lm, tmp_path):
 # ---------------------------------------------------------------------------------------------------------------------------
 # the branch outcomes of the shared headers
 # ---------------------------------------------------------------------------------------------------------------------------
-def doc_lists():
-    """docs/design/09n_hostile_inputs.md -> {(header, list name): [outcome name]}: an outcome is an indented line `source line  [k]`,
-    in the last list followed by `  -- ` and the reason"""
+def doc_lists(path=DOC):
+    """a design note in the format of docs/design/09n_hostile_inputs.md -> {(header, list name): [outcome name]}: an outcome is an
+    indented line `source line  [k]`, in the last list followed by `  -- ` and the reason"""
     out, cur = {}, None
-    with open(DOC) as f:
+    with open(path) as f:
         for row in f:
             m = re.match(r"^\*\*(mcorb_\w+\.h): (unreached by the existing inputs|reached by the tables|still unreached)\*\*", row)
             if m:
@@ -292,12 +292,10 @@ def doc_lists():
     return out
 
 
-def test_the_headers_branch_outcomes(tmp_path):
-    """needs g++ and gcov, as the sanitizer tests of the family need g++: fails without them"""
-    H = header_coverage()
-    lists = doc_lists()
-    hostile, existing = H.coverage("hostile"), H.coverage("existing")
-    for h in H.HEADERS:
+def hold_the_lists(H, lists, headers, hostile, existing):
+    """the three lists of every header against the two readings: every "reached" outcome is taken by the tables, nothing taken by
+    neither is missing from "still unreached", and the three lists are consistent"""
+    for h in headers:
         for k in ("unreached by the existing inputs", "reached by the tables", "still unreached"):
             assert (h, k) in lists, (h, k)
         by_name = {H.name_of(key): key for key in hostile[h]}
@@ -308,5 +306,11 @@ def test_the_headers_branch_outcomes(tmp_path):
         never = set(H.name_of(key) for key in hostile[h] if hostile[h][key] == 0 and existing[h].get(key, 0) == 0)
         assert never <= set(lists[h, "still unreached"]), (h, "reached by nothing and not listed", sorted(never - set(lists[h, "still unreached"])))
         assert set(lists[h, "reached by the tables"]) | set(lists[h, "still unreached"]) == set(lists[h, "unreached by the existing inputs"]), h
+
+
+def test_the_headers_branch_outcomes(tmp_path):
+    """needs g++ and gcov, as the sanitizer tests of the family need g++: fails without them"""
+    H = header_coverage()
+    hold_the_lists(H, doc_lists(), H.HEADERS, H.coverage("hostile"), H.coverage("existing"))
     committed = os.path.join(ROOT, "profiles", "header_coverage.txt")
     assert os.path.exists(committed) and "taken by neither" in open(committed).read()

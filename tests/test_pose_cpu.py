@@ -4,7 +4,11 @@
 On the commit before this call existed every test of this file fails (`python -m pytest tests/test_pose_cpu.py`): LocalMap has
 no refine_pose."""
 import ctypes as C
+import importlib.util
 import math
+import os
+import struct
+import subprocess
 
 import numpy as np
 import pytest
@@ -304,3 +308,31 @@ def test_track_refine_state_rules(mc, lm):
     lm.set_track_refine(None)
     lm.track(v, *empty)
     state_error()
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# the header under the sanitizers
+# ---------------------------------------------------------------------------------------------------------------------------
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def test_header_under_asan_ubsan(mc, lm, seeded, tmp_path):
+    """tests/cpp/test_pose_sanitize.cpp (its own main, -fsanitize=address,undefined) runs the two rounds of pose_round on the seeded
+    scene and on the hand-written z and Huber rows: no report, and its records -- the result and the flags -- equal the library's"""
+    spec = importlib.util.spec_from_file_location("header_coverage", os.path.join(ROOT, "scripts", "header_coverage.py"))
+    H = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(H)
+    exe = str(tmp_path / "test_pose_sanitize")
+    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                           "-I" + os.path.join(ROOT, "mc-slam_amd", "csrc"), os.path.join(ROOT, "tests", "cpp", "test_pose_sanitize.cpp"),
+                           "-o", exe])
+    cams, truth, init, obs, moved, ref = seeded
+    for what, (rig, start, rows) in (("the seeded scene", (cams, init, obs)), ("z and Huber rows", (PC.flat_rig(), PC.IDENT, PC.z_rows(True) + PC.huber_rows())),
+                                     ("without the NaN row", (PC.flat_rig(), PC.IDENT, PC.z_rows(False) + PC.huber_rows()))):
+        (tmp_path / "in.bin").write_bytes(H.blob_pose(rig, start, rows))
+        out = subprocess.run([exe, str(tmp_path / "in.bin"), str(tmp_path / "out.bin")], capture_output=True, text=True, timeout=300)
+        assert out.returncode == 0 and "bad=0" in out.stdout and not out.stderr, (what, out.stdout + out.stderr)
+        got = PC.refine(mc, lm, rig, start, rows)
+        want = got.R.tobytes() + got.t.tobytes() + struct.pack("<2d6i", got.cost_initial, got.cost_final, got.status, got.iterations[0],
+                                                                got.iterations[1], got.n_inliers, got.n_obs, 0)
+        assert (tmp_path / "out.bin").read_bytes() == want + got.inliers.astype(np.uint8).tobytes(), what
